@@ -16,6 +16,8 @@ parallel construct is rows of one frame (main.cpp:653-656); "weak" (--scaling we
 per-GPU work stays at 1920x1080.  `--scaling strong` at N = 1 renders the config-5 frame on one GPU (the base of the curve).
 Other workloads: --workload shaded (cgrt_render: primary + shadow + mirror rays, the reference's whole frame),
 --tris 87000 (the report's dragon size), --obj PATH (a user-supplied mesh, e.g. the real dragon.obj).
+--dump-outputs DIR writes what the last timed step computed (rank 0's hit records, or the shaded frame's RGB) as .npy files;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -31,8 +33,30 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as entry  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X: HBM3E 8.0 TB/s spec
 CONFIG5 = (3840, 2160)  # BASELINE.json configs[4]
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(out_dir, rows, index=None, whole=None):
+    """--dump-outputs: writes what the timed path returned in its last step as DIR/<name>.npy, float32 or float64.  `rows` maps
+    names to arrays with one row per output element (a pixel); when they do not fit in DUMP_LIMIT_BYTES, a fixed seeded sample
+    of rows is written, and `pixel_index` (float64) says which pixels they are -- as it does whenever `index` (the pixel of each
+    row) is given.  `whole` maps names to small arrays written as they are."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows, whole = dict(rows), dict(whole or {})
+    n = len(next(iter(rows.values())))
+    row_bytes = sum(a.nbytes for a in rows.values()) // max(1, n)
+    budget = DUMP_LIMIT_BYTES - sum(a.nbytes for a in whole.values()) - 256 * (len(rows) + len(whole) + 1)
+    if index is not None or n * row_bytes > budget:
+        keep = np.arange(n)
+        if n * (row_bytes + 8) > budget:
+            keep = np.sort(np.random.default_rng(0).choice(n, budget // (row_bytes + 8), replace=False))
+            rows = {k: a[keep] for k, a in rows.items()}
+        rows["pixel_index"] = (keep if index is None else np.asarray(index)[keep]).astype(np.float64)
+    for name, a in {**rows, **whole}.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_model() -> str:
@@ -169,7 +193,12 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--frames-in-flight", type=int, default=1,
                     help="independent frames kept in flight on separate HIP streams (1 = strictly back to back, the reported default)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32/float64, "
+                         "at most 64 MB in all: a fixed seeded sample of the pixels when the frame is larger)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
 
@@ -288,6 +317,16 @@ def main():
         host.copy_(bufs[0], non_blocking=True)
         torch.cuda.synchronize()
         gather_ms = (time.perf_counter() - g0) * 1e3
+        if args.dump_outputs and rank == 0:
+            # the CgrtHit frame of the last timed step (warm-up and timed steps share the frames in flight round robin), the
+            # pixels this rank traced; the ids as float64, which holds every uint32 / int32 exactly
+            last = bufs[(args.warmup + args.steps - 1) % nfl].cpu().numpy().view(pkg.HIT_DTYPE)
+            pix = np.flatnonzero(tiling.owned_mask(W, H, rank, world).ravel())
+            last = last[pix]
+            dump_outputs(args.dump_outputs, {"hits_t": last["t"].astype(np.float32), "hits_prim_id": last["prim_id"].astype(np.float64),
+                                             "hits_material_id": last["material_id"].astype(np.float64),
+                                             "hits_hit": last["hit"].astype(np.float32)},
+                         index=pix if world > 1 else None)
         per_rank = [my_rays]
         walls = torch.tensor([wall, gather_ms], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         if dist is not None:
@@ -383,10 +422,13 @@ def main():
             scene.render(cam, W, H, max_level=2)
         t_start = time.perf_counter()
         for _ in range(args.steps):
-            _, st = scene.render(cam, W, H, max_level=2)
+            rgb, st = scene.render(cam, W, H, max_level=2)
             if best is None or st["device_ms"] < best["device_ms"]:
                 best = st
         wall = time.perf_counter() - t_start
+        if args.dump_outputs:  # the last timed frame: its RGB and the rays it cast
+            dump_outputs(args.dump_outputs, {"rgb": rgb},
+                         whole={"rays": np.float64([st["primary_rays"], st["shadow_rays"], st["reflection_rays"]])})
         rays = best["primary_rays"] + best["shadow_rays"] + best["reflection_rays"]
         path = scene.last_render_path()
         # the same frame drawn the exact way (what a first frame, a resized frame or a frame after a camera jump costs): after the timed region
@@ -404,15 +446,16 @@ def main():
             "n_gpus": 1,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(best["device_ms"], 4),
+            "ms_per_step": round(wall / args.steps * 1e3, 4),
             "higher_is_better": True,
             "vs_baseline": None,
             "dtype": "f32",
             "data": data,
             "config": {"workload": f"{scene_name}, {W}x{H}, cgrt_render depth 2 ({walk} walk): {best['primary_rays']} primary, "
                                    f"{best['shadow_rays']} shadow, {best['reflection_rays']} mirror rays",
-                       "timing": "ms_per_step: HIP events around all kernels of the best frame (device side of cgrt_render); "
-                                 f"host-inclusive mean {wall / args.steps * 1e3:.3f} ms (RGB download included)",
+                       "timing": "ms_per_step: wall clock over the timed frames / steps (cgrt_render returns with the RGB downloaded); "
+                                 "value and best_frame_device_ms: HIP events around all kernels of the best frame (device side of cgrt_render)",
+                       "best_frame_device_ms": round(best["device_ms"], 4),
                        "frame_path": {0: "exactly sized (the host waits for the device's hit count inside the frame)",
                                       1: "predicted: every launch issued at once, sized from the previous frame of the same shape, counts checked behind the frame "
                                          "(cgrt_set_render_prediction; same pixels, tests/test_render_prediction_gpu.py)",

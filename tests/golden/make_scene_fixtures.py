@@ -1,10 +1,10 @@
-"""Generates tests/golden/scenes/*.npz from the reference's data/*.obj files (run in the dev container,
-where /root/reference exists; the GPU box only sees the committed .npz).
+"""Generates tests/golden/scenes/*.npz from the reference's data/*.obj files (run where a checkout of the reference
+exists; the tests only see the committed .npz).
 
 The .npz hold the flat arrays cgrt_scene_create takes (vertices as assimp would deliver them, triangles,
 mesh ids, materials, the preset's point lights) -- i.e. loaded scene DATA, produced by this repo's own
 loader (cg-raytracer_amd/scenes.py); no reference source is involved.
-    python tests/golden/make_scene_fixtures.py
+    python tests/golden/make_scene_fixtures.py <reference checkout>/data
 """
 import os
 import sys
@@ -13,9 +13,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as entry  # noqa: E402
 
-DATA = "/root/reference/data"
-
 if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        raise SystemExit(__doc__)
+    DATA = sys.argv[1]
     pkg = entry.load_package()
     out = os.path.join(ROOT, "tests", "golden", "scenes")
     os.makedirs(out, exist_ok=True)

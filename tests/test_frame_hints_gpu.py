@@ -123,7 +123,10 @@ def test_two_streams_taking_turns_and_threads_on_one_scene(pkg, hints):
     out: cgrt.h)."""
     import ctypes as C
 
-    hip = C.CDLL("libamdhip64.so")  # (the runtime libcgrt.so is linked against: plain streams and buffers, no torch in the tests)
+    # the HIP runtime libcgrt.so is linked against (plain streams and buffers, no torch in the tests), looked up through libcgrt.so's
+    # own dependencies: by name, a process that has loaded a second copy of the runtime as well (torch ships one) may hand out that
+    # copy, whose streams and buffers libcgrt.so cannot use
+    hip = C.CDLL(pkg.LIB_PATH)
 
     def ok(rc):
         assert rc == 0, rc

@@ -9,24 +9,88 @@ import pytest
 
 from conftest import GOLDEN, bits
 
-REF_DATA = "/root/reference/data"
+
+def write_obj_from_fixture(sd, path, group="g", one_group=False, normals=True, mtl=True, vt=True, relative=False):
+    """Writes the loaded scene `sd` back out as an OBJ (+ MTL) that loadMesh turns into the same arrays, in the token forms
+    exported files use: `group` ("o", "g" or None) starts one group per mesh, written in reverse (the loader pops groups
+    last-first), or -- `one_group` -- one group holding a usemtl run per mesh; every face corner its own `v` (the loader keeps one
+    vertex per corner) with a `vt` and a `vn` as asked (v/vt/vn, v//vn, v/vt or v faces, `relative` indices counted back from
+    the last one read), `s` lines between faces; no `normals`: the fixture's normals must be the flat ones the loader generates;
+    no `mtl`: no mtllib or usemtl at all (one mesh, default material).  Polygons are re-assembled from the fan triangulation, and
+    numbers are printed so that they parse back to the same float32 bits."""
+    num = lambda x: repr(float(x))
+    base = os.path.splitext(os.path.basename(path))[0]
+    assert mtl or sd.nmesh == 1
+    lines = []
+    if mtl:
+        with open(os.path.splitext(path)[0] + ".mtl", "w") as f:
+            for m, row in enumerate(sd.materials):
+                f.write(f"newmtl m{m}\nKd {' '.join(map(num, row[0:3]))}\nKs {' '.join(map(num, row[3:6]))}\n"
+                        f"Ns {num(row[6])}\nd {num(row[7])}\n")
+        lines.append(f"mtllib {base}.mtl")
+    if one_group and group:
+        lines.append(f"{group} all")
+    nv = 0
+    for m in (range(sd.nmesh) if one_group else reversed(range(sd.nmesh))):
+        if group and not one_group:
+            lines.append(f"{group} m{m}")
+        if mtl:
+            lines.append(f"usemtl m{m}")
+        lines.append("s off" if m % 2 else "s 1")
+        tris = sd.tri[sd.tri_mesh == m].astype(np.int64)
+        polys = []  # a polygon of k corners was triangulated as (b, b+j, b+j+1), j = 1 .. k-2
+        for a, b, c in tris:
+            if polys and a == polys[-1][0] and b == polys[-1][-1] and c == b + 1:
+                polys[-1].append(c)
+            else:
+                assert b == a + 1 and c == a + 2, "not a triangulation loadMesh produces"
+                polys.append([a, b, c])
+        rows = [r for p in polys for r in p]
+        lines += [f"v {' '.join(map(num, sd.pos_nrm[r, 0:3]))}" for r in rows]
+        if vt:
+            lines += [f"vt {i % 2} {i // 2 % 2}" for i in range(len(rows))]
+        if normals:
+            lines += [f"vn {' '.join(map(num, sd.pos_nrm[r, 3:6]))}" for r in rows]
+        k = nv
+        for p in polys:
+            first = k - nv - len(rows) if relative else k + 1  # every v, vt and vn list has one entry per corner
+            ids = [str(first + i) for i in range(len(p))]
+            lines.append("f " + " ".join(i + ("/" + i if vt else "/" if normals else "") + ("/" + i if normals else "") for i in ids))
+            k += len(p)
+        nv += len(rows)
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+# the token forms each preset's file is written in: the reference's triangle.obj has v/vt faces and no mtllib, the cube and the
+# monkey g groups, s lines and v/vt/vn triplets, the Cornell box one object with a usemtl run per mesh
+FORMS = {"triangle": dict(group=None, normals=False, mtl=False), "cube": dict(group="g"),
+         "cornell": dict(group="o", one_group=True, vt=False), "monkey": dict(group="g", relative=True)}
 
 
 @pytest.mark.parametrize("name,fn,norm", [("triangle", "triangle.obj", False), ("cube", "cube.obj", False),
                                          ("cornell", "CornellBox-Mirror-Rotated.obj", True), ("monkey", "monkey-rotated.obj", True)])
-def test_cpp_loader_matches_fixture(pkg, scene_data, name, fn, norm):
+def test_cpp_loader_matches_fixture(pkg, scene_data, tmp_path, name, fn, norm):
     """loadMesh of the C++ mirror == the committed scene fixture (made by the Python loader): two independent
-    implementations of the same assimp-like semantics agree bit for bit.  Needs the reference's data files."""
-    path = os.path.join(REF_DATA, fn)
-    if not os.path.exists(path):
-        pytest.skip("reference data files are only present in the dev container")
-    a, b = pkg.host_load_obj(path, norm), scene_data(name)
+    implementations of the same assimp-like semantics agree bit for bit.  The scene is written back out as an OBJ from the
+    fixture itself, in the token forms of the preset's file (the reference's data files are not part of this repository); a
+    normalised preset's fixture holds the normalised vertices, so the normalisation is checked by loading that file again with
+    it, C++ against Python."""
+    b = scene_data(name)
+    path = str(tmp_path / fn)
+    write_obj_from_fixture(b, path, **FORMS[name])
+    a = pkg.host_load_obj(path, False)
     assert np.array_equal(a.tri, b.tri) and np.array_equal(a.tri_mesh, b.tri_mesh)
     assert np.array_equal(bits(a.pos_nrm), bits(b.pos_nrm))
     mats_b = b.materials.copy()
     if name == "triangle":
         mats_b[0, 0:3] = a.materials[0, 0:3]  # scene.cpp:11 overrides kd in the preset, not in loadMesh
     assert np.array_equal(bits(a.materials), bits(mats_b))
+    if norm:
+        an, bn = pkg.host_load_obj(path, True), pkg.scenes.load_obj(path, normalize=True)
+        assert np.array_equal(an.tri, b.tri) and np.array_equal(an.tri_mesh, b.tri_mesh)
+        assert np.array_equal(bits(an.pos_nrm), bits(bn.pos_nrm)) and np.array_equal(bits(an.materials), bits(bn.materials))
+        assert not np.array_equal(bits(an.pos_nrm), bits(a.pos_nrm))  # the normalisation did run
 
 
 def test_bmp_writer(pkg, tmp_path):

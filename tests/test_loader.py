@@ -47,6 +47,33 @@ def test_cpp_loader_equals_python_loader(pkg):
     assert np.abs(np.linalg.norm(n.pos_nrm[:, 0:3], axis=1).max() - 1.0) < 1e-6  # centred, farthest vertex at distance 1 (mesh.cpp:143-166)
 
 
+def test_exported_token_forms(pkg):
+    """forms.obj: vt lines and v/vt pairs (normals generated), v/vt/vn triplets whose normal is the THIRD index (the given
+    normals differ from the flat ones, and reading the vt index as the normal would pick another normal or run past the list),
+    relative triplets, g groups (objects in reverse file order), s lines (ignored), two usemtl runs in one group, and a
+    material that stays current across groups.  The C++ and the Python loader must agree bit for bit."""
+    path = os.path.join(OBJ, "forms.obj")
+    sd = pkg.host_load_obj(path)
+    py = pkg.scenes.load_obj(path)
+    assert sd.tri.tobytes() == py.tri.tobytes() and sd.tri_mesh.tobytes() == py.tri_mesh.tobytes()
+    assert sd.pos_nrm.tobytes() == py.pos_nrm.tobytes() and sd.materials.tobytes() == py.materials.tobytes()
+    # groups reversed: `last` (mirror, kept from `side`), `side` (red run, mirror run), then the faces before any group (default)
+    assert sd.nmesh == 4 and sd.ntris == 4 and sd.tri_mesh.tolist() == [0, 1, 2, 3]
+    mirror = [0.1, 0.1, 0.1, 0.9, 0.9, 0.9, 200.0, 1.0]
+    red = [0.8, 0.1, 0.1, 0.2, 0.2, 0.2, 12.0, 1.0]
+    default = [0.6, 0.6, 0.6, 0.0, 0.0, 0.0, 0.0, 1.0]
+    assert np.array_equal(sd.materials, np.float32([mirror, red, mirror, default]))
+    P = np.float32([[0, 0, 0], [2, 0, 0], [0, 2, 0], [0, 0, 3]])
+    corners = {0: ([0, 1, 2], [1, 0, 0]),   # f -4/-3/-1 -3/-2/-1 -2/-1/-1: vertices 1 2 3, normal 2
+               1: ([0, 1, 3], [1, 0, 0]),   # f 1/1/2 2/2/2 4/3/2 (its flat normal would be (0, -1, 0))
+               2: ([1, 2, 3], [0, 0, -1]),  # f 2/1/1 3/2/1 4/3/1
+               3: ([0, 2, 1], [0, 0, -1])}  # f 1/1 3/3 2/2: no normals, flat normal of (0,2,0) x (2,0,0)
+    for m, (vi, nrm) in corners.items():
+        rows = sd.pos_nrm[sd.tri[sd.tri_mesh == m][0]]
+        assert np.array_equal(rows[:, 0:3], P[vi]), m
+        assert np.array_equal(rows[:, 3:6], np.float32([nrm] * 3)), m
+
+
 @pytest.mark.parametrize("name", ["bad_out_of_range", "bad_zero_index", "bad_negative", "bad_token", "bad_normal_index", "does_not_exist"])
 def test_invalid_files_throw_like_upstream(pkg, name, capfd):
     """Malformed faces are REJECTED with upstream's message and a bare exception (mesh.cpp:60-71).  PARITY UNPINNED: which malformed
