@@ -108,7 +108,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -172,6 +172,9 @@ def lib() -> C.CDLL:
     L.cgrt_render_rank.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, i32, i32, vp, C.POINTER(RenderStats)]
     L.cgrt_trace_primary_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(Camera), i32, i32, vp, vp, C.POINTER(MultiStats)]
     L.cgrt_render_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
+    L.cgrt_render_aa.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, i32, i32, vp, C.POINTER(RenderStats)]
+    L.cgrt_render_aa_mapped.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, C.POINTER(vp), C.POINTER(RenderStats)]
+    L.cgrt_render_multi_aa.argtypes = [C.POINTER(vp), i32, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
     L.cgrt_count_batch.argtypes = [vp, vp, u64, C.POINTER(Counters)]
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
@@ -495,6 +498,30 @@ class Scene:
         _check(lib().cgrt_render_rank(self._h, C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, rank, nranks, _ptr(rgb), C.byref(st)))
         return rgb, {k: getattr(st, k) for k, _ in st._fields_}
 
+    def render_aa(self, cam, W: int, H: int, lights=None, max_level: int = 2, spherical=None, units=None, samples: int = 200, seed: int = 0,
+                  rank: int = 0, nranks: int = 1, mapped: bool = False, rgb: Optional[np.ndarray] = None):
+        """cgrt_render_aa / cgrt_render_aa_mapped: the reference's 2x2 anti-aliasing (main.cpp:663-687) -- 4 sub-samples per pixel,
+        summed in loop order and divided by 5.0f.  rank/nranks: this rank's 32x32-pixel blocks only, other pixels of `rgb` are
+        kept.  mapped=True (whole frame only) reads the scene's pinned frame and returns a copy.  Returns (rgb[W*H,3], stats dict)."""
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        st = RenderStats()
+        q = None
+        if spherical is not None:
+            spherical, units = _f32(spherical, (-1, 7)), _f32(units, (-1, 3))
+            q = C.byref(SoftShadows(spherical.ctypes.data, units.ctypes.data, len(spherical), samples, len(units), seed, 0))
+        c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
+        if mapped:
+            if nranks != 1 or rgb is not None:
+                raise ValueError("render_aa(mapped=True) returns the whole frame: rank/nranks/rgb do not apply")
+            ptr = C.c_void_p()
+            _check(lib().cgrt_render_aa_mapped(self._h, C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, C.byref(ptr), C.byref(st)))
+            rgb = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(W * H, 3)).copy()
+        else:
+            rgb = np.zeros((W * H, 3), np.float32) if rgb is None else rgb
+            assert rgb.dtype == np.float32 and rgb.size == W * H * 3 and rgb.flags.c_contiguous
+            _check(lib().cgrt_render_aa(self._h, C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, rank, nranks, _ptr(rgb), C.byref(st)))
+        return rgb, {k: getattr(st, k) for k, _ in st._fields_}
+
     def generate_rays(self, cam, W: int, H: int, rect=None) -> np.ndarray:
         x0, y0, x1, y1 = rect if rect is not None else (0, 0, W, H)
         rays = np.zeros((x1 - x0) * (y1 - y0), RAY_DTYPE)
@@ -551,6 +578,34 @@ def render_multi(scenes, cam, W: int, H: int, lights=None, max_level: int = 2, s
     c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
     _check(lib().cgrt_render_multi(arr, len(scenes), C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, _ptr(rgb), C.byref(st)))
     return rgb, {k: getattr(st, k) for k, _ in st._fields_}
+
+
+def render_multi_aa(scenes, cam, W: int, H: int, lights=None, max_level: int = 2, spherical=None, units=None, samples: int = 200,
+                    seed: int = 0):
+    """cgrt_render_multi_aa over replicas `scenes`: the anti-aliased frame (Scene.render_aa), every replica downloading only its own
+    resolved pixels. Returns (rgb[W*H,3], stats dict)."""
+    arr = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
+    lights = _f32(scenes[0].sd.point_lights if lights is None else lights, (-1, 6))
+    rgb = np.zeros((W * H, 3), np.float32)
+    st = RenderStats()
+    q = None
+    if spherical is not None:
+        spherical, units = _f32(spherical, (-1, 7)), _f32(units, (-1, 3))
+        q = C.byref(SoftShadows(spherical.ctypes.data, units.ctypes.data, len(spherical), samples, len(units), seed, 0))
+    c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
+    _check(lib().cgrt_render_multi_aa(arr, len(scenes), C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, _ptr(rgb), C.byref(st)))
+    return rgb, {k: getattr(st, k) for k, _ in st._fields_}
+
+
+def resolve_aa(sub: np.ndarray, W: int, H: int) -> np.ndarray:
+    """The resolve of the reference's antiAliasing branch (main.cpp:663-687) in numpy float32, for checking: `sub` is a 2W x 2H frame
+    ((2W*2H, 3), index yc*2W + xc); pixel (x, y) = (((0 + s[2y][2x]) + s[2y][2x+1]) + s[2y+1][2x]) + s[2y+1][2x+1]) / 5.0f."""
+    s = np.asarray(sub, np.float32).reshape(2 * H, 2 * W, 3)
+    acc = np.zeros((H, W, 3), np.float32)
+    for dy in (0, 1):
+        for dx in (0, 1):
+            acc = acc + s[dy::2, dx::2]
+    return (acc / (np.float32(2.0) * np.float32(2.5))).reshape(W * H, 3)
 
 
 # ---- element-wise primitives (src/ray_tracing.h:10-20) ----
@@ -636,6 +691,7 @@ def host_lib() -> C.CDLL:
         H.cgrt_host_selftest.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, C.POINTER(i32)]
         H.cgrt_host_threads_test.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, i32, vp]
         H.cgrt_host_render_bmp.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, i32, i32, i32, i32, C.c_char_p, vp]
+        H.cgrt_host_render_aa.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, i32, i32, i32, i32, i32, C.c_char_p, vp, vp]
         _host = H
     return _host
 
@@ -764,6 +820,25 @@ def host_render_bmp(sd: SceneData, cam, W: int, H: int, path: str, max_level: in
     if rc:
         raise RuntimeError("cgrt_host_render_bmp: " + Hl.cgrt_host_last_error().decode())
     return rgb
+
+
+def host_render_aa(sd: SceneData, cam, W: int, H: int, max_level: int = 2, driver: str = "device", nreplicas: int = 1,
+                   path: Optional[str] = None):
+    """The anti-aliased frame (antiAliasing = true, main.cpp:663-687) through a driver of the C++ mirror: "device"
+    (renderToBufferOnDevices over nreplicas replicas; with `path` also Screen -> writeBitmapToFile, as `render --aa` does),
+    "wavefront" (renderToBuffer, resolved on the host) or "per_ray" (the reference's loop literally). Returns (rgb[W*H,3], stats dict)."""
+    Hl = host_lib()
+    pn, tri = _f32(sd.pos_nrm, (-1, 6)), np.ascontiguousarray(sd.tri, np.uint32).reshape(-1, 3)
+    tm, mats = np.ascontiguousarray(sd.tri_mesh, np.uint32), _f32(sd.materials, (-1, 8))
+    lights, camv = _f32(sd.point_lights, (-1, 6)), _f32(cam, (9,))
+    rgb = np.zeros((W * H, 3), np.float32)
+    st = np.zeros(5, np.float64)
+    d = {"device": 0, "wavefront": 1, "per_ray": 2}[driver]
+    rc = Hl.cgrt_host_render_aa(_ptr(pn), len(pn), _ptr(tri), _ptr(tm), len(tri), _ptr(mats), len(mats), _ptr(lights), len(lights), _ptr(camv),
+                                W, H, max_level, d, nreplicas, None if path is None else path.encode(), _ptr(rgb), _ptr(st))
+    if rc:
+        raise RuntimeError("cgrt_host_render_aa: " + Hl.cgrt_host_last_error().decode())
+    return rgb, dict(primary=int(st[0]), shadow=int(st[1]), reflection=int(st[2]), seconds_device=float(st[3]), seconds_total=float(st[4]))
 
 
 def host_write_bmp(path: str, rgb, W: int, H: int) -> None:

@@ -280,7 +280,7 @@ struct CgrtScene {
     struct WorkSlot {
         void* p = nullptr;
         size_t cap = 0;
-    } work[32];  // slots 0..29 are in use (render_impl)
+    } work[32];  // slots 0..30 are in use (render_impl)
     // pinned host staging of cgrt_render*'s frame (grown on demand, guarded by render_mutex): the device frame comes down with ONE
     // asynchronous copy at PCIe speed; cgrt_render_mapped hands this memory to the caller instead of copying it once more
     void* pin_frame = nullptr;
@@ -1666,9 +1666,12 @@ int cgrt_count_batch(CgrtScene* s, const CgrtRay* rays, uint64_t n, CgrtCounters
 // rgb (optional): the caller's frame; mapped (optional): receives the scene's pinned staging frame (valid until the next
 // cgrt_render* call on this scene).  With nranks > 1 only the pixels this rank owns are meaningful in the staging frame, and only
 // those are copied into rgb (pixels of other ranks keep the caller's contents).
+// aa: the reference's antiAliasing branch (main.cpp:663-687): the wavefront shades the 2W x 2H sub-sample frame, ranks own its
+// 64x64 super-tiles (32x32 pixel blocks of the W x H frame), k_resolve_aa writes the W x H frame on the device and only that comes
+// down (nranks > 1: only this rank's pixels, packed).  The caller has checked the arguments (aa_args).
 static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats, CgrtCounters* counted = nullptr,
-                       const float** mapped = nullptr) {
+                       const float** mapped = nullptr, bool aa = false) {
     if (!s || !cam || (!rgb && !mapped) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);
     if (W <= 0 || H <= 0 || max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad frame size or recursion depth");
@@ -1677,6 +1680,11 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         if (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24))
             return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
         if ((unsigned long long)W * H > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large");
+    }
+    const int PW = W, PH = H;  // the frame the caller receives
+    if (aa) {                  // from here on W x H is the frame the wavefront shades: sub-sample (xc, yc) is its pixel (xc, yc)
+        W *= 2;
+        H *= 2;
     }
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> one_frame(s->render_mutex);  // the workspace below belongs to one frame at a time
@@ -1696,7 +1704,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     WsBuf rays[3] = {{s, 0}, {s, 1}, {s, 21}}, hits[3] = {{s, 2}, {s, 3}, {s, 22}}, normals[3] = {{s, 4}, {s, 5}, {s, 23}},
           pix[3] = {{s, 6}, {s, 7}, {s, 24}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
           sslot[2] = {{s, 12}, {s, 28}}, dlights{s, 13}, levels{s, 14}, drgb{s, 15}, dctr{s, 16}, dslights{s, 17}, dunits{s, 18}, dlit{s, 19},
-          dwork{s, 20}, dspawn{s, 29};
+          dwork{s, 20}, dspawn{s, 29}, dres{s, 30};
     unsigned long long *cw_primary = nullptr, *cw_shadow = nullptr, *cw_mirror = nullptr;
     if (counted) {
         HIP_TRY(dwork.alloc(3 * 8 * sizeof(unsigned long long)));
@@ -1722,6 +1730,11 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     HIP_TRY(dlights.alloc((size_t)L * 24));
     HIP_TRY(levels.alloc((size_t)(max_level > 0 ? max_level : 1) * n * 32));
     HIP_TRY(drgb.alloc(npix * 12));
+    const int packed = aa && nranks > 1;
+    const size_t res_bytes = packed ? (size_t)F.nst_rank * 1024 * 12 : (size_t)PW * PH * 12;  // the resolved frame (aa)
+    if (aa) HIP_TRY(dres.alloc(std::max<size_t>(res_bytes, (size_t)F.nst_rank * 1024 * 12)));
+    // (k_resolve_aa's grid covers whole 32x32 blocks; threads outside the frame write nothing)
+    auto resolve = [&](hipStream_t on) { return aa ? launch_resolve_aa(F, drgb.as<float>(), dres.as<float>(), packed, on) : hipSuccess; };
     const size_t nctr = 4 * (size_t)(max_level + 1);
     HIP_TRY(dctr.alloc(nctr * sizeof(uint32_t)));  // per level {shadow rays, mirror rays, hits, -}; the last block: [3] = primary hits
     if (L) HIP_TRY(hipMemcpy(dlights.p, lights, (size_t)L * 24, hipMemcpyHostToDevice));
@@ -1876,6 +1889,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         }
         for (int level = np - 2; level >= 1; level--) HIP_TRY(launch_fold(lvl_of(level), lvl_of(level + 1), cap_of(level), nullptr, count_of(level)));
         HIP_TRY(launch_write_rgb(lvl_of(0), np >= 2 ? lvl_of(1) : nullptr, cap0, ipix.as<int>(), drgb.as<float>(), tail, pair));
+        HIP_TRY(resolve(tail));
         HIP_TRY(hipEventRecord(aux.e1, tail));
         HIP_TRY(hipEventSynchronize(aux.e1));
         std::vector<uint32_t> hc(nctr);
@@ -1898,7 +1912,9 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             return CGRT_OK;  // (frame_done stays false: the exact path draws the frame)
         }
         st.primary_rays = owned_pixels(F);
-        st.shadow_rays = (uint64_t)actual[0] * L;  // (level 0's counter block is not used by the fused spawn)
+        // (level 0's counter block is not used by the fused spawn; a frame without primary hits has no level at all: it is black,
+        // the primary kernel cleared its pixels)
+        st.shadow_rays = actual.empty() ? 0 : (uint64_t)actual[0] * L;
         st.reflection_rays = hc[4 * (size_t)max_level + 3];
         for (size_t level = 1; level < actual.size(); level++) {
             st.shadow_rays += hc[4 * level + 0];
@@ -2012,6 +2028,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                     // carries child = -1, so the scatter kernel can fold with level 1 whether or not level 1 has entries); the
                     // counts are read after the frame's closing event.
                     HIP_TRY(launch_write_rgb(levels.as<float>(), levels.as<float>() + (size_t)n * 8, cnt, ipix.as<int>(), drgb.as<float>(), nullptr));
+                    HIP_TRY(resolve(nullptr));
                     finished = true;
                     HIP_TRY(hipEventRecord(aux.e1, nullptr));
                     uint32_t h2[8];
@@ -2060,7 +2077,10 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             HIP_TRY(launch_write_rgb(levels.as<float>(), nlev >= 2 ? levels.as<float>() + (size_t)n * 8 : nullptr, level_count[0], ipix.as<int>(),
                                      drgb.as<float>(), nullptr));
         }
-        if (!finished) HIP_TRY(hipEventRecord(aux.e1, nullptr));
+        if (!finished) {
+            HIP_TRY(resolve(nullptr));
+            HIP_TRY(hipEventRecord(aux.e1, nullptr));
+        }
         HIP_TRY(hipEventSynchronize(aux.e1));
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, aux.e0, aux.e1));
@@ -2080,7 +2100,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         if (erc != CGRT_OK) return erc;
     }
     {
-        const size_t bytes = (size_t)npix * 12;
+        const size_t bytes = aa ? res_bytes : (size_t)npix * 12;
         if (s->pin_frame_cap < bytes) {
             if (s->pin_frame) (void)hipHostFree(s->pin_frame);
             s->pin_frame = nullptr;
@@ -2088,12 +2108,19 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             HIP_TRY(hipHostMalloc(&s->pin_frame, bytes, hipHostMallocDefault));
             s->pin_frame_cap = bytes;
         }
-        HIP_TRY(hipMemcpyAsync(s->pin_frame, drgb.p, bytes, hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipMemcpyAsync(s->pin_frame, aa ? dres.p : drgb.p, bytes, hipMemcpyDeviceToHost, nullptr));
         HIP_TRY(hipStreamSynchronize(nullptr));
         const float* pin = static_cast<const float*>(s->pin_frame);
         if (mapped) *mapped = pin;
         if (rgb && nranks == 1) {
             parallel_copy(rgb, pin, bytes);
+        } else if (rgb && aa) {  // this rank's 32x32 pixel blocks, packed by k_resolve_aa
+            for (uint64_t sl = 0; sl < F.nst_rank; sl++) {
+                const uint64_t k = (uint64_t)rank + (uint64_t)nranks * sl;
+                const int sx = (int)(k % (uint64_t)F.st_x) * 32, sy = (int)(k / (uint64_t)F.st_x) * 32;
+                const int w = std::min(32, PW - sx), h = std::min(32, PH - sy);
+                for (int r = 0; r < h; r++) std::memcpy(rgb + 3 * ((size_t)(sy + r) * PW + sx), pin + 3 * (sl * 1024 + 32 * (uint64_t)r), (size_t)w * 12);
+            }
         } else if (rgb) {  // this rank's super-tiles only (the ownership rule of cgrt_trace_primary)
             const uint64_t nst = (uint64_t)F.st_x * (uint64_t)F.st_y;
             for (uint64_t k = (uint64_t)rank; k < nst; k += (uint64_t)nranks) {
@@ -2136,6 +2163,37 @@ int cgrt_render_mapped(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
 int cgrt_render_rank(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                      int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats) {
     return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, rgb, stats);
+}
+
+// The anti-aliased entries check every argument before any device work (a host-only scene: CGRT_E_NO_DEVICE after the rest).
+static int aa_args(const CgrtCamera* cam, const void* out, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                   int max_level, int rank, int nranks) {
+    if (!cam || !out) return fail(CGRT_E_ARG, "NULL argument");
+    if (nlights && !lights) return fail(CGRT_E_ARG, "nlights > 0 but lights is NULL");
+    if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+    if (4ull * (unsigned long long)W * (unsigned long long)H > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large: 4*W*H sub-samples exceed 0x7fffffff");
+    if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
+    if (nranks <= 0 || rank < 0 || rank >= nranks) return fail(CGRT_E_ARG, "bad rank / nranks");
+    if (soft && soft->nspherical &&
+        (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
+        return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
+    return CGRT_OK;
+}
+int cgrt_render_aa(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                   int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    const int rc = aa_args(cam, rgb, W, H, lights, nlights, soft, max_level, rank, nranks);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, rgb, stats, nullptr, nullptr, true);
+}
+int cgrt_render_aa_mapped(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                          int max_level, const float** rgb, CgrtRenderStats* stats) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    const int rc = aa_args(cam, rgb, W, H, lights, nlights, soft, max_level, 0, 1);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, rgb, true);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2266,15 +2324,9 @@ int cgrt_trace_primary_multi(CgrtScene* const* scenes, int nscenes, const CgrtCa
     return CGRT_OK;
 }
 
-int cgrt_render_multi(CgrtScene* const* scenes, int nscenes, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights,
-                      const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats) {
-    if (!scenes || nscenes <= 0 || nscenes > 64 || !cam || !rgb) return fail(CGRT_E_ARG, "NULL argument or bad replica count");
-    for (int i = 0; i < nscenes; i++) {
-        if (!scenes[i]) return fail(CGRT_E_ARG, "NULL scene");
-        for (int k = 0; k < i; k++)
-            if (scenes[k] == scenes[i]) return fail(CGRT_E_ARG, "the same replica twice: create one scene per rank (the same device may repeat)");
-    }
-    if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+// cgrt_render_multi*: one host thread per replica (arguments checked by the caller)
+static int render_replicas(CgrtScene* const* scenes, int nscenes, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights,
+                           const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats, bool aa) {
     // every replica renders its super-tiles (shading included: a pixel's secondary rays stay on the device that owns it) into a
     // frame of its own on a host thread of its own; the owned pixels are then merged into the caller's frame
     std::vector<CgrtRenderStats> st(nscenes);
@@ -2283,7 +2335,7 @@ int cgrt_render_multi(CgrtScene* const* scenes, int nscenes, const CgrtCamera* c
     auto work = [&](int i) {
         // render_impl downloads the replica's frame into its scene's pinned staging and copies ONLY the super-tiles rank i owns
         // into the caller's frame: disjoint regions, so the replicas' threads write rgb concurrently without a merge pass
-        status[i] = render_impl(scenes[i], cam, W, H, lights, nlights, soft, max_level, i, nscenes, rgb, &st[i]);
+        status[i] = render_impl(scenes[i], cam, W, H, lights, nlights, soft, max_level, i, nscenes, rgb, &st[i], nullptr, nullptr, aa);
         if (status[i]) errs[i] = g_err;  // (thread-local: carried over to the caller's thread below)
     };
     {
@@ -2305,6 +2357,34 @@ int cgrt_render_multi(CgrtScene* const* scenes, int nscenes, const CgrtCamera* c
     }
     if (stats) *stats = tot;
     return CGRT_OK;
+}
+
+int cgrt_render_multi(CgrtScene* const* scenes, int nscenes, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights,
+                      const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats) {
+    if (!scenes || nscenes <= 0 || nscenes > 64 || !cam || !rgb) return fail(CGRT_E_ARG, "NULL argument or bad replica count");
+    for (int i = 0; i < nscenes; i++) {
+        if (!scenes[i]) return fail(CGRT_E_ARG, "NULL scene");
+        for (int k = 0; k < i; k++)
+            if (scenes[k] == scenes[i]) return fail(CGRT_E_ARG, "the same replica twice: create one scene per rank (the same device may repeat)");
+    }
+    if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+    return render_replicas(scenes, nscenes, cam, W, H, lights, nlights, soft, max_level, rgb, stats, false);
+}
+
+// The replicas of cgrt_render_multi_aa each shade the sub-sample super-tiles i % nscenes, resolve them on their device and download
+// only their own pixels (render_impl, packed); the host threads scatter disjoint 32x32 blocks into rgb.
+int cgrt_render_multi_aa(CgrtScene* const* scenes, int nscenes, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights,
+                         const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats) {
+    if (!scenes || nscenes <= 0 || nscenes > 64) return fail(CGRT_E_ARG, "NULL argument or bad replica count");
+    for (int i = 0; i < nscenes; i++) {
+        if (!scenes[i]) return fail(CGRT_E_ARG, "NULL scene");
+        for (int k = 0; k < i; k++)
+            if (scenes[k] == scenes[i]) return fail(CGRT_E_ARG, "the same replica twice: create one scene per rank (the same device may repeat)");
+    }
+    const int rc = aa_args(cam, rgb, W, H, lights, nlights, soft, max_level, 0, nscenes);
+    if (rc) return rc;
+    for (int i = 0; i < nscenes; i++) NEED_DEVICE(scenes[i]);
+    return render_replicas(scenes, nscenes, cam, W, H, lights, nlights, soft, max_level, rgb, stats, true);
 }
 
 // ------------------------------------------------------------------------------------------------

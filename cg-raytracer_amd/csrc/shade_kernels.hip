@@ -209,6 +209,39 @@ __global__ void k_write_rgb(const float4* __restrict__ lvl0, const float4* __res
     rgb[3 * pix + 2] = a.z;
 }
 
+// The reference's antiAliasing branch (main.cpp:663-687): pixel (x, y) of the W x H frame is resolved from the sub-samples
+// (2x + dx, 2y + dy) of the 2W x 2H frame `sub` the wavefront shaded -- summed channel by channel in the reference's loop order (yc
+// outer, xc inner) onto a zero accumulator (upstream's `glm::vec3 color;` is uninitialised, DESIGN.md "Anti-aliasing" finding 1) and
+// divided by level * 2.5f = 5.0f (:685; an IEEE division, not a product with 0.2f: -ffp-contract=off and correctly rounded division,
+// csrc/Makefile).  F is the sub-sample frame: one thread per pixel of the 64x64 sub-sample super-tiles this rank owns (32x32 pixels
+// each, so a pixel's four sub-samples always belong to one rank).  packed: pixel k of the rank's sl-th super-tile goes to
+// out[sl * 1024 + k] (the rank's pixels back to back: one contiguous download), otherwise to out[y * W + x].
+__global__ void k_resolve_aa(FrameDev F, const float* __restrict__ sub, float* __restrict__ out, int packed) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long sl = t >> 10;
+    if (sl >= F.nst_rank) return;
+    const unsigned k = (unsigned)(t & 1023u);
+    const unsigned long long st = (unsigned long long)F.rank + (unsigned long long)F.nranks * sl;
+    const int W = F.W / 2, H = F.H / 2;
+    const int x = (int)(st % (unsigned long long)F.st_x) * 32 + (int)(k & 31u);
+    const int y = (int)(st / (unsigned long long)F.st_x) * 32 + (int)(k >> 5);
+    if (x >= W || y >= H) return;
+    float r = 0.0f, g = 0.0f, b = 0.0f;  // :660, restated as zero
+    for (int yc = 2 * y; yc < 2 * y + 2; yc++)      // :666
+        for (int xc = 2 * x; xc < 2 * x + 2; xc++) {  // :668
+            const float* p = sub + 3ull * ((unsigned long long)yc * (unsigned long long)F.W + (unsigned long long)xc);
+            r = r + p[0];
+            g = g + p[1];
+            b = b + p[2];
+        }
+    const float level = 2.0f;
+    const float d = level * 2.5f;  // :685
+    const unsigned long long o = packed ? (sl << 10) + k : (unsigned long long)y * (unsigned long long)W + (unsigned long long)x;
+    out[3 * o] = r / d;
+    out[3 * o + 1] = g / d;
+    out[3 * o + 2] = b / d;
+}
+
 static inline unsigned grid_for(unsigned long long n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 hipError_t launch_spawn(const float* rays, const CgrtHitDev* hits, const float* normals, const int* pixels, unsigned long long n,
@@ -239,6 +272,13 @@ hipError_t launch_write_rgb(const float* lvl0, const float* child_lvl, unsigned 
     if (n)
         hipLaunchKernelGGL(k_write_rgb, dim3(grid_for(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
                            reinterpret_cast<const float4*>(child_lvl), n, item_pixels, rgb, dcount);
+    return hipGetLastError();
+}
+
+hipError_t launch_resolve_aa(const FrameDev& F, const float* sub, float* out, int packed, hipStream_t s) {
+    const unsigned long long n = (unsigned long long)F.nst_rank * 1024ull;
+    if (n)
+        hipLaunchKernelGGL(k_resolve_aa, dim3(grid_for(n, 256)), dim3(256), 0, s, F, sub, out, packed);
     return hipGetLastError();
 }
 

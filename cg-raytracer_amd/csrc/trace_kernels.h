@@ -86,6 +86,9 @@ hipError_t launch_fold(float* lvl, const float* child_lvl, unsigned long long n,
 // child_lvl (optional): level 0 is folded with level 1 on the fly (colour + childColour * ks, main.cpp:262) instead of by launch_fold
 hipError_t launch_write_rgb(const float* lvl0, const float* child_lvl, unsigned long long n, const int* item_pixels, float* rgb, hipStream_t s,
                             const uint32_t* dcount = nullptr);
+// the anti-aliased frame (main.cpp:663-687) from the 2W x 2H sub-sample frame `sub` of F: see k_resolve_aa (shade_kernels.hip).
+// out: F.nst_rank * 1024 * 3 floats (packed) or (F.W / 2) * (F.H / 2) * 3 floats
+hipError_t launch_resolve_aa(const FrameDev& F, const float* sub, float* out, int packed, hipStream_t s);
 hipError_t launch_gather_calib(const void* table, unsigned long long nrecords, unsigned long long mult, unsigned long long add, float* sink,
                                hipStream_t s);
 hipError_t launch_fastdiv_check(const float* a, const float* d, unsigned long long n, unsigned long long* mismatches, float* first_bad,

@@ -28,34 +28,41 @@ struct SoftShadowSampler {
 };
 
 // maxLevel = 2 reproduces main.cpp:267 (`level >= 2` -> black): primary + one mirror bounce.
+// antiAliasing = the reference's global flag of the same name (main.cpp:35, checkbox "Add Anti Aliasing" :878-882; the branch
+// :663-687): 2x2 sub-samples per pixel, each a full getFinalColor, summed in loop order and divided by 5.0f (include/cgrt.h
+// cgrt_render_aa, findings AA1-AA4).  Sub-sample (xc, yc) is pixel (xc, yc) of the 2W x 2H frame, also for the soft-shadow hash.
+//   device drivers (...OnDevice, ...OnDevices): cgrt_render_aa_mapped / cgrt_render_aa / cgrt_render_multi_aa, resolved on the device;
+//   renderToBuffer / renderRayTracing: the host wavefront over the 2W x 2H frame, resolved on the host in the same order;
+//   renderToBufferPerRay / renderRayTracingPerRay: the reference's loop literally, four getFinalColor calls per pixel with upstream's
+//   ndc expression float(xc) / W * (2.0f / level) - 1.0f.
 // The same frame with the whole driver ON THE DEVICE (cgrt_render_soft: primary rays, shadow and mirror batches and the
 // Phong terms never leave the GPU; one download of W*H*3 floats): the fast path for a caller that wants pixels.
 // RGB agrees with renderToBuffer to the 1e-5 parity bar (powf is the device's).
 RenderStats renderToBufferOnDevice(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, int W, int H, float* rgb,
-                                   int maxLevel = 2, const SoftShadowSampler* sampler = nullptr);
+                                   int maxLevel = 2, const SoftShadowSampler* sampler = nullptr, bool antiAliasing = false);
 RenderStats renderRayTracingOnDevice(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, Screen& screen,
-                                     int maxLevel = 2, const SoftShadowSampler* sampler = nullptr);
+                                     int maxLevel = 2, const SoftShadowSampler* sampler = nullptr, bool antiAliasing = false);
 // One frame on several devices: bvhs[i] is a replica of the scene's BVH on its own device
 // (BoundingVolumeHierarchy(&scene, device)); replica i renders the 64x64 super-tiles i % n, shading included, and the
 // frame is assembled in ONE Screen / buffer, as the reference's renderRayTracing yields one (main.cpp:648-720).
 RenderStats renderToBufferOnDevices(const Scene& scene, const Trackball& camera, const std::vector<const BoundingVolumeHierarchy*>& bvhs, int W, int H,
-                                    float* rgb, int maxLevel = 2, const SoftShadowSampler* sampler = nullptr);
+                                    float* rgb, int maxLevel = 2, const SoftShadowSampler* sampler = nullptr, bool antiAliasing = false);
 RenderStats renderRayTracingOnDevices(const Scene& scene, const Trackball& camera, const std::vector<const BoundingVolumeHierarchy*>& bvhs,
-                                      Screen& screen, int maxLevel = 2, const SoftShadowSampler* sampler = nullptr);
+                                      Screen& screen, int maxLevel = 2, const SoftShadowSampler* sampler = nullptr, bool antiAliasing = false);
 // The reference's driver LITERALLY (src/main.cpp:265-310, :648-696): an `omp parallel for` over the rows, per pixel the recursive
 // getFinalColor -> trace -> shade -> shading -> pointInShadow, ONE BoundingVolumeHierarchy::intersect call per ray -- what an
 // unchanged main.cpp does to the library.  The library combines the rays of concurrent callers into shared launches
 // (include/cgrt.h cgrt_set_call_combining), so the frame's speed grows with the number of calling threads; `threads` = 0 takes
 // OpenMP's default, and MORE threads than cores pay: a caller spends its time waiting for the GPU round trip.
 RenderStats renderToBufferPerRay(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, int W, int H, float* rgb,
-                                 int maxLevel = 2, const SoftShadowSampler* sampler = nullptr, int threads = 0);
+                                 int maxLevel = 2, const SoftShadowSampler* sampler = nullptr, int threads = 0, bool antiAliasing = false);
 RenderStats renderRayTracingPerRay(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, Screen& screen, int maxLevel = 2,
-                                   const SoftShadowSampler* sampler = nullptr, int threads = 0);
+                                   const SoftShadowSampler* sampler = nullptr, int threads = 0, bool antiAliasing = false);
 // sampler: required when the scene has spherical lights (nullptr -> SoftShadowSampler::gaussian()).
 RenderStats renderRayTracing(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, Screen& screen, int maxLevel = 2,
-                             const SoftShadowSampler* sampler = nullptr);
+                             const SoftShadowSampler* sampler = nullptr, bool antiAliasing = false);
 // Same, into a plain W*H rgb float buffer indexed y*W+x (not flipped).
 RenderStats renderToBuffer(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, int W, int H, float* rgb, int maxLevel = 2,
-                           const SoftShadowSampler* sampler = nullptr);
+                           const SoftShadowSampler* sampler = nullptr, bool antiAliasing = false);
 // renderToBuffer keeps its per-level arrays (up to 1 GiB) for the next frame; this hands them back to the C library.
 void releaseRenderBuffers();

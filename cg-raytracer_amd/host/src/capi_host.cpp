@@ -4,6 +4,7 @@
 #include <chrono>
 #include <cstring>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <thread>
 
@@ -416,6 +417,52 @@ int cgrt_host_render_bmp(const float* pos_nrm, uint32_t nverts, const uint32_t* 
         if (rgb_out) (void)renderToBufferOnDevices(sc, camera, bvhs, W, H, rgb_out, maxLevel);
         (void)renderRayTracingOnDevices(sc, camera, bvhs, screen, maxLevel);
         screen.writeBitmapToFile(path);
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
+// The anti-aliased frame (antiAliasing = true, main.cpp:663-687) through one of the mirror's drivers: driver 0 = on the device
+// (renderToBufferOnDevices over nreplicas BVH replicas on device 0; path != NULL: also renderRayTracingOnDevices -> Screen ->
+// writeBitmapToFile, what `render --aa` does), 1 = the host wavefront (renderToBuffer), 2 = the reference's loop literally
+// (renderToBufferPerRay).  rgb: W*H*3 floats, index y*W+x.  stats (optional): primary, shadow, reflection rays, device s, total s.
+int cgrt_host_render_aa(const float* pos_nrm, uint32_t nverts, const uint32_t* tri, const uint32_t* tri_mesh, uint32_t ntris,
+                        const float* materials, uint32_t nmesh, const float* lights, uint32_t nlights, const float* cam, int W, int H,
+                        int maxLevel, int driver, int nreplicas, const char* path, float* rgb, double* stats) {
+    try {
+        Scene sc = scene_from_arrays(pos_nrm, nverts, tri, tri_mesh, ntris, materials, nmesh, lights, nlights);
+        std::vector<std::unique_ptr<BoundingVolumeHierarchy>> own;
+        std::vector<const BoundingVolumeHierarchy*> bvhs;
+        for (int i = 0; i < (driver == 0 && nreplicas > 1 ? nreplicas : 1); i++) {
+            own.emplace_back(new BoundingVolumeHierarchy(&sc, 0));
+            bvhs.push_back(own.back().get());
+        }
+        Trackball camera(cam[7], cam[8], cam[6]);
+        camera.setCamera(cgrt::vec3(cam[0], cam[1], cam[2]), cgrt::vec3(cam[3], cam[4], cam[5]), cam[6]);
+        RenderStats st;
+        if (driver == 0) {
+            st = renderToBufferOnDevices(sc, camera, bvhs, W, H, rgb, maxLevel, nullptr, true);
+            if (path) {
+                Screen screen(W, H);
+                (void)renderRayTracingOnDevices(sc, camera, bvhs, screen, maxLevel, nullptr, true);
+                screen.writeBitmapToFile(path);
+            }
+        } else if (driver == 1) {
+            st = renderToBuffer(sc, camera, *bvhs[0], W, H, rgb, maxLevel, nullptr, true);
+        } else if (driver == 2) {
+            st = renderToBufferPerRay(sc, camera, *bvhs[0], W, H, rgb, maxLevel, nullptr, 0, true);
+        } else {
+            throw std::runtime_error("driver must be 0 (device), 1 (host wavefront) or 2 (per ray)");
+        }
+        if (stats) {
+            stats[0] = (double)st.primary;
+            stats[1] = (double)st.shadow;
+            stats[2] = (double)st.reflection;
+            stats[3] = st.seconds_device;
+            stats[4] = st.seconds_total;
+        }
         return 0;
     } catch (const std::exception& e) {
         g_err = e.what();

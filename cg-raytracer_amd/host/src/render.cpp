@@ -204,8 +204,37 @@ void releaseRenderBuffers() { g_blocks.clear(); }
 
 // The loops over a level's items are `omp parallel for`s, as the reference's loop over rows is (main.cpp:653-656): every item writes
 // only its own entries, and list positions come from prefix sums, so the frame does not depend on the thread count.
+namespace {
+// main.cpp:663-687 after the sub-samples: pixel (x, y) = (((0 + s[2y][2x]) + s[2y][2x+1]) + s[2y+1][2x]) + s[2y+1][2x+1]) / (level * 2.5f),
+// channel by channel; `sub` is the 2W x 2H frame (index yc * 2W + xc).  The accumulator is uninitialised upstream (:660): zero here.
+void resolveAntiAliasing(const float* sub, int W, int H, float* rgb) {
+    const float level = 2.0f;
+#pragma omp parallel for schedule(static) num_threads(cgrt::hostTeam())
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            vec3 color(0.0f);
+            for (int yc = 2 * y; yc < 2 * y + 2; yc++)
+                for (int xc = 2 * x; xc < 2 * x + 2; xc++) {
+                    const float* p = sub + 3 * ((size_t)yc * (size_t)(2 * W) + (size_t)xc);
+                    color = color + vec3(p[0], p[1], p[2]);
+                }
+            color = color / (level * 2.5f);
+            float* q = rgb + 3 * ((size_t)y * W + x);
+            q[0] = color.x, q[1] = color.y, q[2] = color.z;
+        }
+}
+}  // namespace
+
 RenderStats renderToBuffer(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, int W, int H, float* rgb,
-                           int maxLevel, const SoftShadowSampler* sampler) {
+                           int maxLevel, const SoftShadowSampler* sampler, bool antiAliasing) {
+    if (antiAliasing) {  // the wavefront over the 2W x 2H sub-sample frame, resolved here
+        const auto t_begin = Clock::now();
+        std::vector<float> sub((size_t)4 * W * H * 3);
+        RenderStats st = renderToBuffer(scene, camera, bvh, 2 * W, 2 * H, sub.data(), maxLevel, sampler, false);
+        resolveAntiAliasing(sub.data(), W, H, rgb);
+        st.seconds_total = std::chrono::duration<double>(Clock::now() - t_begin).count();
+        return st;
+    }
     RenderStats st;
     SoftShadowSampler fallback;
     if (!scene.sphericalLight.empty() && (!sampler || sampler->units.empty() || sampler->samples == 0)) {
@@ -423,7 +452,7 @@ namespace {
 // Screen (Screen::setPixel's flip, main.cpp:696) -- with one replica straight from the library's pinned frame
 // (cgrt_render_mapped: no intermediate copy of the 12-bytes-per-pixel frame), rows copied in bulk (Screen::setFrame).
 RenderStats render_on_devices(const Scene& scene, const Trackball& camera, const std::vector<const BoundingVolumeHierarchy*>& bvhs, int W, int H,
-                              float* rgb, Screen* screen, int maxLevel, const SoftShadowSampler* sampler) {
+                              float* rgb, Screen* screen, int maxLevel, const SoftShadowSampler* sampler, bool aa) {
     const auto t_begin = Clock::now();
     if (bvhs.empty()) throw std::runtime_error("renderToBufferOnDevices: no BVH replica");
     SoftShadowSampler fallback;
@@ -456,17 +485,20 @@ RenderStats render_on_devices(const Scene& scene, const Trackball& camera, const
     int rc;
     if (handles.size() == 1 && screen) {
         const float* frame = nullptr;
-        rc = cgrt_render_mapped(handles[0], &cam, W, H, lights.data(), L, sp, maxLevel, &frame, &cs);
+        rc = aa ? cgrt_render_aa_mapped(handles[0], &cam, W, H, lights.data(), L, sp, maxLevel, &frame, &cs)
+                : cgrt_render_mapped(handles[0], &cam, W, H, lights.data(), L, sp, maxLevel, &frame, &cs);
         if (rc == 0) screen->setFrame(frame);
     } else if (handles.size() == 1) {
-        rc = cgrt_render_soft(handles[0], &cam, W, H, lights.data(), L, sp, maxLevel, rgb, &cs);
+        rc = aa ? cgrt_render_aa(handles[0], &cam, W, H, lights.data(), L, sp, maxLevel, 0, 1, rgb, &cs)
+                : cgrt_render_soft(handles[0], &cam, W, H, lights.data(), L, sp, maxLevel, rgb, &cs);
     } else {
         std::vector<float> tmp;
         if (!rgb) {
             tmp.resize((size_t)W * H * 3);
             rgb = tmp.data();
         }
-        rc = cgrt_render_multi(handles.data(), (int)handles.size(), &cam, W, H, lights.data(), L, sp, maxLevel, rgb, &cs);
+        rc = aa ? cgrt_render_multi_aa(handles.data(), (int)handles.size(), &cam, W, H, lights.data(), L, sp, maxLevel, rgb, &cs)
+                : cgrt_render_multi(handles.data(), (int)handles.size(), &cam, W, H, lights.data(), L, sp, maxLevel, rgb, &cs);
         if (rc == 0 && screen) screen->setFrame(rgb);
     }
     if (rc != 0) throw std::runtime_error(std::string("cgrt_render: ") + cgrt_last_error());
@@ -482,23 +514,23 @@ RenderStats render_on_devices(const Scene& scene, const Trackball& camera, const
 }  // namespace
 
 RenderStats renderToBufferOnDevices(const Scene& scene, const Trackball& camera, const std::vector<const BoundingVolumeHierarchy*>& bvhs, int W, int H,
-                                    float* rgb, int maxLevel, const SoftShadowSampler* sampler) {
-    return render_on_devices(scene, camera, bvhs, W, H, rgb, nullptr, maxLevel, sampler);
+                                    float* rgb, int maxLevel, const SoftShadowSampler* sampler, bool antiAliasing) {
+    return render_on_devices(scene, camera, bvhs, W, H, rgb, nullptr, maxLevel, sampler, antiAliasing);
 }
 
 RenderStats renderToBufferOnDevice(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, int W, int H, float* rgb,
-                                   int maxLevel, const SoftShadowSampler* sampler) {
-    return render_on_devices(scene, camera, {&bvh}, W, H, rgb, nullptr, maxLevel, sampler);
+                                   int maxLevel, const SoftShadowSampler* sampler, bool antiAliasing) {
+    return render_on_devices(scene, camera, {&bvh}, W, H, rgb, nullptr, maxLevel, sampler, antiAliasing);
 }
 
 RenderStats renderRayTracingOnDevices(const Scene& scene, const Trackball& camera, const std::vector<const BoundingVolumeHierarchy*>& bvhs,
-                                      Screen& screen, int maxLevel, const SoftShadowSampler* sampler) {
-    return render_on_devices(scene, camera, bvhs, screen.width(), screen.height(), nullptr, &screen, maxLevel, sampler);
+                                      Screen& screen, int maxLevel, const SoftShadowSampler* sampler, bool antiAliasing) {
+    return render_on_devices(scene, camera, bvhs, screen.width(), screen.height(), nullptr, &screen, maxLevel, sampler, antiAliasing);
 }
 
 RenderStats renderRayTracingOnDevice(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, Screen& screen, int maxLevel,
-                                     const SoftShadowSampler* sampler) {
-    return render_on_devices(scene, camera, {&bvh}, screen.width(), screen.height(), nullptr, &screen, maxLevel, sampler);
+                                     const SoftShadowSampler* sampler, bool antiAliasing) {
+    return render_on_devices(scene, camera, {&bvh}, screen.width(), screen.height(), nullptr, &screen, maxLevel, sampler, antiAliasing);
 }
 
 // ---- the reference's per-pixel recursion, one intersect call per ray (main.cpp:104-135, :160-310, :648-696) ----
@@ -573,7 +605,7 @@ struct PerRay {
 }  // namespace
 
 RenderStats renderToBufferPerRay(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, int W, int H, float* rgb, int maxLevel,
-                                 const SoftShadowSampler* sampler, int threads) {
+                                 const SoftShadowSampler* sampler, int threads, bool antiAliasing) {
     RenderStats st;
     SoftShadowSampler fallback;
     if (!scene.sphericalLight.empty() && (!sampler || sampler->units.empty() || sampler->samples == 0)) {
@@ -587,6 +619,20 @@ RenderStats renderToBufferPerRay(const Scene& scene, const Trackball& camera, co
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads) reduction(+ : nshadow, nrefl, nsoft)
     for (int y = 0; y < H; y++) {  // main.cpp:653-656
         for (int x = 0; x < W; x++) {
+            if (antiAliasing) {  // :663-687, the loops as upstream writes them
+                vec3 color(0.0f);  // :660 (uninitialised upstream)
+                const float level = 2.0f;
+                for (int yc = y * level; yc < 2 + (level * y); yc++)
+                    for (int xc = x * level; xc < 2 + (level * x); xc++) {
+                        const cgrt::vec2 normalizedPixelPos{float(xc) / W * (2.0f / level) - 1.0f, float(yc) / H * (2.0f / level) - 1.0f};
+                        const Ray cameraRay = camera.generateRay(normalizedPixelPos);
+                        color = color + drv.trace(0, cameraRay, (uint32_t)(yc * 2 * W + xc), nshadow, nrefl, nsoft);
+                    }
+                color = color / (level * 2.5f);  // :685
+                float* p = rgb + 3 * ((size_t)y * W + x);
+                p[0] = color.x, p[1] = color.y, p[2] = color.z;
+                continue;
+            }
             const cgrt::vec2 normalizedPixelPos{float(x) / W * 2.0f - 1.0f, float(y) / H * 2.0f - 1.0f};  // :691-693
             const Ray cameraRay = camera.generateRay(normalizedPixelPos);
             const vec3 c = drv.trace(0, cameraRay, (uint32_t)(y * W + x), nshadow, nrefl, nsoft);
@@ -594,7 +640,7 @@ RenderStats renderToBufferPerRay(const Scene& scene, const Trackball& camera, co
             p[0] = c.x, p[1] = c.y, p[2] = c.z;
         }
     }
-    st.primary = maxLevel >= 1 ? (uint64_t)W * H : 0;
+    st.primary = maxLevel >= 1 ? (uint64_t)W * H * (antiAliasing ? 4 : 1) : 0;
     st.shadow = nshadow;
     st.reflection = nrefl;
     st.softShadow = nsoft;
@@ -603,19 +649,19 @@ RenderStats renderToBufferPerRay(const Scene& scene, const Trackball& camera, co
 }
 
 RenderStats renderRayTracingPerRay(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, Screen& screen, int maxLevel,
-                                   const SoftShadowSampler* sampler, int threads) {
+                                   const SoftShadowSampler* sampler, int threads, bool antiAliasing) {
     const int W = screen.width(), H = screen.height();
     std::vector<float> rgb((size_t)W * H * 3);
-    RenderStats st = renderToBufferPerRay(scene, camera, bvh, W, H, rgb.data(), maxLevel, sampler, threads);
+    RenderStats st = renderToBufferPerRay(scene, camera, bvh, W, H, rgb.data(), maxLevel, sampler, threads, antiAliasing);
     screen.setFrame(rgb.data());  // main.cpp:696 for every pixel
     return st;
 }
 
 RenderStats renderRayTracing(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, Screen& screen, int maxLevel,
-                             const SoftShadowSampler* sampler) {
+                             const SoftShadowSampler* sampler, bool antiAliasing) {
     const int W = screen.width(), H = screen.height();
     Array<float> rgb((size_t)W * H * 3);
-    RenderStats st = renderToBuffer(scene, camera, bvh, W, H, rgb.data(), maxLevel, sampler);
+    RenderStats st = renderToBuffer(scene, camera, bvh, W, H, rgb.data(), maxLevel, sampler, antiAliasing);
     screen.setFrame(rgb.data());  // main.cpp:696 for every pixel
     return st;
 }

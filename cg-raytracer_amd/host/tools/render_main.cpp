@@ -1,7 +1,9 @@
 // Headless stand-in for the reference's interactive main() (src/main.cpp:722-939): load a scene preset or an OBJ,
 // build the BVH, render with the reference's default camera, write render.bmp, print the timing the reference prints
 // (main.cpp:791-797).
-//   render [--gpus N | --per-ray [--threads T]] <data-dir> <triangle|cube|cornell|monkey|dragon|custom|file.obj> [W H [maxLevel [out.bmp]]]
+//   render [--aa] [--gpus N | --per-ray [--threads T]] <data-dir> <triangle|cube|cornell|monkey|dragon|custom|file.obj> [W H [maxLevel [out.bmp]]]
+// --aa: the reference's "Add Anti Aliasing" checkbox (antiAliasing, main.cpp:35, :663-687): 2x2 sub-samples per pixel, summed and
+// divided by 5.0f; combines with every driver.
 // --gpus N: the frame is split over N devices (replica i on device i % cgrt_device_count(), super-tiles i % N), the whole
 // shading driver on the devices, one Screen (renderRayTracingOnDevices).
 // --per-ray: the reference's own structure, literally (main.cpp:265-310, :648-696): `omp parallel for` over rows, per-pixel
@@ -19,12 +21,16 @@ extern "C" int cgrt_device_count(void);
 
 int main(int argc, char** argv) {
     int gpus = 0, threads = 0;
-    bool perRay = false;
+    bool perRay = false, aa = false;
     for (;;) {
         if (argc > 2 && std::strcmp(argv[1], "--gpus") == 0) {
             gpus = std::atoi(argv[2]);
             argv += 2;
             argc -= 2;
+        } else if (argc > 1 && std::strcmp(argv[1], "--aa") == 0) {
+            aa = true;
+            argv += 1;
+            argc -= 1;
         } else if (argc > 1 && std::strcmp(argv[1], "--per-ray") == 0) {
             perRay = true;
             argv += 1;
@@ -38,7 +44,7 @@ int main(int argc, char** argv) {
         }
     }
     if (argc < 3) {
-        std::cerr << "usage: render [--gpus N | --per-ray [--threads T]] <data-dir> <scene|file.obj> [W H [maxLevel [out.bmp]]]\n";
+        std::cerr << "usage: render [--aa] [--gpus N | --per-ray [--threads T]] <data-dir> <scene|file.obj> [W H [maxLevel [out.bmp]]]\n";
         return 2;
     }
     const std::filesystem::path dataDir = argv[1];
@@ -70,7 +76,7 @@ int main(int argc, char** argv) {
         const char* od = std::getenv("CGRT_RENDER_ON_DEVICE");
         RenderStats st;
         if (perRay) {
-            st = renderRayTracingPerRay(scene, camera, bvh, screen, maxLevel, nullptr, threads);
+            st = renderRayTracingPerRay(scene, camera, bvh, screen, maxLevel, nullptr, threads, aa);
         } else if (gpus > 0) {
             const int ndev = cgrt_device_count() > 0 ? cgrt_device_count() : 1;
             std::vector<std::unique_ptr<BoundingVolumeHierarchy>> own;
@@ -79,10 +85,10 @@ int main(int argc, char** argv) {
                 own.emplace_back(new BoundingVolumeHierarchy(&scene, i % ndev));
                 bvhs.push_back(own.back().get());
             }
-            st = renderRayTracingOnDevices(scene, camera, bvhs, screen, maxLevel);
+            st = renderRayTracingOnDevices(scene, camera, bvhs, screen, maxLevel, nullptr, aa);
         } else {
-            st = (od && od[0] == '1') ? renderRayTracingOnDevice(scene, camera, bvh, screen, maxLevel)
-                                      : renderRayTracing(scene, camera, bvh, screen, maxLevel);
+            st = (od && od[0] == '1') ? renderRayTracingOnDevice(scene, camera, bvh, screen, maxLevel, nullptr, aa)
+                                      : renderRayTracing(scene, camera, bvh, screen, maxLevel, nullptr, aa);
         }
         const auto end = std::chrono::high_resolution_clock::now();
         std::cout << "Time to render image: " << std::chrono::duration<float, std::milli>(end - start).count() << " milliseconds" << std::endl;

@@ -294,6 +294,39 @@ int cgrt_trace_primary_multi(CgrtScene* const* scenes, int nscenes, const CgrtCa
 int cgrt_render_multi(CgrtScene* const* scenes, int nscenes, const CgrtCamera* cam, int W, int H, const float* lights,
                       uint32_t nlights, const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats);
 
+/* The reference's antiAliasing branch (src/main.cpp:663-687, checkbox "Add Anti Aliasing" :878-882): 2x2 sub-samples per pixel, each a
+ * full getFinalColor, summed in loop order and divided by 5.0f (level * 2.5f upstream).  For pixel (x, y) of the W x H frame:
+ *     color = 0;  for yc in {2y, 2y+1}: for xc in {2x, 2x+1}: color = color + getFinalColor(ray of ndc (xc/W*1.0f-1.0f, yc/H*1.0f-1.0f));
+ *     rgb = color / 5.0f   (each channel ((0 + c[2y][2x]) + c[2y][2x+1]) + c[2y+1][2x]) + c[2y+1][2x+1], then an IEEE division)
+ * Findings (DESIGN.md "Anti-aliasing"):
+ *   AA1  upstream's accumulator `glm::vec3 color;` (:660) is uninitialised (glm 0.9.9.8 without GLM_FORCE_CTOR_INIT): restated as zero;
+ *   AA2  the four samples are divided by 5, not 4 (:685): an AA frame is 4/5 as bright as its samples' mean -- reproduced, the library is
+ *        a drop-in;
+ *   AA3  sub-sample (xc, yc) gets the ray of pixel (xc, yc) of a 2W x 2H frame: upstream's float(xc)/W*1.0f-1.0f equals
+ *        float(xc)/float(2W)*2.0f-1.0f bit for bit (scaling by powers of two is exact here; tested for every xc), and the aspect ratio
+ *        (Window::aspectRatio) is the same for both frames;
+ *   AA4  only 2x2 exists upstream (the loop bound 2 + level*y is hard-coded): nothing here generalises to k x k.
+ * So with point lights an AA frame is the library's own 2W x 2H frame resolved as above; with spherical lights sub-sample (xc, yc)
+ * hashes as pixel p = yc*2W + xc (cgrt_render_soft), so soft AA frames are the 2W x 2H soft frame of the same table and seed, resolved.
+ * The wavefront (primary kernel, spawn / shadow / mirror lists, fold, soft-shadow kernels, frame prediction) runs unchanged over the
+ * 4*W*H sub-samples; a device kernel resolves the frame and only W*H*3 floats come down.
+ * rank/nranks as cgrt_render_rank (0/1 = whole frame), applied to the sub-sample frame: a rank owns the 64x64 super-tiles
+ * (index % nranks == rank, row-major) of the 2W x 2H frame, i.e. the 32x32-pixel blocks of the W x H frame, so a pixel's four
+ * sub-samples always belong to the rank that owns the pixel; pixels of other ranks keep the caller's contents.  soft may be NULL.
+ * stats count the rays that exist upstream (primary_rays = 4*W*H).  Workspace: about 0.3 KB per SUB-SAMPLE (roughly 2.5 GB for a
+ * 1920x1080 AA frame; extrapolated from the note at cgrt_render, not measured).
+ * Every argument is checked before any device work: NULL pointers, nlights > 0 with lights NULL, W or H <= 0, 4*W*H > 0x7fffffff,
+ * max_level outside 0..16, bad rank / nranks, bad soft -> CGRT_E_ARG; then a host-only scene -> CGRT_E_NO_DEVICE. */
+int cgrt_render_aa(CgrtScene* scene, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights,
+                   const CgrtSoftShadows* soft, int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats);
+/* As cgrt_render_mapped: *rgb receives the scene's pinned W*H*3 frame (index y*W+x), valid until the next cgrt_render* call on it. */
+int cgrt_render_aa_mapped(CgrtScene* scene, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights,
+                          const CgrtSoftShadows* soft, int max_level, const float** rgb, CgrtRenderStats* stats);
+/* As cgrt_render_multi: replica i renders the sub-sample super-tiles i % nscenes (the ownership rule of cgrt_render_aa), resolves them
+ * on its device and downloads only its own resolved pixels.  The bytes written equal those of cgrt_render_aa (tested). */
+int cgrt_render_multi_aa(CgrtScene* const* scenes, int nscenes, const CgrtCamera* cam, int W, int H, const float* lights,
+                         uint32_t nlights, const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats);
+
 /* Work counters of the same traversal (separate instrumented launch; not part of any timed region). */
 int cgrt_count_primary(CgrtScene* scene, const CgrtCamera* cam, int W, int H, int x0, int y0, int x1, int y1,
                        int rank, int nranks, CgrtCounters* out);
