@@ -108,7 +108,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -175,6 +175,9 @@ def lib() -> C.CDLL:
     L.cgrt_render_aa.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, i32, i32, vp, C.POINTER(RenderStats)]
     L.cgrt_render_aa_mapped.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, C.POINTER(vp), C.POINTER(RenderStats)]
     L.cgrt_render_multi_aa.argtypes = [C.POINTER(vp), i32, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
+    L.cgrt_render_device.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, i32, i32, i32, vp, i32, u64, vp,
+                                     C.POINTER(RenderStats)]
+    L.cgrt_debug_export_frame.argtypes = [i32, vp, i32, i32, i32, u64, vp]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
     L.cgrt_count_batch.argtypes = [vp, vp, u64, C.POINTER(Counters)]
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
@@ -292,6 +295,86 @@ def source_hash() -> str:
 
 def device_count() -> int:
     return int(lib().cgrt_device_count())
+
+
+# cgrt_render_device's output formats (include/cgrt.h CGRT_FRAME_*)
+FRAME_FORMATS = {"rgb": 0, "chw": 1, "rgba8": 2}
+
+
+def _frame_format(format) -> int:
+    """"rgb" / "chw" / "rgba8" -> CGRT_FRAME_*; an int is passed through as it is (the library checks it)."""
+    if isinstance(format, str):
+        if format not in FRAME_FORMATS:
+            raise ValueError(f"format must be one of {sorted(FRAME_FORMATS)}, not {format!r}")
+        return FRAME_FORMATS[format]
+    return int(format)
+
+
+def rgba8_of(rgb, W: int, H: int) -> np.ndarray:
+    """CGRT_FRAME_RGBA8 in numpy, for checking: the reference's 8-bit screen image (Screen::writeBitmapToFile, screen.cpp:38-49) of the
+    frame rgb ((W*H, 3), index y*W + x) -- row H-1-y, bytes R, G, B, 255, each (uint8)(min(max(v, 0), 1) * 255.0f) in float32, truncated;
+    a NaN channel gives 0.  Returns (H, W, 4) uint8."""
+    v = np.asarray(rgb, np.float32).reshape(H, W, 3)
+    with np.errstate(invalid="ignore"):
+        c = np.where(v > 0, np.where(v < 1, v, np.float32(1.0)), np.float32(0.0)).astype(np.float32)
+    out = np.empty((H, W, 4), np.uint8)
+    out[..., :3] = (c * np.float32(255.0)).astype(np.uint8)[::-1]
+    out[..., 3] = 255
+    return out
+
+
+def hip_runtimes() -> list:
+    """Files of the HIP runtime (libamdhip64) this process has mapped.  torch ships a copy of its own; a process that has opened a
+    second one (by another name) holds two runtimes, and streams and buffers of one mean nothing to the other."""
+    found = set()
+    with open("/proc/self/maps") as f:
+        for line in f:
+            parts = line.split(None, 5)
+            if len(parts) == 6 and "libamdhip64" in os.path.basename(parts[5].strip()):
+                found.add(os.path.realpath(parts[5].strip()))
+    return sorted(found)
+
+
+_one_runtime_seen = False
+
+
+def _check_one_hip_runtime() -> None:
+    """render_tensor's check that torch's streams and buffers belong to the runtime libcgrt.so uses: the process must map exactly one
+    HIP runtime.  Reading /proc/self/maps costs about as much as the frame's host overhead, so the check runs until it first
+    succeeds and not again: the runtime libcgrt.so is bound to stays the same for the life of the process."""
+    global _one_runtime_seen
+    if _one_runtime_seen:
+        return
+    runtimes = hip_runtimes()
+    if len(runtimes) != 1:
+        raise RuntimeError(f"the process maps {len(runtimes)} HIP runtimes ({runtimes}); render_tensor needs exactly one")
+    _one_runtime_seen = True
+
+
+def _frame_tensor_row_bytes(out, fmt: int, W: int, H: int, device: int) -> int:
+    """Validates a caller's output tensor for Scene.render_tensor and returns its row pitch in bytes (ValueError otherwise)."""
+    import torch
+
+    if not isinstance(out, torch.Tensor):
+        raise ValueError("out must be a torch tensor")
+    dtype, shape = (torch.uint8, (H, W, 4)) if fmt == 2 else (torch.float32, ((3, H, W) if fmt == 1 else (H, W, 3)))
+    if out.dtype != dtype:
+        raise ValueError(f"out has dtype {out.dtype}, format needs {dtype}")
+    if tuple(out.shape) != shape:
+        raise ValueError(f"out has shape {tuple(out.shape)}, format needs {shape}")
+    if out.device.type != "cuda" or out.device.index != device:
+        raise ValueError(f"out is on {out.device}, the scene on cuda:{device}")
+    st, es = out.stride(), out.element_size()
+    if fmt == 1:  # (3, H, W): (H * s, s, 1); the plane stride is H rows
+        s = st[1] if H > 1 else st[0]
+        ok, pitched = (st[2] == 1 or W == 1) and st[0] == H * s, True
+    else:  # (H, W, 3 | 4): (s, 3 | 4, 1); one row has no pitch
+        s = st[0]
+        ok, pitched = st[2] == 1 and (st[1] == shape[2] or W == 1), H > 1
+    row_bytes = s * es
+    if not ok or out.data_ptr() % 4 or (pitched and (row_bytes < W * (12 if fmt == 0 else 4) or row_bytes % 4)):
+        raise ValueError(f"out's strides {st} (or its alignment) do not fit the format's row layout")
+    return row_bytes if pitched else 0
 
 
 def unit_vector_table(n: int = 1 << 16, seed: int = 0) -> np.ndarray:
@@ -522,6 +605,52 @@ class Scene:
             _check(lib().cgrt_render_aa(self._h, C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, rank, nranks, _ptr(rgb), C.byref(st)))
         return rgb, {k: getattr(st, k) for k, _ in st._fields_}
 
+    def render_device(self, cam, W: int, H: int, d_out_ptr: int, format="rgb", row_bytes: int = 0, stream: int = 0, aa: bool = False,
+                      lights=None, max_level: int = 2, spherical=None, units=None, samples: int = 200, seed: int = 0, rank: int = 0,
+                      nranks: int = 1) -> dict:
+        """cgrt_render_device: the frame of render_soft (aa=False) / render_aa (aa=True) written by a device kernel into the device buffer
+        at d_out_ptr (format "rgb" (H, W, 3) f32, "chw" (3, H, W) f32 or "rgba8" (H, W, 4) u8 flipped; row_bytes 0 = packed), enqueued on
+        the hipStream_t `stream` (0 = default stream).  Raw integers, as trace_primary_device.  Returns the stats dict."""
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        st = RenderStats()
+        q = None
+        if spherical is not None:
+            spherical, units = _f32(spherical, (-1, 7)), _f32(units, (-1, 3))
+            q = C.byref(SoftShadows(spherical.ctypes.data, units.ctypes.data, len(spherical), samples, len(units), seed, 0))
+        c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
+        _check(
+            lib().cgrt_render_device(
+                self._h, C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, 1 if aa else 0, rank, nranks,
+                C.c_void_p(d_out_ptr) if d_out_ptr else None, _frame_format(format), int(row_bytes), C.c_void_p(stream) if stream else None,
+                C.byref(st),
+            )
+        )  # fmt: skip
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def render_tensor(self, cam, W: int, H: int, format="rgb", out=None, stream=None, **kw):
+        """render_device into a torch tensor: (H, W, 3) f32, (3, H, W) f32 or (H, W, 4) u8 on cuda:<device> -- `out` (any row stride, e.g.
+        a slice of a larger canvas; validated before any call, ValueError) or a new tensor (zeros when nranks > 1), rendered on `stream`
+        (default: torch.cuda.current_stream()).  Other keywords as render_device.  Returns (tensor, stats dict).
+        Import torch before the library is first used (lib()): torch then brings the one HIP runtime both use; the other way round
+        torch finds no device."""
+        import torch
+
+        fmt = _frame_format(format)
+        row_bytes = 0
+        if out is not None:
+            row_bytes = _frame_tensor_row_bytes(out, fmt, W, H, self.device)
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        _check_one_hip_runtime()
+        if out is None:
+            shape, dtype = {0: ((H, W, 3), torch.float32), 1: ((3, H, W), torch.float32), 2: ((H, W, 4), torch.uint8)}[fmt]
+            with torch.cuda.stream(stream):  # (allocated, and zeroed, on the stream the frame is exported on)
+                out = (torch.zeros if kw.get("nranks", 1) > 1 else torch.empty)(shape, dtype=dtype, device=dev)
+        st = self.render_device(cam, W, H, out.data_ptr(), format=fmt, row_bytes=row_bytes, stream=stream.cuda_stream, **kw)
+        return out, st
+
     def generate_rays(self, cam, W: int, H: int, rect=None) -> np.ndarray:
         x0, y0, x1, y1 = rect if rect is not None else (0, 0, W, H)
         rays = np.zeros((x1 - x0) * (y1 - y0), RAY_DTYPE)
@@ -595,6 +724,22 @@ def render_multi_aa(scenes, cam, W: int, H: int, lights=None, max_level: int = 2
     c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
     _check(lib().cgrt_render_multi_aa(arr, len(scenes), C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, _ptr(rgb), C.byref(st)))
     return rgb, {k: getattr(st, k) for k, _ in st._fields_}
+
+
+def debug_export_frame(rgb, W: int, H: int, format="rgb", row_bytes: int = 0, out: Optional[np.ndarray] = None, device: int = 0) -> np.ndarray:
+    """cgrt_debug_export_frame: the export kernel of render_device on the given float frame ((W*H, 3)).  `out` (uint8, at least the bytes
+    the format and row_bytes span; zeros by default) is uploaded, exported into and returned: bytes the export does not write keep their
+    values.  Returns the raw bytes."""
+    fmt = _frame_format(format)
+    rgb = _f32(rgb, (W * H, 3))
+    row = W * (12 if fmt == 0 else 4)
+    pitch = row_bytes or row
+    n = pitch * ((3 * H if fmt == 1 else H) - 1) + row
+    out = np.zeros(n, np.uint8) if out is None else out
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError(f"out must be a contiguous uint8 array of at least {n} bytes")
+    _check(lib().cgrt_debug_export_frame(device, _ptr(rgb), W, H, fmt, int(row_bytes), _ptr(out)))
+    return out
 
 
 def resolve_aa(sub: np.ndarray, W: int, H: int) -> np.ndarray:

@@ -294,6 +294,11 @@ struct CgrtScene {
         SpawnDev spawn_host{};           // what the workspace's SpawnDev (fused level-0 spawn of predicted frames) holds
         bool spawn_valid = false;
     } raux;
+    // cgrt_render_device: its export kernel reads the frame (work slot 15, or 30 with aa) on the CALLER's stream after the call has
+    // returned.  This event is recorded behind it, and the next cgrt_render* call on the scene makes every stream it uses wait on it
+    // (and waits for it on the host before it reallocates those buffers); the caller's stream handle itself is never kept.
+    hipEvent_t export_done = nullptr;
+    bool export_pending = false;  // recorded, and no later frame has waited for it yet
     // What the previous cgrt_render* frame of this shape found, per level (entries of the level's compact list): the next frame's
     // launches are sized from it and issued WITHOUT waiting for the device to say how many primary rays hit (render_impl).
     struct RenderPred {
@@ -307,6 +312,8 @@ struct CgrtScene {
     ~CgrtScene() {
         if (device < 0) return;
         (void)hipSetDevice(device);
+        if (export_pending) (void)hipEventSynchronize(export_done);  // (an export may still be reading the workspace)
+        if (export_done) (void)hipEventDestroy(export_done);
         for (void* p : {d_records, d_leaves, d_tri_normals, d_spheres, d_materials, d_tri_leaf, d_paths, (void*)d_queues, hints.mem})
             if (p) (void)hipFree(p);
         if (hints.mailbox) (void)hipHostFree(hints.mailbox);
@@ -1669,10 +1676,18 @@ int cgrt_count_batch(CgrtScene* s, const CgrtRay* rays, uint64_t n, CgrtCounters
 // aa: the reference's antiAliasing branch (main.cpp:663-687): the wavefront shades the 2W x 2H sub-sample frame, ranks own its
 // 64x64 super-tiles (32x32 pixel blocks of the W x H frame), k_resolve_aa writes the W x H frame on the device and only that comes
 // down (nranks > 1: only this rank's pixels, packed).  The caller has checked the arguments (aa_args).
+// dout (cgrt_render_device, instead of rgb / mapped): nothing comes down; k_export_frame writes this rank's pixels of the W x H frame
+// into the caller's device buffer on the caller's stream (behind the frame, and behind whatever the caller queued there before).
+struct DeviceOut {
+    void* p;
+    int format;        // CGRT_FRAME_*
+    uint64_t pitch;    // bytes from row to row (never 0 here)
+    hipStream_t stream;
+};
 static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats, CgrtCounters* counted = nullptr,
-                       const float** mapped = nullptr, bool aa = false) {
-    if (!s || !cam || (!rgb && !mapped) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
+                       const float** mapped = nullptr, bool aa = false, const DeviceOut* dout = nullptr) {
+    if (!s || !cam || (!rgb && !mapped && !dout) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);
     if (W <= 0 || H <= 0 || max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad frame size or recursion depth");
     const unsigned SL = soft ? soft->nspherical : 0;
@@ -1713,6 +1728,13 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         cw_shadow = cw_primary + 8;
         cw_mirror = cw_primary + 16;
     }
+    const int packed = aa && nranks > 1;
+    const size_t res_bytes = packed ? (size_t)F.nst_rank * 1024 * 12 : (size_t)PW * PH * 12;  // the resolved frame (aa)
+    const size_t dres_bytes = std::max<size_t>(res_bytes, (size_t)F.nst_rank * 1024 * 12);
+    // A cgrt_render_device export of an earlier frame may still be reading drgb / dres on its caller's stream: the frame's streams wait
+    // for it below, and a buffer that has to grow (hipFree) is not taken from under it.
+    const bool after_export = s->export_pending;
+    if (after_export && (s->work[15].cap < npix * 12 || (aa && s->work[30].cap < dres_bytes))) HIP_TRY(hipEventSynchronize(s->export_done));
     HIP_TRY(dspawn.alloc(sizeof(SpawnDev)));
     HIP_TRY(ipix.alloc(n * 4));  // pixels of level 0, kept to the end
     for (int k = 0; k < 3; k++) {
@@ -1730,9 +1752,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     HIP_TRY(dlights.alloc((size_t)L * 24));
     HIP_TRY(levels.alloc((size_t)(max_level > 0 ? max_level : 1) * n * 32));
     HIP_TRY(drgb.alloc(npix * 12));
-    const int packed = aa && nranks > 1;
-    const size_t res_bytes = packed ? (size_t)F.nst_rank * 1024 * 12 : (size_t)PW * PH * 12;  // the resolved frame (aa)
-    if (aa) HIP_TRY(dres.alloc(std::max<size_t>(res_bytes, (size_t)F.nst_rank * 1024 * 12)));
+    if (aa) HIP_TRY(dres.alloc(dres_bytes));
     // (k_resolve_aa's grid covers whole 32x32 blocks; threads outside the frame write nothing)
     auto resolve = [&](hipStream_t on) { return aa ? launch_resolve_aa(F, drgb.as<float>(), dres.as<float>(), packed, on) : hipSuccess; };
     const size_t nctr = 4 * (size_t)(max_level + 1);
@@ -1773,6 +1793,8 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipEventCreate(&aux.e1));
         HIP_TRY(hipHostMalloc((void**)&aux.pin_counts, 64, hipHostMallocDefault));
     }
+    if (after_export)  // (every stream of the frame, before its first write; a no-op once the export has run)
+        for (hipStream_t st : {(hipStream_t) nullptr, aux.s, aux.copy}) HIP_TRY(hipStreamWaitEvent(st, s->export_done, 0));
     const float* const mats = static_cast<const float*>(s->d_materials);
     uint32_t* const primary_hits = dctr.as<uint32_t>() + 4 * (size_t)max_level + 3;
     auto ctr_of = [&](int level) { return dctr.as<uint32_t>() + 4 * (size_t)level; };
@@ -2099,7 +2121,29 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         const int erc = exact();
         if (erc != CGRT_OK) return erc;
     }
-    {
+    if (after_export) s->export_pending = false;  // aux.e1, which this call has waited for, is behind it
+    if (dout) {
+        // The frame's last kernel is done (aux.e1 was waited for); the wait below only makes that ordering explicit on the caller's stream.
+        ExportDev E{};
+        E.src = aa ? dres.as<float>() : drgb.as<float>();
+        E.dst = static_cast<unsigned char*>(dout->p);
+        E.pitch = dout->pitch;
+        E.W = PW;
+        E.H = PH;
+        E.format = dout->format;
+        if (nranks > 1) {  // super-tiles of the frame, or (aa) 32x32 blocks = super-tiles of the sub-sample frame; F.st_x counts either
+            E.tile = aa ? 32 : 64;
+            E.tiles_x = F.st_x;
+            E.rank = rank;
+            E.nranks = nranks;
+            E.packed = packed;
+        }
+        if (!s->export_done) HIP_TRY(hipEventCreateWithFlags(&s->export_done, hipEventDisableTiming));
+        HIP_TRY(hipStreamWaitEvent(dout->stream, aux.e1, 0));
+        HIP_TRY(launch_export_frame(E, dout->stream));
+        HIP_TRY(hipEventRecord(s->export_done, dout->stream));
+        s->export_pending = true;
+    } else {
         const size_t bytes = aa ? res_bytes : (size_t)npix * 12;
         if (s->pin_frame_cap < bytes) {
             if (s->pin_frame) (void)hipHostFree(s->pin_frame);
@@ -2194,6 +2238,96 @@ int cgrt_render_aa_mapped(CgrtScene* s, const CgrtCamera* cam, int W, int H, con
     if (rc) return rc;
     NEED_DEVICE(s);
     return render_impl(s, cam, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, rgb, true);
+}
+
+// The frame export's own arguments (cgrt_render_device, cgrt_debug_export_frame; W, H > 0 already checked): *pitch = the row pitch,
+// *extent = bytes from out to one past the last byte the export may write.
+static int export_args(const void* out, int W, int H, int format, uint64_t row_bytes, uint64_t* pitch, uint64_t* extent) {
+    const uint64_t row = format == CGRT_FRAME_RGB_F32 ? 12ull * (uint64_t)W
+                         : (format == CGRT_FRAME_CHW_F32 || format == CGRT_FRAME_RGBA8) ? 4ull * (uint64_t)W : 0;
+    if (!row) return fail(CGRT_E_ARG, "unknown frame format");
+    if (row_bytes && (row_bytes < row || row_bytes % 4)) return fail(CGRT_E_ARG, "row_bytes must be 0 or a multiple of 4 of at least the packed row");
+    if ((uintptr_t)out % 4) return fail(CGRT_E_ARG, "the output buffer is not 4-byte aligned");
+    const uint64_t p = row_bytes ? row_bytes : row, rows = (format == CGRT_FRAME_CHW_F32 ? 3ull : 1ull) * (uint64_t)H;
+    if ((unsigned __int128)p * rows > ((unsigned __int128)1 << 62)) return fail(CGRT_E_ARG, "row_bytes too large");
+    *pitch = p;
+    *extent = p * (rows - 1) + row;
+    return CGRT_OK;
+}
+
+int cgrt_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                       int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
+                       CgrtRenderStats* stats) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    if (aa) {
+        const int rc = aa_args(cam, d_out, W, H, lights, nlights, soft, max_level, rank, nranks);
+        if (rc) return rc;
+    } else {
+        if (!cam || !d_out) return fail(CGRT_E_ARG, "NULL argument");
+        if (nlights && !lights) return fail(CGRT_E_ARG, "nlights > 0 but lights is NULL");
+        if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+        if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
+        if (nranks <= 0 || rank < 0 || rank >= nranks) return fail(CGRT_E_ARG, "bad rank / nranks");
+        if (soft && soft->nspherical) {
+            if (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24))
+                return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
+            if ((unsigned long long)W * H > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large");
+        }
+    }
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream)};
+    uint64_t extent = 0;
+    const int rc = export_args(d_out, W, H, format, row_bytes, &D.pitch, &extent);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    // d_out .. d_out + extent must be device memory of the scene's device: one allocation, or several that follow one another in the
+    // address space (a caching allocator that maps its pool in pieces through the virtual-memory API, e.g. torch's expandable
+    // segments), each checked.  A pointer this HIP runtime does not know (another copy of the runtime in the process, host memory) is
+    // refused here, before any work.
+    uintptr_t at = (uintptr_t)d_out;
+    const uintptr_t end = at + extent;
+    for (int piece = 0; at < end; piece++) {
+        if (piece == 65536) return fail(CGRT_E_ARG, "d_out spans too many separate allocations");
+        hipPointerAttribute_t pa{};
+        if (hipPointerGetAttributes(&pa, reinterpret_cast<void*>(at)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(CGRT_E_ARG, piece ? "d_out's allocation is smaller than the frame" : "d_out is not memory of this process's HIP runtime");
+        }
+        if (pa.type != hipMemoryTypeDevice || pa.device != s->device) return fail(CGRT_E_ARG, "d_out is not device memory of the scene's device");
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, reinterpret_cast<hipDeviceptr_t>(at)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(CGRT_E_ARG, "d_out: no device allocation found");
+        }
+        if ((uintptr_t)base + size <= at) return fail(CGRT_E_ARG, "d_out: no device allocation found");
+        at = (uintptr_t)base + size;
+    }
+    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, nullptr, stats, nullptr, nullptr, aa != 0, &D);
+}
+
+int cgrt_debug_export_frame(int device, const float* rgb, int W, int H, int format, uint64_t row_bytes, void* out) {
+    if (!rgb || !out) return fail(CGRT_E_ARG, "NULL argument");
+    if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+    uint64_t pitch = 0, extent = 0;
+    int rc = export_args(out, W, H, format, row_bytes, &pitch, &extent);
+    if (rc) return rc;
+    if ((rc = select_device(device)) != CGRT_OK) return rc;
+    DevBuf src, dst;
+    HIP_TRY(src.alloc((size_t)W * H * 12));
+    HIP_TRY(dst.alloc(extent));
+    HIP_TRY(hipMemcpy(src.p, rgb, (size_t)W * H * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dst.p, out, extent, hipMemcpyHostToDevice));  // (bytes the export must not touch come back as they were)
+    ExportDev E{};
+    E.src = src.as<float>();
+    E.dst = dst.as<unsigned char>();
+    E.pitch = pitch;
+    E.W = W;
+    E.H = H;
+    E.format = format;
+    HIP_TRY(launch_export_frame(E, nullptr));
+    HIP_TRY(hipMemcpy(out, dst.p, extent, hipMemcpyDeviceToHost));
+    return CGRT_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

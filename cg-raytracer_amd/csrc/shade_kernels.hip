@@ -242,7 +242,77 @@ __global__ void k_resolve_aa(FrameDev F, const float* __restrict__ sub, float* _
     out[3 * o + 2] = b / d;
 }
 
+// Screen::writeBitmapToFile's conversion of one channel (screen.cpp:38-49): clamp to [0, 1], * 255.0f, truncated to u8.  NaN (upstream:
+// undefined behaviour of the cast) -> 0: both comparisons are false for it.
+__device__ __forceinline__ unsigned to_u8(float v) {
+    const float c = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
+    return (unsigned)(c * 255.0f);  // (an f32 product, converted toward zero: v_cvt_u32_f32)
+}
+__device__ __forceinline__ unsigned rgba8(float r, float g, float b) { return to_u8(r) | (to_u8(g) << 8) | (to_u8(b) << 16) | 0xff000000u; }
+
+// cgrt_render_device's export: one thread per 4 consecutive pixels of a row -- three float4 loads, then one 16-B store (RGBA8), one
+// float4 store per plane (CHW) or three float4 stores (RGB_F32).  Row ends and bases that are not 16-B aligned (W % 4 != 0, pitches
+// that are not multiples of 16) take the scalar path.  Tiles are multiples of 4 pixels wide, so the 4 pixels share an owner.
+__global__ __launch_bounds__(256) void k_export_frame(ExportDev E) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long G = (unsigned long long)((E.W + 3) >> 2);  // 4-pixel groups per row
+    const unsigned long long yl = t / G;
+    if (yl >= (unsigned long long)E.H) return;
+    const int y = (int)yl, x0 = (int)(t - yl * G) * 4;
+    const int n = E.W - x0 < 4 ? E.W - x0 : 4;
+    unsigned long long sp = (unsigned long long)y * (unsigned long long)E.W + (unsigned long long)x0;  // source pixel of x0
+    if (E.tile) {
+        const unsigned long long k = (unsigned long long)(y / E.tile) * (unsigned long long)E.tiles_x + (unsigned long long)(x0 / E.tile);
+        if (k % (unsigned long long)E.nranks != (unsigned long long)E.rank) return;
+        if (E.packed) sp = ((k / (unsigned long long)E.nranks) << 10) + (unsigned long long)((y & 31) * 32 + (x0 & 31));
+    }
+    const float* s = E.src + 3ull * sp;
+    float v[12];
+    if (n == 4 && ((uintptr_t)s & 15u) == 0) {
+        const float4 a = reinterpret_cast<const float4*>(s)[0], b = reinterpret_cast<const float4*>(s)[1], c = reinterpret_cast<const float4*>(s)[2];
+        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w, v[8] = c.x, v[9] = c.y, v[10] = c.z, v[11] = c.w;
+    } else {
+        for (int i = 0; i < 12; i++) v[i] = i < 3 * n ? s[i] : 0.0f;
+    }
+    if (E.format == 2) {  // RGBA8: row H-1-y (Screen::setPixel's flip)
+        unsigned char* d = E.dst + (unsigned long long)(E.H - 1 - y) * E.pitch + 4ull * (unsigned long long)x0;
+        const unsigned p0 = rgba8(v[0], v[1], v[2]), p1 = rgba8(v[3], v[4], v[5]), p2 = rgba8(v[6], v[7], v[8]), p3 = rgba8(v[9], v[10], v[11]);
+        if (n == 4 && ((uintptr_t)d & 15u) == 0) {
+            *reinterpret_cast<uint4*>(d) = make_uint4(p0, p1, p2, p3);
+        } else {
+            const unsigned p[4] = {p0, p1, p2, p3};
+            for (int i = 0; i < n; i++) reinterpret_cast<unsigned*>(d)[i] = p[i];
+        }
+    } else if (E.format == 1) {  // CHW: plane c, row y
+        for (int c = 0; c < 3; c++) {
+            float* d = reinterpret_cast<float*>(E.dst + ((unsigned long long)c * (unsigned long long)E.H + (unsigned long long)y) * E.pitch) + x0;
+            if (n == 4 && ((uintptr_t)d & 15u) == 0) {
+                *reinterpret_cast<float4*>(d) = make_float4(v[c], v[3 + c], v[6 + c], v[9 + c]);
+            } else {
+                for (int i = 0; i < n; i++) d[i] = v[3 * i + c];
+            }
+        }
+    } else {  // RGB_F32
+        float* d = reinterpret_cast<float*>(E.dst + (unsigned long long)y * E.pitch) + 3 * x0;
+        if (n == 4 && ((uintptr_t)d & 15u) == 0) {
+            reinterpret_cast<float4*>(d)[0] = make_float4(v[0], v[1], v[2], v[3]);
+            reinterpret_cast<float4*>(d)[1] = make_float4(v[4], v[5], v[6], v[7]);
+            reinterpret_cast<float4*>(d)[2] = make_float4(v[8], v[9], v[10], v[11]);
+        } else {
+            for (int i = 0; i < 3 * n; i++) d[i] = v[i];
+        }
+    }
+}
+
 static inline unsigned grid_for(unsigned long long n, unsigned block) { return (unsigned)((n + block - 1) / block); }
+
+hipError_t launch_export_frame(const ExportDev& E, hipStream_t s) {
+    const unsigned long long n = (unsigned long long)((E.W + 3) / 4) * (unsigned long long)E.H;
+    if (n == 0) return hipSuccess;
+    if ((n + 255) / 256 > 0xffffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_export_frame, dim3(grid_for(n, 256)), dim3(256), 0, s, E);
+    return hipGetLastError();
+}
 
 hipError_t launch_spawn(const float* rays, const CgrtHitDev* hits, const float* normals, const int* pixels, unsigned long long n,
                         const float* materials, const float* lights, unsigned nlights, int spawn, float* srays, float* sdist, int* sslot,

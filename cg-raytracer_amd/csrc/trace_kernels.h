@@ -89,6 +89,18 @@ hipError_t launch_write_rgb(const float* lvl0, const float* child_lvl, unsigned 
 // the anti-aliased frame (main.cpp:663-687) from the 2W x 2H sub-sample frame `sub` of F: see k_resolve_aa (shade_kernels.hip).
 // out: F.nst_rank * 1024 * 3 floats (packed) or (F.W / 2) * (F.H / 2) * 3 floats
 hipError_t launch_resolve_aa(const FrameDev& F, const float* sub, float* out, int packed, hipStream_t s);
+// cgrt_render_device's export (k_export_frame, shade_kernels.hip): the W x H float frame `src` into the caller's buffer in one of the
+// CGRT_FRAME_* formats of include/cgrt.h.  tile = 0: every pixel is written; otherwise only pixels whose tile x tile block index
+// (row-major, tiles_x per row) % nranks == rank.  packed (tile 32 only): src holds this rank's blocks back to back, as k_resolve_aa
+// writes them with packed = 1 (block slot k / nranks, 1024 pixels each).  dst is 4-byte aligned, pitch a multiple of 4.
+struct ExportDev {
+    const float* src;
+    unsigned char* dst;
+    unsigned long long pitch;  // bytes from one row of dst to the next (CHW: plane stride pitch * H)
+    int W, H, format;
+    int tile, tiles_x, rank, nranks, packed;
+};
+hipError_t launch_export_frame(const ExportDev& E, hipStream_t s);
 hipError_t launch_gather_calib(const void* table, unsigned long long nrecords, unsigned long long mult, unsigned long long add, float* sink,
                                hipStream_t s);
 hipError_t launch_fastdiv_check(const float* a, const float* d, unsigned long long n, unsigned long long* mismatches, float* first_bad,

@@ -327,6 +327,37 @@ int cgrt_render_aa_mapped(CgrtScene* scene, const CgrtCamera* cam, int W, int H,
 int cgrt_render_multi_aa(CgrtScene* const* scenes, int nscenes, const CgrtCamera* cam, int W, int H, const float* lights,
                          uint32_t nlights, const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats);
 
+/* Shaded frames straight into DEVICE memory: the frame of cgrt_render_soft (aa = 0) or cgrt_render_aa (aa != 0) -- same wavefront,
+ * same prediction, same soft-shadow hashing, same stats (device_ms does not include the export) -- is not downloaded; a device
+ * kernel (k_export_frame) writes it into d_out in one of these formats: */
+#define CGRT_FRAME_RGB_F32 0 /* W*H*3 f32, element (y*W + x)*3 + c: the bytes cgrt_render / cgrt_render_aa return */
+#define CGRT_FRAME_CHW_F32 1 /* 3 planes of H rows x W f32 (torch's (3, H, W)): plane c, row y, column x = the same value */
+#define CGRT_FRAME_RGBA8 2   /* the reference's 8-bit screen image (screen.cpp:30-49): row H-1-y (Screen::setPixel's flip), bytes R, G, B, */
+                             /* 255, each (uint8_t)(min(max(v, 0.0f), 1.0f) * 255.0f) -- truncation; a NaN channel gives 0          */
+/* The float formats hold the bit patterns of cgrt_render_soft / cgrt_render_aa.
+ * row_bytes: 0 = packed rows; otherwise the distance between rows (at least the packed row, a multiple of 4; CHW: the plane stride is
+ * row_bytes * H).  Padding bytes are never written.  d_out: device memory of the scene's device, 4-byte aligned.
+ * rank/nranks: the ownership rule of cgrt_render_rank (64x64 super-tiles), or with aa that of cgrt_render_aa (32x32-pixel blocks of
+ * the W x H frame); only owned pixels are written, so the ranks' outputs merge into exactly the single-rank output.
+ * Stream: the call blocks until the frame's kernels are done (level sizing reads counts on the host, as in cgrt_render) and returns
+ * with the export ENQUEUED on `stream` (a hipStream_t of the scene's device, NULL = default stream): work the caller enqueues on
+ * `stream` afterwards sees the frame, and the export runs after everything the caller enqueued there before the call.  The export
+ * reads the scene's workspace: the scene records an event of its own behind it, which every stream of the next cgrt_render* frame on
+ * the scene waits for before writing that workspace (and which cgrt_scene_destroy waits for); the stream handle is not kept.
+ * Arguments are checked in the order of cgrt_render_aa: NULL scene / cam / d_out, nlights > 0 with lights NULL, W or H <= 0, (aa)
+ * 4*W*H > 0x7fffffff, max_level outside 0..16, bad rank / nranks, bad soft, unknown format, bad row_bytes, d_out not 4-byte aligned
+ * -> CGRT_E_ARG; then a host-only scene -> CGRT_E_NO_DEVICE; then the bytes the frame spans from d_out not all device memory of the
+ * scene's device -- one allocation, or allocations that follow one another in the address space (a pool mapped in pieces, such as
+ * torch's expandable segments) -- (hipPointerGetAttributes, hipMemGetAddressRange: a pointer of another HIP runtime in the process
+ * fails here too) -> CGRT_E_ARG, before the frame is rendered. */
+int cgrt_render_device(CgrtScene* scene, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights,
+                       const CgrtSoftShadows* soft, int max_level, int aa, int rank, int nranks, void* d_out, int format,
+                       uint64_t row_bytes, void* stream, CgrtRenderStats* stats);
+/* Diagnostic: the export kernel of cgrt_render_device on a frame the caller supplies.  Host pointers: rgb (W*H*3 f32) is uploaded,
+ * `out` (as many bytes as the format and row_bytes span) is uploaded too, every pixel is exported on device `device` and `out` comes
+ * back -- bytes the export does not write keep their values.  Synchronous. */
+int cgrt_debug_export_frame(int device, const float* rgb, int W, int H, int format, uint64_t row_bytes, void* out);
+
 /* Work counters of the same traversal (separate instrumented launch; not part of any timed region). */
 int cgrt_count_primary(CgrtScene* scene, const CgrtCamera* cam, int W, int H, int x0, int y0, int x1, int y1,
                        int rank, int nranks, CgrtCounters* out);
