@@ -108,7 +108,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -178,6 +178,8 @@ def lib() -> C.CDLL:
     L.cgrt_render_device.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, i32, i32, i32, vp, i32, u64, vp,
                                      C.POINTER(RenderStats)]
     L.cgrt_debug_export_frame.argtypes = [i32, vp, i32, i32, i32, u64, vp]
+    L.cgrt_shade_rays.argtypes = [vp, vp, u64, vp, u32, C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
+    L.cgrt_shade_rays_device.argtypes = [vp, vp, u64, vp, u32, C.POINTER(SoftShadows), i32, vp, vp, C.POINTER(RenderStats)]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
     L.cgrt_count_batch.argtypes = [vp, vp, u64, C.POINTER(Counters)]
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
@@ -651,6 +653,76 @@ class Scene:
         st = self.render_device(cam, W, H, out.data_ptr(), format=fmt, row_bytes=row_bytes, stream=stream.cuda_stream, **kw)
         return out, st
 
+    def _soft_arg(self, spherical, units, samples: int, seed: int):
+        """The CgrtSoftShadows argument (None without spherical lights) and the arrays it points into, which the caller keeps alive."""
+        if spherical is None:
+            return None, ()
+        spherical, units = _f32(spherical, (-1, 7)), _f32(units, (-1, 3))
+        return C.byref(SoftShadows(spherical.ctypes.data, units.ctypes.data, len(spherical), samples, len(units), seed, 0)), (spherical, units)
+
+    def shade_rays(self, rays, lights=None, max_level: int = 2, spherical=None, units=None, samples: int = 200, seed: int = 0):
+        """cgrt_shade_rays: getFinalColor (main.cpp:298-310) of each of the caller's rays (a RAY_DTYPE array or (n, 7) float32 {origin,
+        direction, t}), recursion cut at max_level; spherical lights as render_soft, sample smp of ray i hashed with pixel i.
+        Returns (rgb[n, 3], stats dict)."""
+        r = _as_ray_array(rays)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841  (keep: the arrays q points into)
+        rgb = np.zeros((len(r), 3), np.float32)
+        st = RenderStats()
+        _check(lib().cgrt_shade_rays(self._h, _ptr(r), len(r), _ptr(lights), len(lights), q, max_level, _ptr(rgb), C.byref(st)))
+        return rgb, {k: getattr(st, k) for k, _ in st._fields_}
+
+    def shade_rays_device(self, d_rays_ptr: int, n: int, d_rgb_ptr: int, stream: int = 0, lights=None, max_level: int = 2, spherical=None,
+                          units=None, samples: int = 200, seed: int = 0) -> dict:
+        """cgrt_shade_rays_device: n rays (7 floats each) at d_rays_ptr shaded into n x 3 floats at d_rgb_ptr, ordered on the hipStream_t
+        `stream` (0 = default stream).  Raw integers, as render_device.  Returns the stats dict."""
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        st = RenderStats()
+        _check(
+            lib().cgrt_shade_rays_device(
+                self._h, C.c_void_p(d_rays_ptr) if d_rays_ptr else None, int(n), _ptr(lights), len(lights), q, max_level,
+                C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None, C.c_void_p(stream) if stream else None, C.byref(st),
+            )
+        )  # fmt: skip
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def shade_rays_tensor(self, rays, out=None, stream=None, **kw):
+        """shade_rays on torch tensors: rays (..., 7) float32, contiguous, on cuda:<device> -> colours (..., 3) float32, e.g. (H, W, 7)
+        rays give an (H, W, 3) image.  Into `out` (validated before any call, ValueError, as render_tensor validates its output) or a new
+        tensor, ordered on `stream` (default: torch.cuda.current_stream()).  Other keywords as shade_rays.  Returns (tensor, stats dict)."""
+        import torch
+
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 7:
+            raise ValueError("rays must be a torch tensor of shape (..., 7)")
+        if rays.dtype != torch.float32:
+            raise ValueError(f"rays has dtype {rays.dtype}, needs torch.float32")
+        if rays.device.type != "cuda" or rays.device.index != self.device:
+            raise ValueError(f"rays is on {rays.device}, the scene on cuda:{self.device}")
+        if not rays.is_contiguous():
+            raise ValueError("rays must be contiguous")
+        n = rays.numel() // 7
+        shape = tuple(rays.shape[:-1]) + (3,)
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape:
+                raise ValueError(f"out must be a torch tensor of shape {shape}")
+            if not out.is_contiguous():
+                raise ValueError("out must be contiguous")
+            if n:  # render_tensor's check of an (H, W, 3) f32 frame: dtype, device, strides, alignment
+                _frame_tensor_row_bytes(out.view(1, n, 3), FRAME_FORMATS["rgb"], n, 1, self.device)
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        _check_one_hip_runtime()
+        if out is None:
+            with torch.cuda.stream(stream):  # (allocated on the stream the colours are written on)
+                out = torch.empty(shape, dtype=torch.float32, device=dev)
+        if n == 0:  # (an empty tensor has no address to pass: the call would touch nothing anyway)
+            return out, {k: 0 for k, _ in RenderStats._fields_}
+        st = self.shade_rays_device(rays.data_ptr(), n, out.data_ptr(), stream=stream.cuda_stream, **kw)
+        return out, st
+
     def generate_rays(self, cam, W: int, H: int, rect=None) -> np.ndarray:
         x0, y0, x1, y1 = rect if rect is not None else (0, 0, W, H)
         rays = np.zeros((x1 - x0) * (y1 - y0), RAY_DTYPE)
@@ -837,6 +909,7 @@ def host_lib() -> C.CDLL:
         H.cgrt_host_threads_test.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, i32, vp]
         H.cgrt_host_render_bmp.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, i32, i32, i32, i32, C.c_char_p, vp]
         H.cgrt_host_render_aa.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, i32, i32, i32, i32, i32, C.c_char_p, vp, vp]
+        H.cgrt_host_shade_rays.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, u32, u32, vp, C.c_uint64, i32, i32, i32, vp, vp]
         _host = H
     return _host
 
@@ -984,6 +1057,28 @@ def host_render_aa(sd: SceneData, cam, W: int, H: int, max_level: int = 2, drive
     if rc:
         raise RuntimeError("cgrt_host_render_aa: " + Hl.cgrt_host_last_error().decode())
     return rgb, dict(primary=int(st[0]), shadow=int(st[1]), reflection=int(st[2]), seconds_device=float(st[3]), seconds_total=float(st[4]))
+
+
+def host_shade_rays(sd: SceneData, rays, max_level: int = 2, driver: str = "device", spherical=None, units=None, samples: int = 200,
+                    seed: int = 0, lights=None, threads: int = 0):
+    """getFinalColor of the caller's rays through the C++ mirror: "device" (getFinalColorsOnDevice -> cgrt_shade_rays) or "per_ray"
+    (getFinalColorsPerRay: the reference's recursion, one intersect per ray).  Returns (rgb[n,3], stats dict)."""
+    Hl = host_lib()
+    pn, tri = _f32(sd.pos_nrm, (-1, 6)), np.ascontiguousarray(sd.tri, np.uint32).reshape(-1, 3)
+    tm, mats = np.ascontiguousarray(sd.tri_mesh, np.uint32), _f32(sd.materials, (-1, 8))
+    lights = _f32(sd.point_lights if lights is None else lights, (-1, 6))
+    r = _as_ray_array(rays)
+    sph = _f32(np.zeros((0, 7)) if spherical is None else spherical, (-1, 7))
+    un = _f32(np.zeros((0, 3)) if units is None else units, (-1, 3))
+    rgb = np.zeros((len(r), 3), np.float32)
+    st = np.zeros(6, np.float64)
+    rc = Hl.cgrt_host_shade_rays(_ptr(pn), len(pn), _ptr(tri), _ptr(tm), len(tri), _ptr(mats), len(mats), _ptr(lights), len(lights),
+                                 _ptr(sph), len(sph), _ptr(un), len(un), samples, seed, _ptr(r), len(r), max_level,
+                                 {"device": 0, "per_ray": 1}[driver], threads, _ptr(rgb), _ptr(st))
+    if rc:
+        raise RuntimeError("cgrt_host_shade_rays: " + Hl.cgrt_host_last_error().decode())
+    return rgb, dict(primary=int(st[0]), shadow=int(st[1]), reflection=int(st[2]), soft_shadow=int(st[3]), seconds_device=float(st[4]),
+                     seconds_total=float(st[5]))
 
 
 def host_write_bmp(path: str, rgb, W: int, H: int) -> None:

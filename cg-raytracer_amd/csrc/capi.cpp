@@ -290,6 +290,7 @@ struct CgrtScene {
     struct RenderAux {
         hipStream_t s = nullptr, copy = nullptr;  // second traversal stream; read-backs that must not wait for queued kernels
         hipEvent_t spawned = nullptr, traced = nullptr, e0 = nullptr, e1 = nullptr, primary_done = nullptr;
+        hipEvent_t caller = nullptr;     // cgrt_shade_rays*: the frame's streams start behind what the caller's stream held
         uint32_t* pin_counts = nullptr;  // 64 pinned bytes for counter read-backs
         SpawnDev spawn_host{};           // what the workspace's SpawnDev (fused level-0 spawn of predicted frames) holds
         bool spawn_valid = false;
@@ -318,7 +319,7 @@ struct CgrtScene {
             if (p) (void)hipFree(p);
         if (hints.mailbox) (void)hipHostFree(hints.mailbox);
         if (pin_frame) (void)hipHostFree(pin_frame);
-        for (hipEvent_t e : {raux.spawned, raux.traced, raux.e0, raux.e1, raux.primary_done})
+        for (hipEvent_t e : {raux.spawned, raux.traced, raux.e0, raux.e1, raux.primary_done, raux.caller})
             if (e) (void)hipEventDestroy(e);
         for (hipStream_t st : {raux.s, raux.copy})
             if (st) (void)hipStreamDestroy(st);
@@ -1684,10 +1685,21 @@ struct DeviceOut {
     uint64_t pitch;    // bytes from row to row (never 0 here)
     hipStream_t stream;
 };
+// Level 0 from a caller's ray list instead of the camera's frame (cgrt_shade_rays*): n > 0 rays in device memory of the scene's device,
+// colours into rgb (n x 3 floats, device memory), both ordered on `stream`: the frame's work starts behind everything queued there
+// before the call, and the stream waits for the frame's end.  The rest of the frame -- the level loop, the fold, k_write_rgb and the
+// soft shadows -- is the camera frame's own; the list always takes the exactly sized path, and neither reads nor writes the scene's
+// prediction record or its frame hints.
+struct ListSrc {
+    const float* rays;
+    unsigned long long n;
+    float* rgb;
+    hipStream_t stream;
+};
 static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats, CgrtCounters* counted = nullptr,
-                       const float** mapped = nullptr, bool aa = false, const DeviceOut* dout = nullptr) {
-    if (!s || !cam || (!rgb && !mapped && !dout) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
+                       const float** mapped = nullptr, bool aa = false, const DeviceOut* dout = nullptr, const ListSrc* list = nullptr) {
+    if (!s || (!cam && !list) || (!rgb && !mapped && !dout && !list) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);
     if (W <= 0 || H <= 0 || max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad frame size or recursion depth");
     const unsigned SL = soft ? soft->nspherical : 0;
@@ -1703,12 +1715,13 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     }
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> one_frame(s->render_mutex);  // the workspace below belongs to one frame at a time
-    const unsigned long long npix = (unsigned long long)W * H;
+    const unsigned long long npix = list ? list->n : (unsigned long long)W * H;
     const unsigned L = nlights;
     CgrtRenderStats st{};
-    FrameDev F;
-    if (!make_frame(W, H, 0, 0, W, H, rank, nranks, trace_block(s->dev), F)) return fail(CGRT_E_ARG, "bad frame or rank");
-    const unsigned long long n = (unsigned long long)F.nblocks * (unsigned long long)F.block;  // items: this rank's part of the frame in the primary kernel's order
+    FrameDev F{};
+    if (!list && !make_frame(W, H, 0, 0, W, H, rank, nranks, trace_block(s->dev), F)) return fail(CGRT_E_ARG, "bad frame or rank");
+    // items: this rank's part of the frame in the primary kernel's order, or the caller's rays
+    const unsigned long long n = list ? list->n : (unsigned long long)F.nblocks * (unsigned long long)F.block;
     // Every level is a compact list: level 0 = the primary rays that hit, level l + 1 = the mirror rays of level l (at most
     // one per entry, so the number of primary hits bounds every list, and n bounds that); the shadow list of a level
     // holds at most entries * L rays.  hits/normals/rays/pixels alternate between two sets (a level's mirror batch is
@@ -1734,7 +1747,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     // A cgrt_render_device export of an earlier frame may still be reading drgb / dres on its caller's stream: the frame's streams wait
     // for it below, and a buffer that has to grow (hipFree) is not taken from under it.
     const bool after_export = s->export_pending;
-    if (after_export && (s->work[15].cap < npix * 12 || (aa && s->work[30].cap < dres_bytes))) HIP_TRY(hipEventSynchronize(s->export_done));
+    if (after_export && ((!list && s->work[15].cap < npix * 12) || (aa && s->work[30].cap < dres_bytes))) HIP_TRY(hipEventSynchronize(s->export_done));
     HIP_TRY(dspawn.alloc(sizeof(SpawnDev)));
     HIP_TRY(ipix.alloc(n * 4));  // pixels of level 0, kept to the end
     for (int k = 0; k < 3; k++) {
@@ -1751,7 +1764,8 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     }
     HIP_TRY(dlights.alloc((size_t)L * 24));
     HIP_TRY(levels.alloc((size_t)(max_level > 0 ? max_level : 1) * n * 32));
-    HIP_TRY(drgb.alloc(npix * 12));
+    if (!list) HIP_TRY(drgb.alloc(npix * 12));  // (a ray list's colours go straight into the caller's buffer)
+    float* const frame_rgb = list ? list->rgb : drgb.as<float>();
     if (aa) HIP_TRY(dres.alloc(dres_bytes));
     // (k_resolve_aa's grid covers whole 32x32 blocks; threads outside the frame write nothing)
     auto resolve = [&](hipStream_t on) { return aa ? launch_resolve_aa(F, drgb.as<float>(), dres.as<float>(), packed, on) : hipSuccess; };
@@ -1772,7 +1786,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         Q.nunits = soft->nunits;
         Q.seed = soft->seed;
     }
-    const CameraDev C = make_camera(*cam);
+    const CameraDev C = list ? CameraDev{} : make_camera(*cam);
     CgrtScene::RenderAux& aux = s->raux;  // second stream + the events that order it against the default stream
     if (!aux.pin_counts) {
         // The second stream carries the frame's critical path (level 0's mirror list, then all of level 1), the default stream the
@@ -1789,12 +1803,17 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipEventCreateWithFlags(&aux.spawned, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&aux.traced, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&aux.primary_done, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&aux.caller, hipEventDisableTiming));
         HIP_TRY(hipEventCreate(&aux.e0));
         HIP_TRY(hipEventCreate(&aux.e1));
         HIP_TRY(hipHostMalloc((void**)&aux.pin_counts, 64, hipHostMallocDefault));
     }
     if (after_export)  // (every stream of the frame, before its first write; a no-op once the export has run)
         for (hipStream_t st : {(hipStream_t) nullptr, aux.s, aux.copy}) HIP_TRY(hipStreamWaitEvent(st, s->export_done, 0));
+    if (list) {  // the rays were written on the caller's stream: every stream of the frame starts from the default stream, which waits here
+        HIP_TRY(hipEventRecord(aux.caller, list->stream));
+        HIP_TRY(hipStreamWaitEvent(nullptr, aux.caller, 0));
+    }
     const float* const mats = static_cast<const float*>(s->d_materials);
     uint32_t* const primary_hits = dctr.as<uint32_t>() + 4 * (size_t)max_level + 3;
     auto ctr_of = [&](int level) { return dctr.as<uint32_t>() + 4 * (size_t)level; };
@@ -1811,7 +1830,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     bool frame_done = false;
     CgrtScene::RenderPred& P = s->rpred;
     const bool predictable = g_render_predict.load() && P.valid && P.W == W && P.H == H && P.rank == rank && P.nranks == nranks &&
-                             P.max_level == max_level && P.L == L && !P.counts.empty() && SL == 0 && !counted && max_level >= 1;
+                             P.max_level == max_level && P.L == L && !P.counts.empty() && SL == 0 && !counted && max_level >= 1 && !list;
     auto predicted = [&]() -> int {
         const int np = (int)P.counts.size();  // levels the previous frame evaluated (P.counts[l] > 0 entries each)
         // {level 0's entries, level 1's entries}: one 64-bit word, filled by the primary kernel's fused spawn with one atomic
@@ -1965,9 +1984,15 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         if (max_level >= 1) {  // trace(level 0): main.cpp:267 returns black without tracing when level >= maxLevel
             // level 0 = the primary rays that hit something, straight out of the fused primary kernel (pixels that miss are
             // black, main.cpp:293, and spawn nothing)
-            HIP_TRY(launch_trace_primary_compact(s->dev, C, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
-                                                 ipix.as<int>(), primary_hits, nullptr, cw_primary, drgb.as<float>()));  // (also clears this rank's pixels)
-            st.primary_rays = owned_pixels(F);
+            if (list) {  // (also clears the list's colours)
+                HIP_TRY(launch_trace_list_compact(s->dev, list->rays, n, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
+                                                  ipix.as<int>(), primary_hits, frame_rgb, nullptr, cw_primary));
+                st.primary_rays = n;
+            } else {
+                HIP_TRY(launch_trace_primary_compact(s->dev, C, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
+                                                     ipix.as<int>(), primary_hits, nullptr, cw_primary, frame_rgb));  // (also clears this rank's pixels)
+                st.primary_rays = owned_pixels(F);
+            }
             // Level 0's spawn does not wait for the host to learn how many primary rays hit: it is launched over every item of the
             // rank's frame and stops at the count it reads on the device, while the host fetches that count on a stream of its own
             // (behind the primary kernel only) to size the traversal launches that follow -- the host round trip (~25 us of an idle
@@ -2049,7 +2074,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                     // on their counts -- the frame is finished without a host round trip (an entry of level 0 without a mirror ray
                     // carries child = -1, so the scatter kernel can fold with level 1 whether or not level 1 has entries); the
                     // counts are read after the frame's closing event.
-                    HIP_TRY(launch_write_rgb(levels.as<float>(), levels.as<float>() + (size_t)n * 8, cnt, ipix.as<int>(), drgb.as<float>(), nullptr));
+                    HIP_TRY(launch_write_rgb(levels.as<float>(), levels.as<float>() + (size_t)n * 8, cnt, ipix.as<int>(), frame_rgb, nullptr));
                     HIP_TRY(resolve(nullptr));
                     finished = true;
                     HIP_TRY(hipEventRecord(aux.e1, nullptr));
@@ -2088,7 +2113,10 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         }
         if (finished) {
         } else if (max_level < 1) {  // trace() returns black without tracing (main.cpp:267): no primary kernel ran, clear here
-            HIP_TRY(launch_clear_owned(F, drgb.as<float>(), nullptr));
+            if (list)
+                HIP_TRY(hipMemsetAsync(frame_rgb, 0, n * 12, nullptr));
+            else
+                HIP_TRY(launch_clear_owned(F, frame_rgb, nullptr));
         } else if (nlev == 0) {  // nothing was hit: the primary kernel has left this rank's pixels black
         } else {
             // color = directColor + reflectedColor * ks (main.cpp:262), deepest level first; the last fold (level 0 with level 1) is
@@ -2097,7 +2125,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                 HIP_TRY(launch_fold(levels.as<float>() + (size_t)level * n * 8, levels.as<float>() + (size_t)(level + 1) * n * 8, level_count[level],
                                     nullptr));
             HIP_TRY(launch_write_rgb(levels.as<float>(), nlev >= 2 ? levels.as<float>() + (size_t)n * 8 : nullptr, level_count[0], ipix.as<int>(),
-                                     drgb.as<float>(), nullptr));
+                                     frame_rgb, nullptr));
         }
         if (!finished) {
             HIP_TRY(resolve(nullptr));
@@ -2108,6 +2136,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipEventElapsedTime(&ms, aux.e0, aux.e1));
         st.device_ms = ms;
         st.levels = nlev;
+        if (list) return CGRT_OK;  // (a ray list sizes no frame)
         // what this frame found sizes the next one
         P.valid = g_render_predict.load() && SL == 0 && !counted && max_level >= 1 && !level_count.empty();
         P.W = W, P.H = H, P.rank = rank, P.nranks = nranks, P.max_level = max_level, P.L = L;
@@ -2116,13 +2145,17 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         return CGRT_OK;
     };
     if (!frame_done) {
-        P.last_path = predictable ? 2 : 0;
+        if (!list) P.last_path = predictable ? 2 : 0;
         st = CgrtRenderStats{};
         const int erc = exact();
         if (erc != CGRT_OK) return erc;
     }
     if (after_export) s->export_pending = false;  // aux.e1, which this call has waited for, is behind it
-    if (dout) {
+    if (list) {
+        // The colours are in the caller's buffer and the frame's last kernel is done (aux.e1 was waited for); the wait only makes that
+        // ordering explicit on the caller's stream.
+        HIP_TRY(hipStreamWaitEvent(list->stream, aux.e1, 0));
+    } else if (dout) {
         // The frame's last kernel is done (aux.e1 was waited for); the wait below only makes that ordering explicit on the caller's stream.
         ExportDev E{};
         E.src = aa ? dres.as<float>() : drgb.as<float>();
@@ -2255,6 +2288,33 @@ static int export_args(const void* out, int W, int H, int format, uint64_t row_b
     return CGRT_OK;
 }
 
+// p .. p + bytes must be device memory of the scene's device (the current device is the scene's): one allocation, or several that follow
+// one another in the address space (a caching allocator that maps its pool in pieces through the virtual-memory API, e.g. torch's
+// expandable segments), each checked.  A pointer this HIP runtime does not know (another copy of the runtime in the process, host memory)
+// is refused here, before any work.  Used by every entry that takes a caller's device buffer (cgrt_render_device, cgrt_shade_rays_device).
+static int check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, const char* name) {
+    uintptr_t at = (uintptr_t)p;
+    const uintptr_t end = at + bytes;
+    for (int piece = 0; at < end; piece++) {
+        if (piece == 65536) return fail(CGRT_E_ARG, std::string(name) + " spans too many separate allocations");
+        hipPointerAttribute_t pa{};
+        if (hipPointerGetAttributes(&pa, reinterpret_cast<void*>(at)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(CGRT_E_ARG, std::string(name) + (piece ? "'s allocation is smaller than the data" : " is not memory of this process's HIP runtime"));
+        }
+        if (pa.type != hipMemoryTypeDevice || pa.device != s->device) return fail(CGRT_E_ARG, std::string(name) + " is not device memory of the scene's device");
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, reinterpret_cast<hipDeviceptr_t>(at)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(CGRT_E_ARG, std::string(name) + ": no device allocation found");
+        }
+        if ((uintptr_t)base + size <= at) return fail(CGRT_E_ARG, std::string(name) + ": no device allocation found");
+        at = (uintptr_t)base + size;
+    }
+    return CGRT_OK;
+}
+
 int cgrt_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
                        CgrtRenderStats* stats) {
@@ -2280,30 +2340,63 @@ int cgrt_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     if (rc) return rc;
     NEED_DEVICE(s);
     HIP_TRY(hipSetDevice(s->device));
-    // d_out .. d_out + extent must be device memory of the scene's device: one allocation, or several that follow one another in the
-    // address space (a caching allocator that maps its pool in pieces through the virtual-memory API, e.g. torch's expandable
-    // segments), each checked.  A pointer this HIP runtime does not know (another copy of the runtime in the process, host memory) is
-    // refused here, before any work.
-    uintptr_t at = (uintptr_t)d_out;
-    const uintptr_t end = at + extent;
-    for (int piece = 0; at < end; piece++) {
-        if (piece == 65536) return fail(CGRT_E_ARG, "d_out spans too many separate allocations");
-        hipPointerAttribute_t pa{};
-        if (hipPointerGetAttributes(&pa, reinterpret_cast<void*>(at)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(CGRT_E_ARG, piece ? "d_out's allocation is smaller than the frame" : "d_out is not memory of this process's HIP runtime");
-        }
-        if (pa.type != hipMemoryTypeDevice || pa.device != s->device) return fail(CGRT_E_ARG, "d_out is not device memory of the scene's device");
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, reinterpret_cast<hipDeviceptr_t>(at)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(CGRT_E_ARG, "d_out: no device allocation found");
-        }
-        if ((uintptr_t)base + size <= at) return fail(CGRT_E_ARG, "d_out: no device allocation found");
-        at = (uintptr_t)base + size;
-    }
+    const int sc = check_device_span(s, d_out, extent, "d_out");
+    if (sc) return sc;
     return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, nullptr, stats, nullptr, nullptr, aa != 0, &D);
+}
+
+// ---- getFinalColor of the caller's rays (main.cpp:298-310): level 0 of the wavefront from a ray list (render_impl, ListSrc) ----
+// Every argument is checked before any device work, in the order include/cgrt.h states; a host-only scene is CGRT_E_NO_DEVICE after that.
+static int shade_rays_args(const CgrtScene* s, const void* rays, uint64_t n, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                           int max_level, const void* rgb) {
+    if (!s || !rgb || (n > 0 && !rays) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many rays: n exceeds 0x7fffffff");
+    if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
+    if (soft && soft->nspherical &&
+        (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
+        return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
+    NEED_DEVICE(s);
+    return CGRT_OK;
+}
+int cgrt_shade_rays_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                           int max_level, float* d_rgb, void* stream, CgrtRenderStats* stats) {
+    int rc = shade_rays_args(s, d_rays, n, lights, nlights, soft, max_level, d_rgb);
+    if (rc) return rc;
+    if (n == 0) {
+        if (stats) *stats = CgrtRenderStats{};
+        return CGRT_OK;
+    }
+    if ((uintptr_t)d_rays % 4 || (uintptr_t)d_rgb % 4) return fail(CGRT_E_ARG, "d_rays and d_rgb must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_rgb, n * 12, "d_rgb")) != CGRT_OK) return rc;
+    const ListSrc src{reinterpret_cast<const float*>(d_rays), n, d_rgb, static_cast<hipStream_t>(stream)};
+    return render_impl(s, nullptr, 1, 1, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, nullptr, &src);
+}
+int cgrt_shade_rays(CgrtScene* s, const CgrtRay* rays, uint64_t n, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                    int max_level, float* rgb, CgrtRenderStats* stats) {
+    int rc = shade_rays_args(s, rays, n, lights, nlights, soft, max_level, rgb);
+    if (rc) return rc;
+    if (n == 0) {
+        if (stats) *stats = CgrtRenderStats{};
+        return CGRT_OK;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    // the rays go up and the colours come down through a call lane's pinned staging, on the lane's stream
+    LaneGuard g(s);
+    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    void *dr = nullptr, *dc = nullptr;
+    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(g.dev(1, n * 12, &dc));
+    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
+    const ListSrc src{static_cast<const float*>(dr), n, static_cast<float*>(dc), g.L->stream};
+    rc = render_impl(s, nullptr, 1, 1, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, nullptr, &src);
+    if (rc) return rc;
+    void* staged = nullptr;
+    HIP_TRY(lane_download(g, 1, rgb, dc, n * 12, &staged));
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    if (staged) std::memcpy(rgb, staged, n * 12);
+    return CGRT_OK;
 }
 
 int cgrt_debug_export_frame(int device, const float* rgb, int W, int H, int format, uint64_t row_bytes, void* out) {

@@ -68,6 +68,11 @@ hipError_t launch_soft_shadow(const SceneDev& S, const SoftDev& Q, const float* 
 hipError_t launch_trace_primary_compact(const SceneDev& S, const CameraDev& C, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals,
                                         int* pixels, uint32_t* count, hipStream_t stream, unsigned long long* counters = nullptr,
                                         float* rgb = nullptr, const SpawnDev* spawn = nullptr);  // spawn (device memory): level 0's k_spawn fused in (spawn_rays.h)  // rgb (optional): the rank's pixels are cleared by the same kernel
+// level 0 of the shading wavefront from a caller's list of n rays (cgrt_shade_rays, k_trace_list_compact): rgb[3i..3i+2] := 0 for every
+// i, the rays that hit appended to the compact list {rays, hits, normals, pixels = i}; count = one zeroed device word.  Laid out by the
+// list's shape (list_shape), as launch_trace_batch.
+hipError_t launch_trace_list_compact(const SceneDev& S, const float* in_rays, unsigned long long n, float* rays, CgrtHitDev* hits, float* normals,
+                                     int* pixels, uint32_t* count, float* rgb, hipStream_t stream, unsigned long long* counters = nullptr);
 hipError_t launch_clear_owned(const FrameDev& F, float* rgb, hipStream_t stream);
 // shading wavefront (shade_kernels.hip); every level is a compact list of live paths
 // counters: 3 device words {shadow rays appended, mirror rays appended, hits}, zeroed by the caller

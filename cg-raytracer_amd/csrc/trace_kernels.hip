@@ -185,6 +185,80 @@ __global__ CGRT_LB void k_trace_primary_compact(SceneDev S, CameraDev C, FrameDe
         }
     }
 }
+// Level 0 of the shading wavefront from a CALLER's ray list (cgrt_shade_rays): getFinalColor(scene, bvh, ray i) for every i of the
+// list (main.cpp:298-310).  The lanes are laid out like k_trace_batch's (the list shapes: quad, sparse or one ray per lane), the walk
+// starts from the caller's t as k_trace_batch's does (the reference's `t >= ray.t` rule), and the tail is k_trace_primary_compact's:
+// rgb[3i..3i+2] = black for every i (main.cpp:293), the rays that hit appended to level 0's list with pixel = i, ONE atomic per
+// workgroup.  The entry keeps the caller's ray as given, t included.  count = one zeroed device word.
+template <bool COUNT, bool FAST, bool QUAD = false>
+__global__ CGRT_LB void k_trace_list_compact(SceneDev S, const float* __restrict__ in_rays, unsigned long long n, float* __restrict__ rays,
+                                             CgrtHitDev* __restrict__ hits, float* __restrict__ normals, int* __restrict__ pixels,
+                                             uint32_t* __restrict__ count, unsigned long long* counters, float* __restrict__ rgb, unsigned qrpw) {
+    extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
+    const int lane = threadIdx.x & 63;
+    const bool sparse = !QUAD && qrpw < 64u;  // (see k_trace_batch)
+    const unsigned long long i = QUAD ? ((unsigned long long)blockIdx.x * qrpw + (threadIdx.x >> 2))
+                                      : (sparse ? (unsigned long long)blockIdx.x * qrpw + threadIdx.x : (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x);
+    const bool writer = !QUAD || (threadIdx.x & 3u) == 0u;
+    const bool active = i < n && (!QUAD || (threadIdx.x >> 2) < qrpw) && (!sparse || threadIdx.x < qrpw);
+    if (active && writer) {  // every ray of the list starts black (main.cpp:293); the hits are written over it at the end
+        float* p = rgb + 3ull * i;
+        p[0] = p[1] = p[2] = 0.0f;
+    }
+    LaneCounters cnt;
+    CgrtHitDev h;
+    h.hit = 0;
+    F3 o = f3(0, 0, 0), d = f3(0, 0, 0), nn = f3(0, 0, 0);
+    float t = 0.0f;
+    if (active) {
+        const float* r = in_rays + 7 * i;
+        o = f3(r[0], r[1], r[2]);
+        d = f3(r[3], r[4], r[5]);
+        t = r[6];
+    }
+    uint32_t hit_rec = REF_NONE;
+    if (QUAD)
+        walk_tree_quad<COUNT>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), cnt);
+    else
+        walk_tree<COUNT, FAST>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), CGRT_WAVE_MAP(s_lds), cnt);
+    if (active && writer) resolve_hit(S, o, d, t, hit_rec, true, h, nn);
+    if (COUNT) flush_counters(cnt, active && writer, counters);
+    const bool keep = active && writer && h.hit != 0;
+    const unsigned long long m = __ballot(keep);
+    uint32_t* s_cnt = CGRT_BLOCK_SCRATCH(s_lds);
+    const unsigned w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if (lane == 0) s_cnt[w] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (unsigned k = 0; k < nw; k++) {
+            const uint32_t c = s_cnt[k];
+            s_cnt[k] = tot;
+            tot += c;
+        }
+        s_cnt[nw] = tot ? atomicAdd(count, tot) : 0u;
+    }
+    __syncthreads();
+    if (keep) {
+        const unsigned long long idx = s_cnt[nw] + s_cnt[w] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        // (the ray's index is rebuilt rather than kept in two registers through the walk; its t is read again, the walk moved it)
+        const unsigned long long k = QUAD ? ((unsigned long long)blockIdx.x * qrpw + (threadIdx.x >> 2))
+                                          : (sparse ? (unsigned long long)blockIdx.x * qrpw + threadIdx.x : (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x);
+        float* r = rays + 7 * idx;
+        r[0] = o.x;
+        r[1] = o.y;
+        r[2] = o.z;
+        r[3] = d.x;
+        r[4] = d.y;
+        r[5] = d.z;
+        r[6] = in_rays[7 * k + 6];
+        hits[idx] = h;
+        normals[3 * idx] = nn.x;
+        normals[3 * idx + 1] = nn.y;
+        normals[3 * idx + 2] = nn.z;
+        pixels[idx] = (int)k;
+    }
+}
 // Two lists in ONE launch: a level's shadow list (occlusion queries, k_trace_shadow's body) and its mirror list (closest hits,
 // k_trace_batch's body), workgroups dealt alternately so that both are on the chip at once.  A predicted frame (capi.cpp
 // render_impl) used to run them on two streams; the event that started the second stream and the wait that joined it again cost
@@ -620,6 +694,28 @@ hipError_t launch_trace_primary_compact(const SceneDev& S, const CameraDev& C, c
         CGRT_LAUNCH2(k_trace_primary_compact, true, fast, F.nblocks, block, stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
     else
         CGRT_LAUNCH2(k_trace_primary_compact, false, fast, F.nblocks, block, stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
+    return hipGetLastError();
+}
+hipError_t launch_trace_list_compact(const SceneDev& S, const float* in_rays, unsigned long long n, float* rays, CgrtHitDev* hits, float* normals,
+                                     int* pixels, uint32_t* count, float* rgb, hipStream_t stream, unsigned long long* counters) {
+    if (n == 0) return hipSuccess;
+    const unsigned block = (unsigned)trace_block(S);
+    const bool fast = S.fast_root != REF_NONE;
+    const int shape = list_shape(S, n);  // (the list's length is known to the host: laid out as any ray list)
+    if (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4) {
+        const unsigned q = shape == SHAPE_QUAD4 ? 4u : 16u;
+        if (counters)
+            CGRT_LAUNCHQ(k_trace_list_compact, true, grid_for(n, q), stream, S, in_rays, n, rays, hits, normals, pixels, count, counters, rgb, q);
+        else
+            CGRT_LAUNCHQ(k_trace_list_compact, false, grid_for(n, q), stream, S, in_rays, n, rays, hits, normals, pixels, count, counters, rgb, q);
+        return hipGetLastError();
+    }
+    const unsigned rpw = shape == SHAPE_LANE16 ? 16u : 64u;
+    const unsigned grid = lane_grid(n, block, rpw, 0u);
+    if (counters)
+        CGRT_LAUNCH2(k_trace_list_compact, true, fast, grid, block, stream, S, in_rays, n, rays, hits, normals, pixels, count, counters, rgb, rpw);
+    else
+        CGRT_LAUNCH2(k_trace_list_compact, false, fast, grid, block, stream, S, in_rays, n, rays, hits, normals, pixels, count, counters, rgb, rpw);
     return hipGetLastError();
 }
 hipError_t launch_clear_owned(const FrameDev& F, float* rgb, hipStream_t stream) {

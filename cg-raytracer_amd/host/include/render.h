@@ -58,6 +58,16 @@ RenderStats renderToBufferPerRay(const Scene& scene, const Trackball& camera, co
                                  int maxLevel = 2, const SoftShadowSampler* sampler = nullptr, int threads = 0, bool antiAliasing = false);
 RenderStats renderRayTracingPerRay(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, Screen& screen, int maxLevel = 2,
                                    const SoftShadowSampler* sampler = nullptr, int threads = 0, bool antiAliasing = false);
+// getFinalColor(scene, bvh, ray) (main.cpp:298-310) of the caller's own rays -- a host that builds its rays some other way than
+// Trackball::generateRay (jittered sub-samples, another camera model, probe rays) and calls getFinalColor per ray:
+// rgb[3i..3i+2] = the colour of rays[i] (the ray as given, t included), recursion cut at maxLevel.  Soft shadows hash sample smp of ray
+// i with pixel = i (include/cgrt.h cgrt_shade_rays).
+//   getFinalColorsOnDevice: the whole driver on the device (cgrt_shade_rays; the fast path);
+//   getFinalColorsPerRay: the reference's recursion literally, one BoundingVolumeHierarchy::intersect per ray, under `omp parallel for`.
+RenderStats getFinalColorsOnDevice(const Scene& scene, const BoundingVolumeHierarchy& bvh, const Ray* rays, size_t n, float* rgb, int maxLevel = 2,
+                                   const SoftShadowSampler* sampler = nullptr);
+RenderStats getFinalColorsPerRay(const Scene& scene, const BoundingVolumeHierarchy& bvh, const Ray* rays, size_t n, float* rgb, int maxLevel = 2,
+                                 const SoftShadowSampler* sampler = nullptr, int threads = 0);
 // sampler: required when the scene has spherical lights (nullptr -> SoftShadowSampler::gaussian()).
 RenderStats renderRayTracing(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, Screen& screen, int maxLevel = 2,
                              const SoftShadowSampler* sampler = nullptr, bool antiAliasing = false);

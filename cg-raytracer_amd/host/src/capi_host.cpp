@@ -178,6 +178,50 @@ int cgrt_host_render_soft(const float* pos_nrm, uint32_t nverts, const uint32_t*
     }
 }
 
+// getFinalColor of the caller's rays (n x 7 floats {origin, direction, t}) through the mirror: per_ray = 0 getFinalColorsOnDevice
+// (cgrt_shade_rays), 1 getFinalColorsPerRay (the reference's recursion, one intersect per ray, `threads` callers).  Spherical lights as
+// cgrt_host_render_soft (nunits = 0: SoftShadowSampler::gaussian()).  stats: primary, shadow, reflection, soft-shadow rays, device s, total s.
+int cgrt_host_shade_rays(const float* pos_nrm, uint32_t nverts, const uint32_t* tri, const uint32_t* tri_mesh, uint32_t ntris,
+                         const float* materials, uint32_t nmesh, const float* lights, uint32_t nlights, const float* spherical,
+                         uint32_t nspherical, const float* units, uint32_t nunits, uint32_t samples, uint32_t seed, const float* rays,
+                         uint64_t n, int maxLevel, int per_ray, int threads, float* rgb, double* stats) {
+    try {
+        Scene sc = scene_from_arrays(pos_nrm, nverts, tri, tri_mesh, ntris, materials, nmesh, lights, nlights);
+        for (uint32_t i = 0; i < nspherical; i++) {
+            const float* q = spherical + 7 * i;
+            sc.sphericalLight.push_back(SphericalLight{cgrt::vec3(q[0], q[1], q[2]), q[3], cgrt::vec3(q[4], q[5], q[6])});
+        }
+        SoftShadowSampler sampler;
+        if (nunits) {
+            for (uint32_t i = 0; i < nunits; i++) sampler.units.push_back(cgrt::vec3(units[3 * i], units[3 * i + 1], units[3 * i + 2]));
+        } else {
+            sampler = SoftShadowSampler::gaussian();
+        }
+        sampler.samples = samples;
+        sampler.seed = seed;
+        std::vector<Ray> rs(n);
+        for (uint64_t i = 0; i < n; i++) {
+            const float* r = rays + 7 * i;
+            rs[i] = Ray{cgrt::vec3(r[0], r[1], r[2]), cgrt::vec3(r[3], r[4], r[5]), r[6]};
+        }
+        BoundingVolumeHierarchy bvh(&sc);
+        RenderStats st = per_ray ? getFinalColorsPerRay(sc, bvh, rs.data(), rs.size(), rgb, maxLevel, &sampler, threads)
+                                 : getFinalColorsOnDevice(sc, bvh, rs.data(), rs.size(), rgb, maxLevel, &sampler);
+        if (stats) {
+            stats[0] = (double)st.primary;
+            stats[1] = (double)st.shadow;
+            stats[2] = (double)st.reflection;
+            stats[3] = (double)st.softShadow;
+            stats[4] = st.seconds_device;
+            stats[5] = st.seconds_total;
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
 // Loads an OBJ with the host loader and reports sizes; a second call with buffers copies the flat arrays out.
 int cgrt_host_load_obj(const char* path, int normalize, uint32_t* nverts, uint32_t* ntris, uint32_t* nmesh, float* pos_nrm, uint32_t* tri,
                        uint32_t* tri_mesh, float* materials) {

@@ -448,6 +448,45 @@ RenderStats renderToBuffer(const Scene& scene, const Trackball& camera, const Bo
 }
 
 namespace {
+// The scene's lights as the C-ABI takes them: point lights {position, colour}, spherical lights {position, radius, colour} and the
+// sampler's unit-vector table (SoftShadowSampler::gaussian() when the scene has spherical lights and no usable sampler was given).
+struct DeviceLights {
+    std::vector<float> lights, spherical, units;
+    CgrtSoftShadows soft{};
+    DeviceLights(const Scene& scene, const SoftShadowSampler* sampler) {
+        SoftShadowSampler fallback;
+        if (!scene.sphericalLight.empty() && (!sampler || sampler->units.empty() || sampler->samples == 0)) {
+            fallback = SoftShadowSampler::gaussian();
+            sampler = &fallback;
+        }
+        for (const PointLight& l : scene.pointLights)
+            lights.insert(lights.end(), {l.position.x, l.position.y, l.position.z, l.color.x, l.color.y, l.color.z});
+        for (const SphericalLight& l : scene.sphericalLight)
+            spherical.insert(spherical.end(), {l.position.x, l.position.y, l.position.z, l.radius, l.color.x, l.color.y, l.color.z});
+        if (!spherical.empty()) {
+            for (const vec3& u : sampler->units) units.insert(units.end(), {u.x, u.y, u.z});
+            soft.spherical = spherical.data();
+            soft.unit_vectors = units.data();
+            soft.nspherical = (uint32_t)scene.sphericalLight.size();
+            soft.samples = sampler->samples;
+            soft.nunits = (uint32_t)sampler->units.size();
+            soft.seed = sampler->seed;
+            soft.closest_hit = 0;
+        }
+    }
+    DeviceLights(const DeviceLights&) = delete;  // (soft points into the vectors)
+    const CgrtSoftShadows* soft_or_null() const { return spherical.empty() ? nullptr : &soft; }
+};
+RenderStats stats_of(const CgrtRenderStats& cs, Clock::time_point t_begin) {
+    RenderStats st;
+    st.primary = cs.primary_rays;
+    st.shadow = cs.shadow_rays;
+    st.reflection = cs.reflection_rays;
+    st.softShadow = cs.soft_shadow_rays;
+    st.seconds_device = cs.device_ms * 1e-3;
+    st.seconds_total = std::chrono::duration<double>(Clock::now() - t_begin).count();
+    return st;
+}
 // The whole driver on the device(s).  rgb != nullptr: the frame goes into the caller's buffer; screen != nullptr: into the
 // Screen (Screen::setPixel's flip, main.cpp:696) -- with one replica straight from the library's pinned frame
 // (cgrt_render_mapped: no intermediate copy of the 12-bytes-per-pixel frame), rows copied in bulk (Screen::setFrame).
@@ -455,33 +494,14 @@ RenderStats render_on_devices(const Scene& scene, const Trackball& camera, const
                               float* rgb, Screen* screen, int maxLevel, const SoftShadowSampler* sampler, bool aa) {
     const auto t_begin = Clock::now();
     if (bvhs.empty()) throw std::runtime_error("renderToBufferOnDevices: no BVH replica");
-    SoftShadowSampler fallback;
-    if (!scene.sphericalLight.empty() && (!sampler || sampler->units.empty() || sampler->samples == 0)) {
-        fallback = SoftShadowSampler::gaussian();
-        sampler = &fallback;
-    }
-    std::vector<float> lights, spherical, units;
-    for (const PointLight& l : scene.pointLights)
-        lights.insert(lights.end(), {l.position.x, l.position.y, l.position.z, l.color.x, l.color.y, l.color.z});
-    for (const SphericalLight& l : scene.sphericalLight)
-        spherical.insert(spherical.end(), {l.position.x, l.position.y, l.position.z, l.radius, l.color.x, l.color.y, l.color.z});
-    CgrtSoftShadows soft{};
-    if (!spherical.empty()) {
-        for (const vec3& u : sampler->units) units.insert(units.end(), {u.x, u.y, u.z});
-        soft.spherical = spherical.data();
-        soft.unit_vectors = units.data();
-        soft.nspherical = (uint32_t)scene.sphericalLight.size();
-        soft.samples = sampler->samples;
-        soft.nunits = (uint32_t)sampler->units.size();
-        soft.seed = sampler->seed;
-        soft.closest_hit = 0;
-    }
+    const DeviceLights dl(scene, sampler);
+    const std::vector<float>& lights = dl.lights;
     CgrtRenderStats cs{};
     const CgrtCamera cam = camera.abi();
     std::vector<CgrtScene*> handles;
     for (const BoundingVolumeHierarchy* b : bvhs) handles.push_back(b->handle());
     const uint32_t L = (uint32_t)scene.pointLights.size();
-    const CgrtSoftShadows* sp = spherical.empty() ? nullptr : &soft;
+    const CgrtSoftShadows* sp = dl.soft_or_null();
     int rc;
     if (handles.size() == 1 && screen) {
         const float* frame = nullptr;
@@ -502,14 +522,7 @@ RenderStats render_on_devices(const Scene& scene, const Trackball& camera, const
         if (rc == 0 && screen) screen->setFrame(rgb);
     }
     if (rc != 0) throw std::runtime_error(std::string("cgrt_render: ") + cgrt_last_error());
-    RenderStats st;
-    st.primary = cs.primary_rays;
-    st.shadow = cs.shadow_rays;
-    st.reflection = cs.reflection_rays;
-    st.softShadow = cs.soft_shadow_rays;
-    st.seconds_device = cs.device_ms * 1e-3;
-    st.seconds_total = std::chrono::duration<double>(Clock::now() - t_begin).count();
-    return st;
+    return stats_of(cs, t_begin);
 }
 }  // namespace
 
@@ -641,6 +654,44 @@ RenderStats renderToBufferPerRay(const Scene& scene, const Trackball& camera, co
         }
     }
     st.primary = maxLevel >= 1 ? (uint64_t)W * H * (antiAliasing ? 4 : 1) : 0;
+    st.shadow = nshadow;
+    st.reflection = nrefl;
+    st.softShadow = nsoft;
+    st.seconds_total = st.seconds_device = std::chrono::duration<double>(Clock::now() - t_begin).count();
+    return st;
+}
+
+RenderStats getFinalColorsOnDevice(const Scene& scene, const BoundingVolumeHierarchy& bvh, const Ray* rays, size_t n, float* rgb, int maxLevel,
+                                   const SoftShadowSampler* sampler) {
+    static_assert(sizeof(Ray) == sizeof(CgrtRay), "Ray must be the C-ABI's CgrtRay (ray.h)");
+    const auto t_begin = Clock::now();
+    const DeviceLights dl(scene, sampler);
+    CgrtRenderStats cs{};
+    if (cgrt_shade_rays(bvh.handle(), reinterpret_cast<const CgrtRay*>(rays), n, dl.lights.data(), (uint32_t)scene.pointLights.size(), dl.soft_or_null(),
+                        maxLevel, rgb, &cs) != 0)
+        throw std::runtime_error(std::string("cgrt_shade_rays: ") + cgrt_last_error());
+    return stats_of(cs, t_begin);
+}
+
+RenderStats getFinalColorsPerRay(const Scene& scene, const BoundingVolumeHierarchy& bvh, const Ray* rays, size_t n, float* rgb, int maxLevel,
+                                 const SoftShadowSampler* sampler, int threads) {
+    RenderStats st;
+    SoftShadowSampler fallback;
+    if (!scene.sphericalLight.empty() && (!sampler || sampler->units.empty() || sampler->samples == 0)) {
+        fallback = SoftShadowSampler::gaussian();
+        sampler = &fallback;
+    }
+    const auto t_begin = Clock::now();
+    const PerRay drv{scene, bvh, sampler, maxLevel};
+    uint64_t nshadow = 0, nrefl = 0, nsoft = 0;
+    if (threads <= 0) threads = omp_get_max_threads();
+#pragma omp parallel for schedule(dynamic, 64) num_threads(threads) reduction(+ : nshadow, nrefl, nsoft)
+    for (int64_t i = 0; i < (int64_t)n; i++) {  // getFinalColor(scene, bvh, rays[i]), main.cpp:298-310
+        const vec3 c = drv.trace(0, rays[i], (uint32_t)i, nshadow, nrefl, nsoft);
+        float* p = rgb + 3 * (size_t)i;
+        p[0] = c.x, p[1] = c.y, p[2] = c.z;
+    }
+    st.primary = maxLevel >= 1 ? (uint64_t)n : 0;
     st.shadow = nshadow;
     st.reflection = nrefl;
     st.softShadow = nsoft;

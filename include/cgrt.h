@@ -358,6 +358,30 @@ int cgrt_render_device(CgrtScene* scene, const CgrtCamera* cam, int W, int H, co
  * back -- bytes the export does not write keep their values.  Synchronous. */
 int cgrt_debug_export_frame(int device, const float* rgb, int W, int H, int format, uint64_t row_bytes, void* out);
 
+/* getFinalColor(scene, bvh, ray) (main.cpp:298-310) of the CALLER's rays: rgb[3i..3i+2] = the colour of rays[i], with the reference's
+ * recursion cut at max_level (2 = upstream), the same wavefront as cgrt_render_soft from level 0 on.  Outputs are written for every
+ * i < n and nowhere else.  A ray is taken as given: the walk starts from its t (the reference's `t >= ray.t` rule, so a ray whose t
+ * ends before the first surface is black), its direction need not be unit length (the mirror ray's t is |d|, main.cpp:254).
+ * Soft shadows: sample smp of ray i hashes with p = i in cgrt_render_soft's formula, so the row-major rays of cgrt_generate_rays over
+ * a whole W x H frame give that frame's draws, and the frame itself, bit for bit.  The result does not depend on the list's order
+ * (a permutation of the rays permutes the colours) nor on the kernel shape, but the speed does: rays next to each other in the list
+ * share waves, and a list in the frame's 8 x 8 tile order traverses faster than the same rays row-major.
+ * stats: as the render entries count them; primary_rays = n when max_level >= 1.  The call always takes the exactly sized path and
+ * neither reads nor writes the scene's frame prediction or frame hints.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene, rgb, or rays with n > 0, or nlights > 0 with NULL
+ * lights; n > 0x7fffffff; max_level outside 0..16; bad `soft` (cgrt_render_soft's rules).  Then a host-only scene: CGRT_E_NO_DEVICE.
+ * n == 0 succeeds with zeroed stats and touches nothing; max_level == 0 writes black and traces nothing.
+ * cgrt_shade_rays: host pointers (staged through pinned memory; synchronous). */
+int cgrt_shade_rays(CgrtScene* scene, const CgrtRay* rays, uint64_t n, const float* lights, uint32_t nlights,
+                    const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats);
+/* cgrt_shade_rays_device: d_rays (n * 28 bytes) and d_rgb (n * 12 bytes) are device memory of the scene's device, each 4-byte aligned,
+ * in one allocation or several that follow one another in the address space (checked as cgrt_render_device checks d_out; CGRT_E_ARG
+ * before any work otherwise).  Stream order: the call's work runs after everything enqueued on `stream` before the call (where the
+ * rays were written), and work enqueued on `stream` after the call returns sees the colours.  The colours are written straight into
+ * d_rgb; the call returns when they are there.  The stream handle is not kept. */
+int cgrt_shade_rays_device(CgrtScene* scene, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights,
+                           const CgrtSoftShadows* soft, int max_level, float* d_rgb, void* stream, CgrtRenderStats* stats);
+
 /* Work counters of the same traversal (separate instrumented launch; not part of any timed region). */
 int cgrt_count_primary(CgrtScene* scene, const CgrtCamera* cam, int W, int H, int x0, int y0, int x1, int y1,
                        int rank, int nranks, CgrtCounters* out);
