@@ -530,6 +530,10 @@ static uint32_t fmix32(uint32_t h) {  // murmur3 32-bit finaliser
     h ^= h >> 16;
     return h;
 }
+// Rays cast, by kind: the keys of the library's CgrtRenderStats (primary_rays, shadow_rays, reflection_rays, soft_shadow_rays).
+struct RayCounts {
+    uint64_t primary = 0, shadow = 0, reflection = 0, soft = 0;
+};
 struct Shader {
     const Oracle* o;
     std::vector<PointLight> lights;
@@ -551,13 +555,13 @@ struct Shader {
     static V3 material_ks(const Mat& m) { return mk(m.v[3], m.v[4], m.v[5]); }
 
     // main.cpp:104-135
-    bool point_in_shadow(V3 pointOn, const PointLight& l, uint64_t* nrays) const {
+    bool point_in_shadow(V3 pointOn, const PointLight& l, RayCounts* nrays) const {
         V3 toLight = l.pos - pointOn;
         Ray r{pointOn, normalize3(toLight), std::numeric_limits<float>::max()};
         float eps = 0.001;
         r.o = r.o + eps * r.d;
         HitState hs{mk(0, 0, 0), -1, 0xffffffffu};
-        if (nrays) (*nrays)++;
+        if (nrays) nrays->shadow++;
         if (o->intersect(r, hs, nullptr)) {
             if (r.t + eps >= length3(toLight)) return false;
             return true;
@@ -580,7 +584,7 @@ struct Shader {
         return l.color * material_ks(m) * p;
     }
     // main.cpp:160-235 (point-light loop :219-232)
-    V3 shading(const Ray& r, const HitState& h, const Mat& m, uint64_t* nrays, uint32_t pixel, int level) const {
+    V3 shading(const Ray& r, const HitState& h, const Mat& m, RayCounts* nrays, uint32_t pixel, int level) const {
         V3 pointOn = r.o + r.d * r.t;
         V3 res = mk(0, 0, 0);
         // main.cpp:168-218: spherical lights come first
@@ -600,7 +604,7 @@ struct Shader {
                 nr.t = length3(nr.o - rp);
                 HitState hs{mk(0, 0, 0), -1, 0xffffffffu};
                 float lightT = length3(nr.o - rp);
-                if (nrays) (*nrays)++;
+                if (nrays) nrays->soft++;
                 if (!o->intersect(nr, hs, nullptr)) {
                     counter += 1.0f;
                 } else if (nr.t > lightT) {
@@ -620,10 +624,11 @@ struct Shader {
         return res;
     }
     // main.cpp:265-295 trace + :241-264 shade
-    V3 trace(int level, Ray r, uint64_t* nrays, uint32_t pixel = 0) const {
+    // level 0 is the caller's ray (primary), deeper levels are mirror rays (reflection).
+    V3 trace(int level, Ray r, RayCounts* nrays, uint32_t pixel = 0) const {
         if (level >= maxLevel) return mk(0, 0, 0);
         HitState h{mk(0, 0, 0), -1, 0xffffffffu};
-        if (nrays) (*nrays)++;
+        if (nrays) (level == 0 ? nrays->primary : nrays->reflection)++;
         if (!o->intersect(r, h, nullptr)) return mk(0, 0, 0);
         // A hit whose material was never written (sphere-only hit) reads an
         // uninitialised Material upstream; restated as the default Material (mesh.h:17-23).
@@ -796,12 +801,8 @@ double oracle_trace_primary_timed(void* h, const float* cam, int W, int H, int y
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// Full getFinalColor (main.cpp:298-310) per pixel of rows [y0,y1): rgb = 3 floats per pixel (not y-flipped).
-// lights: L x 6 (pos, color).  Returns the number of rays cast.
-// oracle_render_soft: + spherical lights, S x 7 (pos, radius, color), sampled from the unit-vector table (see Shader).
-uint64_t oracle_render_soft(void* h, const float* cam, int W, int H, int y0, int y1, const float* lights, int nlights,
-                            const float* slights, int nslights, const float* units, uint32_t nunits, uint32_t samples, uint32_t seed,
-                            int maxLevel, float* rgb, int threads) {
+static Shader make_shader(void* h, const float* lights, int nlights, const float* slights, int nslights, const float* units,
+                          uint32_t nunits, uint32_t samples, uint32_t seed, int maxLevel) {
     Shader sh;
     sh.o = (const Oracle*)h;
     sh.maxLevel = maxLevel;
@@ -815,29 +816,87 @@ uint64_t oracle_render_soft(void* h, const float* cam, int W, int H, int y0, int
     for (int i = 0; i < nlights; i++)
         sh.lights.push_back(PointLight{mk(lights[6 * i], lights[6 * i + 1], lights[6 * i + 2]),
                                        mk(lights[6 * i + 3], lights[6 * i + 4], lights[6 * i + 5])});
+    return sh;
+}
+static void store_counts(const RayCounts& c, uint64_t* counts) {
+    if (!counts) return;
+    counts[0] = c.primary;
+    counts[1] = c.shadow;
+    counts[2] = c.reflection;
+    counts[3] = c.soft;
+}
+
+// Full getFinalColor (main.cpp:298-310) per pixel of rows [y0,y1): rgb = 3 floats per pixel (not y-flipped).
+// lights: L x 6 (pos, color); spherical lights: S x 7 (pos, radius, color), sampled from the unit-vector table (see Shader)
+// with pixel = y * W + x.  counts (optional): 4 x u64 {primary, shadow, reflection, soft_shadow} rays.  Returns their sum.
+uint64_t oracle_render_soft_counted(void* h, const float* cam, int W, int H, int y0, int y1, const float* lights, int nlights,
+                                    const float* slights, int nslights, const float* units, uint32_t nunits, uint32_t samples,
+                                    uint32_t seed, int maxLevel, float* rgb, uint64_t* counts, int threads) {
+    const Shader sh = make_shader(h, lights, nlights, slights, nslights, units, nunits, samples, seed, maxLevel);
     Camera c{mk(cam[0], cam[1], cam[2]), mk(cam[3], cam[4], cam[5]), cam[6], cam[7], cam[8]};
 #ifdef _OPENMP
     if (threads > 0) omp_set_num_threads(threads);
 #endif
-    uint64_t total = 0;
-#pragma omp parallel for reduction(+ : total)
+    uint64_t np = 0, ns = 0, nr = 0, nq = 0;
+#pragma omp parallel for reduction(+ : np, ns, nr, nq)
     for (int y = y0; y < y1; y++)
         for (int x = 0; x != W; x++) {
             Ray r = camera_ray(c, float(x) / W * 2.0f - 1.0f, float(y) / H * 2.0f - 1.0f);
-            uint64_t n = 0;
+            RayCounts n;
             V3 col = sh.trace(0, r, &n, (uint32_t)(y * W + x));
             float* p = rgb + 3 * ((size_t)(y - y0) * W + x);
             p[0] = col.x;
             p[1] = col.y;
             p[2] = col.z;
-            total += n;
+            np += n.primary;
+            ns += n.shadow;
+            nr += n.reflection;
+            nq += n.soft;
         }
-    return total;
+    store_counts(RayCounts{np, ns, nr, nq}, counts);
+    return np + ns + nr + nq;
+}
+
+uint64_t oracle_render_soft(void* h, const float* cam, int W, int H, int y0, int y1, const float* lights, int nlights,
+                            const float* slights, int nslights, const float* units, uint32_t nunits, uint32_t samples, uint32_t seed,
+                            int maxLevel, float* rgb, int threads) {
+    return oracle_render_soft_counted(h, cam, W, H, y0, y1, lights, nlights, slights, nslights, units, nunits, samples, seed, maxLevel,
+                                      rgb, nullptr, threads);
 }
 
 uint64_t oracle_render(void* h, const float* cam, int W, int H, int y0, int y1, const float* lights, int nlights,
                        int maxLevel, float* rgb, int threads) {
     return oracle_render_soft(h, cam, W, H, y0, y1, lights, nlights, nullptr, 0, nullptr, 0, 0, 0, maxLevel, rgb, threads);
+}
+
+// getFinalColor (main.cpp:298-310) of each of n caller-supplied rays (n x 7 floats: origin, direction, t -- the caller's t is kept,
+// as main.cpp:298 passes the ray on unchanged).  Sample smp of ray i hashes with pixel = i, the rule include/cgrt.h gives for
+// cgrt_shade_rays.  rgb: n x 3; counts (optional) as oracle_render_soft_counted.  Returns the number of rays cast.
+uint64_t oracle_shade_rays(void* h, const float* rays, uint64_t n, const float* lights, int nlights, const float* slights, int nslights,
+                           const float* units, uint32_t nunits, uint32_t samples, uint32_t seed, int maxLevel, float* rgb,
+                           uint64_t* counts, int threads) {
+    const Shader sh = make_shader(h, lights, nlights, slights, nslights, units, nunits, samples, seed, maxLevel);
+#ifdef _OPENMP
+    if (threads > 0) omp_set_num_threads(threads);
+#endif
+    uint64_t np = 0, ns = 0, nr = 0, nq = 0;
+#pragma omp parallel for schedule(dynamic, 64) reduction(+ : np, ns, nr, nq)
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        const float* q = rays + 7 * i;
+        Ray r{mk(q[0], q[1], q[2]), mk(q[3], q[4], q[5]), q[6]};
+        RayCounts c;
+        V3 col = sh.trace(0, r, &c, (uint32_t)i);
+        float* p = rgb + 3 * i;
+        p[0] = col.x;
+        p[1] = col.y;
+        p[2] = col.z;
+        np += c.primary;
+        ns += c.shadow;
+        nr += c.reflection;
+        nq += c.soft;
+    }
+    store_counts(RayCounts{np, ns, nr, nq}, counts);
+    return np + ns + nr + nq;
 }
 
 // ---- primitive intersectors, one call per element (for kernel-level parity tests) ----

@@ -62,6 +62,10 @@ def lib(o0: bool = False) -> C.CDLL:
     L.oracle_render.restype = u64
     L.oracle_render_soft.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, vp, i32]
     L.oracle_render_soft.restype = u64
+    L.oracle_render_soft_counted.argtypes = L.oracle_render_soft.argtypes[:-1] + [vp, i32]
+    L.oracle_render_soft_counted.restype = u64
+    L.oracle_shade_rays.argtypes = [vp, vp, u64, vp, i32, vp, i32, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, vp, vp, i32]
+    L.oracle_shade_rays.restype = u64
     for name in ("oracle_ray_triangle", "oracle_ray_plane", "oracle_ray_box", "oracle_ray_sphere"):
         f = getattr(L, name)
         f.argtypes = [vp, vp, u64, vp]
@@ -81,6 +85,14 @@ def _p(a):
 
 def _f32(a, shape):
     return np.ascontiguousarray(np.asarray(a, np.float32).reshape(shape))
+
+
+# ray counts by kind, in the order the oracle writes them: the keys of the library's render stats
+COUNT_KEYS = ("primary_rays", "shadow_rays", "reflection_rays", "soft_shadow_rays")
+
+
+def _counts(c) -> dict:
+    return dict(zip(COUNT_KEYS, (int(x) for x in c)))
 
 
 def rays7(rays) -> np.ndarray:
@@ -148,26 +160,38 @@ class OracleScene:
         sec = float(self.L.oracle_trace_primary_timed(self.h, _p(cam), W, H, y0, y1, _p(out), threads))
         return sec, out
 
-    def render(self, cam, W, H, lights, max_level=2, y0=0, y1=None, threads=0):
+    def render(self, cam, W, H, lights, max_level=2, y0=0, y1=None, threads=0, by_kind=False):
+        """Returns (rgb, number of rays cast), or (rgb, counts dict keyed as the library's stats) with by_kind=True."""
+        return self.render_soft(cam, W, H, lights, None, None, 0, 0, max_level, y0, y1, threads, by_kind)
+
+    def render_soft(self, cam, W, H, lights, spherical=None, units=None, samples=200, seed=0, max_level=2, y0=0, y1=None, threads=0, by_kind=False):
+        """main.cpp:168-218 with the randomUnitVector() draws taken from `units` (n x 3), see cgrt_oracle.cpp Shader.
+        Returns (rgb, number of rays cast), or (rgb, counts dict keyed as the library's stats) with by_kind=True."""
         y1 = H if y1 is None else y1
         cam = _f32(cam, (9,))
         lights = _f32(lights, (-1, 6))
+        spherical = _f32(np.zeros((0, 7)) if spherical is None else spherical, (-1, 7))
+        units = _f32(np.zeros((0, 3)) if units is None else units, (-1, 3))
         rgb = np.zeros(((y1 - y0) * W, 3), np.float32)
-        n = int(self.L.oracle_render(self.h, _p(cam), W, H, y0, y1, _p(lights), len(lights), max_level, _p(rgb), threads))
-        return rgb, n
+        cnt = np.zeros(4, np.uint64)
+        n = int(self.L.oracle_render_soft_counted(self.h, _p(cam), W, H, y0, y1, _p(lights), len(lights), _p(spherical), len(spherical),
+                                                  _p(units), len(units), samples, seed, max_level, _p(rgb), _p(cnt), threads))
+        return (rgb, _counts(cnt)) if by_kind else (rgb, n)
 
-
-    def render_soft(self, cam, W, H, lights, spherical, units, samples=200, seed=0, max_level=2, y0=0, y1=None, threads=0):
-        """main.cpp:168-218 with the randomUnitVector() draws taken from `units` (n x 3), see cgrt_oracle.cpp Shader."""
-        y1 = H if y1 is None else y1
-        cam = _f32(cam, (9,))
+    def shade_rays(self, rays, lights, spherical=None, units=None, samples=200, seed=0, max_level=2, threads=0):
+        """getFinalColor (main.cpp:298-310) of each caller-supplied ray (n x 7 or the product's RAY dtype; its t is kept); spherical
+        lights as render_soft, sample smp of ray i hashed with pixel i.  Returns (rgb[n, 3], counts dict keyed as the library's stats)."""
+        r = rays7(rays)
         lights = _f32(lights, (-1, 6))
-        spherical = _f32(spherical, (-1, 7))
-        units = _f32(units, (-1, 3))
-        rgb = np.zeros(((y1 - y0) * W, 3), np.float32)
-        n = int(self.L.oracle_render_soft(self.h, _p(cam), W, H, y0, y1, _p(lights), len(lights), _p(spherical), len(spherical),
-                                          _p(units), len(units), samples, seed, max_level, _p(rgb), threads))
-        return rgb, n
+        spherical = _f32(np.zeros((0, 7)) if spherical is None else spherical, (-1, 7))
+        units = _f32(np.zeros((0, 3)) if units is None else units, (-1, 3))
+        if len(spherical) and (len(units) == 0 or samples == 0):
+            raise ValueError("spherical lights need a unit-vector table and samples >= 1")
+        rgb = np.zeros((len(r), 3), np.float32)
+        cnt = np.zeros(4, np.uint64)
+        self.L.oracle_shade_rays(self.h, _p(r), len(r), _p(lights), len(lights), _p(spherical), len(spherical), _p(units), len(units),
+                                 samples, seed, max_level, _p(rgb), _p(cnt), threads)
+        return rgb, _counts(cnt)
 
 
 def generate_rays(cam, W, H, rect=None) -> np.ndarray:

@@ -117,3 +117,32 @@ def families(sd, node_boxes, primary, rng=None, n_random=1500):
 
 def concat(fam):
     return np.concatenate([fam[k] for k in sorted(fam)]).astype(np.float32)
+
+
+def arbitrary_rays(sd, n, seed):
+    """Seeded rays about a scene's mesh bounds (written for the Cornell box): origins inside, outside and on its surfaces, directions of length 0.25..4, t either the
+    float maximum, finite beyond the scene, or shorter than the first hit."""
+    rng = np.random.default_rng(seed)
+    p = np.asarray(sd.pos_nrm, np.float32).reshape(-1, 6)[:, :3]
+    lo, hi = p.min(0), p.max(0)
+    c, ext = (lo + hi) / 2, (hi - lo) / 2
+    o = np.empty((n, 3), np.float32)
+    k = n // 3
+    o[:k] = c + rng.uniform(-0.9, 0.9, (k, 3)) * ext  # inside
+    o[k : 2 * k] = c + rng.uniform(-3.0, 3.0, (k, 3)) * ext  # mostly outside
+    tri = np.asarray(sd.tri, np.int64).reshape(-1, 3)
+    pick = tri[rng.integers(0, len(tri), n - 2 * k)]  # on surfaces: random points of random triangles
+    w = rng.dirichlet((1, 1, 1), n - 2 * k).astype(np.float32)
+    o[2 * k :] = (p[pick] * w[:, :, None]).sum(1)
+    d = rng.normal(size=(n, 3)).astype(np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    d *= rng.uniform(0.25, 4.0, (n, 1)).astype(np.float32)
+    outside = np.arange(n) >= k
+    outside &= np.arange(n) < 2 * k
+    d[outside] = (c - o[outside]) * rng.uniform(0.1, 1.0, (outside.sum(), 1)).astype(np.float32)  # aimed at the box, non-unit
+    t = np.full(n, np.finfo(np.float32).max, np.float32)
+    sel = rng.random(n)
+    t[sel < 0.2] = rng.uniform(0.5, 4.0, (sel < 0.2).sum())  # finite: may or may not reach the first hit
+    t[(sel >= 0.2) & (sel < 0.3)] = 1e-6  # shorter than any hit
+    short = (sel >= 0.2) & (sel < 0.3) & (np.arange(n) < 2 * k)  # (an origin ON a surface may still hit at t = 0: not counted)
+    return np.concatenate([o, d, t[:, None]], axis=1).astype(np.float32), short

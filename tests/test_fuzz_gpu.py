@@ -8,7 +8,9 @@ every round appends one seed):
     with frame hints (hard tiles first / as 16-ray waves, thresholds of 20 .. 400 ticks) against the plain frame byte for byte;
   * render: cgrt_render (random scene, camera, 1-3 point lights, depth 0-4) against the oracle's recursive per-pixel driver:
     RGB <= 1e-5 (BASELINE.json north_star's tolerance), equal ray counts, certified == exact == quad-shape frames byte for byte
-    (the first frame of a scene is exactly sized, the later ones are predicted frames: capi.cpp render_impl).
+    (the first frame of a scene is exactly sized, the later ones are predicted frames: capi.cpp render_impl);
+  * shade: tools/fuzz_shade.py, every shading entry (frames, anti-aliased frames, ray lists) with spherical lights, spheres and
+    depths up to 16 against the oracle, RGB <= 1e-5 and ray counts equal by kind.
 The fallback-ray count is asserted > 0 so that the path "no certificate -> exact walk" stays exercised."""
 import os
 import sys
@@ -61,3 +63,23 @@ def test_fuzz_render_time_boxed(pkg, orc):
     assert tot["bad_rgb"] == 0 and tot["bad_counts"] == 0 and tot["walks_differ"] == 0 and tot["shapes_differ"] == 0, tot
     assert tot["max_err"] <= 1e-5  # BASELINE.json north_star: final pixel RGB within 1e-5 abs
     assert tot["frames"] >= len(seeds) and tot["certified_frames"] > 0
+
+
+def test_fuzz_shade_time_boxed(pkg, orc):
+    """tools/fuzz_shade.py: every shading entry (frames with point and spherical lights, anti-aliased frames, ray lists) on random
+    scenes with spheres, 0-8 point lights, 0-3 spherical lights and depths up to 16, against the oracle.  It derives its draws from the
+    render-seed column differently from fuzz_render (numpy's Generator seeded with (seed, iteration, tag))."""
+    import fuzz_shade
+
+    tot = {}
+    seeds = _seeds()
+    for _, _, rs in seeds:
+        st = fuzz_shade.run(BUDGET_S / len(seeds), rs, verbose=False)
+        for k, v in st.items():
+            tot[k] = max(tot.get(k, 0.0), v) if k == "max_err" else tot.get(k, 0) + v
+    print("fuzz shade:", tot)
+    assert tot["mismatches"] == 0 and tot["bad_counts"] == 0 and tot["walks_differ"] == 0 and tot["shapes_differ"] == 0, tot
+    assert tot["max_err"] <= 1e-5
+    assert tot["iterations"] >= len(seeds)
+    assert tot["frame"] > 0 and tot["aa"] > 0 and tot["rays"] > 0, tot
+    assert tot["spherical"] > 0 and tot["spheres"] > 0 and tot["deep"] > 0, tot
