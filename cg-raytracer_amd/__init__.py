@@ -108,7 +108,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -185,6 +185,8 @@ def lib() -> C.CDLL:
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
     L.cgrt_debug_fastdiv_check.argtypes = [i32, vp, vp, u64, vp, vp]
     L.cgrt_debug_wave_times.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u64]
+    L.cgrt_debug_trace_shadow.argtypes = [vp, vp, vp, u64, i32, u32, u64, u64, vp, u64, u64, u64, vp, vp, vp]
+    L.cgrt_debug_soft_lit.argtypes = [vp, vp, vp, vp, u64, C.POINTER(SoftShadows), i32, i32, vp]
     L.cgrt_record_sizes.argtypes = [C.POINTER(u32)] * 4
     L.cgrt_record_sizes.restype = None
     L.cgrt_ray_triangle_batch.argtypes = [i32, vp, vp, u64, vp, vp, vp]
@@ -745,6 +747,39 @@ class Scene:
         c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
         _check(lib().cgrt_debug_wave_times(self._h, C.byref(c), W, H, _ptr(out), nt))
         return out
+
+    def debug_trace_shadow(self, rays, dist, how: int = 0, dmul: int = 1, capacity: int = 0, expected: int = 0, mirror_rays=None,
+                           mirror_capacity: int = 0, mirror_expected: int = 0):
+        """cgrt_debug_trace_shadow: the frame's shadow-list launchers on caller rays (see include/cgrt.h for `how`).  The ray is in
+        shadow iff `hit && !(t + 0.001f >= dist)`.  Returns hits (n entries for how 0, else max(n, capacity): entries the kernel did
+        not write hold the 0xA5 fill), and for how 2 also (mirror hits, mirror normals), max(nmirror, mirror_capacity) entries each."""
+        r = _as_ray_array(rays)
+        d = np.ascontiguousarray(dist, np.float32).reshape(-1)
+        if len(d) != len(r):
+            raise ValueError("dist needs one entry per ray")
+        n = len(r)
+        hits = np.zeros(n if how == 0 else max(n, capacity), HIT_DTYPE)
+        m = _as_ray_array(mirror_rays if mirror_rays is not None else np.zeros((0, 7), np.float32))
+        mcap = max(len(m), mirror_capacity) if how == 2 else 0
+        mh = np.zeros(mcap, HIT_DTYPE)
+        mn = np.zeros((mcap, 3), np.float32)
+        _check(lib().cgrt_debug_trace_shadow(self._h, _ptr(r), _ptr(d), n, how, dmul, capacity, expected, _ptr(m), len(m), mirror_capacity,
+                                             mirror_expected, _ptr(mh), _ptr(mn), _ptr(hits)))
+        return (hits, mh, mn) if how == 2 else hits
+
+    def debug_soft_lit(self, item_rays, item_hits, item_pixels, spherical, units, samples: int, seed: int = 0, level: int = 0,
+                       anyhit: bool = True) -> np.ndarray:
+        """cgrt_debug_soft_lit: the frame's soft-shadow launcher on caller items (ray + hit + pixel).  Returns lit[nitems, nspherical]
+        (uint32): the samples of each spherical light that reach each item's hit point."""
+        r = _as_ray_array(item_rays)
+        h = np.ascontiguousarray(item_hits, HIT_DTYPE)
+        px = np.ascontiguousarray(item_pixels, np.int32)
+        if len(h) != len(r) or len(px) != len(r):
+            raise ValueError("item_rays, item_hits and item_pixels need the same length")
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        lit = np.zeros((len(r), len(keep[0]) if keep else 0), np.uint32)
+        _check(lib().cgrt_debug_soft_lit(self._h, _ptr(r), _ptr(h), _ptr(px), len(r), q, level, 1 if anyhit else 0, _ptr(lit)))
+        return lit
 
     def count_batch(self, rays: np.ndarray) -> dict:
         rays = _as_ray_array(rays)

@@ -1650,6 +1650,101 @@ int cgrt_debug_wave_times(CgrtScene* s, const CgrtCamera* cam, int W, int H, uin
     return CGRT_OK;
 }
 
+// The frame's shadow-list launchers on caller rays (include/cgrt.h).  Only plumbing: the launches are the ones render_impl issues.
+int cgrt_debug_trace_shadow(CgrtScene* s, const CgrtRay* rays, const float* dist, uint64_t n, int how, uint32_t dmul, uint64_t capacity,
+                            uint64_t expected, const CgrtRay* mirror_rays, uint64_t nmirror, uint64_t mirror_capacity, uint64_t mirror_expected,
+                            CgrtHit* mirror_hits, float* mirror_normals, CgrtHit* hits) {
+    if (how < 0 || how > 2) return fail(CGRT_E_ARG, "how must be 0 (plain), 1 (length on the device) or 2 (paired with a mirror list)");
+    const uint64_t cap = how == 0 ? n : std::max<uint64_t>(n, capacity);
+    if (!s || (n && (!rays || !dist)) || (cap && !hits)) return fail(CGRT_E_ARG, "NULL argument");
+    NEED_DEVICE(s);
+    if (how >= 1) {
+        if (dmul == 0 || n % dmul != 0) return fail(CGRT_E_ARG, "n must be a multiple of dmul >= 1");
+        if (n / dmul > 0xffffffffull) return fail(CGRT_E_ARG, "n / dmul must fit the device word");
+    }
+    const uint64_t mcap = std::max<uint64_t>(nmirror, mirror_capacity);
+    if (how == 2) {
+        if ((nmirror && !mirror_rays) || (mcap && !mirror_hits)) return fail(CGRT_E_ARG, "NULL mirror argument");
+        if (nmirror > 0xffffffffull) return fail(CGRT_E_ARG, "nmirror must fit the device word");
+        if (!can_trace_pair(s->dev)) return fail(CGRT_E_ARG, "the scene or the forced kernel shape does not allow the paired launch");
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    DevBuf dr, dd, dh, dc, mr, mh, mn;
+    HIP_TRY(dr.alloc(cap * sizeof(CgrtRay)));
+    HIP_TRY(dd.alloc(cap * sizeof(float)));
+    HIP_TRY(dh.alloc(cap * sizeof(CgrtHit)));
+    HIP_TRY(dc.alloc(2 * sizeof(uint32_t)));
+    // rays past n (the grid covers them, the device word does not) are zero rays: a kernel that read them would not fault
+    HIP_TRY(hipMemset(dr.p, 0, cap * sizeof(CgrtRay)));
+    HIP_TRY(hipMemset(dd.p, 0, cap * sizeof(float)));
+    HIP_TRY(hipMemset(dh.p, 0xA5, cap * sizeof(CgrtHit)));
+    HIP_TRY(hipMemcpy(dr.p, rays, n * sizeof(CgrtRay), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dd.p, dist, n * sizeof(float), hipMemcpyHostToDevice));
+    const uint32_t words[2] = {how >= 1 ? (uint32_t)(n / dmul) : 0u, (uint32_t)nmirror};
+    HIP_TRY(hipMemcpy(dc.p, words, sizeof(words), hipMemcpyHostToDevice));
+    uint32_t* const dcount = dc.as<uint32_t>();
+    if (how == 0) {
+        HIP_TRY(launch_trace_shadow(s->dev, dr.as<float>(), dd.as<float>(), n, dh.as<CgrtHitDev>(), nullptr));
+    } else if (how == 1) {
+        HIP_TRY(launch_trace_shadow(s->dev, dr.as<float>(), dd.as<float>(), cap, dh.as<CgrtHitDev>(), nullptr, dcount, nullptr, expected, dmul));
+    } else {
+        HIP_TRY(mr.alloc(mcap * sizeof(CgrtRay)));
+        HIP_TRY(mh.alloc(mcap * sizeof(CgrtHit)));
+        HIP_TRY(mn.alloc(mcap * 12));
+        HIP_TRY(hipMemset(mr.p, 0, mcap * sizeof(CgrtRay)));
+        HIP_TRY(hipMemset(mh.p, 0xA5, mcap * sizeof(CgrtHit)));
+        HIP_TRY(hipMemset(mn.p, 0xA5, mcap * 12));
+        HIP_TRY(hipMemcpy(mr.p, mirror_rays, nmirror * sizeof(CgrtRay), hipMemcpyHostToDevice));
+        HIP_TRY(launch_trace_pair(s->dev, dr.as<float>(), dd.as<float>(), cap, dh.as<CgrtHitDev>(), dcount, dmul, expected, mr.as<float>(), mcap,
+                                  mh.as<CgrtHitDev>(), mn.as<float>(), dcount + 1, mirror_expected, nullptr));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(hits, dh.p, cap * sizeof(CgrtHit), hipMemcpyDeviceToHost));
+    if (how == 2 && mcap) {
+        HIP_TRY(hipMemcpy(mirror_hits, mh.p, mcap * sizeof(CgrtHit), hipMemcpyDeviceToHost));
+        if (mirror_normals) HIP_TRY(hipMemcpy(mirror_normals, mn.p, mcap * 12, hipMemcpyDeviceToHost));
+    }
+    return CGRT_OK;
+}
+
+// The frame's soft-shadow launcher on caller items (include/cgrt.h).
+int cgrt_debug_soft_lit(CgrtScene* s, const CgrtRay* item_rays, const CgrtHit* item_hits, const int32_t* item_pixels, uint64_t nitems,
+                        const CgrtSoftShadows* soft, int level, int anyhit, uint32_t* lit) {
+    if (!s || !soft || (nitems && (!item_rays || !item_hits || !item_pixels || !lit))) return fail(CGRT_E_ARG, "NULL argument");
+    if (soft->nspherical && (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
+        return fail(CGRT_E_ARG, "spherical lights need a unit-vector table and 1..2^24 samples");
+    if (level < 0) return fail(CGRT_E_ARG, "level must be >= 0");
+    NEED_DEVICE(s);
+    const uint64_t SL = soft->nspherical;
+    if (nitems == 0 || SL == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    DevBuf dr, dh, dp, dl, du, dlit;
+    HIP_TRY(dr.alloc(nitems * sizeof(CgrtRay)));
+    HIP_TRY(dh.alloc(nitems * sizeof(CgrtHit)));
+    HIP_TRY(dp.alloc(nitems * sizeof(int32_t)));
+    HIP_TRY(dl.alloc(SL * 28));
+    HIP_TRY(du.alloc((size_t)soft->nunits * 12));
+    HIP_TRY(dlit.alloc(nitems * SL * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(dr.p, item_rays, nitems * sizeof(CgrtRay), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dh.p, item_hits, nitems * sizeof(CgrtHit), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dp.p, item_pixels, nitems * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dl.p, soft->spherical, SL * 28, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(du.p, soft->unit_vectors, (size_t)soft->nunits * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dlit.p, 0, nitems * SL * sizeof(uint32_t)));
+    SoftDev Q{};
+    Q.lights = dl.as<float>();
+    Q.units = du.as<float>();
+    Q.nlights = (uint32_t)SL;
+    Q.samples = soft->samples;
+    Q.nunits = soft->nunits;
+    Q.seed = soft->seed;
+    Q.level = (uint32_t)level;
+    HIP_TRY(launch_soft_shadow(s->dev, Q, dr.as<float>(), dh.as<CgrtHitDev>(), dp.as<int>(), nitems, dlit.as<uint32_t>(), anyhit != 0, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(lit, dlit.p, nitems * SL * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
 int cgrt_count_batch(CgrtScene* s, const CgrtRay* rays, uint64_t n, CgrtCounters* out) {
     if (!s || !out || (n && !rays)) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);

@@ -391,6 +391,27 @@ int cgrt_count_batch(CgrtScene* scene, const CgrtRay* rays, uint64_t n, CgrtCoun
  * wave-level iterations of the inner, sub-node and triangle bodies; per-lane maxima of inner/leaf/tri/sub; active
  * lanes.  One record per launched wave: cap_waves >= 4 * 16 * 8 * ceil(ceil(W/64)*ceil(H/64) / 8). */
 int cgrt_debug_wave_times(CgrtScene* scene, const CgrtCamera* cam, int W, int H, uint64_t* out, uint64_t cap_waves);
+/* Diagnostic: the frame's shadow-list launchers on the caller's point-light shadow rays (origin, direction and t as k_spawn
+ * writes them, dist[i] = |fromPosToLight|).  hits[i] is what the frame's k_shade reads: the ray is in shadow iff
+ * `hit && !(t + 0.001f >= dist[i])` (main.cpp:104-135); t and prim_id need not be the closest ones.  `how` picks the path:
+ *   0  launch_trace_shadow, n known on the host;
+ *   1  launch_trace_shadow with the length in a device word: the word holds n / dmul (n % dmul == 0), the list dmul x that, the
+ *      grid covers `capacity` >= n rays; expected = the host's estimate that picks the kernel shape (0: chosen on the device);
+ *   2  launch_trace_pair: the shadow list as in 1, beside a mirror list of nmirror closest-hit rays whose length is in a device word of
+ *      its own (grid for mirror_capacity >= nmirror rays, mirror_expected as expected); CGRT_E_ARG when the scene or the forced
+ *      kernel shape does not allow the paired launch.
+ * Every result is filled with the byte 0xA5 before the launch: an entry the kernel did not write keeps it.  hits receives n
+ * entries (how 0) or max(n, capacity); mirror_hits / mirror_normals (how 2) max(nmirror, mirror_capacity) entries. */
+int cgrt_debug_trace_shadow(CgrtScene* scene, const CgrtRay* rays, const float* dist, uint64_t n, int how, uint32_t dmul, uint64_t capacity,
+                            uint64_t expected, const CgrtRay* mirror_rays, uint64_t nmirror, uint64_t mirror_capacity, uint64_t mirror_expected,
+                            CgrtHit* mirror_hits, float* mirror_normals, CgrtHit* hits);
+/* Diagnostic: the frame's soft-shadow launcher (launch_soft_shadow, main.cpp:168-200) on caller items: item i is the ray
+ * item_rays[i] with its hit item_hits[i] (pointOn = origin + direction * hit.t; items with hit == 0 count nothing), sampled as
+ * pixel item_pixels[i] at recursion level `level` (soft->spherical, unit_vectors, samples, seed as cgrt_render_soft; closest_hit
+ * is ignored).  anyhit: 1 = the first accepting leaf ends a sample ray (the frame's default), 0 = the full closest hit.
+ * lit[i * nspherical + l] receives the number of samples of light l that reach item i. */
+int cgrt_debug_soft_lit(CgrtScene* scene, const CgrtRay* item_rays, const CgrtHit* item_hits, const int32_t* item_pixels, uint64_t nitems,
+                        const CgrtSoftShadows* soft, int level, int anyhit, uint32_t* lit);
 /* Diagnostic: `repeats` launches of a kernel that reads nrecords scattered 64-byte records (one per lane, never twice)
  * from a zeroed table -- a known HBM byte count in the traversal kernels' access shape, for calibrating rocprofv3's
  * FETCH_SIZE on gfx950 (tools/calibrate_fetch_size.sh). */

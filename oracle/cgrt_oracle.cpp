@@ -583,6 +583,29 @@ struct Shader {
         float p = std::pow(c, m.v[6]);
         return l.color * material_ks(m) * p;
     }
+    // main.cpp:173-199: the samples of spherical light li that reach pointOn (the reference's `counter` before the division: a sum
+    // of 1.0f per sample, exact as an integer up to 2^24)
+    uint32_t soft_lit(V3 pointOn, size_t li, uint32_t pixel, int level, RayCounts* nrays) const {
+        const SphericalLight& sl = slights[li];
+        uint32_t counter = 0;
+        for (uint32_t i = 1; i <= samples; i++) {
+            V3 rp = sl.pos + sl.radius * unit_draw(pixel, (uint32_t)level, (uint32_t)li, i - 1);
+            // :178 aggregate initialisation in member order: origin, direction, then t from the new origin
+            Ray nr;
+            nr.o = pointOn + (float)(0.001) * normalize3(rp - pointOn);
+            nr.d = normalize3(rp - pointOn);
+            nr.t = length3(nr.o - rp);
+            HitState hs{mk(0, 0, 0), -1, 0xffffffffu};
+            float lightT = length3(nr.o - rp);
+            if (nrays) nrays->soft++;
+            if (!o->intersect(nr, hs, nullptr)) {
+                counter++;
+            } else if (nr.t > lightT) {
+                counter++;
+            }
+        }
+        return counter;
+    }
     // main.cpp:160-235 (point-light loop :219-232)
     V3 shading(const Ray& r, const HitState& h, const Mat& m, RayCounts* nrays, uint32_t pixel, int level) const {
         V3 pointOn = r.o + r.d * r.t;
@@ -594,23 +617,7 @@ struct Shader {
             V3 toLight = normalize3(l.pos - pointOn);
             V3 dif = diffuse(l, toLight, h, m);
             V3 spec = specular(r, l, toLight, h, m);
-            float counter = 0.0f;
-            for (uint32_t i = 1; i <= samples; i++) {
-                V3 rp = sl.pos + sl.radius * unit_draw(pixel, (uint32_t)level, (uint32_t)li, i - 1);
-                // :178 aggregate initialisation in member order: origin, direction, then t from the new origin
-                Ray nr;
-                nr.o = pointOn + (float)(0.001) * normalize3(rp - pointOn);
-                nr.d = normalize3(rp - pointOn);
-                nr.t = length3(nr.o - rp);
-                HitState hs{mk(0, 0, 0), -1, 0xffffffffu};
-                float lightT = length3(nr.o - rp);
-                if (nrays) nrays->soft++;
-                if (!o->intersect(nr, hs, nullptr)) {
-                    counter += 1.0f;
-                } else if (nr.t > lightT) {
-                    counter += 1.0f;
-                }
-            }
+            float counter = (float)soft_lit(pointOn, li, pixel, level, nrays);
             counter = counter / (float)samples;  // :200 `/ 200.0f`
             res = res + dif * counter;
             res = res + spec * counter;
@@ -897,6 +904,25 @@ uint64_t oracle_shade_rays(void* h, const float* rays, uint64_t n, const float* 
     }
     store_counts(RayCounts{np, ns, nr, nq}, counts);
     return np + ns + nr + nq;
+}
+
+// The soft-shadow counts of main.cpp:173-199 for caller items: item i is the ray rays[7i..7i+6] whose t is its hit's t (pointOn =
+// origin + direction * t, main.cpp:163), sampled as pixel pixels[i] at recursion level `level`; items with hit[i] == 0 (hit optional)
+// count nothing.  lit[i * nslights + l] = samples of spherical light l that reach the item (Shader::soft_lit, the loop shading runs).
+void oracle_soft_lit(void* h, const float* rays, const uint32_t* hit, const int32_t* pixels, uint64_t n, const float* slights, int nslights,
+                     const float* units, uint32_t nunits, uint32_t samples, uint32_t seed, int level, uint32_t* lit, int threads) {
+    const Shader sh = make_shader(h, nullptr, 0, slights, nslights, units, nunits, samples, seed, 2);
+#ifdef _OPENMP
+    if (threads > 0) omp_set_num_threads(threads);
+#endif
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        const float* q = rays + 7 * i;
+        const Ray r{mk(q[0], q[1], q[2]), mk(q[3], q[4], q[5]), q[6]};
+        const V3 pointOn = r.o + r.d * r.t;
+        for (int l = 0; l < nslights; l++)
+            lit[i * nslights + l] = (hit && !hit[i]) ? 0u : sh.soft_lit(pointOn, (size_t)l, (uint32_t)pixels[i], level, nullptr);
+    }
 }
 
 // ---- primitive intersectors, one call per element (for kernel-level parity tests) ----

@@ -66,6 +66,8 @@ def lib(o0: bool = False) -> C.CDLL:
     L.oracle_render_soft_counted.restype = u64
     L.oracle_shade_rays.argtypes = [vp, vp, u64, vp, i32, vp, i32, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, vp, vp, i32]
     L.oracle_shade_rays.restype = u64
+    L.oracle_soft_lit.argtypes = [vp, vp, vp, vp, u64, vp, i32, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, vp, i32]
+    L.oracle_soft_lit.restype = None
     for name in ("oracle_ray_triangle", "oracle_ray_plane", "oracle_ray_box", "oracle_ray_sphere"):
         f = getattr(L, name)
         f.argtypes = [vp, vp, u64, vp]
@@ -192,6 +194,22 @@ class OracleScene:
         self.L.oracle_shade_rays(self.h, _p(r), len(r), _p(lights), len(lights), _p(spherical), len(spherical), _p(units), len(units),
                                  samples, seed, max_level, _p(rgb), _p(cnt), threads)
         return rgb, _counts(cnt)
+
+    def soft_lit(self, item_rays, spherical, units, samples, seed=0, level=0, pixels=None, hit=None, threads=0):
+        """main.cpp:173-199 for caller items: item i is the ray item_rays[i] whose t is its hit's t (n x 7 or the product's RAY dtype),
+        sampled as pixel pixels[i] (default i) at recursion level `level`; items with hit[i] == 0 (optional) count nothing.  Returns
+        lit[n, nspherical] (uint32): the samples of each spherical light that reach the item -- the loop shading() runs."""
+        r = rays7(item_rays)
+        spherical = _f32(spherical, (-1, 7))
+        units = _f32(units, (-1, 3))
+        if len(spherical) and (len(units) == 0 or samples == 0):
+            raise ValueError("spherical lights need a unit-vector table and samples >= 1")
+        px = np.ascontiguousarray(np.arange(len(r)) if pixels is None else pixels, np.int32)
+        hf = None if hit is None else np.ascontiguousarray(hit, np.uint32)
+        lit = np.zeros((len(r), len(spherical)), np.uint32)
+        self.L.oracle_soft_lit(self.h, _p(r), _p(hf), _p(px), len(r), _p(spherical), len(spherical), _p(units), len(units), samples,
+                               seed, level, _p(lit), threads)
+        return lit
 
 
 def generate_rays(cam, W, H, rect=None) -> np.ndarray:

@@ -10,7 +10,8 @@ every round appends one seed):
     RGB <= 1e-5 (BASELINE.json north_star's tolerance), equal ray counts, certified == exact == quad-shape frames byte for byte
     (the first frame of a scene is exactly sized, the later ones are predicted frames: capi.cpp render_impl);
   * shade: tools/fuzz_shade.py, every shading entry (frames, anti-aliased frames, ray lists) with spherical lights, spheres and
-    depths up to 16 against the oracle, RGB <= 1e-5 and ray counts equal by kind.
+    depths up to 16 against the oracle, RGB <= 1e-5 and ray counts equal by kind; and its occlusion leg: the shadow verdicts of
+    cgrt_debug_trace_shadow in every kernel shape and on every path against the oracle's.
 The fallback-ray count is asserted > 0 so that the path "no certificate -> exact walk" stays exercised."""
 import os
 import sys
@@ -83,3 +84,4 @@ def test_fuzz_shade_time_boxed(pkg, orc):
     assert tot["iterations"] >= len(seeds)
     assert tot["frame"] > 0 and tot["aa"] > 0 and tot["rays"] > 0, tot
     assert tot["spherical"] > 0 and tot["spheres"] > 0 and tot["deep"] > 0, tot
+    assert tot["bad_verdicts"] == 0 and tot["occlusion"] >= len(seeds), tot  # the occlusion leg: shadow verdicts equal the oracle's

@@ -7,12 +7,17 @@
   * rays:  cgrt_shade_rays on tests/rayfam.py families plus random rays about the scene, against OracleScene.shade_rays.
 RGB within 1e-5 (NaN at the same positions), ray counts equal by kind; where the scene has a certified walk, the same call in the
 quad-per-ray kernel shape and on the exact walk must give the same bytes.
+Every iteration also runs an occlusion leg on its scene (its own generator): shadow rays spawned from the oracle's hits towards the
+iteration's lights and random ones, plus epsilon-boundary rays (tools/occlfam.py), through cgrt_debug_trace_shadow in every kernel
+shape and on every path (n on the host, length on the device with the grid for a larger capacity, paired with a mirror list where
+the shape allows it); each verdict `hit && !(t + 0.001f >= dist)` must equal the oracle's.
 Usage: python tools/fuzz_shade.py [seconds] [seed]; tests/test_fuzz_gpu.py calls run() over the committed seed list."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import __graft_entry__ as e
+import occlfam
 import rayfam
 pkg = e.load_package(); orc = e.load_oracle()
 
@@ -100,12 +105,40 @@ def _compare(got, gst, want, wc, stats):
     return ok
 
 
+def _occlusion(rng, sc, o, sd, lights, c, ext, cam):
+    """The occlusion leg: False when a verdict of any shape / path differs from the oracle's."""
+    base = np.concatenate([orc.generate_rays(cam, 16, 12), occlfam.aimed_rays(sd, 200, rng)])
+    extra = np.concatenate([lights[:, :3], (c + rng.uniform(-1.5, 1.5, (2, 3)) * ext).astype(np.float32)])
+    sr, sdist = occlfam.spawned(o, sd, base, rng, extra_lights=extra, nrandom=0, max_points=200, threads=THREADS)
+    br, bd = occlfam.boundary(o, sr, threads=THREADS, max_rays=200, rng=rng)
+    rays, dist = np.concatenate([sr, br]), np.concatenate([sdist, bd])
+    k = rng.permutation(len(rays))[:int(rng.choice([1, 17, 64, 700, 2000]))]
+    k = k[: max(1, len(k) // 2 * 2)] if len(k) > 1 else k
+    rays, dist = np.ascontiguousarray(rays[k]), np.ascontiguousarray(dist[k])
+    n = len(rays)
+    want, ref = occlfam.reference(o, rays, dist, threads=THREADS)
+    dmul = 2 if n % 2 == 0 else 1
+    ok = True
+    for shape in (-1, 0, 1, 2, 3):
+        pkg.set_kernel_shape(shape)
+        calls = [dict(how=0), dict(how=1, dmul=dmul, capacity=n + int(rng.integers(0, 200)), expected=int(rng.choice([0, 1, n, 50 * n])))]
+        if sc.walk() and shape in (-1, 0, 2):
+            calls.append(dict(how=2, dmul=dmul, capacity=n + 5, mirror_rays=rays[rng.permutation(n)[: int(rng.integers(0, n + 1))]],
+                              mirror_capacity=int(rng.integers(0, 100))))
+        for kw in calls:
+            got = sc.debug_trace_shadow(rays, dist, **kw)
+            h = got[0][:n] if kw["how"] == 2 else got[:n]
+            ok &= bool(np.isin(h["hit"], (0, 1)).all() and np.array_equal(occlfam.verdict(h["hit"], h["t"], dist), want))
+    pkg.set_kernel_shape(-1)
+    return ok
+
+
 def run(budget=120.0, seed0=1, verbose=True):
     """Fuzz for `budget` seconds from seed `seed0`; returns the statistics (mismatches, bad_counts, walks_differ, shapes_differ must
     be 0)."""
     t_end = time.time() + budget
     stats = dict(iterations=0, frame=0, aa=0, rays=0, spherical=0, spheres=0, deep=0, certified=0, max_err=0.0, mismatches=0,
-                 bad_counts=0, walks_differ=0, shapes_differ=0)
+                 bad_counts=0, walks_differ=0, shapes_differ=0, occlusion=0, bad_verdicts=0)
     t_last = time.time()
     it = 0
     while time.time() < t_end:
@@ -136,7 +169,8 @@ def run(budget=120.0, seed0=1, verbose=True):
         pkg.set_kernel_shape(0)  # lane per ray
         got, gst = call()
         bad = not _compare(got, gst, want, wc, stats)
-        if sc.walk():
+        certified = bool(sc.walk())
+        if certified:
             stats["certified"] += 1
             pkg.set_kernel_shape(1)  # quad per ray
             gq, _ = call()
@@ -148,6 +182,11 @@ def run(budget=120.0, seed0=1, verbose=True):
             if g0.tobytes() != got.tobytes():
                 stats["walks_differ"] += 1; bad = True
         pkg.set_kernel_shape(-1)
+        if certified:
+            sc.set_walk(True)  # (the occlusion leg runs on the scene's default walk)
+        if not _occlusion(np.random.default_rng([seed0, it - 1, 0x0CC1]), sc, o, sd, lights, c, ext, cam):
+            stats["bad_verdicts"] += 1; bad = True
+        stats["occlusion"] += 1
         stats[mode] += 1
         stats["spherical"] += bool(soft)
         stats["spheres"] += len(sd.spheres) > 0
