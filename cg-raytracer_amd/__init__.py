@@ -108,7 +108,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -180,6 +180,12 @@ def lib() -> C.CDLL:
     L.cgrt_debug_export_frame.argtypes = [i32, vp, i32, i32, i32, u64, vp]
     L.cgrt_shade_rays.argtypes = [vp, vp, u64, vp, u32, C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
     L.cgrt_shade_rays_device.argtypes = [vp, vp, u64, vp, u32, C.POINTER(SoftShadows), i32, vp, vp, C.POINTER(RenderStats)]
+    L.cgrt_occluded.argtypes = [vp, vp, u64, vp]
+    L.cgrt_occluded_device.argtypes = [vp, vp, u64, vp, vp]
+    L.cgrt_in_shadow.argtypes = [vp, vp, u64, vp, u32, vp]
+    L.cgrt_in_shadow_device.argtypes = [vp, vp, u64, vp, u32, vp, vp]
+    L.cgrt_soft_lit.argtypes = [vp, vp, u64, C.POINTER(SoftShadows), vp]
+    L.cgrt_soft_lit_device.argtypes = [vp, vp, u64, C.POINTER(SoftShadows), vp, vp]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
     L.cgrt_count_batch.argtypes = [vp, vp, u64, C.POINTER(Counters)]
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
@@ -725,6 +731,127 @@ class Scene:
         st = self.shade_rays_device(rays.data_ptr(), n, out.data_ptr(), stream=stream.cuda_stream, **kw)
         return out, st
 
+    # ---- visibility queries (include/cgrt.h cgrt_occluded*, cgrt_in_shadow*, cgrt_soft_lit*) ----
+    def occluded(self, rays) -> np.ndarray:
+        """cgrt_occluded: the bool BoundingVolumeHierarchy::intersect returns for each ray (a RAY_DTYPE array or (n, 7) float32), the ray's
+        t included (a segment query sets t to its length).  Returns an (n,) bool array."""
+        r = _as_ray_array(rays)
+        hit = np.zeros(len(r), np.uint8)
+        _check(lib().cgrt_occluded(self._h, _ptr(r), len(r), _ptr(hit)))
+        return hit.view(np.bool_)
+
+    def occluded_device(self, d_rays_ptr: int, n: int, d_hit_ptr: int, stream: int = 0) -> None:
+        """cgrt_occluded_device: n rays (7 floats each) at d_rays_ptr -> n bytes at d_hit_ptr, enqueued on the hipStream_t `stream`."""
+        _check(lib().cgrt_occluded_device(self._h, C.c_void_p(d_rays_ptr) if d_rays_ptr else None, int(n),
+                                          C.c_void_p(d_hit_ptr) if d_hit_ptr else None, C.c_void_p(stream) if stream else None))
+
+    def in_shadow(self, points, lights=None) -> np.ndarray:
+        """cgrt_in_shadow: pointInShadow (main.cpp:104-135) of every point ((n, 3) float32) and point light ((nlights, 6) {position,
+        colour}; default: the scene's).  Returns an (n, nlights) bool array."""
+        p = _f32(points, (-1, 3))
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        out = np.zeros((len(p), len(lights)), np.uint8)
+        _check(lib().cgrt_in_shadow(self._h, _ptr(p), len(p), _ptr(lights), len(lights), _ptr(out)))
+        return out.view(np.bool_)
+
+    def in_shadow_device(self, d_points_ptr: int, n: int, d_out_ptr: int, stream: int = 0, lights=None) -> None:
+        """cgrt_in_shadow_device: n points (3 floats each) at d_points_ptr -> n * nlights bytes at d_out_ptr, ordered on `stream`."""
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        _check(lib().cgrt_in_shadow_device(self._h, C.c_void_p(d_points_ptr) if d_points_ptr else None, int(n), _ptr(lights), len(lights),
+                                           C.c_void_p(d_out_ptr) if d_out_ptr else None, C.c_void_p(stream) if stream else None))
+
+    def _soft_query(self, spherical, units, samples: int, seed: int, closest_hit: bool):
+        spherical, units = _f32(spherical, (-1, 7)), _f32(units, (-1, 3))
+        q = SoftShadows(spherical.ctypes.data, units.ctypes.data, len(spherical), samples, len(units), seed, 1 if closest_hit else 0)
+        return q, (spherical, units)
+
+    def soft_lit(self, points, spherical, units, samples: int = 200, seed: int = 0, closest_hit: bool = False) -> np.ndarray:
+        """cgrt_soft_lit: of the `samples` soft-shadow rays of each spherical light ((nspherical, 7)), how many reach each point ((n, 3));
+        sample smp of point i draws as render_soft's pixel i at level 0.  Returns an (n, nspherical) uint32 array."""
+        p = _f32(points, (-1, 3))
+        q, keep = self._soft_query(spherical, units, samples, seed, closest_hit)
+        lit = np.zeros((len(p), len(keep[0])), np.uint32)
+        _check(lib().cgrt_soft_lit(self._h, _ptr(p), len(p), C.byref(q), _ptr(lit)))
+        return lit
+
+    def soft_lit_device(self, d_points_ptr: int, n: int, d_lit_ptr: int, spherical, units, samples: int = 200, seed: int = 0,
+                        closest_hit: bool = False, stream: int = 0) -> None:
+        """cgrt_soft_lit_device: n points at d_points_ptr -> n * nspherical u32 counts at d_lit_ptr, ordered on `stream`."""
+        q, keep = self._soft_query(spherical, units, samples, seed, closest_hit)  # noqa: F841
+        _check(lib().cgrt_soft_lit_device(self._h, C.c_void_p(d_points_ptr) if d_points_ptr else None, int(n), C.byref(q),
+                                          C.c_void_p(d_lit_ptr) if d_lit_ptr else None, C.c_void_p(stream) if stream else None))
+
+    def _query_tensor(self, x, width: int, name: str, out, out_shape, out_dtypes):
+        """Validates a *_tensor query's input ((..., width) float32, contiguous, on the scene's device) and its optional `out` before any
+        call (ValueError otherwise).  Returns n."""
+        import torch
+
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != width:
+            raise ValueError(f"{name} must be a torch tensor of shape (..., {width})")
+        if x.dtype != torch.float32:
+            raise ValueError(f"{name} has dtype {x.dtype}, needs torch.float32")
+        if x.device.type != "cuda" or x.device.index != self.device:
+            raise ValueError(f"{name} is on {x.device}, the scene on cuda:{self.device}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or tuple(out.shape) != out_shape:
+                raise ValueError(f"out must be a torch tensor of shape {out_shape}")
+            if out.dtype not in out_dtypes:
+                raise ValueError(f"out has dtype {out.dtype}, needs one of {out_dtypes}")
+            if out.device.type != "cuda" or out.device.index != self.device:
+                raise ValueError(f"out is on {out.device}, the scene on cuda:{self.device}")
+            if not out.is_contiguous() or (out.element_size() == 4 and out.data_ptr() % 4):
+                raise ValueError("out must be contiguous (and 4-byte aligned for counts)")
+        return x.numel() // width
+
+    def _tensor_call(self, out, shape, dtype, stream, call):
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        _check_one_hip_runtime()
+        if out is None:
+            with torch.cuda.stream(stream):  # (allocated on the stream the answers are written on)
+                out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.numel():  # (an empty tensor has no address to pass: the call would touch nothing anyway)
+            call(out, stream.cuda_stream)
+        return out
+
+    def occluded_tensor(self, rays, out=None, stream=None):
+        """occluded on torch tensors: rays (..., 7) float32 on cuda:<device> -> (...) torch.bool (out may also be torch.uint8),
+        enqueued on `stream` (default: torch.cuda.current_stream())."""
+        import torch
+
+        shape = tuple(rays.shape[:-1]) if isinstance(rays, torch.Tensor) else ()
+        n = self._query_tensor(rays, 7, "rays", out, shape, (torch.bool, torch.uint8))
+        return self._tensor_call(out, shape, torch.bool, stream, lambda o, s: self.occluded_device(rays.data_ptr(), n, o.data_ptr(), stream=s))
+
+    def in_shadow_tensor(self, points, lights=None, out=None, stream=None):
+        """in_shadow on torch tensors: points (..., 3) float32 on cuda:<device> -> (..., nlights) torch.bool (out may also be
+        torch.uint8), ordered on `stream` (default: torch.cuda.current_stream()); lights as in_shadow (a host array)."""
+        import torch
+
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        shape = (tuple(points.shape[:-1]) if isinstance(points, torch.Tensor) else ()) + (len(lights),)
+        n = self._query_tensor(points, 3, "points", out, shape, (torch.bool, torch.uint8))
+        return self._tensor_call(out, shape, torch.bool, stream,
+                                 lambda o, s: self.in_shadow_device(points.data_ptr(), n, o.data_ptr(), stream=s, lights=lights))
+
+    def soft_lit_tensor(self, points, spherical, units, samples: int = 200, seed: int = 0, closest_hit: bool = False, out=None, stream=None):
+        """soft_lit on torch tensors: points (..., 3) float32 on cuda:<device> -> (..., nspherical) torch.int32 counts (at most 2^24, the
+        sample cap), ordered on `stream` (default: torch.cuda.current_stream())."""
+        import torch
+
+        spherical = _f32(spherical, (-1, 7))
+        shape = (tuple(points.shape[:-1]) if isinstance(points, torch.Tensor) else ()) + (len(spherical),)
+        n = self._query_tensor(points, 3, "points", out, shape, (torch.int32,))
+        return self._tensor_call(out, shape, torch.int32, stream,
+                                 lambda o, s: self.soft_lit_device(points.data_ptr(), n, o.data_ptr(), spherical, units, samples=samples,
+                                                                   seed=seed, closest_hit=closest_hit, stream=s))
+
     def generate_rays(self, cam, W: int, H: int, rect=None) -> np.ndarray:
         x0, y0, x1, y1 = rect if rect is not None else (0, 0, W, H)
         rays = np.zeros((x1 - x0) * (y1 - y0), RAY_DTYPE)
@@ -945,6 +1072,9 @@ def host_lib() -> C.CDLL:
         H.cgrt_host_render_bmp.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, i32, i32, i32, i32, C.c_char_p, vp]
         H.cgrt_host_render_aa.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, i32, i32, i32, i32, i32, C.c_char_p, vp, vp]
         H.cgrt_host_shade_rays.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, u32, u32, vp, C.c_uint64, i32, i32, i32, vp, vp]
+        H.cgrt_host_occluded.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, C.c_uint64, vp]
+        H.cgrt_host_in_shadow.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, C.c_uint64, vp]
+        H.cgrt_host_soft_lit.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, u32, u32, u32, vp, C.c_uint64, vp]
         _host = H
     return _host
 
@@ -1114,6 +1244,45 @@ def host_shade_rays(sd: SceneData, rays, max_level: int = 2, driver: str = "devi
         raise RuntimeError("cgrt_host_shade_rays: " + Hl.cgrt_host_last_error().decode())
     return rgb, dict(primary=int(st[0]), shadow=int(st[1]), reflection=int(st[2]), soft_shadow=int(st[3]), seconds_device=float(st[4]),
                      seconds_total=float(st[5]))
+
+
+def _host_scene_args(sd: SceneData):
+    pn, tri = _f32(sd.pos_nrm, (-1, 6)), np.ascontiguousarray(sd.tri, np.uint32).reshape(-1, 3)
+    tm, mats = np.ascontiguousarray(sd.tri_mesh, np.uint32), _f32(sd.materials, (-1, 8))
+    return (pn, tri, tm, mats), (_ptr(pn), len(pn), _ptr(tri), _ptr(tm), len(tri), _ptr(mats), len(mats))
+
+
+def host_occluded(sd: SceneData, rays) -> np.ndarray:
+    """BoundingVolumeHierarchy::intersectsBatch of the C++ mirror (cgrt_occluded).  Meshes only (the mirror's test scenes carry no
+    spheres).  Returns an (n,) bool array."""
+    keep, a = _host_scene_args(sd)  # noqa: F841
+    r = _as_ray_array(rays)
+    out = np.zeros(len(r), np.uint8)
+    if host_lib().cgrt_host_occluded(*a, _ptr(r), len(r), _ptr(out)):
+        raise RuntimeError("cgrt_host_occluded: " + host_lib().cgrt_host_last_error().decode())
+    return out.view(np.bool_)
+
+
+def host_in_shadow(sd: SceneData, points, lights=None) -> np.ndarray:
+    """pointsInShadowOnDevice of the C++ mirror (cgrt_in_shadow) with the scene's point lights.  Returns (n, nlights) bool."""
+    keep, a = _host_scene_args(sd)  # noqa: F841
+    p = _f32(points, (-1, 3))
+    lights = _f32(sd.point_lights if lights is None else lights, (-1, 6))
+    out = np.zeros((len(p), len(lights)), np.uint8)
+    if host_lib().cgrt_host_in_shadow(*a, _ptr(lights), len(lights), _ptr(p), len(p), _ptr(out)):
+        raise RuntimeError("cgrt_host_in_shadow: " + host_lib().cgrt_host_last_error().decode())
+    return out.view(np.bool_)
+
+
+def host_soft_lit(sd: SceneData, points, spherical, units, samples: int = 200, seed: int = 0) -> np.ndarray:
+    """softShadowCountsOnDevice of the C++ mirror (cgrt_soft_lit).  Returns (n, nspherical) uint32."""
+    keep, a = _host_scene_args(sd)  # noqa: F841
+    p = _f32(points, (-1, 3))
+    sph, un = _f32(spherical, (-1, 7)), _f32(units, (-1, 3))
+    lit = np.zeros((len(p), len(sph)), np.uint32)
+    if host_lib().cgrt_host_soft_lit(*a, _ptr(sph), len(sph), _ptr(un), len(un), samples, seed, _ptr(p), len(p), _ptr(lit)):
+        raise RuntimeError("cgrt_host_soft_lit: " + host_lib().cgrt_host_last_error().decode())
+    return lit
 
 
 def host_write_bmp(path: str, rgb, W: int, H: int) -> None:

@@ -209,9 +209,10 @@ struct CgrtScene {
         struct Buf {
             void* p = nullptr;
             size_t cap = 0;
-        } dev[3], pin[3];  // rays / hits / normals
+        } dev[4], pin[4];  // rays / hits / normals / light tables
         void* bounce[2] = {nullptr, nullptr};  // pinned halves of the large-transfer pipeline (lane_upload / lane_download), made on first use
         hipEvent_t bounce_ev[2] = {nullptr, nullptr};
+        hipEvent_t follow = nullptr;  // lane_follow: the lane's stream waits for the caller's, made on first use
         unsigned long long* d_counters = nullptr;
     };
     std::mutex lanes_mutex;
@@ -337,6 +338,7 @@ struct CgrtScene {
                 if (b) (void)hipHostFree(b);
             for (hipEvent_t e : L->bounce_ev)
                 if (e) (void)hipEventDestroy(e);
+            if (L->follow) (void)hipEventDestroy(L->follow);
             if (L->d_counters) (void)hipFree(L->d_counters);
             if (L->stream) (void)hipStreamDestroy(L->stream);
             delete L;
@@ -812,7 +814,7 @@ struct LaneGuard {
         L = n;
         return CGRT_OK;
     }
-    // scratch that only grows (geometrically): k = 0 rays, 1 hits, 2 normals
+    // scratch that only grows (geometrically): k = 0 rays, 1 hits, 2 normals, 3 light tables
     hipError_t dev(int k, size_t bytes, void** out) {
         auto& b = L->dev[k];
         if (b.cap < bytes) {
@@ -2491,6 +2493,168 @@ int cgrt_shade_rays(CgrtScene* s, const CgrtRay* rays, uint64_t n, const float* 
     HIP_TRY(lane_download(g, 1, rgb, dc, n * 12, &staged));
     HIP_TRY(hipStreamSynchronize(g.L->stream));
     if (staged) std::memcpy(rgb, staged, n * 12);
+    return CGRT_OK;
+}
+
+// ---- visibility queries (include/cgrt.h cgrt_occluded*, cgrt_in_shadow*, cgrt_soft_lit*): the reference's intersect() bool, pointInShadow
+// and shading's soft-shadow counts for the caller's rays / points.  Arguments are checked in the order include/cgrt.h states, all before any
+// device work; then a host-only scene is CGRT_E_NO_DEVICE.  None of them touches the scene's frame prediction or frame hints.
+namespace {
+const uint64_t kMaxAnswers = 0x7fffffffull;
+int soft_rules(const CgrtSoftShadows* soft) {  // cgrt_shade_rays' rules; NULL = no spherical lights
+    if (soft && soft->nspherical &&
+        (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
+        return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
+    return CGRT_OK;
+}
+// NULL pointers (the rays / points and the output with n > 0, lights missing), then n and n x per_point above 0x7fffffff
+int query_args(const CgrtScene* s, const void* in, uint64_t n, const void* out, uint64_t per_point, bool lights_missing) {
+    if (!s || (n && (!in || !out)) || lights_missing) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > kMaxAnswers || (per_point && n > kMaxAnswers / per_point)) return fail(CGRT_E_ARG, "too many answers: n (x lights) exceeds 0x7fffffff");
+    return CGRT_OK;
+}
+// The device forms that read the caller's host light tables run on a call lane, behind everything queued on `stream` before the call (an
+// event on `stream` that the lane's stream waits for); they return when the answers are in place.
+hipError_t lane_follow(LaneGuard& g, hipStream_t stream) {
+    hipError_t e = hipSuccess;
+    if (!g.L->follow && (e = hipEventCreateWithFlags(&g.L->follow, hipEventDisableTiming)) != hipSuccess) return e;
+    if ((e = hipEventRecord(g.L->follow, stream)) != hipSuccess) return e;
+    return hipStreamWaitEvent(g.L->stream, g.L->follow, 0);
+}
+// n points x nlights lights on the lane's stream (lights through the lane's slot 3)
+int in_shadow_on_lane(LaneGuard& g, CgrtScene* s, const float* d_points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* d_out) {
+    void* dl = nullptr;
+    HIP_TRY(g.dev(3, (size_t)nlights * 24, &dl));
+    HIP_TRY(lane_upload(g, 3, dl, lights, (size_t)nlights * 24));
+    HIP_TRY(launch_in_shadow(s->dev, d_points, n, static_cast<const float*>(dl), nlights, d_out, g.L->stream));
+    return CGRT_OK;
+}
+// the soft-shadow counts of n points on the lane's stream (spherical lights through slot 3, the unit vectors through slot 2); d_lit zeroed here
+int soft_lit_on_lane(LaneGuard& g, CgrtScene* s, const float* d_points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* d_lit) {
+    const uint64_t SL = soft->nspherical;
+    void *dl = nullptr, *du = nullptr;
+    HIP_TRY(g.dev(3, SL * 28, &dl));
+    HIP_TRY(g.dev(2, (size_t)soft->nunits * 12, &du));
+    HIP_TRY(lane_upload(g, 3, dl, soft->spherical, SL * 28));
+    HIP_TRY(lane_upload(g, 2, du, soft->unit_vectors, (size_t)soft->nunits * 12));
+    HIP_TRY(hipMemsetAsync(d_lit, 0, n * SL * sizeof(uint32_t), g.L->stream));
+    SoftDev Q{};
+    Q.lights = static_cast<const float*>(dl);
+    Q.units = static_cast<const float*>(du);
+    Q.nlights = (uint32_t)SL;
+    Q.samples = soft->samples;
+    Q.nunits = soft->nunits;
+    Q.seed = soft->seed;
+    Q.level = 0;  // (cgrt_shade_rays' convention: pixel = i, level 0)
+    HIP_TRY(launch_soft_points(s->dev, Q, d_points, n, d_lit, soft->closest_hit ? 0 : 1, g.L->stream));
+    return CGRT_OK;
+}
+}  // namespace
+
+int cgrt_occluded_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, uint8_t* d_hit, void* stream) {
+    int rc = query_args(s, d_rays, n, d_hit, 0, false);
+    if (rc) return rc;
+    if ((uintptr_t)d_rays % 4) return fail(CGRT_E_ARG, "d_rays must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_hit, n, "d_hit")) != CGRT_OK) return rc;
+    HIP_TRY(launch_occluded(s->dev, reinterpret_cast<const float*>(d_rays), n, d_hit, static_cast<hipStream_t>(stream)));
+    return CGRT_OK;
+}
+int cgrt_occluded(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint8_t* hit) {
+    int rc = query_args(s, rays, n, hit, 0, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    LaneGuard g(s);
+    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    void *dr = nullptr, *dh = nullptr, *staged = nullptr;
+    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(g.dev(1, n, &dh));
+    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
+    HIP_TRY(launch_occluded(s->dev, static_cast<const float*>(dr), n, static_cast<uint8_t*>(dh), g.L->stream));
+    HIP_TRY(lane_download(g, 1, hit, dh, n, &staged));
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    if (staged) std::memcpy(hit, staged, n);
+    return CGRT_OK;
+}
+
+int cgrt_in_shadow_device(CgrtScene* s, const float* d_points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* d_out, void* stream) {
+    int rc = query_args(s, d_points, n, d_out, nlights, nlights && !lights);
+    if (rc) return rc;
+    if ((uintptr_t)d_points % 4) return fail(CGRT_E_ARG, "d_points must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0 || nlights == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_out, n * nlights, "d_out")) != CGRT_OK) return rc;
+    LaneGuard g(s);
+    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    HIP_TRY(lane_follow(g, static_cast<hipStream_t>(stream)));
+    if ((rc = in_shadow_on_lane(g, s, d_points, n, lights, nlights, d_out)) != CGRT_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    return CGRT_OK;
+}
+int cgrt_in_shadow(CgrtScene* s, const float* points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* out) {
+    int rc = query_args(s, points, n, out, nlights, nlights && !lights);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0 || nlights == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    LaneGuard g(s);
+    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    const uint64_t m = n * nlights;
+    void *dp = nullptr, *dout = nullptr, *staged = nullptr;
+    HIP_TRY(g.dev(0, n * 12, &dp));
+    HIP_TRY(g.dev(1, m, &dout));
+    HIP_TRY(lane_upload(g, 0, dp, points, n * 12));
+    if ((rc = in_shadow_on_lane(g, s, static_cast<const float*>(dp), n, lights, nlights, static_cast<uint8_t*>(dout))) != CGRT_OK) return rc;
+    HIP_TRY(lane_download(g, 1, out, dout, m, &staged));
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    if (staged) std::memcpy(out, staged, m);
+    return CGRT_OK;
+}
+
+int cgrt_soft_lit_device(CgrtScene* s, const float* d_points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* d_lit, void* stream) {
+    const uint32_t SL = soft ? soft->nspherical : 0u;
+    int rc = query_args(s, d_points, n, d_lit, SL, false);
+    if (rc) return rc;
+    if ((rc = soft_rules(soft)) != CGRT_OK) return rc;
+    if ((uintptr_t)d_points % 4 || (uintptr_t)d_lit % 4) return fail(CGRT_E_ARG, "d_points and d_lit must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0 || SL == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_lit, n * SL * 4, "d_lit")) != CGRT_OK) return rc;
+    LaneGuard g(s);
+    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    HIP_TRY(lane_follow(g, static_cast<hipStream_t>(stream)));
+    if ((rc = soft_lit_on_lane(g, s, d_points, n, soft, d_lit)) != CGRT_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    return CGRT_OK;
+}
+int cgrt_soft_lit(CgrtScene* s, const float* points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* lit) {
+    const uint32_t SL = soft ? soft->nspherical : 0u;
+    int rc = query_args(s, points, n, lit, SL, false);
+    if (rc) return rc;
+    if ((rc = soft_rules(soft)) != CGRT_OK) return rc;
+    NEED_DEVICE(s);
+    if (n == 0 || SL == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    LaneGuard g(s);
+    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    const uint64_t m = n * SL * sizeof(uint32_t);
+    void *dp = nullptr, *dl = nullptr, *staged = nullptr;
+    HIP_TRY(g.dev(0, n * 12, &dp));
+    HIP_TRY(g.dev(1, m, &dl));
+    HIP_TRY(lane_upload(g, 0, dp, points, n * 12));
+    if ((rc = soft_lit_on_lane(g, s, static_cast<const float*>(dp), n, soft, static_cast<uint32_t*>(dl))) != CGRT_OK) return rc;
+    HIP_TRY(lane_download(g, 1, lit, dl, m, &staged));
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    if (staged) std::memcpy(lit, staged, m);
     return CGRT_OK;
 }
 

@@ -26,14 +26,24 @@ struct SpawnDev {
     int* next_pixels;
 };
 
-// the shadow ray from pointOn towards the light at lights[6 l]: srays[7 idx ..], sdist[idx]
-__device__ __forceinline__ void spawn_shadow_ray(const float* __restrict__ lights, unsigned l, const F3 pointOn, unsigned long long idx,
-                                                 float* __restrict__ srays, float* __restrict__ sdist) {
+// pointInShadow's ray (main.cpp:104-111) from pointOn towards the light at lights[6 l], in registers: origin o, direction dir and
+// dist = |fromPosToLight|; its t is FLT_MAX.  The frame's spawns below and the point-light query (trace_kernels.hip k_visibility)
+// both build the ray here.
+__device__ __forceinline__ void shadow_ray(const float* __restrict__ lights, unsigned l, const F3 pointOn, F3& o, F3& dir, float& dist) {
     const float eps = 0.001f;
     const float* lp = lights + 6 * l;
     const F3 toLight = sub(f3(lp[0], lp[1], lp[2]), pointOn);
-    const F3 dir = normalize(toLight);
-    const F3 o = add(pointOn, f3(eps * dir.x, eps * dir.y, eps * dir.z));  // ray.origin += epsilon * ray.direction
+    dir = normalize(toLight);
+    o = add(pointOn, f3(eps * dir.x, eps * dir.y, eps * dir.z));  // ray.origin += epsilon * ray.direction
+    dist = length(toLight);
+}
+
+// the shadow ray from pointOn towards the light at lights[6 l]: srays[7 idx ..], sdist[idx]
+__device__ __forceinline__ void spawn_shadow_ray(const float* __restrict__ lights, unsigned l, const F3 pointOn, unsigned long long idx,
+                                                 float* __restrict__ srays, float* __restrict__ sdist) {
+    F3 o, dir;
+    float dist;
+    shadow_ray(lights, l, pointOn, o, dir, dist);
     float* s = srays + 7ull * idx;
     s[0] = o.x;
     s[1] = o.y;
@@ -42,7 +52,7 @@ __device__ __forceinline__ void spawn_shadow_ray(const float* __restrict__ light
     s[4] = dir.y;
     s[5] = dir.z;
     s[6] = 3.402823466e+38f;
-    sdist[idx] = length(toLight);
+    sdist[idx] = dist;
 }
 
 // the mirror ray of a ray with direction d that hit at pointOn with normal nrm: next_rays[7 child ..]

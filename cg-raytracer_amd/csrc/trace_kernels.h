@@ -63,6 +63,14 @@ hipError_t launch_generate_rays(const CameraDev& C, int W, int H, int x0, int y0
 // lit[item * nlights + l] += samples of spherical light l that reach it from item's hit point (zeroed by the caller)
 hipError_t launch_soft_shadow(const SceneDev& S, const SoftDev& Q, const float* rays, const CgrtHitDev* hits, const int* item_pixels,
                               unsigned long long nitems, uint32_t* lit, int anyhit, hipStream_t stream);
+// the same count from the caller's points (npoints x 3 floats), point i sampled as pixel i at level Q.level (cgrt_soft_lit*)
+hipError_t launch_soft_points(const SceneDev& S, const SoftDev& Q, const float* points, unsigned long long npoints, uint32_t* lit, int anyhit,
+                              hipStream_t stream);
+// visibility queries (k_visibility), one byte per answer, laid out by the list's shape: out[i] = BoundingVolumeHierarchy::intersect's bool
+// for rays[i] (cgrt_occluded*); out[i * nlights + l] = pointInShadow(points[i], light l) with lights nlights x 6 floats (cgrt_in_shadow*)
+hipError_t launch_occluded(const SceneDev& S, const float* rays, unsigned long long n, uint8_t* out, hipStream_t stream);
+hipError_t launch_in_shadow(const SceneDev& S, const float* points, unsigned long long npoints, const float* lights, unsigned nlights, uint8_t* out,
+                            hipStream_t stream);
 
 // primary frame for the shading wavefront: only the hits, appended to a compact list; count = one zeroed device word
 hipError_t launch_trace_primary_compact(const SceneDev& S, const CameraDev& C, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals,

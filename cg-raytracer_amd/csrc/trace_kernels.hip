@@ -420,13 +420,82 @@ __global__ CGRT_LB void k_trace_shadow(SceneDev S, const float* __restrict__ ray
     if (COUNT) flush_counters(cnt, active && writer, counters);
 }
 
+// Visibility queries of a caller's (include/cgrt.h cgrt_occluded*, cgrt_in_shadow*): ONE answer byte per query, written by the lane (or
+// quad leader) that owns it -- a wave of 64 queries writes 64 consecutive bytes.  The lanes are laid out like k_trace_batch's (the list
+// shapes: quad, sparse or one query per lane); no answer depends on the shape.
+//   POINTS = false: query g is the ray src[7 g ..] as given, its t included; out[g] = the bool BoundingVolumeHierarchy::intersect returns
+//       (bvh.cpp:850-881).  The meshes are searched with WALK_ANYHIT (k_soft_shadow's argument: the flag of the first accepting leaf is
+//       the reference's flag), the spheres only when no mesh accepted a triangle (bvh.cpp:875-880: the bool is true either way).
+//   POINTS = true: query g = i * nlights + l is pointInShadow(src[3 i ..], light l) (main.cpp:104-135): the ray is built in registers by
+//       the frame's expressions (spawn_rays.h shadow_ray), walked as k_trace_shadow walks it (WALK_OCCLUDED bounded by |fromPosToLight|,
+//       spheres as finish_ray tests them), and out[g] = k_shade's verdict `hit && !(t + 0.001f >= dist)`.
+template <bool POINTS, bool FAST, bool QUAD = false>
+__global__ CGRT_LB void k_visibility(SceneDev S, const float* __restrict__ src, const float* __restrict__ lights, unsigned nlights, unsigned long long n,
+                                     uint8_t* __restrict__ out, unsigned qrpw) {
+    extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
+    const bool sparse = !QUAD && qrpw < 64u;  // (see k_trace_batch)
+    const unsigned long long i = QUAD ? ((unsigned long long)blockIdx.x * qrpw + (threadIdx.x >> 2))
+                                      : (sparse ? (unsigned long long)blockIdx.x * qrpw + threadIdx.x : (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x);
+    const bool writer = !QUAD || (threadIdx.x & 3u) == 0u;
+    const bool active = i < n && (!QUAD || (threadIdx.x >> 2) < qrpw) && (!sparse || threadIdx.x < qrpw);
+    LaneCounters cnt;
+    F3 o = f3(0, 0, 0), d = f3(0, 0, 0);
+    float t = 0.0f, qlen = 0.0f;
+    if (active) {
+        if (POINTS) {
+            const unsigned long long p = i / nlights;
+            const float* q = src + 3 * p;
+            shadow_ray(lights, (unsigned)(i - p * nlights), f3(q[0], q[1], q[2]), o, d, qlen);
+            t = 3.402823466e+38f;
+        } else {
+            const float* r = src + 7 * i;
+            o = f3(r[0], r[1], r[2]);
+            d = f3(r[3], r[4], r[5]);
+            t = r[6];
+        }
+    }
+    uint32_t hit_rec = REF_NONE;
+    constexpr int MODE = POINTS ? WALK_OCCLUDED : WALK_ANYHIT;
+    if (QUAD)
+        walk_tree_quad<false, MODE>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), cnt, qlen);
+    else
+        walk_tree<false, FAST, MODE>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), CGRT_WAVE_MAP(s_lds), cnt, qlen);
+    if (active && writer) {
+        // (the query's index is rebuilt rather than kept in two registers through the walk; n <= 0x7fffffff)
+        const uint32_t k = QUAD ? blockIdx.x * qrpw + (threadIdx.x >> 2) : (sparse ? blockIdx.x * qrpw + threadIdx.x : blockIdx.x * blockDim.x + threadIdx.x);
+        bool v;
+        if (POINTS) {
+            CgrtHitDev h;
+            F3 nn;
+            resolve_hit(S, o, d, t, hit_rec, false, h, nn);
+            const uint32_t p = k / nlights;  // (|fromPosToLight| is computed again rather than kept through the walk)
+            const float* q = src + 3ull * p;
+            F3 o2, d2;
+            float dist;
+            shadow_ray(lights, k - p * nlights, f3(q[0], q[1], q[2]), o2, d2, dist);
+            v = h.hit && !(h.t + CGRT_SHADOW_EPS >= dist);  // k_shade, main.cpp:118-130
+        } else {
+            v = hit_rec != REF_NONE;
+            if (!v) {
+                for (uint32_t s = 0; s < S.nspheres; s++) {
+                    F3 nrm;
+                    v |= ray_sphere(f3(S.spheres[s].c[0], S.spheres[s].c[1], S.spheres[s].c[2]), S.spheres[s].radius, o, d, t, nrm);
+                }
+            }
+        }
+        out[k] = v ? 1u : 0u;
+    }
+}
+
 // Soft shadows of spherical lights (main.cpp:168-218): `samples` shadow rays per (hit item, light), generated in
 // registers from the item's ray + hit and the unit-vector table (no ray buffer: 200 samples x 2 M hits would be 12 GB),
 // traversed, and counted: lit[item * nlights + l] = number of samples with !intersect || ray.t > lightT (:183-199).
 // Thread g = (item * nlights + l) * samples + smp: a wave's rays leave one or two surface points towards one small
 // sphere, the most coherent batch this library sees.  ANYHIT stops a ray at its first accepting leaf: the count needs
 // the hit flag only (an accepted t is below lightT by construction, or 0 from the on-plane rule, never above).
-template <bool ANYHIT, bool FAST>
+// POINTS: the items are the caller's points (cgrt_soft_lit*): `rays` holds 3 floats per item, pointOn = that point, every item is live and
+// samples as pixel = item (hits and item_pixels are not read).
+template <bool ANYHIT, bool FAST, bool POINTS = false>
 __global__ CGRT_LB void k_soft_shadow(SceneDev S, SoftDev Q, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
                                       const int* __restrict__ item_pixels, unsigned long long nthreads, uint32_t* __restrict__ lit) {
     extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
@@ -437,14 +506,23 @@ __global__ CGRT_LB void k_soft_shadow(SceneDev S, SoftDev Q, const float* __rest
     const unsigned long long item = key / Q.nlights;
     const uint32_t l = (uint32_t)(key - item * Q.nlights);
     bool is_lit = false;
-    const bool live = in && hits[item].hit != 0;
+    const bool live = in && (POINTS || hits[item].hit != 0);
     F3 o = f3(0, 0, 0), d = f3(0, 0, 0);
     float t = 0.0f;
     if (live) {
-        const float* r = rays + 7 * item;
-        const F3 pointOn = add(f3(r[0], r[1], r[2]), scale(f3(r[3], r[4], r[5]), hits[item].t));
+        F3 pointOn;
+        uint32_t pixel;
+        if (POINTS) {
+            const float* p = rays + 3 * item;
+            pointOn = f3(p[0], p[1], p[2]);
+            pixel = (uint32_t)item;
+        } else {
+            const float* r = rays + 7 * item;
+            pointOn = add(f3(r[0], r[1], r[2]), scale(f3(r[3], r[4], r[5]), hits[item].t));
+            pixel = (uint32_t)item_pixels[item];
+        }
         const float* L = Q.lights + 7 * l;
-        const float* u = Q.units + 3ull * soft_sample_index(Q.seed, (uint32_t)item_pixels[item], Q.level, l, smp, Q.nunits);
+        const float* u = Q.units + 3ull * soft_sample_index(Q.seed, pixel, Q.level, l, smp, Q.nunits);
         soft_shadow_ray(pointOn, f3(L[0], L[1], L[2]), L[3], f3(u[0], u[1], u[2]), o, d, t);
     }
     const float lightT = t;
@@ -736,6 +814,50 @@ hipError_t launch_soft_shadow(const SceneDev& S, const SoftDev& Q, const float* 
     else
         CGRT_LAUNCH2(k_soft_shadow, false, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
     return hipGetLastError();
+}
+hipError_t launch_soft_points(const SceneDev& S, const SoftDev& Q, const float* points, unsigned long long npoints, uint32_t* lit, int anyhit,
+                              hipStream_t stream) {
+    const unsigned long long nthreads = npoints * Q.nlights * Q.samples;
+    if (nthreads == 0) return hipSuccess;
+    const unsigned block = (unsigned)trace_block(S);
+    const unsigned long long blocks = (nthreads + block - 1) / block;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const bool fast = S.fast_root != REF_NONE;
+    const dim3 grid((unsigned)blocks), threads(block);
+    if (anyhit && fast)
+        hipLaunchKernelGGL((k_soft_shadow<true, true, true>), grid, threads, lds_bytes(block), stream, S, Q, points, nullptr, nullptr, nthreads, lit);
+    else if (anyhit)
+        hipLaunchKernelGGL((k_soft_shadow<true, false, true>), grid, threads, lds_bytes(block), stream, S, Q, points, nullptr, nullptr, nthreads, lit);
+    else if (fast)
+        hipLaunchKernelGGL((k_soft_shadow<false, true, true>), grid, threads, lds_bytes(block), stream, S, Q, points, nullptr, nullptr, nthreads, lit);
+    else
+        hipLaunchKernelGGL((k_soft_shadow<false, false, true>), grid, threads, lds_bytes(block), stream, S, Q, points, nullptr, nullptr, nthreads, lit);
+    return hipGetLastError();
+}
+// The visibility queries (k_visibility): n answers, laid out by the list's shape (list_shape, as launch_trace_batch; forced by
+// cgrt_set_kernel_shape).  POINTS: src holds n / nlights points.
+template <bool POINTS>
+static hipError_t launch_visibility(const SceneDev& S, const float* src, const float* lights, unsigned nlights, unsigned long long n, uint8_t* out,
+                                    hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const unsigned block = (unsigned)trace_block(S);
+    const bool fast = S.fast_root != REF_NONE;
+    const int shape = list_shape(S, n);
+    if (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4) {
+        const unsigned q = shape == SHAPE_QUAD4 ? 4u : 16u;
+        CGRT_LAUNCHQ(k_visibility, POINTS, grid_for(n, q), stream, S, src, lights, nlights, n, out, q);
+        return hipGetLastError();
+    }
+    const unsigned rpw = shape == SHAPE_LANE16 ? 16u : 64u;
+    CGRT_LAUNCH2(k_visibility, POINTS, fast, lane_grid(n, block, rpw, 0u), block, stream, S, src, lights, nlights, n, out, rpw);
+    return hipGetLastError();
+}
+hipError_t launch_occluded(const SceneDev& S, const float* rays, unsigned long long n, uint8_t* out, hipStream_t stream) {
+    return launch_visibility<false>(S, rays, nullptr, 0u, n, out, stream);
+}
+hipError_t launch_in_shadow(const SceneDev& S, const float* points, unsigned long long npoints, const float* lights, unsigned nlights, uint8_t* out,
+                            hipStream_t stream) {
+    return launch_visibility<true>(S, points, lights, nlights, npoints * nlights, out, stream);
 }
 // One word into host-visible memory, behind whatever the stream holds: lets a host thread wait for a launch by looking at its own
 // memory instead of sleeping in a runtime call (capi.cpp combined_intersect).

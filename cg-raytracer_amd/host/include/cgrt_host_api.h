@@ -41,6 +41,9 @@ public:
     // n independent intersect() calls: rays[i].t and hitInfos[i] are updated exactly like n sequential calls;
     // hit[i] receives the return value; primIds (optional) the primitive id of include/cgrt.h.
     void intersectBatch(Ray* rays, HitInfo* hitInfos, uint8_t* hit, size_t n, uint32_t* primIds = nullptr) const;
+    // intersect()'s return value for n rays (include/cgrt.h cgrt_occluded: any-hit walk, one byte per ray): hit[i] = 1 iff intersect(rays[i],
+    // ...) would return true.  The rays and any HitInfo stay untouched -- a visibility question needs neither the closest t nor the normal.
+    void intersectsBatch(const Ray* rays, size_t n, uint8_t* hit) const;
     // Whole primary frame with on-device ray generation; outputs indexed y*W+x.
     void tracePrimary(const CgrtCamera& cam, int W, int H, Ray* rays, HitInfo* hitInfos, uint8_t* hit) const;
 

@@ -68,6 +68,13 @@ RenderStats getFinalColorsOnDevice(const Scene& scene, const BoundingVolumeHiera
                                    const SoftShadowSampler* sampler = nullptr);
 RenderStats getFinalColorsPerRay(const Scene& scene, const BoundingVolumeHierarchy& bvh, const Ray* rays, size_t n, float* rgb, int maxLevel = 2,
                                  const SoftShadowSampler* sampler = nullptr, int threads = 0);
+// The visibility questions of shading (main.cpp:104-200) for the caller's points, on the device (include/cgrt.h cgrt_in_shadow, cgrt_soft_lit):
+//   pointsInShadowOnDevice: inShadow[i * scene.pointLights.size() + l] = pointInShadow(points[i], scene.pointLights[l], bvh);
+//   softShadowCountsOnDevice: lit[i * scene.sphericalLight.size() + l] = the samples of spherical light l that reach points[i] (sample smp
+//     draws as pixel i at level 0; sampler nullptr -> SoftShadowSampler::gaussian()).
+void pointsInShadowOnDevice(const Scene& scene, const BoundingVolumeHierarchy& bvh, const cgrt::vec3* points, size_t n, uint8_t* inShadow);
+void softShadowCountsOnDevice(const Scene& scene, const BoundingVolumeHierarchy& bvh, const cgrt::vec3* points, size_t n, uint32_t* lit,
+                              const SoftShadowSampler* sampler = nullptr);
 // sampler: required when the scene has spherical lights (nullptr -> SoftShadowSampler::gaussian()).
 RenderStats renderRayTracing(const Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, Screen& screen, int maxLevel = 2,
                              const SoftShadowSampler* sampler = nullptr, bool antiAliasing = false);

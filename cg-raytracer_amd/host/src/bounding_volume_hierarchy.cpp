@@ -77,6 +77,11 @@ void BoundingVolumeHierarchy::intersectBatch(Ray* rays, HitInfo* hitInfos, uint8
     }
 }
 
+void BoundingVolumeHierarchy::intersectsBatch(const Ray* rays, size_t n, uint8_t* hit) const {
+    if (n == 0) return;
+    if (cgrt_occluded(m_handle.get(), reinterpret_cast<const CgrtRay*>(rays), n, hit) != CGRT_OK) fail("cgrt_occluded");
+}
+
 bool BoundingVolumeHierarchy::intersect(Ray& ray, HitInfo& hitInfo) const {
     uint8_t h = 0;
     intersectBatch(&ray, &hitInfo, &h, 1);

@@ -222,6 +222,65 @@ int cgrt_host_shade_rays(const float* pos_nrm, uint32_t nverts, const uint32_t* 
     }
 }
 
+// The visibility queries through the mirror (tests): what = 0 BoundingVolumeHierarchy::intersectsBatch on n rays (7 floats each) -> out
+// (n bytes); 1 pointsInShadowOnDevice on n points (3 floats each) -> out (n x nlights bytes); 2 softShadowCountsOnDevice -> out (n x
+// nspherical u32; nunits == 0: SoftShadowSampler::gaussian()'s table).  Exported as cgrt_host_occluded / _in_shadow / _soft_lit below.
+static int host_visibility(const float* pos_nrm, uint32_t nverts, const uint32_t* tri, const uint32_t* tri_mesh, uint32_t ntris,
+                         const float* materials, uint32_t nmesh, const float* lights, uint32_t nlights, const float* spherical,
+                         uint32_t nspherical, const float* units, uint32_t nunits, uint32_t samples, uint32_t seed, int what,
+                         const float* in, uint64_t n, void* out) {
+    try {
+        Scene sc = scene_from_arrays(pos_nrm, nverts, tri, tri_mesh, ntris, materials, nmesh, lights, nlights);
+        for (uint32_t i = 0; i < nspherical; i++) {
+            const float* q = spherical + 7 * i;
+            sc.sphericalLight.push_back(SphericalLight{cgrt::vec3(q[0], q[1], q[2]), q[3], cgrt::vec3(q[4], q[5], q[6])});
+        }
+        SoftShadowSampler sampler;
+        if (nunits) {
+            for (uint32_t i = 0; i < nunits; i++) sampler.units.push_back(cgrt::vec3(units[3 * i], units[3 * i + 1], units[3 * i + 2]));
+        } else {
+            sampler = SoftShadowSampler::gaussian();
+        }
+        sampler.samples = samples;
+        sampler.seed = seed;
+        BoundingVolumeHierarchy bvh(&sc);
+        if (what == 0) {
+            std::vector<Ray> rs(n);
+            for (uint64_t i = 0; i < n; i++) {
+                const float* r = in + 7 * i;
+                rs[i] = Ray{cgrt::vec3(r[0], r[1], r[2]), cgrt::vec3(r[3], r[4], r[5]), r[6]};
+            }
+            bvh.intersectsBatch(rs.data(), rs.size(), static_cast<uint8_t*>(out));
+        } else {
+            std::vector<cgrt::vec3> ps(n);
+            for (uint64_t i = 0; i < n; i++) ps[i] = cgrt::vec3(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+            if (what == 1)
+                pointsInShadowOnDevice(sc, bvh, ps.data(), ps.size(), static_cast<uint8_t*>(out));
+            else
+                softShadowCountsOnDevice(sc, bvh, ps.data(), ps.size(), static_cast<uint32_t*>(out), &sampler);
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
+int cgrt_host_occluded(const float* pos_nrm, uint32_t nverts, const uint32_t* tri, const uint32_t* tri_mesh, uint32_t ntris, const float* materials,
+                       uint32_t nmesh, const float* rays, uint64_t n, uint8_t* hit) {
+    return host_visibility(pos_nrm, nverts, tri, tri_mesh, ntris, materials, nmesh, nullptr, 0, nullptr, 0, nullptr, 0, 0, 0, 0, rays, n, hit);
+}
+int cgrt_host_in_shadow(const float* pos_nrm, uint32_t nverts, const uint32_t* tri, const uint32_t* tri_mesh, uint32_t ntris, const float* materials,
+                        uint32_t nmesh, const float* lights, uint32_t nlights, const float* points, uint64_t n, uint8_t* out) {
+    return host_visibility(pos_nrm, nverts, tri, tri_mesh, ntris, materials, nmesh, lights, nlights, nullptr, 0, nullptr, 0, 0, 0, 1, points, n, out);
+}
+int cgrt_host_soft_lit(const float* pos_nrm, uint32_t nverts, const uint32_t* tri, const uint32_t* tri_mesh, uint32_t ntris, const float* materials,
+                       uint32_t nmesh, const float* spherical, uint32_t nspherical, const float* units, uint32_t nunits, uint32_t samples,
+                       uint32_t seed, const float* points, uint64_t n, uint32_t* lit) {
+    return host_visibility(pos_nrm, nverts, tri, tri_mesh, ntris, materials, nmesh, nullptr, 0, spherical, nspherical, units, nunits, samples, seed, 2,
+                           points, n, lit);
+}
+
 // Loads an OBJ with the host loader and reports sizes; a second call with buffers copies the flat arrays out.
 int cgrt_host_load_obj(const char* path, int normalize, uint32_t* nverts, uint32_t* ntris, uint32_t* nmesh, float* pos_nrm, uint32_t* tri,
                        uint32_t* tri_mesh, float* materials) {

@@ -673,6 +673,20 @@ RenderStats getFinalColorsOnDevice(const Scene& scene, const BoundingVolumeHiera
     return stats_of(cs, t_begin);
 }
 
+void pointsInShadowOnDevice(const Scene& scene, const BoundingVolumeHierarchy& bvh, const vec3* points, size_t n, uint8_t* inShadow) {
+    static_assert(sizeof(vec3) == 12, "vec3 must be three packed floats");
+    const DeviceLights dl(scene, nullptr);
+    if (cgrt_in_shadow(bvh.handle(), reinterpret_cast<const float*>(points), n, dl.lights.data(), (uint32_t)scene.pointLights.size(), inShadow) != 0)
+        throw std::runtime_error(std::string("cgrt_in_shadow: ") + cgrt_last_error());
+}
+
+void softShadowCountsOnDevice(const Scene& scene, const BoundingVolumeHierarchy& bvh, const vec3* points, size_t n, uint32_t* lit,
+                              const SoftShadowSampler* sampler) {
+    const DeviceLights dl(scene, sampler);
+    if (cgrt_soft_lit(bvh.handle(), reinterpret_cast<const float*>(points), n, dl.soft_or_null(), lit) != 0)
+        throw std::runtime_error(std::string("cgrt_soft_lit: ") + cgrt_last_error());
+}
+
 RenderStats getFinalColorsPerRay(const Scene& scene, const BoundingVolumeHierarchy& bvh, const Ray* rays, size_t n, float* rgb, int maxLevel,
                                  const SoftShadowSampler* sampler, int threads) {
     RenderStats st;

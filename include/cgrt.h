@@ -382,6 +382,50 @@ int cgrt_shade_rays(CgrtScene* scene, const CgrtRay* rays, uint64_t n, const flo
 int cgrt_shade_rays_device(CgrtScene* scene, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights,
                            const CgrtSoftShadows* soft, int max_level, float* d_rgb, void* stream, CgrtRenderStats* stats);
 
+/* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
+ * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
+ * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
+ * call lane like cgrt_intersect_batch: any number of threads may query one scene at once.
+ *
+ * cgrt_occluded: hit[i] = the bool BoundingVolumeHierarchy::intersect(rays[i], hitInfo) returns (bvh.cpp:850-881) -- true iff a triangle
+ * or a sphere is hit before rays[i].t.  The ray is taken as given, t included (the `t >= ray.t` rule): a segment query sets t to the
+ * segment's length.  The meshes are searched with the any-hit walk (the first leaf that accepts a triangle ends it, as the soft-shadow
+ * samples of cgrt_render_soft end); the spheres are tested only when no mesh accepted a triangle (bvh.cpp:875-880).  hit[i] is 0 or 1.
+ * Kernel shape by the list's size, as cgrt_intersect_batch (cgrt_set_kernel_shape forces it).
+ * Checks, all CGRT_E_ARG, in this order: NULL scene, or NULL rays or hit with n > 0; n > 0x7fffffff; (device form) d_rays not 4-byte
+ * aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and touches nothing.  Device form: then d_rays (n * 28 bytes) and
+ * d_hit (n bytes) not device memory of the scene's device (as cgrt_shade_rays_device checks them) -> CGRT_E_ARG, before any device work.
+ * cgrt_occluded_device reads no host array: it only enqueues on `stream` (NULL = default stream), asynchronously, like
+ * cgrt_intersect_batch_device. */
+int cgrt_occluded(CgrtScene* scene, const CgrtRay* rays, uint64_t n, uint8_t* hit);
+int cgrt_occluded_device(CgrtScene* scene, const CgrtRay* d_rays, uint64_t n, uint8_t* d_hit, void* stream);
+/* cgrt_in_shadow: out[i * nlights + l] = pointInShadow(points[i], lights[l], bvh) (main.cpp:104-135) for every point and light: the ray
+ * from point + 0.001f * dir towards the light, in shadow iff `hit && !(ray.t + 0.001f >= |fromPosToLight|)`.  points: n x 3 floats;
+ * lights: nlights x 6 floats {position, colour} as the render entries take them (colour ignored), a HOST pointer in both forms.  The ray
+ * is built by the frame's own expressions and walked as the frame's shadow lists are (bounded by the light's distance).
+ * Kernel shape by n * nlights, as a ray list of that length.
+ * Checks, all CGRT_E_ARG, in this order: NULL scene, NULL points or out with n > 0, or nlights > 0 with NULL lights; n > 0x7fffffff or
+ * n * nlights > 0x7fffffff; (device form) d_points not 4-byte aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 or nlights == 0
+ * succeeds and touches nothing.  Device form: then d_points (n * 12 bytes) and d_out (n * nlights bytes) checked as device memory of the
+ * scene's device -> CGRT_E_ARG.
+ * cgrt_in_shadow_device: ordered like cgrt_shade_rays_device -- the work runs after everything enqueued on `stream` before the call, and
+ * the call returns when the answers are in d_out (the light table goes up through the library's own staging).  The stream is not kept. */
+int cgrt_in_shadow(CgrtScene* scene, const float* points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* out);
+int cgrt_in_shadow_device(CgrtScene* scene, const float* d_points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* d_out,
+                          void* stream);
+/* cgrt_soft_lit: lit[i * nspherical + l] = the number of the `samples` soft-shadow rays of spherical light l that reach points[i]
+ * (shading's loop, main.cpp:168-200: !intersect || ray.t > lightT).  Sample smp draws as cgrt_render_soft does with pixel = i and level 0
+ * -- cgrt_shade_rays' convention for its rays -- so the counts of a ray's level-0 hit point are the counts its shading uses.
+ * soft->closest_hit as in cgrt_render_soft (0: any-hit sample rays, 1: closest hit; the counts are equal).  soft == NULL: no lights.
+ * Checks, all CGRT_E_ARG, in this order: NULL scene, or NULL points or lit with n > 0; n > 0x7fffffff or n * nspherical > 0x7fffffff;
+ * bad soft (cgrt_shade_rays' rules); (device form) d_points or d_lit not 4-byte aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.
+ * n == 0 or nspherical == 0 succeeds and touches nothing.  Device form: then d_points (n * 12 bytes) and d_lit (n * nspherical * 4 bytes)
+ * checked as device memory of the scene's device -> CGRT_E_ARG.
+ * cgrt_soft_lit_device: d_lit is zeroed and counted behind everything enqueued on `stream` before the call; the call returns when the
+ * counts are in place (soft's tables are host arrays, as in cgrt_shade_rays_device). */
+int cgrt_soft_lit(CgrtScene* scene, const float* points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* lit);
+int cgrt_soft_lit_device(CgrtScene* scene, const float* d_points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* d_lit, void* stream);
+
 /* Work counters of the same traversal (separate instrumented launch; not part of any timed region). */
 int cgrt_count_primary(CgrtScene* scene, const CgrtCamera* cam, int W, int H, int x0, int y0, int x1, int y1,
                        int rank, int nranks, CgrtCounters* out);
