@@ -108,7 +108,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -180,6 +180,9 @@ def lib() -> C.CDLL:
     L.cgrt_debug_export_frame.argtypes = [i32, vp, i32, i32, i32, u64, vp]
     L.cgrt_shade_rays.argtypes = [vp, vp, u64, vp, u32, C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
     L.cgrt_shade_rays_device.argtypes = [vp, vp, u64, vp, u32, C.POINTER(SoftShadows), i32, vp, vp, C.POINTER(RenderStats)]
+    L.cgrt_trace_primary_views_device.argtypes = [vp, vp, u32, i32, i32, vp, vp, vp]
+    L.cgrt_render_views.argtypes = [vp, vp, u32, i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
+    L.cgrt_render_views_device.argtypes = [vp, vp, u32, i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, i32, vp, C.POINTER(RenderStats)]
     L.cgrt_occluded.argtypes = [vp, vp, u64, vp]
     L.cgrt_occluded_device.argtypes = [vp, vp, u64, vp, vp]
     L.cgrt_in_shadow.argtypes = [vp, vp, u64, vp, u32, vp]
@@ -385,6 +388,21 @@ def _frame_tensor_row_bytes(out, fmt: int, W: int, H: int, device: int) -> int:
     if not ok or out.data_ptr() % 4 or (pitched and (row_bytes < W * (12 if fmt == 0 else 4) or row_bytes % 4)):
         raise ValueError(f"out's strides {st} (or its alignment) do not fit the format's row layout")
     return row_bytes if pitched else 0
+
+
+def camera_array(cams) -> np.ndarray:
+    """A batch of cameras for the *_views entries as a contiguous CgrtCamera array: from a (B, 9) float32 array in the layout of
+    Camera.from_array (look_at, euler, distance, fovy, aspect) or a sequence of Camera.  Returns a (B, 9) float32 array (ValueError
+    otherwise)."""
+    if isinstance(cams, np.ndarray) or not all(isinstance(c, Camera) for c in cams):
+        a = np.ascontiguousarray(np.asarray(cams, np.float32))
+        if a.ndim != 2 or a.shape[1] != 9:
+            raise ValueError(f"cams must be a (B, 9) float32 array or a sequence of Camera, not shape {a.shape}")
+        return a
+    a = np.empty((len(cams), 9), np.float32)
+    for i, c in enumerate(cams):
+        a[i, 0:3], a[i, 3:6], a[i, 6:9] = c.look_at[:], c.euler[:], (c.distance, c.fovy, c.aspect)
+    return a
 
 
 def unit_vector_table(n: int = 1 << 16, seed: int = 0) -> np.ndarray:
@@ -659,6 +677,81 @@ class Scene:
             with torch.cuda.stream(stream):  # (allocated, and zeroed, on the stream the frame is exported on)
                 out = (torch.zeros if kw.get("nranks", 1) > 1 else torch.empty)(shape, dtype=dtype, device=dev)
         st = self.render_device(cam, W, H, out.data_ptr(), format=fmt, row_bytes=row_bytes, stream=stream.cuda_stream, **kw)
+        return out, st
+
+    # ---- multi-view frames (include/cgrt.h cgrt_*_views*) ----
+    def trace_views_device(self, cams, W: int, H: int, d_hits_ptr: int, d_normals_ptr: int = 0, stream: int = 0) -> None:
+        """cgrt_trace_primary_views_device: the primary hits of B cameras ((B, 9) array or sequence of Camera) into B*W*H CgrtHit at
+        d_hits_ptr (and B*W*H*3 floats at d_normals_ptr), view b's pixel (x, y) at b*W*H + y*W + x; asynchronous on `stream`."""
+        a = camera_array(cams)
+        _check(
+            lib().cgrt_trace_primary_views_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, C.c_void_p(d_hits_ptr) if d_hits_ptr else None,
+                C.c_void_p(d_normals_ptr) if d_normals_ptr else None, C.c_void_p(stream) if stream else None,
+            )
+        )  # fmt: skip
+
+    def render_views(self, cams, W: int, H: int, lights=None, max_level: int = 2, spherical=None, units=None, samples: int = 200,
+                     seed: int = 0):
+        """cgrt_render_views: view b of the result is render_soft (render without spherical lights) of cams[b], bit for bit; one primary
+        launch and one wavefront for all views.  Returns (rgb[B, W*H, 3], stats dict summed over the views)."""
+        a = camera_array(cams)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        rgb = np.zeros((len(a), W * H, 3), np.float32)
+        st = RenderStats()
+        _check(lib().cgrt_render_views(self._h, _ptr(a) if len(a) else None, len(a), W, H, _ptr(lights), len(lights), q, max_level, _ptr(rgb),
+                                       C.byref(st)))
+        return rgb, {k: getattr(st, k) for k, _ in st._fields_}
+
+    def render_views_device(self, cams, W: int, H: int, d_out_ptr: int, format="rgb", stream: int = 0, lights=None, max_level: int = 2,
+                            spherical=None, units=None, samples: int = 200, seed: int = 0) -> dict:
+        """cgrt_render_views_device: the views exported into device memory at d_out_ptr, view b at b * (packed frame bytes), each in the
+        packed layout of render_device's `format`; enqueued on the hipStream_t `stream`.  Raw integers, as render_device.  Returns stats."""
+        a = camera_array(cams)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        st = RenderStats()
+        _check(
+            lib().cgrt_render_views_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, _ptr(lights), len(lights), q, max_level,
+                C.c_void_p(d_out_ptr) if d_out_ptr else None, _frame_format(format), C.c_void_p(stream) if stream else None, C.byref(st),
+            )
+        )  # fmt: skip
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def render_views_tensor(self, cams, W: int, H: int, format="rgb", out=None, stream=None, **kw):
+        """render_views_device into a torch tensor on cuda:<device>: (B, H, W, 3) f32, (B, 3, H, W) f32 or (B, H, W, 4) u8 -- `out`
+        (contiguous, of exactly that shape and dtype; validated before any call, ValueError) or a new tensor, rendered on `stream`
+        (default: torch.cuda.current_stream()).  Other keywords as render_views.  Returns (tensor, stats dict)."""
+        import torch
+
+        a = camera_array(cams)
+        fmt = _frame_format(format)
+        B = len(a)
+        shape, dtype = {0: ((B, H, W, 3), torch.float32), 1: ((B, 3, H, W), torch.float32), 2: ((B, H, W, 4), torch.uint8)}.get(fmt, (None, None))
+        if shape is None:
+            raise ValueError(f"format must be one of {sorted(FRAME_FORMATS)}, not {format!r}")
+        if out is not None:
+            if not isinstance(out, torch.Tensor):
+                raise ValueError("out must be a torch tensor")
+            if out.dtype != dtype:
+                raise ValueError(f"out has dtype {out.dtype}, format needs {dtype}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out has shape {tuple(out.shape)}, format needs {shape}")
+            if not out.is_contiguous():
+                raise ValueError("out must be contiguous")
+            if out.device.type != "cuda" or out.device.index != self.device:
+                raise ValueError(f"out is on {out.device}, the scene on cuda:{self.device}")
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        _check_one_hip_runtime()
+        if out is None:
+            with torch.cuda.stream(stream):  # (allocated on the stream the views are exported on)
+                out = torch.empty(shape, dtype=dtype, device=dev)
+        st = self.render_views_device(a, W, H, out.data_ptr(), format=fmt, stream=stream.cuda_stream, **kw)
         return out, st
 
     def _soft_arg(self, spherical, units, samples: int, seed: int):

@@ -129,6 +129,20 @@ bool make_frame(int W, int H, int x0, int y0, int x1, int y1, int rank, int nran
     F.packed = 0;
     F.hint = nullptr;
     F.hint_blocks = F.hint_rgen = F.hint_wgen = 0;
+    F.views = nullptr;
+    F.view_st = 0;
+    return true;
+}
+
+// A multi-view frame (FrameDev::views): nviews whole W x H frames, one rank, their super-tiles one list (the table is set by the caller).
+// False when the list does not fit the launch: more than 2^18 super-tiles (a quad-shape grid of 2^32 workgroups).
+bool make_views_frame(int W, int H, uint32_t nviews, int block, FrameDev& F) {
+    if (nviews == 0 || !make_frame(W, H, 0, 0, W, H, 0, 1, block, F)) return false;
+    const uint64_t view_st = (uint64_t)F.st_x * (uint64_t)F.st_y, nst = view_st * nviews;
+    if (nst > (1ull << 18)) return false;
+    F.view_st = (uint32_t)view_st;
+    F.nst_rank = (uint32_t)nst;
+    F.nblocks = ((F.nst_rank + 7u) / 8u) * 8u * (64u / ((uint32_t)block / 64u));
     return true;
 }
 
@@ -281,7 +295,7 @@ struct CgrtScene {
     struct WorkSlot {
         void* p = nullptr;
         size_t cap = 0;
-    } work[32];  // slots 0..30 are in use (render_impl)
+    } work[32];  // slots 0..31 are in use (render_impl)
     // pinned host staging of cgrt_render*'s frame (grown on demand, guarded by render_mutex): the device frame comes down with ONE
     // asynchronous copy at PCIe speed; cgrt_render_mapped hands this memory to the caller instead of copying it once more
     void* pin_frame = nullptr;
@@ -301,6 +315,18 @@ struct CgrtScene {
     // (and waits for it on the host before it reallocates those buffers); the caller's stream handle itself is never kept.
     hipEvent_t export_done = nullptr;
     bool export_pending = false;  // recorded, and no later frame has waited for it yet
+    // cgrt_trace_primary_views_device: the camera tables of its launches (CameraDev per view), which return before the kernels run.  Four
+    // slots in turn, each a pinned host copy and a device copy; a slot is refilled only once the event recorded behind its last launch
+    // has completed, so the copy never reads memory the caller has since reused (the tables come from the caller's stack or array).
+    struct ViewTable {
+        void* pin = nullptr;
+        void* dev = nullptr;
+        size_t cap = 0;
+        hipEvent_t done = nullptr;
+        bool pending = false;
+    } vtab[4];
+    unsigned vtab_seq = 0;
+    std::mutex vtab_mutex;
     // What the previous cgrt_render* frame of this shape found, per level (entries of the level's compact list): the next frame's
     // launches are sized from it and issued WITHOUT waiting for the device to say how many primary rays hit (render_impl).
     struct RenderPred {
@@ -316,6 +342,12 @@ struct CgrtScene {
         (void)hipSetDevice(device);
         if (export_pending) (void)hipEventSynchronize(export_done);  // (an export may still be reading the workspace)
         if (export_done) (void)hipEventDestroy(export_done);
+        for (ViewTable& v : vtab) {
+            if (v.pending) (void)hipEventSynchronize(v.done);
+            if (v.done) (void)hipEventDestroy(v.done);
+            if (v.dev) (void)hipFree(v.dev);
+            if (v.pin) (void)hipHostFree(v.pin);
+        }
         for (void* p : {d_records, d_leaves, d_tri_normals, d_spheres, d_materials, d_tri_leaf, d_paths, (void*)d_queues, hints.mem})
             if (p) (void)hipFree(p);
         if (hints.mailbox) (void)hipHostFree(hints.mailbox);
@@ -1546,6 +1578,65 @@ int cgrt_trace_primary_device(CgrtScene* s, const CgrtCamera* cam, int W, int H,
     return launch_primary(s, make_camera(*cam), F, reinterpret_cast<CgrtHitDev*>(d_hits), d_normals, nullptr, static_cast<hipStream_t>(stream));
 }
 
+// ---- multi-view frames (include/cgrt.h cgrt_*_views*) ----
+// The batch's own checks, all CGRT_E_ARG: NULL cams, nviews == 0, W or H <= 0, nviews * W * H > 0x7fffffff, more super-tiles than one
+// launch takes (make_views_frame).
+static int views_args(const CgrtCamera* cams, uint32_t nviews, int W, int H) {
+    if (!cams) return fail(CGRT_E_ARG, "cams is NULL");
+    if (nviews == 0) return fail(CGRT_E_ARG, "nviews must be at least 1");
+    if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+    if ((unsigned long long)nviews * (unsigned long long)W * (unsigned long long)H > 0x7fffffffull)
+        return fail(CGRT_E_ARG, "batch too large: nviews*W*H exceeds 0x7fffffff");
+    FrameDev F;
+    if (!make_views_frame(W, H, nviews, 64, F)) return fail(CGRT_E_ARG, "batch too large: more than 2^18 64x64 super-tiles over all views");
+    return CGRT_OK;
+}
+static std::vector<CameraDev> view_cameras(const CgrtCamera* cams, uint32_t nviews) {
+    std::vector<CameraDev> v(nviews);
+    for (uint32_t b = 0; b < nviews; b++) v[b] = make_camera(cams[b]);
+    return v;
+}
+static int check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, const char* name);
+
+int cgrt_trace_primary_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, CgrtHit* d_hits, float* d_normals,
+                                    void* stream) {
+    if (!s || !d_hits) return fail(CGRT_E_ARG, "NULL argument");
+    int rc = views_args(cams, nviews, W, H);
+    if (rc) return rc;
+    if ((uintptr_t)d_hits % 4 || (uintptr_t)d_normals % 4) return fail(CGRT_E_ARG, "d_hits / d_normals not 4-byte aligned");
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    const uint64_t npix = (uint64_t)nviews * (uint64_t)W * (uint64_t)H;
+    if ((rc = check_device_span(s, d_hits, npix * sizeof(CgrtHit), "d_hits"))) return rc;
+    if (d_normals && (rc = check_device_span(s, d_normals, npix * 12, "d_normals"))) return rc;
+    FrameDev F;
+    (void)make_views_frame(W, H, nviews, trace_block(s->dev), F);
+    const std::vector<CameraDev> tab = view_cameras(cams, nviews);
+    const size_t bytes = tab.size() * sizeof(CameraDev);
+    hipStream_t const st = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(s->vtab_mutex);
+    CgrtScene::ViewTable& T = s->vtab[s->vtab_seq++ & 3u];
+    if (T.pending) HIP_TRY(hipEventSynchronize(T.done));  // (the slot's last launch has read its table)
+    T.pending = false;
+    if (!T.done) HIP_TRY(hipEventCreateWithFlags(&T.done, hipEventDisableTiming));
+    if (T.cap < bytes) {
+        if (T.dev) (void)hipFree(T.dev);
+        if (T.pin) (void)hipHostFree(T.pin);
+        T.dev = T.pin = nullptr;
+        T.cap = 0;
+        HIP_TRY(hipMalloc(&T.dev, bytes));
+        HIP_TRY(hipHostMalloc(&T.pin, bytes, hipHostMallocDefault));
+        T.cap = bytes;
+    }
+    std::memcpy(T.pin, tab.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(T.dev, T.pin, bytes, hipMemcpyHostToDevice, st));
+    F.views = static_cast<const CameraDev*>(T.dev);
+    HIP_TRY(launch_trace_primary_views(s->dev, F, reinterpret_cast<CgrtHitDev*>(d_hits), d_normals, st));
+    HIP_TRY(hipEventRecord(T.done, st));
+    T.pending = true;
+    return CGRT_OK;
+}
+
 int cgrt_trace_primary(CgrtScene* s, const CgrtCamera* cam, int W, int H, int x0, int y0, int x1, int y1, int rank, int nranks,
                        CgrtHit* hits, float* normals) {
     if (!s || !cam || !hits) return fail(CGRT_E_ARG, "NULL argument");
@@ -1781,6 +1872,7 @@ struct DeviceOut {
     int format;        // CGRT_FRAME_*
     uint64_t pitch;    // bytes from row to row (never 0 here)
     hipStream_t stream;
+    uint64_t view_bytes;  // (a batch of views) bytes from one view's frame to the next
 };
 // Level 0 from a caller's ray list instead of the camera's frame (cgrt_shade_rays*): n > 0 rays in device memory of the scene's device,
 // colours into rgb (n x 3 floats, device memory), both ordered on `stream`: the frame's work starts behind everything queued there
@@ -1793,10 +1885,19 @@ struct ListSrc {
     float* rgb;
     hipStream_t stream;
 };
+// Level 0 from nviews cameras instead of one (cgrt_render_views*): every view a whole W x H frame, their super-tiles ONE primary launch
+// (the VIEWS kernels) and one set of wavefront lists; pixel = view * W * H + y * W + x, so the frame buffer holds the views back to back
+// and the soft-shadow samples are drawn with pixel % (W * H).  Whole frames, one rank, no aa.  Like a ray list, the batch always takes
+// the exactly sized path and neither reads nor writes the scene's prediction record or its frame hints.
+struct ViewSrc {
+    const CgrtCamera* cams;
+    uint32_t n;
+};
 static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats, CgrtCounters* counted = nullptr,
-                       const float** mapped = nullptr, bool aa = false, const DeviceOut* dout = nullptr, const ListSrc* list = nullptr) {
-    if (!s || (!cam && !list) || (!rgb && !mapped && !dout && !list) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
+                       const float** mapped = nullptr, bool aa = false, const DeviceOut* dout = nullptr, const ListSrc* list = nullptr,
+                       const ViewSrc* views = nullptr) {
+    if (!s || (!cam && !list && !views) || (!rgb && !mapped && !dout && !list) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);
     if (W <= 0 || H <= 0 || max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad frame size or recursion depth");
     const unsigned SL = soft ? soft->nspherical : 0;
@@ -1812,11 +1913,16 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     }
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> one_frame(s->render_mutex);  // the workspace below belongs to one frame at a time
-    const unsigned long long npix = list ? list->n : (unsigned long long)W * H;
+    const uint32_t nviews = views ? views->n : 1u;
+    const unsigned long long npix = list ? list->n : (unsigned long long)W * H * nviews;
     const unsigned L = nlights;
     CgrtRenderStats st{};
     FrameDev F{};
-    if (!list && !make_frame(W, H, 0, 0, W, H, rank, nranks, trace_block(s->dev), F)) return fail(CGRT_E_ARG, "bad frame or rank");
+    if (views) {
+        if (!make_views_frame(W, H, nviews, trace_block(s->dev), F)) return fail(CGRT_E_ARG, "bad batch");
+    } else if (!list && !make_frame(W, H, 0, 0, W, H, rank, nranks, trace_block(s->dev), F)) {
+        return fail(CGRT_E_ARG, "bad frame or rank");
+    }
     // items: this rank's part of the frame in the primary kernel's order, or the caller's rays
     const unsigned long long n = list ? list->n : (unsigned long long)F.nblocks * (unsigned long long)F.block;
     // Every level is a compact list: level 0 = the primary rays that hit, level l + 1 = the mirror rays of level l (at most
@@ -1829,7 +1935,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     WsBuf rays[3] = {{s, 0}, {s, 1}, {s, 21}}, hits[3] = {{s, 2}, {s, 3}, {s, 22}}, normals[3] = {{s, 4}, {s, 5}, {s, 23}},
           pix[3] = {{s, 6}, {s, 7}, {s, 24}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
           sslot[2] = {{s, 12}, {s, 28}}, dlights{s, 13}, levels{s, 14}, drgb{s, 15}, dctr{s, 16}, dslights{s, 17}, dunits{s, 18}, dlit{s, 19},
-          dwork{s, 20}, dspawn{s, 29}, dres{s, 30};
+          dwork{s, 20}, dspawn{s, 29}, dres{s, 30}, dviews{s, 31};
     unsigned long long *cw_primary = nullptr, *cw_shadow = nullptr, *cw_mirror = nullptr;
     if (counted) {
         HIP_TRY(dwork.alloc(3 * 8 * sizeof(unsigned long long)));
@@ -1883,7 +1989,14 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         Q.nunits = soft->nunits;
         Q.seed = soft->seed;
     }
-    const CameraDev C = list ? CameraDev{} : make_camera(*cam);
+    const CameraDev C = (list || views) ? CameraDev{} : make_camera(*cam);
+    if (views) {  // (the table of the VIEWS kernels; this call waits for its frame, so the slot is free again when it returns)
+        const std::vector<CameraDev> tab = view_cameras(views->cams, nviews);
+        HIP_TRY(dviews.alloc(tab.size() * sizeof(CameraDev)));
+        HIP_TRY(hipMemcpy(dviews.p, tab.data(), tab.size() * sizeof(CameraDev), hipMemcpyHostToDevice));
+        F.views = dviews.as<CameraDev>();
+        Q.view_pixels = (uint32_t)W * (uint32_t)H;
+    }
     CgrtScene::RenderAux& aux = s->raux;  // second stream + the events that order it against the default stream
     if (!aux.pin_counts) {
         // The second stream carries the frame's critical path (level 0's mirror list, then all of level 1), the default stream the
@@ -1927,7 +2040,8 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     bool frame_done = false;
     CgrtScene::RenderPred& P = s->rpred;
     const bool predictable = g_render_predict.load() && P.valid && P.W == W && P.H == H && P.rank == rank && P.nranks == nranks &&
-                             P.max_level == max_level && P.L == L && !P.counts.empty() && SL == 0 && !counted && max_level >= 1 && !list;
+                             P.max_level == max_level && P.L == L && !P.counts.empty() && SL == 0 && !counted && max_level >= 1 && !list &&
+                             !views;
     auto predicted = [&]() -> int {
         const int np = (int)P.counts.size();  // levels the previous frame evaluated (P.counts[l] > 0 entries each)
         // {level 0's entries, level 1's entries}: one 64-bit word, filled by the primary kernel's fused spawn with one atomic
@@ -2085,6 +2199,10 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                 HIP_TRY(launch_trace_list_compact(s->dev, list->rays, n, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
                                                   ipix.as<int>(), primary_hits, frame_rgb, nullptr, cw_primary));
                 st.primary_rays = n;
+            } else if (views) {  // (also clears every view's pixels)
+                HIP_TRY(launch_trace_primary_views_compact(s->dev, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(),
+                                                           primary_hits, frame_rgb, nullptr));
+                st.primary_rays = npix;
             } else {
                 HIP_TRY(launch_trace_primary_compact(s->dev, C, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
                                                      ipix.as<int>(), primary_hits, nullptr, cw_primary, frame_rgb));  // (also clears this rank's pixels)
@@ -2210,8 +2328,8 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         }
         if (finished) {
         } else if (max_level < 1) {  // trace() returns black without tracing (main.cpp:267): no primary kernel ran, clear here
-            if (list)
-                HIP_TRY(hipMemsetAsync(frame_rgb, 0, n * 12, nullptr));
+            if (list || views)
+                HIP_TRY(hipMemsetAsync(frame_rgb, 0, npix * 12, nullptr));
             else
                 HIP_TRY(launch_clear_owned(F, frame_rgb, nullptr));
         } else if (nlev == 0) {  // nothing was hit: the primary kernel has left this rank's pixels black
@@ -2233,7 +2351,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipEventElapsedTime(&ms, aux.e0, aux.e1));
         st.device_ms = ms;
         st.levels = nlev;
-        if (list) return CGRT_OK;  // (a ray list sizes no frame)
+        if (list || views) return CGRT_OK;  // (a ray list or a batch of views sizes no frame)
         // what this frame found sizes the next one
         P.valid = g_render_predict.load() && SL == 0 && !counted && max_level >= 1 && !level_count.empty();
         P.W = W, P.H = H, P.rank = rank, P.nranks = nranks, P.max_level = max_level, P.L = L;
@@ -2242,7 +2360,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         return CGRT_OK;
     };
     if (!frame_done) {
-        if (!list) P.last_path = predictable ? 2 : 0;
+        if (!list && !views) P.last_path = predictable ? 2 : 0;
         st = CgrtRenderStats{};
         const int erc = exact();
         if (erc != CGRT_OK) return erc;
@@ -2261,6 +2379,10 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         E.W = PW;
         E.H = PH;
         E.format = dout->format;
+        if (views) {
+            E.views = (int)nviews;
+            E.view_bytes = dout->view_bytes;
+        }
         if (nranks > 1) {  // super-tiles of the frame, or (aa) 32x32 blocks = super-tiles of the sub-sample frame; F.st_x counts either
             E.tile = aa ? 32 : 64;
             E.tiles_x = F.st_x;
@@ -2440,6 +2562,43 @@ int cgrt_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     const int sc = check_device_span(s, d_out, extent, "d_out");
     if (sc) return sc;
     return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, nullptr, stats, nullptr, nullptr, aa != 0, &D);
+}
+
+// ---- renderRayTracing's per-pixel loop for a batch of cameras (render_impl, ViewSrc; include/cgrt.h cgrt_render_views*) ----
+// cgrt_render_device's checks without aa / rank / row_bytes, with the batch's own (views_args) in place of the frame size check.
+static int render_views_args(const CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                             const CgrtSoftShadows* soft, int max_level, const void* out) {
+    if (!s || !out) return fail(CGRT_E_ARG, "NULL argument");
+    if (nlights && !lights) return fail(CGRT_E_ARG, "nlights > 0 but lights is NULL");
+    const int rc = views_args(cams, nviews, W, H);
+    if (rc) return rc;
+    if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
+    if (soft && soft->nspherical &&
+        (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
+        return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
+    return CGRT_OK;
+}
+int cgrt_render_views(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                      const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats) {
+    const int rc = render_views_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, rgb);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    const ViewSrc V{cams, nviews};
+    return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, rgb, stats, nullptr, nullptr, false, nullptr, nullptr, &V);
+}
+int cgrt_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                             const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats) {
+    int rc = render_views_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out);
+    if (rc) return rc;
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    uint64_t extent = 0;
+    if ((rc = export_args(d_out, W, H, format, 0, &D.pitch, &extent))) return rc;
+    D.view_bytes = extent;  // (packed rows: one view's frame is exactly its extent)
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_out, extent * nviews, "d_out"))) return rc;
+    const ViewSrc V{cams, nviews};
+    return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, &D, nullptr, &V);
 }
 
 // ---- getFinalColor of the caller's rays (main.cpp:298-310): level 0 of the wavefront from a ray list (render_impl, ListSrc) ----

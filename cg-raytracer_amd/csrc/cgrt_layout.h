@@ -206,6 +206,11 @@ struct FrameDev {
                            // launch can take (<= cap; entries beyond are traced by their regular workgroups)
     uint32_t hint_rgen;    // generation of the set to read (0: nothing to read -- a first frame still writes)
     uint32_t hint_wgen;    // generation this frame stamps on what it writes
+    // Multi-view frames (cgrt_*_views*; read only by the VIEWS instantiations): nst_rank super-tiles = nviews x view_st,
+    // super-tile s of that one list is super-tile s % view_st of view s / view_st, traced with camera views[s / view_st] (device
+    // memory) and written at pixel view * W * H + y * W + x.  Whole frames, one rank.
+    const CameraDev* views;
+    uint32_t view_st;      // super-tiles per view (st_x * st_y)
 };
 static const int ST_TILES = 8;  // tiles per super-tile side
 // Workgroups of the traversal kernels hold 64, 128 or 256 threads (chosen per launch: FrameDev::block, blockDim.x): one wave

@@ -253,9 +253,18 @@ __device__ __forceinline__ unsigned rgba8(float r, float g, float b) { return to
 // cgrt_render_device's export: one thread per 4 consecutive pixels of a row -- three float4 loads, then one 16-B store (RGBA8), one
 // float4 store per plane (CHW) or three float4 stores (RGB_F32).  Row ends and bases that are not 16-B aligned (W % 4 != 0, pitches
 // that are not multiples of 16) take the scalar path.  Tiles are multiples of 4 pixels wide, so the 4 pixels share an owner.
-__global__ __launch_bounds__(256) void k_export_frame(ExportDev E) {
-    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+// VIEWS (ExportDev::views > 1, k_export_views): the threads of all views in one grid, view v's after view v - 1's.
+template <bool VIEWS>
+__device__ __forceinline__ void export_frame(ExportDev E) {
+    unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long G = (unsigned long long)((E.W + 3) >> 2);  // 4-pixel groups per row
+    if (VIEWS) {
+        const unsigned long long per_view = G * (unsigned long long)E.H, v = t / per_view;
+        if (v >= (unsigned long long)E.views) return;
+        t -= v * per_view;
+        E.src += 3ull * (unsigned long long)E.W * (unsigned long long)E.H * v;
+        E.dst += E.view_bytes * v;
+    }
     const unsigned long long yl = t / G;
     if (yl >= (unsigned long long)E.H) return;
     const int y = (int)yl, x0 = (int)(t - yl * G) * 4;
@@ -303,14 +312,20 @@ __global__ __launch_bounds__(256) void k_export_frame(ExportDev E) {
         }
     }
 }
+__global__ __launch_bounds__(256) void k_export_frame(ExportDev E) { export_frame<false>(E); }
+__global__ __launch_bounds__(256) void k_export_views(ExportDev E) { export_frame<true>(E); }
 
 static inline unsigned grid_for(unsigned long long n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 hipError_t launch_export_frame(const ExportDev& E, hipStream_t s) {
-    const unsigned long long n = (unsigned long long)((E.W + 3) / 4) * (unsigned long long)E.H;
+    const unsigned long long views = E.views > 1 ? (unsigned long long)E.views : 1ull;
+    const unsigned long long n = (unsigned long long)((E.W + 3) / 4) * (unsigned long long)E.H * views;
     if (n == 0) return hipSuccess;
     if ((n + 255) / 256 > 0xffffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_export_frame, dim3(grid_for(n, 256)), dim3(256), 0, s, E);
+    if (views > 1)
+        hipLaunchKernelGGL(k_export_views, dim3(grid_for(n, 256)), dim3(256), 0, s, E);
+    else
+        hipLaunchKernelGGL(k_export_frame, dim3(grid_for(n, 256)), dim3(256), 0, s, E);
     return hipGetLastError();
 }
 

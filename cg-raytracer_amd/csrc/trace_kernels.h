@@ -23,6 +23,7 @@ struct SoftDev {
     const float* lights;  // nlights x 7 {position, radius, color} (SphericalLight, scene.h:47-51)
     const float* units;   // nunits x 3 unit vectors: the randomUnitVector() draws (main.cpp:46-59)
     uint32_t nlights, samples, nunits, seed, level;
+    uint32_t view_pixels;  // 0, or W * H of a multi-view frame: samples are drawn with item_pixels[item] % view_pixels (k_soft_shadow)
 };
 
 // threads per workgroup the ray-list kernels (batch, soft shadow) are launched with for this scene; frames carry theirs in FrameDev::block
@@ -76,6 +77,11 @@ hipError_t launch_in_shadow(const SceneDev& S, const float* points, unsigned lon
 hipError_t launch_trace_primary_compact(const SceneDev& S, const CameraDev& C, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals,
                                         int* pixels, uint32_t* count, hipStream_t stream, unsigned long long* counters = nullptr,
                                         float* rgb = nullptr, const SpawnDev* spawn = nullptr);  // spawn (device memory): level 0's k_spawn fused in (spawn_rays.h)  // rgb (optional): the rank's pixels are cleared by the same kernel
+// multi-view frames (F.views set, F.nst_rank = nviews x F.view_st: capi.cpp make_views_frame): the VIEWS instantiations of the two
+// primary kernels, pixel = view * W * H + y * W + x.  No counters, no hints, no fused spawn; the kernel shape as for a frame.
+hipError_t launch_trace_primary_views(const SceneDev& S, const FrameDev& F, CgrtHitDev* hits, float* normals, hipStream_t stream);
+hipError_t launch_trace_primary_views_compact(const SceneDev& S, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals, int* pixels,
+                                              uint32_t* count, float* rgb, hipStream_t stream);
 // level 0 of the shading wavefront from a caller's list of n rays (cgrt_shade_rays, k_trace_list_compact): rgb[3i..3i+2] := 0 for every
 // i, the rays that hit appended to the compact list {rays, hits, normals, pixels = i}; count = one zeroed device word.  Laid out by the
 // list's shape (list_shape), as launch_trace_batch.
@@ -106,12 +112,16 @@ hipError_t launch_resolve_aa(const FrameDev& F, const float* sub, float* out, in
 // CGRT_FRAME_* formats of include/cgrt.h.  tile = 0: every pixel is written; otherwise only pixels whose tile x tile block index
 // (row-major, tiles_x per row) % nranks == rank.  packed (tile 32 only): src holds this rank's blocks back to back, as k_resolve_aa
 // writes them with packed = 1 (block slot k / nranks, 1024 pixels each).  dst is 4-byte aligned, pitch a multiple of 4.
+// views > 1 (multi-view frames, tile = 0): src holds `views` W x H frames back to back, view v goes to dst + v * view_bytes -- one launch
+// (an instantiation of its own; the single frame's kernel is the one it was).
 struct ExportDev {
     const float* src;
     unsigned char* dst;
     unsigned long long pitch;  // bytes from one row of dst to the next (CHW: plane stride pitch * H)
     int W, H, format;
     int tile, tiles_x, rank, nranks, packed;
+    int views;                      // 0 or 1: one frame
+    unsigned long long view_bytes;  // dst bytes from one view to the next
 };
 hipError_t launch_export_frame(const ExportDev& E, hipStream_t s);
 hipError_t launch_gather_calib(const void* table, unsigned long long nrecords, unsigned long long mult, unsigned long long add, float* sink,

@@ -26,49 +26,59 @@ namespace cgrt {
 // tb = (b / 32) * 8 + b % 8 -- the workgroup index the lane-per-ray launch with 64 threads gives that tile, same blockIdx % 8
 // residue, i.e. same XCD -- and of its 64 pixels the 16 with index (b / 8 % 4) * 16 + threadIdx / 4; the four lanes of a quad
 // carry the same pixel.  Results land where the lane-per-ray launch puts them (packed or not).
-template <bool QUAD>
-__device__ __forceinline__ bool frame_pixel(const FrameDev& F, int& x, int& y, size_t& packed_index, bool& writer) {
+// VIEWS: a multi-view frame (FrameDev::views); *view = the lane's view (wave-uniform).
+template <bool QUAD, bool VIEWS = false>
+__device__ __forceinline__ bool frame_pixel(const FrameDev& F, int& x, int& y, size_t& packed_index, bool& writer, uint32_t* view = nullptr) {
     if (QUAD) {
         const uint32_t b = blockIdx.x, tb = ((b >> 5) << 3) | (b & 7u);
         const uint32_t p = ((b >> 3) & 3u) * 16u + (threadIdx.x >> 2);
         packed_index = (size_t)tb * 64u + p;
         writer = (threadIdx.x & 3u) == 0u;
-        return tile_pixel_of(F, tb, p, x, y);
+        return tile_pixel_of<VIEWS>(F, tb, p, x, y, view);
     }
     packed_index = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     writer = true;
-    return tile_pixel_of(F, blockIdx.x, threadIdx.x, x, y);
+    return tile_pixel_of<VIEWS>(F, blockIdx.x, threadIdx.x, x, y, view);
+}
+// A multi-view frame's pixel index: view * W * H + y * W + x (< 2^31: the entries check nviews * W * H).
+__device__ __forceinline__ size_t view_pixel(const FrameDev& F, uint32_t view, int x, int y) {
+    return (size_t)view * (size_t)F.W * (size_t)F.H + (size_t)y * F.W + x;
 }
 
 // HINT: the launch carries frame hints (cgrt_layout.h HintDev) -- an instantiation of its own, so that the plain frame kernel is the
 // kernel it was (the hint code costs every launch a few percent when it is merely compiled in: measured).
-template <bool COUNT, bool FAST, bool QUAD = false, bool HINT = false>
+// VIEWS: a multi-view frame (FrameDev::views, cgrt_trace_primary_views_device) -- also an instantiation of its own, for the same
+// reason; each wave reads its view's camera from the device table (C is not used) and writes at view_pixel.  Never with HINT.
+template <bool COUNT, bool FAST, bool QUAD = false, bool HINT = false, bool VIEWS = false>
 __global__ CGRT_LB void k_trace_primary(SceneDev S, CameraDev C, FrameDev F, CgrtHitDev* __restrict__ hits, float* __restrict__ normals,
                                         unsigned long long* counters) {
+    static_assert(!(HINT && VIEWS), "multi-view frames take no hints");
     extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
     int x = 0, y = 0;
     size_t pidx;
     bool writer;
     bool active;
+    uint32_t view = 0;
     if (HINT && F.hint) {  // (the run-time test is redundant; with it the compiler keeps the walk out of scratch)
         pidx = 0;          // (hinted frames are never packed)
         writer = true;
         active = hinted_tile_pixel(F, x, y, CGRT_HINT_SCRATCH(s_lds));
     } else {
         if (HINT && (threadIdx.x & 63u) == 0u) CGRT_HINT_SCRATCH(s_lds)[1] = 0xffffffffu;  // nothing for hint_finish
-        active = frame_pixel<QUAD>(F, x, y, pidx, writer);
+        active = frame_pixel<QUAD, VIEWS>(F, x, y, pidx, writer, &view);
     }
     LaneCounters cnt;
     F3 o = f3(0, 0, 0), d = f3(0, 0, 0);
-    if (active) primary_ray(C, F.W, F.H, x, y, o, d);
+    if (active) primary_ray(VIEWS ? F.views[view] : C, F.W, F.H, x, y, o, d);
     float t = 3.402823466e+38f;  // std::numeric_limits<float>::max(), trackball.cpp:101
     uint32_t hit_rec = REF_NONE;
     if (QUAD)
         walk_tree_quad<COUNT>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), cnt);
     else
         walk_tree<COUNT, FAST>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), CGRT_WAVE_MAP(s_lds), cnt);
+    if (VIEWS) (void)frame_pixel<QUAD, VIEWS>(F, x, y, pidx, writer, &view);  // (rebuilt, not kept through the walk: that cost 12 B of scratch)
     if (active && writer) {
-        const size_t pix = F.packed ? pidx : (size_t)y * F.W + x;
+        const size_t pix = VIEWS ? view_pixel(F, view, x, y) : (F.packed ? pidx : (size_t)y * F.W + x);
         finish_ray(S, o, d, t, hit_rec, hits + pix, normals ? normals + 3 * pix : nullptr);
     }
     if (COUNT) flush_counters(cnt, active && writer, counters);
@@ -79,7 +89,8 @@ __global__ CGRT_LB void k_trace_primary(SceneDev S, CameraDev C, FrameDev F, Cgr
 // appended to a compact list {ray, hit, normal, pixel} (one atomic per workgroup, lanes ranked by ballot; workgroups
 // finish roughly in launch order, so the list keeps the frame's tile order).  Pixels that miss need no further work upstream
 // either (main.cpp:293: black).  count = one zeroed device word.
-template <bool COUNT, bool FAST, bool QUAD = false>
+// VIEWS: a multi-view frame (k_trace_primary's VIEWS): camera per view from F.views, pixels (and rgb) at view_pixel.
+template <bool COUNT, bool FAST, bool QUAD = false, bool VIEWS = false>
 __global__ CGRT_LB void k_trace_primary_compact(SceneDev S, CameraDev C, FrameDev F, float* __restrict__ rays, CgrtHitDev* __restrict__ hits,
                                                 float* __restrict__ normals, int* __restrict__ pixels, uint32_t* __restrict__ count,
                                                 unsigned long long* counters, float* __restrict__ rgb, const SpawnDev* __restrict__ spawn_dev) {
@@ -88,16 +99,17 @@ __global__ CGRT_LB void k_trace_primary_compact(SceneDev S, CameraDev C, FrameDe
     int x = 0, y = 0;
     size_t pidx;
     bool writer;
-    const bool active = frame_pixel<QUAD>(F, x, y, pidx, writer);
+    uint32_t view = 0;
+    const bool active = frame_pixel<QUAD, VIEWS>(F, x, y, pidx, writer, &view);
     if (active && writer && rgb) {  // every pixel this rank owns starts black (main.cpp:293); the hits are written over it at the end of the frame
-        float* p = rgb + 3ull * ((unsigned long long)y * F.W + x);
+        float* p = rgb + 3ull * (VIEWS ? view_pixel(F, view, x, y) : (unsigned long long)y * F.W + x);
         p[0] = p[1] = p[2] = 0.0f;
     }
     LaneCounters cnt;
     CgrtHitDev h;
     h.hit = 0;
     F3 o = f3(0, 0, 0), d = f3(0, 0, 0), nn = f3(0, 0, 0);
-    if (active) primary_ray(C, F.W, F.H, x, y, o, d);
+    if (active) primary_ray(VIEWS ? F.views[view] : C, F.W, F.H, x, y, o, d);
     float t = 3.402823466e+38f;  // std::numeric_limits<float>::max(), trackball.cpp:101
     uint32_t hit_rec = REF_NONE;
     if (QUAD)
@@ -165,8 +177,9 @@ __global__ CGRT_LB void k_trace_primary_compact(SceneDev S, CameraDev C, FrameDe
         int px = 0, py = 0;  // (the pixel is rebuilt rather than kept in registers through the walk)
         size_t pi;
         bool wr;
-        (void)frame_pixel<QUAD>(F, px, py, pi, wr);
-        pixels[idx] = py * F.W + px;
+        uint32_t pv = 0;
+        (void)frame_pixel<QUAD, VIEWS>(F, px, py, pi, wr, &pv);
+        pixels[idx] = VIEWS ? (int)view_pixel(F, pv, px, py) : py * F.W + px;
         if (spawn_dev) {
             // Entry idx's shadow ray towards light l is shadow ray idx * nlights + l (every entry of level 0 is a hit: no append).
             const SpawnDev SP = *spawn_dev;
@@ -179,7 +192,7 @@ __global__ CGRT_LB void k_trace_primary_compact(SceneDev S, CameraDev C, FrameDe
             const uint32_t child = s_lds[0] + (s_cnt[w] >> 16) + (uint32_t)__popcll(mm & below);
             if (wants_mirror) {
                 spawn_mirror_ray(pointOn, d, nn, child, SP.next_rays);
-                SP.next_pixels[child] = py * F.W + px;
+                SP.next_pixels[child] = VIEWS ? (int)view_pixel(F, pv, px, py) : py * F.W + px;
             }
             SP.lvl[2 * idx + 1] = make_float4(ks.x, ks.y, ks.z, __int_as_float(wants_mirror ? (int)child : -1));
         }
@@ -495,7 +508,9 @@ __global__ CGRT_LB void k_visibility(SceneDev S, const float* __restrict__ src, 
 // the hit flag only (an accepted t is below lightT by construction, or 0 from the on-plane rule, never above).
 // POINTS: the items are the caller's points (cgrt_soft_lit*): `rays` holds 3 floats per item, pointOn = that point, every item is live and
 // samples as pixel = item (hits and item_pixels are not read).
-template <bool ANYHIT, bool FAST, bool POINTS = false>
+// VIEWS: the items belong to a multi-view frame, whose pixels are view * W * H + (in-view pixel): samples are drawn with the in-view
+// pixel item_pixels[item] % Q.view_pixels, so that every view draws what its single-camera frame draws.
+template <bool ANYHIT, bool FAST, bool POINTS = false, bool VIEWS = false>
 __global__ CGRT_LB void k_soft_shadow(SceneDev S, SoftDev Q, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
                                       const int* __restrict__ item_pixels, unsigned long long nthreads, uint32_t* __restrict__ lit) {
     extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
@@ -520,6 +535,7 @@ __global__ CGRT_LB void k_soft_shadow(SceneDev S, SoftDev Q, const float* __rest
             const float* r = rays + 7 * item;
             pointOn = add(f3(r[0], r[1], r[2]), scale(f3(r[3], r[4], r[5]), hits[item].t));
             pixel = (uint32_t)item_pixels[item];
+            if (VIEWS) pixel %= Q.view_pixels;
         }
         const float* L = Q.lights + 7 * l;
         const float* u = Q.units + 3ull * soft_sample_index(Q.seed, pixel, Q.level, l, smp, Q.nunits);
@@ -774,6 +790,39 @@ hipError_t launch_trace_primary_compact(const SceneDev& S, const CameraDev& C, c
         CGRT_LAUNCH2(k_trace_primary_compact, false, fast, F.nblocks, block, stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
     return hipGetLastError();
 }
+// Multi-view frames: the VIEWS instantiations (no counters, no hints), in the shape a single frame of the same workgroup size takes.
+hipError_t launch_trace_primary_views(const SceneDev& S, const FrameDev& F, CgrtHitDev* hits, float* normals, hipStream_t stream) {
+    if (F.nblocks == 0) return hipSuccess;
+    const CameraDev C{};  // (unused: the cameras are in F.views)
+    unsigned long long* const counters = nullptr;
+    if (F.block == 64 && quad_shape_for(S, (unsigned long long)F.nblocks * 64ull))
+        hipLaunchKernelGGL((k_trace_primary<false, true, true, false, true>), dim3(4u * F.nblocks), dim3(64), lds_bytes(64), stream, S, C, F, hits, normals,
+                           counters);
+    else if (S.fast_root != REF_NONE)
+        hipLaunchKernelGGL((k_trace_primary<false, true, false, false, true>), dim3(F.nblocks), dim3((unsigned)F.block), lds_bytes((unsigned)F.block), stream,
+                           S, C, F, hits, normals, counters);
+    else
+        hipLaunchKernelGGL((k_trace_primary<false, false, false, false, true>), dim3(F.nblocks), dim3((unsigned)F.block), lds_bytes((unsigned)F.block), stream,
+                           S, C, F, hits, normals, counters);
+    return hipGetLastError();
+}
+hipError_t launch_trace_primary_views_compact(const SceneDev& S, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals, int* pixels,
+                                              uint32_t* count, float* rgb, hipStream_t stream) {
+    if (F.nblocks == 0) return hipSuccess;
+    const CameraDev C{};
+    unsigned long long* const counters = nullptr;
+    const SpawnDev* const SP = nullptr;
+    if (F.block == 64 && quad_shape_for(S, (unsigned long long)F.nblocks * 64ull))
+        hipLaunchKernelGGL((k_trace_primary_compact<false, true, true, true>), dim3(4u * F.nblocks), dim3(64), lds_bytes(64), stream, S, C, F, rays, hits,
+                           normals, pixels, count, counters, rgb, SP);
+    else if (S.fast_root != REF_NONE)
+        hipLaunchKernelGGL((k_trace_primary_compact<false, true, false, true>), dim3(F.nblocks), dim3((unsigned)F.block), lds_bytes((unsigned)F.block), stream,
+                           S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
+    else
+        hipLaunchKernelGGL((k_trace_primary_compact<false, false, false, true>), dim3(F.nblocks), dim3((unsigned)F.block), lds_bytes((unsigned)F.block),
+                           stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
+    return hipGetLastError();
+}
 hipError_t launch_trace_list_compact(const SceneDev& S, const float* in_rays, unsigned long long n, float* rays, CgrtHitDev* hits, float* normals,
                                      int* pixels, uint32_t* count, float* rgb, hipStream_t stream, unsigned long long* counters) {
     if (n == 0) return hipSuccess;
@@ -809,6 +858,18 @@ hipError_t launch_soft_shadow(const SceneDev& S, const SoftDev& Q, const float* 
     const unsigned long long blocks = (nthreads + block - 1) / block;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     const bool fast = S.fast_root != REF_NONE;
+    if (Q.view_pixels) {  // a multi-view frame's items (k_soft_shadow VIEWS)
+        const dim3 grid((unsigned)blocks), threads(block);
+        if (anyhit && fast)
+            hipLaunchKernelGGL((k_soft_shadow<true, true, false, true>), grid, threads, lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nthreads, lit);
+        else if (anyhit)
+            hipLaunchKernelGGL((k_soft_shadow<true, false, false, true>), grid, threads, lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nthreads, lit);
+        else if (fast)
+            hipLaunchKernelGGL((k_soft_shadow<false, true, false, true>), grid, threads, lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nthreads, lit);
+        else
+            hipLaunchKernelGGL((k_soft_shadow<false, false, false, true>), grid, threads, lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nthreads, lit);
+        return hipGetLastError();
+    }
     if (anyhit)
         CGRT_LAUNCH2(k_soft_shadow, true, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
     else

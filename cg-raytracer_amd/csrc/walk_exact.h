@@ -756,13 +756,23 @@ __device__ __forceinline__ void primary_ray(const CameraDev& C, int W, int H, in
 // Workgroup -> super-tile -> tile -> pixel (FrameDev in cgrt_layout.h): blockIdx % 8 selects the XCD lane of
 // the rank's super-tile list, 16 consecutive workgroups of that lane cover one 64x64 super-tile, the 4 waves
 // of a workgroup take 4 horizontally adjacent 8x8 tiles.
-__device__ __forceinline__ bool tile_pixel_of(const FrameDev& F, const uint32_t b, const uint32_t tid, int& x, int& y) {
+// VIEWS (multi-view frames, FrameDev::views): the same rule over the super-tiles of all views as one list; *view = the view of
+// super-tile s, which the workgroup's waves share (wave-uniform).
+template <bool VIEWS = false>
+__device__ __forceinline__ bool tile_pixel_of(const FrameDev& F, const uint32_t b, const uint32_t tid, int& x, int& y, uint32_t* view = nullptr) {
     const uint32_t lane8 = b & 7u, j = b >> 3;
     const int lane = (int)(tid & 63u);
     const uint32_t wpb = blockDim.x >> 6, bps = 64u / wpb;  // waves per workgroup, workgroups per super-tile
     const uint32_t s = (j / bps) * 8u + lane8;  // rank-local super-tile
     if (s >= F.nst_rank) return false;
-    const uint32_t st = (uint32_t)F.rank + (uint32_t)F.nranks * s;
+    uint32_t st;
+    if (VIEWS) {  // (one rank)
+        const uint32_t v = s / F.view_st;
+        *view = v;
+        st = s - v * F.view_st;
+    } else {
+        st = (uint32_t)F.rank + (uint32_t)F.nranks * s;
+    }
     const int stx = (int)(st % (uint32_t)F.st_x), sty = (int)(st / (uint32_t)F.st_x);
     const int idx = (int)((j % bps) * wpb + (tid >> 6));
     const int tx = stx * ST_TILES + (idx & 7), ty = sty * ST_TILES + (idx >> 3);

@@ -382,6 +382,39 @@ int cgrt_shade_rays(CgrtScene* scene, const CgrtRay* rays, uint64_t n, const flo
 int cgrt_shade_rays_device(CgrtScene* scene, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights,
                            const CgrtSoftShadows* soft, int max_level, float* d_rgb, void* stream, CgrtRenderStats* stats);
 
+/* Multi-view frames: a batch of nviews >= 1 cameras that share one frame shape W x H, the lights, the soft-shadow settings and max_level,
+ * in ONE primary launch and one set of wavefront lists.  View b is bit for bit the single-camera frame of
+ * cams[b]; the views may differ in every camera field.  Pixel (x, y) of view b has index b*W*H + y*W + x.
+ * Limits: nviews * W * H <= 0x7fffffff, and at most 2^18 64x64 super-tiles over all views.  Not batched (use the single-camera
+ * entries): anti-aliasing, rank / nranks ownership, replicas on several devices, per-view frame sizes, per-view lights.
+ * Checks, all CGRT_E_ARG and before any device work: NULL scene / cams / output, nlights > 0 with NULL lights, nviews == 0, W or H <= 0,
+ * the limits above, max_level outside 0..16, bad `soft` (cgrt_render_soft's rules), unknown format, output not 4-byte aligned; then a
+ * host-only scene -> CGRT_E_NO_DEVICE; then (device outputs) the bytes the batch spans not all device memory of the scene's device
+ * (checked as cgrt_render_device checks d_out) -> CGRT_E_ARG.  No entry reads or writes the scene's frame prediction or frame hints:
+ * a single-camera frame after a batch takes the path and gives the bytes it would have without the batch.
+ *
+ * cgrt_trace_primary_views_device: Trackball::generateRay (trackball.cpp:92-103) + intersect for every pixel of every view:
+ * d_hits[b*W*H + y*W + x] (and d_normals, 3 floats each, may be NULL) = what cgrt_trace_primary_device(cams[b], W, H, whole frame,
+ * rank 0 of 1) writes at y*W + x.  Nothing else is written.  Asynchronous on `stream` like cgrt_trace_primary_device: the camera table
+ * is copied into the scene's own pinned memory before the call returns (the caller may reuse cams at once); the scene keeps four
+ * such tables, and a call whose table slot is still in use by a launch four calls back waits for that launch. */
+int cgrt_trace_primary_views_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, CgrtHit* d_hits,
+                                    float* d_normals, void* stream);
+/* cgrt_render_views: renderRayTracing's per-pixel loop (main.cpp:648-720) around getFinalColor (:298-310) for every view: rgb (host,
+ * nviews*W*H*3 f32) holds the views back to back, view b's bytes those of cgrt_render_soft(cams[b], ...) (cgrt_render with soft NULL).
+ * Spherical-light sample smp of pixel (x, y) of view b is drawn with p = y*W + x, as in the single frame.  stats: ray counts summed
+ * over the views, device_ms for the whole batch; the call always takes the exactly sized path.  Synchronous. */
+int cgrt_render_views(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                      const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats);
+/* cgrt_render_views_device: the same views exported into device memory in one launch: view b starts at d_out + b * (the packed frame
+ * bytes of `format`) and holds cgrt_render_device's packed bytes for cams[b] (aa = 0, rank 0 of 1) -- a contiguous (B, H, W, 3) f32,
+ * (B, 3, H, W) f32 or (B, H, W, 4) u8 array.  Stream rules of cgrt_render_device: the call blocks until the batch's kernels are done
+ * and returns with the export enqueued on `stream`, behind everything the caller enqueued there before; the scene's export event is
+ * recorded behind it. */
+int cgrt_render_views_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights,
+                             uint32_t nlights, const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream,
+                             CgrtRenderStats* stats);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
