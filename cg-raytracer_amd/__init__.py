@@ -108,7 +108,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -183,6 +183,12 @@ def lib() -> C.CDLL:
     L.cgrt_trace_primary_views_device.argtypes = [vp, vp, u32, i32, i32, vp, vp, vp]
     L.cgrt_render_views.argtypes = [vp, vp, u32, i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
     L.cgrt_render_views_device.argtypes = [vp, vp, u32, i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, i32, vp, C.POINTER(RenderStats)]
+    L.cgrt_enqueue_render_device.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, i32, i32, i32, vp, i32, u64,
+                                             vp, C.POINTER(u64)]
+    L.cgrt_enqueue_render_views_device.argtypes = [vp, vp, u32, i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, i32, vp, C.POINTER(u64)]
+    L.cgrt_enqueue_shade_rays_device.argtypes = [vp, vp, u64, vp, u32, C.POINTER(SoftShadows), i32, vp, vp, C.POINTER(u64)]
+    L.cgrt_enqueue_stats.argtypes = [vp, u64, C.POINTER(RenderStats)]
+    L.cgrt_debug_strided_waves.argtypes = []
     L.cgrt_occluded.argtypes = [vp, vp, u64, vp]
     L.cgrt_occluded_device.argtypes = [vp, vp, u64, vp, vp]
     L.cgrt_in_shadow.argtypes = [vp, vp, u64, vp, u32, vp]
@@ -661,6 +667,12 @@ class Scene:
         (default: torch.cuda.current_stream()).  Other keywords as render_device.  Returns (tensor, stats dict).
         Import torch before the library is first used (lib()): torch then brings the one HIP runtime both use; the other way round
         torch finds no device."""
+        out, fmt, row_bytes, stream = self._frame_tensor(W, H, format, out, stream, kw.get("nranks", 1))
+        st = self.render_device(cam, W, H, out.data_ptr(), format=fmt, row_bytes=row_bytes, stream=stream.cuda_stream, **kw)
+        return out, st
+
+    def _frame_tensor(self, W, H, format, out, stream, nranks):
+        """render_tensor's checks of `out` (ValueError) and its new tensor: (out, format code, row pitch, stream)."""
         import torch
 
         fmt = _frame_format(format)
@@ -675,9 +687,8 @@ class Scene:
         if out is None:
             shape, dtype = {0: ((H, W, 3), torch.float32), 1: ((3, H, W), torch.float32), 2: ((H, W, 4), torch.uint8)}[fmt]
             with torch.cuda.stream(stream):  # (allocated, and zeroed, on the stream the frame is exported on)
-                out = (torch.zeros if kw.get("nranks", 1) > 1 else torch.empty)(shape, dtype=dtype, device=dev)
-        st = self.render_device(cam, W, H, out.data_ptr(), format=fmt, row_bytes=row_bytes, stream=stream.cuda_stream, **kw)
-        return out, st
+                out = (torch.zeros if nranks > 1 else torch.empty)(shape, dtype=dtype, device=dev)
+        return out, fmt, row_bytes, stream
 
     # ---- multi-view frames (include/cgrt.h cgrt_*_views*) ----
     def trace_views_device(self, cams, W: int, H: int, d_hits_ptr: int, d_normals_ptr: int = 0, stream: int = 0) -> None:
@@ -724,6 +735,12 @@ class Scene:
         """render_views_device into a torch tensor on cuda:<device>: (B, H, W, 3) f32, (B, 3, H, W) f32 or (B, H, W, 4) u8 -- `out`
         (contiguous, of exactly that shape and dtype; validated before any call, ValueError) or a new tensor, rendered on `stream`
         (default: torch.cuda.current_stream()).  Other keywords as render_views.  Returns (tensor, stats dict)."""
+        a, out, fmt, stream = self._views_tensor(cams, W, H, format, out, stream)
+        st = self.render_views_device(a, W, H, out.data_ptr(), format=fmt, stream=stream.cuda_stream, **kw)
+        return out, st
+
+    def _views_tensor(self, cams, W, H, format, out, stream):
+        """render_views_tensor's checks of `out` (ValueError) and its new tensor: (camera array, out, format code, stream)."""
         import torch
 
         a = camera_array(cams)
@@ -751,8 +768,7 @@ class Scene:
         if out is None:
             with torch.cuda.stream(stream):  # (allocated on the stream the views are exported on)
                 out = torch.empty(shape, dtype=dtype, device=dev)
-        st = self.render_views_device(a, W, H, out.data_ptr(), format=fmt, stream=stream.cuda_stream, **kw)
-        return out, st
+        return a, out, fmt, stream
 
     def _soft_arg(self, spherical, units, samples: int, seed: int):
         """The CgrtSoftShadows argument (None without spherical lights) and the arrays it points into, which the caller keeps alive."""
@@ -792,6 +808,14 @@ class Scene:
         """shade_rays on torch tensors: rays (..., 7) float32, contiguous, on cuda:<device> -> colours (..., 3) float32, e.g. (H, W, 7)
         rays give an (H, W, 3) image.  Into `out` (validated before any call, ValueError, as render_tensor validates its output) or a new
         tensor, ordered on `stream` (default: torch.cuda.current_stream()).  Other keywords as shade_rays.  Returns (tensor, stats dict)."""
+        out, n, stream = self._rays_tensor(rays, out, stream)
+        if n == 0:  # (an empty tensor has no address to pass: the call would touch nothing anyway)
+            return out, {k: 0 for k, _ in RenderStats._fields_}
+        st = self.shade_rays_device(rays.data_ptr(), n, out.data_ptr(), stream=stream.cuda_stream, **kw)
+        return out, st
+
+    def _rays_tensor(self, rays, out, stream):
+        """shade_rays_tensor's checks of `rays` and `out` (ValueError) and its new tensor: (out, number of rays, stream)."""
         import torch
 
         if self.device < 0:
@@ -819,10 +843,72 @@ class Scene:
         if out is None:
             with torch.cuda.stream(stream):  # (allocated on the stream the colours are written on)
                 out = torch.empty(shape, dtype=torch.float32, device=dev)
-        if n == 0:  # (an empty tensor has no address to pass: the call would touch nothing anyway)
-            return out, {k: 0 for k, _ in RenderStats._fields_}
-        st = self.shade_rays_device(rays.data_ptr(), n, out.data_ptr(), stream=stream.cuda_stream, **kw)
-        return out, st
+        return out, n, stream
+
+    # ---- enqueued frames (include/cgrt.h cgrt_enqueue_*) ----
+    # These return as soon as the frame is enqueued on `stream`; the tensors the frame reads or writes must stay alive, and unused by other
+    # streams, until it has run there.  A tensor made on another stream (rays written elsewhere, an `out` allocated elsewhere) needs the
+    # usual torch handling: make `stream` wait for its producer (stream.wait_stream) and call tensor.record_stream(stream), so that the
+    # caching allocator does not hand its memory out again while the frame still uses it.  The host arrays (cameras, lights, soft-shadow
+    # tables) are copied by the call.
+    def enqueue_render_tensor(self, cam, W: int, H: int, format="rgb", out=None, stream=None, aa: bool = False, lights=None, max_level: int = 2,
+                              spherical=None, units=None, samples: int = 200, seed: int = 0, rank: int = 0, nranks: int = 1):
+        """render_tensor without waiting for the GPU (cgrt_enqueue_render_device): same checks (ValueError before any call), same bytes,
+        the whole frame on `stream` (default: torch.cuda.current_stream()).  Returns (tensor, ticket); enqueue_stats(ticket) gives the
+        stats dict."""
+        out, fmt, row_bytes, stream = self._frame_tensor(W, H, format, out, stream, nranks)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
+        t = C.c_uint64()
+        _check(
+            lib().cgrt_enqueue_render_device(
+                self._h, C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, 1 if aa else 0, rank, nranks, C.c_void_p(out.data_ptr()),
+                fmt, int(row_bytes), C.c_void_p(stream.cuda_stream) if stream.cuda_stream else None, C.byref(t),
+            )
+        )  # fmt: skip
+        return out, t.value
+
+    def enqueue_render_views_tensor(self, cams, W: int, H: int, format="rgb", out=None, stream=None, lights=None, max_level: int = 2,
+                                    spherical=None, units=None, samples: int = 200, seed: int = 0):
+        """render_views_tensor without waiting for the GPU (cgrt_enqueue_render_views_device).  Returns (tensor, ticket)."""
+        a, out, fmt, stream = self._views_tensor(cams, W, H, format, out, stream)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        t = C.c_uint64()
+        _check(
+            lib().cgrt_enqueue_render_views_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, _ptr(lights), len(lights), q, max_level, C.c_void_p(out.data_ptr()), fmt,
+                C.c_void_p(stream.cuda_stream) if stream.cuda_stream else None, C.byref(t),
+            )
+        )  # fmt: skip
+        return out, t.value
+
+    def enqueue_shade_rays_tensor(self, rays, out=None, stream=None, lights=None, max_level: int = 2, spherical=None, units=None,
+                                  samples: int = 200, seed: int = 0):
+        """shade_rays_tensor without waiting for the GPU (cgrt_enqueue_shade_rays_device): the frame starts behind everything on `stream`
+        (the kernel that wrote `rays`, when it ran there).  rays written on another stream: stream.wait_stream(that stream) first, and
+        rays.record_stream(stream), as for any torch op.  Returns (tensor, ticket).  An empty list enqueues no work but still gets a ticket
+        (its stats are zero); an empty tensor has no device address, so the call is handed the ticket's own address for d_rgb, which the
+        entry's NULL check accepts and nothing reads when n == 0."""
+        out, n, stream = self._rays_tensor(rays, out, stream)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        t = C.c_uint64()
+        _check(
+            lib().cgrt_enqueue_shade_rays_device(
+                self._h, C.c_void_p(rays.data_ptr()) if n else None, n, _ptr(lights), len(lights), q, max_level,
+                C.c_void_p(out.data_ptr() if n else C.addressof(t)), C.c_void_p(stream.cuda_stream) if stream.cuda_stream else None, C.byref(t),
+            )
+        )  # fmt: skip
+        return out, t.value
+
+    def enqueue_stats(self, ticket: int) -> dict:
+        """cgrt_enqueue_stats: waits for the enqueued frame `ticket` and returns its stats dict (CgrtError CGRT_E_ARG for a ticket that was
+        never issued or has left the scene's ring of the last 8 enqueued frames)."""
+        st = RenderStats()
+        _check(lib().cgrt_enqueue_stats(self._h, int(ticket), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
 
     # ---- visibility queries (include/cgrt.h cgrt_occluded*, cgrt_in_shadow*, cgrt_soft_lit*; DESIGN.md section 5.12) ----
     def occluded(self, rays) -> np.ndarray:

@@ -336,10 +336,41 @@ struct CgrtScene {
         std::vector<uint32_t> counts;
         int last_path = 0;  // how the last frame was drawn: 0 exact, 1 as predicted, 2 predicted, found too small, drawn again exactly
     } rpred;
+    // Enqueued frames (cgrt_enqueue_*; enqueue_impl below): a ring of ENQ_SLOTS ticket slots, each with pinned
+    // staging for the frame's tables (copied to enq_dev by hipMemcpyAsync on the caller's stream), a pinned read-back of its counter block
+    // and the events behind it.  A slot is refilled only once its last frame has finished.  Every frame of the scene (enqueued or blocking)
+    // starts behind the last enqueued one on the device (enq_done), so all of them share the workspace above.
+    static const int ENQ_SLOTS = 8;
+    struct EnqSlot {
+        void* pin = nullptr;         // lights | spherical lights | unit vectors | SpawnDev | view table
+        size_t cap = 0;
+        uint32_t* pin_ctr = nullptr;  // the frame's counter block, copied back behind the frame (cgrt_enqueue_stats)
+        hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;
+        bool pending = false;
+        uint64_t ticket = 0;          // 0: never used
+        // what cgrt_enqueue_stats needs to turn the counters into CgrtRenderStats
+        int max_level = 0, fused = 0;
+        unsigned L = 0, SL = 0, samples = 0;
+        uint64_t primary_rays = 0;
+    } eslot[ENQ_SLOTS];
+    unsigned enq_count = 0;           // enqueued frames issued (slot = enq_count % ENQ_SLOTS)
+    uint64_t frame_seq = 0;           // the scene's frames, blocking and enqueued: an enqueued frame's ticket is its number
+    void* enq_dev = nullptr;          // the device copy of the tables (frames are ordered on the device, so one copy serves them all)
+    size_t enq_dev_cap = 0;
+    hipEvent_t enq_done = nullptr;    // behind the last enqueued frame (one of the slots' `done`)
+    bool enq_pending = false;
     uint64_t device_bytes = 0;
     ~CgrtScene() {
         if (device < 0) return;
         (void)hipSetDevice(device);
+        for (EnqSlot& e : eslot) {  // (frames in flight complete before anything they use is released)
+            if (e.pending) (void)hipEventSynchronize(e.done);
+            for (hipEvent_t ev : {e.done, e.t0, e.t1})
+                if (ev) (void)hipEventDestroy(ev);
+            if (e.pin) (void)hipHostFree(e.pin);
+            if (e.pin_ctr) (void)hipHostFree(e.pin_ctr);
+        }
+        if (enq_dev) (void)hipFree(enq_dev);
         if (export_pending) (void)hipEventSynchronize(export_done);  // (an export may still be reading the workspace)
         if (export_done) (void)hipEventDestroy(export_done);
         for (ViewTable& v : vtab) {
@@ -389,6 +420,16 @@ struct WsBuf {  // a slot of the scene's workspace, with DevBuf's interface
     hipError_t alloc(size_t bytes) {
         CgrtScene::WorkSlot& w = sc->work[slot];
         if (w.cap < bytes || !w.p) {
+            // enqueued frames (and a blocking frame's export) may still use the buffer: they finish before it is released
+            if (w.p && sc->enq_pending) {
+                const hipError_t e = hipEventSynchronize(sc->enq_done);
+                if (e != hipSuccess) return e;
+                sc->enq_pending = false;
+            }
+            if (w.p && sc->export_pending) {
+                const hipError_t e = hipEventSynchronize(sc->export_done);
+                if (e != hipSuccess) return e;
+            }
             if (w.p) (void)hipFree(w.p);
             w.p = nullptr;
             w.cap = 0;
@@ -1256,6 +1297,7 @@ int cgrt_debug_combiner_stats(const CgrtScene* s, uint64_t* out4) {  // (five wo
     return CGRT_OK;
 }
 int cgrt_debug_render_path(const CgrtScene* s) { return s ? s->rpred.last_path : -1; }
+int cgrt_debug_strided_waves(void) { return (int)strided_waves(); }
 int cgrt_debug_hint_counts(CgrtScene* s, uint32_t* out3) {  // the three hard lists' lengths (after a device synchronise): diagnostics
     if (!s || !out3) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);
@@ -1893,6 +1935,29 @@ struct ViewSrc {
     const CgrtCamera* cams;
     uint32_t n;
 };
+// k_export_frame's description of a frame F (its PW x PH pixels in `src`) for the caller's buffer (render_impl, enqueue_impl)
+static ExportDev export_of(const FrameDev& F, const float* src, const DeviceOut& dout, int PW, int PH, uint32_t nviews, bool aa, int rank, int nranks,
+                           int packed) {
+    ExportDev E{};
+    E.src = src;
+    E.dst = static_cast<unsigned char*>(dout.p);
+    E.pitch = dout.pitch;
+    E.W = PW;
+    E.H = PH;
+    E.format = dout.format;
+    if (nviews) {
+        E.views = (int)nviews;
+        E.view_bytes = dout.view_bytes;
+    }
+    if (nranks > 1) {  // super-tiles of the frame, or (aa) 32x32 blocks = super-tiles of the sub-sample frame; F.st_x counts either
+        E.tile = aa ? 32 : 64;
+        E.tiles_x = F.st_x;
+        E.rank = rank;
+        E.nranks = nranks;
+        E.packed = packed;
+    }
+    return E;
+}
 static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats, CgrtCounters* counted = nullptr,
                        const float** mapped = nullptr, bool aa = false, const DeviceOut* dout = nullptr, const ListSrc* list = nullptr,
@@ -2020,6 +2085,9 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     }
     if (after_export)  // (every stream of the frame, before its first write; a no-op once the export has run)
         for (hipStream_t st : {(hipStream_t) nullptr, aux.s, aux.copy}) HIP_TRY(hipStreamWaitEvent(st, s->export_done, 0));
+    if (s->enq_pending)  // (the scene's enqueued frames share the workspace: every stream of this one starts behind the last of them)
+        for (hipStream_t st : {(hipStream_t) nullptr, aux.s, aux.copy}) HIP_TRY(hipStreamWaitEvent(st, s->enq_done, 0));
+    s->frame_seq++;
     if (list) {  // the rays were written on the caller's stream: every stream of the frame starts from the default stream, which waits here
         HIP_TRY(hipEventRecord(aux.caller, list->stream));
         HIP_TRY(hipStreamWaitEvent(nullptr, aux.caller, 0));
@@ -2372,24 +2440,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipStreamWaitEvent(list->stream, aux.e1, 0));
     } else if (dout) {
         // The frame's last kernel is done (aux.e1 was waited for); the wait below only makes that ordering explicit on the caller's stream.
-        ExportDev E{};
-        E.src = aa ? dres.as<float>() : drgb.as<float>();
-        E.dst = static_cast<unsigned char*>(dout->p);
-        E.pitch = dout->pitch;
-        E.W = PW;
-        E.H = PH;
-        E.format = dout->format;
-        if (views) {
-            E.views = (int)nviews;
-            E.view_bytes = dout->view_bytes;
-        }
-        if (nranks > 1) {  // super-tiles of the frame, or (aa) 32x32 blocks = super-tiles of the sub-sample frame; F.st_x counts either
-            E.tile = aa ? 32 : 64;
-            E.tiles_x = F.st_x;
-            E.rank = rank;
-            E.nranks = nranks;
-            E.packed = packed;
-        }
+        const ExportDev E = export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, views ? nviews : 0u, aa, rank, nranks, packed);
         if (!s->export_done) HIP_TRY(hipEventCreateWithFlags(&s->export_done, hipEventDisableTiming));
         HIP_TRY(hipStreamWaitEvent(dout->stream, aux.e1, 0));
         HIP_TRY(launch_export_frame(E, dout->stream));
@@ -2534,9 +2585,9 @@ static int check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, 
     return CGRT_OK;
 }
 
-int cgrt_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
-                       int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
-                       CgrtRenderStats* stats) {
+// cgrt_render_device's checks, in include/cgrt.h's order, all before any device work (cgrt_enqueue_render_device: the same); *pitch = the row pitch
+static int render_device_args(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                              int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, uint64_t* pitch) {
     if (!s) return fail(CGRT_E_ARG, "scene is NULL");
     if (aa) {
         const int rc = aa_args(cam, d_out, W, H, lights, nlights, soft, max_level, rank, nranks);
@@ -2553,14 +2604,19 @@ int cgrt_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             if ((unsigned long long)W * H > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large");
         }
     }
-    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream)};
     uint64_t extent = 0;
-    const int rc = export_args(d_out, W, H, format, row_bytes, &D.pitch, &extent);
+    const int rc = export_args(d_out, W, H, format, row_bytes, pitch, &extent);
     if (rc) return rc;
     NEED_DEVICE(s);
     HIP_TRY(hipSetDevice(s->device));
-    const int sc = check_device_span(s, d_out, extent, "d_out");
-    if (sc) return sc;
+    return check_device_span(s, d_out, extent, "d_out");
+}
+int cgrt_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                       int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
+                       CgrtRenderStats* stats) {
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream)};
+    const int rc = render_device_args(s, cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, d_out, format, row_bytes, &D.pitch);
+    if (rc) return rc;
     return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, nullptr, stats, nullptr, nullptr, aa != 0, &D);
 }
 
@@ -2586,17 +2642,23 @@ int cgrt_render_views(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int
     const ViewSrc V{cams, nviews};
     return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, rgb, stats, nullptr, nullptr, false, nullptr, nullptr, &V);
 }
-int cgrt_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
-                             const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats) {
+// cgrt_render_views_device's checks (cgrt_enqueue_render_views_device: the same); D->pitch and D->view_bytes are set
+static int render_views_device_args(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                                    const CgrtSoftShadows* soft, int max_level, void* d_out, int format, DeviceOut* D) {
     int rc = render_views_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out);
     if (rc) return rc;
-    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
     uint64_t extent = 0;
-    if ((rc = export_args(d_out, W, H, format, 0, &D.pitch, &extent))) return rc;
-    D.view_bytes = extent;  // (packed rows: one view's frame is exactly its extent)
+    if ((rc = export_args(d_out, W, H, format, 0, &D->pitch, &extent))) return rc;
+    D->view_bytes = extent;  // (packed rows: one view's frame is exactly its extent)
     NEED_DEVICE(s);
     HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_out, extent * nviews, "d_out"))) return rc;
+    return check_device_span(s, d_out, extent * nviews, "d_out");
+}
+int cgrt_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                             const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats) {
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D);
+    if (rc) return rc;
     const ViewSrc V{cams, nviews};
     return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, &D, nullptr, &V);
 }
@@ -2614,18 +2676,24 @@ static int shade_rays_args(const CgrtScene* s, const void* rays, uint64_t n, con
     NEED_DEVICE(s);
     return CGRT_OK;
 }
+// cgrt_shade_rays_device's checks (cgrt_enqueue_shade_rays_device: the same); n == 0 needs no buffers
+static int shade_rays_device_args(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                                  int max_level, float* d_rgb) {
+    int rc = shade_rays_args(s, d_rays, n, lights, nlights, soft, max_level, d_rgb);
+    if (rc || n == 0) return rc;
+    if ((uintptr_t)d_rays % 4 || (uintptr_t)d_rgb % 4) return fail(CGRT_E_ARG, "d_rays and d_rgb must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
+    return check_device_span(s, d_rgb, n * 12, "d_rgb");
+}
 int cgrt_shade_rays_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                            int max_level, float* d_rgb, void* stream, CgrtRenderStats* stats) {
-    int rc = shade_rays_args(s, d_rays, n, lights, nlights, soft, max_level, d_rgb);
+    const int rc = shade_rays_device_args(s, d_rays, n, lights, nlights, soft, max_level, d_rgb);
     if (rc) return rc;
     if (n == 0) {
         if (stats) *stats = CgrtRenderStats{};
         return CGRT_OK;
     }
-    if ((uintptr_t)d_rays % 4 || (uintptr_t)d_rgb % 4) return fail(CGRT_E_ARG, "d_rays and d_rgb must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_rgb, n * 12, "d_rgb")) != CGRT_OK) return rc;
     const ListSrc src{reinterpret_cast<const float*>(d_rays), n, d_rgb, static_cast<hipStream_t>(stream)};
     return render_impl(s, nullptr, 1, 1, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, nullptr, &src);
 }
@@ -2652,6 +2720,284 @@ int cgrt_shade_rays(CgrtScene* s, const CgrtRay* rays, uint64_t n, const float* 
     HIP_TRY(lane_download(g, 1, rgb, dc, n * 12, &staged));
     HIP_TRY(hipStreamSynchronize(g.L->stream));
     if (staged) std::memcpy(rgb, staged, n * 12);
+    return CGRT_OK;
+}
+
+// ---- enqueued frames (include/cgrt.h cgrt_enqueue_*) ----
+// The frame of render_impl's exact path, issued without a host round trip: every list is sized for the worst case (as render_impl
+// sizes the workspace anyway), all max_level levels are issued, and every launch after the primary kernel is a capped, count-driven grid
+// (the *_strided launchers) that reads its list's length on the device.  A single camera's level 0 is spawned by the primary kernel
+// itself (the predicted frame's fused spawn); views and ray lists run their own primary kernels and a count-driven spawn.  The whole
+// frame, export included, is on the caller's stream, behind the scene's previous frames (enq_done, export_done), and nothing is waited
+// for on the host unless the workspace grows or every ticket slot is in flight.  Same kernels' expressions on the same entries, each
+// scattered back by its pixel: the bytes are the blocking entry's.  The caller has checked the arguments (the blocking entries' checks).
+static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                        int max_level, int rank, int nranks, bool aa, const DeviceOut* dout, const ListSrc* list, const ViewSrc* views,
+                        hipStream_t stream, uint64_t* ticket) {
+    const int PW = W, PH = H;
+    if (aa) {
+        W *= 2;
+        H *= 2;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> one_frame(s->render_mutex);
+    const uint32_t nviews = views ? views->n : 1u;
+    const unsigned long long npix = list ? list->n : (unsigned long long)W * H * nviews;
+    const unsigned L = nlights, SL = soft ? soft->nspherical : 0;
+    FrameDev F{};
+    if (views) {
+        if (!make_views_frame(W, H, nviews, trace_block(s->dev), F)) return fail(CGRT_E_ARG, "bad batch");
+    } else if (!list && !make_frame(W, H, 0, 0, W, H, rank, nranks, trace_block(s->dev), F)) {
+        return fail(CGRT_E_ARG, "bad frame or rank");
+    }
+    const unsigned long long n = list ? list->n : (unsigned long long)F.nblocks * (unsigned long long)F.block;
+    // the ticket slot: its last frame must be over before its staging is written again (the documented wait)
+    CgrtScene::EnqSlot& slot = s->eslot[s->enq_count % CgrtScene::ENQ_SLOTS];
+    if (slot.pending) {
+        HIP_TRY(hipEventSynchronize(slot.done));
+        slot.pending = false;
+    }
+    if (!slot.done) {
+        HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+        HIP_TRY(hipEventCreate(&slot.t0));
+        HIP_TRY(hipEventCreate(&slot.t1));
+        HIP_TRY(hipHostMalloc((void**)&slot.pin_ctr, 4 * 17 * sizeof(uint32_t), hipHostMallocDefault));
+    }
+    // the workspace of render_impl, sized for the worst case (WsBuf::alloc waits for the scene's frames before a buffer grows)
+    WsBuf rays[3] = {{s, 0}, {s, 1}, {s, 21}}, hits[3] = {{s, 2}, {s, 3}, {s, 22}}, normals[3] = {{s, 4}, {s, 5}, {s, 23}},
+          pix[3] = {{s, 6}, {s, 7}, {s, 24}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
+          sslot[2] = {{s, 12}, {s, 28}}, levels{s, 14}, drgb{s, 15}, dctr{s, 16}, dlit{s, 19}, dres{s, 30};
+    const int packed = aa && nranks > 1;
+    const size_t res_bytes = packed ? (size_t)F.nst_rank * 1024 * 12 : (size_t)PW * PH * 12;
+    const size_t dres_bytes = std::max<size_t>(res_bytes, (size_t)F.nst_rank * 1024 * 12);
+    const size_t nctr = 4 * (size_t)(max_level + 1);
+    if (n) {
+        HIP_TRY(ipix.alloc(n * 4));
+        for (int k = 0; k < 3; k++) {
+            HIP_TRY(rays[k].alloc(n * 28));
+            HIP_TRY(hits[k].alloc(n * sizeof(CgrtHit)));
+            HIP_TRY(normals[k].alloc(n * 12));
+            HIP_TRY(pix[k].alloc(n * 4));
+        }
+        for (int k = 0; k < 2; k++) {
+            HIP_TRY(srays[k].alloc(n * L * 28));
+            HIP_TRY(shits[k].alloc(n * L * sizeof(CgrtHit)));
+            HIP_TRY(sdist[k].alloc(n * L * 4));
+            HIP_TRY(sslot[k].alloc(n * L * 4));
+        }
+        HIP_TRY(levels.alloc((size_t)(max_level > 0 ? max_level : 1) * n * 32));
+        if (!list) HIP_TRY(drgb.alloc(npix * 12));
+        if (aa) HIP_TRY(dres.alloc(dres_bytes));
+        HIP_TRY(dctr.alloc(nctr * sizeof(uint32_t)));
+        if (SL) HIP_TRY(dlit.alloc(n * SL * 4));
+    }
+    // the frame's tables, through the slot's pinned staging: the caller may reuse its arrays once the call returns
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_lights = 0, o_slights = up16((size_t)L * 24), o_units = o_slights + up16((size_t)SL * 28),
+                 o_spawn = o_units + up16(SL ? (size_t)soft->nunits * 12 : 0), o_views = o_spawn + up16(sizeof(SpawnDev)),
+                 table_bytes = o_views + (views ? (size_t)nviews * sizeof(CameraDev) : 0);
+    if (slot.cap < table_bytes) {
+        if (slot.pin) (void)hipHostFree(slot.pin);
+        slot.pin = nullptr;
+        slot.cap = 0;
+        HIP_TRY(hipHostMalloc(&slot.pin, table_bytes, hipHostMallocDefault));
+        slot.cap = table_bytes;
+    }
+    if (s->enq_dev_cap < table_bytes) {
+        if (s->enq_dev && s->enq_pending) HIP_TRY(hipEventSynchronize(s->enq_done));  // (the frames in flight read it)
+        if (s->enq_dev) (void)hipFree(s->enq_dev);
+        s->enq_dev = nullptr;
+        s->enq_dev_cap = 0;
+        HIP_TRY(hipMalloc(&s->enq_dev, table_bytes));
+        s->enq_dev_cap = table_bytes;
+    }
+    char* const pin = static_cast<char*>(slot.pin);
+    char* const tab = static_cast<char*>(s->enq_dev);
+    const float* const dl = reinterpret_cast<const float*>(tab + o_lights);
+    if (L) std::memcpy(pin + o_lights, lights, (size_t)L * 24);
+    SoftDev Q{};
+    if (SL) {
+        std::memcpy(pin + o_slights, soft->spherical, (size_t)SL * 28);
+        std::memcpy(pin + o_units, soft->unit_vectors, (size_t)soft->nunits * 12);
+        Q.lights = reinterpret_cast<const float*>(tab + o_slights);
+        Q.units = reinterpret_cast<const float*>(tab + o_units);
+        Q.nlights = SL;
+        Q.samples = soft->samples;
+        Q.nunits = soft->nunits;
+        Q.seed = soft->seed;
+        if (views) Q.view_pixels = (uint32_t)W * (uint32_t)H;
+    }
+    const float* const mats = static_cast<const float*>(s->d_materials);
+    const bool fused = !list && !views;  // level 0 spawned by the primary kernel (spawn_rays.h)
+    auto ctr_of = [&](int level) { return dctr.as<uint32_t>() + 4 * (size_t)level; };
+    auto lvl_of = [&](int level) { return levels.as<float>() + (size_t)level * n * 8; };
+    uint32_t* const pair = dctr.as<uint32_t>() + 4 * (size_t)max_level + 2;  // fused: {level 0's entries, level 1's entries}
+    uint32_t* const primary_hits = pair + 1;                                   // views, lists: level 0's entries
+    if (fused && max_level >= 1) {
+        SpawnDev SP{};
+        SP.materials = mats;
+        SP.lights = dl;
+        SP.nlights = L;
+        SP.spawn = 1 < max_level;
+        SP.srays = srays[0].as<float>();
+        SP.sdist = sdist[0].as<float>();
+        SP.sslot = sslot[0].as<int>();
+        SP.lvl = reinterpret_cast<float4*>(lvl_of(0));
+        SP.next_rays = rays[1].as<float>();
+        SP.next_pixels = pix[1].as<int>();
+        std::memcpy(pin + o_spawn, &SP, sizeof(SP));
+    }
+    if (views) {
+        const std::vector<CameraDev> vt = view_cameras(views->cams, nviews);
+        std::memcpy(pin + o_views, vt.data(), vt.size() * sizeof(CameraDev));
+        F.views = reinterpret_cast<CameraDev*>(tab + o_views);
+    }
+    // ---- the frame, on the caller's stream ----
+    if (s->enq_pending) HIP_TRY(hipStreamWaitEvent(stream, s->enq_done, 0));
+    if (s->export_pending) HIP_TRY(hipStreamWaitEvent(stream, s->export_done, 0));
+    HIP_TRY(hipEventRecord(slot.t0, stream));
+    HIP_TRY(hipMemcpyAsync(tab, pin, table_bytes, hipMemcpyHostToDevice, stream));
+    float* const frame_rgb = list ? list->rgb : drgb.as<float>();
+    if (n) {
+        HIP_TRY(hipMemsetAsync(dctr.p, 0, nctr * sizeof(uint32_t), stream));
+        if (max_level < 1) {  // trace() returns black without tracing (main.cpp:267)
+            if (list || views)
+                HIP_TRY(hipMemsetAsync(frame_rgb, 0, npix * 12, stream));
+            else
+                HIP_TRY(launch_clear_owned(F, frame_rgb, stream));
+        } else {
+            // device word with the entries of a level / the mirror rays a level spawned
+            auto count_of = [&](int level) -> uint32_t* {
+                if (level == 0) return fused ? pair : primary_hits;
+                return (fused && level == 1) ? pair + 1 : ctr_of(level - 1) + 1;
+            };
+            auto mirrors_of = [&](int level) -> uint32_t* { return (fused && level == 0) ? pair + 1 : ctr_of(level) + 1; };
+            if (list)  // (also clears the list's colours)
+                HIP_TRY(launch_trace_list_compact(s->dev, list->rays, n, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
+                                                  ipix.as<int>(), primary_hits, frame_rgb, stream));
+            else if (views)  // (also clears every view's pixels)
+                HIP_TRY(launch_trace_primary_views_compact(s->dev, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
+                                                           ipix.as<int>(), primary_hits, frame_rgb, stream));
+            else  // (also clears this rank's pixels, and spawns level 0)
+                HIP_TRY(launch_trace_primary_compact(s->dev, make_camera(*cam), F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
+                                                     ipix.as<int>(), pair, stream, nullptr, frame_rgb,
+                                                     reinterpret_cast<const SpawnDev*>(tab + o_spawn)));
+            const bool pairable = can_trace_pair(s->dev);
+            for (int level = 0; level < max_level; level++) {
+                const int a = level % 3, b = (level + 1) % 3, q = level & 1;  // as render_impl's buffer sets
+                const int spawn = level + 1 < max_level;
+                const int* cur_pix = level == 0 ? ipix.as<int>() : pix[a].as<int>();
+                if (!(fused && level == 0))
+                    HIP_TRY(launch_spawn_strided(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), cur_pix, n, mats, dl, L, spawn,
+                                                 srays[q].as<float>(), sdist[q].as<float>(), sslot[q].as<int>(), lvl_of(level), rays[b].as<float>(),
+                                                 pix[b].as<int>(), ctr_of(level), stream, count_of(level)));
+                // the level's shadow list: hits x lights rays (fused level 0) or the appended count
+                const uint32_t* sdc = (fused && level == 0) ? pair : ctr_of(level);
+                const unsigned sdmul = (fused && level == 0) ? L : 1u;
+                if (L && spawn && pairable) {
+                    HIP_TRY(launch_trace_pair_strided(s->dev, srays[q].as<float>(), sdist[q].as<float>(), n * L, shits[q].as<CgrtHitDev>(), sdc, sdmul,
+                                                      rays[b].as<float>(), n, hits[b].as<CgrtHitDev>(), normals[b].as<float>(), mirrors_of(level), stream));
+                } else {
+                    if (L)
+                        HIP_TRY(launch_trace_shadow_strided(s->dev, srays[q].as<float>(), sdist[q].as<float>(), n * L, shits[q].as<CgrtHitDev>(), stream, sdc,
+                                                            sdmul));
+                    if (spawn)
+                        HIP_TRY(launch_trace_batch_strided(s->dev, rays[b].as<float>(), n, hits[b].as<CgrtHitDev>(), normals[b].as<float>(), stream,
+                                                           mirrors_of(level)));
+                }
+                if (SL) {
+                    Q.level = (uint32_t)level;
+                    HIP_TRY(hipMemsetAsync(dlit.p, 0, n * SL * 4, stream));
+                    HIP_TRY(launch_soft_shadow_strided(s->dev, Q, rays[a].as<float>(), hits[a].as<CgrtHitDev>(), cur_pix, n, count_of(level),
+                                                       dlit.as<uint32_t>(), soft->closest_hit == 0, stream));
+                }
+                HIP_TRY(launch_shade_strided(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(),
+                                             sdist[q].as<float>(), sslot[q].as<int>(), n, mats, dl, L, Q.lights, SL, dlit.as<uint32_t>(), Q.samples,
+                                             lvl_of(level), stream, count_of(level)));
+            }
+            for (int level = max_level - 2; level >= 1; level--) HIP_TRY(launch_fold_strided(lvl_of(level), lvl_of(level + 1), n, stream, count_of(level)));
+            HIP_TRY(launch_write_rgb_strided(lvl_of(0), max_level >= 2 ? lvl_of(1) : nullptr, n, ipix.as<int>(), frame_rgb, stream, count_of(0)));
+        }
+        if (aa) HIP_TRY(launch_resolve_aa(F, drgb.as<float>(), dres.as<float>(), packed, stream));
+        if (dout) HIP_TRY(launch_export_frame(export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, views ? nviews : 0u, aa, rank, nranks,
+                                                        packed), stream));
+        HIP_TRY(hipMemcpyAsync(slot.pin_ctr, dctr.p, nctr * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipEventRecord(slot.t1, stream));
+    HIP_TRY(hipEventRecord(slot.done, stream));
+    s->enq_done = slot.done;
+    s->enq_pending = true;
+    s->enq_count++;
+    slot.pending = true;
+    slot.ticket = ++s->frame_seq;
+    slot.max_level = n ? max_level : 0;
+    slot.fused = fused;
+    slot.L = L;
+    slot.SL = SL;
+    slot.samples = SL ? soft->samples : 0;
+    slot.primary_rays = (n && max_level >= 1) ? (list ? n : views ? npix : owned_pixels(F)) : 0;
+    if (ticket) *ticket = slot.ticket;
+    return CGRT_OK;
+}
+
+int cgrt_enqueue_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                               int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
+                               uint64_t* ticket) {
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream)};
+    const int rc = render_device_args(s, cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, d_out, format, row_bytes, &D.pitch);
+    if (rc) return rc;
+    return enqueue_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, aa != 0, &D, nullptr, nullptr, D.stream, ticket);
+}
+int cgrt_enqueue_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                                     const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, uint64_t* ticket) {
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D);
+    if (rc) return rc;
+    const ViewSrc V{cams, nviews};
+    return enqueue_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream, ticket);
+}
+int cgrt_enqueue_shade_rays_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                                   int max_level, float* d_rgb, void* stream, uint64_t* ticket) {
+    const int rc = shade_rays_device_args(s, d_rays, n, lights, nlights, soft, max_level, d_rgb);
+    if (rc) return rc;
+    const ListSrc src{reinterpret_cast<const float*>(d_rays), n, d_rgb, static_cast<hipStream_t>(stream)};
+    return enqueue_impl(s, nullptr, 1, 1, lights, nlights, soft, max_level, 0, 1, false, nullptr, &src, nullptr, src.stream, ticket);
+}
+int cgrt_enqueue_stats(CgrtScene* s, uint64_t ticket, CgrtRenderStats* stats) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    hipEvent_t done = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(s->render_mutex);
+        for (const CgrtScene::EnqSlot& e : s->eslot)
+            if (ticket && e.ticket == ticket) done = e.done;
+    }
+    if (!done) return fail(CGRT_E_ARG, "unknown ticket: never issued, or no longer in the scene's ring of enqueued frames");
+    HIP_TRY(hipEventSynchronize(done));
+    std::lock_guard<std::mutex> lk(s->render_mutex);
+    const CgrtScene::EnqSlot* e = nullptr;
+    for (const CgrtScene::EnqSlot& x : s->eslot)
+        if (x.ticket == ticket) e = &x;
+    if (!e) return fail(CGRT_E_ARG, "unknown ticket: no longer in the scene's ring of enqueued frames");
+    CgrtRenderStats st{};
+    const uint32_t* h = e->pin_ctr;
+    const int ml = e->max_level;
+    st.primary_rays = e->primary_rays;
+    for (int level = 0; level < ml; level++) {  // the levels with entries, as the blocking frame evaluates them
+        const uint32_t entries = level == 0 ? h[4 * ml + (e->fused ? 2 : 3)] : (e->fused && level == 1) ? h[4 * ml + 3] : h[4 * (level - 1) + 1];
+        if (entries == 0) break;
+        const bool f0 = e->fused && level == 0;  // (the fused spawn keeps no counter block: every entry is a hit)
+        const uint64_t hits = f0 ? entries : h[4 * level + 2];
+        st.shadow_rays += f0 ? (uint64_t)entries * e->L : h[4 * level + 0];
+        st.reflection_rays += f0 ? h[4 * ml + 3] : h[4 * level + 1];
+        st.soft_shadow_rays += hits * e->SL * e->samples;
+        st.levels = level + 1;
+    }
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e->t0, e->t1));
+    st.device_ms = ms;
+    if (stats) *stats = st;
     return CGRT_OK;
 }
 

@@ -12,6 +12,8 @@
 // ulp may differ from glibc's -- the RGB parity bar is 1e-5 absolute).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "cgrt_layout.h"
 #include "cgrt_math.h"
 #include "spawn_rays.h"
@@ -45,6 +47,50 @@ __device__ __forceinline__ uint32_t block_append(uint32_t* counter, const bool w
 }
 #define CGRT_SHADE_BLOCK 1024
 
+// entry i of k_spawn, for k_spawn_strided (n: the list's length; every thread of the workgroup calls it: the appends are per workgroup);
+// returns whether entry i is a hit.  A copy of k_spawn's body (k_spawn keeps its own: calling this changed its SGPRs, measured
+// with tools/enqueue_resource_usage.py): the two must stay in step.
+__device__ __forceinline__ bool spawn_entry(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits, const float* __restrict__ normals,
+                                            const int* __restrict__ pixels, unsigned long long i, unsigned long long n, const float* __restrict__ materials,
+                                            const float* __restrict__ lights, unsigned nlights, int spawn, float* __restrict__ srays,
+                                            float* __restrict__ sdist, int* __restrict__ sslot, float4* __restrict__ lvl, float* __restrict__ next_rays,
+                                            int* __restrict__ next_pixels, uint32_t* __restrict__ counters, uint32_t* s_tmp) {
+    const bool in = i < n;
+    const bool hit = in && hits[i].hit != 0;
+    F3 pointOn = f3(0.f, 0.f, 0.f), d = f3(0.f, 0.f, 0.f), ks = f3(0.f, 0.f, 0.f);
+    if (hit) {
+        const float* r = rays + 7 * i;
+        d = ldv(r + 3);
+        pointOn = add(ldv(r), scale(d, hits[i].t));
+        const int mid = hits[i].material_id;
+        // a hit that never wrote hitInfo.material (sphere only) reads an indeterminate Material upstream; default Material here
+        ks = mid >= 0 ? ldv(materials + 8 * mid + 3) : f3(0.f, 0.f, 0.f);
+    }
+    for (unsigned l = 0; l < nlights; l++) {
+        const uint32_t idx = block_append(counters + 0, hit, s_tmp);
+        if (in) sslot[i * nlights + l] = hit ? (int)idx : -1;
+        if (hit) spawn_shadow_ray(lights, l, pointOn, idx, srays, sdist);
+    }
+    // :246 tests ks.z only (comma operator); `spawn` = level + 1 < maxLevel (:267)
+    const bool wants_mirror = hit && !(ks.z <= 0.01f) && spawn;
+    const uint32_t child = block_append(counters + 1, wants_mirror, s_tmp);
+    if (wants_mirror) {
+        spawn_mirror_ray(pointOn, d, ldv(normals + 3 * i), child, next_rays);
+        next_pixels[child] = pixels[i];
+    }
+    if (in) lvl[2 * i + 1] = make_float4(ks.x, ks.y, ks.z, __int_as_float(wants_mirror ? (int)child : -1));
+    return hit;
+}
+// hits of the level: one atomic per workgroup (h: the wave's count)
+__device__ __forceinline__ void spawn_count_hits(uint32_t h, uint32_t* __restrict__ counters, uint32_t* s_tmp) {
+    if ((threadIdx.x & 63) == 0) s_tmp[threadIdx.x >> 6] = h;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (unsigned k = 0; k < (blockDim.x >> 6); k++) tot += s_tmp[k];
+        if (tot) atomicAdd(counters + 2, tot);
+    }
+}
 // Everything a hit spawns, in one pass: pointInShadow's rays (main.cpp:104-111) for every light, appended to the level's
 // shadow list, and shade's mirror ray (:246-258), appended to the next level's list -- the mirror ray does not depend on
 // the shadow results, so its batch can be traversed on a second stream while this level's shadow batch runs.
@@ -98,22 +144,36 @@ __global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_spawn(const float* __restr
         if (tot) atomicAdd(counters + 2, tot);
     }
 }
+// The count-driven forms of this file's list kernels (enqueued frames, capi.cpp enqueue_impl): dcount is required, n is the list's
+// capacity, and a capped grid strides over the *dcount entries present, gridDim.x * blockDim.x at a time (the loops are uniform per
+// workgroup, as block_append needs).  An entry is handled by the expressions of the one-pass kernel: the results are its results.
+__global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_spawn_strided(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                                    const float* __restrict__ normals, const int* __restrict__ pixels,
+                                                                    unsigned long long n, const float* __restrict__ materials,
+                                                                    const float* __restrict__ lights, unsigned nlights, int spawn,
+                                                                    float* __restrict__ srays, float* __restrict__ sdist, int* __restrict__ sslot,
+                                                                    float4* __restrict__ lvl, float* __restrict__ next_rays,
+                                                                    int* __restrict__ next_pixels, uint32_t* __restrict__ counters,
+                                                                    const uint32_t* __restrict__ dcount) {
+    const unsigned long long present = *dcount;
+    n = present < n ? present : n;
+    __shared__ uint32_t s_tmp[CGRT_SHADE_BLOCK / 64 + 1];
+    uint32_t h = 0;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x; base < n; base += step) {
+        const bool hit = spawn_entry(rays, hits, normals, pixels, base + threadIdx.x, n, materials, lights, nlights, spawn, srays, sdist, sslot, lvl,
+                                     next_rays, next_pixels, counters, s_tmp);
+        h += (uint32_t)__popcll(__ballot(hit));  // (block_append's last barrier has freed s_tmp for the next pass)
+    }
+    spawn_count_hits(h, counters, s_tmp);
+}
 
 // shading (main.cpp:160-235) for one level: lvl[2 i] = {direct light.xyz, flags}, flags bit0 = hit.
-__global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_shade(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
-                                                            const float* __restrict__ normals, const CgrtHitDev* __restrict__ shits,
-                                                            const float* __restrict__ sdist, const int* __restrict__ sslot,
-                                                            unsigned long long n, const float* __restrict__ materials,
-                                                            const float* __restrict__ lights, unsigned nlights,
-                                                            const float* __restrict__ slights, unsigned nslights,
-                                                            const uint32_t* __restrict__ lit, unsigned samples, float4* __restrict__ lvl,
-                                                            const uint32_t* __restrict__ dcount) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (dcount) {
-        const unsigned long long present = *dcount;
-        n = present < n ? present : n;
-    }
-    if (i >= n) return;
+__device__ __forceinline__ void shade_entry(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits, const float* __restrict__ normals,
+                                            const CgrtHitDev* __restrict__ shits, const float* __restrict__ sdist, const int* __restrict__ sslot,
+                                            unsigned long long i, const float* __restrict__ materials, const float* __restrict__ lights, unsigned nlights,
+                                            const float* __restrict__ slights, unsigned nslights, const uint32_t* __restrict__ lit, unsigned samples,
+                                            float4* __restrict__ lvl) {
     float4 out0 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (hits[i].hit) {
         const float* r = rays + 7 * i;
@@ -166,9 +226,46 @@ __global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_shade(const float* __restr
     }
     lvl[2 * i] = out0;
 }
+__global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_shade(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                            const float* __restrict__ normals, const CgrtHitDev* __restrict__ shits,
+                                                            const float* __restrict__ sdist, const int* __restrict__ sslot,
+                                                            unsigned long long n, const float* __restrict__ materials,
+                                                            const float* __restrict__ lights, unsigned nlights,
+                                                            const float* __restrict__ slights, unsigned nslights,
+                                                            const uint32_t* __restrict__ lit, unsigned samples, float4* __restrict__ lvl,
+                                                            const uint32_t* __restrict__ dcount) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (dcount) {
+        const unsigned long long present = *dcount;
+        n = present < n ? present : n;
+    }
+    if (i >= n) return;
+    shade_entry(rays, hits, normals, shits, sdist, sslot, i, materials, lights, nlights, slights, nslights, lit, samples, lvl);
+}
+__global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_shade_strided(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                                    const float* __restrict__ normals, const CgrtHitDev* __restrict__ shits,
+                                                                    const float* __restrict__ sdist, const int* __restrict__ sslot,
+                                                                    unsigned long long n, const float* __restrict__ materials,
+                                                                    const float* __restrict__ lights, unsigned nlights,
+                                                                    const float* __restrict__ slights, unsigned nslights,
+                                                                    const uint32_t* __restrict__ lit, unsigned samples, float4* __restrict__ lvl,
+                                                                    const uint32_t* __restrict__ dcount) {
+    const unsigned long long present = *dcount;
+    n = present < n ? present : n;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
+        shade_entry(rays, hits, normals, shits, sdist, sslot, i, materials, lights, nlights, slights, nslights, lit, samples, lvl);
+}
 
 // colour = !hit ? 0 : (ks.z <= 0.01 ? direct : direct + childColour * ks)   (main.cpp:248, :262, :293); the child's
 // record already holds its folded colour (levels are folded deepest first).
+__device__ __forceinline__ void fold_entry(float4* __restrict__ lvl, const float4* __restrict__ child_lvl, unsigned long long i) {
+    const float4 a = lvl[2 * i], b = lvl[2 * i + 1];
+    const int child = __float_as_int(b.w);
+    if (!(__float_as_uint(a.w) & 1u) || (b.z <= 0.01f) || child < 0) return;  // no child: colour + 0 * ks = colour
+    const float4 c = child_lvl[2 * (unsigned long long)child];  // a child that missed holds colour 0
+    lvl[2 * i] = make_float4(a.x + c.x * b.x, a.y + c.y * b.y, a.z + c.z * b.z, a.w);
+}
 __global__ void k_fold(float4* __restrict__ lvl, const float4* __restrict__ child_lvl, unsigned long long n,
                        const uint32_t* __restrict__ dcount) {
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -177,22 +274,18 @@ __global__ void k_fold(float4* __restrict__ lvl, const float4* __restrict__ chil
         n = present < n ? present : n;
     }
     if (i >= n) return;
-    const float4 a = lvl[2 * i], b = lvl[2 * i + 1];
-    const int child = __float_as_int(b.w);
-    if (!(__float_as_uint(a.w) & 1u) || (b.z <= 0.01f) || child < 0) return;  // no child: colour + 0 * ks = colour
-    const float4 c = child_lvl[2 * (unsigned long long)child];  // a child that missed holds colour 0
-    lvl[2 * i] = make_float4(a.x + c.x * b.x, a.y + c.y * b.y, a.z + c.z * b.z, a.w);
+    fold_entry(lvl, child_lvl, i);
+}
+__global__ void k_fold_strided(float4* __restrict__ lvl, const float4* __restrict__ child_lvl, unsigned long long n, const uint32_t* __restrict__ dcount) {
+    const unsigned long long present = *dcount;
+    n = present < n ? present : n;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) fold_entry(lvl, child_lvl, i);
 }
 
 // child_lvl (optional): the fold of level 0 with level 1 (k_fold's arithmetic) happens here, one launch less
-__global__ void k_write_rgb(const float4* __restrict__ lvl0, const float4* __restrict__ child_lvl, unsigned long long n,
-                            const int* __restrict__ item_pixels, float* __restrict__ rgb, const uint32_t* __restrict__ dcount) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (dcount) {
-        const unsigned long long present = *dcount;
-        n = present < n ? present : n;
-    }
-    if (i >= n) return;
+__device__ __forceinline__ void write_rgb_entry(const float4* __restrict__ lvl0, const float4* __restrict__ child_lvl, unsigned long long i,
+                                                const int* __restrict__ item_pixels, float* __restrict__ rgb) {
     const long long pix = item_pixels[i];
     if (pix < 0) return;  // item outside the frame
     float4 a = lvl0[2 * i];
@@ -207,6 +300,23 @@ __global__ void k_write_rgb(const float4* __restrict__ lvl0, const float4* __res
     rgb[3 * pix] = a.x;
     rgb[3 * pix + 1] = a.y;
     rgb[3 * pix + 2] = a.z;
+}
+__global__ void k_write_rgb(const float4* __restrict__ lvl0, const float4* __restrict__ child_lvl, unsigned long long n,
+                            const int* __restrict__ item_pixels, float* __restrict__ rgb, const uint32_t* __restrict__ dcount) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (dcount) {
+        const unsigned long long present = *dcount;
+        n = present < n ? present : n;
+    }
+    if (i >= n) return;
+    write_rgb_entry(lvl0, child_lvl, i, item_pixels, rgb);
+}
+__global__ void k_write_rgb_strided(const float4* __restrict__ lvl0, const float4* __restrict__ child_lvl, unsigned long long n,
+                                    const int* __restrict__ item_pixels, float* __restrict__ rgb, const uint32_t* __restrict__ dcount) {
+    const unsigned long long present = *dcount;
+    n = present < n ? present : n;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) write_rgb_entry(lvl0, child_lvl, i, item_pixels, rgb);
 }
 
 // The reference's antiAliasing branch (main.cpp:663-687): pixel (x, y) of the W x H frame is resolved from the sub-samples
@@ -356,6 +466,43 @@ hipError_t launch_write_rgb(const float* lvl0, const float* child_lvl, unsigned 
                             const uint32_t* dcount) {
     if (n)
         hipLaunchKernelGGL(k_write_rgb, dim3(grid_for(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
+                           reinterpret_cast<const float4*>(child_lvl), n, item_pixels, rgb, dcount);
+    return hipGetLastError();
+}
+
+// the count-driven forms: at most strided_waves() waves per launch (trace_kernels.hip), whatever the capacity n
+static inline unsigned strided_grid(unsigned long long n, unsigned block) {
+    const unsigned cap = (unsigned)std::max<unsigned long long>(1ull, (unsigned long long)strided_waves() * 64ull / block);
+    const unsigned full = grid_for(n, block);
+    return full < cap ? full : cap;
+}
+hipError_t launch_spawn_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const int* pixels, unsigned long long n,
+                                const float* materials, const float* lights, unsigned nlights, int spawn, float* srays, float* sdist, int* sslot,
+                                float* lvl, float* next_rays, int* next_pixels, uint32_t* counters, hipStream_t s, const uint32_t* dcount) {
+    if (n)
+        hipLaunchKernelGGL(k_spawn_strided, dim3(strided_grid(n, CGRT_SHADE_BLOCK)), dim3(CGRT_SHADE_BLOCK), 0, s, rays, hits, normals, pixels, n, materials,
+                           lights, nlights, spawn, srays, sdist, sslot, reinterpret_cast<float4*>(lvl), next_rays, next_pixels, counters, dcount);
+    return hipGetLastError();
+}
+hipError_t launch_shade_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
+                                const int* sslot, unsigned long long n, const float* materials, const float* lights, unsigned nlights,
+                                const float* slights, unsigned nslights, const uint32_t* lit, unsigned samples, float* lvl, hipStream_t s,
+                                const uint32_t* dcount) {
+    if (n)
+        hipLaunchKernelGGL(k_shade_strided, dim3(strided_grid(n, CGRT_SHADE_BLOCK)), dim3(CGRT_SHADE_BLOCK), 0, s, rays, hits, normals, shits, sdist, sslot,
+                           n, materials, lights, nlights, slights, nslights, lit, samples, reinterpret_cast<float4*>(lvl), dcount);
+    return hipGetLastError();
+}
+hipError_t launch_fold_strided(float* lvl, const float* child_lvl, unsigned long long n, hipStream_t s, const uint32_t* dcount) {
+    if (n)
+        hipLaunchKernelGGL(k_fold_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, reinterpret_cast<float4*>(lvl),
+                           reinterpret_cast<const float4*>(child_lvl), n, dcount);
+    return hipGetLastError();
+}
+hipError_t launch_write_rgb_strided(const float* lvl0, const float* child_lvl, unsigned long long n, const int* item_pixels, float* rgb, hipStream_t s,
+                                    const uint32_t* dcount) {
+    if (n)
+        hipLaunchKernelGGL(k_write_rgb_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
                            reinterpret_cast<const float4*>(child_lvl), n, item_pixels, rgb, dcount);
     return hipGetLastError();
 }

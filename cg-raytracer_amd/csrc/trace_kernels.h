@@ -88,6 +88,20 @@ hipError_t launch_trace_primary_views_compact(const SceneDev& S, const FrameDev&
 hipError_t launch_trace_list_compact(const SceneDev& S, const float* in_rays, unsigned long long n, float* rays, CgrtHitDev* hits, float* normals,
                                      int* pixels, uint32_t* count, float* rgb, hipStream_t stream, unsigned long long* counters = nullptr);
 hipError_t launch_clear_owned(const FrameDev& F, float* rgb, hipStream_t stream);
+// Capped, count-driven forms (enqueued frames): dcount is required, n is the list's capacity, and the grid covers at
+// most strided_waves() waves (each list of a pair: that many) that stride over the entries present.  The kernel shape is chosen as for
+// the full grid (adapt_max on the device); a forced quad shape takes the full-capacity launch.  Results are the full grid's.
+unsigned strided_waves();
+hipError_t launch_trace_batch_strided(const SceneDev& S, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals, hipStream_t stream,
+                                      const uint32_t* dcount);
+hipError_t launch_trace_shadow_strided(const SceneDev& S, const float* rays, const float* dist, unsigned long long n, CgrtHitDev* hits, hipStream_t stream,
+                                       const uint32_t* dcount, unsigned dmul);
+hipError_t launch_trace_pair_strided(const SceneDev& S, const float* srays, const float* sdist, unsigned long long ns, CgrtHitDev* shits,
+                                     const uint32_t* sdcount, unsigned sdmul, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals,
+                                     const uint32_t* dcount, hipStream_t stream);
+// items: the first *dcount (<= nitems) entries of the level's list (k_soft_shadow_strided)
+hipError_t launch_soft_shadow_strided(const SceneDev& S, const SoftDev& Q, const float* rays, const CgrtHitDev* hits, const int* item_pixels,
+                                      unsigned long long nitems, const uint32_t* dcount, uint32_t* lit, int anyhit, hipStream_t stream);
 // shading wavefront (shade_kernels.hip); every level is a compact list of live paths
 // counters: 3 device words {shadow rays appended, mirror rays appended, hits}, zeroed by the caller
 // k_spawn: shadow rays of every hit -> the level's shadow list; mirror rays -> the next level's list; lvl[2i+1] = {ks, child}
@@ -105,6 +119,17 @@ hipError_t launch_fold(float* lvl, const float* child_lvl, unsigned long long n,
 // child_lvl (optional): level 0 is folded with level 1 on the fly (colour + childColour * ks, main.cpp:262) instead of by launch_fold
 hipError_t launch_write_rgb(const float* lvl0, const float* child_lvl, unsigned long long n, const int* item_pixels, float* rgb, hipStream_t s,
                             const uint32_t* dcount = nullptr);
+// the shading kernels' count-driven forms (enqueued frames): dcount required, n the capacity; a capped grid strides over *dcount entries
+hipError_t launch_spawn_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const int* pixels, unsigned long long n,
+                                const float* materials, const float* lights, unsigned nlights, int spawn, float* srays, float* sdist, int* sslot,
+                                float* lvl, float* next_rays, int* next_pixels, uint32_t* counters, hipStream_t s, const uint32_t* dcount);
+hipError_t launch_shade_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
+                                const int* sslot, unsigned long long n, const float* materials, const float* lights, unsigned nlights,
+                                const float* slights, unsigned nslights, const uint32_t* lit, unsigned samples, float* lvl, hipStream_t s,
+                                const uint32_t* dcount);
+hipError_t launch_fold_strided(float* lvl, const float* child_lvl, unsigned long long n, hipStream_t s, const uint32_t* dcount);
+hipError_t launch_write_rgb_strided(const float* lvl0, const float* child_lvl, unsigned long long n, const int* item_pixels, float* rgb, hipStream_t s,
+                                    const uint32_t* dcount);
 // the anti-aliased frame (main.cpp:663-687) from the 2W x 2H sub-sample frame `sub` of F: see k_resolve_aa (shade_kernels.hip).
 // out: F.nst_rank * 1024 * 3 floats (packed) or (F.W / 2) * (F.H / 2) * 3 floats
 hipError_t launch_resolve_aa(const FrameDev& F, const float* sub, float* out, int packed, hipStream_t s);

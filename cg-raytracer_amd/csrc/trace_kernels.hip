@@ -16,6 +16,9 @@
 #ifndef CGRT_LANE16_MAX_RAYS_DEFAULT
 #define CGRT_LANE16_MAX_RAYS_DEFAULT 131072ull  // ray lists of at most this many rays: 16 rays per wave (see "kernel shape per launch")
 #endif
+#ifndef CGRT_STRIDED_WAVES_DEFAULT
+#define CGRT_STRIDED_WAVES_DEFAULT 6144u  // waves per count-driven launch of an enqueued frame (strided_waves)
+#endif
 #ifndef CGRT_QUAD4_MAX_RAYS_DEFAULT
 #define CGRT_QUAD4_MAX_RAYS_DEFAULT 8192ull  // ... of at most this many: 4 rays per wave, 16 lanes per ray (walk_quad.h)
 #endif
@@ -291,8 +294,66 @@ struct ListPairDev {
     unsigned long long n_b;
     unsigned rpw_b, adapt_b, blocks_b;
 };
+// one workgroup's rays of the shadow list (a) / the mirror list (b) of k_trace_pair; bid = the workgroup's index within its list
 template <bool FAST>
+__device__ __forceinline__ void pair_a_wg(const SceneDev& S, const ListPairDev& P, unsigned long long n, unsigned rpw, unsigned long long bid,
+                                          uint32_t* s_lds) {
+    LaneCounters cnt;
+    const unsigned long long i = bid * rpw + threadIdx.x;
+    const bool active = i < n && threadIdx.x < rpw;
+    F3 o = f3(0, 0, 0), d = f3(0, 0, 0);
+    float t = 0.0f, qlen = 0.0f;
+    if (active) {
+        const float* r = P.rays_a + 7 * i;
+        o = f3(r[0], r[1], r[2]);
+        d = f3(r[3], r[4], r[5]);
+        t = r[6];
+        qlen = P.dist_a[i];
+    }
+    uint32_t hit_rec = REF_NONE;
+    walk_tree<false, FAST, WALK_OCCLUDED>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), CGRT_WAVE_MAP(s_lds), cnt, qlen);
+    if (active) finish_ray(S, o, d, t, hit_rec, P.hits_a + i, nullptr);
+}
+template <bool FAST>
+__device__ __forceinline__ void pair_b_wg(const SceneDev& S, const ListPairDev& P, unsigned long long n, unsigned rpw, unsigned long long bid,
+                                          uint32_t* s_lds) {
+    LaneCounters cnt;
+    const unsigned long long i = bid * rpw + threadIdx.x;
+    const bool active = i < n && threadIdx.x < rpw;
+    F3 o = f3(0, 0, 0), d = f3(0, 0, 0);
+    float t = 0.0f;
+    if (active) {
+        const float* r = P.rays_b + 7 * i;
+        o = f3(r[0], r[1], r[2]);
+        d = f3(r[3], r[4], r[5]);
+        t = r[6];
+    }
+    uint32_t hit_rec = REF_NONE;
+    walk_tree<false, FAST>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), CGRT_WAVE_MAP(s_lds), cnt);
+    if (active) finish_ray(S, o, d, t, hit_rec, P.hits_b + i, P.normals_b ? P.normals_b + 3 * i : nullptr);
+}
+// STRIDED (enqueued frames, capi.cpp enqueue_impl): the grid is capped (P.blocks_a / P.blocks_b workgroups per list, whatever the lists'
+// capacities) and each workgroup strides over the entries its list's device count holds, blocks_a (blocks_b) workgroups at a time.
+template <bool FAST, bool STRIDED = false>
 __global__ CGRT_LB void k_trace_pair(SceneDev S, ListPairDev P) {
+    if constexpr (STRIDED) {
+        extern __shared__ uint32_t s_lds[];
+        const unsigned b = blockIdx.x, both = P.blocks_a < P.blocks_b ? P.blocks_a : P.blocks_b;
+        const bool is_a = b < 2u * both ? (b & 1u) == 0u : P.blocks_a > P.blocks_b;
+        const unsigned bid = b < 2u * both ? (b >> 1) : b - both;  // the workgroup's first index within its list
+        // (as k_trace_batch's: the counts are read again for every pass, only the index lives across a walk)
+        for (unsigned k = bid;; k += is_a ? P.blocks_a : P.blocks_b) {
+            const uint32_t* dc = is_a ? P.dcount_a : P.dcount_b;
+            const unsigned long long cap = is_a ? P.n_a : P.n_b, adapt = is_a ? P.adapt_a : P.adapt_b;
+            const unsigned long long present = (unsigned long long)*(const volatile uint32_t*)dc * (is_a ? P.dmul_a : 1u), m = present < cap ? present : cap;
+            const unsigned rpw = adapt ? ((m <= adapt) ? 16u : 64u) : (is_a ? P.rpw_a : P.rpw_b);
+            if ((unsigned long long)k * rpw >= m) break;
+            if (is_a)
+                pair_a_wg<FAST>(S, P, m, rpw, k, s_lds);
+            else
+                pair_b_wg<FAST>(S, P, m, rpw, k, s_lds);
+        }
+    } else {
     extern __shared__ uint32_t s_lds[];
     const unsigned b = blockIdx.x, both = P.blocks_a < P.blocks_b ? P.blocks_a : P.blocks_b;
     const bool is_a = b < 2u * both ? (b & 1u) == 0u : P.blocks_a > P.blocks_b;
@@ -342,6 +403,7 @@ __global__ CGRT_LB void k_trace_pair(SceneDev S, ListPairDev P) {
         walk_tree<false, FAST>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), CGRT_WAVE_MAP(s_lds), cnt);
         if (active) finish_ray(S, o, d, t, hit_rec, P.hits_b + i, P.normals_b ? P.normals_b + 3 * i : nullptr);
     }
+    }
 }
 // rgb of every pixel this rank owns := 0 (main.cpp:293; the hits are written over it afterwards)
 __global__ __launch_bounds__(CGRT_BLOCK) void k_clear_owned(FrameDev F, float* __restrict__ rgb) {
@@ -351,11 +413,58 @@ __global__ __launch_bounds__(CGRT_BLOCK) void k_clear_owned(FrameDev F, float* _
     p[0] = p[1] = p[2] = 0.0f;
 }
 
-// dcount (optional): device word holding the number of rays actually present (<= n); the grid covers n.
-template <bool COUNT, bool FAST, bool QUAD = false>
+// one workgroup's rays of k_trace_batch (bid: its index in the launch's layout; qrpw as the kernel has chosen it), for the STRIDED form.
+// The one-pass instantiations keep their own copy of this body (calling this helper changed their VGPRs and scratch, measured with
+// tools/enqueue_resource_usage.py): the two copies must stay in step.  trace_shadow_wg and pair_a_wg / pair_b_wg likewise.
+template <bool COUNT, bool FAST, bool QUAD>
+__device__ __forceinline__ void trace_batch_wg(const SceneDev& S, const float* __restrict__ rays, unsigned long long n, CgrtHitDev* __restrict__ hits,
+                                               float* __restrict__ normals, unsigned long long* counters, unsigned qrpw, unsigned long long bid,
+                                               uint32_t* s_lds) {
+    const unsigned long long g = bid * blockDim.x + threadIdx.x;
+    const bool sparse = !QUAD && qrpw < 64u;
+    const unsigned long long i = QUAD ? (bid * qrpw + (threadIdx.x >> 2)) : (sparse ? bid * qrpw + threadIdx.x : g);
+    const bool writer = !QUAD || (threadIdx.x & 3u) == 0u;
+    const bool active = i < n && (!QUAD || (threadIdx.x >> 2) < qrpw) && (!sparse || threadIdx.x < qrpw);
+    LaneCounters cnt;
+    F3 o = f3(0, 0, 0), d = f3(0, 0, 0);
+    float t = 0.0f;
+    if (active) {
+        const float* r = rays + 7 * i;
+        o = f3(r[0], r[1], r[2]);
+        d = f3(r[3], r[4], r[5]);
+        t = r[6];
+    }
+    uint32_t hit_rec = REF_NONE;
+    if (QUAD)
+        walk_tree_quad<COUNT>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), cnt);
+    else
+        walk_tree<COUNT, FAST>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), CGRT_WAVE_MAP(s_lds), cnt);
+    if (active && writer) {
+        // (the ray's index is rebuilt rather than kept in two registers through the walk)
+        const unsigned long long k = QUAD ? (bid * qrpw + (threadIdx.x >> 2)) : (sparse ? bid * qrpw + threadIdx.x : bid * blockDim.x + threadIdx.x);
+        finish_ray(S, o, d, t, hit_rec, hits + k, normals ? normals + 3 * k : nullptr);
+    }
+    if (COUNT) flush_counters(cnt, active && writer, counters);
+}
+// dcount (optional): device word holding the number of rays actually present (<= n); the grid covers n.  The shapes: see the
+// comment in the body.
+// STRIDED (lane shapes, enqueued frames): the grid is capped instead (capi.cpp enqueue_impl) and each workgroup strides over the rays
+// present, gridDim.x workgroups at a time; the rays' layout on the lanes is the one a full grid gives them.
+template <bool COUNT, bool FAST, bool QUAD = false, bool STRIDED = false>
 __global__ CGRT_LB void k_trace_batch(SceneDev S, const float* __restrict__ rays, unsigned long long n,
                                                             CgrtHitDev* __restrict__ hits, float* __restrict__ normals,
                                                             unsigned long long* counters, const uint32_t* __restrict__ dcount, unsigned qrpw, unsigned adapt_max) {
+    static_assert(!(STRIDED && (QUAD || COUNT)), "strided launches are lane-shaped and uncounted");
+    if constexpr (STRIDED) {
+        extern __shared__ uint32_t s_lds[];
+        // (the count is read again for every pass and nothing but the workgroup index lives across a walk: the walk needs every register)
+        for (unsigned b = blockIdx.x;; b += gridDim.x) {
+            const unsigned long long present = *(const volatile uint32_t*)dcount, m = present < n ? present : n;
+            const unsigned rpw = adapt_max ? ((m <= adapt_max) ? 16u : 64u) : qrpw;
+            if ((unsigned long long)b * (rpw < 64u ? rpw : blockDim.x) >= m) break;
+            trace_batch_wg<false, FAST, false>(S, rays, m, hits, normals, counters, rpw, b, s_lds);
+        }
+    } else {
     extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
     if (dcount) {
         const unsigned long long present = *dcount;
@@ -393,16 +502,55 @@ __global__ CGRT_LB void k_trace_batch(SceneDev S, const float* __restrict__ rays
         finish_ray(S, o, d, t, hit_rec, hits + k, normals ? normals + 3 * k : nullptr);
     }
     if (COUNT) flush_counters(cnt, active && writer, counters);
+    }
 }
 
 // pointInShadow's rays (main.cpp:104-135) for the shading wavefront: dist[i] = |fromPosToLight| of ray i.  The caller only
 // evaluates `hit && !(t + epsilon >= dist)`: the certified walk answers that question directly (WALK_OCCLUDED: bounded by
 // the light's distance, stops at the first qualifying triangle); a ray without certificate gets the exact closest hit.
 // hits[i] therefore holds a hit that decides the test like the reference's own, not necessarily the closest one.
-template <bool COUNT, bool FAST, bool QUAD = false>
+template <bool COUNT, bool FAST, bool QUAD>
+__device__ __forceinline__ void trace_shadow_wg(const SceneDev& S, const float* __restrict__ rays, const float* __restrict__ dist, unsigned long long n,
+                                                CgrtHitDev* __restrict__ hits, unsigned long long* counters, unsigned qrpw, unsigned long long bid,
+                                                uint32_t* s_lds) {
+    const unsigned long long g = bid * blockDim.x + threadIdx.x;
+    const bool sparse = !QUAD && qrpw < 64u;
+    const unsigned long long i = QUAD ? (bid * qrpw + (threadIdx.x >> 2)) : (sparse ? bid * qrpw + threadIdx.x : g);
+    const bool writer = !QUAD || (threadIdx.x & 3u) == 0u;
+    const bool active = i < n && (!QUAD || (threadIdx.x >> 2) < qrpw) && (!sparse || threadIdx.x < qrpw);
+    LaneCounters cnt;
+    F3 o = f3(0, 0, 0), d = f3(0, 0, 0);
+    float t = 0.0f, qlen = 0.0f;
+    if (active) {
+        const float* r = rays + 7 * i;
+        o = f3(r[0], r[1], r[2]);
+        d = f3(r[3], r[4], r[5]);
+        t = r[6];
+        qlen = dist[i];
+    }
+    uint32_t hit_rec = REF_NONE;
+    if (QUAD)
+        walk_tree_quad<COUNT, WALK_OCCLUDED>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), cnt, qlen);
+    else
+        walk_tree<COUNT, FAST, WALK_OCCLUDED>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), CGRT_WAVE_MAP(s_lds), cnt, qlen);
+    if (active && writer) finish_ray(S, o, d, t, hit_rec, hits + i, nullptr);
+    if (COUNT) flush_counters(cnt, active && writer, counters);
+}
+// STRIDED: as k_trace_batch's.
+template <bool COUNT, bool FAST, bool QUAD = false, bool STRIDED = false>
 __global__ CGRT_LB void k_trace_shadow(SceneDev S, const float* __restrict__ rays, const float* __restrict__ dist, unsigned long long n,
                                        CgrtHitDev* __restrict__ hits, const uint32_t* __restrict__ dcount, unsigned long long* counters, unsigned qrpw, unsigned adapt_max,
                                        unsigned dmul) {
+    static_assert(!(STRIDED && (QUAD || COUNT)), "strided launches are lane-shaped and uncounted");
+    if constexpr (STRIDED) {
+        extern __shared__ uint32_t s_lds[];
+        for (unsigned b = blockIdx.x;; b += gridDim.x) {  // (as k_trace_batch's)
+            const unsigned long long present = (unsigned long long)*(const volatile uint32_t*)dcount * dmul, m = present < n ? present : n;
+            const unsigned rpw = adapt_max ? ((m <= adapt_max) ? 16u : 64u) : qrpw;
+            if ((unsigned long long)b * (rpw < 64u ? rpw : blockDim.x) >= m) break;
+            trace_shadow_wg<false, FAST, false>(S, rays, dist, m, hits, counters, rpw, b, s_lds);
+        }
+    } else {
     extern __shared__ uint32_t s_lds[];
     if (dcount) {  // dmul: *dcount counts the entries whose shadow rays these are, dmul rays (lights) each
         const unsigned long long present = (unsigned long long)*dcount * dmul;
@@ -431,6 +579,7 @@ __global__ CGRT_LB void k_trace_shadow(SceneDev S, const float* __restrict__ ray
         walk_tree<COUNT, FAST, WALK_OCCLUDED>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), CGRT_WAVE_MAP(s_lds), cnt, qlen);
     if (active && writer) finish_ray(S, o, d, t, hit_rec, hits + i, nullptr);
     if (COUNT) flush_counters(cnt, active && writer, counters);
+    }
 }
 
 // Visibility queries of a caller's (include/cgrt.h cgrt_occluded*, cgrt_in_shadow*): ONE answer byte per query, written by the lane (or
@@ -510,11 +659,11 @@ __global__ CGRT_LB void k_visibility(SceneDev S, const float* __restrict__ src, 
 // samples as pixel = item (hits and item_pixels are not read).
 // VIEWS: the items belong to a multi-view frame, whose pixels are view * W * H + (in-view pixel): samples are drawn with the in-view
 // pixel item_pixels[item] % Q.view_pixels, so that every view draws what its single-camera frame draws.
-template <bool ANYHIT, bool FAST, bool POINTS = false, bool VIEWS = false>
-__global__ CGRT_LB void k_soft_shadow(SceneDev S, SoftDev Q, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
-                                      const int* __restrict__ item_pixels, unsigned long long nthreads, uint32_t* __restrict__ lit) {
-    extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
-    const unsigned long long g = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+// thread g of k_soft_shadow's layout (every lane of the wave calls it: the counts are aggregated per wave)
+template <bool ANYHIT, bool FAST, bool POINTS, bool VIEWS>
+__device__ __forceinline__ void soft_shadow_thread(const SceneDev& S, const SoftDev& Q, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                   const int* __restrict__ item_pixels, unsigned long long g, unsigned long long nthreads,
+                                                   uint32_t* __restrict__ lit, uint32_t* s_lds) {
     const bool in = g < nthreads;
     const unsigned long long key = in ? g / Q.samples : 0ull;  // item * nlights + l
     const uint32_t smp = in ? (uint32_t)(g - key * Q.samples) : 0u;
@@ -564,6 +713,28 @@ __global__ CGRT_LB void k_soft_shadow(SceneDev S, SoftDev Q, const float* __rest
         const uint32_t c = (uint32_t)__popcll(__ballot(live && key == k0 && is_lit));
         if ((int)(threadIdx.x & 63) == first && c) atomicAdd(lit + k0, c);
         todo &= ~same;
+    }
+}
+template <bool ANYHIT, bool FAST, bool POINTS = false, bool VIEWS = false>
+__global__ CGRT_LB void k_soft_shadow(SceneDev S, SoftDev Q, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                      const int* __restrict__ item_pixels, unsigned long long nthreads, uint32_t* __restrict__ lit) {
+    extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
+    const unsigned long long g = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    soft_shadow_thread<ANYHIT, FAST, POINTS, VIEWS>(S, Q, rays, hits, item_pixels, g, nthreads, lit, s_lds);
+}
+// The count-driven form (enqueued frames): the level's items are the first *dcount (<= nitems, the list's capacity) entries, known only on
+// the device; a capped grid strides over their present x nlights x samples threads, gridDim.x * blockDim.x at a time.  Thread g draws
+// and counts what it draws in k_soft_shadow: the draws hash the pixel and the level, never the grid.
+template <bool ANYHIT, bool FAST, bool VIEWS>
+__global__ CGRT_LB void k_soft_shadow_strided(SceneDev S, SoftDev Q, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                              const int* __restrict__ item_pixels, unsigned long long nitems, const uint32_t* __restrict__ dcount,
+                                              uint32_t* __restrict__ lit) {
+    extern __shared__ uint32_t s_lds[];
+    for (unsigned b = blockIdx.x;; b += gridDim.x) {  // (as k_trace_batch's: only the index lives across a walk)
+        const unsigned long long present = *(const volatile uint32_t*)dcount;
+        const unsigned long long nthreads = (present < nitems ? present : nitems) * Q.nlights * Q.samples, base = (unsigned long long)b * blockDim.x;
+        if (base >= nthreads) break;
+        soft_shadow_thread<ANYHIT, FAST, false, VIEWS>(S, Q, rays, hits, item_pixels, base + threadIdx.x, nthreads, lit, s_lds);
     }
 }
 
@@ -768,6 +939,102 @@ hipError_t launch_trace_pair(const SceneDev& S, const float* srays, const float*
     P.rays_b = rays, P.hits_b = hits, P.normals_b = normals, P.dcount_b = dcount, P.n_b = n;
     lane_shape(n, expected, dcount, P.rpw_b, P.adapt_b, P.blocks_b);
     hipLaunchKernelGGL((k_trace_pair<true>), dim3(P.blocks_a + P.blocks_b), dim3(64), lds_bytes(64), stream, S, P);
+    return hipGetLastError();
+}
+// ---- capped, count-driven grids (enqueued frames: capi.cpp enqueue_impl) ----
+// Every list of an enqueued frame is sized for the worst case and only the device knows its length, so a launch covers at most
+// strided_waves() waves, whatever the capacity, and its workgroups stride over the entries present (the STRIDED instantiations).
+// The default is twice the walk waves the chip holds at once (256 CUs x 4 SIMDs x 3 waves); CGRT_STRIDED_WAVES overrides it.
+unsigned strided_waves() {
+    static const unsigned w = [] {
+        const unsigned long long e = env_ull("CGRT_STRIDED_WAVES");
+        return (e >= 64 && e <= (1ull << 24)) ? (unsigned)e : (unsigned)CGRT_STRIDED_WAVES_DEFAULT;
+    }();
+    return w;
+}
+static unsigned strided_blocks(unsigned full, unsigned block) {
+    const unsigned cap = std::max(1u, strided_waves() / (block / 64u));
+    return std::min(full, cap);
+}
+hipError_t launch_trace_batch_strided(const SceneDev& S, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals, hipStream_t stream,
+                                      const uint32_t* dcount) {
+    if (n == 0) return hipSuccess;
+    const unsigned block = (unsigned)trace_block(S);
+    const bool fast = S.fast_root != REF_NONE;
+    const unsigned adapt = list_adapt_max(S, dcount);
+    const int shape = adapt ? SHAPE_LANE64 : list_shape(S, n);
+    if (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4)  // (forced quad shapes, a checking tool: the full-capacity grid)
+        return launch_trace_batch(S, rays, n, hits, normals, nullptr, stream, dcount);
+    const unsigned rpw = shape == SHAPE_LANE16 ? 16u : 64u;
+    const unsigned grid = strided_blocks(lane_grid(n, block, rpw, adapt), block);
+    if (fast)
+        hipLaunchKernelGGL((k_trace_batch<false, true, false, true>), dim3(grid), dim3(block), lds_bytes(block), stream, S, rays, n, hits, normals, nullptr,
+                           dcount, rpw, adapt);
+    else
+        hipLaunchKernelGGL((k_trace_batch<false, false, false, true>), dim3(grid), dim3(block), lds_bytes(block), stream, S, rays, n, hits, normals, nullptr,
+                           dcount, rpw, adapt);
+    return hipGetLastError();
+}
+hipError_t launch_trace_shadow_strided(const SceneDev& S, const float* rays, const float* dist, unsigned long long n, CgrtHitDev* hits, hipStream_t stream,
+                                       const uint32_t* dcount, unsigned dmul) {
+    if (n == 0) return hipSuccess;
+    const unsigned block = (unsigned)trace_block(S);
+    const bool fast = S.fast_root != REF_NONE;
+    const unsigned adapt = list_adapt_max(S, dcount);
+    const int shape = adapt ? SHAPE_LANE64 : list_shape(S, n);
+    if (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4) return launch_trace_shadow(S, rays, dist, n, hits, stream, dcount, nullptr, 0, dmul);
+    const unsigned rpw = shape == SHAPE_LANE16 ? 16u : 64u;
+    const unsigned grid = strided_blocks(lane_grid(n, block, rpw, adapt), block);
+    if (fast)
+        hipLaunchKernelGGL((k_trace_shadow<false, true, false, true>), dim3(grid), dim3(block), lds_bytes(block), stream, S, rays, dist, n, hits, dcount,
+                           nullptr, rpw, adapt, dmul ? dmul : 1u);
+    else
+        hipLaunchKernelGGL((k_trace_shadow<false, false, false, true>), dim3(grid), dim3(block), lds_bytes(block), stream, S, rays, dist, n, hits, dcount,
+                           nullptr, rpw, adapt, dmul ? dmul : 1u);
+    return hipGetLastError();
+}
+hipError_t launch_trace_pair_strided(const SceneDev& S, const float* srays, const float* sdist, unsigned long long ns, CgrtHitDev* shits,
+                                     const uint32_t* sdcount, unsigned sdmul, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals,
+                                     const uint32_t* dcount, hipStream_t stream) {
+    if (ns == 0 || n == 0) return hipErrorInvalidValue;  // (the caller pairs two lists that both have a capacity)
+    auto lane_shape = [&](unsigned long long cap, const uint32_t* dc, unsigned& rpw, unsigned& adapt, unsigned& blocks) {
+        adapt = list_adapt_max(S, dc);
+        const int shape = adapt ? SHAPE_LANE64 : list_shape(S, cap);
+        rpw = (shape == SHAPE_LANE64) ? 64u : 16u;
+        blocks = strided_blocks(lane_grid(cap, 64u, rpw, adapt), 64u);  // (each list gets the cap: the two share the chip)
+        if (adapt) rpw = 64u;
+    };
+    ListPairDev P{};
+    P.rays_a = srays, P.dist_a = sdist, P.hits_a = shits, P.dcount_a = sdcount, P.n_a = ns, P.dmul_a = sdmul ? sdmul : 1u;
+    lane_shape(ns, sdcount, P.rpw_a, P.adapt_a, P.blocks_a);
+    P.rays_b = rays, P.hits_b = hits, P.normals_b = normals, P.dcount_b = dcount, P.n_b = n;
+    lane_shape(n, dcount, P.rpw_b, P.adapt_b, P.blocks_b);
+    hipLaunchKernelGGL((k_trace_pair<true, true>), dim3(P.blocks_a + P.blocks_b), dim3(64), lds_bytes(64), stream, S, P);
+    return hipGetLastError();
+}
+hipError_t launch_soft_shadow_strided(const SceneDev& S, const SoftDev& Q, const float* rays, const CgrtHitDev* hits, const int* item_pixels,
+                                      unsigned long long nitems, const uint32_t* dcount, uint32_t* lit, int anyhit, hipStream_t stream) {
+    const unsigned long long nthreads = nitems * Q.nlights * Q.samples;
+    if (nthreads == 0) return hipSuccess;
+    const unsigned block = (unsigned)trace_block(S);
+    const unsigned long long full = (nthreads + block - 1) / block;
+    const unsigned grid = strided_blocks((unsigned)std::min<unsigned long long>(full, 0x7fffffffull), block);
+    const bool fast = S.fast_root != REF_NONE, views = Q.view_pixels != 0;
+#define CGRT_SOFT_STRIDED(A, F, V)                                                                                                                 \
+    hipLaunchKernelGGL((k_soft_shadow_strided<A, F, V>), dim3(grid), dim3(block), lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nitems, \
+                       dcount, lit)
+    if (views) {
+        if (anyhit && fast) CGRT_SOFT_STRIDED(true, true, true);
+        else if (anyhit) CGRT_SOFT_STRIDED(true, false, true);
+        else if (fast) CGRT_SOFT_STRIDED(false, true, true);
+        else CGRT_SOFT_STRIDED(false, false, true);
+    } else {
+        if (anyhit && fast) CGRT_SOFT_STRIDED(true, true, false);
+        else if (anyhit) CGRT_SOFT_STRIDED(true, false, false);
+        else if (fast) CGRT_SOFT_STRIDED(false, true, false);
+        else CGRT_SOFT_STRIDED(false, false, false);
+    }
+#undef CGRT_SOFT_STRIDED
     return hipGetLastError();
 }
 hipError_t launch_trace_primary_compact(const SceneDev& S, const CameraDev& C, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals,

@@ -415,6 +415,39 @@ int cgrt_render_views_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t 
                              uint32_t nlights, const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream,
                              CgrtRenderStats* stats);
 
+/* Enqueued frames: the three device entries above without waiting for the GPU.  Each takes its blocking
+ * counterpart's arguments, with a ticket out-parameter (NULL allowed) in place of the stats, and writes exactly the bytes its counterpart
+ * writes for the same arguments (every format, row pitch, aa, rank / nranks, soft-shadow setting and max_level 0..16); bytes outside the
+ * output, and pixels of other ranks, are never written.  Arguments are checked in the counterpart's order with its error codes, before
+ * anything is enqueued; a host-only scene is CGRT_E_NO_DEVICE.
+ * Stream order: the whole frame, export included, runs on `stream` (NULL = default stream), after everything enqueued there before the call
+ * (for ray lists: the kernel that wrote the rays); work enqueued there afterwards sees the finished output.  The library's own streams are
+ * not used.  The lights, camera(s) and soft-shadow tables are copied at the call (through pinned memory, hipMemcpyAsync on `stream`): the
+ * caller may reuse every host array as soon as the call returns.  Device buffers (d_out, d_rays, d_rgb) must stay valid until the frame
+ * has run on `stream`.
+ * The call returns without waiting for the GPU, except (1) when the scene's workspace has to grow -- the first frame of a larger shape, more
+ * lights or a deeper level: it then waits for the scene's outstanding frames -- and (2) when all 8 of the scene's ticket slots are in
+ * flight: it then waits for the oldest one.
+ * Frames of one scene, enqueued and blocking, on any streams and in any order, each get their own bytes: every frame starts on the device
+ * behind the scene's last enqueued frame and behind the export of its last blocking one.  cgrt_scene_destroy waits for every outstanding
+ * frame.  Enqueued frames neither read nor write the scene's frame prediction record or its frame hints: a blocking frame takes the path
+ * (cgrt_debug_render_path) and writes the bytes it would without them.
+ * Ticket: the scene's frame sequence number of the enqueued frame (frames are numbered from 1, blocking ones included).  cgrt_enqueue_stats
+ * waits for that frame and returns its CgrtRenderStats: ray counts and levels equal to the blocking call's, device_ms from events around
+ * the frame on its stream.  A ticket that was never issued, or is older than the scene's last 8 enqueued frames, is CGRT_E_ARG. */
+int cgrt_enqueue_render_device(CgrtScene* scene, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights,
+                               const CgrtSoftShadows* soft, int max_level, int aa, int rank, int nranks, void* d_out, int format,
+                               uint64_t row_bytes, void* stream, uint64_t* ticket);
+int cgrt_enqueue_render_views_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights,
+                                     uint32_t nlights, const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream,
+                                     uint64_t* ticket);
+int cgrt_enqueue_shade_rays_device(CgrtScene* scene, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights,
+                                   const CgrtSoftShadows* soft, int max_level, float* d_rgb, void* stream, uint64_t* ticket);
+int cgrt_enqueue_stats(CgrtScene* scene, uint64_t ticket, CgrtRenderStats* stats);
+/* Diagnostic: the cap, in waves, of every count-driven launch of an enqueued frame (each list of a paired launch gets it): 6144, or the
+ * value of CGRT_STRIDED_WAVES (64 .. 2^24), read once per process. */
+int cgrt_debug_strided_waves(void);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
