@@ -18,6 +18,11 @@ Other workloads: --workload shaded (cgrt_render: primary + shadow + mirror rays,
 --tris 87000 (the report's dragon size), --obj PATH (a user-supplied mesh, e.g. the real dragon.obj).
 --dump-outputs DIR writes what the last timed step computed (rank 0's hit records, or the shaded frame's RGB) as .npy files;
 the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, dump if asked, print the line.  --full adds
+everything that is measured or checked beside it, after the timed region: the instrumented counting launch and the roofline
+block, the gather timing, the single-GPU base of a strong-scaling curve, the shaded frame drawn exactly sized, the secondary
+lines at N = 1 (`extras`, skipped by --no-extras) and the CPU oracle baseline (`cpu_baseline`, skipped by --no-cpu-baseline).
 """
 from __future__ import annotations
 
@@ -188,8 +193,12 @@ def main():
                     help="primary = fused ray generation + intersect (the headline); shaded = cgrt_render, depth 2, all rays of the frame")
     ap.add_argument("--walk", choices=["auto", "exact", "certified"], default="auto",
                     help="auto = the scene's default (certified when it carries a fast tree), exact = the reference's steps only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary lines (config-5 frame on one GPU, 87 K dragon) at N = 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: counters + roofline, gather, strong-scaling base, "
+                         "exactly sized shaded frame, secondary lines at N = 1 and the CPU baseline (off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the secondary lines (config-5 frame on one GPU, 87 K dragon) at N = 1")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--frames-in-flight", type=int, default=1,
                     help="independent frames kept in flight on separate HIP streams (1 = strictly back to back, the reported default)")
@@ -307,16 +316,18 @@ def main():
         step, extra_streams, bufs = primary_runner(scene, cam, W, H, rank, world, nfl)
         wall, kern_ms = timed(step, args.steps, args.warmup, extra_streams)
         my_rays = tiling.owned_pixels(W, H, rank, world)
-        cnt = scene.count_primary(cam, W, H, rank=rank, nranks=world)  # instrumented launch, outside the timed region
-        assert cnt["rays"] == my_rays, (cnt, my_rays)
-        alg_bytes = algorithmic_bytes(cnt, rs)
-        # the gather of SURVEY.md section 8(e): this rank's hits device -> pinned host, one async copy, timed on its own
-        host = torch.empty(W * H * 4, dtype=torch.int32).pin_memory()
-        torch.cuda.synchronize()
-        g0 = time.perf_counter()
-        host.copy_(bufs[0], non_blocking=True)
-        torch.cuda.synchronize()
-        gather_ms = (time.perf_counter() - g0) * 1e3
+        gather_ms = 0.0
+        if args.full:
+            cnt = scene.count_primary(cam, W, H, rank=rank, nranks=world)  # instrumented launch, outside the timed region
+            assert cnt["rays"] == my_rays, (cnt, my_rays)
+            alg_bytes = algorithmic_bytes(cnt, rs)
+            # the gather of SURVEY.md section 8(e): this rank's hits device -> pinned host, one async copy, timed on its own
+            host = torch.empty(W * H * 4, dtype=torch.int32).pin_memory()
+            torch.cuda.synchronize()
+            g0 = time.perf_counter()
+            host.copy_(bufs[0], non_blocking=True)
+            torch.cuda.synchronize()
+            gather_ms = (time.perf_counter() - g0) * 1e3
         if args.dump_outputs and rank == 0:
             # the CgrtHit frame of the last timed step (warm-up and timed steps share the frames in flight round robin), the
             # pixels this rank traced; the ids as float64, which holds every uint32 / int32 exactly
@@ -337,7 +348,7 @@ def main():
         wall_max, gather_max = float(walls[0].item()), float(walls[1].item())
         total_rays = W * H
         n1_same = None
-        if world > 1 and rank == 0 and scaling != "weak":
+        if args.full and world > 1 and rank == 0 and scaling != "weak":
             # the base of the strong-scaling curve, measured by rank 0 alone on the whole frame after the timed region
             s1, _, _ = primary_runner(scene, cam, W, H, 0, 1)
             for _ in range(3):
@@ -350,10 +361,6 @@ def main():
             n1_same = total_rays / ((time.perf_counter() - t1) / 10) / 1e6
         if rank == 0:
             ms_per_step = wall_max / args.steps * 1e3
-            achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-            traffic, measured, traffic_src = read_profile(f"dragon{sd.ntris}_{W}x{H}_{'certified' if scene.walk() else 'exact'}", pkg.source_hash())
-            phys_frac = round(traffic / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None
-            tree = max(1, cnt["tree_rays"])
             out = {
                 "metric": (f"primary Mrays/sec (BVH traversal + ray-triangle, {'user OBJ' if args.obj else 'dragon stand-in'} @{W}x{H}"
                            + (f", one frame split over {world} GPUs, strong scaling" if world > 1 and scaling == "strong" else
@@ -372,18 +379,27 @@ def main():
                     "workload": f"{scene_name}, {W}x{H} primary rays, reference default camera, 64x64-pixel super-tiles dealt i % {world} to "
                                 f"{world} rank(s), {walk} walk",
                     "rays_per_step": total_rays,
-                    "rays_entering_tree_rank0": cnt["tree_rays"],
-                    "Mrays_per_s_over_rays_entering_tree_rank0": round(cnt["tree_rays"] / (kern_ms * 1e-3) / 1e6, 1),
                     "frames_in_flight": nfl,
                     "frame_hints": frame_hint_note(args.frame_hints, per_rank[0] if isinstance(per_rank, (list, tuple)) else per_rank, world),
                     "rays_per_rank": per_rank,
-                    "gather_ms_max_over_ranks": round(gather_max, 3),
-                    "gather": "this rank's CgrtHit frame device -> pinned host, one async copy (not part of value)",
                     "bvh_build_and_upload_s": round(setup_s, 3),
                     "scene_device_MB": round(scene.device_bytes() / 1e6, 1),
-                    "timing": "value and ms_per_step: wall clock between barriers (max over ranks) / steps; roofline.kernel_ms: HIP events on the launch stream (rank 0)",
+                    "timing": "value and ms_per_step: wall clock between barriers (max over ranks) / steps",
                 },
-                "roofline": {
+            }
+            if args.full:
+                achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+                traffic, measured, traffic_src = read_profile(f"dragon{sd.ntris}_{W}x{H}_{'certified' if scene.walk() else 'exact'}", pkg.source_hash())
+                phys_frac = round(traffic / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None
+                tree = max(1, cnt["tree_rays"])
+                out["config"].update({
+                    "rays_entering_tree_rank0": cnt["tree_rays"],
+                    "Mrays_per_s_over_rays_entering_tree_rank0": round(cnt["tree_rays"] / (kern_ms * 1e-3) / 1e6, 1),
+                    "gather_ms_max_over_ranks": round(gather_max, 3),
+                    "gather": "this rank's CgrtHit frame device -> pinned host, one async copy (not part of value)",
+                })
+                out["config"]["timing"] += "; roofline.kernel_ms: HIP events on the launch stream (rank 0)"
+                out["roofline"] = {
                     "bound": bound_from(measured, phys_frac),
                     "bound_note": "SURVEY.md 8(d) classifies the path as HBM-bound and defines frac = algorithmic bytes (every record visit + the result "
                                   "store) / kernel time / 8 TB/s; the records are re-read through L1/L2/Infinity Cache, physical HBM traffic is a few % of "
@@ -407,8 +423,7 @@ def main():
                     "per_ray": {k: round(cnt[k] / max(1, cnt["rays"]), 3) for k in ("inner_visits", "leaf_visits", "tri_tests", "sub_visits", "cert_boxes")},
                     "per_ray_entering_tree": {k: round(cnt[k] / tree, 2) for k in ("inner_visits", "tri_tests", "sub_visits", "cert_boxes")},
                     "fallback_rays": cnt["fallback_rays"],
-                },
-            }
+                }
             if world > 1:
                 out["scaling"] = scaling
                 if n1_same is not None:
@@ -431,14 +446,6 @@ def main():
                          whole={"rays": np.float64([st["primary_rays"], st["shadow_rays"], st["reflection_rays"]])})
         rays = best["primary_rays"] + best["shadow_rays"] + best["reflection_rays"]
         path = scene.last_render_path()
-        # the same frame drawn the exact way (what a first frame, a resized frame or a frame after a camera jump costs): after the timed region
-        pkg.set_render_prediction(False)
-        exact_ms = min(scene.render(cam, W, H, max_level=2)[1]["device_ms"] for _ in range(max(3, args.steps // 4)))
-        pkg.set_render_prediction(True)
-        _, _, work = scene.render_counted(cam, W, H, max_level=2)  # instrumented frame, outside the timed region
-        parts = {k: algorithmic_bytes(v, rs) for k, v in work.items()}
-        alg_bytes = sum(parts.values())
-        achieved = alg_bytes / (best["device_ms"] * 1e-3) / 1e9
         out = {
             "metric": f"rays/sec of the whole shaded frame (primary + shadow + mirror, depth 2, {scene_name} @{W}x{H})",
             "value": round(rays / (best["device_ms"] * 1e-3) / 1e6, 3),
@@ -459,9 +466,19 @@ def main():
                        "frame_path": {0: "exactly sized (the host waits for the device's hit count inside the frame)",
                                       1: "predicted: every launch issued at once, sized from the previous frame of the same shape, counts checked behind the frame "
                                          "(cgrt_set_render_prediction; same pixels, tests/test_render_prediction_gpu.py)",
-                                      2: "predicted, outgrown, drawn again exactly"}.get(path, str(path)),
-                       "exactly_sized_frame_ms": round(exact_ms, 4)},
-            "roofline": {
+                                      2: "predicted, outgrown, drawn again exactly"}.get(path, str(path))},
+        }
+        if args.full:
+            # the same frame drawn the exact way (what a first frame, a resized frame or a frame after a camera jump costs): after the timed region
+            pkg.set_render_prediction(False)
+            exact_ms = min(scene.render(cam, W, H, max_level=2)[1]["device_ms"] for _ in range(max(3, args.steps // 4)))
+            pkg.set_render_prediction(True)
+            _, _, work = scene.render_counted(cam, W, H, max_level=2)  # instrumented frame, outside the timed region
+            parts = {k: algorithmic_bytes(v, rs) for k, v in work.items()}
+            alg_bytes = sum(parts.values())
+            achieved = alg_bytes / (best["device_ms"] * 1e-3) / 1e9
+            out["config"]["exactly_sized_frame_ms"] = round(exact_ms, 4)
+            out["roofline"] = {
                 "bound": "hbm",
                 "bound_note": "classification of SURVEY.md 8(d); like the primary kernel these batches are latency-bound (their time is the time of their hardest rays), see profiles/",
                 "achieved": round(achieved, 2),
@@ -477,10 +494,9 @@ def main():
                                           for kind, v in work.items()},
                 "rays_entering_tree": {kind: v["tree_rays"] for kind, v in work.items()},
                 "fallback_rays": {kind: v["fallback_rays"] for kind, v in work.items()},
-            },
-        }
+            }
     if rank == 0 and out is not None:
-        if world == 1 and args.workload == "primary" and not args.no_extras and scaling == "headline" and not args.obj and args.standin == "regular" and not (args.width and args.height):
+        if args.full and world == 1 and args.workload == "primary" and not args.no_extras and scaling == "headline" and not args.obj and args.standin == "regular" and not (args.width and args.height):
             # secondary lines of SURVEY.md section 8(d): the config-5 frame on this one GPU (base of the strong-scaling curve)
             # and the report's 87 K-triangle dragon beside the 800 K one
             extras = {}
@@ -543,7 +559,7 @@ def main():
                            "was long in the previous frame are traced as four 16-ray waves (DESIGN.md 5.8, profiles/r3_frame_hints.txt)")
             extras["latency_regime"] = lat
             out["extras"] = extras
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # N > 1: rank 0 alone, after the timed region's closing barrier (the other ranks wait at the final barrier below), so that
             # every line of the 1/2/4/8 run carries the CPU reference "in the same run" (BASELINE.json north_star)
             out["cpu_baseline"] = cpu_baseline(sd, cam, W, H, args.cpu_budget)

@@ -121,3 +121,13 @@ def test_bench_cli_documents_the_scaling_modes():
     assert out.returncode == 0
     for flag in ("--gpus", "--steps", "--warmup", "--scaling", "--workload", "--obj", "--tris", "--walk"):
         assert flag in out.stdout
+
+
+def test_bench_cli_offers_full():
+    """A plain bench run measures the headline only; --full brings back the side measurements (no GPU needed for --help)."""
+    import subprocess
+
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0
+    for flag in ("--full", "--no-extras", "--no-cpu-baseline", "--dump-outputs"):
+        assert flag in out.stdout

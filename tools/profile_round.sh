@@ -6,8 +6,8 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/profile_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $out/bench_under_trace.json 2> $out/trace.err || exit 1
-pass() { n=$1; shift; rocprofv3 --pmc "$@" --output-format csv -d $out/$n -o p -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras > /dev/null 2> $out/$n.err || exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 $R/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $out/bench_under_trace.json 2> $out/trace.err || exit 1
+pass() { n=$1; shift; timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d $out/$n -o p -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras > /dev/null 2> $out/$n.err || exit 1; }
 pass fetch FETCH_SIZE
 pass write WRITE_SIZE
 pass cache TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum
