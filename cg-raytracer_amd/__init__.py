@@ -68,6 +68,11 @@ class SoftShadows(C.Structure):
                 ("nunits", C.c_uint32), ("seed", C.c_uint32), ("closest_hit", C.c_int32)]
 
 
+class LightSets(C.Structure):  # CgrtLightSets: CSR arrays, one offset array per light kind
+    _fields_ = [("nsets", C.c_uint32), ("lights", C.c_void_p), ("light_offsets", C.c_void_p), ("spherical", C.c_void_p),
+                ("spherical_offsets", C.c_void_p)]
+
+
 class Camera(C.Structure):
     _fields_ = [
         ("look_at", C.c_float * 3),
@@ -108,7 +113,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -183,6 +188,9 @@ def lib() -> C.CDLL:
     L.cgrt_trace_primary_views_device.argtypes = [vp, vp, u32, i32, i32, vp, vp, vp]
     L.cgrt_render_views.argtypes = [vp, vp, u32, i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
     L.cgrt_render_views_device.argtypes = [vp, vp, u32, i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, i32, vp, C.POINTER(RenderStats)]
+    L.cgrt_render_light_sets.argtypes = [vp, C.POINTER(Camera), i32, i32, C.POINTER(LightSets), C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
+    L.cgrt_render_light_sets_device.argtypes = [vp, C.POINTER(Camera), i32, i32, C.POINTER(LightSets), C.POINTER(SoftShadows), i32, vp, i32, vp,
+                                                C.POINTER(RenderStats)]
     L.cgrt_enqueue_render_device.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, i32, i32, i32, vp, i32, u64,
                                              vp, C.POINTER(u64)]
     L.cgrt_enqueue_render_views_device.argtypes = [vp, vp, u32, i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, i32, vp, C.POINTER(u64)]
@@ -741,11 +749,16 @@ class Scene:
 
     def _views_tensor(self, cams, W, H, format, out, stream):
         """render_views_tensor's checks of `out` (ValueError) and its new tensor: (camera array, out, format code, stream)."""
+        a = camera_array(cams)
+        out, fmt, stream = self._batch_tensor(len(a), W, H, format, out, stream)
+        return a, out, fmt, stream
+
+    def _batch_tensor(self, B, W, H, format, out, stream):
+        """The checks of `out` (ValueError) for a batch of B frames exported back to back (views, light sets), and its new tensor:
+        (out, format code, stream)."""
         import torch
 
-        a = camera_array(cams)
         fmt = _frame_format(format)
-        B = len(a)
         shape, dtype = {0: ((B, H, W, 3), torch.float32), 1: ((B, 3, H, W), torch.float32), 2: ((B, H, W, 4), torch.uint8)}.get(fmt, (None, None))
         if shape is None:
             raise ValueError(f"format must be one of {sorted(FRAME_FORMATS)}, not {format!r}")
@@ -766,9 +779,89 @@ class Scene:
         stream = torch.cuda.current_stream(dev) if stream is None else stream
         _check_one_hip_runtime()
         if out is None:
-            with torch.cuda.stream(stream):  # (allocated on the stream the views are exported on)
+            with torch.cuda.stream(stream):  # (allocated on the stream the frames are exported on)
                 out = torch.empty(shape, dtype=dtype, device=dev)
-        return a, out, fmt, stream
+        return out, fmt, stream
+
+    # ---- light sets (include/cgrt.h cgrt_render_light_sets*) ----
+    @staticmethod
+    def _light_sets_arg(light_sets, spherical_sets):
+        """The CgrtLightSets argument built from B arrays of point lights (L_b x 6) and None or B arrays of spherical lights (S_b x 7), and the
+        CSR arrays it points into, which the caller keeps alive.  ValueError for sequences of different lengths or bad shapes."""
+
+        def csr(seq, width, what):
+            arrs = []
+            for b, x in enumerate(seq):
+                a = np.asarray(x, np.float32)
+                if a.size == 0:
+                    a = a.reshape(0, width)
+                if a.ndim != 2 or a.shape[1] != width:
+                    raise ValueError(f"{what}[{b}] has shape {a.shape}, expected (n, {width})")
+                arrs.append(a)
+            offsets = np.zeros(len(arrs) + 1, np.uint32)
+            if arrs:
+                offsets[1:] = np.cumsum([len(a) for a in arrs])
+            flat = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros((0, width), np.float32), np.float32)
+            return flat, offsets
+
+        light_sets = list(light_sets)
+        lights, loff = csr(light_sets, 6, "light_sets")
+        sph, soff = None, None
+        if spherical_sets is not None:
+            spherical_sets = list(spherical_sets)
+            if len(spherical_sets) != len(light_sets):
+                raise ValueError(f"{len(light_sets)} light sets but {len(spherical_sets)} spherical sets")
+            sph, soff = csr(spherical_sets, 7, "spherical_sets")
+        q = LightSets(len(light_sets), lights.ctypes.data if len(lights) else None, loff.ctypes.data,
+                      sph.ctypes.data if sph is not None and len(sph) else None, soff.ctypes.data if soff is not None else None)
+        return q, (lights, loff, sph, soff)
+
+    def _light_sets_soft(self, spherical_sets, units, samples: int, seed: int):
+        """The sampling parameters of a light-set batch (CgrtSoftShadows without lights; None when no set has spherical lights)."""
+        if spherical_sets is None or units is None:
+            return None, ()
+        units = _f32(units, (-1, 3))
+        return C.byref(SoftShadows(None, units.ctypes.data, 0, samples, len(units), seed, 0)), (units,)
+
+    def render_light_sets(self, cam, W: int, H: int, light_sets, spherical_sets=None, units=None, samples: int = 200, seed: int = 0,
+                          max_level: int = 2):
+        """cgrt_render_light_sets: frame b of the result is render_soft (render without spherical lights) of cam under light_sets[b] (and
+        spherical_sets[b]), bit for bit; the batch traces the ray tree once and every distinct light position once.  light_sets: B arrays
+        (L_b, 6); spherical_sets: None or B arrays (S_b, 7).  Returns (rgb[B, W*H, 3], stats dict of the batch)."""
+        q, keep = self._light_sets_arg(light_sets, spherical_sets)  # noqa: F841
+        s, keep_s = self._light_sets_soft(spherical_sets, units, samples, seed)  # noqa: F841
+        rgb = np.zeros((q.nsets, W * H, 3), np.float32)
+        st = RenderStats()
+        c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
+        _check(lib().cgrt_render_light_sets(self._h, C.byref(c), W, H, C.byref(q), s, max_level, _ptr(rgb), C.byref(st)))
+        return rgb, {k: getattr(st, k) for k, _ in st._fields_}
+
+    def render_light_sets_device(self, cam, W: int, H: int, d_out_ptr: int, light_sets, spherical_sets=None, units=None, samples: int = 200,
+                                 seed: int = 0, max_level: int = 2, format="rgb", stream: int = 0) -> dict:
+        """cgrt_render_light_sets_device: the sets' frames exported into device memory at d_out_ptr, set b at b * (packed frame bytes), each
+        in the packed layout of render_device's `format`; enqueued on the hipStream_t `stream`.  Raw integers, as render_device.  Returns
+        the stats dict."""
+        q, keep = self._light_sets_arg(light_sets, spherical_sets)  # noqa: F841
+        s, keep_s = self._light_sets_soft(spherical_sets, units, samples, seed)  # noqa: F841
+        st = RenderStats()
+        c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
+        _check(
+            lib().cgrt_render_light_sets_device(
+                self._h, C.byref(c), W, H, C.byref(q), s, max_level, C.c_void_p(d_out_ptr) if d_out_ptr else None, _frame_format(format),
+                C.c_void_p(stream) if stream else None, C.byref(st),
+            )
+        )  # fmt: skip
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def render_light_sets_tensor(self, cam, W: int, H: int, light_sets, format="rgb", out=None, stream=None, **kw):
+        """render_light_sets_device into a torch tensor on cuda:<device>: (B, H, W, 3) f32, (B, 3, H, W) f32 or (B, H, W, 4) u8 -- `out`
+        (contiguous, of exactly that shape and dtype; validated before any call, ValueError) or a new tensor, rendered on `stream`
+        (default: torch.cuda.current_stream()).  Other keywords as render_light_sets.  Returns (tensor, stats dict)."""
+        light_sets = list(light_sets)
+        self._light_sets_arg(light_sets, kw.get("spherical_sets"))  # (ValueError before anything is allocated)
+        out, fmt, stream = self._batch_tensor(len(light_sets), W, H, format, out, stream)
+        st = self.render_light_sets_device(cam, W, H, out.data_ptr(), light_sets, format=fmt, stream=stream.cuda_stream, **kw)
+        return out, st
 
     def _soft_arg(self, spherical, units, samples: int, seed: int):
         """The CgrtSoftShadows argument (None without spherical lights) and the arrays it points into, which the caller keeps alive."""

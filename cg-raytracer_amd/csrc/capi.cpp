@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <linux/futex.h>
+#include <map>
 #include <sched.h>
 #include <sys/syscall.h>
 #include <unistd.h>
@@ -295,7 +297,7 @@ struct CgrtScene {
     struct WorkSlot {
         void* p = nullptr;
         size_t cap = 0;
-    } work[32];  // slots 0..31 are in use (render_impl)
+    } work[34];  // slots 0..33 are in use (render_impl; 32 and 33 by light-set batches only)
     // pinned host staging of cgrt_render*'s frame (grown on demand, guarded by render_mutex): the device frame comes down with ONE
     // asynchronous copy at PCIe speed; cgrt_render_mapped hands this memory to the caller instead of copying it once more
     void* pin_frame = nullptr;
@@ -1935,6 +1937,70 @@ struct ViewSrc {
     const CgrtCamera* cams;
     uint32_t n;
 };
+// One camera under nsets light sets instead of one light list (cgrt_render_light_sets*): the batch's plan, built on
+// the host from the caller's CSR arrays (plan_light_sets).  A pixel's ray tree does not depend on the lights, so level 0, every level's
+// spawn and every mirror list run once.  A point light's shadow ray depends on its position alone, so each level's shadow list holds one ray
+// per hit and DISTINCT position, compared by bit pattern: `points` is k_spawn's light list.  A spherical light's sample count depends on
+// its position, its radius and its index within its set (the draws' `l`): the soft-shadow keys are the distinct (position, radius, index)
+// triples, `spherical`, drawn as light `sph_index`.  `table` is SetsDev's memory: point_off[nsets + 1] | sph_off[nsets + 1] |
+// sph_index[nsph] | (to 16 B) | every point light, then every spherical light, as {position, slot}, {colour, 0}.  Set b's frame is pixels
+// b * W * H .. of the frame buffer.  Whole frames, one rank, no aa; like views, the batch always takes the exactly sized path and neither
+// reads nor writes the scene's prediction record or its frame hints.
+struct LightSetSrc {
+    uint32_t nsets = 0;
+    std::vector<float> points;        // npos x 6 {position, 0}
+    std::vector<float> spherical;     // nsph x 7 {position, radius, 0}
+    std::vector<uint32_t> sph_index;  // nsph: the in-set index each key draws with
+    std::vector<uint32_t> table;
+    size_t point_at = 0, sph_at = 0;  // words of `table` before the point / spherical light records
+};
+// The plan of a checked CgrtLightSets (light_sets_args): distinct slots in order of first appearance, set after set.
+static void plan_light_sets(const CgrtLightSets& L, LightSetSrc& P) {
+    const uint32_t B = L.nsets, np = L.light_offsets[B], ns = L.spherical_offsets ? L.spherical_offsets[B] : 0u;
+    P.nsets = B;
+    const size_t head = 2 * ((size_t)B + 1) + ns;
+    P.point_at = (head + 3) & ~(size_t)3;
+    P.sph_at = P.point_at + 8 * (size_t)np;
+    P.table.assign(P.sph_at + 8 * (size_t)ns, 0u);
+    for (uint32_t b = 0; b <= B; b++) {
+        P.table[b] = L.light_offsets[b];
+        P.table[B + 1 + b] = L.spherical_offsets ? L.spherical_offsets[b] : 0u;
+    }
+    std::map<std::array<uint32_t, 3>, uint32_t> pos;  // position bits -> distinct slot
+    for (uint32_t k = 0; k < np; k++) {
+        const float* l = L.lights + 6 * (size_t)k;
+        std::array<uint32_t, 3> key;
+        std::memcpy(key.data(), l, 12);
+        const auto r = pos.emplace(key, (uint32_t)(P.points.size() / 6));
+        if (r.second) {
+            P.points.resize(P.points.size() + 6, 0.0f);
+            std::memcpy(P.points.data() + P.points.size() - 6, l, 12);
+        }
+        uint32_t* rec = P.table.data() + P.point_at + 8 * (size_t)k;
+        std::memcpy(rec, l, 12);
+        rec[3] = r.first->second;
+        std::memcpy(rec + 4, l + 3, 12);
+    }
+    std::map<std::array<uint32_t, 5>, uint32_t> sph;  // (position, radius) bits and in-set index -> distinct key
+    for (uint32_t b = 0; b < B && ns; b++)
+        for (uint32_t k = L.spherical_offsets[b]; k < L.spherical_offsets[b + 1]; k++) {
+            const float* l = L.spherical + 7 * (size_t)k;
+            std::array<uint32_t, 5> key;
+            std::memcpy(key.data(), l, 16);
+            key[4] = k - L.spherical_offsets[b];
+            const auto r = sph.emplace(key, (uint32_t)P.sph_index.size());
+            if (r.second) {
+                P.sph_index.push_back(key[4]);
+                P.spherical.resize(P.spherical.size() + 7, 0.0f);
+                std::memcpy(P.spherical.data() + P.spherical.size() - 7, l, 16);
+            }
+            uint32_t* rec = P.table.data() + P.sph_at + 8 * (size_t)k;
+            std::memcpy(rec, l, 12);
+            rec[3] = r.first->second;
+            std::memcpy(rec + 4, l + 4, 12);
+        }
+    std::copy(P.sph_index.begin(), P.sph_index.end(), P.table.begin() + 2 * ((size_t)B + 1));
+}
 // k_export_frame's description of a frame F (its PW x PH pixels in `src`) for the caller's buffer (render_impl, enqueue_impl)
 static ExportDev export_of(const FrameDev& F, const float* src, const DeviceOut& dout, int PW, int PH, uint32_t nviews, bool aa, int rank, int nranks,
                            int packed) {
@@ -1961,12 +2027,13 @@ static ExportDev export_of(const FrameDev& F, const float* src, const DeviceOut&
 static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats, CgrtCounters* counted = nullptr,
                        const float** mapped = nullptr, bool aa = false, const DeviceOut* dout = nullptr, const ListSrc* list = nullptr,
-                       const ViewSrc* views = nullptr) {
+                       const ViewSrc* views = nullptr, const LightSetSrc* sets = nullptr) {
     if (!s || (!cam && !list && !views) || (!rgb && !mapped && !dout && !list) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);
     if (W <= 0 || H <= 0 || max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad frame size or recursion depth");
-    const unsigned SL = soft ? soft->nspherical : 0;
-    if (SL) {
+    // (light sets: the batch's distinct spherical keys, with the caller's sampling parameters; light_sets_args has checked them)
+    const unsigned SL = sets ? (unsigned)sets->sph_index.size() : soft ? soft->nspherical : 0;
+    if (SL && !sets) {
         if (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24))
             return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
         if ((unsigned long long)W * H > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large");
@@ -1979,7 +2046,8 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> one_frame(s->render_mutex);  // the workspace below belongs to one frame at a time
     const uint32_t nviews = views ? views->n : 1u;
-    const unsigned long long npix = list ? list->n : (unsigned long long)W * H * nviews;
+    const uint32_t nsets = sets ? sets->nsets : 1u;  // (the frame buffer holds the sets' frames back to back)
+    const unsigned long long npix = list ? list->n : (unsigned long long)W * H * nviews * nsets;
     const unsigned L = nlights;
     CgrtRenderStats st{};
     FrameDev F{};
@@ -2000,7 +2068,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     WsBuf rays[3] = {{s, 0}, {s, 1}, {s, 21}}, hits[3] = {{s, 2}, {s, 3}, {s, 22}}, normals[3] = {{s, 4}, {s, 5}, {s, 23}},
           pix[3] = {{s, 6}, {s, 7}, {s, 24}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
           sslot[2] = {{s, 12}, {s, 28}}, dlights{s, 13}, levels{s, 14}, drgb{s, 15}, dctr{s, 16}, dslights{s, 17}, dunits{s, 18}, dlit{s, 19},
-          dwork{s, 20}, dspawn{s, 29}, dres{s, 30}, dviews{s, 31};
+          dwork{s, 20}, dspawn{s, 29}, dres{s, 30}, dviews{s, 31}, dsets{s, 32}, dsettab{s, 33};
     unsigned long long *cw_primary = nullptr, *cw_shadow = nullptr, *cw_mirror = nullptr;
     if (counted) {
         HIP_TRY(dwork.alloc(3 * 8 * sizeof(unsigned long long)));
@@ -2040,12 +2108,27 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     const size_t nctr = 4 * (size_t)(max_level + 1);
     HIP_TRY(dctr.alloc(nctr * sizeof(uint32_t)));  // per level {shadow rays, mirror rays, hits, -}; the last block: [3] = primary hits
     if (L) HIP_TRY(hipMemcpy(dlights.p, lights, (size_t)L * 24, hipMemcpyHostToDevice));
+    // light sets: every set's colours of every level (set b's entry i of a level at b * n + i), and the sets' table (SetsDev)
+    SetsDev T{};
+    auto sets_of = [&](int level) { return dsets.as<float>() + (size_t)level * n * nsets * 4; };
+    if (sets) {
+        HIP_TRY(dsets.alloc((size_t)(max_level > 0 ? max_level : 1) * n * nsets * 16));
+        HIP_TRY(dsettab.alloc(sets->table.size() * 4));
+        HIP_TRY(hipMemcpy(dsettab.p, sets->table.data(), sets->table.size() * 4, hipMemcpyHostToDevice));
+        const uint32_t* tab = dsettab.as<uint32_t>();
+        T.point_off = tab;
+        T.sph_off = tab + nsets + 1;
+        T.point = reinterpret_cast<const float4*>(tab + sets->point_at);
+        T.sph = reinterpret_cast<const float4*>(tab + sets->sph_at);
+        T.nsets = nsets;
+    }
     SoftDev Q{};
     if (SL) {
         HIP_TRY(dslights.alloc((size_t)SL * 28));
         HIP_TRY(dunits.alloc((size_t)soft->nunits * 12));
         HIP_TRY(dlit.alloc(n * SL * 4));
-        HIP_TRY(hipMemcpy(dslights.p, soft->spherical, (size_t)SL * 28, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dslights.p, sets ? sets->spherical.data() : soft->spherical, (size_t)SL * 28, hipMemcpyHostToDevice));
+        if (sets) Q.set_index = dsettab.as<uint32_t>() + 2 * ((size_t)nsets + 1);
         HIP_TRY(hipMemcpy(dunits.p, soft->unit_vectors, (size_t)soft->nunits * 12, hipMemcpyHostToDevice));
         Q.lights = dslights.as<float>();
         Q.units = dunits.as<float>();
@@ -2109,7 +2192,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     CgrtScene::RenderPred& P = s->rpred;
     const bool predictable = g_render_predict.load() && P.valid && P.W == W && P.H == H && P.rank == rank && P.nranks == nranks &&
                              P.max_level == max_level && P.L == L && !P.counts.empty() && SL == 0 && !counted && max_level >= 1 && !list &&
-                             !views;
+                             !views && !sets;
     auto predicted = [&]() -> int {
         const int np = (int)P.counts.size();  // levels the previous frame evaluated (P.counts[l] > 0 entries each)
         // {level 0's entries, level 1's entries}: one 64-bit word, filled by the primary kernel's fused spawn with one atomic
@@ -2254,6 +2337,22 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         const int prc = predicted();
         if (prc != CGRT_OK) return prc;
     }
+    // A level's shading (k_shade into its level record; light sets: k_shade_sets into every set's colours of the level) and the scatter of
+    // level 0 into the frame (k_write_rgb, folded with level 1 when with_child; light sets: k_write_rgb_sets, every set into its own frame).
+    auto shade = [&](int level, int a, int q, unsigned long long cnt, hipStream_t on, const uint32_t* dc) -> hipError_t {
+        if (sets)
+            return launch_shade_sets(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(), sdist[q].as<float>(),
+                                     sslot[q].as<int>(), cnt, mats, L, SL, dlit.as<uint32_t>(), Q.samples, T, sets_of(level), n, on, dc);
+        return launch_shade(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(), sdist[q].as<float>(),
+                            sslot[q].as<int>(), cnt, mats, dlights.as<float>(), L, dslights.as<float>(), SL, dlit.as<uint32_t>(), Q.samples, lvl_of(level),
+                            on, dc);
+    };
+    auto write_rgb = [&](bool with_child, unsigned long long cnt, float* frame) -> hipError_t {
+        if (sets)
+            return launch_write_rgb_sets(lvl_of(0), sets_of(0), with_child ? sets_of(1) : nullptr, cnt, n, nsets, ipix.as<int>(), frame,
+                                         (unsigned long long)W * H, nullptr);
+        return launch_write_rgb(lvl_of(0), with_child ? lvl_of(1) : nullptr, cnt, ipix.as<int>(), frame, nullptr);
+    };
     auto exact = [&]() -> int {
         HIP_TRY(hipEventRecord(aux.e0, nullptr));
         int nlev = 0;
@@ -2274,6 +2373,8 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             } else {
                 HIP_TRY(launch_trace_primary_compact(s->dev, C, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
                                                      ipix.as<int>(), primary_hits, nullptr, cw_primary, frame_rgb));  // (also clears this rank's pixels)
+                if (nsets > 1)  // (the primary kernel clears set 0's frame; a pixel that misses is black in every set)
+                    HIP_TRY(hipMemsetAsync(frame_rgb + 3ull * W * H, 0, (npix - (unsigned long long)W * H) * 12, nullptr));
                 st.primary_rays = owned_pixels(F);
             }
             // Level 0's spawn does not wait for the host to learn how many primary rays hit: it is launched over every item of the
@@ -2331,9 +2432,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                         if (L)
                             HIP_TRY(launch_trace_shadow(s->dev, srays[q1].as<float>(), sdist[q1].as<float>(), cnt * L, shits[q1].as<CgrtHitDev>(), aux.s,
                                                         ctr1 + 0, cw_shadow));
-                        HIP_TRY(launch_shade(rays[a1].as<float>(), hits[a1].as<CgrtHitDev>(), normals[a1].as<float>(), shits[q1].as<CgrtHitDev>(),
-                                             sdist[q1].as<float>(), sslot[q1].as<int>(), cnt, mats, dlights.as<float>(), L, dslights.as<float>(), SL,
-                                             dlit.as<uint32_t>(), Q.samples, lvl1, aux.s, ctr + 1));
+                        HIP_TRY(shade(1, a1, q1, cnt, aux.s, ctr + 1));
                         if (spawn1)
                             HIP_TRY(launch_trace_batch(s->dev, rays[b1].as<float>(), cnt, hits[b1].as<CgrtHitDev>(), normals[b1].as<float>(), cw_mirror,
                                                        aux.s, ctr1 + 1));
@@ -2346,9 +2445,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                     HIP_TRY(launch_soft_shadow(s->dev, Q, rays[a].as<float>(), hits[a].as<CgrtHitDev>(), cur_pix, cnt, dlit.as<uint32_t>(),
                                                soft->closest_hit == 0, nullptr));
                 }
-                HIP_TRY(launch_shade(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(), sdist[q].as<float>(),
-                                     sslot[q].as<int>(), cnt, mats, dlights.as<float>(), L, dslights.as<float>(), SL, dlit.as<uint32_t>(), Q.samples, lvl,
-                                     nullptr));
+                HIP_TRY(shade(level, a, q, cnt, nullptr, nullptr));
                 if (overlap) HIP_TRY(hipStreamWaitEvent(nullptr, aux.traced, 0));  // the next level (and the end of the frame) need the second stream's results
                 nlev = level + 1;
                 level_count.push_back(cnt);
@@ -2357,7 +2454,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                     // on their counts -- the frame is finished without a host round trip (an entry of level 0 without a mirror ray
                     // carries child = -1, so the scatter kernel can fold with level 1 whether or not level 1 has entries); the
                     // counts are read after the frame's closing event.
-                    HIP_TRY(launch_write_rgb(levels.as<float>(), levels.as<float>() + (size_t)n * 8, cnt, ipix.as<int>(), frame_rgb, nullptr));
+                    HIP_TRY(write_rgb(true, cnt, frame_rgb));
                     HIP_TRY(resolve(nullptr));
                     finished = true;
                     HIP_TRY(hipEventRecord(aux.e1, nullptr));
@@ -2396,7 +2493,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         }
         if (finished) {
         } else if (max_level < 1) {  // trace() returns black without tracing (main.cpp:267): no primary kernel ran, clear here
-            if (list || views)
+            if (list || views || sets)
                 HIP_TRY(hipMemsetAsync(frame_rgb, 0, npix * 12, nullptr));
             else
                 HIP_TRY(launch_clear_owned(F, frame_rgb, nullptr));
@@ -2404,11 +2501,14 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         } else {
             // color = directColor + reflectedColor * ks (main.cpp:262), deepest level first; the last fold (level 0 with level 1) is
             // done by the kernel that scatters level 0 over the frame
-            for (int level = nlev - 2; level >= 1; level--)
-                HIP_TRY(launch_fold(levels.as<float>() + (size_t)level * n * 8, levels.as<float>() + (size_t)(level + 1) * n * 8, level_count[level],
-                                    nullptr));
-            HIP_TRY(launch_write_rgb(levels.as<float>(), nlev >= 2 ? levels.as<float>() + (size_t)n * 8 : nullptr, level_count[0], ipix.as<int>(),
-                                     frame_rgb, nullptr));
+            for (int level = nlev - 2; level >= 1; level--) {
+                if (sets)
+                    HIP_TRY(launch_fold_sets(lvl_of(level), sets_of(level), sets_of(level + 1), level_count[level], n, nsets, nullptr));
+                else
+                    HIP_TRY(launch_fold(levels.as<float>() + (size_t)level * n * 8, levels.as<float>() + (size_t)(level + 1) * n * 8, level_count[level],
+                                        nullptr));
+            }
+            HIP_TRY(write_rgb(nlev >= 2, level_count[0], frame_rgb));
         }
         if (!finished) {
             HIP_TRY(resolve(nullptr));
@@ -2419,7 +2519,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipEventElapsedTime(&ms, aux.e0, aux.e1));
         st.device_ms = ms;
         st.levels = nlev;
-        if (list || views) return CGRT_OK;  // (a ray list or a batch of views sizes no frame)
+        if (list || views || sets) return CGRT_OK;  // (a ray list or a batch of views or light sets sizes no frame)
         // what this frame found sizes the next one
         P.valid = g_render_predict.load() && SL == 0 && !counted && max_level >= 1 && !level_count.empty();
         P.W = W, P.H = H, P.rank = rank, P.nranks = nranks, P.max_level = max_level, P.L = L;
@@ -2428,7 +2528,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         return CGRT_OK;
     };
     if (!frame_done) {
-        if (!list && !views) P.last_path = predictable ? 2 : 0;
+        if (!list && !views && !sets) P.last_path = predictable ? 2 : 0;
         st = CgrtRenderStats{};
         const int erc = exact();
         if (erc != CGRT_OK) return erc;
@@ -2440,7 +2540,8 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipStreamWaitEvent(list->stream, aux.e1, 0));
     } else if (dout) {
         // The frame's last kernel is done (aux.e1 was waited for); the wait below only makes that ordering explicit on the caller's stream.
-        const ExportDev E = export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, views ? nviews : 0u, aa, rank, nranks, packed);
+        const ExportDev E = export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, views ? nviews : sets ? nsets : 0u, aa, rank, nranks,
+                                      packed);
         if (!s->export_done) HIP_TRY(hipEventCreateWithFlags(&s->export_done, hipEventDisableTiming));
         HIP_TRY(hipStreamWaitEvent(dout->stream, aux.e1, 0));
         HIP_TRY(launch_export_frame(E, dout->stream));
@@ -2661,6 +2762,61 @@ int cgrt_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nvie
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
     return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, &D, nullptr, &V);
+}
+
+// ---- one camera under a batch of light sets (render_impl, LightSetSrc; include/cgrt.h cgrt_render_light_sets*) ----
+// Every check of include/cgrt.h's list, all CGRT_E_ARG and before any device work; then *P holds the batch's plan.
+static int light_sets_args(const CgrtScene* s, const CgrtCamera* cam, int W, int H, const CgrtLightSets* sets, const CgrtSoftShadows* soft,
+                           int max_level, const void* out, LightSetSrc* P) {
+    if (!s || !cam || !sets || !out) return fail(CGRT_E_ARG, "NULL argument");
+    const uint32_t B = sets->nsets;
+    if (B == 0 || B > 1024) return fail(CGRT_E_ARG, "nsets must be 1 .. 1024");
+    const uint32_t* lo = sets->light_offsets;
+    const uint32_t* so = sets->spherical_offsets;
+    if (!lo) return fail(CGRT_E_ARG, "light_offsets is NULL");
+    if (lo[0] != 0 || (so && so[0] != 0)) return fail(CGRT_E_ARG, "light set offsets must start at 0");
+    for (uint32_t b = 0; b < B; b++)
+        if (lo[b + 1] < lo[b] || (so && so[b + 1] < so[b])) return fail(CGRT_E_ARG, "light set offsets must not decrease");
+    const uint32_t np = lo[B], ns = so ? so[B] : 0u;
+    if (np && !sets->lights) return fail(CGRT_E_ARG, "point lights in the sets but lights is NULL");
+    if (ns && !sets->spherical) return fail(CGRT_E_ARG, "spherical lights in the sets but spherical is NULL");
+    if (soft && (soft->spherical || soft->nspherical)) return fail(CGRT_E_ARG, "soft carries the sampling parameters only: its spherical lights must be NULL and 0");
+    if (ns && (!soft || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
+        return fail(CGRT_E_ARG, "spherical lights need soft: a unit-vector table and 1..2^24 samples");
+    if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+    if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
+    const unsigned long long px = (unsigned long long)W * (unsigned long long)H;
+    if (px > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large: W*H exceeds 0x7fffffff");
+    plan_light_sets(*sets, *P);
+    // a level's shadow list holds up to W*H x (distinct positions) rays, its soft-shadow counters W*H x (distinct keys): 32-bit indices
+    if (px * (P->points.size() / 6) > 0x7fffffffull) return fail(CGRT_E_ARG, "too many distinct point-light positions for the frame's 32-bit shadow list");
+    if (px * P->sph_index.size() > 0x7fffffffull || (ns && px * P->sph_index.size() * soft->samples > 0x7fffffffull * 64))
+        return fail(CGRT_E_ARG, "too many distinct spherical lights for the frame's 32-bit soft-shadow lists");
+    return CGRT_OK;
+}
+int cgrt_render_light_sets(CgrtScene* s, const CgrtCamera* cam, int W, int H, const CgrtLightSets* sets, const CgrtSoftShadows* soft, int max_level,
+                           float* rgb, CgrtRenderStats* stats) {
+    LightSetSrc P;
+    const int rc = light_sets_args(s, cam, W, H, sets, soft, max_level, rgb, &P);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    return render_impl(s, cam, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, rgb, stats, nullptr, nullptr, false,
+                       nullptr, nullptr, nullptr, &P);
+}
+int cgrt_render_light_sets_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const CgrtLightSets* sets, const CgrtSoftShadows* soft,
+                                  int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats) {
+    LightSetSrc P;
+    int rc = light_sets_args(s, cam, W, H, sets, soft, max_level, d_out, &P);
+    if (rc) return rc;
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    uint64_t extent = 0;
+    if ((rc = export_args(d_out, W, H, format, 0, &D.pitch, &extent))) return rc;
+    D.view_bytes = extent;  // (packed rows: one set's frame is exactly its extent)
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_out, extent * P.nsets, "d_out"))) return rc;
+    return render_impl(s, cam, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false,
+                       &D, nullptr, nullptr, &P);
 }
 
 // ---- getFinalColor of the caller's rays (main.cpp:298-310): level 0 of the wavefront from a ray list (render_impl, ListSrc) ----

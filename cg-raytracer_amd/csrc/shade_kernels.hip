@@ -319,6 +319,124 @@ __global__ void k_write_rgb_strided(const float4* __restrict__ lvl0, const float
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) write_rgb_entry(lvl0, child_lvl, i, item_pixels, rgb);
 }
 
+// ---- Light sets (cgrt_render_light_sets*): one camera's ray tree shaded under T.nsets light sets ----
+// The level lists, their link records lvl[2i+1] = {ks, child} and the shadow answers belong to the batch and are shared by every set:
+// k_spawn traced one shadow ray per hit and DISTINCT point-light position p (sslot[i * npos + p]), k_soft_shadow_sets counted
+// lit[i * nsph + k] per distinct spherical key k.  What depends on a set is its colours and which lights it holds: set b's direct colour of
+// entry i is out[b * stride + i] = {colour, flags} (consecutive entries at consecutive addresses).  k_shade_sets computes what does not
+// depend on the set once per entry, then every set's sum in shade_entry's expression order (spherical lights first, :168-218, then the
+// point lights, :219-232), so that set b's colour is, bit for bit, what k_shade writes in set b's single frame.
+__global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_shade_sets(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                                 const float* __restrict__ normals, const CgrtHitDev* __restrict__ shits,
+                                                                 const float* __restrict__ sdist, const int* __restrict__ sslot,
+                                                                 unsigned long long n, const float* __restrict__ materials, unsigned npos,
+                                                                 unsigned nsph, const uint32_t* __restrict__ lit, unsigned samples, SetsDev T,
+                                                                 float4* __restrict__ out, unsigned long long stride,
+                                                                 const uint32_t* __restrict__ dcount) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (dcount) {  // (as k_shade: the grid covers the list's capacity)
+        const unsigned long long present = *dcount;
+        n = present < n ? present : n;
+    }
+    if (i >= n) return;
+    const bool hit = hits[i].hit != 0;
+    F3 nrm = f3(0.f, 0.f, 0.f), pointOn = f3(0.f, 0.f, 0.f), kd = f3(0.f, 0.f, 0.f), ks = f3(0.f, 0.f, 0.f), refl = f3(0.f, 0.f, 0.f);
+    float shininess = 1.0f;
+    if (hit) {
+        const float* r = rays + 7 * i;
+        const F3 o = ldv(r), d = ldv(r + 3);
+        nrm = ldv(normals + 3 * i);
+        pointOn = add(o, scale(d, hits[i].t));
+        const int mid = hits[i].material_id;
+        kd = mid >= 0 ? ldv(materials + 8 * mid) : f3(0.f, 0.f, 0.f);
+        ks = mid >= 0 ? ldv(materials + 8 * mid + 3) : f3(0.f, 0.f, 0.f);
+        shininess = mid >= 0 ? materials[8 * mid + 6] : 1.0f;
+        const float dn = dot(nrm, d);  // glm::reflect(I, N) = I - N * dot(N, I) * 2
+        refl = normalize(sub(d, scale(scale(nrm, dn), 2.0f)));
+    }
+    const float eps = 0.001f;
+    for (unsigned b = 0; b < T.nsets; b++) {
+        float4 out0 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (hit) {
+            F3 result = f3(0.f, 0.f, 0.f);
+            for (uint32_t k = T.sph_off[b]; k < T.sph_off[b + 1]; k++) {  // spherical lights first (main.cpp:168-218)
+                const float4 lp = T.sph[2 * k], lc = T.sph[2 * k + 1];
+                const F3 lpos = f3(lp.x, lp.y, lp.z), lcol = f3(lc.x, lc.y, lc.z);
+                const F3 toLight = normalize(sub(lpos, pointOn));
+                const float dc = dot(toLight, nrm);
+                const F3 dif = dc <= 0 ? f3(0.f, 0.f, 0.f) : f3(lcol.x * kd.x * dc, lcol.y * kd.y * dc, lcol.z * kd.z * dc);
+                const float sc = dot(refl, toLight);
+                F3 spec = f3(0.f, 0.f, 0.f);
+                if (!(sc <= 0)) {
+                    const float p = __builtin_powf(sc, shininess);
+                    spec = f3(lcol.x * ks.x * p, lcol.y * ks.y * p, lcol.z * ks.z * p);
+                }
+                const float counter = (float)lit[i * nsph + __float_as_uint(lp.w)] / (float)samples;  // (:200)
+                result = add(result, scale(dif, counter));
+                result = add(result, scale(spec, counter));
+            }
+            for (uint32_t k = T.point_off[b]; k < T.point_off[b + 1]; k++) {
+                const float4 lp = T.point[2 * k], lc = T.point[2 * k + 1];
+                const F3 lpos = f3(lp.x, lp.y, lp.z), lcol = f3(lc.x, lc.y, lc.z);
+                const F3 toLight = normalize(sub(lpos, pointOn));
+                const int slot = sslot[i * npos + __float_as_uint(lp.w)];
+                const CgrtHitDev sh = shits[slot];
+                const bool inShadow = sh.hit && !(sh.t + eps >= sdist[slot]);  // main.cpp:118-130
+                if (inShadow) continue;
+                const float dc = dot(toLight, nrm);  // diffuseOneLight :84-98
+                const F3 dif = dc <= 0 ? f3(0.f, 0.f, 0.f) : f3(lcol.x * kd.x * dc, lcol.y * kd.y * dc, lcol.z * kd.z * dc);
+                const float sc = dot(refl, toLight);  // specularOneLight :61-82
+                F3 spec = f3(0.f, 0.f, 0.f);
+                if (!(sc <= 0)) {
+                    const float p = __builtin_powf(sc, shininess);
+                    spec = f3(lcol.x * ks.x * p, lcol.y * ks.y * p, lcol.z * ks.z * p);
+                }
+                result = add(result, dif);
+                result = add(result, spec);
+            }
+            out0 = make_float4(result.x, result.y, result.z, __uint_as_float(1u));
+        }
+        out[(unsigned long long)b * stride + i] = out0;
+    }
+}
+// fold_entry per set: set blockIdx.y's colours of this level (sets_lvl) += its colours of the next (child_sets) * ks, through the shared
+// link records lvl[2i+1] (main.cpp:262)
+__global__ void k_fold_sets(const float4* __restrict__ lvl, float4* __restrict__ sets_lvl, const float4* __restrict__ child_sets, unsigned long long n,
+                            unsigned long long stride) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long o = (unsigned long long)blockIdx.y * stride;
+    const float4 a = sets_lvl[o + i], b = lvl[2 * i + 1];
+    const int child = __float_as_int(b.w);
+    if (!(__float_as_uint(a.w) & 1u) || (b.z <= 0.01f) || child < 0) return;  // no child: colour + 0 * ks = colour
+    const float4 c = child_sets[o + (unsigned long long)child];             // a child that missed holds colour 0
+    sets_lvl[o + i] = make_float4(a.x + c.x * b.x, a.y + c.y * b.y, a.z + c.z * b.z, a.w);
+}
+// write_rgb_entry per set: set blockIdx.y's level-0 colour (folded with level 1 when child_sets is given) goes to its own frame,
+// rgb[3 * (set * frame_pixels + pixel)]
+__global__ void k_write_rgb_sets(const float4* __restrict__ lvl0, const float4* __restrict__ sets0, const float4* __restrict__ child_sets,
+                                 unsigned long long n, unsigned long long stride, const int* __restrict__ item_pixels, float* __restrict__ rgb,
+                                 unsigned long long frame_pixels) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long pix = item_pixels[i];
+    if (pix < 0) return;  // item outside the frame
+    const unsigned long long o = (unsigned long long)blockIdx.y * stride;
+    float4 a = sets0[o + i];
+    if (child_sets) {
+        const float4 b = lvl0[2 * i + 1];
+        const int child = __float_as_int(b.w);
+        if ((__float_as_uint(a.w) & 1u) && !(b.z <= 0.01f) && child >= 0) {
+            const float4 c = child_sets[o + (unsigned long long)child];
+            a = make_float4(a.x + c.x * b.x, a.y + c.y * b.y, a.z + c.z * b.z, a.w);
+        }
+    }
+    float* p = rgb + 3ull * ((unsigned long long)blockIdx.y * frame_pixels + (unsigned long long)pix);
+    p[0] = a.x;
+    p[1] = a.y;
+    p[2] = a.z;
+}
+
 // The reference's antiAliasing branch (main.cpp:663-687): pixel (x, y) of the W x H frame is resolved from the sub-samples
 // (2x + dx, 2y + dy) of the 2W x 2H frame `sub` the wavefront shaded -- summed channel by channel in the reference's loop order (yc
 // outer, xc inner) onto a zero accumulator (upstream's `glm::vec3 color;` is uninitialised, DESIGN.md "Anti-aliasing" finding 1) and
@@ -467,6 +585,30 @@ hipError_t launch_write_rgb(const float* lvl0, const float* child_lvl, unsigned 
     if (n)
         hipLaunchKernelGGL(k_write_rgb, dim3(grid_for(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
                            reinterpret_cast<const float4*>(child_lvl), n, item_pixels, rgb, dcount);
+    return hipGetLastError();
+}
+
+hipError_t launch_shade_sets(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
+                             const int* sslot, unsigned long long n, const float* materials, unsigned npos, unsigned nsph, const uint32_t* lit,
+                             unsigned samples, const SetsDev& T, float* out, unsigned long long stride, hipStream_t s, const uint32_t* dcount) {
+    if (n)
+        hipLaunchKernelGGL(k_shade_sets, dim3(grid_for(n, CGRT_SHADE_BLOCK)), dim3(CGRT_SHADE_BLOCK), 0, s, rays, hits, normals, shits, sdist, sslot, n,
+                           materials, npos, nsph, lit, samples, T, reinterpret_cast<float4*>(out), stride, dcount);
+    return hipGetLastError();
+}
+hipError_t launch_fold_sets(const float* lvl, float* sets_lvl, const float* child_sets, unsigned long long n, unsigned long long stride, unsigned nsets,
+                            hipStream_t s) {
+    if (n && nsets)
+        hipLaunchKernelGGL(k_fold_sets, dim3(grid_for(n, 256), nsets), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl),
+                           reinterpret_cast<float4*>(sets_lvl), reinterpret_cast<const float4*>(child_sets), n, stride);
+    return hipGetLastError();
+}
+hipError_t launch_write_rgb_sets(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n, unsigned long long stride,
+                                 unsigned nsets, const int* item_pixels, float* rgb, unsigned long long frame_pixels, hipStream_t s) {
+    if (n && nsets)
+        hipLaunchKernelGGL(k_write_rgb_sets, dim3(grid_for(n, 256), nsets), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
+                           reinterpret_cast<const float4*>(sets0), reinterpret_cast<const float4*>(child_sets), n, stride, item_pixels, rgb,
+                           frame_pixels);
     return hipGetLastError();
 }
 

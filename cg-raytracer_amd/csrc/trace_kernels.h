@@ -24,6 +24,21 @@ struct SoftDev {
     const float* units;   // nunits x 3 unit vectors: the randomUnitVector() draws (main.cpp:46-59)
     uint32_t nlights, samples, nunits, seed, level;
     uint32_t view_pixels;  // 0, or W * H of a multi-view frame: samples are drawn with item_pixels[item] % view_pixels (k_soft_shadow)
+    // light sets (k_soft_shadow_sets): lights are the batch's distinct (position, radius, in-set index) keys, and key l draws as light
+    // set_index[l] -- its index within its own set, as that set's single frame draws it.  NULL otherwise.
+    const uint32_t* set_index;
+};
+
+// A batch of light sets on the device (capi.cpp LightSetSrc; cgrt_render_light_sets*): set b holds the point lights point_off[b] ..
+// point_off[b + 1] - 1 and the spherical lights sph_off[b] .. sph_off[b + 1] - 1, in the caller's order.  Light k is two float4s
+// {position, slot}, {colour, 0}; slot (the bits of .w) is its distinct entry: the light index k_spawn traced its shadow ray with, or
+// the soft-shadow key whose samples k_soft_shadow_sets counted.
+struct SetsDev {
+    const uint32_t* point_off;
+    const uint32_t* sph_off;
+    const float4* point;
+    const float4* sph;
+    uint32_t nsets;
 };
 
 // threads per workgroup the ray-list kernels (batch, soft shadow) are launched with for this scene; frames carry theirs in FrameDev::block
@@ -130,6 +145,17 @@ hipError_t launch_shade_strided(const float* rays, const CgrtHitDev* hits, const
 hipError_t launch_fold_strided(float* lvl, const float* child_lvl, unsigned long long n, hipStream_t s, const uint32_t* dcount);
 hipError_t launch_write_rgb_strided(const float* lvl0, const float* child_lvl, unsigned long long n, const int* item_pixels, float* rgb, hipStream_t s,
                                     const uint32_t* dcount);
+// light sets (cgrt_render_light_sets*): set b's direct colour of entry i -> out[b * stride + i] = {colour, flags} (k_shade_sets); npos /
+// nsph: the batch's distinct point positions (sslot's row) and spherical keys (lit's row); dcount as launch_shade
+hipError_t launch_shade_sets(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
+                             const int* sslot, unsigned long long n, const float* materials, unsigned npos, unsigned nsph, const uint32_t* lit,
+                             unsigned samples, const SetsDev& T, float* out, unsigned long long stride, hipStream_t s, const uint32_t* dcount = nullptr);
+// launch_fold / launch_write_rgb per set (n entries, nsets sets of colours `stride` entries apart; lvl / lvl0: the level's link records);
+// set b's frame starts at rgb + 3 * b * frame_pixels
+hipError_t launch_fold_sets(const float* lvl, float* sets_lvl, const float* child_sets, unsigned long long n, unsigned long long stride, unsigned nsets,
+                            hipStream_t s);
+hipError_t launch_write_rgb_sets(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n, unsigned long long stride,
+                                 unsigned nsets, const int* item_pixels, float* rgb, unsigned long long frame_pixels, hipStream_t s);
 // the anti-aliased frame (main.cpp:663-687) from the 2W x 2H sub-sample frame `sub` of F: see k_resolve_aa (shade_kernels.hip).
 // out: F.nst_rank * 1024 * 3 floats (packed) or (F.W / 2) * (F.H / 2) * 3 floats
 hipError_t launch_resolve_aa(const FrameDev& F, const float* sub, float* out, int packed, hipStream_t s);

@@ -659,8 +659,10 @@ __global__ CGRT_LB void k_visibility(SceneDev S, const float* __restrict__ src, 
 // samples as pixel = item (hits and item_pixels are not read).
 // VIEWS: the items belong to a multi-view frame, whose pixels are view * W * H + (in-view pixel): samples are drawn with the in-view
 // pixel item_pixels[item] % Q.view_pixels, so that every view draws what its single-camera frame draws.
+// SETS (k_soft_shadow_sets, light sets): light l is a distinct key of the batch and draws as light Q.set_index[l], its index within its
+// own set, so that every set draws what its single frame draws.
 // thread g of k_soft_shadow's layout (every lane of the wave calls it: the counts are aggregated per wave)
-template <bool ANYHIT, bool FAST, bool POINTS, bool VIEWS>
+template <bool ANYHIT, bool FAST, bool POINTS, bool VIEWS, bool SETS = false>
 __device__ __forceinline__ void soft_shadow_thread(const SceneDev& S, const SoftDev& Q, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
                                                    const int* __restrict__ item_pixels, unsigned long long g, unsigned long long nthreads,
                                                    uint32_t* __restrict__ lit, uint32_t* s_lds) {
@@ -687,7 +689,7 @@ __device__ __forceinline__ void soft_shadow_thread(const SceneDev& S, const Soft
             if (VIEWS) pixel %= Q.view_pixels;
         }
         const float* L = Q.lights + 7 * l;
-        const float* u = Q.units + 3ull * soft_sample_index(Q.seed, pixel, Q.level, l, smp, Q.nunits);
+        const float* u = Q.units + 3ull * soft_sample_index(Q.seed, pixel, Q.level, SETS ? Q.set_index[l] : l, smp, Q.nunits);
         soft_shadow_ray(pointOn, f3(L[0], L[1], L[2]), L[3], f3(u[0], u[1], u[2]), o, d, t);
     }
     const float lightT = t;
@@ -721,6 +723,14 @@ __global__ CGRT_LB void k_soft_shadow(SceneDev S, SoftDev Q, const float* __rest
     extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
     const unsigned long long g = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     soft_shadow_thread<ANYHIT, FAST, POINTS, VIEWS>(S, Q, rays, hits, item_pixels, g, nthreads, lit, s_lds);
+}
+// k_soft_shadow with the SETS flag (a kernel of its own: the instantiations above keep their names and their code)
+template <bool ANYHIT, bool FAST>
+__global__ CGRT_LB void k_soft_shadow_sets(SceneDev S, SoftDev Q, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                           const int* __restrict__ item_pixels, unsigned long long nthreads, uint32_t* __restrict__ lit) {
+    extern __shared__ uint32_t s_lds[];
+    const unsigned long long g = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    soft_shadow_thread<ANYHIT, FAST, false, false, true>(S, Q, rays, hits, item_pixels, g, nthreads, lit, s_lds);
 }
 // The count-driven form (enqueued frames): the level's items are the first *dcount (<= nitems, the list's capacity) entries, known only on
 // the device; a capped grid strides over their present x nlights x samples threads, gridDim.x * blockDim.x at a time.  Thread g draws
@@ -1125,6 +1135,13 @@ hipError_t launch_soft_shadow(const SceneDev& S, const SoftDev& Q, const float* 
     const unsigned long long blocks = (nthreads + block - 1) / block;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     const bool fast = S.fast_root != REF_NONE;
+    if (Q.set_index) {  // a light-set batch's distinct keys (k_soft_shadow_sets)
+        if (anyhit)
+            CGRT_LAUNCH2(k_soft_shadow_sets, true, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
+        else
+            CGRT_LAUNCH2(k_soft_shadow_sets, false, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
+        return hipGetLastError();
+    }
     if (Q.view_pixels) {  // a multi-view frame's items (k_soft_shadow VIEWS)
         const dim3 grid((unsigned)blocks), threads(block);
         if (anyhit && fast)

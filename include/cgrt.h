@@ -415,6 +415,52 @@ int cgrt_render_views_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t 
                              uint32_t nlights, const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream,
                              CgrtRenderStats* stats);
 
+/* Light sets: ONE camera, one W x H frame, one max_level and one set of soft-shadow sampling parameters rendered under nsets light setups
+ * (the reference's Lights panel edits the lights and renders the same view again, src/main.cpp:812-870).  Set b
+ * holds its own point lights (light_offsets[b] .. light_offsets[b+1] - 1, 6 floats each {position, color}, PointLight, scene.h:42-45) and
+ * its own spherical lights (spherical_offsets[b] .. spherical_offsets[b+1] - 1, 7 floats each {position, radius, color}, SphericalLight,
+ * scene.h:47-51); either count may be 0 and the counts may differ from set to set.  spherical_offsets NULL: no set has spherical lights.
+ * Frame b is, bit for bit, what cgrt_render_soft (cgrt_render without spherical lights) returns for cam and set b's lights: spherical-light
+ * sample smp of pixel p = y*W + x at level lv is drawn with l = the light's index WITHIN SET b, as in that single frame.
+ * What is shared: a pixel's ray tree (primary hit, mirror rays, which levels exist) does not depend on the lights, so the primary launch,
+ * every level's spawn and every mirror list run once per batch; a point light's shadow ray and its verdict (pointInShadow, main.cpp:104-135)
+ * depend on its position alone, so shadow rays are traced once per DISTINCT point-light position over all sets; a spherical light's sample
+ * count depends on its position, its radius and its in-set index, never on its colour, so counts are taken once per distinct (position,
+ * radius, in-set index).  Colour enters only the Phong terms (shading, main.cpp:160-235), which are evaluated per set.  Positions and radii
+ * are compared by BIT PATTERN: +0.0 and -0.0 are distinct, and so are NaN payloads.  The dedupe never changes a byte, only the counts:
+ * stats: primary_rays, reflection_rays and levels are the single frame's; shadow_rays = (hits over all levels) x (distinct point-light
+ * positions); soft_shadow_rays = (hits over all levels) x (distinct spherical keys) x samples; device_ms covers the whole batch.  These
+ * differ from the sums over nsets single frames whenever sets share lights (a colour sweep traces exactly one frame's rays).
+ * `soft` carries only the sampling parameters (unit_vectors, nunits, samples, seed, closest_hit): its spherical must be NULL and nspherical
+ * 0; soft may be NULL only when no set has spherical lights.  Whole frames, rank 0 of 1, no anti-aliasing; the call always takes the exactly
+ * sized path and neither reads nor writes the scene's frame prediction or frame hints.  Workspace beyond a single frame's: max_level x
+ * (frame items) x nsets x 16 bytes of per-set colours (about 2 GB at 1920x1080, max_level 4, nsets 16) and nsets x W x H x 12 bytes of
+ * frames.
+ * Checks, all CGRT_E_ARG and before any device work: NULL scene / cam / sets / output; nsets 0 or above 1024; light_offsets NULL; offsets
+ * that do not start at 0 or that decrease; lights (spherical) NULL while its count is > 0; spherical lights without a valid soft (unit
+ * table, 1..2^24 samples), or a soft that carries spherical lights of its own; W or H <= 0; max_level outside 0..16; W*H > 0x7fffffff;
+ * W*H x (distinct point-light positions) or W*H x (distinct spherical keys) above 0x7fffffff (the lists' 32-bit indices); (device form)
+ * unknown format, d_out not 4-byte aligned.  Then a host-only scene -> CGRT_E_NO_DEVICE; then (device form) the bytes the batch spans not
+ * all device memory of the scene's device (as cgrt_render_device checks d_out) -> CGRT_E_ARG.  A batch that fails writes nothing to the
+ * output and leaves the scene usable. */
+typedef struct CgrtLightSets {
+    uint32_t nsets;                    /* B, 1 .. 1024 */
+    const float* lights;               /* point lights of all sets, set after set: light_offsets[nsets] x 6 {position, color} */
+    const uint32_t* light_offsets;     /* nsets + 1, [0] = 0, non-decreasing */
+    const float* spherical;            /* spherical lights, set after set: spherical_offsets[nsets] x 7 {position, radius, color} */
+    const uint32_t* spherical_offsets; /* nsets + 1 ([0] = 0, non-decreasing), or NULL: no set has spherical lights */
+} CgrtLightSets;
+/* cgrt_render_light_sets: rgb (host) holds nsets*W*H*3 floats, the sets' frames back to back (set b's pixel (x, y) at b*W*H + y*W + x).
+ * Synchronous. */
+int cgrt_render_light_sets(CgrtScene* scene, const CgrtCamera* cam, int W, int H, const CgrtLightSets* sets, const CgrtSoftShadows* soft,
+                           int max_level, float* rgb, CgrtRenderStats* stats);
+/* cgrt_render_light_sets_device: set b starts at d_out + b * (the packed frame bytes of `format`) and holds cgrt_render_device's packed
+ * bytes for cam and set b's lights (aa = 0, rank 0 of 1) -- a contiguous (B, H, W, 3) f32, (B, 3, H, W) f32 or (B, H, W, 4) u8 array.
+ * Stream and export-event rules of cgrt_render_views_device: the call blocks until the batch's kernels are done and returns with the
+ * export enqueued on `stream`, behind everything the caller enqueued there before. */
+int cgrt_render_light_sets_device(CgrtScene* scene, const CgrtCamera* cam, int W, int H, const CgrtLightSets* sets,
+                                  const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats);
+
 /* Enqueued frames: the three device entries above without waiting for the GPU.  Each takes its blocking
  * counterpart's arguments, with a ticket out-parameter (NULL allowed) in place of the stats, and writes exactly the bytes its counterpart
  * writes for the same arguments (every format, row pitch, aa, rank / nranks, soft-shadow setting and max_level 0..16); bytes outside the
