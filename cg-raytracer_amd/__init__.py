@@ -113,7 +113,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -191,6 +191,11 @@ def lib() -> C.CDLL:
     L.cgrt_render_light_sets.argtypes = [vp, C.POINTER(Camera), i32, i32, C.POINTER(LightSets), C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
     L.cgrt_render_light_sets_device.argtypes = [vp, C.POINTER(Camera), i32, i32, C.POINTER(LightSets), C.POINTER(SoftShadows), i32, vp, i32, vp,
                                                 C.POINTER(RenderStats)]
+    L.cgrt_render_views_light_sets.argtypes = [vp, vp, u32, i32, i32, C.POINTER(LightSets), C.POINTER(SoftShadows), i32, vp, C.POINTER(RenderStats)]
+    L.cgrt_render_views_light_sets_device.argtypes = [vp, vp, u32, i32, i32, C.POINTER(LightSets), C.POINTER(SoftShadows), i32, vp, i32, vp,
+                                                      C.POINTER(RenderStats)]
+    L.cgrt_enqueue_render_views_light_sets_device.argtypes = [vp, vp, u32, i32, i32, C.POINTER(LightSets), C.POINTER(SoftShadows), i32, vp, i32,
+                                                              vp, C.POINTER(u64)]
     L.cgrt_enqueue_render_device.argtypes = [vp, C.POINTER(Camera), i32, i32, vp, u32, C.POINTER(SoftShadows), i32, i32, i32, i32, vp, i32, u64,
                                              vp, C.POINTER(u64)]
     L.cgrt_enqueue_render_views_device.argtypes = [vp, vp, u32, i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, i32, vp, C.POINTER(u64)]
@@ -750,16 +755,18 @@ class Scene:
     def _views_tensor(self, cams, W, H, format, out, stream):
         """render_views_tensor's checks of `out` (ValueError) and its new tensor: (camera array, out, format code, stream)."""
         a = camera_array(cams)
-        out, fmt, stream = self._batch_tensor(len(a), W, H, format, out, stream)
+        out, fmt, stream = self._batch_tensor((len(a),), W, H, format, out, stream)
         return a, out, fmt, stream
 
-    def _batch_tensor(self, B, W, H, format, out, stream):
-        """The checks of `out` (ValueError) for a batch of B frames exported back to back (views, light sets), and its new tensor:
-        (out, format code, stream)."""
+    def _batch_tensor(self, lead, W, H, format, out, stream):
+        """The checks of `out` (ValueError) for a batch of frames exported back to back (views, light sets, views x light sets), with the
+        leading shape `lead` ((B,) or (V, S)), and its new tensor: (out, format code, stream)."""
         import torch
 
         fmt = _frame_format(format)
-        shape, dtype = {0: ((B, H, W, 3), torch.float32), 1: ((B, 3, H, W), torch.float32), 2: ((B, H, W, 4), torch.uint8)}.get(fmt, (None, None))
+        lead = tuple(lead)
+        shape, dtype = {0: (lead + (H, W, 3), torch.float32), 1: (lead + (3, H, W), torch.float32), 2: (lead + (H, W, 4), torch.uint8)}.get(
+            fmt, (None, None))
         if shape is None:
             raise ValueError(f"format must be one of {sorted(FRAME_FORMATS)}, not {format!r}")
         if out is not None:
@@ -859,8 +866,57 @@ class Scene:
         (default: torch.cuda.current_stream()).  Other keywords as render_light_sets.  Returns (tensor, stats dict)."""
         light_sets = list(light_sets)
         self._light_sets_arg(light_sets, kw.get("spherical_sets"))  # (ValueError before anything is allocated)
-        out, fmt, stream = self._batch_tensor(len(light_sets), W, H, format, out, stream)
+        out, fmt, stream = self._batch_tensor((len(light_sets),), W, H, format, out, stream)
         st = self.render_light_sets_device(cam, W, H, out.data_ptr(), light_sets, format=fmt, stream=stream.cuda_stream, **kw)
+        return out, st
+
+    # ---- multi-view light sets (include/cgrt.h cgrt_render_views_light_sets*; DESIGN.md section 5.16) ----
+    def render_views_light_sets(self, cams, W: int, H: int, light_sets, spherical_sets=None, units=None, samples: int = 200, seed: int = 0,
+                                max_level: int = 2):
+        """cgrt_render_views_light_sets: frame (v, s) of the result is render_soft (render without spherical lights) of cams[v] under
+        light_sets[s] (and spherical_sets[s]), bit for bit; one wavefront for all views, shadow rays once per distinct light position.
+        cams as render_views, the sets as render_light_sets.  Returns (rgb[V, S, W*H, 3], stats dict of the batch)."""
+        a = camera_array(cams)
+        q, keep = self._light_sets_arg(light_sets, spherical_sets)  # noqa: F841
+        s, keep_s = self._light_sets_soft(spherical_sets, units, samples, seed)  # noqa: F841
+        rgb = np.zeros((len(a), q.nsets, W * H, 3), np.float32)
+        st = RenderStats()
+        _check(lib().cgrt_render_views_light_sets(self._h, _ptr(a) if len(a) else None, len(a), W, H, C.byref(q), s, max_level, _ptr(rgb),
+                                                  C.byref(st)))
+        return rgb, {k: getattr(st, k) for k, _ in st._fields_}
+
+    def render_views_light_sets_device(self, cams, W: int, H: int, d_out_ptr: int, light_sets, spherical_sets=None, units=None,
+                                       samples: int = 200, seed: int = 0, max_level: int = 2, format="rgb", stream: int = 0) -> dict:
+        """cgrt_render_views_light_sets_device: the V x S frames exported into device memory at d_out_ptr, frame (v, s) at (v * S + s) *
+        (packed frame bytes), each in the packed layout of render_device's `format`; enqueued on the hipStream_t `stream`.  Raw integers, as
+        render_device.  Returns the stats dict."""
+        a = camera_array(cams)
+        q, keep = self._light_sets_arg(light_sets, spherical_sets)  # noqa: F841
+        s, keep_s = self._light_sets_soft(spherical_sets, units, samples, seed)  # noqa: F841
+        st = RenderStats()
+        _check(
+            lib().cgrt_render_views_light_sets_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, C.byref(q), s, max_level, C.c_void_p(d_out_ptr) if d_out_ptr else None,
+                _frame_format(format), C.c_void_p(stream) if stream else None, C.byref(st),
+            )
+        )  # fmt: skip
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def _views_light_sets_tensor(self, cams, W, H, light_sets, spherical_sets, format, out, stream):
+        """The checks (ValueError, before any call) and the (V, S, ...) tensor of the *_views_light_sets_tensor forms: (cams, sets, the
+        CgrtLightSets argument and the arrays it points into, out, format code, stream)."""
+        a = camera_array(cams)
+        light_sets = list(light_sets)
+        q, keep = self._light_sets_arg(light_sets, spherical_sets)
+        out, fmt, stream = self._batch_tensor((len(a), len(light_sets)), W, H, format, out, stream)
+        return a, light_sets, (q, keep), out, fmt, stream
+
+    def render_views_light_sets_tensor(self, cams, W: int, H: int, light_sets, format="rgb", out=None, stream=None, **kw):
+        """render_views_light_sets_device into a torch tensor on cuda:<device>: (V, S, H, W, 3) f32, (V, S, 3, H, W) f32 or (V, S, H, W, 4)
+        u8 -- `out` (contiguous, of exactly that shape and dtype; validated before any call, ValueError) or a new tensor, rendered on
+        `stream` (default: torch.cuda.current_stream()).  Other keywords as render_views_light_sets.  Returns (tensor, stats dict)."""
+        a, light_sets, _, out, fmt, stream = self._views_light_sets_tensor(cams, W, H, light_sets, kw.get("spherical_sets"), format, out, stream)
+        st = self.render_views_light_sets_device(a, W, H, out.data_ptr(), light_sets, format=fmt, stream=stream.cuda_stream, **kw)
         return out, st
 
     def _soft_arg(self, spherical, units, samples: int, seed: int):
@@ -972,6 +1028,22 @@ class Scene:
         _check(
             lib().cgrt_enqueue_render_views_device(
                 self._h, _ptr(a) if len(a) else None, len(a), W, H, _ptr(lights), len(lights), q, max_level, C.c_void_p(out.data_ptr()), fmt,
+                C.c_void_p(stream.cuda_stream) if stream.cuda_stream else None, C.byref(t),
+            )
+        )  # fmt: skip
+        return out, t.value
+
+    def enqueue_render_views_light_sets_tensor(self, cams, W: int, H: int, light_sets, format="rgb", out=None, stream=None, spherical_sets=None,
+                                               units=None, samples: int = 200, seed: int = 0, max_level: int = 2):
+        """render_views_light_sets_tensor without waiting for the GPU (cgrt_enqueue_render_views_light_sets_device): same checks (ValueError
+        before any call), same bytes, the whole batch on `stream`.  With one camera it is the enqueued light-set batch.  Returns (tensor,
+        ticket); enqueue_stats(ticket) gives the stats dict."""
+        a, light_sets, (q, keep), out, fmt, stream = self._views_light_sets_tensor(cams, W, H, light_sets, spherical_sets, format, out, stream)
+        s, keep_s = self._light_sets_soft(spherical_sets, units, samples, seed)  # noqa: F841
+        t = C.c_uint64()
+        _check(
+            lib().cgrt_enqueue_render_views_light_sets_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, C.byref(q), s, max_level, C.c_void_p(out.data_ptr()), fmt,
                 C.c_void_p(stream.cuda_stream) if stream.cuda_stream else None, C.byref(t),
             )
         )  # fmt: skip

@@ -1625,15 +1625,19 @@ int cgrt_trace_primary_device(CgrtScene* s, const CgrtCamera* cam, int W, int H,
 // ---- multi-view frames (include/cgrt.h cgrt_*_views*) ----
 // The batch's own checks, all CGRT_E_ARG: NULL cams, nviews == 0, W or H <= 0, nviews * W * H > 0x7fffffff, more super-tiles than one
 // launch takes (make_views_frame).
-static int views_args(const CgrtCamera* cams, uint32_t nviews, int W, int H) {
-    if (!cams) return fail(CGRT_E_ARG, "cams is NULL");
-    if (nviews == 0) return fail(CGRT_E_ARG, "nviews must be at least 1");
-    if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+// The batch's size (views_args, views_light_sets_args; nviews > 0, W and H > 0): nviews * W * H and the super-tiles of all views.
+static int views_extent_args(uint32_t nviews, int W, int H) {
     if ((unsigned long long)nviews * (unsigned long long)W * (unsigned long long)H > 0x7fffffffull)
         return fail(CGRT_E_ARG, "batch too large: nviews*W*H exceeds 0x7fffffff");
     FrameDev F;
     if (!make_views_frame(W, H, nviews, 64, F)) return fail(CGRT_E_ARG, "batch too large: more than 2^18 64x64 super-tiles over all views");
     return CGRT_OK;
+}
+static int views_args(const CgrtCamera* cams, uint32_t nviews, int W, int H) {
+    if (!cams) return fail(CGRT_E_ARG, "cams is NULL");
+    if (nviews == 0) return fail(CGRT_E_ARG, "nviews must be at least 1");
+    if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+    return views_extent_args(nviews, W, H);
 }
 static std::vector<CameraDev> view_cameras(const CgrtCamera* cams, uint32_t nviews) {
     std::vector<CameraDev> v(nviews);
@@ -2348,6 +2352,9 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                             on, dc);
     };
     auto write_rgb = [&](bool with_child, unsigned long long cnt, float* frame) -> hipError_t {
+        if (sets && views)  // (frame (view, set) at view * nsets + set)
+            return launch_write_rgb_views_sets(lvl_of(0), sets_of(0), with_child ? sets_of(1) : nullptr, cnt, n, nsets, ipix.as<int>(), frame,
+                                               (unsigned long long)W * H, nullptr);
         if (sets)
             return launch_write_rgb_sets(lvl_of(0), sets_of(0), with_child ? sets_of(1) : nullptr, cnt, n, nsets, ipix.as<int>(), frame,
                                          (unsigned long long)W * H, nullptr);
@@ -2369,14 +2376,16 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             } else if (views) {  // (also clears every view's pixels)
                 HIP_TRY(launch_trace_primary_views_compact(s->dev, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(),
                                                            primary_hits, frame_rgb, nullptr));
-                st.primary_rays = npix;
+                st.primary_rays = (unsigned long long)W * H * nviews;
             } else {
                 HIP_TRY(launch_trace_primary_compact(s->dev, C, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
                                                      ipix.as<int>(), primary_hits, nullptr, cw_primary, frame_rgb));  // (also clears this rank's pixels)
-                if (nsets > 1)  // (the primary kernel clears set 0's frame; a pixel that misses is black in every set)
-                    HIP_TRY(hipMemsetAsync(frame_rgb + 3ull * W * H, 0, (npix - (unsigned long long)W * H) * 12, nullptr));
                 st.primary_rays = owned_pixels(F);
             }
+            // (light sets: the primary kernel clears the first nviews * W * H pixels of the frame buffer; the sets' scatter writes only the
+            // pixels that hit, and a pixel that misses is black in every set: the rest of the buffer is cleared here)
+            if (nsets > 1)
+                HIP_TRY(hipMemsetAsync(frame_rgb + 3ull * W * H * nviews, 0, (npix - (unsigned long long)W * H * nviews) * 12, nullptr));
             // Level 0's spawn does not wait for the host to learn how many primary rays hit: it is launched over every item of the
             // rank's frame and stops at the count it reads on the device, while the host fetches that count on a stream of its own
             // (behind the primary kernel only) to size the traversal launches that follow -- the host round trip (~25 us of an idle
@@ -2540,8 +2549,8 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipStreamWaitEvent(list->stream, aux.e1, 0));
     } else if (dout) {
         // The frame's last kernel is done (aux.e1 was waited for); the wait below only makes that ordering explicit on the caller's stream.
-        const ExportDev E = export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, views ? nviews : sets ? nsets : 0u, aa, rank, nranks,
-                                      packed);
+        const ExportDev E = export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, (views || sets) ? nviews * nsets : 0u, aa, rank,
+                                      nranks, packed);
         if (!s->export_done) HIP_TRY(hipEventCreateWithFlags(&s->export_done, hipEventDisableTiming));
         HIP_TRY(hipStreamWaitEvent(dout->stream, aux.e1, 0));
         HIP_TRY(launch_export_frame(E, dout->stream));
@@ -2765,10 +2774,8 @@ int cgrt_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nvie
 }
 
 // ---- one camera under a batch of light sets (render_impl, LightSetSrc; include/cgrt.h cgrt_render_light_sets*) ----
-// Every check of include/cgrt.h's list, all CGRT_E_ARG and before any device work; then *P holds the batch's plan.
-static int light_sets_args(const CgrtScene* s, const CgrtCamera* cam, int W, int H, const CgrtLightSets* sets, const CgrtSoftShadows* soft,
-                           int max_level, const void* out, LightSetSrc* P) {
-    if (!s || !cam || !sets || !out) return fail(CGRT_E_ARG, "NULL argument");
+// The sets' own rules (light_sets_args, views_light_sets_args): nsets, the offsets, the light arrays and the sampling parameters.
+static int sets_rules(const CgrtLightSets* sets, const CgrtSoftShadows* soft) {
     const uint32_t B = sets->nsets;
     if (B == 0 || B > 1024) return fail(CGRT_E_ARG, "nsets must be 1 .. 1024");
     const uint32_t* lo = sets->light_offsets;
@@ -2783,16 +2790,28 @@ static int light_sets_args(const CgrtScene* s, const CgrtCamera* cam, int W, int
     if (soft && (soft->spherical || soft->nspherical)) return fail(CGRT_E_ARG, "soft carries the sampling parameters only: its spherical lights must be NULL and 0");
     if (ns && (!soft || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
         return fail(CGRT_E_ARG, "spherical lights need soft: a unit-vector table and 1..2^24 samples");
+    return CGRT_OK;
+}
+// The plan's bounds for px items per level (W*H, or nviews*W*H): a level's shadow list holds up to px x (distinct positions) rays, its
+// soft-shadow counters px x (distinct keys), with 32-bit indices; the samples of a level stay below 2^37.
+static int sets_bounds(unsigned long long px, const LightSetSrc& P, const CgrtSoftShadows* soft) {
+    if (px * (P.points.size() / 6) > 0x7fffffffull) return fail(CGRT_E_ARG, "too many distinct point-light positions for the frame's 32-bit shadow list");
+    if (px * P.sph_index.size() > 0x7fffffffull || (!P.sph_index.empty() && px * P.sph_index.size() * soft->samples > 0x7fffffffull * 64))
+        return fail(CGRT_E_ARG, "too many distinct spherical lights for the frame's 32-bit soft-shadow lists");
+    return CGRT_OK;
+}
+// Every check of include/cgrt.h's list, all CGRT_E_ARG and before any device work; then *P holds the batch's plan.
+static int light_sets_args(const CgrtScene* s, const CgrtCamera* cam, int W, int H, const CgrtLightSets* sets, const CgrtSoftShadows* soft,
+                           int max_level, const void* out, LightSetSrc* P) {
+    if (!s || !cam || !sets || !out) return fail(CGRT_E_ARG, "NULL argument");
+    const int rc = sets_rules(sets, soft);
+    if (rc) return rc;
     if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
     if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
     const unsigned long long px = (unsigned long long)W * (unsigned long long)H;
     if (px > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large: W*H exceeds 0x7fffffff");
     plan_light_sets(*sets, *P);
-    // a level's shadow list holds up to W*H x (distinct positions) rays, its soft-shadow counters W*H x (distinct keys): 32-bit indices
-    if (px * (P->points.size() / 6) > 0x7fffffffull) return fail(CGRT_E_ARG, "too many distinct point-light positions for the frame's 32-bit shadow list");
-    if (px * P->sph_index.size() > 0x7fffffffull || (ns && px * P->sph_index.size() * soft->samples > 0x7fffffffull * 64))
-        return fail(CGRT_E_ARG, "too many distinct spherical lights for the frame's 32-bit soft-shadow lists");
-    return CGRT_OK;
+    return sets_bounds(px, *P, soft);
 }
 int cgrt_render_light_sets(CgrtScene* s, const CgrtCamera* cam, int W, int H, const CgrtLightSets* sets, const CgrtSoftShadows* soft, int max_level,
                            float* rgb, CgrtRenderStats* stats) {
@@ -2817,6 +2836,57 @@ int cgrt_render_light_sets_device(CgrtScene* s, const CgrtCamera* cam, int W, in
     if ((rc = check_device_span(s, d_out, extent * P.nsets, "d_out"))) return rc;
     return render_impl(s, cam, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false,
                        &D, nullptr, nullptr, &P);
+}
+
+// ---- nviews cameras under a batch of light sets (render_impl / enqueue_impl with a ViewSrc and a LightSetSrc; include/cgrt.h
+// cgrt_render_views_light_sets*) ----
+// Every check of include/cgrt.h's list, in its order, all CGRT_E_ARG and before any device work; then *P holds the batch's plan.
+static int views_light_sets_args(const CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
+                                 const CgrtSoftShadows* soft, int max_level, const void* out, LightSetSrc* P) {
+    if (!s || !cams || !sets || !out) return fail(CGRT_E_ARG, "NULL argument");
+    if (nviews == 0) return fail(CGRT_E_ARG, "nviews must be at least 1");
+    int rc = sets_rules(sets, soft);
+    if (rc) return rc;
+    if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+    if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
+    if ((rc = views_extent_args(nviews, W, H))) return rc;
+    const unsigned long long px = (unsigned long long)nviews * (unsigned long long)W * (unsigned long long)H;
+    plan_light_sets(*sets, *P);
+    if ((rc = sets_bounds(px, *P, soft))) return rc;
+    if (px * sets->nsets > 0x7fffffffull) return fail(CGRT_E_ARG, "batch too large: nviews*nsets*W*H exceeds 0x7fffffff");
+    return CGRT_OK;
+}
+// the device forms' checks (blocking and enqueued): D->pitch and D->view_bytes are set
+static int views_light_sets_device_args(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
+                                        const CgrtSoftShadows* soft, int max_level, void* d_out, int format, LightSetSrc* P, DeviceOut* D) {
+    int rc = views_light_sets_args(s, cams, nviews, W, H, sets, soft, max_level, d_out, P);
+    if (rc) return rc;
+    uint64_t extent = 0;
+    if ((rc = export_args(d_out, W, H, format, 0, &D->pitch, &extent))) return rc;
+    D->view_bytes = extent;  // (packed rows: one frame is exactly its extent; frame (v, s) is frame v * nsets + s)
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    return check_device_span(s, d_out, extent * nviews * P->nsets, "d_out");
+}
+int cgrt_render_views_light_sets(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
+                                 const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats) {
+    LightSetSrc P;
+    const int rc = views_light_sets_args(s, cams, nviews, W, H, sets, soft, max_level, rgb, &P);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    const ViewSrc V{cams, nviews};
+    return render_impl(s, nullptr, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, rgb, stats, nullptr, nullptr, false,
+                       nullptr, nullptr, &V, &P);
+}
+int cgrt_render_views_light_sets_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
+                                        const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats) {
+    LightSetSrc P;
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    const int rc = views_light_sets_device_args(s, cams, nviews, W, H, sets, soft, max_level, d_out, format, &P, &D);
+    if (rc) return rc;
+    const ViewSrc V{cams, nviews};
+    return render_impl(s, nullptr, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false,
+                       &D, nullptr, &V, &P);
 }
 
 // ---- getFinalColor of the caller's rays (main.cpp:298-310): level 0 of the wavefront from a ray list (render_impl, ListSrc) ----
@@ -2889,7 +2959,7 @@ int cgrt_shade_rays(CgrtScene* s, const CgrtRay* rays, uint64_t n, const float* 
 // scattered back by its pixel: the bytes are the blocking entry's.  The caller has checked the arguments (the blocking entries' checks).
 static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                         int max_level, int rank, int nranks, bool aa, const DeviceOut* dout, const ListSrc* list, const ViewSrc* views,
-                        hipStream_t stream, uint64_t* ticket) {
+                        hipStream_t stream, uint64_t* ticket, const LightSetSrc* sets = nullptr) {
     const int PW = W, PH = H;
     if (aa) {
         W *= 2;
@@ -2898,8 +2968,9 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> one_frame(s->render_mutex);
     const uint32_t nviews = views ? views->n : 1u;
-    const unsigned long long npix = list ? list->n : (unsigned long long)W * H * nviews;
-    const unsigned L = nlights, SL = soft ? soft->nspherical : 0;
+    const uint32_t nsets = sets ? sets->nsets : 1u;  // (light sets: always with views; frame (view, set) is frame view * nsets + set)
+    const unsigned long long npix = list ? list->n : (unsigned long long)W * H * nviews * nsets;
+    const unsigned L = nlights, SL = sets ? (unsigned)sets->sph_index.size() : soft ? soft->nspherical : 0;
     FrameDev F{};
     if (views) {
         if (!make_views_frame(W, H, nviews, trace_block(s->dev), F)) return fail(CGRT_E_ARG, "bad batch");
@@ -2922,7 +2993,7 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
     // the workspace of render_impl, sized for the worst case (WsBuf::alloc waits for the scene's frames before a buffer grows)
     WsBuf rays[3] = {{s, 0}, {s, 1}, {s, 21}}, hits[3] = {{s, 2}, {s, 3}, {s, 22}}, normals[3] = {{s, 4}, {s, 5}, {s, 23}},
           pix[3] = {{s, 6}, {s, 7}, {s, 24}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
-          sslot[2] = {{s, 12}, {s, 28}}, levels{s, 14}, drgb{s, 15}, dctr{s, 16}, dlit{s, 19}, dres{s, 30};
+          sslot[2] = {{s, 12}, {s, 28}}, levels{s, 14}, drgb{s, 15}, dctr{s, 16}, dlit{s, 19}, dres{s, 30}, dsets{s, 32};
     const int packed = aa && nranks > 1;
     const size_t res_bytes = packed ? (size_t)F.nst_rank * 1024 * 12 : (size_t)PW * PH * 12;
     const size_t dres_bytes = std::max<size_t>(res_bytes, (size_t)F.nst_rank * 1024 * 12);
@@ -2946,12 +3017,15 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
         if (aa) HIP_TRY(dres.alloc(dres_bytes));
         HIP_TRY(dctr.alloc(nctr * sizeof(uint32_t)));
         if (SL) HIP_TRY(dlit.alloc(n * SL * 4));
+        if (sets) HIP_TRY(dsets.alloc((size_t)(max_level > 0 ? max_level : 1) * n * nsets * 16));  // (every set's colours of every level)
     }
-    // the frame's tables, through the slot's pinned staging: the caller may reuse its arrays once the call returns
+    // the frame's tables, through the slot's pinned staging: the caller may reuse its arrays once the call returns (light sets: `lights` is
+    // the distinct positions, the spherical lights the distinct keys, and the sets' own table -- SetsDev's memory -- comes last)
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t o_lights = 0, o_slights = up16((size_t)L * 24), o_units = o_slights + up16((size_t)SL * 28),
                  o_spawn = o_units + up16(SL ? (size_t)soft->nunits * 12 : 0), o_views = o_spawn + up16(sizeof(SpawnDev)),
-                 table_bytes = o_views + (views ? (size_t)nviews * sizeof(CameraDev) : 0);
+                 o_sets = o_views + up16(views ? (size_t)nviews * sizeof(CameraDev) : 0),
+                 table_bytes = o_sets + (sets ? sets->table.size() * 4 : 0);
     if (slot.cap < table_bytes) {
         if (slot.pin) (void)hipHostFree(slot.pin);
         slot.pin = nullptr;
@@ -2972,8 +3046,20 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
     const float* const dl = reinterpret_cast<const float*>(tab + o_lights);
     if (L) std::memcpy(pin + o_lights, lights, (size_t)L * 24);
     SoftDev Q{};
+    SetsDev T{};
+    auto sets_of = [&](int level) { return dsets.as<float>() + (size_t)level * n * nsets * 4; };
+    if (sets) {
+        std::memcpy(pin + o_sets, sets->table.data(), sets->table.size() * 4);
+        const uint32_t* st = reinterpret_cast<const uint32_t*>(tab + o_sets);
+        T.point_off = st;
+        T.sph_off = st + nsets + 1;
+        T.point = reinterpret_cast<const float4*>(st + sets->point_at);
+        T.sph = reinterpret_cast<const float4*>(st + sets->sph_at);
+        T.nsets = nsets;
+        Q.set_index = st + 2 * ((size_t)nsets + 1);
+    }
     if (SL) {
-        std::memcpy(pin + o_slights, soft->spherical, (size_t)SL * 28);
+        std::memcpy(pin + o_slights, sets ? sets->spherical.data() : soft->spherical, (size_t)SL * 28);
         std::memcpy(pin + o_units, soft->unit_vectors, (size_t)soft->nunits * 12);
         Q.lights = reinterpret_cast<const float*>(tab + o_slights);
         Q.units = reinterpret_cast<const float*>(tab + o_units);
@@ -3038,6 +3124,8 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
                 HIP_TRY(launch_trace_primary_compact(s->dev, make_camera(*cam), F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
                                                      ipix.as<int>(), pair, stream, nullptr, frame_rgb,
                                                      reinterpret_cast<const SpawnDev*>(tab + o_spawn)));
+            if (nsets > 1)  // (as render_impl: the views' kernel cleared the first nviews * W * H pixels, a miss is black in every set)
+                HIP_TRY(hipMemsetAsync(frame_rgb + 3ull * W * H * nviews, 0, (npix - (unsigned long long)W * H * nviews) * 12, stream));
             const bool pairable = can_trace_pair(s->dev);
             for (int level = 0; level < max_level; level++) {
                 const int a = level % 3, b = (level + 1) % 3, q = level & 1;  // as render_impl's buffer sets
@@ -3067,16 +3155,30 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
                     HIP_TRY(launch_soft_shadow_strided(s->dev, Q, rays[a].as<float>(), hits[a].as<CgrtHitDev>(), cur_pix, n, count_of(level),
                                                        dlit.as<uint32_t>(), soft->closest_hit == 0, stream));
                 }
-                HIP_TRY(launch_shade_strided(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(),
-                                             sdist[q].as<float>(), sslot[q].as<int>(), n, mats, dl, L, Q.lights, SL, dlit.as<uint32_t>(), Q.samples,
-                                             lvl_of(level), stream, count_of(level)));
+                if (sets)
+                    HIP_TRY(launch_shade_sets_strided(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(),
+                                                      sdist[q].as<float>(), sslot[q].as<int>(), n, mats, L, SL, dlit.as<uint32_t>(), Q.samples, T,
+                                                      sets_of(level), n, stream, count_of(level)));
+                else
+                    HIP_TRY(launch_shade_strided(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(),
+                                                 sdist[q].as<float>(), sslot[q].as<int>(), n, mats, dl, L, Q.lights, SL, dlit.as<uint32_t>(), Q.samples,
+                                                 lvl_of(level), stream, count_of(level)));
             }
-            for (int level = max_level - 2; level >= 1; level--) HIP_TRY(launch_fold_strided(lvl_of(level), lvl_of(level + 1), n, stream, count_of(level)));
-            HIP_TRY(launch_write_rgb_strided(lvl_of(0), max_level >= 2 ? lvl_of(1) : nullptr, n, ipix.as<int>(), frame_rgb, stream, count_of(0)));
+            for (int level = max_level - 2; level >= 1; level--) {
+                if (sets)
+                    HIP_TRY(launch_fold_sets_strided(lvl_of(level), sets_of(level), sets_of(level + 1), n, n, nsets, stream, count_of(level)));
+                else
+                    HIP_TRY(launch_fold_strided(lvl_of(level), lvl_of(level + 1), n, stream, count_of(level)));
+            }
+            if (sets)
+                HIP_TRY(launch_write_rgb_views_sets_strided(lvl_of(0), sets_of(0), max_level >= 2 ? sets_of(1) : nullptr, n, n, nsets, ipix.as<int>(),
+                                                            frame_rgb, (unsigned long long)W * H, stream, count_of(0)));
+            else
+                HIP_TRY(launch_write_rgb_strided(lvl_of(0), max_level >= 2 ? lvl_of(1) : nullptr, n, ipix.as<int>(), frame_rgb, stream, count_of(0)));
         }
         if (aa) HIP_TRY(launch_resolve_aa(F, drgb.as<float>(), dres.as<float>(), packed, stream));
-        if (dout) HIP_TRY(launch_export_frame(export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, views ? nviews : 0u, aa, rank, nranks,
-                                                        packed), stream));
+        if (dout) HIP_TRY(launch_export_frame(export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, views ? nviews * nsets : 0u, aa, rank,
+                                                        nranks, packed), stream));
         HIP_TRY(hipMemcpyAsync(slot.pin_ctr, dctr.p, nctr * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     }
     HIP_TRY(hipEventRecord(slot.t1, stream));
@@ -3091,7 +3193,7 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
     slot.L = L;
     slot.SL = SL;
     slot.samples = SL ? soft->samples : 0;
-    slot.primary_rays = (n && max_level >= 1) ? (list ? n : views ? npix : owned_pixels(F)) : 0;
+    slot.primary_rays = (n && max_level >= 1) ? (list ? n : views ? (unsigned long long)W * H * nviews : owned_pixels(F)) : 0;
     if (ticket) *ticket = slot.ticket;
     return CGRT_OK;
 }
@@ -3111,6 +3213,16 @@ int cgrt_enqueue_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint3
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
     return enqueue_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream, ticket);
+}
+int cgrt_enqueue_render_views_light_sets_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
+                                                const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, uint64_t* ticket) {
+    LightSetSrc P;
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    const int rc = views_light_sets_device_args(s, cams, nviews, W, H, sets, soft, max_level, d_out, format, &P, &D);
+    if (rc) return rc;
+    const ViewSrc V{cams, nviews};
+    return enqueue_impl(s, nullptr, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream,
+                        ticket, &P);
 }
 int cgrt_enqueue_shade_rays_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                                    int max_level, float* d_rgb, void* stream, uint64_t* ticket) {

@@ -326,19 +326,12 @@ __global__ void k_write_rgb_strided(const float4* __restrict__ lvl0, const float
 // entry i is out[b * stride + i] = {colour, flags} (consecutive entries at consecutive addresses).  k_shade_sets computes what does not
 // depend on the set once per entry, then every set's sum in shade_entry's expression order (spherical lights first, :168-218, then the
 // point lights, :219-232), so that set b's colour is, bit for bit, what k_shade writes in set b's single frame.
-__global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_shade_sets(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
-                                                                 const float* __restrict__ normals, const CgrtHitDev* __restrict__ shits,
-                                                                 const float* __restrict__ sdist, const int* __restrict__ sslot,
-                                                                 unsigned long long n, const float* __restrict__ materials, unsigned npos,
-                                                                 unsigned nsph, const uint32_t* __restrict__ lit, unsigned samples, SetsDev T,
-                                                                 float4* __restrict__ out, unsigned long long stride,
-                                                                 const uint32_t* __restrict__ dcount) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (dcount) {  // (as k_shade: the grid covers the list's capacity)
-        const unsigned long long present = *dcount;
-        n = present < n ? present : n;
-    }
-    if (i >= n) return;
+// shade_sets_entry: entry i of k_shade_sets (and of k_shade_sets_strided, enqueued batches).
+__device__ __forceinline__ void shade_sets_entry(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits, const float* __restrict__ normals,
+                                                 const CgrtHitDev* __restrict__ shits, const float* __restrict__ sdist, const int* __restrict__ sslot,
+                                                 unsigned long long i, const float* __restrict__ materials, unsigned npos, unsigned nsph,
+                                                 const uint32_t* __restrict__ lit, unsigned samples, const SetsDev& T, float4* __restrict__ out,
+                                                 unsigned long long stride) {
     const bool hit = hits[i].hit != 0;
     F3 nrm = f3(0.f, 0.f, 0.f), pointOn = f3(0.f, 0.f, 0.f), kd = f3(0.f, 0.f, 0.f), ks = f3(0.f, 0.f, 0.f), refl = f3(0.f, 0.f, 0.f);
     float shininess = 1.0f;
@@ -399,18 +392,56 @@ __global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_shade_sets(const float* __
         out[(unsigned long long)b * stride + i] = out0;
     }
 }
-// fold_entry per set: set blockIdx.y's colours of this level (sets_lvl) += its colours of the next (child_sets) * ks, through the shared
-// link records lvl[2i+1] (main.cpp:262)
-__global__ void k_fold_sets(const float4* __restrict__ lvl, float4* __restrict__ sets_lvl, const float4* __restrict__ child_sets, unsigned long long n,
-                            unsigned long long stride) {
+__global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_shade_sets(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                                 const float* __restrict__ normals, const CgrtHitDev* __restrict__ shits,
+                                                                 const float* __restrict__ sdist, const int* __restrict__ sslot,
+                                                                 unsigned long long n, const float* __restrict__ materials, unsigned npos,
+                                                                 unsigned nsph, const uint32_t* __restrict__ lit, unsigned samples, SetsDev T,
+                                                                 float4* __restrict__ out, unsigned long long stride,
+                                                                 const uint32_t* __restrict__ dcount) {
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (dcount) {  // (as k_shade: the grid covers the list's capacity)
+        const unsigned long long present = *dcount;
+        n = present < n ? present : n;
+    }
     if (i >= n) return;
-    const unsigned long long o = (unsigned long long)blockIdx.y * stride;
+    shade_sets_entry(rays, hits, normals, shits, sdist, sslot, i, materials, npos, nsph, lit, samples, T, out, stride);
+}
+// fold_entry per set: the set's colours of this level (sets_lvl + o) += its colours of the next (child_sets + o) * ks, through the shared
+// link records lvl[2i+1] (main.cpp:262)
+__device__ __forceinline__ void fold_sets_entry(const float4* __restrict__ lvl, float4* __restrict__ sets_lvl, const float4* __restrict__ child_sets,
+                                                unsigned long long i, unsigned long long o) {
     const float4 a = sets_lvl[o + i], b = lvl[2 * i + 1];
     const int child = __float_as_int(b.w);
     if (!(__float_as_uint(a.w) & 1u) || (b.z <= 0.01f) || child < 0) return;  // no child: colour + 0 * ks = colour
     const float4 c = child_sets[o + (unsigned long long)child];             // a child that missed holds colour 0
     sets_lvl[o + i] = make_float4(a.x + c.x * b.x, a.y + c.y * b.y, a.z + c.z * b.z, a.w);
+}
+// set blockIdx.y of every entry
+__global__ void k_fold_sets(const float4* __restrict__ lvl, float4* __restrict__ sets_lvl, const float4* __restrict__ child_sets, unsigned long long n,
+                            unsigned long long stride) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fold_sets_entry(lvl, sets_lvl, child_sets, i, (unsigned long long)blockIdx.y * stride);
+}
+// write_rgb_entry's colour per set: the set's level-0 colour of entry i (sets0 + o), folded with level 1 when child_sets is given
+__device__ __forceinline__ float4 sets_colour0(const float4* __restrict__ lvl0, const float4* __restrict__ sets0, const float4* __restrict__ child_sets,
+                                               unsigned long long i, unsigned long long o) {
+    float4 a = sets0[o + i];
+    if (child_sets) {
+        const float4 b = lvl0[2 * i + 1];
+        const int child = __float_as_int(b.w);
+        if ((__float_as_uint(a.w) & 1u) && !(b.z <= 0.01f) && child >= 0) {
+            const float4 c = child_sets[o + (unsigned long long)child];
+            a = make_float4(a.x + c.x * b.x, a.y + c.y * b.y, a.z + c.z * b.z, a.w);
+        }
+    }
+    return a;
+}
+__device__ __forceinline__ void store_rgb(float* __restrict__ p, const float4 a) {
+    p[0] = a.x;
+    p[1] = a.y;
+    p[2] = a.z;
 }
 // write_rgb_entry per set: set blockIdx.y's level-0 colour (folded with level 1 when child_sets is given) goes to its own frame,
 // rgb[3 * (set * frame_pixels + pixel)]
@@ -421,20 +452,66 @@ __global__ void k_write_rgb_sets(const float4* __restrict__ lvl0, const float4* 
     if (i >= n) return;
     const long long pix = item_pixels[i];
     if (pix < 0) return;  // item outside the frame
-    const unsigned long long o = (unsigned long long)blockIdx.y * stride;
-    float4 a = sets0[o + i];
-    if (child_sets) {
-        const float4 b = lvl0[2 * i + 1];
-        const int child = __float_as_int(b.w);
-        if ((__float_as_uint(a.w) & 1u) && !(b.z <= 0.01f) && child >= 0) {
-            const float4 c = child_sets[o + (unsigned long long)child];
-            a = make_float4(a.x + c.x * b.x, a.y + c.y * b.y, a.z + c.z * b.z, a.w);
-        }
+    const float4 a = sets_colour0(lvl0, sets0, child_sets, i, (unsigned long long)blockIdx.y * stride);
+    store_rgb(rgb + 3ull * ((unsigned long long)blockIdx.y * frame_pixels + (unsigned long long)pix), a);
+}
+
+// ---- Multi-view light sets (cgrt_render_views_light_sets*): nviews cameras' ray trees under T.nsets sets ----
+// The lists are a multi-view frame's (pixel = view * view_pixels + in-view pixel); the shading, the folds and the shadow answers are the
+// light sets' kernels above, unchanged.  Only the scatter differs: frame (view, set) is frame number view * nsets + set of the batch, so
+// set s's colour of a pixel goes to rgb[3 * ((view * nsets + s) * view_pixels + in-view pixel)] -- the (V, S, H, W) order of the caller's
+// output, which the export then writes as V * S frames back to back.
+__device__ __forceinline__ unsigned long long views_sets_pixel(unsigned long long pix, unsigned set, unsigned nsets, unsigned long long view_pixels) {
+    const unsigned long long v = pix / view_pixels;
+    return (v * nsets + set) * view_pixels + (pix - v * view_pixels);
+}
+// k_write_rgb_sets for a multi-view batch: set blockIdx.y of every entry
+__global__ void k_write_rgb_views_sets(const float4* __restrict__ lvl0, const float4* __restrict__ sets0, const float4* __restrict__ child_sets,
+                                       unsigned long long n, unsigned long long stride, const int* __restrict__ item_pixels, float* __restrict__ rgb,
+                                       unsigned long long view_pixels) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long pix = item_pixels[i];
+    if (pix < 0) return;  // item outside the frame
+    const float4 a = sets_colour0(lvl0, sets0, child_sets, i, (unsigned long long)blockIdx.y * stride);
+    store_rgb(rgb + 3ull * views_sets_pixel((unsigned long long)pix, blockIdx.y, gridDim.y, view_pixels), a);
+}
+// The count-driven forms (enqueued batches; see k_spawn_strided): a capped grid strides over the *dcount entries present, and each entry
+// handles every set, in the one-pass kernels' expressions.
+__global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_shade_sets_strided(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                                         const float* __restrict__ normals, const CgrtHitDev* __restrict__ shits,
+                                                                         const float* __restrict__ sdist, const int* __restrict__ sslot,
+                                                                         unsigned long long n, const float* __restrict__ materials, unsigned npos,
+                                                                         unsigned nsph, const uint32_t* __restrict__ lit, unsigned samples, SetsDev T,
+                                                                         float4* __restrict__ out, unsigned long long stride,
+                                                                         const uint32_t* __restrict__ dcount) {
+    const unsigned long long present = *dcount;
+    n = present < n ? present : n;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
+        shade_sets_entry(rays, hits, normals, shits, sdist, sslot, i, materials, npos, nsph, lit, samples, T, out, stride);
+}
+__global__ void k_fold_sets_strided(const float4* __restrict__ lvl, float4* __restrict__ sets_lvl, const float4* __restrict__ child_sets,
+                                    unsigned long long n, unsigned long long stride, unsigned nsets, const uint32_t* __restrict__ dcount) {
+    const unsigned long long present = *dcount;
+    n = present < n ? present : n;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
+        for (unsigned b = 0; b < nsets; b++) fold_sets_entry(lvl, sets_lvl, child_sets, i, (unsigned long long)b * stride);
+}
+__global__ void k_write_rgb_views_sets_strided(const float4* __restrict__ lvl0, const float4* __restrict__ sets0, const float4* __restrict__ child_sets,
+                                               unsigned long long n, unsigned long long stride, unsigned nsets, const int* __restrict__ item_pixels,
+                                               float* __restrict__ rgb, unsigned long long view_pixels, const uint32_t* __restrict__ dcount) {
+    const unsigned long long present = *dcount;
+    n = present < n ? present : n;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const long long pix = item_pixels[i];
+        if (pix < 0) continue;  // item outside the frame
+        for (unsigned b = 0; b < nsets; b++)
+            store_rgb(rgb + 3ull * views_sets_pixel((unsigned long long)pix, b, nsets, view_pixels),
+                      sets_colour0(lvl0, sets0, child_sets, i, (unsigned long long)b * stride));
     }
-    float* p = rgb + 3ull * ((unsigned long long)blockIdx.y * frame_pixels + (unsigned long long)pix);
-    p[0] = a.x;
-    p[1] = a.y;
-    p[2] = a.z;
 }
 
 // The reference's antiAliasing branch (main.cpp:663-687): pixel (x, y) of the W x H frame is resolved from the sub-samples
@@ -612,6 +689,15 @@ hipError_t launch_write_rgb_sets(const float* lvl0, const float* sets0, const fl
     return hipGetLastError();
 }
 
+hipError_t launch_write_rgb_views_sets(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n, unsigned long long stride,
+                                       unsigned nsets, const int* item_pixels, float* rgb, unsigned long long view_pixels, hipStream_t s) {
+    if (n && nsets)
+        hipLaunchKernelGGL(k_write_rgb_views_sets, dim3(grid_for(n, 256), nsets), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
+                           reinterpret_cast<const float4*>(sets0), reinterpret_cast<const float4*>(child_sets), n, stride, item_pixels, rgb,
+                           view_pixels);
+    return hipGetLastError();
+}
+
 // the count-driven forms: at most strided_waves() waves per launch (trace_kernels.hip), whatever the capacity n
 static inline unsigned strided_grid(unsigned long long n, unsigned block) {
     const unsigned cap = (unsigned)std::max<unsigned long long>(1ull, (unsigned long long)strided_waves() * 64ull / block);
@@ -646,6 +732,31 @@ hipError_t launch_write_rgb_strided(const float* lvl0, const float* child_lvl, u
     if (n)
         hipLaunchKernelGGL(k_write_rgb_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
                            reinterpret_cast<const float4*>(child_lvl), n, item_pixels, rgb, dcount);
+    return hipGetLastError();
+}
+
+hipError_t launch_shade_sets_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
+                                     const int* sslot, unsigned long long n, const float* materials, unsigned npos, unsigned nsph, const uint32_t* lit,
+                                     unsigned samples, const SetsDev& T, float* out, unsigned long long stride, hipStream_t s, const uint32_t* dcount) {
+    if (n)
+        hipLaunchKernelGGL(k_shade_sets_strided, dim3(strided_grid(n, CGRT_SHADE_BLOCK)), dim3(CGRT_SHADE_BLOCK), 0, s, rays, hits, normals, shits, sdist,
+                           sslot, n, materials, npos, nsph, lit, samples, T, reinterpret_cast<float4*>(out), stride, dcount);
+    return hipGetLastError();
+}
+hipError_t launch_fold_sets_strided(const float* lvl, float* sets_lvl, const float* child_sets, unsigned long long n, unsigned long long stride,
+                                    unsigned nsets, hipStream_t s, const uint32_t* dcount) {
+    if (n && nsets)
+        hipLaunchKernelGGL(k_fold_sets_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl),
+                           reinterpret_cast<float4*>(sets_lvl), reinterpret_cast<const float4*>(child_sets), n, stride, nsets, dcount);
+    return hipGetLastError();
+}
+hipError_t launch_write_rgb_views_sets_strided(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n,
+                                               unsigned long long stride, unsigned nsets, const int* item_pixels, float* rgb,
+                                               unsigned long long view_pixels, hipStream_t s, const uint32_t* dcount) {
+    if (n && nsets)
+        hipLaunchKernelGGL(k_write_rgb_views_sets_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
+                           reinterpret_cast<const float4*>(sets0), reinterpret_cast<const float4*>(child_sets), n, stride, nsets, item_pixels, rgb,
+                           view_pixels, dcount);
     return hipGetLastError();
 }
 

@@ -25,7 +25,8 @@ struct SoftDev {
     uint32_t nlights, samples, nunits, seed, level;
     uint32_t view_pixels;  // 0, or W * H of a multi-view frame: samples are drawn with item_pixels[item] % view_pixels (k_soft_shadow)
     // light sets (k_soft_shadow_sets): lights are the batch's distinct (position, radius, in-set index) keys, and key l draws as light
-    // set_index[l] -- its index within its own set, as that set's single frame draws it.  NULL otherwise.
+    // set_index[l] -- its index within its own set, as that set's single frame draws it.  NULL otherwise.  With view_pixels as well (a
+    // multi-view batch of light sets, k_soft_shadow_views_sets / k_soft_shadow_sets_strided) both rules hold.
     const uint32_t* set_index;
 };
 
@@ -114,7 +115,8 @@ hipError_t launch_trace_shadow_strided(const SceneDev& S, const float* rays, con
 hipError_t launch_trace_pair_strided(const SceneDev& S, const float* srays, const float* sdist, unsigned long long ns, CgrtHitDev* shits,
                                      const uint32_t* sdcount, unsigned sdmul, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals,
                                      const uint32_t* dcount, hipStream_t stream);
-// items: the first *dcount (<= nitems) entries of the level's list (k_soft_shadow_strided)
+// items: the first *dcount (<= nitems) entries of the level's list (k_soft_shadow_strided; Q.set_index: k_soft_shadow_sets_strided, which
+// needs Q.view_pixels)
 hipError_t launch_soft_shadow_strided(const SceneDev& S, const SoftDev& Q, const float* rays, const CgrtHitDev* hits, const int* item_pixels,
                                       unsigned long long nitems, const uint32_t* dcount, uint32_t* lit, int anyhit, hipStream_t stream);
 // shading wavefront (shade_kernels.hip); every level is a compact list of live paths
@@ -156,6 +158,19 @@ hipError_t launch_fold_sets(const float* lvl, float* sets_lvl, const float* chil
                             hipStream_t s);
 hipError_t launch_write_rgb_sets(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n, unsigned long long stride,
                                  unsigned nsets, const int* item_pixels, float* rgb, unsigned long long frame_pixels, hipStream_t s);
+// multi-view light sets (cgrt_render_views_light_sets*): item_pixels are a multi-view frame's (view * view_pixels + in-view pixel), and set
+// s's colour of a pixel of view v goes to frame v * nsets + s: rgb + 3 * ((v * nsets + s) * view_pixels + in-view pixel)
+hipError_t launch_write_rgb_views_sets(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n, unsigned long long stride,
+                                       unsigned nsets, const int* item_pixels, float* rgb, unsigned long long view_pixels, hipStream_t s);
+// the count-driven forms of the light sets' kernels (enqueued batches): n is the list's capacity, *dcount its length
+hipError_t launch_shade_sets_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
+                                     const int* sslot, unsigned long long n, const float* materials, unsigned npos, unsigned nsph, const uint32_t* lit,
+                                     unsigned samples, const SetsDev& T, float* out, unsigned long long stride, hipStream_t s, const uint32_t* dcount);
+hipError_t launch_fold_sets_strided(const float* lvl, float* sets_lvl, const float* child_sets, unsigned long long n, unsigned long long stride,
+                                    unsigned nsets, hipStream_t s, const uint32_t* dcount);
+hipError_t launch_write_rgb_views_sets_strided(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n,
+                                               unsigned long long stride, unsigned nsets, const int* item_pixels, float* rgb,
+                                               unsigned long long view_pixels, hipStream_t s, const uint32_t* dcount);
 // the anti-aliased frame (main.cpp:663-687) from the 2W x 2H sub-sample frame `sub` of F: see k_resolve_aa (shade_kernels.hip).
 // out: F.nst_rank * 1024 * 3 floats (packed) or (F.W / 2) * (F.H / 2) * 3 floats
 hipError_t launch_resolve_aa(const FrameDev& F, const float* sub, float* out, int packed, hipStream_t s);

@@ -732,6 +732,15 @@ __global__ CGRT_LB void k_soft_shadow_sets(SceneDev S, SoftDev Q, const float* _
     const unsigned long long g = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     soft_shadow_thread<ANYHIT, FAST, false, false, true>(S, Q, rays, hits, item_pixels, g, nthreads, lit, s_lds);
 }
+// k_soft_shadow_sets for a multi-view batch of light sets (cgrt_render_views_light_sets*): VIEWS and SETS together -- sample smp of a key
+// draws with the in-view pixel and the key's in-set index, as the single frame of that view under that set draws it
+template <bool ANYHIT, bool FAST>
+__global__ CGRT_LB void k_soft_shadow_views_sets(SceneDev S, SoftDev Q, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                 const int* __restrict__ item_pixels, unsigned long long nthreads, uint32_t* __restrict__ lit) {
+    extern __shared__ uint32_t s_lds[];
+    const unsigned long long g = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    soft_shadow_thread<ANYHIT, FAST, false, true, true>(S, Q, rays, hits, item_pixels, g, nthreads, lit, s_lds);
+}
 // The count-driven form (enqueued frames): the level's items are the first *dcount (<= nitems, the list's capacity) entries, known only on
 // the device; a capped grid strides over their present x nlights x samples threads, gridDim.x * blockDim.x at a time.  Thread g draws
 // and counts what it draws in k_soft_shadow: the draws hash the pixel and the level, never the grid.
@@ -745,6 +754,19 @@ __global__ CGRT_LB void k_soft_shadow_strided(SceneDev S, SoftDev Q, const float
         const unsigned long long nthreads = (present < nitems ? present : nitems) * Q.nlights * Q.samples, base = (unsigned long long)b * blockDim.x;
         if (base >= nthreads) break;
         soft_shadow_thread<ANYHIT, FAST, false, VIEWS>(S, Q, rays, hits, item_pixels, base + threadIdx.x, nthreads, lit, s_lds);
+    }
+}
+// k_soft_shadow_strided for an enqueued batch of light sets (always a multi-view batch, one view or more): k_soft_shadow_views_sets' threads
+template <bool ANYHIT, bool FAST>
+__global__ CGRT_LB void k_soft_shadow_sets_strided(SceneDev S, SoftDev Q, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                   const int* __restrict__ item_pixels, unsigned long long nitems, const uint32_t* __restrict__ dcount,
+                                                   uint32_t* __restrict__ lit) {
+    extern __shared__ uint32_t s_lds[];
+    for (unsigned b = blockIdx.x;; b += gridDim.x) {
+        const unsigned long long present = *(const volatile uint32_t*)dcount;
+        const unsigned long long nthreads = (present < nitems ? present : nitems) * Q.nlights * Q.samples, base = (unsigned long long)b * blockDim.x;
+        if (base >= nthreads) break;
+        soft_shadow_thread<ANYHIT, FAST, false, true, true>(S, Q, rays, hits, item_pixels, base + threadIdx.x, nthreads, lit, s_lds);
     }
 }
 
@@ -1030,6 +1052,14 @@ hipError_t launch_soft_shadow_strided(const SceneDev& S, const SoftDev& Q, const
     const unsigned long long full = (nthreads + block - 1) / block;
     const unsigned grid = strided_blocks((unsigned)std::min<unsigned long long>(full, 0x7fffffffull), block);
     const bool fast = S.fast_root != REF_NONE, views = Q.view_pixels != 0;
+    if (Q.set_index) {  // an enqueued batch of light sets (k_soft_shadow_sets_strided; its items are always a multi-view frame's)
+        if (!views) return hipErrorInvalidValue;
+        if (anyhit)
+            CGRT_LAUNCH2(k_soft_shadow_sets_strided, true, fast, grid, block, stream, S, Q, rays, hits, item_pixels, nitems, dcount, lit);
+        else
+            CGRT_LAUNCH2(k_soft_shadow_sets_strided, false, fast, grid, block, stream, S, Q, rays, hits, item_pixels, nitems, dcount, lit);
+        return hipGetLastError();
+    }
 #define CGRT_SOFT_STRIDED(A, F, V)                                                                                                                 \
     hipLaunchKernelGGL((k_soft_shadow_strided<A, F, V>), dim3(grid), dim3(block), lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nitems, \
                        dcount, lit)
@@ -1135,6 +1165,13 @@ hipError_t launch_soft_shadow(const SceneDev& S, const SoftDev& Q, const float* 
     const unsigned long long blocks = (nthreads + block - 1) / block;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     const bool fast = S.fast_root != REF_NONE;
+    if (Q.set_index && Q.view_pixels) {  // a multi-view light-set batch's distinct keys (k_soft_shadow_views_sets)
+        if (anyhit)
+            CGRT_LAUNCH2(k_soft_shadow_views_sets, true, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
+        else
+            CGRT_LAUNCH2(k_soft_shadow_views_sets, false, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
+        return hipGetLastError();
+    }
     if (Q.set_index) {  // a light-set batch's distinct keys (k_soft_shadow_sets)
         if (anyhit)
             CGRT_LAUNCH2(k_soft_shadow_sets, true, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);

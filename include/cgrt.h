@@ -494,6 +494,54 @@ int cgrt_enqueue_stats(CgrtScene* scene, uint64_t ticket, CgrtRenderStats* stats
  * value of CGRT_STRIDED_WAVES (64 .. 2^24), read once per process. */
 int cgrt_debug_strided_waves(void);
 
+/* Multi-view light sets: V = nviews cameras under S = sets->nsets light setups in one call -- the two batch
+ * families above together, for a relighting rig (every camera under every lighting) or a Lights-panel edit previewed from several
+ * viewpoints.  The cameras share W x H, max_level and the soft-shadow sampling parameters; the sets are a CgrtLightSets as for
+ * cgrt_render_light_sets, `soft` with its rules (sampling parameters only).  With nviews = 1 these are light sets for one camera, and the
+ * enqueued form is the enqueued light-set batch.
+ * Layout: frame (v, s) is frame number v*S + s of the batch, so its pixel (x, y) is element ((v*S + s)*H + y)*W + x.  The host form
+ * writes V*S*W*H*3 floats; the device forms write frame (v, s) at d_out + (v*S + s) * (the packed frame bytes of `format`): a contiguous
+ * (V, S, H, W, 3) f32, (V, S, 3, H, W) f32 or (V, S, H, W, 4) u8 array.
+ * Bytes: frame (v, s) is, bit for bit, what cgrt_render_soft (cgrt_render without spherical lights) returns for cams[v] under set s's
+ * lights: spherical-light sample smp draws with the in-view pixel p = y*W + x, the level and l = the light's index WITHIN ITS SET (the
+ * rules of both families).  So out[v] is the byte image of cgrt_render_light_sets(cams[v], sets), and out[:, s] that of
+ * cgrt_render_views(cams, set s's lights).
+ * What is shared: the primary launch, every level's spawn and every mirror list run once for all views, as in cgrt_render_views; shadow
+ * rays run once per hit and per DISTINCT point-light position over all sets, soft-shadow counts once per hit and per distinct (position,
+ * radius, in-set index) key, compared by bit pattern as cgrt_render_light_sets compares them; light colour enters only the per-set Phong
+ * terms.
+ * stats: primary_rays = V*W*H when max_level >= 1; reflection_rays and levels those of cgrt_render_views(cams); shadow_rays = (hits over all
+ * views and levels) x (distinct positions); soft_shadow_rays = (hits over all views and levels) x (distinct keys) x samples.  The four ray
+ * counts are the sums over v of cgrt_render_light_sets(cams[v], sets)'s, levels their maximum; device_ms covers the whole batch.
+ * Checks, all CGRT_E_ARG and before any device work, in this order: NULL scene / cams / sets / output; nviews == 0; the sets' rules of
+ * cgrt_render_light_sets (nsets 1 .. 1024, light_offsets NULL, offsets that do not start at 0 or that decrease, lights or spherical NULL
+ * while its count is > 0, a soft with spherical lights of its own, spherical lights without a valid soft); W or H <= 0; max_level outside
+ * 0..16; V*W*H > 0x7fffffff or more than 2^18 64x64 super-tiles over all views; V*W*H x (distinct point-light positions) or V*W*H x
+ * (distinct spherical keys) above 0x7fffffff, or V*W*H x (distinct keys) x samples above 64 x 0x7fffffff; V*S*W*H > 0x7fffffff; (device forms)
+ * unknown format, d_out not 4-byte aligned.  Then a host-only scene -> CGRT_E_NO_DEVICE; then (device forms) the V*S frames' bytes not all
+ * device memory of the scene's device (as cgrt_render_device checks d_out) -> CGRT_E_ARG.  A batch that fails writes nothing to the output
+ * and leaves the scene usable.
+ * Scene state: no entry reads or writes the scene's frame prediction or frame hints.  The blocking forms take the exactly sized path.
+ * Memory: beyond a multi-view frame's workspace, max_level x (the batch's items, about V*W*H) x S x 16 bytes of per-set colours and
+ * V*S*W*H*12 bytes of frames -- at 256x256, V = S = 16 and max_level 4 that is about 1.07 GB and 0.2 GB (arithmetic, not a measurement).
+ * Not batched: anti-aliasing, rank / nranks, replicas on several devices, per-view frame sizes, prediction for batches; there is no C++
+ * mirror (no reference function takes several cameras or light sets). */
+/* cgrt_render_views_light_sets: rgb (host) holds the V*S frames in the layout above.  Synchronous. */
+int cgrt_render_views_light_sets(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
+                                 const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats);
+/* cgrt_render_views_light_sets_device: stream and export-event rules of cgrt_render_views_device: the call blocks until the batch's kernels
+ * are done and returns with the export of all V*S frames enqueued on `stream`, behind everything the caller enqueued there before. */
+int cgrt_render_views_light_sets_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
+                                        const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream,
+                                        CgrtRenderStats* stats);
+/* cgrt_enqueue_render_views_light_sets_device: the device form without waiting for the GPU, under the rules of the enqueued frames above
+ * (the same bytes; the whole batch on `stream`; a wait only when the workspace grows or all 8 ticket slots are in flight).  The cameras,
+ * the sets' plan table, the distinct light tables and the unit vectors are copied through the ticket slot's pinned staging, so the caller
+ * may reuse every host array at once.  cgrt_enqueue_stats(ticket) returns the blocking call's ray counts and levels. */
+int cgrt_enqueue_render_views_light_sets_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H,
+                                                const CgrtLightSets* sets, const CgrtSoftShadows* soft, int max_level, void* d_out,
+                                                int format, void* stream, uint64_t* ticket);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
