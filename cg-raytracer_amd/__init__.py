@@ -73,6 +73,25 @@ class LightSets(C.Structure):  # CgrtLightSets: CSR arrays, one offset array per
                 ("spherical_offsets", C.c_void_p)]
 
 
+AOV_NAMES = ("depth", "normal", "position", "albedo", "prim_id", "material_id", "mask")
+
+
+class AovOut(C.Structure):  # CgrtAovOut: device pointers of the wanted geometry-buffer planes (NULL: not wanted)
+    _fields_ = [(k, C.c_void_p) for k in AOV_NAMES] + [("chw", C.c_int)]
+
+    @staticmethod
+    def from_pointers(ptrs, chw: bool = False) -> "AovOut":
+        """From a dict plane name -> device address (0 / None / absent: not wanted).  ValueError for an unknown name."""
+        a = AovOut()
+        for k, p in ptrs.items():
+            if k not in AOV_NAMES:
+                raise ValueError(f"unknown geometry buffer {k!r}; the planes are {AOV_NAMES}")
+            if p:
+                setattr(a, k, p)
+        a.chw = 1 if chw else 0
+        return a
+
+
 class Camera(C.Structure):
     _fields_ = [
         ("look_at", C.c_float * 3),
@@ -113,7 +132,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -200,6 +219,10 @@ def lib() -> C.CDLL:
                                              vp, C.POINTER(u64)]
     L.cgrt_enqueue_render_views_device.argtypes = [vp, vp, u32, i32, i32, vp, u32, C.POINTER(SoftShadows), i32, vp, i32, vp, C.POINTER(u64)]
     L.cgrt_enqueue_shade_rays_device.argtypes = [vp, vp, u64, vp, u32, C.POINTER(SoftShadows), i32, vp, vp, C.POINTER(u64)]
+    L.cgrt_render_aov_device.argtypes = L.cgrt_render_device.argtypes + [C.POINTER(AovOut)]
+    L.cgrt_render_views_aov_device.argtypes = L.cgrt_render_views_device.argtypes + [C.POINTER(AovOut)]
+    L.cgrt_enqueue_render_aov_device.argtypes = L.cgrt_enqueue_render_device.argtypes + [C.POINTER(AovOut)]
+    L.cgrt_enqueue_render_views_aov_device.argtypes = L.cgrt_enqueue_render_views_device.argtypes + [C.POINTER(AovOut)]
     L.cgrt_enqueue_stats.argtypes = [vp, u64, C.POINTER(RenderStats)]
     L.cgrt_debug_strided_waves.argtypes = []
     L.cgrt_occluded.argtypes = [vp, vp, u64, vp]
@@ -1074,6 +1097,161 @@ class Scene:
         st = RenderStats()
         _check(lib().cgrt_enqueue_stats(self._h, int(ticket), C.byref(st)))
         return {k: getattr(st, k) for k, _ in st._fields_}
+
+    # ---- geometry buffers of a device frame (include/cgrt.h CgrtAovOut, cgrt_*_aov_device) ----
+    @staticmethod
+    def _aov_arg(aov, chw):
+        """The CgrtAovOut argument: None (NULL), an AovOut, or a dict plane name -> device address."""
+        if aov is None:
+            return None
+        return C.byref(aov if isinstance(aov, AovOut) else AovOut.from_pointers(aov, chw))
+
+    def render_aov_device(self, cam, W: int, H: int, d_out_ptr: int, aov, chw: bool = False, format="rgb", row_bytes: int = 0, stream: int = 0,
+                          aa: bool = False, lights=None, max_level: int = 2, spherical=None, units=None, samples: int = 200, seed: int = 0,
+                          rank: int = 0, nranks: int = 1) -> dict:
+        """cgrt_render_aov_device: render_device, and the geometry buffers of the frame's primary rays -- `aov`, a dict plane name (AOV_NAMES)
+        -> device address of a packed plane: (H, W) f32 depth, u32 prim_id, i32 material_id, u8 mask; (H, W, 3) f32 normal, position, albedo,
+        or (3, H, W) with chw; (2H, 2W) with aa -- written by the same call from the frame's own level 0.  Raw integers.  Returns stats."""
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        st = RenderStats()
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
+        _check(
+            lib().cgrt_render_aov_device(
+                self._h, C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, 1 if aa else 0, rank, nranks,
+                C.c_void_p(d_out_ptr) if d_out_ptr else None, _frame_format(format), int(row_bytes), C.c_void_p(stream) if stream else None,
+                C.byref(st), self._aov_arg(aov, chw),
+            )
+        )  # fmt: skip
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def render_views_aov_device(self, cams, W: int, H: int, d_out_ptr: int, aov, chw: bool = False, format="rgb", stream: int = 0, lights=None,
+                                max_level: int = 2, spherical=None, units=None, samples: int = 200, seed: int = 0) -> dict:
+        """cgrt_render_views_aov_device: render_views_device, and the views' geometry buffers with a leading view axis: (B, H, W),
+        (B, H, W, 3) or (B, 3, H, W).  Raw integers, as render_aov_device.  Returns stats."""
+        a = camera_array(cams)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        st = RenderStats()
+        _check(
+            lib().cgrt_render_views_aov_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, _ptr(lights), len(lights), q, max_level,
+                C.c_void_p(d_out_ptr) if d_out_ptr else None, _frame_format(format), C.c_void_p(stream) if stream else None, C.byref(st),
+                self._aov_arg(aov, chw),
+            )
+        )  # fmt: skip
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def _aov_plan(self, lead, W, H, aovs, chw, aov_out):
+        """The checks of `aovs` / `aov_out` (ValueError, before any call): the planes as a dict name -> (shape, dtype, caller's tensor or
+        None), shape lead + (H, W) (+ (3,), or lead + (3, H, W) with chw); a caller's tensor is contiguous, of exactly that shape and
+        dtype, on the scene's device."""
+        import torch
+
+        names = (aovs,) if isinstance(aovs, str) else tuple(aovs)
+        if not names or len(set(names)) != len(names) or any(k not in AOV_NAMES for k in names):
+            raise ValueError(f"aovs must be a non-empty subset of {AOV_NAMES} without repeats, not {aovs!r}")
+        aov_out = {} if aov_out is None else aov_out
+        if not isinstance(aov_out, dict) or any(k not in names for k in aov_out):
+            raise ValueError(f"aov_out must be a dict of tensors whose keys are among the requested planes {names}")
+        lead = tuple(lead)
+        one, three = lead + (H, W), lead + ((3, H, W) if chw else (H, W, 3))
+        plan = {}
+        for k in names:
+            shape = three if k in ("normal", "position", "albedo") else one
+            dtype = torch.uint8 if k == "mask" else torch.int32 if k in ("prim_id", "material_id") else torch.float32
+            t = aov_out.get(k)
+            if t is not None:
+                if not isinstance(t, torch.Tensor):
+                    raise ValueError(f"aov_out[{k!r}] must be a torch tensor")
+                if t.dtype != dtype:
+                    raise ValueError(f"aov_out[{k!r}] has dtype {t.dtype}, the plane needs {dtype}")
+                if t.shape != shape:
+                    raise ValueError(f"aov_out[{k!r}] has shape {tuple(t.shape)}, the plane needs {shape}")
+                if not t.is_contiguous():
+                    raise ValueError(f"aov_out[{k!r}] must be contiguous")
+                if not t.is_cuda or t.get_device() != self.device:
+                    raise ValueError(f"aov_out[{k!r}] is on {t.device}, the scene on cuda:{self.device}")
+            plan[k] = (shape, dtype, t)
+        return plan
+
+    def _aov_tensors(self, plan, stream, zero=False):
+        """The planes of an _aov_plan as tensors: the caller's, or new ones allocated on `stream` (zeros when `zero`: other ranks' pixels
+        are not written)."""
+        import torch
+
+        if all(t is not None for _, _, t in plan.values()):
+            return {k: t for k, (_, _, t) in plan.items()}
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.stream(stream):
+            return {k: t if t is not None else (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=dev)
+                    for k, (shape, dtype, t) in plan.items()}
+
+    def render_aov_tensor(self, cam, W: int, H: int, aovs=AOV_NAMES, chw: bool = False, format="rgb", out=None, aov_out=None, stream=None, **kw):
+        """render_tensor, and the frame's geometry buffers as torch tensors on cuda:<device>: `aovs` is a subset of AOV_NAMES; depth f32,
+        prim_id i32 (the u32 id's bits: 0xffffffff, a miss, reads -1), material_id i32, mask u8 of shape (H, W); normal, position, albedo f32
+        of shape (H, W, 3), or (3, H, W) with chw; (2H, 2W) with aa=True (the sub-sample frame).  aov_out: dict name -> caller's tensor for
+        some or all of them (validated before any call, ValueError).  Other keywords as render_device.  Returns (tensor, stats, planes)."""
+        k = 2 if kw.get("aa") else 1
+        nranks = kw.get("nranks", 1)
+        plan = self._aov_plan((), k * W, k * H, aovs, chw, aov_out)
+        out, fmt, row_bytes, stream = self._frame_tensor(W, H, format, out, stream, nranks)
+        planes = self._aov_tensors(plan, stream, zero=nranks > 1)
+        st = self.render_aov_device(cam, W, H, out.data_ptr(), {n: t.data_ptr() for n, t in planes.items()}, chw=chw, format=fmt,
+                                    row_bytes=row_bytes, stream=stream.cuda_stream, **kw)
+        return out, st, planes
+
+    def render_views_aov_tensor(self, cams, W: int, H: int, aovs=AOV_NAMES, chw: bool = False, format="rgb", out=None, aov_out=None, stream=None,
+                                **kw):
+        """render_views_tensor, and the views' geometry buffers: (B, H, W), (B, H, W, 3) or (B, 3, H, W) tensors, as render_aov_tensor.
+        Returns (tensor, stats, planes)."""
+        plan = self._aov_plan((len(camera_array(cams)),), W, H, aovs, chw, aov_out)
+        a, out, fmt, stream = self._views_tensor(cams, W, H, format, out, stream)
+        planes = self._aov_tensors(plan, stream)
+        st = self.render_views_aov_device(a, W, H, out.data_ptr(), {n: t.data_ptr() for n, t in planes.items()}, chw=chw, format=fmt,
+                                          stream=stream.cuda_stream, **kw)
+        return out, st, planes
+
+    def enqueue_render_aov_tensor(self, cam, W: int, H: int, aovs=AOV_NAMES, chw: bool = False, format="rgb", out=None, aov_out=None, stream=None,
+                                  aa: bool = False, lights=None, max_level: int = 2, spherical=None, units=None, samples: int = 200, seed: int = 0,
+                                  rank: int = 0, nranks: int = 1):
+        """render_aov_tensor without waiting for the GPU (cgrt_enqueue_render_aov_device): the whole frame and its planes on `stream`, under
+        the rules of enqueue_render_tensor.  Returns (tensor, ticket, planes)."""
+        k = 2 if aa else 1
+        plan = self._aov_plan((), k * W, k * H, aovs, chw, aov_out)
+        out, fmt, row_bytes, stream = self._frame_tensor(W, H, format, out, stream, nranks)
+        planes = self._aov_tensors(plan, stream, zero=nranks > 1)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
+        t = C.c_uint64()
+        _check(
+            lib().cgrt_enqueue_render_aov_device(
+                self._h, C.byref(c), W, H, _ptr(lights), len(lights), q, max_level, 1 if aa else 0, rank, nranks, C.c_void_p(out.data_ptr()),
+                fmt, int(row_bytes), C.c_void_p(stream.cuda_stream) if stream.cuda_stream else None, C.byref(t),
+                self._aov_arg({n: p.data_ptr() for n, p in planes.items()}, chw),
+            )
+        )  # fmt: skip
+        return out, t.value, planes
+
+    def enqueue_render_views_aov_tensor(self, cams, W: int, H: int, aovs=AOV_NAMES, chw: bool = False, format="rgb", out=None, aov_out=None,
+                                        stream=None, lights=None, max_level: int = 2, spherical=None, units=None, samples: int = 200,
+                                        seed: int = 0):
+        """render_views_aov_tensor without waiting for the GPU (cgrt_enqueue_render_views_aov_device).  Returns (tensor, ticket, planes)."""
+        plan = self._aov_plan((len(camera_array(cams)),), W, H, aovs, chw, aov_out)
+        a, out, fmt, stream = self._views_tensor(cams, W, H, format, out, stream)
+        planes = self._aov_tensors(plan, stream)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        t = C.c_uint64()
+        _check(
+            lib().cgrt_enqueue_render_views_aov_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, _ptr(lights), len(lights), q, max_level, C.c_void_p(out.data_ptr()), fmt,
+                C.c_void_p(stream.cuda_stream) if stream.cuda_stream else None, C.byref(t),
+                self._aov_arg({n: p.data_ptr() for n, p in planes.items()}, chw),
+            )
+        )  # fmt: skip
+        return out, t.value, planes
 
     # ---- visibility queries (include/cgrt.h cgrt_occluded*, cgrt_in_shadow*, cgrt_soft_lit*; DESIGN.md section 5.12) ----
     def occluded(self, rays) -> np.ndarray:

@@ -297,7 +297,7 @@ struct CgrtScene {
     struct WorkSlot {
         void* p = nullptr;
         size_t cap = 0;
-    } work[34];  // slots 0..33 are in use (render_impl; 32 and 33 by light-set batches only)
+    } work[38];  // slots 0..37 are in use (render_impl; 32 and 33 by light-set batches only, 34..37 by deep frames with geometry buffers)
     // pinned host staging of cgrt_render*'s frame (grown on demand, guarded by render_mutex): the device frame comes down with ONE
     // asynchronous copy at PCIe speed; cgrt_render_mapped hands this memory to the caller instead of copying it once more
     void* pin_frame = nullptr;
@@ -308,6 +308,11 @@ struct CgrtScene {
         hipStream_t s = nullptr, copy = nullptr;  // second traversal stream; read-backs that must not wait for queued kernels
         hipEvent_t spawned = nullptr, traced = nullptr, e0 = nullptr, e1 = nullptr, primary_done = nullptr;
         hipEvent_t caller = nullptr;     // cgrt_shade_rays*: the frame's streams start behind what the caller's stream held
+        // geometry buffers of a blocking frame: the planes are written on a stream of their own, behind `caller`
+        // (what the caller's stream held) -- the miss values while the frame is traced, level 0's entries beside the colour export -- and
+        // the caller's stream waits for `filled`, recorded behind them
+        hipStream_t fill = nullptr;
+        hipEvent_t filled = nullptr;
         uint32_t* pin_counts = nullptr;  // 64 pinned bytes for counter read-backs
         SpawnDev spawn_host{};           // what the workspace's SpawnDev (fused level-0 spawn of predicted frames) holds
         bool spawn_valid = false;
@@ -385,9 +390,9 @@ struct CgrtScene {
             if (p) (void)hipFree(p);
         if (hints.mailbox) (void)hipHostFree(hints.mailbox);
         if (pin_frame) (void)hipHostFree(pin_frame);
-        for (hipEvent_t e : {raux.spawned, raux.traced, raux.e0, raux.e1, raux.primary_done, raux.caller})
+        for (hipEvent_t e : {raux.spawned, raux.traced, raux.e0, raux.e1, raux.primary_done, raux.caller, raux.filled})
             if (e) (void)hipEventDestroy(e);
-        for (hipStream_t st : {raux.s, raux.copy})
+        for (hipStream_t st : {raux.s, raux.copy, raux.fill})
             if (st) (void)hipStreamDestroy(st);
         if (raux.pin_counts) (void)hipHostFree(raux.pin_counts);
         for (auto& r : comb.ring) {
@@ -1915,6 +1920,23 @@ int cgrt_count_batch(CgrtScene* s, const CgrtRay* rays, uint64_t n, CgrtCounters
 // down (nranks > 1: only this rank's pixels, packed).  The caller has checked the arguments (aa_args).
 // dout (cgrt_render_device, instead of rgb / mapped): nothing comes down; k_export_frame writes this rank's pixels of the W x H frame
 // into the caller's device buffer on the caller's stream (behind the frame, and behind whatever the caller queued there before).
+// Which of the wavefront's buffer sets a level's hits / normals / rays / pixels live in: level % 3, or -- a frame with geometry buffers
+// that is deep enough to reuse set 0 -- level 0 in set 0 for good and levels 1.. through sets 1, 2, 3 (render_impl, enqueue_impl).
+struct AovSets {
+    bool keep0;
+    int count() const { return keep0 ? 4 : 3; }
+    int of(int level) const { return keep0 ? (level == 0 ? 0 : 1 + (level - 1) % 3) : level % 3; }
+};
+// The kernels' description of the caller's planes for the traced frame (W x H: aa's sub-sample frame) of F
+static AovDev aov_of(const CgrtAovOut& a, const FrameDev& F, int W, int H, uint32_t nviews, int rank, int nranks) {
+    AovDev A{};
+    A.depth = a.depth, A.normal = a.normal, A.position = a.position, A.albedo = a.albedo;
+    A.prim_id = a.prim_id, A.material_id = a.material_id, A.mask = a.mask;
+    A.chw = a.chw != 0;
+    A.W = W, A.H = H, A.views = (int)nviews;
+    A.tiles_x = F.st_x, A.rank = rank, A.nranks = nranks;
+    return A;
+}
 struct DeviceOut {
     void* p;
     int format;        // CGRT_FRAME_*
@@ -2031,7 +2053,7 @@ static ExportDev export_of(const FrameDev& F, const float* src, const DeviceOut&
 static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats, CgrtCounters* counted = nullptr,
                        const float** mapped = nullptr, bool aa = false, const DeviceOut* dout = nullptr, const ListSrc* list = nullptr,
-                       const ViewSrc* views = nullptr, const LightSetSrc* sets = nullptr) {
+                       const ViewSrc* views = nullptr, const LightSetSrc* sets = nullptr, const CgrtAovOut* aov = nullptr) {
     if (!s || (!cam && !list && !views) || (!rgb && !mapped && !dout && !list) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);
     if (W <= 0 || H <= 0 || max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad frame size or recursion depth");
@@ -2069,8 +2091,10 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     // hits/normals/rays/pixels rotate through three sets (level l reads set l % 3 and writes its mirror rays into set (l + 1) % 3;
     // level 1 is evaluated on a second stream while level 0 is still being shaded, so its mirror rays need a third set), the
     // shadow lists through two.
-    WsBuf rays[3] = {{s, 0}, {s, 1}, {s, 21}}, hits[3] = {{s, 2}, {s, 3}, {s, 22}}, normals[3] = {{s, 4}, {s, 5}, {s, 23}},
-          pix[3] = {{s, 6}, {s, 7}, {s, 24}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
+    // Geometry buffers (aov) are scattered from level 0's lists behind the frame: a frame deep enough to reuse set 0 (level 3 reads it,
+    // level 2 writes it) keeps level 0 in set 0 alone and rotates levels 1.. through sets 1, 2 and 3 instead.
+    WsBuf rays[4] = {{s, 0}, {s, 1}, {s, 21}, {s, 34}}, hits[4] = {{s, 2}, {s, 3}, {s, 22}, {s, 35}}, normals[4] = {{s, 4}, {s, 5}, {s, 23}, {s, 36}},
+          pix[4] = {{s, 6}, {s, 7}, {s, 24}, {s, 37}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
           sslot[2] = {{s, 12}, {s, 28}}, dlights{s, 13}, levels{s, 14}, drgb{s, 15}, dctr{s, 16}, dslights{s, 17}, dunits{s, 18}, dlit{s, 19},
           dwork{s, 20}, dspawn{s, 29}, dres{s, 30}, dviews{s, 31}, dsets{s, 32}, dsettab{s, 33};
     unsigned long long *cw_primary = nullptr, *cw_shadow = nullptr, *cw_mirror = nullptr;
@@ -2090,7 +2114,8 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     if (after_export && ((!list && s->work[15].cap < npix * 12) || (aa && s->work[30].cap < dres_bytes))) HIP_TRY(hipEventSynchronize(s->export_done));
     HIP_TRY(dspawn.alloc(sizeof(SpawnDev)));
     HIP_TRY(ipix.alloc(n * 4));  // pixels of level 0, kept to the end
-    for (int k = 0; k < 3; k++) {
+    const AovSets sets_for{aov && max_level >= 4};
+    for (int k = 0; k < sets_for.count(); k++) {
         HIP_TRY(rays[k].alloc(n * 28));
         HIP_TRY(hits[k].alloc(n * sizeof(CgrtHit)));
         HIP_TRY(normals[k].alloc(n * 12));
@@ -2175,6 +2200,25 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     if (s->enq_pending)  // (the scene's enqueued frames share the workspace: every stream of this one starts behind the last of them)
         for (hipStream_t st : {(hipStream_t) nullptr, aux.s, aux.copy}) HIP_TRY(hipStreamWaitEvent(st, s->enq_done, 0));
     s->frame_seq++;
+    // Geometry buffers: the miss values of every owned pixel do not depend on the frame.  They are written beside the frame's kernels (a
+    // bandwidth-bound pass next to latency-bound traversals) instead of behind them: on a stream of their own, behind everything the
+    // caller queued on its stream before the call, and issued right behind the primary kernel so that the frame's first launch does not
+    // wait for these host calls.  Level 0's entries are scattered over them behind the frame, on the same stream, beside the colour
+    // export, and the caller's stream waits for both (below).
+    const AovDev A = aov ? aov_of(*aov, F, W, H, nviews, rank, nranks) : AovDev{};
+    bool planes_filled = false;  // (a frame that is redrawn fills them once)
+    auto fill_planes = [&]() -> int {
+        if (!aov || planes_filled) return CGRT_OK;
+        if (!aux.fill) {
+            HIP_TRY(hipStreamCreateWithFlags(&aux.fill, hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&aux.filled, hipEventDisableTiming));
+        }
+        HIP_TRY(hipEventRecord(aux.caller, dout->stream));
+        HIP_TRY(hipStreamWaitEvent(aux.fill, aux.caller, 0));
+        HIP_TRY(launch_aov_fill(A, aux.fill));
+        planes_filled = true;
+        return CGRT_OK;
+    };
     if (list) {  // the rays were written on the caller's stream: every stream of the frame starts from the default stream, which waits here
         HIP_TRY(hipEventRecord(aux.caller, list->stream));
         HIP_TRY(hipStreamWaitEvent(nullptr, aux.caller, 0));
@@ -2193,6 +2237,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     // entries, the frame is drawn again the exact way below (first frames, resized frames and frames with spherical lights or
     // work counters always are).  Same kernels on the same lists: the frame is bit-identical either way (tests/test_render_prediction_gpu.py).
     bool frame_done = false;
+    unsigned long long aov_entries = 0;  // level 0's entries of the frame that was kept (the geometry buffers' source)
     CgrtScene::RenderPred& P = s->rpred;
     const bool predictable = g_render_predict.load() && P.valid && P.W == W && P.H == H && P.rank == rank && P.nranks == nranks &&
                              P.max_level == max_level && P.L == L && !P.counts.empty() && SL == 0 && !counted && max_level >= 1 && !list &&
@@ -2224,6 +2269,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         }
         HIP_TRY(launch_trace_primary_compact(s->dev, C, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(),
                                              pair, nullptr, nullptr, drgb.as<float>(), static_cast<const SpawnDev*>(dspawn.p)));
+        if (const int frc = fill_planes()) return frc;
         const unsigned long long cap0 = cap_of(0);
         // Level 0's two lists.  With a fast tree they go out as ONE launch (k_trace_pair: workgroups dealt alternately) and the whole
         // frame stays on one stream; otherwise the shadow list runs on the default stream and the mirror list, with all of level 1
@@ -2279,7 +2325,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         }
         hipStream_t const tail = tail_on_aux ? aux.s : nullptr;
         for (int level = 2; level < np; level++) {  // deeper levels: small, one after the other (buffer sets as in the exact path)
-            const int a = level % 3, b = (level + 1) % 3, q = level & 1;
+            const int a = sets_for.of(level), b = sets_for.of(level + 1), q = level & 1;
             const unsigned long long cap = cap_of(level);
             HIP_TRY(launch_spawn(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), pix[a].as<int>(), cap, mats, dlights.as<float>(), L,
                                  level + 1 < max_level, srays[q].as<float>(), sdist[q].as<float>(), sslot[q].as<int>(), lvl_of(level), rays[b].as<float>(),
@@ -2331,6 +2377,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipEventElapsedTime(&ms, aux.e0, aux.e1));
         st.device_ms = ms;
         st.levels = (int)actual.size();
+        aov_entries = actual.empty() ? 0 : actual[0];
         P.counts = actual;
         P.valid = !actual.empty();
         P.last_path = 1;
@@ -2382,6 +2429,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                                                      ipix.as<int>(), primary_hits, nullptr, cw_primary, frame_rgb));  // (also clears this rank's pixels)
                 st.primary_rays = owned_pixels(F);
             }
+            if (const int frc = fill_planes()) return frc;
             // (light sets: the primary kernel clears the first nviews * W * H pixels of the frame buffer; the sets' scatter writes only the
             // pixels that hit, and a pixel that misses is black in every set: the rest of the buffer is cleared here)
             if (nsets > 1)
@@ -2403,9 +2451,10 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             HIP_TRY(hipMemcpyAsync(aux.pin_counts, primary_hits, sizeof(uint32_t), hipMemcpyDeviceToHost, aux.copy));
             HIP_TRY(hipStreamSynchronize(aux.copy));
             unsigned long long cnt = aux.pin_counts[0];
+            aov_entries = cnt;
             int level = 0;
             while (level < max_level && cnt > 0) {
-                const int a = level % 3, b = (level + 1) % 3, q = level & 1;  // this level's buffer set, the next level's, this level's shadow set
+                const int a = sets_for.of(level), b = sets_for.of(level + 1), q = level & 1;  // this level's buffer set, the next level's, this level's shadow set
                 const int spawn = level + 1 < max_level;
                 const int* cur_pix = level == 0 ? ipix.as<int>() : pix[a].as<int>();
                 uint32_t* ctr = dctr.as<uint32_t>() + 4 * (size_t)level;
@@ -2553,7 +2602,13 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                                       nranks, packed);
         if (!s->export_done) HIP_TRY(hipEventCreateWithFlags(&s->export_done, hipEventDisableTiming));
         HIP_TRY(hipStreamWaitEvent(dout->stream, aux.e1, 0));
+        if (aov) {  // (level 0 of the frame that was kept is in set 0, untouched since its primary kernel; aux.e1 has been waited for)
+            HIP_TRY(launch_aov_scatter(A, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(), mats, aov_entries,
+                                       aux.fill));
+            HIP_TRY(hipEventRecord(aux.filled, aux.fill));
+        }
         HIP_TRY(launch_export_frame(E, dout->stream));
+        if (aov) HIP_TRY(hipStreamWaitEvent(dout->stream, aux.filled, 0));  // (export_done, below, is behind the planes too)
         HIP_TRY(hipEventRecord(s->export_done, dout->stream));
         s->export_pending = true;
     } else {
@@ -2695,9 +2750,38 @@ static int check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, 
     return CGRT_OK;
 }
 
+// The geometry buffers' own checks (include/cgrt.h CgrtAovOut), behind the counterpart's: aov_args before the host-only check, aov_spans
+// (px pixels per plane) behind d_out's.
+static int aov_args(const CgrtAovOut* aov, int max_level, int aa, int nranks) {
+    if (!aov) return fail(CGRT_E_ARG, "aov is NULL");
+    if (!aov->depth && !aov->normal && !aov->position && !aov->albedo && !aov->prim_id && !aov->material_id && !aov->mask)
+        return fail(CGRT_E_ARG, "aov requests no plane");
+    if (max_level == 0) return fail(CGRT_E_ARG, "max_level 0 traces no primary rays: there are no geometry buffers to export");
+    if (aa && nranks > 1) return fail(CGRT_E_ARG, "anti-aliased geometry buffers are for nranks == 1 only");
+    if ((uintptr_t)aov->depth % 4 || (uintptr_t)aov->normal % 4 || (uintptr_t)aov->position % 4 || (uintptr_t)aov->albedo % 4 ||
+        (uintptr_t)aov->prim_id % 4 || (uintptr_t)aov->material_id % 4)
+        return fail(CGRT_E_ARG, "a geometry-buffer plane is not aligned to its element size");
+    return CGRT_OK;
+}
+static int aov_spans(const CgrtScene* s, const CgrtAovOut* aov, uint64_t px) {
+    const struct {
+        const void* p;
+        uint64_t bytes;
+        const char* name;
+    } planes[7] = {{aov->depth, 4, "aov.depth"},     {aov->normal, 12, "aov.normal"},          {aov->position, 12, "aov.position"}, {aov->albedo, 12, "aov.albedo"},
+                   {aov->prim_id, 4, "aov.prim_id"}, {aov->material_id, 4, "aov.material_id"}, {aov->mask, 1, "aov.mask"}};
+    for (const auto& pl : planes) {
+        if (!pl.p) continue;
+        const int rc = check_device_span(s, pl.p, pl.bytes * px, pl.name);
+        if (rc) return rc;
+    }
+    return CGRT_OK;
+}
 // cgrt_render_device's checks, in include/cgrt.h's order, all before any device work (cgrt_enqueue_render_device: the same); *pitch = the row pitch
+// with_aov: cgrt_render_aov_device's, which adds the planes' checks
 static int render_device_args(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
-                              int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, uint64_t* pitch) {
+                              int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, uint64_t* pitch,
+                              bool with_aov = false, const CgrtAovOut* aov = nullptr) {
     if (!s) return fail(CGRT_E_ARG, "scene is NULL");
     if (aa) {
         const int rc = aa_args(cam, d_out, W, H, lights, nlights, soft, max_level, rank, nranks);
@@ -2715,11 +2799,13 @@ static int render_device_args(CgrtScene* s, const CgrtCamera* cam, int W, int H,
         }
     }
     uint64_t extent = 0;
-    const int rc = export_args(d_out, W, H, format, row_bytes, pitch, &extent);
+    int rc = export_args(d_out, W, H, format, row_bytes, pitch, &extent);
     if (rc) return rc;
+    if (with_aov && (rc = aov_args(aov, max_level, aa, nranks))) return rc;
     NEED_DEVICE(s);
     HIP_TRY(hipSetDevice(s->device));
-    return check_device_span(s, d_out, extent, "d_out");
+    if ((rc = check_device_span(s, d_out, extent, "d_out"))) return rc;
+    return with_aov ? aov_spans(s, aov, (uint64_t)W * (uint64_t)H * (aa ? 4u : 1u)) : CGRT_OK;
 }
 int cgrt_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
@@ -2728,6 +2814,15 @@ int cgrt_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     const int rc = render_device_args(s, cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, d_out, format, row_bytes, &D.pitch);
     if (rc) return rc;
     return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, nullptr, stats, nullptr, nullptr, aa != 0, &D);
+}
+int cgrt_render_aov_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                           int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
+                           CgrtRenderStats* stats, const CgrtAovOut* aov) {
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream)};
+    const int rc = render_device_args(s, cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, d_out, format, row_bytes, &D.pitch, true, aov);
+    if (rc) return rc;
+    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, nullptr, stats, nullptr, nullptr, aa != 0, &D, nullptr, nullptr,
+                       nullptr, aov);
 }
 
 // ---- renderRayTracing's per-pixel loop for a batch of cameras (render_impl, ViewSrc; include/cgrt.h cgrt_render_views*) ----
@@ -2754,15 +2849,18 @@ int cgrt_render_views(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int
 }
 // cgrt_render_views_device's checks (cgrt_enqueue_render_views_device: the same); D->pitch and D->view_bytes are set
 static int render_views_device_args(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
-                                    const CgrtSoftShadows* soft, int max_level, void* d_out, int format, DeviceOut* D) {
+                                    const CgrtSoftShadows* soft, int max_level, void* d_out, int format, DeviceOut* D, bool with_aov = false,
+                                    const CgrtAovOut* aov = nullptr) {
     int rc = render_views_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out);
     if (rc) return rc;
     uint64_t extent = 0;
     if ((rc = export_args(d_out, W, H, format, 0, &D->pitch, &extent))) return rc;
     D->view_bytes = extent;  // (packed rows: one view's frame is exactly its extent)
+    if (with_aov && (rc = aov_args(aov, max_level, 0, 1))) return rc;
     NEED_DEVICE(s);
     HIP_TRY(hipSetDevice(s->device));
-    return check_device_span(s, d_out, extent * nviews, "d_out");
+    if ((rc = check_device_span(s, d_out, extent * nviews, "d_out"))) return rc;
+    return with_aov ? aov_spans(s, aov, (uint64_t)W * (uint64_t)H * nviews) : CGRT_OK;
 }
 int cgrt_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
                              const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats) {
@@ -2771,6 +2869,15 @@ int cgrt_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nvie
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
     return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, &D, nullptr, &V);
+}
+int cgrt_render_views_aov_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                                 const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats,
+                                 const CgrtAovOut* aov) {
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D, true, aov);
+    if (rc) return rc;
+    const ViewSrc V{cams, nviews};
+    return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, &D, nullptr, &V, nullptr, aov);
 }
 
 // ---- one camera under a batch of light sets (render_impl, LightSetSrc; include/cgrt.h cgrt_render_light_sets*) ----
@@ -2959,7 +3066,7 @@ int cgrt_shade_rays(CgrtScene* s, const CgrtRay* rays, uint64_t n, const float* 
 // scattered back by its pixel: the bytes are the blocking entry's.  The caller has checked the arguments (the blocking entries' checks).
 static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                         int max_level, int rank, int nranks, bool aa, const DeviceOut* dout, const ListSrc* list, const ViewSrc* views,
-                        hipStream_t stream, uint64_t* ticket, const LightSetSrc* sets = nullptr) {
+                        hipStream_t stream, uint64_t* ticket, const LightSetSrc* sets = nullptr, const CgrtAovOut* aov = nullptr) {
     const int PW = W, PH = H;
     if (aa) {
         W *= 2;
@@ -2991,16 +3098,17 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
         HIP_TRY(hipHostMalloc((void**)&slot.pin_ctr, 4 * 17 * sizeof(uint32_t), hipHostMallocDefault));
     }
     // the workspace of render_impl, sized for the worst case (WsBuf::alloc waits for the scene's frames before a buffer grows)
-    WsBuf rays[3] = {{s, 0}, {s, 1}, {s, 21}}, hits[3] = {{s, 2}, {s, 3}, {s, 22}}, normals[3] = {{s, 4}, {s, 5}, {s, 23}},
-          pix[3] = {{s, 6}, {s, 7}, {s, 24}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
+    WsBuf rays[4] = {{s, 0}, {s, 1}, {s, 21}, {s, 34}}, hits[4] = {{s, 2}, {s, 3}, {s, 22}, {s, 35}}, normals[4] = {{s, 4}, {s, 5}, {s, 23}, {s, 36}},
+          pix[4] = {{s, 6}, {s, 7}, {s, 24}, {s, 37}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
           sslot[2] = {{s, 12}, {s, 28}}, levels{s, 14}, drgb{s, 15}, dctr{s, 16}, dlit{s, 19}, dres{s, 30}, dsets{s, 32};
     const int packed = aa && nranks > 1;
     const size_t res_bytes = packed ? (size_t)F.nst_rank * 1024 * 12 : (size_t)PW * PH * 12;
     const size_t dres_bytes = std::max<size_t>(res_bytes, (size_t)F.nst_rank * 1024 * 12);
     const size_t nctr = 4 * (size_t)(max_level + 1);
+    const AovSets sets_for{aov && max_level >= 4};  // (as render_impl: geometry buffers are scattered from level 0's lists behind the frame)
     if (n) {
         HIP_TRY(ipix.alloc(n * 4));
-        for (int k = 0; k < 3; k++) {
+        for (int k = 0; k < sets_for.count(); k++) {
             HIP_TRY(rays[k].alloc(n * 28));
             HIP_TRY(hits[k].alloc(n * sizeof(CgrtHit)));
             HIP_TRY(normals[k].alloc(n * 12));
@@ -3128,7 +3236,7 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
                 HIP_TRY(hipMemsetAsync(frame_rgb + 3ull * W * H * nviews, 0, (npix - (unsigned long long)W * H * nviews) * 12, stream));
             const bool pairable = can_trace_pair(s->dev);
             for (int level = 0; level < max_level; level++) {
-                const int a = level % 3, b = (level + 1) % 3, q = level & 1;  // as render_impl's buffer sets
+                const int a = sets_for.of(level), b = sets_for.of(level + 1), q = level & 1;  // as render_impl's buffer sets
                 const int spawn = level + 1 < max_level;
                 const int* cur_pix = level == 0 ? ipix.as<int>() : pix[a].as<int>();
                 if (!(fused && level == 0))
@@ -3179,6 +3287,12 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
         if (aa) HIP_TRY(launch_resolve_aa(F, drgb.as<float>(), dres.as<float>(), packed, stream));
         if (dout) HIP_TRY(launch_export_frame(export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, views ? nviews * nsets : 0u, aa, rank,
                                                         nranks, packed), stream));
+        if (aov) {  // (max_level >= 1: level 0's length is the word the primary kernel counted into)
+            const AovDev A = aov_of(*aov, F, W, H, nviews, rank, nranks);
+            HIP_TRY(launch_aov_fill(A, stream));
+            HIP_TRY(launch_aov_scatter_strided(A, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(), mats, n, stream,
+                                               fused ? pair : primary_hits));
+        }
         HIP_TRY(hipMemcpyAsync(slot.pin_ctr, dctr.p, nctr * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     }
     HIP_TRY(hipEventRecord(slot.t1, stream));
@@ -3213,6 +3327,23 @@ int cgrt_enqueue_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint3
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
     return enqueue_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream, ticket);
+}
+int cgrt_enqueue_render_aov_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+                                   int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
+                                   uint64_t* ticket, const CgrtAovOut* aov) {
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream)};
+    const int rc = render_device_args(s, cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, d_out, format, row_bytes, &D.pitch, true, aov);
+    if (rc) return rc;
+    return enqueue_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, aa != 0, &D, nullptr, nullptr, D.stream, ticket, nullptr, aov);
+}
+int cgrt_enqueue_render_views_aov_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                                         const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, uint64_t* ticket,
+                                         const CgrtAovOut* aov) {
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D, true, aov);
+    if (rc) return rc;
+    const ViewSrc V{cams, nviews};
+    return enqueue_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream, ticket, nullptr, aov);
 }
 int cgrt_enqueue_render_views_light_sets_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
                                                 const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, uint64_t* ticket) {

@@ -634,6 +634,126 @@ hipError_t launch_export_frame(const ExportDev& E, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- Geometry buffers (AovDev, trace_kernels.h) ----
+// k_aov_fill: one thread per 4 consecutive pixels of a row of a view, as k_export_frame (super-tiles are multiples of 4 pixels wide, so
+// the 4 pixels share an owner): the miss values of every requested plane -- depth FLT_MAX, ids CGRT_NO_PRIM / -1, everything else 0 --
+// as 16-B stores (the mask: one 4-B store) where the group is whole and its address aligned, element by element otherwise.
+__device__ __forceinline__ void fill4(float* d, int n, float v) {
+    if (n == 4 && ((uintptr_t)d & 15u) == 0) {
+        *reinterpret_cast<float4*>(d) = make_float4(v, v, v, v);
+    } else {
+        for (int i = 0; i < n; i++) d[i] = v;
+    }
+}
+__device__ __forceinline__ void fill3(float* plane, int chw, unsigned long long view, unsigned long long wh, unsigned long long p, int n) {
+    if (chw) {
+        for (int c = 0; c < 3; c++) fill4(plane + (3ull * view + (unsigned long long)c) * wh + p, n, 0.0f);
+    } else {
+        float* d = plane + 3ull * (view * wh + p);
+        if (n == 4 && ((uintptr_t)d & 15u) == 0) {
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            reinterpret_cast<float4*>(d)[0] = z;
+            reinterpret_cast<float4*>(d)[1] = z;
+            reinterpret_cast<float4*>(d)[2] = z;
+        } else {
+            for (int i = 0; i < 3 * n; i++) d[i] = 0.0f;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_aov_fill(AovDev A) {
+    unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long G = (unsigned long long)((A.W + 3) >> 2);  // 4-pixel groups per row
+    const unsigned long long per_view = G * (unsigned long long)A.H, view = t / per_view;
+    if (view >= (unsigned long long)A.views) return;
+    t -= view * per_view;
+    const unsigned long long yl = t / G;
+    const int y = (int)yl, x0 = (int)(t - yl * G) * 4;
+    const int n = A.W - x0 < 4 ? A.W - x0 : 4;
+    if (A.nranks > 1) {
+        const unsigned long long k = (unsigned long long)(y >> 6) * (unsigned long long)A.tiles_x + (unsigned long long)(x0 >> 6);
+        if (k % (unsigned long long)A.nranks != (unsigned long long)A.rank) return;
+    }
+    const unsigned long long wh = (unsigned long long)A.W * (unsigned long long)A.H;
+    const unsigned long long p = (unsigned long long)y * (unsigned long long)A.W + (unsigned long long)x0, q = view * wh + p;
+    if (A.depth) fill4(A.depth + q, n, 3.402823466e+38f);  // FLT_MAX: the t a ray that misses keeps
+    if (A.normal) fill3(A.normal, A.chw, view, wh, p, n);
+    if (A.position) fill3(A.position, A.chw, view, wh, p, n);
+    if (A.albedo) fill3(A.albedo, A.chw, view, wh, p, n);
+    if (A.prim_id) fill4(reinterpret_cast<float*>(A.prim_id) + q, n, __uint_as_float(0xffffffffu));   // CGRT_NO_PRIM
+    if (A.material_id) fill4(reinterpret_cast<float*>(A.material_id) + q, n, __uint_as_float(0xffffffffu));  // -1
+    if (A.mask) {
+        uint8_t* d = A.mask + q;
+        if (n == 4 && ((uintptr_t)d & 3u) == 0) {
+            *reinterpret_cast<uint32_t*>(d) = 0u;
+        } else {
+            for (int i = 0; i < n; i++) d[i] = 0;
+        }
+    }
+}
+// k_aov_scatter: entry i of level 0 to its pixel.  The list is in the primary kernel's order (8 x 8 tiles), so a wave's 64 entries are
+// row segments of up to 8 pixels: 32-B pieces of a 4-byte plane (measured: DESIGN.md section 5.17).
+__device__ __forceinline__ void st3(float* plane, int chw, unsigned long long view, unsigned long long wh, unsigned long long p, F3 v) {
+    if (chw) {
+        float* d = plane + 3ull * view * wh + p;
+        d[0] = v.x;
+        d[wh] = v.y;
+        d[2 * wh] = v.z;
+    } else {
+        float* d = plane + 3ull * (view * wh + p);
+        d[0] = v.x;
+        d[1] = v.y;
+        d[2] = v.z;
+    }
+}
+__device__ __forceinline__ void aov_entry(const AovDev& A, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                          const float* __restrict__ normals, const int* __restrict__ item_pixels,
+                                          const float* __restrict__ materials, unsigned long long i) {
+    const long long pix = item_pixels[i];
+    const unsigned long long wh = (unsigned long long)A.W * (unsigned long long)A.H;
+    if (pix < 0 || (unsigned long long)pix >= wh * (unsigned long long)A.views) return;  // item outside the frame
+    const unsigned long long q = (unsigned long long)pix, view = q / wh, p = q - view * wh;
+    const CgrtHitDev h = hits[i];
+    if (A.depth) A.depth[q] = h.t;
+    if (A.normal) st3(A.normal, A.chw, view, wh, p, ldv(normals + 3 * i));
+    if (A.position) {
+        const float* r = rays + 7 * i;
+        st3(A.position, A.chw, view, wh, p, add(ldv(r), scale(ldv(r + 3), h.t)));  // pointOn (main.cpp:164), as k_shade's
+    }
+    if (A.albedo) st3(A.albedo, A.chw, view, wh, p, h.material_id >= 0 ? ldv(materials + 8 * h.material_id) : f3(0.f, 0.f, 0.f));
+    if (A.prim_id) A.prim_id[q] = h.prim_id;
+    if (A.material_id) A.material_id[q] = h.material_id;
+    if (A.mask) A.mask[q] = (uint8_t)(h.hit != 0);
+}
+__global__ __launch_bounds__(256) void k_aov_scatter(AovDev A, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                     const float* __restrict__ normals, const int* __restrict__ item_pixels,
+                                                     const float* __restrict__ materials, unsigned long long n) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    aov_entry(A, rays, hits, normals, item_pixels, materials, i);
+}
+__global__ __launch_bounds__(256) void k_aov_scatter_strided(AovDev A, const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,
+                                                             const float* __restrict__ normals, const int* __restrict__ item_pixels,
+                                                             const float* __restrict__ materials, unsigned long long n,
+                                                             const uint32_t* __restrict__ dcount) {
+    const unsigned long long present = *dcount;
+    n = present < n ? present : n;
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
+        aov_entry(A, rays, hits, normals, item_pixels, materials, i);
+}
+hipError_t launch_aov_fill(const AovDev& A, hipStream_t s) {
+    const unsigned long long n = (unsigned long long)((A.W + 3) / 4) * (unsigned long long)A.H * (unsigned long long)A.views;
+    if (n == 0) return hipSuccess;
+    if ((n + 255) / 256 > 0xffffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_aov_fill, dim3(grid_for(n, 256)), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_aov_scatter(const AovDev& A, const float* rays, const CgrtHitDev* hits, const float* normals, const int* item_pixels,
+                              const float* materials, unsigned long long n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_aov_scatter, dim3(grid_for(n, 256)), dim3(256), 0, s, A, rays, hits, normals, item_pixels, materials, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_spawn(const float* rays, const CgrtHitDev* hits, const float* normals, const int* pixels, unsigned long long n,
                         const float* materials, const float* lights, unsigned nlights, int spawn, float* srays, float* sdist, int* sslot,
                         float* lvl, float* next_rays, int* next_pixels, uint32_t* counters, hipStream_t s, const uint32_t* dcount) {
@@ -732,6 +852,14 @@ hipError_t launch_write_rgb_strided(const float* lvl0, const float* child_lvl, u
     if (n)
         hipLaunchKernelGGL(k_write_rgb_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
                            reinterpret_cast<const float4*>(child_lvl), n, item_pixels, rgb, dcount);
+    return hipGetLastError();
+}
+
+hipError_t launch_aov_scatter_strided(const AovDev& A, const float* rays, const CgrtHitDev* hits, const float* normals, const int* item_pixels,
+                                      const float* materials, unsigned long long n, hipStream_t s, const uint32_t* dcount) {
+    if (n)
+        hipLaunchKernelGGL(k_aov_scatter_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, A, rays, hits, normals, item_pixels, materials, n,
+                           dcount);
     return hipGetLastError();
 }
 

@@ -190,6 +190,30 @@ struct ExportDev {
     unsigned long long view_bytes;  // dst bytes from one view to the next
 };
 hipError_t launch_export_frame(const ExportDev& E, hipStream_t s);
+// Geometry buffers of a frame (cgrt_render_aov_device, include/cgrt.h CgrtAovOut): what the frame's primary rays
+// saw, from level 0 of its own wavefront.  Every plane is packed and row-major, pixel p of view v at v * W * H + p (3-channel planes: 3
+// floats there, or with chw plane c of view v at (3 v + c) * W * H); a NULL plane is not wanted and costs no traffic.
+struct AovDev {
+    float* depth;
+    float* normal;
+    float* position;
+    float* albedo;
+    uint32_t* prim_id;
+    int32_t* material_id;
+    uint8_t* mask;
+    int chw;
+    int W, H, views;                   // the traced frame (aa: the sub-sample frame); views >= 1
+    int tiles_x, rank, nranks;         // nranks > 1: only pixels whose 64 x 64 super-tile (row-major, tiles_x per row) % nranks == rank
+};
+// launch_aov_fill (k_aov_fill): the miss values into every owned pixel of every requested plane, in row order.  launch_aov_scatter
+// (k_aov_scatter), behind it on the same stream: entry i < n of level 0 {rays, hits, normals, item_pixels} and its material's kd to pixel
+// item_pixels[i]; position = origin + direction * t in cgrt_math.h's arithmetic.  launch_aov_scatter_strided: n is the list's capacity,
+// *dcount its length, a capped grid strides over the entries present (enqueued frames).
+hipError_t launch_aov_fill(const AovDev& A, hipStream_t s);
+hipError_t launch_aov_scatter(const AovDev& A, const float* rays, const CgrtHitDev* hits, const float* normals, const int* item_pixels,
+                              const float* materials, unsigned long long n, hipStream_t s);
+hipError_t launch_aov_scatter_strided(const AovDev& A, const float* rays, const CgrtHitDev* hits, const float* normals, const int* item_pixels,
+                                      const float* materials, unsigned long long n, hipStream_t s, const uint32_t* dcount);
 hipError_t launch_gather_calib(const void* table, unsigned long long nrecords, unsigned long long mult, unsigned long long add, float* sink,
                                hipStream_t s);
 hipError_t launch_fastdiv_check(const float* a, const float* d, unsigned long long n, unsigned long long* mismatches, float* first_bad,

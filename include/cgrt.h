@@ -542,6 +542,54 @@ int cgrt_enqueue_render_views_light_sets_device(CgrtScene* scene, const CgrtCame
                                                 const CgrtLightSets* sets, const CgrtSoftShadows* soft, int max_level, void* d_out,
                                                 int format, void* stream, uint64_t* ticket);
 
+/* Geometry buffers ("AOVs") of a device frame: what the frame's primary rays saw -- depth, surface normal, hit
+ * point, albedo, primitive / material id, coverage -- written by the call that writes the shaded frame, from level 0 of the frame's own
+ * wavefront: no second trace.  Every pointer is device memory of the scene's device, aligned to its element size, or NULL (plane not
+ * wanted: it costs nothing and is never touched). */
+typedef struct CgrtAovOut {
+    float*    depth;        /* 1 x f32 per pixel: CgrtHit.t of the pixel's primary ray (the untouched FLT_MAX on a miss)            */
+    float*    normal;       /* 3 x f32: the normal cgrt_trace_primary_device writes for a hit; 0, 0, 0 on a miss                    */
+    float*    position;     /* 3 x f32: the reference's pointOn, ray.origin + ray.direction * ray.t (main.cpp:164), of the primary  */
+                            /*          ray, f32, product rounded, then sum rounded (no FMA); 0, 0, 0 on a miss                     */
+    float*    albedo;       /* 3 x f32: kd of material_id's Material; 0, 0, 0 for material_id -1 (miss, sphere-only hit) -- the kd  */
+                            /*          k_shade uses                                                                                */
+    uint32_t* prim_id;      /* CgrtHit.prim_id (CGRT_NO_PRIM on a miss)                                                             */
+    int32_t*  material_id;  /* CgrtHit.material_id                                                                                  */
+    uint8_t*  mask;         /* CgrtHit.hit, 0 or 1                                                                                  */
+    int       chw;          /* 3-channel planes: 0 = (H, W, 3), 1 = (3, H, W)                                                       */
+} CgrtAovOut;
+/* Planes are packed (no row pitch), row-major, pixel (x, y) at y*W + x, NOT y-flipped, whatever `format` the colour has.  Every owned pixel
+ * of every requested plane is written, hit or miss (unlike the normals of cgrt_trace_primary_device); no byte outside a requested plane, and
+ * no pixel of another rank, is written.  The values are, bit for bit, the fields cgrt_trace_primary_device returns for the same camera.
+ * Each entry below is its counterpart plus `aov`, and writes the colour, the stats, the render path, the prediction record and the frame
+ * hints exactly as the counterpart does; device_ms excludes the plane export as it excludes the colour export.
+ *   cgrt_render_aov_device        cgrt_render_device + planes of (H, W).  With aa != 0 the planes are those of the 2W x 2H sub-sample frame
+ *                                 the wavefront traces, (2H, 2W), equal to cgrt_trace_primary_device(cam, 2W, 2H); aa planes need nranks == 1.
+ *   cgrt_render_views_aov_device  cgrt_render_views_device + planes with a leading view axis: (B, H, W), (B, H, W, 3) or (B, 3, H, W).
+ *   cgrt_enqueue_render_aov_device, cgrt_enqueue_render_views_aov_device: the same two under the rules of the enqueued frames above; the
+ *                                 planes are complete on `stream` when the colour is.
+ * The planes are ordered on `stream` as the colour is -- written behind everything the caller enqueued there before the call, complete for
+ * everything enqueued there after it -- and the scene's export event is recorded behind them too: the next frame on the scene and
+ * cgrt_scene_destroy wait for them.  Arguments are checked in the counterpart's order with its codes; then aov NULL or without any plane,
+ * max_level == 0 (no primary ray is traced at depth 0: nothing to export), aa with nranks > 1, a plane not aligned to its element size
+ * -> CGRT_E_ARG; then a host-only scene -> CGRT_E_NO_DEVICE; then every requested plane's extent is checked to be device memory of the
+ * scene's device as d_out is -> CGRT_E_ARG, all before any device work.
+ * Not offered: light-set entries (the planes do not depend on the lights: render the views once with cgrt_render_views_aov_device), ray
+ * lists (cgrt_intersect_batch_device returns exactly this for caller rays), host-memory outputs, the *_multi entries, aa planes per rank
+ * (aa ownership is in packed 32 x 32 blocks), and the C++ host mirror (the reference has no such output). */
+int cgrt_render_aov_device(CgrtScene* scene, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights,
+                           const CgrtSoftShadows* soft, int max_level, int aa, int rank, int nranks, void* d_out, int format,
+                           uint64_t row_bytes, void* stream, CgrtRenderStats* stats, const CgrtAovOut* aov);
+int cgrt_render_views_aov_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights,
+                                 uint32_t nlights, const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream,
+                                 CgrtRenderStats* stats, const CgrtAovOut* aov);
+int cgrt_enqueue_render_aov_device(CgrtScene* scene, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights,
+                                   const CgrtSoftShadows* soft, int max_level, int aa, int rank, int nranks, void* d_out, int format,
+                                   uint64_t row_bytes, void* stream, uint64_t* ticket, const CgrtAovOut* aov);
+int cgrt_enqueue_render_views_aov_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights,
+                                         uint32_t nlights, const CgrtSoftShadows* soft, int max_level, void* d_out, int format,
+                                         void* stream, uint64_t* ticket, const CgrtAovOut* aov);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
