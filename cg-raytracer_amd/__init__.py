@@ -111,6 +111,104 @@ class Camera(C.Structure):
         return cam
 
 
+class RayCamera(C.Structure):
+    """CgrtRayCamera (include/cgrt.h): the ray of pixel (x, y) has origin and unnormalised direction affine in
+    (x + x_off, y + y_off).  The constructors compute in float64 and round each field to float32 once; a non-finite field is a
+    ValueError."""
+
+    _fields_ = [
+        ("origin", C.c_float * 3), ("origin_dx", C.c_float * 3), ("origin_dy", C.c_float * 3),
+        ("dir", C.c_float * 3), ("dir_dx", C.c_float * 3), ("dir_dy", C.c_float * 3),
+        ("x_off", C.c_int32), ("y_off", C.c_int32),
+    ]  # fmt: skip
+    FLOAT_FIELDS = ("origin", "origin_dx", "origin_dy", "dir", "dir_dx", "dir_dy")
+
+    @staticmethod
+    def from_fields(origin, origin_dx, origin_dy, dir, dir_dx, dir_dy, x_off: int = 0, y_off: int = 0) -> "RayCamera":  # noqa: A002
+        c = RayCamera()
+        for k, v in zip(RayCamera.FLOAT_FIELDS, (origin, origin_dx, origin_dy, dir, dir_dx, dir_dy)):
+            v = np.asarray(v, np.float64).reshape(3)
+            with np.errstate(over="ignore"):
+                f = v.astype(np.float32)
+            if not np.isfinite(f).all():
+                raise ValueError(f"RayCamera.{k} is not finite: {v}")
+            getattr(c, k)[:] = f
+        c.x_off, c.y_off = int(x_off), int(y_off)
+        return c
+
+    @staticmethod
+    def from_pinhole(K, cam_to_world, convention: str = "opencv") -> "RayCamera":
+        """A pinhole with the 3x3 intrinsic matrix K (any upper-triangular K: skew and non-square pixels included) and the camera-to-world
+        pose (3x4 or 4x4).  Pixel (x, y) looks through image point (x + 0.5, y + 0.5): direction = R @ F @ K^-1 @ (x + 0.5, y + 0.5, 1)
+        with F = identity for "opencv" (camera x right, y down, z forward: COLMAP) and diag(1, -1, -1) for "opengl" (x right, y up, z
+        backward: NeRF-style transforms.json).  Image row 0 is the top row in both."""
+        if convention not in ("opencv", "opengl"):
+            raise ValueError(f"convention must be 'opencv' or 'opengl', not {convention!r}")
+        K = np.asarray(K, np.float64)
+        P = np.asarray(cam_to_world, np.float64)
+        if K.shape != (3, 3) or P.shape not in ((3, 4), (4, 4)):
+            raise ValueError("K must be 3x3 and cam_to_world 3x4 or 4x4")
+        M = P[:3, :3] @ (np.diag([1.0, -1.0, -1.0]) if convention == "opengl" else np.eye(3)) @ np.linalg.inv(K)
+        zero = np.zeros(3)
+        return RayCamera.from_fields(P[:3, 3], zero, zero, M @ np.array([0.5, 0.5, 1.0]), M[:, 0], M[:, 1])
+
+    @staticmethod
+    def orthographic(origin, right, up, forward, pixel_size) -> "RayCamera":
+        """Parallel rays along `forward`; pixel (x, y) starts at origin + (x + 0.5) * sx * right + (y + 0.5) * sy * up, where `origin` is
+        the outer corner of pixel (0, 0) on the image plane, `up` the direction in which y grows, and pixel_size = s or (sx, sy)."""
+        sx, sy = np.broadcast_to(np.asarray(pixel_size, np.float64), (2,)) if np.ndim(pixel_size) else (float(pixel_size),) * 2
+        o, r, u = (np.asarray(v, np.float64).reshape(3) for v in (origin, right, up))
+        zero = np.zeros(3)
+        return RayCamera.from_fields(o + 0.5 * sx * r + 0.5 * sy * u, sx * r, sy * u, forward, zero, zero)
+
+    @staticmethod
+    def from_trackball(cam, W: int, H: int) -> "RayCamera":
+        """The ray camera closest to the Trackball camera `cam` (a Camera or its 9 floats) for W x H frames: Trackball::generateRay's
+        position, rotation and image plane evaluated in float64 from the camera's float32 fields.  Close to cgrt_generate_rays, not
+        bit-identical: the formula differs."""
+        a = (camera_array([cam])[0] if isinstance(cam, Camera) else np.asarray(cam, np.float32).reshape(9)).astype(np.float64)
+        h = a[3:6] * 0.5
+        (cx, cy, cz), (sx, sy, sz) = np.cos(h), np.sin(h)
+        w, q = cx * cy * cz + sx * sy * sz, np.array([sx * cy * cz - cx * sy * sz, cx * sy * cz + sx * cy * sz, cx * cy * sz - sx * sy * cz])
+
+        def rot(v):  # glm: v + 2 * (w * (q x v) + q x (q x v))
+            uv = np.cross(q, v)
+            return v + 2.0 * (w * uv + np.cross(q, uv))
+
+        half_h = np.tan(a[7] / 2.0)
+        half_w = a[8] * half_h
+        zero = np.zeros(3)
+        # ndc = p / size * 2 - 1; camera-space direction (-ndc.x * half_w, ndc.y * half_h, 1)
+        return RayCamera.from_fields(a[0:3] + rot(np.array([0.0, 0.0, -a[6]])), zero, zero, rot(np.array([half_w, -half_h, 1.0])),
+                                     rot(np.array([-2.0 * half_w / W, 0.0, 0.0])), rot(np.array([0.0, 2.0 * half_h / H, 0.0])))
+
+    def tile(self, x_off: int, y_off: int) -> "RayCamera":
+        """The same camera for a tile whose pixel (0, 0) is pixel (x_off, y_off) of this camera's frame (offsets add up)."""
+        c = RayCamera.from_buffer_copy(self)
+        c.x_off, c.y_off = self.x_off + int(x_off), self.y_off + int(y_off)
+        return c
+
+    def as_array(self) -> np.ndarray:
+        """The 80 bytes as a (20,) float32 array (the offsets' bits in the last two elements)."""
+        return np.frombuffer(bytes(self), np.float32).copy()
+
+
+def raycam_array(cams) -> np.ndarray:
+    """A batch of ray cameras as a contiguous (B, 20) float32 array of CgrtRayCamera records (the two int32 offsets by bit pattern):
+    from a RayCamera, a sequence of RayCamera, or such an array (ValueError otherwise)."""
+    if isinstance(cams, RayCamera):
+        cams = [cams]
+    if isinstance(cams, np.ndarray):
+        a = np.ascontiguousarray(cams)
+        if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != 20:
+            raise ValueError(f"ray cameras as an array must be (B, 20) float32 records, not {a.dtype} {a.shape}")
+        return a
+    cams = list(cams)
+    if not all(isinstance(c, RayCamera) for c in cams):
+        raise ValueError("cams must be a RayCamera, a sequence of RayCamera or a (B, 20) float32 array of records")
+    return np.ascontiguousarray(np.stack([c.as_array() for c in cams]) if cams else np.zeros((0, 20), np.float32))
+
+
 HOST_LIB_PATH = os.path.join(_HERE, "lib", "libcgrt_host.so")
 
 
@@ -132,7 +230,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -223,6 +321,11 @@ def lib() -> C.CDLL:
     L.cgrt_render_views_aov_device.argtypes = L.cgrt_render_views_device.argtypes + [C.POINTER(AovOut)]
     L.cgrt_enqueue_render_aov_device.argtypes = L.cgrt_enqueue_render_device.argtypes + [C.POINTER(AovOut)]
     L.cgrt_enqueue_render_views_aov_device.argtypes = L.cgrt_enqueue_render_views_device.argtypes + [C.POINTER(AovOut)]
+    L.cgrt_generate_rays_raycam.argtypes = [vp, vp, i32, i32, vp]
+    L.cgrt_trace_primary_raycams_device.argtypes = L.cgrt_trace_primary_views_device.argtypes
+    L.cgrt_render_raycams_device.argtypes = L.cgrt_render_views_aov_device.argtypes
+    L.cgrt_enqueue_render_raycams_device.argtypes = L.cgrt_enqueue_render_views_aov_device.argtypes
+    L.cgrt_render_raycams_light_sets_device.argtypes = L.cgrt_render_views_light_sets_device.argtypes
     L.cgrt_enqueue_stats.argtypes = [vp, u64, C.POINTER(RenderStats)]
     L.cgrt_debug_strided_waves.argtypes = []
     L.cgrt_occluded.argtypes = [vp, vp, u64, vp]
@@ -1252,6 +1355,105 @@ class Scene:
             )
         )  # fmt: skip
         return out, t.value, planes
+
+    # ---- ray cameras (include/cgrt.h CgrtRayCamera, cgrt_*_raycam*) ----
+    def generate_rays_raycam(self, cam: "RayCamera", W: int, H: int) -> np.ndarray:
+        """cgrt_generate_rays_raycam: the W*H rays of a ray camera's frame, row-major, as a RAY_DTYPE array."""
+        a = raycam_array(cam)
+        if len(a) != 1:
+            raise ValueError("generate_rays_raycam takes one camera")
+        rays = np.zeros(max(W, 0) * max(H, 0), RAY_DTYPE)
+        _check(lib().cgrt_generate_rays_raycam(self._h, _ptr(a), W, H, _ptr(rays)))
+        return rays
+
+    def trace_raycams_device(self, cams, W: int, H: int, d_hits_ptr: int, d_normals_ptr: int = 0, stream: int = 0) -> None:
+        """cgrt_trace_primary_raycams_device: trace_views_device for B ray cameras (a RayCamera, a sequence of them or raycam_array's
+        records); asynchronous on `stream`, the cameras reusable at once."""
+        a = raycam_array(cams)
+        _check(
+            lib().cgrt_trace_primary_raycams_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, C.c_void_p(d_hits_ptr) if d_hits_ptr else None,
+                C.c_void_p(d_normals_ptr) if d_normals_ptr else None, C.c_void_p(stream) if stream else None,
+            )
+        )  # fmt: skip
+
+    def render_raycams_device(self, cams, W: int, H: int, d_out_ptr: int, format="rgb", stream: int = 0, lights=None, max_level: int = 2,
+                              spherical=None, units=None, samples: int = 200, seed: int = 0, aov=None, chw: bool = False) -> dict:
+        """cgrt_render_raycams_device: render_views_device for B ray cameras; with `aov` (a dict plane name -> device address, as
+        render_views_aov_device) the views' geometry buffers are written by the same call.  Raw integers.  Returns stats."""
+        a = raycam_array(cams)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        st = RenderStats()
+        _check(
+            lib().cgrt_render_raycams_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, _ptr(lights), len(lights), q, max_level,
+                C.c_void_p(d_out_ptr) if d_out_ptr else None, _frame_format(format), C.c_void_p(stream) if stream else None, C.byref(st),
+                self._aov_arg(aov, chw),
+            )
+        )  # fmt: skip
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def render_raycams_light_sets_device(self, cams, W: int, H: int, d_out_ptr: int, light_sets, spherical_sets=None, units=None,
+                                         samples: int = 200, seed: int = 0, max_level: int = 2, format="rgb", stream: int = 0) -> dict:
+        """cgrt_render_raycams_light_sets_device: render_views_light_sets_device for B ray cameras.  Returns the stats dict."""
+        a = raycam_array(cams)
+        q, keep = self._light_sets_arg(light_sets, spherical_sets)  # noqa: F841
+        s, keep_s = self._light_sets_soft(spherical_sets, units, samples, seed)  # noqa: F841
+        st = RenderStats()
+        _check(
+            lib().cgrt_render_raycams_light_sets_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, C.byref(q), s, max_level, C.c_void_p(d_out_ptr) if d_out_ptr else None,
+                _frame_format(format), C.c_void_p(stream) if stream else None, C.byref(st),
+            )
+        )  # fmt: skip
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def render_raycams_tensor(self, cams, W: int, H: int, format="rgb", out=None, stream=None, aovs=None, chw: bool = False, aov_out=None,
+                              light_sets=None, **kw):
+        """render_views_tensor for B ray cameras: (B, H, W, 3) f32, (B, 3, H, W) f32 or (B, H, W, 4) u8 on cuda:<device>, `out` and
+        `stream` as there.  aovs= (a subset of AOV_NAMES; chw, aov_out as render_views_aov_tensor) also returns the geometry buffers:
+        (tensor, stats, planes).  light_sets= (a sequence of light arrays; spherical_sets and the other keywords as
+        render_views_light_sets_tensor) renders every camera under every set: a (B, S, ...) tensor; not together with aovs.  Otherwise
+        the keywords are render_views'.  Returns (tensor, stats dict)."""
+        a = raycam_array(cams)
+        if light_sets is not None:
+            if aovs is not None:
+                raise ValueError("geometry buffers do not depend on the lights: render them without light_sets")
+            light_sets = list(light_sets)
+            self._light_sets_arg(light_sets, kw.get("spherical_sets"))  # (its checks, before any call)
+            out, fmt, stream = self._batch_tensor((len(a), len(light_sets)), W, H, format, out, stream)
+            st = self.render_raycams_light_sets_device(a, W, H, out.data_ptr(), light_sets, format=fmt, stream=stream.cuda_stream, **kw)
+            return out, st
+        plan = None if aovs is None else self._aov_plan((len(a),), W, H, aovs, chw, aov_out)
+        out, fmt, stream = self._batch_tensor((len(a),), W, H, format, out, stream)
+        if plan is None:
+            return out, self.render_raycams_device(a, W, H, out.data_ptr(), format=fmt, stream=stream.cuda_stream, **kw)
+        planes = self._aov_tensors(plan, stream)
+        st = self.render_raycams_device(a, W, H, out.data_ptr(), format=fmt, stream=stream.cuda_stream,
+                                        aov={n: t.data_ptr() for n, t in planes.items()}, chw=chw, **kw)
+        return out, st, planes
+
+    def enqueue_render_raycams_tensor(self, cams, W: int, H: int, format="rgb", out=None, stream=None, aovs=None, chw: bool = False,
+                                      aov_out=None, lights=None, max_level: int = 2, spherical=None, units=None, samples: int = 200,
+                                      seed: int = 0):
+        """render_raycams_tensor without waiting for the GPU (cgrt_enqueue_render_raycams_device), under the rules of
+        enqueue_render_views_tensor.  Returns (tensor, ticket), with aovs= (tensor, ticket, planes)."""
+        a = raycam_array(cams)
+        plan = None if aovs is None else self._aov_plan((len(a),), W, H, aovs, chw, aov_out)
+        out, fmt, stream = self._batch_tensor((len(a),), W, H, format, out, stream)
+        planes = None if plan is None else self._aov_tensors(plan, stream)
+        lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
+        q, keep = self._soft_arg(spherical, units, samples, seed)  # noqa: F841
+        t = C.c_uint64()
+        _check(
+            lib().cgrt_enqueue_render_raycams_device(
+                self._h, _ptr(a) if len(a) else None, len(a), W, H, _ptr(lights), len(lights), q, max_level, C.c_void_p(out.data_ptr()), fmt,
+                C.c_void_p(stream.cuda_stream) if stream.cuda_stream else None, C.byref(t),
+                None if planes is None else self._aov_arg({n: p.data_ptr() for n, p in planes.items()}, chw),
+            )
+        )  # fmt: skip
+        return (out, t.value) if planes is None else (out, t.value, planes)
 
     # ---- visibility queries (include/cgrt.h cgrt_occluded*, cgrt_in_shadow*, cgrt_soft_lit*; DESIGN.md section 5.12) ----
     def occluded(self, rays) -> np.ndarray:

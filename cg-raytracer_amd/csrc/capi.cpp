@@ -1638,8 +1638,32 @@ static int views_extent_args(uint32_t nviews, int W, int H) {
     if (!make_views_frame(W, H, nviews, 64, F)) return fail(CGRT_E_ARG, "batch too large: more than 2^18 64x64 super-tiles over all views");
     return CGRT_OK;
 }
-static int views_args(const CgrtCamera* cams, uint32_t nviews, int W, int H) {
+// A batch of ray cameras (include/cgrt.h CgrtRayCamera), checked where the Trackball entries check `cams`: every field finite, a direction
+// that is not identically zero, offsets that keep x + x_off and y + y_off exactly convertible to f32.
+static int raycams_check(const CgrtRayCamera* cams, uint32_t nviews, int W, int H) {
+    for (uint32_t b = 0; b < nviews; b++) {
+        const CgrtRayCamera& c = cams[b];
+        const float* f = c.origin;  // (the 18 floats are contiguous: static_assert below)
+        for (int k = 0; k < 18; k++)
+            if (!std::isfinite(f[k])) return fail(CGRT_E_ARG, "ray camera with a non-finite field");
+        bool any = false;
+        for (int k = 9; k < 18; k++) any = any || f[k] != 0.0f;
+        if (!any) return fail(CGRT_E_ARG, "ray camera whose dir, dir_dx and dir_dy are all zero");
+        const long long lim = 1ll << 24;
+        if (std::llabs((long long)c.x_off) + (W > 0 ? W : 0) > lim || std::llabs((long long)c.y_off) + (H > 0 ? H : 0) > lim)
+            return fail(CGRT_E_ARG, "ray camera offsets: |x_off| + W or |y_off| + H exceeds 2^24");
+    }
+    return CGRT_OK;
+}
+static_assert(sizeof(CgrtRayCamera) == 80 && offsetof(CgrtRayCamera, x_off) == 72, "CgrtRayCamera: 18 contiguous floats, two offsets");
+static_assert(sizeof(CgrtRayCamera) == sizeof(RayCameraDev), "the device table holds the caller's records as they are");
+// (ray: the batch's cameras are ray cameras, `cams` the same pointer)
+static int views_args(const void* cams, uint32_t nviews, int W, int H, const CgrtRayCamera* ray = nullptr) {
     if (!cams) return fail(CGRT_E_ARG, "cams is NULL");
+    if (ray) {
+        const int rc = raycams_check(ray, nviews, W, H);
+        if (rc) return rc;
+    }
     if (nviews == 0) return fail(CGRT_E_ARG, "nviews must be at least 1");
     if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
     return views_extent_args(nviews, W, H);
@@ -1649,12 +1673,26 @@ static std::vector<CameraDev> view_cameras(const CgrtCamera* cams, uint32_t nvie
     for (uint32_t b = 0; b < nviews; b++) v[b] = make_camera(cams[b]);
     return v;
 }
+// The device table of a batch, as bytes: CameraDev per Trackball view, or the caller's ray cameras as they are (RayCameraDev).
+static std::vector<uint8_t> view_table(const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews) {
+    std::vector<uint8_t> t;
+    if (raycams) {
+        t.resize((size_t)nviews * sizeof(RayCameraDev));
+        std::memcpy(t.data(), raycams, t.size());
+    } else {
+        const std::vector<CameraDev> v = view_cameras(cams, nviews);
+        t.resize(v.size() * sizeof(CameraDev));
+        std::memcpy(t.data(), v.data(), t.size());
+    }
+    return t;
+}
 static int check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, const char* name);
 
-int cgrt_trace_primary_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, CgrtHit* d_hits, float* d_normals,
-                                    void* stream) {
+// cgrt_trace_primary_views_device and its ray-camera twin (exactly one of cams, raycams)
+static int trace_views_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H, CgrtHit* d_hits,
+                              float* d_normals, void* stream) {
     if (!s || !d_hits) return fail(CGRT_E_ARG, "NULL argument");
-    int rc = views_args(cams, nviews, W, H);
+    int rc = views_args(raycams ? static_cast<const void*>(raycams) : cams, nviews, W, H, raycams);
     if (rc) return rc;
     if ((uintptr_t)d_hits % 4 || (uintptr_t)d_normals % 4) return fail(CGRT_E_ARG, "d_hits / d_normals not 4-byte aligned");
     NEED_DEVICE(s);
@@ -1664,8 +1702,8 @@ int cgrt_trace_primary_views_device(CgrtScene* s, const CgrtCamera* cams, uint32
     if (d_normals && (rc = check_device_span(s, d_normals, npix * 12, "d_normals"))) return rc;
     FrameDev F;
     (void)make_views_frame(W, H, nviews, trace_block(s->dev), F);
-    const std::vector<CameraDev> tab = view_cameras(cams, nviews);
-    const size_t bytes = tab.size() * sizeof(CameraDev);
+    const std::vector<uint8_t> tab = view_table(cams, raycams, nviews);
+    const size_t bytes = tab.size();
     hipStream_t const st = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> lk(s->vtab_mutex);
     CgrtScene::ViewTable& T = s->vtab[s->vtab_seq++ & 3u];
@@ -1683,11 +1721,19 @@ int cgrt_trace_primary_views_device(CgrtScene* s, const CgrtCamera* cams, uint32
     }
     std::memcpy(T.pin, tab.data(), bytes);
     HIP_TRY(hipMemcpyAsync(T.dev, T.pin, bytes, hipMemcpyHostToDevice, st));
-    F.views = static_cast<const CameraDev*>(T.dev);
-    HIP_TRY(launch_trace_primary_views(s->dev, F, reinterpret_cast<CgrtHitDev*>(d_hits), d_normals, st));
+    F.views = static_cast<const CameraDev*>(T.dev);  // (F.raycams: the same slot)
+    HIP_TRY(launch_trace_primary_views(s->dev, F, reinterpret_cast<CgrtHitDev*>(d_hits), d_normals, st, raycams != nullptr));
     HIP_TRY(hipEventRecord(T.done, st));
     T.pending = true;
     return CGRT_OK;
+}
+int cgrt_trace_primary_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, CgrtHit* d_hits, float* d_normals,
+                                    void* stream) {
+    return trace_views_device(s, cams, nullptr, nviews, W, H, d_hits, d_normals, stream);
+}
+int cgrt_trace_primary_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, CgrtHit* d_hits, float* d_normals,
+                                      void* stream) {
+    return trace_views_device(s, nullptr, cams, nviews, W, H, d_hits, d_normals, stream);
 }
 
 int cgrt_trace_primary(CgrtScene* s, const CgrtCamera* cam, int W, int H, int x0, int y0, int x1, int y1, int rank, int nranks,
@@ -1737,6 +1783,29 @@ int cgrt_generate_rays(CgrtScene* s, const CgrtCamera* cam, int W, int H, int x0
     void* dr;
     HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
     HIP_TRY(launch_generate_rays(make_camera(*cam), W, H, x0, y0, x1, y1, static_cast<float*>(dr), g.L->stream));
+    void* sr = nullptr;
+    HIP_TRY(lane_download(g, 0, rays, dr, n * sizeof(CgrtRay), &sr));
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    if (sr) std::memcpy(rays, sr, n * sizeof(CgrtRay));
+    return CGRT_OK;
+}
+
+int cgrt_generate_rays_raycam(CgrtScene* s, const CgrtRayCamera* cam, int W, int H, CgrtRay* rays) {
+    if (!s || !cam || !rays) return fail(CGRT_E_ARG, "NULL argument");
+    int rc = raycams_check(cam, 1, W, H);
+    if (rc) return rc;
+    FrameDev F;
+    if (!make_frame(W, H, 0, 0, W, H, 0, 1, CGRT_BLOCK, F)) return fail(CGRT_E_ARG, "bad frame size");
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)W * (size_t)H;
+    LaneGuard g(s);
+    if ((rc = g.acquire())) return rc;
+    void* dr;
+    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
+    RayCameraDev C;
+    std::memcpy(&C, cam, sizeof(C));
+    HIP_TRY(launch_generate_rays_raycam(C, W, H, static_cast<float*>(dr), g.L->stream));
     void* sr = nullptr;
     HIP_TRY(lane_download(g, 0, rays, dr, n * sizeof(CgrtRay), &sr));
     HIP_TRY(hipStreamSynchronize(g.L->stream));
@@ -1962,6 +2031,8 @@ struct ListSrc {
 struct ViewSrc {
     const CgrtCamera* cams;
     uint32_t n;
+    const CgrtRayCamera* raycams = nullptr;  // the batch's cameras are ray cameras (cgrt_*_raycams*; cams is NULL): the RAYCAM kernels
+    size_t table_bytes() const { return (size_t)n * (raycams ? sizeof(RayCameraDev) : sizeof(CameraDev)); }
 };
 // One camera under nsets light sets instead of one light list (cgrt_render_light_sets*): the batch's plan, built on
 // the host from the caller's CSR arrays (plan_light_sets).  A pixel's ray tree does not depend on the lights, so level 0, every level's
@@ -2168,10 +2239,10 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     }
     const CameraDev C = (list || views) ? CameraDev{} : make_camera(*cam);
     if (views) {  // (the table of the VIEWS kernels; this call waits for its frame, so the slot is free again when it returns)
-        const std::vector<CameraDev> tab = view_cameras(views->cams, nviews);
-        HIP_TRY(dviews.alloc(tab.size() * sizeof(CameraDev)));
-        HIP_TRY(hipMemcpy(dviews.p, tab.data(), tab.size() * sizeof(CameraDev), hipMemcpyHostToDevice));
-        F.views = dviews.as<CameraDev>();
+        const std::vector<uint8_t> tab = view_table(views->cams, views->raycams, nviews);
+        HIP_TRY(dviews.alloc(tab.size()));
+        HIP_TRY(hipMemcpy(dviews.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+        F.views = dviews.as<CameraDev>();  // (F.raycams: the same slot)
         Q.view_pixels = (uint32_t)W * (uint32_t)H;
     }
     CgrtScene::RenderAux& aux = s->raux;  // second stream + the events that order it against the default stream
@@ -2422,7 +2493,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                 st.primary_rays = n;
             } else if (views) {  // (also clears every view's pixels)
                 HIP_TRY(launch_trace_primary_views_compact(s->dev, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(),
-                                                           primary_hits, frame_rgb, nullptr));
+                                                           primary_hits, frame_rgb, nullptr, views->raycams != nullptr));
                 st.primary_rays = (unsigned long long)W * H * nviews;
             } else {
                 HIP_TRY(launch_trace_primary_compact(s->dev, C, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
@@ -2827,11 +2898,11 @@ int cgrt_render_aov_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, co
 
 // ---- renderRayTracing's per-pixel loop for a batch of cameras (render_impl, ViewSrc; include/cgrt.h cgrt_render_views*) ----
 // cgrt_render_device's checks without aa / rank / row_bytes, with the batch's own (views_args) in place of the frame size check.
-static int render_views_args(const CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
-                             const CgrtSoftShadows* soft, int max_level, const void* out) {
+static int render_views_args(const CgrtScene* s, const void* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                             const CgrtSoftShadows* soft, int max_level, const void* out, const CgrtRayCamera* ray = nullptr) {
     if (!s || !out) return fail(CGRT_E_ARG, "NULL argument");
     if (nlights && !lights) return fail(CGRT_E_ARG, "nlights > 0 but lights is NULL");
-    const int rc = views_args(cams, nviews, W, H);
+    const int rc = views_args(cams, nviews, W, H, ray);
     if (rc) return rc;
     if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
     if (soft && soft->nspherical &&
@@ -2848,10 +2919,11 @@ int cgrt_render_views(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int
     return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, rgb, stats, nullptr, nullptr, false, nullptr, nullptr, &V);
 }
 // cgrt_render_views_device's checks (cgrt_enqueue_render_views_device: the same); D->pitch and D->view_bytes are set
-static int render_views_device_args(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+// (ray: the cameras are ray cameras, `cams` the same pointer)
+static int render_views_device_args(CgrtScene* s, const void* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
                                     const CgrtSoftShadows* soft, int max_level, void* d_out, int format, DeviceOut* D, bool with_aov = false,
-                                    const CgrtAovOut* aov = nullptr) {
-    int rc = render_views_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out);
+                                    const CgrtAovOut* aov = nullptr, const CgrtRayCamera* ray = nullptr) {
+    int rc = render_views_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, ray);
     if (rc) return rc;
     uint64_t extent = 0;
     if ((rc = export_args(d_out, W, H, format, 0, &D->pitch, &extent))) return rc;
@@ -2948,12 +3020,14 @@ int cgrt_render_light_sets_device(CgrtScene* s, const CgrtCamera* cam, int W, in
 // ---- nviews cameras under a batch of light sets (render_impl / enqueue_impl with a ViewSrc and a LightSetSrc; include/cgrt.h
 // cgrt_render_views_light_sets*) ----
 // Every check of include/cgrt.h's list, in its order, all CGRT_E_ARG and before any device work; then *P holds the batch's plan.
-static int views_light_sets_args(const CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
-                                 const CgrtSoftShadows* soft, int max_level, const void* out, LightSetSrc* P) {
+// (ray: the cameras are ray cameras, `cams` the same pointer, checked where cams is)
+static int views_light_sets_args(const CgrtScene* s, const void* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
+                                 const CgrtSoftShadows* soft, int max_level, const void* out, LightSetSrc* P, const CgrtRayCamera* ray = nullptr) {
     if (!s || !cams || !sets || !out) return fail(CGRT_E_ARG, "NULL argument");
-    if (nviews == 0) return fail(CGRT_E_ARG, "nviews must be at least 1");
-    int rc = sets_rules(sets, soft);
+    int rc = ray ? raycams_check(ray, nviews, W, H) : CGRT_OK;
     if (rc) return rc;
+    if (nviews == 0) return fail(CGRT_E_ARG, "nviews must be at least 1");
+    if ((rc = sets_rules(sets, soft))) return rc;
     if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
     if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
     if ((rc = views_extent_args(nviews, W, H))) return rc;
@@ -2964,9 +3038,10 @@ static int views_light_sets_args(const CgrtScene* s, const CgrtCamera* cams, uin
     return CGRT_OK;
 }
 // the device forms' checks (blocking and enqueued): D->pitch and D->view_bytes are set
-static int views_light_sets_device_args(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
-                                        const CgrtSoftShadows* soft, int max_level, void* d_out, int format, LightSetSrc* P, DeviceOut* D) {
-    int rc = views_light_sets_args(s, cams, nviews, W, H, sets, soft, max_level, d_out, P);
+static int views_light_sets_device_args(CgrtScene* s, const void* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
+                                        const CgrtSoftShadows* soft, int max_level, void* d_out, int format, LightSetSrc* P, DeviceOut* D,
+                                        const CgrtRayCamera* ray = nullptr) {
+    int rc = views_light_sets_args(s, cams, nviews, W, H, sets, soft, max_level, d_out, P, ray);
     if (rc) return rc;
     uint64_t extent = 0;
     if ((rc = export_args(d_out, W, H, format, 0, &D->pitch, &extent))) return rc;
@@ -2992,6 +3067,27 @@ int cgrt_render_views_light_sets_device(CgrtScene* s, const CgrtCamera* cams, ui
     const int rc = views_light_sets_device_args(s, cams, nviews, W, H, sets, soft, max_level, d_out, format, &P, &D);
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
+    return render_impl(s, nullptr, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false,
+                       &D, nullptr, &V, &P);
+}
+
+// ---- ray cameras (include/cgrt.h CgrtRayCamera): the views entries with a ViewSrc that carries ray cameras ----
+int cgrt_render_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                               const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats,
+                               const CgrtAovOut* aov) {
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D, aov != nullptr, aov, cams);
+    if (rc) return rc;
+    const ViewSrc V{nullptr, nviews, cams};
+    return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, &D, nullptr, &V, nullptr, aov);
+}
+int cgrt_render_raycams_light_sets_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
+                                          const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats) {
+    LightSetSrc P;
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    const int rc = views_light_sets_device_args(s, cams, nviews, W, H, sets, soft, max_level, d_out, format, &P, &D, cams);
+    if (rc) return rc;
+    const ViewSrc V{nullptr, nviews, cams};
     return render_impl(s, nullptr, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false,
                        &D, nullptr, &V, &P);
 }
@@ -3132,7 +3228,7 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t o_lights = 0, o_slights = up16((size_t)L * 24), o_units = o_slights + up16((size_t)SL * 28),
                  o_spawn = o_units + up16(SL ? (size_t)soft->nunits * 12 : 0), o_views = o_spawn + up16(sizeof(SpawnDev)),
-                 o_sets = o_views + up16(views ? (size_t)nviews * sizeof(CameraDev) : 0),
+                 o_sets = o_views + up16(views ? views->table_bytes() : 0),
                  table_bytes = o_sets + (sets ? sets->table.size() * 4 : 0);
     if (slot.cap < table_bytes) {
         if (slot.pin) (void)hipHostFree(slot.pin);
@@ -3198,9 +3294,9 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
         std::memcpy(pin + o_spawn, &SP, sizeof(SP));
     }
     if (views) {
-        const std::vector<CameraDev> vt = view_cameras(views->cams, nviews);
-        std::memcpy(pin + o_views, vt.data(), vt.size() * sizeof(CameraDev));
-        F.views = reinterpret_cast<CameraDev*>(tab + o_views);
+        const std::vector<uint8_t> vt = view_table(views->cams, views->raycams, nviews);
+        std::memcpy(pin + o_views, vt.data(), vt.size());
+        F.views = reinterpret_cast<CameraDev*>(tab + o_views);  // (F.raycams: the same slot)
     }
     // ---- the frame, on the caller's stream ----
     if (s->enq_pending) HIP_TRY(hipStreamWaitEvent(stream, s->enq_done, 0));
@@ -3227,7 +3323,7 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
                                                   ipix.as<int>(), primary_hits, frame_rgb, stream));
             else if (views)  // (also clears every view's pixels)
                 HIP_TRY(launch_trace_primary_views_compact(s->dev, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
-                                                           ipix.as<int>(), primary_hits, frame_rgb, stream));
+                                                           ipix.as<int>(), primary_hits, frame_rgb, stream, views->raycams != nullptr));
             else  // (also clears this rank's pixels, and spawns level 0)
                 HIP_TRY(launch_trace_primary_compact(s->dev, make_camera(*cam), F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
                                                      ipix.as<int>(), pair, stream, nullptr, frame_rgb,
@@ -3343,6 +3439,15 @@ int cgrt_enqueue_render_views_aov_device(CgrtScene* s, const CgrtCamera* cams, u
     const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D, true, aov);
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
+    return enqueue_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream, ticket, nullptr, aov);
+}
+int cgrt_enqueue_render_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
+                                       const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, uint64_t* ticket,
+                                       const CgrtAovOut* aov) {
+    DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream), 0};
+    const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D, aov != nullptr, aov, cams);
+    if (rc) return rc;
+    const ViewSrc V{nullptr, nviews, cams};
     return enqueue_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream, ticket, nullptr, aov);
 }
 int cgrt_enqueue_render_views_light_sets_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,

@@ -151,6 +151,14 @@ struct CameraDev {
     float q[4];  // w x y z
     float half_w, half_h;
 };
+// A ray camera (include/cgrt.h CgrtRayCamera, the same 80 bytes): the ray of pixel (x, y) is affine in the pixel, origin
+// and unnormalised direction both (walk_exact.h primary_ray).  Nothing is evaluated on the host.
+struct RayCameraDev {
+    float origin[3], origin_dx[3], origin_dy[3];
+    float dir[3], dir_dx[3], dir_dy[3];
+    int32_t x_off, y_off;
+};
+static_assert(sizeof(RayCameraDev) == 80, "RayCameraDev must be 80 B");
 
 // Frame decomposition.  The rectangle is cut into 8x8-pixel tiles (one wave each) grouped into
 // super-tiles of 8x8 tiles (64x64 pixels).  Super-tile i (row-major) belongs to rank i % nranks, and
@@ -208,8 +216,12 @@ struct FrameDev {
     uint32_t hint_wgen;    // generation this frame stamps on what it writes
     // Multi-view frames (cgrt_*_views*; read only by the VIEWS instantiations): nst_rank super-tiles = nviews x view_st,
     // super-tile s of that one list is super-tile s % view_st of view s / view_st, traced with camera views[s / view_st] (device
-    // memory) and written at pixel view * W * H + y * W + x.  Whole frames, one rank.
-    const CameraDev* views;
+    // memory) and written at pixel view * W * H + y * W + x.  Whole frames, one rank.  The RAYCAM instantiations read the table as
+    // raycams[s / view_st] instead (the same argument slot: the kernel arguments of every other instantiation stay what they were).
+    union {
+        const CameraDev* views;
+        const RayCameraDev* raycams;
+    };
     uint32_t view_st;      // super-tiles per view (st_x * st_y)
 };
 static const int ST_TILES = 8;  // tiles per super-tile side

@@ -77,6 +77,8 @@ hipError_t launch_trace_pair(const SceneDev& S, const float* srays, const float*
 // *flag = value (system scope) once everything queued on the stream before it has finished
 hipError_t launch_signal(uint32_t* flag, uint32_t value, hipStream_t stream);
 hipError_t launch_generate_rays(const CameraDev& C, int W, int H, int x0, int y0, int x1, int y1, float* rays, hipStream_t stream);
+// the rays of a ray camera's whole W x H frame, row-major (cgrt_generate_rays_raycam)
+hipError_t launch_generate_rays_raycam(const RayCameraDev& C, int W, int H, float* rays, hipStream_t stream);
 // lit[item * nlights + l] += samples of spherical light l that reach it from item's hit point (zeroed by the caller)
 hipError_t launch_soft_shadow(const SceneDev& S, const SoftDev& Q, const float* rays, const CgrtHitDev* hits, const int* item_pixels,
                               unsigned long long nitems, uint32_t* lit, int anyhit, hipStream_t stream);
@@ -95,9 +97,10 @@ hipError_t launch_trace_primary_compact(const SceneDev& S, const CameraDev& C, c
                                         float* rgb = nullptr, const SpawnDev* spawn = nullptr);  // spawn (device memory): level 0's k_spawn fused in (spawn_rays.h)  // rgb (optional): the rank's pixels are cleared by the same kernel
 // multi-view frames (F.views set, F.nst_rank = nviews x F.view_st: capi.cpp make_views_frame): the VIEWS instantiations of the two
 // primary kernels, pixel = view * W * H + y * W + x.  No counters, no hints, no fused spawn; the kernel shape as for a frame.
-hipError_t launch_trace_primary_views(const SceneDev& S, const FrameDev& F, CgrtHitDev* hits, float* normals, hipStream_t stream);
+// raycams: the table is F.raycams (ray cameras, cgrt_*_raycams*: the RAYCAM instantiations) instead of F.views.
+hipError_t launch_trace_primary_views(const SceneDev& S, const FrameDev& F, CgrtHitDev* hits, float* normals, hipStream_t stream, bool raycams = false);
 hipError_t launch_trace_primary_views_compact(const SceneDev& S, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals, int* pixels,
-                                              uint32_t* count, float* rgb, hipStream_t stream);
+                                              uint32_t* count, float* rgb, hipStream_t stream, bool raycams = false);
 // level 0 of the shading wavefront from a caller's list of n rays (cgrt_shade_rays, k_trace_list_compact): rgb[3i..3i+2] := 0 for every
 // i, the rays that hit appended to the compact list {rays, hits, normals, pixels = i}; count = one zeroed device word.  Laid out by the
 // list's shape (list_shape), as launch_trace_batch.

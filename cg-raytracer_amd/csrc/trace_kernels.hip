@@ -52,10 +52,13 @@ __device__ __forceinline__ size_t view_pixel(const FrameDev& F, uint32_t view, i
 // kernel it was (the hint code costs every launch a few percent when it is merely compiled in: measured).
 // VIEWS: a multi-view frame (FrameDev::views, cgrt_trace_primary_views_device) -- also an instantiation of its own, for the same
 // reason; each wave reads its view's camera from the device table (C is not used) and writes at view_pixel.  Never with HINT.
-template <bool COUNT, bool FAST, bool QUAD = false, bool HINT = false, bool VIEWS = false>
+// RAYCAM (with VIEWS only): the table holds ray cameras (FrameDev::raycams, cgrt_*_raycams*) -- again instantiations of their own.  The
+// wave reads its 80-byte entry before the walk; only o and d live through it.
+template <bool COUNT, bool FAST, bool QUAD = false, bool HINT = false, bool VIEWS = false, bool RAYCAM = false>
 __global__ CGRT_LB void k_trace_primary(SceneDev S, CameraDev C, FrameDev F, CgrtHitDev* __restrict__ hits, float* __restrict__ normals,
                                         unsigned long long* counters) {
     static_assert(!(HINT && VIEWS), "multi-view frames take no hints");
+    static_assert(VIEWS || !RAYCAM, "ray cameras come from the views table");
     extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
     int x = 0, y = 0;
     size_t pidx;
@@ -72,7 +75,11 @@ __global__ CGRT_LB void k_trace_primary(SceneDev S, CameraDev C, FrameDev F, Cgr
     }
     LaneCounters cnt;
     F3 o = f3(0, 0, 0), d = f3(0, 0, 0);
-    if (active) primary_ray(VIEWS ? F.views[view] : C, F.W, F.H, x, y, o, d);
+    if (RAYCAM) {
+        if (active) primary_ray(F.raycams[view], x, y, o, d);
+    } else if (active) {
+        primary_ray(VIEWS ? F.views[view] : C, F.W, F.H, x, y, o, d);
+    }
     float t = 3.402823466e+38f;  // std::numeric_limits<float>::max(), trackball.cpp:101
     uint32_t hit_rec = REF_NONE;
     if (QUAD)
@@ -93,10 +100,12 @@ __global__ CGRT_LB void k_trace_primary(SceneDev S, CameraDev C, FrameDev F, Cgr
 // finish roughly in launch order, so the list keeps the frame's tile order).  Pixels that miss need no further work upstream
 // either (main.cpp:293: black).  count = one zeroed device word.
 // VIEWS: a multi-view frame (k_trace_primary's VIEWS): camera per view from F.views, pixels (and rgb) at view_pixel.
-template <bool COUNT, bool FAST, bool QUAD = false, bool VIEWS = false>
+// RAYCAM (with VIEWS only): ray cameras from F.raycams (k_trace_primary's RAYCAM).
+template <bool COUNT, bool FAST, bool QUAD = false, bool VIEWS = false, bool RAYCAM = false>
 __global__ CGRT_LB void k_trace_primary_compact(SceneDev S, CameraDev C, FrameDev F, float* __restrict__ rays, CgrtHitDev* __restrict__ hits,
                                                 float* __restrict__ normals, int* __restrict__ pixels, uint32_t* __restrict__ count,
                                                 unsigned long long* counters, float* __restrict__ rgb, const SpawnDev* __restrict__ spawn_dev) {
+    static_assert(VIEWS || !RAYCAM, "ray cameras come from the views table");
     extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
     const int lane = threadIdx.x & 63;
     int x = 0, y = 0;
@@ -112,7 +121,11 @@ __global__ CGRT_LB void k_trace_primary_compact(SceneDev S, CameraDev C, FrameDe
     CgrtHitDev h;
     h.hit = 0;
     F3 o = f3(0, 0, 0), d = f3(0, 0, 0), nn = f3(0, 0, 0);
-    if (active) primary_ray(VIEWS ? F.views[view] : C, F.W, F.H, x, y, o, d);
+    if (RAYCAM) {
+        if (active) primary_ray(F.raycams[view], x, y, o, d);
+    } else if (active) {
+        primary_ray(VIEWS ? F.views[view] : C, F.W, F.H, x, y, o, d);
+    }
     float t = 3.402823466e+38f;  // std::numeric_limits<float>::max(), trackball.cpp:101
     uint32_t hit_rec = REF_NONE;
     if (QUAD)
@@ -788,6 +801,22 @@ __global__ __launch_bounds__(CGRT_BLOCK) void k_generate_rays(CameraDev C, int W
     r[5] = d.z;
     r[6] = 3.402823466e+38f;
 }
+// k_generate_rays for a ray camera (cgrt_generate_rays_raycam): the whole W x H frame, row-major.
+__global__ __launch_bounds__(CGRT_BLOCK) void k_generate_rays_raycam(RayCameraDev C, int W, int H, float* __restrict__ rays) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * CGRT_BLOCK + threadIdx.x;
+    const unsigned long long n = (unsigned long long)W * (unsigned long long)H;
+    if (i >= n) return;
+    F3 o, d;
+    primary_ray(C, (int)(i % (unsigned long long)W), (int)(i / (unsigned long long)W), o, d);
+    float* r = rays + 7 * i;
+    r[0] = o.x;
+    r[1] = o.y;
+    r[2] = o.z;
+    r[3] = d.x;
+    r[4] = d.y;
+    r[5] = d.z;
+    r[6] = 3.402823466e+38f;
+}
 // ---------------------------------------------------------------------------------------------
 // launchers (host).  A scene with a fast tree (SceneDev::fast_root) takes the FAST instantiations; the C-ABI clears
 // fast_root in its copy of SceneDev to force the exact walk (cgrt_scene_set_walk).  Workgroup size: FrameDev::block for
@@ -1098,37 +1127,48 @@ hipError_t launch_trace_primary_compact(const SceneDev& S, const CameraDev& C, c
     return hipGetLastError();
 }
 // Multi-view frames: the VIEWS instantiations (no counters, no hints), in the shape a single frame of the same workgroup size takes.
-hipError_t launch_trace_primary_views(const SceneDev& S, const FrameDev& F, CgrtHitDev* hits, float* normals, hipStream_t stream) {
+// raycams: F.raycams is set instead of F.views (the RAYCAM instantiations).
+template <bool RAYCAM>
+static hipError_t launch_views(const SceneDev& S, const FrameDev& F, CgrtHitDev* hits, float* normals, hipStream_t stream) {
     if (F.nblocks == 0) return hipSuccess;
     const CameraDev C{};  // (unused: the cameras are in F.views)
     unsigned long long* const counters = nullptr;
     if (F.block == 64 && quad_shape_for(S, (unsigned long long)F.nblocks * 64ull))
-        hipLaunchKernelGGL((k_trace_primary<false, true, true, false, true>), dim3(4u * F.nblocks), dim3(64), lds_bytes(64), stream, S, C, F, hits, normals,
-                           counters);
+        hipLaunchKernelGGL((k_trace_primary<false, true, true, false, true, RAYCAM>), dim3(4u * F.nblocks), dim3(64), lds_bytes(64), stream, S, C, F, hits,
+                           normals, counters);
     else if (S.fast_root != REF_NONE)
-        hipLaunchKernelGGL((k_trace_primary<false, true, false, false, true>), dim3(F.nblocks), dim3((unsigned)F.block), lds_bytes((unsigned)F.block), stream,
-                           S, C, F, hits, normals, counters);
+        hipLaunchKernelGGL((k_trace_primary<false, true, false, false, true, RAYCAM>), dim3(F.nblocks), dim3((unsigned)F.block),
+                           lds_bytes((unsigned)F.block), stream, S, C, F, hits, normals, counters);
     else
-        hipLaunchKernelGGL((k_trace_primary<false, false, false, false, true>), dim3(F.nblocks), dim3((unsigned)F.block), lds_bytes((unsigned)F.block), stream,
-                           S, C, F, hits, normals, counters);
+        hipLaunchKernelGGL((k_trace_primary<false, false, false, false, true, RAYCAM>), dim3(F.nblocks), dim3((unsigned)F.block),
+                           lds_bytes((unsigned)F.block), stream, S, C, F, hits, normals, counters);
     return hipGetLastError();
 }
-hipError_t launch_trace_primary_views_compact(const SceneDev& S, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals, int* pixels,
-                                              uint32_t* count, float* rgb, hipStream_t stream) {
+hipError_t launch_trace_primary_views(const SceneDev& S, const FrameDev& F, CgrtHitDev* hits, float* normals, hipStream_t stream, bool raycams) {
+    return raycams ? launch_views<true>(S, F, hits, normals, stream) : launch_views<false>(S, F, hits, normals, stream);
+}
+template <bool RAYCAM>
+static hipError_t launch_views_compact(const SceneDev& S, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals, int* pixels, uint32_t* count,
+                                       float* rgb, hipStream_t stream) {
     if (F.nblocks == 0) return hipSuccess;
     const CameraDev C{};
     unsigned long long* const counters = nullptr;
     const SpawnDev* const SP = nullptr;
     if (F.block == 64 && quad_shape_for(S, (unsigned long long)F.nblocks * 64ull))
-        hipLaunchKernelGGL((k_trace_primary_compact<false, true, true, true>), dim3(4u * F.nblocks), dim3(64), lds_bytes(64), stream, S, C, F, rays, hits,
-                           normals, pixels, count, counters, rgb, SP);
+        hipLaunchKernelGGL((k_trace_primary_compact<false, true, true, true, RAYCAM>), dim3(4u * F.nblocks), dim3(64), lds_bytes(64), stream, S, C, F, rays,
+                           hits, normals, pixels, count, counters, rgb, SP);
     else if (S.fast_root != REF_NONE)
-        hipLaunchKernelGGL((k_trace_primary_compact<false, true, false, true>), dim3(F.nblocks), dim3((unsigned)F.block), lds_bytes((unsigned)F.block), stream,
-                           S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
+        hipLaunchKernelGGL((k_trace_primary_compact<false, true, false, true, RAYCAM>), dim3(F.nblocks), dim3((unsigned)F.block),
+                           lds_bytes((unsigned)F.block), stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
     else
-        hipLaunchKernelGGL((k_trace_primary_compact<false, false, false, true>), dim3(F.nblocks), dim3((unsigned)F.block), lds_bytes((unsigned)F.block),
-                           stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
+        hipLaunchKernelGGL((k_trace_primary_compact<false, false, false, true, RAYCAM>), dim3(F.nblocks), dim3((unsigned)F.block),
+                           lds_bytes((unsigned)F.block), stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
     return hipGetLastError();
+}
+hipError_t launch_trace_primary_views_compact(const SceneDev& S, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals, int* pixels,
+                                              uint32_t* count, float* rgb, hipStream_t stream, bool raycams) {
+    return raycams ? launch_views_compact<true>(S, F, rays, hits, normals, pixels, count, rgb, stream)
+                   : launch_views_compact<false>(S, F, rays, hits, normals, pixels, count, rgb, stream);
 }
 hipError_t launch_trace_list_compact(const SceneDev& S, const float* in_rays, unsigned long long n, float* rays, CgrtHitDev* hits, float* normals,
                                      int* pixels, uint32_t* count, float* rgb, hipStream_t stream, unsigned long long* counters) {
@@ -1254,6 +1294,12 @@ hipError_t launch_generate_rays(const CameraDev& C, int W, int H, int x0, int y0
     const unsigned long long n = (unsigned long long)(x1 - x0) * (unsigned long long)(y1 - y0);
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_generate_rays, dim3(grid_for(n, CGRT_BLOCK)), dim3(CGRT_BLOCK), 0, stream, C, W, H, x0, y0, x1, y1, rays);
+    return hipGetLastError();
+}
+hipError_t launch_generate_rays_raycam(const RayCameraDev& C, int W, int H, float* rays, hipStream_t stream) {
+    const unsigned long long n = (unsigned long long)W * (unsigned long long)H;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_generate_rays_raycam, dim3(grid_for(n, CGRT_BLOCK)), dim3(CGRT_BLOCK), 0, stream, C, W, H, rays);
     return hipGetLastError();
 }
 

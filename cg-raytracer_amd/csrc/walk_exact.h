@@ -752,6 +752,16 @@ __device__ __forceinline__ void primary_ray(const CameraDev& C, int W, int H, in
     d = quat_rotate(q, cam);
     o = f3(C.pos[0], C.pos[1], C.pos[2]);
 }
+// A ray camera's ray (include/cgrt.h CgrtRayCamera) for pixel (x, y) of the frame: origin and unnormalised direction
+// are affine in (x + x_off, y + y_off), every operation rounded in the order written, the direction normalised as everywhere.
+// The frame's size does not enter.
+__device__ __forceinline__ void primary_ray(const RayCameraDev& C, int x, int y, F3& o, F3& d) {
+    const float fx = float(x + C.x_off), fy = float(y + C.y_off);
+    o = f3((C.origin[0] + fx * C.origin_dx[0]) + fy * C.origin_dy[0], (C.origin[1] + fx * C.origin_dx[1]) + fy * C.origin_dy[1],
+           (C.origin[2] + fx * C.origin_dx[2]) + fy * C.origin_dy[2]);
+    d = normalize(f3((C.dir[0] + fx * C.dir_dx[0]) + fy * C.dir_dy[0], (C.dir[1] + fx * C.dir_dx[1]) + fy * C.dir_dy[1],
+                     (C.dir[2] + fx * C.dir_dx[2]) + fy * C.dir_dy[2]));
+}
 
 // Workgroup -> super-tile -> tile -> pixel (FrameDev in cgrt_layout.h): blockIdx % 8 selects the XCD lane of
 // the rank's super-tile list, 16 consecutive workgroups of that lane cover one 64x64 super-tile, the 4 waves

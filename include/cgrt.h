@@ -590,6 +590,56 @@ int cgrt_enqueue_render_views_aov_device(CgrtScene* scene, const CgrtCamera* cam
                                          uint32_t nlights, const CgrtSoftShadows* soft, int max_level, void* d_out, int format,
                                          void* stream, uint64_t* ticket, const CgrtAovOut* aov);
 
+/* Ray cameras: a second, general way to make the primary ray of a pixel, next to the reference's Trackball
+ * (CgrtCamera).  Origin and unnormalised direction are both affine in the pixel, which covers a pinhole with any intrinsic matrix K (skew,
+ * non-square pixels, off-centre principal point) and any pose (origin_dx = origin_dy = 0), an orthographic camera (dir_dx = dir_dy = 0,
+ * the origins on a plane) and pushbroom-like mixtures of the two. */
+typedef struct CgrtRayCamera {      /* 80 bytes */
+    float origin[3], origin_dx[3], origin_dy[3];
+    float dir[3],    dir_dx[3],    dir_dy[3];
+    int32_t x_off, y_off;
+} CgrtRayCamera;
+/* The ray of pixel (x, y) of a W x H frame, in f32, every operation rounded, nothing contracted:
+ *   fx = (float)(x + x_off);  fy = (float)(y + y_off)         (32-bit integer add, then convert)
+ *   o.c = (origin.c + fx * origin_dx.c) + fy * origin_dy.c     c = x, y, z
+ *   v.c = (dir.c    + fx * dir_dx.c)    + fy * dir_dy.c
+ *   d   = v * (1.0f / sqrt((v.x*v.x + v.y*v.y) + v.z*v.z))     (the library's normalise; IEEE sqrt and division)
+ *   t   = FLT_MAX
+ * W and H do not enter: the caller folds pixel centres, the principal point and the direction of y into `dir`.  A pixel whose v is zero
+ * gets the NaN direction the formula gives and is treated as that ray is treated in a ray list.
+ * Tiles are exact: the rays of a w x h frame with offsets (X, Y) are, bit for bit, the rays of pixels (X + x, Y + y) of the same camera
+ * with zero offsets, so a large image can be split over calls, streams or devices and give the same bytes -- hits, every geometry plane
+ * and the colour under point lights.  The one exception: the soft-shadow draws of spherical lights hash the tile's own pixel index
+ * y*W + x, into which the offsets do not enter, so tiles lit by spherical lights agree with the full frame statistically, not bit for bit.
+ * Camera checks, all CGRT_E_ARG, made where the Trackball twin checks `cams`: a non-finite field; dir, dir_dx and dir_dy all zero;
+ * |x_off| + W or |y_off| + H above 2^24 (the int -> float conversion stays exact).
+ *
+ * Every entry is views-shaped (nviews >= 1; one view is the single frame; pixel (x, y) of view b at b*W*H + y*W + x) and is the twin of a
+ * Trackball entry: the same argument checks in the same order with the same codes, the same limits (nviews * W * H <= 0x7fffffff, at
+ * most 2^18 64x64 super-tiles over all views, max_level 0..16), the same stream, export-event, ticket and stats rules, the same output
+ * layouts.  Like every views call they take the exactly sized path and neither read nor write the prediction record or the frame hints.
+ * Everything behind level 0 -- lists, shading, export, geometry planes -- is the Trackball entries' own code.
+ *   cgrt_generate_rays_raycam             the rays of a whole frame into host memory, row-major (cgrt_generate_rays's twin); synchronous
+ *   cgrt_trace_primary_raycams_device     cgrt_trace_primary_views_device's twin: only enqueues; `cams` is reusable at once
+ *   cgrt_render_raycams_device            twin of cgrt_render_views_device and, with aov != NULL, of cgrt_render_views_aov_device;
+ *                                         aov.position is the formula's o + d*t, rounded as CgrtAovOut states
+ *   cgrt_enqueue_render_raycams_device    twin of cgrt_enqueue_render_views_device / cgrt_enqueue_render_views_aov_device (aov may be NULL)
+ *   cgrt_render_raycams_light_sets_device cgrt_render_views_light_sets_device's twin
+ * Not offered: host-memory outputs, anti-aliasing, rank / nranks and the *_multi entries (tiles replace them), the enqueued light-set
+ * form, a per-camera far limit, and the C++ host mirror (the reference has no such camera). */
+int cgrt_generate_rays_raycam(CgrtScene* scene, const CgrtRayCamera* cam, int W, int H, CgrtRay* rays);
+int cgrt_trace_primary_raycams_device(CgrtScene* scene, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, CgrtHit* d_hits,
+                                      float* d_normals, void* stream);
+int cgrt_render_raycams_device(CgrtScene* scene, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* lights,
+                               uint32_t nlights, const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream,
+                               CgrtRenderStats* stats, const CgrtAovOut* aov);
+int cgrt_enqueue_render_raycams_device(CgrtScene* scene, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* lights,
+                                       uint32_t nlights, const CgrtSoftShadows* soft, int max_level, void* d_out, int format,
+                                       void* stream, uint64_t* ticket, const CgrtAovOut* aov);
+int cgrt_render_raycams_light_sets_device(CgrtScene* scene, const CgrtRayCamera* cams, uint32_t nviews, int W, int H,
+                                          const CgrtLightSets* sets, const CgrtSoftShadows* soft, int max_level, void* d_out, int format,
+                                          void* stream, CgrtRenderStats* stats);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
