@@ -146,3 +146,84 @@ def arbitrary_rays(sd, n, seed):
     t[(sel >= 0.2) & (sel < 0.3)] = 1e-6  # shorter than any hit
     short = (sel >= 0.2) & (sel < 0.3) & (np.arange(n) < 2 * k)  # (an origin ON a surface may still hit at t = 0: not counted)
     return np.concatenate([o, d, t[:, None]], axis=1).astype(np.float32), short
+
+
+def random_rays(rng, n, scale=1.0):
+    r = np.zeros((n, 7), np.float32)
+    r[:, 0:3] = rng.uniform(-2, 2, (n, 3)) * scale
+    d = rng.normal(size=(n, 3))
+    r[:, 3:6] = d / np.linalg.norm(d, axis=1, keepdims=True)
+    r[:, 6] = FMAX
+    return r
+
+
+def primitive_inputs():
+    """The seeded inputs of the element-wise primitive checks, shared by the bit-parity tests (device against oracle) and the referee's
+    tests (both against float64): triangle rows with on-plane, tiny and scaled cases, planes' triangles incl. degenerate ones, boxes with
+    flat ones, zero direction components and origins on faces, spheres; finite ray.t mixed in."""
+    out = {}
+    rng = np.random.RandomState(11)
+    n = 200_000
+    tri = rng.uniform(-1, 1, (n, 18)).astype(np.float32)
+    r = random_rays(rng, n)
+    w = rng.dirichlet((1, 1, 1), n).astype(np.float32)
+    tgt = w[:, 0:1] * tri[:, 0:3] + w[:, 1:2] * tri[:, 3:6] + w[:, 2:3] * tri[:, 6:9]
+    d = tgt - r[:, 0:3]
+    r[: n // 2, 3:6] = (d / np.linalg.norm(d, axis=1, keepdims=True))[: n // 2]
+    r[::7, 6] = rng.uniform(0, 3, len(r[::7]))
+    tri[:1000, [2, 5, 8]] = 0.5
+    r[:1000, 2] = 0.5
+    tri[1000:2000] *= np.float32(1e-18)
+    r[1000:2000, 0:3] *= np.float32(1e-18)
+    r[2000:3000, 3:6] *= np.float32(1e-20)
+    r[3000:4000, 3:6] *= np.float32(1e15)
+    out["triangle"] = (tri, r)
+
+    rng = np.random.RandomState(12)
+    n = 100_000
+    tri9 = rng.uniform(-1, 1, (n, 9)).astype(np.float32)
+    tri9[:500] *= np.float32(1e-15)
+    tri9[500:600, 3:6] = tri9[500:600, 0:3]
+    out["tri9"] = tri9
+    r = random_rays(rng, n)
+    r[::5, 6] = rng.uniform(0, 3, len(r[::5]))
+    r[:2000, 3:6] = 0.0
+    out["plane_rays"] = r
+    out["pin_points"] = rng.uniform(-1, 1, (n, 3)).astype(np.float32)
+
+    rng3 = np.random.RandomState(13)
+    n = 200_000
+    lo = rng3.uniform(-1, 0.5, (n, 3)).astype(np.float32)
+    hi = (lo + rng3.uniform(0, 1, (n, 3))).astype(np.float32)
+    hi[:5000, 0] = lo[:5000, 0]
+    box = np.concatenate([lo, hi], 1)
+    r = random_rays(rng3, n)
+    r[0:20000:2, 3] = 0.0
+    r[1:20000:2, 4] = -0.0
+    r[20000:30000, 3:5] = 0.0
+    r[30000:40000, 0] = lo[30000:40000, 0]
+    r[40000:50000, 0:3] = ((lo[40000:50000].astype(np.float64) + hi[40000:50000]) / 2).astype(np.float32)
+    r[50000:60000, 1] = hi[50000:60000, 1]
+    r[50000:60000, 4] = 0.0
+    r[::3, 6] = rng3.uniform(0, 3, len(r[::3]))
+    out["box"] = (box, r)
+
+    rng4 = np.random.RandomState(14)
+    n = 100_000
+    sph = np.concatenate([rng4.uniform(-1, 1, (n, 3)), rng4.uniform(0.05, 1.5, (n, 1))], 1).astype(np.float32)
+    r = random_rays(rng4, n)
+    d = sph[:, 0:3] - r[:, 0:3]
+    r[: n // 2, 3:6] = (d / np.linalg.norm(d, axis=1, keepdims=True))[: n // 2]
+    r[::4, 6] = rng4.uniform(0, 3, len(r[::4]))
+    out["sphere"] = (sph, r)
+    return out
+
+
+def plane_and_points(inp, planes):
+    """The ray-plane and point-in-triangle inputs, which depend on the planes the code under test computed from inp["tri9"]: the planes
+    with rows 5000-5999 moved (nearly) through their ray's origin, and v0 v1 v2 n p rows."""
+    r = inp["plane_rays"]
+    pl2 = np.array(planes, np.float32)
+    pl2[5000:6000, 0] = (r[5000:6000, 0:3] * pl2[5000:6000, 1:4]).astype(np.float32).sum(1)
+    pin = np.concatenate([inp["tri9"], np.asarray(planes, np.float32)[:, 1:4], inp["pin_points"]], 1)
+    return pl2, pin

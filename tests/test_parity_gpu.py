@@ -32,33 +32,9 @@ def _assert_hits_equal(hits, normals, ref, what=""):
 # ---------------------------------------------------------------------------------------------------
 # primitives (src/ray_tracing.h:10-20)
 # ---------------------------------------------------------------------------------------------------
-def _random_rays(rng, n, scale=1.0):
-    r = np.zeros((n, 7), np.float32)
-    r[:, 0:3] = rng.uniform(-2, 2, (n, 3)) * scale
-    d = rng.normal(size=(n, 3))
-    r[:, 3:6] = d / np.linalg.norm(d, axis=1, keepdims=True)
-    r[:, 6] = FMAX
-    return r
-
-
 def test_ray_triangle_primitive(pkg, orc):
-    rng = np.random.RandomState(11)
-    n = 200_000
-    tri = rng.uniform(-1, 1, (n, 18)).astype(np.float32)
-    r = _random_rays(rng, n)
-    # aim most rays at a point of their triangle so that hits are common
-    w = rng.dirichlet((1, 1, 1), n).astype(np.float32)
-    tgt = w[:, 0:1] * tri[:, 0:3] + w[:, 1:2] * tri[:, 3:6] + w[:, 2:3] * tri[:, 6:9]
-    d = tgt - r[:, 0:3]
-    r[: n // 2, 3:6] = (d / np.linalg.norm(d, axis=1, keepdims=True))[: n // 2]
-    r[::7, 6] = rng.uniform(0, 3, len(r[::7]))  # finite t
-    # exact on-plane origins on axis-aligned triangles, scaled directions, denormal-ish geometry
-    tri[:1000, [2, 5, 8]] = 0.5
-    r[:1000, 2] = 0.5
-    tri[1000:2000] *= np.float32(1e-18)
-    r[1000:2000, 0:3] *= np.float32(1e-18)
-    r[2000:3000, 3:6] *= np.float32(1e-20)
-    r[3000:4000, 3:6] *= np.float32(1e15)
+    # rays aimed at their triangle, finite t, exact on-plane origins, scaled directions, denormal-ish geometry: rayfam.primitive_inputs
+    tri, r = rayfam.primitive_inputs()["triangle"]
     t, hit, nrm = pkg.ray_triangle(tri, _rays(pkg, r))
     ref = orc.ray_triangle(tri, r)
     assert 0.2 < hit.mean() < 0.8
@@ -69,43 +45,22 @@ def test_ray_triangle_primitive(pkg, orc):
 
 
 def test_ray_plane_and_triangle_plane_and_point_in_triangle(pkg, orc):
-    rng = np.random.RandomState(12)
-    n = 100_000
-    tri9 = rng.uniform(-1, 1, (n, 9)).astype(np.float32)
-    tri9[:500] *= np.float32(1e-15)  # tiny triangles: normalisation of tiny cross products
-    tri9[500:600, 3:6] = tri9[500:600, 0:3]  # degenerate: NaN normal
+    inp = rayfam.primitive_inputs()
+    tri9 = inp["tri9"]  # incl. tiny triangles (normalisation of tiny cross products) and degenerate ones (NaN normal)
     pl = pkg.triangle_plane(tri9)
     assert same_bits(pl, orc.triangle_plane(tri9)).all()
-    r = _random_rays(rng, n)
-    r[::5, 6] = rng.uniform(0, 3, len(r[::5]))
-    r[:2000, 3:6] = 0.0  # zero direction
-    pl2 = pl.copy()
-    pl2[5000:6000, 0] = (r[5000:6000, 0:3] * pl2[5000:6000, 1:4]).astype(np.float32).sum(1)  # near on-plane
+    r = inp["plane_rays"]  # finite t, zero directions
+    pl2, pin = rayfam.plane_and_points(inp, pl)  # near on-plane origins
     t, hit = pkg.ray_plane(pl2, _rays(pkg, r))
     ref = orc.ray_plane(pl2, r)
     assert np.array_equal(hit, ref["hit"].astype(np.uint8)) and same_bits(t, ref["t"]).all()
     assert np.isnan(t).sum() > 50  # degenerate planes were exercised
-    pin = np.concatenate([tri9, pl[:, 1:4], rng.uniform(-1, 1, (n, 3)).astype(np.float32)], 1)
     assert np.array_equal(pkg.point_in_triangle(pin), orc.point_in_triangle(pin))
 
 
 def test_ray_box_primitive(pkg, orc):
-    rng = np.random.RandomState(13)
-    n = 200_000
-    lo = rng.uniform(-1, 0.5, (n, 3)).astype(np.float32)
-    hi = (lo + rng.uniform(0, 1, (n, 3))).astype(np.float32)
-    hi[:5000, 0] = lo[:5000, 0]  # zero-thickness boxes (F4)
-    box = np.concatenate([lo, hi], 1)
-    r = _random_rays(rng, n)
-    # zero / negative-zero direction components, origins on faces, inside, finite t
-    r[0:20000:2, 3] = 0.0
-    r[1:20000:2, 4] = -0.0
-    r[20000:30000, 3:5] = 0.0
-    r[30000:40000, 0] = lo[30000:40000, 0]
-    r[40000:50000, 0:3] = ((lo[40000:50000].astype(np.float64) + hi[40000:50000]) / 2).astype(np.float32)
-    r[50000:60000, 1] = hi[50000:60000, 1]
-    r[50000:60000, 4] = 0.0  # origin in the face plane AND parallel to it => 0/0 = NaN
-    r[::3, 6] = rng.uniform(0, 3, len(r[::3]))
+    # zero-thickness boxes (F4), zero / negative-zero direction components, origins on faces and inside, 0/0 slabs, finite t
+    box, r = rayfam.primitive_inputs()["box"]
     t, hit, inside = pkg.ray_box(box, _rays(pkg, r))
     ref = orc.ray_box(box, r)
     assert np.array_equal(hit, ref["hit"].astype(np.uint8))
@@ -115,13 +70,7 @@ def test_ray_box_primitive(pkg, orc):
 
 
 def test_ray_sphere_primitive(pkg, orc):
-    rng = np.random.RandomState(14)
-    n = 100_000
-    sph = np.concatenate([rng.uniform(-1, 1, (n, 3)), rng.uniform(0.05, 1.5, (n, 1))], 1).astype(np.float32)
-    r = _random_rays(rng, n)
-    d = sph[:, 0:3] - r[:, 0:3]
-    r[: n // 2, 3:6] = (d / np.linalg.norm(d, axis=1, keepdims=True))[: n // 2]
-    r[::4, 6] = rng.uniform(0, 3, len(r[::4]))
+    sph, r = rayfam.primitive_inputs()["sphere"]
     t, hit, nrm = pkg.ray_sphere(sph, _rays(pkg, r))
     ref = orc.ray_sphere(sph, r)
     assert np.array_equal(hit, ref["hit"].astype(np.uint8)) and same_bits(t, ref["t"]).all()
