@@ -230,7 +230,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -334,6 +334,12 @@ def lib() -> C.CDLL:
     L.cgrt_in_shadow_device.argtypes = [vp, vp, u64, vp, u32, vp, vp]
     L.cgrt_soft_lit.argtypes = [vp, vp, u64, C.POINTER(SoftShadows), vp]
     L.cgrt_soft_lit_device.argtypes = [vp, vp, u64, C.POINTER(SoftShadows), vp, vp]
+    L.cgrt_hit_barycentrics.argtypes = [vp, vp, vp, u64, vp]
+    L.cgrt_hit_barycentrics_device.argtypes = [vp, vp, vp, u64, vp, vp]
+    L.cgrt_interpolate_hits.argtypes = [vp, vp, vp, u64, vp, u32, vp]
+    L.cgrt_interpolate_hits_device.argtypes = [vp, vp, vp, u64, vp, u32, vp, vp]
+    L.cgrt_surface_views_device.argtypes = [vp, vp, u32, i32, i32, vp, vp, vp, u32, vp, vp, i32, vp]
+    L.cgrt_surface_raycams_device.argtypes = L.cgrt_surface_views_device.argtypes
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
     L.cgrt_count_batch.argtypes = [vp, vp, u64, C.POINTER(Counters)]
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
@@ -1575,6 +1581,194 @@ class Scene:
         return self._tensor_call(out, shape, torch.int32, stream,
                                  lambda o, s: self.soft_lit_device(points.data_ptr(), n, o.data_ptr(), spherical, units, samples=samples,
                                                                    seed=seed, closest_hit=closest_hit, stream=s))
+
+    # ---- surface attributes (include/cgrt.h cgrt_hit_barycentrics*, cgrt_interpolate_hits*, cgrt_surface_*_device) ----
+    @staticmethod
+    def _as_hit_array(hits, n: int) -> np.ndarray:
+        h = np.ascontiguousarray(hits)
+        if h.dtype != HIT_DTYPE or h.ndim != 1 or len(h) != n:
+            raise ValueError(f"hits must be a HIT_DTYPE array with one entry per ray ({n})")
+        return h
+
+    def hit_barycentrics(self, rays, hits) -> np.ndarray:
+        """cgrt_hit_barycentrics: where inside its triangle each ray hit.  rays (RAY_DTYPE or (n, 7) float32) and hits (HIT_DTYPE) are what
+        intersect took and returned.  Returns (n, 3) float32 {alpha, beta, gamma}, the weights of tri[prim_id][0..2] -- the area ratios
+        of ray_tracing.cpp:94-96, not renormalised; zeros for a miss, a sphere hit or an out-of-range prim_id."""
+        r = _as_ray_array(rays)
+        h = self._as_hit_array(hits, len(r))
+        bary = np.zeros((len(r), 3), np.float32)
+        _check(lib().cgrt_hit_barycentrics(self._h, _ptr(r), _ptr(h), len(r), _ptr(bary)))
+        return bary
+
+    def interpolate_hits(self, rays, hits, attr) -> np.ndarray:
+        """cgrt_interpolate_hits: a per-vertex table attr ((nverts, C) float32, row v = vertex v of pos_nrm, C in 1..256) carried to every
+        hit: (alpha * attr[i0] + beta * attr[i1]) + gamma * attr[i2] per channel.  Returns (n, C) float32, zeros where hit_barycentrics
+        gives zeros."""
+        r = _as_ray_array(rays)
+        h = self._as_hit_array(hits, len(r))
+        a = self._attr_array(attr)
+        out = np.zeros((len(r), a.shape[1]), np.float32)
+        _check(lib().cgrt_interpolate_hits(self._h, _ptr(r), _ptr(h), len(r), _ptr(a), a.shape[1], _ptr(out)))
+        return out
+
+    def _attr_array(self, attr) -> np.ndarray:
+        a = np.ascontiguousarray(np.asarray(attr, np.float32))
+        nverts = len(_f32(self.sd.pos_nrm, (-1, 6)))
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if a.ndim != 2 or a.shape[0] != nverts:
+            raise ValueError(f"attr must have one row per vertex: ({nverts}, C), not {a.shape}")
+        return a
+
+    def hit_barycentrics_device(self, d_rays_ptr: int, d_hits_ptr: int, n: int, d_bary_ptr: int, stream: int = 0) -> None:
+        """cgrt_hit_barycentrics_device: n rays (28 bytes each) and hits (16 bytes each) -> n x 3 floats at d_bary_ptr, enqueued on the
+        hipStream_t `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        _check(lib().cgrt_hit_barycentrics_device(self._h, vp(d_rays_ptr), vp(d_hits_ptr), int(n), vp(d_bary_ptr), vp(stream)))
+
+    def interpolate_hits_device(self, d_rays_ptr: int, d_hits_ptr: int, n: int, d_attr_ptr: int, channels: int, d_out_ptr: int,
+                                stream: int = 0) -> None:
+        """cgrt_interpolate_hits_device: d_attr_ptr is an (nverts, channels) float32 table in device memory; n x channels floats go to
+        d_out_ptr, enqueued on `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        _check(lib().cgrt_interpolate_hits_device(self._h, vp(d_rays_ptr), vp(d_hits_ptr), int(n), vp(d_attr_ptr), int(channels),
+                                                  vp(d_out_ptr), vp(stream)))
+
+    def surface_views_device(self, cams, W: int, H: int, d_depth_ptr: int, d_prim_id_ptr: int, d_bary_ptr: int = 0, d_attr_ptr: int = 0,
+                             channels: int = 0, d_out_ptr: int = 0, chw: bool = False, stream: int = 0, raycams: bool = False) -> None:
+        """cgrt_surface_views_device (raycams: cgrt_surface_raycams_device): the barycentrics (d_bary_ptr) and / or an interpolated
+        attribute (d_attr_ptr, channels, d_out_ptr) of every pixel of B frames from their (B, H, W) depth and prim_id planes; the primary
+        rays are regenerated from the cameras.  Raw integers; enqueued on `stream`."""
+        a = raycam_array(cams) if raycams else camera_array(cams)
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        f = lib().cgrt_surface_raycams_device if raycams else lib().cgrt_surface_views_device
+        _check(f(self._h, _ptr(a) if len(a) else None, len(a), W, H, vp(d_depth_ptr), vp(d_prim_id_ptr), vp(d_attr_ptr), int(channels),
+                 vp(d_bary_ptr), vp(d_out_ptr), 1 if chw else 0, vp(stream)))
+
+    def _device_tensor(self, t, name: str, dtypes, shape=None):
+        """A *_tensor argument: a contiguous torch tensor of one of `dtypes` (and of `shape`) on the scene's device (ValueError)."""
+        import torch
+
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{name} has dtype {t.dtype}, needs one of {dtypes}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, needs {tuple(shape)}")
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError(f"{name} is on {t.device}, the scene on cuda:{self.device}")
+        if not t.is_contiguous() or t.data_ptr() % 4:
+            raise ValueError(f"{name} must be contiguous and 4-byte aligned")
+        return t
+
+    def _attr_tensor(self, attr):
+        import torch
+
+        nverts = len(_f32(self.sd.pos_nrm, (-1, 6)))
+        if isinstance(attr, torch.Tensor) and attr.dim() == 2 and attr.shape[0] == nverts and 1 <= attr.shape[1] <= 256:
+            return self._device_tensor(attr, "attr", (torch.float32,))
+        raise ValueError(f"attr must be a torch tensor of shape ({nverts}, C), C in 1..256")
+
+    def _hits_tensor(self, rays, hits):
+        """The checks of a ray list's tensors: rays (..., 7) float32; hits in HIT_DTYPE layout, 16 bytes per ray -- (..., 4) of a 4-byte
+        dtype (as intersect_device's hits viewed as int32) or (..., 16) uint8.  Returns (lead shape, n)."""
+        import torch
+
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 7:
+            raise ValueError("rays must be a torch tensor of shape (..., 7)")
+        self._device_tensor(rays, "rays", (torch.float32,))
+        lead = tuple(rays.shape[:-1])
+        if not isinstance(hits, torch.Tensor) or hits.dim() < 1 or hits.shape[-1] * hits.element_size() != HIT_DTYPE.itemsize or \
+                tuple(hits.shape[:-1]) != lead:
+            raise ValueError(f"hits must be a torch tensor of shape {lead + (4,)} (a 4-byte dtype) or {lead + (16,)} (uint8): HIT_DTYPE records")
+        self._device_tensor(hits, "hits", (torch.int32, torch.float32, torch.uint8) + ((torch.uint32,) if hasattr(torch, "uint32") else ()))
+        return lead, rays.numel() // 7
+
+    def hit_barycentrics_tensor(self, rays, hits, out=None, stream=None):
+        """hit_barycentrics on torch tensors of cuda:<device>: rays (..., 7) float32, hits (..., 4) int32 / float32 (or (..., 16) uint8)
+        holding HIT_DTYPE records -> (..., 3) float32, into `out` or a new tensor, enqueued on `stream` (default:
+        torch.cuda.current_stream())."""
+        import torch
+
+        lead, n = self._hits_tensor(rays, hits)
+        if out is not None:
+            self._device_tensor(out, "out", (torch.float32,), lead + (3,))
+        return self._tensor_call(out, lead + (3,), torch.float32, stream,
+                                 lambda o, s: self.hit_barycentrics_device(rays.data_ptr(), hits.data_ptr(), n, o.data_ptr(), stream=s))
+
+    def interpolate_hits_tensor(self, rays, hits, attr, out=None, stream=None):
+        """interpolate_hits on torch tensors: attr is an (nverts, C) float32 tensor on cuda:<device> (any per-vertex table: colours,
+        texture coordinates, features; it may be a contiguous view into a larger allocation) -> (..., C) float32."""
+        import torch
+
+        lead, n = self._hits_tensor(rays, hits)
+        attr = self._attr_tensor(attr)
+        ch = attr.shape[1]
+        if out is not None:
+            self._device_tensor(out, "out", (torch.float32,), lead + (ch,))
+        return self._tensor_call(out, lead + (ch,), torch.float32, stream,
+                                 lambda o, s: self.interpolate_hits_device(rays.data_ptr(), hits.data_ptr(), n, attr.data_ptr(), ch,
+                                                                           o.data_ptr(), stream=s))
+
+    def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream):
+        import torch
+
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if raycams:
+            a = raycam_array(cams)
+        else:
+            if isinstance(cams, Camera):
+                cams = [cams]
+            elif isinstance(cams, np.ndarray) and cams.ndim == 1:
+                cams = cams.reshape(1, -1)
+            a = camera_array(cams)
+        B = len(a)
+        if attr is None and not want_bary:
+            raise ValueError("nothing requested: pass attr, or want_bary=True")
+        if not isinstance(depth, torch.Tensor) or tuple(depth.shape) not in ((B, H, W),) + (((H, W),) if B == 1 else ()):
+            raise ValueError(f"depth must be a torch tensor of shape {(B, H, W)}" + (f" or {(H, W)}" if B == 1 else ""))
+        lead = tuple(depth.shape[:-2])
+        self._device_tensor(depth, "depth", (torch.float32,))
+        self._device_tensor(prim_id, "prim_id", (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ()), depth.shape)
+        out = {} if out is None else out
+        if not isinstance(out, dict) or any(k not in ("bary", "attr") for k in out):
+            raise ValueError("out must be a dict with the keys 'bary' and / or 'attr'")
+        want = {}
+        if want_bary:
+            want["bary"] = lead + ((3, H, W) if chw else (H, W, 3))
+        if attr is not None:
+            attr = self._attr_tensor(attr)
+            want["attr"] = lead + ((attr.shape[1], H, W) if chw else (H, W, attr.shape[1]))
+        for k, t in out.items():
+            if k not in want:
+                raise ValueError(f"out[{k!r}] given, but that output is not requested")
+            self._device_tensor(t, f"out[{k!r}]", (torch.float32,), want[k])
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        _check_one_hip_runtime()
+        with torch.cuda.stream(stream):
+            res = {k: out[k] if k in out else torch.empty(shape, dtype=torch.float32, device=dev) for k, shape in want.items()}
+        self.surface_views_device(a, W, H, depth.data_ptr(), prim_id.data_ptr(), d_bary_ptr=res["bary"].data_ptr() if "bary" in res else 0,
+                                  d_attr_ptr=0 if attr is None else attr.data_ptr(), channels=0 if attr is None else attr.shape[1],
+                                  d_out_ptr=res["attr"].data_ptr() if "attr" in res else 0, chw=chw, stream=stream.cuda_stream, raycams=raycams)
+        return res
+
+    def surface_views_tensor(self, cams, W: int, H: int, depth, prim_id, attr=None, want_bary: bool = True, chw: bool = False, out=None,
+                             stream=None):
+        """The surface attributes of whole frames from their geometry planes: cams (B Trackball cameras, or one) and the `depth` (float32)
+        and `prim_id` (int32) planes of render_views_aov_tensor / render_aov_tensor, (B, H, W) -- or (H, W) for one camera; for the planes
+        of an aa frame pass 2W, 2H.  Returns a dict: 'bary' (B, H, W, 3) when want_bary, 'attr' (B, H, W, C) when attr ((nverts, C)
+        float32 on the device) is given; (B, 3, H, W) / (B, C, H, W) with chw.  out: dict of caller's tensors for some or all of them.
+        Enqueued on `stream` (default: torch.cuda.current_stream()); nothing is traced."""
+        return self._surface_frames_tensor(False, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream)
+
+    def surface_raycams_tensor(self, cams, W: int, H: int, depth, prim_id, attr=None, want_bary: bool = True, chw: bool = False, out=None,
+                               stream=None):
+        """surface_views_tensor for ray cameras (the planes of render_raycams_tensor(aovs=...))."""
+        return self._surface_frames_tensor(True, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream)
 
     def generate_rays(self, cam, W: int, H: int, rect=None) -> np.ndarray:
         x0, y0, x1, y1 = rect if rect is not None else (0, 0, W, H)

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <utility>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -28,6 +29,7 @@
 #include "bvh_builder.h"
 #include "cgrt_layout.h"
 #include "cgrt_math.h"
+#include "surface_kernels.h"
 #include "trace_kernels.h"
 
 using namespace cgrt;
@@ -367,9 +369,17 @@ struct CgrtScene {
     hipEvent_t enq_done = nullptr;    // behind the last enqueued frame (one of the slots' `done`)
     bool enq_pending = false;
     uint64_t device_bytes = 0;
+    // Surface attributes (cgrt_hit_barycentrics*, cgrt_interpolate_hits*, cgrt_surface_*): the triangles' vertex
+    // indices as the caller gave them (host memory only) and, from the first surface call on, the device table prim_id -> {record, three
+    // vertex rows} (surface_kernels.h SurfaceLookup).  A scene that makes no such call never allocates it.
+    uint32_t nverts = 0;
+    std::vector<uint32_t> tri_index;  // ntris x 3
+    std::mutex surface_mutex;
+    std::atomic<void*> d_surface_lookup{nullptr};
     ~CgrtScene() {
         if (device < 0) return;
         (void)hipSetDevice(device);
+        if (void* p = d_surface_lookup.load()) (void)hipFree(p);
         for (EnqSlot& e : eslot) {  // (frames in flight complete before anything they use is released)
             if (e.pending) (void)hipEventSynchronize(e.done);
             for (hipEvent_t ev : {e.done, e.t0, e.t1})
@@ -532,6 +542,8 @@ int cgrt_scene_create(const float* pos_nrm, uint32_t nverts, const uint32_t* tri
         CgrtScene* s = new CgrtScene();
         s->device = device;
         s->ntris = ntris;
+        s->nverts = nverts;
+        s->tri_index = hs.tri;
         std::string err;
         BuildOptions bo;
         {
@@ -1688,23 +1700,11 @@ static std::vector<uint8_t> view_table(const CgrtCamera* cams, const CgrtRayCame
 }
 static int check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, const char* name);
 
-// cgrt_trace_primary_views_device and its ray-camera twin (exactly one of cams, raycams)
-static int trace_views_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H, CgrtHit* d_hits,
-                              float* d_normals, void* stream) {
-    if (!s || !d_hits) return fail(CGRT_E_ARG, "NULL argument");
-    int rc = views_args(raycams ? static_cast<const void*>(raycams) : cams, nviews, W, H, raycams);
-    if (rc) return rc;
-    if ((uintptr_t)d_hits % 4 || (uintptr_t)d_normals % 4) return fail(CGRT_E_ARG, "d_hits / d_normals not 4-byte aligned");
-    NEED_DEVICE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    const uint64_t npix = (uint64_t)nviews * (uint64_t)W * (uint64_t)H;
-    if ((rc = check_device_span(s, d_hits, npix * sizeof(CgrtHit), "d_hits"))) return rc;
-    if (d_normals && (rc = check_device_span(s, d_normals, npix * 12, "d_normals"))) return rc;
-    FrameDev F;
-    (void)make_views_frame(W, H, nviews, trace_block(s->dev), F);
-    const std::vector<uint8_t> tab = view_table(cams, raycams, nviews);
+// A launch that reads a camera table and returns before it runs (cgrt_trace_primary_views_device, cgrt_surface_views_device and their
+// ray-camera twins): the table goes into the next of the scene's four slots (CgrtScene::ViewTable), is copied to the device on `st`,
+// `launch` is issued with the device copy, and the slot's event is recorded behind it.
+static int launch_with_view_table(CgrtScene* s, const std::vector<uint8_t>& tab, hipStream_t st, const std::function<hipError_t(const void*)>& launch) {
     const size_t bytes = tab.size();
-    hipStream_t const st = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> lk(s->vtab_mutex);
     CgrtScene::ViewTable& T = s->vtab[s->vtab_seq++ & 3u];
     if (T.pending) HIP_TRY(hipEventSynchronize(T.done));  // (the slot's last launch has read its table)
@@ -1721,11 +1721,31 @@ static int trace_views_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRa
     }
     std::memcpy(T.pin, tab.data(), bytes);
     HIP_TRY(hipMemcpyAsync(T.dev, T.pin, bytes, hipMemcpyHostToDevice, st));
-    F.views = static_cast<const CameraDev*>(T.dev);  // (F.raycams: the same slot)
-    HIP_TRY(launch_trace_primary_views(s->dev, F, reinterpret_cast<CgrtHitDev*>(d_hits), d_normals, st, raycams != nullptr));
+    HIP_TRY(launch(static_cast<const void*>(T.dev)));
     HIP_TRY(hipEventRecord(T.done, st));
     T.pending = true;
     return CGRT_OK;
+}
+
+// cgrt_trace_primary_views_device and its ray-camera twin (exactly one of cams, raycams)
+static int trace_views_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H, CgrtHit* d_hits,
+                              float* d_normals, void* stream) {
+    if (!s || !d_hits) return fail(CGRT_E_ARG, "NULL argument");
+    int rc = views_args(raycams ? static_cast<const void*>(raycams) : cams, nviews, W, H, raycams);
+    if (rc) return rc;
+    if ((uintptr_t)d_hits % 4 || (uintptr_t)d_normals % 4) return fail(CGRT_E_ARG, "d_hits / d_normals not 4-byte aligned");
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    const uint64_t npix = (uint64_t)nviews * (uint64_t)W * (uint64_t)H;
+    if ((rc = check_device_span(s, d_hits, npix * sizeof(CgrtHit), "d_hits"))) return rc;
+    if (d_normals && (rc = check_device_span(s, d_normals, npix * 12, "d_normals"))) return rc;
+    FrameDev F;
+    (void)make_views_frame(W, H, nviews, trace_block(s->dev), F);
+    hipStream_t const st = static_cast<hipStream_t>(stream);
+    return launch_with_view_table(s, view_table(cams, raycams, nviews), st, [&](const void* d_table) {
+        F.views = static_cast<const CameraDev*>(d_table);  // (F.raycams: the same slot)
+        return launch_trace_primary_views(s->dev, F, reinterpret_cast<CgrtHitDev*>(d_hits), d_normals, st, raycams != nullptr);
+    });
 }
 int cgrt_trace_primary_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, CgrtHit* d_hits, float* d_normals,
                                     void* stream) {
@@ -3665,6 +3685,189 @@ int cgrt_soft_lit(CgrtScene* s, const float* points, uint64_t n, const CgrtSoftS
     HIP_TRY(hipStreamSynchronize(g.L->stream));
     if (staged) std::memcpy(lit, staged, m);
     return CGRT_OK;
+}
+
+// ---- surface attributes (include/cgrt.h cgrt_hit_barycentrics*, cgrt_interpolate_hits*, cgrt_surface_*_device):
+// where inside its triangle a hit lies, and a caller's per-vertex table carried there.  Nothing is traced and no scene state is read or
+// written except the lookup table below; the checks come in the order include/cgrt.h states, all before any device work.
+namespace {
+const uint64_t kSurfaceMaxBytes = 1ull << 40;  // an output's size: items x channels x 4 bytes (the kernel indexes with 64 bits; a documented bound)
+int surface_channels(uint32_t channels, uint64_t items) {
+    if (channels < 1 || channels > 256) return fail(CGRT_E_ARG, "channels must be in 1..256");
+    if (items * channels * 4ull > kSurfaceMaxBytes) return fail(CGRT_E_ARG, "output too large: items x channels x 4 exceeds 2^40 bytes");
+    return CGRT_OK;
+}
+// prim_id -> {record, three vertex rows}, made once per scene by its first surface call (later calls: one atomic load)
+int surface_lookup(CgrtScene* s, const SurfaceLookup** out) {
+    void* p = s->d_surface_lookup.load(std::memory_order_acquire);
+    if (!p) {
+        std::lock_guard<std::mutex> lk(s->surface_mutex);
+        p = s->d_surface_lookup.load(std::memory_order_acquire);
+        if (!p) {
+            std::vector<SurfaceLookup> T;
+            try {
+                T.resize(s->ntris);
+            } catch (const std::bad_alloc&) {
+                return fail(CGRT_E_ALLOC, "host allocation failed");
+            }
+            const std::vector<TriRecord>& R = s->bvh.tris;
+            if (R.size() != s->ntris || s->tri_index.size() != 3 * (size_t)s->ntris) return fail(CGRT_E_ARG, "the scene's records do not cover its triangles");
+            for (size_t k = 0; k < R.size(); k++) {
+                const uint32_t prim = R[k].prim_id;
+                if (prim >= s->ntris) return fail(CGRT_E_ARG, "a triangle record carries a primitive id out of range");
+                T[prim].record = s->bvh.tri_base + (uint32_t)k;
+                for (int c = 0; c < 3; c++) T[prim].v[c] = s->tri_index[3 * (size_t)prim + c];
+            }
+            const size_t bytes = T.size() * sizeof(SurfaceLookup);
+            void* d = nullptr;
+            HIP_TRY(hipMalloc(&d, bytes ? bytes : 16));
+            if (bytes) {
+                const hipError_t e = staged_h2d(d, T.data(), bytes);  // (complete when it returns: every later launch sees the table)
+                if (e != hipSuccess) {
+                    (void)hipFree(d);
+                    return hip_fail(e, "uploading the surface lookup table");
+                }
+            }
+            s->device_bytes += bytes;
+            s->d_surface_lookup.store(d, std::memory_order_release);
+            p = d;
+        }
+    }
+    *out = static_cast<const SurfaceLookup*>(p);
+    return CGRT_OK;
+}
+SurfaceDev surface_dev(const CgrtScene* s, const SurfaceLookup* lookup, uint64_t n, const float* d_attr, uint32_t channels, float* d_bary,
+                       float* d_out, int chw) {
+    SurfaceDev A{};
+    A.tris = s->dev.tris;
+    A.lookup = lookup;
+    A.ntris = s->dev.ntris;
+    A.n = (uint32_t)n;
+    A.attr = d_out ? d_attr : nullptr;
+    A.channels = d_out ? channels : 0;
+    A.bary = d_bary;
+    A.out = d_out;
+    A.chw = chw ? 1 : 0;
+    A.vec4 = d_out && channels % 4 == 0 && (uintptr_t)d_attr % 16 == 0 && (uintptr_t)d_out % 16 == 0;
+    return A;
+}
+// the list forms' checks up to the host-only scene (attr: the call interpolates; device: the pointers' alignment is checked too)
+int surface_list_args(const CgrtScene* s, const void* rays, const void* hits, uint64_t n, bool attr, const void* table, uint32_t channels,
+                      const void* out, bool device) {
+    if (!s || (n && (!rays || !hits || !out || (attr && !table)))) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many hits: n exceeds 0x7fffffff");
+    if (attr) {
+        const int rc = surface_channels(channels, n);
+        if (rc) return rc;
+    }
+    if (device && ((uintptr_t)rays % 4 || (uintptr_t)hits % 4 || (uintptr_t)table % 4 || (uintptr_t)out % 4))
+        return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    return CGRT_OK;
+}
+// d_bary or d_out (with d_attr, channels) of n hits on `st`; every pointer device memory
+int surface_list_launch(CgrtScene* s, const void* d_rays, const void* d_hits, uint64_t n, const float* d_attr, uint32_t channels, float* d_bary,
+                        float* d_out, hipStream_t st) {
+    const SurfaceLookup* lookup = nullptr;
+    const int rc = surface_lookup(s, &lookup);
+    if (rc) return rc;
+    SurfaceDev A = surface_dev(s, lookup, n, d_attr, channels, d_bary, d_out, 0);
+    A.rays = static_cast<const float*>(d_rays);
+    A.hits = static_cast<const CgrtHitDev*>(d_hits);
+    HIP_TRY(launch_surface(A, SURFACE_LIST, st));
+    return CGRT_OK;
+}
+int surface_list_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, bool attr, const float* d_attr, uint32_t channels,
+                        float* d_res, void* stream) {
+    int rc = surface_list_args(s, d_rays, d_hits, n, attr, d_attr, channels, d_res, true);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_hits, n * sizeof(CgrtHit), "d_hits")) != CGRT_OK) return rc;
+    if (attr && (rc = check_device_span(s, d_attr, (uint64_t)s->nverts * channels * 4ull, "d_attr")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_res, n * (attr ? channels : 3u) * 4ull, attr ? "d_out" : "d_bary")) != CGRT_OK) return rc;
+    return surface_list_launch(s, d_rays, d_hits, n, d_attr, channels, attr ? nullptr : d_res, attr ? d_res : nullptr, static_cast<hipStream_t>(stream));
+}
+// host pointers, on a call lane (slots: 0 rays, 1 hits, 2 the result, 3 the attribute table)
+int surface_list_host(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, bool attr, const float* table, uint32_t channels, float* res) {
+    int rc = surface_list_args(s, rays, hits, n, attr, table, channels, res, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    LaneGuard g(s);
+    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    const size_t res_bytes = (size_t)n * (attr ? channels : 3u) * 4u, table_bytes = attr ? (size_t)s->nverts * channels * 4u : 0;
+    void *dr = nullptr, *dh = nullptr, *dres = nullptr, *dt = nullptr, *staged = nullptr;
+    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(g.dev(1, n * sizeof(CgrtHit), &dh));
+    HIP_TRY(g.dev(2, res_bytes, &dres));
+    if (attr) HIP_TRY(g.dev(3, table_bytes, &dt));
+    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
+    HIP_TRY(lane_upload(g, 1, dh, hits, n * sizeof(CgrtHit)));
+    if (attr) HIP_TRY(lane_upload(g, 3, dt, table, table_bytes));
+    if ((rc = surface_list_launch(s, dr, dh, n, static_cast<const float*>(dt), channels, attr ? nullptr : static_cast<float*>(dres),
+                                  attr ? static_cast<float*>(dres) : nullptr, g.L->stream)) != CGRT_OK)
+        return rc;
+    HIP_TRY(lane_download(g, 2, res, dres, res_bytes, &staged));
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    if (staged) std::memcpy(res, staged, res_bytes);
+    return CGRT_OK;
+}
+// cgrt_surface_views_device and its ray-camera twin (exactly one of cams, raycams)
+int surface_frames_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H, const float* d_depth,
+                          const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
+    if (!s || !d_depth || !d_prim_id || (!d_bary && !d_out) || (d_out && !d_attr)) return fail(CGRT_E_ARG, "NULL argument");
+    int rc = views_args(raycams ? static_cast<const void*>(raycams) : cams, nviews, W, H, raycams);
+    if (rc) return rc;
+    const uint64_t npix = (uint64_t)nviews * (uint64_t)W * (uint64_t)H;
+    if (d_out && (rc = surface_channels(channels, npix)) != CGRT_OK) return rc;
+    if ((uintptr_t)d_depth % 4 || (uintptr_t)d_prim_id % 4 || (uintptr_t)d_attr % 4 || (uintptr_t)d_bary % 4 || (uintptr_t)d_out % 4)
+        return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_depth, npix * 4, "d_depth")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_prim_id, npix * 4, "d_prim_id")) != CGRT_OK) return rc;
+    if (d_out && (rc = check_device_span(s, d_attr, (uint64_t)s->nverts * channels * 4ull, "d_attr")) != CGRT_OK) return rc;
+    if (d_bary && (rc = check_device_span(s, d_bary, npix * 12, "d_bary")) != CGRT_OK) return rc;
+    if (d_out && (rc = check_device_span(s, d_out, npix * channels * 4ull, "d_out")) != CGRT_OK) return rc;
+    const SurfaceLookup* lookup = nullptr;
+    if ((rc = surface_lookup(s, &lookup)) != CGRT_OK) return rc;
+    SurfaceDev A = surface_dev(s, lookup, npix, d_attr, channels, d_bary, d_out, chw);
+    A.depth = d_depth;
+    A.prim = d_prim_id;
+    A.W = W;
+    A.H = H;
+    A.plane = (uint32_t)((uint64_t)W * (uint64_t)H);
+    hipStream_t const st = static_cast<hipStream_t>(stream);
+    return launch_with_view_table(s, view_table(cams, raycams, nviews), st, [&](const void* d_table) {
+        A.cams = d_table;
+        return launch_surface(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, st);
+    });
+}
+}  // namespace
+
+int cgrt_hit_barycentrics(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, float* bary) {
+    return surface_list_host(s, rays, hits, n, false, nullptr, 0, bary);
+}
+int cgrt_hit_barycentrics_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, float* d_bary, void* stream) {
+    return surface_list_device(s, d_rays, d_hits, n, false, nullptr, 0, d_bary, stream);
+}
+int cgrt_interpolate_hits(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* attr, uint32_t channels, float* out) {
+    return surface_list_host(s, rays, hits, n, true, attr, channels, out);
+}
+int cgrt_interpolate_hits_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_attr, uint32_t channels,
+                                 float* d_out, void* stream) {
+    return surface_list_device(s, d_rays, d_hits, n, true, d_attr, channels, d_out, stream);
+}
+int cgrt_surface_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth, const uint32_t* d_prim_id,
+                              const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
+    return surface_frames_device(s, cams, nullptr, nviews, W, H, d_depth, d_prim_id, d_attr, channels, d_bary, d_out, chw, stream);
+}
+int cgrt_surface_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
+    return surface_frames_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_attr, channels, d_bary, d_out, chw, stream);
 }
 
 int cgrt_debug_export_frame(int device, const float* rgb, int W, int H, int format, uint64_t row_bytes, void* out) {

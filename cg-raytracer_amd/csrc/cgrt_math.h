@@ -114,6 +114,20 @@ CGRT_HD F3 hit_normal(F3 v0, F3 v1, F3 v2, F3 pn, F3 n1, F3 n2, F3 n3, F3 o, F3 
     return (dot(pn, neg(d)) > 0) ? ni : neg(ni);
 }
 
+// ---- ray_tracing.cpp:94-96: the three area ratios hit_normal mixes the vertex normals with, kept (include/cgrt.h
+//      cgrt_hit_barycentrics).  The same expressions in the same order, so the bits are hit_normal's. ----
+CGRT_HD void hit_weights(F3 v0, F3 v1, F3 v2, F3 o, F3 d, float t, float& alpha, float& beta, float& gamma) {
+    F3 p = add(o, scale(d, t));
+    float a012 = area_ref(v0, v1, v2);
+    alpha = area_ref(p, v1, v2) / a012;
+    beta = area_ref(p, v0, v2) / a012;
+    gamma = area_ref(p, v0, v1) / a012;
+}
+// ---- ray_tracing.cpp:97: one channel of `alpha * n1 + beta * n2 + gamma * n3`, sums left to right ----
+CGRT_HD float mix_weights(float alpha, float beta, float gamma, float a0, float a1, float a2) {
+    return (alpha * a0 + beta * a1) + gamma * a2;
+}
+
 // ---- ray_tracing.cpp:162-200 intersectRayWithShape(AxisAlignedBox) ----
 // Returns true and writes the box parameter (entry, or exit when the origin is inside the slabs)
 // into tbox when it is < t.  Does NOT modify the ray (the reference writes ray.t and every caller

@@ -1,0 +1,152 @@
+// surface_kernels.hip -- surface attributes of hits (include/cgrt.h cgrt_hit_barycentrics*, cgrt_interpolate_hits*, cgrt_surface_*_device;
+// DESIGN.md section 5.19): the three area ratios the reference mixes the vertex normals with (ray_tracing.cpp:94-96), kept, and a
+// caller's per-vertex table mixed with them in the order of :97.  Nothing is traced: the hit comes from a ray list's {ray, hit} pair or
+// from a frame's depth / prim_id planes and the pixel's regenerated primary ray (walk_exact.h primary_ray).
+//
+// One kernel, k_surface<source>.  Lane l of a wave owns item l of the wave's 64 consecutive items and evaluates its weights once
+// (cgrt_math.h hit_weights: four area_ref, each a double sum and a correctly rounded double sqrt) from one SurfaceLookup (16-byte load)
+// and the three positions of the TriRecord (three 16-byte loads).  The stores are then the WAVE's, not the lane's: the 64 items' 64 x C
+// outputs are one contiguous run of memory, lane l takes element (or 16-byte channel group) k * 64 + l of it, fetches that item's weights
+// and vertex rows from the owning lane (ds_bpermute) and reads attr[row][channel] -- neighbouring lanes read and write neighbouring
+// channels, whatever C is.  Channel-major frames (chw) are written plane by plane instead: every lane walks the channels of its own
+// pixel, and a wave's store is 64 consecutive pixels of one plane.
+#include <hip/hip_runtime.h>
+
+#include "surface_kernels.h"
+#include "walk_exact.h"
+
+namespace cgrt {
+
+namespace {
+
+const uint32_t SURFACE_NONE = 0xffffffffu;  // in place of the first vertex row: the item gets zeros (miss, sphere, prim_id out of range)
+
+template <int SRC>
+__global__ __launch_bounds__(256) void k_surface(const SurfaceDev A) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+    const bool live = i < (unsigned long long)A.n;
+    float wa = 0.0f, wb = 0.0f, wg = 0.0f;
+    uint32_t r0 = SURFACE_NONE, r1 = 0, r2 = 0;
+    uint32_t view = 0, q = 0;
+    if (live) {
+        uint32_t prim;
+        float t;
+        bool hit = true;
+        if (SRC == SURFACE_LIST) {
+            const CgrtHitDev h = A.hits[i];
+            prim = h.prim_id;
+            t = h.t;
+            hit = h.hit != 0u;
+        } else {
+            prim = A.prim[i];  // (a miss carries CGRT_NO_PRIM: there is no flag plane to read)
+            t = A.depth[i];
+            view = (uint32_t)i / A.plane;
+            q = (uint32_t)i - view * A.plane;
+        }
+        if (hit && prim < A.ntris) {
+            const uint4 L = *reinterpret_cast<const uint4*>(A.lookup + prim);
+            const float4* rec = reinterpret_cast<const float4*>(A.tris + L.x);
+            const float4 a = rec[0], b = rec[1], c = rec[2];  // v0 | v1 | v2 (the record's first 36 bytes)
+            F3 o, d;
+            if (SRC == SURFACE_LIST) {
+                const float* r = A.rays + 7ull * i;
+                o = ld3(r);
+                d = ld3(r + 3);
+            } else if (SRC == SURFACE_TRACKBALL) {
+                const int y = (int)(q / (uint32_t)A.W), x = (int)(q - (uint32_t)y * (uint32_t)A.W);
+                primary_ray(static_cast<const CameraDev*>(A.cams)[view], A.W, A.H, x, y, o, d);
+            } else {
+                const int y = (int)(q / (uint32_t)A.W), x = (int)(q - (uint32_t)y * (uint32_t)A.W);
+                primary_ray(static_cast<const RayCameraDev*>(A.cams)[view], x, y, o, d);
+            }
+            hit_weights(f3(a.x, a.y, a.z), f3(a.w, b.x, b.y), f3(b.z, b.w, c.x), o, d, t, wa, wb, wg);
+            r0 = L.y;
+            r1 = L.z;
+            r2 = L.w;
+        }
+    }
+    // from here on every lane of the wave takes the same branches: the loops below exchange values between lanes
+    const unsigned long long wbase = i - lane;  // the wave's first item
+    const uint32_t cnt = wbase >= (unsigned long long)A.n ? 0u : ((unsigned long long)A.n - wbase < 64ull ? (uint32_t)((unsigned long long)A.n - wbase) : 64u);
+    const uint32_t C = A.channels;
+    if (A.chw) {  // frames only: plane by plane, each lane its own pixel
+        if (live) {
+            if (A.bary) {
+                float* p = A.bary + (3ull * view) * A.plane + q;
+                p[0] = wa;
+                p[A.plane] = wb;
+                p[2ull * A.plane] = wg;
+            }
+            if (A.out) {
+                float* p = A.out + ((unsigned long long)C * view) * A.plane + q;
+                const bool ok = r0 != SURFACE_NONE;
+                const float* a0 = A.attr + (unsigned long long)(ok ? r0 : 0u) * C;
+                const float* a1 = A.attr + (unsigned long long)r1 * C;
+                const float* a2 = A.attr + (unsigned long long)r2 * C;
+                for (uint32_t c = 0; c < C; c++) p[(unsigned long long)c * A.plane] = ok ? mix_weights(wa, wb, wg, a0[c], a1[c], a2[c]) : 0.0f;
+            }
+        }
+        return;
+    }
+    if (A.bary) {
+        float* p = A.bary + 3ull * wbase;
+        for (uint32_t k = 0; k < 3u; k++) {
+            const uint32_t e = k * 64u + lane, h = e / 3u, c = e - 3u * h;
+            const float x = __shfl(wa, (int)h, 64), y = __shfl(wb, (int)h, 64), z = __shfl(wg, (int)h, 64);
+            if (h < cnt) p[e] = c == 0u ? x : (c == 1u ? y : z);
+        }
+    }
+    if (A.out) {
+        float* p = A.out + (unsigned long long)C * wbase;
+        const uint32_t G = A.vec4 ? C >> 2 : C;  // channel groups per item
+        const uint32_t total = cnt * G;
+        for (uint32_t k = 0; k < total; k += 64u) {
+            const uint32_t e = k + lane, hq = e / G, g = e - hq * G;
+            const int h = (int)(hq & 63u);  // (lanes behind the last element ask a lane that exists; they store nothing)
+            const float x = __shfl(wa, h, 64), y = __shfl(wb, h, 64), z = __shfl(wg, h, 64);
+            const uint32_t s0 = __shfl(r0, h, 64), s1 = __shfl(r1, h, 64), s2 = __shfl(r2, h, 64);
+            if (e >= total) continue;
+            if (A.vec4) {
+                float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (s0 != SURFACE_NONE) {
+                    const float4 a0 = reinterpret_cast<const float4*>(A.attr + (unsigned long long)s0 * C)[g];
+                    const float4 a1 = reinterpret_cast<const float4*>(A.attr + (unsigned long long)s1 * C)[g];
+                    const float4 a2 = reinterpret_cast<const float4*>(A.attr + (unsigned long long)s2 * C)[g];
+                    v = make_float4(mix_weights(x, y, z, a0.x, a1.x, a2.x), mix_weights(x, y, z, a0.y, a1.y, a2.y),
+                                    mix_weights(x, y, z, a0.z, a1.z, a2.z), mix_weights(x, y, z, a0.w, a1.w, a2.w));
+                }
+                reinterpret_cast<float4*>(p)[e] = v;
+            } else {
+                float v = 0.0f;
+                if (s0 != SURFACE_NONE)
+                    v = mix_weights(x, y, z, A.attr[(unsigned long long)s0 * C + g], A.attr[(unsigned long long)s1 * C + g],
+                                    A.attr[(unsigned long long)s2 * C + g]);
+                p[e] = v;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_surface(const SurfaceDev& A, int source, hipStream_t stream) {
+    if (A.n == 0) return hipSuccess;
+    const dim3 grid((A.n + 255u) / 256u), block(256);
+    switch (source) {
+        case SURFACE_LIST:
+            hipLaunchKernelGGL(k_surface<SURFACE_LIST>, grid, block, 0, stream, A);
+            break;
+        case SURFACE_TRACKBALL:
+            hipLaunchKernelGGL(k_surface<SURFACE_TRACKBALL>, grid, block, 0, stream, A);
+            break;
+        case SURFACE_RAYCAM:
+            hipLaunchKernelGGL(k_surface<SURFACE_RAYCAM>, grid, block, 0, stream, A);
+            break;
+        default:
+            return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace cgrt

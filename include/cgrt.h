@@ -640,6 +640,76 @@ int cgrt_render_raycams_light_sets_device(CgrtScene* scene, const CgrtRayCamera*
                                           const CgrtLightSets* sets, const CgrtSoftShadows* soft, int max_level, void* d_out, int format,
                                           void* stream, CgrtRenderStats* stats);
 
+/* Surface attributes: WHERE inside its triangle a ray hit, and a per-vertex quantity carried there.  The
+ * reference evaluates three area ratios for every accepted triangle hit (`alpha`, `beta`, `gamma`, src/ray_tracing.cpp:94-96, with
+ * `magnitude` / `area` of :13-21), uses them once to mix the vertex normals (:97) and drops them; these entries return them, and mix a
+ * caller's table with them.
+ * Definition.  For a ray (o, d), a parameter t and a triangle prim_id < ntris:
+ *   v0, v1, v2  the positions of tri[prim_id][0..2] as given to cgrt_scene_create (the f32 values the device's triangle records hold);
+ *   p           = o + d * t                                 (f32, product rounded, then sum rounded)
+ *   alpha       = area(p, v1, v2) / area(v0, v1, v2)        weighs vertex 0  (:94)
+ *   beta        = area(p, v0, v2) / area(v0, v1, v2)        weighs vertex 1  (:95)
+ *   gamma       = area(p, v0, v1) / area(v0, v1, v2)        weighs vertex 2  (:96)
+ *   area(a,b,c) = magnitude(cross(b - a, c - a)) / 2.0f, cross and differences in f32, magnitude's squares, sum and sqrt in double and
+ *                 narrowed (:13-21): cgrt_math.h area_ref.  These are the values cgrt_math.h hit_normal uses, bit for bit.
+ * An attribute with C channels from a table attr[nverts][C] (f32, row v = vertex v of pos_nrm):
+ *   out[c]      = (alpha * attr[i0][c] + beta * attr[i1][c]) + gamma * attr[i2][c],   i0..i2 = tri[prim_id][0..2]
+ * the sum order of :97, every operation rounded, nothing contracted.  With attr = the vertex normals, out is the vector the reference
+ * normalises and flips into hitInfo.normal (tested bit for bit against the normals cgrt_intersect_batch returns).
+ * Findings:
+ *   SA1  the weights are UNSIGNED area ratios: never negative, whatever side of an edge p is on;
+ *   SA2  they are not renormalised: their sum is 1 only up to rounding (largest deviation seen on 20 000 rays of the blob scene: 2.4e-7);
+ *   SA3  a zero-area triangle gives the inf / NaN the formula gives.
+ * The value is a pure function of (ray, t, prim_id).  The ray and t are taken as given (as cgrt_shade_rays takes its rays); nothing checks
+ * that p lies in the triangle.  Zeros are written to every requested output of an item that is a miss (hit == 0, or prim_id ==
+ * CGRT_NO_PRIM), a sphere hit (prim_id >= ntris) or carries any other out-of-range prim_id: a caller-supplied id never indexes out of
+ * bounds.  (The frame forms have no hit flag: a miss is the CGRT_NO_PRIM of the prim_id plane.)
+ *
+ * Ray lists.  rays / hits are what cgrt_intersect_batch[_device] took and returned (t and prim_id are read from hits[i], origin and
+ * direction from rays[i]); bary is n x 3 f32 {alpha, beta, gamma}; out is n x channels f32; attr is nverts x channels f32 -- an argument
+ * of the call, so a table that changes every iteration needs no registration.  In the device forms every pointer, d_attr included, is
+ * device memory of the scene's device.
+ * Frames.  cgrt_surface_views_device takes nviews Trackball cameras, cgrt_surface_raycams_device ray cameras; d_depth (f32) and d_prim_id
+ * (u32) are (B, H, W) planes -- the depth and prim_id geometry planes of cgrt_render_views_aov_device / cgrt_render_raycams_device, or the
+ * t and prim_id columns of cgrt_trace_primary_views_device's hits gathered into planes.  The primary ray of every pixel is regenerated
+ * from the camera by the expressions the frame was traced with: no ray buffer exists and nothing is traced again.  d_bary is (B, H, W, 3),
+ * d_out (B, H, W, C); with chw != 0 they are (B, 3, H, W) and (B, C, H, W).  Either may be NULL, not both; d_attr / channels are read only
+ * with d_out.  Rows are not y-flipped and every pixel of every requested output is written.  For the planes of an anti-aliased frame
+ * (cgrt_render_aov_device with aa) pass 2W, 2H: the sub-sample rays are the 2W x 2H frame's (finding AA3).
+ * Streams.  The device forms only enqueue on `stream` (NULL = default stream), like cgrt_intersect_batch_device: they are concurrent on
+ * one scene and neither read nor write the prediction record or the frame hints.  The frame forms copy the camera table as
+ * cgrt_trace_primary_views_device does (`cams` is reusable at once; four table slots).  The host forms run on a call lane like
+ * cgrt_intersect_batch and are synchronous.
+ * Lookup.  The kernel needs, per prim_id, the triangle's record and its three vertex indices: a table of 16 bytes per triangle, built and
+ * uploaded (synchronously) by the scene's FIRST surface call, under a mutex of the scene, and released by cgrt_scene_destroy;
+ * cgrt_device_bytes grows by its size then.  A scene that never makes a surface call keeps its cgrt_device_bytes, its
+ * cgrt_debug_layout_hash and every array it had before these entries existed.
+ * Limits: channels 1..256; n <= 0x7fffffff; frames: the limits of cgrt_trace_primary_views_device (nviews * W * H <= 0x7fffffff, at most
+ * 2^18 64x64 super-tiles); an output of n x channels x 4 bytes may not exceed 2^40 bytes (the kernel indexes with 64 bits; the bound is a
+ * stated one.  For frames the views limits already imply it: 2^18 super-tiles hold 2^30 pixels, 2^40 bytes at 256 channels).
+ * Checks, all CGRT_E_ARG, in this order and before any device work.
+ *   Lists: NULL scene, or with n > 0 NULL rays / hits / bary / out / attr; n > 0x7fffffff; (interpolation) channels outside 1..256, the
+ *   output above 2^40 bytes; (device forms) a pointer not 4-byte aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and
+ *   touches nothing.  Device forms: then d_rays (n * 28 bytes), d_hits (n * 16), d_attr (nverts * channels * 4) and the output checked as
+ *   device memory of the scene's device, as cgrt_shade_rays_device checks its buffers.
+ *   Frames: NULL scene / d_depth / d_prim_id, d_bary and d_out both NULL, d_out with NULL d_attr; NULL cams, (ray cameras) the camera
+ *   checks, nviews == 0, W or H <= 0, the views limits; (with d_out) channels outside 1..256; a pointer not 4-byte aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.  Then d_depth, d_prim_id, d_attr, d_bary, d_out checked as device memory.
+ * Not offered: planes inside the cgrt_render_*aov* calls (CgrtAovOut keeps its size: two enqueued calls on one stream give the same
+ * result without a second trace); per-triangle attributes (a plain gather by prim_id); enqueued-ticket forms (these calls never block);
+ * sphere parameterisations; derivatives; the C++ host mirror (the reference's HitInfo has no such field). */
+int cgrt_hit_barycentrics(CgrtScene* scene, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, float* bary);
+int cgrt_hit_barycentrics_device(CgrtScene* scene, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, float* d_bary, void* stream);
+int cgrt_interpolate_hits(CgrtScene* scene, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* attr, uint32_t channels,
+                          float* out);
+int cgrt_interpolate_hits_device(CgrtScene* scene, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_attr,
+                                 uint32_t channels, float* d_out, void* stream);
+int cgrt_surface_views_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                              const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw,
+                              void* stream);
+int cgrt_surface_raycams_device(CgrtScene* scene, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw,
+                                void* stream);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
