@@ -29,6 +29,9 @@ NO_PRIM = 0xFFFFFFFF
 RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("direction", np.float32, 3), ("t", np.float32)])
 HIT_DTYPE = np.dtype([("t", np.float32), ("prim_id", np.uint32), ("material_id", np.int32), ("hit", np.uint32)])
 assert RAY_DTYPE.itemsize == 28 and HIT_DTYPE.itemsize == 16
+# include/cgrt.h CgrtClosest: one closest-point answer (32 bytes); bary = {u, v, w}, the weights of the triangle's three vertices
+CLOSEST_DTYPE = np.dtype([("point", np.float32, 3), ("dist2", np.float32), ("prim_id", np.uint32), ("bary", np.float32, 3)])
+assert CLOSEST_DTYPE.itemsize == 32
 
 
 class CgrtError(RuntimeError):
@@ -230,7 +233,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -340,6 +343,10 @@ def lib() -> C.CDLL:
     L.cgrt_interpolate_hits_device.argtypes = [vp, vp, vp, u64, vp, u32, vp, vp]
     L.cgrt_surface_views_device.argtypes = [vp, vp, u32, i32, i32, vp, vp, vp, u32, vp, vp, i32, vp]
     L.cgrt_surface_raycams_device.argtypes = L.cgrt_surface_views_device.argtypes
+    L.cgrt_closest_points.argtypes = [vp, vp, u64, C.c_float, vp]
+    L.cgrt_closest_points_brute.argtypes = [vp, vp, u64, C.c_float, vp]
+    L.cgrt_closest_points_device.argtypes = [vp, vp, u64, C.c_float, vp, vp]
+    L.cgrt_debug_closest_work.argtypes = [vp, vp, u64, C.c_float, vp]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
     L.cgrt_count_batch.argtypes = [vp, vp, u64, C.POINTER(Counters)]
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
@@ -1711,6 +1718,55 @@ class Scene:
         return self._tensor_call(out, lead + (ch,), torch.float32, stream,
                                  lambda o, s: self.interpolate_hits_device(rays.data_ptr(), hits.data_ptr(), n, attr.data_ptr(), ch,
                                                                            o.data_ptr(), stream=s))
+
+    # ---- closest-point queries (include/cgrt.h cgrt_closest_points*) ----
+    def _closest_host(self, f, points, max_dist2: float) -> np.ndarray:
+        p = _f32(points, (-1, 3))
+        out = np.zeros(len(p), CLOSEST_DTYPE)
+        _check(f(self._h, _ptr(p), len(p), float(max_dist2), _ptr(out)))
+        return out
+
+    def closest_points(self, points, max_dist2: float = float("inf")) -> np.ndarray:
+        """cgrt_closest_points: the nearest point of the scene's triangles for every query point ((n, 3) float32) within the squared
+        radius max_dist2 (inf: unbounded).  Returns a CLOSEST_DTYPE array {point, dist2, prim_id, bary = {u, v, w}}; a query that finds
+        nothing (or is not finite) gets {0, +inf, NO_PRIM, 0}.  Equal distances go to the smaller prim_id.  Spheres are ignored."""
+        return self._closest_host(lib().cgrt_closest_points, points, max_dist2)
+
+    def closest_points_brute(self, points, max_dist2: float = float("inf")) -> np.ndarray:
+        """cgrt_closest_points_brute: closest_points by testing every triangle in turn (validation; the same bytes)."""
+        return self._closest_host(lib().cgrt_closest_points_brute, points, max_dist2)
+
+    def closest_points_device(self, d_points_ptr: int, n: int, d_out_ptr: int, max_dist2: float = float("inf"), stream: int = 0) -> None:
+        """cgrt_closest_points_device: n points (3 floats each) at d_points_ptr -> n CLOSEST_DTYPE records (32 bytes each) at d_out_ptr,
+        enqueued on the hipStream_t `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        _check(lib().cgrt_closest_points_device(self._h, vp(d_points_ptr), int(n), float(max_dist2), vp(d_out_ptr), vp(stream)))
+
+    def closest_points_tensor(self, points, max_dist2: float = float("inf"), out=None, stream=None):
+        """closest_points on torch tensors: points (n, 3) float32 on cuda:<device> -> an (n, 8) float32 tensor of CLOSEST_DTYPE records
+        (`out`, or a new one), enqueued on `stream` (default: torch.cuda.current_stream()).  Returns a dict of views of it: 'point'
+        (n, 3), 'dist2' (n,), 'prim_id' (n,) int32 (-1 = NO_PRIM), 'bary' (n, 3), and 'out' itself."""
+        import torch
+
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be a torch tensor of shape (n, 3)")
+        self._device_tensor(points, "points", (torch.float32,))
+        n = points.shape[0]
+        if out is not None:
+            self._device_tensor(out, "out", (torch.float32,), (n, 8))
+        o = self._tensor_call(out, (n, 8), torch.float32, stream,
+                              lambda t, s: self.closest_points_device(points.data_ptr(), n, t.data_ptr(), max_dist2=max_dist2, stream=s))
+        return {"point": o[:, 0:3], "dist2": o[:, 3], "prim_id": o.view(torch.int32)[:, 4], "bary": o[:, 5:8], "out": o}
+
+    def debug_closest_work(self, points, max_dist2: float = float("inf")):
+        """cgrt_debug_closest_work: (node steps, triangles evaluated) of closest_points' search, summed over the queries (a separate
+        counting launch)."""
+        p = _f32(points, (-1, 3))
+        w = np.zeros(2, np.uint64)
+        _check(lib().cgrt_debug_closest_work(self._h, _ptr(p), len(p), float(max_dist2), _ptr(w)))
+        return int(w[0]), int(w[1])
 
     def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream):
         import torch

@@ -29,6 +29,7 @@
 #include "bvh_builder.h"
 #include "cgrt_layout.h"
 #include "cgrt_math.h"
+#include "closest_kernels.h"
 #include "surface_kernels.h"
 #include "trace_kernels.h"
 
@@ -3868,6 +3869,74 @@ int cgrt_surface_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nvi
 int cgrt_surface_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
                                 const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
     return surface_frames_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_attr, channels, d_bary, d_out, chw, stream);
+}
+
+// ---- closest-point queries (include/cgrt.h cgrt_closest_points*): the nearest surface point of every query point.
+// Nothing is traced and no scene state is read or written; the checks come in the order include/cgrt.h states, all before any device work.
+namespace {
+static_assert(sizeof(CgrtClosest) == sizeof(CgrtClosestDev), "CgrtClosest is what the kernels write");
+int closest_args(const CgrtScene* s, const void* points, uint64_t n, float max_dist2, const void* out, bool device) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    if (n && (!points || !out)) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many queries: n exceeds 0x7fffffff");
+    if (!(max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)out % 4)) return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    return CGRT_OK;
+}
+// host pointers, on a call lane (slots: 0 the points, 1 the records); how: 0 tree search, 1 brute force, 2 counted tree search
+int closest_host(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out, int how, uint64_t* work) {
+    int rc = closest_args(s, points, n, max_dist2, how == 2 ? static_cast<const void*>(work) : out, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    LaneGuard g(s);
+    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    const size_t out_bytes = (size_t)n * sizeof(CgrtClosest);
+    void *dp = nullptr, *dout = nullptr, *staged = nullptr;
+    HIP_TRY(g.dev(0, n * 12, &dp));
+    HIP_TRY(g.dev(1, out_bytes, &dout));
+    HIP_TRY(lane_upload(g, 0, dp, points, n * 12));
+    if (how == 2) {
+        HIP_TRY(hipMemsetAsync(g.L->d_counters, 0, 2 * sizeof(unsigned long long), g.L->stream));
+        HIP_TRY(launch_closest(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), g.L->d_counters, g.L->stream));
+        unsigned long long h[2];
+        HIP_TRY(hipMemcpyAsync(h, g.L->d_counters, sizeof(h), hipMemcpyDeviceToHost, g.L->stream));
+        HIP_TRY(hipStreamSynchronize(g.L->stream));
+        work[0] = h[0];
+        work[1] = h[1];
+        return CGRT_OK;
+    }
+    if (how == 1)
+        HIP_TRY(launch_closest_brute(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), g.L->stream));
+    else
+        HIP_TRY(launch_closest(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), nullptr, g.L->stream));
+    HIP_TRY(lane_download(g, 1, out, dout, out_bytes, &staged));
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    if (staged) std::memcpy(out, staged, out_bytes);
+    return CGRT_OK;
+}
+}  // namespace
+
+int cgrt_closest_points(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out) {
+    return closest_host(s, points, n, max_dist2, out, 0, nullptr);
+}
+int cgrt_closest_points_brute(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out) {
+    return closest_host(s, points, n, max_dist2, out, 1, nullptr);
+}
+int cgrt_debug_closest_work(CgrtScene* s, const float* points, uint64_t n, float max_dist2, uint64_t* out2) {
+    return closest_host(s, points, n, max_dist2, nullptr, 2, out2);
+}
+int cgrt_closest_points_device(CgrtScene* s, const float* d_points, uint64_t n, float max_dist2, CgrtClosest* d_out, void* stream) {
+    int rc = closest_args(s, d_points, n, max_dist2, d_out, true);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_out, n * sizeof(CgrtClosest), "d_out")) != CGRT_OK) return rc;
+    HIP_TRY(launch_closest(s->dev, d_points, n, max_dist2, reinterpret_cast<CgrtClosestDev*>(d_out), nullptr, static_cast<hipStream_t>(stream)));
+    return CGRT_OK;
 }
 
 int cgrt_debug_export_frame(int device, const float* rgb, int W, int H, int format, uint64_t row_bytes, void* out) {

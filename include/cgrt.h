@@ -710,6 +710,64 @@ int cgrt_surface_raycams_device(CgrtScene* scene, const CgrtRayCamera* cams, uin
                                 const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw,
                                 void* stream);
 
+/* Closest-point queries: "which point of the surface is nearest to p?" for a list of points -- the other question
+ * put to a triangle BVH (distance fields, snapping and registration of point clouds, collision margins, carrying per-vertex data to
+ * arbitrary points).  Nothing is traced; the reference has no such function, so the definition below IS the specification.
+ * Definition (bit level).  All arithmetic is f32, every operation rounded, nothing contracted.  For a query point p and a triangle with
+ * a, b, c = v0, v1, v2 of its record (the f32 positions of tri[prim_id][0..2] as given to cgrt_scene_create), with
+ * dot(x, y) = (x0*y0 + x1*y1) + x2*y2:
+ *   ab = b-a  ac = c-a  ap = p-a  bp = p-b  cp = p-c
+ *   d1 = dot(ab,ap)  d2 = dot(ac,ap)  d3 = dot(ab,bp)  d4 = dot(ac,bp)  d5 = dot(ab,cp)  d6 = dot(ac,cp)
+ *   vc = d1*d4 - d3*d2   vb = d5*d2 - d1*d6   va = d3*d6 - d5*d4   e1 = d4-d3   e2 = d5-d6
+ *   the first region whose test is true:
+ *     A   d1 <= 0 && d2 <= 0                v = 0, w = 0,  q = a
+ *     B   d3 >= 0 && d4 <= d3               v = 1, w = 0,  q = b
+ *     AB  vc <= 0 && d1 >= 0 && d3 <= 0     v = d1 / (d1-d3), w = 0
+ *     C   d6 >= 0 && d5 <= d6               v = 0, w = 1,  q = c
+ *     AC  vb <= 0 && d2 >= 0 && d6 <= 0     v = 0, w = d2 / (d2-d6)
+ *     BC  va <= 0 && e1 >= 0 && e2 >= 0     w = e1 / (e1+e2), v = 1.0f - w
+ *     else                                  den = 1.0f / ((va+vb)+vc), v = vb*den, w = vc*den
+ *   non-vertex regions: q.k = (a.k + ab.k*v) + ac.k*w   (the full expression, also when v or w is 0)
+ *   u = (1.0f - v) - w
+ *   clamp: lo.k / hi.k = min / max of a.k, b.k, c.k;  q.k = q.k < lo.k ? lo.k : (q.k > hi.k ? hi.k : q.k)
+ *   r = p - q;  dist2 = dot(r, r)
+ * This is Ericson's region walk plus one clamp of q to the triangle's own bounding box; the clamp is part of the definition (it is what
+ * makes the tree search exact, below).  A NaN anywhere makes every region test false and dist2 NaN.
+ * Result of a query.  Among the triangles with dist2 <= max_dist2 (a NaN never qualifies) the one with the smallest dist2; equal dist2
+ * goes to the smaller prim_id (queries at a shared vertex tie exactly).  out[i] = {point = q, dist2, prim_id, bary = {u, v, w}}; when
+ * nothing qualifies, {0,0,0, +inf, CGRT_NO_PRIM, 0,0,0}.  A non-finite p gets that miss record without a search; in a scene without meshes
+ * every query misses.  Spheres are ignored.  points is n x 3 f32; max_dist2 = +inf means unbounded.
+ * Exactness.  Box lower bound: dx.k = max(max(lo.k - p.k, p.k - hi.k), 0), lb2 = (dx0*dx0 + dx1*dx1) + dx2*dx2 -- dist2's operations and
+ * association.  Every box of the structures is the exact min / max of its triangles' vertices, the clamped q lies in its triangle's box,
+ * hence in every ancestor box: per axis |p.k - q.k| >= dx.k in the reals, and rounding, squaring and same-order summing are monotone, so
+ * lb2 <= dist2 holds in f32 with no slack.  The search skips a subtree iff `lb2 > bound` is TRUE (bound = the best dist2 so far, max_dist2
+ * while nothing has been accepted; strict, a NaN never culls) and therefore returns exactly what cgrt_closest_points_brute -- every
+ * triangle in turn, same function, same rule; a validation path, not a fast one -- returns, bit for bit.
+ * The search uses the structure every scene has (the reference tree, the in-leaf accelerators, linear leaves under
+ * cgrt_set_leaf_accel(0)); the walk settings (cgrt_scene_set_walk, cgrt_set_fast_tree, cgrt_set_kernel_shape) do not change it.
+ * Streams.  The host forms (host pointers, synchronous) run on a call lane like cgrt_occluded: any number of threads may query one scene
+ * at once.  cgrt_closest_points_device reads no host array: it only enqueues on `stream` (NULL = default stream), asynchronously, like
+ * cgrt_intersect_batch_device, and neither reads nor writes the prediction record or the frame hints.  Only records 0..n-1 are written.
+ * cgrt_debug_closest_work: a separate counting launch of the same search (never part of a timed region); out2 = {node steps, triangles
+ * evaluated}, summed over the n queries.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene; NULL points or out with n > 0; n > 0x7fffffff; max_dist2
+ * NaN or negative; (device form) a pointer not 4-byte aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and touches
+ * nothing.  Device form: then d_points (n * 12 bytes) and d_out (n * 32 bytes) checked as device memory of the scene's device, as
+ * cgrt_shade_rays_device checks its buffers.
+ * Not offered: signed distance; sphere primitives; k nearest; a per-query radius; attribute interpolation at the closest point
+ * (attr[tri[prim_id]] weighted by bary is a plain gather); the fast tree as a search structure; enqueued-ticket forms (the device form
+ * never blocks); the C++ host mirror (the reference has no such function). */
+typedef struct CgrtClosest {
+    float point[3];   /* q, the nearest point of the triangle                   */
+    float dist2;      /* |p - q|^2 as defined above; +inf on a miss             */
+    uint32_t prim_id; /* CGRT_NO_PRIM on a miss                                 */
+    float bary[3];    /* {u, v, w}: the weights of v0, v1, v2                   */
+} CgrtClosest;
+int cgrt_closest_points(CgrtScene* scene, const float* points, uint64_t n, float max_dist2, CgrtClosest* out);
+int cgrt_closest_points_device(CgrtScene* scene, const float* d_points, uint64_t n, float max_dist2, CgrtClosest* d_out, void* stream);
+int cgrt_closest_points_brute(CgrtScene* scene, const float* points, uint64_t n, float max_dist2, CgrtClosest* out);
+int cgrt_debug_closest_work(CgrtScene* scene, const float* points, uint64_t n, float max_dist2, uint64_t* out2);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
