@@ -233,7 +233,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -263,6 +263,11 @@ def lib() -> C.CDLL:
     L.cgrt_num_subnodes.argtypes = [vp]
     L.cgrt_debug_check_layout.argtypes = [vp]
     L.cgrt_debug_layout_hash.argtypes = [vp, C.POINTER(u64)]
+    L.cgrt_debug_node_pack.argtypes = [vp, vp, u32, vp]
+    L.cgrt_debug_node_pack.restype = None
+    L.cgrt_debug_node_unpack.argtypes = [vp, vp, vp, C.POINTER(u32)]
+    L.cgrt_debug_node_unpack.restype = None
+    L.cgrt_debug_get_subnodes.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), vp, C.POINTER(u32)]
     L.cgrt_set_build_threads.argtypes = [i32]
     L.cgrt_set_primary_mode.argtypes = [i32]
     L.cgrt_set_fast_tree.argtypes = [i32]
@@ -398,6 +403,25 @@ def _as_ray_array(rays) -> np.ndarray:
             raise ValueError("rays must be a RAY_DTYPE array or an (n, 7) float32 array")
         a = a.view(RAY_DTYPE).reshape(-1)
     return np.ascontiguousarray(a)
+
+
+def node_pack(boxes, refs, leaf_index: int = 0) -> np.ndarray:
+    """cgrt_debug_node_pack: four child boxes (4, 6) {lower.xyz, upper.xyz}, four references and a leaf index -> the node's 32 words."""
+    b = _f32(boxes, (4, 6))
+    r = np.ascontiguousarray(refs, dtype=np.uint32).reshape(4)
+    words = np.zeros(32, dtype=np.uint32)
+    lib().cgrt_debug_node_pack(_ptr(b), _ptr(r), leaf_index, _ptr(words))
+    return words
+
+
+def node_unpack(words):
+    """cgrt_debug_node_unpack: a node's 32 words -> (boxes (4, 6), refs (4,), leaf index) through the builder's load helpers."""
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(32)
+    boxes = np.zeros((4, 6), dtype=np.float32)
+    refs = np.zeros(4, dtype=np.uint32)
+    li = C.c_uint32()
+    lib().cgrt_debug_node_unpack(_ptr(w), _ptr(boxes), _ptr(refs), C.byref(li))
+    return boxes, refs, li.value
 
 
 def record_sizes() -> dict:
@@ -701,6 +725,19 @@ class Scene:
     def check_layout(self) -> None:
         """cgrt_debug_check_layout: raises when a reference of the record arrays is inconsistent."""
         _check(lib().cgrt_debug_check_layout(self._h))
+
+    def subnodes(self) -> dict:
+        """cgrt_debug_get_subnodes: the 4-wide nodes as the device reads them -- `words` (n, 32) uint32, one row per 128-byte node;
+        `sub_base` the record index of node 0; `fast_root`; `leaf_roots` the record index of every reference leaf's accelerator root
+        (0xffffffff: none)."""
+        L = lib()
+        n = self.num_subnodes()
+        words = np.zeros((n // 2, 32), dtype=np.uint32)
+        base, root, nleaves = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(L.cgrt_debug_get_subnodes(self._h, None, None, None, None, C.byref(nleaves)))
+        roots = np.zeros(max(nleaves.value, 1), dtype=np.uint32)
+        _check(L.cgrt_debug_get_subnodes(self._h, _ptr(words) if n else None, C.byref(base), C.byref(root), _ptr(roots), None))
+        return {"words": words, "sub_base": base.value, "fast_root": root.value, "leaf_roots": roots[: nleaves.value]}
 
     def layout_hash(self) -> int:
         """cgrt_debug_layout_hash: FNV-1a over every array the device reads."""

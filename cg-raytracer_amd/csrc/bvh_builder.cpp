@@ -190,7 +190,7 @@ struct SubBuilder {
     }
 
     // 4-wide node over idx[b, e) (more than leaf_tris triangles): split in two, then each half again; the node is two
-    // consecutive SubNode records {children 0,1} {children 2,3}; a missing child has an empty box (never hit).
+    // consecutive SubNode records (cgrt_layout.h: transposed quarters); a missing child has an empty box (never hit).
     uint32_t build4(uint32_t base, uint32_t b, uint32_t e, int depth_left) {
         const uint32_t me = (uint32_t)nodes.size();
         nodes.push_back(SubNode());
@@ -220,13 +220,9 @@ struct SubBuilder {
                 ref[c] = REF_NONE;
             }
         }
-        for (int r = 0; r < 2; r++) {
-            SubNode& N = nodes[me + r];
-            sub_box_store(N.box0, box[2 * r]);
-            sub_box_store(N.box1, box[2 * r + 1]);
-            N.ref0 = ref[2 * r];
-            N.ref1 = ref[2 * r + 1];
-            N.pad[0] = N.pad[1] = 0;
+        for (int c = 0; c < 4; c++) {  // (nodes.push_back above may have moved the array: address the node now)
+            sub_box_store(&nodes[me], c, box[c]);
+            sub_child_ref(&nodes[me], c) = ref[c];
         }
         return me;
     }
@@ -313,11 +309,12 @@ void build_leaf_accelerators(BuiltBvh& out, int leaf_tris, int threads) {
     }
     for (unsigned t = 0; t < nthreads; t++) {
         const uint32_t base = (uint32_t)out.subnodes.size();
-        for (SubNode N : part[t]) {
-            for (uint32_t* r : {&N.ref0, &N.ref1})
-                if (*r != REF_NONE && !(*r & REF_LEAF)) *r += base;  // node references were local to the part
-            out.subnodes.push_back(N);
-        }
+        out.subnodes.insert(out.subnodes.end(), part[t].begin(), part[t].end());
+        for (size_t i = base; i < out.subnodes.size(); i += 2)
+            for (int c = 0; c < 4; c++) {
+                uint32_t& r = sub_child_ref(&out.subnodes[i], c);
+                if (r != REF_NONE && !(r & REF_LEAF)) r += base;  // node references were local to the part
+            }
         const size_t b = nleaves * t / nthreads, e = nleaves * (t + 1) / nthreads;
         for (size_t i = b; i < e; i++)
             if (out.leaves[i].sub_root != REF_NONE) out.leaves[i].sub_root += base;
@@ -542,13 +539,9 @@ struct TopBuilder {
                 cref[c] = REF_NONE;
             }
         }
-        for (int r = 0; r < 2; r++) {
-            SubNode& N = nodes[me + r];
-            sub_box_store(N.box0, cbox[2 * r]);
-            sub_box_store(N.box1, cbox[2 * r + 1]);
-            N.ref0 = cref[2 * r];
-            N.ref1 = cref[2 * r + 1];
-            N.pad[0] = N.pad[1] = 0;
+        for (int c = 0; c < 4; c++) {  // (nodes.push_back above may have moved the array: address the node now)
+            sub_box_store(&nodes[me], c, cbox[c]);
+            sub_child_ref(&nodes[me], c) = cref[c];
         }
         return TOP_LOCAL | me;
     }
@@ -560,26 +553,26 @@ static uint32_t stitch(std::vector<SubNode>& dst, const std::vector<SubNode>& sr
     const uint32_t at = (uint32_t)dst.size();
     dst.push_back(src[r]);
     dst.push_back(src[r + 1]);
-    for (int h = 0; h < 2; h++)
-        for (int c = 0; c < 2; c++) {
-            const uint32_t cr = c ? src[r + h].ref1 : src[r + h].ref0;
-            uint32_t out_ref = cr;
-            if (cr != REF_NONE && !(cr & REF_LEAF)) {
-                if (cr & TOP_LOCAL) {
-                    out_ref = stitch(dst, src, cr & ~TOP_LOCAL, tasks);
-                } else if (cr & TOP_TASK) {  // a task's part is already in pre-order: append it whole, shifted
-                    const TopTask& T = tasks[cr & ~TOP_TASK];
-                    const uint32_t base = (uint32_t)dst.size();
-                    for (SubNode N : T.nodes) {
-                        for (uint32_t* q : {&N.ref0, &N.ref1})
-                            if (*q != REF_NONE && !(*q & REF_LEAF) && (*q & TOP_LOCAL)) *q = (*q & ~TOP_LOCAL) + base;
-                        dst.push_back(N);
+    for (int c = 0; c < 4; c++) {
+        const uint32_t cr = sub_child_ref(&src[r], c);
+        uint32_t out_ref = cr;
+        if (cr != REF_NONE && !(cr & REF_LEAF)) {
+            if (cr & TOP_LOCAL) {
+                out_ref = stitch(dst, src, cr & ~TOP_LOCAL, tasks);
+            } else if (cr & TOP_TASK) {  // a task's part is already in pre-order: append it whole, shifted
+                const TopTask& T = tasks[cr & ~TOP_TASK];
+                const uint32_t base = (uint32_t)dst.size();
+                dst.insert(dst.end(), T.nodes.begin(), T.nodes.end());
+                for (size_t i = base; i < dst.size(); i += 2)
+                    for (int k = 0; k < 4; k++) {
+                        uint32_t& q = sub_child_ref(&dst[i], k);
+                        if (q != REF_NONE && !(q & REF_LEAF) && (q & TOP_LOCAL)) q = (q & ~TOP_LOCAL) + base;
                     }
-                    out_ref = (T.root & ~TOP_LOCAL) + base;
-                }
+                out_ref = (T.root & ~TOP_LOCAL) + base;
             }
-            (c ? dst[at + h].ref1 : dst[at + h].ref0) = out_ref;
         }
+        sub_child_ref(&dst[at], c) = out_ref;
+    }
     return at;
 }
 
@@ -654,15 +647,11 @@ void build_fast_tree(BuiltBvh& out, bool force, bool leaf_accel, int open, int t
                 r2.push_back(ref[i]);
                 continue;
             }
-            for (int h = 0; h < 2; h++) {
-                const SubNode& N = out.subnodes[ref[i] + h];
-                const uint32_t cr[2] = {N.ref0, N.ref1};
-                const float* cb[2] = {N.box0, N.box1};
-                for (int c = 0; c < 2; c++) {
-                    if (cr[c] == REF_NONE) continue;
-                    b2.push_back(sub_box_load(cb[c]));
-                    r2.push_back(cr[c]);
-                }
+            const SubNode* N = &out.subnodes[ref[i]];
+            for (int c = 0; c < 4; c++) {
+                if (sub_child_ref(N, c) == REF_NONE) continue;
+                b2.push_back(sub_box_load(N, c));
+                r2.push_back(sub_child_ref(N, c));
             }
         }
         box.swap(b2);
@@ -985,15 +974,13 @@ bool build_reference_bvh(const HostScene& sc, const BuildOptions& opt, BuiltBvh&
         L.first += out.tri_base;
         if (L.sub_root != REF_NONE) L.sub_root += out.sub_base;
     }
-    for (SubNode& N : out.subnodes)
-        for (uint32_t* r : {&N.ref0, &N.ref1})
-            if (*r != REF_NONE) *r += (*r & REF_LEAF) ? out.tri_base : out.sub_base;
+    // (every record index stays below SUB_MAX_RECORDS, so a node's byte offset in the record array fits 32 bits: cgrt_layout.h)
+    for (size_t i = 0; i + 1 < out.subnodes.size(); i += 2)
+        for (int c = 0; c < 4; c++) {
+            uint32_t& r = sub_child_ref(&out.subnodes[i], c);
+            if (r != REF_NONE) r += (r & REF_LEAF) ? out.tri_base : out.sub_base;
+        }
     if (out.fast_root != REF_NONE) out.fast_root += (out.fast_root & REF_LEAF) ? out.tri_base : out.sub_base;
-    // the device reads all four child references of a node with ONE 16-byte load: the first half's last quarter
-    for (size_t i = 0; i + 1 < out.subnodes.size(); i += 2) {
-        out.subnodes[i].pad[0] = out.subnodes[i + 1].ref0;
-        out.subnodes[i].pad[1] = out.subnodes[i + 1].ref1;
-    }
     out.root_box = out.nodes[0].box;
     out.root_ref = ref_of(0);
     if (!out.subnodes.empty()) {
@@ -1003,7 +990,7 @@ bool build_reference_bvh(const HostScene& sc, const BuildOptions& opt, BuiltBvh&
             const uint32_t li = r & ~REF_LEAF;
             const uint32_t root = out.leaves[li].sub_root;
             if (root == REF_NONE) return r;
-            out.subnodes[root - out.sub_base + 1].pad[0] = li;  // (second half: the first half's pad words carry references)
+            sub_leaf_index(&out.subnodes[root - out.sub_base]) = li;
             return REF_LEAF | REF_LEAF_ACCEL | root;
         };
         for (NodePacket& P : out.packets) {

@@ -742,6 +742,40 @@ int cgrt_debug_layout_hash(const CgrtScene* s, uint64_t* out) {
     *out = h;
     return CGRT_OK;
 }
+void cgrt_debug_node_pack(const float* boxes, const uint32_t* refs, uint32_t leaf_index, uint32_t* words) {
+    SubNode node[2] = {};
+    for (int c = 0; c < SUB_WIDTH; c++) {
+        Box6 b;
+        std::memcpy(b.lo, boxes + 6 * c, 12);
+        std::memcpy(b.hi, boxes + 6 * c + 3, 12);
+        sub_box_store(node, c, b);
+        sub_child_ref(node, c) = refs[c];
+    }
+    sub_leaf_index(node) = leaf_index;
+    std::memcpy(words, node, sizeof(node));
+}
+void cgrt_debug_node_unpack(const uint32_t* words, float* boxes, uint32_t* refs, uint32_t* leaf_index) {
+    SubNode node[2];
+    std::memcpy(node, words, sizeof(node));
+    for (int c = 0; c < SUB_WIDTH; c++) {
+        const Box6 b = sub_box_load(node, c);
+        std::memcpy(boxes + 6 * c, b.lo, 12);
+        std::memcpy(boxes + 6 * c + 3, b.hi, 12);
+        refs[c] = sub_child_ref(node, c);
+    }
+    *leaf_index = sub_leaf_index(node);
+}
+int cgrt_debug_get_subnodes(const CgrtScene* s, uint32_t* words, uint32_t* sub_base, uint32_t* fast_root, uint32_t* leaf_roots, uint32_t* nleaves) {
+    if (!s) return fail(CGRT_E_ARG, "NULL scene");
+    const BuiltBvh& B = s->bvh;
+    if (words && !B.subnodes.empty()) std::memcpy(words, B.subnodes.data(), B.subnodes.size() * sizeof(SubNode));
+    if (sub_base) *sub_base = B.sub_base;
+    if (fast_root) *fast_root = B.fast_root;
+    if (leaf_roots)
+        for (size_t i = 0; i < B.leaves.size(); i++) leaf_roots[i] = B.leaves[i].sub_root;
+    if (nleaves) *nleaves = (uint32_t)B.leaves.size();
+    return CGRT_OK;
+}
 int cgrt_debug_check_layout(CgrtScene* s) {
     if (!s) return fail(CGRT_E_ARG, "NULL scene");
     const BuiltBvh& B = s->bvh;
@@ -756,7 +790,7 @@ int cgrt_debug_check_layout(CgrtScene* s) {
         if (r & REF_LEAF_ACCEL) {
             const uint32_t root = r & REF_INDEX26;
             if (root < B.sub_base || root >= B.tri_base || ((root - B.sub_base) & 1u)) return false;
-            li = B.subnodes[root - B.sub_base + 1].pad[0];
+            li = sub_leaf_index(&B.subnodes[root - B.sub_base]);
             if (li >= nleaf || B.leaves[li].sub_root != root) return false;
         } else {
             li = r & ~REF_LEAF;
@@ -770,6 +804,20 @@ int cgrt_debug_check_layout(CgrtScene* s) {
     auto check_topo_ref = [&](uint32_t r) -> bool {
         if (r == REF_NONE) return false;
         return (r & REF_LEAF) ? check_leaf_ref(r) : (r < npk);
+    };
+    // the transposed node (cgrt_layout.h SubNode): an absent child has an empty box (no ray enters it, whichever plane quarter
+    // it reads first), and the last quarter holds the leaf index of an accelerator root and zeros
+    auto check_node_quarters = [&](const SubNode* N, uint32_t leaf_index) -> bool {
+        for (int c = 0; c < SUB_WIDTH; c++) {
+            if (sub_child_ref(N, c) != REF_NONE) continue;
+            const Box6 b = sub_box_load(N, c);
+            for (int a = 0; a < 3; a++)
+                if (!(b.lo[a] > b.hi[a])) return false;
+        }
+        if (sub_leaf_index(N) != leaf_index) return false;
+        for (uint32_t w = SUB_LEAF_WORD + 1; w < 32; w++)
+            if (sub_word(N, w) != 0u) return false;
+        return true;
     };
     if (!check_topo_ref(B.root_ref)) return fail(CGRT_E_ARG, "bad root reference");
     const uint32_t real_packets = (uint32_t)(B.nodes.size() - nleaf);
@@ -796,13 +844,10 @@ int cgrt_debug_check_layout(CgrtScene* s) {
                 continue;
             }
             if (r < B.sub_base || r >= B.tri_base) return fail(CGRT_E_ARG, "accelerator node reference out of range");
-            const uint32_t width_recs = 2u;
             if ((r - B.sub_base) & 1u) return fail(CGRT_E_ARG, "4-wide node not 128-byte aligned");
-            for (uint32_t h = 0; h < width_recs; h++) {
-                const SubNode& N = B.subnodes[r - B.sub_base + h];
-                todo.push_back(N.ref0);
-                todo.push_back(N.ref1);
-            }
+            const SubNode* N = &B.subnodes[r - B.sub_base];
+            if (!check_node_quarters(N, r == L.sub_root ? li : 0u)) return fail(CGRT_E_ARG, "accelerator node: absent child or last quarter malformed");
+            for (int c = 0; c < SUB_WIDTH; c++) todo.push_back(sub_child_ref(N, c));
         }
     }
     for (uint32_t t = 0; t < ntri; t++)
@@ -826,11 +871,8 @@ int cgrt_debug_check_layout(CgrtScene* s) {
             }
             if (r < B.sub_base || r >= B.tri_base || ((r - B.sub_base) & 1u)) return fail(CGRT_E_ARG, "fast tree: node reference out of range");
             if (depth >= (int)(FAST_STACK_ENTRIES / (SUB_WIDTH - 1))) return fail(CGRT_E_ARG, "fast tree deeper than its stack allows");
-            for (uint32_t h = 0; h < 2; h++) {
-                const SubNode& N = B.subnodes[r - B.sub_base + h];
-                todo.push_back({N.ref0, depth + 1});
-                todo.push_back({N.ref1, depth + 1});
-            }
+            const SubNode* N = &B.subnodes[r - B.sub_base];
+            for (int c = 0; c < SUB_WIDTH; c++) todo.push_back({sub_child_ref(N, c), depth + 1});
         }
         for (uint32_t t = 0; t < ntri; t++)
             if (seen2[t] != 1) return fail(CGRT_E_ARG, "fast tree: a triangle record is reachable " + std::to_string(seen2[t]) + " times");

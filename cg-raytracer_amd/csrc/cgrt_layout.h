@@ -10,7 +10,7 @@ static const uint32_t REF_LEAF = 0x80000000u;
 static const uint32_t REF_NONE = 0xffffffffu;
 // A leaf with an in-leaf accelerator is referenced by the accelerator's root directly: REF_LEAF | REF_LEAF_ACCEL | index
 // of the root SubNode in the record array (26 bits), so that entering the leaf needs no LeafRec load; the leaf-table
-// index of such a leaf is kept in pad[0] of its root node's SECOND SubNode for the paths that want first/count (linear scan).
+// index of such a leaf is kept in the root node's last quarter (SUB_LEAF_WORD) for the paths that want first/count (linear scan).
 static const uint32_t REF_LEAF_ACCEL = 0x40000000u;
 static const uint32_t REF_INDEX26 = 0x03ffffffu;
 static const int MAX_LEVELS = 12;  // bvh.cpp:48 maxDepth; per-ray stack never exceeds MAX_LEVELS - 1
@@ -38,22 +38,29 @@ struct LeafRec {
 };
 static_assert(sizeof(LeafRec) == 16, "LeafRec must be 16 B");
 
-// Half a node of a leaf's in-leaf accelerator or of the fast tree (DESIGN.md "In-leaf accelerator", "Certified walk"): two
-// child boxes inline (64 B); a node is two consecutive SubNodes, 128-byte aligned.  A child is another SubNode
-// (ref = index) or a run of 1..32 TriRecords (ref = REF_LEAF | (count - 1) << 26 | first record).
-// A child box is stored per axis as the pair {lower, upper}: {lo.x, hi.x, lo.y, hi.y, lo.z, hi.z}, so that the two planes
-// of an axis are one operand of the packed FP32 pipe (walk_exact.h slab_cons).
-// In the FIRST half of a node pad[0], pad[1] repeat the second half's ref0, ref1, so that the device reads the four child
-// references with one 16-byte load (7 loads per node step instead of 8); in the second half pad[0] carries the leaf index
-// of an accelerator root (REF_LEAF_ACCEL).
+// A node of a leaf's in-leaf accelerator or of the fast tree (DESIGN.md "In-leaf accelerator", "Certified walk"): four child
+// boxes and four child references in 128 bytes, 128-byte aligned.  It lives in the 64-byte record array as two consecutive
+// SubNode halves (every index, count and reference counts halves), and is laid out TRANSPOSED, as eight 16-byte quarters:
+//   q0 = lo.x of children 0..3, q1 = hi.x, q2 = lo.y, q3 = hi.y, q4 = lo.z, q5 = hi.z
+//   q6 = the four child references
+//   q7 = word 0: the leaf index of an accelerator root (REF_LEAF_ACCEL), the rest zero
+// A child is another node (ref = index of its first half) or a run of 1..32 TriRecords (ref = REF_LEAF | (count - 1) << 26 |
+// first record); an absent child has REF_NONE and an empty box.
+// Why transposed: the plane of an axis a ray meets FIRST is the lower one for a positive direction component and the upper one
+// for a negative one -- a per-ray constant -- so a ray reads "the near planes of the four children" as quarter 2a + s_a and the
+// far ones as quarter 2a + 1 - s_a (s_a = sign of the clamped component): the choice is made in the load address, not by
+// selects on the loaded values (walk_exact.h slab_cons4).  sub_box_store / sub_box_load / sub_child_ref / sub_leaf_index are the only
+// host code that knows the slot arithmetic; the device's is in walk_exact.h (sub_node_step), walk_fast.h (quad_tail),
+// walk_quad.h (lane k finds child k's planes at words k, 4 + k, .. 20 + k) and closest_kernels.hip.
 struct alignas(16) SubNode {
-    float box0[6];
-    float box1[6];
-    uint32_t ref0, ref1;
-    uint32_t pad[2];
+    uint32_t w[16];
 };
+static const uint32_t SUB_REF_WORD = 24;   // word of child 0's reference in the 32 words of a node (quarter 6)
+static const uint32_t SUB_LEAF_WORD = 28;  // word of an accelerator root's leaf index (quarter 7)
 static const uint32_t SUB_RUN_MAX = 32;            // records per run
 static const uint32_t SUB_MAX_RECORDS = 1u << 26;  // run references address records with 26 bits
+// ... and the device addresses a node by a 32-bit BYTE offset from the start of the record array (walk_exact.h sub_node_step)
+static_assert((uint64_t)SUB_MAX_RECORDS * 64u <= (1ull << 32), "every record must lie below a 32-bit byte offset");
 static_assert(sizeof(SubNode) == 64, "SubNode must be 64 B");
 // The in-leaf accelerator is 4 wide: every node is TWO consecutive SubNode records (four child boxes: half the dependent
 // steps of a binary tree; measured +10 %, profiles/r1_exp_accelerator_width.txt).
@@ -102,21 +109,28 @@ struct SphereRecord {
 struct Box6 {
     float lo[3], hi[3];
 };
-// SubNode box slot <-> Box6
-inline void sub_box_store(float dst[6], const Box6& b) {
+// Node (two consecutive SubNode halves starting at `node`) <-> the boxes and references of its four children.
+inline uint32_t& sub_word(SubNode* node, uint32_t i) { return node[i >> 4].w[i & 15u]; }
+inline uint32_t sub_word(const SubNode* node, uint32_t i) { return node[i >> 4].w[i & 15u]; }
+inline void sub_box_store(SubNode* node, int child, const Box6& b) {
     for (int a = 0; a < 3; a++) {
-        dst[2 * a] = b.lo[a];
-        dst[2 * a + 1] = b.hi[a];
+        __builtin_memcpy(&sub_word(node, (uint32_t)(8 * a + child)), &b.lo[a], 4);
+        __builtin_memcpy(&sub_word(node, (uint32_t)(8 * a + 4 + child)), &b.hi[a], 4);
     }
 }
-inline Box6 sub_box_load(const float src[6]) {
+inline Box6 sub_box_load(const SubNode* node, int child) {
     Box6 b;
     for (int a = 0; a < 3; a++) {
-        b.lo[a] = src[2 * a];
-        b.hi[a] = src[2 * a + 1];
+        const uint32_t lo = sub_word(node, (uint32_t)(8 * a + child)), hi = sub_word(node, (uint32_t)(8 * a + 4 + child));
+        __builtin_memcpy(&b.lo[a], &lo, 4);
+        __builtin_memcpy(&b.hi[a], &hi, 4);
     }
     return b;
 }
+inline uint32_t& sub_child_ref(SubNode* node, int child) { return sub_word(node, SUB_REF_WORD + (uint32_t)child); }
+inline uint32_t sub_child_ref(const SubNode* node, int child) { return sub_word(node, SUB_REF_WORD + (uint32_t)child); }
+inline uint32_t& sub_leaf_index(SubNode* node) { return sub_word(node, SUB_LEAF_WORD); }
+inline uint32_t sub_leaf_index(const SubNode* node) { return sub_word(node, SUB_LEAF_WORD); }
 
 // Everything a kernel needs, passed by value.
 struct SceneDev {

@@ -201,15 +201,14 @@ __global__ __launch_bounds__(CGRT_CLOSEST_BLOCK) void k_closest(const SceneDev S
             } else {
                 if (COUNT) c_nodes++;
                 uint32_t k0, k1, k2 = 0xffffffffu, k3 = 0xffffffffu, f0, f1, f2 = REF_NONE, f3 = REF_NONE;
-                if (cur & CL_SUB) {  // four child boxes {lo.x, hi.x, lo.y, hi.y, lo.z, hi.z}; the four references in one 16-byte load
+                if (cur & CL_SUB) {  // a transposed node (cgrt_layout.h SubNode): lo.x, hi.x, lo.y, hi.y, lo.z, hi.z of the four children, then the references
                     const float4* q = reinterpret_cast<const float4*>(S.subnodes + (cur & ~CL_SUB));
-                    const float4 a0 = q[0], b0 = q[1], c0 = q[2];
-                    const uint4 m = *reinterpret_cast<const uint4*>(q + 3);
-                    const float4 a1 = q[4], b1 = q[5], c1 = q[6];
-                    const float l0 = box_lb2(a0.x, a0.y, a0.z, a0.w, b0.x, b0.y, px, py, pz);
-                    const float l1 = box_lb2(b0.z, b0.w, c0.x, c0.y, c0.z, c0.w, px, py, pz);
-                    const float l2 = box_lb2(a1.x, a1.y, a1.z, a1.w, b1.x, b1.y, px, py, pz);
-                    const float l3 = box_lb2(b1.z, b1.w, c1.x, c1.y, c1.z, c1.w, px, py, pz);
+                    const float4 lx = q[0], hx = q[1], ly = q[2], hy = q[3], lz = q[4], hz = q[5];
+                    const uint4 m = *reinterpret_cast<const uint4*>(q + 6);
+                    const float l0 = box_lb2(lx.x, hx.x, ly.x, hy.x, lz.x, hz.x, px, py, pz);
+                    const float l1 = box_lb2(lx.y, hx.y, ly.y, hy.y, lz.y, hz.y, px, py, pz);
+                    const float l2 = box_lb2(lx.z, hx.z, ly.z, hy.z, lz.z, hz.z, px, py, pz);
+                    const float l3 = box_lb2(lx.w, hx.w, ly.w, hy.w, lz.w, hz.w, px, py, pz);
                     k0 = child_key(m.x, l0, B.d2);
                     k1 = child_key(m.y, l1, B.d2);
                     k2 = child_key(m.z, l2, B.d2);

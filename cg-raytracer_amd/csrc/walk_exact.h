@@ -75,13 +75,33 @@ __device__ __forceinline__ F3 ld3(const float* p) { return f3(p[0], p[1], p[2]);
 // leaf instead.  DESIGN.md "In-leaf accelerator" has the full argument.
 typedef float f2v __attribute__((ext_vector_type(2)));  // one operand of the packed FP32 pipe (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32)
 struct RayPre {
-    F3 inv;
-    // per axis the addends of the {lower, upper} plane pair: -(o * inv + slack) for the plane the ray meets first,
-    // -(o * inv - slack) for the other one (which is which depends on the direction's sign)
-    f2v cx, cy, cz;
+    // Per axis 1 / clamped direction and the addends of the plane the ray meets first, -(o * inv + slack), and of the other one,
+    // -(o * inv - slack).  The node step multiplies FOUR children's planes of one kind by the same scalars on the packed FP32 pipe,
+    // which reads a scalar as either half of a 64-bit register pair (pk_fma_bcast); paired up, the nine scalars take nine registers
+    // where nine splat pairs would take eighteen:
+    //   ax = {inv.x, near.x}   ay = {inv.y, near.y}   az = {inv.z, near.z}   fxy = {far.x, far.y}   cfz = far.z
+    // (far.z has no partner: its four fma are scalar ones -- a fifth pair would cost the register that kernels at the
+    // three-waves-per-SIMD budget do not have)
+    f2v ax, ay, az, fxy;
+    float cfz;
+    // the signs of the clamped direction components: for axis a the four children's NEAR planes are in quarter 2a + s_a of a node
+    // (cgrt_layout.h SubNode) and the far ones in quarter 2a + 1 - s_a -- raypre_near_x/y/z give the near quarter's byte offset, the
+    // far one is at offset ^ 16.  Kept as flags (lane masks in scalar registers): three offsets would cost three vector registers
+    // in kernels that sit at the three-waves-per-SIMD budget.
     bool sx, sy, sz;
     bool regular;
 };
+__device__ __forceinline__ void raypre_set_signs(RayPre& P, const bool sx, const bool sy, const bool sz) {
+    P.sx = sx;
+    P.sy = sy;
+    P.sz = sz;
+}
+__device__ __forceinline__ uint32_t raypre_near_x(const RayPre& P) { return P.sx ? 16u : 0u; }
+__device__ __forceinline__ uint32_t raypre_near_y(const RayPre& P) { return P.sy ? 48u : 32u; }
+__device__ __forceinline__ uint32_t raypre_near_z(const RayPre& P) { return P.sz ? 80u : 64u; }
+// the three signs in one word, for a shuffle
+__device__ __forceinline__ uint32_t raypre_pack_signs(const RayPre& P) { return (P.sx ? 1u : 0u) | (P.sy ? 2u : 0u) | (P.sz ? 4u : 0u); }
+__device__ __forceinline__ void raypre_unpack_signs(RayPre& P, const uint32_t sg) { raypre_set_signs(P, (sg & 1u) != 0u, (sg & 2u) != 0u, (sg & 4u) != 0u); }
 
 __device__ __forceinline__ RayPre make_raypre(const SceneDev& S, const F3 o, const F3 d, const float t) {
     RayPre P;
@@ -97,40 +117,61 @@ __device__ __forceinline__ RayPre make_raypre(const SceneDev& S, const F3 o, con
     const float dx = fabsf(d.x) >= fl ? d.x : copysignf(fl, d.x);
     const float dy = fabsf(d.y) >= fl ? d.y : copysignf(fl, d.y);
     const float dz = fabsf(d.z) >= fl ? d.z : copysignf(fl, d.z);
-    P.inv = f3(1.0f / dx, 1.0f / dy, 1.0f / dz);
-    P.sx = dx < 0;
-    P.sy = dy < 0;
-    P.sz = dz < 0;
-    const F3 oi = f3(o.x * P.inv.x, o.y * P.inv.y, o.z * P.inv.z);
-    const F3 sl = f3(eps * fabsf(P.inv.x), eps * fabsf(P.inv.y), eps * fabsf(P.inv.z));
+    const F3 inv = f3(1.0f / dx, 1.0f / dy, 1.0f / dz);
+    raypre_set_signs(P, dx < 0, dy < 0, dz < 0);
+    const F3 oi = f3(o.x * inv.x, o.y * inv.y, o.z * inv.z);
+    const F3 sl = f3(eps * fabsf(inv.x), eps * fabsf(inv.y), eps * fabsf(inv.z));
     const F3 oin = f3(oi.x + sl.x, oi.y + sl.y, oi.z + sl.z), oif = f3(oi.x - sl.x, oi.y - sl.y, oi.z - sl.z);
-    P.cx = P.sx ? (f2v){-oif.x, -oin.x} : (f2v){-oin.x, -oif.x};
-    P.cy = P.sy ? (f2v){-oif.y, -oin.y} : (f2v){-oin.y, -oif.y};
-    P.cz = P.sz ? (f2v){-oif.z, -oin.z} : (f2v){-oin.z, -oif.z};
+    P.ax = (f2v){inv.x, -oin.x};
+    P.ay = (f2v){inv.y, -oin.y};
+    P.az = (f2v){inv.z, -oin.z};
+    P.fxy = (f2v){-oif.x, -oif.y};
+    P.cfz = -oif.z;
     return P;
 }
 
-// Conservative [tn, tf] of the widened box whose planes come as per-axis {lower, upper} pairs (SubNode's layout): one
-// packed fma per axis, then the entry / exit plane picked by the direction's sign.  Explicit fma: this is NOT reference
-// arithmetic.
-__device__ __forceinline__ void slab_cons(const RayPre& P, const f2v bx, const f2v by, const f2v bz, float& tn, float& tf) {
-    const f2v tx = __builtin_elementwise_fma(bx, (f2v){P.inv.x, P.inv.x}, P.cx);
-    const f2v ty = __builtin_elementwise_fma(by, (f2v){P.inv.y, P.inv.y}, P.cy);
-    const f2v tz = __builtin_elementwise_fma(bz, (f2v){P.inv.z, P.inv.z}, P.cz);
-    const float nx = P.sx ? tx.y : tx.x, fx = P.sx ? tx.x : tx.y;
-    const float ny = P.sy ? ty.y : ty.x, fy = P.sy ? ty.x : ty.y;
-    const float nz = P.sz ? tz.y : tz.x, fz = P.sz ? tz.x : tz.y;
-    tn = fmaxf(fmaxf(nx, ny), nz);
-    tf = fminf(fminf(fx, fy), fz);
+// {b.x * s + c, b.y * s + c} in ONE packed fma: s = the low half of the pair ps, c = half H of the pair pc (VOP3P op_sel picks the
+// half a result's low lane reads, op_sel_hi the half its high lane reads; the plane operand b keeps the default, lane for lane).
+// Each lane is the IEEE fma v_fma_f32 computes.  Written as an instruction: the compiler does not fold a splat into op_sel, it
+// builds the splat in a register pair of its own.
+template <int H>
+__device__ __forceinline__ f2v pk_fma_bcast(const f2v b, const f2v ps, const f2v pc) {
+    f2v r;
+    if (H == 0)
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(b), "v"(ps), "v"(pc));
+    else
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(b), "v"(ps), "v"(pc));
+    return r;
 }
-// the four children of a 128-byte node held in six 16-byte quarters (cgrt_layout.h SubNode: per child x, y, z pairs)
-__device__ __forceinline__ void slab_cons4(const RayPre& P, const float4 a0, const float4 b0, const float4 c0, const float4 a1, const float4 b1,
-                                           const float4 c1, float& tn0, float& tf0, float& tn1, float& tf1, float& tn2, float& tf2, float& tn3,
+// Conservative [tn, tf] of ONE child's widened box from its near and far plane per axis (already picked by address).  Explicit
+// fma: this is NOT reference arithmetic.
+__device__ __forceinline__ void slab_cons(const RayPre& P, const float nx, const float fx, const float ny, const float fy, const float nz,
+                                          const float fz, float& tn, float& tf) {
+    tn = fmaxf(fmaxf(__builtin_fmaf(nx, P.ax.x, P.ax.y), __builtin_fmaf(ny, P.ay.x, P.ay.y)), __builtin_fmaf(nz, P.az.x, P.az.y));
+    tf = fminf(fminf(__builtin_fmaf(fx, P.ax.x, P.fxy.x), __builtin_fmaf(fy, P.ay.x, P.fxy.y)), __builtin_fmaf(fz, P.az.x, P.cfz));
+}
+// The four children of a 128-byte node from its six plane quarters, near and far per axis (cgrt_layout.h SubNode; which quarter
+// is which was decided in the load address): 10 packed fma -- two children per issue -- and 4 scalar ones (RayPre::cfz), then a max3 and a min3 per child.  No
+// selects.  The same fma on the same operands as slab_cons, child for child.
+__device__ __forceinline__ void slab_cons4(const RayPre& P, const float4 nx, const float4 fx, const float4 ny, const float4 fy, const float4 nz,
+                                           const float4 fz, float& tn0, float& tf0, float& tn1, float& tf1, float& tn2, float& tf2, float& tn3,
                                            float& tf3) {
-    slab_cons(P, (f2v){a0.x, a0.y}, (f2v){a0.z, a0.w}, (f2v){b0.x, b0.y}, tn0, tf0);
-    slab_cons(P, (f2v){b0.z, b0.w}, (f2v){c0.x, c0.y}, (f2v){c0.z, c0.w}, tn1, tf1);
-    slab_cons(P, (f2v){a1.x, a1.y}, (f2v){a1.z, a1.w}, (f2v){b1.x, b1.y}, tn2, tf2);
-    slab_cons(P, (f2v){b1.z, b1.w}, (f2v){c1.x, c1.y}, (f2v){c1.z, c1.w}, tn3, tf3);
+    const f2v nx01 = pk_fma_bcast<1>((f2v){nx.x, nx.y}, P.ax, P.ax), nx23 = pk_fma_bcast<1>((f2v){nx.z, nx.w}, P.ax, P.ax);
+    const f2v fx01 = pk_fma_bcast<0>((f2v){fx.x, fx.y}, P.ax, P.fxy), fx23 = pk_fma_bcast<0>((f2v){fx.z, fx.w}, P.ax, P.fxy);
+    const f2v ny01 = pk_fma_bcast<1>((f2v){ny.x, ny.y}, P.ay, P.ay), ny23 = pk_fma_bcast<1>((f2v){ny.z, ny.w}, P.ay, P.ay);
+    const f2v fy01 = pk_fma_bcast<1>((f2v){fy.x, fy.y}, P.ay, P.fxy), fy23 = pk_fma_bcast<1>((f2v){fy.z, fy.w}, P.ay, P.fxy);
+    const f2v nz01 = pk_fma_bcast<1>((f2v){nz.x, nz.y}, P.az, P.az), nz23 = pk_fma_bcast<1>((f2v){nz.z, nz.w}, P.az, P.az);
+    const float fz0 = __builtin_fmaf(fz.x, P.az.x, P.cfz), fz1 = __builtin_fmaf(fz.y, P.az.x, P.cfz);
+    const float fz2 = __builtin_fmaf(fz.z, P.az.x, P.cfz), fz3 = __builtin_fmaf(fz.w, P.az.x, P.cfz);
+    tn0 = fmaxf(fmaxf(nx01.x, ny01.x), nz01.x), tf0 = fminf(fminf(fx01.x, fy01.x), fz0);
+    tn1 = fmaxf(fmaxf(nx01.y, ny01.y), nz01.y), tf1 = fminf(fminf(fx01.y, fy01.y), fz1);
+    tn2 = fmaxf(fmaxf(nx23.x, ny23.x), nz23.x), tf2 = fminf(fminf(fx23.x, fy23.x), fz2);
+    tn3 = fmaxf(fmaxf(nx23.y, ny23.y), nz23.y), tf3 = fminf(fminf(fx23.y, fy23.y), fz3);
+}
+// A 16-byte quarter of the record array at a 32-bit byte offset: the uniform base stays in scalar registers, the lane supplies
+// the offset alone (every record lies below 2^32 bytes: cgrt_layout.h SUB_MAX_RECORDS).
+__device__ __forceinline__ float4 ld_quarter(const SceneDev& S, const uint32_t byte_off) {
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(S.subnodes) + byte_off);
 }
 
 // State of one reference leaf's scan, order-free form (see bvh_builder.cpp "In-leaf accelerator"):
@@ -328,12 +369,19 @@ __device__ __forceinline__ void sub_node_step(const SceneDev& S, const RayPre& P
             cnt.sub++;
             if (first_active_lane()) cnt.w_sub++;
         }
-        const float4* q = reinterpret_cast<const float4*>(S.subnodes + cur);
-        const float4 a0 = q[0], b0 = q[1], c0 = q[2];
-        const uint4 m = *reinterpret_cast<const uint4*>(q + 3);  // the four child references (cgrt_layout.h SubNode)
-        const float4 a1 = q[4], b1 = q[5], c1 = q[6];
+        // near and far plane quarters per axis, picked by the ray's signs in the address (raypre_near_x/y/z); quarter 6: the references
+        const uint32_t b = cur << 6;
+        const uint32_t ox = b + raypre_near_x(P), oy = b + raypre_near_y(P), oz = b + raypre_near_z(P);
+        const float4 qnx = ld_quarter(S, ox), qfx = ld_quarter(S, ox ^ 16u);
+        const float4 qny = ld_quarter(S, oy), qfy = ld_quarter(S, oy ^ 16u);
+        const float4 qnz = ld_quarter(S, oz), qfz = ld_quarter(S, oz ^ 16u);
+        const float4 mr = ld_quarter(S, b + 4u * SUB_REF_WORD);
+        const uint4 m = make_uint4(__float_as_uint(mr.x), __float_as_uint(mr.y), __float_as_uint(mr.z), __float_as_uint(mr.w));
+        // all seven loads are in flight before the first fma waits for one: ONE round trip to memory per step (left alone, the
+        // scheduler issues the last loads after the wait for the first ones)
+        __builtin_amdgcn_sched_barrier(0);
         float tn0, tf0, tn1, tf1, tn2, tf2, tn3, tf3;
-        slab_cons4(P, a0, b0, c0, a1, b1, c1, tn0, tf0, tn1, tf1, tn2, tf2, tn3, tf3);
+        slab_cons4(P, qnx, qfx, qny, qfy, qnz, qfz, tn0, tf0, tn1, tf1, tn2, tf2, tn3, tf3);
         // Bound for culling: the running minimum, but never below 0 -- an origin-on-plane acceptance
         // ignores ray.t altogether (ray_tracing.cpp:43-47) and its box contains the origin (tn < 0).
         const float tc = fmaxf(best_t, 0.0f);
@@ -589,7 +637,7 @@ __device__ __forceinline__ bool topo_pop(const float t, uint32_t& cur, int& sp, 
 
 // LeafRec of a leaf reference in either encoding (cgrt_layout.h REF_LEAF_ACCEL).
 __device__ __forceinline__ LeafRec leaf_rec_of(const SceneDev& S, const uint32_t ref) {
-    const uint32_t li = (ref & REF_LEAF_ACCEL) ? S.subnodes[(ref & REF_INDEX26) + 1u].pad[0] : (ref & ~REF_LEAF);
+    const uint32_t li = (ref & REF_LEAF_ACCEL) ? S.subnodes[(ref & REF_INDEX26) + (SUB_LEAF_WORD >> 4)].w[SUB_LEAF_WORD & 15u] : (ref & ~REF_LEAF);
     return S.leaves[li];
 }
 // "One loop" form of the same walk: an iteration offers every lane, in this order, two topology steps (pops included),

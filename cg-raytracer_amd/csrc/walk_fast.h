@@ -183,14 +183,12 @@ __device__ __forceinline__ void quad_tail(const SceneDev& S, const unsigned long
     const int src = valid ? (int)s_map[Q] : lane;
     // the owner's ray, broadcast to its quad (all 64 lanes take part in the shuffles)
     RayPre P;
-    P.inv = f3(__shfl(W.P.inv.x, src, 64), __shfl(W.P.inv.y, src, 64), __shfl(W.P.inv.z, src, 64));
-    P.cx = (f2v){__shfl(W.P.cx.x, src, 64), __shfl(W.P.cx.y, src, 64)};
-    P.cy = (f2v){__shfl(W.P.cy.x, src, 64), __shfl(W.P.cy.y, src, 64)};
-    P.cz = (f2v){__shfl(W.P.cz.x, src, 64), __shfl(W.P.cz.y, src, 64)};
-    const int sg = __shfl((int)((W.P.sx ? 1 : 0) | (W.P.sy ? 2 : 0) | (W.P.sz ? 4 : 0)), src, 64);
-    P.sx = (sg & 1) != 0;
-    P.sy = (sg & 2) != 0;
-    P.sz = (sg & 4) != 0;
+    P.ax = (f2v){__shfl(W.P.ax.x, src, 64), __shfl(W.P.ax.y, src, 64)};
+    P.ay = (f2v){__shfl(W.P.ay.x, src, 64), __shfl(W.P.ay.y, src, 64)};
+    P.az = (f2v){__shfl(W.P.az.x, src, 64), __shfl(W.P.az.y, src, 64)};
+    P.fxy = (f2v){__shfl(W.P.fxy.x, src, 64), __shfl(W.P.fxy.y, src, 64)};
+    P.cfz = __shfl(W.P.cfz, src, 64);
+    raypre_unpack_signs(P, (uint32_t)__shfl((int)raypre_pack_signs(W.P), src, 64));
     P.regular = true;
     const F3 o = f3(__shfl(W.o.x, src, 64), __shfl(W.o.y, src, 64), __shfl(W.o.z, src, 64));
     const F3 d = f3(__shfl(W.d.x, src, 64), __shfl(W.d.y, src, 64), __shfl(W.d.z, src, 64));
@@ -238,9 +236,15 @@ __device__ __forceinline__ void quad_tail(const SceneDev& S, const unsigned long
                 cnt.sub++;
                 if (first_active_lane()) cnt.w_sub++;
             }
-            const uint4 m = make_uint4(__float_as_uint(u3.x), __float_as_uint(u3.y), __float_as_uint(u3.z), __float_as_uint(u3.w));
+            const uint4 m = make_uint4(__float_as_uint(u6.x), __float_as_uint(u6.y), __float_as_uint(u6.z), __float_as_uint(u6.w));
             float tn0, tf0, tn1, tf1, tn2, tf2, tn3, tf3;
-            slab_cons4(P, u0, u1, u2, u4, u5, u6, tn0, tf0, tn1, tf1, tn2, tf2, tn3, tf3);
+            // (the load phase is shared with the runs and reads the quarters in stored order -- one address, eight immediates: picking
+            // the near ones by address here costs the register that puts the frame kernels over three waves per SIMD -- so this
+            // step picks them by the ray's signs after the load, as every step did before the nodes were transposed)
+            const float4 qnx = P.sx ? u1 : u0, qfx = P.sx ? u0 : u1;
+            const float4 qny = P.sy ? u3 : u2, qfy = P.sy ? u2 : u3;
+            const float4 qnz = P.sz ? u5 : u4, qfz = P.sz ? u4 : u5;
+            slab_cons4(P, qnx, qfx, qny, qfy, qnz, qfz, tn0, tf0, tn1, tf1, tn2, tf2, tn3, tf3);
             const float tc = fmaxf(G.best_t, 0.0f);
             float k0 = ((tn0 <= tf0) && (tf0 >= 0.0f) && (tn0 <= tc)) ? tn0 : inf;
             float k1 = ((tn1 <= tf1) && (tf1 >= 0.0f) && (tn1 <= tc)) ? tn1 : inf;

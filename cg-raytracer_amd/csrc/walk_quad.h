@@ -8,7 +8,7 @@
 // four cycles however few lanes are live).  Here a ray owns a quad: lane k of the quad tests child box k of the node (3
 // packed fma + min/max instead of 12), the four children are ranked with three quad-permute compares, the survivors go on the
 // ray's LDS stack with one write per lane, and a run's triangles are tested one per lane.  A node step is ~45 instructions
-// per wave, 4 load instructions of 8 bytes per lane on ONE 128-byte line per quad (instead of seven 16-byte loads on 64
+// per wave, 7 load instructions of 4 bytes per lane on ONE 128-byte line per quad (instead of seven 16-byte loads on 64
 // lines per wave), and a wave carries 16 rays instead of 64, so the hard rays of a tile no longer wait for each other's
 // bodies.  The price is throughput -- per-ray set-up (ray generation, root gate, per-ray constants, certificate, normal) is
 // evaluated by all four lanes -- which is why large launches keep the lane-per-ray shape.
@@ -35,6 +35,21 @@ static_assert(16 * CGRT_QSLOTS <= 64 * CGRT_STACK_SLOTS, "the quad stacks must f
 #define CGRT_QUAD_WIDE_RAYS 4  // a wave with at most this many live rays gives each a row of 16 lanes (0: never)
 #endif
 
+// Child q of the node `node` for the ray of this quad: its six planes sit at words q, 4 + q, .. 20 + q of the transposed node
+// (cgrt_layout.h SubNode), the near one of an axis in the quarter the ray's sign names (raypre_near_x/y/z) and the far one in
+// the quarter beside it, its reference at word 24 + q.  Returns the reference; [tn, tf] as slab_cons.
+__device__ __forceinline__ uint32_t quad_child_slab(const SceneDev& S, const RayPre& P, const uint32_t node, const int q, float& tn, float& tf) {
+    const char* base = reinterpret_cast<const char*>(S.subnodes);
+    const uint32_t b = (node << 6) + 4u * (uint32_t)q;
+    const uint32_t ox = b + raypre_near_x(P), oy = b + raypre_near_y(P), oz = b + raypre_near_z(P);
+    const float nx = *reinterpret_cast<const float*>(base + ox), fx = *reinterpret_cast<const float*>(base + (ox ^ 16u));
+    const float ny = *reinterpret_cast<const float*>(base + oy), fy = *reinterpret_cast<const float*>(base + (oy ^ 16u));
+    const float nz = *reinterpret_cast<const float*>(base + oz), fz = *reinterpret_cast<const float*>(base + (oz ^ 16u));
+    const uint32_t ref = *reinterpret_cast<const uint32_t*>(base + (b + 4u * SUB_REF_WORD));
+    slab_cons(P, nx, fx, ny, fy, nz, fz, tn, tf);
+    return ref;
+}
+
 // One node step for the ray of this quad: lane q tests child box q.  On return (quad-uniform) cur = the nearest hit child or
 // REF_NONE, the other hit children are on the stack, nearest on top.
 template <bool COUNT>
@@ -44,13 +59,8 @@ __device__ __forceinline__ void quad_node_step(const SceneDev& S, const RayPre& 
         cnt.sub++;
         if (first_active_lane()) cnt.w_sub++;
     }
-    const uint32_t* base = reinterpret_cast<const uint32_t*>(S.subnodes + cur);
-    // child q's box: words 0..5 / 6..11 of the node's first half, 16..21 / 22..27 of its second (cgrt_layout.h SubNode), 8-byte aligned
-    const float2* b = reinterpret_cast<const float2*>(base + ((q & 1) * 6 + (q >> 1) * 16));
-    const float2 bx = b[0], by = b[1], bz = b[2];
-    const uint32_t ref = base[12 + q];  // the four child references sit in words 12..15 of the first half
     float tn, tf;
-    slab_cons(P, (f2v){bx.x, bx.y}, (f2v){by.x, by.y}, (f2v){bz.x, bz.y}, tn, tf);
+    const uint32_t ref = quad_child_slab(S, P, cur, q, tn, tf);
     const float inf = __builtin_inff();
     const float tc = fmaxf(best_t, 0.0f);  // never below 0: an origin-on-plane acceptance ignores ray.t (walk_exact.h sub_node_step)
     const bool hit = (tn <= tf) && (tf >= 0.0f) && (tn <= tc) && (tn < inf);
@@ -132,14 +142,12 @@ __device__ __forceinline__ void quad_wide_tail(const SceneDev& S, const unsigned
     const bool valid = row < nlive;
     if (valid) src = __ffsll((long long)m) - 1;
     RayPre P;
-    P.inv = f3(shfl_f(W.P.inv.x, src), shfl_f(W.P.inv.y, src), shfl_f(W.P.inv.z, src));
-    P.cx = (f2v){shfl_f(W.P.cx.x, src), shfl_f(W.P.cx.y, src)};
-    P.cy = (f2v){shfl_f(W.P.cy.x, src), shfl_f(W.P.cy.y, src)};
-    P.cz = (f2v){shfl_f(W.P.cz.x, src), shfl_f(W.P.cz.y, src)};
-    const int sg = __shfl((int)((W.P.sx ? 1 : 0) | (W.P.sy ? 2 : 0) | (W.P.sz ? 4 : 0)), src, 64);
-    P.sx = (sg & 1) != 0;
-    P.sy = (sg & 2) != 0;
-    P.sz = (sg & 4) != 0;
+    P.ax = (f2v){shfl_f(W.P.ax.x, src), shfl_f(W.P.ax.y, src)};
+    P.ay = (f2v){shfl_f(W.P.ay.x, src), shfl_f(W.P.ay.y, src)};
+    P.az = (f2v){shfl_f(W.P.az.x, src), shfl_f(W.P.az.y, src)};
+    P.fxy = (f2v){shfl_f(W.P.fxy.x, src), shfl_f(W.P.fxy.y, src)};
+    P.cfz = shfl_f(W.P.cfz, src);
+    raypre_unpack_signs(P, (uint32_t)__shfl((int)raypre_pack_signs(W.P), src, 64));
     P.regular = true;
     const F3 o = f3(shfl_f(W.o.x, src), shfl_f(W.o.y, src), shfl_f(W.o.z, src));
     const F3 d = f3(shfl_f(W.d.x, src), shfl_f(W.d.y, src), shfl_f(W.d.z, src));
@@ -176,12 +184,8 @@ __device__ __forceinline__ void quad_wide_tail(const SceneDev& S, const unsigned
                 cnt.sub++;
                 if (first_active_lane()) cnt.w_sub++;
             }
-            const uint32_t* base = reinterpret_cast<const uint32_t*>(S.subnodes + ref);
-            const float2* b = reinterpret_cast<const float2*>(base + ((q & 1) * 6 + (q >> 1) * 16));
-            const float2 bx = b[0], by = b[1], bz = b[2];
-            cref = base[12 + q];
             float tn, tf;
-            slab_cons(P, (f2v){bx.x, bx.y}, (f2v){by.x, by.y}, (f2v){bz.x, bz.y}, tn, tf);
+            cref = quad_child_slab(S, P, ref, q, tn, tf);
             const float inf = __builtin_inff();
             const float tc = fmaxf(G.best_t, 0.0f);
             hit = (tn <= tf) && (tf >= 0.0f) && (tn <= tc) && (tn < inf);

@@ -857,6 +857,16 @@ int cgrt_debug_check_layout(CgrtScene* scene);
  * number of builder threads (cgrt_set_build_threads: 0 = hardware concurrency, at most 16 are used; process-wide, for scenes
  * created afterwards).  Works on host-only scenes. */
 int cgrt_debug_layout_hash(const CgrtScene* scene, uint64_t* out);
+/* Diagnostic: the 4-wide nodes of the in-leaf accelerators and of the fast tree as the device reads them (128 bytes
+ * = 32 words each, transposed quarters).  cgrt_debug_node_pack writes four child boxes (boxes[6 * c ..] = lower.xyz, upper.xyz of
+ * child c), four child references and an accelerator root's leaf index into the 32 words of one node through the builder's own
+ * store helpers; cgrt_debug_node_unpack reads them back through the matching load helpers.  cgrt_debug_get_subnodes copies the
+ * scene's node array (16 words per 64-byte half, cgrt_num_subnodes halves; `words` may be NULL), the record index of its first half,
+ * the fast tree's root reference (0xffffffff: none) and, per reference leaf, the record index of its accelerator's root node
+ * (0xffffffff: the leaf has none; `leaf_roots` may be NULL, else cgrt_num_nodes entries are enough).  Works on host-only scenes. */
+void cgrt_debug_node_pack(const float* boxes, const uint32_t* refs, uint32_t leaf_index, uint32_t* words);
+void cgrt_debug_node_unpack(const uint32_t* words, float* boxes, uint32_t* refs, uint32_t* leaf_index);
+int cgrt_debug_get_subnodes(const CgrtScene* scene, uint32_t* words, uint32_t* sub_base, uint32_t* fast_root, uint32_t* leaf_roots, uint32_t* nleaves);
 int cgrt_set_build_threads(int threads);
 /* Bytes of one inner-node record / one triangle record / one in-leaf accelerator node / one result. */
 void cgrt_record_sizes(uint32_t* node_bytes, uint32_t* tri_bytes, uint32_t* sub_bytes, uint32_t* hit_bytes);
