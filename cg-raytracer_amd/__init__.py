@@ -32,6 +32,13 @@ assert RAY_DTYPE.itemsize == 28 and HIT_DTYPE.itemsize == 16
 # include/cgrt.h CgrtClosest: one closest-point answer (32 bytes); bary = {u, v, w}, the weights of the triangle's three vertices
 CLOSEST_DTYPE = np.dtype([("point", np.float32, 3), ("dist2", np.float32), ("prim_id", np.uint32), ("bary", np.float32, 3)])
 assert CLOSEST_DTYPE.itemsize == 32
+# include/cgrt.h CgrtCrossing: one surface crossing of a ray (8 bytes); an unused entry of a slot is {+inf, NO_PRIM}
+CROSSING_DTYPE = np.dtype([("t", np.float32), ("prim_id", np.uint32)])
+assert CROSSING_DTYPE.itemsize == 8
+# Scene.inside_tensor's default directions: three fixed generic ones (no component zero, none along an axis, a face diagonal or a space
+# diagonal, pairwise far from parallel), so that a ray through an edge or a vertex of an axis-aligned or diagonal-symmetric mesh is the
+# exception in at most one of them
+INSIDE_DIRECTIONS = ((0.5310871, 0.2178203, 0.8188417), (-0.3319057, 0.9047763, -0.2670293), (0.6834621, -0.5712349, -0.4544671))
 
 
 class CgrtError(RuntimeError):
@@ -233,7 +240,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -352,6 +359,12 @@ def lib() -> C.CDLL:
     L.cgrt_closest_points_brute.argtypes = [vp, vp, u64, C.c_float, vp]
     L.cgrt_closest_points_device.argtypes = [vp, vp, u64, C.c_float, vp, vp]
     L.cgrt_debug_closest_work.argtypes = [vp, vp, u64, C.c_float, vp]
+    L.cgrt_count_crossings.argtypes = [vp, vp, u64, vp]
+    L.cgrt_count_crossings_device.argtypes = [vp, vp, u64, vp, vp]
+    L.cgrt_list_crossings.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp]
+    L.cgrt_list_crossings_brute.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp]
+    L.cgrt_list_crossings_device.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp]
+    L.cgrt_debug_crossing_work.argtypes = [vp, vp, u64, vp]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
     L.cgrt_count_batch.argtypes = [vp, vp, u64, C.POINTER(Counters)]
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
@@ -1804,6 +1817,188 @@ class Scene:
         w = np.zeros(2, np.uint64)
         _check(lib().cgrt_debug_closest_work(self._h, _ptr(p), len(p), float(max_dist2), _ptr(w)))
         return int(w[0]), int(w[1])
+
+    # ---- crossing queries (include/cgrt.h cgrt_count_crossings*, cgrt_list_crossings*) ----
+    def count_crossings(self, rays) -> np.ndarray:
+        """cgrt_count_crossings: for every ray (RAY_DTYPE or (n, 7) float32, taken as given: t bounds it) the number of triangles it
+        passes through -- the triangles the reference's intersectRayWithTriangle accepts on a fresh copy of the ray.  (n,) uint32."""
+        r = _as_ray_array(rays)
+        counts = np.zeros(len(r), np.uint32)
+        _check(lib().cgrt_count_crossings(self._h, _ptr(r), len(r), _ptr(counts)))
+        return counts
+
+    def _list_host(self, f, r, offsets, k: int, want_counts: bool = True):
+        m = int(offsets[-1]) if offsets is not None else len(r) * k
+        out = np.zeros(m, CROSSING_DTYPE)
+        counts = np.zeros(len(r), np.uint32) if want_counts else None
+        _check(f(self._h, _ptr(r), len(r), _ptr(offsets), int(k), _ptr(out), m, _ptr(counts)))
+        return out, counts
+
+    def list_crossings(self, rays, offsets=None, want_counts: bool = True):
+        """Every crossing of every ray, in order (by t, equal t by prim_id): cgrt_count_crossings, the exclusive prefix sums, then
+        cgrt_list_crossings.  Returns (offsets, records): offsets (n + 1,) int64, ray i's crossings are records[offsets[i]:offsets[i + 1]]
+        (CROSSING_DTYPE {t, prim_id}).
+        With offsets ((n + 1,) slot boundaries chosen by the caller) one cgrt_list_crossings call: ray i receives its first crossings in
+        order in records [offsets[i], offsets[i + 1]), {+inf, NO_PRIM} in what remains.  Returns (records (offsets[-1],), counts: the full
+        numbers of crossings -- or None with want_counts=False, which lets the search of a ray stop at the largest t its full slot keeps)."""
+        r = _as_ray_array(rays)
+        if offsets is not None:
+            return self._list_host(lib().cgrt_list_crossings, r, np.ascontiguousarray(offsets, np.uint64), 0, want_counts)
+        offsets = np.zeros(len(r) + 1, np.uint64)
+        np.cumsum(self.count_crossings(r), dtype=np.uint64, out=offsets[1:])
+        out, _ = self._list_host(lib().cgrt_list_crossings, r, offsets, 0, want_counts=False)
+        return offsets.astype(np.int64), out
+
+    def list_crossings_brute(self, rays, offsets=None, k: int = 0):
+        """cgrt_list_crossings_brute: the list by testing every triangle in turn (validation; the same bytes).  With neither offsets nor
+        k the full list, as list_crossings returns it: (offsets, records); with offsets ((n + 1,) slot boundaries) or k (k records per
+        ray): (records, counts)."""
+        r = _as_ray_array(rays)
+        if offsets is None and not k:
+            c = np.zeros(len(r), np.uint32)  # k = 1 only to obtain the counts
+            one = np.zeros(len(r), CROSSING_DTYPE)
+            _check(lib().cgrt_list_crossings_brute(self._h, _ptr(r), len(r), None, 1, _ptr(one), len(r), _ptr(c)))
+            off = np.zeros(len(r) + 1, np.uint64)
+            np.cumsum(c, dtype=np.uint64, out=off[1:])
+            out, _ = self._list_host(lib().cgrt_list_crossings_brute, r, off, 0, want_counts=False)
+            return off.astype(np.int64), out
+        off = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
+        out, counts = self._list_host(lib().cgrt_list_crossings_brute, r, off, k)
+        return (out.reshape(len(r), k) if off is None else out), counts
+
+    def first_crossings(self, rays, k: int, want_counts: bool = True):
+        """The first k crossings of every ray: ((n, k) CROSSING_DTYPE records, unused entries {+inf, NO_PRIM}; (n,) uint32 counts -- the
+        full numbers of crossings; None with want_counts=False, as list_crossings with offsets)."""
+        r = _as_ray_array(rays)
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        out, counts = self._list_host(lib().cgrt_list_crossings, r, None, k, want_counts)
+        return out.reshape(len(r), k), counts
+
+    def debug_crossing_work(self, rays):
+        """cgrt_debug_crossing_work: (node steps, triangles evaluated) of count_crossings' search, summed over the rays (a separate
+        counting launch)."""
+        r = _as_ray_array(rays)
+        w = np.zeros(2, np.uint64)
+        _check(lib().cgrt_debug_crossing_work(self._h, _ptr(r), len(r), _ptr(w)))
+        return int(w[0]), int(w[1])
+
+    def count_crossings_device(self, d_rays_ptr: int, n: int, d_counts_ptr: int, stream: int = 0) -> None:
+        """cgrt_count_crossings_device: n rays (28 bytes each) at d_rays_ptr -> n uint32 counts at d_counts_ptr, enqueued on the
+        hipStream_t `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        _check(lib().cgrt_count_crossings_device(self._h, vp(d_rays_ptr), int(n), vp(d_counts_ptr), vp(stream)))
+
+    def list_crossings_device(self, d_rays_ptr: int, n: int, d_out_ptr: int, capacity: int, d_offsets_ptr: int = 0, k: int = 0,
+                              d_counts_ptr: int = 0, stream: int = 0) -> None:
+        """cgrt_list_crossings_device: slots from the n + 1 uint64 offsets at d_offsets_ptr, or of k records each; `capacity` records of
+        8 bytes at d_out_ptr, nothing beyond them is written whatever the offsets hold; d_counts_ptr (optional) receives the full counts.
+        Enqueued on `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        _check(lib().cgrt_list_crossings_device(self._h, vp(d_rays_ptr), int(n), vp(d_offsets_ptr), int(k), vp(d_out_ptr), int(capacity),
+                                                vp(d_counts_ptr), vp(stream)))
+
+    def first_crossings_device(self, d_rays_ptr: int, n: int, k: int, d_out_ptr: int, d_counts_ptr: int = 0, stream: int = 0) -> None:
+        """list_crossings_device with k records per ray: n * k records at d_out_ptr."""
+        self.list_crossings_device(d_rays_ptr, n, d_out_ptr, int(n) * int(k), k=k, d_counts_ptr=d_counts_ptr, stream=stream)
+
+    def _crossing_rays_tensor(self, rays):
+        import torch
+
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 7:
+            raise ValueError("rays must be a torch tensor of shape (n, 7)")
+        self._device_tensor(rays, "rays", (torch.float32,))
+        return rays.shape[0]
+
+    def count_crossings_tensor(self, rays, out=None, stream=None):
+        """count_crossings on torch tensors: rays (n, 7) float32 on cuda:<device> -> (n,) torch.int32, into `out` or a new tensor,
+        enqueued on `stream` (default: torch.cuda.current_stream())."""
+        import torch
+
+        n = self._crossing_rays_tensor(rays)
+        if out is not None:
+            self._device_tensor(out, "out", (torch.int32,), (n,))
+        return self._tensor_call(out, (n,), torch.int32, stream, lambda o, s: self.count_crossings_device(rays.data_ptr(), n, o.data_ptr(), stream=s))
+
+    def list_crossings_tensor(self, rays, stream=None):
+        """list_crossings on torch tensors: rays (n, 7) float32 on cuda:<device> -> (offsets (n + 1,) torch.int64, records (m, 2) float32
+        with the prim_id BITS in column 1: records.view(torch.int32)[:, 1]).  Count, a torch cumsum and the list are enqueued on `stream`;
+        the total m is read back in between (one synchronisation of that stream)."""
+        import torch
+
+        n = self._crossing_rays_tensor(rays)
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        counts = self.count_crossings_tensor(rays, stream=stream)
+        with torch.cuda.stream(stream):
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+            m = int(offsets[-1].item())
+            records = torch.empty((m, 2), dtype=torch.float32, device=dev)
+        if n and m:
+            self.list_crossings_device(rays.data_ptr(), n, records.data_ptr(), m, d_offsets_ptr=offsets.data_ptr(), stream=stream.cuda_stream)
+        return offsets, records
+
+    def first_crossings_tensor(self, rays, k: int, out=None, stream=None):
+        """first_crossings on torch tensors: rays (n, 7) float32 on cuda:<device> -> (records (n, k, 2) float32 -- `out`, or a new tensor;
+        the prim_id bits in [..., 1], unused entries {+inf, NO_PRIM} --, counts (n,) torch.int32: the full numbers of crossings)."""
+        import torch
+
+        n = self._crossing_rays_tensor(rays)
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        if out is not None:
+            self._device_tensor(out, "out", (torch.float32,), (n, k, 2))
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(stream):
+            counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        rec = self._tensor_call(out, (n, k, 2), torch.float32, stream,
+                                lambda o, s: self.first_crossings_device(rays.data_ptr(), n, k, o.data_ptr(), d_counts_ptr=counts.data_ptr(), stream=s))
+        return rec, counts
+
+    def inside_tensor(self, points, directions=None, stream=None):
+        """Inside / outside for points (n, 3) float32 on cuda:<device>, meaningful for WATERTIGHT meshes: the majority vote, over an odd
+        number of fixed directions (default: the three of INSIDE_DIRECTIONS), of the parity of count_crossings along the unbounded ray from
+        the point.  One ray's parity fails where the ray passes exactly through a shared edge or a vertex (both triangles are crossed);
+        the vote absorbs one such failure in three.  A composition in Python: no kernel of its own.  Returns (n,) torch.bool."""
+        import torch
+
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be a torch tensor of shape (n, 3)")
+        self._device_tensor(points, "points", (torch.float32,))
+        dirs = np.asarray(INSIDE_DIRECTIONS if directions is None else directions, np.float32).reshape(-1, 3)
+        if len(dirs) % 2 == 0:
+            raise ValueError("an odd number of directions is needed for a majority")
+        n = points.shape[0]
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(stream):
+            votes = torch.zeros((n,), dtype=torch.int32, device=dev)
+            for d in dirs:
+                rays = torch.empty((n, 7), dtype=torch.float32, device=dev)
+                rays[:, 0:3] = points
+                rays[:, 3:6] = torch.tensor(d, dtype=torch.float32, device=dev)
+                rays[:, 6] = float("inf")
+                votes += self.count_crossings_tensor(rays, stream=stream) & 1
+            return votes > len(dirs) // 2
+
+    def signed_distance_tensor(self, points, stream=None):
+        """Signed distance for points (n, 3) float32 on cuda:<device>, meaningful for watertight meshes: sqrt(closest_points' dist2),
+        negated where inside_tensor says inside.  A composition in Python.  Returns (n,) float32."""
+        import torch
+
+        inside = self.inside_tensor(points, stream=stream)
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        d2 = self.closest_points_tensor(points, stream=stream)["dist2"]
+        with torch.cuda.stream(stream):
+            dist = torch.sqrt(d2)
+            return torch.where(inside, -dist, dist)
 
     def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream):
         import torch

@@ -30,6 +30,7 @@
 #include "cgrt_layout.h"
 #include "cgrt_math.h"
 #include "closest_kernels.h"
+#include "crossing_kernels.h"
 #include "surface_kernels.h"
 #include "trace_kernels.h"
 
@@ -3979,6 +3980,140 @@ int cgrt_closest_points_device(CgrtScene* s, const float* d_points, uint64_t n, 
     if ((rc = check_device_span(s, d_out, n * sizeof(CgrtClosest), "d_out")) != CGRT_OK) return rc;
     HIP_TRY(launch_closest(s->dev, d_points, n, max_dist2, reinterpret_cast<CgrtClosestDev*>(d_out), nullptr, static_cast<hipStream_t>(stream)));
     return CGRT_OK;
+}
+
+// ---- crossing queries (include/cgrt.h cgrt_count_crossings*, cgrt_list_crossings*): every triangle a ray passes
+// through, counted or listed in (t, prim_id) order.  No scene state is read or written; the checks come in the order include/cgrt.h
+// states, all before any device work.
+namespace {
+static_assert(sizeof(CgrtCrossing) == sizeof(CgrtCrossingDev), "CgrtCrossing is what the kernels write");
+const uint64_t kCrossingMaxCapacity = 1ull << 37;
+// where the conservative box test's argument does not hold the whole call tests every triangle: a wild triangle is accepted by every ray
+// wherever its boxes are, and a non-finite vertex leaves its boxes meaningless
+bool crossing_brute_scene(const CgrtScene* s) {
+    if (!s->bvh.geometry_finite) return true;
+    for (uint8_t w : s->bvh.leaf_wild)
+        if (w) return true;
+    return false;
+}
+// result: counts for the count entries, out2 for the work entry, out for the list entries; list: the slot arguments are checked
+int crossing_args(const CgrtScene* s, const void* rays, uint64_t n, const void* result, bool list, const uint64_t* offsets, uint32_t k,
+                  uint64_t capacity, const void* counts, bool device) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    if (n && (!rays || !result)) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many rays: n exceeds 0x7fffffff");
+    if (list) {
+        if ((offsets != nullptr) == (k > 0)) return fail(CGRT_E_ARG, "exactly one of offsets and k > 0 must be given");
+        if (capacity > kCrossingMaxCapacity) return fail(CGRT_E_ARG, "capacity exceeds 2^37 records");
+        if (k && n * (uint64_t)k > capacity) return fail(CGRT_E_ARG, "n * k records exceed capacity");
+        if (!device && offsets && n) {
+            if (offsets[0] != 0) return fail(CGRT_E_ARG, "offsets must start at 0");
+            for (uint64_t i = 0; i < n; i++)
+                if (offsets[i + 1] < offsets[i]) return fail(CGRT_E_ARG, "offsets must not decrease");
+            if (offsets[n] > capacity) return fail(CGRT_E_ARG, "offsets end beyond capacity");
+        }
+    }
+    if (device && ((uintptr_t)rays % 4 || (uintptr_t)result % 4 || (uintptr_t)counts % 4 || (uintptr_t)offsets % 8))
+        return fail(CGRT_E_ARG, "device pointers must be aligned to their elements");
+    return CGRT_OK;
+}
+// host pointers, on a call lane (slots: 0 the rays, 1 the offsets, 2 the records, 3 the counts); how: 0 tree search, 1 brute force,
+// 2 counted tree search (count mode)
+int crossing_host(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out, uint64_t capacity,
+                  uint32_t* counts, bool list, int how, uint64_t* work) {
+    int rc = crossing_args(s, rays, n, how == 2 ? static_cast<const void*>(work) : (list ? static_cast<const void*>(out) : counts), list, offsets,
+                           k, capacity, counts, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    const uint64_t used = list ? (offsets ? offsets[n] : n * (uint64_t)k) : 0;  // the slots are records [0, used)
+    const bool want_counts = !list || counts != nullptr;
+    if (how != 2 && used == 0 && !want_counts) return CGRT_OK;  // every slot is empty and no count is asked for: nothing to write
+    HIP_TRY(hipSetDevice(s->device));
+    LaneGuard g(s);
+    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    const bool brute = how == 1 || crossing_brute_scene(s);
+    const size_t out_bytes = (size_t)used * sizeof(CgrtCrossing), cnt_bytes = (size_t)n * 4u;
+    void *dr = nullptr, *doff = nullptr, *dout = nullptr, *dcnt = nullptr, *staged_out = nullptr, *staged_cnt = nullptr;
+    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
+    if (offsets) {
+        HIP_TRY(g.dev(1, (n + 1) * 8, &doff));
+        HIP_TRY(lane_upload(g, 1, doff, offsets, (n + 1) * 8));
+    }
+    if (used) HIP_TRY(g.dev(2, out_bytes, &dout));  // (a lane's buffer that was never needed is a null pointer)
+    if (want_counts || how == 2) HIP_TRY(g.dev(3, cnt_bytes, &dcnt));
+    CrossingArgs A{};
+    A.rays = static_cast<const float*>(dr);
+    A.n = n;
+    A.offsets = static_cast<const unsigned long long*>(doff);
+    A.k = k;
+    A.out = static_cast<CgrtCrossingDev*>(dout);  // no record to write (count entries, or every slot empty): the count search
+    A.capacity = used;
+    A.counts = static_cast<uint32_t*>(dcnt);
+    if (how == 2) {
+        HIP_TRY(hipMemsetAsync(g.L->d_counters, 0, 2 * sizeof(unsigned long long), g.L->stream));
+        HIP_TRY(launch_crossings(s->dev, A, brute, g.L->d_counters, g.L->stream));
+        unsigned long long h[2];
+        HIP_TRY(hipMemcpyAsync(h, g.L->d_counters, sizeof(h), hipMemcpyDeviceToHost, g.L->stream));
+        HIP_TRY(hipStreamSynchronize(g.L->stream));
+        work[0] = h[0];
+        work[1] = h[1];
+        return CGRT_OK;
+    }
+    HIP_TRY(launch_crossings(s->dev, A, brute, nullptr, g.L->stream));
+    if (used) HIP_TRY(lane_download(g, 2, out, dout, out_bytes, &staged_out));
+    if (want_counts) HIP_TRY(lane_download(g, 3, counts, dcnt, cnt_bytes, &staged_cnt));
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    if (staged_out) std::memcpy(out, staged_out, out_bytes);
+    if (staged_cnt) std::memcpy(counts, staged_cnt, cnt_bytes);
+    return CGRT_OK;
+}
+int crossing_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const uint64_t* d_offsets, uint32_t k, CgrtCrossing* d_out, uint64_t capacity,
+                    uint32_t* d_counts, bool list, void* stream) {
+    int rc = crossing_args(s, d_rays, n, list ? static_cast<const void*>(d_out) : d_counts, list, d_offsets, k, capacity, d_counts, true);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
+    if (d_offsets && (rc = check_device_span(s, d_offsets, (n + 1) * 8, "d_offsets")) != CGRT_OK) return rc;
+    // with offsets any record below capacity may be written; with k the slots are the first n * k records
+    if (list && (rc = check_device_span(s, d_out, (d_offsets ? capacity : n * (uint64_t)k) * sizeof(CgrtCrossing), "d_out")) != CGRT_OK) return rc;
+    if (d_counts && (rc = check_device_span(s, d_counts, n * 4, "d_counts")) != CGRT_OK) return rc;
+    CrossingArgs A{};
+    A.rays = reinterpret_cast<const float*>(d_rays);
+    A.n = n;
+    A.offsets = reinterpret_cast<const unsigned long long*>(d_offsets);
+    A.k = k;
+    A.out = list ? reinterpret_cast<CgrtCrossingDev*>(d_out) : nullptr;
+    A.capacity = capacity;
+    A.counts = d_counts;
+    HIP_TRY(launch_crossings(s->dev, A, crossing_brute_scene(s), nullptr, static_cast<hipStream_t>(stream)));
+    return CGRT_OK;
+}
+}  // namespace
+
+int cgrt_count_crossings(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint32_t* counts) {
+    return crossing_host(s, rays, n, nullptr, 0, nullptr, 0, counts, false, 0, nullptr);
+}
+int cgrt_count_crossings_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, uint32_t* d_counts, void* stream) {
+    return crossing_device(s, d_rays, n, nullptr, 0, nullptr, 0, d_counts, false, stream);
+}
+int cgrt_list_crossings(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out, uint64_t capacity,
+                        uint32_t* counts) {
+    return crossing_host(s, rays, n, offsets, k, out, capacity, counts, true, 0, nullptr);
+}
+int cgrt_list_crossings_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const uint64_t* d_offsets, uint32_t k, CgrtCrossing* d_out,
+                               uint64_t capacity, uint32_t* d_counts, void* stream) {
+    return crossing_device(s, d_rays, n, d_offsets, k, d_out, capacity, d_counts, true, stream);
+}
+int cgrt_list_crossings_brute(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out,
+                              uint64_t capacity, uint32_t* counts) {
+    return crossing_host(s, rays, n, offsets, k, out, capacity, counts, true, 1, nullptr);
+}
+int cgrt_debug_crossing_work(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint64_t* out2) {
+    return crossing_host(s, rays, n, nullptr, 0, nullptr, 0, nullptr, false, 2, out2);
 }
 
 int cgrt_debug_export_frame(int device, const float* rgb, int W, int H, int format, uint64_t row_bytes, void* out) {

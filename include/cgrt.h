@@ -754,7 +754,7 @@ int cgrt_surface_raycams_device(CgrtScene* scene, const CgrtRayCamera* cams, uin
  * NaN or negative; (device form) a pointer not 4-byte aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and touches
  * nothing.  Device form: then d_points (n * 12 bytes) and d_out (n * 32 bytes) checked as device memory of the scene's device, as
  * cgrt_shade_rays_device checks its buffers.
- * Not offered: signed distance; sphere primitives; k nearest; a per-query radius; attribute interpolation at the closest point
+ * Not offered: sphere primitives; k nearest; a per-query radius; attribute interpolation at the closest point
  * (attr[tri[prim_id]] weighted by bary is a plain gather); the fast tree as a search structure; enqueued-ticket forms (the device form
  * never blocks); the C++ host mirror (the reference has no such function). */
 typedef struct CgrtClosest {
@@ -767,6 +767,67 @@ int cgrt_closest_points(CgrtScene* scene, const float* points, uint64_t n, float
 int cgrt_closest_points_device(CgrtScene* scene, const float* d_points, uint64_t n, float max_dist2, CgrtClosest* d_out, void* stream);
 int cgrt_closest_points_brute(CgrtScene* scene, const float* points, uint64_t n, float max_dist2, CgrtClosest* out);
 int cgrt_debug_closest_work(CgrtScene* scene, const float* points, uint64_t n, float max_dist2, uint64_t* out2);
+
+/* Crossing queries: "which surfaces does this ray pass through -- all of them, in order?"  The count_intersections
+ * / list_intersections pair of other ray-casting scene interfaces: thickness and x-ray images, depth peeling, transparency, inside /
+ * outside tests.  The reference has no such function; the definition below IS the specification.
+ * Definition.  For a ray r = (o, d, t_in), triangle k is a CROSSING iff the reference's intersectRayWithTriangle (ray_tracing.cpp:86-114),
+ * called on a fresh copy of r, returns true; its parameter t_k is the ray.t that call leaves.  With on = dot(o, n), den = dot(d, n) of the
+ * triangle's plane (n, D) as trianglePlane gives it: onp = (on == D); tt = onp ? 0 : (D - on) / den; p = o + d * tt; inside =
+ * pointInTriangle(v0, v1, v2, n, p) (three `>= 0` tests); crossing iff
+ *     inside && (onp || (den != 0 && !(tt < 0) && !(tt >= t_in))),    t_k = tt.
+ * An origin-on-plane acceptance has t = 0 and ignores t_in, as upstream does (ray_tracing.cpp:43-47).  A crossing is a pure function of
+ * (ray, triangle): no tree, no visiting order, no running minimum enters.  The ray is taken as given: a segment sets t to its length, the
+ * direction need not be of unit length.  Spheres are ignored.  A ray's crossings are ordered by t compared as floats (-0 equals +0), equal
+ * t going to the smaller prim_id: a total order, so every output byte is determined.
+ * Consequences.
+ *   C1  On a scene without spheres, for a ray with no origin-on-plane acceptance, the first crossing is cgrt_intersect_brute_batch(mesh <
+ *       0)'s t (bit pattern) and prim_id.  It is NOT always cgrt_intersect_batch's hit: the reference's tree walk misses hits (SURVEY.md
+ *       F4); the list does not.
+ *   C2  A ray through an edge shared by two triangles crosses both (pointInTriangle uses `>= 0`), so the parity of the count along one ray
+ *       is only almost always the inside test.
+ * Slots.  CgrtCrossing = {t, prim_id}, 8 bytes.  cgrt_count_crossings* write counts[i] = the number of crossings of ray i.  In the list
+ * calls ray i owns the records [offsets[i], offsets[i + 1]) of out (offsets: n + 1 entries; the exclusive prefix sums of a count call give
+ * the full list, CSR style) or, with offsets == NULL, the records [i * k, (i + 1) * k): exactly one of offsets and k > 0 must be given.  A
+ * slot of s records receives the first min(s, count) crossings in order and {+inf, CGRT_NO_PRIM} in its remaining entries; counts[i] (may
+ * be NULL in the list calls) is always the full number of crossings.  Every record of every slot is written, nothing outside the slots.
+ * The host forms check that offsets start at 0, do not decrease and end <= capacity.  The device form never reads the offsets on the host:
+ * the kernel treats a decreasing pair as an empty slot and clamps both ends to capacity, so no offset table makes it write outside the
+ * first `capacity` records of d_out (slots that overlap are written by several rays, in no defined order).
+ * Search.  One ray per lane over the structure every scene has (the reference tree, the in-leaf accelerators, linear leaves under
+ * cgrt_set_leaf_accel(0)) with the conservative box test alone, bounded by t_in; while a slot is full and no count is asked for, the bound
+ * shrinks to the largest t kept (non-strictly: an equal-t smaller prim_id still arrives).  The result is what cgrt_list_crossings_brute --
+ * every triangle in turn, same function, same slot rule; a validation path -- returns, byte for byte.  Where the conservative argument does
+ * not hold the search is not used: a scene with a wild leaf or a non-finite vertex (cgrt_scene_build_info [1] > 0 or [2] == 0) runs the
+ * brute-force kernel for the whole call, and a ray outside the box test's envelope (non-finite or beyond 2^+-40, NaN t) tests every
+ * triangle itself.  The walk settings (cgrt_scene_set_walk, cgrt_set_fast_tree, cgrt_set_kernel_shape) do not enter.
+ * cgrt_debug_crossing_work: a separate counting launch of the count search (never part of a timed region); out2 = {node steps, triangles
+ * evaluated}, summed over the n rays.
+ * Streams.  The host forms (host pointers, synchronous) run on a call lane like cgrt_closest_points: any number of threads may query one
+ * scene at once.  The device forms read no host array and only enqueue on `stream` (NULL = default stream); they are concurrent on one
+ * scene and neither read nor write the prediction record or the frame hints.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene; NULL rays or result array (counts of the count calls, out
+ * of the list calls, out2) with n > 0; n > 0x7fffffff; (list calls) both or neither of offsets and k > 0; capacity above 2^37 records;
+ * with k, n * k > capacity; (host list calls, n > 0) offsets not starting at 0, decreasing, or ending above capacity; (device forms) a
+ * pointer not aligned to its element (4 bytes; 8 for d_offsets).  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and touches
+ * nothing.  Device forms: then d_rays (n * 28 bytes), d_offsets ((n + 1) * 8), d_out (capacity records with offsets, n * k with k) and
+ * d_counts (n * 4) checked as device memory of the scene's device, as cgrt_shade_rays_device checks its buffers.
+ * Not offered: the fast tree as the search structure (there is no closest-first pruning for it to win on: one path); quad / 16-lane
+ * shapes; spheres; normals or material ids per record (tri_mesh[prim_id] is a gather; barycentrics come from cgrt_hit_barycentrics_device
+ * on gathered rays); frame / camera forms; enqueued-ticket forms (the device forms never block); the C++ host mirror. */
+typedef struct CgrtCrossing {
+    float t;          /* the crossing's parameter; +inf in an unused entry      */
+    uint32_t prim_id; /* CGRT_NO_PRIM in an unused entry                        */
+} CgrtCrossing;
+int cgrt_count_crossings(CgrtScene* scene, const CgrtRay* rays, uint64_t n, uint32_t* counts);
+int cgrt_count_crossings_device(CgrtScene* scene, const CgrtRay* d_rays, uint64_t n, uint32_t* d_counts, void* stream);
+int cgrt_list_crossings(CgrtScene* scene, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out,
+                        uint64_t capacity, uint32_t* counts);
+int cgrt_list_crossings_device(CgrtScene* scene, const CgrtRay* d_rays, uint64_t n, const uint64_t* d_offsets, uint32_t k, CgrtCrossing* d_out,
+                               uint64_t capacity, uint32_t* d_counts, void* stream);
+int cgrt_list_crossings_brute(CgrtScene* scene, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out,
+                              uint64_t capacity, uint32_t* counts);
+int cgrt_debug_crossing_work(CgrtScene* scene, const CgrtRay* rays, uint64_t n, uint64_t* out2);
 
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.

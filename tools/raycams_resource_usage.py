@@ -26,7 +26,8 @@ FIELDS = [("VGPRs", r"VGPRs: (\d+)"), ("SGPRs", r"SGPRs: (\d+)"), ("scratch", r"
 
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
-    return [re.sub(r"^void |\(.*$", "", o) for o in out]
+    # (a kernel of an anonymous namespace keeps its name: the argument list is cut at the first parenthesis AFTER that qualifier)
+    return [re.sub(r"^void |\(.*$", "", o.replace("(anonymous namespace)::", "")) for o in out]
 
 
 def usage(csrc_dir: str, src: str, obj: str) -> dict:
