@@ -166,6 +166,20 @@ unsigned long long owned_pixels(const FrameDev& F) {
 
 }  // namespace
 
+// The slots of a scene's device workspace (CgrtScene::work), by what the shaded frame keeps in them (Wavefront and render_impl below).  A
+// level's list (rays / hits / normals / pixels) has four buffer sets and its shadow list two; their numbers are not contiguous because
+// slots were added as features came.
+enum WorkSlotId {
+    WS_RAYS0, WS_RAYS1, WS_HITS0, WS_HITS1, WS_NORMALS0, WS_NORMALS1, WS_PIX0, WS_PIX1, WS_IPIX,  // 0..8
+    WS_SRAYS0, WS_SHITS0, WS_SDIST0, WS_SSLOT0,                                                   // 9..12
+    WS_LIGHTS, WS_LEVELS, WS_RGB, WS_CTR, WS_SLIGHTS, WS_UNITS, WS_LIT, WS_COUNTED,               // 13..20
+    WS_RAYS2, WS_HITS2, WS_NORMALS2, WS_PIX2, WS_SRAYS1, WS_SHITS1, WS_SDIST1, WS_SSLOT1,         // 21..28
+    WS_SPAWN, WS_RESOLVED, WS_VIEWS, WS_SETS, WS_SETTAB,  // 29..33 (32 and 33: light-set batches only)
+    WS_RAYS3, WS_HITS3, WS_NORMALS3, WS_PIX3,             // 34..37: deep frames with geometry buffers only
+    WS_SLOTS
+};
+static_assert(WS_RGB == 15 && WS_RESOLVED == 30 && WS_SLOTS == 38, "the workspace's slot numbers");
+
 struct CgrtScene {
     int device = 0;
     BuiltBvh bvh;
@@ -301,7 +315,7 @@ struct CgrtScene {
     struct WorkSlot {
         void* p = nullptr;
         size_t cap = 0;
-    } work[38];  // slots 0..37 are in use (render_impl; 32 and 33 by light-set batches only, 34..37 by deep frames with geometry buffers)
+    } work[WS_SLOTS];
     // pinned host staging of cgrt_render*'s frame (grown on demand, guarded by render_mutex): the device frame comes down with ONE
     // asynchronous copy at PCIe speed; cgrt_render_mapped hands this memory to the caller instead of copying it once more
     void* pin_frame = nullptr;
@@ -321,7 +335,7 @@ struct CgrtScene {
         SpawnDev spawn_host{};           // what the workspace's SpawnDev (fused level-0 spawn of predicted frames) holds
         bool spawn_valid = false;
     } raux;
-    // cgrt_render_device: its export kernel reads the frame (work slot 15, or 30 with aa) on the CALLER's stream after the call has
+    // cgrt_render_device: its export kernel reads the frame (work slot WS_RGB, or WS_RESOLVED with aa) on the CALLER's stream after the call has
     // returned.  This event is recorded behind it, and the next cgrt_render* call on the scene makes every stream it uses wait on it
     // (and waits for it on the host before it reallocates those buffers); the caller's stream handle itself is never kept.
     hipEvent_t export_done = nullptr;
@@ -459,6 +473,7 @@ struct WsBuf {  // a slot of the scene's workspace, with DevBuf's interface
         p = w.p;
         return hipSuccess;
     }
+    size_t cap() const { return sc->work[slot].cap; }
     template <class T>
     T* as() const {
         return static_cast<T*>(p);
@@ -1986,6 +2001,14 @@ int cgrt_debug_trace_shadow(CgrtScene* s, const CgrtRay* rays, const float* dist
     return CGRT_OK;
 }
 
+// SoftDev of the caller's sampling parameters, for SL spherical lights and the unit vectors where they lie on the device; level,
+// view_pixels and set_index are the caller's to set
+static SoftDev soft_dev(const CgrtSoftShadows& soft, unsigned SL, const float* lights, const float* units) {
+    SoftDev Q{};
+    Q.lights = lights, Q.units = units, Q.nlights = SL;
+    Q.samples = soft.samples, Q.nunits = soft.nunits, Q.seed = soft.seed;
+    return Q;
+}
 // The frame's soft-shadow launcher on caller items (include/cgrt.h).
 int cgrt_debug_soft_lit(CgrtScene* s, const CgrtRay* item_rays, const CgrtHit* item_hits, const int32_t* item_pixels, uint64_t nitems,
                         const CgrtSoftShadows* soft, int level, int anyhit, uint32_t* lit) {
@@ -2010,13 +2033,7 @@ int cgrt_debug_soft_lit(CgrtScene* s, const CgrtRay* item_rays, const CgrtHit* i
     HIP_TRY(hipMemcpy(dl.p, soft->spherical, SL * 28, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(du.p, soft->unit_vectors, (size_t)soft->nunits * 12, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(dlit.p, 0, nitems * SL * sizeof(uint32_t)));
-    SoftDev Q{};
-    Q.lights = dl.as<float>();
-    Q.units = du.as<float>();
-    Q.nlights = (uint32_t)SL;
-    Q.samples = soft->samples;
-    Q.nunits = soft->nunits;
-    Q.seed = soft->seed;
+    SoftDev Q = soft_dev(*soft, (unsigned)SL, dl.as<float>(), du.as<float>());
     Q.level = (uint32_t)level;
     HIP_TRY(launch_soft_shadow(s->dev, Q, dr.as<float>(), dh.as<CgrtHitDev>(), dp.as<int>(), nitems, dlit.as<uint32_t>(), anyhit != 0, nullptr));
     HIP_TRY(hipDeviceSynchronize());
@@ -2045,16 +2062,8 @@ int cgrt_count_batch(CgrtScene* s, const CgrtRay* rays, uint64_t n, CgrtCounters
 // counted (optional, 3 blocks): the frame is rendered with the instrumented kernels (never timed) and the work of its primary,
 // shadow and mirror traversals is returned separately
 
-// rgb (optional): the caller's frame; mapped (optional): receives the scene's pinned staging frame (valid until the next
-// cgrt_render* call on this scene).  With nranks > 1 only the pixels this rank owns are meaningful in the staging frame, and only
-// those are copied into rgb (pixels of other ranks keep the caller's contents).
-// aa: the reference's antiAliasing branch (main.cpp:663-687): the wavefront shades the 2W x 2H sub-sample frame, ranks own its
-// 64x64 super-tiles (32x32 pixel blocks of the W x H frame), k_resolve_aa writes the W x H frame on the device and only that comes
-// down (nranks > 1: only this rank's pixels, packed).  The caller has checked the arguments (aa_args).
-// dout (cgrt_render_device, instead of rgb / mapped): nothing comes down; k_export_frame writes this rank's pixels of the W x H frame
-// into the caller's device buffer on the caller's stream (behind the frame, and behind whatever the caller queued there before).
 // Which of the wavefront's buffer sets a level's hits / normals / rays / pixels live in: level % 3, or -- a frame with geometry buffers
-// that is deep enough to reuse set 0 -- level 0 in set 0 for good and levels 1.. through sets 1, 2, 3 (render_impl, enqueue_impl).
+// that is deep enough to reuse set 0 -- level 0 in set 0 for good and levels 1.. through sets 1, 2, 3 (applied by Wavefront::level alone).
 struct AovSets {
     bool keep0;
     int count() const { return keep0 ? 4 : 3; }
@@ -2185,53 +2194,201 @@ static ExportDev export_of(const FrameDev& F, const float* src, const DeviceOut&
     }
     return E;
 }
-static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
-                       int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats, CgrtCounters* counted = nullptr,
-                       const float** mapped = nullptr, bool aa = false, const DeviceOut* dout = nullptr, const ListSrc* list = nullptr,
-                       const ViewSrc* views = nullptr, const LightSetSrc* sets = nullptr, const CgrtAovOut* aov = nullptr) {
-    if (!s || (!cam && !list && !views) || (!rgb && !mapped && !dout && !list) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
-    NEED_DEVICE(s);
-    if (W <= 0 || H <= 0 || max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad frame size or recursion depth");
-    // (light sets: the batch's distinct spherical keys, with the caller's sampling parameters; light_sets_args has checked them)
-    const unsigned SL = sets ? (unsigned)sets->sph_index.size() : soft ? soft->nspherical : 0;
-    if (SL && !sets) {
-        if (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24))
-            return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
-        if ((unsigned long long)W * H > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large");
+// cgrt_shade_rays' rules for the spherical lights, which every frame entry shares; NULL = no spherical lights
+static int soft_rules(const CgrtSoftShadows* soft) {
+    if (soft && soft->nspherical &&
+        (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
+        return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
+    return CGRT_OK;
+}
+
+// ---- The shaded frame as both of its drivers see it (render_impl: blocking; enqueue_impl: without a host round trip) ----
+// What a frame entry asks for.  Each C entry runs its own argument check and fills the fields it means; the others keep their defaults.
+// rgb (optional): the caller's frame; mapped (optional): receives the scene's pinned staging frame (valid until the next
+// cgrt_render* call on this scene).  With nranks > 1 only the pixels this rank owns are meaningful in the staging frame, and only
+// those are copied into rgb (pixels of other ranks keep the caller's contents).
+// aa: the reference's antiAliasing branch (main.cpp:663-687): the wavefront shades the 2W x 2H sub-sample frame, ranks own its
+// 64x64 super-tiles (32x32 pixel blocks of the W x H frame), k_resolve_aa writes the W x H frame on the device and only that comes
+// down (nranks > 1: only this rank's pixels, packed).  The caller has checked the arguments (aa_args).
+// dout (cgrt_render_device, instead of rgb / mapped): nothing comes down; k_export_frame writes this rank's pixels of the W x H frame
+// into the caller's device buffer on the caller's stream (behind the frame, and behind whatever the caller queued there before).
+struct FrameRequest {
+    const CgrtCamera* cam = nullptr;  // level 0: one camera's W x H frame, or a caller's ray list, or a batch of views of W x H each
+    const ListSrc* list = nullptr;
+    const ViewSrc* views = nullptr;
+    int W = 1, H = 1;
+    const float* lights = nullptr;  // point lights, nlights x 6
+    uint32_t nlights = 0;
+    const LightSetSrc* sets = nullptr;      // a batch of light sets instead (use_sets)
+    const CgrtSoftShadows* soft = nullptr;  // spherical lights and their sampling (light sets: the sampling parameters only)
+    int max_level = 0;
+    int rank = 0, nranks = 1;
+    bool aa = false;
+    float* rgb = nullptr;  // (a ray list's colours go to list->rgb instead of these three)
+    const float** mapped = nullptr;
+    const DeviceOut* dout = nullptr;
+    const CgrtAovOut* aov = nullptr;
+    CgrtCounters* counted = nullptr;   // (blocking frames) 3 blocks of work counters
+    CgrtRenderStats* stats = nullptr;  // (blocking frames)
+    hipStream_t stream = nullptr;      // (enqueued frames) the caller's stream
+    uint64_t* ticket = nullptr;        // (enqueued frames) receives the frame's number
+    void use_sets(const LightSetSrc& P) {  // (k_spawn's light list is the batch's distinct positions)
+        sets = &P;
+        lights = P.points.data();
+        nlights = (uint32_t)(P.points.size() / 6);
     }
-    const int PW = W, PH = H;  // the frame the caller receives
-    if (aa) {                  // from here on W x H is the frame the wavefront shades: sub-sample (xc, yc) is its pixel (xc, yc)
-        W *= 2;
-        H *= 2;
+    // (light sets: the batch's distinct spherical keys, with the caller's sampling parameters; light_sets_args has checked them)
+    unsigned spherical() const { return sets ? (unsigned)sets->sph_index.size() : soft ? soft->nspherical : 0; }
+};
+// The sizes that follow from a request.
+struct FrameShape {
+    int PW, PH;  // the frame the caller receives
+    int W, H;    // the frame the wavefront shades (aa: 2 PW x 2 PH, sub-sample (xc, yc) is its pixel (xc, yc))
+    int max_level;
+    bool aa, list, light_sets;
+    unsigned L, SL;          // point lights; spherical lights
+    uint32_t nviews, nsets;  // (the frame buffer holds the views' and the sets' frames back to back)
+    unsigned long long npix;
+    unsigned long long n;  // items: this rank's part of the frame in the primary kernel's order, or the caller's rays
+    FrameDev F;
+    int packed;
+    size_t res_bytes, dres_bytes;  // the resolved frame (aa), and the buffer k_resolve_aa writes it into
+    size_t nctr;  // counter words: per level {shadow rays, mirror rays, hits, -}; the last block: [2], [3] = entries of levels 0, 1 / primary hits
+    AovSets sets_for;
+};
+static int frame_shape(const FrameRequest& R, int block, FrameShape& S) {
+    S.PW = R.W, S.PH = R.H;
+    S.W = R.aa ? 2 * R.W : R.W, S.H = R.aa ? 2 * R.H : R.H;
+    S.max_level = R.max_level;
+    S.aa = R.aa, S.list = R.list != nullptr, S.light_sets = R.sets != nullptr;
+    S.L = R.nlights, S.SL = R.spherical();
+    S.nviews = R.views ? R.views->n : 1u;
+    S.nsets = R.sets ? R.sets->nsets : 1u;
+    S.npix = R.list ? R.list->n : (unsigned long long)S.W * S.H * S.nviews * S.nsets;
+    S.F = FrameDev{};
+    if (R.views) {
+        if (!make_views_frame(S.W, S.H, S.nviews, block, S.F)) return fail(CGRT_E_ARG, "bad batch");
+    } else if (!R.list && !make_frame(S.W, S.H, 0, 0, S.W, S.H, R.rank, R.nranks, block, S.F)) {
+        return fail(CGRT_E_ARG, "bad frame or rank");
+    }
+    S.n = R.list ? R.list->n : (unsigned long long)S.F.nblocks * (unsigned long long)S.F.block;
+    S.packed = R.aa && R.nranks > 1;
+    S.res_bytes = S.packed ? (size_t)S.F.nst_rank * 1024 * 12 : (size_t)S.PW * S.PH * 12;
+    S.dres_bytes = std::max<size_t>(S.res_bytes, (size_t)S.F.nst_rank * 1024 * 12);
+    S.nctr = 4 * (size_t)(R.max_level + 1);
+    S.sets_for = AovSets{R.aov && R.max_level >= 4};
+    return CGRT_OK;
+}
+// The wavefront's part of the scene's workspace.
+// Every level is a compact list: level 0 = the primary rays that hit, level l + 1 = the mirror rays of level l (at most one per entry,
+// so the number of primary hits bounds every list, and n bounds that); the shadow list of a level holds at most entries * L rays.
+// hits/normals/rays/pixels rotate through three sets (level l reads set l % 3 and writes its mirror rays into set (l + 1) % 3;
+// level 1 is evaluated on a second stream while level 0 is still being shaded, so its mirror rays need a third set), the
+// shadow lists through two.
+// Geometry buffers (aov) are scattered from level 0's lists behind the frame: a frame deep enough to reuse set 0 (level 3 reads it,
+// level 2 writes it) keeps level 0 in set 0 alone and rotates levels 1.. through sets 1, 2 and 3 instead.
+struct Wavefront {
+    const FrameShape& S;
+    WsBuf rays[4], hits[4], normals[4], pix[4], ipix, srays[2], shits[2], sdist[2], sslot[2], levels, rgb, ctr, lit, resolved, sets;
+    Wavefront(CgrtScene* s, const FrameShape& shape)
+        : S(shape), rays{{s, WS_RAYS0}, {s, WS_RAYS1}, {s, WS_RAYS2}, {s, WS_RAYS3}}, hits{{s, WS_HITS0}, {s, WS_HITS1}, {s, WS_HITS2}, {s, WS_HITS3}},
+          normals{{s, WS_NORMALS0}, {s, WS_NORMALS1}, {s, WS_NORMALS2}, {s, WS_NORMALS3}}, pix{{s, WS_PIX0}, {s, WS_PIX1}, {s, WS_PIX2}, {s, WS_PIX3}},
+          ipix{s, WS_IPIX}, srays{{s, WS_SRAYS0}, {s, WS_SRAYS1}}, shits{{s, WS_SHITS0}, {s, WS_SHITS1}}, sdist{{s, WS_SDIST0}, {s, WS_SDIST1}},
+          sslot{{s, WS_SSLOT0}, {s, WS_SSLOT1}}, levels{s, WS_LEVELS}, rgb{s, WS_RGB}, ctr{s, WS_CTR}, lit{s, WS_LIT}, resolved{s, WS_RESOLVED},
+          sets{s, WS_SETS} {}
+    // what both drivers allocate, sized for the worst case
+    int reserve() {
+        const unsigned long long n = S.n;
+        const size_t depth = (size_t)(S.max_level > 0 ? S.max_level : 1);
+        HIP_TRY(ipix.alloc(n * 4));  // pixels of level 0, kept to the end
+        for (int k = 0; k < S.sets_for.count(); k++) {
+            HIP_TRY(rays[k].alloc(n * 28));
+            HIP_TRY(hits[k].alloc(n * sizeof(CgrtHit)));
+            HIP_TRY(normals[k].alloc(n * 12));
+            HIP_TRY(pix[k].alloc(n * 4));
+        }
+        for (int k = 0; k < 2; k++) {
+            HIP_TRY(srays[k].alloc(n * S.L * 28));
+            HIP_TRY(shits[k].alloc(n * S.L * sizeof(CgrtHit)));
+            HIP_TRY(sdist[k].alloc(n * S.L * 4));
+            HIP_TRY(sslot[k].alloc(n * S.L * 4));
+        }
+        HIP_TRY(levels.alloc(depth * n * 32));
+        if (!S.list) HIP_TRY(rgb.alloc(S.npix * 12));  // (a ray list's colours go straight into the caller's buffer)
+        if (S.aa) HIP_TRY(resolved.alloc(S.dres_bytes));
+        HIP_TRY(ctr.alloc(S.nctr * sizeof(uint32_t)));
+        if (S.SL) HIP_TRY(lit.alloc(n * S.SL * 4));
+        // light sets: every set's colours of every level (set b's entry i of a level at b * n + i)
+        if (S.light_sets) HIP_TRY(sets.alloc(depth * n * S.nsets * 16));
+        return CGRT_OK;
+    }
+    uint32_t* ctr_of(int level) const { return ctr.as<uint32_t>() + 4 * (size_t)level; }
+    float* lvl_of(int level) const { return levels.as<float>() + (size_t)level * S.n * 8; }
+    float* sets_of(int level) const { return sets.p ? sets.as<float>() + (size_t)level * S.n * S.nsets * 4 : nullptr; }
+    // Level l's lists, records and counters, and the next level's list: the one place that says which buffer set a level lives in.
+    LevelDev level(int l) const {
+        const int a = S.sets_for.of(l), b = S.sets_for.of(l + 1), q = l & 1;  // this level's buffer set, the next level's, this level's shadow set
+        const bool child = l + 1 < S.max_level;
+        LevelDev V{};
+        V.rays = rays[a].as<float>(), V.hits = hits[a].as<CgrtHitDev>(), V.normals = normals[a].as<float>();
+        V.pixels = l == 0 ? ipix.as<int>() : pix[a].as<int>();
+        V.srays = srays[q].as<float>(), V.sdist = sdist[q].as<float>(), V.sslot = sslot[q].as<int>(), V.shits = shits[q].as<CgrtHitDev>();
+        V.lvl = lvl_of(l), V.counters = ctr_of(l), V.sets = sets_of(l);
+        V.spawn = child;
+        V.next_rays = rays[b].as<float>(), V.next_hits = hits[b].as<CgrtHitDev>(), V.next_normals = normals[b].as<float>(), V.next_pixels = pix[b].as<int>();
+        V.child_lvl = child ? lvl_of(l + 1) : nullptr, V.child_sets = child ? sets_of(l + 1) : nullptr;
+        V.stride = S.n, V.nsets = S.nsets;
+        return V;
+    }
+};
+// The tables of a frame from where their data lies on the device: workspace slots (render_impl) or the staged table (enqueue_impl).
+static SetsDev sets_dev(const LightSetSrc& P, const uint32_t* tab) {  // tab: a copy of P.table; sph_index follows the two offset rows
+    SetsDev T{};
+    T.point_off = tab, T.sph_off = tab + P.nsets + 1, T.nsets = P.nsets;
+    T.point = reinterpret_cast<const float4*>(tab + P.point_at), T.sph = reinterpret_cast<const float4*>(tab + P.sph_at);
+    return T;
+}
+// level 0's spawn as the primary kernel does it itself, from the registers of the lanes that hit (spawn_rays.h)
+static SpawnDev spawn_dev(const LevelDev& V0, const FrameConst& K) {
+    SpawnDev SP{};
+    SP.materials = K.materials, SP.lights = K.lights, SP.nlights = K.nlights, SP.spawn = V0.spawn;
+    SP.srays = V0.srays, SP.sdist = V0.sdist, SP.sslot = V0.sslot, SP.lvl = reinterpret_cast<float4*>(V0.lvl);
+    SP.next_rays = V0.next_rays, SP.next_pixels = V0.next_pixels;
+    return SP;
+}
+// The blocking frame.  The caller has checked the arguments (aa: aa_args).
+static int render_impl(CgrtScene* s, const FrameRequest& R) {
+    const ListSrc* const list = R.list;
+    const ViewSrc* const views = R.views;
+    const LightSetSrc* const sets = R.sets;
+    const CgrtSoftShadows* const soft = R.soft;
+    const DeviceOut* const dout = R.dout;
+    const CgrtAovOut* const aov = R.aov;
+    float* const rgb = R.rgb;
+    const int max_level = R.max_level, rank = R.rank, nranks = R.nranks;
+    const bool aa = R.aa, counted = R.counted != nullptr;
+    if (!s || (!R.cam && !list && !views) || (!rgb && !R.mapped && !dout && !list) || (R.nlights && !R.lights)) return fail(CGRT_E_ARG, "NULL argument");
+    NEED_DEVICE(s);
+    if (R.W <= 0 || R.H <= 0 || max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad frame size or recursion depth");
+    const unsigned L = R.nlights, SL = R.spherical();
+    if (SL && !sets) {
+        const int rc = soft_rules(soft);
+        if (rc) return rc;
+        if ((unsigned long long)R.W * R.H > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large");
     }
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> one_frame(s->render_mutex);  // the workspace below belongs to one frame at a time
-    const uint32_t nviews = views ? views->n : 1u;
-    const uint32_t nsets = sets ? sets->nsets : 1u;  // (the frame buffer holds the sets' frames back to back)
-    const unsigned long long npix = list ? list->n : (unsigned long long)W * H * nviews * nsets;
-    const unsigned L = nlights;
+    FrameShape S;
+    if (const int rc = frame_shape(R, trace_block(s->dev), S)) return rc;
+    const int W = S.W, H = S.H, PW = S.PW, PH = S.PH, packed = S.packed;
+    const uint32_t nviews = S.nviews, nsets = S.nsets;
+    const unsigned long long npix = S.npix, n = S.n;
+    const size_t nctr = S.nctr;
+    FrameDev& F = S.F;
     CgrtRenderStats st{};
-    FrameDev F{};
-    if (views) {
-        if (!make_views_frame(W, H, nviews, trace_block(s->dev), F)) return fail(CGRT_E_ARG, "bad batch");
-    } else if (!list && !make_frame(W, H, 0, 0, W, H, rank, nranks, trace_block(s->dev), F)) {
-        return fail(CGRT_E_ARG, "bad frame or rank");
-    }
-    // items: this rank's part of the frame in the primary kernel's order, or the caller's rays
-    const unsigned long long n = list ? list->n : (unsigned long long)F.nblocks * (unsigned long long)F.block;
-    // Every level is a compact list: level 0 = the primary rays that hit, level l + 1 = the mirror rays of level l (at most
-    // one per entry, so the number of primary hits bounds every list, and n bounds that); the shadow list of a level
-    // holds at most entries * L rays.  hits/normals/rays/pixels alternate between two sets (a level's mirror batch is
-    // traversed on a second stream while the level itself is still being shaded).
-    // hits/normals/rays/pixels rotate through three sets (level l reads set l % 3 and writes its mirror rays into set (l + 1) % 3;
-    // level 1 is evaluated on a second stream while level 0 is still being shaded, so its mirror rays need a third set), the
-    // shadow lists through two.
-    // Geometry buffers (aov) are scattered from level 0's lists behind the frame: a frame deep enough to reuse set 0 (level 3 reads it,
-    // level 2 writes it) keeps level 0 in set 0 alone and rotates levels 1.. through sets 1, 2 and 3 instead.
-    WsBuf rays[4] = {{s, 0}, {s, 1}, {s, 21}, {s, 34}}, hits[4] = {{s, 2}, {s, 3}, {s, 22}, {s, 35}}, normals[4] = {{s, 4}, {s, 5}, {s, 23}, {s, 36}},
-          pix[4] = {{s, 6}, {s, 7}, {s, 24}, {s, 37}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
-          sslot[2] = {{s, 12}, {s, 28}}, dlights{s, 13}, levels{s, 14}, drgb{s, 15}, dctr{s, 16}, dslights{s, 17}, dunits{s, 18}, dlit{s, 19},
-          dwork{s, 20}, dspawn{s, 29}, dres{s, 30}, dviews{s, 31}, dsets{s, 32}, dsettab{s, 33};
+    Wavefront ws(s, S);
+    WsBuf dlights{s, WS_LIGHTS}, dslights{s, WS_SLIGHTS}, dunits{s, WS_UNITS}, dwork{s, WS_COUNTED}, dspawn{s, WS_SPAWN}, dviews{s, WS_VIEWS},
+        dsettab{s, WS_SETTAB};  // (the blocking frame's own slots)
     unsigned long long *cw_primary = nullptr, *cw_shadow = nullptr, *cw_mirror = nullptr;
     if (counted) {
         HIP_TRY(dwork.alloc(3 * 8 * sizeof(unsigned long long)));
@@ -2240,68 +2397,33 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         cw_shadow = cw_primary + 8;
         cw_mirror = cw_primary + 16;
     }
-    const int packed = aa && nranks > 1;
-    const size_t res_bytes = packed ? (size_t)F.nst_rank * 1024 * 12 : (size_t)PW * PH * 12;  // the resolved frame (aa)
-    const size_t dres_bytes = std::max<size_t>(res_bytes, (size_t)F.nst_rank * 1024 * 12);
-    // A cgrt_render_device export of an earlier frame may still be reading drgb / dres on its caller's stream: the frame's streams wait
-    // for it below, and a buffer that has to grow (hipFree) is not taken from under it.
+    // A cgrt_render_device export of an earlier frame may still be reading the frame or the resolved frame on its caller's stream: the
+    // frame's streams wait for it below, and a buffer that has to grow (hipFree) is not taken from under it.
     const bool after_export = s->export_pending;
-    if (after_export && ((!list && s->work[15].cap < npix * 12) || (aa && s->work[30].cap < dres_bytes))) HIP_TRY(hipEventSynchronize(s->export_done));
+    if (after_export && ((!list && ws.rgb.cap() < npix * 12) || (aa && ws.resolved.cap() < S.dres_bytes))) HIP_TRY(hipEventSynchronize(s->export_done));
     HIP_TRY(dspawn.alloc(sizeof(SpawnDev)));
-    HIP_TRY(ipix.alloc(n * 4));  // pixels of level 0, kept to the end
-    const AovSets sets_for{aov && max_level >= 4};
-    for (int k = 0; k < sets_for.count(); k++) {
-        HIP_TRY(rays[k].alloc(n * 28));
-        HIP_TRY(hits[k].alloc(n * sizeof(CgrtHit)));
-        HIP_TRY(normals[k].alloc(n * 12));
-        HIP_TRY(pix[k].alloc(n * 4));
-    }
-    for (int k = 0; k < 2; k++) {
-        HIP_TRY(srays[k].alloc(n * L * 28));
-        HIP_TRY(shits[k].alloc(n * L * sizeof(CgrtHit)));
-        HIP_TRY(sdist[k].alloc(n * L * 4));
-        HIP_TRY(sslot[k].alloc(n * L * 4));
-    }
+    if (const int rc = ws.reserve()) return rc;
     HIP_TRY(dlights.alloc((size_t)L * 24));
-    HIP_TRY(levels.alloc((size_t)(max_level > 0 ? max_level : 1) * n * 32));
-    if (!list) HIP_TRY(drgb.alloc(npix * 12));  // (a ray list's colours go straight into the caller's buffer)
-    float* const frame_rgb = list ? list->rgb : drgb.as<float>();
-    if (aa) HIP_TRY(dres.alloc(dres_bytes));
+    float* const frame_rgb = list ? list->rgb : ws.rgb.as<float>();
     // (k_resolve_aa's grid covers whole 32x32 blocks; threads outside the frame write nothing)
-    auto resolve = [&](hipStream_t on) { return aa ? launch_resolve_aa(F, drgb.as<float>(), dres.as<float>(), packed, on) : hipSuccess; };
-    const size_t nctr = 4 * (size_t)(max_level + 1);
-    HIP_TRY(dctr.alloc(nctr * sizeof(uint32_t)));  // per level {shadow rays, mirror rays, hits, -}; the last block: [3] = primary hits
-    if (L) HIP_TRY(hipMemcpy(dlights.p, lights, (size_t)L * 24, hipMemcpyHostToDevice));
-    // light sets: every set's colours of every level (set b's entry i of a level at b * n + i), and the sets' table (SetsDev)
+    auto resolve = [&](hipStream_t on) { return aa ? launch_resolve_aa(F, ws.rgb.as<float>(), ws.resolved.as<float>(), packed, on) : hipSuccess; };
+    if (L) HIP_TRY(hipMemcpy(dlights.p, R.lights, (size_t)L * 24, hipMemcpyHostToDevice));
     SetsDev T{};
-    auto sets_of = [&](int level) { return dsets.as<float>() + (size_t)level * n * nsets * 4; };
-    if (sets) {
-        HIP_TRY(dsets.alloc((size_t)(max_level > 0 ? max_level : 1) * n * nsets * 16));
+    if (sets) {  // the sets' table (SetsDev)
         HIP_TRY(dsettab.alloc(sets->table.size() * 4));
         HIP_TRY(hipMemcpy(dsettab.p, sets->table.data(), sets->table.size() * 4, hipMemcpyHostToDevice));
-        const uint32_t* tab = dsettab.as<uint32_t>();
-        T.point_off = tab;
-        T.sph_off = tab + nsets + 1;
-        T.point = reinterpret_cast<const float4*>(tab + sets->point_at);
-        T.sph = reinterpret_cast<const float4*>(tab + sets->sph_at);
-        T.nsets = nsets;
+        T = sets_dev(*sets, dsettab.as<uint32_t>());
     }
     SoftDev Q{};
     if (SL) {
         HIP_TRY(dslights.alloc((size_t)SL * 28));
         HIP_TRY(dunits.alloc((size_t)soft->nunits * 12));
-        HIP_TRY(dlit.alloc(n * SL * 4));
         HIP_TRY(hipMemcpy(dslights.p, sets ? sets->spherical.data() : soft->spherical, (size_t)SL * 28, hipMemcpyHostToDevice));
-        if (sets) Q.set_index = dsettab.as<uint32_t>() + 2 * ((size_t)nsets + 1);
         HIP_TRY(hipMemcpy(dunits.p, soft->unit_vectors, (size_t)soft->nunits * 12, hipMemcpyHostToDevice));
-        Q.lights = dslights.as<float>();
-        Q.units = dunits.as<float>();
-        Q.nlights = SL;
-        Q.samples = soft->samples;
-        Q.nunits = soft->nunits;
-        Q.seed = soft->seed;
+        Q = soft_dev(*soft, SL, dslights.as<float>(), dunits.as<float>());
+        if (sets) Q.set_index = dsettab.as<uint32_t>() + 2 * ((size_t)nsets + 1);
     }
-    const CameraDev C = (list || views) ? CameraDev{} : make_camera(*cam);
+    const CameraDev C = (list || views) ? CameraDev{} : make_camera(*R.cam);
     if (views) {  // (the table of the VIEWS kernels; this call waits for its frame, so the slot is free again when it returns)
         const std::vector<uint8_t> tab = view_table(views->cams, views->raycams, nviews);
         HIP_TRY(dviews.alloc(tab.size()));
@@ -2309,6 +2431,9 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         F.views = dviews.as<CameraDev>();  // (F.raycams: the same slot)
         Q.view_pixels = (uint32_t)W * (uint32_t)H;
     }
+    const float* const mats = static_cast<const float*>(s->d_materials);
+    const FrameConst K{mats, dlights.as<float>(), L, Q.lights, SL, ws.lit.as<uint32_t>(), Q.samples, frame_rgb, (unsigned long long)W * H};
+    const LevelDev V0 = ws.level(0);
     CgrtScene::RenderAux& aux = s->raux;  // second stream + the events that order it against the default stream
     if (!aux.pin_counts) {
         // The second stream carries the frame's critical path (level 0's mirror list, then all of level 1), the default stream the
@@ -2358,10 +2483,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipEventRecord(aux.caller, list->stream));
         HIP_TRY(hipStreamWaitEvent(nullptr, aux.caller, 0));
     }
-    const float* const mats = static_cast<const float*>(s->d_materials);
-    uint32_t* const primary_hits = dctr.as<uint32_t>() + 4 * (size_t)max_level + 3;
-    auto ctr_of = [&](int level) { return dctr.as<uint32_t>() + 4 * (size_t)level; };
-    auto lvl_of = [&](int level) { return levels.as<float>() + (size_t)level * n * 8; };
+    uint32_t* const primary_hits = ws.ctr_of(max_level) + 3;
     // ---- The frame as the previous frame of this shape predicts it ----
     // An interactive renderer draws the same scene again and again (main.cpp:776-797 re-renders on every camera change), and what
     // stands between the kernels of one frame is the HOST learning list lengths: a read-back and a round trip (~25-40 us of an
@@ -2380,30 +2502,20 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     auto predicted = [&]() -> int {
         const int np = (int)P.counts.size();  // levels the previous frame evaluated (P.counts[l] > 0 entries each)
         // {level 0's entries, level 1's entries}: one 64-bit word, filled by the primary kernel's fused spawn with one atomic
-        uint32_t* const pair = dctr.as<uint32_t>() + 4 * (size_t)max_level + 2;
-        auto count_of = [&](int level) { return level <= 1 ? pair + level : ctr_of(level - 1) + 1; };  // device word: entries of the level
+        uint32_t* const pair = ws.ctr_of(max_level) + 2;
+        auto count_of = [&](int level) { return level <= 1 ? pair + level : ws.ctr_of(level - 1) + 1; };  // device word: entries of the level
         auto cap_of = [&](int level) { return std::min<unsigned long long>(n, (unsigned long long)P.counts[level] + P.counts[level] / 8 + 1024); };
         HIP_TRY(hipEventRecord(aux.e0, nullptr));
-        HIP_TRY(hipMemsetAsync(dctr.p, 0, nctr * sizeof(uint32_t), nullptr));
+        HIP_TRY(hipMemsetAsync(ws.ctr.p, 0, nctr * sizeof(uint32_t), nullptr));
         // (level 0's spawn is done by the primary kernel itself, from the registers of the lanes that hit: spawn_rays.h)
-        SpawnDev SP{};
-        SP.materials = mats;
-        SP.lights = dlights.as<float>();
-        SP.nlights = L;
-        SP.spawn = 1 < max_level;
-        SP.srays = srays[0].as<float>();
-        SP.sdist = sdist[0].as<float>();
-        SP.sslot = sslot[0].as<int>();
-        SP.lvl = reinterpret_cast<float4*>(lvl_of(0));
-        SP.next_rays = rays[1].as<float>();
-        SP.next_pixels = pix[1].as<int>();
+        const SpawnDev SP = spawn_dev(V0, K);
         if (!aux.spawn_valid || std::memcmp(&SP, &aux.spawn_host, sizeof(SP)) != 0) {  // (the workspace keeps its addresses from frame to frame)
             HIP_TRY(hipMemcpy(dspawn.p, &SP, sizeof(SP), hipMemcpyHostToDevice));
             aux.spawn_host = SP;
             aux.spawn_valid = true;
         }
-        HIP_TRY(launch_trace_primary_compact(s->dev, C, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(),
-                                             pair, nullptr, nullptr, drgb.as<float>(), static_cast<const SpawnDev*>(dspawn.p)));
+        HIP_TRY(launch_trace_primary_compact(s->dev, C, F, V0.rays, V0.hits, V0.normals, V0.pixels, pair, nullptr, nullptr, K.rgb,
+                                             static_cast<const SpawnDev*>(dspawn.p)));
         if (const int frc = fill_planes()) return frc;
         const unsigned long long cap0 = cap_of(0);
         // Level 0's two lists.  With a fast tree they go out as ONE launch (k_trace_pair: workgroups dealt alternately) and the whole
@@ -2412,40 +2524,31 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         const bool paired = np >= 2 && L > 0 && can_trace_pair(s->dev);
         hipStream_t const side = paired ? nullptr : aux.s;  // where level 1 is evaluated
         bool tail_on_aux = false;
+        const LevelDev V1 = ws.level(1);
         if (paired) {
-            HIP_TRY(launch_trace_pair(s->dev, srays[0].as<float>(), sdist[0].as<float>(), cap0 * L, shits[0].as<CgrtHitDev>(), pair, L,
-                                      (unsigned long long)P.counts[0] * L, rays[1].as<float>(), cap_of(1), hits[1].as<CgrtHitDev>(), normals[1].as<float>(),
-                                      pair + 1, P.counts[1], nullptr));
+            HIP_TRY(launch_trace_pair(s->dev, V0.srays, V0.sdist, cap0 * L, V0.shits, pair, L, (unsigned long long)P.counts[0] * L, V1.rays, cap_of(1), V1.hits,
+                                      V1.normals, pair + 1, P.counts[1], nullptr));
         } else {
             HIP_TRY(hipEventRecord(aux.spawned, nullptr));
-            if (L)
-                HIP_TRY(launch_trace_shadow(s->dev, srays[0].as<float>(), sdist[0].as<float>(), cap0 * L, shits[0].as<CgrtHitDev>(), nullptr, pair,
-                                            nullptr, (unsigned long long)P.counts[0] * L, L));  // (hits x lights rays)
+            if (L)  // (hits x lights rays)
+                HIP_TRY(launch_trace_shadow(s->dev, V0.srays, V0.sdist, cap0 * L, V0.shits, nullptr, pair, nullptr, (unsigned long long)P.counts[0] * L, L));
         }
         if (np >= 2) {  // level 1 (and, unpaired, level 0's mirror list in front of it)
             const unsigned long long cap1 = cap_of(1);
             if (!paired) {
                 HIP_TRY(hipStreamWaitEvent(aux.s, aux.spawned, 0));
-                HIP_TRY(launch_trace_batch(s->dev, rays[1].as<float>(), cap1, hits[1].as<CgrtHitDev>(), normals[1].as<float>(), nullptr, aux.s, pair + 1,
-                                           P.counts[1]));
+                HIP_TRY(launch_trace_batch(s->dev, V1.rays, cap1, V1.hits, V1.normals, nullptr, aux.s, pair + 1, P.counts[1]));
             }
-            HIP_TRY(launch_spawn(rays[1].as<float>(), hits[1].as<CgrtHitDev>(), normals[1].as<float>(), pix[1].as<int>(), cap1, mats, dlights.as<float>(), L,
-                                 2 < max_level, srays[1].as<float>(), sdist[1].as<float>(), sslot[1].as<int>(), lvl_of(1), rays[2].as<float>(),
-                                 pix[2].as<int>(), ctr_of(1), side, pair + 1));
+            HIP_TRY(launch_spawn(V1, K, cap1, side, pair + 1));
             if (L)
-                HIP_TRY(launch_trace_shadow(s->dev, srays[1].as<float>(), sdist[1].as<float>(), cap1 * L, shits[1].as<CgrtHitDev>(), side, ctr_of(1) + 0,
-                                            nullptr, (unsigned long long)P.counts[1] * L));
-            HIP_TRY(launch_shade(rays[1].as<float>(), hits[1].as<CgrtHitDev>(), normals[1].as<float>(), shits[1].as<CgrtHitDev>(), sdist[1].as<float>(),
-                                 sslot[1].as<int>(), cap1, mats, dlights.as<float>(), L, dslights.as<float>(), 0, dlit.as<uint32_t>(), Q.samples, lvl_of(1),
-                                 side, pair + 1));
+                HIP_TRY(launch_trace_shadow(s->dev, V1.srays, V1.sdist, cap1 * L, V1.shits, side, V1.counters + 0, nullptr,
+                                            (unsigned long long)P.counts[1] * L));
+            HIP_TRY(launch_shade(V1, K, cap1, side, pair + 1));
             if (np >= 3)
-                HIP_TRY(launch_trace_batch(s->dev, rays[2].as<float>(), cap_of(2), hits[2].as<CgrtHitDev>(), normals[2].as<float>(), nullptr, side,
-                                           ctr_of(1) + 1, P.counts[2]));
+                HIP_TRY(launch_trace_batch(s->dev, V1.next_rays, cap_of(2), V1.next_hits, V1.next_normals, nullptr, side, V1.counters + 1, P.counts[2]));
             if (!paired) HIP_TRY(hipEventRecord(aux.traced, aux.s));
         }
-        HIP_TRY(launch_shade(rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), shits[0].as<CgrtHitDev>(), sdist[0].as<float>(),
-                             sslot[0].as<int>(), cap0, mats, dlights.as<float>(), L, dslights.as<float>(), 0, dlit.as<uint32_t>(), Q.samples, lvl_of(0), nullptr,
-                             pair));
+        HIP_TRY(launch_shade(V0, K, cap0, nullptr, pair));
         if (!paired) {
             // Two levels (the reference's depth, and most frames at any depth): the frame's last kernels are on the second stream, so
             // the scatter into the frame goes there too, behind level 0's shading -- which finished long before -- instead of the
@@ -2460,28 +2563,24 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         }
         hipStream_t const tail = tail_on_aux ? aux.s : nullptr;
         for (int level = 2; level < np; level++) {  // deeper levels: small, one after the other (buffer sets as in the exact path)
-            const int a = sets_for.of(level), b = sets_for.of(level + 1), q = level & 1;
+            const LevelDev V = ws.level(level);
             const unsigned long long cap = cap_of(level);
-            HIP_TRY(launch_spawn(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), pix[a].as<int>(), cap, mats, dlights.as<float>(), L,
-                                 level + 1 < max_level, srays[q].as<float>(), sdist[q].as<float>(), sslot[q].as<int>(), lvl_of(level), rays[b].as<float>(),
-                                 pix[b].as<int>(), ctr_of(level), nullptr, count_of(level)));
+            HIP_TRY(launch_spawn(V, K, cap, nullptr, count_of(level)));
             if (L)
-                HIP_TRY(launch_trace_shadow(s->dev, srays[q].as<float>(), sdist[q].as<float>(), cap * L, shits[q].as<CgrtHitDev>(), nullptr,
-                                            ctr_of(level) + 0, nullptr, (unsigned long long)P.counts[level] * L));
-            HIP_TRY(launch_shade(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(), sdist[q].as<float>(),
-                                 sslot[q].as<int>(), cap, mats, dlights.as<float>(), L, dslights.as<float>(), 0, dlit.as<uint32_t>(), Q.samples, lvl_of(level),
-                                 nullptr, count_of(level)));
+                HIP_TRY(launch_trace_shadow(s->dev, V.srays, V.sdist, cap * L, V.shits, nullptr, V.counters + 0, nullptr,
+                                            (unsigned long long)P.counts[level] * L));
+            HIP_TRY(launch_shade(V, K, cap, nullptr, count_of(level)));
             if (level + 1 < np)
-                HIP_TRY(launch_trace_batch(s->dev, rays[b].as<float>(), cap_of(level + 1), hits[b].as<CgrtHitDev>(), normals[b].as<float>(), nullptr, nullptr,
-                                           ctr_of(level) + 1, P.counts[level + 1]));
+                HIP_TRY(launch_trace_batch(s->dev, V.next_rays, cap_of(level + 1), V.next_hits, V.next_normals, nullptr, nullptr, V.counters + 1,
+                                           P.counts[level + 1]));
         }
-        for (int level = np - 2; level >= 1; level--) HIP_TRY(launch_fold(lvl_of(level), lvl_of(level + 1), cap_of(level), nullptr, count_of(level)));
-        HIP_TRY(launch_write_rgb(lvl_of(0), np >= 2 ? lvl_of(1) : nullptr, cap0, ipix.as<int>(), drgb.as<float>(), tail, pair));
+        for (int level = np - 2; level >= 1; level--) HIP_TRY(launch_fold(ws.level(level), cap_of(level), nullptr, count_of(level)));
+        HIP_TRY(launch_write_rgb(V0, K, np >= 2, cap0, tail, pair));
         HIP_TRY(resolve(tail));
         HIP_TRY(hipEventRecord(aux.e1, tail));
         HIP_TRY(hipEventSynchronize(aux.e1));
         std::vector<uint32_t> hc(nctr);
-        HIP_TRY(hipMemcpy(hc.data(), dctr.p, nctr * sizeof(uint32_t), hipMemcpyDeviceToHost));  // (waits for the frame)
+        HIP_TRY(hipMemcpy(hc.data(), ws.ctr.p, nctr * sizeof(uint32_t), hipMemcpyDeviceToHost));  // (waits for the frame)
         // ---- did every list fit its grid, and did the frame end where it was expected to? ----
         std::vector<uint32_t> actual;  // entries per level, levels with entries only
         bool fits = true;
@@ -2525,43 +2624,31 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
     }
     // A level's shading (k_shade into its level record; light sets: k_shade_sets into every set's colours of the level) and the scatter of
     // level 0 into the frame (k_write_rgb, folded with level 1 when with_child; light sets: k_write_rgb_sets, every set into its own frame).
-    auto shade = [&](int level, int a, int q, unsigned long long cnt, hipStream_t on, const uint32_t* dc) -> hipError_t {
-        if (sets)
-            return launch_shade_sets(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(), sdist[q].as<float>(),
-                                     sslot[q].as<int>(), cnt, mats, L, SL, dlit.as<uint32_t>(), Q.samples, T, sets_of(level), n, on, dc);
-        return launch_shade(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(), sdist[q].as<float>(),
-                            sslot[q].as<int>(), cnt, mats, dlights.as<float>(), L, dslights.as<float>(), SL, dlit.as<uint32_t>(), Q.samples, lvl_of(level),
-                            on, dc);
+    auto shade = [&](const LevelDev& V, unsigned long long cnt, hipStream_t on, const uint32_t* dc) -> hipError_t {
+        return sets ? launch_shade_sets(V, K, T, cnt, on, dc) : launch_shade(V, K, cnt, on, dc);
     };
-    auto write_rgb = [&](bool with_child, unsigned long long cnt, float* frame) -> hipError_t {
-        if (sets && views)  // (frame (view, set) at view * nsets + set)
-            return launch_write_rgb_views_sets(lvl_of(0), sets_of(0), with_child ? sets_of(1) : nullptr, cnt, n, nsets, ipix.as<int>(), frame,
-                                               (unsigned long long)W * H, nullptr);
-        if (sets)
-            return launch_write_rgb_sets(lvl_of(0), sets_of(0), with_child ? sets_of(1) : nullptr, cnt, n, nsets, ipix.as<int>(), frame,
-                                         (unsigned long long)W * H, nullptr);
-        return launch_write_rgb(lvl_of(0), with_child ? lvl_of(1) : nullptr, cnt, ipix.as<int>(), frame, nullptr);
+    auto write_rgb = [&](bool with_child, unsigned long long cnt) -> hipError_t {
+        if (sets) return launch_write_rgb_sets(V0, K, views != nullptr, with_child, cnt, nullptr);  // (views: frame (view, set) at view * nsets + set)
+        return launch_write_rgb(V0, K, with_child, cnt, nullptr);
     };
     auto exact = [&]() -> int {
         HIP_TRY(hipEventRecord(aux.e0, nullptr));
         int nlev = 0;
         bool finished = false;  // the frame's last kernels and its closing event have been issued inside the level loop
         std::vector<unsigned long long> level_count;  // entries per evaluated level
-        HIP_TRY(hipMemsetAsync(dctr.p, 0, nctr * sizeof(uint32_t), nullptr));
+        HIP_TRY(hipMemsetAsync(ws.ctr.p, 0, nctr * sizeof(uint32_t), nullptr));
         if (max_level >= 1) {  // trace(level 0): main.cpp:267 returns black without tracing when level >= maxLevel
             // level 0 = the primary rays that hit something, straight out of the fused primary kernel (pixels that miss are
             // black, main.cpp:293, and spawn nothing)
             if (list) {  // (also clears the list's colours)
-                HIP_TRY(launch_trace_list_compact(s->dev, list->rays, n, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
-                                                  ipix.as<int>(), primary_hits, frame_rgb, nullptr, cw_primary));
+                HIP_TRY(launch_trace_list_compact(s->dev, list->rays, n, V0.rays, V0.hits, V0.normals, V0.pixels, primary_hits, frame_rgb, nullptr, cw_primary));
                 st.primary_rays = n;
             } else if (views) {  // (also clears every view's pixels)
-                HIP_TRY(launch_trace_primary_views_compact(s->dev, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(),
-                                                           primary_hits, frame_rgb, nullptr, views->raycams != nullptr));
+                HIP_TRY(launch_trace_primary_views_compact(s->dev, F, V0.rays, V0.hits, V0.normals, V0.pixels, primary_hits, frame_rgb, nullptr,
+                                                           views->raycams != nullptr));
                 st.primary_rays = (unsigned long long)W * H * nviews;
-            } else {
-                HIP_TRY(launch_trace_primary_compact(s->dev, C, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
-                                                     ipix.as<int>(), primary_hits, nullptr, cw_primary, frame_rgb));  // (also clears this rank's pixels)
+            } else {  // (also clears this rank's pixels)
+                HIP_TRY(launch_trace_primary_compact(s->dev, C, F, V0.rays, V0.hits, V0.normals, V0.pixels, primary_hits, nullptr, cw_primary, frame_rgb));
                 st.primary_rays = owned_pixels(F);
             }
             if (const int frc = fill_planes()) return frc;
@@ -2574,9 +2661,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             // (behind the primary kernel only) to size the traversal launches that follow -- the host round trip (~25 us of an idle
             // GPU per frame, profiles/r3_config3_timeline.txt) now overlaps the spawn kernel.
             HIP_TRY(hipEventRecord(aux.primary_done, nullptr));
-            HIP_TRY(launch_spawn(rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(), n, mats, dlights.as<float>(), L,
-                                 1 < max_level, srays[0].as<float>(), sdist[0].as<float>(), sslot[0].as<int>(), levels.as<float>(), rays[1].as<float>(),
-                                 pix[1].as<int>(), dctr.as<uint32_t>(), nullptr, primary_hits));
+            HIP_TRY(launch_spawn(V0, K, n, nullptr, primary_hits));
             // (Issuing level 0's shadow list here too, over its capacity n * L, was measured: Cornell 0.182 -> 0.179 ms, but the dragon
             // frame 0.46 -> 0.50 ms -- a grid of 32 K workgroups for 318 K rays costs more than the round trip it saves.  It is sized
             // exactly after the read-back, and issued FIRST: it used to start 64 us after the spawn kernel ended, behind the second
@@ -2589,15 +2674,10 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             aov_entries = cnt;
             int level = 0;
             while (level < max_level && cnt > 0) {
-                const int a = sets_for.of(level), b = sets_for.of(level + 1), q = level & 1;  // this level's buffer set, the next level's, this level's shadow set
-                const int spawn = level + 1 < max_level;
-                const int* cur_pix = level == 0 ? ipix.as<int>() : pix[a].as<int>();
-                uint32_t* ctr = dctr.as<uint32_t>() + 4 * (size_t)level;
-                float* lvl = levels.as<float>() + (size_t)level * n * 8;
-                if (level > 0)  // (level 0's spawn is already in flight, see above)
-                    HIP_TRY(launch_spawn(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), cur_pix, cnt, mats, dlights.as<float>(), L,
-                                         spawn, srays[q].as<float>(), sdist[q].as<float>(), sslot[q].as<int>(), lvl, rays[b].as<float>(), pix[b].as<int>(),
-                                         ctr, nullptr));
+                const LevelDev V = ws.level(level);
+                const int spawn = V.spawn;
+                uint32_t* const ctr = V.counters;
+                if (level > 0) HIP_TRY(launch_spawn(V, K, cnt, nullptr));  // (level 0's spawn is already in flight, see above)
                 // Level 0's mirror batch runs on the second stream, beside level 0's shadow batch (two batches of a few hundred
                 // thousand rays each; its grid covers the list's capacity -- one mirror ray per entry -- and the kernel stops at the
                 // appended count).  Without spherical lights the whole of level 1 follows it there -- spawn, shadow list, shading,
@@ -2605,40 +2685,29 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                 // level 1's tail overlaps level 0's.  Deeper levels are small and often empty: they run one after the other,
                 // exactly sized after each level's read-back, or not at all.
                 // the level's shadow list first: the long pole of the default stream must not wait behind the second stream's launches
-                if (L)
-                    HIP_TRY(launch_trace_shadow(s->dev, srays[q].as<float>(), sdist[q].as<float>(), cnt * L, shits[q].as<CgrtHitDev>(), nullptr, ctr + 0,
-                                                cw_shadow));
+                if (L) HIP_TRY(launch_trace_shadow(s->dev, V.srays, V.sdist, cnt * L, V.shits, nullptr, ctr + 0, cw_shadow));
                 const bool overlap = spawn && level == 0;
                 const bool pipelined = overlap && SL == 0;
                 const int spawn1 = 2 < max_level;
-                uint32_t* const ctr1 = dctr.as<uint32_t>() + 4;
                 if (overlap) {  // (level 0: aux.spawned was recorded right behind the spawn kernel)
                     HIP_TRY(hipStreamWaitEvent(aux.s, aux.spawned, 0));
-                    HIP_TRY(launch_trace_batch(s->dev, rays[b].as<float>(), cnt, hits[b].as<CgrtHitDev>(), normals[b].as<float>(), cw_mirror, aux.s,
-                                               ctr + 1));
+                    HIP_TRY(launch_trace_batch(s->dev, V.next_rays, cnt, V.next_hits, V.next_normals, cw_mirror, aux.s, ctr + 1));
                     if (pipelined) {
-                        const int a1 = b, b1 = 2, q1 = 1;
-                        float* lvl1 = levels.as<float>() + (size_t)n * 8;
-                        HIP_TRY(launch_spawn(rays[a1].as<float>(), hits[a1].as<CgrtHitDev>(), normals[a1].as<float>(), pix[a1].as<int>(), cnt, mats,
-                                             dlights.as<float>(), L, spawn1, srays[q1].as<float>(), sdist[q1].as<float>(), sslot[q1].as<int>(), lvl1,
-                                             rays[b1].as<float>(), pix[b1].as<int>(), ctr1, aux.s, ctr + 1));
-                        if (L)
-                            HIP_TRY(launch_trace_shadow(s->dev, srays[q1].as<float>(), sdist[q1].as<float>(), cnt * L, shits[q1].as<CgrtHitDev>(), aux.s,
-                                                        ctr1 + 0, cw_shadow));
-                        HIP_TRY(shade(1, a1, q1, cnt, aux.s, ctr + 1));
+                        const LevelDev V1 = ws.level(1);
+                        HIP_TRY(launch_spawn(V1, K, cnt, aux.s, ctr + 1));
+                        if (L) HIP_TRY(launch_trace_shadow(s->dev, V1.srays, V1.sdist, cnt * L, V1.shits, aux.s, V1.counters + 0, cw_shadow));
+                        HIP_TRY(shade(V1, cnt, aux.s, ctr + 1));
                         if (spawn1)
-                            HIP_TRY(launch_trace_batch(s->dev, rays[b1].as<float>(), cnt, hits[b1].as<CgrtHitDev>(), normals[b1].as<float>(), cw_mirror,
-                                                       aux.s, ctr1 + 1));
+                            HIP_TRY(launch_trace_batch(s->dev, V1.next_rays, cnt, V1.next_hits, V1.next_normals, cw_mirror, aux.s, V1.counters + 1));
                     }
                     HIP_TRY(hipEventRecord(aux.traced, aux.s));
                 }
                 if (SL) {
                     Q.level = (uint32_t)level;
-                    HIP_TRY(hipMemsetAsync(dlit.p, 0, cnt * SL * 4, nullptr));
-                    HIP_TRY(launch_soft_shadow(s->dev, Q, rays[a].as<float>(), hits[a].as<CgrtHitDev>(), cur_pix, cnt, dlit.as<uint32_t>(),
-                                               soft->closest_hit == 0, nullptr));
+                    HIP_TRY(hipMemsetAsync(ws.lit.p, 0, cnt * SL * 4, nullptr));
+                    HIP_TRY(launch_soft_shadow(s->dev, Q, V.rays, V.hits, V.pixels, cnt, ws.lit.as<uint32_t>(), soft->closest_hit == 0, nullptr));
                 }
-                HIP_TRY(shade(level, a, q, cnt, nullptr, nullptr));
+                HIP_TRY(shade(V, cnt, nullptr, nullptr));
                 if (overlap) HIP_TRY(hipStreamWaitEvent(nullptr, aux.traced, 0));  // the next level (and the end of the frame) need the second stream's results
                 nlev = level + 1;
                 level_count.push_back(cnt);
@@ -2647,7 +2716,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                     // on their counts -- the frame is finished without a host round trip (an entry of level 0 without a mirror ray
                     // carries child = -1, so the scatter kernel can fold with level 1 whether or not level 1 has entries); the
                     // counts are read after the frame's closing event.
-                    HIP_TRY(write_rgb(true, cnt, frame_rgb));
+                    HIP_TRY(write_rgb(true, cnt));
                     HIP_TRY(resolve(nullptr));
                     finished = true;
                     HIP_TRY(hipEventRecord(aux.e1, nullptr));
@@ -2678,8 +2747,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
                     level = 2;
                     continue;
                 }
-                if (!overlap)
-                    HIP_TRY(launch_trace_batch(s->dev, rays[b].as<float>(), h[1], hits[b].as<CgrtHitDev>(), normals[b].as<float>(), cw_mirror, nullptr));
+                if (!overlap) HIP_TRY(launch_trace_batch(s->dev, V.next_rays, h[1], V.next_hits, V.next_normals, cw_mirror, nullptr));
                 cnt = h[1];
                 level += 1;
             }
@@ -2695,13 +2763,10 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             // color = directColor + reflectedColor * ks (main.cpp:262), deepest level first; the last fold (level 0 with level 1) is
             // done by the kernel that scatters level 0 over the frame
             for (int level = nlev - 2; level >= 1; level--) {
-                if (sets)
-                    HIP_TRY(launch_fold_sets(lvl_of(level), sets_of(level), sets_of(level + 1), level_count[level], n, nsets, nullptr));
-                else
-                    HIP_TRY(launch_fold(levels.as<float>() + (size_t)level * n * 8, levels.as<float>() + (size_t)(level + 1) * n * 8, level_count[level],
-                                        nullptr));
+                const LevelDev V = ws.level(level);
+                HIP_TRY(sets ? launch_fold_sets(V, level_count[level], nullptr) : launch_fold(V, level_count[level], nullptr));
             }
-            HIP_TRY(write_rgb(nlev >= 2, level_count[0], frame_rgb));
+            HIP_TRY(write_rgb(nlev >= 2, level_count[0]));
         }
         if (!finished) {
             HIP_TRY(resolve(nullptr));
@@ -2733,13 +2798,12 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipStreamWaitEvent(list->stream, aux.e1, 0));
     } else if (dout) {
         // The frame's last kernel is done (aux.e1 was waited for); the wait below only makes that ordering explicit on the caller's stream.
-        const ExportDev E = export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, (views || sets) ? nviews * nsets : 0u, aa, rank,
+        const ExportDev E = export_of(F, aa ? ws.resolved.as<float>() : ws.rgb.as<float>(), *dout, PW, PH, (views || sets) ? nviews * nsets : 0u, aa, rank,
                                       nranks, packed);
         if (!s->export_done) HIP_TRY(hipEventCreateWithFlags(&s->export_done, hipEventDisableTiming));
         HIP_TRY(hipStreamWaitEvent(dout->stream, aux.e1, 0));
         if (aov) {  // (level 0 of the frame that was kept is in set 0, untouched since its primary kernel; aux.e1 has been waited for)
-            HIP_TRY(launch_aov_scatter(A, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(), mats, aov_entries,
-                                       aux.fill));
+            HIP_TRY(launch_aov_scatter(A, V0, mats, aov_entries, aux.fill));
             HIP_TRY(hipEventRecord(aux.filled, aux.fill));
         }
         HIP_TRY(launch_export_frame(E, dout->stream));
@@ -2747,7 +2811,7 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipEventRecord(s->export_done, dout->stream));
         s->export_pending = true;
     } else {
-        const size_t bytes = aa ? res_bytes : (size_t)npix * 12;
+        const size_t bytes = aa ? S.res_bytes : (size_t)npix * 12;
         if (s->pin_frame_cap < bytes) {
             if (s->pin_frame) (void)hipHostFree(s->pin_frame);
             s->pin_frame = nullptr;
@@ -2755,10 +2819,10 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
             HIP_TRY(hipHostMalloc(&s->pin_frame, bytes, hipHostMallocDefault));
             s->pin_frame_cap = bytes;
         }
-        HIP_TRY(hipMemcpyAsync(s->pin_frame, aa ? dres.p : drgb.p, bytes, hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipMemcpyAsync(s->pin_frame, aa ? ws.resolved.p : ws.rgb.p, bytes, hipMemcpyDeviceToHost, nullptr));
         HIP_TRY(hipStreamSynchronize(nullptr));
         const float* pin = static_cast<const float*>(s->pin_frame);
-        if (mapped) *mapped = pin;
+        if (R.mapped) *R.mapped = pin;
         if (rgb && nranks == 1) {
             parallel_copy(rgb, pin, bytes);
         } else if (rgb && aa) {  // this rank's 32x32 pixel blocks, packed by k_resolve_aa
@@ -2782,34 +2846,46 @@ static int render_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const 
         HIP_TRY(hipMemcpy(h, dwork.p, sizeof(h), hipMemcpyDeviceToHost));
         for (int k = 0; k < 3; k++) {
             const unsigned long long* q = h + 8 * k;
-            counted[k] = CgrtCounters{q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]};
+            R.counted[k] = CgrtCounters{q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]};
         }
     }
-    if (stats) *stats = st;
+    if (R.stats) *R.stats = st;
     return CGRT_OK;
 }
 
+// a request with where its driver reports: a blocking frame's stats, an enqueued frame's ticket
+static int render_frame(CgrtScene* s, FrameRequest R, CgrtRenderStats* stats) {
+    R.stats = stats;
+    return render_impl(s, R);
+}
 int cgrt_render(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, int max_level, float* rgb,
                 CgrtRenderStats* stats) {
-    return render_impl(s, cam, W, H, lights, nlights, nullptr, max_level, 0, 1, rgb, stats);
+    return cgrt_render_rank(s, cam, W, H, lights, nlights, nullptr, max_level, 0, 1, rgb, stats);
 }
 int cgrt_render_counted(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, int max_level, float* rgb,
                         CgrtRenderStats* stats, CgrtCounters* work3) {
     if (!work3) return fail(CGRT_E_ARG, "work3 is NULL");
-    return render_impl(s, cam, W, H, lights, nlights, nullptr, max_level, 0, 1, rgb, stats, work3);
+    FrameRequest R;
+    R.cam = cam, R.W = W, R.H = H, R.lights = lights, R.nlights = nlights, R.max_level = max_level, R.rgb = rgb, R.stats = stats, R.counted = work3;
+    return render_impl(s, R);
 }
 int cgrt_render_soft(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                      int max_level, float* rgb, CgrtRenderStats* stats) {
-    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, 0, 1, rgb, stats);
+    return cgrt_render_rank(s, cam, W, H, lights, nlights, soft, max_level, 0, 1, rgb, stats);
 }
 int cgrt_render_mapped(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, const float** rgb, CgrtRenderStats* stats) {
     if (!rgb) return fail(CGRT_E_ARG, "rgb is NULL");
-    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, rgb);
+    FrameRequest R;
+    R.cam = cam, R.W = W, R.H = H, R.lights = lights, R.nlights = nlights, R.soft = soft, R.max_level = max_level, R.mapped = rgb, R.stats = stats;
+    return render_impl(s, R);
 }
 int cgrt_render_rank(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                      int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats) {
-    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, rgb, stats);
+    FrameRequest R;
+    R.cam = cam, R.W = W, R.H = H, R.lights = lights, R.nlights = nlights, R.soft = soft, R.max_level = max_level, R.rank = rank, R.nranks = nranks;
+    R.rgb = rgb, R.stats = stats;
+    return render_impl(s, R);
 }
 
 // The anti-aliased entries check every argument before any device work (a host-only scene: CGRT_E_NO_DEVICE after the rest).
@@ -2821,10 +2897,7 @@ static int aa_args(const CgrtCamera* cam, const void* out, int W, int H, const f
     if (4ull * (unsigned long long)W * (unsigned long long)H > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large: 4*W*H sub-samples exceed 0x7fffffff");
     if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
     if (nranks <= 0 || rank < 0 || rank >= nranks) return fail(CGRT_E_ARG, "bad rank / nranks");
-    if (soft && soft->nspherical &&
-        (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
-        return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
-    return CGRT_OK;
+    return soft_rules(soft);
 }
 int cgrt_render_aa(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                    int max_level, int rank, int nranks, float* rgb, CgrtRenderStats* stats) {
@@ -2832,7 +2905,10 @@ int cgrt_render_aa(CgrtScene* s, const CgrtCamera* cam, int W, int H, const floa
     const int rc = aa_args(cam, rgb, W, H, lights, nlights, soft, max_level, rank, nranks);
     if (rc) return rc;
     NEED_DEVICE(s);
-    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, rgb, stats, nullptr, nullptr, true);
+    FrameRequest R;
+    R.cam = cam, R.W = W, R.H = H, R.lights = lights, R.nlights = nlights, R.soft = soft, R.max_level = max_level, R.rank = rank, R.nranks = nranks;
+    R.aa = true, R.rgb = rgb, R.stats = stats;
+    return render_impl(s, R);
 }
 int cgrt_render_aa_mapped(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                           int max_level, const float** rgb, CgrtRenderStats* stats) {
@@ -2840,7 +2916,10 @@ int cgrt_render_aa_mapped(CgrtScene* s, const CgrtCamera* cam, int W, int H, con
     const int rc = aa_args(cam, rgb, W, H, lights, nlights, soft, max_level, 0, 1);
     if (rc) return rc;
     NEED_DEVICE(s);
-    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, rgb, true);
+    FrameRequest R;
+    R.cam = cam, R.W = W, R.H = H, R.lights = lights, R.nlights = nlights, R.soft = soft, R.max_level = max_level, R.aa = true, R.mapped = rgb;
+    R.stats = stats;
+    return render_impl(s, R);
 }
 
 // The frame export's own arguments (cgrt_render_device, cgrt_debug_export_frame; W, H > 0 already checked): *pitch = the row pitch,
@@ -2927,11 +3006,8 @@ static int render_device_args(CgrtScene* s, const CgrtCamera* cam, int W, int H,
         if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
         if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
         if (nranks <= 0 || rank < 0 || rank >= nranks) return fail(CGRT_E_ARG, "bad rank / nranks");
-        if (soft && soft->nspherical) {
-            if (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24))
-                return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
-            if ((unsigned long long)W * H > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large");
-        }
+        if (const int rc = soft_rules(soft)) return rc;
+        if (soft && soft->nspherical && (unsigned long long)W * H > 0x7fffffffull) return fail(CGRT_E_ARG, "frame too large");
     }
     uint64_t extent = 0;
     int rc = export_args(d_out, W, H, format, row_bytes, pitch, &extent);
@@ -2942,13 +3018,21 @@ static int render_device_args(CgrtScene* s, const CgrtCamera* cam, int W, int H,
     if ((rc = check_device_span(s, d_out, extent, "d_out"))) return rc;
     return with_aov ? aov_spans(s, aov, (uint64_t)W * (uint64_t)H * (aa ? 4u : 1u)) : CGRT_OK;
 }
+// the request of the single-camera device entries, blocking and enqueued (D: filled by render_device_args)
+static FrameRequest device_request(const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft, int max_level,
+                                   int aa, int rank, int nranks, const DeviceOut* D, const CgrtAovOut* aov = nullptr) {
+    FrameRequest R;
+    R.cam = cam, R.W = W, R.H = H, R.lights = lights, R.nlights = nlights, R.soft = soft, R.max_level = max_level, R.rank = rank, R.nranks = nranks;
+    R.aa = aa != 0, R.dout = D, R.aov = aov, R.stream = D->stream;
+    return R;
+}
 int cgrt_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                        int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
                        CgrtRenderStats* stats) {
     DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream)};
     const int rc = render_device_args(s, cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, d_out, format, row_bytes, &D.pitch);
     if (rc) return rc;
-    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, nullptr, stats, nullptr, nullptr, aa != 0, &D);
+    return render_frame(s, device_request(cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, &D), stats);
 }
 int cgrt_render_aov_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                            int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
@@ -2956,8 +3040,7 @@ int cgrt_render_aov_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, co
     DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream)};
     const int rc = render_device_args(s, cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, d_out, format, row_bytes, &D.pitch, true, aov);
     if (rc) return rc;
-    return render_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, nullptr, stats, nullptr, nullptr, aa != 0, &D, nullptr, nullptr,
-                       nullptr, aov);
+    return render_frame(s, device_request(cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, &D, aov), stats);
 }
 
 // ---- renderRayTracing's per-pixel loop for a batch of cameras (render_impl, ViewSrc; include/cgrt.h cgrt_render_views*) ----
@@ -2969,10 +3052,15 @@ static int render_views_args(const CgrtScene* s, const void* cams, uint32_t nvie
     const int rc = views_args(cams, nviews, W, H, ray);
     if (rc) return rc;
     if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
-    if (soft && soft->nspherical &&
-        (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
-        return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
-    return CGRT_OK;
+    return soft_rules(soft);
+}
+// the request of the views entries, blocking and enqueued (V: the batch; D: NULL, or filled by render_views_device_args)
+static FrameRequest views_request(const ViewSrc* V, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft, int max_level,
+                                  const DeviceOut* D = nullptr, const CgrtAovOut* aov = nullptr) {
+    FrameRequest R;
+    R.views = V, R.W = W, R.H = H, R.lights = lights, R.nlights = nlights, R.soft = soft, R.max_level = max_level, R.dout = D, R.aov = aov;
+    if (D) R.stream = D->stream;
+    return R;
 }
 int cgrt_render_views(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
                       const CgrtSoftShadows* soft, int max_level, float* rgb, CgrtRenderStats* stats) {
@@ -2980,7 +3068,9 @@ int cgrt_render_views(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int
     if (rc) return rc;
     NEED_DEVICE(s);
     const ViewSrc V{cams, nviews};
-    return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, rgb, stats, nullptr, nullptr, false, nullptr, nullptr, &V);
+    FrameRequest R = views_request(&V, W, H, lights, nlights, soft, max_level);
+    R.rgb = rgb, R.stats = stats;
+    return render_impl(s, R);
 }
 // cgrt_render_views_device's checks (cgrt_enqueue_render_views_device: the same); D->pitch and D->view_bytes are set
 // (ray: the cameras are ray cameras, `cams` the same pointer)
@@ -3004,7 +3094,7 @@ int cgrt_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nvie
     const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D);
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
-    return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, &D, nullptr, &V);
+    return render_frame(s, views_request(&V, W, H, lights, nlights, soft, max_level, &D), stats);
 }
 int cgrt_render_views_aov_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
                                  const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats,
@@ -3013,7 +3103,7 @@ int cgrt_render_views_aov_device(CgrtScene* s, const CgrtCamera* cams, uint32_t 
     const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D, true, aov);
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
-    return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, &D, nullptr, &V, nullptr, aov);
+    return render_frame(s, views_request(&V, W, H, lights, nlights, soft, max_level, &D, aov), stats);
 }
 
 // ---- one camera under a batch of light sets (render_impl, LightSetSrc; include/cgrt.h cgrt_render_light_sets*) ----
@@ -3056,14 +3146,24 @@ static int light_sets_args(const CgrtScene* s, const CgrtCamera* cam, int W, int
     plan_light_sets(*sets, *P);
     return sets_bounds(px, *P, soft);
 }
+// the request of the light-set entries, blocking and enqueued (V: NULL or the batch of views; P: the checked plan; D: NULL or filled)
+static FrameRequest sets_request(const CgrtCamera* cam, const ViewSrc* V, int W, int H, const LightSetSrc& P, const CgrtSoftShadows* soft, int max_level,
+                                 const DeviceOut* D = nullptr) {
+    FrameRequest R;
+    R.cam = cam, R.views = V, R.W = W, R.H = H, R.soft = soft, R.max_level = max_level, R.dout = D;
+    R.use_sets(P);
+    if (D) R.stream = D->stream;
+    return R;
+}
 int cgrt_render_light_sets(CgrtScene* s, const CgrtCamera* cam, int W, int H, const CgrtLightSets* sets, const CgrtSoftShadows* soft, int max_level,
                            float* rgb, CgrtRenderStats* stats) {
     LightSetSrc P;
     const int rc = light_sets_args(s, cam, W, H, sets, soft, max_level, rgb, &P);
     if (rc) return rc;
     NEED_DEVICE(s);
-    return render_impl(s, cam, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, rgb, stats, nullptr, nullptr, false,
-                       nullptr, nullptr, nullptr, &P);
+    FrameRequest R = sets_request(cam, nullptr, W, H, P, soft, max_level);
+    R.rgb = rgb, R.stats = stats;
+    return render_impl(s, R);
 }
 int cgrt_render_light_sets_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const CgrtLightSets* sets, const CgrtSoftShadows* soft,
                                   int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats) {
@@ -3077,8 +3177,7 @@ int cgrt_render_light_sets_device(CgrtScene* s, const CgrtCamera* cam, int W, in
     NEED_DEVICE(s);
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = check_device_span(s, d_out, extent * P.nsets, "d_out"))) return rc;
-    return render_impl(s, cam, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false,
-                       &D, nullptr, nullptr, &P);
+    return render_frame(s, sets_request(cam, nullptr, W, H, P, soft, max_level, &D), stats);
 }
 
 // ---- nviews cameras under a batch of light sets (render_impl / enqueue_impl with a ViewSrc and a LightSetSrc; include/cgrt.h
@@ -3121,8 +3220,9 @@ int cgrt_render_views_light_sets(CgrtScene* s, const CgrtCamera* cams, uint32_t 
     if (rc) return rc;
     NEED_DEVICE(s);
     const ViewSrc V{cams, nviews};
-    return render_impl(s, nullptr, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, rgb, stats, nullptr, nullptr, false,
-                       nullptr, nullptr, &V, &P);
+    FrameRequest R = sets_request(nullptr, &V, W, H, P, soft, max_level);
+    R.rgb = rgb, R.stats = stats;
+    return render_impl(s, R);
 }
 int cgrt_render_views_light_sets_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
                                         const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats) {
@@ -3131,8 +3231,7 @@ int cgrt_render_views_light_sets_device(CgrtScene* s, const CgrtCamera* cams, ui
     const int rc = views_light_sets_device_args(s, cams, nviews, W, H, sets, soft, max_level, d_out, format, &P, &D);
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
-    return render_impl(s, nullptr, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false,
-                       &D, nullptr, &V, &P);
+    return render_frame(s, sets_request(nullptr, &V, W, H, P, soft, max_level, &D), stats);
 }
 
 // ---- ray cameras (include/cgrt.h CgrtRayCamera): the views entries with a ViewSrc that carries ray cameras ----
@@ -3143,7 +3242,7 @@ int cgrt_render_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t
     const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D, aov != nullptr, aov, cams);
     if (rc) return rc;
     const ViewSrc V{nullptr, nviews, cams};
-    return render_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, &D, nullptr, &V, nullptr, aov);
+    return render_frame(s, views_request(&V, W, H, lights, nlights, soft, max_level, &D, aov), stats);
 }
 int cgrt_render_raycams_light_sets_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
                                           const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, CgrtRenderStats* stats) {
@@ -3152,8 +3251,7 @@ int cgrt_render_raycams_light_sets_device(CgrtScene* s, const CgrtRayCamera* cam
     const int rc = views_light_sets_device_args(s, cams, nviews, W, H, sets, soft, max_level, d_out, format, &P, &D, cams);
     if (rc) return rc;
     const ViewSrc V{nullptr, nviews, cams};
-    return render_impl(s, nullptr, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false,
-                       &D, nullptr, &V, &P);
+    return render_frame(s, sets_request(nullptr, &V, W, H, P, soft, max_level, &D), stats);
 }
 
 // ---- getFinalColor of the caller's rays (main.cpp:298-310): level 0 of the wavefront from a ray list (render_impl, ListSrc) ----
@@ -3163,11 +3261,15 @@ static int shade_rays_args(const CgrtScene* s, const void* rays, uint64_t n, con
     if (!s || !rgb || (n > 0 && !rays) || (nlights && !lights)) return fail(CGRT_E_ARG, "NULL argument");
     if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many rays: n exceeds 0x7fffffff");
     if (max_level < 0 || max_level > 16) return fail(CGRT_E_ARG, "bad recursion depth");
-    if (soft && soft->nspherical &&
-        (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
-        return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
+    if (const int rc = soft_rules(soft)) return rc;
     NEED_DEVICE(s);
     return CGRT_OK;
+}
+// the request of the ray-list entries, blocking and enqueued (stream: where the ticket of an enqueued list goes)
+static FrameRequest list_request(const ListSrc* src, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft, int max_level) {
+    FrameRequest R;
+    R.list = src, R.lights = lights, R.nlights = nlights, R.soft = soft, R.max_level = max_level, R.stream = src->stream;
+    return R;
 }
 // cgrt_shade_rays_device's checks (cgrt_enqueue_shade_rays_device: the same); n == 0 needs no buffers
 static int shade_rays_device_args(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
@@ -3188,7 +3290,7 @@ int cgrt_shade_rays_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, cons
         return CGRT_OK;
     }
     const ListSrc src{reinterpret_cast<const float*>(d_rays), n, d_rgb, static_cast<hipStream_t>(stream)};
-    return render_impl(s, nullptr, 1, 1, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, nullptr, &src);
+    return render_frame(s, list_request(&src, lights, nlights, soft, max_level), stats);
 }
 int cgrt_shade_rays(CgrtScene* s, const CgrtRay* rays, uint64_t n, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                     int max_level, float* rgb, CgrtRenderStats* stats) {
@@ -3207,7 +3309,7 @@ int cgrt_shade_rays(CgrtScene* s, const CgrtRay* rays, uint64_t n, const float* 
     HIP_TRY(g.dev(1, n * 12, &dc));
     HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
     const ListSrc src{static_cast<const float*>(dr), n, static_cast<float*>(dc), g.L->stream};
-    rc = render_impl(s, nullptr, 1, 1, lights, nlights, soft, max_level, 0, 1, nullptr, stats, nullptr, nullptr, false, nullptr, &src);
+    rc = render_frame(s, list_request(&src, lights, nlights, soft, max_level), stats);
     if (rc) return rc;
     void* staged = nullptr;
     HIP_TRY(lane_download(g, 1, rgb, dc, n * 12, &staged));
@@ -3219,32 +3321,27 @@ int cgrt_shade_rays(CgrtScene* s, const CgrtRay* rays, uint64_t n, const float* 
 // ---- enqueued frames (include/cgrt.h cgrt_enqueue_*) ----
 // The frame of render_impl's exact path, issued without a host round trip: every list is sized for the worst case (as render_impl
 // sizes the workspace anyway), all max_level levels are issued, and every launch after the primary kernel is a capped, count-driven grid
-// (the *_strided launchers) that reads its list's length on the device.  A single camera's level 0 is spawned by the primary kernel
+// (GRID_STRIDED and the *_strided launchers) that reads its list's length on the device.  A single camera's level 0 is spawned by the primary kernel
 // itself (the predicted frame's fused spawn); views and ray lists run their own primary kernels and a count-driven spawn.  The whole
 // frame, export included, is on the caller's stream, behind the scene's previous frames (enq_done, export_done), and nothing is waited
 // for on the host unless the workspace grows or every ticket slot is in flight.  Same kernels' expressions on the same entries, each
 // scattered back by its pixel: the bytes are the blocking entry's.  The caller has checked the arguments (the blocking entries' checks).
-static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
-                        int max_level, int rank, int nranks, bool aa, const DeviceOut* dout, const ListSrc* list, const ViewSrc* views,
-                        hipStream_t stream, uint64_t* ticket, const LightSetSrc* sets = nullptr, const CgrtAovOut* aov = nullptr) {
-    const int PW = W, PH = H;
-    if (aa) {
-        W *= 2;
-        H *= 2;
-    }
+static int enqueue_impl(CgrtScene* s, const FrameRequest& R) {
+    const ListSrc* const list = R.list;
+    const ViewSrc* const views = R.views;
+    const LightSetSrc* const sets = R.sets;  // (light sets: always with views; frame (view, set) is frame view * nsets + set)
+    const CgrtSoftShadows* const soft = R.soft;
+    const int max_level = R.max_level;
+    hipStream_t const stream = R.stream;
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> one_frame(s->render_mutex);
-    const uint32_t nviews = views ? views->n : 1u;
-    const uint32_t nsets = sets ? sets->nsets : 1u;  // (light sets: always with views; frame (view, set) is frame view * nsets + set)
-    const unsigned long long npix = list ? list->n : (unsigned long long)W * H * nviews * nsets;
-    const unsigned L = nlights, SL = sets ? (unsigned)sets->sph_index.size() : soft ? soft->nspherical : 0;
-    FrameDev F{};
-    if (views) {
-        if (!make_views_frame(W, H, nviews, trace_block(s->dev), F)) return fail(CGRT_E_ARG, "bad batch");
-    } else if (!list && !make_frame(W, H, 0, 0, W, H, rank, nranks, trace_block(s->dev), F)) {
-        return fail(CGRT_E_ARG, "bad frame or rank");
-    }
-    const unsigned long long n = list ? list->n : (unsigned long long)F.nblocks * (unsigned long long)F.block;
+    FrameShape S;
+    if (const int rc = frame_shape(R, trace_block(s->dev), S)) return rc;
+    const int W = S.W, H = S.H;
+    const uint32_t nviews = S.nviews, nsets = S.nsets;
+    const unsigned long long npix = S.npix, n = S.n;
+    const unsigned L = S.L, SL = S.SL;
+    FrameDev& F = S.F;
     // the ticket slot: its last frame must be over before its staging is written again (the documented wait)
     CgrtScene::EnqSlot& slot = s->eslot[s->enq_count % CgrtScene::ENQ_SLOTS];
     if (slot.pending) {
@@ -3258,35 +3355,9 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
         HIP_TRY(hipHostMalloc((void**)&slot.pin_ctr, 4 * 17 * sizeof(uint32_t), hipHostMallocDefault));
     }
     // the workspace of render_impl, sized for the worst case (WsBuf::alloc waits for the scene's frames before a buffer grows)
-    WsBuf rays[4] = {{s, 0}, {s, 1}, {s, 21}, {s, 34}}, hits[4] = {{s, 2}, {s, 3}, {s, 22}, {s, 35}}, normals[4] = {{s, 4}, {s, 5}, {s, 23}, {s, 36}},
-          pix[4] = {{s, 6}, {s, 7}, {s, 24}, {s, 37}}, ipix{s, 8}, srays[2] = {{s, 9}, {s, 25}}, shits[2] = {{s, 10}, {s, 26}}, sdist[2] = {{s, 11}, {s, 27}},
-          sslot[2] = {{s, 12}, {s, 28}}, levels{s, 14}, drgb{s, 15}, dctr{s, 16}, dlit{s, 19}, dres{s, 30}, dsets{s, 32};
-    const int packed = aa && nranks > 1;
-    const size_t res_bytes = packed ? (size_t)F.nst_rank * 1024 * 12 : (size_t)PW * PH * 12;
-    const size_t dres_bytes = std::max<size_t>(res_bytes, (size_t)F.nst_rank * 1024 * 12);
-    const size_t nctr = 4 * (size_t)(max_level + 1);
-    const AovSets sets_for{aov && max_level >= 4};  // (as render_impl: geometry buffers are scattered from level 0's lists behind the frame)
-    if (n) {
-        HIP_TRY(ipix.alloc(n * 4));
-        for (int k = 0; k < sets_for.count(); k++) {
-            HIP_TRY(rays[k].alloc(n * 28));
-            HIP_TRY(hits[k].alloc(n * sizeof(CgrtHit)));
-            HIP_TRY(normals[k].alloc(n * 12));
-            HIP_TRY(pix[k].alloc(n * 4));
-        }
-        for (int k = 0; k < 2; k++) {
-            HIP_TRY(srays[k].alloc(n * L * 28));
-            HIP_TRY(shits[k].alloc(n * L * sizeof(CgrtHit)));
-            HIP_TRY(sdist[k].alloc(n * L * 4));
-            HIP_TRY(sslot[k].alloc(n * L * 4));
-        }
-        HIP_TRY(levels.alloc((size_t)(max_level > 0 ? max_level : 1) * n * 32));
-        if (!list) HIP_TRY(drgb.alloc(npix * 12));
-        if (aa) HIP_TRY(dres.alloc(dres_bytes));
-        HIP_TRY(dctr.alloc(nctr * sizeof(uint32_t)));
-        if (SL) HIP_TRY(dlit.alloc(n * SL * 4));
-        if (sets) HIP_TRY(dsets.alloc((size_t)(max_level > 0 ? max_level : 1) * n * nsets * 16));  // (every set's colours of every level)
-    }
+    Wavefront ws(s, S);
+    if (n)
+        if (const int rc = ws.reserve()) return rc;
     // the frame's tables, through the slot's pinned staging: the caller may reuse its arrays once the call returns (light sets: `lights` is
     // the distinct positions, the spherical lights the distinct keys, and the sets' own table -- SetsDev's memory -- comes last)
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
@@ -3311,50 +3382,29 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
     }
     char* const pin = static_cast<char*>(slot.pin);
     char* const tab = static_cast<char*>(s->enq_dev);
-    const float* const dl = reinterpret_cast<const float*>(tab + o_lights);
-    if (L) std::memcpy(pin + o_lights, lights, (size_t)L * 24);
+    if (L) std::memcpy(pin + o_lights, R.lights, (size_t)L * 24);
     SoftDev Q{};
     SetsDev T{};
-    auto sets_of = [&](int level) { return dsets.as<float>() + (size_t)level * n * nsets * 4; };
-    if (sets) {
-        std::memcpy(pin + o_sets, sets->table.data(), sets->table.size() * 4);
-        const uint32_t* st = reinterpret_cast<const uint32_t*>(tab + o_sets);
-        T.point_off = st;
-        T.sph_off = st + nsets + 1;
-        T.point = reinterpret_cast<const float4*>(st + sets->point_at);
-        T.sph = reinterpret_cast<const float4*>(st + sets->sph_at);
-        T.nsets = nsets;
-        Q.set_index = st + 2 * ((size_t)nsets + 1);
-    }
     if (SL) {
         std::memcpy(pin + o_slights, sets ? sets->spherical.data() : soft->spherical, (size_t)SL * 28);
         std::memcpy(pin + o_units, soft->unit_vectors, (size_t)soft->nunits * 12);
-        Q.lights = reinterpret_cast<const float*>(tab + o_slights);
-        Q.units = reinterpret_cast<const float*>(tab + o_units);
-        Q.nlights = SL;
-        Q.samples = soft->samples;
-        Q.nunits = soft->nunits;
-        Q.seed = soft->seed;
+        Q = soft_dev(*soft, SL, reinterpret_cast<const float*>(tab + o_slights), reinterpret_cast<const float*>(tab + o_units));
         if (views) Q.view_pixels = (uint32_t)W * (uint32_t)H;
     }
+    if (sets) {
+        std::memcpy(pin + o_sets, sets->table.data(), sets->table.size() * 4);
+        T = sets_dev(*sets, reinterpret_cast<const uint32_t*>(tab + o_sets));
+        Q.set_index = T.point_off + 2 * ((size_t)nsets + 1);
+    }
+    float* const frame_rgb = list ? list->rgb : ws.rgb.as<float>();
     const float* const mats = static_cast<const float*>(s->d_materials);
+    const FrameConst K{mats, reinterpret_cast<const float*>(tab + o_lights), L, Q.lights, SL, ws.lit.as<uint32_t>(), Q.samples, frame_rgb,
+                       (unsigned long long)W * H};
     const bool fused = !list && !views;  // level 0 spawned by the primary kernel (spawn_rays.h)
-    auto ctr_of = [&](int level) { return dctr.as<uint32_t>() + 4 * (size_t)level; };
-    auto lvl_of = [&](int level) { return levels.as<float>() + (size_t)level * n * 8; };
-    uint32_t* const pair = dctr.as<uint32_t>() + 4 * (size_t)max_level + 2;  // fused: {level 0's entries, level 1's entries}
-    uint32_t* const primary_hits = pair + 1;                                   // views, lists: level 0's entries
+    uint32_t* const pair = ws.ctr_of(max_level) + 2;  // fused: {level 0's entries, level 1's entries}
+    uint32_t* const primary_hits = pair + 1;          // views, lists: level 0's entries
     if (fused && max_level >= 1) {
-        SpawnDev SP{};
-        SP.materials = mats;
-        SP.lights = dl;
-        SP.nlights = L;
-        SP.spawn = 1 < max_level;
-        SP.srays = srays[0].as<float>();
-        SP.sdist = sdist[0].as<float>();
-        SP.sslot = sslot[0].as<int>();
-        SP.lvl = reinterpret_cast<float4*>(lvl_of(0));
-        SP.next_rays = rays[1].as<float>();
-        SP.next_pixels = pix[1].as<int>();
+        const SpawnDev SP = spawn_dev(ws.level(0), K);
         std::memcpy(pin + o_spawn, &SP, sizeof(SP));
     }
     if (views) {
@@ -3367,9 +3417,9 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
     if (s->export_pending) HIP_TRY(hipStreamWaitEvent(stream, s->export_done, 0));
     HIP_TRY(hipEventRecord(slot.t0, stream));
     HIP_TRY(hipMemcpyAsync(tab, pin, table_bytes, hipMemcpyHostToDevice, stream));
-    float* const frame_rgb = list ? list->rgb : drgb.as<float>();
     if (n) {
-        HIP_TRY(hipMemsetAsync(dctr.p, 0, nctr * sizeof(uint32_t), stream));
+        const LevelDev V0 = ws.level(0);
+        HIP_TRY(hipMemsetAsync(ws.ctr.p, 0, S.nctr * sizeof(uint32_t), stream));
         if (max_level < 1) {  // trace() returns black without tracing (main.cpp:267)
             if (list || views)
                 HIP_TRY(hipMemsetAsync(frame_rgb, 0, npix * 12, stream));
@@ -3379,81 +3429,66 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
             // device word with the entries of a level / the mirror rays a level spawned
             auto count_of = [&](int level) -> uint32_t* {
                 if (level == 0) return fused ? pair : primary_hits;
-                return (fused && level == 1) ? pair + 1 : ctr_of(level - 1) + 1;
+                return (fused && level == 1) ? pair + 1 : ws.ctr_of(level - 1) + 1;
             };
-            auto mirrors_of = [&](int level) -> uint32_t* { return (fused && level == 0) ? pair + 1 : ctr_of(level) + 1; };
+            auto mirrors_of = [&](int level) -> uint32_t* { return (fused && level == 0) ? pair + 1 : ws.ctr_of(level) + 1; };
             if (list)  // (also clears the list's colours)
-                HIP_TRY(launch_trace_list_compact(s->dev, list->rays, n, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
-                                                  ipix.as<int>(), primary_hits, frame_rgb, stream));
+                HIP_TRY(launch_trace_list_compact(s->dev, list->rays, n, V0.rays, V0.hits, V0.normals, V0.pixels, primary_hits, frame_rgb, stream));
             else if (views)  // (also clears every view's pixels)
-                HIP_TRY(launch_trace_primary_views_compact(s->dev, F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
-                                                           ipix.as<int>(), primary_hits, frame_rgb, stream, views->raycams != nullptr));
+                HIP_TRY(launch_trace_primary_views_compact(s->dev, F, V0.rays, V0.hits, V0.normals, V0.pixels, primary_hits, frame_rgb, stream,
+                                                           views->raycams != nullptr));
             else  // (also clears this rank's pixels, and spawns level 0)
-                HIP_TRY(launch_trace_primary_compact(s->dev, make_camera(*cam), F, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(),
-                                                     ipix.as<int>(), pair, stream, nullptr, frame_rgb,
-                                                     reinterpret_cast<const SpawnDev*>(tab + o_spawn)));
+                HIP_TRY(launch_trace_primary_compact(s->dev, make_camera(*R.cam), F, V0.rays, V0.hits, V0.normals, V0.pixels, pair, stream, nullptr,
+                                                     frame_rgb, reinterpret_cast<const SpawnDev*>(tab + o_spawn)));
             if (nsets > 1)  // (as render_impl: the views' kernel cleared the first nviews * W * H pixels, a miss is black in every set)
                 HIP_TRY(hipMemsetAsync(frame_rgb + 3ull * W * H * nviews, 0, (npix - (unsigned long long)W * H * nviews) * 12, stream));
             const bool pairable = can_trace_pair(s->dev);
             for (int level = 0; level < max_level; level++) {
-                const int a = sets_for.of(level), b = sets_for.of(level + 1), q = level & 1;  // as render_impl's buffer sets
-                const int spawn = level + 1 < max_level;
-                const int* cur_pix = level == 0 ? ipix.as<int>() : pix[a].as<int>();
-                if (!(fused && level == 0))
-                    HIP_TRY(launch_spawn_strided(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), cur_pix, n, mats, dl, L, spawn,
-                                                 srays[q].as<float>(), sdist[q].as<float>(), sslot[q].as<int>(), lvl_of(level), rays[b].as<float>(),
-                                                 pix[b].as<int>(), ctr_of(level), stream, count_of(level)));
+                const LevelDev V = ws.level(level);
+                const bool fused0 = fused && level == 0;
+                if (!fused0) HIP_TRY(launch_spawn(V, K, n, stream, count_of(level), GRID_STRIDED));
                 // the level's shadow list: hits x lights rays (fused level 0) or the appended count
-                const uint32_t* sdc = (fused && level == 0) ? pair : ctr_of(level);
-                const unsigned sdmul = (fused && level == 0) ? L : 1u;
-                if (L && spawn && pairable) {
-                    HIP_TRY(launch_trace_pair_strided(s->dev, srays[q].as<float>(), sdist[q].as<float>(), n * L, shits[q].as<CgrtHitDev>(), sdc, sdmul,
-                                                      rays[b].as<float>(), n, hits[b].as<CgrtHitDev>(), normals[b].as<float>(), mirrors_of(level), stream));
+                const uint32_t* sdc = fused0 ? pair : V.counters;
+                const unsigned sdmul = fused0 ? L : 1u;
+                if (L && V.spawn && pairable) {
+                    HIP_TRY(launch_trace_pair_strided(s->dev, V.srays, V.sdist, n * L, V.shits, sdc, sdmul, V.next_rays, n, V.next_hits, V.next_normals,
+                                                      mirrors_of(level), stream));
                 } else {
-                    if (L)
-                        HIP_TRY(launch_trace_shadow_strided(s->dev, srays[q].as<float>(), sdist[q].as<float>(), n * L, shits[q].as<CgrtHitDev>(), stream, sdc,
-                                                            sdmul));
-                    if (spawn)
-                        HIP_TRY(launch_trace_batch_strided(s->dev, rays[b].as<float>(), n, hits[b].as<CgrtHitDev>(), normals[b].as<float>(), stream,
-                                                           mirrors_of(level)));
+                    if (L) HIP_TRY(launch_trace_shadow_strided(s->dev, V.srays, V.sdist, n * L, V.shits, stream, sdc, sdmul));
+                    if (V.spawn) HIP_TRY(launch_trace_batch_strided(s->dev, V.next_rays, n, V.next_hits, V.next_normals, stream, mirrors_of(level)));
                 }
                 if (SL) {
                     Q.level = (uint32_t)level;
-                    HIP_TRY(hipMemsetAsync(dlit.p, 0, n * SL * 4, stream));
-                    HIP_TRY(launch_soft_shadow_strided(s->dev, Q, rays[a].as<float>(), hits[a].as<CgrtHitDev>(), cur_pix, n, count_of(level),
-                                                       dlit.as<uint32_t>(), soft->closest_hit == 0, stream));
+                    HIP_TRY(hipMemsetAsync(ws.lit.p, 0, n * SL * 4, stream));
+                    HIP_TRY(launch_soft_shadow_strided(s->dev, Q, V.rays, V.hits, V.pixels, n, count_of(level), ws.lit.as<uint32_t>(),
+                                                       soft->closest_hit == 0, stream));
                 }
                 if (sets)
-                    HIP_TRY(launch_shade_sets_strided(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(),
-                                                      sdist[q].as<float>(), sslot[q].as<int>(), n, mats, L, SL, dlit.as<uint32_t>(), Q.samples, T,
-                                                      sets_of(level), n, stream, count_of(level)));
+                    HIP_TRY(launch_shade_sets(V, K, T, n, stream, count_of(level), GRID_STRIDED));
                 else
-                    HIP_TRY(launch_shade_strided(rays[a].as<float>(), hits[a].as<CgrtHitDev>(), normals[a].as<float>(), shits[q].as<CgrtHitDev>(),
-                                                 sdist[q].as<float>(), sslot[q].as<int>(), n, mats, dl, L, Q.lights, SL, dlit.as<uint32_t>(), Q.samples,
-                                                 lvl_of(level), stream, count_of(level)));
+                    HIP_TRY(launch_shade(V, K, n, stream, count_of(level), GRID_STRIDED));
             }
             for (int level = max_level - 2; level >= 1; level--) {
                 if (sets)
-                    HIP_TRY(launch_fold_sets_strided(lvl_of(level), sets_of(level), sets_of(level + 1), n, n, nsets, stream, count_of(level)));
+                    HIP_TRY(launch_fold_sets_strided(ws.level(level), n, stream, count_of(level)));
                 else
-                    HIP_TRY(launch_fold_strided(lvl_of(level), lvl_of(level + 1), n, stream, count_of(level)));
+                    HIP_TRY(launch_fold(ws.level(level), n, stream, count_of(level), GRID_STRIDED));
             }
             if (sets)
-                HIP_TRY(launch_write_rgb_views_sets_strided(lvl_of(0), sets_of(0), max_level >= 2 ? sets_of(1) : nullptr, n, n, nsets, ipix.as<int>(),
-                                                            frame_rgb, (unsigned long long)W * H, stream, count_of(0)));
+                HIP_TRY(launch_write_rgb_views_sets_strided(V0, K, max_level >= 2, n, stream, count_of(0)));
             else
-                HIP_TRY(launch_write_rgb_strided(lvl_of(0), max_level >= 2 ? lvl_of(1) : nullptr, n, ipix.as<int>(), frame_rgb, stream, count_of(0)));
+                HIP_TRY(launch_write_rgb(V0, K, max_level >= 2, n, stream, count_of(0), GRID_STRIDED));
         }
-        if (aa) HIP_TRY(launch_resolve_aa(F, drgb.as<float>(), dres.as<float>(), packed, stream));
-        if (dout) HIP_TRY(launch_export_frame(export_of(F, aa ? dres.as<float>() : drgb.as<float>(), *dout, PW, PH, views ? nviews * nsets : 0u, aa, rank,
-                                                        nranks, packed), stream));
-        if (aov) {  // (max_level >= 1: level 0's length is the word the primary kernel counted into)
-            const AovDev A = aov_of(*aov, F, W, H, nviews, rank, nranks);
+        if (R.aa) HIP_TRY(launch_resolve_aa(F, ws.rgb.as<float>(), ws.resolved.as<float>(), S.packed, stream));
+        if (R.dout)
+            HIP_TRY(launch_export_frame(export_of(F, R.aa ? ws.resolved.as<float>() : ws.rgb.as<float>(), *R.dout, S.PW, S.PH, views ? nviews * nsets : 0u,
+                                                  R.aa, R.rank, R.nranks, S.packed), stream));
+        if (R.aov) {  // (max_level >= 1: level 0's length is the word the primary kernel counted into)
+            const AovDev A = aov_of(*R.aov, F, W, H, nviews, R.rank, R.nranks);
             HIP_TRY(launch_aov_fill(A, stream));
-            HIP_TRY(launch_aov_scatter_strided(A, rays[0].as<float>(), hits[0].as<CgrtHitDev>(), normals[0].as<float>(), ipix.as<int>(), mats, n, stream,
-                                               fused ? pair : primary_hits));
+            HIP_TRY(launch_aov_scatter_strided(A, V0, mats, n, stream, fused ? pair : primary_hits));
         }
-        HIP_TRY(hipMemcpyAsync(slot.pin_ctr, dctr.p, nctr * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(slot.pin_ctr, ws.ctr.p, S.nctr * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     }
     HIP_TRY(hipEventRecord(slot.t1, stream));
     HIP_TRY(hipEventRecord(slot.done, stream));
@@ -3468,17 +3503,21 @@ static int enqueue_impl(CgrtScene* s, const CgrtCamera* cam, int W, int H, const
     slot.SL = SL;
     slot.samples = SL ? soft->samples : 0;
     slot.primary_rays = (n && max_level >= 1) ? (list ? n : views ? (unsigned long long)W * H * nviews : owned_pixels(F)) : 0;
-    if (ticket) *ticket = slot.ticket;
+    if (R.ticket) *R.ticket = slot.ticket;
     return CGRT_OK;
 }
 
+static int enqueue_frame(CgrtScene* s, FrameRequest R, uint64_t* ticket) {
+    R.ticket = ticket;
+    return enqueue_impl(s, R);
+}
 int cgrt_enqueue_render_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                                int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
                                uint64_t* ticket) {
     DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream)};
     const int rc = render_device_args(s, cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, d_out, format, row_bytes, &D.pitch);
     if (rc) return rc;
-    return enqueue_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, aa != 0, &D, nullptr, nullptr, D.stream, ticket);
+    return enqueue_frame(s, device_request(cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, &D), ticket);
 }
 int cgrt_enqueue_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
                                      const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, uint64_t* ticket) {
@@ -3486,7 +3525,7 @@ int cgrt_enqueue_render_views_device(CgrtScene* s, const CgrtCamera* cams, uint3
     const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D);
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
-    return enqueue_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream, ticket);
+    return enqueue_frame(s, views_request(&V, W, H, lights, nlights, soft, max_level, &D), ticket);
 }
 int cgrt_enqueue_render_aov_device(CgrtScene* s, const CgrtCamera* cam, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                                    int max_level, int aa, int rank, int nranks, void* d_out, int format, uint64_t row_bytes, void* stream,
@@ -3494,7 +3533,7 @@ int cgrt_enqueue_render_aov_device(CgrtScene* s, const CgrtCamera* cam, int W, i
     DeviceOut D{d_out, format, 0, static_cast<hipStream_t>(stream)};
     const int rc = render_device_args(s, cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, d_out, format, row_bytes, &D.pitch, true, aov);
     if (rc) return rc;
-    return enqueue_impl(s, cam, W, H, lights, nlights, soft, max_level, rank, nranks, aa != 0, &D, nullptr, nullptr, D.stream, ticket, nullptr, aov);
+    return enqueue_frame(s, device_request(cam, W, H, lights, nlights, soft, max_level, aa, rank, nranks, &D, aov), ticket);
 }
 int cgrt_enqueue_render_views_aov_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
                                          const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, uint64_t* ticket,
@@ -3503,7 +3542,7 @@ int cgrt_enqueue_render_views_aov_device(CgrtScene* s, const CgrtCamera* cams, u
     const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D, true, aov);
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
-    return enqueue_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream, ticket, nullptr, aov);
+    return enqueue_frame(s, views_request(&V, W, H, lights, nlights, soft, max_level, &D, aov), ticket);
 }
 int cgrt_enqueue_render_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* lights, uint32_t nlights,
                                        const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, uint64_t* ticket,
@@ -3512,7 +3551,7 @@ int cgrt_enqueue_render_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, 
     const int rc = render_views_device_args(s, cams, nviews, W, H, lights, nlights, soft, max_level, d_out, format, &D, aov != nullptr, aov, cams);
     if (rc) return rc;
     const ViewSrc V{nullptr, nviews, cams};
-    return enqueue_impl(s, nullptr, W, H, lights, nlights, soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream, ticket, nullptr, aov);
+    return enqueue_frame(s, views_request(&V, W, H, lights, nlights, soft, max_level, &D, aov), ticket);
 }
 int cgrt_enqueue_render_views_light_sets_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const CgrtLightSets* sets,
                                                 const CgrtSoftShadows* soft, int max_level, void* d_out, int format, void* stream, uint64_t* ticket) {
@@ -3521,15 +3560,14 @@ int cgrt_enqueue_render_views_light_sets_device(CgrtScene* s, const CgrtCamera* 
     const int rc = views_light_sets_device_args(s, cams, nviews, W, H, sets, soft, max_level, d_out, format, &P, &D);
     if (rc) return rc;
     const ViewSrc V{cams, nviews};
-    return enqueue_impl(s, nullptr, W, H, P.points.data(), (uint32_t)(P.points.size() / 6), soft, max_level, 0, 1, false, &D, nullptr, &V, D.stream,
-                        ticket, &P);
+    return enqueue_frame(s, sets_request(nullptr, &V, W, H, P, soft, max_level, &D), ticket);
 }
 int cgrt_enqueue_shade_rays_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
                                    int max_level, float* d_rgb, void* stream, uint64_t* ticket) {
     const int rc = shade_rays_device_args(s, d_rays, n, lights, nlights, soft, max_level, d_rgb);
     if (rc) return rc;
     const ListSrc src{reinterpret_cast<const float*>(d_rays), n, d_rgb, static_cast<hipStream_t>(stream)};
-    return enqueue_impl(s, nullptr, 1, 1, lights, nlights, soft, max_level, 0, 1, false, nullptr, &src, nullptr, src.stream, ticket);
+    return enqueue_frame(s, list_request(&src, lights, nlights, soft, max_level), ticket);
 }
 int cgrt_enqueue_stats(CgrtScene* s, uint64_t ticket, CgrtRenderStats* stats) {
     if (!s) return fail(CGRT_E_ARG, "scene is NULL");
@@ -3574,12 +3612,6 @@ int cgrt_enqueue_stats(CgrtScene* s, uint64_t ticket, CgrtRenderStats* stats) {
 // device work; then a host-only scene is CGRT_E_NO_DEVICE.  None of them touches the scene's frame prediction or frame hints.
 namespace {
 const uint64_t kMaxAnswers = 0x7fffffffull;
-int soft_rules(const CgrtSoftShadows* soft) {  // cgrt_shade_rays' rules; NULL = no spherical lights
-    if (soft && soft->nspherical &&
-        (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
-        return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
-    return CGRT_OK;
-}
 // NULL pointers (the rays / points and the output with n > 0, lights missing), then n and n x per_point above 0x7fffffff
 int query_args(const CgrtScene* s, const void* in, uint64_t n, const void* out, uint64_t per_point, bool lights_missing) {
     if (!s || (n && (!in || !out)) || lights_missing) return fail(CGRT_E_ARG, "NULL argument");
@@ -3611,14 +3643,8 @@ int soft_lit_on_lane(LaneGuard& g, CgrtScene* s, const float* d_points, uint64_t
     HIP_TRY(lane_upload(g, 3, dl, soft->spherical, SL * 28));
     HIP_TRY(lane_upload(g, 2, du, soft->unit_vectors, (size_t)soft->nunits * 12));
     HIP_TRY(hipMemsetAsync(d_lit, 0, n * SL * sizeof(uint32_t), g.L->stream));
-    SoftDev Q{};
-    Q.lights = static_cast<const float*>(dl);
-    Q.units = static_cast<const float*>(du);
-    Q.nlights = (uint32_t)SL;
-    Q.samples = soft->samples;
-    Q.nunits = soft->nunits;
-    Q.seed = soft->seed;
-    Q.level = 0;  // (cgrt_shade_rays' convention: pixel = i, level 0)
+    // (level stays 0, cgrt_shade_rays' convention: pixel = i, level 0)
+    const SoftDev Q = soft_dev(*soft, (unsigned)SL, static_cast<const float*>(dl), static_cast<const float*>(du));
     HIP_TRY(launch_soft_points(s->dev, Q, d_points, n, d_lit, soft->closest_hit ? 0 : 1, g.L->stream));
     return CGRT_OK;
 }
@@ -4279,7 +4305,10 @@ static int render_replicas(CgrtScene* const* scenes, int nscenes, const CgrtCame
     auto work = [&](int i) {
         // render_impl downloads the replica's frame into its scene's pinned staging and copies ONLY the super-tiles rank i owns
         // into the caller's frame: disjoint regions, so the replicas' threads write rgb concurrently without a merge pass
-        status[i] = render_impl(scenes[i], cam, W, H, lights, nlights, soft, max_level, i, nscenes, rgb, &st[i], nullptr, nullptr, aa);
+        FrameRequest R;
+        R.cam = cam, R.W = W, R.H = H, R.lights = lights, R.nlights = nlights, R.soft = soft, R.max_level = max_level, R.rank = i, R.nranks = nscenes;
+        R.aa = aa, R.rgb = rgb, R.stats = &st[i];
+        status[i] = render_impl(scenes[i], R);
         if (status[i]) errs[i] = g_err;  // (thread-local: carried over to the caller's thread below)
     };
     {

@@ -748,143 +748,92 @@ hipError_t launch_aov_fill(const AovDev& A, hipStream_t s) {
     hipLaunchKernelGGL(k_aov_fill, dim3(grid_for(n, 256)), dim3(256), 0, s, A);
     return hipGetLastError();
 }
-hipError_t launch_aov_scatter(const AovDev& A, const float* rays, const CgrtHitDev* hits, const float* normals, const int* item_pixels,
-                              const float* materials, unsigned long long n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_aov_scatter, dim3(grid_for(n, 256)), dim3(256), 0, s, A, rays, hits, normals, item_pixels, materials, n);
-    return hipGetLastError();
-}
-
-hipError_t launch_spawn(const float* rays, const CgrtHitDev* hits, const float* normals, const int* pixels, unsigned long long n,
-                        const float* materials, const float* lights, unsigned nlights, int spawn, float* srays, float* sdist, int* sslot,
-                        float* lvl, float* next_rays, int* next_pixels, uint32_t* counters, hipStream_t s, const uint32_t* dcount) {
-    if (n)
-        hipLaunchKernelGGL(k_spawn, dim3(grid_for(n, CGRT_SHADE_BLOCK)), dim3(CGRT_SHADE_BLOCK), 0, s, rays, hits, normals, pixels, n, materials,
-                           lights, nlights, spawn, srays, sdist, sslot, reinterpret_cast<float4*>(lvl), next_rays, next_pixels, counters, dcount);
-    return hipGetLastError();
-}
-hipError_t launch_shade(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
-                        const int* sslot, unsigned long long n, const float* materials, const float* lights, unsigned nlights,
-                        const float* slights, unsigned nslights, const uint32_t* lit, unsigned samples, float* lvl, hipStream_t s,
-                        const uint32_t* dcount) {
-    if (n)
-        hipLaunchKernelGGL(k_shade, dim3(grid_for(n, CGRT_SHADE_BLOCK)), dim3(CGRT_SHADE_BLOCK), 0, s, rays, hits, normals, shits, sdist, sslot, n,
-                           materials, lights, nlights, slights, nslights, lit, samples, reinterpret_cast<float4*>(lvl), dcount);
-    return hipGetLastError();
-}
-hipError_t launch_fold(float* lvl, const float* child_lvl, unsigned long long n, hipStream_t s, const uint32_t* dcount) {
-    if (n)
-        hipLaunchKernelGGL(k_fold, dim3(grid_for(n, 256)), dim3(256), 0, s, reinterpret_cast<float4*>(lvl),
-                           reinterpret_cast<const float4*>(child_lvl), n, dcount);
-    return hipGetLastError();
-}
-hipError_t launch_write_rgb(const float* lvl0, const float* child_lvl, unsigned long long n, const int* item_pixels, float* rgb, hipStream_t s,
-                            const uint32_t* dcount) {
-    if (n)
-        hipLaunchKernelGGL(k_write_rgb, dim3(grid_for(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
-                           reinterpret_cast<const float4*>(child_lvl), n, item_pixels, rgb, dcount);
-    return hipGetLastError();
-}
-
-hipError_t launch_shade_sets(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
-                             const int* sslot, unsigned long long n, const float* materials, unsigned npos, unsigned nsph, const uint32_t* lit,
-                             unsigned samples, const SetsDev& T, float* out, unsigned long long stride, hipStream_t s, const uint32_t* dcount) {
-    if (n)
-        hipLaunchKernelGGL(k_shade_sets, dim3(grid_for(n, CGRT_SHADE_BLOCK)), dim3(CGRT_SHADE_BLOCK), 0, s, rays, hits, normals, shits, sdist, sslot, n,
-                           materials, npos, nsph, lit, samples, T, reinterpret_cast<float4*>(out), stride, dcount);
-    return hipGetLastError();
-}
-hipError_t launch_fold_sets(const float* lvl, float* sets_lvl, const float* child_sets, unsigned long long n, unsigned long long stride, unsigned nsets,
-                            hipStream_t s) {
-    if (n && nsets)
-        hipLaunchKernelGGL(k_fold_sets, dim3(grid_for(n, 256), nsets), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl),
-                           reinterpret_cast<float4*>(sets_lvl), reinterpret_cast<const float4*>(child_sets), n, stride);
-    return hipGetLastError();
-}
-hipError_t launch_write_rgb_sets(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n, unsigned long long stride,
-                                 unsigned nsets, const int* item_pixels, float* rgb, unsigned long long frame_pixels, hipStream_t s) {
-    if (n && nsets)
-        hipLaunchKernelGGL(k_write_rgb_sets, dim3(grid_for(n, 256), nsets), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
-                           reinterpret_cast<const float4*>(sets0), reinterpret_cast<const float4*>(child_sets), n, stride, item_pixels, rgb,
-                           frame_pixels);
-    return hipGetLastError();
-}
-
-hipError_t launch_write_rgb_views_sets(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n, unsigned long long stride,
-                                       unsigned nsets, const int* item_pixels, float* rgb, unsigned long long view_pixels, hipStream_t s) {
-    if (n && nsets)
-        hipLaunchKernelGGL(k_write_rgb_views_sets, dim3(grid_for(n, 256), nsets), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
-                           reinterpret_cast<const float4*>(sets0), reinterpret_cast<const float4*>(child_sets), n, stride, item_pixels, rgb,
-                           view_pixels);
-    return hipGetLastError();
-}
-
 // the count-driven forms: at most strided_waves() waves per launch (trace_kernels.hip), whatever the capacity n
 static inline unsigned strided_grid(unsigned long long n, unsigned block) {
     const unsigned cap = (unsigned)std::max<unsigned long long>(1ull, (unsigned long long)strided_waves() * 64ull / block);
     const unsigned full = grid_for(n, block);
     return full < cap ? full : cap;
 }
-hipError_t launch_spawn_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const int* pixels, unsigned long long n,
-                                const float* materials, const float* lights, unsigned nlights, int spawn, float* srays, float* sdist, int* sslot,
-                                float* lvl, float* next_rays, int* next_pixels, uint32_t* counters, hipStream_t s, const uint32_t* dcount) {
-    if (n)
-        hipLaunchKernelGGL(k_spawn_strided, dim3(strided_grid(n, CGRT_SHADE_BLOCK)), dim3(CGRT_SHADE_BLOCK), 0, s, rays, hits, normals, pixels, n, materials,
-                           lights, nlights, spawn, srays, sdist, sslot, reinterpret_cast<float4*>(lvl), next_rays, next_pixels, counters, dcount);
-    return hipGetLastError();
-}
-hipError_t launch_shade_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
-                                const int* sslot, unsigned long long n, const float* materials, const float* lights, unsigned nlights,
-                                const float* slights, unsigned nslights, const uint32_t* lit, unsigned samples, float* lvl, hipStream_t s,
-                                const uint32_t* dcount) {
-    if (n)
-        hipLaunchKernelGGL(k_shade_strided, dim3(strided_grid(n, CGRT_SHADE_BLOCK)), dim3(CGRT_SHADE_BLOCK), 0, s, rays, hits, normals, shits, sdist, sslot,
-                           n, materials, lights, nlights, slights, nslights, lit, samples, reinterpret_cast<float4*>(lvl), dcount);
-    return hipGetLastError();
-}
-hipError_t launch_fold_strided(float* lvl, const float* child_lvl, unsigned long long n, hipStream_t s, const uint32_t* dcount) {
-    if (n)
-        hipLaunchKernelGGL(k_fold_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, reinterpret_cast<float4*>(lvl),
-                           reinterpret_cast<const float4*>(child_lvl), n, dcount);
-    return hipGetLastError();
-}
-hipError_t launch_write_rgb_strided(const float* lvl0, const float* child_lvl, unsigned long long n, const int* item_pixels, float* rgb, hipStream_t s,
-                                    const uint32_t* dcount) {
-    if (n)
-        hipLaunchKernelGGL(k_write_rgb_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
-                           reinterpret_cast<const float4*>(child_lvl), n, item_pixels, rgb, dcount);
-    return hipGetLastError();
-}
+// KERNEL with one thread per entry of the list's n, or KERNEL_strided (the same parameters) with a capped grid, as `grid` says
+#define LAUNCH_LIST(KERNEL, block, ...)                                                                         \
+    do {                                                                                                        \
+        if (grid == GRID_STRIDED)                                                                               \
+            hipLaunchKernelGGL(KERNEL##_strided, dim3(strided_grid(n, block)), dim3(block), 0, s, __VA_ARGS__); \
+        else                                                                                                    \
+            hipLaunchKernelGGL(KERNEL, dim3(grid_for(n, block)), dim3(block), 0, s, __VA_ARGS__);               \
+    } while (0)
+static inline const float4* f4(const float* p) { return reinterpret_cast<const float4*>(p); }
+static inline float4* f4(float* p) { return reinterpret_cast<float4*>(p); }
 
-hipError_t launch_aov_scatter_strided(const AovDev& A, const float* rays, const CgrtHitDev* hits, const float* normals, const int* item_pixels,
-                                      const float* materials, unsigned long long n, hipStream_t s, const uint32_t* dcount) {
+hipError_t launch_aov_scatter(const AovDev& A, const LevelDev& V0, const float* materials, unsigned long long n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_aov_scatter, dim3(grid_for(n, 256)), dim3(256), 0, s, A, V0.rays, V0.hits, V0.normals, V0.pixels, materials, n);
+    return hipGetLastError();
+}
+hipError_t launch_aov_scatter_strided(const AovDev& A, const LevelDev& V0, const float* materials, unsigned long long n, hipStream_t s,
+                                      const uint32_t* dcount) {
     if (n)
-        hipLaunchKernelGGL(k_aov_scatter_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, A, rays, hits, normals, item_pixels, materials, n,
+        hipLaunchKernelGGL(k_aov_scatter_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, A, V0.rays, V0.hits, V0.normals, V0.pixels, materials, n,
                            dcount);
     return hipGetLastError();
 }
 
-hipError_t launch_shade_sets_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
-                                     const int* sslot, unsigned long long n, const float* materials, unsigned npos, unsigned nsph, const uint32_t* lit,
-                                     unsigned samples, const SetsDev& T, float* out, unsigned long long stride, hipStream_t s, const uint32_t* dcount) {
+hipError_t launch_spawn(const LevelDev& V, const FrameConst& K, unsigned long long n, hipStream_t s, const uint32_t* dcount, ListGrid grid) {
     if (n)
-        hipLaunchKernelGGL(k_shade_sets_strided, dim3(strided_grid(n, CGRT_SHADE_BLOCK)), dim3(CGRT_SHADE_BLOCK), 0, s, rays, hits, normals, shits, sdist,
-                           sslot, n, materials, npos, nsph, lit, samples, T, reinterpret_cast<float4*>(out), stride, dcount);
+        LAUNCH_LIST(k_spawn, CGRT_SHADE_BLOCK, V.rays, V.hits, V.normals, V.pixels, n, K.materials, K.lights, K.nlights, V.spawn, V.srays, V.sdist,
+                    V.sslot, f4(V.lvl), V.next_rays, V.next_pixels, V.counters, dcount);
     return hipGetLastError();
 }
-hipError_t launch_fold_sets_strided(const float* lvl, float* sets_lvl, const float* child_sets, unsigned long long n, unsigned long long stride,
-                                    unsigned nsets, hipStream_t s, const uint32_t* dcount) {
-    if (n && nsets)
-        hipLaunchKernelGGL(k_fold_sets_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl),
-                           reinterpret_cast<float4*>(sets_lvl), reinterpret_cast<const float4*>(child_sets), n, stride, nsets, dcount);
+hipError_t launch_shade(const LevelDev& V, const FrameConst& K, unsigned long long n, hipStream_t s, const uint32_t* dcount, ListGrid grid) {
+    if (n)
+        LAUNCH_LIST(k_shade, CGRT_SHADE_BLOCK, V.rays, V.hits, V.normals, V.shits, V.sdist, V.sslot, n, K.materials, K.lights, K.nlights, K.slights,
+                    K.nslights, K.lit, K.samples, f4(V.lvl), dcount);
     return hipGetLastError();
 }
-hipError_t launch_write_rgb_views_sets_strided(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n,
-                                               unsigned long long stride, unsigned nsets, const int* item_pixels, float* rgb,
-                                               unsigned long long view_pixels, hipStream_t s, const uint32_t* dcount) {
-    if (n && nsets)
-        hipLaunchKernelGGL(k_write_rgb_views_sets_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(lvl0),
-                           reinterpret_cast<const float4*>(sets0), reinterpret_cast<const float4*>(child_sets), n, stride, nsets, item_pixels, rgb,
-                           view_pixels, dcount);
+hipError_t launch_fold(const LevelDev& V, unsigned long long n, hipStream_t s, const uint32_t* dcount, ListGrid grid) {
+    if (n) LAUNCH_LIST(k_fold, 256, f4(V.lvl), f4(V.child_lvl), n, dcount);
+    return hipGetLastError();
+}
+hipError_t launch_write_rgb(const LevelDev& V0, const FrameConst& K, bool with_child, unsigned long long n, hipStream_t s, const uint32_t* dcount,
+                            ListGrid grid) {
+    if (n)
+        LAUNCH_LIST(k_write_rgb, 256, f4(V0.lvl), with_child ? f4(V0.child_lvl) : nullptr, n, V0.pixels, K.rgb, dcount);
+    return hipGetLastError();
+}
+
+hipError_t launch_shade_sets(const LevelDev& V, const FrameConst& K, const SetsDev& T, unsigned long long n, hipStream_t s, const uint32_t* dcount,
+                             ListGrid grid) {
+    if (n)
+        LAUNCH_LIST(k_shade_sets, CGRT_SHADE_BLOCK, V.rays, V.hits, V.normals, V.shits, V.sdist, V.sslot, n, K.materials, K.nlights, K.nslights, K.lit,
+                    K.samples, T, f4(V.sets), V.stride, dcount);
+    return hipGetLastError();
+}
+hipError_t launch_fold_sets(const LevelDev& V, unsigned long long n, hipStream_t s) {
+    if (n && V.nsets)
+        hipLaunchKernelGGL(k_fold_sets, dim3(grid_for(n, 256), V.nsets), dim3(256), 0, s, f4(V.lvl), f4(V.sets), f4(V.child_sets), n, V.stride);
+    return hipGetLastError();
+}
+hipError_t launch_write_rgb_sets(const LevelDev& V0, const FrameConst& K, bool views, bool with_child, unsigned long long n, hipStream_t s) {
+    if (n && V0.nsets) {
+        const dim3 grid(grid_for(n, 256), V0.nsets);
+        const float4* const child = with_child ? f4(V0.child_sets) : nullptr;
+        if (views)
+            hipLaunchKernelGGL(k_write_rgb_views_sets, grid, dim3(256), 0, s, f4(V0.lvl), f4(V0.sets), child, n, V0.stride, V0.pixels, K.rgb, K.frame_pixels);
+        else
+            hipLaunchKernelGGL(k_write_rgb_sets, grid, dim3(256), 0, s, f4(V0.lvl), f4(V0.sets), child, n, V0.stride, V0.pixels, K.rgb, K.frame_pixels);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_fold_sets_strided(const LevelDev& V, unsigned long long n, hipStream_t s, const uint32_t* dcount) {
+    if (n && V.nsets)
+        hipLaunchKernelGGL(k_fold_sets_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, f4(V.lvl), f4(V.sets), f4(V.child_sets), n, V.stride, V.nsets,
+                           dcount);
+    return hipGetLastError();
+}
+hipError_t launch_write_rgb_views_sets_strided(const LevelDev& V0, const FrameConst& K, bool with_child, unsigned long long n, hipStream_t s,
+                                               const uint32_t* dcount) {
+    if (n && V0.nsets)
+        hipLaunchKernelGGL(k_write_rgb_views_sets_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, f4(V0.lvl), f4(V0.sets),
+                           with_child ? f4(V0.child_sets) : nullptr, n, V0.stride, V0.nsets, V0.pixels, K.rgb, K.frame_pixels, dcount);
     return hipGetLastError();
 }
 

@@ -123,57 +123,70 @@ hipError_t launch_trace_pair_strided(const SceneDev& S, const float* srays, cons
 hipError_t launch_soft_shadow_strided(const SceneDev& S, const SoftDev& Q, const float* rays, const CgrtHitDev* hits, const int* item_pixels,
                                       unsigned long long nitems, const uint32_t* dcount, uint32_t* lit, int anyhit, hipStream_t stream);
 // shading wavefront (shade_kernels.hip); every level is a compact list of live paths
-// counters: 3 device words {shadow rays appended, mirror rays appended, hits}, zeroed by the caller
+// One level of it, as the launchers below take it: typed device pointers into the frame's workspace (capi.cpp Wavefront::level -- the
+// only place that knows which buffer set a level lives in).  A plain value, built on the stack per launch group.
+struct LevelDev {
+    float* rays;  // the level's list: a ray, a hit, a normal and a pixel per entry
+    CgrtHitDev* hits;
+    float* normals;
+    int* pixels;
+    float *srays, *sdist;  // its shadow list (k_spawn appends, the shadow traversal fills shits)
+    int* sslot;
+    CgrtHitDev* shits;
+    float* lvl;          // its level record: lvl[2i] = {direct light, flags} (k_shade), lvl[2i+1] = {ks, child} (k_spawn)
+    uint32_t* counters;  // its counter block: 3 device words {shadow rays appended, mirror rays appended, hits}, zeroed by the caller
+    float* sets;         // light sets: set b's colour of entry i at sets + 4 * (b * stride + i) = {colour, flags}; NULL otherwise
+    int spawn;           // the level spawns mirror rays (level + 1 < max_level) ...
+    float* next_rays;    // ... into the next level's list
+    CgrtHitDev* next_hits;
+    float* next_normals;
+    int* next_pixels;
+    const float *child_lvl, *child_sets;  // the next level's record and per-set colours (NULL: there is no next level)
+    unsigned long long stride;            // entries the lists are sized for
+    unsigned nsets;                       // 1 without light sets
+};
+// What does not change over a frame.  lights: the point lights k_spawn traces shadow rays to (light sets: the batch's distinct positions,
+// sslot's row); slights: the spherical lights whose samples `lit` counts (light sets: the distinct keys, lit's row).
+struct FrameConst {
+    const float *materials, *lights;
+    unsigned nlights;
+    const float* slights;
+    unsigned nslights;
+    const uint32_t* lit;
+    unsigned samples;
+    float* rgb;                       // the frame the colours are scattered into
+    unsigned long long frame_pixels;  // pixels of one frame in it (light sets, views: W * H)
+};
+// How a launch covers its list of n entries.  GRID_FULL: one thread per entry; with dcount (optional: the device word with the list's
+// length) n is the capacity the grid covers and the kernel stops at *dcount.  GRID_STRIDED (enqueued frames): dcount is required, n is
+// the capacity, and a capped grid strides over the *dcount entries present (the *_strided kernels).
+enum ListGrid { GRID_FULL, GRID_STRIDED };
 // k_spawn: shadow rays of every hit -> the level's shadow list; mirror rays -> the next level's list; lvl[2i+1] = {ks, child}
-hipError_t launch_spawn(const float* rays, const CgrtHitDev* hits, const float* normals, const int* pixels, unsigned long long n,
-                        const float* materials, const float* lights, unsigned nlights, int spawn, float* srays, float* sdist, int* sslot,
-                        float* lvl, float* next_rays, int* next_pixels, uint32_t* counters, hipStream_t s, const uint32_t* dcount = nullptr);
+hipError_t launch_spawn(const LevelDev& V, const FrameConst& K, unsigned long long n, hipStream_t s, const uint32_t* dcount = nullptr,
+                        ListGrid grid = GRID_FULL);
 // k_shade: lvl[2i] = {direct light, flags}
-hipError_t launch_shade(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
-                        const int* sslot, unsigned long long n, const float* materials, const float* lights, unsigned nlights,
-                        const float* slights, unsigned nslights, const uint32_t* lit, unsigned samples, float* lvl, hipStream_t s,
-                        const uint32_t* dcount = nullptr);  // dcount (optional): device word with the list's length (<= n, the capacity the grid covers)
-// colour of level `lvl` entries += colour of their child (level lvl + 1) * ks  (main.cpp:262)
-// dcount (optional, also launch_write_rgb): the list's length on the device; n is then its capacity
-hipError_t launch_fold(float* lvl, const float* child_lvl, unsigned long long n, hipStream_t s, const uint32_t* dcount = nullptr);
-// child_lvl (optional): level 0 is folded with level 1 on the fly (colour + childColour * ks, main.cpp:262) instead of by launch_fold
-hipError_t launch_write_rgb(const float* lvl0, const float* child_lvl, unsigned long long n, const int* item_pixels, float* rgb, hipStream_t s,
-                            const uint32_t* dcount = nullptr);
-// the shading kernels' count-driven forms (enqueued frames): dcount required, n the capacity; a capped grid strides over *dcount entries
-hipError_t launch_spawn_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const int* pixels, unsigned long long n,
-                                const float* materials, const float* lights, unsigned nlights, int spawn, float* srays, float* sdist, int* sslot,
-                                float* lvl, float* next_rays, int* next_pixels, uint32_t* counters, hipStream_t s, const uint32_t* dcount);
-hipError_t launch_shade_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
-                                const int* sslot, unsigned long long n, const float* materials, const float* lights, unsigned nlights,
-                                const float* slights, unsigned nslights, const uint32_t* lit, unsigned samples, float* lvl, hipStream_t s,
-                                const uint32_t* dcount);
-hipError_t launch_fold_strided(float* lvl, const float* child_lvl, unsigned long long n, hipStream_t s, const uint32_t* dcount);
-hipError_t launch_write_rgb_strided(const float* lvl0, const float* child_lvl, unsigned long long n, const int* item_pixels, float* rgb, hipStream_t s,
-                                    const uint32_t* dcount);
-// light sets (cgrt_render_light_sets*): set b's direct colour of entry i -> out[b * stride + i] = {colour, flags} (k_shade_sets); npos /
-// nsph: the batch's distinct point positions (sslot's row) and spherical keys (lit's row); dcount as launch_shade
-hipError_t launch_shade_sets(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
-                             const int* sslot, unsigned long long n, const float* materials, unsigned npos, unsigned nsph, const uint32_t* lit,
-                             unsigned samples, const SetsDev& T, float* out, unsigned long long stride, hipStream_t s, const uint32_t* dcount = nullptr);
-// launch_fold / launch_write_rgb per set (n entries, nsets sets of colours `stride` entries apart; lvl / lvl0: the level's link records);
-// set b's frame starts at rgb + 3 * b * frame_pixels
-hipError_t launch_fold_sets(const float* lvl, float* sets_lvl, const float* child_sets, unsigned long long n, unsigned long long stride, unsigned nsets,
-                            hipStream_t s);
-hipError_t launch_write_rgb_sets(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n, unsigned long long stride,
-                                 unsigned nsets, const int* item_pixels, float* rgb, unsigned long long frame_pixels, hipStream_t s);
-// multi-view light sets (cgrt_render_views_light_sets*): item_pixels are a multi-view frame's (view * view_pixels + in-view pixel), and set
-// s's colour of a pixel of view v goes to frame v * nsets + s: rgb + 3 * ((v * nsets + s) * view_pixels + in-view pixel)
-hipError_t launch_write_rgb_views_sets(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n, unsigned long long stride,
-                                       unsigned nsets, const int* item_pixels, float* rgb, unsigned long long view_pixels, hipStream_t s);
-// the count-driven forms of the light sets' kernels (enqueued batches): n is the list's capacity, *dcount its length
-hipError_t launch_shade_sets_strided(const float* rays, const CgrtHitDev* hits, const float* normals, const CgrtHitDev* shits, const float* sdist,
-                                     const int* sslot, unsigned long long n, const float* materials, unsigned npos, unsigned nsph, const uint32_t* lit,
-                                     unsigned samples, const SetsDev& T, float* out, unsigned long long stride, hipStream_t s, const uint32_t* dcount);
-hipError_t launch_fold_sets_strided(const float* lvl, float* sets_lvl, const float* child_sets, unsigned long long n, unsigned long long stride,
-                                    unsigned nsets, hipStream_t s, const uint32_t* dcount);
-hipError_t launch_write_rgb_views_sets_strided(const float* lvl0, const float* sets0, const float* child_sets, unsigned long long n,
-                                               unsigned long long stride, unsigned nsets, const int* item_pixels, float* rgb,
-                                               unsigned long long view_pixels, hipStream_t s, const uint32_t* dcount);
+hipError_t launch_shade(const LevelDev& V, const FrameConst& K, unsigned long long n, hipStream_t s, const uint32_t* dcount = nullptr,
+                        ListGrid grid = GRID_FULL);
+// colour of the level's entries += colour of their child (the next level) * ks  (main.cpp:262)
+hipError_t launch_fold(const LevelDev& V, unsigned long long n, hipStream_t s, const uint32_t* dcount = nullptr, ListGrid grid = GRID_FULL);
+// level 0's colours to K.rgb; with_child: level 0 is folded with level 1 on the fly (colour + childColour * ks, main.cpp:262) instead of
+// by launch_fold
+hipError_t launch_write_rgb(const LevelDev& V0, const FrameConst& K, bool with_child, unsigned long long n, hipStream_t s,
+                            const uint32_t* dcount = nullptr, ListGrid grid = GRID_FULL);
+// light sets (cgrt_render_light_sets*): set b's direct colour of entry i -> V.sets (k_shade_sets); K.nlights / K.nslights: the batch's
+// distinct point positions and spherical keys
+hipError_t launch_shade_sets(const LevelDev& V, const FrameConst& K, const SetsDev& T, unsigned long long n, hipStream_t s,
+                             const uint32_t* dcount = nullptr, ListGrid grid = GRID_FULL);
+// launch_fold / launch_write_rgb per set (n entries, V.nsets sets of colours V.stride entries apart); set b's frame starts at
+// K.rgb + 3 * b * K.frame_pixels.  views (multi-view light sets, cgrt_render_views_light_sets*: k_write_rgb_views_sets): the pixels are
+// a multi-view frame's (view * frame_pixels + in-view pixel), and set s's colour of a pixel of view v goes to frame v * nsets + s
+hipError_t launch_fold_sets(const LevelDev& V, unsigned long long n, hipStream_t s);
+hipError_t launch_write_rgb_sets(const LevelDev& V0, const FrameConst& K, bool views, bool with_child, unsigned long long n, hipStream_t s);
+// the count-driven forms of the two (enqueued batches; one grid row for every set, so not GRID_STRIDED of the above): n is the list's
+// capacity, *dcount its length
+hipError_t launch_fold_sets_strided(const LevelDev& V, unsigned long long n, hipStream_t s, const uint32_t* dcount);
+hipError_t launch_write_rgb_views_sets_strided(const LevelDev& V0, const FrameConst& K, bool with_child, unsigned long long n, hipStream_t s,
+                                               const uint32_t* dcount);
 // the anti-aliased frame (main.cpp:663-687) from the 2W x 2H sub-sample frame `sub` of F: see k_resolve_aa (shade_kernels.hip).
 // out: F.nst_rank * 1024 * 3 floats (packed) or (F.W / 2) * (F.H / 2) * 3 floats
 hipError_t launch_resolve_aa(const FrameDev& F, const float* sub, float* out, int packed, hipStream_t s);
@@ -213,10 +226,9 @@ struct AovDev {
 // item_pixels[i]; position = origin + direction * t in cgrt_math.h's arithmetic.  launch_aov_scatter_strided: n is the list's capacity,
 // *dcount its length, a capped grid strides over the entries present (enqueued frames).
 hipError_t launch_aov_fill(const AovDev& A, hipStream_t s);
-hipError_t launch_aov_scatter(const AovDev& A, const float* rays, const CgrtHitDev* hits, const float* normals, const int* item_pixels,
-                              const float* materials, unsigned long long n, hipStream_t s);
-hipError_t launch_aov_scatter_strided(const AovDev& A, const float* rays, const CgrtHitDev* hits, const float* normals, const int* item_pixels,
-                                      const float* materials, unsigned long long n, hipStream_t s, const uint32_t* dcount);
+hipError_t launch_aov_scatter(const AovDev& A, const LevelDev& V0, const float* materials, unsigned long long n, hipStream_t s);
+hipError_t launch_aov_scatter_strided(const AovDev& A, const LevelDev& V0, const float* materials, unsigned long long n, hipStream_t s,
+                                      const uint32_t* dcount);
 hipError_t launch_gather_calib(const void* table, unsigned long long nrecords, unsigned long long mult, unsigned long long add, float* sink,
                                hipStream_t s);
 hipError_t launch_fastdiv_check(const float* a, const float* d, unsigned long long n, unsigned long long* mismatches, float* first_bad,
