@@ -238,7 +238,7 @@ _lib: Optional[C.CDLL] = None
 
 # every symbol include/cgrt.h declares
 EXPORTS = [
-    "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
+    "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
     "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
@@ -281,6 +281,8 @@ def lib() -> C.CDLL:
     L.cgrt_set_kernel_shape.argtypes = [i32, u64]
     L.cgrt_set_render_prediction.argtypes = [i32]
     L.cgrt_set_frame_hints.argtypes = [i32]
+    L.cgrt_set_frame_gate.argtypes = [i32]
+    L.cgrt_debug_frame_gate.argtypes = [vp, C.POINTER(Camera), i32, i32, C.POINTER(i32)]
     L.cgrt_debug_set_hint_thresholds.argtypes = [u32, u32]
     L.cgrt_debug_render_path.argtypes = [C.c_void_p]
     L.cgrt_get_kernel_shape.argtypes = [C.POINTER(i32), C.POINTER(u64)]
@@ -465,6 +467,12 @@ def set_frame_hints(mode: int = -1) -> None:
     _check(lib().cgrt_set_frame_hints(int(mode)))
 
 
+def set_frame_gate(enabled: bool = True) -> None:
+    """Camera frames: waves whose pixels all lie outside the root box's screen rectangle write their misses without tracing (default),
+    or every pixel takes the per-pixel root gate; same bytes either way."""
+    _check(lib().cgrt_set_frame_gate(1 if enabled else 0))
+
+
 def debug_set_hint_thresholds(dense_ticks: int = 0, sparse_ticks: int = 0) -> None:
     _check(lib().cgrt_debug_set_hint_thresholds(int(dense_ticks), int(sparse_ticks)))
 
@@ -642,6 +650,14 @@ class Scene:
         out = (C.c_uint32 * 3)()
         _check(lib().cgrt_debug_hint_counts(self._h, out))
         return [int(v) for v in out]
+
+    def frame_gate(self, cam, W: int, H: int):
+        """cgrt_debug_frame_gate: (x0, y0, x1, y1) -- every pixel of the W x H frame outside it misses the mesh root gate ((0, 0, 0, 0):
+        every pixel does) -- or None when the host computes no rectangle for this camera (the frame is not gated).  Host-only scenes too."""
+        out = (C.c_int * 5)()
+        c = cam if isinstance(cam, Camera) else Camera.from_array(cam)
+        _check(lib().cgrt_debug_frame_gate(self._h, C.byref(c), int(W), int(H), out))
+        return (int(out[0]), int(out[1]), int(out[2]), int(out[3])) if out[4] else None
 
     def last_render_path(self) -> int:
         """0 = the last render() sized every list exactly, 1 = drawn as the previous frame predicted, 2 = predicted, too small, drawn again."""

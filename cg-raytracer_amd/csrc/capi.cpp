@@ -50,6 +50,7 @@ std::atomic<int> g_call_combining{1};  // cgrt_set_call_combining
 std::atomic<int> g_render_predict{1};  // cgrt_set_render_prediction
 std::atomic<int> g_frame_hints{-1};    // cgrt_set_frame_hints: -1 auto, 0 off, 1 hard tiles first, 2 hard tiles 16 rays per wave
 std::atomic<unsigned> g_hint_thr_dense{0}, g_hint_thr_sparse{0};  // cgrt_debug_set_hint_thresholds (0: the defaults)
+std::atomic<int> g_frame_gate{1};      // cgrt_set_frame_gate: 1 = tiles outside the root box's screen rectangle skip their rays, 0 = off
 std::atomic<int> g_primary_mode{0};  // 0 = one wave per tile, 1 = persistent waves with lane refill
 
 int fail(int code, const std::string& msg) {
@@ -137,6 +138,7 @@ bool make_frame(int W, int H, int x0, int y0, int x1, int y1, int rank, int nran
     F.hint_blocks = F.hint_rgen = F.hint_wgen = 0;
     F.views = nullptr;
     F.view_st = 0;
+    F.gate_x0 = F.gate_y0 = F.gate_x1 = F.gate_y1 = 0;  // no gate (apply_frame_gate)
     return true;
 }
 
@@ -149,6 +151,92 @@ bool make_views_frame(int W, int H, uint32_t nviews, int block, FrameDev& F) {
     F.view_st = (uint32_t)view_st;
     F.nst_rank = (uint32_t)nst;
     F.nblocks = ((F.nst_rank + 7u) / 8u) * 8u * (64u / ((uint32_t)block / 64u));
+    return true;
+}
+
+// Frame gate (FrameDev::gate_*): a pixel rectangle of the W x H frame outside which every primary ray of camera C fails
+// the mesh root gate, walk_begin's `starts_in_box(o, lo, hi) || ray_box(lo, hi, o, d, t, tb)` in its float arithmetic.  All in float64:
+//   * the box is widened plane by plane by 2^-20 |plane - o|: the gate's six quotients fl(fl(plane - o) / d) are each within 2^-23 of
+//     the exact quotient, so the float verdict "enters" implies that the ray (o, d) of the float direction d meets the widened box;
+//   * the eight corners of the widened box are taken through the inverse of primary_ray -- M^-1 (corner - o), M the matrix of
+//     quat_rotate for the float quaternion as it is (not assumed unit) -- and divided by their depth: the box being convex and
+//     wholly in front of the camera plane, a ray that meets it passes the image plane inside the hull of the eight projections, hence
+//     inside their bounding rectangle (pixel x samples the plane at ndc fl(x / W) * 2 - 1: no half-pixel offset);
+//   * the rectangle is widened by one whole pixel plus 2^-18 W (1 + hw^2 + hh^2) / hw pixels (H, hh for y): d differs from the exact
+//     direction of the pixel by less than 2^-20 per component (ndc, normalisation and rotation, about twenty roundings of values <= 2),
+//     an angle below 2^-19, which moves the point on the image plane by less than 2^-19 (1 + hw^2 + hh^2), i.e. half the second term.
+// No rectangle (false) whenever that argument does not apply as it stands:
+//   non-finite camera or box values, half extents outside 2^-40 .. 2^40, coordinates outside the fast_boxes envelope (0 or 2^-40 ..
+//   2^40 in magnitude, box and origin); the origin inside or on the widened box, or exactly on one of the six box planes (a zero
+//   direction component then makes the gate's quotient 0/0 and its ternaries order-sensitive); a corner behind the camera plane or
+//   closer to it than 2^-20 of its distance from the origin.
+// The caller adds what is not geometry: scenes with spheres (resolve_hit tests them for rays that failed the gate), scenes without a
+// tree (root_ref == REF_NONE), the switch.  out = {x0, y0, x1, y1} clipped to the frame; {0, 0, 0, 0}: every pixel misses.
+bool frame_gate_rect(const CameraDev& C, const Box6& box, int W, int H, int out[4]) {
+    const double hw = C.half_w, hh = C.half_h;
+    // (half extents in 2^-40 .. 2^40, like the coordinates: the float normalisation of (-px hw, py hh, 1) then neither overflows nor loses
+    // a component, which the direction bound above takes for granted)
+    if (!(hw >= 9.094947017729282e-13) || !(hh >= 9.094947017729282e-13) || !(hw <= 1099511627776.0) || !(hh <= 1099511627776.0) || W <= 0 || H <= 0) return false;
+    auto in_envelope = [](float v) {
+        const float a = std::fabs(v);
+        return v == 0.0f || (a >= 9.094947017729282e-13f && a <= 1099511627776.0f);  // (false for NaN and inf)
+    };
+    double o[3], lo[3], hi[3];
+    bool inside = true;
+    for (int k = 0; k < 3; k++) {
+        if (!in_envelope(C.pos[k]) || !in_envelope(box.lo[k]) || !in_envelope(box.hi[k]) || !(box.lo[k] <= box.hi[k])) return false;
+        if (C.pos[k] == box.lo[k] || C.pos[k] == box.hi[k]) return false;
+        o[k] = C.pos[k];
+        const double r = 9.5367431640625e-07;  // 2^-20
+        lo[k] = (double)box.lo[k] - r * std::fabs((double)box.lo[k] - o[k]);
+        hi[k] = (double)box.hi[k] + r * std::fabs((double)box.hi[k] - o[k]);
+        inside = inside && lo[k] <= o[k] && o[k] <= hi[k];
+    }
+    if (inside) return false;
+    for (int k = 0; k < 4; k++)
+        if (!std::isfinite(C.q[k])) return false;
+    // quat_rotate(q, v) = v + 2 (w (q x v) + q x (q x v)): its matrix, column by column, and the inverse by cofactors
+    const double w = C.q[0], q[3] = {C.q[1], C.q[2], C.q[3]};
+    double M[3][3];
+    for (int c = 0; c < 3; c++) {
+        double v[3] = {0, 0, 0};
+        v[c] = 1.0;
+        const double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
+        const double uuv[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+        for (int r = 0; r < 3; r++) M[r][c] = v[r] + 2.0 * (w * uv[r] + uuv[r]);
+    }
+    const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
+                       M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+    if (!(std::fabs(det) > 0.5) || !std::isfinite(det)) return false;  // (1 for a unit quaternion)
+    double I[3][3];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            const int a = (c + 1) % 3, b = (c + 2) % 3, e = (r + 1) % 3, f = (r + 2) % 3;  // cofactor of M[c][r]
+            I[r][c] = (M[a][e] * M[b][f] - M[a][f] * M[b][e]) / det;
+        }
+    double xmin = HUGE_VAL, xmax = -HUGE_VAL, ymin = HUGE_VAL, ymax = -HUGE_VAL;
+    for (int corner = 0; corner < 8; corner++) {
+        const double p[3] = {((corner & 1) ? hi[0] : lo[0]) - o[0], ((corner & 2) ? hi[1] : lo[1]) - o[1], ((corner & 4) ? hi[2] : lo[2]) - o[2]};
+        double v[3];
+        for (int r = 0; r < 3; r++) v[r] = I[r][0] * p[0] + I[r][1] * p[1] + I[r][2] * p[2];
+        const double dist = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        if (!(v[2] > 9.5367431640625e-07 * dist) || !std::isfinite(dist)) return false;  // at, behind or too close to the camera plane
+        // primary_ray: the camera-space direction is (-px * hw, py * hh, 1), px = x / W * 2 - 1
+        const double xf = (-(v[0] / v[2]) / hw + 1.0) * 0.5 * (double)W, yf = ((v[1] / v[2]) / hh + 1.0) * 0.5 * (double)H;
+        xmin = std::min(xmin, xf), xmax = std::max(xmax, xf);
+        ymin = std::min(ymin, yf), ymax = std::max(ymax, yf);
+    }
+    const double rel = 3.814697265625e-06 * (1.0 + hw * hw + hh * hh);  // 2^-18 (1 + hw^2 + hh^2)
+    const double mx = 1.0 + rel * (double)W / hw, my = 1.0 + rel * (double)H / hh;
+    if (!std::isfinite(xmin) || !std::isfinite(xmax) || !std::isfinite(ymin) || !std::isfinite(ymax) || !std::isfinite(mx) || !std::isfinite(my)) return false;
+    // pixels x with x < xmin - mx or x > xmax + mx are outside: [floor(xmin - mx), floor(xmax + mx) + 1) keeps the rest
+    const double x0 = std::floor(xmin - mx), x1 = std::floor(xmax + mx) + 1.0, y0 = std::floor(ymin - my), y1 = std::floor(ymax + my) + 1.0;
+    const double cx0 = std::max(x0, 0.0), cx1 = std::min(x1, (double)W), cy0 = std::max(y0, 0.0), cy1 = std::min(y1, (double)H);
+    if (cx0 >= cx1 || cy0 >= cy1) {
+        out[0] = out[1] = out[2] = out[3] = 0;
+        return true;
+    }
+    out[0] = (int)cx0, out[1] = (int)cy0, out[2] = (int)cx1, out[3] = (int)cy1;
     return true;
 }
 
@@ -1662,9 +1750,40 @@ static int attach_hints(CgrtScene* s, FrameDev& F, hipStream_t stream) {
     return CGRT_OK;
 }
 
+// The frame gate of one camera launch (frame_gate_rect): F's rectangle, or none.  What disables it beyond the geometry: the switch, a
+// scene with spheres (resolve_hit tests every sphere for a ray that failed the mesh root gate) and a scene without a tree (walk_begin
+// returns before the gate).  Nothing else is evaluated for such a ray: finish_ray writes {t as given, no primitive, no material, hit = 0}.
+static bool scene_frame_gate(const CgrtScene* s, const CameraDev& C, int W, int H, int out[4]) {
+    if (!s->bvh.spheres.empty() || s->bvh.root_ref == REF_NONE) return false;
+    return frame_gate_rect(C, s->bvh.root_box, W, H, out);
+}
+static void apply_frame_gate(const CgrtScene* s, const CameraDev& C, FrameDev& F) {
+    int r[4];
+    F.gate_x0 = F.gate_y0 = F.gate_x1 = F.gate_y1 = 0;
+    if (!g_frame_gate.load() || !scene_frame_gate(s, C, F.W, F.H, r)) return;
+    if (r[2] == 0) {  // every pixel misses: a rectangle no pixel is inside of (gate_x1 != 0: the gate is on)
+        F.gate_x0 = F.gate_y0 = F.gate_x1 = F.gate_y1 = 0x7fffffff;
+        return;
+    }
+    F.gate_x0 = r[0], F.gate_y0 = r[1], F.gate_x1 = r[2], F.gate_y1 = r[3];
+}
+int cgrt_set_frame_gate(int mode) {
+    if (mode != 0 && mode != 1) return fail(CGRT_E_ARG, "frame gate mode: 1 on (default), 0 off");
+    g_frame_gate.store(mode);
+    return CGRT_OK;
+}
+int cgrt_debug_frame_gate(const CgrtScene* s, const CgrtCamera* cam, int W, int H, int* out5) {
+    if (!s || !cam || !out5) return fail(CGRT_E_ARG, "NULL argument");
+    if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
+    out5[0] = out5[1] = out5[2] = out5[3] = 0;
+    out5[4] = scene_frame_gate(s, make_camera(*cam), W, H, out5) ? 1 : 0;
+    return CGRT_OK;
+}
+
 static int launch_primary(CgrtScene* s, const CameraDev& C, const FrameDev& F_in, CgrtHitDev* d_hits, float* d_normals, unsigned long long* counters,
                           hipStream_t stream) {
     FrameDev F = F_in;
+    apply_frame_gate(s, C, F);
     if (g_primary_mode.load() == 0 && !counters) {  // (the instrumented and the persistent kernels take no hints)
         std::lock_guard<std::mutex> lk(s->hints.mu);
         const int rc = attach_hints(s, F, stream);
@@ -2424,6 +2543,7 @@ static int render_impl(CgrtScene* s, const FrameRequest& R) {
         if (sets) Q.set_index = dsettab.as<uint32_t>() + 2 * ((size_t)nsets + 1);
     }
     const CameraDev C = (list || views) ? CameraDev{} : make_camera(*R.cam);
+    if (!list && !views) apply_frame_gate(s, C, F);  // (one camera: the compact primary kernel of every path below)
     if (views) {  // (the table of the VIEWS kernels; this call waits for its frame, so the slot is free again when it returns)
         const std::vector<uint8_t> tab = view_table(views->cams, views->raycams, nviews);
         HIP_TRY(dviews.alloc(tab.size()));
@@ -3437,9 +3557,12 @@ static int enqueue_impl(CgrtScene* s, const FrameRequest& R) {
             else if (views)  // (also clears every view's pixels)
                 HIP_TRY(launch_trace_primary_views_compact(s->dev, F, V0.rays, V0.hits, V0.normals, V0.pixels, primary_hits, frame_rgb, stream,
                                                            views->raycams != nullptr));
-            else  // (also clears this rank's pixels, and spawns level 0)
-                HIP_TRY(launch_trace_primary_compact(s->dev, make_camera(*R.cam), F, V0.rays, V0.hits, V0.normals, V0.pixels, pair, stream, nullptr,
+            else {  // (also clears this rank's pixels, and spawns level 0)
+                const CameraDev C = make_camera(*R.cam);
+                apply_frame_gate(s, C, F);
+                HIP_TRY(launch_trace_primary_compact(s->dev, C, F, V0.rays, V0.hits, V0.normals, V0.pixels, pair, stream, nullptr,
                                                      frame_rgb, reinterpret_cast<const SpawnDev*>(tab + o_spawn)));
+            }
             if (nsets > 1)  // (as render_impl: the views' kernel cleared the first nviews * W * H pixels, a miss is black in every set)
                 HIP_TRY(hipMemsetAsync(frame_rgb + 3ull * W * H * nviews, 0, (npix - (unsigned long long)W * H * nviews) * 12, stream));
             const bool pairable = can_trace_pair(s->dev);
@@ -4217,6 +4340,7 @@ int cgrt_trace_primary_multi(CgrtScene* const* scenes, int nscenes, const CgrtCa
         Part& P = part[i];
         if (!make_frame(W, H, 0, 0, W, H, i, nscenes, trace_block(scenes[i]->dev), P.F)) return fail(CGRT_E_ARG, "bad frame");
         P.F.packed = 1;
+        apply_frame_gate(scenes[i], C, P.F);
         P.n = (size_t)P.F.nblocks * (size_t)P.F.block;
         if (P.n == 0) continue;
         HIP_TRY(hipSetDevice(scenes[i]->device));

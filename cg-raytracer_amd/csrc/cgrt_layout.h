@@ -237,6 +237,10 @@ struct FrameDev {
         const RayCameraDev* raycams;
     };
     uint32_t view_st;      // super-tiles per view (st_x * st_y)
+    // Frame gate (capi.cpp frame_gate_rect): pixels of the full frame outside [gate_x0, gate_x1) x [gate_y0, gate_y1)
+    // miss the mesh root gate whatever else is true of them, so a wave whose pixels all lie outside writes its miss records without
+    // generating a ray.  gate_x1 == 0: no gate (what FrameDev{} and make_frame leave).  Read by the CameraDev frame kernels only, the hinted instantiation excepted.
+    int gate_x0, gate_y0, gate_x1, gate_y1;
 };
 static const int ST_TILES = 8;  // tiles per super-tile side
 // Workgroups of the traversal kernels hold 64, 128 or 256 threads (chosen per launch: FrameDev::block, blockDim.x): one wave

@@ -48,6 +48,15 @@ __device__ __forceinline__ size_t view_pixel(const FrameDev& F, uint32_t view, i
     return (size_t)view * (size_t)F.W * (size_t)F.H + (size_t)y * F.W + x;
 }
 
+// Frame gate (FrameDev::gate_*, capi.cpp frame_gate_rect): true for the whole wave when none of its lanes has a pixel
+// inside the rectangle outside which every ray fails the mesh root gate -- the wave then needs no ray.  One scalar test when the
+// launch carries no rectangle; four compares and a ballot otherwise.
+__device__ __forceinline__ bool wave_outside_gate(const FrameDev& F, const bool active, const int x, const int y) {
+    if (F.gate_x1 == 0) return false;
+    const bool inside = active && x >= F.gate_x0 && x < F.gate_x1 && y >= F.gate_y0 && y < F.gate_y1;
+    return __ballot(inside) == 0ull;
+}
+
 // HINT: the launch carries frame hints (cgrt_layout.h HintDev) -- an instantiation of its own, so that the plain frame kernel is the
 // kernel it was (the hint code costs every launch a few percent when it is merely compiled in: measured).
 // VIEWS: a multi-view frame (FrameDev::views, cgrt_trace_primary_views_device) -- also an instantiation of its own, for the same
@@ -72,6 +81,21 @@ __global__ CGRT_LB void k_trace_primary(SceneDev S, CameraDev C, FrameDev F, Cgr
     } else {
         if (HINT && (threadIdx.x & 63u) == 0u) CGRT_HINT_SCRATCH(s_lds)[1] = 0xffffffffu;  // nothing for hint_finish
         active = frame_pixel<QUAD, VIEWS>(F, x, y, pidx, writer, &view);
+    }
+    // The counting instantiations take every pixel through the per-pixel gate (their counters are the per-pixel path's), the multi-view
+    // ones carry no rectangle, and the hinted one is the kernel it was: its frames are as long as their longest wave, not their empty ones
+    // (DESIGN.md 5.22).  A wave outside the rectangle writes what finish_ray writes for a ray that failed the root gate of a scene
+    // without spheres -- the same 16 bytes at the same address, no normal -- and ends.
+    if (!COUNT && !VIEWS && !HINT && wave_outside_gate(F, active, x, y)) {
+        if (active && writer) {
+            CgrtHitDev miss;
+            miss.t = 3.402823466e+38f;
+            miss.prim_id = 0xffffffffu;
+            miss.material_id = -1;
+            miss.hit = 0u;
+            hits[F.packed ? pidx : (size_t)y * F.W + x] = miss;
+        }
+        return;
     }
     LaneCounters cnt;
     F3 o = f3(0, 0, 0), d = f3(0, 0, 0);
@@ -112,11 +136,14 @@ __global__ CGRT_LB void k_trace_primary_compact(SceneDev S, CameraDev C, FrameDe
     size_t pidx;
     bool writer;
     uint32_t view = 0;
-    const bool active = frame_pixel<QUAD, VIEWS>(F, x, y, pidx, writer, &view);
-    if (active && writer && rgb) {  // every pixel this rank owns starts black (main.cpp:293); the hits are written over it at the end of the frame
+    const bool owned = frame_pixel<QUAD, VIEWS>(F, x, y, pidx, writer, &view);
+    if (owned && writer && rgb) {  // every pixel this rank owns starts black (main.cpp:293); the hits are written over it at the end of the frame
         float* p = rgb + 3ull * (VIEWS ? view_pixel(F, view, x, y) : (unsigned long long)y * F.W + x);
         p[0] = p[1] = p[2] = 0.0f;
     }
+    // A wave outside the frame gate (wave_outside_gate; never the counting and the multi-view instantiations) traces nothing: its pixels
+    // miss, and a miss appends nothing.  It stays for the workgroup's count below.
+    const bool active = owned && !(!COUNT && !VIEWS && wave_outside_gate(F, owned, x, y));
     LaneCounters cnt;
     CgrtHitDev h;
     h.hit = 0;

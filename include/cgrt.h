@@ -138,6 +138,16 @@ int cgrt_get_kernel_shape(int* mode, uint64_t* max_rays);
  * streams the library falls back to unhinted launches for a few frames (the *_device entries stay safe to call from several
  * threads, they are just not accelerated then).  Process-wide. */
 int cgrt_set_frame_hints(int mode);
+/* Frame gate of the camera frames (cgrt_trace_primary*, cgrt_render* with one CgrtCamera): 1 (default) = the host projects the mesh
+ * root box onto the screen per launch, and a wave whose pixels all lie outside that rectangle (widened by a margin)
+ * writes its miss records without generating rays; 0 = every pixel takes the per-pixel root gate.  Same bytes either way (tested).
+ * Scenes with spheres, cameras inside or on the box, a box that reaches behind the camera, launches that carry frame hints (small
+ * frames, cgrt_set_frame_hints), ray cameras and multi-view batches are never gated.  Process-wide. */
+int cgrt_set_frame_gate(int mode);
+/* Diagnostics: the rectangle the host computes for this camera and a W x H frame, out5 = {x0, y0, x1, y1, valid}: with valid == 1
+ * every pixel with x < x0, x >= x1, y < y0 or y >= y1 misses the root gate ({0, 0, 0, 0} when every pixel does); valid == 0: no
+ * rectangle, the frame is not gated.  Does not depend on cgrt_set_frame_gate.  Works on host-only scenes. */
+int cgrt_debug_frame_gate(const CgrtScene* scene, const CgrtCamera* cam, int W, int H, int* out5);
 /* Tests: the wall time (s_memrealtime ticks, 100 MHz) from which a 64-ray / a 16-ray wave puts its tile on the hard list; 0 = the
  * default (4500 = 45 us, the floor of the adaptive threshold; a 16-ray wave counts from 5/9 of the threshold in force, the second
  * argument is ignored).  With a few ticks every tile that reaches the tree is "hard" and the lists overflow. */
