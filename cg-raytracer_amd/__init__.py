@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import warnings
 from typing import Optional, Tuple
 
 import numpy as np
@@ -221,6 +222,46 @@ def raycam_array(cams) -> np.ndarray:
 
 HOST_LIB_PATH = os.path.join(_HERE, "lib", "libcgrt_host.so")
 
+_surface_fn = None
+
+
+def _surface_function():
+    """The torch.autograd.Function behind interpolate_hits_tensor / surface_views_tensor / surface_raycams_tensor when attr requires grad
+    (DESIGN.md section 5.23): apply(attr, forward, backward, which=None).  forward(attr.detach()) is the ordinary, non-recording call (a
+    tensor, or a tuple of which entry `which` is the attribute and the others, the barycentrics, are marked non-differentiable);
+    backward(grad) is the matching *_grad_tensor call on torch.cuda.current_stream().  Only attr gets a gradient: rays, hits, planes and
+    cameras are held as given and are not differentiable."""
+    global _surface_fn
+    if _surface_fn is not None:
+        return _surface_fn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class SurfaceAttribute(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, attr, forward, backward, which=None):
+            ctx.backward_call, ctx.which = backward, which
+            res = forward(attr.detach())
+            if which is not None:
+                ctx.mark_non_differentiable(*(t for k, t in enumerate(res) if k != which))
+            return res
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, *grads):
+            if torch.are_deterministic_algorithms_enabled():
+                msg = ("the surface-attribute backward adds into the table with float atomics: the order of the additions into one element "
+                       "is unspecified and the last bits of the gradient may differ from run to run")
+                if torch.is_deterministic_algorithms_warn_only_enabled():
+                    warnings.warn(msg, UserWarning, stacklevel=2)
+                else:
+                    raise RuntimeError(msg + " (torch.use_deterministic_algorithms(True) is set)")
+            g = grads[0 if ctx.which is None else ctx.which]
+            return ctx.backward_call(g.contiguous()), None, None, None
+
+    _surface_fn = SurfaceAttribute
+    return _surface_fn
+
 
 def build_native(verbose: bool = False) -> str:
     """Compile libcgrt.so for gfx950 in-tree (hipcc cross-compiles without a GPU), then the C++ host mirror of the
@@ -240,7 +281,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -357,6 +398,10 @@ def lib() -> C.CDLL:
     L.cgrt_interpolate_hits_device.argtypes = [vp, vp, vp, u64, vp, u32, vp, vp]
     L.cgrt_surface_views_device.argtypes = [vp, vp, u32, i32, i32, vp, vp, vp, u32, vp, vp, i32, vp]
     L.cgrt_surface_raycams_device.argtypes = L.cgrt_surface_views_device.argtypes
+    L.cgrt_interpolate_hits_grad.argtypes = [vp, vp, vp, u64, vp, u32, vp]
+    L.cgrt_interpolate_hits_grad_device.argtypes = [vp, vp, vp, u64, vp, u32, vp, vp]
+    L.cgrt_surface_views_grad_device.argtypes = [vp, vp, u32, i32, i32, vp, vp, vp, u32, i32, vp, vp]
+    L.cgrt_surface_raycams_grad_device.argtypes = L.cgrt_surface_views_grad_device.argtypes
     L.cgrt_closest_points.argtypes = [vp, vp, u64, C.c_float, vp]
     L.cgrt_closest_points_brute.argtypes = [vp, vp, u64, C.c_float, vp]
     L.cgrt_closest_points_device.argtypes = [vp, vp, u64, C.c_float, vp, vp]
@@ -1779,11 +1824,91 @@ class Scene:
         lead, n = self._hits_tensor(rays, hits)
         attr = self._attr_tensor(attr)
         ch = attr.shape[1]
+        if attr.requires_grad and torch.is_grad_enabled():  # recorded: the output carries a grad_fn (interpolate_hits_grad_tensor)
+            if out is not None:
+                raise ValueError("out= cannot be combined with an attr that requires grad")
+            return _surface_function().apply(
+                attr, lambda a: self.interpolate_hits_tensor(rays, hits, a, stream=stream),
+                lambda g: self.interpolate_hits_grad_tensor(rays, hits, g))
         if out is not None:
             self._device_tensor(out, "out", (torch.float32,), lead + (ch,))
         return self._tensor_call(out, lead + (ch,), torch.float32, stream,
                                  lambda o, s: self.interpolate_hits_device(rays.data_ptr(), hits.data_ptr(), n, attr.data_ptr(), ch,
                                                                            o.data_ptr(), stream=s))
+
+    # ---- surface attributes: gradients back to the table (include/cgrt.h cgrt_interpolate_hits_grad*, cgrt_surface_*_grad_device;
+    # DESIGN.md section 5.23) ----
+    def interpolate_hits_grad(self, rays, hits, grad_out, grad_attr=None) -> np.ndarray:
+        """cgrt_interpolate_hits_grad, the adjoint of interpolate_hits with respect to attr: grad_out ((n, C) float32) is the gradient
+        with respect to interpolate_hits' result; alpha / beta / gamma times each valid item's row is ADDED into rows tri[prim_id][0..2]
+        of grad_attr -- a C-contiguous (nverts, C) float32 array that is accumulated into in place, or None for a new zero array.
+        Returns grad_attr.  The order of the additions into one element is unspecified (last bits may differ from run to run)."""
+        r = _as_ray_array(rays)
+        h = self._as_hit_array(hits, len(r))
+        g = np.ascontiguousarray(np.asarray(grad_out, np.float32))
+        if g.ndim == 1:
+            g = g.reshape(-1, 1)
+        if g.ndim != 2 or g.shape[0] != len(r):
+            raise ValueError(f"grad_out must have one row per ray: ({len(r)}, C), not {g.shape}")
+        nverts = len(_f32(self.sd.pos_nrm, (-1, 6)))
+        if grad_attr is None:
+            grad_attr = np.zeros((nverts, g.shape[1]), np.float32)
+        elif not (isinstance(grad_attr, np.ndarray) and grad_attr.dtype == np.float32 and grad_attr.flags.c_contiguous
+                  and grad_attr.flags.writeable and grad_attr.shape == (nverts, g.shape[1])):
+            raise ValueError(f"grad_attr must be a writeable C-contiguous float32 array of shape ({nverts}, {g.shape[1]})")
+        _check(lib().cgrt_interpolate_hits_grad(self._h, _ptr(r), _ptr(h), len(r), _ptr(g), g.shape[1], _ptr(grad_attr)))
+        return grad_attr
+
+    def interpolate_hits_grad_device(self, d_rays_ptr: int, d_hits_ptr: int, n: int, d_grad_out_ptr: int, channels: int,
+                                     d_grad_attr_ptr: int, stream: int = 0) -> None:
+        """cgrt_interpolate_hits_grad_device: n x channels floats at d_grad_out_ptr are added, weighted, into the (nverts, channels)
+        float32 table at d_grad_attr_ptr; enqueued on `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        _check(lib().cgrt_interpolate_hits_grad_device(self._h, vp(d_rays_ptr), vp(d_hits_ptr), int(n), vp(d_grad_out_ptr), int(channels),
+                                                       vp(d_grad_attr_ptr), vp(stream)))
+
+    def surface_views_grad_device(self, cams, W: int, H: int, d_depth_ptr: int, d_prim_id_ptr: int, d_grad_out_ptr: int, channels: int,
+                                  d_grad_attr_ptr: int, chw: bool = False, stream: int = 0, raycams: bool = False) -> None:
+        """cgrt_surface_views_grad_device (raycams: cgrt_surface_raycams_grad_device): the gradient (B, H, W, channels) -- (B, channels,
+        H, W) with chw -- of B frames' interpolated attribute, added into the table at d_grad_attr_ptr.  Raw integers; enqueued."""
+        a = raycam_array(cams) if raycams else camera_array(cams)
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        f = lib().cgrt_surface_raycams_grad_device if raycams else lib().cgrt_surface_views_grad_device
+        _check(f(self._h, _ptr(a) if len(a) else None, len(a), W, H, vp(d_depth_ptr), vp(d_prim_id_ptr), vp(d_grad_out_ptr), int(channels),
+                 1 if chw else 0, vp(d_grad_attr_ptr), vp(stream)))
+
+    def _grad_attr_tensor(self, grad_attr, channels: int, stream):
+        """The table a *_grad_tensor call accumulates into and the stream it runs on: the caller's (nverts, C) tensor, or new zeros."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        _check_one_hip_runtime()
+        nverts = len(_f32(self.sd.pos_nrm, (-1, 6)))
+        if grad_attr is None:
+            with torch.cuda.stream(stream):
+                grad_attr = torch.zeros((nverts, channels), dtype=torch.float32, device=dev)
+        else:
+            self._device_tensor(grad_attr, "grad_attr", (torch.float32,), (nverts, channels))
+        return grad_attr, stream
+
+    def interpolate_hits_grad_tensor(self, rays, hits, grad_out, grad_attr=None, stream=None):
+        """interpolate_hits_grad on torch tensors: rays, hits as interpolate_hits_tensor took them, grad_out (..., C) float32; added into
+        grad_attr ((nverts, C) float32 on the device, or None for a new zero tensor), which is returned.  Enqueued on `stream` (default:
+        torch.cuda.current_stream()).  interpolate_hits_tensor calls this in its backward when attr requires grad."""
+        import torch
+
+        lead, n = self._hits_tensor(rays, hits)
+        if not isinstance(grad_out, torch.Tensor) or grad_out.dim() != len(lead) + 1 or tuple(grad_out.shape[:-1]) != lead or \
+                not 1 <= grad_out.shape[-1] <= 256:
+            raise ValueError(f"grad_out must be a torch tensor of shape {lead + ('C',)}, C in 1..256")
+        self._device_tensor(grad_out, "grad_out", (torch.float32,))
+        ch = grad_out.shape[-1]
+        grad_attr, stream = self._grad_attr_tensor(grad_attr, ch, stream)
+        if n:
+            self.interpolate_hits_grad_device(rays.data_ptr(), hits.data_ptr(), n, grad_out.data_ptr(), ch, grad_attr.data_ptr(),
+                                              stream=stream.cuda_stream)
+        return grad_attr
 
     # ---- closest-point queries (include/cgrt.h cgrt_closest_points*; DESIGN.md section 5.20) ----
     def _closest_host(self, f, points, max_dist2: float) -> np.ndarray:
@@ -2050,6 +2175,19 @@ class Scene:
             if k not in want:
                 raise ValueError(f"out[{k!r}] given, but that output is not requested")
             self._device_tensor(t, f"out[{k!r}]", (torch.float32,), want[k])
+        if attr is not None and attr.requires_grad and torch.is_grad_enabled():  # recorded: 'attr' carries a grad_fn (_surface_frames_grad_tensor)
+            if "attr" in out:
+                raise ValueError("out['attr'] cannot be combined with an attr that requires grad")
+            keys = list(want)
+
+            def forward(table):
+                res = self._surface_frames_tensor(raycams, cams, W, H, depth, prim_id, table, want_bary, chw, out, stream)
+                return tuple(res[k] for k in keys)
+
+            got = _surface_function().apply(
+                attr, forward, lambda g: self._surface_frames_grad_tensor(raycams, cams, W, H, depth, prim_id, g, chw, None, None),
+                keys.index("attr"))
+            return dict(zip(keys, got))
         dev = torch.device("cuda", self.device)
         stream = torch.cuda.current_stream(dev) if stream is None else stream
         _check_one_hip_runtime()
@@ -2059,6 +2197,48 @@ class Scene:
                                   d_attr_ptr=0 if attr is None else attr.data_ptr(), channels=0 if attr is None else attr.shape[1],
                                   d_out_ptr=res["attr"].data_ptr() if "attr" in res else 0, chw=chw, stream=stream.cuda_stream, raycams=raycams)
         return res
+
+    def _surface_frames_grad_tensor(self, raycams, cams, W, H, depth, prim_id, grad_out, chw, grad_attr, stream):
+        import torch
+
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if raycams:
+            a = raycam_array(cams)
+        else:
+            if isinstance(cams, Camera):
+                cams = [cams]
+            elif isinstance(cams, np.ndarray) and cams.ndim == 1:
+                cams = cams.reshape(1, -1)
+            a = camera_array(cams)
+        B = len(a)
+        if not isinstance(depth, torch.Tensor) or tuple(depth.shape) not in ((B, H, W),) + (((H, W),) if B == 1 else ()):
+            raise ValueError(f"depth must be a torch tensor of shape {(B, H, W)}" + (f" or {(H, W)}" if B == 1 else ""))
+        lead = tuple(depth.shape[:-2])
+        self._device_tensor(depth, "depth", (torch.float32,))
+        self._device_tensor(prim_id, "prim_id", (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ()), depth.shape)
+        if not isinstance(grad_out, torch.Tensor) or grad_out.dim() != len(lead) + 3:
+            raise ValueError("grad_out must be a torch tensor in the layout of the forward's 'attr' output")
+        ch = grad_out.shape[-3] if chw else grad_out.shape[-1]
+        if not 1 <= ch <= 256:
+            raise ValueError("grad_out must have 1..256 channels")
+        self._device_tensor(grad_out, "grad_out", (torch.float32,), lead + ((ch, H, W) if chw else (H, W, ch)))
+        grad_attr, stream = self._grad_attr_tensor(grad_attr, ch, stream)
+        self.surface_views_grad_device(a, W, H, depth.data_ptr(), prim_id.data_ptr(), grad_out.data_ptr(), ch, grad_attr.data_ptr(), chw=chw,
+                                       stream=stream.cuda_stream, raycams=raycams)
+        return grad_attr
+
+    def surface_views_grad_tensor(self, cams, W: int, H: int, depth, prim_id, grad_out, chw: bool = False, grad_attr=None, stream=None):
+        """The adjoint of surface_views_tensor's 'attr' output with respect to the table: cams, W, H, depth and prim_id as the forward
+        took them, grad_out (B, H, W, C) float32 -- (B, C, H, W) with chw; (H, W, C) / (C, H, W) for one camera's (H, W) planes.  Added
+        into grad_attr ((nverts, C) float32 on the device, or None for a new zero tensor), which is returned: a running gradient over
+        several frames is one tensor passed again and again.  Enqueued on `stream` (default: torch.cuda.current_stream()).  The order of
+        the additions into one element is unspecified.  surface_views_tensor calls this in its backward when attr requires grad."""
+        return self._surface_frames_grad_tensor(False, cams, W, H, depth, prim_id, grad_out, chw, grad_attr, stream)
+
+    def surface_raycams_grad_tensor(self, cams, W: int, H: int, depth, prim_id, grad_out, chw: bool = False, grad_attr=None, stream=None):
+        """surface_views_grad_tensor for ray cameras."""
+        return self._surface_frames_grad_tensor(True, cams, W, H, depth, prim_id, grad_out, chw, grad_attr, stream)
 
     def surface_views_tensor(self, cams, W: int, H: int, depth, prim_id, attr=None, want_bary: bool = True, chw: bool = False, out=None,
                              stream=None):

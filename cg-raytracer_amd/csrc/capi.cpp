@@ -4039,7 +4039,125 @@ int surface_frames_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCam
         return launch_surface(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, st);
     });
 }
+
+// ---- the adjoint with respect to the table (include/cgrt.h cgrt_interpolate_hits_grad*, cgrt_surface_*_grad_device; DESIGN.md section
+// 5.23): twins of the entries above, grad_out in the place of out and grad_attr in the place of attr, the same checks in the same order.
+SurfaceGradDev surface_grad_dev(const CgrtScene* s, const SurfaceLookup* lookup, uint64_t n, const float* d_grad_out, uint32_t channels,
+                                float* d_grad_attr, int chw) {
+    SurfaceGradDev A{};
+    A.tris = s->dev.tris;
+    A.lookup = lookup;
+    A.ntris = s->dev.ntris;
+    A.n = (uint32_t)n;
+    A.grad_out = d_grad_out;
+    A.channels = channels;
+    A.grad_attr = d_grad_attr;
+    A.chw = chw ? 1 : 0;
+    surface_grad_policy(channels, A.chw, &A.by_item, &A.combine);
+    return A;
+}
+int surface_list_grad_launch(CgrtScene* s, const void* d_rays, const void* d_hits, uint64_t n, const float* d_grad_out, uint32_t channels,
+                             float* d_grad_attr, hipStream_t st) {
+    const SurfaceLookup* lookup = nullptr;
+    const int rc = surface_lookup(s, &lookup);
+    if (rc) return rc;
+    SurfaceGradDev A = surface_grad_dev(s, lookup, n, d_grad_out, channels, d_grad_attr, 0);
+    A.rays = static_cast<const float*>(d_rays);
+    A.hits = static_cast<const CgrtHitDev*>(d_hits);
+    HIP_TRY(launch_surface_grad(A, SURFACE_LIST, st));
+    return CGRT_OK;
+}
+int surface_list_grad_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out, uint32_t channels,
+                             float* d_grad_attr, void* stream) {
+    int rc = surface_list_args(s, d_rays, d_hits, n, true, d_grad_attr, channels, d_grad_out, true);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_hits, n * sizeof(CgrtHit), "d_hits")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_grad_out, n * channels * 4ull, "d_grad_out")) != CGRT_OK) return rc;
+    return surface_list_grad_launch(s, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, static_cast<hipStream_t>(stream));
+}
+// host pointers, on a call lane (slots: 0 rays, 1 hits, 2 grad_out, 3 grad_attr: uploaded, accumulated into, downloaded)
+int surface_list_grad_host(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
+                           float* grad_attr) {
+    int rc = surface_list_args(s, rays, hits, n, true, grad_attr, channels, grad_out, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    LaneGuard g(s);
+    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    const size_t go_bytes = (size_t)n * channels * 4u, table_bytes = (size_t)s->nverts * channels * 4u;
+    void *dr = nullptr, *dh = nullptr, *dgo = nullptr, *dt = nullptr, *staged = nullptr;
+    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(g.dev(1, n * sizeof(CgrtHit), &dh));
+    HIP_TRY(g.dev(2, go_bytes, &dgo));
+    HIP_TRY(g.dev(3, table_bytes, &dt));
+    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
+    HIP_TRY(lane_upload(g, 1, dh, hits, n * sizeof(CgrtHit)));
+    HIP_TRY(lane_upload(g, 2, dgo, grad_out, go_bytes));
+    HIP_TRY(lane_upload(g, 3, dt, grad_attr, table_bytes));
+    if ((rc = surface_list_grad_launch(s, dr, dh, n, static_cast<const float*>(dgo), channels, static_cast<float*>(dt), g.L->stream)) != CGRT_OK)
+        return rc;
+    HIP_TRY(lane_download(g, 3, grad_attr, dt, table_bytes, &staged));
+    HIP_TRY(hipStreamSynchronize(g.L->stream));
+    if (staged) std::memcpy(grad_attr, staged, table_bytes);
+    return CGRT_OK;
+}
+// cgrt_surface_views_grad_device and its ray-camera twin (exactly one of cams, raycams)
+int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H,
+                               const float* d_depth, const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw,
+                               float* d_grad_attr, void* stream) {
+    if (!s || !d_depth || !d_prim_id || !d_grad_out || !d_grad_attr) return fail(CGRT_E_ARG, "NULL argument");
+    int rc = views_args(raycams ? static_cast<const void*>(raycams) : cams, nviews, W, H, raycams);
+    if (rc) return rc;
+    const uint64_t npix = (uint64_t)nviews * (uint64_t)W * (uint64_t)H;
+    if ((rc = surface_channels(channels, npix)) != CGRT_OK) return rc;
+    if ((uintptr_t)d_depth % 4 || (uintptr_t)d_prim_id % 4 || (uintptr_t)d_grad_attr % 4 || (uintptr_t)d_grad_out % 4)
+        return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_depth, npix * 4, "d_depth")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_prim_id, npix * 4, "d_prim_id")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_grad_out, npix * channels * 4ull, "d_grad_out")) != CGRT_OK) return rc;
+    const SurfaceLookup* lookup = nullptr;
+    if ((rc = surface_lookup(s, &lookup)) != CGRT_OK) return rc;
+    SurfaceGradDev A = surface_grad_dev(s, lookup, npix, d_grad_out, channels, d_grad_attr, chw);
+    A.depth = d_depth;
+    A.prim = d_prim_id;
+    A.W = W;
+    A.H = H;
+    A.plane = (uint32_t)((uint64_t)W * (uint64_t)H);
+    hipStream_t const st = static_cast<hipStream_t>(stream);
+    return launch_with_view_table(s, view_table(cams, raycams, nviews), st, [&](const void* d_table) {
+        A.cams = d_table;
+        return launch_surface_grad(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, st);
+    });
+}
 }  // namespace
+
+int cgrt_interpolate_hits_grad(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
+                               float* grad_attr) {
+    return surface_list_grad_host(s, rays, hits, n, grad_out, channels, grad_attr);
+}
+int cgrt_interpolate_hits_grad_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out,
+                                      uint32_t channels, float* d_grad_attr, void* stream) {
+    return surface_list_grad_device(s, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, stream);
+}
+int cgrt_surface_views_grad_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                   const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
+                                   void* stream) {
+    return surface_frames_grad_device(s, cams, nullptr, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, stream);
+}
+int cgrt_surface_raycams_grad_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                     const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
+                                     void* stream) {
+    return surface_frames_grad_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, stream);
+}
 
 int cgrt_hit_barycentrics(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, float* bary) {
     return surface_list_host(s, rays, hits, n, false, nullptr, 0, bary);

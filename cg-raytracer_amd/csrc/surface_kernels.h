@@ -45,4 +45,32 @@ struct SurfaceDev {
 };
 hipError_t launch_surface(const SurfaceDev& A, int source, hipStream_t stream);
 
+// One launch of the adjoint: the same n items, grad_out in the layout of SurfaceDev::out, every valid item's
+// three weighted copies of its grad_out row added into grad_attr.
+struct SurfaceGradDev {
+    const TriRecord* tris;
+    const SurfaceLookup* lookup;
+    uint32_t ntris;
+    uint32_t n;
+    // ray list
+    const float* rays;
+    const CgrtHitDev* hits;
+    // frames
+    const void* cams;
+    const float* depth;
+    const uint32_t* prim;
+    int W, H;
+    uint32_t plane;
+    // the gradient
+    const float* grad_out;        // n x channels (frames with chw: (views, channels, H, W))
+    uint32_t channels;
+    float* grad_attr;             // nverts x channels, accumulated into
+    int chw;
+    int by_item;                  // each lane walks the channels of its own item (always with chw); else lanes walk the wave's 64 x C run
+    int combine;                  // by_item: sum consecutive lanes of one prim_id inside the wave, one lane of each run adds
+};
+// The mapping the library ships for (channels, chw): see surface_grad_policy in surface_kernels.hip and DESIGN.md section 5.23.
+void surface_grad_policy(uint32_t channels, int chw, int* by_item, int* combine);
+hipError_t launch_surface_grad(const SurfaceGradDev& A, int source, hipStream_t stream);
+
 }  // namespace cgrt

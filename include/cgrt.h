@@ -706,7 +706,8 @@ int cgrt_render_raycams_light_sets_device(CgrtScene* scene, const CgrtRayCamera*
  *   checks, nviews == 0, W or H <= 0, the views limits; (with d_out) channels outside 1..256; a pointer not 4-byte aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.  Then d_depth, d_prim_id, d_attr, d_bary, d_out checked as device memory.
  * Not offered: planes inside the cgrt_render_*aov* calls (CgrtAovOut keeps its size: two enqueued calls on one stream give the same
  * result without a second trace); per-triangle attributes (a plain gather by prim_id); enqueued-ticket forms (these calls never block);
- * sphere parameterisations; derivatives; the C++ host mirror (the reference's HitInfo has no such field). */
+ * sphere parameterisations; derivatives other than the one with respect to the table (below: cgrt_interpolate_hits_grad and its kin);
+ * the C++ host mirror (the reference's HitInfo has no such field). */
 int cgrt_hit_barycentrics(CgrtScene* scene, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, float* bary);
 int cgrt_hit_barycentrics_device(CgrtScene* scene, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, float* d_bary, void* stream);
 int cgrt_interpolate_hits(CgrtScene* scene, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* attr, uint32_t channels,
@@ -719,6 +720,49 @@ int cgrt_surface_views_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t
 int cgrt_surface_raycams_device(CgrtScene* scene, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
                                 const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw,
                                 void* stream);
+
+/* Surface attributes, gradients back to the per-vertex table.  The interpolation above is linear in attr; these
+ * entries apply its adjoint, so that a table can be fitted to images or ray samples: given grad_out, the gradient of some scalar with
+ * respect to `out`, they add the gradient with respect to attr into grad_attr.
+ * Definition.  An item is valid under the forward's rule, unchanged: hit != 0 (lists) and prim_id < ntris.  For a valid item i, with
+ * (alpha, beta, gamma) the cgrt_math.h hit_weights of its ray, t and triangle -- the very bits the forward used --,
+ * (i0, i1, i2) = tri[prim_id] and g = grad_out[i] (C channels):
+ *   grad_attr[i0][c] += alpha * g[c]
+ *   grad_attr[i1][c] += beta  * g[c]
+ *   grad_attr[i2][c] += gamma * g[c]
+ * Each product is rounded to f32 and nothing is contracted.  A triangle that names one vertex twice contributes twice to it.  Invalid
+ * items (misses, sphere hits, any out-of-range prim_id) contribute nothing: their grad_out is not multiplied in (a NaN there stays
+ * out) and they never index anything.
+ * Accumulation.  The calls ADD into grad_attr: the caller zeroes it, or keeps a running gradient over several calls or frames.  Only
+ * rows of vertices that received a contribution are touched.
+ * Order.  The order of the additions into one element is unspecified: the value is the sum, in f32, of the element's previous content
+ * and its contributions in SOME order (contributions of neighbouring items may be summed with each other first), and its last bits may
+ * differ from run to run.  For an element with m contributions w*g and previous content a, every such order obeys
+ *   |got - exact| <= gamma(m + 1) * S + (m + 1) * 2^-126,   gamma(k) = k*u / (1 - k*u),  u = 2^-24,  S = |a| + sum |w*g|
+ * (exact: the sum of a and the products of the f32 weights, in real arithmetic); this is the bound the tests use.  Whether the hardware
+ * add flushes a denormal sum to zero is not known: nobody has measured it on gfx950 (the absolute term above allows for either).
+ * Layouts.  grad_out has the layout of the forward's out: (n, C); (B, H, W, C); (B, C, H, W) with chw != 0.  grad_attr is nverts x C
+ * f32.  cgrt_interpolate_hits_grad takes host pointers, runs on a call lane and is synchronous; the *_device forms only enqueue on
+ * `stream`, are concurrent on one scene, neither read nor write the prediction record or the frame hints, and use the four camera-table
+ * slots and the lookup table (built by the scene's first surface call, forward or gradient) as the forward does.
+ * Checks, all CGRT_E_ARG: those of the forward twin, in its order, with grad_out / grad_attr in the places of out / attr (both are
+ * required): NULL pointers; n > 0x7fffffff; channels outside 1..256; the 2^40-byte bound; 4-byte alignment; the camera checks; the views
+ * limits.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and touches nothing.  Device forms: then every buffer's extent is
+ * checked as device memory of the scene's device (d_grad_attr over nverts * channels * 4 bytes).
+ * Not offered: a bitwise-reproducible form (a store pass, a per-destination sum through an inverted index and a fixed order: a
+ * follow-up); gradients with respect to vertex positions, rays or cameras (the weights are piecewise-smooth in them: a different
+ * feature); per-triangle tables; bf16 / f16 tables; planes inside the cgrt_render_*aov* calls; enqueued-ticket forms (these calls never
+ * block); the C++ host mirror. */
+int cgrt_interpolate_hits_grad(CgrtScene* scene, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out,
+                               uint32_t channels, float* grad_attr);
+int cgrt_interpolate_hits_grad_device(CgrtScene* scene, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out,
+                                      uint32_t channels, float* d_grad_attr, void* stream);
+int cgrt_surface_views_grad_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                   const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
+                                   void* stream);
+int cgrt_surface_raycams_grad_device(CgrtScene* scene, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                     const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
+                                     void* stream);
 
 /* Closest-point queries: "which point of the surface is nearest to p?" for a list of points -- the other question
  * put to a triangle BVH (distance fields, snapping and registration of point clouds, collision margins, carrying per-vertex data to
