@@ -1,43 +1,11 @@
 // capi.cpp -- implementation of the C-ABI declared in include/cgrt.h.
 // Host C++ over the HIP runtime; no torch types, no CPU traversal path: every intersect/trace entry
 // launches the gfx950 kernels of trace_kernels.hip and fails loudly when no device is usable.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <array>
-#include <linux/futex.h>
-#include <map>
-#include <sched.h>
-#include <sys/syscall.h>
-#include <unistd.h>
-
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <mutex>
-#include <thread>
-#include <cstdio>
-#include <cstdlib>
-#include <utility>
-#include <cstring>
-#include <functional>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "../../include/cgrt.h"
-#include "bvh_builder.h"
-#include "cgrt_layout.h"
-#include "cgrt_math.h"
-#include "closest_kernels.h"
-#include "crossing_kernels.h"
-#include "surface_kernels.h"
-#include "trace_kernels.h"
-
-using namespace cgrt;
+#include "capi_internal.h"
 
 static_assert(sizeof(CgrtRay) == 28, "CgrtRay must match the reference Ray (ray.h:9-13)");
 static_assert(sizeof(CgrtHit) == sizeof(CgrtHitDev), "CgrtHit layout");
+static_assert(sizeof(CgrtCounters) == 8 * sizeof(uint64_t), "CgrtCounters is a lane's counter block, word for word (LaneCall::read_counters)");
 
 namespace {
 
@@ -46,6 +14,9 @@ thread_local std::string g_err;
 // under a mutex when a scene is created; the primary mode is read atomically by every launch.
 std::mutex g_options_mutex;
 BuildOptions g_build_options;
+}  // namespace
+
+namespace cgrt {  // (declared in capi_internal.h, for every translation unit of the C-ABI)
 std::atomic<int> g_call_combining{1};  // cgrt_set_call_combining
 std::atomic<int> g_render_predict{1};  // cgrt_set_render_prediction
 std::atomic<int> g_frame_hints{-1};    // cgrt_set_frame_hints: -1 auto, 0 off, 1 hard tiles first, 2 hard tiles 16 rays per wave
@@ -61,24 +32,6 @@ int hip_fail(hipError_t e, const char* what) {
     g_err = std::string(what) + ": " + hipGetErrorString(e);
     return CGRT_E_HIP;
 }
-#define HIP_TRY(expr)                                  \
-    do {                                               \
-        hipError_t _e = (expr);                        \
-        if (_e != hipSuccess) return hip_fail(_e, #expr); \
-    } while (0)
-
-// RAII device buffer for the host-pointer convenience entries.
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T>
-    T* as() const {
-        return static_cast<T*>(p);
-    }
-};
 
 int select_device(int device) {
     int n = 0;
@@ -141,7 +94,9 @@ bool make_frame(int W, int H, int x0, int y0, int x1, int y1, int rank, int nran
     F.gate_x0 = F.gate_y0 = F.gate_x1 = F.gate_y1 = 0;  // no gate (apply_frame_gate)
     return true;
 }
+}  // namespace cgrt
 
+namespace {
 // A multi-view frame (FrameDev::views): nviews whole W x H frames, one rank, their super-tiles one list (the table is set by the caller).
 // False when the list does not fit the launch: more than 2^18 super-tiles (a quad-shape grid of 2^32 workgroups).
 bool make_views_frame(int W, int H, uint32_t nviews, int block, FrameDev& F) {
@@ -254,322 +209,7 @@ unsigned long long owned_pixels(const FrameDev& F) {
 
 }  // namespace
 
-// The slots of a scene's device workspace (CgrtScene::work), by what the shaded frame keeps in them (Wavefront and render_impl below).  A
-// level's list (rays / hits / normals / pixels) has four buffer sets and its shadow list two; their numbers are not contiguous because
-// slots were added as features came.
-enum WorkSlotId {
-    WS_RAYS0, WS_RAYS1, WS_HITS0, WS_HITS1, WS_NORMALS0, WS_NORMALS1, WS_PIX0, WS_PIX1, WS_IPIX,  // 0..8
-    WS_SRAYS0, WS_SHITS0, WS_SDIST0, WS_SSLOT0,                                                   // 9..12
-    WS_LIGHTS, WS_LEVELS, WS_RGB, WS_CTR, WS_SLIGHTS, WS_UNITS, WS_LIT, WS_COUNTED,               // 13..20
-    WS_RAYS2, WS_HITS2, WS_NORMALS2, WS_PIX2, WS_SRAYS1, WS_SHITS1, WS_SDIST1, WS_SSLOT1,         // 21..28
-    WS_SPAWN, WS_RESOLVED, WS_VIEWS, WS_SETS, WS_SETTAB,  // 29..33 (32 and 33: light-set batches only)
-    WS_RAYS3, WS_HITS3, WS_NORMALS3, WS_PIX3,             // 34..37: deep frames with geometry buffers only
-    WS_SLOTS
-};
-static_assert(WS_RGB == 15 && WS_RESOLVED == 30 && WS_SLOTS == 38, "the workspace's slot numbers");
-
-struct CgrtScene {
-    int device = 0;
-    BuiltBvh bvh;
-    uint32_t ntris = 0;
-    SceneDev dev = [] {
-        SceneDev d{};
-        d.fast_root = REF_NONE;
-        d.root_ref = REF_NONE;
-        return d;
-    }();
-    void* d_records = nullptr;  // [packets | subnodes | tris], 64 B each
-    void* d_leaves = nullptr;
-    void* d_tri_normals = nullptr;
-    void* d_spheres = nullptr;
-    void* d_materials = nullptr;  // nmesh x 8 floats, for the shading wavefront
-    void* d_tri_leaf = nullptr;   // certified walk: leaf of every record, per-leaf box paths (SceneDev::tri_leaf, paths)
-    void* d_paths = nullptr;
-    uint32_t fast_root = REF_NONE;  // the scene's fast tree (REF_NONE: none); dev.fast_root is this or REF_NONE by cgrt_scene_set_walk
-    uint32_t nmesh = 0;
-    unsigned int* d_queues = nullptr;  // ring of 8 queue blocks (CGRT_QUEUE_BLOCK_WORDS u32 each) for the persistent kernel, reset by every launch
-    // the persistent kernel's launches take the queue blocks in turn; a block is handed to a new launch only behind the
-    // launch that used it last (an event per block), so any number of frames may be in flight on any streams
-    std::mutex queue_mutex;
-    unsigned launch_seq = 0;
-    // Frame hints (cgrt_layout.h HintDev; attach_hints below): the hard-tile lists a primary frame leaves for the next frame of
-    // the same shape.  Guarded by hints_mutex while a launch is being issued; the buffers themselves are only touched by kernels.
-    struct FrameHints {
-        std::mutex mu;
-        bool ready = false;           // buffers allocated for `key`
-        int key[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // W, H, x0, y0, x1, y1, rank, nranks
-        int wanted[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the shape (+ mode, threshold) of the last launches that asked for other buffers
-        int wanted_count = 0;         // ... and how many in a row did
-        int per_tile = 0;             // 1 / 4 (the policy the buffers were made for)
-        unsigned thr[2] = {0, 0};     // the thresholds in the device structs
-        uint32_t cap = 0;
-        void* mem = nullptr;          // 3 x {flag[ntiles], list[cap], count} + 3 HintDev
-        size_t mem_bytes = 0;
-        HintDev* phase[3] = {nullptr, nullptr, nullptr};  // device addresses
-        HintDev phase_host[3];        // what they hold
-        uint32_t* mailbox = nullptr;  // 64 pinned, device-mapped bytes: {generation, length of the list that frame read, threshold}
-        uint32_t* mailbox_dev = nullptr;
-        uint32_t seen_gen = 0;        // the last mailbox generation the host has looked at
-        uint32_t last_listed = 0;     // ... and what it said
-        int empty_streak = 0;         // hinted frames in a row whose list was empty
-        int dormant = 0;              // frames still to run plain because of that
-        uint64_t seq = 0;             // frames issued with these buffers
-        bool have_prev = false;       // the set this frame would read was written by frame seq - 1
-        hipStream_t last_stream = nullptr;
-        bool last_stream_valid = false;
-        hipStream_t hint_stream = nullptr;  // the stream of the last launch that used the buffers
-        bool hint_stream_valid = false;
-        int cooldown = 0;             // frames to run without hints after the caller changed streams
-    } hints;
-    hipEvent_t queue_done[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // Host-pointer entries (cgrt_intersect_batch, cgrt_trace_primary, cgrt_count_*, ...) run on "call lanes": a private
-    // stream + device scratch + pinned staging + a counter block, taken from this pool for the duration of one call and
-    // kept afterwards.  Concurrent callers (the reference calls intersect from an omp parallel for, main.cpp:653-656) get
-    // different lanes; no call allocates, frees or synchronises the device once its lane has grown to the call's size.
-    struct CallLane {
-        hipStream_t stream = nullptr;
-        struct Buf {
-            void* p = nullptr;
-            size_t cap = 0;
-        } dev[4], pin[4];  // rays / hits / normals / light tables
-        void* bounce[2] = {nullptr, nullptr};  // pinned halves of the large-transfer pipeline (lane_upload / lane_download), made on first use
-        hipEvent_t bounce_ev[2] = {nullptr, nullptr};
-        hipEvent_t follow = nullptr;  // lane_follow: the lane's stream waits for the caller's, made on first use
-        unsigned long long* d_counters = nullptr;
-    };
-    std::mutex lanes_mutex;
-    std::vector<CallLane*> lanes_free, lanes_all;
-    // Call combining (cgrt_intersect_batch with a handful of rays, i.e. BoundingVolumeHierarchy::intersect as the reference's
-    // `omp parallel for` issues it, main.cpp:653-656: one ray per call from many threads at once).  A launch per ray costs the
-    // GPU round trip per RAY; here concurrent callers append their rays to the open GENERATION of one of two pinned, device-mapped
-    // rings; the first caller of a generation is its leader: it closes the generation, launches ONE kernel over all its rays
-    // (the kernel reads the rays from and writes the hits to host memory directly: no copy commands), waits for that stream and
-    // publishes the results; the other callers wait on the generation's state and copy their own hits out.  While a generation
-    // is on the GPU the next one fills up, so the batch size adapts to the load.  Nothing stays resident on the device.
-#ifndef CGRT_COMBINE_RINGS
-#define CGRT_COMBINE_RINGS 16  // most generations that can be open / in flight at a time; `nrings` of them are used
-#endif
-    struct Combiner {
-        static const int NRINGS = CGRT_COMBINE_RINGS;
-        int nrings = 8;  // set before the rings are made (combined_intersect; CGRT_COMBINE_NRINGS)
-        static const uint32_t CAP = 32768;       // ray slots per ring
-        static const uint32_t MAX_N = 64;        // calls with more rays than this take the direct path
-        static const int MAX_CALLERS = 256;      // callers inside the entry at a time (more take the direct path)
-        static const uint32_t JOIN_MAX = CAP - MAX_N * MAX_CALLERS;  // a generation is joined while it holds at most this many rays:
-                                                                     // MAX_CALLERS joins of MAX_N rays in flight cannot overflow it
-        enum State : uint64_t { FREE = 0, OPEN = 1, RUNNING = 2, DONE = 3 };
-        // One 64-bit word per ring says everything a caller needs, so joining is ONE atomic add, leader election and closing single
-        // compare-and-swaps, and nobody takes a lock on the way in (with a mutex 64 callers formed a convoy: 139 K calls/s):
-        //   bits 0..1 state | 2..15 callers that joined | 16..31 rays appended | 32..63 generation number
-        // An add that arrives after the generation was closed lands on a RUNNING / DONE / FREE word: the adder sees the old state in
-        // the value it gets back and tries again elsewhere; the stray counts are overwritten by the next transition (the leader
-        // keeps its own copy of the counts it closed with), and the caller limit keeps them inside their bit fields.
-        static uint64_t pack(uint64_t st, uint64_t joined, uint64_t count, uint64_t gen) { return st | (joined << 2) | (count << 16) | (gen << 32); }
-        static uint64_t st_of(uint64_t w) { return w & 3u; }
-        static uint32_t joined_of(uint64_t w) { return (uint32_t)((w >> 2) & 0x3fffu); }
-        static uint32_t count_of(uint64_t w) { return (uint32_t)((w >> 16) & 0xffffu); }
-        struct alignas(64) Ring {
-            std::atomic<uint64_t> word{0};     // FREE, generation 0
-            char pad0[56];
-            // what the WAITERS of a generation spin on -- a line of its own, written once per generation: spinning on `word`
-            // made every join fight 60 readers for the line (64 callers: 0.46 M calls/s)
-            std::atomic<uint32_t> done_gen{0}; // generations of this ring whose results are published
-            char pad1[60];
-            std::atomic<uint32_t> copied{0};   // joiners whose rays are in the ring (the leader launches when copied == joined)
-            std::atomic<uint32_t> readers{0};  // callers that still have to copy their results out (the last one frees the ring)
-            char pad2[56];
-            void* host = nullptr;  // pinned + mapped: [CgrtRay x CAP | CgrtHit x CAP | normals 3 x CAP]
-            void* dev = nullptr;   // the same memory as the device sees it
-            hipStream_t stream = nullptr;
-            int rc = 0;            // the leader's status for the whole generation (written before done_gen is published)
-            std::string err;
-        } ring[CGRT_COMBINE_RINGS];
-        std::mutex init_mu;
-        // Callers that SLEEP (futex) instead of spinning -- taken when more callers are inside than the process has CPUs (see
-        // combined_intersect): `epoch` counts rings set free (what callers without a ring wait for), the sleeper counts tell the
-        // thread that publishes whether a wake-up call is needed at all.
-        alignas(64) std::atomic<uint32_t> epoch{0};
-        std::atomic<int> epoch_sleepers{0}, done_sleepers{0};
-        alignas(64) std::atomic<int> inside{0};   // callers currently inside the combining entry
-        alignas(64) std::atomic<int> ready{0};    // 0 = rings not allocated yet, 1 = usable, -1 = allocation failed (direct path for good)
-        // diagnostics (cgrt_debug_combiner_stats): generations launched, rays in them, the largest generation, nanoseconds the
-        // leaders spent from closing a generation to its results (launch + kernel + stream wait)
-        std::atomic<uint64_t> n_gen{0}, n_rays{0}, max_gen{0}, ns_gpu{0}, ns_launch{0};  // ns_launch: the part of ns_gpu spent issuing the launch
-    } comb;
-    std::mutex render_mutex;  // cgrt_render* share the workspace below: one frame per scene at a time
-    unsigned persistent_blocks = 1024;  // 4 workgroups per CU
-    // Device workspace of cgrt_render*: kept between frames (a frame of the same shape then allocates nothing; hipMalloc and
-    // hipFree of ~20 buffers cost more than the frame itself), grown on demand, released with the scene.
-    struct WorkSlot {
-        void* p = nullptr;
-        size_t cap = 0;
-    } work[WS_SLOTS];
-    // pinned host staging of cgrt_render*'s frame (grown on demand, guarded by render_mutex): the device frame comes down with ONE
-    // asynchronous copy at PCIe speed; cgrt_render_mapped hands this memory to the caller instead of copying it once more
-    void* pin_frame = nullptr;
-    size_t pin_frame_cap = 0;
-    // streams and events of cgrt_render* (created once per scene, guarded by render_mutex: creating and destroying a stream and
-    // five events per frame cost more host time than the Cornell frame's device time)
-    struct RenderAux {
-        hipStream_t s = nullptr, copy = nullptr;  // second traversal stream; read-backs that must not wait for queued kernels
-        hipEvent_t spawned = nullptr, traced = nullptr, e0 = nullptr, e1 = nullptr, primary_done = nullptr;
-        hipEvent_t caller = nullptr;     // cgrt_shade_rays*: the frame's streams start behind what the caller's stream held
-        // geometry buffers of a blocking frame: the planes are written on a stream of their own, behind `caller`
-        // (what the caller's stream held) -- the miss values while the frame is traced, level 0's entries beside the colour export -- and
-        // the caller's stream waits for `filled`, recorded behind them
-        hipStream_t fill = nullptr;
-        hipEvent_t filled = nullptr;
-        uint32_t* pin_counts = nullptr;  // 64 pinned bytes for counter read-backs
-        SpawnDev spawn_host{};           // what the workspace's SpawnDev (fused level-0 spawn of predicted frames) holds
-        bool spawn_valid = false;
-    } raux;
-    // cgrt_render_device: its export kernel reads the frame (work slot WS_RGB, or WS_RESOLVED with aa) on the CALLER's stream after the call has
-    // returned.  This event is recorded behind it, and the next cgrt_render* call on the scene makes every stream it uses wait on it
-    // (and waits for it on the host before it reallocates those buffers); the caller's stream handle itself is never kept.
-    hipEvent_t export_done = nullptr;
-    bool export_pending = false;  // recorded, and no later frame has waited for it yet
-    // cgrt_trace_primary_views_device: the camera tables of its launches (CameraDev per view), which return before the kernels run.  Four
-    // slots in turn, each a pinned host copy and a device copy; a slot is refilled only once the event recorded behind its last launch
-    // has completed, so the copy never reads memory the caller has since reused (the tables come from the caller's stack or array).
-    struct ViewTable {
-        void* pin = nullptr;
-        void* dev = nullptr;
-        size_t cap = 0;
-        hipEvent_t done = nullptr;
-        bool pending = false;
-    } vtab[4];
-    unsigned vtab_seq = 0;
-    std::mutex vtab_mutex;
-    // What the previous cgrt_render* frame of this shape found, per level (entries of the level's compact list): the next frame's
-    // launches are sized from it and issued WITHOUT waiting for the device to say how many primary rays hit (render_impl).
-    struct RenderPred {
-        bool valid = false;
-        int W = 0, H = 0, rank = 0, nranks = 0, max_level = 0;
-        unsigned L = 0;
-        std::vector<uint32_t> counts;
-        int last_path = 0;  // how the last frame was drawn: 0 exact, 1 as predicted, 2 predicted, found too small, drawn again exactly
-    } rpred;
-    // Enqueued frames (cgrt_enqueue_*; enqueue_impl below): a ring of ENQ_SLOTS ticket slots, each with pinned
-    // staging for the frame's tables (copied to enq_dev by hipMemcpyAsync on the caller's stream), a pinned read-back of its counter block
-    // and the events behind it.  A slot is refilled only once its last frame has finished.  Every frame of the scene (enqueued or blocking)
-    // starts behind the last enqueued one on the device (enq_done), so all of them share the workspace above.
-    static const int ENQ_SLOTS = 8;
-    struct EnqSlot {
-        void* pin = nullptr;         // lights | spherical lights | unit vectors | SpawnDev | view table
-        size_t cap = 0;
-        uint32_t* pin_ctr = nullptr;  // the frame's counter block, copied back behind the frame (cgrt_enqueue_stats)
-        hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;
-        bool pending = false;
-        uint64_t ticket = 0;          // 0: never used
-        // what cgrt_enqueue_stats needs to turn the counters into CgrtRenderStats
-        int max_level = 0, fused = 0;
-        unsigned L = 0, SL = 0, samples = 0;
-        uint64_t primary_rays = 0;
-    } eslot[ENQ_SLOTS];
-    unsigned enq_count = 0;           // enqueued frames issued (slot = enq_count % ENQ_SLOTS)
-    uint64_t frame_seq = 0;           // the scene's frames, blocking and enqueued: an enqueued frame's ticket is its number
-    void* enq_dev = nullptr;          // the device copy of the tables (frames are ordered on the device, so one copy serves them all)
-    size_t enq_dev_cap = 0;
-    hipEvent_t enq_done = nullptr;    // behind the last enqueued frame (one of the slots' `done`)
-    bool enq_pending = false;
-    uint64_t device_bytes = 0;
-    // Surface attributes (cgrt_hit_barycentrics*, cgrt_interpolate_hits*, cgrt_surface_*): the triangles' vertex
-    // indices as the caller gave them (host memory only) and, from the first surface call on, the device table prim_id -> {record, three
-    // vertex rows} (surface_kernels.h SurfaceLookup).  A scene that makes no such call never allocates it.
-    uint32_t nverts = 0;
-    std::vector<uint32_t> tri_index;  // ntris x 3
-    std::mutex surface_mutex;
-    std::atomic<void*> d_surface_lookup{nullptr};
-    ~CgrtScene() {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (void* p = d_surface_lookup.load()) (void)hipFree(p);
-        for (EnqSlot& e : eslot) {  // (frames in flight complete before anything they use is released)
-            if (e.pending) (void)hipEventSynchronize(e.done);
-            for (hipEvent_t ev : {e.done, e.t0, e.t1})
-                if (ev) (void)hipEventDestroy(ev);
-            if (e.pin) (void)hipHostFree(e.pin);
-            if (e.pin_ctr) (void)hipHostFree(e.pin_ctr);
-        }
-        if (enq_dev) (void)hipFree(enq_dev);
-        if (export_pending) (void)hipEventSynchronize(export_done);  // (an export may still be reading the workspace)
-        if (export_done) (void)hipEventDestroy(export_done);
-        for (ViewTable& v : vtab) {
-            if (v.pending) (void)hipEventSynchronize(v.done);
-            if (v.done) (void)hipEventDestroy(v.done);
-            if (v.dev) (void)hipFree(v.dev);
-            if (v.pin) (void)hipHostFree(v.pin);
-        }
-        for (void* p : {d_records, d_leaves, d_tri_normals, d_spheres, d_materials, d_tri_leaf, d_paths, (void*)d_queues, hints.mem})
-            if (p) (void)hipFree(p);
-        if (hints.mailbox) (void)hipHostFree(hints.mailbox);
-        if (pin_frame) (void)hipHostFree(pin_frame);
-        for (hipEvent_t e : {raux.spawned, raux.traced, raux.e0, raux.e1, raux.primary_done, raux.caller, raux.filled})
-            if (e) (void)hipEventDestroy(e);
-        for (hipStream_t st : {raux.s, raux.copy, raux.fill})
-            if (st) (void)hipStreamDestroy(st);
-        if (raux.pin_counts) (void)hipHostFree(raux.pin_counts);
-        for (auto& r : comb.ring) {
-            if (r.host) (void)hipHostFree(r.host);
-            if (r.stream) (void)hipStreamDestroy(r.stream);
-        }
-        for (CallLane* L : lanes_all) {
-            for (auto& b : L->dev)
-                if (b.p) (void)hipFree(b.p);
-            for (auto& b : L->pin)
-                if (b.p) (void)hipHostFree(b.p);
-            for (void* b : L->bounce)
-                if (b) (void)hipHostFree(b);
-            for (hipEvent_t e : L->bounce_ev)
-                if (e) (void)hipEventDestroy(e);
-            if (L->follow) (void)hipEventDestroy(L->follow);
-            if (L->d_counters) (void)hipFree(L->d_counters);
-            if (L->stream) (void)hipStreamDestroy(L->stream);
-            delete L;
-        }
-        for (WorkSlot& w : work)
-            if (w.p) (void)hipFree(w.p);
-        for (hipEvent_t e : queue_done)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
-struct WsBuf {  // a slot of the scene's workspace, with DevBuf's interface
-    CgrtScene* sc;
-    int slot;
-    void* p = nullptr;
-    hipError_t alloc(size_t bytes) {
-        CgrtScene::WorkSlot& w = sc->work[slot];
-        if (w.cap < bytes || !w.p) {
-            // enqueued frames (and a blocking frame's export) may still use the buffer: they finish before it is released
-            if (w.p && sc->enq_pending) {
-                const hipError_t e = hipEventSynchronize(sc->enq_done);
-                if (e != hipSuccess) return e;
-                sc->enq_pending = false;
-            }
-            if (w.p && sc->export_pending) {
-                const hipError_t e = hipEventSynchronize(sc->export_done);
-                if (e != hipSuccess) return e;
-            }
-            if (w.p) (void)hipFree(w.p);
-            w.p = nullptr;
-            w.cap = 0;
-            const hipError_t e = hipMalloc(&w.p, bytes ? bytes : 1);
-            if (e != hipSuccess) return e;
-            w.cap = bytes ? bytes : 1;
-        }
-        p = w.p;
-        return hipSuccess;
-    }
-    size_t cap() const { return sc->work[slot].cap; }
-    template <class T>
-    T* as() const {
-        return static_cast<T*>(p);
-    }
-};
-
-namespace {
-void parallel_copy(void* dst, const void* src, size_t bytes);  // (below: large host copies on a few threads)
+namespace cgrt {
 // Host -> device for the scene's arrays (113 MB for the 800 K-triangle bench scene): through two alternating 8 MB pinned buffers kept
 // for the process, the host copying piece k + 1 on a few threads while the DMA engine moves piece k.  Handing the runtime the
 // std::vector's pageable memory took 60-90 ms of the 0.41 s a scene took to create (profiles/r3_build_times.txt).
@@ -600,6 +240,8 @@ hipError_t staged_h2d(void* dst, const void* src, size_t bytes) {
     }
     return hipStreamSynchronize(nullptr);
 }
+}  // namespace cgrt
+namespace {
 template <class T>
 int upload(const std::vector<T>& v, void** dptr, uint64_t& total) {
     const size_t bytes = v.size() * sizeof(T);
@@ -1010,195 +652,6 @@ void cgrt_record_sizes(uint32_t* node_bytes, uint32_t* tri_bytes, uint32_t* sub_
     if (hit_bytes) *hit_bytes = sizeof(CgrtHit);
 }
 
-// ------------------------------------------------------------------------------------------------
-#define NEED_DEVICE(s) \
-    if ((s)->device < 0) return fail(CGRT_E_NO_DEVICE, "scene was created host-only (CGRT_DEVICE_NONE); there is no CPU traversal path")
-
-// A call lane of the scene for the duration of one host-pointer call (RAII).
-namespace {
-struct LaneGuard {
-    CgrtScene* sc;
-    CgrtScene::CallLane* L = nullptr;
-    explicit LaneGuard(CgrtScene* s) : sc(s) {}
-    ~LaneGuard() {
-        if (!L) return;
-        // An entry that returns early (an error after work was queued) must not leave copies in flight into its caller's
-        // memory or hand a busy lane's staging buffers to the next caller: a finished stream answers the query at once.
-        if (hipSetDevice(sc->device) == hipSuccess && hipStreamQuery(L->stream) != hipSuccess) (void)hipStreamSynchronize(L->stream);
-        std::lock_guard<std::mutex> lk(sc->lanes_mutex);
-        sc->lanes_free.push_back(L);
-    }
-    int acquire() {
-        {
-            std::lock_guard<std::mutex> lk(sc->lanes_mutex);
-            if (!sc->lanes_free.empty()) {
-                L = sc->lanes_free.back();
-                sc->lanes_free.pop_back();
-                return CGRT_OK;
-            }
-        }
-        CgrtScene::CallLane* n = new (std::nothrow) CgrtScene::CallLane();
-        if (!n) return fail(CGRT_E_ALLOC, "host allocation failed");
-        hipError_t e = hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMalloc((void**)&n->d_counters, 8 * sizeof(unsigned long long));
-        if (e != hipSuccess) {
-            if (n->stream) (void)hipStreamDestroy(n->stream);
-            delete n;
-            return hip_fail(e, "creating a call lane");
-        }
-        {
-            std::lock_guard<std::mutex> lk(sc->lanes_mutex);
-            sc->lanes_all.push_back(n);
-        }
-        L = n;
-        return CGRT_OK;
-    }
-    // scratch that only grows (geometrically): k = 0 rays, 1 hits, 2 normals, 3 light tables
-    hipError_t dev(int k, size_t bytes, void** out) {
-        auto& b = L->dev[k];
-        if (b.cap < bytes) {
-            if (b.p) (void)hipFree(b.p);
-            b.p = nullptr;
-            b.cap = 0;
-            const size_t want = std::max<size_t>(bytes, 4096) * 3 / 2;
-            const hipError_t e = hipMalloc(&b.p, want);
-            if (e != hipSuccess) return e;
-            b.cap = want;
-        }
-        *out = b.p;
-        return hipSuccess;
-    }
-    hipError_t pin(int k, size_t bytes, void** out) {
-        auto& b = L->pin[k];
-        if (b.cap < bytes) {
-            if (b.p) (void)hipHostFree(b.p);
-            b.p = nullptr;
-            b.cap = 0;
-            const size_t want = std::max<size_t>(bytes, 4096) * 3 / 2;
-            const hipError_t e = hipHostMalloc(&b.p, want, hipHostMallocDefault);
-            if (e != hipSuccess) return e;
-            b.cap = want;
-        }
-        *out = b.p;
-        return hipSuccess;
-    }
-};
-// large host copies on a few threads (one thread moves ~10 GB/s: a 1080p float frame would take as long as 8 device frames)
-void parallel_copy(void* dst, const void* src, size_t bytes) {
-    const size_t chunk = 2u << 20;
-    if (bytes < 2 * chunk) {
-        std::memcpy(dst, src, bytes);
-        return;
-    }
-    const unsigned nt = (unsigned)std::min<size_t>(4, bytes / chunk);
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < nt; t++)
-        pool.emplace_back([=] {
-            const size_t b = bytes * t / nt, e = bytes * (t + 1) / nt;
-            std::memcpy(static_cast<char*>(dst) + b, static_cast<const char*>(src) + b, e - b);
-        });
-    std::memcpy(dst, src, bytes / nt);
-    for (std::thread& th : pool) th.join();
-}
-
-// Transfers below this size go through the lane's pinned staging buffers (a pageable hipMemcpyAsync of a few bytes costs
-// far more than copying them twice).  Larger ones -- the lists of a host-driven wavefront, whole frames -- are cut into
-// kBounceBytes pieces that alternate between two pinned buffers: the host copies piece k+1 (on a few threads) while the DMA engine
-// moves piece k.  Handing the runtime a pageable pointer instead moved ~3 GB/s (66 MB of rays + 56 MB of hits and normals for a
-// 1080p list: 40-50 ms around a 0.3 ms kernel, profiles/r3_host_mirror.txt).
-const size_t kStageBytes = 1u << 20;
-const size_t kBounceBytes = 8u << 20;
-
-hipError_t lane_bounce(LaneGuard& g) {
-    for (int b = 0; b < 2; b++) {
-        if (!g.L->bounce[b]) {
-            const hipError_t e = hipHostMalloc(&g.L->bounce[b], kBounceBytes, hipHostMallocDefault);
-            if (e != hipSuccess) return e;
-        }
-        if (!g.L->bounce_ev[b]) {
-            const hipError_t e = hipEventCreateWithFlags(&g.L->bounce_ev[b], hipEventDisableTiming);
-            if (e != hipSuccess) return e;
-        }
-    }
-    return hipSuccess;
-}
-
-// host -> device on the lane's stream
-hipError_t lane_upload(LaneGuard& g, int k, void* dst, const void* src, size_t bytes) {
-    if (bytes == 0) return hipSuccess;
-    if (bytes <= kStageBytes) {
-        void* st = nullptr;
-        const hipError_t e = g.pin(k, bytes, &st);
-        if (e != hipSuccess) return e;
-        std::memcpy(st, src, bytes);
-        return hipMemcpyAsync(dst, st, bytes, hipMemcpyHostToDevice, g.L->stream);
-    }
-    hipError_t e = lane_bounce(g);
-    if (e != hipSuccess) return e;
-    size_t piece = 0;
-    for (size_t off = 0; off < bytes; off += kBounceBytes, piece++) {
-        const int b = (int)(piece & 1);
-        const size_t m = std::min(kBounceBytes, bytes - off);
-        if (piece >= 2 && (e = hipEventSynchronize(g.L->bounce_ev[b])) != hipSuccess) return e;  // the DMA out of this half has finished
-        parallel_copy(g.L->bounce[b], static_cast<const char*>(src) + off, m);
-        if ((e = hipMemcpyAsync(static_cast<char*>(dst) + off, g.L->bounce[b], m, hipMemcpyHostToDevice, g.L->stream)) != hipSuccess) return e;
-        if ((e = hipEventRecord(g.L->bounce_ev[b], g.L->stream)) != hipSuccess) return e;
-    }
-    // the halves are reused by the next transfer of this call: it must not overwrite a piece still being read
-    for (int b = 0; b < 2; b++)
-        if ((e = hipEventSynchronize(g.L->bounce_ev[b])) != hipSuccess) return e;
-    return hipSuccess;
-}
-// device -> host.  Small: returns the pinned address to copy from after the stream has been synchronised.  Large: the data is in
-// dst when the call returns (the stream's earlier work has been waited for), *staged stays null.  `keep` (optional, large path
-// only): one flag word per `stride` bytes -- elements whose word is zero are NOT written (normals of rays that missed).
-hipError_t lane_download(LaneGuard& g, int k, void* dst, const void* src, size_t bytes, void** staged, const CgrtHit* keep = nullptr,
-                         size_t stride = 0) {
-    *staged = nullptr;
-    if (bytes == 0) return hipSuccess;
-    if (bytes <= kStageBytes && !keep) {
-        void* st = nullptr;
-        const hipError_t e = g.pin(k, bytes, &st);
-        if (e != hipSuccess) return e;
-        *staged = st;
-        return hipMemcpyAsync(st, src, bytes, hipMemcpyDeviceToHost, g.L->stream);
-    }
-    hipError_t e = lane_bounce(g);
-    if (e != hipSuccess) return e;
-    const size_t piece_bytes = stride ? kBounceBytes / stride * stride : kBounceBytes;
-    const size_t npieces = (bytes + piece_bytes - 1) / piece_bytes;
-    for (size_t piece = 0; piece <= npieces; piece++) {
-        if (piece < npieces) {
-            const int b = (int)(piece & 1);
-            const size_t off = piece * piece_bytes, m = std::min(piece_bytes, bytes - off);
-            if ((e = hipMemcpyAsync(g.L->bounce[b], static_cast<const char*>(src) + off, m, hipMemcpyDeviceToHost, g.L->stream)) != hipSuccess) return e;
-            if ((e = hipEventRecord(g.L->bounce_ev[b], g.L->stream)) != hipSuccess) return e;
-        }
-        if (piece >= 1) {  // copy the previous piece out while this one is on the wire
-            const int b = (int)((piece - 1) & 1);
-            const size_t off = (piece - 1) * piece_bytes, m = std::min(piece_bytes, bytes - off);
-            if ((e = hipEventSynchronize(g.L->bounce_ev[b])) != hipSuccess) return e;
-            if (!keep) {
-                parallel_copy(static_cast<char*>(dst) + off, g.L->bounce[b], m);
-            } else {
-                const size_t first = off / stride, cnt = m / stride;
-                const unsigned nt = cnt >= 65536 ? 4 : 1;
-                auto part = [&](unsigned t) {
-                    const char* from = static_cast<const char*>(g.L->bounce[b]);
-                    char* to = static_cast<char*>(dst) + off;
-                    for (size_t i = cnt * t / nt, e2 = cnt * (t + 1) / nt; i < e2; i++)
-                        if (keep[first + i].hit) std::memcpy(to + i * stride, from + i * stride, stride);
-                };
-                std::vector<std::thread> pool;
-                for (unsigned t = 1; t < nt; t++) pool.emplace_back(part, t);
-                part(0);
-                for (std::thread& th : pool) th.join();
-            }
-        }
-    }
-    return hipSuccess;
-}
-}  // namespace
 
 int cgrt_intersect_batch_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, CgrtHit* d_hits, float* d_normals, void* stream) {
     if (!s || (n && (!d_rays || !d_hits))) return fail(CGRT_E_ARG, "NULL argument");
@@ -1506,30 +959,21 @@ int cgrt_intersect_batch(CgrtScene* s, const CgrtRay* rays, uint64_t n, CgrtHit*
         int rc = CGRT_OK;
         if (!env_off && combined_intersect(s, rays, (uint32_t)n, hits, normals, rc)) return rc;
     }
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    int rc = g.acquire();
+    LaneCall c(s);
+    int rc = c.begin();
     if (rc) return rc;
     void *dr, *dh, *dn = nullptr;
-    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(g.dev(1, n * sizeof(CgrtHit), &dh));
-    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
+    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(c.scratch(1, n * sizeof(CgrtHit), &dh));
     // HitInfo is left untouched on a miss (the kernels write a normal only with a hit): a short list starts from the caller's
     // contents on the device; of a long one only the normals of rays that hit are copied back (lane_download's `keep`)
     const bool big = n * sizeof(CgrtHit) > kStageBytes;
-    if (normals) {
-        HIP_TRY(g.dev(2, n * 12, &dn));
-        if (!big) HIP_TRY(lane_upload(g, 2, dn, normals, n * 12));
-    }
-    rc = cgrt_intersect_batch_device(s, static_cast<const CgrtRay*>(dr), n, static_cast<CgrtHit*>(dh), static_cast<float*>(dn), g.L->stream);
+    if (normals) HIP_TRY(big ? c.scratch(2, n * 12, &dn) : c.input(2, normals, n * 12, &dn));
+    rc = cgrt_intersect_batch_device(s, static_cast<const CgrtRay*>(dr), n, static_cast<CgrtHit*>(dh), static_cast<float*>(dn), c.stream());
     if (rc) return rc;
-    void *sh = nullptr, *sn = nullptr;
-    HIP_TRY(lane_download(g, 1, hits, dh, n * sizeof(CgrtHit), &sh));
-    if (normals && !big) HIP_TRY(lane_download(g, 2, normals, dn, n * 12, &sn));
-    if (normals && big) HIP_TRY(lane_download(g, 2, normals, dn, n * 12, &sn, hits, 12));  // hits is complete here: only rays that hit
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (sh) std::memcpy(hits, sh, n * sizeof(CgrtHit));
-    if (sn) std::memcpy(normals, sn, n * 12);
+    HIP_TRY(c.output(1, hits, dh, n * sizeof(CgrtHit)));
+    if (normals) HIP_TRY(c.output(2, normals, dn, n * 12, big ? hits : nullptr, 12));  // big: hits is complete here, only rays that hit
+    HIP_TRY(c.finish());
     return CGRT_OK;
 }
 
@@ -1538,28 +982,19 @@ int cgrt_intersect_brute_batch(CgrtScene* s, const CgrtRay* rays, uint64_t n, in
     NEED_DEVICE(s);
     if (mesh >= (int)s->nmesh) return fail(CGRT_E_ARG, "mesh index out of range");
     if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    int rc = g.acquire();
+    LaneCall c(s);
+    int rc = c.begin();
     if (rc) return rc;
     void *dr, *dh, *dn = nullptr;
-    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(g.dev(1, n * sizeof(CgrtHit), &dh));
-    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
+    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(c.scratch(1, n * sizeof(CgrtHit), &dh));
     const bool big = n * sizeof(CgrtHit) > kStageBytes;  // as cgrt_intersect_batch
-    if (normals) {
-        HIP_TRY(g.dev(2, n * 12, &dn));
-        if (!big) HIP_TRY(lane_upload(g, 2, dn, normals, n * 12));
-    }
+    if (normals) HIP_TRY(big ? c.scratch(2, n * 12, &dn) : c.input(2, normals, n * 12, &dn));
     HIP_TRY(launch_brute_batch(s->dev, static_cast<const float*>(dr), n, mesh < 0 ? -1 : mesh, static_cast<CgrtHitDev*>(dh), static_cast<float*>(dn),
-                               g.L->stream));
-    void *sh = nullptr, *sn = nullptr;
-    HIP_TRY(lane_download(g, 1, hits, dh, n * sizeof(CgrtHit), &sh));
-    if (normals && !big) HIP_TRY(lane_download(g, 2, normals, dn, n * 12, &sn));
-    if (normals && big) HIP_TRY(lane_download(g, 2, normals, dn, n * 12, &sn, hits, 12));  // hits is complete here: only rays that hit
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (sh) std::memcpy(hits, sh, n * sizeof(CgrtHit));
-    if (sn) std::memcpy(normals, sn, n * 12);
+                               c.stream()));
+    HIP_TRY(c.output(1, hits, dh, n * sizeof(CgrtHit)));
+    if (normals) HIP_TRY(c.output(2, normals, dn, n * 12, big ? hits : nullptr, 12));  // big: hits is complete here, only rays that hit
+    HIP_TRY(c.finish());
     return CGRT_OK;
 }
 
@@ -1848,7 +1283,8 @@ static int raycams_check(const CgrtRayCamera* cams, uint32_t nviews, int W, int 
 static_assert(sizeof(CgrtRayCamera) == 80 && offsetof(CgrtRayCamera, x_off) == 72, "CgrtRayCamera: 18 contiguous floats, two offsets");
 static_assert(sizeof(CgrtRayCamera) == sizeof(RayCameraDev), "the device table holds the caller's records as they are");
 // (ray: the batch's cameras are ray cameras, `cams` the same pointer)
-static int views_args(const void* cams, uint32_t nviews, int W, int H, const CgrtRayCamera* ray = nullptr) {
+// (extern "C++": this and the like below are capi_internal.h's, defined inside this file's extern "C" block)
+extern "C++" int cgrt::views_args(const void* cams, uint32_t nviews, int W, int H, const CgrtRayCamera* ray) {
     if (!cams) return fail(CGRT_E_ARG, "cams is NULL");
     if (ray) {
         const int rc = raycams_check(ray, nviews, W, H);
@@ -1864,7 +1300,7 @@ static std::vector<CameraDev> view_cameras(const CgrtCamera* cams, uint32_t nvie
     return v;
 }
 // The device table of a batch, as bytes: CameraDev per Trackball view, or the caller's ray cameras as they are (RayCameraDev).
-static std::vector<uint8_t> view_table(const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews) {
+extern "C++" std::vector<uint8_t> cgrt::view_table(const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews) {
     std::vector<uint8_t> t;
     if (raycams) {
         t.resize((size_t)nviews * sizeof(RayCameraDev));
@@ -1876,12 +1312,11 @@ static std::vector<uint8_t> view_table(const CgrtCamera* cams, const CgrtRayCame
     }
     return t;
 }
-static int check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, const char* name);
 
 // A launch that reads a camera table and returns before it runs (cgrt_trace_primary_views_device, cgrt_surface_views_device and their
 // ray-camera twins): the table goes into the next of the scene's four slots (CgrtScene::ViewTable), is copied to the device on `st`,
 // `launch` is issued with the device copy, and the slot's event is recorded behind it.
-static int launch_with_view_table(CgrtScene* s, const std::vector<uint8_t>& tab, hipStream_t st, const std::function<hipError_t(const void*)>& launch) {
+extern "C++" int cgrt::launch_with_view_table(CgrtScene* s, const std::vector<uint8_t>& tab, hipStream_t st, const std::function<hipError_t(const void*)>& launch) {
     const size_t bytes = tab.size();
     std::lock_guard<std::mutex> lk(s->vtab_mutex);
     CgrtScene::ViewTable& T = s->vtab[s->vtab_seq++ & 3u];
@@ -1939,31 +1374,23 @@ int cgrt_trace_primary(CgrtScene* s, const CgrtCamera* cam, int W, int H, int x0
     if (!s || !cam || !hits) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);
     if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
-    HIP_TRY(hipSetDevice(s->device));
     const size_t npix = (size_t)W * (size_t)H;
-    LaneGuard g(s);
-    int rc = g.acquire();
+    LaneCall c(s);
+    int rc = c.begin();
     if (rc) return rc;
     void *dh, *dn = nullptr;
-    HIP_TRY(g.dev(1, npix * sizeof(CgrtHit), &dh));
     // pixels outside the traced tiles keep caller data: seed the device frame with it -- unless this call writes every pixel
     const bool whole_frame = (x0 == 0 && y0 == 0 && x1 == W && y1 == H && nranks == 1);
-    if (!whole_frame) HIP_TRY(lane_upload(g, 1, dh, hits, npix * sizeof(CgrtHit)));
+    HIP_TRY(whole_frame ? c.scratch(1, npix * sizeof(CgrtHit), &dh) : c.input(1, hits, npix * sizeof(CgrtHit), &dh));
     // normals of pixels that miss keep the caller's contents: seeded on the device, or -- a large whole frame, whose hit flags all
     // come from this call -- only the normals of pixels that hit are copied back
     const bool keep_by_hit = whole_frame && npix * sizeof(CgrtHit) > kStageBytes;
-    if (normals) {
-        HIP_TRY(g.dev(2, npix * 12, &dn));
-        if (!keep_by_hit) HIP_TRY(lane_upload(g, 2, dn, normals, npix * 12));
-    }
-    rc = cgrt_trace_primary_device(s, cam, W, H, x0, y0, x1, y1, rank, nranks, static_cast<CgrtHit*>(dh), static_cast<float*>(dn), g.L->stream);
+    if (normals) HIP_TRY(keep_by_hit ? c.scratch(2, npix * 12, &dn) : c.input(2, normals, npix * 12, &dn));
+    rc = cgrt_trace_primary_device(s, cam, W, H, x0, y0, x1, y1, rank, nranks, static_cast<CgrtHit*>(dh), static_cast<float*>(dn), c.stream());
     if (rc) return rc;
-    void *sh = nullptr, *sn = nullptr;
-    HIP_TRY(lane_download(g, 1, hits, dh, npix * sizeof(CgrtHit), &sh));
-    if (normals) HIP_TRY(lane_download(g, 2, normals, dn, npix * 12, &sn, keep_by_hit ? hits : nullptr, 12));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (sh) std::memcpy(hits, sh, npix * sizeof(CgrtHit));
-    if (sn) std::memcpy(normals, sn, npix * 12);
+    HIP_TRY(c.output(1, hits, dh, npix * sizeof(CgrtHit)));
+    if (normals) HIP_TRY(c.output(2, normals, dn, npix * 12, keep_by_hit ? hits : nullptr, 12));
+    HIP_TRY(c.finish());
     return CGRT_OK;
 }
 
@@ -1972,19 +1399,16 @@ int cgrt_generate_rays(CgrtScene* s, const CgrtCamera* cam, int W, int H, int x0
     NEED_DEVICE(s);
     FrameDev F;
     if (!make_frame(W, H, x0, y0, x1, y1, 0, 1, CGRT_BLOCK, F)) return fail(CGRT_E_ARG, "bad frame rectangle");
-    HIP_TRY(hipSetDevice(s->device));
     const size_t n = (size_t)(x1 - x0) * (size_t)(y1 - y0);
     if (!n) return CGRT_OK;
-    LaneGuard g(s);
-    int rc = g.acquire();
+    LaneCall c(s);
+    int rc = c.begin();
     if (rc) return rc;
     void* dr;
-    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(launch_generate_rays(make_camera(*cam), W, H, x0, y0, x1, y1, static_cast<float*>(dr), g.L->stream));
-    void* sr = nullptr;
-    HIP_TRY(lane_download(g, 0, rays, dr, n * sizeof(CgrtRay), &sr));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (sr) std::memcpy(rays, sr, n * sizeof(CgrtRay));
+    HIP_TRY(c.scratch(0, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(launch_generate_rays(make_camera(*cam), W, H, x0, y0, x1, y1, static_cast<float*>(dr), c.stream()));
+    HIP_TRY(c.output(0, rays, dr, n * sizeof(CgrtRay)));
+    HIP_TRY(c.finish());
     return CGRT_OK;
 }
 
@@ -1995,34 +1419,16 @@ int cgrt_generate_rays_raycam(CgrtScene* s, const CgrtRayCamera* cam, int W, int
     FrameDev F;
     if (!make_frame(W, H, 0, 0, W, H, 0, 1, CGRT_BLOCK, F)) return fail(CGRT_E_ARG, "bad frame size");
     NEED_DEVICE(s);
-    HIP_TRY(hipSetDevice(s->device));
     const size_t n = (size_t)W * (size_t)H;
-    LaneGuard g(s);
-    if ((rc = g.acquire())) return rc;
+    LaneCall c(s);
+    if ((rc = c.begin())) return rc;
     void* dr;
-    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(c.scratch(0, n * sizeof(CgrtRay), &dr));
     RayCameraDev C;
     std::memcpy(&C, cam, sizeof(C));
-    HIP_TRY(launch_generate_rays_raycam(C, W, H, static_cast<float*>(dr), g.L->stream));
-    void* sr = nullptr;
-    HIP_TRY(lane_download(g, 0, rays, dr, n * sizeof(CgrtRay), &sr));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (sr) std::memcpy(rays, sr, n * sizeof(CgrtRay));
-    return CGRT_OK;
-}
-
-static int read_counters(LaneGuard& g, CgrtCounters* out) {
-    unsigned long long h[8];
-    HIP_TRY(hipMemcpyAsync(h, g.L->d_counters, sizeof(h), hipMemcpyDeviceToHost, g.L->stream));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    out->rays = h[0];
-    out->inner_visits = h[1];
-    out->leaf_visits = h[2];
-    out->tri_tests = h[3];
-    out->sub_visits = h[4];
-    out->cert_boxes = h[5];
-    out->fallback_rays = h[6];
-    out->tree_rays = h[7];
+    HIP_TRY(launch_generate_rays_raycam(C, W, H, static_cast<float*>(dr), c.stream()));
+    HIP_TRY(c.output(0, rays, dr, n * sizeof(CgrtRay)));
+    HIP_TRY(c.finish());
     return CGRT_OK;
 }
 
@@ -2032,16 +1438,16 @@ int cgrt_count_primary(CgrtScene* s, const CgrtCamera* cam, int W, int H, int x0
     NEED_DEVICE(s);
     FrameDev F;
     if (!make_frame(W, H, x0, y0, x1, y1, rank, nranks, trace_block(s->dev), F)) return fail(CGRT_E_ARG, "bad frame rectangle or rank");
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    int rc = g.acquire();
+    LaneCall c(s);
+    int rc = c.begin();
     if (rc) return rc;
     void* dh;
-    HIP_TRY(g.dev(1, (size_t)W * (size_t)H * sizeof(CgrtHit), &dh));
-    HIP_TRY(hipMemsetAsync(g.L->d_counters, 0, 8 * sizeof(unsigned long long), g.L->stream));
-    rc = launch_primary(s, make_camera(*cam), F, static_cast<CgrtHitDev*>(dh), nullptr, g.L->d_counters, g.L->stream);
+    HIP_TRY(c.scratch(1, (size_t)W * (size_t)H * sizeof(CgrtHit), &dh));
+    HIP_TRY(c.zero_counters(8));
+    rc = launch_primary(s, make_camera(*cam), F, static_cast<CgrtHitDev*>(dh), nullptr, c.counters(), c.stream());
     if (rc) return rc;
-    return read_counters(g, out);
+    HIP_TRY(c.read_counters(&out->rays, 8));
+    return CGRT_OK;
 }
 
 int cgrt_debug_wave_times(CgrtScene* s, const CgrtCamera* cam, int W, int H, uint64_t* out, uint64_t cap_waves) {
@@ -2122,7 +1528,7 @@ int cgrt_debug_trace_shadow(CgrtScene* s, const CgrtRay* rays, const float* dist
 
 // SoftDev of the caller's sampling parameters, for SL spherical lights and the unit vectors where they lie on the device; level,
 // view_pixels and set_index are the caller's to set
-static SoftDev soft_dev(const CgrtSoftShadows& soft, unsigned SL, const float* lights, const float* units) {
+extern "C++" SoftDev cgrt::soft_dev(const CgrtSoftShadows& soft, unsigned SL, const float* lights, const float* units) {
     SoftDev Q{};
     Q.lights = lights, Q.units = units, Q.nlights = SL;
     Q.samples = soft.samples, Q.nunits = soft.nunits, Q.seed = soft.seed;
@@ -2163,17 +1569,16 @@ int cgrt_debug_soft_lit(CgrtScene* s, const CgrtRay* item_rays, const CgrtHit* i
 int cgrt_count_batch(CgrtScene* s, const CgrtRay* rays, uint64_t n, CgrtCounters* out) {
     if (!s || !out || (n && !rays)) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    int rc = g.acquire();
+    LaneCall c(s);
+    int rc = c.begin();
     if (rc) return rc;
     void *dr, *dh;
-    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(g.dev(1, n * sizeof(CgrtHit), &dh));
-    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
-    HIP_TRY(hipMemsetAsync(g.L->d_counters, 0, 8 * sizeof(unsigned long long), g.L->stream));
-    HIP_TRY(launch_trace_batch(s->dev, static_cast<const float*>(dr), n, static_cast<CgrtHitDev*>(dh), nullptr, g.L->d_counters, g.L->stream));
-    return read_counters(g, out);
+    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(c.scratch(1, n * sizeof(CgrtHit), &dh));
+    HIP_TRY(c.zero_counters(8));
+    HIP_TRY(launch_trace_batch(s->dev, static_cast<const float*>(dr), n, static_cast<CgrtHitDev*>(dh), nullptr, c.counters(), c.stream()));
+    HIP_TRY(c.read_counters(&out->rays, 8));
+    return CGRT_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2314,7 +1719,7 @@ static ExportDev export_of(const FrameDev& F, const float* src, const DeviceOut&
     return E;
 }
 // cgrt_shade_rays' rules for the spherical lights, which every frame entry shares; NULL = no spherical lights
-static int soft_rules(const CgrtSoftShadows* soft) {
+extern "C++" int cgrt::soft_rules(const CgrtSoftShadows* soft) {
     if (soft && soft->nspherical &&
         (!soft->spherical || !soft->unit_vectors || soft->nunits == 0 || soft->samples == 0 || soft->samples > (1u << 24)))
         return fail(CGRT_E_ARG, "soft shadows need lights, a unit-vector table and 1..2^24 samples");
@@ -3061,7 +2466,7 @@ static int export_args(const void* out, int W, int H, int format, uint64_t row_b
 // one another in the address space (a caching allocator that maps its pool in pieces through the virtual-memory API, e.g. torch's
 // expandable segments), each checked.  A pointer this HIP runtime does not know (another copy of the runtime in the process, host memory)
 // is refused here, before any work.  Used by every entry that takes a caller's device buffer (cgrt_render_device, cgrt_shade_rays_device).
-static int check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, const char* name) {
+extern "C++" int cgrt::check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, const char* name) {
     uintptr_t at = (uintptr_t)p;
     const uintptr_t end = at + bytes;
     for (int piece = 0; at < end; piece++) {
@@ -3420,21 +2825,17 @@ int cgrt_shade_rays(CgrtScene* s, const CgrtRay* rays, uint64_t n, const float* 
         if (stats) *stats = CgrtRenderStats{};
         return CGRT_OK;
     }
-    HIP_TRY(hipSetDevice(s->device));
     // the rays go up and the colours come down through a call lane's pinned staging, on the lane's stream
-    LaneGuard g(s);
-    if ((rc = g.acquire()) != CGRT_OK) return rc;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
     void *dr = nullptr, *dc = nullptr;
-    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(g.dev(1, n * 12, &dc));
-    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
-    const ListSrc src{static_cast<const float*>(dr), n, static_cast<float*>(dc), g.L->stream};
+    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(c.scratch(1, n * 12, &dc));
+    const ListSrc src{static_cast<const float*>(dr), n, static_cast<float*>(dc), c.stream()};
     rc = render_frame(s, list_request(&src, lights, nlights, soft, max_level), stats);
     if (rc) return rc;
-    void* staged = nullptr;
-    HIP_TRY(lane_download(g, 1, rgb, dc, n * 12, &staged));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (staged) std::memcpy(rgb, staged, n * 12);
+    HIP_TRY(c.output(1, rgb, dc, n * 12));
+    HIP_TRY(c.finish());
     return CGRT_OK;
 }
 
@@ -3730,659 +3131,6 @@ int cgrt_enqueue_stats(CgrtScene* s, uint64_t ticket, CgrtRenderStats* stats) {
     return CGRT_OK;
 }
 
-// ---- visibility queries (include/cgrt.h cgrt_occluded*, cgrt_in_shadow*, cgrt_soft_lit*): the reference's intersect() bool, pointInShadow
-// and shading's soft-shadow counts for the caller's rays / points.  Arguments are checked in the order include/cgrt.h states, all before any
-// device work; then a host-only scene is CGRT_E_NO_DEVICE.  None of them touches the scene's frame prediction or frame hints.
-namespace {
-const uint64_t kMaxAnswers = 0x7fffffffull;
-// NULL pointers (the rays / points and the output with n > 0, lights missing), then n and n x per_point above 0x7fffffff
-int query_args(const CgrtScene* s, const void* in, uint64_t n, const void* out, uint64_t per_point, bool lights_missing) {
-    if (!s || (n && (!in || !out)) || lights_missing) return fail(CGRT_E_ARG, "NULL argument");
-    if (n > kMaxAnswers || (per_point && n > kMaxAnswers / per_point)) return fail(CGRT_E_ARG, "too many answers: n (x lights) exceeds 0x7fffffff");
-    return CGRT_OK;
-}
-// The device forms that read the caller's host light tables run on a call lane, behind everything queued on `stream` before the call (an
-// event on `stream` that the lane's stream waits for); they return when the answers are in place.
-hipError_t lane_follow(LaneGuard& g, hipStream_t stream) {
-    hipError_t e = hipSuccess;
-    if (!g.L->follow && (e = hipEventCreateWithFlags(&g.L->follow, hipEventDisableTiming)) != hipSuccess) return e;
-    if ((e = hipEventRecord(g.L->follow, stream)) != hipSuccess) return e;
-    return hipStreamWaitEvent(g.L->stream, g.L->follow, 0);
-}
-// n points x nlights lights on the lane's stream (lights through the lane's slot 3)
-int in_shadow_on_lane(LaneGuard& g, CgrtScene* s, const float* d_points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* d_out) {
-    void* dl = nullptr;
-    HIP_TRY(g.dev(3, (size_t)nlights * 24, &dl));
-    HIP_TRY(lane_upload(g, 3, dl, lights, (size_t)nlights * 24));
-    HIP_TRY(launch_in_shadow(s->dev, d_points, n, static_cast<const float*>(dl), nlights, d_out, g.L->stream));
-    return CGRT_OK;
-}
-// the soft-shadow counts of n points on the lane's stream (spherical lights through slot 3, the unit vectors through slot 2); d_lit zeroed here
-int soft_lit_on_lane(LaneGuard& g, CgrtScene* s, const float* d_points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* d_lit) {
-    const uint64_t SL = soft->nspherical;
-    void *dl = nullptr, *du = nullptr;
-    HIP_TRY(g.dev(3, SL * 28, &dl));
-    HIP_TRY(g.dev(2, (size_t)soft->nunits * 12, &du));
-    HIP_TRY(lane_upload(g, 3, dl, soft->spherical, SL * 28));
-    HIP_TRY(lane_upload(g, 2, du, soft->unit_vectors, (size_t)soft->nunits * 12));
-    HIP_TRY(hipMemsetAsync(d_lit, 0, n * SL * sizeof(uint32_t), g.L->stream));
-    // (level stays 0, cgrt_shade_rays' convention: pixel = i, level 0)
-    const SoftDev Q = soft_dev(*soft, (unsigned)SL, static_cast<const float*>(dl), static_cast<const float*>(du));
-    HIP_TRY(launch_soft_points(s->dev, Q, d_points, n, d_lit, soft->closest_hit ? 0 : 1, g.L->stream));
-    return CGRT_OK;
-}
-}  // namespace
-
-int cgrt_occluded_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, uint8_t* d_hit, void* stream) {
-    int rc = query_args(s, d_rays, n, d_hit, 0, false);
-    if (rc) return rc;
-    if ((uintptr_t)d_rays % 4) return fail(CGRT_E_ARG, "d_rays must be 4-byte aligned");
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_hit, n, "d_hit")) != CGRT_OK) return rc;
-    HIP_TRY(launch_occluded(s->dev, reinterpret_cast<const float*>(d_rays), n, d_hit, static_cast<hipStream_t>(stream)));
-    return CGRT_OK;
-}
-int cgrt_occluded(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint8_t* hit) {
-    int rc = query_args(s, rays, n, hit, 0, false);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    if ((rc = g.acquire()) != CGRT_OK) return rc;
-    void *dr = nullptr, *dh = nullptr, *staged = nullptr;
-    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(g.dev(1, n, &dh));
-    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
-    HIP_TRY(launch_occluded(s->dev, static_cast<const float*>(dr), n, static_cast<uint8_t*>(dh), g.L->stream));
-    HIP_TRY(lane_download(g, 1, hit, dh, n, &staged));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (staged) std::memcpy(hit, staged, n);
-    return CGRT_OK;
-}
-
-int cgrt_in_shadow_device(CgrtScene* s, const float* d_points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* d_out, void* stream) {
-    int rc = query_args(s, d_points, n, d_out, nlights, nlights && !lights);
-    if (rc) return rc;
-    if ((uintptr_t)d_points % 4) return fail(CGRT_E_ARG, "d_points must be 4-byte aligned");
-    NEED_DEVICE(s);
-    if (n == 0 || nlights == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_out, n * nlights, "d_out")) != CGRT_OK) return rc;
-    LaneGuard g(s);
-    if ((rc = g.acquire()) != CGRT_OK) return rc;
-    HIP_TRY(lane_follow(g, static_cast<hipStream_t>(stream)));
-    if ((rc = in_shadow_on_lane(g, s, d_points, n, lights, nlights, d_out)) != CGRT_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    return CGRT_OK;
-}
-int cgrt_in_shadow(CgrtScene* s, const float* points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* out) {
-    int rc = query_args(s, points, n, out, nlights, nlights && !lights);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0 || nlights == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    if ((rc = g.acquire()) != CGRT_OK) return rc;
-    const uint64_t m = n * nlights;
-    void *dp = nullptr, *dout = nullptr, *staged = nullptr;
-    HIP_TRY(g.dev(0, n * 12, &dp));
-    HIP_TRY(g.dev(1, m, &dout));
-    HIP_TRY(lane_upload(g, 0, dp, points, n * 12));
-    if ((rc = in_shadow_on_lane(g, s, static_cast<const float*>(dp), n, lights, nlights, static_cast<uint8_t*>(dout))) != CGRT_OK) return rc;
-    HIP_TRY(lane_download(g, 1, out, dout, m, &staged));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (staged) std::memcpy(out, staged, m);
-    return CGRT_OK;
-}
-
-int cgrt_soft_lit_device(CgrtScene* s, const float* d_points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* d_lit, void* stream) {
-    const uint32_t SL = soft ? soft->nspherical : 0u;
-    int rc = query_args(s, d_points, n, d_lit, SL, false);
-    if (rc) return rc;
-    if ((rc = soft_rules(soft)) != CGRT_OK) return rc;
-    if ((uintptr_t)d_points % 4 || (uintptr_t)d_lit % 4) return fail(CGRT_E_ARG, "d_points and d_lit must be 4-byte aligned");
-    NEED_DEVICE(s);
-    if (n == 0 || SL == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_lit, n * SL * 4, "d_lit")) != CGRT_OK) return rc;
-    LaneGuard g(s);
-    if ((rc = g.acquire()) != CGRT_OK) return rc;
-    HIP_TRY(lane_follow(g, static_cast<hipStream_t>(stream)));
-    if ((rc = soft_lit_on_lane(g, s, d_points, n, soft, d_lit)) != CGRT_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    return CGRT_OK;
-}
-int cgrt_soft_lit(CgrtScene* s, const float* points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* lit) {
-    const uint32_t SL = soft ? soft->nspherical : 0u;
-    int rc = query_args(s, points, n, lit, SL, false);
-    if (rc) return rc;
-    if ((rc = soft_rules(soft)) != CGRT_OK) return rc;
-    NEED_DEVICE(s);
-    if (n == 0 || SL == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    if ((rc = g.acquire()) != CGRT_OK) return rc;
-    const uint64_t m = n * SL * sizeof(uint32_t);
-    void *dp = nullptr, *dl = nullptr, *staged = nullptr;
-    HIP_TRY(g.dev(0, n * 12, &dp));
-    HIP_TRY(g.dev(1, m, &dl));
-    HIP_TRY(lane_upload(g, 0, dp, points, n * 12));
-    if ((rc = soft_lit_on_lane(g, s, static_cast<const float*>(dp), n, soft, static_cast<uint32_t*>(dl))) != CGRT_OK) return rc;
-    HIP_TRY(lane_download(g, 1, lit, dl, m, &staged));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (staged) std::memcpy(lit, staged, m);
-    return CGRT_OK;
-}
-
-// ---- surface attributes (include/cgrt.h cgrt_hit_barycentrics*, cgrt_interpolate_hits*, cgrt_surface_*_device):
-// where inside its triangle a hit lies, and a caller's per-vertex table carried there.  Nothing is traced and no scene state is read or
-// written except the lookup table below; the checks come in the order include/cgrt.h states, all before any device work.
-namespace {
-const uint64_t kSurfaceMaxBytes = 1ull << 40;  // an output's size: items x channels x 4 bytes (the kernel indexes with 64 bits; a documented bound)
-int surface_channels(uint32_t channels, uint64_t items) {
-    if (channels < 1 || channels > 256) return fail(CGRT_E_ARG, "channels must be in 1..256");
-    if (items * channels * 4ull > kSurfaceMaxBytes) return fail(CGRT_E_ARG, "output too large: items x channels x 4 exceeds 2^40 bytes");
-    return CGRT_OK;
-}
-// prim_id -> {record, three vertex rows}, made once per scene by its first surface call (later calls: one atomic load)
-int surface_lookup(CgrtScene* s, const SurfaceLookup** out) {
-    void* p = s->d_surface_lookup.load(std::memory_order_acquire);
-    if (!p) {
-        std::lock_guard<std::mutex> lk(s->surface_mutex);
-        p = s->d_surface_lookup.load(std::memory_order_acquire);
-        if (!p) {
-            std::vector<SurfaceLookup> T;
-            try {
-                T.resize(s->ntris);
-            } catch (const std::bad_alloc&) {
-                return fail(CGRT_E_ALLOC, "host allocation failed");
-            }
-            const std::vector<TriRecord>& R = s->bvh.tris;
-            if (R.size() != s->ntris || s->tri_index.size() != 3 * (size_t)s->ntris) return fail(CGRT_E_ARG, "the scene's records do not cover its triangles");
-            for (size_t k = 0; k < R.size(); k++) {
-                const uint32_t prim = R[k].prim_id;
-                if (prim >= s->ntris) return fail(CGRT_E_ARG, "a triangle record carries a primitive id out of range");
-                T[prim].record = s->bvh.tri_base + (uint32_t)k;
-                for (int c = 0; c < 3; c++) T[prim].v[c] = s->tri_index[3 * (size_t)prim + c];
-            }
-            const size_t bytes = T.size() * sizeof(SurfaceLookup);
-            void* d = nullptr;
-            HIP_TRY(hipMalloc(&d, bytes ? bytes : 16));
-            if (bytes) {
-                const hipError_t e = staged_h2d(d, T.data(), bytes);  // (complete when it returns: every later launch sees the table)
-                if (e != hipSuccess) {
-                    (void)hipFree(d);
-                    return hip_fail(e, "uploading the surface lookup table");
-                }
-            }
-            s->device_bytes += bytes;
-            s->d_surface_lookup.store(d, std::memory_order_release);
-            p = d;
-        }
-    }
-    *out = static_cast<const SurfaceLookup*>(p);
-    return CGRT_OK;
-}
-SurfaceDev surface_dev(const CgrtScene* s, const SurfaceLookup* lookup, uint64_t n, const float* d_attr, uint32_t channels, float* d_bary,
-                       float* d_out, int chw) {
-    SurfaceDev A{};
-    A.tris = s->dev.tris;
-    A.lookup = lookup;
-    A.ntris = s->dev.ntris;
-    A.n = (uint32_t)n;
-    A.attr = d_out ? d_attr : nullptr;
-    A.channels = d_out ? channels : 0;
-    A.bary = d_bary;
-    A.out = d_out;
-    A.chw = chw ? 1 : 0;
-    A.vec4 = d_out && channels % 4 == 0 && (uintptr_t)d_attr % 16 == 0 && (uintptr_t)d_out % 16 == 0;
-    return A;
-}
-// the list forms' checks up to the host-only scene (attr: the call interpolates; device: the pointers' alignment is checked too)
-int surface_list_args(const CgrtScene* s, const void* rays, const void* hits, uint64_t n, bool attr, const void* table, uint32_t channels,
-                      const void* out, bool device) {
-    if (!s || (n && (!rays || !hits || !out || (attr && !table)))) return fail(CGRT_E_ARG, "NULL argument");
-    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many hits: n exceeds 0x7fffffff");
-    if (attr) {
-        const int rc = surface_channels(channels, n);
-        if (rc) return rc;
-    }
-    if (device && ((uintptr_t)rays % 4 || (uintptr_t)hits % 4 || (uintptr_t)table % 4 || (uintptr_t)out % 4))
-        return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
-    return CGRT_OK;
-}
-// d_bary or d_out (with d_attr, channels) of n hits on `st`; every pointer device memory
-int surface_list_launch(CgrtScene* s, const void* d_rays, const void* d_hits, uint64_t n, const float* d_attr, uint32_t channels, float* d_bary,
-                        float* d_out, hipStream_t st) {
-    const SurfaceLookup* lookup = nullptr;
-    const int rc = surface_lookup(s, &lookup);
-    if (rc) return rc;
-    SurfaceDev A = surface_dev(s, lookup, n, d_attr, channels, d_bary, d_out, 0);
-    A.rays = static_cast<const float*>(d_rays);
-    A.hits = static_cast<const CgrtHitDev*>(d_hits);
-    HIP_TRY(launch_surface(A, SURFACE_LIST, st));
-    return CGRT_OK;
-}
-int surface_list_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, bool attr, const float* d_attr, uint32_t channels,
-                        float* d_res, void* stream) {
-    int rc = surface_list_args(s, d_rays, d_hits, n, attr, d_attr, channels, d_res, true);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_hits, n * sizeof(CgrtHit), "d_hits")) != CGRT_OK) return rc;
-    if (attr && (rc = check_device_span(s, d_attr, (uint64_t)s->nverts * channels * 4ull, "d_attr")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_res, n * (attr ? channels : 3u) * 4ull, attr ? "d_out" : "d_bary")) != CGRT_OK) return rc;
-    return surface_list_launch(s, d_rays, d_hits, n, d_attr, channels, attr ? nullptr : d_res, attr ? d_res : nullptr, static_cast<hipStream_t>(stream));
-}
-// host pointers, on a call lane (slots: 0 rays, 1 hits, 2 the result, 3 the attribute table)
-int surface_list_host(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, bool attr, const float* table, uint32_t channels, float* res) {
-    int rc = surface_list_args(s, rays, hits, n, attr, table, channels, res, false);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    if ((rc = g.acquire()) != CGRT_OK) return rc;
-    const size_t res_bytes = (size_t)n * (attr ? channels : 3u) * 4u, table_bytes = attr ? (size_t)s->nverts * channels * 4u : 0;
-    void *dr = nullptr, *dh = nullptr, *dres = nullptr, *dt = nullptr, *staged = nullptr;
-    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(g.dev(1, n * sizeof(CgrtHit), &dh));
-    HIP_TRY(g.dev(2, res_bytes, &dres));
-    if (attr) HIP_TRY(g.dev(3, table_bytes, &dt));
-    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
-    HIP_TRY(lane_upload(g, 1, dh, hits, n * sizeof(CgrtHit)));
-    if (attr) HIP_TRY(lane_upload(g, 3, dt, table, table_bytes));
-    if ((rc = surface_list_launch(s, dr, dh, n, static_cast<const float*>(dt), channels, attr ? nullptr : static_cast<float*>(dres),
-                                  attr ? static_cast<float*>(dres) : nullptr, g.L->stream)) != CGRT_OK)
-        return rc;
-    HIP_TRY(lane_download(g, 2, res, dres, res_bytes, &staged));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (staged) std::memcpy(res, staged, res_bytes);
-    return CGRT_OK;
-}
-// cgrt_surface_views_device and its ray-camera twin (exactly one of cams, raycams)
-int surface_frames_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H, const float* d_depth,
-                          const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
-    if (!s || !d_depth || !d_prim_id || (!d_bary && !d_out) || (d_out && !d_attr)) return fail(CGRT_E_ARG, "NULL argument");
-    int rc = views_args(raycams ? static_cast<const void*>(raycams) : cams, nviews, W, H, raycams);
-    if (rc) return rc;
-    const uint64_t npix = (uint64_t)nviews * (uint64_t)W * (uint64_t)H;
-    if (d_out && (rc = surface_channels(channels, npix)) != CGRT_OK) return rc;
-    if ((uintptr_t)d_depth % 4 || (uintptr_t)d_prim_id % 4 || (uintptr_t)d_attr % 4 || (uintptr_t)d_bary % 4 || (uintptr_t)d_out % 4)
-        return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
-    NEED_DEVICE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_depth, npix * 4, "d_depth")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_prim_id, npix * 4, "d_prim_id")) != CGRT_OK) return rc;
-    if (d_out && (rc = check_device_span(s, d_attr, (uint64_t)s->nverts * channels * 4ull, "d_attr")) != CGRT_OK) return rc;
-    if (d_bary && (rc = check_device_span(s, d_bary, npix * 12, "d_bary")) != CGRT_OK) return rc;
-    if (d_out && (rc = check_device_span(s, d_out, npix * channels * 4ull, "d_out")) != CGRT_OK) return rc;
-    const SurfaceLookup* lookup = nullptr;
-    if ((rc = surface_lookup(s, &lookup)) != CGRT_OK) return rc;
-    SurfaceDev A = surface_dev(s, lookup, npix, d_attr, channels, d_bary, d_out, chw);
-    A.depth = d_depth;
-    A.prim = d_prim_id;
-    A.W = W;
-    A.H = H;
-    A.plane = (uint32_t)((uint64_t)W * (uint64_t)H);
-    hipStream_t const st = static_cast<hipStream_t>(stream);
-    return launch_with_view_table(s, view_table(cams, raycams, nviews), st, [&](const void* d_table) {
-        A.cams = d_table;
-        return launch_surface(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, st);
-    });
-}
-
-// ---- the adjoint with respect to the table (include/cgrt.h cgrt_interpolate_hits_grad*, cgrt_surface_*_grad_device; DESIGN.md section
-// 5.23): twins of the entries above, grad_out in the place of out and grad_attr in the place of attr, the same checks in the same order.
-SurfaceGradDev surface_grad_dev(const CgrtScene* s, const SurfaceLookup* lookup, uint64_t n, const float* d_grad_out, uint32_t channels,
-                                float* d_grad_attr, int chw) {
-    SurfaceGradDev A{};
-    A.tris = s->dev.tris;
-    A.lookup = lookup;
-    A.ntris = s->dev.ntris;
-    A.n = (uint32_t)n;
-    A.grad_out = d_grad_out;
-    A.channels = channels;
-    A.grad_attr = d_grad_attr;
-    A.chw = chw ? 1 : 0;
-    surface_grad_policy(channels, A.chw, &A.by_item, &A.combine);
-    return A;
-}
-int surface_list_grad_launch(CgrtScene* s, const void* d_rays, const void* d_hits, uint64_t n, const float* d_grad_out, uint32_t channels,
-                             float* d_grad_attr, hipStream_t st) {
-    const SurfaceLookup* lookup = nullptr;
-    const int rc = surface_lookup(s, &lookup);
-    if (rc) return rc;
-    SurfaceGradDev A = surface_grad_dev(s, lookup, n, d_grad_out, channels, d_grad_attr, 0);
-    A.rays = static_cast<const float*>(d_rays);
-    A.hits = static_cast<const CgrtHitDev*>(d_hits);
-    HIP_TRY(launch_surface_grad(A, SURFACE_LIST, st));
-    return CGRT_OK;
-}
-int surface_list_grad_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out, uint32_t channels,
-                             float* d_grad_attr, void* stream) {
-    int rc = surface_list_args(s, d_rays, d_hits, n, true, d_grad_attr, channels, d_grad_out, true);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_hits, n * sizeof(CgrtHit), "d_hits")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_grad_out, n * channels * 4ull, "d_grad_out")) != CGRT_OK) return rc;
-    return surface_list_grad_launch(s, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, static_cast<hipStream_t>(stream));
-}
-// host pointers, on a call lane (slots: 0 rays, 1 hits, 2 grad_out, 3 grad_attr: uploaded, accumulated into, downloaded)
-int surface_list_grad_host(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
-                           float* grad_attr) {
-    int rc = surface_list_args(s, rays, hits, n, true, grad_attr, channels, grad_out, false);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    if ((rc = g.acquire()) != CGRT_OK) return rc;
-    const size_t go_bytes = (size_t)n * channels * 4u, table_bytes = (size_t)s->nverts * channels * 4u;
-    void *dr = nullptr, *dh = nullptr, *dgo = nullptr, *dt = nullptr, *staged = nullptr;
-    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(g.dev(1, n * sizeof(CgrtHit), &dh));
-    HIP_TRY(g.dev(2, go_bytes, &dgo));
-    HIP_TRY(g.dev(3, table_bytes, &dt));
-    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
-    HIP_TRY(lane_upload(g, 1, dh, hits, n * sizeof(CgrtHit)));
-    HIP_TRY(lane_upload(g, 2, dgo, grad_out, go_bytes));
-    HIP_TRY(lane_upload(g, 3, dt, grad_attr, table_bytes));
-    if ((rc = surface_list_grad_launch(s, dr, dh, n, static_cast<const float*>(dgo), channels, static_cast<float*>(dt), g.L->stream)) != CGRT_OK)
-        return rc;
-    HIP_TRY(lane_download(g, 3, grad_attr, dt, table_bytes, &staged));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (staged) std::memcpy(grad_attr, staged, table_bytes);
-    return CGRT_OK;
-}
-// cgrt_surface_views_grad_device and its ray-camera twin (exactly one of cams, raycams)
-int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H,
-                               const float* d_depth, const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw,
-                               float* d_grad_attr, void* stream) {
-    if (!s || !d_depth || !d_prim_id || !d_grad_out || !d_grad_attr) return fail(CGRT_E_ARG, "NULL argument");
-    int rc = views_args(raycams ? static_cast<const void*>(raycams) : cams, nviews, W, H, raycams);
-    if (rc) return rc;
-    const uint64_t npix = (uint64_t)nviews * (uint64_t)W * (uint64_t)H;
-    if ((rc = surface_channels(channels, npix)) != CGRT_OK) return rc;
-    if ((uintptr_t)d_depth % 4 || (uintptr_t)d_prim_id % 4 || (uintptr_t)d_grad_attr % 4 || (uintptr_t)d_grad_out % 4)
-        return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
-    NEED_DEVICE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_depth, npix * 4, "d_depth")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_prim_id, npix * 4, "d_prim_id")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_grad_out, npix * channels * 4ull, "d_grad_out")) != CGRT_OK) return rc;
-    const SurfaceLookup* lookup = nullptr;
-    if ((rc = surface_lookup(s, &lookup)) != CGRT_OK) return rc;
-    SurfaceGradDev A = surface_grad_dev(s, lookup, npix, d_grad_out, channels, d_grad_attr, chw);
-    A.depth = d_depth;
-    A.prim = d_prim_id;
-    A.W = W;
-    A.H = H;
-    A.plane = (uint32_t)((uint64_t)W * (uint64_t)H);
-    hipStream_t const st = static_cast<hipStream_t>(stream);
-    return launch_with_view_table(s, view_table(cams, raycams, nviews), st, [&](const void* d_table) {
-        A.cams = d_table;
-        return launch_surface_grad(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, st);
-    });
-}
-}  // namespace
-
-int cgrt_interpolate_hits_grad(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
-                               float* grad_attr) {
-    return surface_list_grad_host(s, rays, hits, n, grad_out, channels, grad_attr);
-}
-int cgrt_interpolate_hits_grad_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out,
-                                      uint32_t channels, float* d_grad_attr, void* stream) {
-    return surface_list_grad_device(s, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, stream);
-}
-int cgrt_surface_views_grad_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
-                                   const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
-                                   void* stream) {
-    return surface_frames_grad_device(s, cams, nullptr, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, stream);
-}
-int cgrt_surface_raycams_grad_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
-                                     const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
-                                     void* stream) {
-    return surface_frames_grad_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, stream);
-}
-
-int cgrt_hit_barycentrics(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, float* bary) {
-    return surface_list_host(s, rays, hits, n, false, nullptr, 0, bary);
-}
-int cgrt_hit_barycentrics_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, float* d_bary, void* stream) {
-    return surface_list_device(s, d_rays, d_hits, n, false, nullptr, 0, d_bary, stream);
-}
-int cgrt_interpolate_hits(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* attr, uint32_t channels, float* out) {
-    return surface_list_host(s, rays, hits, n, true, attr, channels, out);
-}
-int cgrt_interpolate_hits_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_attr, uint32_t channels,
-                                 float* d_out, void* stream) {
-    return surface_list_device(s, d_rays, d_hits, n, true, d_attr, channels, d_out, stream);
-}
-int cgrt_surface_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth, const uint32_t* d_prim_id,
-                              const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
-    return surface_frames_device(s, cams, nullptr, nviews, W, H, d_depth, d_prim_id, d_attr, channels, d_bary, d_out, chw, stream);
-}
-int cgrt_surface_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
-                                const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
-    return surface_frames_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_attr, channels, d_bary, d_out, chw, stream);
-}
-
-// ---- closest-point queries (include/cgrt.h cgrt_closest_points*): the nearest surface point of every query point.
-// Nothing is traced and no scene state is read or written; the checks come in the order include/cgrt.h states, all before any device work.
-namespace {
-static_assert(sizeof(CgrtClosest) == sizeof(CgrtClosestDev), "CgrtClosest is what the kernels write");
-int closest_args(const CgrtScene* s, const void* points, uint64_t n, float max_dist2, const void* out, bool device) {
-    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
-    if (n && (!points || !out)) return fail(CGRT_E_ARG, "NULL argument");
-    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many queries: n exceeds 0x7fffffff");
-    if (!(max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
-    if (device && ((uintptr_t)points % 4 || (uintptr_t)out % 4)) return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
-    return CGRT_OK;
-}
-// host pointers, on a call lane (slots: 0 the points, 1 the records); how: 0 tree search, 1 brute force, 2 counted tree search
-int closest_host(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out, int how, uint64_t* work) {
-    int rc = closest_args(s, points, n, max_dist2, how == 2 ? static_cast<const void*>(work) : out, false);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    if ((rc = g.acquire()) != CGRT_OK) return rc;
-    const size_t out_bytes = (size_t)n * sizeof(CgrtClosest);
-    void *dp = nullptr, *dout = nullptr, *staged = nullptr;
-    HIP_TRY(g.dev(0, n * 12, &dp));
-    HIP_TRY(g.dev(1, out_bytes, &dout));
-    HIP_TRY(lane_upload(g, 0, dp, points, n * 12));
-    if (how == 2) {
-        HIP_TRY(hipMemsetAsync(g.L->d_counters, 0, 2 * sizeof(unsigned long long), g.L->stream));
-        HIP_TRY(launch_closest(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), g.L->d_counters, g.L->stream));
-        unsigned long long h[2];
-        HIP_TRY(hipMemcpyAsync(h, g.L->d_counters, sizeof(h), hipMemcpyDeviceToHost, g.L->stream));
-        HIP_TRY(hipStreamSynchronize(g.L->stream));
-        work[0] = h[0];
-        work[1] = h[1];
-        return CGRT_OK;
-    }
-    if (how == 1)
-        HIP_TRY(launch_closest_brute(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), g.L->stream));
-    else
-        HIP_TRY(launch_closest(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), nullptr, g.L->stream));
-    HIP_TRY(lane_download(g, 1, out, dout, out_bytes, &staged));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (staged) std::memcpy(out, staged, out_bytes);
-    return CGRT_OK;
-}
-}  // namespace
-
-int cgrt_closest_points(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out) {
-    return closest_host(s, points, n, max_dist2, out, 0, nullptr);
-}
-int cgrt_closest_points_brute(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out) {
-    return closest_host(s, points, n, max_dist2, out, 1, nullptr);
-}
-int cgrt_debug_closest_work(CgrtScene* s, const float* points, uint64_t n, float max_dist2, uint64_t* out2) {
-    return closest_host(s, points, n, max_dist2, nullptr, 2, out2);
-}
-int cgrt_closest_points_device(CgrtScene* s, const float* d_points, uint64_t n, float max_dist2, CgrtClosest* d_out, void* stream) {
-    int rc = closest_args(s, d_points, n, max_dist2, d_out, true);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_out, n * sizeof(CgrtClosest), "d_out")) != CGRT_OK) return rc;
-    HIP_TRY(launch_closest(s->dev, d_points, n, max_dist2, reinterpret_cast<CgrtClosestDev*>(d_out), nullptr, static_cast<hipStream_t>(stream)));
-    return CGRT_OK;
-}
-
-// ---- crossing queries (include/cgrt.h cgrt_count_crossings*, cgrt_list_crossings*): every triangle a ray passes
-// through, counted or listed in (t, prim_id) order.  No scene state is read or written; the checks come in the order include/cgrt.h
-// states, all before any device work.
-namespace {
-static_assert(sizeof(CgrtCrossing) == sizeof(CgrtCrossingDev), "CgrtCrossing is what the kernels write");
-const uint64_t kCrossingMaxCapacity = 1ull << 37;
-// where the conservative box test's argument does not hold the whole call tests every triangle: a wild triangle is accepted by every ray
-// wherever its boxes are, and a non-finite vertex leaves its boxes meaningless
-bool crossing_brute_scene(const CgrtScene* s) {
-    if (!s->bvh.geometry_finite) return true;
-    for (uint8_t w : s->bvh.leaf_wild)
-        if (w) return true;
-    return false;
-}
-// result: counts for the count entries, out2 for the work entry, out for the list entries; list: the slot arguments are checked
-int crossing_args(const CgrtScene* s, const void* rays, uint64_t n, const void* result, bool list, const uint64_t* offsets, uint32_t k,
-                  uint64_t capacity, const void* counts, bool device) {
-    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
-    if (n && (!rays || !result)) return fail(CGRT_E_ARG, "NULL argument");
-    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many rays: n exceeds 0x7fffffff");
-    if (list) {
-        if ((offsets != nullptr) == (k > 0)) return fail(CGRT_E_ARG, "exactly one of offsets and k > 0 must be given");
-        if (capacity > kCrossingMaxCapacity) return fail(CGRT_E_ARG, "capacity exceeds 2^37 records");
-        if (k && n * (uint64_t)k > capacity) return fail(CGRT_E_ARG, "n * k records exceed capacity");
-        if (!device && offsets && n) {
-            if (offsets[0] != 0) return fail(CGRT_E_ARG, "offsets must start at 0");
-            for (uint64_t i = 0; i < n; i++)
-                if (offsets[i + 1] < offsets[i]) return fail(CGRT_E_ARG, "offsets must not decrease");
-            if (offsets[n] > capacity) return fail(CGRT_E_ARG, "offsets end beyond capacity");
-        }
-    }
-    if (device && ((uintptr_t)rays % 4 || (uintptr_t)result % 4 || (uintptr_t)counts % 4 || (uintptr_t)offsets % 8))
-        return fail(CGRT_E_ARG, "device pointers must be aligned to their elements");
-    return CGRT_OK;
-}
-// host pointers, on a call lane (slots: 0 the rays, 1 the offsets, 2 the records, 3 the counts); how: 0 tree search, 1 brute force,
-// 2 counted tree search (count mode)
-int crossing_host(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out, uint64_t capacity,
-                  uint32_t* counts, bool list, int how, uint64_t* work) {
-    int rc = crossing_args(s, rays, n, how == 2 ? static_cast<const void*>(work) : (list ? static_cast<const void*>(out) : counts), list, offsets,
-                           k, capacity, counts, false);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    const uint64_t used = list ? (offsets ? offsets[n] : n * (uint64_t)k) : 0;  // the slots are records [0, used)
-    const bool want_counts = !list || counts != nullptr;
-    if (how != 2 && used == 0 && !want_counts) return CGRT_OK;  // every slot is empty and no count is asked for: nothing to write
-    HIP_TRY(hipSetDevice(s->device));
-    LaneGuard g(s);
-    if ((rc = g.acquire()) != CGRT_OK) return rc;
-    const bool brute = how == 1 || crossing_brute_scene(s);
-    const size_t out_bytes = (size_t)used * sizeof(CgrtCrossing), cnt_bytes = (size_t)n * 4u;
-    void *dr = nullptr, *doff = nullptr, *dout = nullptr, *dcnt = nullptr, *staged_out = nullptr, *staged_cnt = nullptr;
-    HIP_TRY(g.dev(0, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(lane_upload(g, 0, dr, rays, n * sizeof(CgrtRay)));
-    if (offsets) {
-        HIP_TRY(g.dev(1, (n + 1) * 8, &doff));
-        HIP_TRY(lane_upload(g, 1, doff, offsets, (n + 1) * 8));
-    }
-    if (used) HIP_TRY(g.dev(2, out_bytes, &dout));  // (a lane's buffer that was never needed is a null pointer)
-    if (want_counts || how == 2) HIP_TRY(g.dev(3, cnt_bytes, &dcnt));
-    CrossingArgs A{};
-    A.rays = static_cast<const float*>(dr);
-    A.n = n;
-    A.offsets = static_cast<const unsigned long long*>(doff);
-    A.k = k;
-    A.out = static_cast<CgrtCrossingDev*>(dout);  // no record to write (count entries, or every slot empty): the count search
-    A.capacity = used;
-    A.counts = static_cast<uint32_t*>(dcnt);
-    if (how == 2) {
-        HIP_TRY(hipMemsetAsync(g.L->d_counters, 0, 2 * sizeof(unsigned long long), g.L->stream));
-        HIP_TRY(launch_crossings(s->dev, A, brute, g.L->d_counters, g.L->stream));
-        unsigned long long h[2];
-        HIP_TRY(hipMemcpyAsync(h, g.L->d_counters, sizeof(h), hipMemcpyDeviceToHost, g.L->stream));
-        HIP_TRY(hipStreamSynchronize(g.L->stream));
-        work[0] = h[0];
-        work[1] = h[1];
-        return CGRT_OK;
-    }
-    HIP_TRY(launch_crossings(s->dev, A, brute, nullptr, g.L->stream));
-    if (used) HIP_TRY(lane_download(g, 2, out, dout, out_bytes, &staged_out));
-    if (want_counts) HIP_TRY(lane_download(g, 3, counts, dcnt, cnt_bytes, &staged_cnt));
-    HIP_TRY(hipStreamSynchronize(g.L->stream));
-    if (staged_out) std::memcpy(out, staged_out, out_bytes);
-    if (staged_cnt) std::memcpy(counts, staged_cnt, cnt_bytes);
-    return CGRT_OK;
-}
-int crossing_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const uint64_t* d_offsets, uint32_t k, CgrtCrossing* d_out, uint64_t capacity,
-                    uint32_t* d_counts, bool list, void* stream) {
-    int rc = crossing_args(s, d_rays, n, list ? static_cast<const void*>(d_out) : d_counts, list, d_offsets, k, capacity, d_counts, true);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
-    if (d_offsets && (rc = check_device_span(s, d_offsets, (n + 1) * 8, "d_offsets")) != CGRT_OK) return rc;
-    // with offsets any record below capacity may be written; with k the slots are the first n * k records
-    if (list && (rc = check_device_span(s, d_out, (d_offsets ? capacity : n * (uint64_t)k) * sizeof(CgrtCrossing), "d_out")) != CGRT_OK) return rc;
-    if (d_counts && (rc = check_device_span(s, d_counts, n * 4, "d_counts")) != CGRT_OK) return rc;
-    CrossingArgs A{};
-    A.rays = reinterpret_cast<const float*>(d_rays);
-    A.n = n;
-    A.offsets = reinterpret_cast<const unsigned long long*>(d_offsets);
-    A.k = k;
-    A.out = list ? reinterpret_cast<CgrtCrossingDev*>(d_out) : nullptr;
-    A.capacity = capacity;
-    A.counts = d_counts;
-    HIP_TRY(launch_crossings(s->dev, A, crossing_brute_scene(s), nullptr, static_cast<hipStream_t>(stream)));
-    return CGRT_OK;
-}
-}  // namespace
-
-int cgrt_count_crossings(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint32_t* counts) {
-    return crossing_host(s, rays, n, nullptr, 0, nullptr, 0, counts, false, 0, nullptr);
-}
-int cgrt_count_crossings_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, uint32_t* d_counts, void* stream) {
-    return crossing_device(s, d_rays, n, nullptr, 0, nullptr, 0, d_counts, false, stream);
-}
-int cgrt_list_crossings(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out, uint64_t capacity,
-                        uint32_t* counts) {
-    return crossing_host(s, rays, n, offsets, k, out, capacity, counts, true, 0, nullptr);
-}
-int cgrt_list_crossings_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const uint64_t* d_offsets, uint32_t k, CgrtCrossing* d_out,
-                               uint64_t capacity, uint32_t* d_counts, void* stream) {
-    return crossing_device(s, d_rays, n, d_offsets, k, d_out, capacity, d_counts, true, stream);
-}
-int cgrt_list_crossings_brute(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out,
-                              uint64_t capacity, uint32_t* counts) {
-    return crossing_host(s, rays, n, offsets, k, out, capacity, counts, true, 1, nullptr);
-}
-int cgrt_debug_crossing_work(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint64_t* out2) {
-    return crossing_host(s, rays, n, nullptr, 0, nullptr, 0, nullptr, false, 2, out2);
-}
-
 int cgrt_debug_export_frame(int device, const float* rgb, int W, int H, int format, uint64_t row_bytes, void* out) {
     if (!rgb || !out) return fail(CGRT_E_ARG, "NULL argument");
     if (W <= 0 || H <= 0) return fail(CGRT_E_ARG, "bad frame size");
@@ -4442,14 +3190,14 @@ int cgrt_trace_primary_multi(CgrtScene* const* scenes, int nscenes, const CgrtCa
     const CameraDev C = make_camera(*cam);
     struct Part {
         FrameDev F;
-        LaneGuard* g = nullptr;
+        LaneCall* c = nullptr;
         void *dh = nullptr, *dn = nullptr, *ph = nullptr, *pn = nullptr;
         size_t n = 0;
         hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
         ~Part() {
             for (hipEvent_t e : {e0, e1, e2})
                 if (e) (void)hipEventDestroy(e);
-            delete g;
+            delete c;
         }
     };
     std::vector<Part> part(nscenes);
@@ -4461,20 +3209,19 @@ int cgrt_trace_primary_multi(CgrtScene* const* scenes, int nscenes, const CgrtCa
         apply_frame_gate(scenes[i], C, P.F);
         P.n = (size_t)P.F.nblocks * (size_t)P.F.block;
         if (P.n == 0) continue;
-        HIP_TRY(hipSetDevice(scenes[i]->device));
-        P.g = new LaneGuard(scenes[i]);
-        int rc = P.g->acquire();
+        P.c = new LaneCall(scenes[i]);
+        int rc = P.c->begin();
         if (rc) return rc;
-        HIP_TRY(P.g->dev(1, P.n * sizeof(CgrtHit), &P.dh));
-        HIP_TRY(P.g->pin(1, P.n * sizeof(CgrtHit), &P.ph));
+        HIP_TRY(P.c->scratch(1, P.n * sizeof(CgrtHit), &P.dh));
+        HIP_TRY(P.c->g.pin(1, P.n * sizeof(CgrtHit), &P.ph));
         if (normals) {
-            HIP_TRY(P.g->dev(2, P.n * 12, &P.dn));
-            HIP_TRY(P.g->pin(2, P.n * 12, &P.pn));
+            HIP_TRY(P.c->scratch(2, P.n * 12, &P.dn));
+            HIP_TRY(P.c->g.pin(2, P.n * 12, &P.pn));
         }
         HIP_TRY(hipEventCreate(&P.e0));
         HIP_TRY(hipEventCreate(&P.e1));
         HIP_TRY(hipEventCreate(&P.e2));
-        hipStream_t st = P.g->L->stream;
+        hipStream_t st = P.c->stream();
         HIP_TRY(hipEventRecord(P.e0, st));
         HIP_TRY(launch_trace_primary(scenes[i]->dev, C, P.F, static_cast<CgrtHitDev*>(P.dh), static_cast<float*>(P.dn), nullptr, st));
         HIP_TRY(hipEventRecord(P.e1, st));
@@ -4488,7 +3235,7 @@ int cgrt_trace_primary_multi(CgrtScene* const* scenes, int nscenes, const CgrtCa
     auto finish = [&](int i) {
         Part& P = part[i];
         if (P.n == 0) return;
-        if (hipSetDevice(scenes[i]->device) != hipSuccess || hipStreamSynchronize(P.g->L->stream) != hipSuccess) {
+        if (hipSetDevice(scenes[i]->device) != hipSuccess || hipStreamSynchronize(P.c->stream()) != hipSuccess) {
             status[i] = CGRT_E_HIP;
             errs[i] = "waiting for a replica's stream failed";
             return;
@@ -4600,164 +3347,6 @@ int cgrt_render_multi_aa(CgrtScene* const* scenes, int nscenes, const CgrtCamera
     if (rc) return rc;
     for (int i = 0; i < nscenes; i++) NEED_DEVICE(scenes[i]);
     return render_replicas(scenes, nscenes, cam, W, H, lights, nlights, soft, max_level, rgb, stats, true);
-}
-
-// ------------------------------------------------------------------------------------------------
-// element-wise primitives
-#define PRIM_PROLOGUE(device)           \
-    int rc_ = select_device(device);    \
-    if (rc_) return rc_;                \
-    if (n == 0) return CGRT_OK;
-
-int cgrt_ray_triangle_batch(int device, const float* tri, const CgrtRay* rays, uint64_t n, float* t_out, uint8_t* hit, float* normals) {
-    if (n && (!tri || !rays || !t_out || !hit)) return fail(CGRT_E_ARG, "NULL argument");
-    PRIM_PROLOGUE(device)
-    DevBuf a, r, t, h, nn;
-    HIP_TRY(a.alloc(n * 72));
-    HIP_TRY(r.alloc(n * 28));
-    HIP_TRY(t.alloc(n * 4));
-    HIP_TRY(h.alloc(n));
-    HIP_TRY(hipMemcpy(a.p, tri, n * 72, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(r.p, rays, n * 28, hipMemcpyHostToDevice));
-    if (normals) {
-        HIP_TRY(nn.alloc(n * 12));
-        HIP_TRY(hipMemcpy(nn.p, normals, n * 12, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(launch_ray_triangle(a.as<float>(), r.as<float>(), n, t.as<float>(), h.as<uint8_t>(), normals ? nn.as<float>() : nullptr, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(t_out, t.p, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hit, h.p, n, hipMemcpyDeviceToHost));
-    if (normals) HIP_TRY(hipMemcpy(normals, nn.p, n * 12, hipMemcpyDeviceToHost));
-    return CGRT_OK;
-}
-
-int cgrt_ray_plane_batch(int device, const float* plane, const CgrtRay* rays, uint64_t n, float* t_out, uint8_t* hit) {
-    if (n && (!plane || !rays || !t_out || !hit)) return fail(CGRT_E_ARG, "NULL argument");
-    PRIM_PROLOGUE(device)
-    DevBuf a, r, t, h;
-    HIP_TRY(a.alloc(n * 16));
-    HIP_TRY(r.alloc(n * 28));
-    HIP_TRY(t.alloc(n * 4));
-    HIP_TRY(h.alloc(n));
-    HIP_TRY(hipMemcpy(a.p, plane, n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(r.p, rays, n * 28, hipMemcpyHostToDevice));
-    HIP_TRY(launch_ray_plane(a.as<float>(), r.as<float>(), n, t.as<float>(), h.as<uint8_t>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(t_out, t.p, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hit, h.p, n, hipMemcpyDeviceToHost));
-    return CGRT_OK;
-}
-
-int cgrt_ray_box_batch(int device, const float* box, const CgrtRay* rays, uint64_t n, float* t_out, uint8_t* hit, uint8_t* inside) {
-    if (n && (!box || !rays || !t_out || !hit)) return fail(CGRT_E_ARG, "NULL argument");
-    PRIM_PROLOGUE(device)
-    DevBuf a, r, t, h, in;
-    HIP_TRY(a.alloc(n * 24));
-    HIP_TRY(r.alloc(n * 28));
-    HIP_TRY(t.alloc(n * 4));
-    HIP_TRY(h.alloc(n));
-    HIP_TRY(in.alloc(n));
-    HIP_TRY(hipMemcpy(a.p, box, n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(r.p, rays, n * 28, hipMemcpyHostToDevice));
-    HIP_TRY(launch_ray_box(a.as<float>(), r.as<float>(), n, t.as<float>(), h.as<uint8_t>(), in.as<uint8_t>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(t_out, t.p, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hit, h.p, n, hipMemcpyDeviceToHost));
-    if (inside) HIP_TRY(hipMemcpy(inside, in.p, n, hipMemcpyDeviceToHost));
-    return CGRT_OK;
-}
-
-int cgrt_ray_sphere_batch(int device, const float* sphere, const CgrtRay* rays, uint64_t n, float* t_out, uint8_t* hit, float* normals) {
-    if (n && (!sphere || !rays || !t_out || !hit)) return fail(CGRT_E_ARG, "NULL argument");
-    PRIM_PROLOGUE(device)
-    DevBuf a, r, t, h, nn;
-    HIP_TRY(a.alloc(n * 16));
-    HIP_TRY(r.alloc(n * 28));
-    HIP_TRY(t.alloc(n * 4));
-    HIP_TRY(h.alloc(n));
-    HIP_TRY(hipMemcpy(a.p, sphere, n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(r.p, rays, n * 28, hipMemcpyHostToDevice));
-    if (normals) {
-        HIP_TRY(nn.alloc(n * 12));
-        HIP_TRY(hipMemcpy(nn.p, normals, n * 12, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(launch_ray_sphere(a.as<float>(), r.as<float>(), n, t.as<float>(), h.as<uint8_t>(), normals ? nn.as<float>() : nullptr, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(t_out, t.p, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hit, h.p, n, hipMemcpyDeviceToHost));
-    if (normals) HIP_TRY(hipMemcpy(normals, nn.p, n * 12, hipMemcpyDeviceToHost));
-    return CGRT_OK;
-}
-
-int cgrt_debug_gather_calibration(int device, uint64_t nrecords, int repeats) {
-    // nrecords x 64 B of zeros, each record read exactly once per launch in a scattered order (see k_gather_calib)
-    int n_ = 1;
-    (void)n_;
-    int rc_ = select_device(device);
-    if (rc_) return rc_;
-    if (nrecords < 1024 || repeats < 1) return fail(CGRT_E_ARG, "nrecords >= 1024, repeats >= 1");
-    DevBuf table, sink;
-    HIP_TRY(table.alloc((size_t)nrecords * 64));
-    HIP_TRY(sink.alloc(16));
-    HIP_TRY(hipMemset(table.p, 0, (size_t)nrecords * 64));
-    unsigned long long mult = 2654435761ull;
-    auto gcd = [](unsigned long long a, unsigned long long b) {
-        while (b) {
-            const unsigned long long t = a % b;
-            a = b;
-            b = t;
-        }
-        return a;
-    };
-    while (gcd(mult, nrecords) != 1) mult += 2;
-    for (int r = 0; r < repeats; r++) HIP_TRY(launch_gather_calib(table.p, nrecords, mult, 12345ull + 7919ull * r, sink.as<float>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    return CGRT_OK;
-}
-
-int cgrt_debug_fastdiv_check(int device, const float* a, const float* d, uint64_t n, uint64_t* mismatches, float* first_bad) {
-    if (n && (!a || !d || !mismatches || !first_bad)) return fail(CGRT_E_ARG, "NULL argument");
-    PRIM_PROLOGUE(device)
-    DevBuf da, dd, dm, db;
-    HIP_TRY(da.alloc(n * 4));
-    HIP_TRY(dd.alloc(n * 4));
-    HIP_TRY(dm.alloc(8));
-    HIP_TRY(db.alloc(16));
-    HIP_TRY(hipMemcpy(da.p, a, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dd.p, d, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(dm.p, 0, 8));
-    HIP_TRY(hipMemset(db.p, 0, 16));
-    HIP_TRY(launch_fastdiv_check(da.as<float>(), dd.as<float>(), n, dm.as<unsigned long long>(), db.as<float>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(mismatches, dm.p, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(first_bad, db.p, 16, hipMemcpyDeviceToHost));
-    return CGRT_OK;
-}
-
-int cgrt_triangle_plane_batch(int device, const float* tri, uint64_t n, float* plane) {
-    if (n && (!tri || !plane)) return fail(CGRT_E_ARG, "NULL argument");
-    PRIM_PROLOGUE(device)
-    DevBuf a, p;
-    HIP_TRY(a.alloc(n * 36));
-    HIP_TRY(p.alloc(n * 16));
-    HIP_TRY(hipMemcpy(a.p, tri, n * 36, hipMemcpyHostToDevice));
-    HIP_TRY(launch_triangle_plane(a.as<float>(), n, p.as<float>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(plane, p.p, n * 16, hipMemcpyDeviceToHost));
-    return CGRT_OK;
-}
-
-int cgrt_point_in_triangle_batch(int device, const float* in, uint64_t n, uint8_t* out) {
-    if (n && (!in || !out)) return fail(CGRT_E_ARG, "NULL argument");
-    PRIM_PROLOGUE(device)
-    DevBuf a, o;
-    HIP_TRY(a.alloc(n * 60));
-    HIP_TRY(o.alloc(n));
-    HIP_TRY(hipMemcpy(a.p, in, n * 60, hipMemcpyHostToDevice));
-    HIP_TRY(launch_point_in_triangle(a.as<float>(), n, o.as<uint8_t>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, o.p, n, hipMemcpyDeviceToHost));
-    return CGRT_OK;
 }
 
 }  // extern "C"

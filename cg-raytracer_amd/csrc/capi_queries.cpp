@@ -1,0 +1,611 @@
+// capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
+// closest points, crossings.  None of them touches the scene's frame state (workspace, prediction, hints).
+#include "capi_internal.h"
+
+extern "C" {
+
+// ---- visibility queries (include/cgrt.h cgrt_occluded*, cgrt_in_shadow*, cgrt_soft_lit*): the reference's intersect() bool, pointInShadow
+// and shading's soft-shadow counts for the caller's rays / points.  Arguments are checked in the order include/cgrt.h states, all before any
+// device work; then a host-only scene is CGRT_E_NO_DEVICE.  None of them touches the scene's frame prediction or frame hints.
+namespace {
+const uint64_t kMaxAnswers = 0x7fffffffull;
+// NULL pointers (the rays / points and the output with n > 0, lights missing), then n and n x per_point above 0x7fffffff
+int query_args(const CgrtScene* s, const void* in, uint64_t n, const void* out, uint64_t per_point, bool lights_missing) {
+    if (!s || (n && (!in || !out)) || lights_missing) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > kMaxAnswers || (per_point && n > kMaxAnswers / per_point)) return fail(CGRT_E_ARG, "too many answers: n (x lights) exceeds 0x7fffffff");
+    return CGRT_OK;
+}
+// n points x nlights lights on the lane's stream (lights through the lane's slot 3)
+int in_shadow_on_lane(LaneCall& c, CgrtScene* s, const float* d_points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* d_out) {
+    void* dl = nullptr;
+    HIP_TRY(c.input(3, lights, (size_t)nlights * 24, &dl));
+    HIP_TRY(launch_in_shadow(s->dev, d_points, n, static_cast<const float*>(dl), nlights, d_out, c.stream()));
+    return CGRT_OK;
+}
+// the soft-shadow counts of n points on the lane's stream (spherical lights through slot 3, the unit vectors through slot 2); d_lit zeroed here
+int soft_lit_on_lane(LaneCall& c, CgrtScene* s, const float* d_points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* d_lit) {
+    const uint64_t SL = soft->nspherical;
+    void *dl = nullptr, *du = nullptr;
+    HIP_TRY(c.input(3, soft->spherical, SL * 28, &dl));
+    HIP_TRY(c.input(2, soft->unit_vectors, (size_t)soft->nunits * 12, &du));
+    HIP_TRY(hipMemsetAsync(d_lit, 0, n * SL * sizeof(uint32_t), c.stream()));
+    // (level stays 0, cgrt_shade_rays' convention: pixel = i, level 0)
+    const SoftDev Q = soft_dev(*soft, (unsigned)SL, static_cast<const float*>(dl), static_cast<const float*>(du));
+    HIP_TRY(launch_soft_points(s->dev, Q, d_points, n, d_lit, soft->closest_hit ? 0 : 1, c.stream()));
+    return CGRT_OK;
+}
+}  // namespace
+
+int cgrt_occluded_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, uint8_t* d_hit, void* stream) {
+    int rc = query_args(s, d_rays, n, d_hit, 0, false);
+    if (rc) return rc;
+    if ((uintptr_t)d_rays % 4) return fail(CGRT_E_ARG, "d_rays must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_hit, n, "d_hit")) != CGRT_OK) return rc;
+    HIP_TRY(launch_occluded(s->dev, reinterpret_cast<const float*>(d_rays), n, d_hit, static_cast<hipStream_t>(stream)));
+    return CGRT_OK;
+}
+int cgrt_occluded(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint8_t* hit) {
+    int rc = query_args(s, rays, n, hit, 0, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    void *dr = nullptr, *dh = nullptr;
+    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(c.scratch(1, n, &dh));
+    HIP_TRY(launch_occluded(s->dev, static_cast<const float*>(dr), n, static_cast<uint8_t*>(dh), c.stream()));
+    HIP_TRY(c.output(1, hit, dh, n));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+
+int cgrt_in_shadow_device(CgrtScene* s, const float* d_points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* d_out, void* stream) {
+    int rc = query_args(s, d_points, n, d_out, nlights, nlights && !lights);
+    if (rc) return rc;
+    if ((uintptr_t)d_points % 4) return fail(CGRT_E_ARG, "d_points must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0 || nlights == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_out, n * nlights, "d_out")) != CGRT_OK) return rc;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    HIP_TRY(lane_follow(c.g, static_cast<hipStream_t>(stream)));
+    if ((rc = in_shadow_on_lane(c, s, d_points, n, lights, nlights, d_out)) != CGRT_OK) return rc;
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+int cgrt_in_shadow(CgrtScene* s, const float* points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* out) {
+    int rc = query_args(s, points, n, out, nlights, nlights && !lights);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0 || nlights == 0) return CGRT_OK;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    const uint64_t m = n * nlights;
+    void *dp = nullptr, *dout = nullptr;
+    HIP_TRY(c.input(0, points, n * 12, &dp));
+    HIP_TRY(c.scratch(1, m, &dout));
+    if ((rc = in_shadow_on_lane(c, s, static_cast<const float*>(dp), n, lights, nlights, static_cast<uint8_t*>(dout))) != CGRT_OK) return rc;
+    HIP_TRY(c.output(1, out, dout, m));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+
+int cgrt_soft_lit_device(CgrtScene* s, const float* d_points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* d_lit, void* stream) {
+    const uint32_t SL = soft ? soft->nspherical : 0u;
+    int rc = query_args(s, d_points, n, d_lit, SL, false);
+    if (rc) return rc;
+    if ((rc = soft_rules(soft)) != CGRT_OK) return rc;
+    if ((uintptr_t)d_points % 4 || (uintptr_t)d_lit % 4) return fail(CGRT_E_ARG, "d_points and d_lit must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0 || SL == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_lit, n * SL * 4, "d_lit")) != CGRT_OK) return rc;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    HIP_TRY(lane_follow(c.g, static_cast<hipStream_t>(stream)));
+    if ((rc = soft_lit_on_lane(c, s, d_points, n, soft, d_lit)) != CGRT_OK) return rc;
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+int cgrt_soft_lit(CgrtScene* s, const float* points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* lit) {
+    const uint32_t SL = soft ? soft->nspherical : 0u;
+    int rc = query_args(s, points, n, lit, SL, false);
+    if (rc) return rc;
+    if ((rc = soft_rules(soft)) != CGRT_OK) return rc;
+    NEED_DEVICE(s);
+    if (n == 0 || SL == 0) return CGRT_OK;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    const uint64_t m = n * SL * sizeof(uint32_t);
+    void *dp = nullptr, *dl = nullptr;
+    HIP_TRY(c.input(0, points, n * 12, &dp));
+    HIP_TRY(c.scratch(1, m, &dl));
+    if ((rc = soft_lit_on_lane(c, s, static_cast<const float*>(dp), n, soft, static_cast<uint32_t*>(dl))) != CGRT_OK) return rc;
+    HIP_TRY(c.output(1, lit, dl, m));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+
+// ---- surface attributes (include/cgrt.h cgrt_hit_barycentrics*, cgrt_interpolate_hits*, cgrt_surface_*_device):
+// where inside its triangle a hit lies, and a caller's per-vertex table carried there.  Nothing is traced and no scene state is read or
+// written except the lookup table below; the checks come in the order include/cgrt.h states, all before any device work.
+namespace {
+const uint64_t kSurfaceMaxBytes = 1ull << 40;  // an output's size: items x channels x 4 bytes (the kernel indexes with 64 bits; a documented bound)
+int surface_channels(uint32_t channels, uint64_t items) {
+    if (channels < 1 || channels > 256) return fail(CGRT_E_ARG, "channels must be in 1..256");
+    if (items * channels * 4ull > kSurfaceMaxBytes) return fail(CGRT_E_ARG, "output too large: items x channels x 4 exceeds 2^40 bytes");
+    return CGRT_OK;
+}
+// prim_id -> {record, three vertex rows}, made once per scene by its first surface call (later calls: one atomic load)
+int surface_lookup(CgrtScene* s, const SurfaceLookup** out) {
+    void* p = s->d_surface_lookup.load(std::memory_order_acquire);
+    if (!p) {
+        std::lock_guard<std::mutex> lk(s->surface_mutex);
+        p = s->d_surface_lookup.load(std::memory_order_acquire);
+        if (!p) {
+            std::vector<SurfaceLookup> T;
+            try {
+                T.resize(s->ntris);
+            } catch (const std::bad_alloc&) {
+                return fail(CGRT_E_ALLOC, "host allocation failed");
+            }
+            const std::vector<TriRecord>& R = s->bvh.tris;
+            if (R.size() != s->ntris || s->tri_index.size() != 3 * (size_t)s->ntris) return fail(CGRT_E_ARG, "the scene's records do not cover its triangles");
+            for (size_t k = 0; k < R.size(); k++) {
+                const uint32_t prim = R[k].prim_id;
+                if (prim >= s->ntris) return fail(CGRT_E_ARG, "a triangle record carries a primitive id out of range");
+                T[prim].record = s->bvh.tri_base + (uint32_t)k;
+                for (int c = 0; c < 3; c++) T[prim].v[c] = s->tri_index[3 * (size_t)prim + c];
+            }
+            const size_t bytes = T.size() * sizeof(SurfaceLookup);
+            void* d = nullptr;
+            HIP_TRY(hipMalloc(&d, bytes ? bytes : 16));
+            if (bytes) {
+                const hipError_t e = staged_h2d(d, T.data(), bytes);  // (complete when it returns: every later launch sees the table)
+                if (e != hipSuccess) {
+                    (void)hipFree(d);
+                    return hip_fail(e, "uploading the surface lookup table");
+                }
+            }
+            s->device_bytes += bytes;
+            s->d_surface_lookup.store(d, std::memory_order_release);
+            p = d;
+        }
+    }
+    *out = static_cast<const SurfaceLookup*>(p);
+    return CGRT_OK;
+}
+SurfaceDev surface_dev(const CgrtScene* s, const SurfaceLookup* lookup, uint64_t n, const float* d_attr, uint32_t channels, float* d_bary,
+                       float* d_out, int chw) {
+    SurfaceDev A{};
+    A.tris = s->dev.tris;
+    A.lookup = lookup;
+    A.ntris = s->dev.ntris;
+    A.n = (uint32_t)n;
+    A.attr = d_out ? d_attr : nullptr;
+    A.channels = d_out ? channels : 0;
+    A.bary = d_bary;
+    A.out = d_out;
+    A.chw = chw ? 1 : 0;
+    A.vec4 = d_out && channels % 4 == 0 && (uintptr_t)d_attr % 16 == 0 && (uintptr_t)d_out % 16 == 0;
+    return A;
+}
+// the list forms' checks up to the host-only scene (attr: the call interpolates; device: the pointers' alignment is checked too)
+int surface_list_args(const CgrtScene* s, const void* rays, const void* hits, uint64_t n, bool attr, const void* table, uint32_t channels,
+                      const void* out, bool device) {
+    if (!s || (n && (!rays || !hits || !out || (attr && !table)))) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many hits: n exceeds 0x7fffffff");
+    if (attr) {
+        const int rc = surface_channels(channels, n);
+        if (rc) return rc;
+    }
+    if (device && ((uintptr_t)rays % 4 || (uintptr_t)hits % 4 || (uintptr_t)table % 4 || (uintptr_t)out % 4))
+        return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    return CGRT_OK;
+}
+// d_bary or d_out (with d_attr, channels) of n hits on `st`; every pointer device memory
+int surface_list_launch(CgrtScene* s, const void* d_rays, const void* d_hits, uint64_t n, const float* d_attr, uint32_t channels, float* d_bary,
+                        float* d_out, hipStream_t st) {
+    const SurfaceLookup* lookup = nullptr;
+    const int rc = surface_lookup(s, &lookup);
+    if (rc) return rc;
+    SurfaceDev A = surface_dev(s, lookup, n, d_attr, channels, d_bary, d_out, 0);
+    A.rays = static_cast<const float*>(d_rays);
+    A.hits = static_cast<const CgrtHitDev*>(d_hits);
+    HIP_TRY(launch_surface(A, SURFACE_LIST, st));
+    return CGRT_OK;
+}
+int surface_list_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, bool attr, const float* d_attr, uint32_t channels,
+                        float* d_res, void* stream) {
+    int rc = surface_list_args(s, d_rays, d_hits, n, attr, d_attr, channels, d_res, true);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_hits, n * sizeof(CgrtHit), "d_hits")) != CGRT_OK) return rc;
+    if (attr && (rc = check_device_span(s, d_attr, (uint64_t)s->nverts * channels * 4ull, "d_attr")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_res, n * (attr ? channels : 3u) * 4ull, attr ? "d_out" : "d_bary")) != CGRT_OK) return rc;
+    return surface_list_launch(s, d_rays, d_hits, n, d_attr, channels, attr ? nullptr : d_res, attr ? d_res : nullptr, static_cast<hipStream_t>(stream));
+}
+// host pointers, on a call lane (slots: 0 rays, 1 hits, 2 the result, 3 the attribute table)
+int surface_list_host(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, bool attr, const float* table, uint32_t channels, float* res) {
+    int rc = surface_list_args(s, rays, hits, n, attr, table, channels, res, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    const size_t res_bytes = (size_t)n * (attr ? channels : 3u) * 4u, table_bytes = attr ? (size_t)s->nverts * channels * 4u : 0;
+    void *dr = nullptr, *dh = nullptr, *dres = nullptr, *dt = nullptr;
+    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(c.input(1, hits, n * sizeof(CgrtHit), &dh));
+    HIP_TRY(c.scratch(2, res_bytes, &dres));
+    if (attr) HIP_TRY(c.input(3, table, table_bytes, &dt));
+    if ((rc = surface_list_launch(s, dr, dh, n, static_cast<const float*>(dt), channels, attr ? nullptr : static_cast<float*>(dres),
+                                  attr ? static_cast<float*>(dres) : nullptr, c.stream())) != CGRT_OK)
+        return rc;
+    HIP_TRY(c.output(2, res, dres, res_bytes));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+// cgrt_surface_views_device and its ray-camera twin (exactly one of cams, raycams)
+int surface_frames_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H, const float* d_depth,
+                          const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
+    if (!s || !d_depth || !d_prim_id || (!d_bary && !d_out) || (d_out && !d_attr)) return fail(CGRT_E_ARG, "NULL argument");
+    int rc = views_args(raycams ? static_cast<const void*>(raycams) : cams, nviews, W, H, raycams);
+    if (rc) return rc;
+    const uint64_t npix = (uint64_t)nviews * (uint64_t)W * (uint64_t)H;
+    if (d_out && (rc = surface_channels(channels, npix)) != CGRT_OK) return rc;
+    if ((uintptr_t)d_depth % 4 || (uintptr_t)d_prim_id % 4 || (uintptr_t)d_attr % 4 || (uintptr_t)d_bary % 4 || (uintptr_t)d_out % 4)
+        return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_depth, npix * 4, "d_depth")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_prim_id, npix * 4, "d_prim_id")) != CGRT_OK) return rc;
+    if (d_out && (rc = check_device_span(s, d_attr, (uint64_t)s->nverts * channels * 4ull, "d_attr")) != CGRT_OK) return rc;
+    if (d_bary && (rc = check_device_span(s, d_bary, npix * 12, "d_bary")) != CGRT_OK) return rc;
+    if (d_out && (rc = check_device_span(s, d_out, npix * channels * 4ull, "d_out")) != CGRT_OK) return rc;
+    const SurfaceLookup* lookup = nullptr;
+    if ((rc = surface_lookup(s, &lookup)) != CGRT_OK) return rc;
+    SurfaceDev A = surface_dev(s, lookup, npix, d_attr, channels, d_bary, d_out, chw);
+    A.depth = d_depth;
+    A.prim = d_prim_id;
+    A.W = W;
+    A.H = H;
+    A.plane = (uint32_t)((uint64_t)W * (uint64_t)H);
+    hipStream_t const st = static_cast<hipStream_t>(stream);
+    return launch_with_view_table(s, view_table(cams, raycams, nviews), st, [&](const void* d_table) {
+        A.cams = d_table;
+        return launch_surface(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, st);
+    });
+}
+
+// ---- the adjoint with respect to the table (include/cgrt.h cgrt_interpolate_hits_grad*, cgrt_surface_*_grad_device; DESIGN.md section
+// 5.23): twins of the entries above, grad_out in the place of out and grad_attr in the place of attr, the same checks in the same order.
+SurfaceGradDev surface_grad_dev(const CgrtScene* s, const SurfaceLookup* lookup, uint64_t n, const float* d_grad_out, uint32_t channels,
+                                float* d_grad_attr, int chw) {
+    SurfaceGradDev A{};
+    A.tris = s->dev.tris;
+    A.lookup = lookup;
+    A.ntris = s->dev.ntris;
+    A.n = (uint32_t)n;
+    A.grad_out = d_grad_out;
+    A.channels = channels;
+    A.grad_attr = d_grad_attr;
+    A.chw = chw ? 1 : 0;
+    surface_grad_policy(channels, A.chw, &A.by_item, &A.combine);
+    return A;
+}
+int surface_list_grad_launch(CgrtScene* s, const void* d_rays, const void* d_hits, uint64_t n, const float* d_grad_out, uint32_t channels,
+                             float* d_grad_attr, hipStream_t st) {
+    const SurfaceLookup* lookup = nullptr;
+    const int rc = surface_lookup(s, &lookup);
+    if (rc) return rc;
+    SurfaceGradDev A = surface_grad_dev(s, lookup, n, d_grad_out, channels, d_grad_attr, 0);
+    A.rays = static_cast<const float*>(d_rays);
+    A.hits = static_cast<const CgrtHitDev*>(d_hits);
+    HIP_TRY(launch_surface_grad(A, SURFACE_LIST, st));
+    return CGRT_OK;
+}
+int surface_list_grad_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out, uint32_t channels,
+                             float* d_grad_attr, void* stream) {
+    int rc = surface_list_args(s, d_rays, d_hits, n, true, d_grad_attr, channels, d_grad_out, true);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_hits, n * sizeof(CgrtHit), "d_hits")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_grad_out, n * channels * 4ull, "d_grad_out")) != CGRT_OK) return rc;
+    return surface_list_grad_launch(s, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, static_cast<hipStream_t>(stream));
+}
+// host pointers, on a call lane (slots: 0 rays, 1 hits, 2 grad_out, 3 grad_attr: uploaded, accumulated into, downloaded)
+int surface_list_grad_host(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
+                           float* grad_attr) {
+    int rc = surface_list_args(s, rays, hits, n, true, grad_attr, channels, grad_out, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    const size_t go_bytes = (size_t)n * channels * 4u, table_bytes = (size_t)s->nverts * channels * 4u;
+    void *dr = nullptr, *dh = nullptr, *dgo = nullptr, *dt = nullptr;
+    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
+    HIP_TRY(c.input(1, hits, n * sizeof(CgrtHit), &dh));
+    HIP_TRY(c.input(2, grad_out, go_bytes, &dgo));
+    HIP_TRY(c.input(3, grad_attr, table_bytes, &dt));
+    if ((rc = surface_list_grad_launch(s, dr, dh, n, static_cast<const float*>(dgo), channels, static_cast<float*>(dt), c.stream())) != CGRT_OK)
+        return rc;
+    HIP_TRY(c.output(3, grad_attr, dt, table_bytes));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+// cgrt_surface_views_grad_device and its ray-camera twin (exactly one of cams, raycams)
+int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H,
+                               const float* d_depth, const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw,
+                               float* d_grad_attr, void* stream) {
+    if (!s || !d_depth || !d_prim_id || !d_grad_out || !d_grad_attr) return fail(CGRT_E_ARG, "NULL argument");
+    int rc = views_args(raycams ? static_cast<const void*>(raycams) : cams, nviews, W, H, raycams);
+    if (rc) return rc;
+    const uint64_t npix = (uint64_t)nviews * (uint64_t)W * (uint64_t)H;
+    if ((rc = surface_channels(channels, npix)) != CGRT_OK) return rc;
+    if ((uintptr_t)d_depth % 4 || (uintptr_t)d_prim_id % 4 || (uintptr_t)d_grad_attr % 4 || (uintptr_t)d_grad_out % 4)
+        return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_depth, npix * 4, "d_depth")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_prim_id, npix * 4, "d_prim_id")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_grad_out, npix * channels * 4ull, "d_grad_out")) != CGRT_OK) return rc;
+    const SurfaceLookup* lookup = nullptr;
+    if ((rc = surface_lookup(s, &lookup)) != CGRT_OK) return rc;
+    SurfaceGradDev A = surface_grad_dev(s, lookup, npix, d_grad_out, channels, d_grad_attr, chw);
+    A.depth = d_depth;
+    A.prim = d_prim_id;
+    A.W = W;
+    A.H = H;
+    A.plane = (uint32_t)((uint64_t)W * (uint64_t)H);
+    hipStream_t const st = static_cast<hipStream_t>(stream);
+    return launch_with_view_table(s, view_table(cams, raycams, nviews), st, [&](const void* d_table) {
+        A.cams = d_table;
+        return launch_surface_grad(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, st);
+    });
+}
+}  // namespace
+
+int cgrt_interpolate_hits_grad(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
+                               float* grad_attr) {
+    return surface_list_grad_host(s, rays, hits, n, grad_out, channels, grad_attr);
+}
+int cgrt_interpolate_hits_grad_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out,
+                                      uint32_t channels, float* d_grad_attr, void* stream) {
+    return surface_list_grad_device(s, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, stream);
+}
+int cgrt_surface_views_grad_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                   const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
+                                   void* stream) {
+    return surface_frames_grad_device(s, cams, nullptr, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, stream);
+}
+int cgrt_surface_raycams_grad_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                     const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
+                                     void* stream) {
+    return surface_frames_grad_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, stream);
+}
+
+int cgrt_hit_barycentrics(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, float* bary) {
+    return surface_list_host(s, rays, hits, n, false, nullptr, 0, bary);
+}
+int cgrt_hit_barycentrics_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, float* d_bary, void* stream) {
+    return surface_list_device(s, d_rays, d_hits, n, false, nullptr, 0, d_bary, stream);
+}
+int cgrt_interpolate_hits(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* attr, uint32_t channels, float* out) {
+    return surface_list_host(s, rays, hits, n, true, attr, channels, out);
+}
+int cgrt_interpolate_hits_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_attr, uint32_t channels,
+                                 float* d_out, void* stream) {
+    return surface_list_device(s, d_rays, d_hits, n, true, d_attr, channels, d_out, stream);
+}
+int cgrt_surface_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth, const uint32_t* d_prim_id,
+                              const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
+    return surface_frames_device(s, cams, nullptr, nviews, W, H, d_depth, d_prim_id, d_attr, channels, d_bary, d_out, chw, stream);
+}
+int cgrt_surface_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                const uint32_t* d_prim_id, const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
+    return surface_frames_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_attr, channels, d_bary, d_out, chw, stream);
+}
+
+// ---- closest-point queries (include/cgrt.h cgrt_closest_points*): the nearest surface point of every query point.
+// Nothing is traced and no scene state is read or written; the checks come in the order include/cgrt.h states, all before any device work.
+namespace {
+static_assert(sizeof(CgrtClosest) == sizeof(CgrtClosestDev), "CgrtClosest is what the kernels write");
+int closest_args(const CgrtScene* s, const void* points, uint64_t n, float max_dist2, const void* out, bool device) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    if (n && (!points || !out)) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many queries: n exceeds 0x7fffffff");
+    if (!(max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)out % 4)) return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    return CGRT_OK;
+}
+// host pointers, on a call lane (slots: 0 the points, 1 the records); how: 0 tree search, 1 brute force, 2 counted tree search
+int closest_host(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out, int how, uint64_t* work) {
+    int rc = closest_args(s, points, n, max_dist2, how == 2 ? static_cast<const void*>(work) : out, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    const size_t out_bytes = (size_t)n * sizeof(CgrtClosest);
+    void *dp = nullptr, *dout = nullptr;
+    HIP_TRY(c.input(0, points, n * 12, &dp));
+    HIP_TRY(c.scratch(1, out_bytes, &dout));
+    if (how == 2) {
+        HIP_TRY(c.zero_counters(2));
+        HIP_TRY(launch_closest(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), c.counters(), c.stream()));
+        HIP_TRY(c.read_counters(work, 2));
+        return CGRT_OK;
+    }
+    if (how == 1)
+        HIP_TRY(launch_closest_brute(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), c.stream()));
+    else
+        HIP_TRY(launch_closest(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), nullptr, c.stream()));
+    HIP_TRY(c.output(1, out, dout, out_bytes));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+}  // namespace
+
+int cgrt_closest_points(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out) {
+    return closest_host(s, points, n, max_dist2, out, 0, nullptr);
+}
+int cgrt_closest_points_brute(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out) {
+    return closest_host(s, points, n, max_dist2, out, 1, nullptr);
+}
+int cgrt_debug_closest_work(CgrtScene* s, const float* points, uint64_t n, float max_dist2, uint64_t* out2) {
+    return closest_host(s, points, n, max_dist2, nullptr, 2, out2);
+}
+int cgrt_closest_points_device(CgrtScene* s, const float* d_points, uint64_t n, float max_dist2, CgrtClosest* d_out, void* stream) {
+    int rc = closest_args(s, d_points, n, max_dist2, d_out, true);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
+    if ((rc = check_device_span(s, d_out, n * sizeof(CgrtClosest), "d_out")) != CGRT_OK) return rc;
+    HIP_TRY(launch_closest(s->dev, d_points, n, max_dist2, reinterpret_cast<CgrtClosestDev*>(d_out), nullptr, static_cast<hipStream_t>(stream)));
+    return CGRT_OK;
+}
+
+// ---- crossing queries (include/cgrt.h cgrt_count_crossings*, cgrt_list_crossings*): every triangle a ray passes
+// through, counted or listed in (t, prim_id) order.  No scene state is read or written; the checks come in the order include/cgrt.h
+// states, all before any device work.
+namespace {
+static_assert(sizeof(CgrtCrossing) == sizeof(CgrtCrossingDev), "CgrtCrossing is what the kernels write");
+const uint64_t kCrossingMaxCapacity = 1ull << 37;
+// where the conservative box test's argument does not hold the whole call tests every triangle: a wild triangle is accepted by every ray
+// wherever its boxes are, and a non-finite vertex leaves its boxes meaningless
+bool crossing_brute_scene(const CgrtScene* s) {
+    if (!s->bvh.geometry_finite) return true;
+    for (uint8_t w : s->bvh.leaf_wild)
+        if (w) return true;
+    return false;
+}
+// result: counts for the count entries, out2 for the work entry, out for the list entries; list: the slot arguments are checked
+int crossing_args(const CgrtScene* s, const void* rays, uint64_t n, const void* result, bool list, const uint64_t* offsets, uint32_t k,
+                  uint64_t capacity, const void* counts, bool device) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    if (n && (!rays || !result)) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many rays: n exceeds 0x7fffffff");
+    if (list) {
+        if ((offsets != nullptr) == (k > 0)) return fail(CGRT_E_ARG, "exactly one of offsets and k > 0 must be given");
+        if (capacity > kCrossingMaxCapacity) return fail(CGRT_E_ARG, "capacity exceeds 2^37 records");
+        if (k && n * (uint64_t)k > capacity) return fail(CGRT_E_ARG, "n * k records exceed capacity");
+        if (!device && offsets && n) {
+            if (offsets[0] != 0) return fail(CGRT_E_ARG, "offsets must start at 0");
+            for (uint64_t i = 0; i < n; i++)
+                if (offsets[i + 1] < offsets[i]) return fail(CGRT_E_ARG, "offsets must not decrease");
+            if (offsets[n] > capacity) return fail(CGRT_E_ARG, "offsets end beyond capacity");
+        }
+    }
+    if (device && ((uintptr_t)rays % 4 || (uintptr_t)result % 4 || (uintptr_t)counts % 4 || (uintptr_t)offsets % 8))
+        return fail(CGRT_E_ARG, "device pointers must be aligned to their elements");
+    return CGRT_OK;
+}
+// host pointers, on a call lane (slots: 0 the rays, 1 the offsets, 2 the records, 3 the counts); how: 0 tree search, 1 brute force,
+// 2 counted tree search (count mode)
+int crossing_host(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out, uint64_t capacity,
+                  uint32_t* counts, bool list, int how, uint64_t* work) {
+    int rc = crossing_args(s, rays, n, how == 2 ? static_cast<const void*>(work) : (list ? static_cast<const void*>(out) : counts), list, offsets,
+                           k, capacity, counts, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    const uint64_t used = list ? (offsets ? offsets[n] : n * (uint64_t)k) : 0;  // the slots are records [0, used)
+    const bool want_counts = !list || counts != nullptr;
+    if (how != 2 && used == 0 && !want_counts) return CGRT_OK;  // every slot is empty and no count is asked for: nothing to write
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    const bool brute = how == 1 || crossing_brute_scene(s);
+    const size_t out_bytes = (size_t)used * sizeof(CgrtCrossing), cnt_bytes = (size_t)n * 4u;
+    void *dr = nullptr, *doff = nullptr, *dout = nullptr, *dcnt = nullptr;
+    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
+    if (offsets) HIP_TRY(c.input(1, offsets, (n + 1) * 8, &doff));
+    if (used) HIP_TRY(c.scratch(2, out_bytes, &dout));  // (a lane's buffer that was never needed is a null pointer)
+    if (want_counts || how == 2) HIP_TRY(c.scratch(3, cnt_bytes, &dcnt));
+    CrossingArgs A{};
+    A.rays = static_cast<const float*>(dr);
+    A.n = n;
+    A.offsets = static_cast<const unsigned long long*>(doff);
+    A.k = k;
+    A.out = static_cast<CgrtCrossingDev*>(dout);  // no record to write (count entries, or every slot empty): the count search
+    A.capacity = used;
+    A.counts = static_cast<uint32_t*>(dcnt);
+    if (how == 2) {
+        HIP_TRY(c.zero_counters(2));
+        HIP_TRY(launch_crossings(s->dev, A, brute, c.counters(), c.stream()));
+        HIP_TRY(c.read_counters(work, 2));
+        return CGRT_OK;
+    }
+    HIP_TRY(launch_crossings(s->dev, A, brute, nullptr, c.stream()));
+    if (used) HIP_TRY(c.output(2, out, dout, out_bytes));
+    if (want_counts) HIP_TRY(c.output(3, counts, dcnt, cnt_bytes));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+int crossing_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const uint64_t* d_offsets, uint32_t k, CgrtCrossing* d_out, uint64_t capacity,
+                    uint32_t* d_counts, bool list, void* stream) {
+    int rc = crossing_args(s, d_rays, n, list ? static_cast<const void*>(d_out) : d_counts, list, d_offsets, k, capacity, d_counts, true);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
+    if (d_offsets && (rc = check_device_span(s, d_offsets, (n + 1) * 8, "d_offsets")) != CGRT_OK) return rc;
+    // with offsets any record below capacity may be written; with k the slots are the first n * k records
+    if (list && (rc = check_device_span(s, d_out, (d_offsets ? capacity : n * (uint64_t)k) * sizeof(CgrtCrossing), "d_out")) != CGRT_OK) return rc;
+    if (d_counts && (rc = check_device_span(s, d_counts, n * 4, "d_counts")) != CGRT_OK) return rc;
+    CrossingArgs A{};
+    A.rays = reinterpret_cast<const float*>(d_rays);
+    A.n = n;
+    A.offsets = reinterpret_cast<const unsigned long long*>(d_offsets);
+    A.k = k;
+    A.out = list ? reinterpret_cast<CgrtCrossingDev*>(d_out) : nullptr;
+    A.capacity = capacity;
+    A.counts = d_counts;
+    HIP_TRY(launch_crossings(s->dev, A, crossing_brute_scene(s), nullptr, static_cast<hipStream_t>(stream)));
+    return CGRT_OK;
+}
+}  // namespace
+
+int cgrt_count_crossings(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint32_t* counts) {
+    return crossing_host(s, rays, n, nullptr, 0, nullptr, 0, counts, false, 0, nullptr);
+}
+int cgrt_count_crossings_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, uint32_t* d_counts, void* stream) {
+    return crossing_device(s, d_rays, n, nullptr, 0, nullptr, 0, d_counts, false, stream);
+}
+int cgrt_list_crossings(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out, uint64_t capacity,
+                        uint32_t* counts) {
+    return crossing_host(s, rays, n, offsets, k, out, capacity, counts, true, 0, nullptr);
+}
+int cgrt_list_crossings_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const uint64_t* d_offsets, uint32_t k, CgrtCrossing* d_out,
+                               uint64_t capacity, uint32_t* d_counts, void* stream) {
+    return crossing_device(s, d_rays, n, d_offsets, k, d_out, capacity, d_counts, true, stream);
+}
+int cgrt_list_crossings_brute(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out,
+                              uint64_t capacity, uint32_t* counts) {
+    return crossing_host(s, rays, n, offsets, k, out, capacity, counts, true, 1, nullptr);
+}
+int cgrt_debug_crossing_work(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint64_t* out2) {
+    return crossing_host(s, rays, n, nullptr, 0, nullptr, 0, nullptr, false, 2, out2);
+}
+
+}  // extern "C"

@@ -272,7 +272,7 @@ def test_per_ray_driver_matches_oracle(pkg, orc, scene_data, name, W, H, level, 
 
 @pytest.mark.gpu
 def test_large_host_lists_go_through_the_bounce_buffers_unchanged(pkg, orc):
-    """Transfers above 1 MB take another road than small ones (capi.cpp lane_upload / lane_download: two alternating pinned 8 MB
+    """Transfers above 1 MB take another road than small ones (capi_lanes.cpp lane_upload / lane_download: two alternating pinned 8 MB
     buffers, pieces copied on several threads, and of a long list only the normals of rays that hit are copied back): a list of
     700 K rays -- several pieces per buffer, a ragged last piece -- must come back exactly as its 20 K-ray slices do, HitInfo of a
     miss untouched (the caller's normal stays), through the tree and through the brute force; and a whole 4 M-pixel frame's hits
