@@ -42,6 +42,55 @@ assert CROSSING_DTYPE.itemsize == 8
 INSIDE_DIRECTIONS = ((0.5310871, 0.2178203, 0.8188417), (-0.3319057, 0.9047763, -0.2670293), (0.6834621, -0.5712349, -0.4544671))
 
 
+class SdfParams(C.Structure):
+    """include/cgrt.h CgrtSdfParams."""
+    _fields_ = [("max_dist2", C.c_float), ("ndirs", C.c_uint32), ("dirs", (C.c_float * 3) * 7)]
+
+
+class Grid(C.Structure):
+    """include/cgrt.h CgrtGrid: point (ix, iy, iz) = origin + (float)i * spacing per component; dims = (nx, ny, nz)."""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_uint32 * 3)]
+
+
+def _sdf_params(max_dist2: float = float("inf"), directions=None) -> SdfParams:
+    """CgrtSdfParams from max_dist2 and the parity directions (None: the library's defaults, INSIDE_DIRECTIONS).  ValueError for what
+    the structure cannot hold (no directions, more than 7, not (k, 3)); the library checks the values."""
+    p = SdfParams()
+    p.max_dist2 = float(max_dist2)
+    if directions is not None:
+        d = np.asarray(directions, np.float32)
+        if d.ndim != 2 or d.shape[1] != 3 or not 1 <= len(d) <= 7:
+            raise ValueError("directions must be (k, 3) with k in 1..7")
+        if len(d) % 2 == 0:
+            raise ValueError("an odd number of directions is needed for a majority")
+        p.ndirs = len(d)
+        for j, row in enumerate(d):
+            p.dirs[j][:] = [float(x) for x in row]
+    return p
+
+
+def _sdf_grid_struct(origin, spacing, dims) -> Grid:
+    """CgrtGrid from origin (3,), spacing (3,) and dims = (nx, ny, nz)."""
+    o, sp = np.asarray(origin, np.float32).reshape(3), np.asarray(spacing, np.float32).reshape(3)
+    d = [int(x) for x in dims]
+    if len(d) != 3 or min(d) < 0 or max(d) > 0xFFFFFFFF:
+        raise ValueError("dims must be (nx, ny, nz)")
+    g = Grid()
+    g.origin[:], g.spacing[:], g.dims[:] = [float(x) for x in o], [float(x) for x in sp], d
+    return g
+
+
+def sdf_grid_points(origin, spacing, dims) -> np.ndarray:
+    """The float32 points of a CgrtGrid in result order, (nx * ny * nz, 3): point (ix, iy, iz) = origin + float32(i) * spacing per
+    component (the product rounded, then the sum) at row (iz * ny + iy) * nx + ix."""
+    o, sp = np.asarray(origin, np.float32).reshape(3), np.asarray(spacing, np.float32).reshape(3)
+    nx, ny, nz = (int(x) for x in dims)
+    ax = [o[c] + np.arange(m, dtype=np.float32) * sp[c] for c, m in enumerate((nx, ny, nz))]  # (float32 throughout: each operation rounds)
+    p = np.empty((nz, ny, nx, 3), np.float32)
+    p[..., 0], p[..., 1], p[..., 2] = ax[0][None, None, :], ax[1][None, :, None], ax[2][:, None, None]
+    return p.reshape(-1, 3)
+
+
 class CgrtError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"cgrt error {code}: {msg}")
@@ -281,7 +330,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -412,6 +461,12 @@ def lib() -> C.CDLL:
     L.cgrt_list_crossings_brute.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp]
     L.cgrt_list_crossings_device.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp]
     L.cgrt_debug_crossing_work.argtypes = [vp, vp, u64, vp]
+    L.cgrt_signed_distance.argtypes = [vp, vp, u64, C.POINTER(SdfParams), vp, vp]
+    L.cgrt_signed_distance_device.argtypes = [vp, vp, u64, C.POINTER(SdfParams), vp, vp, vp]
+    L.cgrt_signed_distance_grid.argtypes = [vp, C.POINTER(Grid), C.POINTER(SdfParams), vp, vp]
+    L.cgrt_signed_distance_grid_device.argtypes = [vp, C.POINTER(Grid), C.POINTER(SdfParams), vp, vp, vp]
+    L.cgrt_debug_sdf_work.argtypes = [vp, vp, u64, C.POINTER(SdfParams), i32, vp]
+    L.cgrt_debug_set_sdf_grid_mapping.argtypes = [i32]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
     L.cgrt_count_batch.argtypes = [vp, vp, u64, C.POINTER(Counters)]
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
@@ -2104,7 +2159,8 @@ class Scene:
         """Inside / outside for points (n, 3) float32 on cuda:<device>, meaningful for WATERTIGHT meshes: the majority vote, over an odd
         number of fixed directions (default: the three of INSIDE_DIRECTIONS), of the parity of count_crossings along the unbounded ray from
         the point.  One ray's parity fails where the ray passes exactly through a shared edge or a vertex (both triangles are crossed);
-        the vote absorbs one such failure in three.  A composition in Python: no kernel of its own.  Returns (n,) torch.bool."""
+        the vote absorbs one such failure in three.  A composition in Python: no kernel of its own (sdf_tensor(want=("inside",)) is the
+        native entry with the same bytes).  Returns (n,) torch.bool."""
         import torch
 
         if self.device < 0:
@@ -2130,7 +2186,8 @@ class Scene:
 
     def signed_distance_tensor(self, points, stream=None):
         """Signed distance for points (n, 3) float32 on cuda:<device>, meaningful for watertight meshes: sqrt(closest_points' dist2),
-        negated where inside_tensor says inside.  A composition in Python.  Returns (n,) float32."""
+        negated where inside_tensor says inside.  A composition in Python (sdf_tensor is the native entry with the same bytes).  Returns
+        (n,) float32."""
         import torch
 
         inside = self.inside_tensor(points, stream=stream)
@@ -2140,6 +2197,128 @@ class Scene:
         with torch.cuda.stream(stream):
             dist = torch.sqrt(d2)
             return torch.where(inside, -dist, dist)
+
+    # ---- signed distance and occupancy (include/cgrt.h cgrt_signed_distance*) ----
+    @staticmethod
+    def _sdf_want(want):
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in ("sdf", "inside") for w in want) or len(set(want)) != len(want):
+            raise ValueError('want must name "sdf", "inside" or both')
+        return want
+
+    def sdf(self, points, max_dist2: float = float("inf"), directions=None, want=("sdf", "inside")):
+        """cgrt_signed_distance: for every point ((n, 3) float32) sqrt(closest_points' dist2), negative where the majority of the parity
+        walks along `directions` (None: INSIDE_DIRECTIONS; an odd number, at most 7) says inside -- one fused kernel, the bytes of
+        signed_distance_tensor / inside_tensor.  Beyond max_dist2 the value is +-inf; a non-finite point gets (+inf, False).  Returns the
+        arrays named by `want`, in that order ((n,) float32 / (n,) bool); a single name returns the array itself."""
+        want = self._sdf_want(want)
+        p = _f32(points, (-1, 3))
+        prm = _sdf_params(max_dist2, directions)
+        res = {"sdf": np.zeros(len(p), np.float32) if "sdf" in want else None, "inside": np.zeros(len(p), np.uint8) if "inside" in want else None}
+        _check(lib().cgrt_signed_distance(self._h, _ptr(p), len(p), C.byref(prm), _ptr(res["sdf"]), _ptr(res["inside"])))
+        return self._sdf_result(res, want)
+
+    @staticmethod
+    def _sdf_result(res, want):
+        if res["inside"] is not None and res["inside"].dtype == np.uint8:
+            res["inside"] = res["inside"].view(np.bool_)
+        out = tuple(res[w] for w in want)
+        return out[0] if len(out) == 1 else out
+
+    def sdf_device(self, d_points_ptr: int, n: int, d_sdf_ptr: int, d_inside_ptr: int, max_dist2: float = float("inf"), directions=None,
+                   stream: int = 0) -> None:
+        """cgrt_signed_distance_device: n points (3 floats each) at d_points_ptr -> n float32 at d_sdf_ptr and / or n bytes (0 / 1) at
+        d_inside_ptr (0: not wanted; without d_sdf_ptr the closest-point search is not run), enqueued on the hipStream_t `stream`.  Raw
+        integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        prm = _sdf_params(max_dist2, directions)
+        _check(lib().cgrt_signed_distance_device(self._h, vp(d_points_ptr), int(n), C.byref(prm), vp(d_sdf_ptr), vp(d_inside_ptr), vp(stream)))
+
+    def _sdf_tensors(self, shape, want, out, stream, call):
+        """The *_tensor conventions for the two outputs: `out` None, or a dict / tuple (in want's order) of tensors to write into."""
+        import torch
+
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if out is not None and not isinstance(out, dict):
+            out = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+            if len(out) != len(want):
+                raise ValueError("out must hold one tensor per name in want")
+            out = dict(zip(want, out))
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        _check_one_hip_runtime()
+        res = {}
+        for w, dtypes in (("sdf", (torch.float32,)), ("inside", (torch.bool, torch.uint8))):
+            if w not in want:
+                continue
+            t = None if out is None else out.get(w)
+            if t is None:
+                with torch.cuda.stream(stream):  # (allocated on the stream the answers are written on)
+                    t = torch.empty(shape, dtype=dtypes[0], device=dev)
+            else:
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype not in dtypes:
+                    raise ValueError(f"out[{w!r}] must be a torch tensor of shape {tuple(shape)} and one of {dtypes}")
+                if t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or (w == "sdf" and t.data_ptr() % 4):
+                    raise ValueError(f"out[{w!r}] must be contiguous (sdf: 4-byte aligned) on cuda:{self.device}")
+            res[w] = t
+        if int(np.prod(shape)):  # (an empty tensor has no address to pass: the call would touch nothing anyway)
+            call(res["sdf"].data_ptr() if "sdf" in res else 0, res["inside"].data_ptr() if "inside" in res else 0, stream.cuda_stream)
+        got = tuple(res[w] for w in want)
+        return got[0] if len(got) == 1 else got
+
+    def sdf_tensor(self, points, max_dist2: float = float("inf"), directions=None, want=("sdf", "inside"), out=None, stream=None):
+        """sdf on torch tensors: points (n, 3) float32 on cuda:<device> -> the tensors named by `want`, in that order ((n,) float32 /
+        (n,) torch.bool; a single name returns the tensor itself), written into `out` (one tensor, a tuple in want's order or a dict by
+        name; inside may also be torch.uint8) or new ones, enqueued on `stream` (default: torch.cuda.current_stream())."""
+        import torch
+
+        want = self._sdf_want(want)
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be a torch tensor of shape (n, 3)")
+        if self.device >= 0:
+            self._device_tensor(points, "points", (torch.float32,))
+        n = points.shape[0]
+        return self._sdf_tensors((n,), want, out, stream,
+                                 lambda ds, di, s: self.sdf_device(points.data_ptr(), n, ds, di, max_dist2=max_dist2, directions=directions, stream=s))
+
+    def sdf_grid(self, origin, spacing, dims, max_dist2: float = float("inf"), directions=None, want=("sdf", "inside")):
+        """cgrt_signed_distance_grid: sdf on the regular grid of sdf_grid_points(origin, spacing, dims), dims = (nx, ny, nz); the lanes
+        make their own points.  Returns the arrays named by `want` shaped (nz, ny, nx) (x fastest), as sdf returns them."""
+        want = self._sdf_want(want)
+        g, prm = _sdf_grid_struct(origin, spacing, dims), _sdf_params(max_dist2, directions)
+        shape = (g.dims[2], g.dims[1], g.dims[0])
+        m = shape[0] * shape[1] * shape[2] if max(shape) <= 1 << 24 and shape[0] * shape[1] * shape[2] <= 0x7FFFFFFF else 0  # (else: the library says why)
+        res = {"sdf": np.zeros(m, np.float32) if "sdf" in want else None, "inside": np.zeros(m, np.uint8) if "inside" in want else None}
+        _check(lib().cgrt_signed_distance_grid(self._h, C.byref(g), C.byref(prm), _ptr(res["sdf"]), _ptr(res["inside"])))
+        res = {k: (None if v is None else v.reshape(shape)) for k, v in res.items()}
+        return self._sdf_result(res, want)
+
+    def sdf_grid_device(self, origin, spacing, dims, d_sdf_ptr: int, d_inside_ptr: int, max_dist2: float = float("inf"), directions=None,
+                        stream: int = 0) -> None:
+        """cgrt_signed_distance_grid_device: nx * ny * nz float32 at d_sdf_ptr and / or bytes at d_inside_ptr (0: not wanted), in
+        (nz, ny, nx) order, enqueued on the hipStream_t `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        g, prm = _sdf_grid_struct(origin, spacing, dims), _sdf_params(max_dist2, directions)
+        _check(lib().cgrt_signed_distance_grid_device(self._h, C.byref(g), C.byref(prm), vp(d_sdf_ptr), vp(d_inside_ptr), vp(stream)))
+
+    def sdf_grid_tensor(self, origin, spacing, dims, max_dist2: float = float("inf"), directions=None, want=("sdf", "inside"), out=None,
+                        stream=None):
+        """sdf_grid on torch tensors: the tensors named by `want`, shaped (nz, ny, nx), as sdf_tensor returns them."""
+        want = self._sdf_want(want)
+        nx, ny, nz = (int(x) for x in dims)
+        return self._sdf_tensors((nz, ny, nx), want, out, stream,
+                                 lambda ds, di, s: self.sdf_grid_device(origin, spacing, dims, ds, di, max_dist2=max_dist2, directions=directions,
+                                                                        stream=s))
+
+    def debug_sdf_work(self, points, max_dist2: float = float("inf"), directions=None, want_sdf: bool = True):
+        """cgrt_debug_sdf_work: (closest node steps, closest triangles evaluated, crossing node steps, crossing triangles evaluated,
+        direction walks run) of sdf's search, summed over the points (a separate counting launch)."""
+        p = _f32(points, (-1, 3))
+        prm = _sdf_params(max_dist2, directions)
+        w = np.zeros(5, np.uint64)
+        _check(lib().cgrt_debug_sdf_work(self._h, _ptr(p), len(p), C.byref(prm), 1 if want_sdf else 0, _ptr(w)))
+        return tuple(int(x) for x in w)
 
     def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream):
         import torch

@@ -32,6 +32,7 @@
 #include "cgrt_math.h"
 #include "closest_kernels.h"
 #include "crossing_kernels.h"
+#include "sdf_kernels.h"
 #include "surface_kernels.h"
 #include "trace_kernels.h"
 

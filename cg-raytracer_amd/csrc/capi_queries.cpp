@@ -1,5 +1,5 @@
 // capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
-// closest points, crossings.  None of them touches the scene's frame state (workspace, prediction, hints).
+// closest points, crossings, signed distance.  None of them touches the scene's frame state (workspace, prediction, hints).
 #include "capi_internal.h"
 
 extern "C" {
@@ -606,6 +606,127 @@ int cgrt_list_crossings_brute(CgrtScene* s, const CgrtRay* rays, uint64_t n, con
 }
 int cgrt_debug_crossing_work(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint64_t* out2) {
     return crossing_host(s, rays, n, nullptr, 0, nullptr, 0, nullptr, false, 2, out2);
+}
+
+// ---- signed distance and occupancy (include/cgrt.h cgrt_signed_distance*): the closest-point search and the parity
+// vote of a few count searches, fused per point.  No scene state is read or written; the checks come in the order include/cgrt.h states,
+// all before any device work.
+namespace {
+std::atomic<int> g_sdf_grid_linear{0};  // cgrt_debug_set_sdf_grid_mapping
+const float kSdfDefaultDirs[CGRT_SDF_DEFAULT_NDIRS][3] = CGRT_SDF_DEFAULT_DIRS;
+static_assert(sizeof(SdfArgs{}.dirs) == sizeof(CgrtSdfParams{}.dirs) && CGRT_SDF_MAX_DIRS == 7, "the kernel's directions are the parameters'");
+// the checks up to the host-only scene; fills A (result: sdf / inside, or out5 of the work entry in the place of both)
+int sdf_args(const CgrtScene* s, const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtSdfParams* params,
+             const void* sdf, const void* inside, bool device, SdfArgs* A) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    if (is_grid ? !grid : (n && !points)) return fail(CGRT_E_ARG, is_grid ? "grid is NULL" : "NULL argument");
+    if (!sdf && !inside) return fail(CGRT_E_ARG, "NULL argument: neither sdf nor inside is asked for");
+    *A = SdfArgs{};
+    if (is_grid) {
+        n = 1;
+        for (int c = 0; c < 3; c++) {
+            if (grid->dims[c] < 1 || grid->dims[c] > (1u << 24)) return fail(CGRT_E_ARG, "grid dims must be in 1..2^24");
+            n *= grid->dims[c];  // (below 2^55 before the test, which follows every factor)
+            if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many grid points: nx * ny * nz exceeds 0x7fffffff");
+            if (!std::isfinite(grid->origin[c]) || !std::isfinite(grid->spacing[c])) return fail(CGRT_E_ARG, "grid origin and spacing must be finite");
+            A->origin[c] = grid->origin[c];
+            A->spacing[c] = grid->spacing[c];
+            A->dims[c] = grid->dims[c];
+        }
+    } else if (n > 0x7fffffffull) {
+        return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
+    }
+    A->max_dist2 = params ? params->max_dist2 : INFINITY;
+    if (!(A->max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
+    A->ndirs = params ? params->ndirs : 0u;
+    if (A->ndirs > CGRT_SDF_MAX_DIRS || (A->ndirs && A->ndirs % 2 == 0)) return fail(CGRT_E_ARG, "ndirs must be 0 or odd, 1..7");
+    const float(*dirs)[3] = A->ndirs ? params->dirs : kSdfDefaultDirs;
+    if (!A->ndirs) A->ndirs = CGRT_SDF_DEFAULT_NDIRS;
+    for (uint32_t j = 0; j < A->ndirs; j++) {
+        const float* d = dirs[j];
+        if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) return fail(CGRT_E_ARG, "a direction has a non-finite component");
+        if (d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f) return fail(CGRT_E_ARG, "a direction is all zero");
+        memcpy(A->dirs[j], d, 12);
+    }
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)sdf % 4)) return fail(CGRT_E_ARG, "d_points and d_sdf must be 4-byte aligned");
+    A->points = points;
+    A->n = (uint32_t)n;
+    return CGRT_OK;
+}
+// host pointers, on a call lane (slots: 0 the points, 1 sdf, 2 inside); work: the counted launch
+int sdf_host(CgrtScene* s, const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtSdfParams* params, float* sdf,
+             uint8_t* inside, bool counted, int want_sdf, uint64_t* work) {
+    SdfArgs A;
+    int rc = sdf_args(s, points, grid, is_grid, n, params, counted ? static_cast<const void*>(work) : sdf, counted ? nullptr : inside, false, &A);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (A.n == 0) return CGRT_OK;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    void *dp = nullptr, *ds = nullptr, *di = nullptr;
+    if (!is_grid) HIP_TRY(c.input(0, points, (size_t)A.n * 12, &dp));
+    A.points = static_cast<const float*>(dp);
+    const bool brute = crossing_brute_scene(s);
+    if (counted) {
+        A.want_sdf = want_sdf ? 1u : 0u;
+        HIP_TRY(c.zero_counters(5));
+        HIP_TRY(launch_sdf(s->dev, A, SDF_LIST, brute, c.counters(), c.stream()));
+        HIP_TRY(c.read_counters(work, 5));
+        return CGRT_OK;
+    }
+    if (sdf) HIP_TRY(c.scratch(1, (size_t)A.n * 4, &ds));
+    if (inside) HIP_TRY(c.scratch(2, A.n, &di));
+    A.want_sdf = sdf ? 1u : 0u;
+    A.sdf = static_cast<float*>(ds);
+    A.inside = static_cast<uint8_t*>(di);
+    const SdfPoints how = !is_grid ? SDF_LIST : (g_sdf_grid_linear.load() ? SDF_GRID_LINEAR : SDF_GRID_BRICK);
+    HIP_TRY(launch_sdf(s->dev, A, how, brute, nullptr, c.stream()));
+    if (sdf) HIP_TRY(c.output(1, sdf, ds, (size_t)A.n * 4));
+    if (inside) HIP_TRY(c.output(2, inside, di, A.n));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+int sdf_device(CgrtScene* s, const float* d_points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtSdfParams* params, float* d_sdf,
+               uint8_t* d_inside, void* stream) {
+    SdfArgs A;
+    int rc = sdf_args(s, d_points, grid, is_grid, n, params, d_sdf, d_inside, true, &A);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (A.n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if (!is_grid && (rc = check_device_span(s, d_points, (uint64_t)A.n * 12, "d_points")) != CGRT_OK) return rc;
+    if (d_sdf && (rc = check_device_span(s, d_sdf, (uint64_t)A.n * 4, "d_sdf")) != CGRT_OK) return rc;
+    if (d_inside && (rc = check_device_span(s, d_inside, A.n, "d_inside")) != CGRT_OK) return rc;
+    A.want_sdf = d_sdf ? 1u : 0u;
+    A.sdf = d_sdf;
+    A.inside = d_inside;
+    const SdfPoints how = !is_grid ? SDF_LIST : (g_sdf_grid_linear.load() ? SDF_GRID_LINEAR : SDF_GRID_BRICK);
+    HIP_TRY(launch_sdf(s->dev, A, how, crossing_brute_scene(s), nullptr, static_cast<hipStream_t>(stream)));
+    return CGRT_OK;
+}
+}  // namespace
+
+int cgrt_signed_distance(CgrtScene* s, const float* points, uint64_t n, const CgrtSdfParams* params, float* sdf, uint8_t* inside) {
+    return sdf_host(s, points, nullptr, false, n, params, sdf, inside, false, 0, nullptr);
+}
+int cgrt_signed_distance_device(CgrtScene* s, const float* d_points, uint64_t n, const CgrtSdfParams* params, float* d_sdf, uint8_t* d_inside,
+                                void* stream) {
+    return sdf_device(s, d_points, nullptr, false, n, params, d_sdf, d_inside, stream);
+}
+int cgrt_signed_distance_grid(CgrtScene* s, const CgrtGrid* grid, const CgrtSdfParams* params, float* sdf, uint8_t* inside) {
+    return sdf_host(s, nullptr, grid, true, 0, params, sdf, inside, false, 0, nullptr);
+}
+int cgrt_signed_distance_grid_device(CgrtScene* s, const CgrtGrid* grid, const CgrtSdfParams* params, float* d_sdf, uint8_t* d_inside,
+                                     void* stream) {
+    return sdf_device(s, nullptr, grid, true, 0, params, d_sdf, d_inside, stream);
+}
+int cgrt_debug_sdf_work(CgrtScene* s, const float* points, uint64_t n, const CgrtSdfParams* params, int want_sdf, uint64_t* out5) {
+    return sdf_host(s, points, nullptr, false, n, params, nullptr, nullptr, true, want_sdf, out5);
+}
+int cgrt_debug_set_sdf_grid_mapping(int linear) {
+    if (linear != 0 && linear != 1) return fail(CGRT_E_ARG, "linear must be 0 or 1");
+    g_sdf_grid_linear.store(linear);
+    return CGRT_OK;
 }
 
 }  // extern "C"

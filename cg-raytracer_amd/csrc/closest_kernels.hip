@@ -15,139 +15,12 @@
 // lane-interleaved in LDS, two dwords per entry.  k_closest_brute: every record in turn, same function, same rule (validation).
 #include <hip/hip_runtime.h>
 
+#include "closest_device.h"
 #include "closest_kernels.h"
 
 namespace cgrt {
 
 namespace {
-
-#define CGRT_CLOSEST_BLOCK 128
-
-// A deferred subtree on the stack.  Topology references and accelerator references overlap (bit 30 is REF_LEAF_ACCEL in the first and a
-// count bit of a run in the second), so the stack holds one encoding of its own:
-//   bit 31 set             a run of records, exactly the accelerator's REF_LEAF | (count - 1) << 26 | first record
-//   CL_SUB  | index        an accelerator node (two consecutive SubNodes)
-//   CL_LEAF | index        a reference leaf without accelerator: LeafRec{first, count}
-//   index                  a NodePacket
-const uint32_t CL_SUB = 0x20000000u;
-const uint32_t CL_LEAF = 0x40000000u;
-static_assert(SUB_MAX_RECORDS <= CL_SUB, "record indices must stay below the kind bits");
-static_assert(CLOSEST_STACK_ENTRIES == (MAX_LEVELS - 1) + (SUB_WIDTH - 1) * SUB_MAX_DEPTH,
-              "the stack holds one deferred child per NodePacket level and three per accelerator level");
-static_assert(2 * CLOSEST_STACK_ENTRIES * CGRT_CLOSEST_BLOCK * 4 <= 65536, "the stacks of a workgroup must fit its LDS");
-
-__device__ __forceinline__ uint32_t topo_ref(const uint32_t r) {  // a child reference of a NodePacket (or the root), not REF_NONE
-    if (!(r & REF_LEAF)) return r;
-    return (r & REF_LEAF_ACCEL) ? (CL_SUB | (r & REF_INDEX26)) : (CL_LEAF | (r & ~REF_LEAF));
-}
-__device__ __forceinline__ uint32_t sub_ref(const uint32_t r) {  // a child reference of an accelerator node, not REF_NONE
-    return (r & REF_LEAF) ? r : (CL_SUB | r);
-}
-
-struct Best {
-    float d2;       // the bound: best dist2 so far, max_dist2 while prim == CGRT_NO_PRIM
-    uint32_t prim;
-    float qx, qy, qz, v, w;
-};
-
-__device__ __forceinline__ float dot3(const float x0, const float x1, const float x2, const float y0, const float y1, const float y2) {
-    return (x0 * y0 + x1 * y1) + x2 * y2;
-}
-__device__ __forceinline__ float clamp1(const float q, const float a, const float b, const float c) {
-    const float lo = fminf(a, fminf(b, c)), hi = fmaxf(a, fmaxf(b, c));  // (a NaN vertex coordinate makes dist2 NaN whatever these return)
-    return q < lo ? lo : (q > hi ? hi : q);
-}
-
-// include/cgrt.h "Closest-point queries", the definition, operation for operation; r0..r3 = the record's four 16-byte quarters
-__device__ __forceinline__ void closest_tri(const float4 r0, const float4 r1, const float4 r2, const float4 r3, const float px, const float py,
-                                            const float pz, Best& B) {
-    const float ax = r0.x, ay = r0.y, az = r0.z, bx = r0.w, by = r1.x, bz = r1.y, cx = r1.z, cy = r1.w, cz = r2.x;
-    const float abx = bx - ax, aby = by - ay, abz = bz - az;
-    const float acx = cx - ax, acy = cy - ay, acz = cz - az;
-    const float apx = px - ax, apy = py - ay, apz = pz - az;
-    const float bpx = px - bx, bpy = py - by, bpz = pz - bz;
-    const float cpx = px - cx, cpy = py - cy, cpz = pz - cz;
-    const float d1 = dot3(abx, aby, abz, apx, apy, apz), d2 = dot3(acx, acy, acz, apx, apy, apz);
-    const float d3 = dot3(abx, aby, abz, bpx, bpy, bpz), d4 = dot3(acx, acy, acz, bpx, bpy, bpz);
-    const float d5 = dot3(abx, aby, abz, cpx, cpy, cpz), d6 = dot3(acx, acy, acz, cpx, cpy, cpz);
-    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-    const float e1 = d4 - d3, e2 = d5 - d6;
-    const bool rA = d1 <= 0.0f && d2 <= 0.0f;
-    const bool rB = d3 >= 0.0f && d4 <= d3;
-    const bool rAB = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
-    const bool rC = d6 >= 0.0f && d5 <= d6;
-    const bool rAC = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
-    const bool rBC = va <= 0.0f && e1 >= 0.0f && e2 >= 0.0f;
-    // every non-vertex region divides once: one division, its operands selected in the regions' priority
-    float num = 1.0f, den = (va + vb) + vc;
-    if (rBC) num = e1, den = e1 + e2;
-    if (rAC) num = d2, den = d2 - d6;
-    if (rC) num = 0.0f, den = 1.0f;
-    if (rAB) num = d1, den = d1 - d3;
-    if (rA || rB) num = 0.0f, den = 1.0f;
-    const float t = num / den;
-    float v, w;
-    if (rA) {
-        v = 0.0f, w = 0.0f;
-    } else if (rB) {
-        v = 1.0f, w = 0.0f;
-    } else if (rAB) {
-        v = t, w = 0.0f;
-    } else if (rC) {
-        v = 0.0f, w = 1.0f;
-    } else if (rAC) {
-        v = 0.0f, w = t;
-    } else if (rBC) {
-        w = t, v = 1.0f - w;
-    } else {
-        v = vb * t, w = vc * t;
-    }
-    float qx = (ax + abx * v) + acx * w, qy = (ay + aby * v) + acy * w, qz = (az + abz * v) + acz * w;
-    const bool atA = rA, atB = !rA && rB, atC = !rA && !rB && !rAB && rC;
-    qx = atA ? ax : (atB ? bx : (atC ? cx : qx));
-    qy = atA ? ay : (atB ? by : (atC ? cy : qy));
-    qz = atA ? az : (atB ? bz : (atC ? cz : qz));
-    qx = clamp1(qx, ax, bx, cx);
-    qy = clamp1(qy, ay, by, cy);
-    qz = clamp1(qz, az, bz, cz);
-    const float rx = px - qx, ry = py - qy, rz = pz - qz;
-    const float dist2 = dot3(rx, ry, rz, rx, ry, rz);
-    const uint32_t prim = __float_as_uint(r3.y);
-    // dist2 <= max_dist2 qualifies (prim starts as CGRT_NO_PRIM, above every id); smaller dist2 wins, equal dist2 goes to the smaller id
-    const bool take = dist2 < B.d2 || (dist2 == B.d2 && prim < B.prim);
-    B.d2 = take ? dist2 : B.d2;
-    B.prim = take ? prim : B.prim;
-    B.qx = take ? qx : B.qx;
-    B.qy = take ? qy : B.qy;
-    B.qz = take ? qz : B.qz;
-    B.v = take ? v : B.v;
-    B.w = take ? w : B.w;
-}
-
-// squared distance from p to the box, in dist2's operations and association
-__device__ __forceinline__ float box_lb2(const float lox, const float hix, const float loy, const float hiy, const float loz, const float hiz,
-                                         const float px, const float py, const float pz) {
-    const float dx = fmaxf(fmaxf(lox - px, px - hix), 0.0f);
-    const float dy = fmaxf(fmaxf(loy - py, py - hiy), 0.0f);
-    const float dz = fmaxf(fmaxf(loz - pz, pz - hiz), 0.0f);
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// Sort key of a child: the bits of its lb2 (non-negative floats order as integers; a NaN bound never culls and sorts first, as 0), all
-// ones for a child that is absent or culled.
-__device__ __forceinline__ uint32_t child_key(const uint32_t ref, const float lb, const float bound) {
-    if (ref == REF_NONE || lb > bound) return 0xffffffffu;
-    return lb != lb ? 0u : __float_as_uint(lb);
-}
-__device__ __forceinline__ void order2(uint32_t& ka, uint32_t& ra, uint32_t& kb, uint32_t& rb) {
-    const bool s = ka > kb;
-    const uint32_t k0 = s ? kb : ka, k1 = s ? ka : kb, q0 = s ? rb : ra, q1 = s ? ra : rb;
-    ka = k0, kb = k1, ra = q0, rb = q1;
-}
-
-__device__ __forceinline__ bool finite3(const float x, const float y, const float z) {
-    return fabsf(x) <= 3.402823466e+38f && fabsf(y) <= 3.402823466e+38f && fabsf(z) <= 3.402823466e+38f;
-}
 
 __device__ __forceinline__ void store_result(CgrtClosestDev* out, const unsigned long long i, const Best& B) {
     float* o = reinterpret_cast<float*>(out + i);  // (the caller's buffer is only 4-byte aligned)

@@ -883,6 +883,66 @@ int cgrt_list_crossings_brute(CgrtScene* scene, const CgrtRay* rays, uint64_t n,
                               uint64_t capacity, uint32_t* counts);
 int cgrt_debug_crossing_work(CgrtScene* scene, const CgrtRay* rays, uint64_t n, uint64_t* out2);
 
+/* Signed distance and occupancy: "how far is this point from the surface, and is it inside?" -- for point lists
+ * and for regular grids (a mesh turned into an SDF volume).  The compute_signed_distance / compute_occupancy pair of other ray-casting
+ * scene interfaces, meaningful for WATERTIGHT meshes.  One fused kernel: no rays, counts or closest records are written in between.
+ * Definition.  For a finite point p, with the parameters' max_dist2 and directions dirs[0 .. ndirs) (ndirs == 0: the three rows of
+ * CGRT_SDF_DEFAULT_DIRS):
+ *   C      = the cgrt_closest_points record of p under max_dist2
+ *   c_j    = the cgrt_count_crossings count of the ray {origin p, direction dirs[j], t = +inf}
+ *   inside = (number of odd c_j) > ndirs / 2
+ *   s      = sqrt(C.dist2), IEEE, correctly rounded (+inf stays +inf);   sdf = inside ? -s : s
+ * so beyond max_dist2 the value is +-inf with the sign of the vote, and dist2 == 0 inside gives -0.0.  These are, bit for bit, the bytes
+ * the Python compositions Scene.signed_distance_tensor and Scene.inside_tensor produce for finite points.  A non-finite p gets sdf = +inf,
+ * inside = 0 without a search; in a scene without meshes every point gets the same.  Spheres are ignored, as in both underlying queries.
+ * Outputs.  sdf (f32) and inside (u8, 0 or 1), n of each; either may be NULL, not both.  With sdf == NULL (occupancy only) the
+ * closest-point search is not run.  Nothing outside records 0..n-1 is written.
+ * Grid.  Point (ix, iy, iz) is p.c = origin.c + (float)i_c * spacing.c -- the product rounded, then the sum, nothing contracted -- and its
+ * result is at index (iz * ny + iy) * nx + ix: a contiguous (nz, ny, nx) array with x fastest.  The value is what the list form returns
+ * for that point.  Each dim is 1..2^24, nx * ny * nz <= 0x7fffffff, origin and spacing finite (zero or negative spacing is allowed).
+ * Search.  One point per lane.  First the closest-point search of cgrt_closest_points keeping only the bound (the equal-dist2 tie rule
+ * does not affect the value), then per direction the count search of cgrt_count_crossings keeping only the parity.  Once more than
+ * ndirs / 2 walks agree (odd or even) the remaining walks are skipped; the outputs do not depend on this.  Where the conservative box
+ * argument does not hold the parity walks do what the crossing entries do: on a scene with a wild leaf or a non-finite vertex they test
+ * every triangle, and a ray outside the box test's envelope scans every record itself.  The closest search needs no such rule.
+ * cgrt_debug_sdf_work: a separate counting launch (never part of a timed region), want_sdf != 0 including the closest search; out5 =
+ * {closest node steps, closest triangles evaluated, crossing node steps, crossing triangles evaluated, direction walks run}, summed over
+ * the n points.
+ * Streams.  The host forms (host pointers, synchronous) run on a call lane like cgrt_closest_points: any number of threads may query one
+ * scene at once.  The device forms read no host array behind the call (the parameters travel in the kernel arguments) and only enqueue on
+ * `stream` (NULL = default stream); they are concurrent on one scene and neither read nor write the prediction record or the frame hints.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene; NULL points (or grid) with n > 0; both outputs NULL (out5
+ * of the work entry); n > 0x7fffffff, or the grid limits above; bad parameters (max_dist2 NaN or negative; ndirs even or above 7; a
+ * direction with a non-finite component or all zero); (device forms) d_points or d_sdf not 4-byte aligned.  Then a host-only scene:
+ * CGRT_E_NO_DEVICE.  n == 0 succeeds and touches nothing.  Device forms: then d_points (n * 12 bytes), d_sdf (n * 4) and d_inside (n)
+ * checked as device memory of the scene's device, as cgrt_shade_rays_device checks its buffers.
+ * Not offered: one parity ray per grid row (the crossing arithmetic depends on the origin, so it would not give these bytes);
+ * winding-number signs for open meshes; spheres; gradients; enqueued-ticket forms (the device forms never block); the C++ host mirror. */
+#define CGRT_SDF_MAX_DIRS 7
+#define CGRT_SDF_DEFAULT_NDIRS 3
+#define CGRT_SDF_DEFAULT_DIRS \
+    { {0.5310871f, 0.2178203f, 0.8188417f}, {-0.3319057f, 0.9047763f, -0.2670293f}, {0.6834621f, -0.5712349f, -0.4544671f} }
+typedef struct CgrtSdfParams { /* NULL = all defaults */
+    float max_dist2;           /* as cgrt_closest_points: +inf = unbounded; NaN or negative -> CGRT_E_ARG           */
+    uint32_t ndirs;            /* 0 = the three default directions; otherwise odd, 1..7                             */
+    float dirs[7][3];          /* read when ndirs > 0: every component finite, no all-zero row                      */
+} CgrtSdfParams;
+typedef struct CgrtGrid {
+    float origin[3];
+    float spacing[3];
+    uint32_t dims[3]; /* nx, ny, nz */
+} CgrtGrid;
+int cgrt_signed_distance(CgrtScene* scene, const float* points, uint64_t n, const CgrtSdfParams* params, float* sdf, uint8_t* inside);
+int cgrt_signed_distance_device(CgrtScene* scene, const float* d_points, uint64_t n, const CgrtSdfParams* params, float* d_sdf,
+                                uint8_t* d_inside, void* stream);
+int cgrt_signed_distance_grid(CgrtScene* scene, const CgrtGrid* grid, const CgrtSdfParams* params, float* sdf, uint8_t* inside);
+int cgrt_signed_distance_grid_device(CgrtScene* scene, const CgrtGrid* grid, const CgrtSdfParams* params, float* d_sdf, uint8_t* d_inside,
+                                     void* stream);
+int cgrt_debug_sdf_work(CgrtScene* scene, const float* points, uint64_t n, const CgrtSdfParams* params, int want_sdf, uint64_t* out5);
+/* How the grid forms map lanes to grid points (process-wide; a measuring switch, the results are the same bytes): 0 = each wave takes a
+ * 4 x 4 x 4 brick of grid points, a block two bricks next to each other in x (the default); 1 = lanes follow the result index. */
+int cgrt_debug_set_sdf_grid_mapping(int linear);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
