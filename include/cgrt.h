@@ -797,6 +797,20 @@ int cgrt_surface_raycams_grad_device(CgrtScene* scene, const CgrtRayCamera* cams
  * lb2 <= dist2 holds in f32 with no slack.  The search skips a subtree iff `lb2 > bound` is TRUE (bound = the best dist2 so far, max_dist2
  * while nothing has been accepted; strict, a NaN never culls) and therefore returns exactly what cgrt_closest_points_brute -- every
  * triangle in turn, same function, same rule; a validation path, not a fast one -- returns, bit for bit.
+ * Envelope.  va, vb, vc are products of dot products: they grow as the FOURTH power of the scene's size.  With E the largest triangle
+ * edge, A the smallest non-zero (2 * area)^2 = |ab x ac|^2 of the triangles, S the largest |coordinate| and M the largest |p - vertex| of
+ * the query:
+ *   upper edge  8 * (E * M)^2 <= FLT_MAX   (|d1..d6| <= E * M, so va, vb, vc and (va+vb)+vc do not overflow)  and  3 * M^2 <= FLT_MAX
+ *   lower edge  A >= 2^12 * FLT_MIN        ((va+vb)+vc = |ab x ac|^2 in the reals: it, and va, vb, vc down to 2^-12 of it, stay normal)
+ *               max(S, |p|inf) >= 2^-39    (the square of a residual of one rounding, 2^-24 of the coordinates, stays normal)
+ * e.g. a unit-sized mesh with edges of 1/16 and queries within its box: about 2^-24 .. 2^+32. Inside the envelope (a) the accuracy
+ * bound holds -- sqrt(dist2) and the distance to the returned triangle are within 5.66 * 2^-24 * max(1, |p|inf, S) of the float64
+ * distance (tests/test_closest_cpu.py) -- and (b) multiplying every position and every query by 2^k is an exact symmetry: the same
+ * prim_id and bary bits, point * 2^k, dist2 * 2^2k.  The upper edge is a proof.  The lower one is a margin: a query whose weight towards
+ * an edge is non-zero but below 2^-12 can have that va, vb or vc rounded as a subnormal.  Outside the envelope the result is still the
+ * defined one, bit for bit, on every path, but can be far from the geometric answer: on a unit cube scaled by 2^33 about 5 % of
+ * unbounded queries miss (every dist2 NaN), from 2^60 a fifth of the records have dist2 = +inf (which qualifies under max_dist2 = +inf),
+ * and on a 1 848-triangle unit blob scaled by 2^-31 only 65 % of the queries are still covariant (DESIGN.md 5.20 has the table).
  * The search uses the structure every scene has (the reference tree, the in-leaf accelerators, linear leaves under
  * cgrt_set_leaf_accel(0)); the walk settings (cgrt_scene_set_walk, cgrt_set_fast_tree, cgrt_set_kernel_shape) do not change it.
  * Streams.  The host forms (host pointers, synchronous) run on a call lane like cgrt_occluded: any number of threads may query one scene
@@ -855,6 +869,17 @@ int cgrt_debug_closest_work(CgrtScene* scene, const float* points, uint64_t n, f
  * not hold the search is not used: a scene with a wild leaf or a non-finite vertex (cgrt_scene_build_info [1] > 0 or [2] == 0) runs the
  * brute-force kernel for the whole call, and a ray outside the box test's envelope (non-finite or beyond 2^+-40, NaN t) tests every
  * triangle itself.  The walk settings (cgrt_scene_set_walk, cgrt_set_fast_tree, cgrt_set_kernel_shape) do not enter.
+ * Envelope.  trianglePlane normalises cross(v1-v0, v2-v0), and |cross|^2 = (2 * area)^2 grows as the FOURTH power of the scene's size.
+ * With E, A, S as in "Closest-point queries" and M the largest |o - vertex|: inside  8 * (E * M)^2 <= FLT_MAX,  A >= 2^12 * FLT_MIN
+ * and  max(S, |o|inf) >= 2^-39, multiplying every position, every origin and every t by 2^k -- the directions kept -- is an exact
+ * symmetry: the same counts, the same prim_id order, every t_k * 2^k.  For crossings NEITHER edge is a proof.  |cross|^2 <= E^4 and the
+ * plane's D and dot(o, n) are covered, but pointInTriangle multiplies an edge by |p - vertex| with p = o + d * tt the hit of the PLANE,
+ * which for a grazing ray lies arbitrarily far from the triangle: M does not bound it.  (Such a product overflows only where p is far
+ * outside the triangle, where the three tests then fail through inf - inf = NaN as they fail in the reals; the tests hold the envelope
+ * to the definition on their own rays, they do not prove it.)  Outside, the records are still the defined ones, byte for byte, on every
+ * path, but need not mean anything: a |cross|^2 that overflows gives n = (0, 0, 0), D = 0, and the origin-on-plane rule then accepts
+ * EVERY ray at t = 0 (from 2^33 on, a unit cube is crossed twelve times by almost every ray; a slot is insertion-sorted, so such lists
+ * cost count^2); one that underflows gives a NaN normal and the triangle is never crossed.
  * cgrt_debug_crossing_work: a separate counting launch of the count search (never part of a timed region); out2 = {node steps, triangles
  * evaluated}, summed over the n rays.
  * Streams.  The host forms (host pointers, synchronous) run on a call lane like cgrt_closest_points: any number of threads may query one
@@ -905,6 +930,14 @@ int cgrt_debug_crossing_work(CgrtScene* scene, const CgrtRay* rays, uint64_t n, 
  * ndirs / 2 walks agree (odd or even) the remaining walks are skipped; the outputs do not depend on this.  Where the conservative box
  * argument does not hold the parity walks do what the crossing entries do: on a scene with a wild leaf or a non-finite vertex they test
  * every triangle, and a ray outside the box test's envelope scans every record itself.  The closest search needs no such rule.
+ * Envelope and meaning.  `inside` is a statement about geometry for CLOSED meshes only (every directed edge matched once by its reverse
+ * after welding equal positions): there it equals |winding number| > 0.5 and |sdf| the float64 distance within 5.66 * 2^-24 * max(1,
+ * |p|inf, S) for every point farther than 1e-4 extents from the surface (tests/test_point_scale_cpu.py, _gpu.py: a cube and a curved
+ * 20 000-triangle mesh).  On an open mesh the vote is still the defined one, and means nothing.  The envelope is the intersection of
+ * those of the two underlying queries with M the largest |p - vertex| ("Closest-point queries", "Crossing queries"): inside it,
+ * multiplying every position, every point and the grid's origin and spacing by 2^k (max_dist2 by 2^2k) leaves `inside` unchanged and
+ * multiplies sdf by 2^k, exactly; outside it the bytes are still the defined ones but the vote flips (for 23-27 % of the points of
+ * unit-sized meshes of a few thousand triangles scaled by 2^-30, for 18 % on a unit cube scaled by 2^32).
  * cgrt_debug_sdf_work: a separate counting launch (never part of a timed region), want_sdf != 0 including the closest search; out5 =
  * {closest node steps, closest triangles evaluated, crossing node steps, crossing triangles evaluated, direction walks run}, summed over
  * the n points.

@@ -1,0 +1,192 @@
+"""Power-of-two scaling of scenes and queries, and what the point queries owe to it (include/cgrt.h "Envelope" paragraphs of the closest-point,
+crossing and signed-distance entries).  numpy only.
+
+Multiplying every position, every query point and every ray origin by 2^k changes no significand, so inside the envelope -- no
+intermediate of the definition overflows or becomes subnormal -- every float32 operation of the definitions rounds the same way: prim_id,
+barycentrics, counts, orders and `inside` are unchanged, points, t and sdf are multiplied by 2^k, dist2 by 2^2k, exactly.  The predicates
+below state that per record; `in_envelope` is the headers' envelope paragraph in code.  Beside them what a sign test needs: `is_closed`,
+the float64 generalised winding number and queries just off the surface."""
+import dataclasses
+
+import numpy as np
+
+import closest_ref as cr
+
+F32 = np.float32
+FLT_MAX = float(np.finfo(np.float32).max)
+FLT_MIN = float(np.finfo(np.float32).tiny)  # 2^-126, the smallest normal
+HEADROOM = 2.0 ** 12  # the lower edge: what stays normal below the smallest triangle's (2 * area)^2 (see in_envelope)
+
+
+# ---- scaling ----
+def scaled(sd, k):
+    """The scene with every position multiplied by 2^k (np.ldexp: exact unless it overflows or becomes subnormal).  Normals, indices and
+    everything else are untouched."""
+    pn = np.asarray(sd.pos_nrm, np.float32).reshape(-1, 6).copy()
+    with np.errstate(all="ignore"):
+        pn[:, 0:3] = np.ldexp(pn[:, 0:3], int(k))
+    return dataclasses.replace(sd, pos_nrm=pn, name=f"{sd.name}*2^{int(k)}")
+
+
+def scaled_points(q, k):
+    with np.errstate(all="ignore"):
+        return np.ldexp(np.ascontiguousarray(np.asarray(q, np.float32).reshape(-1, 3)), int(k)).astype(np.float32)
+
+
+def scaled_rays(rays, k):
+    """(n, 7) rays with the origin and t multiplied by 2^k; the directions are kept."""
+    r = np.ascontiguousarray(np.asarray(rays, np.float32).reshape(-1, 7)).copy()
+    with np.errstate(all="ignore"):
+        r[:, 0:3] = np.ldexp(r[:, 0:3], int(k))
+        r[:, 6] = np.ldexp(r[:, 6], int(k))
+    return r
+
+
+def _ld(x, k):
+    with np.errstate(all="ignore"):
+        return np.ldexp(np.asarray(x, np.float32), int(k)).astype(np.float32)
+
+
+def _bits_eq(a, b):
+    """Bit equality of float32 arrays, a NaN equal to a NaN (conftest.same_bits)."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+
+
+# ---- the covariance predicates: (n,) bool, one verdict per record ----
+def covariant_closest(r0, rk, k):
+    """CLOSEST_DTYPE records at scale 1 and at scale 2^k: the same prim_id and bary bits, point = ldexp(point0, k), dist2 = ldexp(dist2_0, 2k)."""
+    ok = (r0["prim_id"] == rk["prim_id"]) & _bits_eq(r0["bary"], rk["bary"]).all(axis=1)
+    ok &= _bits_eq(_ld(r0["point"], k), rk["point"]).all(axis=1)
+    return ok & _bits_eq(_ld(r0["dist2"], 2 * k), rk["dist2"])
+
+
+def covariant_crossings(ref0, refk, k):
+    """(counts, offsets, records) of a full list at scale 1 and at scale 2^k (origins and t scaled, directions kept): the same count, the
+    same prim_id order, t = ldexp(t0, k)."""
+    (c0, o0, rec0), (ck, ok_, reck) = ref0, refk
+    good = np.asarray(c0) == np.asarray(ck)
+    for i in np.flatnonzero(good):
+        a, b = rec0[o0[i] : o0[i + 1]], reck[ok_[i] : ok_[i + 1]]
+        good[i] = bool((a["prim_id"] == b["prim_id"]).all() and _bits_eq(_ld(a["t"], k), b["t"]).all())
+    return good
+
+
+def covariant_first(f0, fk, k):
+    """(n, m) CROSSING_DTYPE slots (first_crossings): the same ids, t = ldexp(t0, k) (+inf of an unused entry stays +inf)."""
+    return ((f0["prim_id"] == fk["prim_id"]) & _bits_eq(_ld(f0["t"], k), fk["t"])).reshape(len(f0), -1).all(axis=1)
+
+
+def covariant_sdf(a, b, k):
+    """(sdf, inside) at scale 1 and at scale 2^k: inside equal, sdf = ldexp(sdf0, k) (sign and +-inf included)."""
+    (s0, i0), (sk, ik) = a, b
+    return (np.asarray(i0) == np.asarray(ik)) & _bits_eq(_ld(s0, k), sk)
+
+
+# ---- the envelope ----
+def _triangle_measures(sd):
+    """(largest edge length, smallest non-zero (2 * area)^2 = |ab x ac|^2, largest |coordinate|) in float64, over finite triangles."""
+    a, b, c = cr.tri_verts(sd, np.float64)
+    with np.errstate(all="ignore"):
+        fin = np.isfinite(a).all(axis=1) & np.isfinite(b).all(axis=1) & np.isfinite(c).all(axis=1)
+        a, b, c = a[fin], b[fin], c[fin]
+        edge = max(np.linalg.norm(b - a, axis=1).max(), np.linalg.norm(c - a, axis=1).max(), np.linalg.norm(c - b, axis=1).max())
+        n = np.cross(b - a, c - a)
+        area2 = (n * n).sum(axis=1)
+    return float(edge), float(area2[area2 > 0].min()), float(max(np.abs(a).max(), np.abs(b).max(), np.abs(c).max()))
+
+
+def in_envelope(sd, points):
+    """(n,) bool: the point (a query point, or a ray's origin) lies in the envelope of the point queries on this scene -- the "Envelope"
+    paragraphs of include/cgrt.h in code.  With E the scene's largest triangle edge, A the smallest non-zero (2 * area)^2 = |ab x ac|^2 of
+    its triangles, S its largest |coordinate| and M(p) the largest |p - vertex| (bounded by the farthest corner of the scene's box):
+
+      upper edge   8 * (E * M(p))^2 <= FLT_MAX       each of d1..d6 is at most E * M(p); va, vb, vc are differences of two products of
+                                                     them and (va + vb) + vc sums three: none overflows.  (|cross|^2 <= E^4 and dist2 <=
+                                                     3 M^2 are smaller.)
+                   3 * M(p)^2 <= FLT_MAX             dist2 where E is tiny
+      lower edge   A >= 2^12 * FLT_MIN               (va + vb) + vc = |ab x ac|^2 in the reals, and |cross|^2 of the crossing test is the
+                                                     same quantity: it and every va, vb, vc down to 2^-12 of it stay normal
+                   (2^-24 * max(S, |p|inf))^2 >= FLT_MIN   a residual of one rounding of the coordinates still has a normal square
+                                                     (max(S, |p|inf) >= 2^-39)
+
+    The upper edge is a proof for the closest-point definition.  For crossings it is not: pointInTriangle multiplies an edge by
+    |p - vertex| with p the ray's hit of the triangle's PLANE, which for a grazing ray lies arbitrarily far away, so M(origin) does not
+    bound it (such a product overflows only far outside the triangle, where the tests then fail through NaN as they fail in the reals).
+    The lower one is a margin: cancellation can leave a non-zero va, vb or vc below 2^-12 of the sum (a weight towards an edge that small
+    but not 0), which is then rounded as a subnormal; a bound that excludes it needs the granularity of the coordinates (ulp^4) and would
+    put scale 1 itself outside.  tests/test_point_scale_cpu.py holds both edges to the restatements: it
+    fails if covariance breaks anywhere inside.  Non-finite points are outside."""
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    E, A, S = _triangle_measures(sd)
+    lo, hi = cr.scene_box(sd)
+    with np.errstate(all="ignore"):
+        far = np.maximum(np.abs(p - lo), np.abs(p - hi))
+        M = np.sqrt((far * far).sum(axis=1))
+        pmax = np.maximum(S, np.abs(p).max(axis=1))
+        ok = np.isfinite(p).all(axis=1)
+        ok &= 8.0 * (E * M) ** 2 <= FLT_MAX
+        ok &= 3.0 * M * M <= FLT_MAX
+        ok &= A >= HEADROOM * FLT_MIN
+        ok &= (2.0 ** -24 * pmax) ** 2 >= FLT_MIN
+    return ok
+
+
+# ---- closed meshes and the winding number ----
+def is_closed(sd):
+    """Every directed edge of every triangle is matched exactly once by its reverse, after welding vertices with equal positions."""
+    pos = np.asarray(sd.pos_nrm, np.float32).reshape(-1, 6)[:, 0:3]
+    tri = np.asarray(sd.tri, np.int64).reshape(-1, 3)
+    _, weld = np.unique(pos + F32(0.0), axis=0, return_inverse=True)  # (-0 + 0 = +0: the two zeros are one position)
+    t = weld.reshape(-1)[tri]
+    e = np.concatenate([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]])
+    if (e[:, 0] == e[:, 1]).any():
+        return False
+    V = int(t.max()) + 1
+    fwd, cnt_f = np.unique(e[:, 0] * V + e[:, 1], return_counts=True)
+    rev, cnt_r = np.unique(e[:, 1] * V + e[:, 0], return_counts=True)
+    return bool(len(fwd) == len(rev) and (fwd == rev).all() and (cnt_f == 1).all() and (cnt_r == 1).all())
+
+
+def winding64(sd, points, chunk_elems=1 << 20):
+    """(n,) float64 generalised winding number of the scene's triangles about every point: the sum of the signed solid angles (van
+    Oosterom and Strackee's arctan2 form) over 4 pi.  +-1 inside a closed mesh (the sign is its orientation), 0 outside."""
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    a, b, c = cr.tri_verts(sd, np.float64)
+    out = np.zeros(len(p))
+    step = max(1, chunk_elems // max(len(a), 1))
+    for s in range(0, len(p), step):
+        pp = p[s : s + step, None, :]
+        ra, rb, rc = a - pp, b - pp, c - pp
+        la, lb, lc = (np.sqrt((x * x).sum(axis=-1)) for x in (ra, rb, rc))
+        num = (ra * np.cross(rb, rc)).sum(axis=-1)
+        den = la * lb * lc + (ra * rb).sum(axis=-1) * lc + (rb * rc).sum(axis=-1) * la + (rc * ra).sum(axis=-1) * lb
+        out[s : s + step] = np.arctan2(num, den).sum(axis=1) / (2.0 * np.pi)
+    return out
+
+
+def offset_queries(sd, n, seed, h):
+    """Random surface points (closest_ref.surface_queries' sampling) moved by +h (even rows) or -h (odd rows) along the float64 geometric
+    normal of their triangle: just off the surface, on both sides."""
+    a, b, c = cr.tri_verts(sd, np.float64)
+    rng = np.random.default_rng(seed)
+    k = rng.integers(0, len(a), n)
+    r1, r2 = np.sqrt(rng.random(n)), rng.random(n)
+    u, v, w = 1 - r1, r1 * (1 - r2), r1 * r2
+    nrm = np.cross(b[k] - a[k], c[k] - a[k])
+    nrm /= np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-300)
+    side = np.where(np.arange(n) % 2 == 0, 1.0, -1.0)[:, None]
+    return (a[k] * u[:, None] + b[k] * v[:, None] + c[k] * w[:, None] + side * float(h) * nrm).astype(np.float32)
+
+
+def extent(sd):
+    lo, hi = cr.scene_box(sd)
+    return float((hi - lo).max())
+
+
+def sign_queries(sd, n, seed):
+    """The point mix of the sign tests: a third uniform in the grown box, a third offset by 1e-2 of the extent, a third by 1e-3."""
+    m = n // 3
+    ext = extent(sd)
+    return np.ascontiguousarray(np.concatenate([cr.uniform_queries(sd, m, seed), offset_queries(sd, n - 2 * m - (n - 3 * m) // 2, seed + 1, 1e-2 * ext),
+                                                offset_queries(sd, m + (n - 3 * m) // 2, seed + 2, 1e-3 * ext)]), np.float32)

@@ -6,7 +6,11 @@
 * sdf_grid_points is the grid formula in the (nz, ny, nx) order.
 * tests/sdf_ref.py -- the definition on the CPU, what the GPU tests hold the device to -- agrees with the analytic box distance on the
   cube (the 4 096 points of test_crossings_gpu.py's cube test, seed 78): within 1e-5 where |sdf| > 1e-3; at most 2 % of the points may be
-  left out (measured: 0.17 % left out, 12.6 % inside)."""
+  left out (measured: 0.17 % left out, 12.6 % inside).
+
+The cube is the closed mesh here.  blob, monkey and dodge, on which tests/test_sdf_gpu.py runs, are OPEN (tests/test_point_scale_cpu.py
+asserts it): their tests pin the definition, not geometry; the sign on a curved closed mesh is held to the float64 winding number in
+tests/test_point_scale_cpu.py and tests/test_point_scale_gpu.py."""
 import ctypes as C
 import os
 import re

@@ -5,7 +5,10 @@ Everything is compared as bytes and no point is left out: the fused kernel (k_sd
 (Scene.signed_distance_tensor / Scene.inside_tensor: three count_crossings launches, one closest_points launch and torch arithmetic) and
 tests/sdf_ref.py -- the definition on the CPU, which tests/test_sdf_cpu.py holds to the analytic box distance -- give the same values.  The
 point lists are closest_ref.mixed_queries (uniform, on the surface, at vertices, on edges, far; one NaN and one inf point): the on-plane
-and through-edge points are where a parity goes wrong.  Device outputs lie between guards of sentinel bytes."""
+and through-edge points are where a parity goes wrong.  Device outputs lie between guards of sentinel bytes.
+
+blob, monkey and dodge are OPEN meshes (tests/test_point_scale_cpu.py asserts it): on them "inside" has no geometric meaning, and these
+tests pin the definition, not geometry.  The sign is held to geometry on the closed meshes (cube, dragon) in tests/test_point_scale_*.py."""
 import dataclasses
 import threading
 
