@@ -52,6 +52,18 @@ class Grid(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_uint32 * 3)]
 
 
+class WindingParams(C.Structure):
+    """include/cgrt.h CgrtWindingParams."""
+    _fields_ = [("beta", C.c_float), ("threshold", C.c_float)]
+
+
+def _winding_params(beta: float = 2.0, threshold: float = 0.5) -> WindingParams:
+    """CgrtWindingParams; the library checks beta (>= 1, +inf allowed, 0 = its default)."""
+    p = WindingParams()
+    p.beta, p.threshold = float(beta), float(threshold)
+    return p
+
+
 def _sdf_params(max_dist2: float = float("inf"), directions=None) -> SdfParams:
     """CgrtSdfParams from max_dist2 and the parity directions (None: the library's defaults, INSIDE_DIRECTIONS).  ValueError for what
     the structure cannot hold (no directions, more than 7, not (k, 3)); the library checks the values."""
@@ -330,7 +342,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -467,6 +479,13 @@ def lib() -> C.CDLL:
     L.cgrt_signed_distance_grid_device.argtypes = [vp, C.POINTER(Grid), C.POINTER(SdfParams), vp, vp, vp]
     L.cgrt_debug_sdf_work.argtypes = [vp, vp, u64, C.POINTER(SdfParams), i32, vp]
     L.cgrt_debug_set_sdf_grid_mapping.argtypes = [i32]
+    L.cgrt_winding_numbers.argtypes = [vp, vp, u64, C.POINTER(WindingParams), vp, vp]
+    L.cgrt_winding_numbers_device.argtypes = [vp, vp, u64, C.POINTER(WindingParams), vp, vp, vp]
+    L.cgrt_winding_numbers_grid.argtypes = [vp, C.POINTER(Grid), C.POINTER(WindingParams), vp, vp]
+    L.cgrt_winding_numbers_grid_device.argtypes = [vp, C.POINTER(Grid), C.POINTER(WindingParams), vp, vp, vp]
+    L.cgrt_winding_numbers_brute.argtypes = [vp, vp, u64, C.POINTER(WindingParams), vp, vp]
+    L.cgrt_debug_winding_work.argtypes = [vp, vp, u64, C.POINTER(WindingParams), vp]
+    L.cgrt_debug_get_winding_tree.argtypes = [vp, vp, vp, C.POINTER(u32), vp]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
     L.cgrt_count_batch.argtypes = [vp, vp, u64, C.POINTER(Counters)]
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
@@ -2234,8 +2253,9 @@ class Scene:
         prm = _sdf_params(max_dist2, directions)
         _check(lib().cgrt_signed_distance_device(self._h, vp(d_points_ptr), int(n), C.byref(prm), vp(d_sdf_ptr), vp(d_inside_ptr), vp(stream)))
 
-    def _sdf_tensors(self, shape, want, out, stream, call):
-        """The *_tensor conventions for the two outputs: `out` None, or a dict / tuple (in want's order) of tensors to write into."""
+    def _sdf_tensors(self, shape, want, out, stream, call, value="sdf"):
+        """The *_tensor conventions for the two outputs (`value`: the name of the float32 one): `out` None, or a dict / tuple (in want's
+        order) of tensors to write into."""
         import torch
 
         if self.device < 0:
@@ -2249,7 +2269,7 @@ class Scene:
         stream = torch.cuda.current_stream(dev) if stream is None else stream
         _check_one_hip_runtime()
         res = {}
-        for w, dtypes in (("sdf", (torch.float32,)), ("inside", (torch.bool, torch.uint8))):
+        for w, dtypes in ((value, (torch.float32,)), ("inside", (torch.bool, torch.uint8))):
             if w not in want:
                 continue
             t = None if out is None else out.get(w)
@@ -2259,11 +2279,11 @@ class Scene:
             else:
                 if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype not in dtypes:
                     raise ValueError(f"out[{w!r}] must be a torch tensor of shape {tuple(shape)} and one of {dtypes}")
-                if t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or (w == "sdf" and t.data_ptr() % 4):
-                    raise ValueError(f"out[{w!r}] must be contiguous (sdf: 4-byte aligned) on cuda:{self.device}")
+                if t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or (w == value and t.data_ptr() % 4):
+                    raise ValueError(f"out[{w!r}] must be contiguous ({value}: 4-byte aligned) on cuda:{self.device}")
             res[w] = t
         if int(np.prod(shape)):  # (an empty tensor has no address to pass: the call would touch nothing anyway)
-            call(res["sdf"].data_ptr() if "sdf" in res else 0, res["inside"].data_ptr() if "inside" in res else 0, stream.cuda_stream)
+            call(res[value].data_ptr() if value in res else 0, res["inside"].data_ptr() if "inside" in res else 0, stream.cuda_stream)
         got = tuple(res[w] for w in want)
         return got[0] if len(got) == 1 else got
 
@@ -2319,6 +2339,126 @@ class Scene:
         w = np.zeros(5, np.uint64)
         _check(lib().cgrt_debug_sdf_work(self._h, _ptr(p), len(p), C.byref(prm), 1 if want_sdf else 0, _ptr(w)))
         return tuple(int(x) for x in w)
+
+    # ---- winding numbers (include/cgrt.h cgrt_winding_numbers*) ----
+    @staticmethod
+    def _winding_want(want):
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in ("w", "inside") for w in want) or len(set(want)) != len(want):
+            raise ValueError('want must name "w", "inside" or both')
+        return want
+
+    def _winding_host(self, f, points, prm, want):
+        want = self._winding_want(want)
+        p = _f32(points, (-1, 3))
+        res = {"w": np.zeros(len(p), np.float32) if "w" in want else None, "inside": np.zeros(len(p), np.uint8) if "inside" in want else None}
+        _check(f(self._h, _ptr(p), len(p), C.byref(prm), _ptr(res["w"]), _ptr(res["inside"])))
+        return self._sdf_result(res, want)
+
+    def winding_numbers(self, points, beta: float = 2.0, threshold: float = 0.5, want=("w", "inside")):
+        """cgrt_winding_numbers: for every point ((n, 3) float32) the generalised winding number of the scene's triangles -- +-1 inside a
+        closed mesh, 0 outside, smooth near holes: a sign that also means something on OPEN meshes -- by the cluster tree (far clusters,
+        from `beta` cluster radii on, are replaced by their dipole; beta = inf: every triangle, the bytes of winding_numbers_brute), and
+        inside = |w| > threshold.  A non-finite point gets (0, False).  Returns the arrays named by `want`, in that order ((n,) float32 /
+        (n,) bool); a single name returns the array itself."""
+        return self._winding_host(lib().cgrt_winding_numbers, points, _winding_params(beta, threshold), want)
+
+    def winding_numbers_brute(self, points, threshold: float = 0.5, want=("w", "inside")):
+        """cgrt_winding_numbers_brute: the sum over every triangle in record order (validation; what winding_numbers returns with
+        beta = inf, byte for byte)."""
+        return self._winding_host(lib().cgrt_winding_numbers_brute, points, _winding_params(0.0, threshold), want)
+
+    def winding_numbers_device(self, d_points_ptr: int, n: int, d_w_ptr: int, d_inside_ptr: int, beta: float = 2.0, threshold: float = 0.5,
+                               stream: int = 0) -> None:
+        """cgrt_winding_numbers_device: n points (3 floats each) at d_points_ptr -> n float32 at d_w_ptr and / or n bytes (0 / 1) at
+        d_inside_ptr (0: not wanted), enqueued on the hipStream_t `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        prm = _winding_params(beta, threshold)
+        _check(lib().cgrt_winding_numbers_device(self._h, vp(d_points_ptr), int(n), C.byref(prm), vp(d_w_ptr), vp(d_inside_ptr), vp(stream)))
+
+    def winding_numbers_tensor(self, points, beta: float = 2.0, threshold: float = 0.5, want=("w", "inside"), out=None, stream=None):
+        """winding_numbers on torch tensors: points (n, 3) float32 on cuda:<device> -> the tensors named by `want`, in that order ((n,)
+        float32 / (n,) torch.bool; a single name returns the tensor itself), written into `out` (one tensor, a tuple in want's order or
+        a dict by name; inside may also be torch.uint8) or new ones, enqueued on `stream` (default: torch.cuda.current_stream())."""
+        import torch
+
+        want = self._winding_want(want)
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be a torch tensor of shape (n, 3)")
+        if self.device >= 0:
+            self._device_tensor(points, "points", (torch.float32,))
+        n = points.shape[0]
+        return self._sdf_tensors((n,), want, out, stream,
+                                 lambda dw, di, s: self.winding_numbers_device(points.data_ptr(), n, dw, di, beta=beta, threshold=threshold, stream=s),
+                                 value="w")
+
+    def winding_grid(self, origin, spacing, dims, beta: float = 2.0, threshold: float = 0.5, want=("w", "inside")):
+        """cgrt_winding_numbers_grid: winding_numbers on the regular grid of sdf_grid_points(origin, spacing, dims), dims = (nx, ny, nz);
+        the lanes make their own points.  Returns the arrays named by `want` shaped (nz, ny, nx) (x fastest)."""
+        want = self._winding_want(want)
+        g, prm = _sdf_grid_struct(origin, spacing, dims), _winding_params(beta, threshold)
+        shape = (g.dims[2], g.dims[1], g.dims[0])
+        m = shape[0] * shape[1] * shape[2] if max(shape) <= 1 << 24 and shape[0] * shape[1] * shape[2] <= 0x7FFFFFFF else 0  # (else: the library says why)
+        res = {"w": np.zeros(m, np.float32) if "w" in want else None, "inside": np.zeros(m, np.uint8) if "inside" in want else None}
+        _check(lib().cgrt_winding_numbers_grid(self._h, C.byref(g), C.byref(prm), _ptr(res["w"]), _ptr(res["inside"])))
+        res = {k: (None if v is None else v.reshape(shape)) for k, v in res.items()}
+        return self._sdf_result(res, want)
+
+    def winding_grid_device(self, origin, spacing, dims, d_w_ptr: int, d_inside_ptr: int, beta: float = 2.0, threshold: float = 0.5,
+                            stream: int = 0) -> None:
+        """cgrt_winding_numbers_grid_device: nx * ny * nz float32 at d_w_ptr and / or bytes at d_inside_ptr (0: not wanted), in
+        (nz, ny, nx) order, enqueued on the hipStream_t `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        g, prm = _sdf_grid_struct(origin, spacing, dims), _winding_params(beta, threshold)
+        _check(lib().cgrt_winding_numbers_grid_device(self._h, C.byref(g), C.byref(prm), vp(d_w_ptr), vp(d_inside_ptr), vp(stream)))
+
+    def winding_grid_tensor(self, origin, spacing, dims, beta: float = 2.0, threshold: float = 0.5, want=("w", "inside"), out=None, stream=None):
+        """winding_grid on torch tensors: the tensors named by `want`, shaped (nz, ny, nx), as winding_numbers_tensor returns them."""
+        want = self._winding_want(want)
+        nx, ny, nz = (int(x) for x in dims)
+        return self._sdf_tensors((nz, ny, nx), want, out, stream,
+                                 lambda dw, di, s: self.winding_grid_device(origin, spacing, dims, dw, di, beta=beta, threshold=threshold, stream=s),
+                                 value="w")
+
+    def debug_winding_work(self, points, beta: float = 2.0):
+        """cgrt_debug_winding_work: (clusters tested, dipoles taken, triangles evaluated) of winding_numbers' walk, summed over the points
+        (a separate counting launch)."""
+        p = _f32(points, (-1, 3))
+        prm = _winding_params(beta)
+        w = np.zeros(3, np.uint64)
+        _check(lib().cgrt_debug_winding_work(self._h, _ptr(p), len(p), C.byref(prm), _ptr(w)))
+        return tuple(int(x) for x in w)
+
+    def debug_winding_tree(self):
+        """cgrt_debug_get_winding_tree (works host-only): {'clusters': (m, 8) float32 rows {c.xyz, r2, n.xyz, 0}, 'level_offsets':
+        (nlevels + 1,) int64 -- level L is rows [level_offsets[L], level_offsets[L + 1]), level 0 first --, 'record_prims': (ntris,)
+        uint32, the prim_id of every triangle record in record order: level 0's cluster i covers records [8 i, 8 i + 8)}."""
+        nlev = C.c_uint32(0)
+        off = np.zeros(10, np.uint32)
+        _check(lib().cgrt_debug_get_winding_tree(self._h, None, _ptr(off), C.byref(nlev), None))
+        off = off[: nlev.value + 1]
+        clusters = np.zeros((int(off[-1]), 8), np.float32)
+        prims = np.zeros(int(np.asarray(self.sd.tri).size // 3), np.uint32)
+        _check(lib().cgrt_debug_get_winding_tree(self._h, _ptr(clusters), None, C.byref(nlev), _ptr(prims)))
+        return {"clusters": clusters, "level_offsets": off.astype(np.int64), "record_prims": prims}
+
+    def inside_winding_tensor(self, points, beta: float = 2.0, threshold: float = 0.5, stream=None):
+        """Inside / outside by the winding number, meaningful for open meshes too: |winding_numbers_tensor| > threshold.  (n,) torch.bool."""
+        return self.winding_numbers_tensor(points, beta=beta, threshold=threshold, want=("inside",), stream=stream)
+
+    def signed_distance_winding_tensor(self, points, max_dist2: float = float("inf"), beta: float = 2.0, stream=None):
+        """Signed distance with the winding number's sign: sqrt(closest_points' dist2), negated where |w| > 0.5.  On a closed mesh away
+        from the surface these are sdf_tensor's bytes; on an open mesh the sign still means something.  A composition in Python (the
+        signed-distance kernel is left as it is).  Returns (n,) float32."""
+        import torch
+
+        inside = self.inside_winding_tensor(points, beta=beta, stream=stream)
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        d2 = self.closest_points_tensor(points, max_dist2=max_dist2, stream=stream)["dist2"]
+        with torch.cuda.stream(stream):
+            dist = torch.sqrt(d2)
+            return torch.where(inside, -dist, dist)
 
     def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream):
         import torch

@@ -35,6 +35,7 @@
 #include "sdf_kernels.h"
 #include "surface_kernels.h"
 #include "trace_kernels.h"
+#include "winding_kernels.h"
 
 using namespace cgrt;
 
@@ -302,10 +303,17 @@ struct CgrtScene {
     std::vector<uint32_t> tri_index;  // ntris x 3
     std::mutex surface_mutex;
     std::atomic<void*> d_surface_lookup{nullptr};
+    // Winding numbers (cgrt_winding_numbers*): the cluster tree over the records (winding_builder.h), made on the
+    // host by the scene's first winding call under surface_mutex (a host-only scene included: cgrt_debug_get_winding_tree reads it), and
+    // its device copy, uploaded once by the first call that launches.  A scene that makes no such call never builds either.
+    WindingTree winding;
+    std::atomic<bool> winding_built{false};
+    std::atomic<void*> d_winding{nullptr};
     ~CgrtScene() {
         if (device < 0) return;
         (void)hipSetDevice(device);
         if (void* p = d_surface_lookup.load()) (void)hipFree(p);
+        if (void* p = d_winding.load()) (void)hipFree(p);
         for (EnqSlot& e : eslot) {  // (frames in flight complete before anything they use is released)
             if (e.pending) (void)hipEventSynchronize(e.done);
             for (hipEvent_t ev : {e.done, e.t0, e.t1})

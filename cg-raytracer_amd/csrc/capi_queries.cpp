@@ -1,5 +1,5 @@
 // capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
-// closest points, crossings, signed distance.  None of them touches the scene's frame state (workspace, prediction, hints).
+// closest points, crossings, signed distance, winding numbers.  None of them touches the scene's frame state (workspace, prediction, hints).
 #include "capi_internal.h"
 
 extern "C" {
@@ -726,6 +726,174 @@ int cgrt_debug_sdf_work(CgrtScene* s, const float* points, uint64_t n, const Cgr
 int cgrt_debug_set_sdf_grid_mapping(int linear) {
     if (linear != 0 && linear != 1) return fail(CGRT_E_ARG, "linear must be 0 or 1");
     g_sdf_grid_linear.store(linear);
+    return CGRT_OK;
+}
+
+// ---- winding numbers (include/cgrt.h cgrt_winding_numbers*): the signed solid angles of the triangles over 4 pi,
+// every triangle (brute) or far clusters of the tree of winding_builder.h replaced by their dipoles.  No frame state is read or written;
+// the checks come in the order include/cgrt.h states, all before any device work.
+namespace {
+// the scene's cluster tree on the host, built by the first caller (later calls: one atomic load); works on a host-only scene
+int winding_host_tree(CgrtScene* s) {
+    if (s->winding_built.load(std::memory_order_acquire)) return CGRT_OK;
+    std::lock_guard<std::mutex> lk(s->surface_mutex);
+    if (s->winding_built.load(std::memory_order_acquire)) return CGRT_OK;
+    if (s->bvh.tris.size() != s->ntris || s->ntris > SUB_MAX_RECORDS) return fail(CGRT_E_ARG, "the scene's records do not cover its triangles");
+    try {
+        build_winding_tree(s->bvh.tris.data(), s->ntris, s->winding);
+    } catch (const std::bad_alloc&) {
+        return fail(CGRT_E_ALLOC, "host allocation failed");
+    }
+    s->winding_built.store(true, std::memory_order_release);
+    return CGRT_OK;
+}
+// ... and on the device, uploaded once (complete when this returns: every later launch on any stream sees it); fills A's tree fields
+int winding_device_tree(CgrtScene* s, WindingArgs* A) {
+    int rc = winding_host_tree(s);
+    if (rc) return rc;
+    const WindingTree& T = s->winding;
+    void* p = s->d_winding.load(std::memory_order_acquire);
+    if (!p && !T.clusters.empty()) {
+        std::lock_guard<std::mutex> lk(s->surface_mutex);
+        p = s->d_winding.load(std::memory_order_acquire);
+        if (!p) {
+            const size_t bytes = T.clusters.size() * sizeof(WindingCluster);
+            void* d = nullptr;
+            HIP_TRY(hipMalloc(&d, bytes));
+            const hipError_t e = staged_h2d(d, T.clusters.data(), bytes);
+            if (e != hipSuccess) {
+                (void)hipFree(d);
+                return hip_fail(e, "uploading the winding cluster tree");
+            }
+            s->device_bytes += bytes;
+            s->d_winding.store(d, std::memory_order_release);
+            p = d;
+        }
+    }
+    A->clusters = static_cast<const WindingCluster*>(p);
+    A->nlevels = T.nlevels();
+    A->top_base = A->nlevels ? T.level_offsets[A->nlevels - 1] : 0u;
+    return CGRT_OK;
+}
+// the checks up to the host-only scene; fills A (result: w / inside, or out3 of the work entry in the place of both); brute: beta is not read
+int winding_args(const CgrtScene* s, const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtWindingParams* params, bool brute,
+                 const void* w, const void* inside, bool device, WindingArgs* A) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    if (is_grid ? !grid : (n && !points)) return fail(CGRT_E_ARG, is_grid ? "grid is NULL" : "NULL argument");
+    if (!w && !inside) return fail(CGRT_E_ARG, "NULL argument: neither w nor inside is asked for");
+    *A = WindingArgs{};
+    if (is_grid) {
+        n = 1;
+        for (int c = 0; c < 3; c++) {
+            if (grid->dims[c] < 1 || grid->dims[c] > (1u << 24)) return fail(CGRT_E_ARG, "grid dims must be in 1..2^24");
+            n *= grid->dims[c];  // (below 2^55 before the test, which follows every factor)
+            if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many grid points: nx * ny * nz exceeds 0x7fffffff");
+            if (!std::isfinite(grid->origin[c]) || !std::isfinite(grid->spacing[c])) return fail(CGRT_E_ARG, "grid origin and spacing must be finite");
+            A->origin[c] = grid->origin[c];
+            A->spacing[c] = grid->spacing[c];
+            A->dims[c] = grid->dims[c];
+        }
+    } else if (n > 0x7fffffffull) {
+        return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
+    }
+    float beta = params ? params->beta : 0.0f;
+    if (beta == 0.0f || brute) beta = CGRT_WINDING_DEFAULT_BETA;
+    if (!(beta >= 1.0f)) return fail(CGRT_E_ARG, "beta must be a number >= 1 (0: the default; +inf: no cluster is far)");
+    A->beta2 = beta * beta;  // rounded once, here
+    A->threshold = params ? params->threshold : CGRT_WINDING_DEFAULT_THRESHOLD;
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)w % 4)) return fail(CGRT_E_ARG, "d_points and d_w must be 4-byte aligned");
+    A->points = points;
+    A->n = (uint32_t)n;
+    return CGRT_OK;
+}
+// host pointers, on a call lane (slots: 0 the points, 1 w, 2 inside); work: the counted launch
+int winding_host(CgrtScene* s, const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtWindingParams* params, float* w,
+                 uint8_t* inside, bool brute, uint64_t* work) {
+    WindingArgs A;
+    int rc = winding_args(s, points, grid, is_grid, n, params, brute, work ? static_cast<const void*>(work) : w, work ? nullptr : inside, false, &A);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (A.n == 0) return CGRT_OK;
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    A.recs = s->dev.tris + s->dev.tri_base;
+    A.ntris = s->dev.ntris;
+    if (!brute && (rc = winding_device_tree(s, &A)) != CGRT_OK) return rc;
+    void *dp = nullptr, *dw = nullptr, *di = nullptr;
+    if (!is_grid) HIP_TRY(c.input(0, points, (size_t)A.n * 12, &dp));
+    A.points = static_cast<const float*>(dp);
+    if (work) {
+        HIP_TRY(c.zero_counters(3));
+        HIP_TRY(launch_winding(A, WINDING_LIST, false, c.counters(), c.stream()));
+        HIP_TRY(c.read_counters(work, 3));
+        return CGRT_OK;
+    }
+    if (w) HIP_TRY(c.scratch(1, (size_t)A.n * 4, &dw));
+    if (inside) HIP_TRY(c.scratch(2, A.n, &di));
+    A.w = static_cast<float*>(dw);
+    A.inside = static_cast<uint8_t*>(di);
+    HIP_TRY(launch_winding(A, is_grid ? WINDING_GRID_BRICK : WINDING_LIST, brute, nullptr, c.stream()));
+    if (w) HIP_TRY(c.output(1, w, dw, (size_t)A.n * 4));
+    if (inside) HIP_TRY(c.output(2, inside, di, A.n));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+int winding_device(CgrtScene* s, const float* d_points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtWindingParams* params, float* d_w,
+                   uint8_t* d_inside, void* stream) {
+    WindingArgs A;
+    int rc = winding_args(s, d_points, grid, is_grid, n, params, false, d_w, d_inside, true, &A);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (A.n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if (!is_grid && (rc = check_device_span(s, d_points, (uint64_t)A.n * 12, "d_points")) != CGRT_OK) return rc;
+    if (d_w && (rc = check_device_span(s, d_w, (uint64_t)A.n * 4, "d_w")) != CGRT_OK) return rc;
+    if (d_inside && (rc = check_device_span(s, d_inside, A.n, "d_inside")) != CGRT_OK) return rc;
+    A.recs = s->dev.tris + s->dev.tri_base;
+    A.ntris = s->dev.ntris;
+    if ((rc = winding_device_tree(s, &A)) != CGRT_OK) return rc;
+    A.w = d_w;
+    A.inside = d_inside;
+    HIP_TRY(launch_winding(A, is_grid ? WINDING_GRID_BRICK : WINDING_LIST, false, nullptr, static_cast<hipStream_t>(stream)));
+    return CGRT_OK;
+}
+}  // namespace
+
+int cgrt_winding_numbers(CgrtScene* s, const float* points, uint64_t n, const CgrtWindingParams* params, float* w, uint8_t* inside) {
+    return winding_host(s, points, nullptr, false, n, params, w, inside, false, nullptr);
+}
+int cgrt_winding_numbers_device(CgrtScene* s, const float* d_points, uint64_t n, const CgrtWindingParams* params, float* d_w, uint8_t* d_inside,
+                                void* stream) {
+    return winding_device(s, d_points, nullptr, false, n, params, d_w, d_inside, stream);
+}
+int cgrt_winding_numbers_grid(CgrtScene* s, const CgrtGrid* grid, const CgrtWindingParams* params, float* w, uint8_t* inside) {
+    return winding_host(s, nullptr, grid, true, 0, params, w, inside, false, nullptr);
+}
+int cgrt_winding_numbers_grid_device(CgrtScene* s, const CgrtGrid* grid, const CgrtWindingParams* params, float* d_w, uint8_t* d_inside,
+                                     void* stream) {
+    return winding_device(s, nullptr, grid, true, 0, params, d_w, d_inside, stream);
+}
+int cgrt_winding_numbers_brute(CgrtScene* s, const float* points, uint64_t n, const CgrtWindingParams* params, float* w, uint8_t* inside) {
+    return winding_host(s, points, nullptr, false, n, params, w, inside, true, nullptr);
+}
+int cgrt_debug_winding_work(CgrtScene* s, const float* points, uint64_t n, const CgrtWindingParams* params, uint64_t* out3) {
+    return winding_host(s, points, nullptr, false, n, params, nullptr, nullptr, false, out3);
+}
+int cgrt_debug_get_winding_tree(CgrtScene* s, float* clusters, uint32_t* level_offsets, uint32_t* nlevels, uint32_t* record_prims) {
+    if (!s || !nlevels) return fail(CGRT_E_ARG, "NULL argument");
+    const int rc = winding_host_tree(s);
+    if (rc) return rc;
+    const WindingTree& T = s->winding;
+    *nlevels = T.nlevels();
+    if (level_offsets) {
+        if (T.level_offsets.empty())
+            level_offsets[0] = 0;
+        else
+            memcpy(level_offsets, T.level_offsets.data(), T.level_offsets.size() * sizeof(uint32_t));
+    }
+    if (clusters && !T.clusters.empty()) memcpy(clusters, T.clusters.data(), T.clusters.size() * sizeof(WindingCluster));
+    if (record_prims)
+        for (size_t k = 0; k < s->bvh.tris.size(); k++) record_prims[k] = s->bvh.tris[k].prim_id;
     return CGRT_OK;
 }
 

@@ -950,7 +950,8 @@ int cgrt_debug_crossing_work(CgrtScene* scene, const CgrtRay* rays, uint64_t n, 
  * CGRT_E_NO_DEVICE.  n == 0 succeeds and touches nothing.  Device forms: then d_points (n * 12 bytes), d_sdf (n * 4) and d_inside (n)
  * checked as device memory of the scene's device, as cgrt_shade_rays_device checks its buffers.
  * Not offered: one parity ray per grid row (the crossing arithmetic depends on the origin, so it would not give these bytes);
- * winding-number signs for open meshes; spheres; gradients; enqueued-ticket forms (the device forms never block); the C++ host mirror. */
+ * spheres; gradients; enqueued-ticket forms (the device forms never block); the C++ host mirror.  (Signs
+ * for open meshes: "Winding numbers" below.) */
 #define CGRT_SDF_MAX_DIRS 7
 #define CGRT_SDF_DEFAULT_NDIRS 3
 #define CGRT_SDF_DEFAULT_DIRS \
@@ -975,6 +976,84 @@ int cgrt_debug_sdf_work(CgrtScene* scene, const float* points, uint64_t n, const
 /* How the grid forms map lanes to grid points (process-wide; a measuring switch, the results are the same bytes): 0 = each wave takes a
  * 4 x 4 x 4 brick of grid points, a block two bricks next to each other in x (the default); 1 = lanes follow the result index. */
 int cgrt_debug_set_sdf_grid_mapping(int linear);
+
+/* Winding numbers: a robust inside / outside for meshes that are NOT watertight -- for point lists and for
+ * regular grids.  The generalised winding number of the scene's triangles about a point is the sum of their signed solid angles over
+ * 4 pi: +-1 inside a closed mesh (the sign is its orientation), 0 outside, and it degrades smoothly near holes, self-intersections and
+ * duplicated faces, where the parity vote of cgrt_signed_distance means nothing.  An exact all-triangles form (brute) and a hierarchical
+ * form (tree) that replaces far clusters of triangles by one dipole.
+ * Definition.  Everything is f32, every operation rounded on its own (nothing contracted), sums associated as the parentheses say.  For a
+ * finite point p and a triangle record {v0, v1, v2} (the vertices in the caller's order):
+ *   ra = v0 - p, rb = v1 - p, rc = v2 - p                      (componentwise)
+ *   la = sqrtf((ra.x * ra.x + ra.y * ra.y) + ra.z * ra.z), lb and lc alike
+ *   u  = rb x rc:  u.x = rb.y * rc.z - rb.z * rc.y,  u.y = rb.z * rc.x - rb.x * rc.z,  u.z = rb.x * rc.y - rb.y * rc.x
+ *   num = (ra.x * u.x + ra.y * u.y) + ra.z * u.z
+ *   ab = (ra.x * rb.x + ra.y * rb.y) + ra.z * rb.z,  bc = (rb.x * rc.x + ..) + ..,  ca = (rc.x * ra.x + ..) + ..
+ *   den = (((la * lb) * lc + ab * lc) + bc * la) + ca * lb
+ *   omega = 2.0f * atan2f(num, den)                             (van Oosterom and Strackee)
+ * Brute form: acc = 0; acc = acc + omega_k for the records k = 0 .. ntris - 1 in RECORD ORDER (the order of the device's triangle array:
+ * cgrt_debug_get_winding_tree reports it); w = acc * (1 / (4 pi)), the constant rounded to f32.
+ * Tree form.  The records carry an implicit 8-ary cluster tree: level 0's cluster i covers records [8 i, min(8 i + 8, ntris)), level L's
+ * cluster i the level-(L - 1) clusters 8 i .. 8 i + 7; level L has ceil(ntris / 8^(L+1)) clusters and the top level is the first with at
+ * most 8 (at most 9 levels).  A cluster is 32 bytes {c.xyz, r2, n.xyz, 0}: c the area-weighted mean of its triangles' centroids (their
+ * plain mean when the area sum is 0 or not finite), n the sum of their area vectors (v1 - v0) x (v2 - v0) / 2, both evaluated in double and
+ * rounded once; r2 the largest ((dx * dx + dy * dy) + dz * dz), d = vertex - c, over the vertices of its records, evaluated in f32 in that
+ * association (NaN if one of them is).  The walk is depth-first from the top level, clusters and children in index order, into the same
+ * accumulator acc (0 at the start), with d = c - p and d2 = (d.x * d.x + d.y * d.y) + d.z * d.z:
+ *   the cluster is FAR iff  d2 > beta2 * r2  is TRUE (beta2 = beta * beta, rounded once on the host; a NaN therefore opens the cluster)
+ *   far:                acc = acc + ((n.x * d.x + n.y * d.y) + n.z * d.z) / (d2 * sqrtf(d2))      (the cluster's dipole; IEEE division)
+ *   near, level 0:      acc = acc + omega_k for its records in record order
+ *   near, level > 0:    its children are walked
+ * and w = acc * (1 / (4 pi)) as above.  With beta = +inf no cluster is far (inf * 0 is a NaN) and the walk performs the brute form's
+ * additions in the brute form's order: it returns the brute form's bytes.  inside = fabsf(w) > threshold, for every point.
+ * A non-finite p gets w = 0 without a walk; in a scene without meshes every point gets 0.  Spheres are ignored.  A scene with non-finite
+ * vertices may give NaN (inside = 0 then); no call faults or hangs over it.  As in the other point queries the values are meaningful
+ * while no intermediate overflows (|p - vertex|^3 within f32).
+ * Parameters.  beta >= 1 (the opening ratio: a cluster is replaced by its dipole from beta cluster radii on; larger = more exact, more
+ * work; +inf allowed), 0 = CGRT_WINDING_DEFAULT_BETA; NaN or anything else below 1 -> CGRT_E_ARG.  threshold: taken as given (a NaN
+ * makes every inside 0).  params == NULL: {2.0f, 0.5f}.  The brute entry reads only the threshold.
+ * Accuracy (DESIGN.md 5.25 has the table): against the float64 sum over every triangle the tree form's largest error at beta = 2 was
+ * 1.8e-2 .. 3.2e-2 on the test meshes (6.3e-2 on an 800 000-triangle mesh), 2e-3 .. 1.3e-2 at beta = 4, and no verdict |w| > 0.5 differed
+ * among the points with ||w| - 0.5| >= 0.05.
+ * Outputs.  w (f32) and inside (u8, 0 or 1), n of each; either may be NULL, not both.  Nothing outside records 0..n-1 is written.
+ * Grid.  CgrtGrid and the result order of cgrt_signed_distance_grid: point (ix, iy, iz) = origin + (float)i * spacing per component (the
+ * product rounded, then the sum), result at (iz * ny + iy) * nx + ix; the value is what the list form returns for that point.
+ * The tree is built on the host by the scene's first winding call (any entry below but the brute one), under the scene's lock, uploaded
+ * once and freed with the scene; cgrt_device_bytes includes it from then on; cgrt_debug_layout_hash does not change (no existing array
+ * is touched).  With cgrt_set_leaf_accel(0) the record order inside a leaf is the reference's scan order, the clusters get fat and the
+ * walk does more work; the answers stay within the same bounds.
+ * cgrt_debug_winding_work: a separate counting launch of the tree form; out3 = {clusters tested, dipoles taken, triangles evaluated},
+ * summed over the n points.  The far decisions are f32 arithmetic in the order above, so the counters are reproducible on a CPU.
+ * cgrt_debug_get_winding_tree (works on host-only scenes, building the tree if need be): *nlevels receives the number of levels;
+ * level_offsets (NULL, or 10 entries are always enough) nlevels + 1 entries, level L's clusters are [level_offsets[L], level_offsets[L+1]);
+ * clusters (NULL, or 8 floats per cluster) the array; record_prims (NULL, or one entry per triangle) the prim_id of every record in
+ * record order.  Sizes first: call with NULL arrays, or compute them from the triangle count.
+ * Streams.  The host forms (host pointers, synchronous) run on a call lane like cgrt_closest_points: any number of threads may query one
+ * scene at once.  The device forms read no host array behind the call (the parameters travel in the kernel arguments) and only enqueue
+ * on `stream` (NULL = default stream); the first of them on a scene uploads the tree before it enqueues.  They are concurrent on one
+ * scene and neither read nor write the prediction record or the frame hints.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene; NULL points (or grid) with n > 0; both outputs NULL (out3
+ * of the work entry); n > 0x7fffffff, or the grid limits of cgrt_signed_distance_grid; bad beta; (device forms) d_points or d_w not
+ * 4-byte aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and touches nothing.  Device forms: then d_points (n * 12
+ * bytes), d_w (n * 4) and d_inside (n) checked as device memory of the scene's device.
+ * Not offered: the winding sign fused into the signed-distance kernel (whose registers must not move: Scene.signed_distance_winding_tensor
+ * composes the two); higher-order expansions than the dipole; gradients; spheres; enqueued-ticket forms (the device forms never block);
+ * the C++ host mirror; a Morton re-sort of the records. */
+#define CGRT_WINDING_DEFAULT_BETA 2.0f
+#define CGRT_WINDING_DEFAULT_THRESHOLD 0.5f
+typedef struct CgrtWindingParams { /* NULL = all defaults */
+    float beta;                    /* 0 = CGRT_WINDING_DEFAULT_BETA; otherwise >= 1 (+inf allowed); NaN or below 1 -> CGRT_E_ARG */
+    float threshold;               /* inside = fabsf(w) > threshold                                                          */
+} CgrtWindingParams;
+int cgrt_winding_numbers(CgrtScene* scene, const float* points, uint64_t n, const CgrtWindingParams* params, float* w, uint8_t* inside);
+int cgrt_winding_numbers_device(CgrtScene* scene, const float* d_points, uint64_t n, const CgrtWindingParams* params, float* d_w,
+                                uint8_t* d_inside, void* stream);
+int cgrt_winding_numbers_grid(CgrtScene* scene, const CgrtGrid* grid, const CgrtWindingParams* params, float* w, uint8_t* inside);
+int cgrt_winding_numbers_grid_device(CgrtScene* scene, const CgrtGrid* grid, const CgrtWindingParams* params, float* d_w, uint8_t* d_inside,
+                                     void* stream);
+int cgrt_winding_numbers_brute(CgrtScene* scene, const float* points, uint64_t n, const CgrtWindingParams* params, float* w, uint8_t* inside);
+int cgrt_debug_winding_work(CgrtScene* scene, const float* points, uint64_t n, const CgrtWindingParams* params, uint64_t* out3);
+int cgrt_debug_get_winding_tree(CgrtScene* scene, float* clusters, uint32_t* level_offsets, uint32_t* nlevels, uint32_t* record_prims);
 
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
