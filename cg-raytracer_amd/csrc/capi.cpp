@@ -657,8 +657,8 @@ int cgrt_intersect_batch_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n,
     if (!s || (n && (!d_rays || !d_hits))) return fail(CGRT_E_ARG, "NULL argument");
     NEED_DEVICE(s);
     HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(launch_trace_batch(s->dev, reinterpret_cast<const float*>(d_rays), n, reinterpret_cast<CgrtHitDev*>(d_hits), d_normals,
-                               nullptr, static_cast<hipStream_t>(stream)));
+    HIP_TRY(launch_trace_batch(s->dev, RayList{reinterpret_cast<const float*>(d_rays), n, reinterpret_cast<CgrtHitDev*>(d_hits), d_normals}, nullptr,
+                               static_cast<hipStream_t>(stream)));
     return CGRT_OK;
 }
 
@@ -823,8 +823,8 @@ int combined_intersect(CgrtScene* s, const CgrtRay* rays, uint32_t n, CgrtHit* h
         int rc = CGRT_OK;
         hipError_t e = hipSetDevice(s->device);
         if (e == hipSuccess)
-            e = launch_trace_batch(s->dev, static_cast<const float*>(r.dev), cnt, reinterpret_cast<CgrtHitDev*>(static_cast<char*>(r.dev) + off_hits),
-                                   reinterpret_cast<float*>(static_cast<char*>(r.dev) + off_nrm), nullptr, r.stream);
+            e = launch_trace_batch(s->dev, RayList{static_cast<const float*>(r.dev), cnt, reinterpret_cast<CgrtHitDev*>(static_cast<char*>(r.dev) + off_hits),
+                                                   reinterpret_cast<float*>(static_cast<char*>(r.dev) + off_nrm)}, nullptr, r.stream);
         cb.ns_launch.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_closed).count(),
                                std::memory_order_relaxed);
         if (e == hipSuccess) {
@@ -1502,10 +1502,10 @@ int cgrt_debug_trace_shadow(CgrtScene* s, const CgrtRay* rays, const float* dist
     const uint32_t words[2] = {how >= 1 ? (uint32_t)(n / dmul) : 0u, (uint32_t)nmirror};
     HIP_TRY(hipMemcpy(dc.p, words, sizeof(words), hipMemcpyHostToDevice));
     uint32_t* const dcount = dc.as<uint32_t>();
-    if (how == 0) {
-        HIP_TRY(launch_trace_shadow(s->dev, dr.as<float>(), dd.as<float>(), n, dh.as<CgrtHitDev>(), nullptr));
-    } else if (how == 1) {
-        HIP_TRY(launch_trace_shadow(s->dev, dr.as<float>(), dd.as<float>(), cap, dh.as<CgrtHitDev>(), nullptr, dcount, nullptr, expected, dmul));
+    const ShadowList shadows = how == 0 ? ShadowList{dr.as<float>(), dd.as<float>(), n, dh.as<CgrtHitDev>()}
+                                        : ShadowList{dr.as<float>(), dd.as<float>(), cap, dh.as<CgrtHitDev>(), dcount, dmul, expected};
+    if (how <= 1) {
+        HIP_TRY(launch_trace_shadow(s->dev, shadows, nullptr, nullptr));
     } else {
         HIP_TRY(mr.alloc(mcap * sizeof(CgrtRay)));
         HIP_TRY(mh.alloc(mcap * sizeof(CgrtHit)));
@@ -1514,8 +1514,7 @@ int cgrt_debug_trace_shadow(CgrtScene* s, const CgrtRay* rays, const float* dist
         HIP_TRY(hipMemset(mh.p, 0xA5, mcap * sizeof(CgrtHit)));
         HIP_TRY(hipMemset(mn.p, 0xA5, mcap * 12));
         HIP_TRY(hipMemcpy(mr.p, mirror_rays, nmirror * sizeof(CgrtRay), hipMemcpyHostToDevice));
-        HIP_TRY(launch_trace_pair(s->dev, dr.as<float>(), dd.as<float>(), cap, dh.as<CgrtHitDev>(), dcount, dmul, expected, mr.as<float>(), mcap,
-                                  mh.as<CgrtHitDev>(), mn.as<float>(), dcount + 1, mirror_expected, nullptr));
+        HIP_TRY(launch_trace_pair(s->dev, shadows, RayList{mr.as<float>(), mcap, mh.as<CgrtHitDev>(), mn.as<float>(), dcount + 1, mirror_expected}, nullptr));
     }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(hits, dh.p, cap * sizeof(CgrtHit), hipMemcpyDeviceToHost));
@@ -1576,7 +1575,7 @@ int cgrt_count_batch(CgrtScene* s, const CgrtRay* rays, uint64_t n, CgrtCounters
     HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
     HIP_TRY(c.scratch(1, n * sizeof(CgrtHit), &dh));
     HIP_TRY(c.zero_counters(8));
-    HIP_TRY(launch_trace_batch(s->dev, static_cast<const float*>(dr), n, static_cast<CgrtHitDev*>(dh), nullptr, c.counters(), c.stream()));
+    HIP_TRY(launch_trace_batch(s->dev, RayList{static_cast<const float*>(dr), n, static_cast<CgrtHitDev*>(dh), nullptr}, c.counters(), c.stream()));
     HIP_TRY(c.read_counters(&out->rays, 8));
     return CGRT_OK;
 }
@@ -2051,26 +2050,25 @@ static int render_impl(CgrtScene* s, const FrameRequest& R) {
         bool tail_on_aux = false;
         const LevelDev V1 = ws.level(1);
         if (paired) {
-            HIP_TRY(launch_trace_pair(s->dev, V0.srays, V0.sdist, cap0 * L, V0.shits, pair, L, (unsigned long long)P.counts[0] * L, V1.rays, cap_of(1), V1.hits,
-                                      V1.normals, pair + 1, P.counts[1], nullptr));
+            HIP_TRY(launch_trace_pair(s->dev, V0.shadow_list(cap0 * L, pair, L, (unsigned long long)P.counts[0] * L), V0.mirror_list(cap_of(1), pair + 1, P.counts[1]),
+                                      nullptr));
         } else {
             HIP_TRY(hipEventRecord(aux.spawned, nullptr));
             if (L)  // (hits x lights rays)
-                HIP_TRY(launch_trace_shadow(s->dev, V0.srays, V0.sdist, cap0 * L, V0.shits, nullptr, pair, nullptr, (unsigned long long)P.counts[0] * L, L));
+                HIP_TRY(launch_trace_shadow(s->dev, V0.shadow_list(cap0 * L, pair, L, (unsigned long long)P.counts[0] * L), nullptr, nullptr));
         }
         if (np >= 2) {  // level 1 (and, unpaired, level 0's mirror list in front of it)
             const unsigned long long cap1 = cap_of(1);
             if (!paired) {
                 HIP_TRY(hipStreamWaitEvent(aux.s, aux.spawned, 0));
-                HIP_TRY(launch_trace_batch(s->dev, V1.rays, cap1, V1.hits, V1.normals, nullptr, aux.s, pair + 1, P.counts[1]));
+                HIP_TRY(launch_trace_batch(s->dev, V0.mirror_list(cap1, pair + 1, P.counts[1]), nullptr, aux.s));
             }
             HIP_TRY(launch_spawn(V1, K, cap1, side, pair + 1));
             if (L)
-                HIP_TRY(launch_trace_shadow(s->dev, V1.srays, V1.sdist, cap1 * L, V1.shits, side, V1.counters + 0, nullptr,
-                                            (unsigned long long)P.counts[1] * L));
+                HIP_TRY(launch_trace_shadow(s->dev, V1.shadow_list(cap1 * L, V1.counters + 0, 1, (unsigned long long)P.counts[1] * L), nullptr, side));
             HIP_TRY(launch_shade(V1, K, cap1, side, pair + 1));
             if (np >= 3)
-                HIP_TRY(launch_trace_batch(s->dev, V1.next_rays, cap_of(2), V1.next_hits, V1.next_normals, nullptr, side, V1.counters + 1, P.counts[2]));
+                HIP_TRY(launch_trace_batch(s->dev, V1.mirror_list(cap_of(2), V1.counters + 1, P.counts[2]), nullptr, side));
             if (!paired) HIP_TRY(hipEventRecord(aux.traced, aux.s));
         }
         HIP_TRY(launch_shade(V0, K, cap0, nullptr, pair));
@@ -2092,12 +2090,10 @@ static int render_impl(CgrtScene* s, const FrameRequest& R) {
             const unsigned long long cap = cap_of(level);
             HIP_TRY(launch_spawn(V, K, cap, nullptr, count_of(level)));
             if (L)
-                HIP_TRY(launch_trace_shadow(s->dev, V.srays, V.sdist, cap * L, V.shits, nullptr, V.counters + 0, nullptr,
-                                            (unsigned long long)P.counts[level] * L));
+                HIP_TRY(launch_trace_shadow(s->dev, V.shadow_list(cap * L, V.counters + 0, 1, (unsigned long long)P.counts[level] * L), nullptr, nullptr));
             HIP_TRY(launch_shade(V, K, cap, nullptr, count_of(level)));
             if (level + 1 < np)
-                HIP_TRY(launch_trace_batch(s->dev, V.next_rays, cap_of(level + 1), V.next_hits, V.next_normals, nullptr, nullptr, V.counters + 1,
-                                           P.counts[level + 1]));
+                HIP_TRY(launch_trace_batch(s->dev, V.mirror_list(cap_of(level + 1), V.counters + 1, P.counts[level + 1]), nullptr, nullptr));
         }
         for (int level = np - 2; level >= 1; level--) HIP_TRY(launch_fold(ws.level(level), cap_of(level), nullptr, count_of(level)));
         HIP_TRY(launch_write_rgb(V0, K, np >= 2, cap0, tail, pair));
@@ -2210,20 +2206,20 @@ static int render_impl(CgrtScene* s, const FrameRequest& R) {
                 // level 1's tail overlaps level 0's.  Deeper levels are small and often empty: they run one after the other,
                 // exactly sized after each level's read-back, or not at all.
                 // the level's shadow list first: the long pole of the default stream must not wait behind the second stream's launches
-                if (L) HIP_TRY(launch_trace_shadow(s->dev, V.srays, V.sdist, cnt * L, V.shits, nullptr, ctr + 0, cw_shadow));
+                if (L) HIP_TRY(launch_trace_shadow(s->dev, V.shadow_list(cnt * L, ctr + 0), cw_shadow, nullptr));
                 const bool overlap = spawn && level == 0;
                 const bool pipelined = overlap && SL == 0;
                 const int spawn1 = 2 < max_level;
                 if (overlap) {  // (level 0: aux.spawned was recorded right behind the spawn kernel)
                     HIP_TRY(hipStreamWaitEvent(aux.s, aux.spawned, 0));
-                    HIP_TRY(launch_trace_batch(s->dev, V.next_rays, cnt, V.next_hits, V.next_normals, cw_mirror, aux.s, ctr + 1));
+                    HIP_TRY(launch_trace_batch(s->dev, V.mirror_list(cnt, ctr + 1), cw_mirror, aux.s));
                     if (pipelined) {
                         const LevelDev V1 = ws.level(1);
                         HIP_TRY(launch_spawn(V1, K, cnt, aux.s, ctr + 1));
-                        if (L) HIP_TRY(launch_trace_shadow(s->dev, V1.srays, V1.sdist, cnt * L, V1.shits, aux.s, V1.counters + 0, cw_shadow));
+                        if (L) HIP_TRY(launch_trace_shadow(s->dev, V1.shadow_list(cnt * L, V1.counters + 0), cw_shadow, aux.s));
                         HIP_TRY(shade(V1, cnt, aux.s, ctr + 1));
                         if (spawn1)
-                            HIP_TRY(launch_trace_batch(s->dev, V1.next_rays, cnt, V1.next_hits, V1.next_normals, cw_mirror, aux.s, V1.counters + 1));
+                            HIP_TRY(launch_trace_batch(s->dev, V1.mirror_list(cnt, V1.counters + 1), cw_mirror, aux.s));
                     }
                     HIP_TRY(hipEventRecord(aux.traced, aux.s));
                 }
@@ -2272,7 +2268,7 @@ static int render_impl(CgrtScene* s, const FrameRequest& R) {
                     level = 2;
                     continue;
                 }
-                if (!overlap) HIP_TRY(launch_trace_batch(s->dev, V.next_rays, h[1], V.next_hits, V.next_normals, cw_mirror, nullptr));
+                if (!overlap) HIP_TRY(launch_trace_batch(s->dev, V.mirror_list(h[1], nullptr), cw_mirror, nullptr));
                 cnt = h[1];
                 level += 1;
             }
@@ -2842,7 +2838,7 @@ int cgrt_shade_rays(CgrtScene* s, const CgrtRay* rays, uint64_t n, const float* 
 // ---- enqueued frames (include/cgrt.h cgrt_enqueue_*) ----
 // The frame of render_impl's exact path, issued without a host round trip: every list is sized for the worst case (as render_impl
 // sizes the workspace anyway), all max_level levels are issued, and every launch after the primary kernel is a capped, count-driven grid
-// (GRID_STRIDED and the *_strided launchers) that reads its list's length on the device.  A single camera's level 0 is spawned by the primary kernel
+// (GRID_STRIDED) that reads its list's length on the device.  A single camera's level 0 is spawned by the primary kernel
 // itself (the predicted frame's fused spawn); views and ray lists run their own primary kernels and a count-driven spawn.  The whole
 // frame, export included, is on the caller's stream, behind the scene's previous frames (enq_done, export_done), and nothing is waited
 // for on the host unless the workspace grows or every ticket slot is in flight.  Same kernels' expressions on the same entries, each
@@ -2975,17 +2971,16 @@ static int enqueue_impl(CgrtScene* s, const FrameRequest& R) {
                 const uint32_t* sdc = fused0 ? pair : V.counters;
                 const unsigned sdmul = fused0 ? L : 1u;
                 if (L && V.spawn && pairable) {
-                    HIP_TRY(launch_trace_pair_strided(s->dev, V.srays, V.sdist, n * L, V.shits, sdc, sdmul, V.next_rays, n, V.next_hits, V.next_normals,
-                                                      mirrors_of(level), stream));
+                    HIP_TRY(launch_trace_pair(s->dev, V.shadow_list(n * L, sdc, sdmul), V.mirror_list(n, mirrors_of(level)), stream, GRID_STRIDED));
                 } else {
-                    if (L) HIP_TRY(launch_trace_shadow_strided(s->dev, V.srays, V.sdist, n * L, V.shits, stream, sdc, sdmul));
-                    if (V.spawn) HIP_TRY(launch_trace_batch_strided(s->dev, V.next_rays, n, V.next_hits, V.next_normals, stream, mirrors_of(level)));
+                    if (L) HIP_TRY(launch_trace_shadow(s->dev, V.shadow_list(n * L, sdc, sdmul), nullptr, stream, GRID_STRIDED));
+                    if (V.spawn) HIP_TRY(launch_trace_batch(s->dev, V.mirror_list(n, mirrors_of(level)), nullptr, stream, GRID_STRIDED));
                 }
                 if (SL) {
                     Q.level = (uint32_t)level;
                     HIP_TRY(hipMemsetAsync(ws.lit.p, 0, n * SL * 4, stream));
-                    HIP_TRY(launch_soft_shadow_strided(s->dev, Q, V.rays, V.hits, V.pixels, n, count_of(level), ws.lit.as<uint32_t>(),
-                                                       soft->closest_hit == 0, stream));
+                    HIP_TRY(launch_soft_shadow(s->dev, Q, V.rays, V.hits, V.pixels, n, ws.lit.as<uint32_t>(), soft->closest_hit == 0, stream, count_of(level),
+                                               GRID_STRIDED));
                 }
                 if (sets)
                     HIP_TRY(launch_shade_sets(V, K, T, n, stream, count_of(level), GRID_STRIDED));
@@ -2993,13 +2988,11 @@ static int enqueue_impl(CgrtScene* s, const FrameRequest& R) {
                     HIP_TRY(launch_shade(V, K, n, stream, count_of(level), GRID_STRIDED));
             }
             for (int level = max_level - 2; level >= 1; level--) {
-                if (sets)
-                    HIP_TRY(launch_fold_sets_strided(ws.level(level), n, stream, count_of(level)));
-                else
-                    HIP_TRY(launch_fold(ws.level(level), n, stream, count_of(level), GRID_STRIDED));
+                const LevelDev V = ws.level(level);
+                HIP_TRY(sets ? launch_fold_sets(V, n, stream, count_of(level), GRID_STRIDED) : launch_fold(V, n, stream, count_of(level), GRID_STRIDED));
             }
-            if (sets)
-                HIP_TRY(launch_write_rgb_views_sets_strided(V0, K, max_level >= 2, n, stream, count_of(0)));
+            if (sets)  // (an enqueued batch of sets is a multi-view one)
+                HIP_TRY(launch_write_rgb_sets(V0, K, true, max_level >= 2, n, stream, count_of(0), GRID_STRIDED));
             else
                 HIP_TRY(launch_write_rgb(V0, K, max_level >= 2, n, stream, count_of(0), GRID_STRIDED));
         }
@@ -3010,7 +3003,7 @@ static int enqueue_impl(CgrtScene* s, const FrameRequest& R) {
         if (R.aov) {  // (max_level >= 1: level 0's length is the word the primary kernel counted into)
             const AovDev A = aov_of(*R.aov, F, W, H, nviews, R.rank, R.nranks);
             HIP_TRY(launch_aov_fill(A, stream));
-            HIP_TRY(launch_aov_scatter_strided(A, V0, mats, n, stream, fused ? pair : primary_hits));
+            HIP_TRY(launch_aov_scatter(A, V0, mats, n, stream, fused ? pair : primary_hits, GRID_STRIDED));
         }
         HIP_TRY(hipMemcpyAsync(slot.pin_ctr, ws.ctr.p, S.nctr * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     }

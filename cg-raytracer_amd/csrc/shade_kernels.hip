@@ -748,32 +748,25 @@ hipError_t launch_aov_fill(const AovDev& A, hipStream_t s) {
     hipLaunchKernelGGL(k_aov_fill, dim3(grid_for(n, 256)), dim3(256), 0, s, A);
     return hipGetLastError();
 }
-// the count-driven forms: at most strided_waves() waves per launch (trace_kernels.hip), whatever the capacity n
-static inline unsigned strided_grid(unsigned long long n, unsigned block) {
-    const unsigned cap = (unsigned)std::max<unsigned long long>(1ull, (unsigned long long)strided_waves() * 64ull / block);
-    const unsigned full = grid_for(n, block);
-    return full < cap ? full : cap;
-}
-// KERNEL with one thread per entry of the list's n, or KERNEL_strided (the same parameters) with a capped grid, as `grid` says
+// KERNEL with one thread per entry of the list's n, or KERNEL_strided (the same parameters) with a capped grid (strided_blocks,
+// trace_kernels.hip: at most strided_waves() waves, whatever the capacity n), as `grid` says
 #define LAUNCH_LIST(KERNEL, block, ...)                                                                         \
     do {                                                                                                        \
         if (grid == GRID_STRIDED)                                                                               \
-            hipLaunchKernelGGL(KERNEL##_strided, dim3(strided_grid(n, block)), dim3(block), 0, s, __VA_ARGS__); \
+            hipLaunchKernelGGL(KERNEL##_strided, dim3(strided_blocks(grid_for(n, block), block)), dim3(block), 0, s, __VA_ARGS__); \
         else                                                                                                    \
             hipLaunchKernelGGL(KERNEL, dim3(grid_for(n, block)), dim3(block), 0, s, __VA_ARGS__);               \
     } while (0)
 static inline const float4* f4(const float* p) { return reinterpret_cast<const float4*>(p); }
 static inline float4* f4(float* p) { return reinterpret_cast<float4*>(p); }
 
-hipError_t launch_aov_scatter(const AovDev& A, const LevelDev& V0, const float* materials, unsigned long long n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_aov_scatter, dim3(grid_for(n, 256)), dim3(256), 0, s, A, V0.rays, V0.hits, V0.normals, V0.pixels, materials, n);
-    return hipGetLastError();
-}
-hipError_t launch_aov_scatter_strided(const AovDev& A, const LevelDev& V0, const float* materials, unsigned long long n, hipStream_t s,
-                                      const uint32_t* dcount) {
-    if (n)
-        hipLaunchKernelGGL(k_aov_scatter_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, A, V0.rays, V0.hits, V0.normals, V0.pixels, materials, n,
+hipError_t launch_aov_scatter(const AovDev& A, const LevelDev& V0, const float* materials, unsigned long long n, hipStream_t s, const uint32_t* dcount,
+                              ListGrid grid) {
+    if (n && grid == GRID_STRIDED)
+        hipLaunchKernelGGL(k_aov_scatter_strided, dim3(strided_blocks(grid_for(n, 256), 256)), dim3(256), 0, s, A, V0.rays, V0.hits, V0.normals, V0.pixels, materials, n,
                            dcount);
+    else if (n)
+        hipLaunchKernelGGL(k_aov_scatter, dim3(grid_for(n, 256)), dim3(256), 0, s, A, V0.rays, V0.hits, V0.normals, V0.pixels, materials, n);
     return hipGetLastError();
 }
 
@@ -807,33 +800,29 @@ hipError_t launch_shade_sets(const LevelDev& V, const FrameConst& K, const SetsD
                     K.samples, T, f4(V.sets), V.stride, dcount);
     return hipGetLastError();
 }
-hipError_t launch_fold_sets(const LevelDev& V, unsigned long long n, hipStream_t s) {
-    if (n && V.nsets)
+// the sets' forms: one grid row for every set, or (GRID_STRIDED) one capped grid whose threads loop over the sets
+hipError_t launch_fold_sets(const LevelDev& V, unsigned long long n, hipStream_t s, const uint32_t* dcount, ListGrid grid) {
+    if (n && V.nsets && grid == GRID_STRIDED)
+        hipLaunchKernelGGL(k_fold_sets_strided, dim3(strided_blocks(grid_for(n, 256), 256)), dim3(256), 0, s, f4(V.lvl), f4(V.sets), f4(V.child_sets), n, V.stride, V.nsets,
+                           dcount);
+    else if (n && V.nsets)
         hipLaunchKernelGGL(k_fold_sets, dim3(grid_for(n, 256), V.nsets), dim3(256), 0, s, f4(V.lvl), f4(V.sets), f4(V.child_sets), n, V.stride);
     return hipGetLastError();
 }
-hipError_t launch_write_rgb_sets(const LevelDev& V0, const FrameConst& K, bool views, bool with_child, unsigned long long n, hipStream_t s) {
+hipError_t launch_write_rgb_sets(const LevelDev& V0, const FrameConst& K, bool views, bool with_child, unsigned long long n, hipStream_t s,
+                                 const uint32_t* dcount, ListGrid grid) {
+    if (grid == GRID_STRIDED && !views) return hipErrorInvalidValue;  // (no such kernel: an enqueued batch of sets is a multi-view one)
     if (n && V0.nsets) {
-        const dim3 grid(grid_for(n, 256), V0.nsets);
+        const dim3 rows(grid_for(n, 256), V0.nsets);
         const float4* const child = with_child ? f4(V0.child_sets) : nullptr;
-        if (views)
-            hipLaunchKernelGGL(k_write_rgb_views_sets, grid, dim3(256), 0, s, f4(V0.lvl), f4(V0.sets), child, n, V0.stride, V0.pixels, K.rgb, K.frame_pixels);
+        if (grid == GRID_STRIDED)
+            hipLaunchKernelGGL(k_write_rgb_views_sets_strided, dim3(strided_blocks(grid_for(n, 256), 256)), dim3(256), 0, s, f4(V0.lvl), f4(V0.sets), child, n, V0.stride,
+                               V0.nsets, V0.pixels, K.rgb, K.frame_pixels, dcount);
+        else if (views)
+            hipLaunchKernelGGL(k_write_rgb_views_sets, rows, dim3(256), 0, s, f4(V0.lvl), f4(V0.sets), child, n, V0.stride, V0.pixels, K.rgb, K.frame_pixels);
         else
-            hipLaunchKernelGGL(k_write_rgb_sets, grid, dim3(256), 0, s, f4(V0.lvl), f4(V0.sets), child, n, V0.stride, V0.pixels, K.rgb, K.frame_pixels);
+            hipLaunchKernelGGL(k_write_rgb_sets, rows, dim3(256), 0, s, f4(V0.lvl), f4(V0.sets), child, n, V0.stride, V0.pixels, K.rgb, K.frame_pixels);
     }
-    return hipGetLastError();
-}
-hipError_t launch_fold_sets_strided(const LevelDev& V, unsigned long long n, hipStream_t s, const uint32_t* dcount) {
-    if (n && V.nsets)
-        hipLaunchKernelGGL(k_fold_sets_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, f4(V.lvl), f4(V.sets), f4(V.child_sets), n, V.stride, V.nsets,
-                           dcount);
-    return hipGetLastError();
-}
-hipError_t launch_write_rgb_views_sets_strided(const LevelDev& V0, const FrameConst& K, bool with_child, unsigned long long n, hipStream_t s,
-                                               const uint32_t* dcount) {
-    if (n && V0.nsets)
-        hipLaunchKernelGGL(k_write_rgb_views_sets_strided, dim3(strided_grid(n, 256)), dim3(256), 0, s, f4(V0.lvl), f4(V0.sets),
-                           with_child ? f4(V0.child_sets) : nullptr, n, V0.stride, V0.nsets, V0.pixels, K.rgb, K.frame_pixels, dcount);
     return hipGetLastError();
 }
 

@@ -42,6 +42,32 @@ struct SetsDev {
     uint32_t nsets;
 };
 
+// How a launch covers its list of n entries.  GRID_FULL: one thread per entry; with dcount (optional: the device word with the list's
+// length) n is the capacity the grid covers and the kernel stops at *dcount.  GRID_STRIDED (enqueued frames):
+// dcount is required, and at most strided_waves() waves stride over the *dcount entries present, in the shape the full grid has (a forced
+// quad shape: the full grid itself), with the full grid's results.  A combination without a kernel is hipErrorInvalidValue.
+enum ListGrid { GRID_FULL, GRID_STRIDED };
+unsigned strided_waves();
+unsigned strided_blocks(unsigned full, unsigned block);  // workgroups of a GRID_STRIDED launch whose full grid has `full` of `block` threads
+// A ray list: n rays (the capacity the grid covers), *dcount (optional) of them present; expected (with dcount): the host's estimate of
+// *dcount picks the kernel shape.  A shadow list holds pointInShadow's rays (main.cpp:104-135), *dcount x dmul of them: hits[i] decides
+// `hit && !(t + 0.001f >= dist[i])` like the reference's closest hit does.
+struct RayList {
+    const float* rays;
+    unsigned long long n;
+    CgrtHitDev* hits;
+    float* normals;
+    const uint32_t* dcount;
+    unsigned long long expected;
+};
+struct ShadowList {
+    const float *rays, *dist;
+    unsigned long long n;
+    CgrtHitDev* hits;
+    const uint32_t* dcount;
+    unsigned dmul;  // (0: 1)
+    unsigned long long expected;
+};
 // threads per workgroup the ray-list kernels (batch, soft shadow) are launched with for this scene; frames carry theirs in FrameDev::block
 int trace_block(const SceneDev& S);
 // kernel shape per launch (walk_quad.h): mode -1 = by size (launches of at most max_rays rays take the quad shape), 0 = never, 1 = always;
@@ -58,30 +84,22 @@ hipError_t launch_trace_primary_persistent(const SceneDev& S, const CameraDev& C
 // diagnostic: stamps = 4 x ntiles_rank u64 {memtime start, end, memrealtime start, end} per wave
 hipError_t launch_trace_primary_stamped(const SceneDev& S, const CameraDev& C, const FrameDev& F, CgrtHitDev* hits,
                                         unsigned long long* stamps, hipStream_t stream);
-// dcount (optional): device word with the number of rays actually present (<= n, the capacity the grid is sized for)
-hipError_t launch_trace_batch(const SceneDev& S, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals,
-                              unsigned long long* counters, hipStream_t stream, const uint32_t* dcount = nullptr,
-                              unsigned long long expected = 0);  // expected (with dcount): the host's estimate of *dcount picks the kernel shape
+hipError_t launch_trace_batch(const SceneDev& S, const RayList& R, unsigned long long* counters, hipStream_t stream, ListGrid grid = GRID_FULL);
 // every triangle, no tree (ray_tracing.cpp:202-213); mesh < 0: all meshes + spheres
 hipError_t launch_brute_batch(const SceneDev& S, const float* rays, unsigned long long n, int mesh, CgrtHitDev* hits, float* normals, hipStream_t s);
-// pointInShadow's rays (main.cpp:104-135): hits[i] decides `hit && !(t + 0.001f >= dist[i])` like the reference's closest hit does
-hipError_t launch_trace_shadow(const SceneDev& S, const float* rays, const float* dist, unsigned long long n, CgrtHitDev* hits, hipStream_t stream,
-                               const uint32_t* dcount = nullptr, unsigned long long* counters = nullptr, unsigned long long expected = 0,
-                               unsigned dmul = 1);  // dmul: the list holds *dcount x dmul rays
-// a level's shadow list (srays .. sexpected, as launch_trace_shadow) and its mirror list (rays .. expected, as launch_trace_batch) in ONE
-// launch, workgroups dealt alternately; can_trace_pair: the scene has a fast tree and the forced shape (if any) is a lane shape
+hipError_t launch_trace_shadow(const SceneDev& S, const ShadowList& A, unsigned long long* counters, hipStream_t stream, ListGrid grid = GRID_FULL);
+// a level's two lists in ONE launch, workgroups dealt alternately; can_trace_pair: a fast tree and no forced quad shape
 bool can_trace_pair(const SceneDev& S);
-hipError_t launch_trace_pair(const SceneDev& S, const float* srays, const float* sdist, unsigned long long ns, CgrtHitDev* shits, const uint32_t* sdcount,
-                             unsigned sdmul, unsigned long long sexpected, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals,
-                             const uint32_t* dcount, unsigned long long expected, hipStream_t stream);
+hipError_t launch_trace_pair(const SceneDev& S, const ShadowList& A, const RayList& B, hipStream_t stream, ListGrid grid = GRID_FULL);
 // *flag = value (system scope) once everything queued on the stream before it has finished
 hipError_t launch_signal(uint32_t* flag, uint32_t value, hipStream_t stream);
 hipError_t launch_generate_rays(const CameraDev& C, int W, int H, int x0, int y0, int x1, int y1, float* rays, hipStream_t stream);
 // the rays of a ray camera's whole W x H frame, row-major (cgrt_generate_rays_raycam)
 hipError_t launch_generate_rays_raycam(const RayCameraDev& C, int W, int H, float* rays, hipStream_t stream);
-// lit[item * nlights + l] += samples of spherical light l that reach it from item's hit point (zeroed by the caller)
+// lit[item * nlights + l] += samples of spherical light l that reach item's hit point (zeroed by the caller); GRID_STRIDED light sets: views only
 hipError_t launch_soft_shadow(const SceneDev& S, const SoftDev& Q, const float* rays, const CgrtHitDev* hits, const int* item_pixels,
-                              unsigned long long nitems, uint32_t* lit, int anyhit, hipStream_t stream);
+                              unsigned long long nitems, uint32_t* lit, int anyhit, hipStream_t stream, const uint32_t* dcount = nullptr,
+                              ListGrid grid = GRID_FULL);
 // the same count from the caller's points (npoints x 3 floats), point i sampled as pixel i at level Q.level (cgrt_soft_lit*)
 hipError_t launch_soft_points(const SceneDev& S, const SoftDev& Q, const float* points, unsigned long long npoints, uint32_t* lit, int anyhit,
                               hipStream_t stream);
@@ -107,21 +125,6 @@ hipError_t launch_trace_primary_views_compact(const SceneDev& S, const FrameDev&
 hipError_t launch_trace_list_compact(const SceneDev& S, const float* in_rays, unsigned long long n, float* rays, CgrtHitDev* hits, float* normals,
                                      int* pixels, uint32_t* count, float* rgb, hipStream_t stream, unsigned long long* counters = nullptr);
 hipError_t launch_clear_owned(const FrameDev& F, float* rgb, hipStream_t stream);
-// Capped, count-driven forms (enqueued frames): dcount is required, n is the list's capacity, and the grid covers at
-// most strided_waves() waves (each list of a pair: that many) that stride over the entries present.  The kernel shape is chosen as for
-// the full grid (adapt_max on the device); a forced quad shape takes the full-capacity launch.  Results are the full grid's.
-unsigned strided_waves();
-hipError_t launch_trace_batch_strided(const SceneDev& S, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals, hipStream_t stream,
-                                      const uint32_t* dcount);
-hipError_t launch_trace_shadow_strided(const SceneDev& S, const float* rays, const float* dist, unsigned long long n, CgrtHitDev* hits, hipStream_t stream,
-                                       const uint32_t* dcount, unsigned dmul);
-hipError_t launch_trace_pair_strided(const SceneDev& S, const float* srays, const float* sdist, unsigned long long ns, CgrtHitDev* shits,
-                                     const uint32_t* sdcount, unsigned sdmul, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals,
-                                     const uint32_t* dcount, hipStream_t stream);
-// items: the first *dcount (<= nitems) entries of the level's list (k_soft_shadow_strided; Q.set_index: k_soft_shadow_sets_strided, which
-// needs Q.view_pixels)
-hipError_t launch_soft_shadow_strided(const SceneDev& S, const SoftDev& Q, const float* rays, const CgrtHitDev* hits, const int* item_pixels,
-                                      unsigned long long nitems, const uint32_t* dcount, uint32_t* lit, int anyhit, hipStream_t stream);
 // shading wavefront (shade_kernels.hip); every level is a compact list of live paths
 // One level of it, as the launchers below take it: typed device pointers into the frame's workspace (capi.cpp Wavefront::level -- the
 // only place that knows which buffer set a level lives in).  A plain value, built on the stack per launch group.
@@ -144,6 +147,11 @@ struct LevelDev {
     const float *child_lvl, *child_sets;  // the next level's record and per-set colours (NULL: there is no next level)
     unsigned long long stride;            // entries the lists are sized for
     unsigned nsets;                       // 1 without light sets
+    // its shadow list and its mirror list (the next level's), of capacity n
+    ShadowList shadow_list(unsigned long long n, const uint32_t* dc, unsigned dmul = 1, unsigned long long expected = 0) const {
+        return {srays, sdist, n, shits, dc, dmul, expected};
+    }
+    RayList mirror_list(unsigned long long n, const uint32_t* dc, unsigned long long expected = 0) const { return {next_rays, n, next_hits, next_normals, dc, expected}; }
 };
 // What does not change over a frame.  lights: the point lights k_spawn traces shadow rays to (light sets: the batch's distinct positions,
 // sslot's row); slights: the spherical lights whose samples `lit` counts (light sets: the distinct keys, lit's row).
@@ -157,10 +165,6 @@ struct FrameConst {
     float* rgb;                       // the frame the colours are scattered into
     unsigned long long frame_pixels;  // pixels of one frame in it (light sets, views: W * H)
 };
-// How a launch covers its list of n entries.  GRID_FULL: one thread per entry; with dcount (optional: the device word with the list's
-// length) n is the capacity the grid covers and the kernel stops at *dcount.  GRID_STRIDED (enqueued frames): dcount is required, n is
-// the capacity, and a capped grid strides over the *dcount entries present (the *_strided kernels).
-enum ListGrid { GRID_FULL, GRID_STRIDED };
 // k_spawn: shadow rays of every hit -> the level's shadow list; mirror rays -> the next level's list; lvl[2i+1] = {ks, child}
 hipError_t launch_spawn(const LevelDev& V, const FrameConst& K, unsigned long long n, hipStream_t s, const uint32_t* dcount = nullptr,
                         ListGrid grid = GRID_FULL);
@@ -179,14 +183,11 @@ hipError_t launch_shade_sets(const LevelDev& V, const FrameConst& K, const SetsD
                              const uint32_t* dcount = nullptr, ListGrid grid = GRID_FULL);
 // launch_fold / launch_write_rgb per set (n entries, V.nsets sets of colours V.stride entries apart); set b's frame starts at
 // K.rgb + 3 * b * K.frame_pixels.  views (multi-view light sets, cgrt_render_views_light_sets*: k_write_rgb_views_sets): the pixels are
-// a multi-view frame's (view * frame_pixels + in-view pixel), and set s's colour of a pixel of view v goes to frame v * nsets + s
-hipError_t launch_fold_sets(const LevelDev& V, unsigned long long n, hipStream_t s);
-hipError_t launch_write_rgb_sets(const LevelDev& V0, const FrameConst& K, bool views, bool with_child, unsigned long long n, hipStream_t s);
-// the count-driven forms of the two (enqueued batches; one grid row for every set, so not GRID_STRIDED of the above): n is the list's
-// capacity, *dcount its length
-hipError_t launch_fold_sets_strided(const LevelDev& V, unsigned long long n, hipStream_t s, const uint32_t* dcount);
-hipError_t launch_write_rgb_views_sets_strided(const LevelDev& V0, const FrameConst& K, bool with_child, unsigned long long n, hipStream_t s,
-                                               const uint32_t* dcount);
+// a multi-view frame's (view * frame_pixels + in-view pixel), and set s's colour of a pixel of view v goes to frame v * nsets + s.
+// GRID_STRIDED (one capped grid for every set): the scatter only with views
+hipError_t launch_fold_sets(const LevelDev& V, unsigned long long n, hipStream_t s, const uint32_t* dcount = nullptr, ListGrid grid = GRID_FULL);
+hipError_t launch_write_rgb_sets(const LevelDev& V0, const FrameConst& K, bool views, bool with_child, unsigned long long n, hipStream_t s,
+                                 const uint32_t* dcount = nullptr, ListGrid grid = GRID_FULL);
 // the anti-aliased frame (main.cpp:663-687) from the 2W x 2H sub-sample frame `sub` of F: see k_resolve_aa (shade_kernels.hip).
 // out: F.nst_rank * 1024 * 3 floats (packed) or (F.W / 2) * (F.H / 2) * 3 floats
 hipError_t launch_resolve_aa(const FrameDev& F, const float* sub, float* out, int packed, hipStream_t s);
@@ -223,12 +224,10 @@ struct AovDev {
 };
 // launch_aov_fill (k_aov_fill): the miss values into every owned pixel of every requested plane, in row order.  launch_aov_scatter
 // (k_aov_scatter), behind it on the same stream: entry i < n of level 0 {rays, hits, normals, item_pixels} and its material's kd to pixel
-// item_pixels[i]; position = origin + direction * t in cgrt_math.h's arithmetic.  launch_aov_scatter_strided: n is the list's capacity,
-// *dcount its length, a capped grid strides over the entries present (enqueued frames).
+// item_pixels[i]; position = origin + direction * t in cgrt_math.h's arithmetic.
 hipError_t launch_aov_fill(const AovDev& A, hipStream_t s);
-hipError_t launch_aov_scatter(const AovDev& A, const LevelDev& V0, const float* materials, unsigned long long n, hipStream_t s);
-hipError_t launch_aov_scatter_strided(const AovDev& A, const LevelDev& V0, const float* materials, unsigned long long n, hipStream_t s,
-                                      const uint32_t* dcount);
+hipError_t launch_aov_scatter(const AovDev& A, const LevelDev& V0, const float* materials, unsigned long long n, hipStream_t s,
+                              const uint32_t* dcount = nullptr, ListGrid grid = GRID_FULL);
 hipError_t launch_gather_calib(const void* table, unsigned long long nrecords, unsigned long long mult, unsigned long long add, float* sink,
                                hipStream_t s);
 hipError_t launch_fastdiv_check(const float* a, const float* d, unsigned long long n, unsigned long long* mismatches, float* first_bad,

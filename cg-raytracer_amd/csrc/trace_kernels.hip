@@ -861,16 +861,25 @@ int trace_block(const SceneDev& S) {
     if (forced) return forced;
     return S.fast_root != REF_NONE ? 64 : 256;
 }
-#define CGRT_LAUNCH2(KERNEL, A, fast, grid, block, stream, ...)                                                             \
-    do {                                                                                                                      \
-        if (fast)                                                                                                             \
-            hipLaunchKernelGGL((KERNEL<A, true>), dim3(grid), dim3(block), lds_bytes(block), stream, __VA_ARGS__);           \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((KERNEL<A, false>), dim3(grid), dim3(block), lds_bytes(block), stream, __VA_ARGS__);          \
-    } while (0)
-// the quad shape (walk_quad.h): single-wave workgroups, four lanes per ray
-#define CGRT_LAUNCHQ(KERNEL, A, grid, stream, ...) \
-    hipLaunchKernelGGL((KERNEL<A, true, true>), dim3(grid), dim3(64), lds_bytes(64), stream, __VA_ARGS__)
+// From run-time bools to template arguments: f(std::true_type) or f(std::false_type), so that a generic lambda names its kernel as
+// k<decltype(B)::value, ..>.  A lambda instantiates what it names for both values: `if constexpr` keeps out the combinations no launch
+// takes (quad shapes only FAST, STRIDED only uncounted lane shapes, HINT only <false, true, false, true>).
+template <class F>
+static inline void with_bool(bool b, F&& f) {
+    if (b)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+template <class F>
+static inline void with_bools(bool a, bool b, F&& f) {
+    with_bool(a, [&](auto A) { with_bool(b, [&](auto B) { f(A, B); }); });
+}
+// every traversal kernel takes the LDS of its workgroup size (CGRT_LDS_WORDS)
+template <class K, class... A>
+static inline void launch(K kernel, unsigned grid, unsigned block, hipStream_t stream, const A&... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_bytes(block), stream, args...);
+}
 
 // ---- kernel shape per launch ----
 // How a launch lays its rays out on the lanes (results never depend on it; tests/test_quad_shape_gpu.py):
@@ -932,104 +941,12 @@ bool quad_shape_for(const SceneDev& S, unsigned long long rays) {  // frames: th
     (void)rays;
     return S.fast_root != REF_NONE && trace_block(S) == 64 && shape_mode() == SHAPE_QUAD16;
 }
-
-hipError_t launch_trace_primary(const SceneDev& S, const CameraDev& C, const FrameDev& F, CgrtHitDev* hits, float* normals,
-                                unsigned long long* counters, hipStream_t stream) {
-    if (F.nblocks == 0) return hipSuccess;
-    const bool fast = S.fast_root != REF_NONE;
-    if (F.block == 64 && quad_shape_for(S, (unsigned long long)F.nblocks * 64ull)) {
-        if (counters)
-            CGRT_LAUNCHQ(k_trace_primary, true, 4u * F.nblocks, stream, S, C, F, hits, normals, counters);
-        else
-            CGRT_LAUNCHQ(k_trace_primary, false, 4u * F.nblocks, stream, S, C, F, hits, normals, counters);
-        return hipGetLastError();
-    }
-    if (F.hint && fast && F.block == 64 && !counters) {  // frame hints: the hard list's workgroups come first
-        hipLaunchKernelGGL((k_trace_primary<false, true, false, true>), dim3(F.nblocks + F.hint_blocks), dim3(64), lds_bytes(64), stream, S, C, F, hits,
-                           normals, counters);
-        return hipGetLastError();
-    }
-    if (counters)
-        CGRT_LAUNCH2(k_trace_primary, true, fast, F.nblocks, (unsigned)F.block, stream, S, C, F, hits, normals, counters);
-    else
-        CGRT_LAUNCH2(k_trace_primary, false, fast, F.nblocks, (unsigned)F.block, stream, S, C, F, hits, normals, counters);
-    return hipGetLastError();
-}
 // grid of a list launch in the lane shapes: covers 64 rays per workgroup, and 16 per workgroup up to the adaptive bound
 static unsigned lane_grid(unsigned long long n, unsigned block, unsigned rpw, unsigned adapt_max) {
     if (adapt_max) return std::max(grid_for(n, block), grid_for(std::min<unsigned long long>(n, adapt_max), 16));
     return grid_for(n, rpw < 64u ? rpw : block);
 }
-hipError_t launch_trace_batch(const SceneDev& S, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals,
-                              unsigned long long* counters, hipStream_t stream, const uint32_t* dcount, unsigned long long expected) {
-    if (n == 0) return hipSuccess;
-    const unsigned block = (unsigned)trace_block(S);
-    const bool fast = S.fast_root != REF_NONE;
-    // expected (with dcount): the host's estimate of the device count picks the shape, as an exact length would
-    const unsigned adapt = expected ? 0u : list_adapt_max(S, dcount);
-    const int shape = adapt ? SHAPE_LANE64 : list_shape(S, expected ? expected : n);
-    if (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4) {
-        const unsigned q = shape == SHAPE_QUAD4 ? 4u : 16u;
-        if (counters)
-            CGRT_LAUNCHQ(k_trace_batch, true, grid_for(n, q), stream, S, rays, n, hits, normals, counters, dcount, q, 0u);
-        else
-            CGRT_LAUNCHQ(k_trace_batch, false, grid_for(n, q), stream, S, rays, n, hits, normals, counters, dcount, q, 0u);
-        return hipGetLastError();
-    }
-    const unsigned rpw = shape == SHAPE_LANE16 ? 16u : 64u;
-    const unsigned grid = lane_grid(n, block, rpw, adapt);
-    if (counters)
-        CGRT_LAUNCH2(k_trace_batch, true, fast, grid, block, stream, S, rays, n, hits, normals, counters, dcount, rpw, adapt);
-    else
-        CGRT_LAUNCH2(k_trace_batch, false, fast, grid, block, stream, S, rays, n, hits, normals, counters, dcount, rpw, adapt);
-    return hipGetLastError();
-}
-hipError_t launch_trace_shadow(const SceneDev& S, const float* rays, const float* dist, unsigned long long n, CgrtHitDev* hits, hipStream_t stream,
-                               const uint32_t* dcount, unsigned long long* counters, unsigned long long expected, unsigned dmul) {
-    if (n == 0) return hipSuccess;
-    const unsigned block = (unsigned)trace_block(S);
-    const bool fast = S.fast_root != REF_NONE;
-    const unsigned adapt = expected ? 0u : list_adapt_max(S, dcount);
-    const int shape = adapt ? SHAPE_LANE64 : list_shape(S, expected ? expected : n);
-    if (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4) {
-        const unsigned q = shape == SHAPE_QUAD4 ? 4u : 16u;
-        if (counters)
-            CGRT_LAUNCHQ(k_trace_shadow, true, grid_for(n, q), stream, S, rays, dist, n, hits, dcount, counters, q, 0u, dmul ? dmul : 1u);
-        else
-            CGRT_LAUNCHQ(k_trace_shadow, false, grid_for(n, q), stream, S, rays, dist, n, hits, dcount, counters, q, 0u, dmul ? dmul : 1u);
-        return hipGetLastError();
-    }
-    const unsigned rpw = shape == SHAPE_LANE16 ? 16u : 64u;
-    const unsigned grid = lane_grid(n, block, rpw, adapt);
-    if (counters)
-        CGRT_LAUNCH2(k_trace_shadow, true, fast, grid, block, stream, S, rays, dist, n, hits, dcount, counters, rpw, adapt, dmul ? dmul : 1u);
-    else
-        CGRT_LAUNCH2(k_trace_shadow, false, fast, grid, block, stream, S, rays, dist, n, hits, dcount, counters, rpw, adapt, dmul ? dmul : 1u);
-    return hipGetLastError();
-}
-// The two lists of one level in one launch (k_trace_pair); false when the scene or the forced shape does not allow it -- the caller
-// then launches them one by one.
-bool can_trace_pair(const SceneDev& S) { return S.fast_root != REF_NONE && trace_block(S) == 64 && (shape_mode() == SHAPE_AUTO || shape_mode() == SHAPE_LANE64 || shape_mode() == SHAPE_LANE16); }
-hipError_t launch_trace_pair(const SceneDev& S, const float* srays, const float* sdist, unsigned long long ns, CgrtHitDev* shits, const uint32_t* sdcount,
-                             unsigned sdmul, unsigned long long sexpected, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals,
-                             const uint32_t* dcount, unsigned long long expected, hipStream_t stream) {
-    if (ns == 0 && n == 0) return hipSuccess;
-    auto lane_shape = [&](unsigned long long cap, unsigned long long exp_, const uint32_t* dc, unsigned& rpw, unsigned& adapt, unsigned& blocks) {
-        adapt = exp_ ? 0u : list_adapt_max(S, dc);
-        const int shape = adapt ? SHAPE_LANE64 : list_shape(S, exp_ ? exp_ : cap);
-        rpw = (shape == SHAPE_LANE64) ? 64u : 16u;  // (the quad shapes of a short list: 16 rays per wave here)
-        blocks = cap ? lane_grid(cap, 64u, rpw, adapt) : 0u;
-        if (adapt) rpw = 64u;
-    };
-    ListPairDev P{};
-    P.rays_a = srays, P.dist_a = sdist, P.hits_a = shits, P.dcount_a = sdcount, P.n_a = ns, P.dmul_a = sdmul ? sdmul : 1u;
-    lane_shape(ns, sexpected, sdcount, P.rpw_a, P.adapt_a, P.blocks_a);
-    P.rays_b = rays, P.hits_b = hits, P.normals_b = normals, P.dcount_b = dcount, P.n_b = n;
-    lane_shape(n, expected, dcount, P.rpw_b, P.adapt_b, P.blocks_b);
-    hipLaunchKernelGGL((k_trace_pair<true>), dim3(P.blocks_a + P.blocks_b), dim3(64), lds_bytes(64), stream, S, P);
-    return hipGetLastError();
-}
-// ---- capped, count-driven grids (enqueued frames: capi.cpp enqueue_impl) ----
+// ---- capped, count-driven grids (GRID_STRIDED; enqueued frames: capi.cpp enqueue_impl) ----
 // Every list of an enqueued frame is sized for the worst case and only the device knows its length, so a launch covers at most
 // strided_waves() waves, whatever the capacity, and its workgroups stride over the entries present (the STRIDED instantiations).
 // The default is twice the walk waves the chip holds at once (256 CUs x 4 SIMDs x 3 waves); CGRT_STRIDED_WAVES overrides it.
@@ -1040,183 +957,188 @@ unsigned strided_waves() {
     }();
     return w;
 }
-static unsigned strided_blocks(unsigned full, unsigned block) {
+unsigned strided_blocks(unsigned full, unsigned block) {
     const unsigned cap = std::max(1u, strided_waves() / (block / 64u));
     return std::min(full, cap);
 }
-hipError_t launch_trace_batch_strided(const SceneDev& S, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals, hipStream_t stream,
-                                      const uint32_t* dcount) {
-    if (n == 0) return hipSuccess;
-    const unsigned block = (unsigned)trace_block(S);
-    const bool fast = S.fast_root != REF_NONE;
-    const unsigned adapt = list_adapt_max(S, dcount);
-    const int shape = adapt ? SHAPE_LANE64 : list_shape(S, n);
-    if (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4)  // (forced quad shapes, a checking tool: the full-capacity grid)
-        return launch_trace_batch(S, rays, n, hits, normals, nullptr, stream, dcount);
-    const unsigned rpw = shape == SHAPE_LANE16 ? 16u : 64u;
-    const unsigned grid = strided_blocks(lane_grid(n, block, rpw, adapt), block);
-    if (fast)
-        hipLaunchKernelGGL((k_trace_batch<false, true, false, true>), dim3(grid), dim3(block), lds_bytes(block), stream, S, rays, n, hits, normals, nullptr,
-                           dcount, rpw, adapt);
-    else
-        hipLaunchKernelGGL((k_trace_batch<false, false, false, true>), dim3(grid), dim3(block), lds_bytes(block), stream, S, rays, n, hits, normals, nullptr,
-                           dcount, rpw, adapt);
+// ---- the plan of a list launch: everything the rules above derive from a list of capacity n ----
+// expected (with dcount): the host's estimate of *dcount picks the shape, as an exact length would, and switches adapt off.  GRID_STRIDED
+// ignores it, caps the grid and selects the STRIDED instantiation -- but a quad shape (forced: a checking tool) keeps the full-capacity
+// grid of the quad kernel.  pair (k_trace_pair): one list of the two, 64-thread workgroups, and a quad shape of a short list becomes 16
+// rays per wave.
+struct ListPlan {
+    bool quad;      // QUAD4 / QUAD16: the <.., true, true> instantiation, single-wave workgroups of qrpw rays
+    bool strided;   // the STRIDED instantiation, its grid capped
+    bool fast;      // the scene has a fast tree
+    unsigned qrpw;  // rays per wave: 4 or 16 (quad), 16 or 64 (lane)
+    unsigned adapt;  // list_adapt_max: LANE16 or LANE64 is chosen on the device (then the host's shape is LANE64)
+    unsigned block, grid;
+};
+static ListPlan plan_list(const SceneDev& S, unsigned long long n, const uint32_t* dcount, unsigned long long expected, ListGrid grid,
+                          bool pair = false) {
+    ListPlan p{};
+    if (grid == GRID_STRIDED) expected = 0;
+    p.fast = S.fast_root != REF_NONE;
+    p.adapt = expected ? 0u : list_adapt_max(S, dcount);
+    const int shape = p.adapt ? SHAPE_LANE64 : list_shape(S, expected ? expected : n);
+    p.quad = !pair && (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4);
+    if (p.quad) {
+        p.qrpw = shape == SHAPE_QUAD4 ? 4u : 16u;
+        p.block = 64u;
+        p.grid = grid_for(n, p.qrpw);
+        return p;
+    }
+    p.qrpw = shape == SHAPE_LANE64 ? 64u : 16u;
+    p.block = pair ? 64u : (unsigned)trace_block(S);
+    p.grid = lane_grid(n, p.block, p.qrpw, p.adapt);
+    p.strided = grid == GRID_STRIDED;
+    if (p.strided) p.grid = strided_blocks(p.grid, p.block);
+    return p;
+}
+template <class K, class... A>
+static inline void launch(K kernel, const ListPlan& p, hipStream_t stream, const A&... args) {
+    launch(kernel, p.grid, p.block, stream, args...);
+}
+// a frame's grid: F.nblocks workgroups of F.block threads, or -- the quad shape, when forced -- four single-wave workgroups for each
+struct FramePlan {
+    bool quad, fast;
+    unsigned grid, block;
+};
+static FramePlan plan_frame(const SceneDev& S, const FrameDev& F) {
+    const bool quad = F.block == 64 && quad_shape_for(S, (unsigned long long)F.nblocks * 64ull);
+    return FramePlan{quad, S.fast_root != REF_NONE, quad ? 4u * F.nblocks : F.nblocks, quad ? 64u : (unsigned)F.block};
+}
+
+hipError_t launch_trace_primary(const SceneDev& S, const CameraDev& C, const FrameDev& F, CgrtHitDev* hits, float* normals,
+                                unsigned long long* counters, hipStream_t stream) {
+    if (F.nblocks == 0) return hipSuccess;
+    const FramePlan p = plan_frame(S, F);
+    const bool hint = !p.quad && F.hint && p.fast && F.block == 64 && !counters;  // frame hints: the hard list's workgroups come first
+    with_bools(counters != nullptr, p.fast, [&](auto count, auto fast) {
+        constexpr bool COUNT = decltype(count)::value, FAST = decltype(fast)::value;
+        auto go = [&](auto kernel, unsigned grid) { launch(kernel, grid, p.block, stream, S, C, F, hits, normals, counters); };
+        if constexpr (FAST) {
+            if (p.quad) return go(k_trace_primary<COUNT, true, true>, p.grid);
+            if constexpr (!COUNT) {
+                if (hint) return go(k_trace_primary<false, true, false, true>, F.nblocks + F.hint_blocks);
+            }
+        }
+        go(k_trace_primary<COUNT, FAST>, p.grid);
+    });
     return hipGetLastError();
 }
-hipError_t launch_trace_shadow_strided(const SceneDev& S, const float* rays, const float* dist, unsigned long long n, CgrtHitDev* hits, hipStream_t stream,
-                                       const uint32_t* dcount, unsigned dmul) {
-    if (n == 0) return hipSuccess;
-    const unsigned block = (unsigned)trace_block(S);
-    const bool fast = S.fast_root != REF_NONE;
-    const unsigned adapt = list_adapt_max(S, dcount);
-    const int shape = adapt ? SHAPE_LANE64 : list_shape(S, n);
-    if (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4) return launch_trace_shadow(S, rays, dist, n, hits, stream, dcount, nullptr, 0, dmul);
-    const unsigned rpw = shape == SHAPE_LANE16 ? 16u : 64u;
-    const unsigned grid = strided_blocks(lane_grid(n, block, rpw, adapt), block);
-    if (fast)
-        hipLaunchKernelGGL((k_trace_shadow<false, true, false, true>), dim3(grid), dim3(block), lds_bytes(block), stream, S, rays, dist, n, hits, dcount,
-                           nullptr, rpw, adapt, dmul ? dmul : 1u);
-    else
-        hipLaunchKernelGGL((k_trace_shadow<false, false, false, true>), dim3(grid), dim3(block), lds_bytes(block), stream, S, rays, dist, n, hits, dcount,
-                           nullptr, rpw, adapt, dmul ? dmul : 1u);
+hipError_t launch_trace_batch(const SceneDev& S, const RayList& R, unsigned long long* counters, hipStream_t stream, ListGrid grid) {
+    if (R.n == 0) return hipSuccess;
+    if (grid == GRID_STRIDED && (counters || !R.dcount)) return hipErrorInvalidValue;
+    const ListPlan p = plan_list(S, R.n, R.dcount, R.expected, grid);
+    with_bools(counters != nullptr, p.fast, [&](auto count, auto fast) {
+        constexpr bool COUNT = decltype(count)::value, FAST = decltype(fast)::value;
+        auto go = [&](auto kernel) { launch(kernel, p, stream, S, R.rays, R.n, R.hits, R.normals, counters, R.dcount, p.qrpw, p.adapt); };
+        if constexpr (FAST) {
+            if (p.quad) return go(k_trace_batch<COUNT, true, true>);
+        }
+        if constexpr (!COUNT) {
+            if (p.strided) return go(k_trace_batch<false, FAST, false, true>);
+        }
+        go(k_trace_batch<COUNT, FAST>);
+    });
     return hipGetLastError();
 }
-hipError_t launch_trace_pair_strided(const SceneDev& S, const float* srays, const float* sdist, unsigned long long ns, CgrtHitDev* shits,
-                                     const uint32_t* sdcount, unsigned sdmul, const float* rays, unsigned long long n, CgrtHitDev* hits, float* normals,
-                                     const uint32_t* dcount, hipStream_t stream) {
-    if (ns == 0 || n == 0) return hipErrorInvalidValue;  // (the caller pairs two lists that both have a capacity)
-    auto lane_shape = [&](unsigned long long cap, const uint32_t* dc, unsigned& rpw, unsigned& adapt, unsigned& blocks) {
-        adapt = list_adapt_max(S, dc);
-        const int shape = adapt ? SHAPE_LANE64 : list_shape(S, cap);
-        rpw = (shape == SHAPE_LANE64) ? 64u : 16u;
-        blocks = strided_blocks(lane_grid(cap, 64u, rpw, adapt), 64u);  // (each list gets the cap: the two share the chip)
-        if (adapt) rpw = 64u;
-    };
+hipError_t launch_trace_shadow(const SceneDev& S, const ShadowList& A, unsigned long long* counters, hipStream_t stream, ListGrid grid) {
+    if (A.n == 0) return hipSuccess;
+    if (grid == GRID_STRIDED && (counters || !A.dcount)) return hipErrorInvalidValue;
+    const ListPlan p = plan_list(S, A.n, A.dcount, A.expected, grid);
+    const unsigned dmul = A.dmul ? A.dmul : 1u;
+    with_bools(counters != nullptr, p.fast, [&](auto count, auto fast) {
+        constexpr bool COUNT = decltype(count)::value, FAST = decltype(fast)::value;
+        auto go = [&](auto kernel) { launch(kernel, p, stream, S, A.rays, A.dist, A.n, A.hits, A.dcount, counters, p.qrpw, p.adapt, dmul); };
+        if constexpr (FAST) {
+            if (p.quad) return go(k_trace_shadow<COUNT, true, true>);
+        }
+        if constexpr (!COUNT) {
+            if (p.strided) return go(k_trace_shadow<false, FAST, false, true>);
+        }
+        go(k_trace_shadow<COUNT, FAST>);
+    });
+    return hipGetLastError();
+}
+// The two lists of one level in one launch (k_trace_pair); false when the scene or the forced shape does not allow it -- the caller
+// then launches them one by one.
+bool can_trace_pair(const SceneDev& S) { return S.fast_root != REF_NONE && trace_block(S) == 64 && (shape_mode() == SHAPE_AUTO || shape_mode() == SHAPE_LANE64 || shape_mode() == SHAPE_LANE16); }
+// GRID_FULL: a list of capacity 0 takes no workgroups.  GRID_STRIDED: the caller pairs two lists that both have a capacity, and each
+// list gets the cap (the two share the chip).
+hipError_t launch_trace_pair(const SceneDev& S, const ShadowList& A, const RayList& B, hipStream_t stream, ListGrid grid) {
+    if (grid == GRID_STRIDED ? (A.n == 0 || B.n == 0) : (A.n == 0 && B.n == 0)) return grid == GRID_STRIDED ? hipErrorInvalidValue : hipSuccess;
+    const ListPlan a = plan_list(S, A.n, A.dcount, A.expected, grid, true), b = plan_list(S, B.n, B.dcount, B.expected, grid, true);
     ListPairDev P{};
-    P.rays_a = srays, P.dist_a = sdist, P.hits_a = shits, P.dcount_a = sdcount, P.n_a = ns, P.dmul_a = sdmul ? sdmul : 1u;
-    lane_shape(ns, sdcount, P.rpw_a, P.adapt_a, P.blocks_a);
-    P.rays_b = rays, P.hits_b = hits, P.normals_b = normals, P.dcount_b = dcount, P.n_b = n;
-    lane_shape(n, dcount, P.rpw_b, P.adapt_b, P.blocks_b);
-    hipLaunchKernelGGL((k_trace_pair<true, true>), dim3(P.blocks_a + P.blocks_b), dim3(64), lds_bytes(64), stream, S, P);
-    return hipGetLastError();
-}
-hipError_t launch_soft_shadow_strided(const SceneDev& S, const SoftDev& Q, const float* rays, const CgrtHitDev* hits, const int* item_pixels,
-                                      unsigned long long nitems, const uint32_t* dcount, uint32_t* lit, int anyhit, hipStream_t stream) {
-    const unsigned long long nthreads = nitems * Q.nlights * Q.samples;
-    if (nthreads == 0) return hipSuccess;
-    const unsigned block = (unsigned)trace_block(S);
-    const unsigned long long full = (nthreads + block - 1) / block;
-    const unsigned grid = strided_blocks((unsigned)std::min<unsigned long long>(full, 0x7fffffffull), block);
-    const bool fast = S.fast_root != REF_NONE, views = Q.view_pixels != 0;
-    if (Q.set_index) {  // an enqueued batch of light sets (k_soft_shadow_sets_strided; its items are always a multi-view frame's)
-        if (!views) return hipErrorInvalidValue;
-        if (anyhit)
-            CGRT_LAUNCH2(k_soft_shadow_sets_strided, true, fast, grid, block, stream, S, Q, rays, hits, item_pixels, nitems, dcount, lit);
-        else
-            CGRT_LAUNCH2(k_soft_shadow_sets_strided, false, fast, grid, block, stream, S, Q, rays, hits, item_pixels, nitems, dcount, lit);
-        return hipGetLastError();
-    }
-#define CGRT_SOFT_STRIDED(A, F, V)                                                                                                                 \
-    hipLaunchKernelGGL((k_soft_shadow_strided<A, F, V>), dim3(grid), dim3(block), lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nitems, \
-                       dcount, lit)
-    if (views) {
-        if (anyhit && fast) CGRT_SOFT_STRIDED(true, true, true);
-        else if (anyhit) CGRT_SOFT_STRIDED(true, false, true);
-        else if (fast) CGRT_SOFT_STRIDED(false, true, true);
-        else CGRT_SOFT_STRIDED(false, false, true);
-    } else {
-        if (anyhit && fast) CGRT_SOFT_STRIDED(true, true, false);
-        else if (anyhit) CGRT_SOFT_STRIDED(true, false, false);
-        else if (fast) CGRT_SOFT_STRIDED(false, true, false);
-        else CGRT_SOFT_STRIDED(false, false, false);
-    }
-#undef CGRT_SOFT_STRIDED
+    P.rays_a = A.rays, P.dist_a = A.dist, P.hits_a = A.hits, P.dcount_a = A.dcount, P.n_a = A.n, P.dmul_a = A.dmul ? A.dmul : 1u;
+    P.rpw_a = a.qrpw, P.adapt_a = a.adapt, P.blocks_a = a.grid;
+    P.rays_b = B.rays, P.hits_b = B.hits, P.normals_b = B.normals, P.dcount_b = B.dcount, P.n_b = B.n;
+    P.rpw_b = b.qrpw, P.adapt_b = b.adapt, P.blocks_b = b.grid;
+    with_bool(grid == GRID_STRIDED, [&](auto strided) { launch(k_trace_pair<true, decltype(strided)::value>, P.blocks_a + P.blocks_b, 64u, stream, S, P); });
     return hipGetLastError();
 }
 hipError_t launch_trace_primary_compact(const SceneDev& S, const CameraDev& C, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals,
                                         int* pixels, uint32_t* count, hipStream_t stream, unsigned long long* counters, float* rgb,
-                                        const SpawnDev* spawn) {
-    const SpawnDev* SP = spawn;  // (a DEVICE address)
+                                        const SpawnDev* spawn) {  // (spawn: a DEVICE address)
     if (F.nblocks == 0) return hipSuccess;
-    const unsigned block = (unsigned)F.block;
-    const bool fast = S.fast_root != REF_NONE;
-    if (F.block == 64 && quad_shape_for(S, (unsigned long long)F.nblocks * 64ull)) {
-        if (counters)
-            CGRT_LAUNCHQ(k_trace_primary_compact, true, 4u * F.nblocks, stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
-        else
-            CGRT_LAUNCHQ(k_trace_primary_compact, false, 4u * F.nblocks, stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
-        return hipGetLastError();
-    }
-    if (counters)
-        CGRT_LAUNCH2(k_trace_primary_compact, true, fast, F.nblocks, block, stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
-    else
-        CGRT_LAUNCH2(k_trace_primary_compact, false, fast, F.nblocks, block, stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
+    const FramePlan p = plan_frame(S, F);
+    with_bools(counters != nullptr, p.fast, [&](auto c, auto fast) {
+        constexpr bool COUNT = decltype(c)::value, FAST = decltype(fast)::value;
+        auto go = [&](auto kernel) { launch(kernel, p.grid, p.block, stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, spawn); };
+        if constexpr (FAST) {
+            if (p.quad) return go(k_trace_primary_compact<COUNT, true, true>);
+        }
+        go(k_trace_primary_compact<COUNT, FAST>);
+    });
     return hipGetLastError();
 }
 // Multi-view frames: the VIEWS instantiations (no counters, no hints), in the shape a single frame of the same workgroup size takes.
 // raycams: F.raycams is set instead of F.views (the RAYCAM instantiations).
-template <bool RAYCAM>
-static hipError_t launch_views(const SceneDev& S, const FrameDev& F, CgrtHitDev* hits, float* normals, hipStream_t stream) {
+hipError_t launch_trace_primary_views(const SceneDev& S, const FrameDev& F, CgrtHitDev* hits, float* normals, hipStream_t stream, bool raycams) {
     if (F.nblocks == 0) return hipSuccess;
+    const FramePlan p = plan_frame(S, F);
     const CameraDev C{};  // (unused: the cameras are in F.views)
     unsigned long long* const counters = nullptr;
-    if (F.block == 64 && quad_shape_for(S, (unsigned long long)F.nblocks * 64ull))
-        hipLaunchKernelGGL((k_trace_primary<false, true, true, false, true, RAYCAM>), dim3(4u * F.nblocks), dim3(64), lds_bytes(64), stream, S, C, F, hits,
-                           normals, counters);
-    else if (S.fast_root != REF_NONE)
-        hipLaunchKernelGGL((k_trace_primary<false, true, false, false, true, RAYCAM>), dim3(F.nblocks), dim3((unsigned)F.block),
-                           lds_bytes((unsigned)F.block), stream, S, C, F, hits, normals, counters);
-    else
-        hipLaunchKernelGGL((k_trace_primary<false, false, false, false, true, RAYCAM>), dim3(F.nblocks), dim3((unsigned)F.block),
-                           lds_bytes((unsigned)F.block), stream, S, C, F, hits, normals, counters);
-    return hipGetLastError();
-}
-hipError_t launch_trace_primary_views(const SceneDev& S, const FrameDev& F, CgrtHitDev* hits, float* normals, hipStream_t stream, bool raycams) {
-    return raycams ? launch_views<true>(S, F, hits, normals, stream) : launch_views<false>(S, F, hits, normals, stream);
-}
-template <bool RAYCAM>
-static hipError_t launch_views_compact(const SceneDev& S, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals, int* pixels, uint32_t* count,
-                                       float* rgb, hipStream_t stream) {
-    if (F.nblocks == 0) return hipSuccess;
-    const CameraDev C{};
-    unsigned long long* const counters = nullptr;
-    const SpawnDev* const SP = nullptr;
-    if (F.block == 64 && quad_shape_for(S, (unsigned long long)F.nblocks * 64ull))
-        hipLaunchKernelGGL((k_trace_primary_compact<false, true, true, true, RAYCAM>), dim3(4u * F.nblocks), dim3(64), lds_bytes(64), stream, S, C, F, rays,
-                           hits, normals, pixels, count, counters, rgb, SP);
-    else if (S.fast_root != REF_NONE)
-        hipLaunchKernelGGL((k_trace_primary_compact<false, true, false, true, RAYCAM>), dim3(F.nblocks), dim3((unsigned)F.block),
-                           lds_bytes((unsigned)F.block), stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
-    else
-        hipLaunchKernelGGL((k_trace_primary_compact<false, false, false, true, RAYCAM>), dim3(F.nblocks), dim3((unsigned)F.block),
-                           lds_bytes((unsigned)F.block), stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, SP);
+    with_bools(raycams, p.fast, [&](auto raycam, auto fast) {
+        constexpr bool RAYCAM = decltype(raycam)::value, FAST = decltype(fast)::value;
+        auto go = [&](auto kernel) { launch(kernel, p.grid, p.block, stream, S, C, F, hits, normals, counters); };
+        if constexpr (FAST) {
+            if (p.quad) return go(k_trace_primary<false, true, true, false, true, RAYCAM>);
+        }
+        go(k_trace_primary<false, FAST, false, false, true, RAYCAM>);
+    });
     return hipGetLastError();
 }
 hipError_t launch_trace_primary_views_compact(const SceneDev& S, const FrameDev& F, float* rays, CgrtHitDev* hits, float* normals, int* pixels,
                                               uint32_t* count, float* rgb, hipStream_t stream, bool raycams) {
-    return raycams ? launch_views_compact<true>(S, F, rays, hits, normals, pixels, count, rgb, stream)
-                   : launch_views_compact<false>(S, F, rays, hits, normals, pixels, count, rgb, stream);
+    if (F.nblocks == 0) return hipSuccess;
+    const FramePlan p = plan_frame(S, F);
+    const CameraDev C{};
+    unsigned long long* const counters = nullptr;
+    const SpawnDev* const spawn = nullptr;
+    with_bools(raycams, p.fast, [&](auto raycam, auto fast) {
+        constexpr bool RAYCAM = decltype(raycam)::value, FAST = decltype(fast)::value;
+        auto go = [&](auto kernel) { launch(kernel, p.grid, p.block, stream, S, C, F, rays, hits, normals, pixels, count, counters, rgb, spawn); };
+        if constexpr (FAST) {
+            if (p.quad) return go(k_trace_primary_compact<false, true, true, true, RAYCAM>);
+        }
+        go(k_trace_primary_compact<false, FAST, false, true, RAYCAM>);
+    });
+    return hipGetLastError();
 }
 hipError_t launch_trace_list_compact(const SceneDev& S, const float* in_rays, unsigned long long n, float* rays, CgrtHitDev* hits, float* normals,
                                      int* pixels, uint32_t* count, float* rgb, hipStream_t stream, unsigned long long* counters) {
     if (n == 0) return hipSuccess;
-    const unsigned block = (unsigned)trace_block(S);
-    const bool fast = S.fast_root != REF_NONE;
-    const int shape = list_shape(S, n);  // (the list's length is known to the host: laid out as any ray list)
-    if (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4) {
-        const unsigned q = shape == SHAPE_QUAD4 ? 4u : 16u;
-        if (counters)
-            CGRT_LAUNCHQ(k_trace_list_compact, true, grid_for(n, q), stream, S, in_rays, n, rays, hits, normals, pixels, count, counters, rgb, q);
-        else
-            CGRT_LAUNCHQ(k_trace_list_compact, false, grid_for(n, q), stream, S, in_rays, n, rays, hits, normals, pixels, count, counters, rgb, q);
-        return hipGetLastError();
-    }
-    const unsigned rpw = shape == SHAPE_LANE16 ? 16u : 64u;
-    const unsigned grid = lane_grid(n, block, rpw, 0u);
-    if (counters)
-        CGRT_LAUNCH2(k_trace_list_compact, true, fast, grid, block, stream, S, in_rays, n, rays, hits, normals, pixels, count, counters, rgb, rpw);
-    else
-        CGRT_LAUNCH2(k_trace_list_compact, false, fast, grid, block, stream, S, in_rays, n, rays, hits, normals, pixels, count, counters, rgb, rpw);
+    const ListPlan p = plan_list(S, n, nullptr, 0, GRID_FULL);  // (the list's length is known to the host: laid out as any ray list)
+    with_bools(counters != nullptr, p.fast, [&](auto c, auto fast) {
+        constexpr bool COUNT = decltype(c)::value, FAST = decltype(fast)::value;
+        auto go = [&](auto kernel) { launch(kernel, p, stream, S, in_rays, n, rays, hits, normals, pixels, count, counters, rgb, p.qrpw); };
+        if constexpr (FAST) {
+            if (p.quad) return go(k_trace_list_compact<COUNT, true, true>);
+        }
+        go(k_trace_list_compact<COUNT, FAST>);
+    });
     return hipGetLastError();
 }
 hipError_t launch_clear_owned(const FrameDev& F, float* rgb, hipStream_t stream) {
@@ -1224,44 +1146,29 @@ hipError_t launch_clear_owned(const FrameDev& F, float* rgb, hipStream_t stream)
     hipLaunchKernelGGL(k_clear_owned, dim3(F.nblocks), dim3((unsigned)F.block), 0, stream, F, rgb);
     return hipGetLastError();
 }
+// Soft shadows of a level's items: one thread per (item, light, sample).  Q.set_index: a light-set batch's distinct keys, Q.view_pixels:
+// a multi-view frame's items.  GRID_STRIDED: the first *dcount (<= nitems) items, a capped grid (k_soft_shadow_strided; light sets:
+// k_soft_shadow_sets_strided, whose items are always a multi-view frame's).
 hipError_t launch_soft_shadow(const SceneDev& S, const SoftDev& Q, const float* rays, const CgrtHitDev* hits, const int* item_pixels,
-                              unsigned long long nitems, uint32_t* lit, int anyhit, hipStream_t stream) {
+                              unsigned long long nitems, uint32_t* lit, int anyhit, hipStream_t stream, const uint32_t* dcount, ListGrid grid) {
     const unsigned long long nthreads = nitems * Q.nlights * Q.samples;
     if (nthreads == 0) return hipSuccess;
     const unsigned block = (unsigned)trace_block(S);
-    const unsigned long long blocks = (nthreads + block - 1) / block;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const bool fast = S.fast_root != REF_NONE;
-    if (Q.set_index && Q.view_pixels) {  // a multi-view light-set batch's distinct keys (k_soft_shadow_views_sets)
-        if (anyhit)
-            CGRT_LAUNCH2(k_soft_shadow_views_sets, true, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
-        else
-            CGRT_LAUNCH2(k_soft_shadow_views_sets, false, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
-        return hipGetLastError();
-    }
-    if (Q.set_index) {  // a light-set batch's distinct keys (k_soft_shadow_sets)
-        if (anyhit)
-            CGRT_LAUNCH2(k_soft_shadow_sets, true, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
-        else
-            CGRT_LAUNCH2(k_soft_shadow_sets, false, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
-        return hipGetLastError();
-    }
-    if (Q.view_pixels) {  // a multi-view frame's items (k_soft_shadow VIEWS)
-        const dim3 grid((unsigned)blocks), threads(block);
-        if (anyhit && fast)
-            hipLaunchKernelGGL((k_soft_shadow<true, true, false, true>), grid, threads, lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nthreads, lit);
-        else if (anyhit)
-            hipLaunchKernelGGL((k_soft_shadow<true, false, false, true>), grid, threads, lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nthreads, lit);
-        else if (fast)
-            hipLaunchKernelGGL((k_soft_shadow<false, true, false, true>), grid, threads, lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nthreads, lit);
-        else
-            hipLaunchKernelGGL((k_soft_shadow<false, false, false, true>), grid, threads, lds_bytes(block), stream, S, Q, rays, hits, item_pixels, nthreads, lit);
-        return hipGetLastError();
-    }
-    if (anyhit)
-        CGRT_LAUNCH2(k_soft_shadow, true, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
-    else
-        CGRT_LAUNCH2(k_soft_shadow, false, fast, (unsigned)blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit);
+    const unsigned long long full = (nthreads + block - 1) / block;
+    const bool strided = grid == GRID_STRIDED, views = Q.view_pixels != 0, sets = Q.set_index != nullptr;
+    if (strided ? (!dcount || (sets && !views)) : full > 0x7fffffffull) return hipErrorInvalidValue;
+    const unsigned blocks = strided ? strided_blocks((unsigned)std::min<unsigned long long>(full, 0x7fffffffull), block) : (unsigned)full;
+    with_bools(anyhit != 0, S.fast_root != REF_NONE, [&](auto a, auto f) {
+        constexpr bool A = decltype(a)::value, F = decltype(f)::value;
+        auto go = [&](auto kernel) { launch(kernel, blocks, block, stream, S, Q, rays, hits, item_pixels, nthreads, lit); };
+        auto go_strided = [&](auto kernel) { launch(kernel, blocks, block, stream, S, Q, rays, hits, item_pixels, nitems, dcount, lit); };
+        if (strided) {
+            if (sets) return go_strided(k_soft_shadow_sets_strided<A, F>);
+            return views ? go_strided(k_soft_shadow_strided<A, F, true>) : go_strided(k_soft_shadow_strided<A, F, false>);
+        }
+        if (sets) return views ? go(k_soft_shadow_views_sets<A, F>) : go(k_soft_shadow_sets<A, F>);
+        return views ? go(k_soft_shadow<A, F, false, true>) : go(k_soft_shadow<A, F>);
+    });
     return hipGetLastError();
 }
 hipError_t launch_soft_points(const SceneDev& S, const SoftDev& Q, const float* points, unsigned long long npoints, uint32_t* lit, int anyhit,
@@ -1271,34 +1178,26 @@ hipError_t launch_soft_points(const SceneDev& S, const SoftDev& Q, const float* 
     const unsigned block = (unsigned)trace_block(S);
     const unsigned long long blocks = (nthreads + block - 1) / block;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const bool fast = S.fast_root != REF_NONE;
-    const dim3 grid((unsigned)blocks), threads(block);
-    if (anyhit && fast)
-        hipLaunchKernelGGL((k_soft_shadow<true, true, true>), grid, threads, lds_bytes(block), stream, S, Q, points, nullptr, nullptr, nthreads, lit);
-    else if (anyhit)
-        hipLaunchKernelGGL((k_soft_shadow<true, false, true>), grid, threads, lds_bytes(block), stream, S, Q, points, nullptr, nullptr, nthreads, lit);
-    else if (fast)
-        hipLaunchKernelGGL((k_soft_shadow<false, true, true>), grid, threads, lds_bytes(block), stream, S, Q, points, nullptr, nullptr, nthreads, lit);
-    else
-        hipLaunchKernelGGL((k_soft_shadow<false, false, true>), grid, threads, lds_bytes(block), stream, S, Q, points, nullptr, nullptr, nthreads, lit);
+    with_bools(anyhit != 0, S.fast_root != REF_NONE, [&](auto a, auto f) {
+        launch(k_soft_shadow<decltype(a)::value, decltype(f)::value, true>, (unsigned)blocks, block, stream, S, Q, points, nullptr, nullptr, nthreads, lit);
+    });
     return hipGetLastError();
 }
-// The visibility queries (k_visibility): n answers, laid out by the list's shape (list_shape, as launch_trace_batch; forced by
-// cgrt_set_kernel_shape).  POINTS: src holds n / nlights points.
+// The visibility queries (k_visibility): n answers, laid out by the list's shape (as launch_trace_batch; forced by cgrt_set_kernel_shape).
+// POINTS: src holds n / nlights points.
 template <bool POINTS>
 static hipError_t launch_visibility(const SceneDev& S, const float* src, const float* lights, unsigned nlights, unsigned long long n, uint8_t* out,
                                     hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    const unsigned block = (unsigned)trace_block(S);
-    const bool fast = S.fast_root != REF_NONE;
-    const int shape = list_shape(S, n);
-    if (shape == SHAPE_QUAD16 || shape == SHAPE_QUAD4) {
-        const unsigned q = shape == SHAPE_QUAD4 ? 4u : 16u;
-        CGRT_LAUNCHQ(k_visibility, POINTS, grid_for(n, q), stream, S, src, lights, nlights, n, out, q);
-        return hipGetLastError();
-    }
-    const unsigned rpw = shape == SHAPE_LANE16 ? 16u : 64u;
-    CGRT_LAUNCH2(k_visibility, POINTS, fast, lane_grid(n, block, rpw, 0u), block, stream, S, src, lights, nlights, n, out, rpw);
+    const ListPlan p = plan_list(S, n, nullptr, 0, GRID_FULL);
+    with_bool(p.fast, [&](auto fast) {
+        constexpr bool FAST = decltype(fast)::value;
+        auto go = [&](auto kernel) { launch(kernel, p, stream, S, src, lights, nlights, n, out, p.qrpw); };
+        if constexpr (FAST) {
+            if (p.quad) return go(k_visibility<POINTS, true, true>);
+        }
+        go(k_visibility<POINTS, FAST>);
+    });
     return hipGetLastError();
 }
 hipError_t launch_occluded(const SceneDev& S, const float* rays, unsigned long long n, uint8_t* out, hipStream_t stream) {

@@ -12,36 +12,11 @@ from __future__ import annotations
 import argparse
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join("cg-raytracer_amd", "csrc")
-FLAGS = ["--offload-arch=gfx950", "-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-         "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero", "-Rpass-analysis=kernel-resource-usage"]
-FIELDS = [("VGPRs", r"VGPRs: (\d+)"), ("SGPRs", r"SGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-          ("LDS", r"LDS Size \[bytes/block\]: (\d+)"), ("waves", r"Occupancy \[waves/SIMD\]: (\d+)")]
-
-
-def demangle(names):
-    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
-    # (a kernel of an anonymous namespace keeps its name: the argument list is cut at the first parenthesis AFTER that qualifier)
-    return [re.sub(r"^void |\(.*$", "", o.replace("(anonymous namespace)::", "")) for o in out]
-
-
-def usage(csrc_dir: str, src: str, obj: str) -> dict:
-    """{kernel name: (VGPRs, SGPRs, scratch, LDS)} of one translation unit."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    r = subprocess.run([hipcc, *FLAGS, "-c", src, "-o", obj], cwd=csrc_dir, capture_output=True, text=True)
-    if r.returncode:
-        sys.exit(r.stderr[-4000:])
-    blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
-    names = demangle([b.split()[0] for b in blocks])
-    res = {}
-    for name, b in zip(names, blocks):
-        res[name] = tuple(int(re.search(pat, b).group(1)) for _, pat in FIELDS)
-    return res
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from resource_usage import CSRC, ROOT, parent_tree, usage  # noqa: E402
 
 
 def trim(name: str) -> str:
@@ -69,13 +44,8 @@ def main() -> int:
     ap.add_argument("--parent", default=None, help="revision to compare with (default: HEAD when the kernel sources differ from it, else HEAD~1)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "raycams_resource_usage.txt"))
     a = ap.parse_args()
-    if a.parent is None:
-        dirty = subprocess.run(["git", "-C", ROOT, "diff", "--quiet", "HEAD", "--", CSRC, "include"]).returncode != 0
-        a.parent = "HEAD" if dirty else "HEAD~1"
     with tempfile.TemporaryDirectory() as tmp:
-        tar = subprocess.run(["git", "-C", ROOT, "archive", a.parent, CSRC, "include"], capture_output=True, check=True).stdout
-        subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
-        before = {trim(k): v for k, v in usage(os.path.join(tmp, CSRC), "trace_kernels.hip", os.path.join(tmp, "a.o")).items()}
+        before = {trim(k): v for k, v in usage(parent_tree(a.parent, tmp)[1], "trace_kernels.hip", os.path.join(tmp, "a.o")).items()}
         after = {trim(k): v for k, v in usage(os.path.join(ROOT, CSRC), "trace_kernels.hip", os.path.join(tmp, "b.o")).items()}
     fmt = lambda v: " ".join(str(x) for x in v)  # noqa: E731
     lines = ["hipcc --offload-arch=gfx950 -O3 (the Makefile's flags) -Rpass-analysis=kernel-resource-usage on trace_kernels.hip, before (parent",
