@@ -36,6 +36,9 @@ assert CLOSEST_DTYPE.itemsize == 32
 # include/cgrt.h CgrtCrossing: one surface crossing of a ray (8 bytes); an unused entry of a slot is {+inf, NO_PRIM}
 CROSSING_DTYPE = np.dtype([("t", np.float32), ("prim_id", np.uint32)])
 assert CROSSING_DTYPE.itemsize == 8
+# include/cgrt.h CgrtNeighbor: one triangle within a query point's radius (8 bytes); an unused entry of a slot is {+inf, NO_PRIM}
+NEIGHBOR_DTYPE = np.dtype([("dist2", np.float32), ("prim_id", np.uint32)])
+assert NEIGHBOR_DTYPE.itemsize == 8
 # Scene.inside_tensor's default directions: three fixed generic ones (no component zero, none along an axis, a face diagonal or a space
 # diagonal, pairwise far from parallel), so that a ray through an edge or a vertex of an axis-aligned or diagonal-symmetric mesh is the
 # exception in at most one of them
@@ -342,7 +345,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -473,6 +476,12 @@ def lib() -> C.CDLL:
     L.cgrt_list_crossings_brute.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp]
     L.cgrt_list_crossings_device.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp]
     L.cgrt_debug_crossing_work.argtypes = [vp, vp, u64, vp]
+    L.cgrt_count_neighbors.argtypes = [vp, vp, u64, vp, C.c_float, vp]
+    L.cgrt_count_neighbors_device.argtypes = [vp, vp, u64, vp, C.c_float, vp, vp]
+    L.cgrt_list_neighbors.argtypes = [vp, vp, u64, vp, C.c_float, vp, u32, vp, u64, vp]
+    L.cgrt_list_neighbors_brute.argtypes = [vp, vp, u64, vp, C.c_float, vp, u32, vp, u64, vp]
+    L.cgrt_list_neighbors_device.argtypes = [vp, vp, u64, vp, C.c_float, vp, u32, vp, u64, vp, vp]
+    L.cgrt_debug_neighbor_work.argtypes = [vp, vp, u64, vp, C.c_float, u32, vp]
     L.cgrt_signed_distance.argtypes = [vp, vp, u64, C.POINTER(SdfParams), vp, vp]
     L.cgrt_signed_distance_device.argtypes = [vp, vp, u64, C.POINTER(SdfParams), vp, vp, vp]
     L.cgrt_signed_distance_grid.argtypes = [vp, C.POINTER(Grid), C.POINTER(SdfParams), vp, vp]
@@ -2173,6 +2182,170 @@ class Scene:
         rec = self._tensor_call(out, (n, k, 2), torch.float32, stream,
                                 lambda o, s: self.first_crossings_device(rays.data_ptr(), n, k, o.data_ptr(), d_counts_ptr=counts.data_ptr(), stream=s))
         return rec, counts
+
+    # ---- neighbour queries (include/cgrt.h cgrt_count_neighbors*, cgrt_list_neighbors*) ----
+    @staticmethod
+    def _neighbor_points(points, radius2):
+        p = _f32(points, (-1, 3))
+        r = None if radius2 is None else _f32(radius2, (-1,))
+        if r is not None and len(r) != len(p):
+            raise ValueError("radius2 must hold one squared radius per point")
+        return p, r
+
+    def count_neighbors(self, points, radius2=None, max_dist2: float = float("inf")) -> np.ndarray:
+        """cgrt_count_neighbors: for every query point ((n, 3) float32) the number of triangles whose closest_points dist2 is <= its
+        squared radius -- radius2[i] ((n,) float32; NaN or negative: no neighbours), or max_dist2 for every query.  (n,) uint32."""
+        p, r = self._neighbor_points(points, radius2)
+        counts = np.zeros(len(p), np.uint32)
+        _check(lib().cgrt_count_neighbors(self._h, _ptr(p), len(p), _ptr(r), float(max_dist2), _ptr(counts)))
+        return counts
+
+    def _neighbors_host(self, f, p, r, max_dist2: float, offsets, k: int, want_counts: bool = True):
+        m = int(offsets[-1]) if offsets is not None else len(p) * k
+        out = np.zeros(m, NEIGHBOR_DTYPE)
+        counts = np.zeros(len(p), np.uint32) if want_counts else None
+        _check(f(self._h, _ptr(p), len(p), _ptr(r), float(max_dist2), _ptr(offsets), int(k), _ptr(out), m, _ptr(counts)))
+        return out, counts
+
+    def list_neighbors(self, points, radius2=None, max_dist2: float = float("inf"), offsets=None, want_counts: bool = True):
+        """Every neighbour of every query point, in order (by dist2, equal dist2 by prim_id): cgrt_count_neighbors, the exclusive prefix
+        sums, then cgrt_list_neighbors.  Returns (offsets, records): offsets (n + 1,) int64, query i's neighbours are
+        records[offsets[i]:offsets[i + 1]] (NEIGHBOR_DTYPE {dist2, prim_id}).
+        With offsets ((n + 1,) slot boundaries chosen by the caller) one cgrt_list_neighbors call: query i receives its first neighbours
+        in order in records [offsets[i], offsets[i + 1]), {+inf, NO_PRIM} in what remains.  Returns (records (offsets[-1],), counts: the
+        full numbers of neighbours -- or None with want_counts=False, which lets a query's search shrink to the largest dist2 its full
+        slot keeps)."""
+        p, r = self._neighbor_points(points, radius2)
+        if offsets is not None:
+            return self._neighbors_host(lib().cgrt_list_neighbors, p, r, max_dist2, np.ascontiguousarray(offsets, np.uint64), 0, want_counts)
+        offsets = np.zeros(len(p) + 1, np.uint64)
+        np.cumsum(self.count_neighbors(p, r, max_dist2), dtype=np.uint64, out=offsets[1:])
+        out, _ = self._neighbors_host(lib().cgrt_list_neighbors, p, r, max_dist2, offsets, 0, want_counts=False)
+        return offsets.astype(np.int64), out
+
+    def list_neighbors_brute(self, points, radius2=None, max_dist2: float = float("inf"), offsets=None, k: int = 0):
+        """cgrt_list_neighbors_brute: the list by testing every triangle in turn (validation; the same bytes).  With neither offsets nor
+        k the full list, as list_neighbors returns it: (offsets, records); with offsets ((n + 1,) slot boundaries) or k (k records per
+        query): (records, counts)."""
+        p, r = self._neighbor_points(points, radius2)
+        f = lib().cgrt_list_neighbors_brute
+        if offsets is None and not k:
+            _, c = self._neighbors_host(f, p, r, max_dist2, None, 1)  # k = 1 only to obtain the counts
+            off = np.zeros(len(p) + 1, np.uint64)
+            np.cumsum(c, dtype=np.uint64, out=off[1:])
+            out, _ = self._neighbors_host(f, p, r, max_dist2, off, 0, want_counts=False)
+            return off.astype(np.int64), out
+        off = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
+        out, counts = self._neighbors_host(f, p, r, max_dist2, off, k)
+        return (out.reshape(len(p), k) if off is None else out), counts
+
+    def nearest_triangles(self, points, k: int, radius2=None, max_dist2: float = float("inf"), want_counts: bool = False):
+        """The k nearest triangles of every query point within its squared radius: (n, k) NEIGHBOR_DTYPE records in order, unused entries
+        {+inf, NO_PRIM}.  With want_counts=True returns (records, counts): counts (n,) uint32, the full numbers of neighbours (the
+        search then cannot shrink its bound to the slot)."""
+        p, r = self._neighbor_points(points, radius2)
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        out, counts = self._neighbors_host(lib().cgrt_list_neighbors, p, r, max_dist2, None, k, want_counts)
+        out = out.reshape(len(p), k)
+        return (out, counts) if want_counts else out
+
+    def debug_neighbor_work(self, points, radius2=None, max_dist2: float = float("inf"), k: int = 0):
+        """cgrt_debug_neighbor_work: (node steps, triangles evaluated), summed over the queries (a separate counting launch), of
+        count_neighbors' search (k = 0) or of nearest_triangles' (k > 0: the shrinking bound)."""
+        p, r = self._neighbor_points(points, radius2)
+        w = np.zeros(2, np.uint64)
+        _check(lib().cgrt_debug_neighbor_work(self._h, _ptr(p), len(p), _ptr(r), float(max_dist2), int(k), _ptr(w)))
+        return int(w[0]), int(w[1])
+
+    def count_neighbors_device(self, d_points_ptr: int, n: int, d_counts_ptr: int, d_radius2_ptr: int = 0, max_dist2: float = float("inf"),
+                               stream: int = 0) -> None:
+        """cgrt_count_neighbors_device: n points (3 floats each) at d_points_ptr (and n squared radii at d_radius2_ptr, or 0) -> n uint32
+        counts at d_counts_ptr, enqueued on the hipStream_t `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        _check(lib().cgrt_count_neighbors_device(self._h, vp(d_points_ptr), int(n), vp(d_radius2_ptr), float(max_dist2), vp(d_counts_ptr),
+                                                 vp(stream)))
+
+    def list_neighbors_device(self, d_points_ptr: int, n: int, d_out_ptr: int, capacity: int, d_offsets_ptr: int = 0, k: int = 0,
+                              d_counts_ptr: int = 0, d_radius2_ptr: int = 0, max_dist2: float = float("inf"), stream: int = 0) -> None:
+        """cgrt_list_neighbors_device: slots from the n + 1 uint64 offsets at d_offsets_ptr, or of k records each; `capacity` records of
+        8 bytes at d_out_ptr, nothing beyond them is written whatever the offsets hold; d_counts_ptr (optional) receives the full counts.
+        Enqueued on `stream`.  Raw integers."""
+        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
+        _check(lib().cgrt_list_neighbors_device(self._h, vp(d_points_ptr), int(n), vp(d_radius2_ptr), float(max_dist2), vp(d_offsets_ptr),
+                                                int(k), vp(d_out_ptr), int(capacity), vp(d_counts_ptr), vp(stream)))
+
+    def _neighbor_tensors(self, points, radius2, max_dist2):
+        """(n, the radii's address or 0, the scalar bound) of a *_tensor call: radius2 a float (it replaces max_dist2) or an (n,) tensor."""
+        import torch
+
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be a torch tensor of shape (n, 3)")
+        self._device_tensor(points, "points", (torch.float32,))
+        n = points.shape[0]
+        if radius2 is None:
+            return n, 0, float(max_dist2)
+        if isinstance(radius2, torch.Tensor):
+            self._device_tensor(radius2, "radius2", (torch.float32,), (n,))
+            return n, (radius2.data_ptr() if n else 0), float(max_dist2)
+        return n, 0, float(radius2)
+
+    def count_neighbors_tensor(self, points, radius2=None, max_dist2: float = float("inf"), out=None, stream=None):
+        """count_neighbors on torch tensors: points (n, 3) float32 on cuda:<device>, radius2 None, a float (one squared radius for every
+        query) or an (n,) float32 tensor -> (n,) torch.int32, into `out` or a new tensor, enqueued on `stream` (default:
+        torch.cuda.current_stream())."""
+        import torch
+
+        n, rad, md = self._neighbor_tensors(points, radius2, max_dist2)
+        if out is not None:
+            self._device_tensor(out, "out", (torch.int32,), (n,))
+        return self._tensor_call(out, (n,), torch.int32, stream,
+                                 lambda o, s: self.count_neighbors_device(points.data_ptr(), n, o.data_ptr(), d_radius2_ptr=rad, max_dist2=md, stream=s))
+
+    def list_neighbors_tensor(self, points, radius2=None, max_dist2: float = float("inf"), stream=None):
+        """list_neighbors on torch tensors -> (offsets (n + 1,) torch.int64, records (m, 2) float32 with the prim_id BITS in column 1:
+        records.view(torch.int32)[:, 1]).  Count, a torch cumsum and the list are enqueued on `stream`; the total m is read back in
+        between (one synchronisation of that stream)."""
+        import torch
+
+        n, rad, md = self._neighbor_tensors(points, radius2, max_dist2)
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        counts = self.count_neighbors_tensor(points, radius2, max_dist2, stream=stream)
+        with torch.cuda.stream(stream):
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+            m = int(offsets[-1].item())
+            records = torch.empty((m, 2), dtype=torch.float32, device=dev)
+        if n and m:
+            self.list_neighbors_device(points.data_ptr(), n, records.data_ptr(), m, d_offsets_ptr=offsets.data_ptr(), d_radius2_ptr=rad,
+                                       max_dist2=md, stream=stream.cuda_stream)
+        return offsets, records
+
+    def nearest_triangles_tensor(self, points, k: int, radius2=None, max_dist2: float = float("inf"), want_counts: bool = False, out=None,
+                                 stream=None):
+        """nearest_triangles on torch tensors -> records (n, k, 2) float32 (`out`, or a new tensor; the prim_id bits in [..., 1], unused
+        entries {+inf, NO_PRIM}); with want_counts=True (records, counts (n,) torch.int32: the full numbers of neighbours)."""
+        import torch
+
+        n, rad, md = self._neighbor_tensors(points, radius2, max_dist2)
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        if out is not None:
+            self._device_tensor(out, "out", (torch.float32,), (n, k, 2))
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        counts = None
+        if want_counts:
+            with torch.cuda.stream(stream):
+                counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        cp = counts.data_ptr() if want_counts and n else 0
+        rec = self._tensor_call(out, (n, k, 2), torch.float32, stream,
+                                lambda o, s: self.list_neighbors_device(points.data_ptr(), n, o.data_ptr(), n * k, k=k, d_counts_ptr=cp,
+                                                                        d_radius2_ptr=rad, max_dist2=md, stream=s))
+        return (rec, counts) if want_counts else rec
 
     def inside_tensor(self, points, directions=None, stream=None):
         """Inside / outside for points (n, 3) float32 on cuda:<device>, meaningful for WATERTIGHT meshes: the majority vote, over an odd

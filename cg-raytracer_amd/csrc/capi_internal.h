@@ -32,6 +32,7 @@
 #include "cgrt_math.h"
 #include "closest_kernels.h"
 #include "crossing_kernels.h"
+#include "neighbor_kernels.h"
 #include "sdf_kernels.h"
 #include "surface_kernels.h"
 #include "trace_kernels.h"
@@ -154,7 +155,7 @@ struct CgrtScene {
         struct Buf {
             void* p = nullptr;
             size_t cap = 0;
-        } dev[4], pin[4];  // rays / hits / normals / light tables
+        } dev[5], pin[5];  // rays / hits / normals / light tables / a query's fifth array (per-query radii)
         void* bounce[2] = {nullptr, nullptr};  // pinned halves of the large-transfer pipeline (lane_upload / lane_download), made on first use
         hipEvent_t bounce_ev[2] = {nullptr, nullptr};
         hipEvent_t follow = nullptr;  // lane_follow: the lane's stream waits for the caller's, made on first use
@@ -421,7 +422,7 @@ struct LaneGuard {
     explicit LaneGuard(CgrtScene* s) : sc(s) {}
     ~LaneGuard();
     int acquire();
-    // scratch that only grows (geometrically): k = 0 rays, 1 hits, 2 normals, 3 light tables
+    // scratch that only grows (geometrically): k = 0 rays, 1 hits, 2 normals, 3 light tables, 4 per-query radii
     hipError_t dev(int k, size_t bytes, void** out);
     hipError_t pin(int k, size_t bytes, void** out);
 };
@@ -434,7 +435,7 @@ struct LaneCall {
     struct Staged {  // by slot; from: the lane's pinned buffer of the slot, or null (nothing pending)
         void *host = nullptr, *from = nullptr;
         size_t bytes = 0;
-    } staged[4];
+    } staged[5];
     explicit LaneCall(CgrtScene* s) : g(s) {}
     hipStream_t stream() const { return g.L->stream; }
     int begin();  // the scene's device becomes current, a lane is taken

@@ -1,5 +1,5 @@
 // capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
-// closest points, crossings, signed distance, winding numbers.  None of them touches the scene's frame state (workspace, prediction, hints).
+// closest points, crossings, neighbours, signed distance, winding numbers.  None of them touches the scene's frame state (workspace, prediction, hints).
 #include "capi_internal.h"
 
 extern "C" {
@@ -606,6 +606,132 @@ int cgrt_list_crossings_brute(CgrtScene* s, const CgrtRay* rays, uint64_t n, con
 }
 int cgrt_debug_crossing_work(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint64_t* out2) {
     return crossing_host(s, rays, n, nullptr, 0, nullptr, 0, nullptr, false, 2, out2);
+}
+
+// ---- neighbour queries (include/cgrt.h cgrt_count_neighbors*, cgrt_list_neighbors*): every triangle within a
+// query point's squared radius, counted or listed in (dist2, prim_id) order.  No scene state is read or written; the checks come in the
+// order include/cgrt.h states, all before any device work.
+namespace {
+static_assert(sizeof(CgrtNeighbor) == sizeof(CgrtNeighborDev), "CgrtNeighbor is what the kernels write");
+// result: counts for the count entries, out2 for the work entry, out for the list entries; list: the slot arguments are checked
+int neighbor_args(const CgrtScene* s, const void* points, uint64_t n, const void* radius2, float max_dist2, const void* result, bool list,
+                  const uint64_t* offsets, uint32_t k, uint64_t capacity, const void* counts, bool device) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    if (n && (!points || !result)) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many queries: n exceeds 0x7fffffff");
+    if (!(max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
+    if (list) {
+        if ((offsets != nullptr) == (k > 0)) return fail(CGRT_E_ARG, "exactly one of offsets and k > 0 must be given");
+        if (capacity > kCrossingMaxCapacity) return fail(CGRT_E_ARG, "capacity exceeds 2^37 records");
+        if (k && n * (uint64_t)k > capacity) return fail(CGRT_E_ARG, "n * k records exceed capacity");
+        if (!device && offsets && n) {
+            if (offsets[0] != 0) return fail(CGRT_E_ARG, "offsets must start at 0");
+            for (uint64_t i = 0; i < n; i++)
+                if (offsets[i + 1] < offsets[i]) return fail(CGRT_E_ARG, "offsets must not decrease");
+            if (offsets[n] > capacity) return fail(CGRT_E_ARG, "offsets end beyond capacity");
+        }
+    }
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)radius2 % 4 || (uintptr_t)result % 4 || (uintptr_t)counts % 4 || (uintptr_t)offsets % 8))
+        return fail(CGRT_E_ARG, "device pointers must be aligned to their elements");
+    return CGRT_OK;
+}
+// host pointers, on a call lane (slots: 0 the points, 1 the offsets, 2 the records, 3 the counts, 4 the radii); how: 0 tree search,
+// 1 brute force, 2 counted tree search (k == 0: the count search; k > 0: the k-nearest search into records of the lane's own)
+int neighbor_host(CgrtScene* s, const float* points, uint64_t n, const float* radius2, float max_dist2, const uint64_t* offsets, uint32_t k,
+                  CgrtNeighbor* out, uint64_t capacity, uint32_t* counts, bool list, int how, uint64_t* work) {
+    if (how == 2) {
+        list = k > 0;
+        capacity = n * (uint64_t)k;  // (n <= 0x7fffffff is checked before this is looked at)
+    }
+    int rc = neighbor_args(s, points, n, radius2, max_dist2, how == 2 ? static_cast<const void*>(work) : (list ? static_cast<const void*>(out) : counts),
+                           list, offsets, k, capacity, counts, false);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    const uint64_t used = list ? (offsets ? offsets[n] : n * (uint64_t)k) : 0;  // the slots are records [0, used)
+    const bool want_counts = how == 2 ? !list : (!list || counts != nullptr);
+    if (how != 2 && used == 0 && !want_counts) return CGRT_OK;  // every slot is empty and no count is asked for: nothing to write
+    LaneCall c(s);
+    if ((rc = c.begin()) != CGRT_OK) return rc;
+    const size_t out_bytes = (size_t)used * sizeof(CgrtNeighbor), cnt_bytes = (size_t)n * 4u;
+    void *dp = nullptr, *doff = nullptr, *dout = nullptr, *dcnt = nullptr, *drad = nullptr;
+    HIP_TRY(c.input(0, points, n * 12, &dp));
+    if (offsets) HIP_TRY(c.input(1, offsets, (n + 1) * 8, &doff));
+    if (used) HIP_TRY(c.scratch(2, out_bytes, &dout));  // (a lane's buffer that was never needed is a null pointer)
+    if (want_counts) HIP_TRY(c.scratch(3, cnt_bytes, &dcnt));
+    if (radius2) HIP_TRY(c.input(4, radius2, n * 4, &drad));
+    NeighborArgs A{};
+    A.points = static_cast<const float*>(dp);
+    A.radius2 = static_cast<const float*>(drad);
+    A.max_dist2 = max_dist2;
+    A.n = n;
+    A.offsets = static_cast<const unsigned long long*>(doff);
+    A.k = k;
+    A.out = static_cast<CgrtNeighborDev*>(dout);  // no record to write (count entries, or every slot empty): the count search
+    A.capacity = used;
+    A.counts = static_cast<uint32_t*>(dcnt);
+    if (how == 2) {
+        HIP_TRY(c.zero_counters(2));
+        HIP_TRY(launch_neighbors(s->dev, A, false, c.counters(), c.stream()));
+        HIP_TRY(c.read_counters(work, 2));
+        return CGRT_OK;
+    }
+    HIP_TRY(launch_neighbors(s->dev, A, how == 1, nullptr, c.stream()));
+    if (used) HIP_TRY(c.output(2, out, dout, out_bytes));
+    if (want_counts) HIP_TRY(c.output(3, counts, dcnt, cnt_bytes));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
+int neighbor_device(CgrtScene* s, const float* d_points, uint64_t n, const float* d_radius2, float max_dist2, const uint64_t* d_offsets, uint32_t k,
+                    CgrtNeighbor* d_out, uint64_t capacity, uint32_t* d_counts, bool list, void* stream) {
+    int rc = neighbor_args(s, d_points, n, d_radius2, max_dist2, list ? static_cast<const void*>(d_out) : d_counts, list, d_offsets, k, capacity,
+                           d_counts, true);
+    if (rc) return rc;
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
+    if (d_radius2 && (rc = check_device_span(s, d_radius2, n * 4, "d_radius2")) != CGRT_OK) return rc;
+    if (d_offsets && (rc = check_device_span(s, d_offsets, (n + 1) * 8, "d_offsets")) != CGRT_OK) return rc;
+    // with offsets any record below capacity may be written; with k the slots are the first n * k records
+    if (list && (rc = check_device_span(s, d_out, (d_offsets ? capacity : n * (uint64_t)k) * sizeof(CgrtNeighbor), "d_out")) != CGRT_OK) return rc;
+    if (d_counts && (rc = check_device_span(s, d_counts, n * 4, "d_counts")) != CGRT_OK) return rc;
+    NeighborArgs A{};
+    A.points = d_points;
+    A.radius2 = d_radius2;
+    A.max_dist2 = max_dist2;
+    A.n = n;
+    A.offsets = reinterpret_cast<const unsigned long long*>(d_offsets);
+    A.k = k;
+    A.out = list ? reinterpret_cast<CgrtNeighborDev*>(d_out) : nullptr;
+    A.capacity = capacity;
+    A.counts = d_counts;
+    HIP_TRY(launch_neighbors(s->dev, A, false, nullptr, static_cast<hipStream_t>(stream)));
+    return CGRT_OK;
+}
+}  // namespace
+
+int cgrt_count_neighbors(CgrtScene* s, const float* points, uint64_t n, const float* radius2, float max_dist2, uint32_t* counts) {
+    return neighbor_host(s, points, n, radius2, max_dist2, nullptr, 0, nullptr, 0, counts, false, 0, nullptr);
+}
+int cgrt_count_neighbors_device(CgrtScene* s, const float* d_points, uint64_t n, const float* d_radius2, float max_dist2, uint32_t* d_counts,
+                                void* stream) {
+    return neighbor_device(s, d_points, n, d_radius2, max_dist2, nullptr, 0, nullptr, 0, d_counts, false, stream);
+}
+int cgrt_list_neighbors(CgrtScene* s, const float* points, uint64_t n, const float* radius2, float max_dist2, const uint64_t* offsets, uint32_t k,
+                        CgrtNeighbor* out, uint64_t capacity, uint32_t* counts) {
+    return neighbor_host(s, points, n, radius2, max_dist2, offsets, k, out, capacity, counts, true, 0, nullptr);
+}
+int cgrt_list_neighbors_device(CgrtScene* s, const float* d_points, uint64_t n, const float* d_radius2, float max_dist2, const uint64_t* d_offsets,
+                               uint32_t k, CgrtNeighbor* d_out, uint64_t capacity, uint32_t* d_counts, void* stream) {
+    return neighbor_device(s, d_points, n, d_radius2, max_dist2, d_offsets, k, d_out, capacity, d_counts, true, stream);
+}
+int cgrt_list_neighbors_brute(CgrtScene* s, const float* points, uint64_t n, const float* radius2, float max_dist2, const uint64_t* offsets,
+                              uint32_t k, CgrtNeighbor* out, uint64_t capacity, uint32_t* counts) {
+    return neighbor_host(s, points, n, radius2, max_dist2, offsets, k, out, capacity, counts, true, 1, nullptr);
+}
+int cgrt_debug_neighbor_work(CgrtScene* s, const float* points, uint64_t n, const float* radius2, float max_dist2, uint32_t k, uint64_t* out2) {
+    return neighbor_host(s, points, n, radius2, max_dist2, nullptr, k, nullptr, 0, nullptr, false, 2, out2);
 }
 
 // ---- signed distance and occupancy (include/cgrt.h cgrt_signed_distance*): the closest-point search and the parity

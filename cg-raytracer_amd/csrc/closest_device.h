@@ -45,9 +45,17 @@ __device__ __forceinline__ float clamp1(const float q, const float a, const floa
     return q < lo ? lo : (q > hi ? hi : q);
 }
 
-// include/cgrt.h "Closest-point queries", the definition, operation for operation; r0..r3 = the record's four 16-byte quarters
-__device__ __forceinline__ void closest_tri(const float4 r0, const float4 r1, const float4 r2, const float4 r3, const float px, const float py,
-                                            const float pz, Best& B) {
+// One triangle's answer for a query: the definition's q, v, w and dist2, and the record's prim_id.
+struct TriClosest {
+    float dist2;
+    uint32_t prim;
+    float qx, qy, qz, v, w;
+};
+
+// include/cgrt.h "Closest-point queries", the definition, operation for operation; r0..r3 = the record's four 16-byte quarters.
+// A pure function of (p, triangle): closest_tri takes its result into a Best, the neighbour search (neighbor_kernels.hip) into a slot.
+__device__ __forceinline__ TriClosest closest_eval(const float4 r0, const float4 r1, const float4 r2, const float4 r3, const float px,
+                                                   const float py, const float pz) {
     const float ax = r0.x, ay = r0.y, az = r0.z, bx = r0.w, by = r1.x, bz = r1.y, cx = r1.z, cy = r1.w, cz = r2.x;
     const float abx = bx - ax, aby = by - ay, abz = bz - az;
     const float acx = cx - ax, acy = cy - ay, acz = cz - az;
@@ -98,17 +106,25 @@ __device__ __forceinline__ void closest_tri(const float4 r0, const float4 r1, co
     qy = clamp1(qy, ay, by, cy);
     qz = clamp1(qz, az, bz, cz);
     const float rx = px - qx, ry = py - qy, rz = pz - qz;
-    const float dist2 = dot3(rx, ry, rz, rx, ry, rz);
-    const uint32_t prim = __float_as_uint(r3.y);
+    TriClosest E;
+    E.dist2 = dot3(rx, ry, rz, rx, ry, rz);
+    E.prim = __float_as_uint(r3.y);
+    E.qx = qx, E.qy = qy, E.qz = qz, E.v = v, E.w = w;
+    return E;
+}
+
+__device__ __forceinline__ void closest_tri(const float4 r0, const float4 r1, const float4 r2, const float4 r3, const float px, const float py,
+                                            const float pz, Best& B) {
+    const TriClosest E = closest_eval(r0, r1, r2, r3, px, py, pz);
     // dist2 <= max_dist2 qualifies (prim starts as CGRT_NO_PRIM, above every id); smaller dist2 wins, equal dist2 goes to the smaller id
-    const bool take = dist2 < B.d2 || (dist2 == B.d2 && prim < B.prim);
-    B.d2 = take ? dist2 : B.d2;
-    B.prim = take ? prim : B.prim;
-    B.qx = take ? qx : B.qx;
-    B.qy = take ? qy : B.qy;
-    B.qz = take ? qz : B.qz;
-    B.v = take ? v : B.v;
-    B.w = take ? w : B.w;
+    const bool take = E.dist2 < B.d2 || (E.dist2 == B.d2 && E.prim < B.prim);
+    B.d2 = take ? E.dist2 : B.d2;
+    B.prim = take ? E.prim : B.prim;
+    B.qx = take ? E.qx : B.qx;
+    B.qy = take ? E.qy : B.qy;
+    B.qz = take ? E.qz : B.qz;
+    B.v = take ? E.v : B.v;
+    B.w = take ? E.w : B.w;
 }
 
 // squared distance from p to the box, in dist2's operations and association

@@ -822,7 +822,7 @@ int cgrt_surface_raycams_grad_device(CgrtScene* scene, const CgrtRayCamera* cams
  * NaN or negative; (device form) a pointer not 4-byte aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and touches
  * nothing.  Device form: then d_points (n * 12 bytes) and d_out (n * 32 bytes) checked as device memory of the scene's device, as
  * cgrt_shade_rays_device checks its buffers.
- * Not offered: sphere primitives; k nearest; a per-query radius; attribute interpolation at the closest point
+ * Not offered: sphere primitives; attribute interpolation at the closest point (k nearest and a per-query radius: "Neighbour queries")
  * (attr[tri[prim_id]] weighted by bary is a plain gather); the fast tree as a search structure; enqueued-ticket forms (the device form
  * never blocks); the C++ host mirror (the reference has no such function). */
 typedef struct CgrtClosest {
@@ -907,6 +907,75 @@ int cgrt_list_crossings_device(CgrtScene* scene, const CgrtRay* d_rays, uint64_t
 int cgrt_list_crossings_brute(CgrtScene* scene, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out,
                               uint64_t capacity, uint32_t* counts);
 int cgrt_debug_crossing_work(CgrtScene* scene, const CgrtRay* rays, uint64_t n, uint64_t* out2);
+
+/* Neighbour queries: "which triangles lie within r of p -- all of them, nearest first?" and "which are the k
+ * nearest?" for a list of points -- the point-side twin of the crossing queries: contact and proximity sets, neighbourhoods for smoothing
+ * and robust normals, projection with fallbacks, per-particle radii.  The reference has no such function; the definition below IS the
+ * specification.
+ * Definition.  For a query point p with bound r2, triangle k is a NEIGHBOUR iff `dist2_k <= r2` is true, dist2_k being exactly the dist2
+ * of "Closest-point queries": the same operations, the same clamp, a pure function of (p, triangle) -- no tree, no visiting order, no
+ * running minimum enters.  A NaN dist2 never qualifies.  Spheres are ignored.
+ * Bound.  r2 = radius2 ? radius2[i] : max_dist2 (radius2: n f32, or NULL).  The scalar max_dist2 is checked as cgrt_closest_points checks
+ * it (NaN or negative: CGRT_E_ARG; +inf: unbounded), also where radius2 is given.  A per-query radius2[i] for which `radius2[i] >= 0` is
+ * false (NaN or negative) gives that query no neighbours: this is decided in the kernel, identically in the host and the device forms;
+ * the host forms do not scan the array.  A non-finite p has no neighbours; in a scene without meshes no query has any.
+ * Order.  A query's neighbours are ordered by dist2 compared as floats, equal dist2 going to the smaller prim_id: a total order, so
+ * every output byte is determined.
+ * Slots.  CgrtNeighbor = {dist2, prim_id}, 8 bytes.  The rule is exactly that of "Crossing queries".  cgrt_count_neighbors* write
+ * counts[i] = the number of neighbours of query i.  In the list calls query i owns the records [offsets[i], offsets[i + 1]) of out
+ * (offsets: n + 1 entries; the exclusive prefix sums of a count call give the full list, CSR style) or, with offsets == NULL, the records
+ * [i * k, (i + 1) * k): exactly one of offsets and k > 0 must be given.  A slot of s records receives the first min(s, count) neighbours
+ * in order and {+inf, CGRT_NO_PRIM} in its remaining entries; counts[i] (may be NULL in the list calls) is always the full number of
+ * neighbours.  Every record of every slot is written, nothing outside the slots.  The host forms check that offsets start at 0, do not
+ * decrease and end <= capacity.  The device form never reads the offsets on the host: the kernel treats a decreasing pair as an empty
+ * slot and clamps both ends to capacity, so no offset table makes it write outside the first `capacity` records of d_out (slots that
+ * overlap are written by several queries, in no defined order).
+ * Consequences.
+ *   N1  With k = 1 and radius2 == NULL, record i is {dist2, prim_id} of cgrt_closest_points for the same max_dist2, bit for bit; a miss
+ *       is {+inf, CGRT_NO_PRIM}.
+ *   N2  With k > 0 and counts == NULL the call is "the k nearest within r2".
+ *   N3  cgrt_count_neighbors, the exclusive prefix sums of its counts, then cgrt_list_neighbors with those offsets: the full CSR
+ *       neighbour list.
+ * Search.  One query per lane over the structure cgrt_closest_points walks (the reference tree, the in-leaf accelerators, linear leaves
+ * under cgrt_set_leaf_accel(0)) with its box lower bound lb2; a subtree is skipped iff `lb2 > bound` is TRUE.  The bound is r2; while a
+ * slot is full and no count is asked for it shrinks to the largest dist2 kept (non-strictly: an equal-dist2 smaller prim_id still
+ * arrives).  Because lb2 <= dist2 holds in f32 with no slack for every triangle under a box ("Closest-point queries", Exactness), the
+ * result is what cgrt_list_neighbors_brute -- every triangle in turn, same function, same slot rule; a validation path -- returns, byte
+ * for byte, whatever the visiting order.  Non-finite vertices need no other path: a NaN lb2 never culls, and a NaN dist2 never
+ * qualifies.  The walk settings (cgrt_scene_set_walk, cgrt_set_fast_tree, cgrt_set_kernel_shape) do not enter.  A slot is kept sorted
+ * by insertion: a full list of c neighbours costs up to c^2 / 2 record moves.  Envelope and accuracy are those of dist2
+ * ("Closest-point queries"): within 5.66 * 2^-24 * max(1, |p|inf, S) of the radius in distance, membership can differ from the float64
+ * answer (tests/test_neighbors_cpu.py).
+ * cgrt_debug_neighbor_work: a separate counting launch (never part of a timed region); out2 = {node steps, triangles evaluated}, summed
+ * over the n queries.  k = 0: the count search; k > 0: the k-nearest search (k records per query, no counts: the shrinking bound).
+ * Streams.  The host forms (host pointers, synchronous) run on a call lane like cgrt_closest_points: any number of threads may query one
+ * scene at once.  The device forms read no host array and only enqueue on `stream` (NULL = default stream); they are concurrent on one
+ * scene and neither read nor write the prediction record or the frame hints.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene; NULL points or result array (counts of the count calls,
+ * out of the list calls, out2) with n > 0; n > 0x7fffffff; max_dist2 NaN or negative; (list calls) both or neither of offsets and k > 0;
+ * capacity above 2^37 records; with k, n * k > capacity; (host list calls, n > 0) offsets not starting at 0, decreasing, or ending above
+ * capacity; (device forms) a pointer not aligned to its element (4 bytes; 8 for d_offsets).  Then a host-only scene: CGRT_E_NO_DEVICE.
+ * n == 0 succeeds and touches nothing.  Device forms: then d_points (n * 12 bytes), d_radius2 (n * 4), d_offsets ((n + 1) * 8), d_out
+ * (capacity records with offsets, n * k with k) and d_counts (n * 4) checked as device memory of the scene's device, as
+ * cgrt_shade_rays_device checks its buffers.
+ * Not offered: the closest point and the barycentrics per record (cgrt_closest_points has them for the nearest; for the others they are
+ * a function of (p, prim_id)); spheres; a per-query k (offsets give per-query slot sizes); grid forms; enqueued-ticket forms (the device
+ * forms never block); the C++ host mirror. */
+typedef struct CgrtNeighbor {
+    float dist2;      /* |p - q|^2 as "Closest-point queries" defines it; +inf in an unused entry */
+    uint32_t prim_id; /* CGRT_NO_PRIM in an unused entry                                           */
+} CgrtNeighbor;
+int cgrt_count_neighbors(CgrtScene* scene, const float* points, uint64_t n, const float* radius2, float max_dist2, uint32_t* counts);
+int cgrt_count_neighbors_device(CgrtScene* scene, const float* d_points, uint64_t n, const float* d_radius2, float max_dist2, uint32_t* d_counts,
+                                void* stream);
+int cgrt_list_neighbors(CgrtScene* scene, const float* points, uint64_t n, const float* radius2, float max_dist2, const uint64_t* offsets,
+                        uint32_t k, CgrtNeighbor* out, uint64_t capacity, uint32_t* counts);
+int cgrt_list_neighbors_device(CgrtScene* scene, const float* d_points, uint64_t n, const float* d_radius2, float max_dist2,
+                               const uint64_t* d_offsets, uint32_t k, CgrtNeighbor* d_out, uint64_t capacity, uint32_t* d_counts, void* stream);
+int cgrt_list_neighbors_brute(CgrtScene* scene, const float* points, uint64_t n, const float* radius2, float max_dist2, const uint64_t* offsets,
+                              uint32_t k, CgrtNeighbor* out, uint64_t capacity, uint32_t* counts);
+int cgrt_debug_neighbor_work(CgrtScene* scene, const float* points, uint64_t n, const float* radius2, float max_dist2, uint32_t k,
+                             uint64_t* out2);
 
 /* Signed distance and occupancy: "how far is this point from the surface, and is it inside?" -- for point lists
  * and for regular grids (a mesh turned into an SDF volume).  The compute_signed_distance / compute_occupancy pair of other ray-casting
