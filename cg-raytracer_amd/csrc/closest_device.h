@@ -1,10 +1,12 @@
 // closest_device.h -- the device functions of the closest-point search (include/cgrt.h "Closest-point queries"):
-// the per-triangle function, the box lower bound, the child ordering and the search stack's encoding.  closest_kernels.hip (k_closest,
-// k_closest_brute) and sdf_kernels.hip (phase 1 of k_sdf) call these very functions, so both compute the same dist2, bit for bit.
+// the per-triangle function, the box lower bound, the child ordering, the search stack's encoding and the walk itself (closest_walk).
+// closest_kernels.hip (k_closest, k_closest_brute), sdf_kernels.hip (phase 1 of k_sdf) and neighbor_kernels.hip (k_neighbors) call these
+// very functions, so all compute the same dist2, bit for bit, and visit the tree under the same rule.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "closest_kernels.h"
+#include "query_device.h"
 
 namespace cgrt {
 
@@ -148,8 +150,106 @@ __device__ __forceinline__ void order2(uint32_t& ka, uint32_t& ra, uint32_t& kb,
     ka = k0, kb = k1, ra = q0, rb = q1;
 }
 
-__device__ __forceinline__ bool finite3(const float x, const float y, const float z) {
-    return fabsf(x) <= 3.402823466e+38f && fabsf(y) <= 3.402823466e+38f && fabsf(z) <= 3.402823466e+38f;
+// The search of one query p, from the root (S.root_ref != REF_NONE) over the structure every scene has -- the reference tree's
+// NodePackets (two child boxes), then the leaves' 4-wide accelerators (SubNode pairs) down to runs of 1..32 records, or plain LeafRec
+// ranges where a leaf has no accelerator.  A subtree is skipped iff `lb2 > bound()` is TRUE; bound() is re-read at every use, because
+// records(first, count) -- the caller's evaluation of records [first, first + count) -- may lower it.  The nearest child is entered, the
+// others are deferred farthest-first with their lb2 and culled again on pop.  stk: the lane's column of a lane-interleaved LDS region,
+// slot s at stk[s * 64]; entry e = slots 2e {ref}, 2e + 1 {lb2}, CLOSEST_STACK_ENTRIES entries.
+template <bool COUNT, class Records, class Bound>
+__device__ __forceinline__ void closest_walk(const SceneDev& S, const float px, const float py, const float pz, uint32_t* const stk,
+                                             const Records& records, const Bound& bound, unsigned long long& c_nodes,
+                                             unsigned long long& c_tris) {
+    uint32_t cur = topo_ref(S.root_ref);
+    int sp = 0;
+    for (;;) {
+        bool pop = true;
+        if (cur & REF_LEAF) {  // a run of 1..32 records
+            const uint32_t first = cur & REF_INDEX26, cnt = ((cur >> 26) & 31u) + 1u;
+            if (COUNT) c_tris += cnt;
+            records(first, cnt);
+        } else if (cur & CL_LEAF) {  // a reference leaf scanned linearly
+            const LeafRec L = S.leaves[cur & ~CL_LEAF];
+            if (COUNT) c_tris += L.count;
+            records(L.first, L.count);
+        } else {
+            if (COUNT) c_nodes++;
+            uint32_t k0, k1, k2 = 0xffffffffu, k3 = 0xffffffffu, f0, f1, f2 = REF_NONE, f3 = REF_NONE;
+            if (cur & CL_SUB) {  // a transposed node (cgrt_layout.h SubNode): lo.x, hi.x, lo.y, hi.y, lo.z, hi.z of the four children, then the references
+                const float4* q = reinterpret_cast<const float4*>(S.subnodes + (cur & ~CL_SUB));
+                const float4 lx = q[0], hx = q[1], ly = q[2], hy = q[3], lz = q[4], hz = q[5];
+                const uint4 m = *reinterpret_cast<const uint4*>(q + 6);
+                const float l0 = box_lb2(lx.x, hx.x, ly.x, hy.x, lz.x, hz.x, px, py, pz);
+                const float l1 = box_lb2(lx.y, hx.y, ly.y, hy.y, lz.y, hz.y, px, py, pz);
+                const float l2 = box_lb2(lx.z, hx.z, ly.z, hy.z, lz.z, hz.z, px, py, pz);
+                const float l3 = box_lb2(lx.w, hx.w, ly.w, hy.w, lz.w, hz.w, px, py, pz);
+                k0 = child_key(m.x, l0, bound());
+                k1 = child_key(m.y, l1, bound());
+                k2 = child_key(m.z, l2, bound());
+                k3 = child_key(m.w, l3, bound());
+                f0 = sub_ref(m.x), f1 = sub_ref(m.y), f2 = sub_ref(m.z), f3 = sub_ref(m.w);  // (only read where the key is not all ones)
+            } else {  // NodePacket: two child boxes {lo.xyz, hi.xyz}
+                const float4* q = reinterpret_cast<const float4*>(S.packets + cur);
+                const float4 a = q[0], b = q[1], c = q[2];
+                const uint4 m = *reinterpret_cast<const uint4*>(q + 3);
+                const float l0 = box_lb2(a.x, a.w, a.y, b.x, a.z, b.y, px, py, pz);
+                const float l1 = box_lb2(b.z, c.y, b.w, c.z, c.x, c.w, px, py, pz);
+                k0 = child_key(m.x, l0, bound());
+                k1 = child_key(m.y, l1, bound());
+                f0 = topo_ref(m.x), f1 = topo_ref(m.y);
+            }
+            // ascending by key: absent and culled children (all ones) last
+            order2(k0, f0, k1, f1);
+            order2(k2, f2, k3, f3);
+            order2(k0, f0, k2, f2);
+            order2(k1, f1, k3, f3);
+            order2(k1, f1, k2, f2);
+            // farthest first, so that the deferred children pop nearest first (a falling bound falls sooner)
+            if (k3 != 0xffffffffu) {
+                stk[(2 * sp) * 64] = f3, stk[(2 * sp + 1) * 64] = k3;
+                sp++;
+            }
+            if (k2 != 0xffffffffu) {
+                stk[(2 * sp) * 64] = f2, stk[(2 * sp + 1) * 64] = k2;
+                sp++;
+            }
+            if (k1 != 0xffffffffu) {
+                stk[(2 * sp) * 64] = f1, stk[(2 * sp + 1) * 64] = k1;
+                sp++;
+            }
+            if (k0 != 0xffffffffu) {
+                cur = f0;
+                pop = false;
+            }
+        }
+        if (pop) {
+            bool got = false;
+            while (sp > 0) {
+                sp--;
+                const uint32_t r = stk[(2 * sp) * 64];
+                const float lb = __uint_as_float(stk[(2 * sp + 1) * 64]);
+                if (!(lb > bound())) {  // the bound may have fallen since the child was deferred
+                    cur = r;
+                    got = true;
+                    break;
+                }
+            }
+            if (!got) break;
+        }
+    }
+}
+
+// The closest-point search proper: the walk with the minimum taken into B, whose d2 is the bound (k_closest, phase 1 of k_sdf).
+template <bool COUNT>
+__device__ __forceinline__ void closest_search(const SceneDev& S, const float px, const float py, const float pz, uint32_t* const stk, Best& B,
+                                               unsigned long long& c_nodes, unsigned long long& c_tris) {
+    closest_walk<COUNT>(
+        S, px, py, pz, stk,
+        [&](const uint32_t first, const uint32_t cnt) {
+            const float4* q = reinterpret_cast<const float4*>(S.tris + first);
+            for (uint32_t k = 0; k < cnt; k++) closest_tri(q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3], px, py, pz, B);
+        },
+        [&]() { return B.d2; }, c_nodes, c_tris);
 }
 
 }  // namespace cgrt

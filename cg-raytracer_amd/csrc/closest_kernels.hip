@@ -9,10 +9,9 @@
 // `lb2 > bound` is TRUE, bound = the best dist2 so far (max_dist2 while nothing has been accepted): under that rule the search returns
 // the brute-force result whatever the visiting order.  Equal dist2 goes to the smaller prim_id.
 //
-// k_closest: one query per lane over the structure every scene has -- the reference tree's NodePackets (two child boxes), then the
-// leaves' 4-wide accelerators (SubNode pairs) down to runs of 1..32 records, or plain LeafRec ranges where a leaf has no accelerator.
-// The nearest child is entered, the others are deferred farthest-first with their lb2 and culled again on pop.  The per-lane stack is
-// lane-interleaved in LDS, two dwords per entry.  k_closest_brute: every record in turn, same function, same rule (validation).
+// k_closest: one query per lane, closest_device.h's closest_search (closest_walk with the minimum taken into a Best) over the structure
+// every scene has.  The per-lane stack is lane-interleaved in LDS, two dwords per entry.  k_closest_brute: every record in turn, same
+// function, same rule (validation).
 #include <hip/hip_runtime.h>
 
 #include "closest_device.h"
@@ -56,87 +55,7 @@ __global__ __launch_bounds__(CGRT_CLOSEST_BLOCK) void k_closest(const SceneDev S
     B.prim = REF_NONE;
     B.qx = B.qy = B.qz = B.v = B.w = 0.0f;
     unsigned long long c_nodes = 0, c_tris = 0;
-    if (S.root_ref != REF_NONE && finite3(px, py, pz)) {
-        uint32_t cur = topo_ref(S.root_ref);
-        int sp = 0;
-        for (;;) {
-            bool pop = true;
-            if (cur & REF_LEAF) {  // a run of 1..32 records
-                const uint32_t first = cur & REF_INDEX26, cnt = ((cur >> 26) & 31u) + 1u;
-                const float4* q = reinterpret_cast<const float4*>(S.tris + first);
-                if (COUNT) c_tris += cnt;
-                for (uint32_t k = 0; k < cnt; k++) closest_tri(q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3], px, py, pz, B);
-            } else if (cur & CL_LEAF) {  // a reference leaf scanned linearly
-                const LeafRec L = S.leaves[cur & ~CL_LEAF];
-                const float4* q = reinterpret_cast<const float4*>(S.tris + L.first);
-                if (COUNT) c_tris += L.count;
-                for (uint32_t k = 0; k < L.count; k++) closest_tri(q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3], px, py, pz, B);
-            } else {
-                if (COUNT) c_nodes++;
-                uint32_t k0, k1, k2 = 0xffffffffu, k3 = 0xffffffffu, f0, f1, f2 = REF_NONE, f3 = REF_NONE;
-                if (cur & CL_SUB) {  // a transposed node (cgrt_layout.h SubNode): lo.x, hi.x, lo.y, hi.y, lo.z, hi.z of the four children, then the references
-                    const float4* q = reinterpret_cast<const float4*>(S.subnodes + (cur & ~CL_SUB));
-                    const float4 lx = q[0], hx = q[1], ly = q[2], hy = q[3], lz = q[4], hz = q[5];
-                    const uint4 m = *reinterpret_cast<const uint4*>(q + 6);
-                    const float l0 = box_lb2(lx.x, hx.x, ly.x, hy.x, lz.x, hz.x, px, py, pz);
-                    const float l1 = box_lb2(lx.y, hx.y, ly.y, hy.y, lz.y, hz.y, px, py, pz);
-                    const float l2 = box_lb2(lx.z, hx.z, ly.z, hy.z, lz.z, hz.z, px, py, pz);
-                    const float l3 = box_lb2(lx.w, hx.w, ly.w, hy.w, lz.w, hz.w, px, py, pz);
-                    k0 = child_key(m.x, l0, B.d2);
-                    k1 = child_key(m.y, l1, B.d2);
-                    k2 = child_key(m.z, l2, B.d2);
-                    k3 = child_key(m.w, l3, B.d2);
-                    f0 = sub_ref(m.x), f1 = sub_ref(m.y), f2 = sub_ref(m.z), f3 = sub_ref(m.w);  // (only read where the key is not all ones)
-                } else {  // NodePacket: two child boxes {lo.xyz, hi.xyz}
-                    const float4* q = reinterpret_cast<const float4*>(S.packets + cur);
-                    const float4 a = q[0], b = q[1], c = q[2];
-                    const uint4 m = *reinterpret_cast<const uint4*>(q + 3);
-                    const float l0 = box_lb2(a.x, a.w, a.y, b.x, a.z, b.y, px, py, pz);
-                    const float l1 = box_lb2(b.z, c.y, b.w, c.z, c.x, c.w, px, py, pz);
-                    k0 = child_key(m.x, l0, B.d2);
-                    k1 = child_key(m.y, l1, B.d2);
-                    f0 = topo_ref(m.x), f1 = topo_ref(m.y);
-                }
-                // ascending by key: absent and culled children (all ones) last
-                order2(k0, f0, k1, f1);
-                order2(k2, f2, k3, f3);
-                order2(k0, f0, k2, f2);
-                order2(k1, f1, k3, f3);
-                order2(k1, f1, k2, f2);
-                // farthest first, so that the deferred children pop nearest first
-                if (k3 != 0xffffffffu) {
-                    stk[(2 * sp) * 64] = f3, stk[(2 * sp + 1) * 64] = k3;
-                    sp++;
-                }
-                if (k2 != 0xffffffffu) {
-                    stk[(2 * sp) * 64] = f2, stk[(2 * sp + 1) * 64] = k2;
-                    sp++;
-                }
-                if (k1 != 0xffffffffu) {
-                    stk[(2 * sp) * 64] = f1, stk[(2 * sp + 1) * 64] = k1;
-                    sp++;
-                }
-                if (k0 != 0xffffffffu) {
-                    cur = f0;
-                    pop = false;
-                }
-            }
-            if (pop) {
-                bool got = false;
-                while (sp > 0) {
-                    sp--;
-                    const uint32_t r = stk[(2 * sp) * 64];
-                    const float lb = __uint_as_float(stk[(2 * sp + 1) * 64]);
-                    if (!(lb > B.d2)) {  // the bound may have fallen since the child was deferred
-                        cur = r;
-                        got = true;
-                        break;
-                    }
-                }
-                if (!got) break;
-            }
-        }
-    }
+    if (S.root_ref != REF_NONE && finite3(px, py, pz)) closest_search<COUNT>(S, px, py, pz, stk, B, c_nodes, c_tris);
     store_result(out, i, B);
     if (COUNT) {
         atomicAdd(counters, c_nodes);

@@ -1,12 +1,13 @@
 // crossing_device.h -- the device functions of the crossing search (include/cgrt.h "Crossing queries"): the
-// definition on a TriEval with the slot rule, the evaluation of a run of records, the search stack's encoding and the NodePacket step.
-// crossing_kernels.hip (k_crossings) and sdf_kernels.hip (the parity walks of k_sdf) call these very functions, so both accept the same
-// triangles for a ray.
+// definition on a TriEval, the evaluation of a run of records, the search stack's encoding, the NodePacket step and the walk itself
+// (cross_walk).  crossing_kernels.hip (k_crossings) and sdf_kernels.hip (the parity walks of k_sdf) call these very functions, so both
+// accept the same triangles for a ray.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "closest_kernels.h"
 #include "crossing_kernels.h"
+#include "query_device.h"
 #include "walk_exact.h"
 
 namespace cgrt {
@@ -32,52 +33,17 @@ __device__ __forceinline__ uint32_t cross_topo_ref(const uint32_t r) {  // a chi
     return (r & REF_LEAF_ACCEL) ? (r & REF_INDEX26) : (CR_LEAF | (r & ~REF_LEAF));
 }
 
-// A lane's slot and its running state.
-struct CrossSlot {
-    uint32_t* rec;           // the slot's first record, two dwords per record {t, prim_id}
-    unsigned long long len;  // records the slot holds
-    uint32_t room;           // min(len, 2^32 - 1): a ray has fewer crossings than that
-    uint32_t kept;           // records rec[0 .. kept) are the smallest `kept` crossings so far, in order
-    uint32_t count;          // all crossings so far
-    float t_in;              // the ray's own t: what a crossing is tested against
-    float bound;             // what boxes are tested against: t_in, or the largest t kept once the slot is full (shrink)
-    bool shrink;
-};
-
-__device__ __forceinline__ bool cross_before(const float ta, const uint32_t pa, const float tb, const uint32_t pb) {
-    return ta < tb || (ta == tb && pa < pb);
-}
-
-// include/cgrt.h "Crossing queries": the definition on a TriEval, then the slot rule
+// include/cgrt.h "Crossing queries": the definition on a TriEval; a crossing is taken into the slot under its t (query_device.h slot_take)
 template <bool LIST>
-__device__ __forceinline__ void cross_apply(const TriEval& E, const uint32_t prim, CrossSlot& Q) {
-    const bool ok = E.inside && (E.onp || (E.den_ok && !(E.tt < 0) && !(E.tt >= Q.t_in)));
-    if (!ok) return;
-    Q.count++;
-    if (!LIST || Q.room == 0u) return;
-    size_t j = Q.kept;
-    if (Q.kept == Q.room) {  // full: the largest one leaves, unless that is the new one
-        if (!cross_before(E.tt, prim, __uint_as_float(Q.rec[2 * (j - 1)]), Q.rec[2 * (j - 1) + 1])) return;
-        j--;
-    } else {
-        Q.kept++;
-    }
-    while (j > 0) {
-        const uint32_t pt = Q.rec[2 * (j - 1)], pp = Q.rec[2 * (j - 1) + 1];
-        if (!cross_before(E.tt, prim, __uint_as_float(pt), pp)) break;
-        Q.rec[2 * j] = pt;
-        Q.rec[2 * j + 1] = pp;
-        j--;
-    }
-    Q.rec[2 * j] = __float_as_uint(E.tt);
-    Q.rec[2 * j + 1] = prim;
-    if (Q.shrink && Q.kept == Q.room) Q.bound = __uint_as_float(Q.rec[2 * (size_t)(Q.room - 1u)]);
+__device__ __forceinline__ void cross_apply(const TriEval& E, const uint32_t prim, QuerySlot& Q) {
+    const bool ok = E.inside && (E.onp || (E.den_ok && !(E.tt < 0) && !(E.tt >= Q.limit)));
+    if (ok) slot_take<LIST>(E.tt, prim, Q);
 }
 
 // records [first, first + n): the first two on the packed pipe when that is the whole run, as the walks evaluate runs
 template <bool LIST>
 __device__ __forceinline__ void cross_records(const SceneDev& S, const unsigned long long first, const uint32_t n, const F3 o, const F3 d,
-                                              CrossSlot& Q) {
+                                              QuerySlot& Q) {
     const float4* q = reinterpret_cast<const float4*>(S.tris + first);
     if (n <= 2u) {
         const uint32_t j = (n > 1u) ? 4u : 0u;
@@ -115,6 +81,49 @@ __device__ __forceinline__ void cross_packet_step(const SceneDev& S, const RayPr
         sp++;
     }
     cur = second_first ? r1 : (h0 ? r0 : REF_NONE);
+}
+
+// The search of one ray {o, d, Q.limit}, from the root (S.root_ref != REF_NONE): every triangle the definition can accept reaches
+// cross_apply, in any order.  The structure is the one closest_walk visits; boxes are tested with the conservative test alone, bounded by
+// Q.bound.  BRUTE, and a ray outside that test's envelope (RayPre::regular false), scan every record instead.  stk: the lane's column of
+// a lane-interleaved LDS region, entry e at stk[e * 64], CLOSEST_STACK_ENTRIES entries (not touched under BRUTE).
+template <bool LIST, bool COUNT, bool BRUTE>
+__device__ __forceinline__ void cross_walk(const SceneDev& S, const F3 o, const F3 d, uint32_t* const stk, QuerySlot& Q,
+                                           unsigned long long& c_nodes, unsigned long long& c_tris) {
+    const RayPre P = make_raypre(S, o, d, Q.limit);
+    if (BRUTE || !P.regular) {
+        if (COUNT) c_tris += S.ntris;
+        for (uint32_t r = 0; r < S.ntris; r += SUB_RUN_MAX)
+            cross_records<LIST>(S, (unsigned long long)S.tri_base + r, min(SUB_RUN_MAX, S.ntris - r), o, d, Q);
+        return;
+    }
+    LaneCounters cnt;
+    uint32_t cur = cross_topo_ref(S.root_ref);
+    int sp = 0;
+    for (;;) {
+        if (cur == REF_NONE) {
+            if (sp == 0) break;
+            sp--;
+            cur = stk[sp * CGRT_STRIDE];
+        }
+        if (cur & REF_LEAF) {  // a run of 1..32 records
+            if (COUNT) c_tris += run_count(cur);
+            cross_records<LIST>(S, run_first(cur), run_count(cur), o, d, Q);
+            cur = REF_NONE;
+        } else if (cur & CR_LEAF) {  // a reference leaf scanned linearly
+            const LeafRec L = S.leaves[cur & ~CR_LEAF];
+            if (COUNT) c_tris += L.count;
+            for (uint32_t r = 0; r < L.count; r += SUB_RUN_MAX)
+                cross_records<LIST>(S, (unsigned long long)L.first + r, min(SUB_RUN_MAX, L.count - r), o, d, Q);
+            cur = REF_NONE;
+        } else if (cur & CR_PACKET) {  // NodePacket: two child boxes {lo.xyz, hi.xyz}
+            if (COUNT) c_nodes++;
+            cross_packet_step(S, P, Q.bound, cur, sp, stk);
+        } else {  // an accelerator node: the nearest hit child becomes cur, the others are deferred
+            sub_node_step<COUNT>(S, P, Q.bound, cur, sp, stk, cnt);
+        }
+    }
+    if (COUNT) c_nodes += cnt.sub;
 }
 
 }  // namespace cgrt

@@ -3,13 +3,13 @@
 // (t, prim_id) order.  A crossing is a pure function of (ray, triangle) -- TriEval of walk_exact.h, unchanged -- so the search only has to
 // reach every acceptable triangle, in any order:
 //
-// k_crossings: one ray per lane over the structure every scene has, as k_closest walks it -- the reference tree's NodePackets, then the
-// leaves' 4-wide accelerators down to runs of records, or plain LeafRec ranges where a leaf has no accelerator.  Boxes are tested with
-// the conservative test alone (walk_exact.h make_raypre / slab_cons / sub_node_step: no box that holds a point the triangle arithmetic
+// k_crossings: one ray per lane, crossing_device.h's cross_walk over the structure every scene has, as closest_walk visits it -- the
+// reference tree's NodePackets, then the leaves' 4-wide accelerators down to runs of records, or plain LeafRec ranges where a leaf has
+// no accelerator.  Boxes are tested with the conservative test alone (walk_exact.h make_raypre / slab_cons / sub_node_step: no box that holds a point the triangle arithmetic
 // could accept is rejected), bounded by the ray's own t; while a slot is full the bound shrinks to the largest t kept, non-strictly, so
 // an equal-t smaller prim_id still arrives.  A ray outside that test's envelope (RayPre::regular false) scans every record itself.
 // The per-lane stack is lane-interleaved in LDS, one dword per entry.  A lane owns its slot of the output and keeps it sorted in global
-// memory by insertion, dropping the largest when full: no atomics, no scratch.
+// memory by insertion, dropping the largest when full: no atomics, no scratch (query_device.h QuerySlot).
 // k_crossings<.., BRUTE>: every record in turn for every ray, same function, same slot rule (validation, and the whole call on scenes
 // where the conservative argument does not hold: capi.cpp crossing_brute_scene).
 #include <hip/hip_runtime.h>
@@ -30,77 +30,22 @@ __global__ __launch_bounds__(CGRT_CROSS_BLOCK) void k_crossings(const SceneDev S
     const unsigned long long i = (unsigned long long)blockIdx.x * CGRT_CROSS_BLOCK + threadIdx.x;
     if (i >= n) return;
     const F3 o = f3(rays[7 * i], rays[7 * i + 1], rays[7 * i + 2]), d = f3(rays[7 * i + 3], rays[7 * i + 4], rays[7 * i + 5]);
-    CrossSlot Q;
-    Q.t_in = rays[7 * i + 6];
-    Q.bound = Q.t_in;
-    Q.kept = 0u;
-    Q.count = 0u;
-    Q.rec = out;
-    Q.len = 0ull;
-    Q.shrink = LIST && counts == nullptr;  // the full count needs every crossing, whatever the slot holds
-    if (LIST) {
-        unsigned long long b, e;
-        if (offsets) {
-            b = offsets[i];
-            e = offsets[i + 1];
-            if (e < b) e = b;  // a decreasing pair: an empty slot
-        } else {
-            b = i * k;
-            e = b + k;
-        }
-        b = b < capacity ? b : capacity;
-        e = e < capacity ? e : capacity;
-        Q.rec = out + 2 * b;
-        Q.len = e - b;
-    }
-    Q.room = Q.len < 0xffffffffull ? (uint32_t)Q.len : 0xffffffffu;
-    LaneCounters cnt;
+    uint32_t* const stk = s_stk + (threadIdx.x >> 6) * (CLOSEST_STACK_ENTRIES * 64) + (threadIdx.x & 63u);
+    QuerySlot Q;
+    const bool wanted = slot_open<LIST>(Q, rays[7 * i + 6], out, offsets, k, capacity, counts != nullptr, i);
     unsigned long long c_nodes = 0, c_tris = 0;
-    const bool wanted = !LIST || counts != nullptr || Q.room != 0u;  // (an empty slot without a count asks for nothing)
     if (S.root_ref != REF_NONE && wanted) {
-        const RayPre P = make_raypre(S, o, d, Q.t_in);
-        if (BRUTE || !P.regular) {
+        if (BRUTE) {  // cross_walk's own scan, written out: through the call these kernels take two more VGPRs and lose a wave per SIMD
             if (COUNT) c_tris += S.ntris;
             for (uint32_t r = 0; r < S.ntris; r += SUB_RUN_MAX)
                 cross_records<LIST>(S, (unsigned long long)S.tri_base + r, min(SUB_RUN_MAX, S.ntris - r), o, d, Q);
         } else {
-            uint32_t* const stk = s_stk + (threadIdx.x >> 6) * (CLOSEST_STACK_ENTRIES * 64) + (threadIdx.x & 63u);
-            uint32_t cur = cross_topo_ref(S.root_ref);
-            int sp = 0;
-            for (;;) {
-                if (cur == REF_NONE) {
-                    if (sp == 0) break;
-                    sp--;
-                    cur = stk[sp * CGRT_STRIDE];
-                }
-                if (cur & REF_LEAF) {  // a run of 1..32 records
-                    if (COUNT) c_tris += run_count(cur);
-                    cross_records<LIST>(S, run_first(cur), run_count(cur), o, d, Q);
-                    cur = REF_NONE;
-                } else if (cur & CR_LEAF) {  // a reference leaf scanned linearly
-                    const LeafRec L = S.leaves[cur & ~CR_LEAF];
-                    if (COUNT) c_tris += L.count;
-                    for (uint32_t r = 0; r < L.count; r += SUB_RUN_MAX)
-                        cross_records<LIST>(S, (unsigned long long)L.first + r, min(SUB_RUN_MAX, L.count - r), o, d, Q);
-                    cur = REF_NONE;
-                } else if (cur & CR_PACKET) {  // NodePacket: two child boxes {lo.xyz, hi.xyz}
-                    if (COUNT) c_nodes++;
-                    cross_packet_step(S, P, Q.bound, cur, sp, stk);
-                } else {  // an accelerator node: the nearest hit child becomes cur, the others are deferred
-                    sub_node_step<COUNT>(S, P, Q.bound, cur, sp, stk, cnt);
-                }
-            }
+            cross_walk<LIST, COUNT, false>(S, o, d, stk, Q, c_nodes, c_tris);
         }
     }
-    if (LIST) {
-        for (unsigned long long j = Q.kept; j < Q.len; j++) {  // the rest of the slot: {+inf, CGRT_NO_PRIM}
-            Q.rec[2 * j] = 0x7f800000u;
-            Q.rec[2 * j + 1] = 0xffffffffu;
-        }
-    }
-    if (counts) counts[i] = Q.count;
+    slot_close<LIST>(Q, counts, i);
     if (COUNT) {
-        atomicAdd(counters, c_nodes + cnt.sub);
+        atomicAdd(counters, c_nodes);
         atomicAdd(counters + 1, c_tris);
     }
 }

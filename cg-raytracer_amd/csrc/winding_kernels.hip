@@ -13,10 +13,11 @@
 // is accepted: the additions are not reordered to mend it, the bytes depend on their order (DESIGN.md 5.25 has the work counters).
 // Every sum's association is include/cgrt.h's; nothing is contracted (the Makefile's -ffp-contract=off).
 // A cluster is one 32-byte load, a record the three 16-byte loads that hold its vertices (its last quarter is not read).
-// GRID: the lane makes its point from its grid index (a copy of sdf_kernels.hip's brick mapping: a wave = a 4 x 4 x 4 brick, so that a
-// wave's 64 walks open the same clusters).
+// GRID: the lane makes its point from its grid index (query_device.h brick_index and grid_coord, as k_sdf does: a wave = a 4 x 4 x 4
+// brick, so that a wave's 64 walks open the same clusters).
 #include <hip/hip_runtime.h>
 
+#include "query_device.h"
 #include "winding_kernels.h"
 
 namespace cgrt {
@@ -55,23 +56,18 @@ __global__ __launch_bounds__(CGRT_WINDING_BLOCK) void k_winding(const WindingArg
         i = (unsigned long long)blockIdx.x * CGRT_WINDING_BLOCK + threadIdx.x;
         if (i >= A.n) return;
         px = A.points[3 * i], py = A.points[3 * i + 1], pz = A.points[3 * i + 2];
-    } else {  // a block: 8 x 4 x 4 grid points, wave w the brick at x offset 4w, lane l at {l & 3, (l >> 2) & 3, l >> 4}
+    } else {
         const uint32_t nx = A.dims[0], ny = A.dims[1], nz = A.dims[2];
-        const uint32_t bx = (nx + 7u) >> 3, by = (ny + 3u) >> 2;
-        const uint32_t b = blockIdx.x, bxi = b % bx, rest = b / bx, byi = rest % by, bzi = rest / by;
-        const uint32_t ix = bxi * 8u + (threadIdx.x >> 6) * 4u + (threadIdx.x & 3u);
-        const uint32_t iy = byi * 4u + ((threadIdx.x >> 2) & 3u);
-        const uint32_t iz = bzi * 4u + ((threadIdx.x >> 4) & 3u);
-        if (ix >= nx || iy >= ny || iz >= nz) return;  // beyond the grid's edge
+        uint32_t ix, iy, iz;
+        if (!brick_index(nx, ny, nz, ix, iy, iz)) return;
         i = ((unsigned long long)iz * ny + iy) * nx + ix;
-        // origin + (float)index * spacing: the product rounded, then the sum (an index is below 2^24: exact as f32)
-        px = __fadd_rn(A.origin[0], __fmul_rn((float)ix, A.spacing[0]));
-        py = __fadd_rn(A.origin[1], __fmul_rn((float)iy, A.spacing[1]));
-        pz = __fadd_rn(A.origin[2], __fmul_rn((float)iz, A.spacing[2]));
+        px = grid_coord(A.origin[0], ix, A.spacing[0]);
+        py = grid_coord(A.origin[1], iy, A.spacing[1]);
+        pz = grid_coord(A.origin[2], iz, A.spacing[2]);
     }
     unsigned long long c_clusters = 0, c_dipoles = 0, c_tris = 0;
     float acc = 0.0f;
-    const bool finite = fabsf(px) < __builtin_inff() && fabsf(py) < __builtin_inff() && fabsf(pz) < __builtin_inff();
+    const bool finite = finite3(px, py, pz);
     if (A.ntris != 0u && finite) {
         const float4* const recs = reinterpret_cast<const float4*>(A.recs);
         if (BRUTE) {
