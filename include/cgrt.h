@@ -914,7 +914,9 @@ int cgrt_debug_crossing_work(CgrtScene* scene, const CgrtRay* rays, uint64_t n, 
  * specification.
  * Definition.  For a query point p with bound r2, triangle k is a NEIGHBOUR iff `dist2_k <= r2` is true, dist2_k being exactly the dist2
  * of "Closest-point queries": the same operations, the same clamp, a pure function of (p, triangle) -- no tree, no visiting order, no
- * running minimum enters.  A NaN dist2 never qualifies.  Spheres are ignored.
+ * running minimum enters.  A NaN dist2 never qualifies.  A dist2 of +inf (a finite point and finite vertices whose squares overflow: far
+ * outside the envelope) qualifies under r2 = +inf, as `inf <= inf` is true, and under no other bound; all such records tie on dist2, so
+ * they follow the finite ones in prim_id order, and a full slot whose largest dist2 is +inf culls nothing.  Spheres are ignored.
  * Bound.  r2 = radius2 ? radius2[i] : max_dist2 (radius2: n f32, or NULL).  The scalar max_dist2 is checked as cgrt_closest_points checks
  * it (NaN or negative: CGRT_E_ARG; +inf: unbounded), also where radius2 is given.  A per-query radius2[i] for which `radius2[i] >= 0` is
  * false (NaN or negative) gives that query no neighbours: this is decided in the kernel, identically in the host and the device forms;
@@ -1076,8 +1078,28 @@ int cgrt_debug_set_sdf_grid_mapping(int linear);
  * and w = acc * (1 / (4 pi)) as above.  With beta = +inf no cluster is far (inf * 0 is a NaN) and the walk performs the brute form's
  * additions in the brute form's order: it returns the brute form's bytes.  inside = fabsf(w) > threshold, for every point.
  * A non-finite p gets w = 0 without a walk; in a scene without meshes every point gets 0.  Spheres are ignored.  A scene with non-finite
- * vertices may give NaN (inside = 0 then); no call faults or hangs over it.  As in the other point queries the values are meaningful
- * while no intermediate overflows (|p - vertex|^3 within f32).
+ * vertices may give NaN (inside = 0 then); no call faults or hangs over it.
+ * Envelope.  num, the four terms of den and the dipole's d2 * sqrtf(d2) are products of THREE lengths: they grow as the third power of
+ * the scene's size.  With M the largest and m the smallest |p - vertex| of the point, E the largest and e the smallest non-zero triangle
+ * edge, a the sum of the triangle areas and D the diagonal of the scene's box:
+ *   upper edge  8 * M^3 <= FLT_MAX         (every product and partial sum of num and den is at most 4 M^3; d2 * sqrtf(d2) <= M^3)
+ *               2 * a * M <= FLT_MAX       (|n| <= a: the dipole's numerator)   and   2 * beta^2 * D^2 <= FLT_MAX   (beta2 * r2 finite)
+ *               E^2 * M <= 2^-18 * FLT_MAX (|num| <= E^2 * M: atan2f, the one operation not pinned here, sees no argument pair it must screen)
+ *   lower edge  m^3 >= FLT_MIN             ((la * lb) * lc, the one term of den nothing cancels, stays normal)
+ *               e^3 >= 2^12 * FLT_MIN      (num is six tetrahedron volumes: one as small as the smallest edge in all its extents, and
+ *                                           products down to 2^-12 of it, stay normal; a far cluster has d2 * sqrtf(d2) > e^3 / 8)
+ * e.g. a unit-sized mesh with edges between 1/64 and 1/8 and points within a hundred extents: about 2^-32 .. 2^+35.  Inside the envelope multiplying
+ * every position and every point (a grid's origin and spacing) by 2^k is an exact symmetry: the cluster tree is the power-of-two image
+ * (c * 2^k; r2 and n * 2^2k), every far decision and so every work counter is the same, and w is the SAME float, bit for bit, where
+ * atan2f(2^j y, 2^j x) == atan2f(y, x) -- which held for every point tested on the device and holds for numpy's float32 arctan2 within
+ * the third upper line.  The first upper lines are a proof; the third and the second lower line are margins (a point in a triangle's
+ * plane has num = 0 in the reals, and a product far below e^3 is then rounded as a subnormal).  The record order is the BVH builder's and
+ * is not part of this envelope: on meshes of many small triangles it changes earlier (a 16 311-triangle mesh with slivers: below 2^-20
+ * and above 2^33).  Outside the envelope the bytes are still the defined ones on every path -- the tree form at beta = +inf returns the
+ * brute form's bytes, inf and NaN sums included, and the counters stay those of the definition -- but w loses its meaning silently:
+ * below, num and den underflow and w tends to 0 (unit-sized meshes: errors of 4e-5 at 2^-40, 4e-3 at 2^-42; at 2^-70 every point inside
+ * a unit cube reads 0); above, errors of 0.1 from 2^42 on, and NaN once the sums overflow (every point at 2^62; inside = 0 for a NaN).
+ * DESIGN.md 5.25 has the table; tests/test_query_scale_cpu.py and _gpu.py hold both edges.
  * Parameters.  beta >= 1 (the opening ratio: a cluster is replaced by its dipole from beta cluster radii on; larger = more exact, more
  * work; +inf allowed), 0 = CGRT_WINDING_DEFAULT_BETA; NaN or anything else below 1 -> CGRT_E_ARG.  threshold: taken as given (a NaN
  * makes every inside 0).  params == NULL: {2.0f, 0.5f}.  The brute entry reads only the threshold.

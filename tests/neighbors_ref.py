@@ -26,8 +26,9 @@ def bounds(n, radius2=None, max_dist2=np.inf):
     return r
 
 
-def membership(sd, points, r2, chunk_elems=1 << 18):
-    """Yields (first query, dist2 (q, T) float32, member (q, T) bool) for chunks of the queries."""
+def membership(sd, points, r2, chunk_elems=1 << 18, dist2=None):
+    """Yields (first query, dist2 (q, T) float32, member (q, T) bool) for chunks of the queries.  dist2: a dict that keeps every chunk's
+    dist2 for a later call on the same scene and points (another radius); the chunks are not changed."""
     p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
     T = int(np.asarray(sd.tri).reshape(-1, 3).shape[0])
     if T == 0 or len(p) == 0:
@@ -37,18 +38,23 @@ def membership(sd, points, r2, chunk_elems=1 << 18):
     with np.errstate(all="ignore"):
         for s in range(0, len(p), step):
             pp, rr = p[s : s + step], r2[s : s + step]
-            _, d2, _, _, _ = cr.closest_tri32(pp[:, None, :], a, b, c)
+            if dist2 is not None and s in dist2:
+                d2 = dist2[s]
+            else:
+                _, d2, _, _, _ = cr.closest_tri32(pp[:, None, :], a, b, c)
+                if dist2 is not None:
+                    dist2[s] = d2
             live = np.isfinite(pp).all(axis=1) & (rr >= F32(0.0))  # (a NaN radius compares false)
             yield s, d2, (d2 <= rr[:, None]) & live[:, None]  # (a NaN dist2 never qualifies)
 
 
-def neighbors(sd, points, radius2=None, max_dist2=np.inf):
+def neighbors(sd, points, radius2=None, max_dist2=np.inf, dist2=None):
     """The full answer by the definition: (offsets (n + 1,) int64, records NEIGHBOR_DTYPE) -- query i's neighbours, in (dist2, prim_id)
-    order, are records[offsets[i]:offsets[i + 1]]; its count is offsets[i + 1] - offsets[i]."""
+    order, are records[offsets[i]:offsets[i + 1]]; its count is offsets[i + 1] - offsets[i].  dist2: membership's."""
     n = len(np.asarray(points, np.float32).reshape(-1, 3))
     counts = np.zeros(n, np.int64)
     parts = []
-    for s, d2, ok in membership(sd, points, bounds(n, radius2, max_dist2)):
+    for s, d2, ok in membership(sd, points, bounds(n, radius2, max_dist2), dist2=dist2):
         counts[s : s + len(ok)] = ok.sum(axis=1)
         rows, prims = np.nonzero(ok)
         d = d2[rows, prims]

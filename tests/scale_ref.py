@@ -5,7 +5,9 @@ Multiplying every position, every query point and every ray origin by 2^k change
 intermediate of the definition overflows or becomes subnormal -- every float32 operation of the definitions rounds the same way: prim_id,
 barycentrics, counts, orders and `inside` are unchanged, points, t and sdf are multiplied by 2^k, dist2 by 2^2k, exactly.  The predicates
 below state that per record; `in_envelope` is the headers' envelope paragraph in code.  Beside them what a sign test needs: `is_closed`,
-the float64 generalised winding number and queries just off the surface."""
+the float64 generalised winding number and queries just off the surface.
+The neighbour lists share dist2's envelope (`covariant_neighbors`).  The winding numbers (5.25) have one of their own,
+cubic where the others are quartic (`in_winding_envelope`, `covariant_winding_tree`): inside it w is not scaled but unchanged."""
 import dataclasses
 
 import numpy as np
@@ -15,6 +17,7 @@ import closest_ref as cr
 F32 = np.float32
 FLT_MAX = float(np.finfo(np.float32).max)
 FLT_MIN = float(np.finfo(np.float32).tiny)  # 2^-126, the smallest normal
+ATAN_HEADROOM = 2.0 ** 18  # the winding numbers' upper edge: how far atan2f's smaller argument stays below FLT_MAX (see in_winding_envelope)
 HEADROOM = 2.0 ** 12  # the lower edge: what stays normal below the smallest triangle's (2 * area)^2 (see in_envelope)
 
 
@@ -83,6 +86,31 @@ def covariant_sdf(a, b, k):
     return (np.asarray(i0) == np.asarray(ik)) & _bits_eq(_ld(s0, k), sk)
 
 
+def covariant_neighbors(full0, fullk, k):
+    """(offsets, records) of neighbour lists (neighbors_ref.neighbors, Scene.list_neighbors; slots of any size described by their
+    offsets) at scale 1 and at scale 2^k, the radius multiplied by 2^2k: the same count, the same prim_id order, dist2 = ldexp(dist2_0,
+    2k) (+inf of an unused entry stays +inf).  (n,) bool, one verdict per query."""
+    (o0, rec0), (ok_, reck) = full0, fullk
+    o0, ok_ = np.asarray(o0, np.int64), np.asarray(ok_, np.int64)
+    good = np.diff(o0) == np.diff(ok_)
+    for i in np.flatnonzero(good):
+        a, b = rec0[o0[i] : o0[i + 1]], reck[ok_[i] : ok_[i + 1]]
+        good[i] = bool((a["prim_id"] == b["prim_id"]).all() and _bits_eq(_ld(a["dist2"], 2 * k), b["dist2"]).all())
+    return good
+
+
+def covariant_winding_tree(tree0, treek, k):
+    """Scene.debug_winding_tree at scale 1 and at scale 2^k: the same record order and level table, every centre multiplied by 2^k,
+    every r2 and every area vector by 2^2k, by bits.  One bool."""
+    if not (np.array_equal(tree0["record_prims"], treek["record_prims"]) and np.array_equal(tree0["level_offsets"], treek["level_offsets"])):
+        return False
+    c0, ck = np.asarray(tree0["clusters"], np.float32).reshape(-1, 8), np.asarray(treek["clusters"], np.float32).reshape(-1, 8)
+    if c0.shape != ck.shape:
+        return False
+    return bool(_bits_eq(_ld(c0[:, 0:3], k), ck[:, 0:3]).all() and _bits_eq(_ld(c0[:, 3:7], 2 * k), ck[:, 3:7]).all()
+                and _bits_eq(c0[:, 7], ck[:, 7]).all())
+
+
 # ---- the envelope ----
 def _triangle_measures(sd):
     """(largest edge length, smallest non-zero (2 * area)^2 = |ab x ac|^2, largest |coordinate|) in float64, over finite triangles."""
@@ -129,6 +157,89 @@ def in_envelope(sd, points):
         ok &= 3.0 * M * M <= FLT_MAX
         ok &= A >= HEADROOM * FLT_MIN
         ok &= (2.0 ** -24 * pmax) ** 2 >= FLT_MIN
+    return ok
+
+
+def _winding_measures(sd):
+    """(smallest non-zero triangle edge, sum of the triangle areas, diagonal of the scene's box) in float64, over finite triangles."""
+    a, b, c = cr.tri_verts(sd, np.float64)
+    with np.errstate(all="ignore"):
+        fin = np.isfinite(a).all(axis=1) & np.isfinite(b).all(axis=1) & np.isfinite(c).all(axis=1)
+        a, b, c = a[fin], b[fin], c[fin]
+        edges = np.concatenate([np.linalg.norm(b - a, axis=1), np.linalg.norm(c - a, axis=1), np.linalg.norm(c - b, axis=1)])
+        area = 0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1).sum()
+    lo, hi = cr.scene_box(sd)
+    return float(edges[edges > 0].min()), float(area), float(np.linalg.norm(hi - lo))
+
+
+def nearest_vertex(sd, points, chunk_elems=1 << 22):
+    """(n,) float64: the distance from every point to the nearest vertex a triangle uses (inf for a non-finite point)."""
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    pos = np.asarray(sd.pos_nrm, np.float64).reshape(-1, 6)[:, 0:3]
+    v = pos[np.unique(np.asarray(sd.tri, np.int64))]
+    v = v[np.isfinite(v).all(axis=1)]
+    out = np.full(len(p), np.inf)
+    step = max(1, chunk_elems // max(len(v), 1))
+    with np.errstate(all="ignore"):
+        for s in range(0, len(p), step):
+            d = p[s : s + step, None, :] - v[None]
+            out[s : s + step] = np.sqrt((d * d).sum(axis=-1).min(axis=1))
+    return np.where(np.isfinite(p).all(axis=1), out, np.inf)
+
+
+def in_winding_envelope(sd, points, beta=2.0):
+    """(n,) bool: the point lies in the envelope of the winding-number queries on this scene -- the "Envelope" paragraph of include/cgrt.h
+    "Winding numbers" in code.  With M(p) the largest |p - vertex| (bounded by the farthest corner of the scene's box), m(p) the smallest
+    |p - vertex|, e the smallest non-zero triangle edge, a the sum of the triangle areas and D the diagonal of the scene's box:
+
+      upper edge   8 * M(p)^3 <= FLT_MAX             |ra|, |rb|, |rc| <= M: every product and partial sum of num = ra . (rb x rc) is at most
+                                                     M^3 (Cauchy-Schwarz, |rb x rc| <= M^2), each of den's four terms is at most M^3 and
+                                                     their partial sums at most 4 M^3; the factor 2 left pays for the roundings.  A centre
+                                                     lies in the box, so the dipole's d2 * sqrtf(d2) <= M^3 too.
+                   2 * a * M(p) <= FLT_MAX           |n| <= a for every cluster: (n.x * d.x + n.y * d.y) + n.z * d.z stays finite
+                   2 * beta^2 * D^2 <= FLT_MAX       r2 <= D^2 (centre and vertices lie in the box): beta2 * r2 of the far test stays finite,
+                                                     so that no cluster is opened only because its product became +inf (beta = +inf: no
+                                                     condition, no cluster is ever far)
+                   E^2 * M(p) <= 2^-18 * FLT_MAX     E the largest triangle edge: |num| = 2 * area * height <= E^2 * M.  atan2f is the one
+                                                     operation the definition does not pin, and an implementation is scale-free only
+                                                     while it need not screen its arguments: numpy's float32 arctan2 returns other bits
+                                                     for (2^j y, 2^j x) than for (y, x) once |y| >= 2^123, or |x| >= 2^123 with |y| >=
+                                                     2^110 (measured; den reaches 4 M^3, so only num can be kept below)
+      lower edge  m(p)^3 >= FLT_MIN                 la, lb, lc >= m: (la * lb) * lc, the one term of den that nothing cancels, stays normal
+                   e^3 >= 2^12 * FLT_MIN             num is six times the volume of the tetrahedron {p, v0, v1, v2} and each of its
+                                                     products an edge times two distances; the three other terms of den are a dot product
+                                                     times a length: a tetrahedron as small as the smallest edge in all three extents, and
+                                                     every such product down to 2^-12 of its e^3, stays normal.  A far cluster has d2 > r2
+                                                     >= (e / 2)^2 (a centre is not nearer than e / 2 to both ends of an edge it covers),
+                                                     so d2 * sqrtf(d2) > e^3 / 8 stays normal as well.
+
+    The upper edge is a proof but for its last line: inside it no intermediate of the definition overflows; the last line is a margin
+    (ATAN_HEADROOM) for the restatement's atan2f, and says nothing about another implementation's.  Of the lower edge the first line is a proof for that
+    one term; the second is a margin (HEADROOM, as for the closest points): a point in a triangle's plane has num = 0 in the reals, a right
+    angle at p makes a dot product vanish, and then a non-zero product far below e^3 is rounded as a subnormal.  Excluding that needs the
+    granularity of the coordinates and would put scale 1 itself outside.  Inside the envelope multiplying every position and every point
+    by 2^k leaves every significand of the definition unchanged: the cluster tree is the power-of-two image (covariant_winding_tree), the
+    far decisions and hence the three work counters are the same and w is the same float, bit for bit.  tests/test_query_scale_cpu.py
+    holds both edges to the restatement (tests/winding_ref.py): it fails if that breaks anywhere inside.  The RECORD ORDER is not part of
+    the definition -- it is the BVH builder's, whose own limits are narrower on meshes of many small triangles -- so a scale at which it
+    differs from scale 1 counts as outside whatever this predicate says (that test asserts where it may not differ).  Non-finite points
+    are outside."""
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    e, a, D = _winding_measures(sd)
+    E = _triangle_measures(sd)[0]
+    lo, hi = cr.scene_box(sd)
+    near = nearest_vertex(sd, p)
+    with np.errstate(all="ignore"):
+        far = np.maximum(np.abs(p - lo), np.abs(p - hi))
+        M = np.sqrt((far * far).sum(axis=1))
+        ok = np.isfinite(p).all(axis=1)
+        ok &= 8.0 * M ** 3 <= FLT_MAX
+        ok &= 2.0 * a * M <= FLT_MAX
+        if np.isfinite(beta):
+            ok &= 2.0 * float(beta) ** 2 * D * D <= FLT_MAX
+        ok &= E * E * M <= FLT_MAX / ATAN_HEADROOM
+        ok &= near ** 3 >= FLT_MIN
+        ok &= e ** 3 >= HEADROOM * FLT_MIN
     return ok
 
 
