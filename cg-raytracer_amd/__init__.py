@@ -39,6 +39,7 @@ assert CROSSING_DTYPE.itemsize == 8
 # include/cgrt.h CgrtNeighbor: one triangle within a query point's radius (8 bytes); an unused entry of a slot is {+inf, NO_PRIM}
 NEIGHBOR_DTYPE = np.dtype([("dist2", np.float32), ("prim_id", np.uint32)])
 assert NEIGHBOR_DTYPE.itemsize == 8
+_SLOT_RECORDS = {"crossings": CROSSING_DTYPE, "neighbors": NEIGHBOR_DTYPE}  # the slot-list entries (Scene._slots_*) by the name in their symbols
 # Scene.inside_tensor's default directions: three fixed generic ones (no component zero, none along an axis, a face diagonal or a space
 # diagonal, pairwise far from parallel), so that a ray through an edge or a vertex of an axis-aligned or diagonal-symmetric mesh is the
 # exception in at most one of them
@@ -521,6 +522,11 @@ def _check(rc: int) -> None:
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _vp(v):
+    """A raw address or stream handle (an integer) as a pointer argument; 0 is NULL."""
+    return C.c_void_p(v) if v else None
 
 
 def _f32(a, shape) -> np.ndarray:
@@ -1027,8 +1033,7 @@ class Scene:
             row_bytes = _frame_tensor_row_bytes(out, fmt, W, H, self.device)
         if self.device < 0:
             raise ValueError("the scene has no device (created host-only)")
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        dev, stream = self._torch_stream(stream)
         _check_one_hip_runtime()
         if out is None:
             shape, dtype = {0: ((H, W, 3), torch.float32), 1: ((3, H, W), torch.float32), 2: ((H, W, 4), torch.uint8)}[fmt]
@@ -1115,8 +1120,7 @@ class Scene:
                 raise ValueError(f"out is on {out.device}, the scene on cuda:{self.device}")
         if self.device < 0:
             raise ValueError("the scene has no device (created host-only)")
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        dev, stream = self._torch_stream(stream)
         _check_one_hip_runtime()
         if out is None:
             with torch.cuda.stream(stream):  # (allocated on the stream the frames are exported on)
@@ -1319,8 +1323,7 @@ class Scene:
                 raise ValueError("out must be contiguous")
             if n:  # render_tensor's check of an (H, W, 3) f32 frame: dtype, device, strides, alignment
                 _frame_tensor_row_bytes(out.view(1, n, 3), FRAME_FORMATS["rgb"], n, 1, self.device)
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        dev, stream = self._torch_stream(stream)
         _check_one_hip_runtime()
         if out is None:
             with torch.cuda.stream(stream):  # (allocated on the stream the colours are written on)
@@ -1673,8 +1676,8 @@ class Scene:
 
     def occluded_device(self, d_rays_ptr: int, n: int, d_hit_ptr: int, stream: int = 0) -> None:
         """cgrt_occluded_device: n rays (7 floats each) at d_rays_ptr -> n bytes at d_hit_ptr, enqueued on the hipStream_t `stream`."""
-        _check(lib().cgrt_occluded_device(self._h, C.c_void_p(d_rays_ptr) if d_rays_ptr else None, int(n),
-                                          C.c_void_p(d_hit_ptr) if d_hit_ptr else None, C.c_void_p(stream) if stream else None))
+        _check(lib().cgrt_occluded_device(self._h, _vp(d_rays_ptr), int(n),
+                                          _vp(d_hit_ptr), _vp(stream)))
 
     def in_shadow(self, points, lights=None) -> np.ndarray:
         """cgrt_in_shadow: pointInShadow (main.cpp:104-135) of every point ((n, 3) float32) and point light ((nlights, 6) {position,
@@ -1688,8 +1691,8 @@ class Scene:
     def in_shadow_device(self, d_points_ptr: int, n: int, d_out_ptr: int, stream: int = 0, lights=None) -> None:
         """cgrt_in_shadow_device: n points (3 floats each) at d_points_ptr -> n * nlights bytes at d_out_ptr, ordered on `stream`."""
         lights = _f32(self.sd.point_lights if lights is None else lights, (-1, 6))
-        _check(lib().cgrt_in_shadow_device(self._h, C.c_void_p(d_points_ptr) if d_points_ptr else None, int(n), _ptr(lights), len(lights),
-                                           C.c_void_p(d_out_ptr) if d_out_ptr else None, C.c_void_p(stream) if stream else None))
+        _check(lib().cgrt_in_shadow_device(self._h, _vp(d_points_ptr), int(n), _ptr(lights), len(lights),
+                                           _vp(d_out_ptr), _vp(stream)))
 
     def _soft_query(self, spherical, units, samples: int, seed: int, closest_hit: bool):
         spherical, units = _f32(spherical, (-1, 7)), _f32(units, (-1, 3))
@@ -1709,8 +1712,8 @@ class Scene:
                         closest_hit: bool = False, stream: int = 0) -> None:
         """cgrt_soft_lit_device: n points at d_points_ptr -> n * nspherical u32 counts at d_lit_ptr, ordered on `stream`."""
         q, keep = self._soft_query(spherical, units, samples, seed, closest_hit)  # noqa: F841
-        _check(lib().cgrt_soft_lit_device(self._h, C.c_void_p(d_points_ptr) if d_points_ptr else None, int(n), C.byref(q),
-                                          C.c_void_p(d_lit_ptr) if d_lit_ptr else None, C.c_void_p(stream) if stream else None))
+        _check(lib().cgrt_soft_lit_device(self._h, _vp(d_points_ptr), int(n), C.byref(q),
+                                          _vp(d_lit_ptr), _vp(stream)))
 
     def _query_tensor(self, x, width: int, name: str, out, out_shape, out_dtypes):
         """Validates a *_tensor query's input ((..., width) float32, contiguous, on the scene's device) and its optional `out` before any
@@ -1738,11 +1741,17 @@ class Scene:
                 raise ValueError("out must be contiguous (and 4-byte aligned for counts)")
         return x.numel() // width
 
-    def _tensor_call(self, out, shape, dtype, stream, call):
+    def _torch_stream(self, stream):
+        """(the scene's torch device, the torch stream of this call: `stream`, or None for that device's current stream)."""
         import torch
 
         dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        return dev, (torch.cuda.current_stream(dev) if stream is None else stream)
+
+    def _tensor_call(self, out, shape, dtype, stream, call):
+        import torch
+
+        dev, stream = self._torch_stream(stream)
         _check_one_hip_runtime()
         if out is None:
             with torch.cuda.stream(stream):  # (allocated on the stream the answers are written on)
@@ -1824,16 +1833,14 @@ class Scene:
     def hit_barycentrics_device(self, d_rays_ptr: int, d_hits_ptr: int, n: int, d_bary_ptr: int, stream: int = 0) -> None:
         """cgrt_hit_barycentrics_device: n rays (28 bytes each) and hits (16 bytes each) -> n x 3 floats at d_bary_ptr, enqueued on the
         hipStream_t `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
-        _check(lib().cgrt_hit_barycentrics_device(self._h, vp(d_rays_ptr), vp(d_hits_ptr), int(n), vp(d_bary_ptr), vp(stream)))
+        _check(lib().cgrt_hit_barycentrics_device(self._h, _vp(d_rays_ptr), _vp(d_hits_ptr), int(n), _vp(d_bary_ptr), _vp(stream)))
 
     def interpolate_hits_device(self, d_rays_ptr: int, d_hits_ptr: int, n: int, d_attr_ptr: int, channels: int, d_out_ptr: int,
                                 stream: int = 0) -> None:
         """cgrt_interpolate_hits_device: d_attr_ptr is an (nverts, channels) float32 table in device memory; n x channels floats go to
         d_out_ptr, enqueued on `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
-        _check(lib().cgrt_interpolate_hits_device(self._h, vp(d_rays_ptr), vp(d_hits_ptr), int(n), vp(d_attr_ptr), int(channels),
-                                                  vp(d_out_ptr), vp(stream)))
+        _check(lib().cgrt_interpolate_hits_device(self._h, _vp(d_rays_ptr), _vp(d_hits_ptr), int(n), _vp(d_attr_ptr), int(channels),
+                                                  _vp(d_out_ptr), _vp(stream)))
 
     def surface_views_device(self, cams, W: int, H: int, d_depth_ptr: int, d_prim_id_ptr: int, d_bary_ptr: int = 0, d_attr_ptr: int = 0,
                              channels: int = 0, d_out_ptr: int = 0, chw: bool = False, stream: int = 0, raycams: bool = False) -> None:
@@ -1841,10 +1848,9 @@ class Scene:
         attribute (d_attr_ptr, channels, d_out_ptr) of every pixel of B frames from their (B, H, W) depth and prim_id planes; the primary
         rays are regenerated from the cameras.  Raw integers; enqueued on `stream`."""
         a = raycam_array(cams) if raycams else camera_array(cams)
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
         f = lib().cgrt_surface_raycams_device if raycams else lib().cgrt_surface_views_device
-        _check(f(self._h, _ptr(a) if len(a) else None, len(a), W, H, vp(d_depth_ptr), vp(d_prim_id_ptr), vp(d_attr_ptr), int(channels),
-                 vp(d_bary_ptr), vp(d_out_ptr), 1 if chw else 0, vp(stream)))
+        _check(f(self._h, _ptr(a) if len(a) else None, len(a), W, H, _vp(d_depth_ptr), _vp(d_prim_id_ptr), _vp(d_attr_ptr), int(channels),
+                 _vp(d_bary_ptr), _vp(d_out_ptr), 1 if chw else 0, _vp(stream)))
 
     def _device_tensor(self, t, name: str, dtypes, shape=None):
         """A *_tensor argument: a contiguous torch tensor of one of `dtypes` (and of `shape`) on the scene's device (ValueError)."""
@@ -1946,26 +1952,23 @@ class Scene:
                                      d_grad_attr_ptr: int, stream: int = 0) -> None:
         """cgrt_interpolate_hits_grad_device: n x channels floats at d_grad_out_ptr are added, weighted, into the (nverts, channels)
         float32 table at d_grad_attr_ptr; enqueued on `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
-        _check(lib().cgrt_interpolate_hits_grad_device(self._h, vp(d_rays_ptr), vp(d_hits_ptr), int(n), vp(d_grad_out_ptr), int(channels),
-                                                       vp(d_grad_attr_ptr), vp(stream)))
+        _check(lib().cgrt_interpolate_hits_grad_device(self._h, _vp(d_rays_ptr), _vp(d_hits_ptr), int(n), _vp(d_grad_out_ptr), int(channels),
+                                                       _vp(d_grad_attr_ptr), _vp(stream)))
 
     def surface_views_grad_device(self, cams, W: int, H: int, d_depth_ptr: int, d_prim_id_ptr: int, d_grad_out_ptr: int, channels: int,
                                   d_grad_attr_ptr: int, chw: bool = False, stream: int = 0, raycams: bool = False) -> None:
         """cgrt_surface_views_grad_device (raycams: cgrt_surface_raycams_grad_device): the gradient (B, H, W, channels) -- (B, channels,
         H, W) with chw -- of B frames' interpolated attribute, added into the table at d_grad_attr_ptr.  Raw integers; enqueued."""
         a = raycam_array(cams) if raycams else camera_array(cams)
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
         f = lib().cgrt_surface_raycams_grad_device if raycams else lib().cgrt_surface_views_grad_device
-        _check(f(self._h, _ptr(a) if len(a) else None, len(a), W, H, vp(d_depth_ptr), vp(d_prim_id_ptr), vp(d_grad_out_ptr), int(channels),
-                 1 if chw else 0, vp(d_grad_attr_ptr), vp(stream)))
+        _check(f(self._h, _ptr(a) if len(a) else None, len(a), W, H, _vp(d_depth_ptr), _vp(d_prim_id_ptr), _vp(d_grad_out_ptr), int(channels),
+                 1 if chw else 0, _vp(d_grad_attr_ptr), _vp(stream)))
 
     def _grad_attr_tensor(self, grad_attr, channels: int, stream):
         """The table a *_grad_tensor call accumulates into and the stream it runs on: the caller's (nverts, C) tensor, or new zeros."""
         import torch
 
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        dev, stream = self._torch_stream(stream)
         _check_one_hip_runtime()
         nverts = len(_f32(self.sd.pos_nrm, (-1, 6)))
         if grad_attr is None:
@@ -2013,8 +2016,7 @@ class Scene:
     def closest_points_device(self, d_points_ptr: int, n: int, d_out_ptr: int, max_dist2: float = float("inf"), stream: int = 0) -> None:
         """cgrt_closest_points_device: n points (3 floats each) at d_points_ptr -> n CLOSEST_DTYPE records (32 bytes each) at d_out_ptr,
         enqueued on the hipStream_t `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
-        _check(lib().cgrt_closest_points_device(self._h, vp(d_points_ptr), int(n), float(max_dist2), vp(d_out_ptr), vp(stream)))
+        _check(lib().cgrt_closest_points_device(self._h, _vp(d_points_ptr), int(n), float(max_dist2), _vp(d_out_ptr), _vp(stream)))
 
     def closest_points_tensor(self, points, max_dist2: float = float("inf"), out=None, stream=None):
         """closest_points on torch tensors: points (n, 3) float32 on cuda:<device> -> an (n, 8) float32 tensor of CLOSEST_DTYPE records
@@ -2022,12 +2024,7 @@ class Scene:
         (n, 3), 'dist2' (n,), 'prim_id' (n,) int32 (-1 = NO_PRIM), 'bary' (n, 3), and 'out' itself."""
         import torch
 
-        if self.device < 0:
-            raise ValueError("the scene has no device (created host-only)")
-        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError("points must be a torch tensor of shape (n, 3)")
-        self._device_tensor(points, "points", (torch.float32,))
-        n = points.shape[0]
+        n = self._points_tensor(points)
         if out is not None:
             self._device_tensor(out, "out", (torch.float32,), (n, 8))
         o = self._tensor_call(out, (n, 8), torch.float32, stream,
@@ -2043,20 +2040,87 @@ class Scene:
         return int(w[0]), int(w[1])
 
     # ---- crossing queries (include/cgrt.h cgrt_count_crossings*, cgrt_list_crossings*) ----
+    # The slot lists of crossings and neighbours are one layer.  `kind` ("crossings" / "neighbors") names the C entries (cgrt_count_<kind>,
+    # cgrt_list_<kind>, cgrt_list_<kind>_brute) and the record dtype (_SLOT_RECORDS); `lead` is what those entries take between the scene and
+    # the slot arguments -- (rays, n) or (points, n, radius2, max_dist2) -- as ctypes arguments of arrays the caller keeps alive.
+    def _slots_count(self, kind, lead) -> np.ndarray:
+        counts = np.zeros(lead[1], np.uint32)
+        _check(getattr(lib(), f"cgrt_count_{kind}")(self._h, *lead, _ptr(counts)))
+        return counts
+
+    def _slots_host(self, kind, lead, offsets, k: int, want_counts: bool = True, brute: bool = False):
+        """One cgrt_list_<kind> call into slots from `offsets` or of k records each: (records, counts or None)."""
+        m = int(offsets[-1]) if offsets is not None else lead[1] * k
+        out = np.zeros(m, _SLOT_RECORDS[kind])
+        counts = np.zeros(lead[1], np.uint32) if want_counts else None
+        f = getattr(lib(), f"cgrt_list_{kind}_brute" if brute else f"cgrt_list_{kind}")
+        _check(f(self._h, *lead, _ptr(offsets), int(k), _ptr(out), m, _ptr(counts)))
+        return out, counts
+
+    def _slots_full(self, kind, lead, counts, brute: bool = False):
+        """The full lists from the full counts: (offsets (n + 1,) int64, records)."""
+        off = np.zeros(lead[1] + 1, np.uint64)
+        np.cumsum(counts, dtype=np.uint64, out=off[1:])
+        out, _ = self._slots_host(kind, lead, off, 0, want_counts=False, brute=brute)
+        return off.astype(np.int64), out
+
+    def _slots_list(self, kind, lead, offsets, want_counts: bool):
+        if offsets is not None:
+            return self._slots_host(kind, lead, np.ascontiguousarray(offsets, np.uint64), 0, want_counts)
+        return self._slots_full(kind, lead, self._slots_count(kind, lead))
+
+    def _slots_brute(self, kind, lead, offsets, k: int):
+        if offsets is None and not k:
+            _, c = self._slots_host(kind, lead, None, 1, brute=True)  # k = 1 only to obtain the counts
+            return self._slots_full(kind, lead, c, brute=True)
+        off = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
+        out, counts = self._slots_host(kind, lead, off, k, brute=True)
+        return (out.reshape(lead[1], k) if off is None else out), counts
+
+    def _slots_first(self, kind, lead, k: int, want_counts: bool):
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        out, counts = self._slots_host(kind, lead, None, k, want_counts)
+        return out.reshape(lead[1], k), counts
+
+    def _slots_full_tensor(self, n: int, stream, count, list_device):
+        """The full lists on torch tensors: count(stream) gives the (n,) int32 counts, list_device(d_out_ptr, capacity, d_offsets_ptr, stream
+        handle) lists into the slots of their prefix sums.  (offsets (n + 1,) int64, records (m, 2) float32)."""
+        import torch
+
+        dev, stream = self._torch_stream(stream)
+        counts = count(stream)
+        with torch.cuda.stream(stream):
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+            m = int(offsets[-1].item())
+            records = torch.empty((m, 2), dtype=torch.float32, device=dev)
+        if n and m:
+            list_device(records.data_ptr(), m, offsets.data_ptr(), stream.cuda_stream)
+        return offsets, records
+
+    def _slots_first_tensor(self, n: int, k: int, want_counts: bool, out, stream, list_device):
+        """k records per query on torch tensors: list_device(d_out_ptr, d_counts_ptr, stream handle) fills the (n, k, 2) float32 records
+        (`out`, or a new tensor) and, if wanted, the (n,) int32 counts.  (records, counts or None)."""
+        import torch
+
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        if out is not None:
+            self._device_tensor(out, "out", (torch.float32,), (n, k, 2))
+        dev, stream = self._torch_stream(stream)
+        counts = None
+        if want_counts:
+            with torch.cuda.stream(stream):
+                counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        cp = counts.data_ptr() if want_counts and n else 0
+        return self._tensor_call(out, (n, k, 2), torch.float32, stream, lambda o, s: list_device(o.data_ptr(), cp, s)), counts
+
     def count_crossings(self, rays) -> np.ndarray:
         """cgrt_count_crossings: for every ray (RAY_DTYPE or (n, 7) float32, taken as given: t bounds it) the number of triangles it
         passes through -- the triangles the reference's intersectRayWithTriangle accepts on a fresh copy of the ray.  (n,) uint32."""
         r = _as_ray_array(rays)
-        counts = np.zeros(len(r), np.uint32)
-        _check(lib().cgrt_count_crossings(self._h, _ptr(r), len(r), _ptr(counts)))
-        return counts
-
-    def _list_host(self, f, r, offsets, k: int, want_counts: bool = True):
-        m = int(offsets[-1]) if offsets is not None else len(r) * k
-        out = np.zeros(m, CROSSING_DTYPE)
-        counts = np.zeros(len(r), np.uint32) if want_counts else None
-        _check(f(self._h, _ptr(r), len(r), _ptr(offsets), int(k), _ptr(out), m, _ptr(counts)))
-        return out, counts
+        return self._slots_count("crossings", (_ptr(r), len(r)))
 
     def list_crossings(self, rays, offsets=None, want_counts: bool = True):
         """Every crossing of every ray, in order (by t, equal t by prim_id): cgrt_count_crossings, the exclusive prefix sums, then
@@ -2066,38 +2130,20 @@ class Scene:
         order in records [offsets[i], offsets[i + 1]), {+inf, NO_PRIM} in what remains.  Returns (records (offsets[-1],), counts: the full
         numbers of crossings -- or None with want_counts=False, which lets the search of a ray stop at the largest t its full slot keeps)."""
         r = _as_ray_array(rays)
-        if offsets is not None:
-            return self._list_host(lib().cgrt_list_crossings, r, np.ascontiguousarray(offsets, np.uint64), 0, want_counts)
-        offsets = np.zeros(len(r) + 1, np.uint64)
-        np.cumsum(self.count_crossings(r), dtype=np.uint64, out=offsets[1:])
-        out, _ = self._list_host(lib().cgrt_list_crossings, r, offsets, 0, want_counts=False)
-        return offsets.astype(np.int64), out
+        return self._slots_list("crossings", (_ptr(r), len(r)), offsets, want_counts)
 
     def list_crossings_brute(self, rays, offsets=None, k: int = 0):
         """cgrt_list_crossings_brute: the list by testing every triangle in turn (validation; the same bytes).  With neither offsets nor
         k the full list, as list_crossings returns it: (offsets, records); with offsets ((n + 1,) slot boundaries) or k (k records per
         ray): (records, counts)."""
         r = _as_ray_array(rays)
-        if offsets is None and not k:
-            c = np.zeros(len(r), np.uint32)  # k = 1 only to obtain the counts
-            one = np.zeros(len(r), CROSSING_DTYPE)
-            _check(lib().cgrt_list_crossings_brute(self._h, _ptr(r), len(r), None, 1, _ptr(one), len(r), _ptr(c)))
-            off = np.zeros(len(r) + 1, np.uint64)
-            np.cumsum(c, dtype=np.uint64, out=off[1:])
-            out, _ = self._list_host(lib().cgrt_list_crossings_brute, r, off, 0, want_counts=False)
-            return off.astype(np.int64), out
-        off = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
-        out, counts = self._list_host(lib().cgrt_list_crossings_brute, r, off, k)
-        return (out.reshape(len(r), k) if off is None else out), counts
+        return self._slots_brute("crossings", (_ptr(r), len(r)), offsets, k)
 
     def first_crossings(self, rays, k: int, want_counts: bool = True):
         """The first k crossings of every ray: ((n, k) CROSSING_DTYPE records, unused entries {+inf, NO_PRIM}; (n,) uint32 counts -- the
         full numbers of crossings; None with want_counts=False, as list_crossings with offsets)."""
         r = _as_ray_array(rays)
-        if k < 1:
-            raise ValueError("k must be at least 1")
-        out, counts = self._list_host(lib().cgrt_list_crossings, r, None, k, want_counts)
-        return out.reshape(len(r), k), counts
+        return self._slots_first("crossings", (_ptr(r), len(r)), k, want_counts)
 
     def debug_crossing_work(self, rays):
         """cgrt_debug_crossing_work: (node steps, triangles evaluated) of count_crossings' search, summed over the rays (a separate
@@ -2110,17 +2156,15 @@ class Scene:
     def count_crossings_device(self, d_rays_ptr: int, n: int, d_counts_ptr: int, stream: int = 0) -> None:
         """cgrt_count_crossings_device: n rays (28 bytes each) at d_rays_ptr -> n uint32 counts at d_counts_ptr, enqueued on the
         hipStream_t `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
-        _check(lib().cgrt_count_crossings_device(self._h, vp(d_rays_ptr), int(n), vp(d_counts_ptr), vp(stream)))
+        _check(lib().cgrt_count_crossings_device(self._h, _vp(d_rays_ptr), int(n), _vp(d_counts_ptr), _vp(stream)))
 
     def list_crossings_device(self, d_rays_ptr: int, n: int, d_out_ptr: int, capacity: int, d_offsets_ptr: int = 0, k: int = 0,
                               d_counts_ptr: int = 0, stream: int = 0) -> None:
         """cgrt_list_crossings_device: slots from the n + 1 uint64 offsets at d_offsets_ptr, or of k records each; `capacity` records of
         8 bytes at d_out_ptr, nothing beyond them is written whatever the offsets hold; d_counts_ptr (optional) receives the full counts.
         Enqueued on `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
-        _check(lib().cgrt_list_crossings_device(self._h, vp(d_rays_ptr), int(n), vp(d_offsets_ptr), int(k), vp(d_out_ptr), int(capacity),
-                                                vp(d_counts_ptr), vp(stream)))
+        _check(lib().cgrt_list_crossings_device(self._h, _vp(d_rays_ptr), int(n), _vp(d_offsets_ptr), int(k), _vp(d_out_ptr), int(capacity),
+                                                _vp(d_counts_ptr), _vp(stream)))
 
     def first_crossings_device(self, d_rays_ptr: int, n: int, k: int, d_out_ptr: int, d_counts_ptr: int = 0, stream: int = 0) -> None:
         """list_crossings_device with k records per ray: n * k records at d_out_ptr."""
@@ -2136,6 +2180,20 @@ class Scene:
         self._device_tensor(rays, "rays", (torch.float32,))
         return rays.shape[0]
 
+    def _points_tensor(self, points, shape_first: bool = False):
+        """The checks of a point list's tensor: (n, 3) float32, contiguous, on the scene's device (ValueError).  Returns n.  The host-only
+        scene is reported first, or with shape_first (sdf_tensor, winding_numbers_tensor) behind the shape."""
+        import torch
+
+        if self.device < 0 and not shape_first:
+            raise ValueError("the scene has no device (created host-only)")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be a torch tensor of shape (n, 3)")
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        self._device_tensor(points, "points", (torch.float32,))
+        return points.shape[0]
+
     def count_crossings_tensor(self, rays, out=None, stream=None):
         """count_crossings on torch tensors: rays (n, 7) float32 on cuda:<device> -> (n,) torch.int32, into `out` or a new tensor,
         enqueued on `stream` (default: torch.cuda.current_stream())."""
@@ -2150,38 +2208,16 @@ class Scene:
         """list_crossings on torch tensors: rays (n, 7) float32 on cuda:<device> -> (offsets (n + 1,) torch.int64, records (m, 2) float32
         with the prim_id BITS in column 1: records.view(torch.int32)[:, 1]).  Count, a torch cumsum and the list are enqueued on `stream`;
         the total m is read back in between (one synchronisation of that stream)."""
-        import torch
-
         n = self._crossing_rays_tensor(rays)
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
-        counts = self.count_crossings_tensor(rays, stream=stream)
-        with torch.cuda.stream(stream):
-            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-            offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
-            m = int(offsets[-1].item())
-            records = torch.empty((m, 2), dtype=torch.float32, device=dev)
-        if n and m:
-            self.list_crossings_device(rays.data_ptr(), n, records.data_ptr(), m, d_offsets_ptr=offsets.data_ptr(), stream=stream.cuda_stream)
-        return offsets, records
+        return self._slots_full_tensor(n, stream, lambda s: self.count_crossings_tensor(rays, stream=s),
+                                       lambda o, m, off, s: self.list_crossings_device(rays.data_ptr(), n, o, m, d_offsets_ptr=off, stream=s))
 
     def first_crossings_tensor(self, rays, k: int, out=None, stream=None):
         """first_crossings on torch tensors: rays (n, 7) float32 on cuda:<device> -> (records (n, k, 2) float32 -- `out`, or a new tensor;
         the prim_id bits in [..., 1], unused entries {+inf, NO_PRIM} --, counts (n,) torch.int32: the full numbers of crossings)."""
-        import torch
-
         n = self._crossing_rays_tensor(rays)
-        if k < 1:
-            raise ValueError("k must be at least 1")
-        if out is not None:
-            self._device_tensor(out, "out", (torch.float32,), (n, k, 2))
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
-        with torch.cuda.stream(stream):
-            counts = torch.empty((n,), dtype=torch.int32, device=dev)
-        rec = self._tensor_call(out, (n, k, 2), torch.float32, stream,
-                                lambda o, s: self.first_crossings_device(rays.data_ptr(), n, k, o.data_ptr(), d_counts_ptr=counts.data_ptr(), stream=s))
-        return rec, counts
+        return self._slots_first_tensor(n, k, True, out, stream,
+                                        lambda o, c, s: self.first_crossings_device(rays.data_ptr(), n, k, o, d_counts_ptr=c, stream=s))
 
     # ---- neighbour queries (include/cgrt.h cgrt_count_neighbors*, cgrt_list_neighbors*; DESIGN.md section 5.26) ----
     @staticmethod
@@ -2196,16 +2232,7 @@ class Scene:
         """cgrt_count_neighbors: for every query point ((n, 3) float32) the number of triangles whose closest_points dist2 is <= its
         squared radius -- radius2[i] ((n,) float32; NaN or negative: no neighbours), or max_dist2 for every query.  (n,) uint32."""
         p, r = self._neighbor_points(points, radius2)
-        counts = np.zeros(len(p), np.uint32)
-        _check(lib().cgrt_count_neighbors(self._h, _ptr(p), len(p), _ptr(r), float(max_dist2), _ptr(counts)))
-        return counts
-
-    def _neighbors_host(self, f, p, r, max_dist2: float, offsets, k: int, want_counts: bool = True):
-        m = int(offsets[-1]) if offsets is not None else len(p) * k
-        out = np.zeros(m, NEIGHBOR_DTYPE)
-        counts = np.zeros(len(p), np.uint32) if want_counts else None
-        _check(f(self._h, _ptr(p), len(p), _ptr(r), float(max_dist2), _ptr(offsets), int(k), _ptr(out), m, _ptr(counts)))
-        return out, counts
+        return self._slots_count("neighbors", (_ptr(p), len(p), _ptr(r), float(max_dist2)))
 
     def list_neighbors(self, points, radius2=None, max_dist2: float = float("inf"), offsets=None, want_counts: bool = True):
         """Every neighbour of every query point, in order (by dist2, equal dist2 by prim_id): cgrt_count_neighbors, the exclusive prefix
@@ -2216,38 +2243,21 @@ class Scene:
         full numbers of neighbours -- or None with want_counts=False, which lets a query's search shrink to the largest dist2 its full
         slot keeps)."""
         p, r = self._neighbor_points(points, radius2)
-        if offsets is not None:
-            return self._neighbors_host(lib().cgrt_list_neighbors, p, r, max_dist2, np.ascontiguousarray(offsets, np.uint64), 0, want_counts)
-        offsets = np.zeros(len(p) + 1, np.uint64)
-        np.cumsum(self.count_neighbors(p, r, max_dist2), dtype=np.uint64, out=offsets[1:])
-        out, _ = self._neighbors_host(lib().cgrt_list_neighbors, p, r, max_dist2, offsets, 0, want_counts=False)
-        return offsets.astype(np.int64), out
+        return self._slots_list("neighbors", (_ptr(p), len(p), _ptr(r), float(max_dist2)), offsets, want_counts)
 
     def list_neighbors_brute(self, points, radius2=None, max_dist2: float = float("inf"), offsets=None, k: int = 0):
         """cgrt_list_neighbors_brute: the list by testing every triangle in turn (validation; the same bytes).  With neither offsets nor
         k the full list, as list_neighbors returns it: (offsets, records); with offsets ((n + 1,) slot boundaries) or k (k records per
         query): (records, counts)."""
         p, r = self._neighbor_points(points, radius2)
-        f = lib().cgrt_list_neighbors_brute
-        if offsets is None and not k:
-            _, c = self._neighbors_host(f, p, r, max_dist2, None, 1)  # k = 1 only to obtain the counts
-            off = np.zeros(len(p) + 1, np.uint64)
-            np.cumsum(c, dtype=np.uint64, out=off[1:])
-            out, _ = self._neighbors_host(f, p, r, max_dist2, off, 0, want_counts=False)
-            return off.astype(np.int64), out
-        off = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
-        out, counts = self._neighbors_host(f, p, r, max_dist2, off, k)
-        return (out.reshape(len(p), k) if off is None else out), counts
+        return self._slots_brute("neighbors", (_ptr(p), len(p), _ptr(r), float(max_dist2)), offsets, k)
 
     def nearest_triangles(self, points, k: int, radius2=None, max_dist2: float = float("inf"), want_counts: bool = False):
         """The k nearest triangles of every query point within its squared radius: (n, k) NEIGHBOR_DTYPE records in order, unused entries
         {+inf, NO_PRIM}.  With want_counts=True returns (records, counts): counts (n,) uint32, the full numbers of neighbours (the
         search then cannot shrink its bound to the slot)."""
         p, r = self._neighbor_points(points, radius2)
-        if k < 1:
-            raise ValueError("k must be at least 1")
-        out, counts = self._neighbors_host(lib().cgrt_list_neighbors, p, r, max_dist2, None, k, want_counts)
-        out = out.reshape(len(p), k)
+        out, counts = self._slots_first("neighbors", (_ptr(p), len(p), _ptr(r), float(max_dist2)), k, want_counts)
         return (out, counts) if want_counts else out
 
     def debug_neighbor_work(self, points, radius2=None, max_dist2: float = float("inf"), k: int = 0):
@@ -2262,29 +2272,22 @@ class Scene:
                                stream: int = 0) -> None:
         """cgrt_count_neighbors_device: n points (3 floats each) at d_points_ptr (and n squared radii at d_radius2_ptr, or 0) -> n uint32
         counts at d_counts_ptr, enqueued on the hipStream_t `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
-        _check(lib().cgrt_count_neighbors_device(self._h, vp(d_points_ptr), int(n), vp(d_radius2_ptr), float(max_dist2), vp(d_counts_ptr),
-                                                 vp(stream)))
+        _check(lib().cgrt_count_neighbors_device(self._h, _vp(d_points_ptr), int(n), _vp(d_radius2_ptr), float(max_dist2), _vp(d_counts_ptr),
+                                                 _vp(stream)))
 
     def list_neighbors_device(self, d_points_ptr: int, n: int, d_out_ptr: int, capacity: int, d_offsets_ptr: int = 0, k: int = 0,
                               d_counts_ptr: int = 0, d_radius2_ptr: int = 0, max_dist2: float = float("inf"), stream: int = 0) -> None:
         """cgrt_list_neighbors_device: slots from the n + 1 uint64 offsets at d_offsets_ptr, or of k records each; `capacity` records of
         8 bytes at d_out_ptr, nothing beyond them is written whatever the offsets hold; d_counts_ptr (optional) receives the full counts.
         Enqueued on `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
-        _check(lib().cgrt_list_neighbors_device(self._h, vp(d_points_ptr), int(n), vp(d_radius2_ptr), float(max_dist2), vp(d_offsets_ptr),
-                                                int(k), vp(d_out_ptr), int(capacity), vp(d_counts_ptr), vp(stream)))
+        _check(lib().cgrt_list_neighbors_device(self._h, _vp(d_points_ptr), int(n), _vp(d_radius2_ptr), float(max_dist2), _vp(d_offsets_ptr),
+                                                int(k), _vp(d_out_ptr), int(capacity), _vp(d_counts_ptr), _vp(stream)))
 
     def _neighbor_tensors(self, points, radius2, max_dist2):
         """(n, the radii's address or 0, the scalar bound) of a *_tensor call: radius2 a float (it replaces max_dist2) or an (n,) tensor."""
         import torch
 
-        if self.device < 0:
-            raise ValueError("the scene has no device (created host-only)")
-        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError("points must be a torch tensor of shape (n, 3)")
-        self._device_tensor(points, "points", (torch.float32,))
-        n = points.shape[0]
+        n = self._points_tensor(points)
         if radius2 is None:
             return n, 0, float(max_dist2)
         if isinstance(radius2, torch.Tensor):
@@ -2308,43 +2311,19 @@ class Scene:
         """list_neighbors on torch tensors -> (offsets (n + 1,) torch.int64, records (m, 2) float32 with the prim_id BITS in column 1:
         records.view(torch.int32)[:, 1]).  Count, a torch cumsum and the list are enqueued on `stream`; the total m is read back in
         between (one synchronisation of that stream)."""
-        import torch
-
         n, rad, md = self._neighbor_tensors(points, radius2, max_dist2)
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
-        counts = self.count_neighbors_tensor(points, radius2, max_dist2, stream=stream)
-        with torch.cuda.stream(stream):
-            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-            offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
-            m = int(offsets[-1].item())
-            records = torch.empty((m, 2), dtype=torch.float32, device=dev)
-        if n and m:
-            self.list_neighbors_device(points.data_ptr(), n, records.data_ptr(), m, d_offsets_ptr=offsets.data_ptr(), d_radius2_ptr=rad,
-                                       max_dist2=md, stream=stream.cuda_stream)
-        return offsets, records
+        return self._slots_full_tensor(n, stream, lambda s: self.count_neighbors_tensor(points, radius2, max_dist2, stream=s),
+                                       lambda o, m, off, s: self.list_neighbors_device(points.data_ptr(), n, o, m, d_offsets_ptr=off,
+                                                                                       d_radius2_ptr=rad, max_dist2=md, stream=s))
 
     def nearest_triangles_tensor(self, points, k: int, radius2=None, max_dist2: float = float("inf"), want_counts: bool = False, out=None,
                                  stream=None):
         """nearest_triangles on torch tensors -> records (n, k, 2) float32 (`out`, or a new tensor; the prim_id bits in [..., 1], unused
         entries {+inf, NO_PRIM}); with want_counts=True (records, counts (n,) torch.int32: the full numbers of neighbours)."""
-        import torch
-
         n, rad, md = self._neighbor_tensors(points, radius2, max_dist2)
-        if k < 1:
-            raise ValueError("k must be at least 1")
-        if out is not None:
-            self._device_tensor(out, "out", (torch.float32,), (n, k, 2))
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
-        counts = None
-        if want_counts:
-            with torch.cuda.stream(stream):
-                counts = torch.empty((n,), dtype=torch.int32, device=dev)
-        cp = counts.data_ptr() if want_counts and n else 0
-        rec = self._tensor_call(out, (n, k, 2), torch.float32, stream,
-                                lambda o, s: self.list_neighbors_device(points.data_ptr(), n, o.data_ptr(), n * k, k=k, d_counts_ptr=cp,
-                                                                        d_radius2_ptr=rad, max_dist2=md, stream=s))
+        rec, counts = self._slots_first_tensor(n, k, want_counts, out, stream,
+                                               lambda o, c, s: self.list_neighbors_device(points.data_ptr(), n, o, n * k, k=k, d_counts_ptr=c,
+                                                                                          d_radius2_ptr=rad, max_dist2=md, stream=s))
         return (rec, counts) if want_counts else rec
 
     def inside_tensor(self, points, directions=None, stream=None):
@@ -2355,17 +2334,12 @@ class Scene:
         native entry with the same bytes).  Returns (n,) torch.bool."""
         import torch
 
-        if self.device < 0:
-            raise ValueError("the scene has no device (created host-only)")
-        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError("points must be a torch tensor of shape (n, 3)")
-        self._device_tensor(points, "points", (torch.float32,))
+        self._points_tensor(points)
         dirs = np.asarray(INSIDE_DIRECTIONS if directions is None else directions, np.float32).reshape(-1, 3)
         if len(dirs) % 2 == 0:
             raise ValueError("an odd number of directions is needed for a majority")
         n = points.shape[0]
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        dev, stream = self._torch_stream(stream)
         with torch.cuda.stream(stream):
             votes = torch.zeros((n,), dtype=torch.int32, device=dev)
             for d in dirs:
@@ -2383,8 +2357,7 @@ class Scene:
         import torch
 
         inside = self.inside_tensor(points, stream=stream)
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        _, stream = self._torch_stream(stream)
         d2 = self.closest_points_tensor(points, stream=stream)["dist2"]
         with torch.cuda.stream(stream):
             dist = torch.sqrt(d2)
@@ -2392,23 +2365,36 @@ class Scene:
 
     # ---- signed distance and occupancy (include/cgrt.h cgrt_signed_distance*) ----
     @staticmethod
-    def _sdf_want(want):
+    def _field_want(want, value: str):
+        """`want` of the signed-distance (value "sdf") and winding (value "w") entries as a tuple of names."""
         want = (want,) if isinstance(want, str) else tuple(want)
-        if not want or any(w not in ("sdf", "inside") for w in want) or len(set(want)) != len(want):
-            raise ValueError('want must name "sdf", "inside" or both')
+        if not want or any(w not in (value, "inside") for w in want) or len(set(want)) != len(want):
+            raise ValueError(f'want must name "{value}", "inside" or both')
         return want
+
+    def _field_host(self, f, value: str, want, params, points=None, grid=None):
+        """The host form of a signed-distance or winding entry f on a point list (points) or a grid (grid = (origin, spacing, dims)):
+        the arrays named by `want` ((n,), or (nz, ny, nx) for a grid), as _sdf_result returns them.  params() makes the parameter
+        structure, after the points have been looked at."""
+        want = self._field_want(want, value)
+        if grid is None:
+            p = _f32(points, (-1, 3))
+            lead, shape, m = (_ptr(p), len(p)), (len(p),), len(p)
+        else:
+            g = _sdf_grid_struct(*grid)
+            lead, shape = (C.byref(g),), (g.dims[2], g.dims[1], g.dims[0])
+            m = shape[0] * shape[1] * shape[2] if max(shape) <= 1 << 24 and shape[0] * shape[1] * shape[2] <= 0x7FFFFFFF else 0  # (else: the library says why)
+        prm = params()
+        res = {value: np.zeros(m, np.float32) if value in want else None, "inside": np.zeros(m, np.uint8) if "inside" in want else None}
+        _check(f(self._h, *lead, C.byref(prm), _ptr(res[value]), _ptr(res["inside"])))
+        return self._sdf_result({k: (None if v is None else v.reshape(shape)) for k, v in res.items()}, want)
 
     def sdf(self, points, max_dist2: float = float("inf"), directions=None, want=("sdf", "inside")):
         """cgrt_signed_distance: for every point ((n, 3) float32) sqrt(closest_points' dist2), negative where the majority of the parity
         walks along `directions` (None: INSIDE_DIRECTIONS; an odd number, at most 7) says inside -- one fused kernel, the bytes of
         signed_distance_tensor / inside_tensor.  Beyond max_dist2 the value is +-inf; a non-finite point gets (+inf, False).  Returns the
         arrays named by `want`, in that order ((n,) float32 / (n,) bool); a single name returns the array itself."""
-        want = self._sdf_want(want)
-        p = _f32(points, (-1, 3))
-        prm = _sdf_params(max_dist2, directions)
-        res = {"sdf": np.zeros(len(p), np.float32) if "sdf" in want else None, "inside": np.zeros(len(p), np.uint8) if "inside" in want else None}
-        _check(lib().cgrt_signed_distance(self._h, _ptr(p), len(p), C.byref(prm), _ptr(res["sdf"]), _ptr(res["inside"])))
-        return self._sdf_result(res, want)
+        return self._field_host(lib().cgrt_signed_distance, "sdf", want, lambda: _sdf_params(max_dist2, directions), points=points)
 
     @staticmethod
     def _sdf_result(res, want):
@@ -2422,9 +2408,8 @@ class Scene:
         """cgrt_signed_distance_device: n points (3 floats each) at d_points_ptr -> n float32 at d_sdf_ptr and / or n bytes (0 / 1) at
         d_inside_ptr (0: not wanted; without d_sdf_ptr the closest-point search is not run), enqueued on the hipStream_t `stream`.  Raw
         integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
         prm = _sdf_params(max_dist2, directions)
-        _check(lib().cgrt_signed_distance_device(self._h, vp(d_points_ptr), int(n), C.byref(prm), vp(d_sdf_ptr), vp(d_inside_ptr), vp(stream)))
+        _check(lib().cgrt_signed_distance_device(self._h, _vp(d_points_ptr), int(n), C.byref(prm), _vp(d_sdf_ptr), _vp(d_inside_ptr), _vp(stream)))
 
     def _sdf_tensors(self, shape, want, out, stream, call, value="sdf"):
         """The *_tensor conventions for the two outputs (`value`: the name of the float32 one): `out` None, or a dict / tuple (in want's
@@ -2438,8 +2423,7 @@ class Scene:
             if len(out) != len(want):
                 raise ValueError("out must hold one tensor per name in want")
             out = dict(zip(want, out))
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        dev, stream = self._torch_stream(stream)
         _check_one_hip_runtime()
         res = {}
         for w, dtypes in ((value, (torch.float32,)), ("inside", (torch.bool, torch.uint8))):
@@ -2464,41 +2448,28 @@ class Scene:
         """sdf on torch tensors: points (n, 3) float32 on cuda:<device> -> the tensors named by `want`, in that order ((n,) float32 /
         (n,) torch.bool; a single name returns the tensor itself), written into `out` (one tensor, a tuple in want's order or a dict by
         name; inside may also be torch.uint8) or new ones, enqueued on `stream` (default: torch.cuda.current_stream())."""
-        import torch
-
-        want = self._sdf_want(want)
-        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError("points must be a torch tensor of shape (n, 3)")
-        if self.device >= 0:
-            self._device_tensor(points, "points", (torch.float32,))
-        n = points.shape[0]
+        want = self._field_want(want, "sdf")
+        n = self._points_tensor(points, shape_first=True)
         return self._sdf_tensors((n,), want, out, stream,
                                  lambda ds, di, s: self.sdf_device(points.data_ptr(), n, ds, di, max_dist2=max_dist2, directions=directions, stream=s))
 
     def sdf_grid(self, origin, spacing, dims, max_dist2: float = float("inf"), directions=None, want=("sdf", "inside")):
         """cgrt_signed_distance_grid: sdf on the regular grid of sdf_grid_points(origin, spacing, dims), dims = (nx, ny, nz); the lanes
         make their own points.  Returns the arrays named by `want` shaped (nz, ny, nx) (x fastest), as sdf returns them."""
-        want = self._sdf_want(want)
-        g, prm = _sdf_grid_struct(origin, spacing, dims), _sdf_params(max_dist2, directions)
-        shape = (g.dims[2], g.dims[1], g.dims[0])
-        m = shape[0] * shape[1] * shape[2] if max(shape) <= 1 << 24 and shape[0] * shape[1] * shape[2] <= 0x7FFFFFFF else 0  # (else: the library says why)
-        res = {"sdf": np.zeros(m, np.float32) if "sdf" in want else None, "inside": np.zeros(m, np.uint8) if "inside" in want else None}
-        _check(lib().cgrt_signed_distance_grid(self._h, C.byref(g), C.byref(prm), _ptr(res["sdf"]), _ptr(res["inside"])))
-        res = {k: (None if v is None else v.reshape(shape)) for k, v in res.items()}
-        return self._sdf_result(res, want)
+        return self._field_host(lib().cgrt_signed_distance_grid, "sdf", want, lambda: _sdf_params(max_dist2, directions),
+                                grid=(origin, spacing, dims))
 
     def sdf_grid_device(self, origin, spacing, dims, d_sdf_ptr: int, d_inside_ptr: int, max_dist2: float = float("inf"), directions=None,
                         stream: int = 0) -> None:
         """cgrt_signed_distance_grid_device: nx * ny * nz float32 at d_sdf_ptr and / or bytes at d_inside_ptr (0: not wanted), in
         (nz, ny, nx) order, enqueued on the hipStream_t `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
         g, prm = _sdf_grid_struct(origin, spacing, dims), _sdf_params(max_dist2, directions)
-        _check(lib().cgrt_signed_distance_grid_device(self._h, C.byref(g), C.byref(prm), vp(d_sdf_ptr), vp(d_inside_ptr), vp(stream)))
+        _check(lib().cgrt_signed_distance_grid_device(self._h, C.byref(g), C.byref(prm), _vp(d_sdf_ptr), _vp(d_inside_ptr), _vp(stream)))
 
     def sdf_grid_tensor(self, origin, spacing, dims, max_dist2: float = float("inf"), directions=None, want=("sdf", "inside"), out=None,
                         stream=None):
         """sdf_grid on torch tensors: the tensors named by `want`, shaped (nz, ny, nx), as sdf_tensor returns them."""
-        want = self._sdf_want(want)
+        want = self._field_want(want, "sdf")
         nx, ny, nz = (int(x) for x in dims)
         return self._sdf_tensors((nz, ny, nx), want, out, stream,
                                  lambda ds, di, s: self.sdf_grid_device(origin, spacing, dims, ds, di, max_dist2=max_dist2, directions=directions,
@@ -2514,53 +2485,32 @@ class Scene:
         return tuple(int(x) for x in w)
 
     # ---- winding numbers (include/cgrt.h cgrt_winding_numbers*) ----
-    @staticmethod
-    def _winding_want(want):
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if not want or any(w not in ("w", "inside") for w in want) or len(set(want)) != len(want):
-            raise ValueError('want must name "w", "inside" or both')
-        return want
-
-    def _winding_host(self, f, points, prm, want):
-        want = self._winding_want(want)
-        p = _f32(points, (-1, 3))
-        res = {"w": np.zeros(len(p), np.float32) if "w" in want else None, "inside": np.zeros(len(p), np.uint8) if "inside" in want else None}
-        _check(f(self._h, _ptr(p), len(p), C.byref(prm), _ptr(res["w"]), _ptr(res["inside"])))
-        return self._sdf_result(res, want)
-
     def winding_numbers(self, points, beta: float = 2.0, threshold: float = 0.5, want=("w", "inside")):
         """cgrt_winding_numbers: for every point ((n, 3) float32) the generalised winding number of the scene's triangles -- +-1 inside a
         closed mesh, 0 outside, smooth near holes: a sign that also means something on OPEN meshes -- by the cluster tree (far clusters,
         from `beta` cluster radii on, are replaced by their dipole; beta = inf: every triangle, the bytes of winding_numbers_brute), and
         inside = |w| > threshold.  A non-finite point gets (0, False).  Returns the arrays named by `want`, in that order ((n,) float32 /
         (n,) bool); a single name returns the array itself."""
-        return self._winding_host(lib().cgrt_winding_numbers, points, _winding_params(beta, threshold), want)
+        return self._field_host(lib().cgrt_winding_numbers, "w", want, lambda: _winding_params(beta, threshold), points=points)
 
     def winding_numbers_brute(self, points, threshold: float = 0.5, want=("w", "inside")):
         """cgrt_winding_numbers_brute: the sum over every triangle in record order (validation; what winding_numbers returns with
         beta = inf, byte for byte)."""
-        return self._winding_host(lib().cgrt_winding_numbers_brute, points, _winding_params(0.0, threshold), want)
+        return self._field_host(lib().cgrt_winding_numbers_brute, "w", want, lambda: _winding_params(0.0, threshold), points=points)
 
     def winding_numbers_device(self, d_points_ptr: int, n: int, d_w_ptr: int, d_inside_ptr: int, beta: float = 2.0, threshold: float = 0.5,
                                stream: int = 0) -> None:
         """cgrt_winding_numbers_device: n points (3 floats each) at d_points_ptr -> n float32 at d_w_ptr and / or n bytes (0 / 1) at
         d_inside_ptr (0: not wanted), enqueued on the hipStream_t `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
         prm = _winding_params(beta, threshold)
-        _check(lib().cgrt_winding_numbers_device(self._h, vp(d_points_ptr), int(n), C.byref(prm), vp(d_w_ptr), vp(d_inside_ptr), vp(stream)))
+        _check(lib().cgrt_winding_numbers_device(self._h, _vp(d_points_ptr), int(n), C.byref(prm), _vp(d_w_ptr), _vp(d_inside_ptr), _vp(stream)))
 
     def winding_numbers_tensor(self, points, beta: float = 2.0, threshold: float = 0.5, want=("w", "inside"), out=None, stream=None):
         """winding_numbers on torch tensors: points (n, 3) float32 on cuda:<device> -> the tensors named by `want`, in that order ((n,)
         float32 / (n,) torch.bool; a single name returns the tensor itself), written into `out` (one tensor, a tuple in want's order or
         a dict by name; inside may also be torch.uint8) or new ones, enqueued on `stream` (default: torch.cuda.current_stream())."""
-        import torch
-
-        want = self._winding_want(want)
-        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError("points must be a torch tensor of shape (n, 3)")
-        if self.device >= 0:
-            self._device_tensor(points, "points", (torch.float32,))
-        n = points.shape[0]
+        want = self._field_want(want, "w")
+        n = self._points_tensor(points, shape_first=True)
         return self._sdf_tensors((n,), want, out, stream,
                                  lambda dw, di, s: self.winding_numbers_device(points.data_ptr(), n, dw, di, beta=beta, threshold=threshold, stream=s),
                                  value="w")
@@ -2568,26 +2518,19 @@ class Scene:
     def winding_grid(self, origin, spacing, dims, beta: float = 2.0, threshold: float = 0.5, want=("w", "inside")):
         """cgrt_winding_numbers_grid: winding_numbers on the regular grid of sdf_grid_points(origin, spacing, dims), dims = (nx, ny, nz);
         the lanes make their own points.  Returns the arrays named by `want` shaped (nz, ny, nx) (x fastest)."""
-        want = self._winding_want(want)
-        g, prm = _sdf_grid_struct(origin, spacing, dims), _winding_params(beta, threshold)
-        shape = (g.dims[2], g.dims[1], g.dims[0])
-        m = shape[0] * shape[1] * shape[2] if max(shape) <= 1 << 24 and shape[0] * shape[1] * shape[2] <= 0x7FFFFFFF else 0  # (else: the library says why)
-        res = {"w": np.zeros(m, np.float32) if "w" in want else None, "inside": np.zeros(m, np.uint8) if "inside" in want else None}
-        _check(lib().cgrt_winding_numbers_grid(self._h, C.byref(g), C.byref(prm), _ptr(res["w"]), _ptr(res["inside"])))
-        res = {k: (None if v is None else v.reshape(shape)) for k, v in res.items()}
-        return self._sdf_result(res, want)
+        return self._field_host(lib().cgrt_winding_numbers_grid, "w", want, lambda: _winding_params(beta, threshold),
+                                grid=(origin, spacing, dims))
 
     def winding_grid_device(self, origin, spacing, dims, d_w_ptr: int, d_inside_ptr: int, beta: float = 2.0, threshold: float = 0.5,
                             stream: int = 0) -> None:
         """cgrt_winding_numbers_grid_device: nx * ny * nz float32 at d_w_ptr and / or bytes at d_inside_ptr (0: not wanted), in
         (nz, ny, nx) order, enqueued on the hipStream_t `stream`.  Raw integers."""
-        vp = lambda v: C.c_void_p(v) if v else None  # noqa: E731
         g, prm = _sdf_grid_struct(origin, spacing, dims), _winding_params(beta, threshold)
-        _check(lib().cgrt_winding_numbers_grid_device(self._h, C.byref(g), C.byref(prm), vp(d_w_ptr), vp(d_inside_ptr), vp(stream)))
+        _check(lib().cgrt_winding_numbers_grid_device(self._h, C.byref(g), C.byref(prm), _vp(d_w_ptr), _vp(d_inside_ptr), _vp(stream)))
 
     def winding_grid_tensor(self, origin, spacing, dims, beta: float = 2.0, threshold: float = 0.5, want=("w", "inside"), out=None, stream=None):
         """winding_grid on torch tensors: the tensors named by `want`, shaped (nz, ny, nx), as winding_numbers_tensor returns them."""
-        want = self._winding_want(want)
+        want = self._field_want(want, "w")
         nx, ny, nz = (int(x) for x in dims)
         return self._sdf_tensors((nz, ny, nx), want, out, stream,
                                  lambda dw, di, s: self.winding_grid_device(origin, spacing, dims, dw, di, beta=beta, threshold=threshold, stream=s),
@@ -2626,8 +2569,7 @@ class Scene:
         import torch
 
         inside = self.inside_winding_tensor(points, beta=beta, stream=stream)
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        _, stream = self._torch_stream(stream)
         d2 = self.closest_points_tensor(points, max_dist2=max_dist2, stream=stream)["dist2"]
         with torch.cuda.stream(stream):
             dist = torch.sqrt(d2)
@@ -2680,8 +2622,7 @@ class Scene:
                 attr, forward, lambda g: self._surface_frames_grad_tensor(raycams, cams, W, H, depth, prim_id, g, chw, None, None),
                 keys.index("attr"))
             return dict(zip(keys, got))
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        dev, stream = self._torch_stream(stream)
         _check_one_hip_runtime()
         with torch.cuda.stream(stream):
             res = {k: out[k] if k in out else torch.empty(shape, dtype=torch.float32, device=dev) for k, shape in want.items()}

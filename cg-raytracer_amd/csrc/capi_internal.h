@@ -58,6 +58,11 @@ int hip_fail(hipError_t e, const char* what);
         hipError_t _e = (expr);                        \
         if (_e != hipSuccess) return hip_fail(_e, #expr); \
     } while (0)
+#define CGRT_TRY(expr)              \
+    do {                            \
+        const int _rc = (expr);     \
+        if (_rc) return _rc;        \
+    } while (0)
 
 // RAII device buffer for the host-pointer convenience entries.
 struct DevBuf {
@@ -427,9 +432,10 @@ struct LaneGuard {
     hipError_t pin(int k, size_t bytes, void** out);
 };
 extern const size_t kStageBytes;  // transfers up to this size are staged, larger ones go through the bounce buffers
-// One host-pointer call on a lane.  An entry reads: its checks; begin; input / scratch per slot (the slots size the lane's buffers, which
-// persist); its launch on stream(); output per result; finish.  A result of up to kStageBytes is only staged by output and reaches the
-// caller's memory in finish, behind the stream; a larger one is in place when output returns.  An entry that returns early copies nothing.
+// The transfers of one host-pointer call on a lane: begin; input / scratch per slot (the slots size the lane's buffers, which persist); the
+// launch on stream(); output per result; finish.  A result of up to kStageBytes is only staged by output and reaches the caller's memory in
+// finish, behind the stream; a larger one is in place when output returns.  An entry that returns early copies nothing.  The primitives
+// (capi_prims.cpp) are written with it directly, the queries with QueryCall below.
 struct LaneCall {
     LaneGuard g;
     struct Staged {  // by slot; from: the lane's pinned buffer of the slot, or null (nothing pending)
@@ -447,6 +453,35 @@ struct LaneCall {
     hipError_t zero_counters(size_t words);
     hipError_t read_counters(uint64_t* out, size_t words);
     hipError_t finish();  // waits for the stream, then copies the staged results out
+};
+// One query (capi_queries.cpp) in either form, so that an entry is written once.  Host form: the caller's arrays are host memory and the
+// call runs on a lane.  Device form: they are device memory, checked as spans and used in place on the caller's stream, which is not
+// waited for.  An entry reads: its argument checks; begin; in / out / inout per array, which yield the device pointer either way (every
+// span check passes here, before anything is uploaded or launched: a host form's checks are all argument checks); host_in per host
+// table; its launch on stream(); finish.  Zero bytes: the array is not used, the device pointer is null (host form) or the caller's.
+struct QueryCall {
+    LaneCall c;
+    const bool device;
+    hipStream_t const caller;
+    bool on_lane = false;
+    struct Result {  // by slot; bytes 0: none
+        void *host = nullptr, *d = nullptr;
+        size_t bytes = 0;
+    } results[5];
+    QueryCall(CgrtScene* s, bool device_form, void* stream) : c(s), device(device_form), caller(static_cast<hipStream_t>(stream)) {}
+    hipStream_t stream() const { return on_lane ? c.stream() : caller; }
+    int begin();  // the scene's device becomes current; host form: a lane is taken
+    int in(int slot, const void* p, uint64_t bytes, const char* name, void** d);
+    int out(int slot, void* p, uint64_t bytes, const char* name, void** d);    // host form: downloaded by finish
+    int inout(int slot, void* p, uint64_t bytes, const char* name, void** d);  // uploaded, and downloaded by finish
+    // a table that is host memory in both forms (lights).  A device-form call that has one runs on a lane behind what the caller's stream
+    // held (lane_follow), and its finish blocks; call it after the in / out of the caller's arrays
+    int host_in(int slot, const void* p, size_t bytes, void** d);
+    // counted work (host form only), as LaneCall's; an entry returns after read_counters, without finish
+    unsigned long long* counters() const { return c.counters(); }
+    int zero_counters(size_t words);
+    int read_counters(uint64_t* out, size_t words);
+    int finish();  // on a lane: the results in ascending slot order, then LaneCall::finish; else nothing
 };
 }  // namespace cgrt
 #pragma GCC visibility pop

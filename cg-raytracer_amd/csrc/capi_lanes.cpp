@@ -218,4 +218,53 @@ hipError_t LaneCall::finish() {
         if (e == hipSuccess && s.from) std::memcpy(s.host, s.from, s.bytes);
     return e;
 }
+
+int QueryCall::begin() {
+    HIP_TRY(hipSetDevice(c.g.sc->device));
+    if (device) return CGRT_OK;
+    on_lane = true;
+    return c.g.acquire();
+}
+int QueryCall::in(int slot, const void* p, uint64_t bytes, const char* name, void** d) {
+    *d = device ? const_cast<void*>(p) : nullptr;
+    if (device) return check_device_span(c.g.sc, p, bytes, name);
+    if (bytes) HIP_TRY(c.input(slot, p, bytes, d));
+    return CGRT_OK;
+}
+int QueryCall::out(int slot, void* p, uint64_t bytes, const char* name, void** d) {
+    *d = device ? p : nullptr;
+    if (device) return check_device_span(c.g.sc, p, bytes, name);
+    if (bytes) HIP_TRY(c.scratch(slot, bytes, d));
+    results[slot] = {p, *d, (size_t)bytes};
+    return CGRT_OK;
+}
+int QueryCall::inout(int slot, void* p, uint64_t bytes, const char* name, void** d) {
+    CGRT_TRY(in(slot, p, bytes, name, d));
+    if (!device) results[slot] = {p, *d, (size_t)bytes};
+    return CGRT_OK;
+}
+int QueryCall::host_in(int slot, const void* p, size_t bytes, void** d) {
+    if (!on_lane) {
+        CGRT_TRY(c.g.acquire());
+        on_lane = true;
+        HIP_TRY(lane_follow(c.g, caller));
+    }
+    HIP_TRY(c.input(slot, p, bytes, d));
+    return CGRT_OK;
+}
+int QueryCall::zero_counters(size_t words) {
+    HIP_TRY(c.zero_counters(words));
+    return CGRT_OK;
+}
+int QueryCall::read_counters(uint64_t* out, size_t words) {
+    HIP_TRY(c.read_counters(out, words));
+    return CGRT_OK;
+}
+int QueryCall::finish() {
+    if (!on_lane) return CGRT_OK;
+    for (int k = 0; k < 5; k++)
+        if (results[k].bytes) HIP_TRY(c.output(k, results[k].host, results[k].d, results[k].bytes));
+    HIP_TRY(c.finish());
+    return CGRT_OK;
+}
 }  // namespace cgrt

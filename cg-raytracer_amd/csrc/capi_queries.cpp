@@ -1,6 +1,89 @@
 // capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
 // closest points, crossings, neighbours, signed distance, winding numbers.  None of them touches the scene's frame state (workspace, prediction, hints).
+// Every family is ONE body for its host-pointer and its device-pointer entries, written with a QueryCall (capi_internal.h): the argument
+// checks in the order include/cgrt.h states (`device`: the pointers' alignment too), the host-only scene, the empty call, then begin,
+// in / out per array, the launch on the call's stream, finish.  The exported entries are one-line forwarders.
 #include "capi_internal.h"
+
+// The two pieces more than one family shares come first (templates over the kernels' argument records: C++ linkage).
+
+// ---- the slots of the list entries (crossings and neighbours; DESIGN.md sections 5.21 and 5.26): query i's records go to
+// [offsets[i], offsets[i + 1]) or [i k, (i + 1) k) of `out`, its full count to counts[i].  The one home of the slot rules, their
+// messages and the three slot transfers.
+namespace {
+const uint64_t kSlotMaxCapacity = 1ull << 37;  // records of 8 bytes: 2^40 bytes, the bound of every output here
+struct SlotList {
+    bool list;  // false: a count entry, the fields below but counts unused
+    const uint64_t* offsets;
+    uint32_t k;
+    void* out;
+    uint64_t capacity;
+    uint32_t* counts;
+    // host offsets are read here; device offsets are the kernel's to clamp
+    int rules(uint64_t n, bool device) const {
+        if (!list) return CGRT_OK;
+        if ((offsets != nullptr) == (k > 0)) return fail(CGRT_E_ARG, "exactly one of offsets and k > 0 must be given");
+        if (capacity > kSlotMaxCapacity) return fail(CGRT_E_ARG, "capacity exceeds 2^37 records");
+        if (k && n * (uint64_t)k > capacity) return fail(CGRT_E_ARG, "n * k records exceed capacity");
+        if (!device && offsets && n) {
+            if (offsets[0] != 0) return fail(CGRT_E_ARG, "offsets must start at 0");
+            for (uint64_t i = 0; i < n; i++)
+                if (offsets[i + 1] < offsets[i]) return fail(CGRT_E_ARG, "offsets must not decrease");
+            if (offsets[n] > capacity) return fail(CGRT_E_ARG, "offsets end beyond capacity");
+        }
+        return CGRT_OK;
+    }
+    bool aligned() const { return !((uintptr_t)out % 4 || (uintptr_t)counts % 4 || (uintptr_t)offsets % 8); }
+    // the records the call may write, [0, records): with device offsets any record below capacity, with host offsets those they cover
+    uint64_t records(uint64_t n, bool device) const { return !list ? 0 : offsets ? (device ? capacity : offsets[n]) : n * (uint64_t)k; }
+    bool want_counts() const { return !list || counts != nullptr; }
+    // a host call whose every slot is empty and that asks for no count has nothing to write
+    bool nothing(uint64_t n, bool device) const { return !device && records(n, false) == 0 && !want_counts(); }
+    // slots 1 the offsets, 2 the records, 3 the counts, into the kernel's record (no record to write: the count search)
+    template <class Args>
+    int transfer(QueryCall& c, uint64_t n, Args* A) const {
+        void *doff = nullptr, *dout = nullptr, *dcnt = nullptr;
+        A->k = k;
+        A->capacity = records(n, c.device);
+        CGRT_TRY(c.in(1, offsets, offsets ? (n + 1) * 8 : 0, "d_offsets", &doff));
+        CGRT_TRY(c.out(2, out, A->capacity * sizeof(*A->out), "d_out", &dout));
+        CGRT_TRY(c.out(3, counts, want_counts() ? n * 4 : 0, "d_counts", &dcnt));
+        A->offsets = static_cast<const unsigned long long*>(doff);
+        A->out = static_cast<decltype(A->out)>(dout);
+        A->counts = static_cast<uint32_t*>(dcnt);
+        return CGRT_OK;
+    }
+};
+}  // namespace
+
+// ---- the points of the signed-distance and winding entries (DESIGN.md sections 5.24 and 5.25)
+namespace {
+// The points of a signed-distance or winding call, a list or a grid whose lanes make their own: the NULL rules, the sizes, and A's points /
+// n / origin / spacing / dims (SdfArgs or WindingArgs).  kNoResult: neither output is asked for, which the family reports in its own words.
+const int kNoResult = 1;
+template <class Args>
+int point_source(const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, bool have_result, Args* A) {
+    if (is_grid ? !grid : (n && !points)) return fail(CGRT_E_ARG, is_grid ? "grid is NULL" : "NULL argument");
+    if (!have_result) return kNoResult;
+    if (is_grid) {
+        n = 1;
+        for (int c = 0; c < 3; c++) {
+            if (grid->dims[c] < 1 || grid->dims[c] > (1u << 24)) return fail(CGRT_E_ARG, "grid dims must be in 1..2^24");
+            n *= grid->dims[c];  // (below 2^55 before the test, which follows every factor)
+            if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many grid points: nx * ny * nz exceeds 0x7fffffff");
+            if (!std::isfinite(grid->origin[c]) || !std::isfinite(grid->spacing[c])) return fail(CGRT_E_ARG, "grid origin and spacing must be finite");
+            A->origin[c] = grid->origin[c];
+            A->spacing[c] = grid->spacing[c];
+            A->dims[c] = grid->dims[c];
+        }
+    } else if (n > 0x7fffffffull) {
+        return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
+    }
+    A->points = points;
+    A->n = (uint32_t)n;
+    return CGRT_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -15,123 +98,74 @@ int query_args(const CgrtScene* s, const void* in, uint64_t n, const void* out, 
     if (n > kMaxAnswers || (per_point && n > kMaxAnswers / per_point)) return fail(CGRT_E_ARG, "too many answers: n (x lights) exceeds 0x7fffffff");
     return CGRT_OK;
 }
-// n points x nlights lights on the lane's stream (lights through the lane's slot 3)
-int in_shadow_on_lane(LaneCall& c, CgrtScene* s, const float* d_points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* d_out) {
-    void* dl = nullptr;
-    HIP_TRY(c.input(3, lights, (size_t)nlights * 24, &dl));
-    HIP_TRY(launch_in_shadow(s->dev, d_points, n, static_cast<const float*>(dl), nlights, d_out, c.stream()));
-    return CGRT_OK;
+// slots: 0 the rays, 1 the answers
+int occluded_query(CgrtScene* s, bool device, const CgrtRay* rays, uint64_t n, uint8_t* hit, void* stream) {
+    CGRT_TRY(query_args(s, rays, n, hit, 0, false));
+    if (device && (uintptr_t)rays % 4) return fail(CGRT_E_ARG, "d_rays must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    QueryCall c(s, device, stream);
+    void *dr = nullptr, *dh = nullptr;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, rays, n * sizeof(CgrtRay), "d_rays", &dr));
+    CGRT_TRY(c.out(1, hit, n, "d_hit", &dh));
+    HIP_TRY(launch_occluded(s->dev, static_cast<const float*>(dr), n, static_cast<uint8_t*>(dh), c.stream()));
+    return c.finish();
 }
-// the soft-shadow counts of n points on the lane's stream (spherical lights through slot 3, the unit vectors through slot 2); d_lit zeroed here
-int soft_lit_on_lane(LaneCall& c, CgrtScene* s, const float* d_points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* d_lit) {
-    const uint64_t SL = soft->nspherical;
-    void *dl = nullptr, *du = nullptr;
-    HIP_TRY(c.input(3, soft->spherical, SL * 28, &dl));
-    HIP_TRY(c.input(2, soft->unit_vectors, (size_t)soft->nunits * 12, &du));
-    HIP_TRY(hipMemsetAsync(d_lit, 0, n * SL * sizeof(uint32_t), c.stream()));
+// n points x nlights lights (slots: 0 the points, 1 the answers, 3 the lights, host memory in both forms)
+int in_shadow_query(CgrtScene* s, bool device, const float* points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* out, void* stream) {
+    CGRT_TRY(query_args(s, points, n, out, nlights, nlights && !lights));
+    if (device && (uintptr_t)points % 4) return fail(CGRT_E_ARG, "d_points must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0 || nlights == 0) return CGRT_OK;
+    QueryCall c(s, device, stream);
+    void *dp = nullptr, *dout = nullptr, *dl = nullptr;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, points, n * 12, "d_points", &dp));
+    CGRT_TRY(c.out(1, out, n * nlights, "d_out", &dout));
+    CGRT_TRY(c.host_in(3, lights, (size_t)nlights * 24, &dl));
+    HIP_TRY(launch_in_shadow(s->dev, static_cast<const float*>(dp), n, static_cast<const float*>(dl), nlights, static_cast<uint8_t*>(dout), c.stream()));
+    return c.finish();
+}
+// the soft-shadow counts of n points (slots: 0 the points, 1 the counts, zeroed here, 3 the spherical lights, 2 the unit vectors)
+int soft_lit_query(CgrtScene* s, bool device, const float* points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* lit, void* stream) {
+    const uint64_t SL = soft ? soft->nspherical : 0u;
+    CGRT_TRY(query_args(s, points, n, lit, SL, false));
+    CGRT_TRY(soft_rules(soft));
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)lit % 4)) return fail(CGRT_E_ARG, "d_points and d_lit must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0 || SL == 0) return CGRT_OK;
+    QueryCall c(s, device, stream);
+    const uint64_t lit_bytes = n * SL * sizeof(uint32_t);
+    void *dp = nullptr, *dlit = nullptr, *dl = nullptr, *du = nullptr;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, points, n * 12, "d_points", &dp));
+    CGRT_TRY(c.out(1, lit, lit_bytes, "d_lit", &dlit));
+    CGRT_TRY(c.host_in(3, soft->spherical, SL * 28, &dl));
+    CGRT_TRY(c.host_in(2, soft->unit_vectors, (size_t)soft->nunits * 12, &du));
+    HIP_TRY(hipMemsetAsync(dlit, 0, lit_bytes, c.stream()));
     // (level stays 0, cgrt_shade_rays' convention: pixel = i, level 0)
     const SoftDev Q = soft_dev(*soft, (unsigned)SL, static_cast<const float*>(dl), static_cast<const float*>(du));
-    HIP_TRY(launch_soft_points(s->dev, Q, d_points, n, d_lit, soft->closest_hit ? 0 : 1, c.stream()));
-    return CGRT_OK;
+    HIP_TRY(launch_soft_points(s->dev, Q, static_cast<const float*>(dp), n, static_cast<uint32_t*>(dlit), soft->closest_hit ? 0 : 1, c.stream()));
+    return c.finish();
 }
 }  // namespace
 
 int cgrt_occluded_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, uint8_t* d_hit, void* stream) {
-    int rc = query_args(s, d_rays, n, d_hit, 0, false);
-    if (rc) return rc;
-    if ((uintptr_t)d_rays % 4) return fail(CGRT_E_ARG, "d_rays must be 4-byte aligned");
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_hit, n, "d_hit")) != CGRT_OK) return rc;
-    HIP_TRY(launch_occluded(s->dev, reinterpret_cast<const float*>(d_rays), n, d_hit, static_cast<hipStream_t>(stream)));
-    return CGRT_OK;
+    return occluded_query(s, true, d_rays, n, d_hit, stream);
 }
-int cgrt_occluded(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint8_t* hit) {
-    int rc = query_args(s, rays, n, hit, 0, false);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    void *dr = nullptr, *dh = nullptr;
-    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(c.scratch(1, n, &dh));
-    HIP_TRY(launch_occluded(s->dev, static_cast<const float*>(dr), n, static_cast<uint8_t*>(dh), c.stream()));
-    HIP_TRY(c.output(1, hit, dh, n));
-    HIP_TRY(c.finish());
-    return CGRT_OK;
-}
-
+int cgrt_occluded(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint8_t* hit) { return occluded_query(s, false, rays, n, hit, nullptr); }
 int cgrt_in_shadow_device(CgrtScene* s, const float* d_points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* d_out, void* stream) {
-    int rc = query_args(s, d_points, n, d_out, nlights, nlights && !lights);
-    if (rc) return rc;
-    if ((uintptr_t)d_points % 4) return fail(CGRT_E_ARG, "d_points must be 4-byte aligned");
-    NEED_DEVICE(s);
-    if (n == 0 || nlights == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_out, n * nlights, "d_out")) != CGRT_OK) return rc;
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    HIP_TRY(lane_follow(c.g, static_cast<hipStream_t>(stream)));
-    if ((rc = in_shadow_on_lane(c, s, d_points, n, lights, nlights, d_out)) != CGRT_OK) return rc;
-    HIP_TRY(c.finish());
-    return CGRT_OK;
+    return in_shadow_query(s, true, d_points, n, lights, nlights, d_out, stream);
 }
 int cgrt_in_shadow(CgrtScene* s, const float* points, uint64_t n, const float* lights, uint32_t nlights, uint8_t* out) {
-    int rc = query_args(s, points, n, out, nlights, nlights && !lights);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0 || nlights == 0) return CGRT_OK;
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    const uint64_t m = n * nlights;
-    void *dp = nullptr, *dout = nullptr;
-    HIP_TRY(c.input(0, points, n * 12, &dp));
-    HIP_TRY(c.scratch(1, m, &dout));
-    if ((rc = in_shadow_on_lane(c, s, static_cast<const float*>(dp), n, lights, nlights, static_cast<uint8_t*>(dout))) != CGRT_OK) return rc;
-    HIP_TRY(c.output(1, out, dout, m));
-    HIP_TRY(c.finish());
-    return CGRT_OK;
+    return in_shadow_query(s, false, points, n, lights, nlights, out, nullptr);
 }
-
 int cgrt_soft_lit_device(CgrtScene* s, const float* d_points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* d_lit, void* stream) {
-    const uint32_t SL = soft ? soft->nspherical : 0u;
-    int rc = query_args(s, d_points, n, d_lit, SL, false);
-    if (rc) return rc;
-    if ((rc = soft_rules(soft)) != CGRT_OK) return rc;
-    if ((uintptr_t)d_points % 4 || (uintptr_t)d_lit % 4) return fail(CGRT_E_ARG, "d_points and d_lit must be 4-byte aligned");
-    NEED_DEVICE(s);
-    if (n == 0 || SL == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_lit, n * SL * 4, "d_lit")) != CGRT_OK) return rc;
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    HIP_TRY(lane_follow(c.g, static_cast<hipStream_t>(stream)));
-    if ((rc = soft_lit_on_lane(c, s, d_points, n, soft, d_lit)) != CGRT_OK) return rc;
-    HIP_TRY(c.finish());
-    return CGRT_OK;
+    return soft_lit_query(s, true, d_points, n, soft, d_lit, stream);
 }
 int cgrt_soft_lit(CgrtScene* s, const float* points, uint64_t n, const CgrtSoftShadows* soft, uint32_t* lit) {
-    const uint32_t SL = soft ? soft->nspherical : 0u;
-    int rc = query_args(s, points, n, lit, SL, false);
-    if (rc) return rc;
-    if ((rc = soft_rules(soft)) != CGRT_OK) return rc;
-    NEED_DEVICE(s);
-    if (n == 0 || SL == 0) return CGRT_OK;
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    const uint64_t m = n * SL * sizeof(uint32_t);
-    void *dp = nullptr, *dl = nullptr;
-    HIP_TRY(c.input(0, points, n * 12, &dp));
-    HIP_TRY(c.scratch(1, m, &dl));
-    if ((rc = soft_lit_on_lane(c, s, static_cast<const float*>(dp), n, soft, static_cast<uint32_t*>(dl))) != CGRT_OK) return rc;
-    HIP_TRY(c.output(1, lit, dl, m));
-    HIP_TRY(c.finish());
-    return CGRT_OK;
+    return soft_lit_query(s, false, points, n, soft, lit, nullptr);
 }
 
 // ---- surface attributes (include/cgrt.h cgrt_hit_barycentrics*, cgrt_interpolate_hits*, cgrt_surface_*_device):
@@ -223,39 +257,22 @@ int surface_list_launch(CgrtScene* s, const void* d_rays, const void* d_hits, ui
     HIP_TRY(launch_surface(A, SURFACE_LIST, st));
     return CGRT_OK;
 }
-int surface_list_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, bool attr, const float* d_attr, uint32_t channels,
-                        float* d_res, void* stream) {
-    int rc = surface_list_args(s, d_rays, d_hits, n, attr, d_attr, channels, d_res, true);
-    if (rc) return rc;
+// cgrt_hit_barycentrics* (attr false: res is bary) and cgrt_interpolate_hits* (res is out); slots: 0 rays, 1 hits, 2 the result, 3 the table
+int surface_list(CgrtScene* s, bool device, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, bool attr, const float* table, uint32_t channels,
+                 float* res, void* stream) {
+    CGRT_TRY(surface_list_args(s, rays, hits, n, attr, table, channels, res, device));
     NEED_DEVICE(s);
     if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_hits, n * sizeof(CgrtHit), "d_hits")) != CGRT_OK) return rc;
-    if (attr && (rc = check_device_span(s, d_attr, (uint64_t)s->nverts * channels * 4ull, "d_attr")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_res, n * (attr ? channels : 3u) * 4ull, attr ? "d_out" : "d_bary")) != CGRT_OK) return rc;
-    return surface_list_launch(s, d_rays, d_hits, n, d_attr, channels, attr ? nullptr : d_res, attr ? d_res : nullptr, static_cast<hipStream_t>(stream));
-}
-// host pointers, on a call lane (slots: 0 rays, 1 hits, 2 the result, 3 the attribute table)
-int surface_list_host(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, bool attr, const float* table, uint32_t channels, float* res) {
-    int rc = surface_list_args(s, rays, hits, n, attr, table, channels, res, false);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    const size_t res_bytes = (size_t)n * (attr ? channels : 3u) * 4u, table_bytes = attr ? (size_t)s->nverts * channels * 4u : 0;
-    void *dr = nullptr, *dh = nullptr, *dres = nullptr, *dt = nullptr;
-    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(c.input(1, hits, n * sizeof(CgrtHit), &dh));
-    HIP_TRY(c.scratch(2, res_bytes, &dres));
-    if (attr) HIP_TRY(c.input(3, table, table_bytes, &dt));
-    if ((rc = surface_list_launch(s, dr, dh, n, static_cast<const float*>(dt), channels, attr ? nullptr : static_cast<float*>(dres),
-                                  attr ? static_cast<float*>(dres) : nullptr, c.stream())) != CGRT_OK)
-        return rc;
-    HIP_TRY(c.output(2, res, dres, res_bytes));
-    HIP_TRY(c.finish());
-    return CGRT_OK;
+    QueryCall c(s, device, stream);
+    void *dr = nullptr, *dh = nullptr, *dt = nullptr, *dres = nullptr;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, rays, n * sizeof(CgrtRay), "d_rays", &dr));
+    CGRT_TRY(c.in(1, hits, n * sizeof(CgrtHit), "d_hits", &dh));
+    CGRT_TRY(c.in(3, table, attr ? (uint64_t)s->nverts * channels * 4ull : 0, "d_attr", &dt));
+    CGRT_TRY(c.out(2, res, n * (attr ? channels : 3u) * 4ull, attr ? "d_out" : "d_bary", &dres));
+    CGRT_TRY(surface_list_launch(s, dr, dh, n, static_cast<const float*>(dt), channels, attr ? nullptr : static_cast<float*>(dres),
+                                 attr ? static_cast<float*>(dres) : nullptr, c.stream()));
+    return c.finish();
 }
 // cgrt_surface_views_device and its ray-camera twin (exactly one of cams, raycams)
 int surface_frames_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H, const float* d_depth,
@@ -316,39 +333,21 @@ int surface_list_grad_launch(CgrtScene* s, const void* d_rays, const void* d_hit
     HIP_TRY(launch_surface_grad(A, SURFACE_LIST, st));
     return CGRT_OK;
 }
-int surface_list_grad_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out, uint32_t channels,
-                             float* d_grad_attr, void* stream) {
-    int rc = surface_list_args(s, d_rays, d_hits, n, true, d_grad_attr, channels, d_grad_out, true);
-    if (rc) return rc;
+// cgrt_interpolate_hits_grad*; slots: 0 rays, 1 hits, 2 grad_out, 3 grad_attr (host form: uploaded, accumulated into, downloaded)
+int surface_list_grad(CgrtScene* s, bool device, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
+                      float* grad_attr, void* stream) {
+    CGRT_TRY(surface_list_args(s, rays, hits, n, true, grad_attr, channels, grad_out, device));
     NEED_DEVICE(s);
     if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_hits, n * sizeof(CgrtHit), "d_hits")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_grad_out, n * channels * 4ull, "d_grad_out")) != CGRT_OK) return rc;
-    return surface_list_grad_launch(s, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, static_cast<hipStream_t>(stream));
-}
-// host pointers, on a call lane (slots: 0 rays, 1 hits, 2 grad_out, 3 grad_attr: uploaded, accumulated into, downloaded)
-int surface_list_grad_host(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
-                           float* grad_attr) {
-    int rc = surface_list_args(s, rays, hits, n, true, grad_attr, channels, grad_out, false);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    const size_t go_bytes = (size_t)n * channels * 4u, table_bytes = (size_t)s->nverts * channels * 4u;
-    void *dr = nullptr, *dh = nullptr, *dgo = nullptr, *dt = nullptr;
-    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
-    HIP_TRY(c.input(1, hits, n * sizeof(CgrtHit), &dh));
-    HIP_TRY(c.input(2, grad_out, go_bytes, &dgo));
-    HIP_TRY(c.input(3, grad_attr, table_bytes, &dt));
-    if ((rc = surface_list_grad_launch(s, dr, dh, n, static_cast<const float*>(dgo), channels, static_cast<float*>(dt), c.stream())) != CGRT_OK)
-        return rc;
-    HIP_TRY(c.output(3, grad_attr, dt, table_bytes));
-    HIP_TRY(c.finish());
-    return CGRT_OK;
+    QueryCall c(s, device, stream);
+    void *dr = nullptr, *dh = nullptr, *dt = nullptr, *dgo = nullptr;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, rays, n * sizeof(CgrtRay), "d_rays", &dr));
+    CGRT_TRY(c.in(1, hits, n * sizeof(CgrtHit), "d_hits", &dh));
+    CGRT_TRY(c.inout(3, grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr", &dt));
+    CGRT_TRY(c.in(2, grad_out, n * channels * 4ull, "d_grad_out", &dgo));
+    CGRT_TRY(surface_list_grad_launch(s, dr, dh, n, static_cast<const float*>(dgo), channels, static_cast<float*>(dt), c.stream()));
+    return c.finish();
 }
 // cgrt_surface_views_grad_device and its ray-camera twin (exactly one of cams, raycams)
 int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H,
@@ -385,11 +384,24 @@ int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtR
 
 int cgrt_interpolate_hits_grad(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
                                float* grad_attr) {
-    return surface_list_grad_host(s, rays, hits, n, grad_out, channels, grad_attr);
+    return surface_list_grad(s, false, rays, hits, n, grad_out, channels, grad_attr, nullptr);
 }
 int cgrt_interpolate_hits_grad_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out,
                                       uint32_t channels, float* d_grad_attr, void* stream) {
-    return surface_list_grad_device(s, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, stream);
+    return surface_list_grad(s, true, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, stream);
+}
+int cgrt_hit_barycentrics(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, float* bary) {
+    return surface_list(s, false, rays, hits, n, false, nullptr, 0, bary, nullptr);
+}
+int cgrt_hit_barycentrics_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, float* d_bary, void* stream) {
+    return surface_list(s, true, d_rays, d_hits, n, false, nullptr, 0, d_bary, stream);
+}
+int cgrt_interpolate_hits(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* attr, uint32_t channels, float* out) {
+    return surface_list(s, false, rays, hits, n, true, attr, channels, out, nullptr);
+}
+int cgrt_interpolate_hits_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_attr, uint32_t channels,
+                                 float* d_out, void* stream) {
+    return surface_list(s, true, d_rays, d_hits, n, true, d_attr, channels, d_out, stream);
 }
 int cgrt_surface_views_grad_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
                                    const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
@@ -402,19 +414,6 @@ int cgrt_surface_raycams_grad_device(CgrtScene* s, const CgrtRayCamera* cams, ui
     return surface_frames_grad_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, stream);
 }
 
-int cgrt_hit_barycentrics(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, float* bary) {
-    return surface_list_host(s, rays, hits, n, false, nullptr, 0, bary);
-}
-int cgrt_hit_barycentrics_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, float* d_bary, void* stream) {
-    return surface_list_device(s, d_rays, d_hits, n, false, nullptr, 0, d_bary, stream);
-}
-int cgrt_interpolate_hits(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* attr, uint32_t channels, float* out) {
-    return surface_list_host(s, rays, hits, n, true, attr, channels, out);
-}
-int cgrt_interpolate_hits_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_attr, uint32_t channels,
-                                 float* d_out, void* stream) {
-    return surface_list_device(s, d_rays, d_hits, n, true, d_attr, channels, d_out, stream);
-}
 int cgrt_surface_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth, const uint32_t* d_prim_id,
                               const float* d_attr, uint32_t channels, float* d_bary, float* d_out, int chw, void* stream) {
     return surface_frames_device(s, cams, nullptr, nviews, W, H, d_depth, d_prim_id, d_attr, channels, d_bary, d_out, chw, stream);
@@ -428,61 +427,47 @@ int cgrt_surface_raycams_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_
 // Nothing is traced and no scene state is read or written; the checks come in the order include/cgrt.h states, all before any device work.
 namespace {
 static_assert(sizeof(CgrtClosest) == sizeof(CgrtClosestDev), "CgrtClosest is what the kernels write");
-int closest_args(const CgrtScene* s, const void* points, uint64_t n, float max_dist2, const void* out, bool device) {
+// slots: 0 the points, 1 the records; how: 0 tree search, 1 brute force, 2 counted tree search (host form only: `work` in the place of out)
+int closest_query(CgrtScene* s, bool device, const float* points, uint64_t n, float max_dist2, CgrtClosest* out, int how, uint64_t* work,
+                  void* stream) {
     if (!s) return fail(CGRT_E_ARG, "scene is NULL");
-    if (n && (!points || !out)) return fail(CGRT_E_ARG, "NULL argument");
+    if (n && (!points || (how == 2 ? !work : !out))) return fail(CGRT_E_ARG, "NULL argument");
     if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many queries: n exceeds 0x7fffffff");
     if (!(max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
     if (device && ((uintptr_t)points % 4 || (uintptr_t)out % 4)) return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
-    return CGRT_OK;
-}
-// host pointers, on a call lane (slots: 0 the points, 1 the records); how: 0 tree search, 1 brute force, 2 counted tree search
-int closest_host(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out, int how, uint64_t* work) {
-    int rc = closest_args(s, points, n, max_dist2, how == 2 ? static_cast<const void*>(work) : out, false);
-    if (rc) return rc;
     NEED_DEVICE(s);
     if (n == 0) return CGRT_OK;
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    const size_t out_bytes = (size_t)n * sizeof(CgrtClosest);
+    QueryCall c(s, device, stream);
     void *dp = nullptr, *dout = nullptr;
-    HIP_TRY(c.input(0, points, n * 12, &dp));
-    HIP_TRY(c.scratch(1, out_bytes, &dout));
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, points, n * 12, "d_points", &dp));
+    CGRT_TRY(c.out(1, out, n * sizeof(CgrtClosest), "d_out", &dout));
+    const float* const P = static_cast<const float*>(dp);
+    CgrtClosestDev* const R = static_cast<CgrtClosestDev*>(dout);
     if (how == 2) {
-        HIP_TRY(c.zero_counters(2));
-        HIP_TRY(launch_closest(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), c.counters(), c.stream()));
-        HIP_TRY(c.read_counters(work, 2));
-        return CGRT_OK;
+        CGRT_TRY(c.zero_counters(2));
+        HIP_TRY(launch_closest(s->dev, P, n, max_dist2, R, c.counters(), c.stream()));
+        return c.read_counters(work, 2);
     }
     if (how == 1)
-        HIP_TRY(launch_closest_brute(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), c.stream()));
+        HIP_TRY(launch_closest_brute(s->dev, P, n, max_dist2, R, c.stream()));
     else
-        HIP_TRY(launch_closest(s->dev, static_cast<const float*>(dp), n, max_dist2, static_cast<CgrtClosestDev*>(dout), nullptr, c.stream()));
-    HIP_TRY(c.output(1, out, dout, out_bytes));
-    HIP_TRY(c.finish());
-    return CGRT_OK;
+        HIP_TRY(launch_closest(s->dev, P, n, max_dist2, R, nullptr, c.stream()));
+    return c.finish();
 }
 }  // namespace
 
 int cgrt_closest_points(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out) {
-    return closest_host(s, points, n, max_dist2, out, 0, nullptr);
+    return closest_query(s, false, points, n, max_dist2, out, 0, nullptr, nullptr);
 }
 int cgrt_closest_points_brute(CgrtScene* s, const float* points, uint64_t n, float max_dist2, CgrtClosest* out) {
-    return closest_host(s, points, n, max_dist2, out, 1, nullptr);
+    return closest_query(s, false, points, n, max_dist2, out, 1, nullptr, nullptr);
 }
 int cgrt_debug_closest_work(CgrtScene* s, const float* points, uint64_t n, float max_dist2, uint64_t* out2) {
-    return closest_host(s, points, n, max_dist2, nullptr, 2, out2);
+    return closest_query(s, false, points, n, max_dist2, nullptr, 2, out2, nullptr);
 }
 int cgrt_closest_points_device(CgrtScene* s, const float* d_points, uint64_t n, float max_dist2, CgrtClosest* d_out, void* stream) {
-    int rc = closest_args(s, d_points, n, max_dist2, d_out, true);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
-    if ((rc = check_device_span(s, d_out, n * sizeof(CgrtClosest), "d_out")) != CGRT_OK) return rc;
-    HIP_TRY(launch_closest(s->dev, d_points, n, max_dist2, reinterpret_cast<CgrtClosestDev*>(d_out), nullptr, static_cast<hipStream_t>(stream)));
-    return CGRT_OK;
+    return closest_query(s, true, d_points, n, max_dist2, d_out, 0, nullptr, stream);
 }
 
 // ---- crossing queries (include/cgrt.h cgrt_count_crossings*, cgrt_list_crossings*): every triangle a ray passes
@@ -490,7 +475,6 @@ int cgrt_closest_points_device(CgrtScene* s, const float* d_points, uint64_t n, 
 // states, all before any device work.
 namespace {
 static_assert(sizeof(CgrtCrossing) == sizeof(CgrtCrossingDev), "CgrtCrossing is what the kernels write");
-const uint64_t kCrossingMaxCapacity = 1ull << 37;
 // where the conservative box test's argument does not hold the whole call tests every triangle: a wild triangle is accepted by every ray
 // wherever its boxes are, and a non-finite vertex leaves its boxes meaningless
 bool crossing_brute_scene(const CgrtScene* s) {
@@ -499,113 +483,55 @@ bool crossing_brute_scene(const CgrtScene* s) {
         if (w) return true;
     return false;
 }
-// result: counts for the count entries, out2 for the work entry, out for the list entries; list: the slot arguments are checked
-int crossing_args(const CgrtScene* s, const void* rays, uint64_t n, const void* result, bool list, const uint64_t* offsets, uint32_t k,
-                  uint64_t capacity, const void* counts, bool device) {
+// slots: 0 the rays, then the list's; how: 0 tree search, 1 brute force, 2 counted tree search (count mode; host form only: `work`)
+int crossing_query(CgrtScene* s, bool device, const CgrtRay* rays, uint64_t n, const SlotList& L, int how, uint64_t* work, void* stream) {
+    const void* const result = how == 2 ? static_cast<const void*>(work) : (L.list ? L.out : static_cast<const void*>(L.counts));
     if (!s) return fail(CGRT_E_ARG, "scene is NULL");
     if (n && (!rays || !result)) return fail(CGRT_E_ARG, "NULL argument");
     if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many rays: n exceeds 0x7fffffff");
-    if (list) {
-        if ((offsets != nullptr) == (k > 0)) return fail(CGRT_E_ARG, "exactly one of offsets and k > 0 must be given");
-        if (capacity > kCrossingMaxCapacity) return fail(CGRT_E_ARG, "capacity exceeds 2^37 records");
-        if (k && n * (uint64_t)k > capacity) return fail(CGRT_E_ARG, "n * k records exceed capacity");
-        if (!device && offsets && n) {
-            if (offsets[0] != 0) return fail(CGRT_E_ARG, "offsets must start at 0");
-            for (uint64_t i = 0; i < n; i++)
-                if (offsets[i + 1] < offsets[i]) return fail(CGRT_E_ARG, "offsets must not decrease");
-            if (offsets[n] > capacity) return fail(CGRT_E_ARG, "offsets end beyond capacity");
-        }
-    }
-    if (device && ((uintptr_t)rays % 4 || (uintptr_t)result % 4 || (uintptr_t)counts % 4 || (uintptr_t)offsets % 8))
-        return fail(CGRT_E_ARG, "device pointers must be aligned to their elements");
-    return CGRT_OK;
-}
-// host pointers, on a call lane (slots: 0 the rays, 1 the offsets, 2 the records, 3 the counts); how: 0 tree search, 1 brute force,
-// 2 counted tree search (count mode)
-int crossing_host(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out, uint64_t capacity,
-                  uint32_t* counts, bool list, int how, uint64_t* work) {
-    int rc = crossing_args(s, rays, n, how == 2 ? static_cast<const void*>(work) : (list ? static_cast<const void*>(out) : counts), list, offsets,
-                           k, capacity, counts, false);
-    if (rc) return rc;
+    CGRT_TRY(L.rules(n, device));
+    if (device && ((uintptr_t)rays % 4 || !L.aligned())) return fail(CGRT_E_ARG, "device pointers must be aligned to their elements");
     NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    const uint64_t used = list ? (offsets ? offsets[n] : n * (uint64_t)k) : 0;  // the slots are records [0, used)
-    const bool want_counts = !list || counts != nullptr;
-    if (how != 2 && used == 0 && !want_counts) return CGRT_OK;  // every slot is empty and no count is asked for: nothing to write
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    const bool brute = how == 1 || crossing_brute_scene(s);
-    const size_t out_bytes = (size_t)used * sizeof(CgrtCrossing), cnt_bytes = (size_t)n * 4u;
-    void *dr = nullptr, *doff = nullptr, *dout = nullptr, *dcnt = nullptr;
-    HIP_TRY(c.input(0, rays, n * sizeof(CgrtRay), &dr));
-    if (offsets) HIP_TRY(c.input(1, offsets, (n + 1) * 8, &doff));
-    if (used) HIP_TRY(c.scratch(2, out_bytes, &dout));  // (a lane's buffer that was never needed is a null pointer)
-    if (want_counts || how == 2) HIP_TRY(c.scratch(3, cnt_bytes, &dcnt));
+    if (n == 0 || L.nothing(n, device)) return CGRT_OK;
+    QueryCall c(s, device, stream);
+    void* dr = nullptr;
     CrossingArgs A{};
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, rays, n * sizeof(CgrtRay), "d_rays", &dr));
+    CGRT_TRY(L.transfer(c, n, &A));
     A.rays = static_cast<const float*>(dr);
     A.n = n;
-    A.offsets = static_cast<const unsigned long long*>(doff);
-    A.k = k;
-    A.out = static_cast<CgrtCrossingDev*>(dout);  // no record to write (count entries, or every slot empty): the count search
-    A.capacity = used;
-    A.counts = static_cast<uint32_t*>(dcnt);
+    const bool brute = how == 1 || crossing_brute_scene(s);
     if (how == 2) {
-        HIP_TRY(c.zero_counters(2));
+        CGRT_TRY(c.zero_counters(2));
         HIP_TRY(launch_crossings(s->dev, A, brute, c.counters(), c.stream()));
-        HIP_TRY(c.read_counters(work, 2));
-        return CGRT_OK;
+        return c.read_counters(work, 2);
     }
     HIP_TRY(launch_crossings(s->dev, A, brute, nullptr, c.stream()));
-    if (used) HIP_TRY(c.output(2, out, dout, out_bytes));
-    if (want_counts) HIP_TRY(c.output(3, counts, dcnt, cnt_bytes));
-    HIP_TRY(c.finish());
-    return CGRT_OK;
-}
-int crossing_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const uint64_t* d_offsets, uint32_t k, CgrtCrossing* d_out, uint64_t capacity,
-                    uint32_t* d_counts, bool list, void* stream) {
-    int rc = crossing_args(s, d_rays, n, list ? static_cast<const void*>(d_out) : d_counts, list, d_offsets, k, capacity, d_counts, true);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_rays, n * sizeof(CgrtRay), "d_rays")) != CGRT_OK) return rc;
-    if (d_offsets && (rc = check_device_span(s, d_offsets, (n + 1) * 8, "d_offsets")) != CGRT_OK) return rc;
-    // with offsets any record below capacity may be written; with k the slots are the first n * k records
-    if (list && (rc = check_device_span(s, d_out, (d_offsets ? capacity : n * (uint64_t)k) * sizeof(CgrtCrossing), "d_out")) != CGRT_OK) return rc;
-    if (d_counts && (rc = check_device_span(s, d_counts, n * 4, "d_counts")) != CGRT_OK) return rc;
-    CrossingArgs A{};
-    A.rays = reinterpret_cast<const float*>(d_rays);
-    A.n = n;
-    A.offsets = reinterpret_cast<const unsigned long long*>(d_offsets);
-    A.k = k;
-    A.out = list ? reinterpret_cast<CgrtCrossingDev*>(d_out) : nullptr;
-    A.capacity = capacity;
-    A.counts = d_counts;
-    HIP_TRY(launch_crossings(s->dev, A, crossing_brute_scene(s), nullptr, static_cast<hipStream_t>(stream)));
-    return CGRT_OK;
+    return c.finish();
 }
 }  // namespace
 
 int cgrt_count_crossings(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint32_t* counts) {
-    return crossing_host(s, rays, n, nullptr, 0, nullptr, 0, counts, false, 0, nullptr);
+    return crossing_query(s, false, rays, n, {false, nullptr, 0, nullptr, 0, counts}, 0, nullptr, nullptr);
 }
 int cgrt_count_crossings_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, uint32_t* d_counts, void* stream) {
-    return crossing_device(s, d_rays, n, nullptr, 0, nullptr, 0, d_counts, false, stream);
+    return crossing_query(s, true, d_rays, n, {false, nullptr, 0, nullptr, 0, d_counts}, 0, nullptr, stream);
 }
 int cgrt_list_crossings(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out, uint64_t capacity,
                         uint32_t* counts) {
-    return crossing_host(s, rays, n, offsets, k, out, capacity, counts, true, 0, nullptr);
+    return crossing_query(s, false, rays, n, {true, offsets, k, out, capacity, counts}, 0, nullptr, nullptr);
 }
 int cgrt_list_crossings_device(CgrtScene* s, const CgrtRay* d_rays, uint64_t n, const uint64_t* d_offsets, uint32_t k, CgrtCrossing* d_out,
                                uint64_t capacity, uint32_t* d_counts, void* stream) {
-    return crossing_device(s, d_rays, n, d_offsets, k, d_out, capacity, d_counts, true, stream);
+    return crossing_query(s, true, d_rays, n, {true, d_offsets, k, d_out, capacity, d_counts}, 0, nullptr, stream);
 }
 int cgrt_list_crossings_brute(CgrtScene* s, const CgrtRay* rays, uint64_t n, const uint64_t* offsets, uint32_t k, CgrtCrossing* out,
                               uint64_t capacity, uint32_t* counts) {
-    return crossing_host(s, rays, n, offsets, k, out, capacity, counts, true, 1, nullptr);
+    return crossing_query(s, false, rays, n, {true, offsets, k, out, capacity, counts}, 1, nullptr, nullptr);
 }
 int cgrt_debug_crossing_work(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint64_t* out2) {
-    return crossing_host(s, rays, n, nullptr, 0, nullptr, 0, nullptr, false, 2, out2);
+    return crossing_query(s, false, rays, n, {false, nullptr, 0, nullptr, 0, nullptr}, 2, out2, nullptr);
 }
 
 // ---- neighbour queries (include/cgrt.h cgrt_count_neighbors*, cgrt_list_neighbors*): every triangle within a
@@ -613,125 +539,63 @@ int cgrt_debug_crossing_work(CgrtScene* s, const CgrtRay* rays, uint64_t n, uint
 // order include/cgrt.h states, all before any device work.
 namespace {
 static_assert(sizeof(CgrtNeighbor) == sizeof(CgrtNeighborDev), "CgrtNeighbor is what the kernels write");
-// result: counts for the count entries, out2 for the work entry, out for the list entries; list: the slot arguments are checked
-int neighbor_args(const CgrtScene* s, const void* points, uint64_t n, const void* radius2, float max_dist2, const void* result, bool list,
-                  const uint64_t* offsets, uint32_t k, uint64_t capacity, const void* counts, bool device) {
+// slots: 0 the points, 4 the radii, then the list's; how: 0 tree search, 1 brute force, 2 counted tree search (host form only: `work`;
+// L is k records per query of the lane's own, or with k == 0 the count search)
+int neighbor_query(CgrtScene* s, bool device, const float* points, uint64_t n, const float* radius2, float max_dist2, const SlotList& L, int how,
+                   uint64_t* work, void* stream) {
+    const void* const result = how == 2 ? static_cast<const void*>(work) : (L.list ? L.out : static_cast<const void*>(L.counts));
     if (!s) return fail(CGRT_E_ARG, "scene is NULL");
     if (n && (!points || !result)) return fail(CGRT_E_ARG, "NULL argument");
     if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many queries: n exceeds 0x7fffffff");
     if (!(max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
-    if (list) {
-        if ((offsets != nullptr) == (k > 0)) return fail(CGRT_E_ARG, "exactly one of offsets and k > 0 must be given");
-        if (capacity > kCrossingMaxCapacity) return fail(CGRT_E_ARG, "capacity exceeds 2^37 records");
-        if (k && n * (uint64_t)k > capacity) return fail(CGRT_E_ARG, "n * k records exceed capacity");
-        if (!device && offsets && n) {
-            if (offsets[0] != 0) return fail(CGRT_E_ARG, "offsets must start at 0");
-            for (uint64_t i = 0; i < n; i++)
-                if (offsets[i + 1] < offsets[i]) return fail(CGRT_E_ARG, "offsets must not decrease");
-            if (offsets[n] > capacity) return fail(CGRT_E_ARG, "offsets end beyond capacity");
-        }
-    }
-    if (device && ((uintptr_t)points % 4 || (uintptr_t)radius2 % 4 || (uintptr_t)result % 4 || (uintptr_t)counts % 4 || (uintptr_t)offsets % 8))
+    CGRT_TRY(L.rules(n, device));
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)radius2 % 4 || !L.aligned()))
         return fail(CGRT_E_ARG, "device pointers must be aligned to their elements");
-    return CGRT_OK;
-}
-// host pointers, on a call lane (slots: 0 the points, 1 the offsets, 2 the records, 3 the counts, 4 the radii); how: 0 tree search,
-// 1 brute force, 2 counted tree search (k == 0: the count search; k > 0: the k-nearest search into records of the lane's own)
-int neighbor_host(CgrtScene* s, const float* points, uint64_t n, const float* radius2, float max_dist2, const uint64_t* offsets, uint32_t k,
-                  CgrtNeighbor* out, uint64_t capacity, uint32_t* counts, bool list, int how, uint64_t* work) {
-    if (how == 2) {
-        list = k > 0;
-        capacity = n * (uint64_t)k;  // (n <= 0x7fffffff is checked before this is looked at)
-    }
-    int rc = neighbor_args(s, points, n, radius2, max_dist2, how == 2 ? static_cast<const void*>(work) : (list ? static_cast<const void*>(out) : counts),
-                           list, offsets, k, capacity, counts, false);
-    if (rc) return rc;
     NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    const uint64_t used = list ? (offsets ? offsets[n] : n * (uint64_t)k) : 0;  // the slots are records [0, used)
-    const bool want_counts = how == 2 ? !list : (!list || counts != nullptr);
-    if (how != 2 && used == 0 && !want_counts) return CGRT_OK;  // every slot is empty and no count is asked for: nothing to write
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    const size_t out_bytes = (size_t)used * sizeof(CgrtNeighbor), cnt_bytes = (size_t)n * 4u;
-    void *dp = nullptr, *doff = nullptr, *dout = nullptr, *dcnt = nullptr, *drad = nullptr;
-    HIP_TRY(c.input(0, points, n * 12, &dp));
-    if (offsets) HIP_TRY(c.input(1, offsets, (n + 1) * 8, &doff));
-    if (used) HIP_TRY(c.scratch(2, out_bytes, &dout));  // (a lane's buffer that was never needed is a null pointer)
-    if (want_counts) HIP_TRY(c.scratch(3, cnt_bytes, &dcnt));
-    if (radius2) HIP_TRY(c.input(4, radius2, n * 4, &drad));
+    if (n == 0 || L.nothing(n, device)) return CGRT_OK;
+    QueryCall c(s, device, stream);
+    void *dp = nullptr, *drad = nullptr;
     NeighborArgs A{};
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, points, n * 12, "d_points", &dp));
+    CGRT_TRY(c.in(4, radius2, radius2 ? n * 4 : 0, "d_radius2", &drad));
+    CGRT_TRY(L.transfer(c, n, &A));
     A.points = static_cast<const float*>(dp);
     A.radius2 = static_cast<const float*>(drad);
     A.max_dist2 = max_dist2;
     A.n = n;
-    A.offsets = static_cast<const unsigned long long*>(doff);
-    A.k = k;
-    A.out = static_cast<CgrtNeighborDev*>(dout);  // no record to write (count entries, or every slot empty): the count search
-    A.capacity = used;
-    A.counts = static_cast<uint32_t*>(dcnt);
     if (how == 2) {
-        HIP_TRY(c.zero_counters(2));
+        CGRT_TRY(c.zero_counters(2));
         HIP_TRY(launch_neighbors(s->dev, A, false, c.counters(), c.stream()));
-        HIP_TRY(c.read_counters(work, 2));
-        return CGRT_OK;
+        return c.read_counters(work, 2);
     }
     HIP_TRY(launch_neighbors(s->dev, A, how == 1, nullptr, c.stream()));
-    if (used) HIP_TRY(c.output(2, out, dout, out_bytes));
-    if (want_counts) HIP_TRY(c.output(3, counts, dcnt, cnt_bytes));
-    HIP_TRY(c.finish());
-    return CGRT_OK;
-}
-int neighbor_device(CgrtScene* s, const float* d_points, uint64_t n, const float* d_radius2, float max_dist2, const uint64_t* d_offsets, uint32_t k,
-                    CgrtNeighbor* d_out, uint64_t capacity, uint32_t* d_counts, bool list, void* stream) {
-    int rc = neighbor_args(s, d_points, n, d_radius2, max_dist2, list ? static_cast<const void*>(d_out) : d_counts, list, d_offsets, k, capacity,
-                           d_counts, true);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = check_device_span(s, d_points, n * 12, "d_points")) != CGRT_OK) return rc;
-    if (d_radius2 && (rc = check_device_span(s, d_radius2, n * 4, "d_radius2")) != CGRT_OK) return rc;
-    if (d_offsets && (rc = check_device_span(s, d_offsets, (n + 1) * 8, "d_offsets")) != CGRT_OK) return rc;
-    // with offsets any record below capacity may be written; with k the slots are the first n * k records
-    if (list && (rc = check_device_span(s, d_out, (d_offsets ? capacity : n * (uint64_t)k) * sizeof(CgrtNeighbor), "d_out")) != CGRT_OK) return rc;
-    if (d_counts && (rc = check_device_span(s, d_counts, n * 4, "d_counts")) != CGRT_OK) return rc;
-    NeighborArgs A{};
-    A.points = d_points;
-    A.radius2 = d_radius2;
-    A.max_dist2 = max_dist2;
-    A.n = n;
-    A.offsets = reinterpret_cast<const unsigned long long*>(d_offsets);
-    A.k = k;
-    A.out = list ? reinterpret_cast<CgrtNeighborDev*>(d_out) : nullptr;
-    A.capacity = capacity;
-    A.counts = d_counts;
-    HIP_TRY(launch_neighbors(s->dev, A, false, nullptr, static_cast<hipStream_t>(stream)));
-    return CGRT_OK;
+    return c.finish();
 }
 }  // namespace
 
 int cgrt_count_neighbors(CgrtScene* s, const float* points, uint64_t n, const float* radius2, float max_dist2, uint32_t* counts) {
-    return neighbor_host(s, points, n, radius2, max_dist2, nullptr, 0, nullptr, 0, counts, false, 0, nullptr);
+    return neighbor_query(s, false, points, n, radius2, max_dist2, {false, nullptr, 0, nullptr, 0, counts}, 0, nullptr, nullptr);
 }
 int cgrt_count_neighbors_device(CgrtScene* s, const float* d_points, uint64_t n, const float* d_radius2, float max_dist2, uint32_t* d_counts,
                                 void* stream) {
-    return neighbor_device(s, d_points, n, d_radius2, max_dist2, nullptr, 0, nullptr, 0, d_counts, false, stream);
+    return neighbor_query(s, true, d_points, n, d_radius2, max_dist2, {false, nullptr, 0, nullptr, 0, d_counts}, 0, nullptr, stream);
 }
 int cgrt_list_neighbors(CgrtScene* s, const float* points, uint64_t n, const float* radius2, float max_dist2, const uint64_t* offsets, uint32_t k,
                         CgrtNeighbor* out, uint64_t capacity, uint32_t* counts) {
-    return neighbor_host(s, points, n, radius2, max_dist2, offsets, k, out, capacity, counts, true, 0, nullptr);
+    return neighbor_query(s, false, points, n, radius2, max_dist2, {true, offsets, k, out, capacity, counts}, 0, nullptr, nullptr);
 }
 int cgrt_list_neighbors_device(CgrtScene* s, const float* d_points, uint64_t n, const float* d_radius2, float max_dist2, const uint64_t* d_offsets,
                                uint32_t k, CgrtNeighbor* d_out, uint64_t capacity, uint32_t* d_counts, void* stream) {
-    return neighbor_device(s, d_points, n, d_radius2, max_dist2, d_offsets, k, d_out, capacity, d_counts, true, stream);
+    return neighbor_query(s, true, d_points, n, d_radius2, max_dist2, {true, d_offsets, k, d_out, capacity, d_counts}, 0, nullptr, stream);
 }
 int cgrt_list_neighbors_brute(CgrtScene* s, const float* points, uint64_t n, const float* radius2, float max_dist2, const uint64_t* offsets,
                               uint32_t k, CgrtNeighbor* out, uint64_t capacity, uint32_t* counts) {
-    return neighbor_host(s, points, n, radius2, max_dist2, offsets, k, out, capacity, counts, true, 1, nullptr);
+    return neighbor_query(s, false, points, n, radius2, max_dist2, {true, offsets, k, out, capacity, counts}, 1, nullptr, nullptr);
 }
 int cgrt_debug_neighbor_work(CgrtScene* s, const float* points, uint64_t n, const float* radius2, float max_dist2, uint32_t k, uint64_t* out2) {
-    return neighbor_host(s, points, n, radius2, max_dist2, nullptr, k, nullptr, 0, nullptr, false, 2, out2);
+    // (n <= 0x7fffffff is checked before the capacity n k is looked at)
+    return neighbor_query(s, false, points, n, radius2, max_dist2, {k > 0, nullptr, k, nullptr, n * (uint64_t)k, nullptr}, 2, out2, nullptr);
 }
 
 // ---- signed distance and occupancy (include/cgrt.h cgrt_signed_distance*): the closest-point search and the parity
@@ -741,113 +605,67 @@ namespace {
 std::atomic<int> g_sdf_grid_linear{0};  // cgrt_debug_set_sdf_grid_mapping
 const float kSdfDefaultDirs[CGRT_SDF_DEFAULT_NDIRS][3] = CGRT_SDF_DEFAULT_DIRS;
 static_assert(sizeof(SdfArgs{}.dirs) == sizeof(CgrtSdfParams{}.dirs) && CGRT_SDF_MAX_DIRS == 7, "the kernel's directions are the parameters'");
-// the checks up to the host-only scene; fills A (result: sdf / inside, or out5 of the work entry in the place of both)
-int sdf_args(const CgrtScene* s, const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtSdfParams* params,
-             const void* sdf, const void* inside, bool device, SdfArgs* A) {
+// slots: 0 the points, 1 sdf, 2 inside; work: the counted launch (host form only: out5 in the place of both outputs)
+int sdf_query(CgrtScene* s, bool device, const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtSdfParams* params,
+              float* sdf, uint8_t* inside, int want_sdf, uint64_t* work, void* stream) {
+    SdfArgs A{};
     if (!s) return fail(CGRT_E_ARG, "scene is NULL");
-    if (is_grid ? !grid : (n && !points)) return fail(CGRT_E_ARG, is_grid ? "grid is NULL" : "NULL argument");
-    if (!sdf && !inside) return fail(CGRT_E_ARG, "NULL argument: neither sdf nor inside is asked for");
-    *A = SdfArgs{};
-    if (is_grid) {
-        n = 1;
-        for (int c = 0; c < 3; c++) {
-            if (grid->dims[c] < 1 || grid->dims[c] > (1u << 24)) return fail(CGRT_E_ARG, "grid dims must be in 1..2^24");
-            n *= grid->dims[c];  // (below 2^55 before the test, which follows every factor)
-            if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many grid points: nx * ny * nz exceeds 0x7fffffff");
-            if (!std::isfinite(grid->origin[c]) || !std::isfinite(grid->spacing[c])) return fail(CGRT_E_ARG, "grid origin and spacing must be finite");
-            A->origin[c] = grid->origin[c];
-            A->spacing[c] = grid->spacing[c];
-            A->dims[c] = grid->dims[c];
-        }
-    } else if (n > 0x7fffffffull) {
-        return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
-    }
-    A->max_dist2 = params ? params->max_dist2 : INFINITY;
-    if (!(A->max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
-    A->ndirs = params ? params->ndirs : 0u;
-    if (A->ndirs > CGRT_SDF_MAX_DIRS || (A->ndirs && A->ndirs % 2 == 0)) return fail(CGRT_E_ARG, "ndirs must be 0 or odd, 1..7");
-    const float(*dirs)[3] = A->ndirs ? params->dirs : kSdfDefaultDirs;
-    if (!A->ndirs) A->ndirs = CGRT_SDF_DEFAULT_NDIRS;
-    for (uint32_t j = 0; j < A->ndirs; j++) {
+    const int rc = point_source(points, grid, is_grid, n, sdf || inside || work, &A);
+    if (rc) return rc == kNoResult ? fail(CGRT_E_ARG, "NULL argument: neither sdf nor inside is asked for") : rc;
+    A.max_dist2 = params ? params->max_dist2 : INFINITY;
+    if (!(A.max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
+    A.ndirs = params ? params->ndirs : 0u;
+    if (A.ndirs > CGRT_SDF_MAX_DIRS || (A.ndirs && A.ndirs % 2 == 0)) return fail(CGRT_E_ARG, "ndirs must be 0 or odd, 1..7");
+    const float(*dirs)[3] = A.ndirs ? params->dirs : kSdfDefaultDirs;
+    if (!A.ndirs) A.ndirs = CGRT_SDF_DEFAULT_NDIRS;
+    for (uint32_t j = 0; j < A.ndirs; j++) {
         const float* d = dirs[j];
         if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) return fail(CGRT_E_ARG, "a direction has a non-finite component");
         if (d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f) return fail(CGRT_E_ARG, "a direction is all zero");
-        memcpy(A->dirs[j], d, 12);
+        memcpy(A.dirs[j], d, 12);
     }
     if (device && ((uintptr_t)points % 4 || (uintptr_t)sdf % 4)) return fail(CGRT_E_ARG, "d_points and d_sdf must be 4-byte aligned");
-    A->points = points;
-    A->n = (uint32_t)n;
-    return CGRT_OK;
-}
-// host pointers, on a call lane (slots: 0 the points, 1 sdf, 2 inside); work: the counted launch
-int sdf_host(CgrtScene* s, const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtSdfParams* params, float* sdf,
-             uint8_t* inside, bool counted, int want_sdf, uint64_t* work) {
-    SdfArgs A;
-    int rc = sdf_args(s, points, grid, is_grid, n, params, counted ? static_cast<const void*>(work) : sdf, counted ? nullptr : inside, false, &A);
-    if (rc) return rc;
     NEED_DEVICE(s);
     if (A.n == 0) return CGRT_OK;
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
+    QueryCall c(s, device, stream);
     void *dp = nullptr, *ds = nullptr, *di = nullptr;
-    if (!is_grid) HIP_TRY(c.input(0, points, (size_t)A.n * 12, &dp));
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, points, is_grid ? 0 : (uint64_t)A.n * 12, "d_points", &dp));
     A.points = static_cast<const float*>(dp);
     const bool brute = crossing_brute_scene(s);
-    if (counted) {
+    if (work) {
         A.want_sdf = want_sdf ? 1u : 0u;
-        HIP_TRY(c.zero_counters(5));
+        CGRT_TRY(c.zero_counters(5));
         HIP_TRY(launch_sdf(s->dev, A, SDF_LIST, brute, c.counters(), c.stream()));
-        HIP_TRY(c.read_counters(work, 5));
-        return CGRT_OK;
+        return c.read_counters(work, 5);
     }
-    if (sdf) HIP_TRY(c.scratch(1, (size_t)A.n * 4, &ds));
-    if (inside) HIP_TRY(c.scratch(2, A.n, &di));
+    CGRT_TRY(c.out(1, sdf, sdf ? (uint64_t)A.n * 4 : 0, "d_sdf", &ds));
+    CGRT_TRY(c.out(2, inside, inside ? A.n : 0, "d_inside", &di));
     A.want_sdf = sdf ? 1u : 0u;
     A.sdf = static_cast<float*>(ds);
     A.inside = static_cast<uint8_t*>(di);
     const SdfPoints how = !is_grid ? SDF_LIST : (g_sdf_grid_linear.load() ? SDF_GRID_LINEAR : SDF_GRID_BRICK);
     HIP_TRY(launch_sdf(s->dev, A, how, brute, nullptr, c.stream()));
-    if (sdf) HIP_TRY(c.output(1, sdf, ds, (size_t)A.n * 4));
-    if (inside) HIP_TRY(c.output(2, inside, di, A.n));
-    HIP_TRY(c.finish());
-    return CGRT_OK;
-}
-int sdf_device(CgrtScene* s, const float* d_points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtSdfParams* params, float* d_sdf,
-               uint8_t* d_inside, void* stream) {
-    SdfArgs A;
-    int rc = sdf_args(s, d_points, grid, is_grid, n, params, d_sdf, d_inside, true, &A);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (A.n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if (!is_grid && (rc = check_device_span(s, d_points, (uint64_t)A.n * 12, "d_points")) != CGRT_OK) return rc;
-    if (d_sdf && (rc = check_device_span(s, d_sdf, (uint64_t)A.n * 4, "d_sdf")) != CGRT_OK) return rc;
-    if (d_inside && (rc = check_device_span(s, d_inside, A.n, "d_inside")) != CGRT_OK) return rc;
-    A.want_sdf = d_sdf ? 1u : 0u;
-    A.sdf = d_sdf;
-    A.inside = d_inside;
-    const SdfPoints how = !is_grid ? SDF_LIST : (g_sdf_grid_linear.load() ? SDF_GRID_LINEAR : SDF_GRID_BRICK);
-    HIP_TRY(launch_sdf(s->dev, A, how, crossing_brute_scene(s), nullptr, static_cast<hipStream_t>(stream)));
-    return CGRT_OK;
+    return c.finish();
 }
 }  // namespace
 
 int cgrt_signed_distance(CgrtScene* s, const float* points, uint64_t n, const CgrtSdfParams* params, float* sdf, uint8_t* inside) {
-    return sdf_host(s, points, nullptr, false, n, params, sdf, inside, false, 0, nullptr);
+    return sdf_query(s, false, points, nullptr, false, n, params, sdf, inside, 0, nullptr, nullptr);
 }
 int cgrt_signed_distance_device(CgrtScene* s, const float* d_points, uint64_t n, const CgrtSdfParams* params, float* d_sdf, uint8_t* d_inside,
                                 void* stream) {
-    return sdf_device(s, d_points, nullptr, false, n, params, d_sdf, d_inside, stream);
+    return sdf_query(s, true, d_points, nullptr, false, n, params, d_sdf, d_inside, 0, nullptr, stream);
 }
 int cgrt_signed_distance_grid(CgrtScene* s, const CgrtGrid* grid, const CgrtSdfParams* params, float* sdf, uint8_t* inside) {
-    return sdf_host(s, nullptr, grid, true, 0, params, sdf, inside, false, 0, nullptr);
+    return sdf_query(s, false, nullptr, grid, true, 0, params, sdf, inside, 0, nullptr, nullptr);
 }
 int cgrt_signed_distance_grid_device(CgrtScene* s, const CgrtGrid* grid, const CgrtSdfParams* params, float* d_sdf, uint8_t* d_inside,
                                      void* stream) {
-    return sdf_device(s, nullptr, grid, true, 0, params, d_sdf, d_inside, stream);
+    return sdf_query(s, true, nullptr, grid, true, 0, params, d_sdf, d_inside, 0, nullptr, stream);
 }
 int cgrt_debug_sdf_work(CgrtScene* s, const float* points, uint64_t n, const CgrtSdfParams* params, int want_sdf, uint64_t* out5) {
-    return sdf_host(s, points, nullptr, false, n, params, nullptr, nullptr, true, want_sdf, out5);
+    return sdf_query(s, false, points, nullptr, false, n, params, nullptr, nullptr, want_sdf, out5, nullptr);
 }
 int cgrt_debug_set_sdf_grid_mapping(int linear) {
     if (linear != 0 && linear != 1) return fail(CGRT_E_ARG, "linear must be 0 or 1");
@@ -901,109 +719,65 @@ int winding_device_tree(CgrtScene* s, WindingArgs* A) {
     A->top_base = A->nlevels ? T.level_offsets[A->nlevels - 1] : 0u;
     return CGRT_OK;
 }
-// the checks up to the host-only scene; fills A (result: w / inside, or out3 of the work entry in the place of both); brute: beta is not read
-int winding_args(const CgrtScene* s, const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtWindingParams* params, bool brute,
-                 const void* w, const void* inside, bool device, WindingArgs* A) {
+// slots: 0 the points, 1 w, 2 inside; brute: every triangle, beta is not read; work: the counted launch (both host form only: out3 in
+// the place of both outputs)
+int winding_query(CgrtScene* s, bool device, const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtWindingParams* params,
+                  float* w, uint8_t* inside, bool brute, uint64_t* work, void* stream) {
+    WindingArgs A{};
     if (!s) return fail(CGRT_E_ARG, "scene is NULL");
-    if (is_grid ? !grid : (n && !points)) return fail(CGRT_E_ARG, is_grid ? "grid is NULL" : "NULL argument");
-    if (!w && !inside) return fail(CGRT_E_ARG, "NULL argument: neither w nor inside is asked for");
-    *A = WindingArgs{};
-    if (is_grid) {
-        n = 1;
-        for (int c = 0; c < 3; c++) {
-            if (grid->dims[c] < 1 || grid->dims[c] > (1u << 24)) return fail(CGRT_E_ARG, "grid dims must be in 1..2^24");
-            n *= grid->dims[c];  // (below 2^55 before the test, which follows every factor)
-            if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many grid points: nx * ny * nz exceeds 0x7fffffff");
-            if (!std::isfinite(grid->origin[c]) || !std::isfinite(grid->spacing[c])) return fail(CGRT_E_ARG, "grid origin and spacing must be finite");
-            A->origin[c] = grid->origin[c];
-            A->spacing[c] = grid->spacing[c];
-            A->dims[c] = grid->dims[c];
-        }
-    } else if (n > 0x7fffffffull) {
-        return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
-    }
+    const int rc = point_source(points, grid, is_grid, n, w || inside || work, &A);
+    if (rc) return rc == kNoResult ? fail(CGRT_E_ARG, "NULL argument: neither w nor inside is asked for") : rc;
     float beta = params ? params->beta : 0.0f;
     if (beta == 0.0f || brute) beta = CGRT_WINDING_DEFAULT_BETA;
     if (!(beta >= 1.0f)) return fail(CGRT_E_ARG, "beta must be a number >= 1 (0: the default; +inf: no cluster is far)");
-    A->beta2 = beta * beta;  // rounded once, here
-    A->threshold = params ? params->threshold : CGRT_WINDING_DEFAULT_THRESHOLD;
+    A.beta2 = beta * beta;  // rounded once, here
+    A.threshold = params ? params->threshold : CGRT_WINDING_DEFAULT_THRESHOLD;
     if (device && ((uintptr_t)points % 4 || (uintptr_t)w % 4)) return fail(CGRT_E_ARG, "d_points and d_w must be 4-byte aligned");
-    A->points = points;
-    A->n = (uint32_t)n;
-    return CGRT_OK;
-}
-// host pointers, on a call lane (slots: 0 the points, 1 w, 2 inside); work: the counted launch
-int winding_host(CgrtScene* s, const float* points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtWindingParams* params, float* w,
-                 uint8_t* inside, bool brute, uint64_t* work) {
-    WindingArgs A;
-    int rc = winding_args(s, points, grid, is_grid, n, params, brute, work ? static_cast<const void*>(work) : w, work ? nullptr : inside, false, &A);
-    if (rc) return rc;
     NEED_DEVICE(s);
     if (A.n == 0) return CGRT_OK;
-    LaneCall c(s);
-    if ((rc = c.begin()) != CGRT_OK) return rc;
-    A.recs = s->dev.tris + s->dev.tri_base;
-    A.ntris = s->dev.ntris;
-    if (!brute && (rc = winding_device_tree(s, &A)) != CGRT_OK) return rc;
+    QueryCall c(s, device, stream);
     void *dp = nullptr, *dw = nullptr, *di = nullptr;
-    if (!is_grid) HIP_TRY(c.input(0, points, (size_t)A.n * 12, &dp));
-    A.points = static_cast<const float*>(dp);
-    if (work) {
-        HIP_TRY(c.zero_counters(3));
-        HIP_TRY(launch_winding(A, WINDING_LIST, false, c.counters(), c.stream()));
-        HIP_TRY(c.read_counters(work, 3));
-        return CGRT_OK;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, points, is_grid ? 0 : (uint64_t)A.n * 12, "d_points", &dp));
+    if (!work) {
+        CGRT_TRY(c.out(1, w, w ? (uint64_t)A.n * 4 : 0, "d_w", &dw));
+        CGRT_TRY(c.out(2, inside, inside ? A.n : 0, "d_inside", &di));
     }
-    if (w) HIP_TRY(c.scratch(1, (size_t)A.n * 4, &dw));
-    if (inside) HIP_TRY(c.scratch(2, A.n, &di));
+    A.points = static_cast<const float*>(dp);
     A.w = static_cast<float*>(dw);
     A.inside = static_cast<uint8_t*>(di);
-    HIP_TRY(launch_winding(A, is_grid ? WINDING_GRID_BRICK : WINDING_LIST, brute, nullptr, c.stream()));
-    if (w) HIP_TRY(c.output(1, w, dw, (size_t)A.n * 4));
-    if (inside) HIP_TRY(c.output(2, inside, di, A.n));
-    HIP_TRY(c.finish());
-    return CGRT_OK;
-}
-int winding_device(CgrtScene* s, const float* d_points, const CgrtGrid* grid, bool is_grid, uint64_t n, const CgrtWindingParams* params, float* d_w,
-                   uint8_t* d_inside, void* stream) {
-    WindingArgs A;
-    int rc = winding_args(s, d_points, grid, is_grid, n, params, false, d_w, d_inside, true, &A);
-    if (rc) return rc;
-    NEED_DEVICE(s);
-    if (A.n == 0) return CGRT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if (!is_grid && (rc = check_device_span(s, d_points, (uint64_t)A.n * 12, "d_points")) != CGRT_OK) return rc;
-    if (d_w && (rc = check_device_span(s, d_w, (uint64_t)A.n * 4, "d_w")) != CGRT_OK) return rc;
-    if (d_inside && (rc = check_device_span(s, d_inside, A.n, "d_inside")) != CGRT_OK) return rc;
     A.recs = s->dev.tris + s->dev.tri_base;
     A.ntris = s->dev.ntris;
-    if ((rc = winding_device_tree(s, &A)) != CGRT_OK) return rc;
-    A.w = d_w;
-    A.inside = d_inside;
-    HIP_TRY(launch_winding(A, is_grid ? WINDING_GRID_BRICK : WINDING_LIST, false, nullptr, static_cast<hipStream_t>(stream)));
-    return CGRT_OK;
+    if (!brute) CGRT_TRY(winding_device_tree(s, &A));
+    if (work) {
+        CGRT_TRY(c.zero_counters(3));
+        HIP_TRY(launch_winding(A, WINDING_LIST, false, c.counters(), c.stream()));
+        return c.read_counters(work, 3);
+    }
+    HIP_TRY(launch_winding(A, is_grid ? WINDING_GRID_BRICK : WINDING_LIST, brute, nullptr, c.stream()));
+    return c.finish();
 }
 }  // namespace
 
 int cgrt_winding_numbers(CgrtScene* s, const float* points, uint64_t n, const CgrtWindingParams* params, float* w, uint8_t* inside) {
-    return winding_host(s, points, nullptr, false, n, params, w, inside, false, nullptr);
+    return winding_query(s, false, points, nullptr, false, n, params, w, inside, false, nullptr, nullptr);
 }
 int cgrt_winding_numbers_device(CgrtScene* s, const float* d_points, uint64_t n, const CgrtWindingParams* params, float* d_w, uint8_t* d_inside,
                                 void* stream) {
-    return winding_device(s, d_points, nullptr, false, n, params, d_w, d_inside, stream);
+    return winding_query(s, true, d_points, nullptr, false, n, params, d_w, d_inside, false, nullptr, stream);
 }
 int cgrt_winding_numbers_grid(CgrtScene* s, const CgrtGrid* grid, const CgrtWindingParams* params, float* w, uint8_t* inside) {
-    return winding_host(s, nullptr, grid, true, 0, params, w, inside, false, nullptr);
+    return winding_query(s, false, nullptr, grid, true, 0, params, w, inside, false, nullptr, nullptr);
 }
 int cgrt_winding_numbers_grid_device(CgrtScene* s, const CgrtGrid* grid, const CgrtWindingParams* params, float* d_w, uint8_t* d_inside,
                                      void* stream) {
-    return winding_device(s, nullptr, grid, true, 0, params, d_w, d_inside, stream);
+    return winding_query(s, true, nullptr, grid, true, 0, params, d_w, d_inside, false, nullptr, stream);
 }
 int cgrt_winding_numbers_brute(CgrtScene* s, const float* points, uint64_t n, const CgrtWindingParams* params, float* w, uint8_t* inside) {
-    return winding_host(s, points, nullptr, false, n, params, w, inside, true, nullptr);
+    return winding_query(s, false, points, nullptr, false, n, params, w, inside, true, nullptr, nullptr);
 }
 int cgrt_debug_winding_work(CgrtScene* s, const float* points, uint64_t n, const CgrtWindingParams* params, uint64_t* out3) {
-    return winding_host(s, points, nullptr, false, n, params, nullptr, nullptr, false, out3);
+    return winding_query(s, false, points, nullptr, false, n, params, nullptr, nullptr, false, out3, nullptr);
 }
 int cgrt_debug_get_winding_tree(CgrtScene* s, float* clusters, uint32_t* level_offsets, uint32_t* nlevels, uint32_t* record_prims) {
     if (!s || !nlevels) return fail(CGRT_E_ARG, "NULL argument");

@@ -1,5 +1,6 @@
 """GPU tests of the host-pointer entries' one call helper (csrc/capi_lanes.cpp LaneCall: begin, input / scratch per slot, the launch,
-output per result, finish) through the entries written with it.
+output per result, finish; the queries reach it through QueryCall, one body for their host and device forms) through the entries written
+with it.
 
 A lane stages transfers of up to 1 MiB in pinned buffers -- a staged result reaches the caller's memory only in finish, behind the
 stream -- and sends larger ones through the bounce buffers, in place when output returns.  Every entry below runs at N = 40 000 items,
@@ -45,6 +46,22 @@ def world(pkg, orc):
              attr=attr, d_rays=d_rays, d_hits=d_hits, d_points=torch.from_numpy(points).cuda(), d_attr=torch.from_numpy(attr).cuda())
     yield w
     sc.close()
+
+
+@pytest.fixture(scope="module")
+def fields(world):
+    """What the neighbour, signed-distance and winding tests add to the world: per-query squared radii in [0, (0.1 extent)^2] with a few NaN
+    and negative ones (slot 4 of the lane), and a 64 x 64 x 65 grid over the scene's box padded by 10 %, whose float plane (1 064 960 B)
+    goes direct while its byte plane stays staged.  Made once, never written."""
+    pos = np.asarray(world["sd"].pos_nrm, np.float32).reshape(-1, 6)[:, :3]
+    lo, hi = pos.min(0), pos.max(0)
+    extent = float((hi - lo).max())
+    radius2 = np.random.default_rng(42).uniform(0, (0.1 * extent) ** 2, N).astype(np.float32)
+    radius2[::1000], radius2[500::1000] = np.nan, -1.0
+    dims = (64, 64, 65)
+    grid = (lo - 0.1 * (hi - lo), 1.2 * (hi - lo) / (np.array(dims, np.float32) - 1), dims)
+    assert dims[0] * dims[1] * dims[2] * 4 > STAGE > dims[0] * dims[1] * dims[2]
+    return dict(radius2=radius2, d_radius2=torch.from_numpy(radius2).cuda(), max_dist2=(0.05 * extent) ** 2, grid=grid)
 
 
 def _np(t):
@@ -186,11 +203,117 @@ def test_intersect_batch_leaves_the_normals_of_misses(world):
     assert hits.tobytes() == np.concatenate([h for h, _ in parts]).tobytes() and normals.tobytes() == np.concatenate([n for _, n in parts]).tobytes()
 
 
-def test_counted_entries_add_up_over_slices(world):
-    """cgrt_debug_closest_work and cgrt_debug_crossing_work (zero the lane's counters, a counted launch, two words back): the work of
-    5 000 items is the work of its slices of 1 000."""
-    sc, p, rays = world["sc"], world["points"][:5_000], world["rays"][17_500:22_500]
-    for whole, parts in ((sc.debug_closest_work(p), _slices(lambda s: sc.debug_closest_work(p[s]), 5_000, 1_000)),
-                         (sc.debug_crossing_work(rays), _slices(lambda s: sc.debug_crossing_work(rays[s]), 5_000, 1_000))):
-        assert whole[0] > 0 and whole[1] > 0
-        assert whole == (sum(a for a, _ in parts), sum(b for _, b in parts))
+def test_counted_entries_add_up_over_slices(world, fields):
+    """cgrt_debug_closest_work, cgrt_debug_crossing_work, cgrt_debug_neighbor_work (the count search and the k-nearest search into records
+    of the lane's own), cgrt_debug_sdf_work and cgrt_debug_winding_work (zero the lane's counters, a counted launch, the words back): the
+    work of 5 000 items is the work of its slices of 1 000."""
+    sc, p, rays, rad = world["sc"], world["points"][:5_000], world["rays"][17_500:22_500], fields["radius2"][:5_000]
+
+    def parts(f):
+        return _slices(f, 5_000, 1_000)
+
+    for whole, part in ((sc.debug_closest_work(p), parts(lambda s: sc.debug_closest_work(p[s]))),
+                        (sc.debug_crossing_work(rays), parts(lambda s: sc.debug_crossing_work(rays[s]))),
+                        (sc.debug_neighbor_work(p, radius2=rad), parts(lambda s: sc.debug_neighbor_work(p[s], radius2=rad[s]))),
+                        (sc.debug_neighbor_work(p, radius2=rad, k=8), parts(lambda s: sc.debug_neighbor_work(p[s], radius2=rad[s], k=8))),
+                        (sc.debug_sdf_work(p), parts(lambda s: sc.debug_sdf_work(p[s]))),
+                        (sc.debug_winding_work(p), parts(lambda s: sc.debug_winding_work(p[s])))):
+        assert len(whole) in (2, 3, 5) and all(x > 0 for x in whole)
+        assert whole == tuple(sum(col) for col in zip(*part))
+
+
+def test_nearest_triangles_with_counts(world, fields):
+    """k = 4 and the counts asked for, per-query radii: the records (1.28 MB) direct, the counts (160 KB) staged, the radii up through the
+    lane's fifth slot."""
+    sc, p, rad = world["sc"], world["points"], fields["radius2"]
+    rec, cnt = sc.nearest_triangles(p, 4, radius2=rad, want_counts=True)
+    assert rec.nbytes > STAGE > cnt.nbytes and (cnt == 0).any() and (cnt > 4).any() and ((cnt > 0) & (cnt < 4)).any()
+    assert (cnt[::1000] == 0).all() and (cnt[500::1000] == 0).all(), "a NaN or negative radius has no neighbours"
+    d_rec, d_cnt = sc.nearest_triangles_tensor(world["d_points"], 4, radius2=fields["d_radius2"], want_counts=True)
+    assert rec.tobytes() == _np(d_rec).tobytes() and cnt.tobytes() == _np(d_cnt).tobytes()
+    parts = _slices(lambda s: sc.nearest_triangles(p[s], 4, radius2=rad[s], want_counts=True))
+    assert rec.tobytes() == np.concatenate([r for r, _ in parts]).tobytes() and cnt.tobytes() == np.concatenate([c for _, c in parts]).tobytes()
+
+
+def test_count_neighbors(world, fields):
+    sc, p, rad = world["sc"], world["points"], fields["radius2"]
+    whole = sc.count_neighbors(p, radius2=rad)
+    assert whole.any() and (whole == 0).any() and len(np.unique(whole)) > 2
+    _check(whole, _np(sc.count_neighbors_tensor(world["d_points"], radius2=fields["d_radius2"])),
+           _slices(lambda s: sc.count_neighbors(p[s], radius2=rad[s])), "count_neighbors")
+
+
+def test_list_neighbors_in_full(world, fields):
+    """The full lists under one radius: count, prefix sums, list; the offsets (320 KB) go up through slot 1, the records come down direct."""
+    sc, p, r2 = world["sc"], world["points"], fields["max_dist2"]
+    off, rec = sc.list_neighbors(p, max_dist2=r2)
+    cnt = np.diff(off)
+    assert rec.nbytes > STAGE > (N + 1) * 8 and len(rec) == off[-1] and (cnt == 0).any() and len(np.unique(cnt)) > 2
+    d_off, d_rec = sc.list_neighbors_tensor(world["d_points"], max_dist2=r2)
+    assert off.tobytes() == _np(d_off).tobytes() and rec.tobytes() == _np(d_rec).tobytes()
+    parts = _slices(lambda s: sc.list_neighbors(p[s], max_dist2=r2))
+    assert rec.tobytes() == np.concatenate([r for _, r in parts]).tobytes() and (cnt == np.concatenate([np.diff(o) for o, _ in parts])).all()
+
+
+def test_list_crossings_in_full(world):
+    """The full lists of the camera rays (the k form is above): the offsets through slot 1, as many records as the rays cross."""
+    sc, rays = world["sc"], world["rays"]
+    off, rec = sc.list_crossings(rays)
+    cnt = np.diff(off)
+    assert (N + 1) * 8 <= STAGE and len(rec) == off[-1] > 0 and (cnt == 0).any() and len(np.unique(cnt)) > 2
+    d_off, d_rec = sc.list_crossings_tensor(world["d_rays"])
+    assert off.tobytes() == _np(d_off).tobytes() and rec.tobytes() == _np(d_rec).tobytes()
+    parts = _slices(lambda s: sc.list_crossings(rays[s]))
+    assert rec.tobytes() == np.concatenate([r for _, r in parts]).tobytes() and (cnt == np.concatenate([np.diff(o) for o, _ in parts])).all()
+
+
+def test_sdf(world):
+    sc, p = world["sc"], world["points"]  # both outputs staged (160 KB and 40 KB)
+    s, ins = sc.sdf(p)
+    assert s.nbytes <= STAGE and ins.any() and not ins.all()
+    d_s, d_ins = sc.sdf_tensor(world["d_points"])
+    assert s.tobytes() == _np(d_s).tobytes() and ins.tobytes() == _np(d_ins).tobytes()
+    parts = _slices(lambda q: sc.sdf(p[q]))
+    assert s.tobytes() == np.concatenate([a for a, _ in parts]).tobytes() and ins.tobytes() == np.concatenate([b for _, b in parts]).tobytes()
+    # inside alone: the lane's slot 1 is not used by the call
+    _check(sc.sdf(p, want=("inside",)), ins, _slices(lambda q: sc.sdf(p[q], want=("inside",))), "sdf, inside alone")
+
+
+def test_sdf_grid(world, fields):
+    sc, (origin, spacing, dims) = world["sc"], fields["grid"]  # (a slab of the grid is another grid: no slices)
+    s, ins = sc.sdf_grid(origin, spacing, dims)
+    assert s.nbytes == 1_064_960 > STAGE > ins.nbytes and s.shape == ins.shape == dims[::-1] and ins.any() and not ins.all()
+    d_s, d_ins = sc.sdf_grid_tensor(origin, spacing, dims)
+    assert s.tobytes() == _np(d_s).tobytes() and ins.tobytes() == _np(d_ins).tobytes()
+
+
+def test_winding_numbers(world, fields):
+    sc, p = world["sc"], world["points"]  # the list staged; the grid's float plane direct, its byte plane staged
+    w, ins = sc.winding_numbers(p)
+    assert ins.any() and not ins.all()
+    d_w, d_ins = sc.winding_numbers_tensor(world["d_points"])
+    assert w.tobytes() == _np(d_w).tobytes() and ins.tobytes() == _np(d_ins).tobytes()
+    parts = _slices(lambda q: sc.winding_numbers(p[q]))
+    assert w.tobytes() == np.concatenate([a for a, _ in parts]).tobytes() and ins.tobytes() == np.concatenate([b for _, b in parts]).tobytes()
+    origin, spacing, dims = fields["grid"]
+    w, ins = sc.winding_grid(origin, spacing, dims)
+    assert w.nbytes > STAGE > ins.nbytes and w.shape == ins.shape == dims[::-1] and ins.any() and not ins.all()
+    d_w, d_ins = sc.winding_grid_tensor(origin, spacing, dims)
+    assert w.tobytes() == _np(d_w).tobytes() and ins.tobytes() == _np(d_ins).tobytes()
+
+
+@pytest.mark.parametrize("want_counts", [False, True])
+def test_first_call_of_a_fresh_scene_lists_into_empty_slots(world, fields, want_counts):
+    """A scene whose first host call is list_neighbors with every slot empty: without counts there is nothing to write and the call
+    returns without a lane; with counts the lane is new and its records buffer is never sized."""
+    pkg, p, r2 = world["pkg"], world["points"][:SLICE], fields["max_dist2"]
+    sc = pkg.Scene(world["sd"], device=0)
+    try:
+        rec, cnt = sc.list_neighbors(p, max_dist2=r2, offsets=np.zeros(len(p) + 1, np.uint64), want_counts=want_counts)
+        assert rec.shape == (0,) and rec.dtype == pkg.NEIGHBOR_DTYPE
+        if want_counts:
+            assert cnt.any() and (cnt == 0).any() and cnt.tobytes() == world["sc"].count_neighbors(p, max_dist2=r2).tobytes()
+        else:
+            assert cnt is None
+    finally:
+        sc.close()
