@@ -39,6 +39,9 @@ assert CROSSING_DTYPE.itemsize == 8
 # include/cgrt.h CgrtNeighbor: one triangle within a query point's radius (8 bytes); an unused entry of a slot is {+inf, NO_PRIM}
 NEIGHBOR_DTYPE = np.dtype([("dist2", np.float32), ("prim_id", np.uint32)])
 assert NEIGHBOR_DTYPE.itemsize == 8
+# include/cgrt.h CgrtSurfaceSample: one surface sample (32 bytes); point, prim_id and bary at CLOSEST_DTYPE's offsets
+SURFACE_SAMPLE_DTYPE = np.dtype([("point", np.float32, 3), ("mesh_id", np.uint32), ("prim_id", np.uint32), ("bary", np.float32, 3)])
+assert SURFACE_SAMPLE_DTYPE.itemsize == 32
 _SLOT_RECORDS = {"crossings": CROSSING_DTYPE, "neighbors": NEIGHBOR_DTYPE}  # the slot-list entries (Scene._slots_*) by the name in their symbols
 # Scene.inside_tensor's default directions: three fixed generic ones (no component zero, none along an axis, a face diagonal or a space
 # diagonal, pairwise far from parallel), so that a ray through an edge or a vertex of an axis-aligned or diagonal-symmetric mesh is the
@@ -65,6 +68,21 @@ def _winding_params(beta: float = 2.0, threshold: float = 0.5) -> WindingParams:
     """CgrtWindingParams; the library checks beta (>= 1, +inf allowed, 0 = its default)."""
     p = WindingParams()
     p.beta, p.threshold = float(beta), float(threshold)
+    return p
+
+
+class SampleParams(C.Structure):
+    """include/cgrt.h CgrtSampleParams."""
+    _fields_ = [("seed", C.c_uint64), ("first", C.c_uint64), ("strata", C.c_uint64)]
+
+
+def _sample_params(seed: int = 0, first: int = 0, strata: int = 0) -> SampleParams:
+    """CgrtSampleParams; 64-bit unsigned values (ValueError otherwise), the library checks first and strata against n."""
+    for name, v in (("seed", seed), ("first", first), ("strata", strata)):
+        if not 0 <= int(v) < 1 << 64:
+            raise ValueError(f"{name} must be in 0 .. 2^64 - 1")
+    p = SampleParams()
+    p.seed, p.first, p.strata = int(seed), int(first), int(strata)
     return p
 
 
@@ -346,7 +364,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -496,6 +514,10 @@ def lib() -> C.CDLL:
     L.cgrt_winding_numbers_brute.argtypes = [vp, vp, u64, C.POINTER(WindingParams), vp, vp]
     L.cgrt_debug_winding_work.argtypes = [vp, vp, u64, C.POINTER(WindingParams), vp]
     L.cgrt_debug_get_winding_tree.argtypes = [vp, vp, vp, C.POINTER(u32), vp]
+    L.cgrt_sample_surface.argtypes = [vp, u64, C.POINTER(SampleParams), vp, vp, u32, vp]
+    L.cgrt_sample_surface_device.argtypes = [vp, u64, C.POINTER(SampleParams), vp, vp, u32, vp, vp]
+    L.cgrt_triangle_areas.argtypes = [vp, vp, C.POINTER(C.c_double)]
+    L.cgrt_debug_get_sample_table.argtypes = [vp, vp, C.POINTER(u32)]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
     L.cgrt_count_batch.argtypes = [vp, vp, u64, C.POINTER(Counters)]
     L.cgrt_debug_gather_calibration.argtypes = [i32, u64, i32]
@@ -2574,6 +2596,86 @@ class Scene:
         with torch.cuda.stream(stream):
             dist = torch.sqrt(d2)
             return torch.where(inside, -dist, dist)
+
+    # ---- surface sampling (include/cgrt.h cgrt_sample_surface*) ----
+    def triangle_areas(self):
+        """cgrt_triangle_areas (works host-only): ((ntris,) float32 areas in prim_id order -- the reference's area function, 0 where it is
+        NaN, infinite or not > 0 --, their float64 sum added in that order)."""
+        areas = np.zeros(int(np.asarray(self.sd.tri).size // 3), np.float32)
+        total = C.c_double(0.0)
+        _check(lib().cgrt_triangle_areas(self._h, _ptr(areas) if len(areas) else None, C.byref(total)))
+        return areas, float(total.value)
+
+    def debug_sample_table(self):
+        """cgrt_debug_get_sample_table (works host-only): {'thresholds': (ntris,) uint32, 'last': the largest prim_id with an area, or
+        NO_PRIM when the scene is empty for sampling}."""
+        thr = np.zeros(int(np.asarray(self.sd.tri).size // 3), np.uint32)
+        last = C.c_uint32(0)
+        _check(lib().cgrt_debug_get_sample_table(self._h, _ptr(thr) if len(thr) else None, C.byref(last)))
+        return {"thresholds": thr, "last": int(last.value)}
+
+    def sample_surface(self, n: int, seed: int = 0, first: int = 0, strata: int = 0, attr=None):
+        """cgrt_sample_surface: samples first .. first + n - 1 of the stream `seed` -- area-weighted points on the scene's triangles, each
+        a function of (scene, seed, index, strata) alone; strata = N > 0 puts sample j into stratum j of N equal strata of the area.
+        Returns a SURFACE_SAMPLE_DTYPE array {point, mesh_id, prim_id, bary}; with attr ((nverts, C) float32) also the (n, C) rows
+        (bary0 * attr[i0] + bary1 * attr[i1]) + bary2 * attr[i2].  A scene without a triangle of positive area gives
+        {0, 0xffffffff, NO_PRIM, 0} records and zero rows."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        prm = _sample_params(seed, first, strata)
+        out = np.zeros(n, SURFACE_SAMPLE_DTYPE)
+        if attr is None:
+            _check(lib().cgrt_sample_surface(self._h, n, C.byref(prm), _ptr(out) if n else None, None, 0, None))
+            return out
+        a = self._attr_array(attr)
+        rows = np.zeros((n, a.shape[1]), np.float32)
+        _check(lib().cgrt_sample_surface(self._h, n, C.byref(prm), _ptr(out) if n else None, _ptr(a), a.shape[1], _ptr(rows)))
+        return out, rows
+
+    def sample_surface_device(self, n: int, d_out_ptr: int, seed: int = 0, first: int = 0, strata: int = 0, d_attr_ptr: int = 0,
+                              channels: int = 0, d_out_attr_ptr: int = 0, stream: int = 0) -> None:
+        """cgrt_sample_surface_device: n SURFACE_SAMPLE_DTYPE records (32 bytes each) to d_out_ptr and, with a table (d_attr_ptr:
+        (nverts, channels) float32), n x channels floats to d_out_attr_ptr; enqueued on the hipStream_t `stream`.  Raw integers."""
+        prm = _sample_params(seed, first, strata)
+        _check(lib().cgrt_sample_surface_device(self._h, int(n), C.byref(prm), _vp(d_out_ptr), _vp(d_attr_ptr), int(channels),
+                                                _vp(d_out_attr_ptr), _vp(stream)))
+
+    def sample_surface_tensor(self, n: int, seed: int = 0, first: int = 0, strata: int = 0, attr=None, out=None, out_attr=None, stream=None):
+        """sample_surface on torch tensors: an (n, 8) float32 tensor of SURFACE_SAMPLE_DTYPE records (`out`, or a new one) on
+        cuda:<device>, enqueued on `stream` (default: torch.cuda.current_stream()).  Returns a dict of views of it: 'point' (n, 3),
+        'mesh_id' and 'prim_id' (n,) int32 (-1 = NO_PRIM), 'bary' (n, 3), 'out' itself, and with attr ((nverts, C) float32 on the device)
+        'attr': the (n, C) rows (`out_attr`, or a new tensor)."""
+        import torch
+
+        n = int(n)
+        if self.device < 0:
+            raise ValueError("the scene has no device (created host-only)")
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        if out is not None:
+            self._device_tensor(out, "out", (torch.float32,), (n, 8))
+        if attr is None:
+            if out_attr is not None:
+                raise ValueError("out_attr needs attr")
+            o = self._tensor_call(out, (n, 8), torch.float32, stream,
+                                  lambda t, s: self.sample_surface_device(n, t.data_ptr(), seed=seed, first=first, strata=strata, stream=s))
+            rows = None
+        else:
+            attr = self._attr_tensor(attr)
+            ch = attr.shape[1]
+            if out_attr is not None:
+                self._device_tensor(out_attr, "out_attr", (torch.float32,), (n, ch))
+            _, stream = self._torch_stream(stream)
+            rows = self._tensor_call(out_attr, (n, ch), torch.float32, stream, lambda t, s: None)  # (out_attr, or new on the stream)
+            o = self._tensor_call(out, (n, 8), torch.float32, stream,
+                                  lambda t, s: self.sample_surface_device(n, t.data_ptr(), seed=seed, first=first, strata=strata,
+                                                                          d_attr_ptr=attr.data_ptr(), channels=ch,
+                                                                          d_out_attr_ptr=rows.data_ptr(), stream=s))
+        res = {"point": o[:, 0:3], "mesh_id": o.view(torch.int32)[:, 3], "prim_id": o.view(torch.int32)[:, 4], "bary": o[:, 5:8], "out": o}
+        if rows is not None:
+            res["attr"] = rows
+        return res
 
     def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream):
         import torch

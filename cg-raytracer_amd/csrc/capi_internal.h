@@ -35,6 +35,8 @@
 #include "neighbor_kernels.h"
 #include "sdf_kernels.h"
 #include "surface_kernels.h"
+#include "surface_sample_builder.h"
+#include "surface_sample_kernels.h"
 #include "trace_kernels.h"
 #include "winding_kernels.h"
 
@@ -315,11 +317,18 @@ struct CgrtScene {
     WindingTree winding;
     std::atomic<bool> winding_built{false};
     std::atomic<void*> d_winding{nullptr};
+    // Surface sampling (cgrt_sample_surface*): the areas and thresholds in prim_id order (surface_sample_builder.h),
+    // made on the host by the scene's first sampling call under surface_mutex (a host-only scene included: cgrt_triangle_areas and
+    // cgrt_debug_get_sample_table read it), and the thresholds' device copy, uploaded once by the first call that launches.
+    SampleTable sampling;
+    std::atomic<bool> sampling_built{false};
+    std::atomic<void*> d_sampling{nullptr};
     ~CgrtScene() {
         if (device < 0) return;
         (void)hipSetDevice(device);
         if (void* p = d_surface_lookup.load()) (void)hipFree(p);
         if (void* p = d_winding.load()) (void)hipFree(p);
+        if (void* p = d_sampling.load()) (void)hipFree(p);
         for (EnqSlot& e : eslot) {  // (frames in flight complete before anything they use is released)
             if (e.pending) (void)hipEventSynchronize(e.done);
             for (hipEvent_t ev : {e.done, e.t0, e.t1})

@@ -1,5 +1,5 @@
 // capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
-// closest points, crossings, neighbours, signed distance, winding numbers.  None of them touches the scene's frame state (workspace, prediction, hints).
+// closest points, crossings, neighbours, signed distance, winding numbers, surface samples.  None of them touches the scene's frame state (workspace, prediction, hints).
 // Every family is ONE body for its host-pointer and its device-pointer entries, written with a QueryCall (capi_internal.h): the argument
 // checks in the order include/cgrt.h states (`device`: the pointers' alignment too), the host-only scene, the empty call, then begin,
 // in / out per array, the launch on the call's stream, finish.  The exported entries are one-line forwarders.
@@ -794,6 +794,123 @@ int cgrt_debug_get_winding_tree(CgrtScene* s, float* clusters, uint32_t* level_o
     if (clusters && !T.clusters.empty()) memcpy(clusters, T.clusters.data(), T.clusters.size() * sizeof(WindingCluster));
     if (record_prims)
         for (size_t k = 0; k < s->bvh.tris.size(); k++) record_prims[k] = s->bvh.tris[k].prim_id;
+    return CGRT_OK;
+}
+
+// ---- surface sampling (include/cgrt.h cgrt_sample_surface*): area-weighted points on the triangles, sample j a
+// function of (scene, seed, j, strata) alone.  No frame state is read or written; the checks come in the order include/cgrt.h states, all
+// before any device work.
+namespace {
+static_assert(sizeof(CgrtSurfaceSample) == sizeof(CgrtSurfaceSampleDev), "CgrtSurfaceSample is what the kernel writes");
+// the scene's areas and thresholds on the host, built by the first caller (later calls: one atomic load); works on a host-only scene
+int sample_host_table(CgrtScene* s) {
+    if (s->sampling_built.load(std::memory_order_acquire)) return CGRT_OK;
+    std::lock_guard<std::mutex> lk(s->surface_mutex);
+    if (s->sampling_built.load(std::memory_order_acquire)) return CGRT_OK;
+    if (s->bvh.tris.size() != s->ntris) return fail(CGRT_E_ARG, "the scene's records do not cover its triangles");
+    try {
+        if (!build_sample_table(s->bvh.tris.data(), s->ntris, s->sampling)) return fail(CGRT_E_ARG, "a triangle record carries a primitive id out of range");
+    } catch (const std::bad_alloc&) {
+        return fail(CGRT_E_ALLOC, "host allocation failed");
+    }
+    s->sampling_built.store(true, std::memory_order_release);
+    return CGRT_OK;
+}
+// ... and the thresholds on the device, uploaded once (complete when this returns: every later launch on any stream sees them); fills
+// A's table fields.  A scene that is empty for sampling uploads nothing.
+int sample_device_table(CgrtScene* s, SampleArgs* A) {
+    CGRT_TRY(sample_host_table(s));
+    const SampleTable& T = s->sampling;
+    A->last = T.last;
+    A->steps = 0;
+    A->thresholds = nullptr;
+    if (T.last == SAMPLE_NO_PRIM) return CGRT_OK;
+    while (A->steps < 32u && (1ull << A->steps) < (uint64_t)T.last + 1ull) A->steps++;  // ceil(log2(last + 1))
+    void* p = s->d_sampling.load(std::memory_order_acquire);
+    if (!p) {
+        std::lock_guard<std::mutex> lk(s->surface_mutex);
+        p = s->d_sampling.load(std::memory_order_acquire);
+        if (!p) {
+            const size_t bytes = T.thresholds.size() * sizeof(uint32_t);
+            void* d = nullptr;
+            HIP_TRY(hipMalloc(&d, bytes));
+            const hipError_t e = staged_h2d(d, T.thresholds.data(), bytes);
+            if (e != hipSuccess) {
+                (void)hipFree(d);
+                return hip_fail(e, "uploading the sampling thresholds");
+            }
+            s->device_bytes += bytes;
+            s->d_sampling.store(d, std::memory_order_release);
+            p = d;
+        }
+    }
+    A->thresholds = static_cast<const uint32_t*>(p);
+    return CGRT_OK;
+}
+// slots: 0 out, 1 attr, 2 out_attr
+int sample_query(CgrtScene* s, bool device, uint64_t n, const CgrtSampleParams* params, CgrtSurfaceSample* out, const float* attr,
+                 uint32_t channels, float* out_attr, void* stream) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    if (n && !out) return fail(CGRT_E_ARG, "NULL argument");
+    if ((attr != nullptr) != (out_attr != nullptr)) return fail(CGRT_E_ARG, "attr and out_attr must be given together");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many samples: n exceeds 0x7fffffff");
+    if (attr) CGRT_TRY(surface_channels(channels, n));
+    const CgrtSampleParams P = params ? *params : CgrtSampleParams{0, 0, 0};
+    if (P.strata > 0xffffffffull) return fail(CGRT_E_ARG, "strata exceeds 0xffffffff");
+    if (P.strata && (P.first > P.strata || n > P.strata - P.first)) return fail(CGRT_E_ARG, "first + n exceeds strata");
+    if (P.first + n < P.first) return fail(CGRT_E_ARG, "first + n overflows 64 bits");
+    if (device && ((uintptr_t)out % 4 || (uintptr_t)attr % 4 || (uintptr_t)out_attr % 4))
+        return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    QueryCall c(s, device, stream);
+    void *dout = nullptr, *dattr = nullptr, *drows = nullptr;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.out(0, out, n * sizeof(CgrtSurfaceSample), "d_out", &dout));
+    CGRT_TRY(c.in(1, attr, attr ? (uint64_t)s->nverts * channels * 4ull : 0, "d_attr", &dattr));
+    CGRT_TRY(c.out(2, out_attr, attr ? n * channels * 4ull : 0, "d_out_attr", &drows));
+    SampleArgs A{};
+    CGRT_TRY(sample_device_table(s, &A));
+    const SurfaceLookup* lookup = nullptr;
+    if (A.last != SAMPLE_NO_PRIM) CGRT_TRY(surface_lookup(s, &lookup));
+    A.tris = s->dev.tris;
+    A.lookup = lookup;
+    A.n = (uint32_t)n;
+    A.seed = P.seed;
+    A.first = P.first;
+    A.strata = P.strata;
+    A.out = static_cast<CgrtSurfaceSampleDev*>(dout);
+    A.attr = attr ? static_cast<const float*>(dattr) : nullptr;
+    A.channels = attr ? channels : 0;
+    A.out_attr = attr ? static_cast<float*>(drows) : nullptr;
+    A.vec4 = attr && channels % 4 == 0 && (uintptr_t)dattr % 16 == 0 && (uintptr_t)drows % 16 == 0;
+    HIP_TRY(launch_sample_surface(A, c.stream()));
+    return c.finish();
+}
+}  // namespace
+
+int cgrt_sample_surface(CgrtScene* s, uint64_t n, const CgrtSampleParams* params, CgrtSurfaceSample* out, const float* attr, uint32_t channels,
+                        float* out_attr) {
+    return sample_query(s, false, n, params, out, attr, channels, out_attr, nullptr);
+}
+int cgrt_sample_surface_device(CgrtScene* s, uint64_t n, const CgrtSampleParams* params, CgrtSurfaceSample* d_out, const float* d_attr,
+                               uint32_t channels, float* d_out_attr, void* stream) {
+    return sample_query(s, true, n, params, d_out, d_attr, channels, d_out_attr, stream);
+}
+int cgrt_triangle_areas(CgrtScene* s, float* areas, double* total) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    CGRT_TRY(sample_host_table(s));
+    const SampleTable& T = s->sampling;
+    if (areas && !T.areas.empty()) memcpy(areas, T.areas.data(), T.areas.size() * sizeof(float));
+    if (total) *total = T.total;
+    return CGRT_OK;
+}
+int cgrt_debug_get_sample_table(CgrtScene* s, uint32_t* thresholds, uint32_t* last) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    CGRT_TRY(sample_host_table(s));
+    const SampleTable& T = s->sampling;
+    if (thresholds && !T.thresholds.empty()) memcpy(thresholds, T.thresholds.data(), T.thresholds.size() * sizeof(uint32_t));
+    if (last) *last = T.last;
     return CGRT_OK;
 }
 

@@ -15,14 +15,13 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "surface_device.h"
 #include "surface_kernels.h"
 #include "walk_exact.h"
 
 namespace cgrt {
 
 namespace {
-
-const uint32_t SURFACE_NONE = 0xffffffffu;  // in place of the first vertex row: the item gets zeros (miss, sphere, prim_id out of range)
 
 template <int SRC>
 __global__ __launch_bounds__(256) void k_surface(const SurfaceDev A) {
@@ -100,35 +99,7 @@ __global__ __launch_bounds__(256) void k_surface(const SurfaceDev A) {
             if (h < cnt) p[e] = c == 0u ? x : (c == 1u ? y : z);
         }
     }
-    if (A.out) {
-        float* p = A.out + (unsigned long long)C * wbase;
-        const uint32_t G = A.vec4 ? C >> 2 : C;  // channel groups per item
-        const uint32_t total = cnt * G;
-        for (uint32_t k = 0; k < total; k += 64u) {
-            const uint32_t e = k + lane, hq = e / G, g = e - hq * G;
-            const int h = (int)(hq & 63u);  // (lanes behind the last element ask a lane that exists; they store nothing)
-            const float x = __shfl(wa, h, 64), y = __shfl(wb, h, 64), z = __shfl(wg, h, 64);
-            const uint32_t s0 = __shfl(r0, h, 64), s1 = __shfl(r1, h, 64), s2 = __shfl(r2, h, 64);
-            if (e >= total) continue;
-            if (A.vec4) {
-                float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (s0 != SURFACE_NONE) {
-                    const float4 a0 = reinterpret_cast<const float4*>(A.attr + (unsigned long long)s0 * C)[g];
-                    const float4 a1 = reinterpret_cast<const float4*>(A.attr + (unsigned long long)s1 * C)[g];
-                    const float4 a2 = reinterpret_cast<const float4*>(A.attr + (unsigned long long)s2 * C)[g];
-                    v = make_float4(mix_weights(x, y, z, a0.x, a1.x, a2.x), mix_weights(x, y, z, a0.y, a1.y, a2.y),
-                                    mix_weights(x, y, z, a0.z, a1.z, a2.z), mix_weights(x, y, z, a0.w, a1.w, a2.w));
-                }
-                reinterpret_cast<float4*>(p)[e] = v;
-            } else {
-                float v = 0.0f;
-                if (s0 != SURFACE_NONE)
-                    v = mix_weights(x, y, z, A.attr[(unsigned long long)s0 * C + g], A.attr[(unsigned long long)s1 * C + g],
-                                    A.attr[(unsigned long long)s2 * C + g]);
-                p[e] = v;
-            }
-        }
-    }
+    if (A.out) surface_rows(A.attr, A.out, C, A.vec4, wbase, cnt, lane, wa, wb, wg, r0, r1, r2);  // (surface_device.h)
 }
 
 // The adjoint of k_surface's mix with respect to the table (include/cgrt.h cgrt_interpolate_hits_grad*, cgrt_surface_*_grad_device;

@@ -1146,6 +1146,68 @@ int cgrt_winding_numbers_brute(CgrtScene* scene, const float* points, uint64_t n
 int cgrt_debug_winding_work(CgrtScene* scene, const float* points, uint64_t n, const CgrtWindingParams* params, uint64_t* out3);
 int cgrt_debug_get_winding_tree(CgrtScene* scene, float* clusters, uint32_t* level_offsets, uint32_t* nlevels, uint32_t* record_prims);
 
+/* Surface sampling: points ON the scene's triangles, spread by area -- the producer the point queries above
+ * lack ("sample A, cgrt_closest_points on B" is a mesh-to-mesh distance; "sample, make rays, cgrt_occluded" a hemisphere integral).
+ * Sample j is a function of (scene, seed, j, strata) and nothing else, defined to the last bit, and everything that decides it is
+ * integer arithmetic.  All integer arithmetic below is unsigned and wraps; all f32 arithmetic is IEEE, every operation rounded on its own.
+ * Areas.  area_i = the reference's own area function (ray_tracing.cpp:13-21: the cross product of v1 - v0 and v2 - v0 in f32, its
+ * magnitude with squares, sum and sqrt in double, narrowed to f32, divided by 2.0f) of triangle i, i in prim_id order.  An area that is
+ * NaN, infinite or not > 0 counts as 0.  S_i is the running sum of the areas as doubles, added sequentially in prim_id order; A =
+ * S_{ntris-1} is the total.
+ * Thresholds.  T_i = min(floor((S_i / A) * 4294967296.0), 4294967295), evaluated in double, stored as u32.  L is the largest i with
+ * area_i > 0; a scene without such a triangle (or without meshes) is EMPTY FOR SAMPLING.
+ * Random words.  Philox4x32-10 with the Random123 constants (multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and
+ * 0xBB67AE85); for the 64-bit sample index j the counter is {lo32(j), hi32(j), 0, 0} and the key {lo32(seed), hi32(seed)}; of the output
+ * words w0..w3, w3 is unused.  (Known answer: counter 0,0,0,0 under key 0,0 gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8.)
+ * Position word.  strata == 0 (independent samples): x = w0.  strata = N > 0 (sample j lies in stratum j of N equal strata of the area
+ * measure): x = floor((j * 2^32 + w0) / N) in 64-bit integers, which needs j < N <= 0xffffffff.
+ * Triangle.  prim = #{ i < L : T_i <= x }: an upper bound over the first L thresholds; the last triangle with an area takes the rest.
+ * Hence a triangle of area 0 is never chosen, wherever it sits, and a triangle smaller than 2^-32 of the total area may never be chosen.
+ * Point.  a = w1 >> 8, b = w2 >> 8; if a + b > 2^24 then a = 2^24 - a and b = 2^24 - b; c = 2^24 - a - b.  bary = {c, a, b} * 2^-24 (exact
+ * in f32), the weights of v0, v1, v2.  point.k = (bary0 * v0.k + bary1 * v1.k) + bary2 * v2.k, the order of cgrt_interpolate_hits.
+ * Record.  CgrtSurfaceSample, 32 bytes; point, prim_id and bary sit at the offsets of CgrtClosest; mesh_id is the triangle's material
+ * index (CgrtHit.material_id).  In a scene that is empty for sampling every record is {0,0,0, 0xffffffff, CGRT_NO_PRIM, 0,0,0}.
+ * Per-vertex table (optional: attr and out_attr both, or neither).  attr is nverts x channels f32 (channels in 1..256), as
+ * cgrt_interpolate_hits takes it; out_attr (n x channels) receives (bary0 * a0 + bary1 * a1) + bary2 * a2 over the triangle's three
+ * vertex rows, zero rows for empty records.  With the vertex positions as the table the rows are the records' points, bit for bit.
+ * Chunking.  A call with params->first = f writes samples f .. f + n - 1: any split of a range into calls, streams or devices gives the
+ * same bytes.
+ * Scale.  Multiplying every position by 2^k scales the areas exactly while none leaves the normal f32 range: thresholds, prim_id and
+ * bary are then unchanged and the points are the old points times 2^k.
+ * cgrt_triangle_areas: areas (NULL, or ntris floats: area_i, 0 where it counts as 0) and *total (NULL, or A).  cgrt_debug_get_sample_table:
+ * thresholds (NULL, or ntris entries; all 0 in an empty scene) and *last (NULL, or L; CGRT_NO_PRIM in an empty scene).  Both are host
+ * work and succeed on a host-only scene, as cgrt_debug_get_winding_tree does.
+ * The table is built on the host by the scene's first sampling call (any of the four entries), under the scene's lock; the thresholds
+ * are uploaded once and freed with the scene, and cgrt_device_bytes includes them (and the lookup table of cgrt_interpolate_hits) from
+ * then on.
+ * Streams.  The host form (host pointers, synchronous) runs on a call lane like cgrt_closest_points: any number of threads may sample
+ * one scene at once.  The device form reads no host array behind the call and only enqueues on `stream` (NULL = default stream).
+ * Neither reads or writes the prediction record, the frame hints or any frame state.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene; NULL out with n > 0; exactly one of attr and out_attr
+ * given; n > 0x7fffffff; (with a table) channels outside 1..256, or n x channels x 4 above 2^40 bytes; strata > 0xffffffff; strata > 0
+ * and first + n > strata; first + n overflows 64 bits; (device form) a pointer not 4-byte aligned.  Then a host-only scene:
+ * CGRT_E_NO_DEVICE.  n == 0 succeeds and touches nothing.  Device form: then d_out (n * 32 bytes), d_attr (nverts * channels * 4) and
+ * d_out_attr (n * channels * 4) checked as device memory of the scene's device.
+ * Not offered: gradients through the samples; spheres; a restriction to some meshes or materials; weights other than area; blue-noise
+ * or Poisson-disk sets; grid and enqueued-ticket forms (the device form never blocks); the C++ host mirror. */
+typedef struct CgrtSurfaceSample {
+    float point[3];
+    uint32_t mesh_id; /* 0xffffffff in an empty scene */
+    uint32_t prim_id; /* CGRT_NO_PRIM in an empty scene */
+    float bary[3];    /* the weights of tri[prim_id][0..2] */
+} CgrtSurfaceSample;
+typedef struct CgrtSampleParams { /* NULL = zeros */
+    uint64_t seed;                /* the Philox key */
+    uint64_t first;               /* the index of the call's first sample */
+    uint64_t strata;              /* 0 = independent samples; N = sample j in stratum j of N (first + n <= N <= 0xffffffff) */
+} CgrtSampleParams;
+int cgrt_sample_surface(CgrtScene* scene, uint64_t n, const CgrtSampleParams* params, CgrtSurfaceSample* out, const float* attr,
+                        uint32_t channels, float* out_attr);
+int cgrt_sample_surface_device(CgrtScene* scene, uint64_t n, const CgrtSampleParams* params, CgrtSurfaceSample* d_out, const float* d_attr,
+                               uint32_t channels, float* d_out_attr, void* stream);
+int cgrt_triangle_areas(CgrtScene* scene, float* areas, double* total);
+int cgrt_debug_get_sample_table(CgrtScene* scene, uint32_t* thresholds, uint32_t* last);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
