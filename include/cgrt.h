@@ -674,6 +674,21 @@ int cgrt_render_raycams_light_sets_device(CgrtScene* scene, const CgrtRayCamera*
  * that p lies in the triangle.  Zeros are written to every requested output of an item that is a miss (hit == 0, or prim_id ==
  * CGRT_NO_PRIM), a sphere hit (prim_id >= ntris) or carries any other out-of-range prim_id: a caller-supplied id never indexes out of
  * bounds.  (The frame forms have no hit flag: a miss is the CGRT_NO_PRIM of the prim_id plane.)
+ * Envelope.  The cross products are products of two differences: they and the areas grow as the SQUARE of the scene's size -- quadratic
+ * where the closest points are quartic and the winding numbers cubic, because magnitude takes its squares, their sum and the square
+ * root in double, where nothing an f32 can hold overflows or is lost.  Per item: every non-zero f32 intermediate of the definition is a
+ * normal number -- the linear ones (o, d * t, p, the vertices and the two differences each of the four areas takes) and the quadratic
+ * ones (the six products and three components of each cross product, each magnitude as narrowed, each area):
+ *   min_lin * 2^k >= FLT_MIN,  max_lin * 2^k <= FLT_MAX,  min_quad * 2^2k >= FLT_MIN,  max_quad * 2^2k <= FLT_MAX
+ * with the minima and maxima taken at scale 1 (tests/scale_ref.py in_surface_envelope).  Inside, multiplying every position, every ray
+ * origin and t by 2^k is an exact symmetry: every operation rounds as at scale 1, both operands of each ratio carry the factor 2^2k,
+ * and alpha, beta, gamma have the bits they have at scale 1.  E.g. a unit-sized mesh (4 097 items each on cube, cornell, monkey, a
+ * 1 848-triangle blob and the 16 311-triangle dodge, one in eight on an edge, one in sixteen on a vertex): every item is inside from
+ * 2^-31 to 2^+63; at 2^-40 93.7 % (dodge) to 99.7 % (cube) are, at 2^-56 a third to nine tenths, at 2^-75 none; at 2^+64 none of the
+ * unit cube's (its area overflows), a fifth of cornell's, and still all of the three finer meshes'.  The condition is a proof, not a
+ * margin: no inside item was seen with other bits.  Outside the envelope the bytes are still the defined ones, on every path --
+ * subnormal differences, products and areas are kept, not flushed, and an overflowed area gives the 0 (finite / inf) or NaN (inf / inf)
+ * the formula gives -- but they need not be the weights of scale 1 (tests/test_surface_scale_cpu.py prints the table).
  *
  * Ray lists.  rays / hits are what cgrt_intersect_batch[_device] took and returned (t and prim_id are read from hits[i], origin and
  * direction from rays[i]); bary is n x 3 f32 {alpha, beta, gamma}; out is n x channels f32; attr is nverts x channels f32 -- an argument
@@ -739,8 +754,12 @@ int cgrt_surface_raycams_device(CgrtScene* scene, const CgrtRayCamera* cams, uin
  * and its contributions in SOME order (contributions of neighbouring items may be summed with each other first), and its last bits may
  * differ from run to run.  For an element with m contributions w*g and previous content a, every such order obeys
  *   |got - exact| <= gamma(m + 1) * S + (m + 1) * 2^-126,   gamma(k) = k*u / (1 - k*u),  u = 2^-24,  S = |a| + sum |w*g|
- * (exact: the sum of a and the products of the f32 weights, in real arithmetic); this is the bound the tests use.  Whether the hardware
- * add flushes a denormal sum to zero is not known: nobody has measured it on gfx950 (the absolute term above allows for either).
+ * (exact: the sum of a and the products of the f32 weights, in real arithmetic); this is the bound the tests use.  The hardware add
+ * (global_atomic_add_f32) KEEPS subnormals on gfx950, operands and sums alike: measured under every mapping of the kernel (the shipped
+ * policy, and `element`, `item` and `item_plain` of CGRT_SURFACE_GRAD_MAP) on sums that are exact in every order -- 320 shuffled items
+ * of the unit square, weights in sixteenths, grad_out and previous content integers times 2^e, e = -120, -130, -140 -- every element
+ * was the exact subnormal image, bit for bit (tests/test_surface_scale_gpu.py asserts it).  The absolute term above is therefore slack
+ * on this hardware; it stays in the bound, which does not depend on it.
  * Layouts.  grad_out has the layout of the forward's out: (n, C); (B, H, W, C); (B, C, H, W) with chw != 0.  grad_attr is nverts x C
  * f32.  cgrt_interpolate_hits_grad takes host pointers, runs on a call lane and is synchronous; the *_device forms only enqueue on
  * `stream`, are concurrent on one scene, neither read nor write the prediction record or the frame hints, and use the four camera-table
@@ -1173,7 +1192,11 @@ int cgrt_debug_get_winding_tree(CgrtScene* scene, float* clusters, uint32_t* lev
  * Chunking.  A call with params->first = f writes samples f .. f + n - 1: any split of a range into calls, streams or devices gives the
  * same bytes.
  * Scale.  Multiplying every position by 2^k scales the areas exactly while none leaves the normal f32 range: thresholds, prim_id and
- * bary are then unchanged and the points are the old points times 2^k.
+ * bary are then unchanged and the points are the old points times 2^k.  Beyond that range triangles drop out SILENTLY, since an area
+ * that overflows to +inf or vanishes counts as 0: of the 32 triangles of a unit-sized Cornell box scaled by 2^64 the 10 largest are
+ * never sampled again (L is unchanged), a unit cube scaled by 2^64 -- or any unit-sized scene scaled by 2^-75 -- is empty for
+ * sampling, and at 2^-70 a 16 311-triangle mesh keeps 12 triangles, L moves to 11 and one threshold repeats 16 300 times.  The records
+ * are the defined ones throughout (tests/test_surface_scale_gpu.py).
  * cgrt_triangle_areas: areas (NULL, or ntris floats: area_i, 0 where it counts as 0) and *total (NULL, or A).  cgrt_debug_get_sample_table:
  * thresholds (NULL, or ntris entries; all 0 in an empty scene) and *last (NULL, or L; CGRT_NO_PRIM in an empty scene).  Both are host
  * work and succeed on a host-only scene, as cgrt_debug_get_winding_tree does.

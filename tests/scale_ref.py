@@ -7,7 +7,9 @@ barycentrics, counts, orders and `inside` are unchanged, points, t and sdf are m
 below state that per record; `in_envelope` is the headers' envelope paragraph in code.  Beside them what a sign test needs: `is_closed`,
 the float64 generalised winding number and queries just off the surface.
 The neighbour lists share dist2's envelope (`covariant_neighbors`).  The winding numbers (5.25) have one of their own,
-cubic where the others are quartic (`in_winding_envelope`, `covariant_winding_tree`): inside it w is not scaled but unchanged."""
+cubic where the others are quartic (`in_winding_envelope`, `covariant_winding_tree`): inside it w is not scaled but unchanged.
+The surface attributes (5.19) have a quadratic one, per item (`surface_items`, `surface_measures`, `in_surface_envelope`,
+`covariant_weights`): inside it the weights are unchanged; `covariant_samples` is the same statement for surface-sample records (5.27)."""
 import dataclasses
 
 import numpy as np
@@ -301,3 +303,89 @@ def sign_queries(sd, n, seed):
     ext = extent(sd)
     return np.ascontiguousarray(np.concatenate([cr.uniform_queries(sd, m, seed), offset_queries(sd, n - 2 * m - (n - 3 * m) // 2, seed + 1, 1e-2 * ext),
                                                 offset_queries(sd, m + (n - 3 * m) // 2, seed + 2, 1e-3 * ext)]), np.float32)
+
+
+# ---- the surface attributes (include/cgrt.h cgrt_hit_barycentrics*, "Envelope") ----
+def surface_items(sd, n, seed):
+    """(rays (n, 7) float32, prim (n,) int64): n hits made without a tracer.  The points and their triangles are sampling_ref.sample(sd, n,
+    seed)'s; item i with i % 8 == 1 has the weight of v0 moved onto v1 (a point on the edge v1 v2), item i with i % 16 == 2 the weights
+    (0, 0, 1) (the vertex v2), their points recomputed by the same float32 mix.  Unit directions and t in [0.5, 2] extents are drawn
+    from np.random.default_rng(seed); the origin is float32(p - d * t), so that o + d * t lands on p up to rounding.  t is rays[:, 6]."""
+    import sampling_ref
+
+    rec, _ = sampling_ref.sample(sd, n, seed)
+    prim = rec["prim_id"].astype(np.int64)
+    bary = rec["bary"].copy()
+    i = np.arange(n)
+    edge, vertex = i % 8 == 1, i % 16 == 2
+    bary[edge] = np.stack([np.zeros(int(edge.sum()), F32), bary[edge, 0] + bary[edge, 1], bary[edge, 2]], axis=1)
+    bary[vertex] = (0.0, 0.0, 1.0)
+    v0, v1, v2 = (v[prim] for v in sampling_ref.vertices(sd))
+    p = (bary[:, 0:1] * v0 + bary[:, 1:2] * v1) + bary[:, 2:3] * v2
+    rng = np.random.default_rng(seed)
+    d = rng.standard_normal((n, 3))
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F32)
+    t = (rng.uniform(0.5, 2.0, n) * extent(sd)).astype(F32)
+    rays = np.empty((n, 7), F32)
+    rays[:, 0:3] = (p.astype(np.float64) - d.astype(np.float64) * t.astype(np.float64)[:, None]).astype(F32)
+    rays[:, 3:6], rays[:, 6] = d, t
+    return rays, prim
+
+
+def _span(parts):
+    """(smallest non-zero magnitude, largest magnitude) per row, in float64, over float32 arrays of n rows (+inf and 0 for a row of zeros)."""
+    a = np.abs(np.concatenate([np.asarray(x, np.float64).reshape(len(x), -1) for x in parts], axis=1))
+    return np.where(a > 0, a, np.inf).min(axis=1), a.max(axis=1)
+
+
+def surface_measures(sd, rays, prim):
+    """(min_lin, max_lin, min_quad, max_quad), each (n,) float64: the smallest non-zero and the largest magnitude of the float32
+    intermediates of the weights' definition (tests/surface_ref.py) at scale 1, per item.
+      linear     (multiplied by 2^k under a scale of 2^k)   o, d * t, p = o + d * t, the three vertices, and the two edge differences each
+                 of the four areas takes: of (v0, v1, v2), (p, v1, v2), (p, v0, v2) and (p, v0, v1)
+      quadratic  (multiplied by 2^2k)   the six products and the three components of each cross product, each magnitude as narrowed to
+                 float32, and each area
+    A zero stays a zero at every scale and is left out of the minimum.  The magnitude's squares and their sum are taken in double, where
+    nothing a float32 can hold overflows or is lost, so nothing of the fourth degree enters."""
+    import surface_ref
+
+    r = np.ascontiguousarray(np.asarray(rays, F32).reshape(-1, 7))
+    o, d, t = r[:, 0:3], r[:, 3:6], r[:, 6]
+    _, (v0, v1, v2), _ = surface_ref.triangle_vertices(sd, np.asarray(prim, np.int64))
+    with np.errstate(all="ignore"):
+        dt = d * t[:, None]
+        p = o + dt
+        lin, quad = [o, dt, p, v0, v1, v2], []
+        for a, b, c in ((v0, v1, v2), (p, v1, v2), (p, v0, v2), (p, v0, v1)):
+            e1, e2 = b - a, c - a
+            lin += [e1, e2]
+            x = surface_ref._cross(e1, e2)
+            mag = surface_ref.magnitude(x)
+            quad += [e1[:, 1] * e2[:, 2], e2[:, 1] * e1[:, 2], e1[:, 2] * e2[:, 0], e2[:, 2] * e1[:, 0], e1[:, 0] * e2[:, 1], e2[:, 0] * e1[:, 1],
+                     x, mag, mag / F32(2.0)]
+    return _span(lin) + _span(quad)
+
+
+def in_surface_envelope(measures, k):
+    """(n,) bool: the item lies in the envelope of the surface attributes at scale 2^k -- the "Envelope" paragraph of include/cgrt.h's
+    surface-attribute entries in code: every linear intermediate of its definition times 2^k, and every quadratic one times 2^2k, is a
+    normal float32 (or zero).  Quadratic where the point queries are quartic and the winding numbers cubic.  Inside, every float32
+    operation of the definition rounds as at scale 1 and the two operands of each ratio carry the same factor 2^2k: the weights have the
+    bits they have at scale 1."""
+    min_lin, max_lin, min_quad, max_quad = measures
+    k = int(k)
+    with np.errstate(all="ignore"):
+        return ((np.ldexp(min_lin, k) >= FLT_MIN) & (np.ldexp(max_lin, k) <= FLT_MAX)
+                & (np.ldexp(min_quad, 2 * k) >= FLT_MIN) & (np.ldexp(max_quad, 2 * k) <= FLT_MAX))
+
+
+def covariant_weights(w0, wk):
+    """(n, 3) weights at scale 1 and at scale 2^k: the same bits (a NaN equal to a NaN), whatever k is."""
+    return _bits_eq(w0, wk).reshape(len(w0), -1).all(axis=1)
+
+
+def covariant_samples(r0, rk, k):
+    """Surface-sample records (sampling_ref.SAMPLE_DTYPE) at scale 1 and at scale 2^k: the same prim_id, mesh_id and bary bits, point =
+    ldexp(point0, k)."""
+    ok = (r0["prim_id"] == rk["prim_id"]) & (r0["mesh_id"] == rk["mesh_id"]) & _bits_eq(r0["bary"], rk["bary"]).all(axis=1)
+    return ok & _bits_eq(_ld(r0["point"], k), rk["point"]).all(axis=1)
