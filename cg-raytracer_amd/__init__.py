@@ -310,10 +310,11 @@ _surface_fn = None
 
 def _surface_function():
     """The torch.autograd.Function behind interpolate_hits_tensor / surface_views_tensor / surface_raycams_tensor when attr requires grad
-    (DESIGN.md section 5.23): apply(attr, forward, backward, which=None).  forward(attr.detach()) is the ordinary, non-recording call (a
+    (DESIGN.md sections 5.23 and 5.28): apply(attr, forward, backward, which=None, reproducible=False).  forward(attr.detach()) is the ordinary, non-recording call (a
     tensor, or a tuple of which entry `which` is the attribute and the others, the barycentrics, are marked non-differentiable);
     backward(grad) is the matching *_grad_tensor call on torch.cuda.current_stream().  Only attr gets a gradient: rays, hits, planes and
-    cameras are held as given and are not differentiable."""
+    cameras are held as given and are not differentiable.  With `reproducible` the backward call is the bitwise-reproducible entry, and
+    deterministic mode has nothing to object to."""
     global _surface_fn
     if _surface_fn is not None:
         return _surface_fn
@@ -322,8 +323,8 @@ def _surface_function():
 
     class SurfaceAttribute(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, attr, forward, backward, which=None):
-            ctx.backward_call, ctx.which = backward, which
+        def forward(ctx, attr, forward, backward, which=None, reproducible=False):
+            ctx.backward_call, ctx.which, ctx.reproducible = backward, which, reproducible
             res = forward(attr.detach())
             if which is not None:
                 ctx.mark_non_differentiable(*(t for k, t in enumerate(res) if k != which))
@@ -332,7 +333,7 @@ def _surface_function():
         @staticmethod
         @once_differentiable
         def backward(ctx, *grads):
-            if torch.are_deterministic_algorithms_enabled():
+            if not ctx.reproducible and torch.are_deterministic_algorithms_enabled():
                 msg = ("the surface-attribute backward adds into the table with float atomics: the order of the additions into one element "
                        "is unspecified and the last bits of the gradient may differ from run to run")
                 if torch.is_deterministic_algorithms_warn_only_enabled():
@@ -340,7 +341,7 @@ def _surface_function():
                 else:
                     raise RuntimeError(msg + " (torch.use_deterministic_algorithms(True) is set)")
             g = grads[0 if ctx.which is None else ctx.which]
-            return ctx.backward_call(g.contiguous()), None, None, None
+            return ctx.backward_call(g.contiguous()), None, None, None, None
 
     _surface_fn = SurfaceAttribute
     return _surface_fn
@@ -364,7 +365,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -485,6 +486,11 @@ def lib() -> C.CDLL:
     L.cgrt_interpolate_hits_grad_device.argtypes = [vp, vp, vp, u64, vp, u32, vp, vp]
     L.cgrt_surface_views_grad_device.argtypes = [vp, vp, u32, i32, i32, vp, vp, vp, u32, i32, vp, vp]
     L.cgrt_surface_raycams_grad_device.argtypes = L.cgrt_surface_views_grad_device.argtypes
+    L.cgrt_surface_grad_repro_workspace.argtypes = [vp, u32, C.POINTER(C.c_uint64)]
+    L.cgrt_interpolate_hits_grad_repro.argtypes = L.cgrt_interpolate_hits_grad.argtypes
+    L.cgrt_interpolate_hits_grad_repro_device.argtypes = [vp, vp, vp, u64, vp, u32, vp, vp, u64, vp]
+    L.cgrt_surface_views_grad_repro_device.argtypes = [vp, vp, u32, i32, i32, vp, vp, vp, u32, i32, vp, vp, u64, vp]
+    L.cgrt_surface_raycams_grad_repro_device.argtypes = L.cgrt_surface_views_grad_repro_device.argtypes
     L.cgrt_closest_points.argtypes = [vp, vp, u64, C.c_float, vp]
     L.cgrt_closest_points_brute.argtypes = [vp, vp, u64, C.c_float, vp]
     L.cgrt_closest_points_device.argtypes = [vp, vp, u64, C.c_float, vp, vp]
@@ -1927,9 +1933,11 @@ class Scene:
         return self._tensor_call(out, lead + (3,), torch.float32, stream,
                                  lambda o, s: self.hit_barycentrics_device(rays.data_ptr(), hits.data_ptr(), n, o.data_ptr(), stream=s))
 
-    def interpolate_hits_tensor(self, rays, hits, attr, out=None, stream=None):
+    def interpolate_hits_tensor(self, rays, hits, attr, out=None, stream=None, reproducible: bool = False):
         """interpolate_hits on torch tensors: attr is an (nverts, C) float32 tensor on cuda:<device> (any per-vertex table: colours,
-        texture coordinates, features; it may be a contiguous view into a larger allocation) -> (..., C) float32."""
+        texture coordinates, features; it may be a contiguous view into a larger allocation) -> (..., C) float32.  reproducible: when
+        attr requires grad, the recorded backward is the bitwise-reproducible entry (it runs under
+        torch.use_deterministic_algorithms(True)); the forward is the same either way."""
         import torch
 
         lead, n = self._hits_tensor(rays, hits)
@@ -1940,7 +1948,7 @@ class Scene:
                 raise ValueError("out= cannot be combined with an attr that requires grad")
             return _surface_function().apply(
                 attr, lambda a: self.interpolate_hits_tensor(rays, hits, a, stream=stream),
-                lambda g: self.interpolate_hits_grad_tensor(rays, hits, g))
+                lambda g: self.interpolate_hits_grad_tensor(rays, hits, g, reproducible=reproducible), None, bool(reproducible))
         if out is not None:
             self._device_tensor(out, "out", (torch.float32,), lead + (ch,))
         return self._tensor_call(out, lead + (ch,), torch.float32, stream,
@@ -1949,11 +1957,18 @@ class Scene:
 
     # ---- surface attributes: gradients back to the table (include/cgrt.h cgrt_interpolate_hits_grad*, cgrt_surface_*_grad_device;
     # DESIGN.md section 5.23) ----
-    def interpolate_hits_grad(self, rays, hits, grad_out, grad_attr=None) -> np.ndarray:
+    def surface_grad_repro_workspace(self, channels: int) -> int:
+        """cgrt_surface_grad_repro_workspace: the bytes of device memory a reproducible gradient call with `channels` channels needs."""
+        b = C.c_uint64(0)
+        _check(lib().cgrt_surface_grad_repro_workspace(self._h, int(channels), C.byref(b)))
+        return int(b.value)
+
+    def interpolate_hits_grad(self, rays, hits, grad_out, grad_attr=None, reproducible: bool = False) -> np.ndarray:
         """cgrt_interpolate_hits_grad, the adjoint of interpolate_hits with respect to attr: grad_out ((n, C) float32) is the gradient
         with respect to interpolate_hits' result; alpha / beta / gamma times each valid item's row is ADDED into rows tri[prim_id][0..2]
         of grad_attr -- a C-contiguous (nverts, C) float32 array that is accumulated into in place, or None for a new zero array.
-        Returns grad_attr.  The order of the additions into one element is unspecified (last bits may differ from run to run)."""
+        Returns grad_attr.  The order of the additions into one element is unspecified (last bits may differ from run to run), unless
+        reproducible: then cgrt_interpolate_hits_grad_repro, whose result is defined to the last bit (include/cgrt.h)."""
         r = _as_ray_array(rays)
         h = self._as_hit_array(hits, len(r))
         g = np.ascontiguousarray(np.asarray(grad_out, np.float32))
@@ -1967,21 +1982,36 @@ class Scene:
         elif not (isinstance(grad_attr, np.ndarray) and grad_attr.dtype == np.float32 and grad_attr.flags.c_contiguous
                   and grad_attr.flags.writeable and grad_attr.shape == (nverts, g.shape[1])):
             raise ValueError(f"grad_attr must be a writeable C-contiguous float32 array of shape ({nverts}, {g.shape[1]})")
-        _check(lib().cgrt_interpolate_hits_grad(self._h, _ptr(r), _ptr(h), len(r), _ptr(g), g.shape[1], _ptr(grad_attr)))
+        f = lib().cgrt_interpolate_hits_grad_repro if reproducible else lib().cgrt_interpolate_hits_grad
+        _check(f(self._h, _ptr(r), _ptr(h), len(r), _ptr(g), g.shape[1], _ptr(grad_attr)))
         return grad_attr
 
     def interpolate_hits_grad_device(self, d_rays_ptr: int, d_hits_ptr: int, n: int, d_grad_out_ptr: int, channels: int,
-                                     d_grad_attr_ptr: int, stream: int = 0) -> None:
+                                     d_grad_attr_ptr: int, stream: int = 0, reproducible: bool = False, d_workspace_ptr: int = 0,
+                                     workspace_bytes: int = 0) -> None:
         """cgrt_interpolate_hits_grad_device: n x channels floats at d_grad_out_ptr are added, weighted, into the (nverts, channels)
-        float32 table at d_grad_attr_ptr; enqueued on `stream`.  Raw integers."""
+        float32 table at d_grad_attr_ptr; enqueued on `stream`.  Raw integers.  reproducible: cgrt_interpolate_hits_grad_repro_device
+        with the caller's workspace (surface_grad_repro_workspace(channels) bytes of device memory, 8-byte aligned, this call's alone)."""
+        if reproducible:
+            _check(lib().cgrt_interpolate_hits_grad_repro_device(self._h, _vp(d_rays_ptr), _vp(d_hits_ptr), int(n), _vp(d_grad_out_ptr),
+                                                                 int(channels), _vp(d_grad_attr_ptr), _vp(d_workspace_ptr),
+                                                                 int(workspace_bytes), _vp(stream)))
+            return
         _check(lib().cgrt_interpolate_hits_grad_device(self._h, _vp(d_rays_ptr), _vp(d_hits_ptr), int(n), _vp(d_grad_out_ptr), int(channels),
                                                        _vp(d_grad_attr_ptr), _vp(stream)))
 
     def surface_views_grad_device(self, cams, W: int, H: int, d_depth_ptr: int, d_prim_id_ptr: int, d_grad_out_ptr: int, channels: int,
-                                  d_grad_attr_ptr: int, chw: bool = False, stream: int = 0, raycams: bool = False) -> None:
+                                  d_grad_attr_ptr: int, chw: bool = False, stream: int = 0, raycams: bool = False,
+                                  reproducible: bool = False, d_workspace_ptr: int = 0, workspace_bytes: int = 0) -> None:
         """cgrt_surface_views_grad_device (raycams: cgrt_surface_raycams_grad_device): the gradient (B, H, W, channels) -- (B, channels,
-        H, W) with chw -- of B frames' interpolated attribute, added into the table at d_grad_attr_ptr.  Raw integers; enqueued."""
+        H, W) with chw -- of B frames' interpolated attribute, added into the table at d_grad_attr_ptr.  Raw integers; enqueued.
+        reproducible: the *_grad_repro_device twin with the caller's workspace, as interpolate_hits_grad_device takes it."""
         a = raycam_array(cams) if raycams else camera_array(cams)
+        if reproducible:
+            f = lib().cgrt_surface_raycams_grad_repro_device if raycams else lib().cgrt_surface_views_grad_repro_device
+            _check(f(self._h, _ptr(a) if len(a) else None, len(a), W, H, _vp(d_depth_ptr), _vp(d_prim_id_ptr), _vp(d_grad_out_ptr),
+                     int(channels), 1 if chw else 0, _vp(d_grad_attr_ptr), _vp(d_workspace_ptr), int(workspace_bytes), _vp(stream)))
+            return
         f = lib().cgrt_surface_raycams_grad_device if raycams else lib().cgrt_surface_views_grad_device
         _check(f(self._h, _ptr(a) if len(a) else None, len(a), W, H, _vp(d_depth_ptr), _vp(d_prim_id_ptr), _vp(d_grad_out_ptr), int(channels),
                  1 if chw else 0, _vp(d_grad_attr_ptr), _vp(stream)))
@@ -2000,10 +2030,24 @@ class Scene:
             self._device_tensor(grad_attr, "grad_attr", (torch.float32,), (nverts, channels))
         return grad_attr, stream
 
-    def interpolate_hits_grad_tensor(self, rays, hits, grad_out, grad_attr=None, stream=None):
+    def _repro_workspace_tensor(self, reproducible: bool, channels: int, stream):
+        """(workspace, keywords) of a reproducible *_grad_device call: the workspace is a torch.uint8 tensor allocated on the call's
+        stream, which the caller holds until the call has enqueued its passes -- from then on the caching allocator hands the block only
+        to work that the same stream runs later.  (None, {}) for the float form."""
+        if not reproducible:
+            return None, {}
+        import torch
+
+        nbytes = self.surface_grad_repro_workspace(channels)
+        with torch.cuda.stream(stream):
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=stream.device)
+        return ws, {"reproducible": True, "d_workspace_ptr": ws.data_ptr(), "workspace_bytes": nbytes}
+
+    def interpolate_hits_grad_tensor(self, rays, hits, grad_out, grad_attr=None, stream=None, reproducible: bool = False):
         """interpolate_hits_grad on torch tensors: rays, hits as interpolate_hits_tensor took them, grad_out (..., C) float32; added into
         grad_attr ((nverts, C) float32 on the device, or None for a new zero tensor), which is returned.  Enqueued on `stream` (default:
-        torch.cuda.current_stream()).  interpolate_hits_tensor calls this in its backward when attr requires grad."""
+        torch.cuda.current_stream()).  interpolate_hits_tensor calls this in its backward when attr requires grad.  reproducible: the
+        bitwise-reproducible entry, its workspace allocated here on the call's stream."""
         import torch
 
         lead, n = self._hits_tensor(rays, hits)
@@ -2014,8 +2058,10 @@ class Scene:
         ch = grad_out.shape[-1]
         grad_attr, stream = self._grad_attr_tensor(grad_attr, ch, stream)
         if n:
+            ws, kw = self._repro_workspace_tensor(reproducible, ch, stream)
             self.interpolate_hits_grad_device(rays.data_ptr(), hits.data_ptr(), n, grad_out.data_ptr(), ch, grad_attr.data_ptr(),
-                                              stream=stream.cuda_stream)
+                                              stream=stream.cuda_stream, **kw)
+            del ws  # (held until here: the passes are enqueued)
         return grad_attr
 
     # ---- closest-point queries (include/cgrt.h cgrt_closest_points*) ----
@@ -2677,7 +2723,7 @@ class Scene:
             res["attr"] = rows
         return res
 
-    def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream):
+    def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream, reproducible=False):
         import torch
 
         if self.device < 0:
@@ -2721,8 +2767,8 @@ class Scene:
                 return tuple(res[k] for k in keys)
 
             got = _surface_function().apply(
-                attr, forward, lambda g: self._surface_frames_grad_tensor(raycams, cams, W, H, depth, prim_id, g, chw, None, None),
-                keys.index("attr"))
+                attr, forward, lambda g: self._surface_frames_grad_tensor(raycams, cams, W, H, depth, prim_id, g, chw, None, None, reproducible),
+                keys.index("attr"), bool(reproducible))
             return dict(zip(keys, got))
         dev, stream = self._torch_stream(stream)
         _check_one_hip_runtime()
@@ -2733,7 +2779,7 @@ class Scene:
                                   d_out_ptr=res["attr"].data_ptr() if "attr" in res else 0, chw=chw, stream=stream.cuda_stream, raycams=raycams)
         return res
 
-    def _surface_frames_grad_tensor(self, raycams, cams, W, H, depth, prim_id, grad_out, chw, grad_attr, stream):
+    def _surface_frames_grad_tensor(self, raycams, cams, W, H, depth, prim_id, grad_out, chw, grad_attr, stream, reproducible=False):
         import torch
 
         if self.device < 0:
@@ -2759,35 +2805,41 @@ class Scene:
             raise ValueError("grad_out must have 1..256 channels")
         self._device_tensor(grad_out, "grad_out", (torch.float32,), lead + ((ch, H, W) if chw else (H, W, ch)))
         grad_attr, stream = self._grad_attr_tensor(grad_attr, ch, stream)
+        ws, kw = self._repro_workspace_tensor(reproducible, ch, stream)
         self.surface_views_grad_device(a, W, H, depth.data_ptr(), prim_id.data_ptr(), grad_out.data_ptr(), ch, grad_attr.data_ptr(), chw=chw,
-                                       stream=stream.cuda_stream, raycams=raycams)
+                                       stream=stream.cuda_stream, raycams=raycams, **kw)
+        del ws  # (held until here: the passes are enqueued)
         return grad_attr
 
-    def surface_views_grad_tensor(self, cams, W: int, H: int, depth, prim_id, grad_out, chw: bool = False, grad_attr=None, stream=None):
+    def surface_views_grad_tensor(self, cams, W: int, H: int, depth, prim_id, grad_out, chw: bool = False, grad_attr=None, stream=None,
+                                  reproducible: bool = False):
         """The adjoint of surface_views_tensor's 'attr' output with respect to the table: cams, W, H, depth and prim_id as the forward
         took them, grad_out (B, H, W, C) float32 -- (B, C, H, W) with chw; (H, W, C) / (C, H, W) for one camera's (H, W) planes.  Added
         into grad_attr ((nverts, C) float32 on the device, or None for a new zero tensor), which is returned: a running gradient over
         several frames is one tensor passed again and again.  Enqueued on `stream` (default: torch.cuda.current_stream()).  The order of
-        the additions into one element is unspecified.  surface_views_tensor calls this in its backward when attr requires grad."""
-        return self._surface_frames_grad_tensor(False, cams, W, H, depth, prim_id, grad_out, chw, grad_attr, stream)
+        the additions into one element is unspecified, unless reproducible: then the bitwise-reproducible entry (include/cgrt.h), its
+        workspace allocated here on the call's stream.  surface_views_tensor calls this in its backward when attr requires grad."""
+        return self._surface_frames_grad_tensor(False, cams, W, H, depth, prim_id, grad_out, chw, grad_attr, stream, reproducible)
 
-    def surface_raycams_grad_tensor(self, cams, W: int, H: int, depth, prim_id, grad_out, chw: bool = False, grad_attr=None, stream=None):
+    def surface_raycams_grad_tensor(self, cams, W: int, H: int, depth, prim_id, grad_out, chw: bool = False, grad_attr=None, stream=None,
+                                    reproducible: bool = False):
         """surface_views_grad_tensor for ray cameras."""
-        return self._surface_frames_grad_tensor(True, cams, W, H, depth, prim_id, grad_out, chw, grad_attr, stream)
+        return self._surface_frames_grad_tensor(True, cams, W, H, depth, prim_id, grad_out, chw, grad_attr, stream, reproducible)
 
     def surface_views_tensor(self, cams, W: int, H: int, depth, prim_id, attr=None, want_bary: bool = True, chw: bool = False, out=None,
-                             stream=None):
+                             stream=None, reproducible: bool = False):
         """The surface attributes of whole frames from their geometry planes: cams (B Trackball cameras, or one) and the `depth` (float32)
         and `prim_id` (int32) planes of render_views_aov_tensor / render_aov_tensor, (B, H, W) -- or (H, W) for one camera; for the planes
         of an aa frame pass 2W, 2H.  Returns a dict: 'bary' (B, H, W, 3) when want_bary, 'attr' (B, H, W, C) when attr ((nverts, C)
         float32 on the device) is given; (B, 3, H, W) / (B, C, H, W) with chw.  out: dict of caller's tensors for some or all of them.
-        Enqueued on `stream` (default: torch.cuda.current_stream()); nothing is traced."""
-        return self._surface_frames_tensor(False, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream)
+        Enqueued on `stream` (default: torch.cuda.current_stream()); nothing is traced.  reproducible: when attr requires grad, the
+        recorded backward is the bitwise-reproducible entry (it runs under torch.use_deterministic_algorithms(True))."""
+        return self._surface_frames_tensor(False, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream, reproducible)
 
     def surface_raycams_tensor(self, cams, W: int, H: int, depth, prim_id, attr=None, want_bary: bool = True, chw: bool = False, out=None,
-                               stream=None):
+                               stream=None, reproducible: bool = False):
         """surface_views_tensor for ray cameras (the planes of render_raycams_tensor(aovs=...))."""
-        return self._surface_frames_tensor(True, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream)
+        return self._surface_frames_tensor(True, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream, reproducible)
 
     def generate_rays(self, cam, W: int, H: int, rect=None) -> np.ndarray:
         x0, y0, x1, y1 = rect if rect is not None else (0, 0, W, H)

@@ -34,6 +34,7 @@
 #include "crossing_kernels.h"
 #include "neighbor_kernels.h"
 #include "sdf_kernels.h"
+#include "surface_grad_repro_kernels.h"
 #include "surface_kernels.h"
 #include "surface_sample_builder.h"
 #include "surface_sample_kernels.h"

@@ -322,21 +322,40 @@ SurfaceGradDev surface_grad_dev(const CgrtScene* s, const SurfaceLookup* lookup,
     surface_grad_policy(channels, A.chw, &A.by_item, &A.combine);
     return A;
 }
+// The reproducible form's workspace as the caller gave it (include/cgrt.h cgrt_*_grad_repro*); null: the float form.
+struct ReproWorkspace {
+    void* d;
+    uint64_t bytes;
+};
+// d_workspace NULL, misaligned or too small: the checks that follow the twin's, before the host-only scene
+int surface_repro_args(const CgrtScene* s, uint32_t channels, const ReproWorkspace* ws) {
+    if (!ws) return CGRT_OK;
+    if (!ws->d) return fail(CGRT_E_ARG, "NULL argument");
+    if ((uintptr_t)ws->d % 8) return fail(CGRT_E_ARG, "d_workspace must be 8-byte aligned");
+    if (ws->bytes < surface_grad_repro_bytes((uint64_t)s->nverts * channels))
+        return fail(CGRT_E_ARG, "workspace_bytes is below cgrt_surface_grad_repro_workspace");
+    return CGRT_OK;
+}
 int surface_list_grad_launch(CgrtScene* s, const void* d_rays, const void* d_hits, uint64_t n, const float* d_grad_out, uint32_t channels,
-                             float* d_grad_attr, hipStream_t st) {
+                             float* d_grad_attr, void* d_workspace, hipStream_t st) {
     const SurfaceLookup* lookup = nullptr;
     const int rc = surface_lookup(s, &lookup);
     if (rc) return rc;
     SurfaceGradDev A = surface_grad_dev(s, lookup, n, d_grad_out, channels, d_grad_attr, 0);
     A.rays = static_cast<const float*>(d_rays);
     A.hits = static_cast<const CgrtHitDev*>(d_hits);
-    HIP_TRY(launch_surface_grad(A, SURFACE_LIST, st));
+    if (d_workspace)
+        HIP_TRY(launch_surface_grad_repro(A, SURFACE_LIST, (uint64_t)s->nverts * channels, d_workspace, st));
+    else
+        HIP_TRY(launch_surface_grad(A, SURFACE_LIST, st));
     return CGRT_OK;
 }
-// cgrt_interpolate_hits_grad*; slots: 0 rays, 1 hits, 2 grad_out, 3 grad_attr (host form: uploaded, accumulated into, downloaded)
+// cgrt_interpolate_hits_grad*; slots: 0 rays, 1 hits, 2 grad_out, 3 grad_attr (host form: uploaded, accumulated into, downloaded).
+// repro: the reproducible form, whose workspace is the caller's `ws` (device form) or the lane's slot 4 (host form)
 int surface_list_grad(CgrtScene* s, bool device, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
-                      float* grad_attr, void* stream) {
+                      float* grad_attr, bool repro, const ReproWorkspace* ws, void* stream) {
     CGRT_TRY(surface_list_args(s, rays, hits, n, true, grad_attr, channels, grad_out, device));
+    if (n) CGRT_TRY(surface_repro_args(s, channels, ws));
     NEED_DEVICE(s);
     if (n == 0) return CGRT_OK;
     QueryCall c(s, device, stream);
@@ -346,13 +365,20 @@ int surface_list_grad(CgrtScene* s, bool device, const CgrtRay* rays, const Cgrt
     CGRT_TRY(c.in(1, hits, n * sizeof(CgrtHit), "d_hits", &dh));
     CGRT_TRY(c.inout(3, grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr", &dt));
     CGRT_TRY(c.in(2, grad_out, n * channels * 4ull, "d_grad_out", &dgo));
-    CGRT_TRY(surface_list_grad_launch(s, dr, dh, n, static_cast<const float*>(dgo), channels, static_cast<float*>(dt), c.stream()));
+    void* dws = nullptr;
+    if (ws) {
+        dws = ws->d;
+        CGRT_TRY(check_device_span(s, dws, surface_grad_repro_bytes((uint64_t)s->nverts * channels), "d_workspace"));
+    } else if (repro) {
+        HIP_TRY(c.c.scratch(4, surface_grad_repro_bytes((uint64_t)s->nverts * channels), &dws));
+    }
+    CGRT_TRY(surface_list_grad_launch(s, dr, dh, n, static_cast<const float*>(dgo), channels, static_cast<float*>(dt), dws, c.stream()));
     return c.finish();
 }
 // cgrt_surface_views_grad_device and its ray-camera twin (exactly one of cams, raycams)
 int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews, int W, int H,
                                const float* d_depth, const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw,
-                               float* d_grad_attr, void* stream) {
+                               float* d_grad_attr, const ReproWorkspace* ws, void* stream) {
     if (!s || !d_depth || !d_prim_id || !d_grad_out || !d_grad_attr) return fail(CGRT_E_ARG, "NULL argument");
     int rc = views_args(raycams ? static_cast<const void*>(raycams) : cams, nviews, W, H, raycams);
     if (rc) return rc;
@@ -360,12 +386,15 @@ int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtR
     if ((rc = surface_channels(channels, npix)) != CGRT_OK) return rc;
     if ((uintptr_t)d_depth % 4 || (uintptr_t)d_prim_id % 4 || (uintptr_t)d_grad_attr % 4 || (uintptr_t)d_grad_out % 4)
         return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    if ((rc = surface_repro_args(s, channels, ws)) != CGRT_OK) return rc;
     NEED_DEVICE(s);
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = check_device_span(s, d_depth, npix * 4, "d_depth")) != CGRT_OK) return rc;
     if ((rc = check_device_span(s, d_prim_id, npix * 4, "d_prim_id")) != CGRT_OK) return rc;
     if ((rc = check_device_span(s, d_grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr")) != CGRT_OK) return rc;
     if ((rc = check_device_span(s, d_grad_out, npix * channels * 4ull, "d_grad_out")) != CGRT_OK) return rc;
+    const uint64_t elements = (uint64_t)s->nverts * channels;
+    if (ws && (rc = check_device_span(s, ws->d, surface_grad_repro_bytes(elements), "d_workspace")) != CGRT_OK) return rc;
     const SurfaceLookup* lookup = nullptr;
     if ((rc = surface_lookup(s, &lookup)) != CGRT_OK) return rc;
     SurfaceGradDev A = surface_grad_dev(s, lookup, npix, d_grad_out, channels, d_grad_attr, chw);
@@ -377,6 +406,7 @@ int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtR
     hipStream_t const st = static_cast<hipStream_t>(stream);
     return launch_with_view_table(s, view_table(cams, raycams, nviews), st, [&](const void* d_table) {
         A.cams = d_table;
+        if (ws) return launch_surface_grad_repro(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, elements, ws->d, st);
         return launch_surface_grad(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, st);
     });
 }
@@ -384,11 +414,38 @@ int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtR
 
 int cgrt_interpolate_hits_grad(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out, uint32_t channels,
                                float* grad_attr) {
-    return surface_list_grad(s, false, rays, hits, n, grad_out, channels, grad_attr, nullptr);
+    return surface_list_grad(s, false, rays, hits, n, grad_out, channels, grad_attr, false, nullptr, nullptr);
+}
+int cgrt_surface_grad_repro_workspace(CgrtScene* s, uint32_t channels, uint64_t* bytes) {
+    if (!s || !bytes) return fail(CGRT_E_ARG, "NULL argument");
+    if (channels < 1 || channels > 256) return fail(CGRT_E_ARG, "channels must be in 1..256");
+    *bytes = surface_grad_repro_bytes((uint64_t)s->nverts * channels);
+    return CGRT_OK;
+}
+int cgrt_interpolate_hits_grad_repro(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out,
+                                     uint32_t channels, float* grad_attr) {
+    return surface_list_grad(s, false, rays, hits, n, grad_out, channels, grad_attr, true, nullptr, nullptr);
+}
+int cgrt_interpolate_hits_grad_repro_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out,
+                                            uint32_t channels, float* d_grad_attr, void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    const ReproWorkspace ws{d_workspace, workspace_bytes};
+    return surface_list_grad(s, true, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, true, &ws, stream);
+}
+int cgrt_surface_views_grad_repro_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                         const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
+                                         void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    const ReproWorkspace ws{d_workspace, workspace_bytes};
+    return surface_frames_grad_device(s, cams, nullptr, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, &ws, stream);
+}
+int cgrt_surface_raycams_grad_repro_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                           const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
+                                           void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    const ReproWorkspace ws{d_workspace, workspace_bytes};
+    return surface_frames_grad_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, &ws, stream);
 }
 int cgrt_interpolate_hits_grad_device(CgrtScene* s, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n, const float* d_grad_out,
                                       uint32_t channels, float* d_grad_attr, void* stream) {
-    return surface_list_grad(s, true, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, stream);
+    return surface_list_grad(s, true, d_rays, d_hits, n, d_grad_out, channels, d_grad_attr, false, nullptr, stream);
 }
 int cgrt_hit_barycentrics(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, float* bary) {
     return surface_list(s, false, rays, hits, n, false, nullptr, 0, bary, nullptr);
@@ -406,12 +463,12 @@ int cgrt_interpolate_hits_device(CgrtScene* s, const CgrtRay* d_rays, const Cgrt
 int cgrt_surface_views_grad_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
                                    const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
                                    void* stream) {
-    return surface_frames_grad_device(s, cams, nullptr, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, stream);
+    return surface_frames_grad_device(s, cams, nullptr, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, nullptr, stream);
 }
 int cgrt_surface_raycams_grad_device(CgrtScene* s, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
                                      const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
                                      void* stream) {
-    return surface_frames_grad_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, stream);
+    return surface_frames_grad_device(s, nullptr, cams, nviews, W, H, d_depth, d_prim_id, d_grad_out, channels, chw, d_grad_attr, nullptr, stream);
 }
 
 int cgrt_surface_views_device(CgrtScene* s, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth, const uint32_t* d_prim_id,

@@ -768,8 +768,9 @@ int cgrt_surface_raycams_device(CgrtScene* scene, const CgrtRayCamera* cams, uin
  * required): NULL pointers; n > 0x7fffffff; channels outside 1..256; the 2^40-byte bound; 4-byte alignment; the camera checks; the views
  * limits.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and touches nothing.  Device forms: then every buffer's extent is
  * checked as device memory of the scene's device (d_grad_attr over nverts * channels * 4 bytes).
- * Not offered: a bitwise-reproducible form (a store pass, a per-destination sum through an inverted index and a fixed order: a
- * follow-up); gradients with respect to vertex positions, rays or cameras (the weights are piecewise-smooth in them: a different
+ * Not offered: reproducible bits from THESE entries (the *_grad_repro* entries below are the bitwise-reproducible form; it is per call:
+ * a gradient accumulated over several calls is reproducible because each call is, and it equals no single larger call);
+ * gradients with respect to vertex positions, rays or cameras (the weights are piecewise-smooth in them: a different
  * feature); per-triangle tables; bf16 / f16 tables; planes inside the cgrt_render_*aov* calls; enqueued-ticket forms (these calls never
  * block); the C++ host mirror. */
 int cgrt_interpolate_hits_grad(CgrtScene* scene, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out,
@@ -782,6 +783,50 @@ int cgrt_surface_views_grad_device(CgrtScene* scene, const CgrtCamera* cams, uin
 int cgrt_surface_raycams_grad_device(CgrtScene* scene, const CgrtRayCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
                                      const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw, float* d_grad_attr,
                                      void* stream);
+
+/* Surface attributes, the bitwise-reproducible form of the gradients above.  An opt-in second form of the table
+ * adjoint whose result is a pure function of the call's inputs: it does not depend on the order in which the hardware performs the
+ * additions, on the mapping of lanes to items, on a permutation of the items, or on the run.  The entries above are unchanged.
+ * Definition.  Validity, weights, rows and products are those of the entries above.  A valid item i contributes
+ * x = fl32(w_k * g[i][c]) to element (tri[prim][k], c), rounded on its own, nothing contracted; invalid items contribute nothing and
+ * their grad_out is never read.  For an element with previous content a and contributions x_1..x_m (m >= 1), n the call's item count
+ * (frames: n = B * H * W):
+ *   S = min(24, 38 - bitlength(3 n))                      (n <= 0x7fffffff, so S >= 5)
+ *   a finite x_j is +-M_j * 2^(e'_j - 150), e'_j = max(exponent field, 1), M_j the 24-bit significand (a subnormal: no implicit bit)
+ *   E = max_j e'_j,  d_j = E - e'_j
+ *   T_j = +-(M_j << (S - d_j)) if d_j <= S, else +-(M_j >> (d_j - S))   (the magnitude is truncated; 0 once the shift reaches 24)
+ *   I = sum_j T_j in int64                                (no overflow: |I| < 2^(24 + S) * 3 n <= 2^62)
+ *   new value = fl32( fl64(a) + fl64(I) * 2^(E - 150 - S) )
+ * fl64(I) is the round-to-nearest-even conversion, the scaling is exact, the sum is rounded to double and then once to float,
+ * subnormals kept.  If any x_j is not finite the element becomes fl32(a + s), s = NaN if a NaN contribution is present or both +inf and
+ * -inf are, else the infinity that is present.  Every NaN result is stored as the quiet NaN 0x7fc00000.  Elements without a contribution
+ * are not written: rows no valid item names keep their bytes.  A contribution of +-0 still counts: the element becomes fl32(a + 0).
+ * Integer addition is associative, hence the order-freedom.  The result also obeys the bound of the entries above,
+ * gamma(m + 1) * S_abs + (m + 1) * 2^-126: it is a legal value of the float form.  It is per call: S depends on n, and E on the call's
+ * contributions, so a gradient accumulated over several calls equals no single larger call.
+ * Workspace.  cgrt_surface_grad_repro_workspace reports the bytes a call on this scene with `channels` channels needs (12 per table
+ * element: nverts * channels * 12).  The device forms take it as d_workspace / workspace_bytes: device memory of the scene's device,
+ * 8-byte aligned, contents need no initialisation, owned by the caller, and not to be shared by calls in flight at the same time.  With
+ * separate workspaces the device forms stay concurrent on one scene; they only enqueue (a clear, two passes over the items -- integer
+ * atomic max / or, then 64-bit integer atomic add -- and one pass over the table) and touch neither the prediction record nor the frame
+ * hints.  cgrt_interpolate_hits_grad_repro takes host pointers, runs on a call lane, is synchronous and allocates the workspace itself.
+ * Checks: those of the float twin in its order (CGRT_E_ARG); then d_workspace NULL, not 8-byte aligned or workspace_bytes too small
+ * (CGRT_E_ARG; the list form with n == 0 skips these as it skips its NULL checks); then a host-only scene: CGRT_E_NO_DEVICE; n == 0
+ * succeeds and touches nothing; then the extents of the device buffers, the workspace included.
+ * Not offered: a form reproducible across a split into several calls; gradients with respect to positions, rays or cameras; f16 / bf16
+ * tables; the C++ host mirror. */
+int cgrt_surface_grad_repro_workspace(CgrtScene* scene, uint32_t channels, uint64_t* bytes);
+int cgrt_interpolate_hits_grad_repro(CgrtScene* scene, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out,
+                                     uint32_t channels, float* grad_attr);
+int cgrt_interpolate_hits_grad_repro_device(CgrtScene* scene, const CgrtRay* d_rays, const CgrtHit* d_hits, uint64_t n,
+                                            const float* d_grad_out, uint32_t channels, float* d_grad_attr, void* d_workspace,
+                                            uint64_t workspace_bytes, void* stream);
+int cgrt_surface_views_grad_repro_device(CgrtScene* scene, const CgrtCamera* cams, uint32_t nviews, int W, int H, const float* d_depth,
+                                         const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels, int chw,
+                                         float* d_grad_attr, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int cgrt_surface_raycams_grad_repro_device(CgrtScene* scene, const CgrtRayCamera* cams, uint32_t nviews, int W, int H,
+                                           const float* d_depth, const uint32_t* d_prim_id, const float* d_grad_out, uint32_t channels,
+                                           int chw, float* d_grad_attr, void* d_workspace, uint64_t workspace_bytes, void* stream);
 
 /* Closest-point queries: "which point of the surface is nearest to p?" for a list of points -- the other question
  * put to a triangle BVH (distance fields, snapping and registration of point clouds, collision margins, carrying per-vertex data to
