@@ -86,6 +86,20 @@ def _sample_params(seed: int = 0, first: int = 0, strata: int = 0) -> SamplePara
     return p
 
 
+class PoissonParams(C.Structure):
+    """include/cgrt.h CgrtPoissonParams."""
+    _fields_ = [("min_dist2", C.c_float), ("seed", C.c_uint64), ("priority", C.c_void_p)]
+
+
+def _poisson_params(min_dist2: float, seed: int = 0, priority_ptr: int = 0) -> PoissonParams:
+    """CgrtPoissonParams; seed a 64-bit unsigned value (ValueError otherwise), priority a raw address or 0; the library checks min_dist2."""
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed must be in 0 .. 2^64 - 1")
+    p = PoissonParams()
+    p.min_dist2, p.seed, p.priority = float(min_dist2), int(seed), (int(priority_ptr) or None)
+    return p
+
+
 def _sdf_params(max_dist2: float = float("inf"), directions=None) -> SdfParams:
     """CgrtSdfParams from max_dist2 and the parity directions (None: the library's defaults, INSIDE_DIRECTIONS).  ValueError for what
     the structure cannot hold (no directions, more than 7, not (k, 3)); the library checks the values."""
@@ -365,7 +379,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -522,6 +536,11 @@ def lib() -> C.CDLL:
     L.cgrt_debug_get_winding_tree.argtypes = [vp, vp, vp, C.POINTER(u32), vp]
     L.cgrt_sample_surface.argtypes = [vp, u64, C.POINTER(SampleParams), vp, vp, u32, vp]
     L.cgrt_sample_surface_device.argtypes = [vp, u64, C.POINTER(SampleParams), vp, vp, u32, vp, vp]
+    for f in (L.cgrt_poisson_disk, L.cgrt_poisson_disk_brute):
+        f.argtypes = [vp, vp, u64, C.POINTER(PoissonParams), vp, C.POINTER(u64)]
+    L.cgrt_poisson_disk_device.argtypes = [vp, vp, u64, C.POINTER(PoissonParams), vp, C.POINTER(u64), vp, u64, vp]
+    L.cgrt_poisson_disk_workspace.argtypes = [vp, u64, C.POINTER(u64)]
+    L.cgrt_debug_poisson_work.argtypes = [vp, vp, u64, C.POINTER(PoissonParams), vp]
     L.cgrt_triangle_areas.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.cgrt_debug_get_sample_table.argtypes = [vp, vp, C.POINTER(u32)]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
@@ -2722,6 +2741,109 @@ class Scene:
         if rows is not None:
             res["attr"] = rows
         return res
+
+    # ---- Poisson-disk sets (include/cgrt.h cgrt_poisson_disk*) ----
+    @staticmethod
+    def _priority_array(priority, n: int):
+        if priority is None:
+            return None
+        a = np.asarray(priority)
+        if a.shape != (n,) or a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF)):
+            raise ValueError(f"priority must be ({n},) integers in 0 .. 2^32 - 1")
+        return np.ascontiguousarray(a, np.uint32)
+
+    def _poisson_host(self, f, points, min_dist2: float, seed: int, priority) -> np.ndarray:
+        p = _f32(points, (-1, 3))
+        pr = self._priority_array(priority, len(p))
+        prm = _poisson_params(min_dist2, seed, pr.ctypes.data if pr is not None and len(pr) else 0)
+        keep = np.zeros(len(p), np.uint8)
+        kept = C.c_uint64(0)
+        _check(f(self._h, _ptr(p) if len(p) else None, len(p), C.byref(prm), _ptr(keep) if len(p) else None, C.byref(kept)))
+        mask = keep.view(np.bool_)
+        if int(kept.value) != int(mask.sum()):
+            raise RuntimeError(f"the library reports {int(kept.value)} kept points, its flags hold {int(mask.sum())}")
+        return mask
+
+    def poisson_disk(self, points, min_dist2: float, seed: int = 0, priority=None) -> np.ndarray:
+        """cgrt_poisson_disk: of the points ((n, 3) float32), the (n,) bool mask of the lexicographically first maximal subset in which no
+        two points have a squared distance below min_dist2.  Point i goes before j iff (P_i, i) < (P_j, j), P the caller's priority
+        ((n,) uint32) or Philox word 3 of index i under `seed`.  A non-finite point is never kept; min_dist2 NaN or <= 0 keeps every
+        finite point.  Defined to the last bit (include/cgrt.h); blocks."""
+        return self._poisson_host(lib().cgrt_poisson_disk, points, min_dist2, seed, priority)
+
+    def poisson_disk_brute(self, points, min_dist2: float, seed: int = 0, priority=None) -> np.ndarray:
+        """cgrt_poisson_disk_brute: poisson_disk without the grid, every pair tested in every round (validation; the same bytes)."""
+        return self._poisson_host(lib().cgrt_poisson_disk_brute, points, min_dist2, seed, priority)
+
+    def debug_poisson_work(self, points, min_dist2: float, seed: int = 0, priority=None) -> dict:
+        """cgrt_debug_poisson_work (a counted run): {'rounds', 'pair_tests', 'buckets_used', 'buckets', 'build_ns', 'rounds_ns'}."""
+        p = _f32(points, (-1, 3))
+        pr = self._priority_array(priority, len(p))
+        prm = _poisson_params(min_dist2, seed, pr.ctypes.data if pr is not None and len(pr) else 0)
+        w = np.zeros(6, np.uint64)
+        _check(lib().cgrt_debug_poisson_work(self._h, _ptr(p) if len(p) else None, len(p), C.byref(prm), _ptr(w)))
+        return dict(zip(("rounds", "pair_tests", "buckets_used", "buckets", "build_ns", "rounds_ns"), (int(x) for x in w)))
+
+    def poisson_disk_workspace(self, n: int) -> int:
+        """cgrt_poisson_disk_workspace: the bytes of device memory a poisson_disk_device call with n points needs."""
+        b = C.c_uint64(0)
+        _check(lib().cgrt_poisson_disk_workspace(self._h, int(n), C.byref(b)))
+        return int(b.value)
+
+    def poisson_disk_device(self, d_points_ptr: int, n: int, min_dist2: float, d_keep_ptr: int, d_workspace_ptr: int, workspace_bytes: int,
+                            seed: int = 0, d_priority_ptr: int = 0, stream: int = 0) -> int:
+        """cgrt_poisson_disk_device: n points (3 floats each) at d_points_ptr -> n flag bytes at d_keep_ptr, with the caller's workspace
+        (poisson_disk_workspace(n) bytes of device memory, 8-byte aligned, this call's alone).  Ordered on the hipStream_t `stream`;
+        returns the number of kept points once the flags are complete.  Raw integers."""
+        prm = _poisson_params(min_dist2, seed, d_priority_ptr)
+        kept = C.c_uint64(0)
+        _check(lib().cgrt_poisson_disk_device(self._h, _vp(d_points_ptr), int(n), C.byref(prm), _vp(d_keep_ptr), C.byref(kept),
+                                              _vp(d_workspace_ptr), int(workspace_bytes), _vp(stream)))
+        return int(kept.value)
+
+    def poisson_disk_tensor(self, points, min_dist2: float, seed: int = 0, priority=None, out=None, workspace=None, stream=None):
+        """poisson_disk on torch tensors: points (n, 3) float32 on cuda:<device> -> an (n,) torch.bool mask (`out`, which may also be
+        torch.uint8, or a new tensor).  priority: None, or an (n,) torch.int32 / torch.uint32 tensor whose words are read as unsigned.
+        workspace: None (allocated here on the call's stream), or a torch.uint8 tensor of at least poisson_disk_workspace(n) bytes,
+        8-byte aligned.  Ordered on `stream` (default: torch.cuda.current_stream()); returns when the mask is complete."""
+        import torch
+
+        n = self._points_tensor(points)
+        if out is not None:
+            self._device_tensor(out, "out", (torch.bool, torch.uint8), (n,))
+        if priority is not None:
+            self._device_tensor(priority, "priority", (torch.int32, getattr(torch, "uint32", torch.int32)), (n,))
+        nbytes = self.poisson_disk_workspace(n)
+        if workspace is not None:
+            self._device_tensor(workspace, "workspace", (torch.uint8,))
+            if workspace.numel() < nbytes or workspace.data_ptr() % 8:
+                raise ValueError(f"workspace must hold {nbytes} bytes and be 8-byte aligned")
+        _, stream = self._torch_stream(stream)
+        if workspace is None and n:
+            with torch.cuda.stream(stream):
+                workspace = torch.empty((nbytes,), dtype=torch.uint8, device=stream.device)
+        return self._tensor_call(out, (n,), torch.bool, stream,
+                                 lambda o, s: self.poisson_disk_device(points.data_ptr(), n, min_dist2, o.data_ptr(), workspace.data_ptr(),
+                                                                       workspace.numel(), seed=seed,
+                                                                       d_priority_ptr=priority.data_ptr() if priority is not None else 0,
+                                                                       stream=s))
+
+    def sample_surface_poisson_tensor(self, candidates: int, min_dist2: float, seed: int = 0, strata: bool = True, attr=None):
+        """Blue-noise surface samples: sample_surface_tensor(candidates, seed, strata = candidates or 0), its points filtered by
+        poisson_disk_tensor under the same seed.  Returns sample_surface_tensor's keys restricted to the kept rows, in ascending
+        candidate index, plus 'index' ((kept,) int64, the candidate indices): a function of (scene, candidates, min_dist2, seed,
+        strata) alone."""
+        import torch
+
+        candidates = int(candidates)
+        res = self.sample_surface_tensor(candidates, seed=seed, strata=candidates if strata else 0, attr=attr)
+        _, stream = self._torch_stream(None)
+        with torch.cuda.stream(stream):
+            mask = self.poisson_disk_tensor(res["point"].contiguous(), min_dist2, seed=seed, stream=stream)
+            index = torch.nonzero(mask).reshape(-1)
+            out = {k: v[index] for k, v in res.items()}
+        out["index"] = index
+        return out
 
     def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream, reproducible=False):
         import torch

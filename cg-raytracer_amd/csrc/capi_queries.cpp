@@ -1,5 +1,5 @@
 // capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
-// closest points, crossings, neighbours, signed distance, winding numbers, surface samples.  None of them touches the scene's frame state (workspace, prediction, hints).
+// closest points, crossings, neighbours, signed distance, winding numbers, surface samples, Poisson-disk sets.  None of them touches the scene's frame state (workspace, prediction, hints).
 // Every family is ONE body for its host-pointer and its device-pointer entries, written with a QueryCall (capi_internal.h): the argument
 // checks in the order include/cgrt.h states (`device`: the pointers' alignment too), the host-only scene, the empty call, then begin,
 // in / out per array, the launch on the call's stream, finish.  The exported entries are one-line forwarders.
@@ -969,6 +969,90 @@ int cgrt_debug_get_sample_table(CgrtScene* s, uint32_t* thresholds, uint32_t* la
     if (thresholds && !T.thresholds.empty()) memcpy(thresholds, T.thresholds.data(), T.thresholds.size() * sizeof(uint32_t));
     if (last) *last = T.last;
     return CGRT_OK;
+}
+
+// ---- Poisson-disk sets (include/cgrt.h cgrt_poisson_disk*): the points of a list that keep a minimum spacing, the
+// first maximal independent set in a seeded (or the caller's) order.  The scene only names the device and lends the call lane; no frame
+// state is read or written; the checks come in the order include/cgrt.h states, all before any device work.
+namespace {
+// the device form's workspace as the caller gave it
+struct PoissonWorkspace {
+    void* d;
+    uint64_t bytes;
+};
+// slots: 0 the points, 1 the flags, 2 the priorities, 3 the workspace (host form: the lane's) and the pinned header both forms read back.
+// how: 0 hashed grid, 1 brute force, 2 counted grid (both host form only; 2: `work` in the place of keep and kept)
+int poisson_query(CgrtScene* s, bool device, const float* points, uint64_t n, const CgrtPoissonParams* params, uint8_t* keep, uint64_t* kept,
+                  const PoissonWorkspace* ws, int how, uint64_t* work, void* stream) {
+    if (!s || !params) return fail(CGRT_E_ARG, "scene or params is NULL");
+    if (n && (!points || (how == 2 ? !work : !keep))) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
+    if (params->min_dist2 == INFINITY) return fail(CGRT_E_ARG, "min_dist2 must not be +inf");
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)params->priority % 4)) return fail(CGRT_E_ARG, "device pointers must be 4-byte aligned");
+    if (ws && n) {
+        if (!ws->d) return fail(CGRT_E_ARG, "NULL argument");
+        if ((uintptr_t)ws->d % 8) return fail(CGRT_E_ARG, "d_workspace must be 8-byte aligned");
+        if (ws->bytes < poisson_workspace_bytes(n)) return fail(CGRT_E_ARG, "workspace_bytes is below cgrt_poisson_disk_workspace");
+    }
+    NEED_DEVICE(s);
+    if (n == 0) {
+        if (kept) *kept = 0;
+        if (work) memset(work, 0, 6 * sizeof(uint64_t));
+        return CGRT_OK;
+    }
+    QueryCall c(s, device, stream);
+    void *dp = nullptr, *dk = nullptr, *dprio = nullptr, *dws = nullptr, *pin = nullptr;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, points, n * 12, "d_points", &dp));
+    CGRT_TRY(c.out(1, keep, how == 2 ? 0 : n, "d_keep", &dk));
+    CGRT_TRY(c.in(2, params->priority, params->priority ? n * 4 : 0, "d_priority", &dprio));
+    if (ws) {
+        dws = ws->d;
+        CGRT_TRY(check_device_span(s, dws, poisson_workspace_bytes(n), "d_workspace"));
+    } else {
+        HIP_TRY(c.c.scratch(3, poisson_workspace_bytes(n), &dws));
+        if (how == 2) HIP_TRY(c.c.scratch(1, n, &dk));
+    }
+    if (device) CGRT_TRY(c.c.g.acquire());  // (a lane for its pinned words only: the work runs on the caller's stream)
+    HIP_TRY(c.c.g.pin(3, 64, &pin));
+    PoissonCall Q{};
+    Q.points = static_cast<const float*>(dp);
+    Q.n = (uint32_t)n;
+    Q.min_dist2 = params->min_dist2;
+    Q.seed = params->seed;
+    Q.priority = params->priority ? static_cast<const uint32_t*>(dprio) : nullptr;
+    Q.keep = static_cast<uint8_t*>(dk);
+    Q.workspace = dws;
+    PoissonWork W{};
+    HIP_TRY(run_poisson_disk(Q, how == 1, static_cast<uint32_t*>(pin), c.stream(), kept, how == 2 ? &W : nullptr));
+    if (how == 2) {
+        const uint64_t out6[6] = {W.rounds, W.pair_tests, W.buckets_used, W.buckets, W.build_ns, W.rounds_ns};
+        memcpy(work, out6, sizeof(out6));
+        return CGRT_OK;
+    }
+    return c.finish();
+}
+}  // namespace
+
+int cgrt_poisson_disk(CgrtScene* s, const float* points, uint64_t n, const CgrtPoissonParams* params, uint8_t* keep, uint64_t* kept) {
+    return poisson_query(s, false, points, n, params, keep, kept, nullptr, 0, nullptr, nullptr);
+}
+int cgrt_poisson_disk_device(CgrtScene* s, const float* d_points, uint64_t n, const CgrtPoissonParams* params, uint8_t* d_keep, uint64_t* kept,
+                             void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    const PoissonWorkspace ws{d_workspace, workspace_bytes};
+    return poisson_query(s, true, d_points, n, params, d_keep, kept, &ws, 0, nullptr, stream);
+}
+int cgrt_poisson_disk_workspace(CgrtScene* s, uint64_t n, uint64_t* bytes) {
+    if (!s || !bytes) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > 0x7fffffffull) return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
+    *bytes = poisson_workspace_bytes(n);
+    return CGRT_OK;
+}
+int cgrt_poisson_disk_brute(CgrtScene* s, const float* points, uint64_t n, const CgrtPoissonParams* params, uint8_t* keep, uint64_t* kept) {
+    return poisson_query(s, false, points, n, params, keep, kept, nullptr, 1, nullptr, nullptr);
+}
+int cgrt_debug_poisson_work(CgrtScene* s, const float* points, uint64_t n, const CgrtPoissonParams* params, uint64_t* out6) {
+    return poisson_query(s, false, points, n, params, nullptr, nullptr, nullptr, 2, out6, nullptr);
 }
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 // barycentric weights; the only f32 operations are the three exact conversions of the weights and the mix of the vertices.
 //
 // One kernel, k_sample_surface<STRATIFIED>.  Lane l of a wave owns sample l of the wave's 64 consecutive samples:
-//   * Philox4x32-10 of counter {j, 0, 0} under key {seed}: ten rounds of two 32 x 32 -> 64 multiplies (v_mul_lo_u32 + v_mul_hi_u32);
+//   * Philox4x32-10 (philox_device.h) of counter {j, 0, 0} under key {seed}: ten rounds of two 32 x 32 -> 64 multiplies (v_mul_lo_u32 +
+//     v_mul_hi_u32);
 //   * the position word x = w0, or (STRATIFIED) floor((j 2^32 + w0) / strata): the one 64-bit division of the kernel;
 //   * prim = the number of thresholds T[0 .. last) that are <= x, by a search of `steps` probes whose trip count is the launch's, so a
 //     wave never diverges in it and nothing is indexed dynamically (no stack, no scratch); a probe beyond `last` reads entry last - 1
@@ -15,31 +16,13 @@
 #include <hip/hip_runtime.h>
 
 #include "cgrt_math.h"
+#include "philox_device.h"
 #include "surface_device.h"
 #include "surface_sample_kernels.h"
 
 namespace cgrt {
 
 namespace {
-
-// Philox4x32-10 (Salmon et al., Random123): words 0..2 of the output for counter {c0, c1, 0, 0} and key {k0, k1}
-__device__ __forceinline__ void philox3(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t& w0, uint32_t& w1, uint32_t& w2) {
-    uint32_t c2 = 0u, c3 = 0u;
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    w0 = c0;
-    w1 = c1;
-    w2 = c2;
-}
 
 template <bool STRATIFIED>
 __global__ __launch_bounds__(256) void k_sample_surface(const SampleArgs A) {
@@ -53,8 +36,8 @@ __global__ __launch_bounds__(256) void k_sample_surface(const SampleArgs A) {
         uint32_t mesh = 0xffffffffu, prim = 0xffffffffu;
         if (A.last != 0xffffffffu) {
             const unsigned long long j = A.first + i;
-            uint32_t w0, w1, w2;
-            philox3((uint32_t)j, (uint32_t)(j >> 32), (uint32_t)A.seed, (uint32_t)(A.seed >> 32), w0, w1, w2);
+            uint32_t w0, w1, w2, w3;  // (w3 is the Poisson-disk order's word, poisson_kernels.hip: unused here)
+            philox4x32_10((uint32_t)j, (uint32_t)(j >> 32), (uint32_t)A.seed, (uint32_t)(A.seed >> 32), w0, w1, w2, w3);
             uint32_t x = w0;
             if (STRATIFIED) x = (uint32_t)(((j << 32) | (unsigned long long)w0) / A.strata);  // (j < strata <= 2^32 - 1: below 2^32)
             uint32_t count = 0u;

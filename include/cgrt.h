@@ -1256,8 +1256,9 @@ int cgrt_debug_get_winding_tree(CgrtScene* scene, float* clusters, uint32_t* lev
  * and first + n > strata; first + n overflows 64 bits; (device form) a pointer not 4-byte aligned.  Then a host-only scene:
  * CGRT_E_NO_DEVICE.  n == 0 succeeds and touches nothing.  Device form: then d_out (n * 32 bytes), d_attr (nverts * channels * 4) and
  * d_out_attr (n * channels * 4) checked as device memory of the scene's device.
- * Not offered: gradients through the samples; spheres; a restriction to some meshes or materials; weights other than area; blue-noise
- * or Poisson-disk sets; grid and enqueued-ticket forms (the device form never blocks); the C++ host mirror. */
+ * Not offered: gradients through the samples; spheres; a restriction to some meshes or materials; weights other than area (blue-noise
+ * sets: "Poisson-disk sets" below filters these samples); grid and enqueued-ticket forms (the device form never blocks); the C++ host
+ * mirror. */
 typedef struct CgrtSurfaceSample {
     float point[3];
     uint32_t mesh_id; /* 0xffffffff in an empty scene */
@@ -1275,6 +1276,54 @@ int cgrt_sample_surface_device(CgrtScene* scene, uint64_t n, const CgrtSamplePar
                                uint32_t channels, float* d_out_attr, void* stream);
 int cgrt_triangle_areas(CgrtScene* scene, float* areas, double* total);
 int cgrt_debug_get_sample_table(CgrtScene* scene, uint32_t* thresholds, uint32_t* last);
+
+/* Poisson-disk sets: of n points, a subset in which no two are closer than a radius and to which none can be
+ * added -- blue-noise samples when the points are cgrt_sample_surface's.  The result is defined to the last bit: a pure function of
+ * (points, min_dist2, seed or priority), whatever the grid, the launch shape, the stream, the thread or the run.  The scene names the
+ * device and lends its call lanes; its geometry is not read.  All f32 arithmetic is IEEE, every operation rounded on its own.
+ * Inputs.  points: n x 3 f32.  params (CgrtPoissonParams, not NULL): min_dist2 (f32), seed (u64), priority (NULL, or n u32: host memory
+ * in the host form, device memory in the device form).
+ * Finite.  Point i is finite iff its three coordinates are.  A point that is not is never kept and conflicts with nobody.
+ * Order.  P_i = priority[i] if a priority is given; else word w3 of Philox4x32-10 with the constants of "Surface sampling" above,
+ * counter {lo32(i), hi32(i), 0, 0}, key {lo32(seed), hi32(seed)} -- the word the sampler leaves unused, so the order does not depend
+ * on where a sample lies even under the sampler's own seed.  (Known answer: w3 = 9b00dbd8 for the zero counter and key.)  i comes
+ * before j iff (P_i, i) < (P_j, j) lexicographically.
+ * Conflict.  dx = fl(x_i - x_j), dy and dz likewise; d2 = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)), nothing contracted; the value is the
+ * same for (i, j) and (j, i).  i and j conflict iff both are finite, i != j and d2 < min_dist2, strictly.  A d2 that overflows to +inf
+ * is never a conflict.  min_dist2 NaN or <= 0: nothing conflicts, every finite point is kept.  min_dist2 == +inf: CGRT_E_ARG.
+ * Result.  Going through the points in the order, i is kept iff it is finite and no point kept before it conflicts with it: the
+ * lexicographically first maximal independent set of the conflict graph, which is unique.  No two kept points conflict, and every finite
+ * point that is not kept conflicts with a kept point that comes before it.
+ * Outputs.  keep: n bytes, each 1 or 0.  *kept (host memory in both forms; NULL: not wanted): the number of ones.
+ * Both forms BLOCK.  The work is a few passes that build a hashed grid and then rounds whose number depends on the data: each round
+ * decides every undecided point all of whose earlier conflicting points are decided.  With the Philox order the number of rounds
+ * grows like log n; with a caller priority it can reach n (points on a line, priority = index).  The host form (host pointers) runs on a
+ * call lane like cgrt_closest_points and allocates its own workspace: any number of threads may call at once.  The device form is
+ * ordered on `stream` (NULL = default stream) behind what it held, reads one 64-byte header back from the device into pinned memory
+ * per batch of rounds, and returns when keep[] is complete.  An enqueued form is not offered.
+ * Workspace (device form).  cgrt_poisson_disk_workspace reports the bytes a call with n points needs (about 40 per point): caller-owned
+ * device memory, 8-byte aligned, contents need no initialisation, not shared between calls in flight.
+ * cgrt_poisson_disk_brute: the same bytes without a grid -- every pair is tested in every round; the yardstick.  Host form only.
+ * cgrt_debug_poisson_work (host form, a counted run, no flags): out6 = {rounds that had undecided points, pair tests, buckets in use,
+ * buckets, nanoseconds of the grid build, nanoseconds of the rounds (both on the host's clock around a wait for the stream)}.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene or params; NULL points or keep with n > 0; n > 0x7fffffff;
+ * min_dist2 == +inf; (device form) d_points or priority not 4-byte aligned; (device form, n > 0) d_workspace NULL, not 8-byte aligned,
+ * or workspace_bytes below cgrt_poisson_disk_workspace.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds, writes *kept = 0
+ * and touches nothing else.  Device form: then d_points (n * 12 bytes), d_keep (n), priority (n * 4) and d_workspace checked as device
+ * memory of the scene's device.  Neither form reads or writes the prediction record, the frame hints, the layout or any frame state.
+ * Not offered: per-point radii; geodesic distance; weighted elimination beyond the caller priority; progressive or multi-class sets; an
+ * enqueued form; the C++ host mirror. */
+typedef struct CgrtPoissonParams {
+    float min_dist2;          /* squared minimum distance; NaN or <= 0: nothing conflicts; +inf -> CGRT_E_ARG */
+    uint64_t seed;            /* the Philox key of the order (ignored with a priority) */
+    const uint32_t* priority; /* NULL, or n words: smaller goes first, ties by index */
+} CgrtPoissonParams;
+int cgrt_poisson_disk(CgrtScene* scene, const float* points, uint64_t n, const CgrtPoissonParams* params, uint8_t* keep, uint64_t* kept);
+int cgrt_poisson_disk_device(CgrtScene* scene, const float* d_points, uint64_t n, const CgrtPoissonParams* params, uint8_t* d_keep,
+                             uint64_t* kept, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int cgrt_poisson_disk_workspace(CgrtScene* scene, uint64_t n, uint64_t* bytes);
+int cgrt_poisson_disk_brute(CgrtScene* scene, const float* points, uint64_t n, const CgrtPoissonParams* params, uint8_t* keep, uint64_t* kept);
+int cgrt_debug_poisson_work(CgrtScene* scene, const float* points, uint64_t n, const CgrtPoissonParams* params, uint64_t* out6);
 
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
