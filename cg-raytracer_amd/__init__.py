@@ -42,6 +42,10 @@ assert NEIGHBOR_DTYPE.itemsize == 8
 # include/cgrt.h CgrtSurfaceSample: one surface sample (32 bytes); point, prim_id and bary at CLOSEST_DTYPE's offsets
 SURFACE_SAMPLE_DTYPE = np.dtype([("point", np.float32, 3), ("mesh_id", np.uint32), ("prim_id", np.uint32), ("bary", np.float32, 3)])
 assert SURFACE_SAMPLE_DTYPE.itemsize == 32
+# include/cgrt.h CgrtPointNeighbor: one data point within a query point's radius (8 bytes); an unused entry of a slot is {+inf, NO_PRIM}
+POINT_NEIGHBOR_DTYPE = np.dtype([("dist2", np.float32), ("index", np.uint32)])
+assert POINT_NEIGHBOR_DTYPE.itemsize == 8
+POINTS_SKIP_SAME_INDEX = 1  # include/cgrt.h CGRT_POINTS_SKIP_SAME_INDEX
 _SLOT_RECORDS = {"crossings": CROSSING_DTYPE, "neighbors": NEIGHBOR_DTYPE}  # the slot-list entries (Scene._slots_*) by the name in their symbols
 # Scene.inside_tensor's default directions: three fixed generic ones (no component zero, none along an axis, a face diagonal or a space
 # diagonal, pairwise far from parallel), so that a ray through an edge or a vertex of an axis-aligned or diagonal-symmetric mesh is the
@@ -98,6 +102,23 @@ def _poisson_params(min_dist2: float, seed: int = 0, priority_ptr: int = 0) -> P
     p = PoissonParams()
     p.min_dist2, p.seed, p.priority = float(min_dist2), int(seed), (int(priority_ptr) or None)
     return p
+
+
+class PointNeighbor(C.Structure):
+    """include/cgrt.h CgrtPointNeighbor."""
+    _fields_ = [("dist2", C.c_float), ("index", C.c_uint32)]
+
+
+class PointQuery(C.Structure):
+    """include/cgrt.h CgrtPointQuery."""
+    _fields_ = [("radius2", C.c_void_p), ("max_dist2", C.c_float), ("flags", C.c_uint32)]
+
+
+def _point_query(radius2_ptr: int = 0, max_dist2: float = float("inf"), skip_same_index: bool = False) -> PointQuery:
+    """CgrtPointQuery; radius2 a raw address or 0; the library checks max_dist2."""
+    q = PointQuery()
+    q.radius2, q.max_dist2, q.flags = (int(radius2_ptr) or None), float(max_dist2), (POINTS_SKIP_SAME_INDEX if skip_same_index else 0)
+    return q
 
 
 def _sdf_params(max_dist2: float = float("inf"), directions=None) -> SdfParams:
@@ -379,7 +400,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_point_grid_workspace", "cgrt_point_grid_build_device", "cgrt_count_point_neighbors", "cgrt_count_point_neighbors_device", "cgrt_list_point_neighbors", "cgrt_list_point_neighbors_device", "cgrt_list_point_neighbors_brute", "cgrt_debug_point_neighbor_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -541,6 +562,15 @@ def lib() -> C.CDLL:
     L.cgrt_poisson_disk_device.argtypes = [vp, vp, u64, C.POINTER(PoissonParams), vp, C.POINTER(u64), vp, u64, vp]
     L.cgrt_poisson_disk_workspace.argtypes = [vp, u64, C.POINTER(u64)]
     L.cgrt_debug_poisson_work.argtypes = [vp, vp, u64, C.POINTER(PoissonParams), vp]
+    pq = C.POINTER(PointQuery)
+    L.cgrt_point_grid_workspace.argtypes = [vp, u64, C.POINTER(u64)]
+    L.cgrt_point_grid_build_device.argtypes = [vp, vp, u64, C.c_float, vp, u64, vp]
+    L.cgrt_count_point_neighbors_device.argtypes = [vp, vp, u64, vp, u64, pq, vp, vp]
+    L.cgrt_list_point_neighbors_device.argtypes = [vp, vp, u64, vp, u64, pq, vp, u32, vp, u64, vp, vp]
+    L.cgrt_count_point_neighbors.argtypes = [vp, vp, u64, C.c_float, vp, u64, pq, vp]
+    L.cgrt_list_point_neighbors.argtypes = [vp, vp, u64, C.c_float, vp, u64, pq, vp, u32, vp, u64, vp]
+    L.cgrt_list_point_neighbors_brute.argtypes = [vp, vp, u64, vp, u64, pq, vp, u32, vp, u64, vp]
+    L.cgrt_debug_point_neighbor_work.argtypes = [vp, vp, u64, C.c_float, vp, u64, pq, u32, vp]
     L.cgrt_triangle_areas.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.cgrt_debug_get_sample_table.argtypes = [vp, vp, C.POINTER(u32)]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
@@ -2845,6 +2875,138 @@ class Scene:
         out["index"] = index
         return out
 
+    # ---- point-set neighbours (include/cgrt.h cgrt_point_grid_*, cgrt_count_point_neighbors*, cgrt_list_point_neighbors*) ----
+    @staticmethod
+    def _point_cloud_args(data, points, radius2, max_dist2, skip_same_index):
+        """(data (m, 3), points (n, 3), the radii or None -- kept alive by the caller --, the CgrtPointQuery)."""
+        d, p = _f32(data, (-1, 3)), _f32(points, (-1, 3))
+        r = None if radius2 is None else _f32(radius2, (-1,))
+        if r is not None and len(r) != len(p):
+            raise ValueError("radius2 must hold one squared radius per point")
+        return d, p, r, _point_query(r.ctypes.data if r is not None and len(r) else 0, max_dist2, skip_same_index)
+
+    def _point_list_host(self, d, cell, p, q, offsets, k: int, want_counts: bool = True, brute: bool = False):
+        """One cgrt_list_point_neighbors(_brute) call into slots from `offsets` or of k records each: (records, counts or None)."""
+        n = len(p)
+        cap = int(offsets[-1]) if offsets is not None else n * k
+        out = np.zeros(cap, POINT_NEIGHBOR_DTYPE)
+        counts = np.zeros(n, np.uint32) if want_counts else None
+        tail = (_ptr(p), n, C.byref(q), _ptr(offsets), int(k), _ptr(out), cap, _ptr(counts))
+        if brute:
+            _check(lib().cgrt_list_point_neighbors_brute(self._h, _ptr(d), len(d), *tail))
+        else:
+            _check(lib().cgrt_list_point_neighbors(self._h, _ptr(d), len(d), float(cell), *tail))
+        return out, counts
+
+    def _point_list_full(self, d, cell, p, q, counts, brute: bool = False):
+        off = np.zeros(len(p) + 1, np.uint64)
+        np.cumsum(counts, dtype=np.uint64, out=off[1:])
+        out, _ = self._point_list_host(d, cell, p, q, off, 0, want_counts=False, brute=brute)
+        return off.astype(np.int64), out
+
+    def count_point_neighbors(self, data, cell: float, points, radius2=None, max_dist2: float = float("inf"),
+                              skip_same_index: bool = False) -> np.ndarray:
+        """cgrt_count_point_neighbors: for every query point ((n, 3) float32) the number of points of `data` ((m, 3) float32) whose d2 is
+        <= its squared radius -- radius2[i] ((n,) float32; NaN or negative: no neighbours), or max_dist2 for every query.  cell: the
+        wanted cell edge of the call's own grid (about the radius; no result depends on it).  skip_same_index: data point i is not a
+        neighbour of query i.  (n,) uint32."""
+        d, p, r, q = self._point_cloud_args(data, points, radius2, max_dist2, skip_same_index)
+        counts = np.zeros(len(p), np.uint32)
+        _check(lib().cgrt_count_point_neighbors(self._h, _ptr(d), len(d), float(cell), _ptr(p), len(p), C.byref(q), _ptr(counts)))
+        return counts
+
+    def list_point_neighbors(self, data, cell: float, points, radius2=None, max_dist2: float = float("inf"), skip_same_index: bool = False,
+                             offsets=None, want_counts: bool = True):
+        """Every neighbour of every query point among `data`, in order (by d2, equal d2 by index): cgrt_count_point_neighbors, the
+        exclusive prefix sums, then cgrt_list_point_neighbors.  Returns (offsets, records): offsets (n + 1,) int64, query i's neighbours
+        are records[offsets[i]:offsets[i + 1]] (POINT_NEIGHBOR_DTYPE {dist2, index}).
+        With offsets ((n + 1,) slot boundaries chosen by the caller) one cgrt_list_point_neighbors call: (records (offsets[-1],),
+        counts: the full numbers of neighbours -- or None with want_counts=False), as list_neighbors."""
+        d, p, r, q = self._point_cloud_args(data, points, radius2, max_dist2, skip_same_index)
+        if offsets is not None:
+            return self._point_list_host(d, cell, p, q, np.ascontiguousarray(offsets, np.uint64), 0, want_counts)
+        counts = np.zeros(len(p), np.uint32)
+        _check(lib().cgrt_count_point_neighbors(self._h, _ptr(d), len(d), float(cell), _ptr(p), len(p), C.byref(q), _ptr(counts)))
+        return self._point_list_full(d, cell, p, q, counts)
+
+    def nearest_points(self, data, cell: float, points, k: int, radius2=None, max_dist2: float = float("inf"), skip_same_index: bool = False,
+                       want_counts: bool = False):
+        """The k nearest points of `data` of every query point within its squared radius: (n, k) POINT_NEIGHBOR_DTYPE records in order,
+        unused entries {+inf, NO_PRIM}.  With want_counts=True returns (records, counts): counts (n,) uint32, the full numbers of
+        neighbours."""
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        d, p, r, q = self._point_cloud_args(data, points, radius2, max_dist2, skip_same_index)
+        out, counts = self._point_list_host(d, cell, p, q, None, k, want_counts)
+        out = out.reshape(len(p), k)
+        return (out, counts) if want_counts else out
+
+    def list_point_neighbors_brute(self, data, points, radius2=None, max_dist2: float = float("inf"), skip_same_index: bool = False,
+                                   offsets=None, k: int = 0):
+        """cgrt_list_point_neighbors_brute: the list by testing every data point in turn, no grid (validation; the same bytes).  With
+        neither offsets nor k the full list, as list_point_neighbors returns it: (offsets, records); with offsets ((n + 1,) slot
+        boundaries) or k (k records per query): (records, counts)."""
+        d, p, r, q = self._point_cloud_args(data, points, radius2, max_dist2, skip_same_index)
+        if offsets is None and not k:
+            _, c = self._point_list_host(d, 0.0, p, q, None, 1, brute=True)  # k = 1 only to obtain the counts
+            return self._point_list_full(d, 0.0, p, q, c, brute=True)
+        off = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
+        out, counts = self._point_list_host(d, 0.0, p, q, off, k, brute=True)
+        return (out.reshape(len(p), k) if off is None else out), counts
+
+    def debug_point_neighbor_work(self, data, cell: float, points, radius2=None, max_dist2: float = float("inf"), skip_same_index: bool = False,
+                                  k: int = 0) -> dict:
+        """cgrt_debug_point_neighbor_work (a counted launch): {'cells', 'entries', 'foreign', 'd2_evals', 'linear', 'buckets_used'}, summed
+        over the queries, of count_point_neighbors' search (k = 0) or of nearest_points' (k > 0: k records per query, no counts)."""
+        d, p, r, q = self._point_cloud_args(data, points, radius2, max_dist2, skip_same_index)
+        w = np.zeros(6, np.uint64)
+        _check(lib().cgrt_debug_point_neighbor_work(self._h, _ptr(d), len(d), float(cell), _ptr(p), len(p), C.byref(q), int(k), _ptr(w)))
+        return dict(zip(("cells", "entries", "foreign", "d2_evals", "linear", "buckets_used"), (int(x) for x in w)))
+
+    def point_grid_workspace(self, m: int) -> int:
+        """cgrt_point_grid_workspace: the bytes of device memory a grid over m points needs."""
+        b = C.c_uint64(0)
+        _check(lib().cgrt_point_grid_workspace(self._h, int(m), C.byref(b)))
+        return int(b.value)
+
+    def point_grid_build_device(self, d_data_ptr: int, m: int, cell: float, d_grid_ptr: int, grid_bytes: int, stream: int = 0) -> None:
+        """cgrt_point_grid_build_device: enqueues the build of the grid over m points (3 floats each) at d_data_ptr into the caller's
+        memory at d_grid_ptr (point_grid_workspace(m) bytes, 8-byte aligned) on the hipStream_t `stream`.  Raw integers."""
+        _check(lib().cgrt_point_grid_build_device(self._h, _vp(d_data_ptr), int(m), float(cell), _vp(d_grid_ptr), int(grid_bytes), _vp(stream)))
+
+    def count_point_neighbors_device(self, d_grid_ptr: int, grid_bytes: int, d_points_ptr: int, n: int, d_counts_ptr: int, d_radius2_ptr: int = 0,
+                                     max_dist2: float = float("inf"), skip_same_index: bool = False, stream: int = 0) -> None:
+        """cgrt_count_point_neighbors_device: n points (3 floats each) at d_points_ptr (and n squared radii at d_radius2_ptr, or 0) against
+        the built grid at d_grid_ptr -> n uint32 counts at d_counts_ptr, enqueued on the hipStream_t `stream`.  Raw integers."""
+        q = _point_query(d_radius2_ptr, max_dist2, skip_same_index)
+        _check(lib().cgrt_count_point_neighbors_device(self._h, _vp(d_grid_ptr), int(grid_bytes), _vp(d_points_ptr), int(n), C.byref(q),
+                                                       _vp(d_counts_ptr), _vp(stream)))
+
+    def list_point_neighbors_device(self, d_grid_ptr: int, grid_bytes: int, d_points_ptr: int, n: int, d_out_ptr: int, capacity: int,
+                                    d_offsets_ptr: int = 0, k: int = 0, d_counts_ptr: int = 0, d_radius2_ptr: int = 0,
+                                    max_dist2: float = float("inf"), skip_same_index: bool = False, stream: int = 0) -> None:
+        """cgrt_list_point_neighbors_device: slots from the n + 1 uint64 offsets at d_offsets_ptr, or of k records each; `capacity` records
+        of 8 bytes at d_out_ptr, nothing beyond them is written whatever the offsets hold; d_counts_ptr (optional) receives the full
+        counts.  Enqueued on `stream`.  Raw integers."""
+        q = _point_query(d_radius2_ptr, max_dist2, skip_same_index)
+        _check(lib().cgrt_list_point_neighbors_device(self._h, _vp(d_grid_ptr), int(grid_bytes), _vp(d_points_ptr), int(n), C.byref(q),
+                                                      _vp(d_offsets_ptr), int(k), _vp(d_out_ptr), int(capacity), _vp(d_counts_ptr), _vp(stream)))
+
+    def point_grid_tensor(self, data, cell: float, stream=None) -> "PointGrid":
+        """The grid over data ((m, 3) float32 on cuda:<device>) with the wanted cell edge `cell` (about the query radius), built on
+        `stream` (default: torch.cuda.current_stream()) into a tensor the returned PointGrid owns.  Only enqueues.  The grid holds the
+        coordinates: `data` may be freed once the build has run."""
+        import torch
+
+        m = self._points_tensor(data)
+        dev, stream = self._torch_stream(stream)
+        _check_one_hip_runtime()
+        nbytes = self.point_grid_workspace(m)
+        with torch.cuda.stream(stream):
+            grid = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        self.point_grid_build_device(data.data_ptr() if m else 0, m, cell, grid.data_ptr(), nbytes, stream=stream.cuda_stream)
+        return PointGrid(self, grid, m, float(cell))
+
     def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream, reproducible=False):
         import torch
 
@@ -3024,6 +3186,89 @@ class Scene:
         out = Counters()
         _check(lib().cgrt_count_batch(self._h, _ptr(rays), len(rays), C.byref(out)))
         return out.as_dict()
+
+
+class PointGrid:
+    """A built point-set neighbour grid on the device (Scene.point_grid_tensor; include/cgrt.h "Point-set neighbours"): it owns the grid's
+    tensor and answers queries on torch tensors -- points (n, 3) float32 on the scene's device, radius2 None, a float (one squared
+    radius for every query) or an (n,) float32 tensor, skip_same_index: data point i is not a neighbour of query i.  Every call only
+    enqueues on `stream` (default: torch.cuda.current_stream()), except where it says it blocks; the caller orders a query on another
+    stream behind the build.  Records are (…, 2) float32 with the data index BITS in column 1: records.view(torch.int32)[..., 1]."""
+
+    #: bounded passes of knn (the radius doubles in each) before the unbounded one
+    KNN_PASSES = 8
+
+    def __init__(self, scene: "Scene", grid, m: int, cell: float):
+        self.scene, self.grid, self.m, self.cell = scene, grid, int(m), float(cell)
+
+    def _args(self, points, radius2, max_dist2):
+        n, rad, md = self.scene._neighbor_tensors(points, radius2, max_dist2)
+        return n, rad, md, self.grid.data_ptr(), self.grid.numel()
+
+    def count(self, points, radius2=None, max_dist2: float = float("inf"), skip_same_index: bool = False, out=None, stream=None):
+        """The number of data points within each query's squared radius: (n,) torch.int32, into `out` or a new tensor."""
+        import torch
+
+        n, rad, md, g, gb = self._args(points, radius2, max_dist2)
+        if out is not None:
+            self.scene._device_tensor(out, "out", (torch.int32,), (n,))
+        return self.scene._tensor_call(out, (n,), torch.int32, stream, lambda o, s: self.scene.count_point_neighbors_device(
+            g, gb, points.data_ptr(), n, o.data_ptr(), d_radius2_ptr=rad, max_dist2=md, skip_same_index=skip_same_index, stream=s))
+
+    def list(self, points, radius2=None, max_dist2: float = float("inf"), skip_same_index: bool = False, stream=None):
+        """Every neighbour of every query, CSR style: (offsets (n + 1,) torch.int64, records (total, 2) float32), query i's neighbours
+        are records[offsets[i]:offsets[i + 1]] in (d2, index) order.  A count call, a torch cumsum and the list call are enqueued on
+        `stream`; the total is read back in between (one synchronisation of that stream)."""
+        n, rad, md, g, gb = self._args(points, radius2, max_dist2)
+        return self.scene._slots_full_tensor(
+            n, stream, lambda s: self.count(points, radius2, max_dist2, skip_same_index, stream=s),
+            lambda o, cap, off, s: self.scene.list_point_neighbors_device(g, gb, points.data_ptr(), n, o, cap, d_offsets_ptr=off, d_radius2_ptr=rad,
+                                                                          max_dist2=md, skip_same_index=skip_same_index, stream=s))
+
+    def nearest(self, points, k: int, radius2=None, max_dist2: float = float("inf"), skip_same_index: bool = False, want_counts: bool = False,
+                out=None, stream=None):
+        """The k nearest data points of every query within its squared radius: records (n, k, 2) float32 (`out`, or a new tensor), unused
+        entries {+inf, NO_PRIM}; with want_counts=True (records, counts (n,) torch.int32: the full numbers of neighbours)."""
+        n, rad, md, g, gb = self._args(points, radius2, max_dist2)
+        rec, counts = self.scene._slots_first_tensor(
+            n, k, want_counts, out, stream,
+            lambda o, c, s: self.scene.list_point_neighbors_device(g, gb, points.data_ptr(), n, o, n * k, k=k, d_counts_ptr=c, d_radius2_ptr=rad,
+                                                                   max_dist2=md, skip_same_index=skip_same_index, stream=s))
+        return (rec, counts) if want_counts else rec
+
+    def knn(self, points, k: int, skip_same_index: bool = False, stream=None):
+        """The k nearest data points of every query, no radius from the caller: records (n, k, 2) float32, byte for byte what the brute
+        form gives for r2 = +inf and k records per query (fewer than k data points: the rest {+inf, NO_PRIM}).  A composition, not a C
+        entry: `nearest` with counts at r2 = cell^2; a query whose count reaches k holds its exact k nearest (whatever lies outside the
+        radius is farther than everything inside); the others are asked again with 4 r2 -- in place, under a per-query radius that is
+        negative for the finished ones, so that every query keeps its index and skip_same_index its meaning -- up to KNN_PASSES times,
+        and what is still short then takes one pass with r2 = +inf, the linear walk over the grid's entries.  BLOCKS: the number of
+        unfinished queries is read back after every pass."""
+        import torch
+
+        n = self.scene._points_tensor(points)
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        dev, stream = self.scene._torch_stream(stream)
+        with torch.cuda.stream(stream):
+            out = torch.empty((n, k, 2), dtype=torch.float32, device=dev)
+            if n == 0:
+                return out
+            c2 = float(np.float32(self.cell) * np.float32(self.cell))
+            r2 = torch.full((n,), c2, dtype=torch.float32, device=dev)
+            done = torch.zeros((n,), dtype=torch.bool, device=dev)
+            for p in range(self.KNN_PASSES + 1):
+                if p == self.KNN_PASSES:
+                    r2 = torch.where(done, torch.full_like(r2, -1.0), torch.full_like(r2, float("inf")))
+                rec, cnt = self.nearest(points, k, radius2=r2, skip_same_index=skip_same_index, want_counts=True, stream=stream)
+                if p:  # (as integers: an index's bits may spell a NaN)
+                    rec = torch.where(done[:, None, None], out.view(torch.int32), rec.view(torch.int32)).view(torch.float32)
+                out = rec
+                done = done | (cnt >= k)
+                if p == self.KNN_PASSES or bool(done.all().item()):
+                    break
+                r2 = torch.where(done, torch.full_like(r2, -1.0), r2 * 4.0)
+        return out
 
 
 # ---- one caller, N devices, one framebuffer ----

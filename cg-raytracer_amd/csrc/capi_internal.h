@@ -33,6 +33,7 @@
 #include "closest_kernels.h"
 #include "crossing_kernels.h"
 #include "neighbor_kernels.h"
+#include "point_neighbor_kernels.h"
 #include "poisson_kernels.h"
 #include "sdf_kernels.h"
 #include "surface_grad_repro_kernels.h"

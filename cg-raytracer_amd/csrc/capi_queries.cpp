@@ -1,5 +1,5 @@
 // capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
-// closest points, crossings, neighbours, signed distance, winding numbers, surface samples, Poisson-disk sets.  None of them touches the scene's frame state (workspace, prediction, hints).
+// closest points, crossings, neighbours, signed distance, winding numbers, surface samples, Poisson-disk sets, point-set neighbours.  None of them touches the scene's frame state (workspace, prediction, hints).
 // Every family is ONE body for its host-pointer and its device-pointer entries, written with a QueryCall (capi_internal.h): the argument
 // checks in the order include/cgrt.h states (`device`: the pointers' alignment too), the host-only scene, the empty call, then begin,
 // in / out per array, the launch on the call's stream, finish.  The exported entries are one-line forwarders.
@@ -1053,6 +1053,137 @@ int cgrt_poisson_disk_brute(CgrtScene* s, const float* points, uint64_t n, const
 }
 int cgrt_debug_poisson_work(CgrtScene* s, const float* points, uint64_t n, const CgrtPoissonParams* params, uint64_t* out6) {
     return poisson_query(s, false, points, n, params, nullptr, nullptr, nullptr, 2, out6, nullptr);
+}
+
+// ---- point-set neighbours (include/cgrt.h cgrt_point_grid_*, cgrt_count_point_neighbors*, cgrt_list_point_neighbors*; DESIGN.md section
+// 5.30): every point of a cloud within a query point's squared radius, counted or listed in (d2, index) order, over a hashed grid that
+// lives in the caller's device memory.  The scene only names the device and lends the call lane; no frame state is read or written; the
+// checks come in the order include/cgrt.h states, all before any device work.
+namespace {
+static_assert(sizeof(CgrtPointNeighbor) == sizeof(CgrtPointNeighborDev), "CgrtPointNeighbor is what the kernels write");
+const uint64_t kMaxCloud = 0x7fffffffull;
+// the cloud of a call: the built grid (device forms), or the points themselves (host forms, which build a grid of their own or none)
+struct PointCloud {
+    const float* data;
+    uint64_t m;
+    float cell;
+    const void* d_grid;
+    uint64_t grid_bytes;
+};
+// a host form's own device memory, returned when the call ends (declared before the QueryCall: the lane has been waited for by then)
+struct OwnedDevice {
+    void* p = nullptr;
+    ~OwnedDevice() {
+        if (p) (void)hipFree(p);
+    }
+};
+bool cell_ok(float cell) { return cell > 0.0f && cell <= 3.402823466e+38f; }
+// slots: 0 the points, 4 the radii, then the list's; how: 0 the grid, 1 brute force, 2 the counted grid search (1 and 2 host form only;
+// 2: `work`, L is k records per query of the lane's own, or with k == 0 the count search)
+int point_neighbor_query(CgrtScene* s, bool device, const PointCloud& G, const float* points, uint64_t n, const CgrtPointQuery* q,
+                         const SlotList& L, int how, uint64_t* work, void* stream) {
+    const void* const result = how == 2 ? static_cast<const void*>(work) : (L.list ? L.out : static_cast<const void*>(L.counts));
+    if (!s || !q) return fail(CGRT_E_ARG, "scene or query is NULL");
+    if (n && (!points || !result || (device ? !G.d_grid : (G.m && !G.data)))) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > kMaxCloud) return fail(CGRT_E_ARG, "too many queries: n exceeds 0x7fffffff");
+    if (!device && G.m > kMaxCloud) return fail(CGRT_E_ARG, "too many data points: m exceeds 0x7fffffff");
+    if (!device && how != 1 && !cell_ok(G.cell)) return fail(CGRT_E_ARG, "cell must be finite and > 0");
+    if (!(q->max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
+    if (q->flags & ~(uint32_t)CGRT_POINTS_SKIP_SAME_INDEX) return fail(CGRT_E_ARG, "unknown flags");
+    CGRT_TRY(L.rules(n, device));
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)q->radius2 % 4 || !L.aligned() || (uintptr_t)G.d_grid % 8))
+        return fail(CGRT_E_ARG, "device pointers must be aligned to their elements (d_grid: 8 bytes)");
+    if (device && n && G.grid_bytes < point_grid_bytes(0)) return fail(CGRT_E_ARG, "grid_bytes is below cgrt_point_grid_workspace");
+    NEED_DEVICE(s);
+    if (n == 0 || L.nothing(n, device)) return CGRT_OK;
+    OwnedDevice own;
+    QueryCall c(s, device, stream);
+    void *dp = nullptr, *drad = nullptr;
+    PointNeighborArgs A{};
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, points, n * 12, "d_points", &dp));
+    CGRT_TRY(c.in(4, q->radius2, q->radius2 ? n * 4 : 0, "d_radius2", &drad));
+    CGRT_TRY(L.transfer(c, n, &A));
+    if (device) {
+        CGRT_TRY(check_device_span(s, G.d_grid, G.grid_bytes, "d_grid"));
+        A.grid = G.d_grid;
+        A.grid_bytes = G.grid_bytes;
+    } else {  // the grid (none: brute force), then the cloud
+        const uint64_t gbytes = how == 1 ? 0 : point_grid_bytes(G.m);
+        HIP_TRY(hipMalloc(&own.p, gbytes + 12 * G.m + 16));
+        float* const ddata = reinterpret_cast<float*>(static_cast<char*>(own.p) + gbytes);
+        if (G.m) HIP_TRY(staged_h2d(ddata, G.data, 12 * G.m));  // (complete when it returns)
+        if (how != 1) HIP_TRY(launch_point_grid_build(ddata, G.m, G.cell, own.p, c.stream()));
+        A.grid = own.p;
+        A.grid_bytes = gbytes;
+        A.data = ddata;
+        A.m = G.m;
+    }
+    A.points = static_cast<const float*>(dp);
+    A.radius2 = static_cast<const float*>(drad);
+    A.max_dist2 = q->max_dist2;
+    A.flags = q->flags;
+    A.n = n;
+    if (how == 2) {
+        CGRT_TRY(c.zero_counters(6));
+        HIP_TRY(launch_point_neighbors(A, false, c.counters(), c.stream()));
+        return c.read_counters(work, 6);
+    }
+    HIP_TRY(launch_point_neighbors(A, how == 1, nullptr, c.stream()));
+    return c.finish();
+}
+}  // namespace
+
+int cgrt_point_grid_workspace(CgrtScene* s, uint64_t m, uint64_t* bytes) {
+    if (!s || !bytes) return fail(CGRT_E_ARG, "NULL argument");
+    if (m > kMaxCloud) return fail(CGRT_E_ARG, "too many data points: m exceeds 0x7fffffff");
+    *bytes = point_grid_bytes(m);
+    return CGRT_OK;
+}
+int cgrt_point_grid_build_device(CgrtScene* s, const float* d_data, uint64_t m, float cell, void* d_grid, uint64_t grid_bytes, void* stream) {
+    if (!s) return fail(CGRT_E_ARG, "scene is NULL");
+    if ((m && !d_data) || !d_grid) return fail(CGRT_E_ARG, "NULL argument");
+    if (m > kMaxCloud) return fail(CGRT_E_ARG, "too many data points: m exceeds 0x7fffffff");
+    if (!cell_ok(cell)) return fail(CGRT_E_ARG, "cell must be finite and > 0");
+    if ((uintptr_t)d_data % 4 || (uintptr_t)d_grid % 8) return fail(CGRT_E_ARG, "d_data must be 4-byte and d_grid 8-byte aligned");
+    if (grid_bytes < point_grid_bytes(m)) return fail(CGRT_E_ARG, "grid_bytes is below cgrt_point_grid_workspace");
+    NEED_DEVICE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    CGRT_TRY(check_device_span(s, d_data, m * 12, "d_data"));
+    CGRT_TRY(check_device_span(s, d_grid, point_grid_bytes(m), "d_grid"));
+    HIP_TRY(launch_point_grid_build(d_data, m, cell, d_grid, static_cast<hipStream_t>(stream)));
+    return CGRT_OK;
+}
+int cgrt_count_point_neighbors_device(CgrtScene* s, const void* d_grid, uint64_t grid_bytes, const float* d_points, uint64_t n,
+                                      const CgrtPointQuery* query, uint32_t* d_counts, void* stream) {
+    return point_neighbor_query(s, true, {nullptr, 0, 0.0f, d_grid, grid_bytes}, d_points, n, query, {false, nullptr, 0, nullptr, 0, d_counts}, 0,
+                                nullptr, stream);
+}
+int cgrt_list_point_neighbors_device(CgrtScene* s, const void* d_grid, uint64_t grid_bytes, const float* d_points, uint64_t n,
+                                     const CgrtPointQuery* query, const uint64_t* d_offsets, uint32_t k, CgrtPointNeighbor* d_out,
+                                     uint64_t capacity, uint32_t* d_counts, void* stream) {
+    return point_neighbor_query(s, true, {nullptr, 0, 0.0f, d_grid, grid_bytes}, d_points, n, query, {true, d_offsets, k, d_out, capacity, d_counts},
+                                0, nullptr, stream);
+}
+int cgrt_count_point_neighbors(CgrtScene* s, const float* data, uint64_t m, float cell, const float* points, uint64_t n,
+                               const CgrtPointQuery* query, uint32_t* counts) {
+    return point_neighbor_query(s, false, {data, m, cell, nullptr, 0}, points, n, query, {false, nullptr, 0, nullptr, 0, counts}, 0, nullptr, nullptr);
+}
+int cgrt_list_point_neighbors(CgrtScene* s, const float* data, uint64_t m, float cell, const float* points, uint64_t n, const CgrtPointQuery* query,
+                              const uint64_t* offsets, uint32_t k, CgrtPointNeighbor* out, uint64_t capacity, uint32_t* counts) {
+    return point_neighbor_query(s, false, {data, m, cell, nullptr, 0}, points, n, query, {true, offsets, k, out, capacity, counts}, 0, nullptr,
+                                nullptr);
+}
+int cgrt_list_point_neighbors_brute(CgrtScene* s, const float* data, uint64_t m, const float* points, uint64_t n, const CgrtPointQuery* query,
+                                    const uint64_t* offsets, uint32_t k, CgrtPointNeighbor* out, uint64_t capacity, uint32_t* counts) {
+    return point_neighbor_query(s, false, {data, m, 0.0f, nullptr, 0}, points, n, query, {true, offsets, k, out, capacity, counts}, 1, nullptr,
+                                nullptr);
+}
+int cgrt_debug_point_neighbor_work(CgrtScene* s, const float* data, uint64_t m, float cell, const float* points, uint64_t n,
+                                   const CgrtPointQuery* query, uint32_t k, uint64_t* out6) {
+    // (n <= 0x7fffffff is checked before the capacity n k is looked at)
+    return point_neighbor_query(s, false, {data, m, cell, nullptr, 0}, points, n, query, {k > 0, nullptr, k, nullptr, n * (uint64_t)k, nullptr}, 2,
+                                out6, nullptr);
 }
 
 }  // extern "C"

@@ -1,0 +1,284 @@
+// point_neighbor_kernels.hip -- point-set neighbours (include/cgrt.h cgrt_point_grid_*, cgrt_count_point_neighbors*,
+// cgrt_list_point_neighbors*): for every query point ALL the points of a cloud within its squared radius, counted,
+// or listed in (d2, index) order.  d2 is point_dist2 below, a pure function of the two points, so the search only has to reach every
+// data point that can qualify, each exactly once, in any order.
+//
+// The build, all enqueued on the caller's stream (launch_point_grid_build; the grid of point_grid_device.h, which Poisson-disk sets share):
+//   k_pgrid_bounds    per data point: finite?; the per-axis minimum and maximum of the finite points by ordered-integer atomics, one
+//                     set per wave; thread 0 leaves the caller's cell edge, the bucket mask and m in the header
+//   k_pgrid_count     per finite point: its cell, the cell's bucket, one atomic add on the bucket's count (the first one of a bucket
+//                     counts the bucket as in use)
+//   launch_bucket_scan  the exclusive scan of the bucket counts: poisson_kernels.hip's three scan kernels through its one helper
+//   k_pgrid_scatter   per finite point: {x, y, z, index} and the 63-bit key of its cell into the bucket's range (the order inside a bucket
+//                     is whatever the atomics gave, and no result depends on it)
+// The cell edge is h = max(cell, half extent * 2^-18), computed by load_grid from the header in every pass and in every query alike.
+// Nothing is read back: the bucket count follows from m on the host, everything else stays in the header.
+//
+// The query, k_point_neighbors: one query per lane.  r2 is the query's bound, up the next float above it, R = the root of `up` rounded
+// to nearest and moved two floats up (so R >= the exact root of `up`).  A neighbour j has d2 <= r2 < up; adding non-negative terms with
+// round-to-nearest never decreases a value, so fl(dx dx) <= d2 < up, and -- rounding being monotone and `up` a float -- dx^2 < up exactly:
+// |fl(x_q - x_j)| < R and, again by monotone rounding, |x_q - x_j| < R exactly; then x_j <= fl(x_q + R) and x_j >= fl(x_q - R) because x_j
+// is a float.  (With Poisson's strict `<` the bound itself serves as `up`; with `<=` a dx^2 just above r2 may round down to it, which is
+// why the next float is taken: that also covers subnormal bounds, where half an ulp is no small relative step.)  cell() is monotone, so
+// cell(x_j) lies in [cell(fl(x_q - R)), cell(fl(x_q + R))] per axis; and x_j <= hi, the data's maximum, so cell(x_j) <= cell(hi):
+// clamping the upper end to cell(hi) loses nobody, and a query far outside the cloud does not walk up to 2^21 empty cells per axis.  The
+// lower end needs no clamp, cell() is 0 = cell(lo) below lo.  An upper end below the lower end is an empty range.
+// A bucket also holds points of other cells, and two cells of one range may share a bucket: a count or a list would then meet a point
+// twice.  Every entry carries the key of its own cell and is accepted only in the visit of that cell: each data point of the range is met
+// exactly once.  The cells of a range are counted in 64 bits; more cells than entries (r2 = +inf or FLT_MAX, radii far above h): the lane
+// walks the entry array itself, [0, entries), where every finite data point stands exactly once and no key is needed.
+// Members go to the lane's slot (query_device.h QuerySlot, the slot of the crossing and neighbour queries); while a slot is full and no
+// count is asked for, an entry with `d2 > bound` is passed over (bound = the largest d2 kept, non-strictly: an equal-d2 smaller index
+// still arrives).  No cell is ever skipped on the bound.
+// The header is the device's: the kernel takes m and the bucket mask from it, checks them against each other and against grid_bytes, clamps
+// the number of entries to m and every bucket's end to the number of entries -- a workspace that was never built reads as an empty or
+// a wrong grid, never as an address outside it.
+// k_point_neighbors<.., BRUTE>: every data point in turn for every query, same function, same slot rule (validation).
+//
+// Plain vector loads and stores only in the query (atomics in the build and in the counted instantiation); no scratch, no LDS.
+#include <hip/hip_runtime.h>
+
+#include "point_grid_device.h"
+#include "point_neighbor_kernels.h"
+#include "query_device.h"
+
+namespace cgrt {
+
+namespace {
+
+const uint32_t kSkipSameIndex = 1u;  // include/cgrt.h CGRT_POINTS_SKIP_SAME_INDEX
+
+struct PointGridDev {
+    const float* data;
+    uint32_t m;
+    float cell;
+    uint32_t bmask;
+    uint32_t* hdr;
+    uint32_t* bcount;
+    uint32_t* bstart;
+    float4* epos;
+    unsigned long long* ekey;
+};
+
+__device__ __forceinline__ unsigned long long cell_key(uint32_t cx, uint32_t cy, uint32_t cz) {
+    return (unsigned long long)cx | ((unsigned long long)cy << 21) | ((unsigned long long)cz << 42);
+}
+
+__global__ __launch_bounds__(256) void k_pgrid_bounds(const PointGridDev A) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint32_t klo[3] = {0u, 0u, 0u}, khi[3] = {0u, 0u, 0u};
+    if (i == 0u) {
+        A.hdr[PG_CELL] = __float_as_uint(A.cell);
+        A.hdr[PG_BMASK] = A.bmask;
+        A.hdr[PG_M] = A.m;
+    }
+    if (i < A.m) {
+        const float x = A.data[3ull * i], y = A.data[3ull * i + 1], z = A.data[3ull * i + 2];
+        if (finite3(x, y, z)) {
+            khi[0] = ordered(x), khi[1] = ordered(y), khi[2] = ordered(z);
+            klo[0] = ~khi[0], klo[1] = ~khi[1], klo[2] = ~khi[2];
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const uint32_t l = wave_max(klo[a]), h = wave_max(khi[a]);
+        if (lane_id() == 0u && h != 0u) {
+            atomicMax(A.hdr + H_LO + a, l);
+            atomicMax(A.hdr + H_HI + a, h);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pgrid_count(const PointGridDev A) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= A.m) return;
+    const float x = A.data[3ull * i], y = A.data[3ull * i + 1], z = A.data[3ull * i + 2];
+    if (!finite3(x, y, z)) return;
+    const Grid g = load_grid(A.hdr, A.cell);
+    const uint32_t b = bucket(cell(x, g.lo[0], g.h), cell(y, g.lo[1], g.h), cell(z, g.lo[2], g.h), A.bmask);
+    if (atomicAdd(A.bcount + b, 1u) == 0u) atomicAdd(A.hdr + PG_USED, 1u);
+}
+
+// (takes the counts back down to 0: slot = start + what is left of the count)
+__global__ __launch_bounds__(256) void k_pgrid_scatter(const PointGridDev A) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= A.m) return;
+    const float x = A.data[3ull * i], y = A.data[3ull * i + 1], z = A.data[3ull * i + 2];
+    if (!finite3(x, y, z)) return;
+    const Grid g = load_grid(A.hdr, A.cell);
+    const uint32_t cx = cell(x, g.lo[0], g.h), cy = cell(y, g.lo[1], g.h), cz = cell(z, g.lo[2], g.h);
+    const uint32_t b = bucket(cx, cy, cz, A.bmask);
+    const uint32_t slot = A.bstart[b] + atomicSub(A.bcount + b, 1u) - 1u;  // below bstart[B] <= m
+    A.epos[slot] = make_float4(x, y, z, __uint_as_float(i));
+    A.ekey[slot] = cell_key(cx, cy, cz);
+}
+
+// what a query reads of a built grid
+struct PointGridView {
+    const uint32_t* bstart;
+    const float4* epos;
+    const unsigned long long* ekey;
+    uint32_t bmask, entries, used;
+    Grid g;
+    float hi[3];
+};
+// False: no entries, or a header that does not describe a grid inside grid_bytes (uniform over the launch).
+__device__ __forceinline__ bool grid_view(const void* grid, const unsigned long long grid_bytes, PointGridView& V) {
+    const char* const p0 = reinterpret_cast<const char*>(((uintptr_t)grid + 15u) & ~(uintptr_t)15u);
+    const unsigned long long slack = (unsigned long long)(p0 - static_cast<const char*>(grid));
+    V.used = 0u;
+    if (grid_bytes < slack + 64ull) return false;
+    const uint32_t* const hdr = reinterpret_cast<const uint32_t*>(p0);
+    const uint32_t m = hdr[PG_M];
+    V.bmask = hdr[PG_BMASK];
+    if (m > 0x7fffffffu || V.bmask != poisson_buckets(m) - 1u) return false;
+    const PointGridLayout L = point_grid_layout(m);
+    if (slack + L.bytes > grid_bytes) return false;
+    V.bstart = reinterpret_cast<const uint32_t*>(p0 + L.bstart);
+    V.epos = reinterpret_cast<const float4*>(p0 + L.epos);
+    V.ekey = reinterpret_cast<const unsigned long long*>(p0 + L.ekey);
+    V.entries = min(V.bstart[V.bmask + 1u], m);
+    V.used = hdr[PG_USED];
+    if (V.entries == 0u) return false;
+    V.g = load_grid(hdr, __uint_as_float(hdr[PG_CELL]));
+#pragma unroll
+    for (int a = 0; a < 3; a++) V.hi[a] = unordered(hdr[H_HI + a]);
+    return true;
+}
+
+// include/cgrt.h "Point-set neighbours", Distance: every operation rounded on its own (-ffp-contract=off); Poisson's conflict() arithmetic
+__device__ __forceinline__ float point_dist2(float qx, float qy, float qz, float x, float y, float z) {
+    const float dx = qx - x, dy = qy - y, dz = qz - z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// membership; a neighbour is taken into the slot under its d2 (a NaN never qualifies).  Q.bound is the query's r2, or below it while a
+// full slot shrinks it
+template <bool LIST, bool COUNT>
+__device__ __forceinline__ void point_apply(float qx, float qy, float qz, float x, float y, float z, uint32_t j, uint32_t skip, QuerySlot& Q,
+                                            unsigned long long& c_d2) {
+    if (j == skip) return;
+    const float d2 = point_dist2(qx, qy, qz, x, y, z);
+    if (COUNT) c_d2++;
+    if (d2 <= Q.bound) slot_take<LIST>(d2, j, Q);
+}
+// R of the head comment for a bound in [0, FLT_MAX)
+__device__ __forceinline__ float query_reach(float r2) {
+    const float up = __uint_as_float(__float_as_uint(fabsf(r2)) + 1u);
+    return __uint_as_float(__float_as_uint(sqrtf(up)) + 2u);
+}
+
+template <bool LIST, bool COUNT, bool BRUTE>
+__global__ __launch_bounds__(256) void k_point_neighbors(const PointNeighborArgs A, unsigned long long* __restrict__ counters) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (i >= A.n) return;
+    const float px = A.points[3 * i], py = A.points[3 * i + 1], pz = A.points[3 * i + 2];
+    QuerySlot Q;
+    const bool wanted = slot_open<LIST>(Q, A.radius2 ? A.radius2[i] : A.max_dist2, reinterpret_cast<uint32_t*>(A.out), A.offsets, A.k,
+                                        A.capacity, A.counts != nullptr, i);
+    const uint32_t skip = (A.flags & kSkipSameIndex) ? (uint32_t)i : 0xffffffffu;  // (no data point has index 0xffffffff)
+    unsigned long long c_cells = 0, c_read = 0, c_foreign = 0, c_d2 = 0, c_linear = 0;
+    PointGridView V;
+    const bool built = !BRUTE && grid_view(A.grid, A.grid_bytes, V);
+    // a radius that is NaN or below zero and a point that is not finite have no neighbours
+    if (wanted && Q.limit >= 0.0f && finite3(px, py, pz)) {
+        if (BRUTE) {
+            for (uint32_t j = 0u; j < (uint32_t)A.m; j++) {
+                const float x = A.data[3ull * j], y = A.data[3ull * j + 1], z = A.data[3ull * j + 2];
+                if (finite3(x, y, z)) point_apply<LIST, COUNT>(px, py, pz, x, y, z, j, skip, Q, c_d2);
+            }
+        } else if (built) {
+            unsigned long long ncells = ~0ull;
+            uint32_t x0 = 0u, x1 = 0u, y0 = 0u, y1 = 0u, z0 = 0u, z1 = 0u;
+            if (Q.limit < 3.402823466e+38f) {
+                const float R = query_reach(Q.limit);
+                const Grid& g = V.g;
+                x0 = cell(px - R, g.lo[0], g.h), x1 = min(cell(px + R, g.lo[0], g.h), cell(V.hi[0], g.lo[0], g.h));
+                y0 = cell(py - R, g.lo[1], g.h), y1 = min(cell(py + R, g.lo[1], g.h), cell(V.hi[1], g.lo[1], g.h));
+                z0 = cell(pz - R, g.lo[2], g.h), z1 = min(cell(pz + R, g.lo[2], g.h), cell(V.hi[2], g.lo[2], g.h));
+                const unsigned long long nx = x1 >= x0 ? x1 - x0 + 1u : 0u, ny = y1 >= y0 ? y1 - y0 + 1u : 0u, nz = z1 >= z0 ? z1 - z0 + 1u : 0u;
+                ncells = nx * ny * nz;  // each factor at most 2^21
+            }
+            if (ncells > V.entries) {
+                if (COUNT) c_linear++;
+                for (uint32_t t = 0u; t < V.entries; t++) {
+                    const float4 q = V.epos[t];
+                    if (COUNT) c_read++;
+                    point_apply<LIST, COUNT>(px, py, pz, q.x, q.y, q.z, __float_as_uint(q.w), skip, Q, c_d2);
+                }
+            } else if (ncells != 0ull) {
+                for (uint32_t cz = z0; cz <= z1; cz++)
+                    for (uint32_t cy = y0; cy <= y1; cy++)
+                        for (uint32_t cx = x0; cx <= x1; cx++) {
+                            const unsigned long long key = cell_key(cx, cy, cz);
+                            const uint32_t b = bucket(cx, cy, cz, V.bmask);
+                            const uint32_t end = min(V.bstart[b + 1u], V.entries);
+                            if (COUNT) c_cells++;
+                            for (uint32_t t = V.bstart[b]; t < end; t++) {
+                                if (COUNT) c_read++;
+                                if (V.ekey[t] != key) {  // a point of another cell: met in that cell's visit, if the range holds it
+                                    if (COUNT) c_foreign++;
+                                    continue;
+                                }
+                                const float4 q = V.epos[t];
+                                point_apply<LIST, COUNT>(px, py, pz, q.x, q.y, q.z, __float_as_uint(q.w), skip, Q, c_d2);
+                            }
+                        }
+            }
+        }
+    }
+    slot_close<LIST>(Q, A.counts, i);
+    if (COUNT) {
+        if (c_cells) atomicAdd(counters, c_cells);
+        if (c_read) atomicAdd(counters + 1, c_read);
+        if (c_foreign) atomicAdd(counters + 2, c_foreign);
+        if (c_d2) atomicAdd(counters + 3, c_d2);
+        if (c_linear) atomicAdd(counters + 4, c_linear);
+        if (i == 0ull && V.used) atomicAdd(counters + 5, (unsigned long long)V.used);
+    }
+}
+
+template <bool LIST, bool COUNT, bool BRUTE>
+hipError_t launch_one(const PointNeighborArgs& A, unsigned long long* counters, hipStream_t stream) {
+    const dim3 grid((unsigned)((A.n + 255u) / 256u)), block(256);
+    hipLaunchKernelGGL((k_point_neighbors<LIST, COUNT, BRUTE>), grid, block, 0, stream, A, counters);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_point_grid_build(const float* data, uint64_t m, float cell, void* grid, hipStream_t stream) {
+    if (m > 0x7fffffffull || !grid || (m && !data) || !(cell > 0.0f) || !(cell <= 3.402823466e+38f)) return hipErrorInvalidValue;
+    char* const p0 = reinterpret_cast<char*>(((uintptr_t)grid + 15u) & ~(uintptr_t)15u);
+    const PointGridLayout L = point_grid_layout(m);
+    const uint32_t B = poisson_buckets(m);
+    PointGridDev A{};
+    A.data = data;
+    A.m = (uint32_t)m;
+    A.cell = cell;
+    A.bmask = B - 1u;
+    A.hdr = reinterpret_cast<uint32_t*>(p0);
+    A.bcount = reinterpret_cast<uint32_t*>(p0 + L.bcount);
+    A.bstart = reinterpret_cast<uint32_t*>(p0 + L.bstart);
+    A.epos = reinterpret_cast<float4*>(p0 + L.epos);
+    A.ekey = reinterpret_cast<unsigned long long*>(p0 + L.ekey);
+    const hipError_t e = hipMemsetAsync(p0, 0, 64ull + 4ull * B, stream);  // the header and the bucket counts
+    if (e != hipSuccess) return e;
+    const dim3 block(256), grid_dim((unsigned)(m ? (m + 255u) / 256u : 1u));  // (one block without points: thread 0 fills the header)
+    hipLaunchKernelGGL(k_pgrid_bounds, grid_dim, block, 0, stream, A);
+    if (m) hipLaunchKernelGGL(k_pgrid_count, grid_dim, block, 0, stream, A);
+    launch_bucket_scan(A.bcount, reinterpret_cast<uint32_t*>(p0 + L.sums), A.bstart, B, stream);
+    if (m) hipLaunchKernelGGL(k_pgrid_scatter, grid_dim, block, 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_point_neighbors(const PointNeighborArgs& A, bool brute, unsigned long long* counters, hipStream_t stream) {
+    if (A.n == 0) return hipSuccess;
+    if (A.n > 0x7fffffffull || A.m > 0x7fffffffull || (!A.out && !A.counts && !counters) || (counters && brute) || (!brute && !A.grid) ||
+        (brute && A.m && !A.data))
+        return hipErrorInvalidValue;
+    if (counters) return A.out ? launch_one<true, true, false>(A, counters, stream) : launch_one<false, true, false>(A, counters, stream);
+    if (!A.out) return brute ? launch_one<false, false, true>(A, nullptr, stream) : launch_one<false, false, false>(A, nullptr, stream);
+    return brute ? launch_one<true, false, true>(A, nullptr, stream) : launch_one<true, false, false>(A, nullptr, stream);
+}
+
+}  // namespace cgrt

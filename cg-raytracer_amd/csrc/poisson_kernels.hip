@@ -12,15 +12,8 @@
 //   k_poisson_round    one round over the work list of undecided points (below), as often as the data needs
 //   k_poisson_finish   keep[i] = (state == KEPT), and the count
 //
-// The grid.  cell(x) = uint(clamp((x - lo) / h, 0, 2^21 - 1)) per axis: f32 subtraction of a constant, division by a positive constant, the
-// clamp and the truncation are all monotone in x, so cell() is.  lo is the minimum of the finite points, h = max(R, half extent * 2^-18) (so
-// the quotient stays below 2^20 and two floats next to each other are less than a cell apart), R the upward-rounded root of min_dist2 plus an
-// ulp.  d2 < min_dist2 implies fl(dx dx) < min_dist2 (adding non-negative terms with round-to-nearest never decreases a value), hence
-// dx^2 < min_dist2 exactly, |fl(x_i - x_j)| < R and -- rounding being monotone -- |x_i - x_j| < R exactly; then x_j <= fl(x_i + R) and
-// x_j >= fl(x_i - R), again because rounding is monotone and x_j is a float.  So every conflicting j lies in a cell of
-// [cell(x_i - R), cell(x_i + R)] per axis, and the round visits exactly that range (two to four cells per axis).  Cells are hashed into
-// buckets; a bucket also holds points of other cells and two cells of a range may share a bucket: pairs are then tested that need not be,
-// or twice, and a Boolean cannot change.  With a radius that covers the cloud everything lies in one cell: still right, every pair tested.
+// The grid: point_grid_device.h, which states its arithmetic and argues that the cell range of a point holds every point that can conflict
+// with it; the point-neighbour queries (point_neighbor_kernels.hip) share it.
 //
 // The rounds.  A state only ever goes from UNDECIDED to KEPT or REJECTED and never changes again.  An undecided i scans the points that come
 // before it and conflict with it: one of them KEPT -> i is REJECTED; none of them UNDECIDED (all REJECTED) -> i is KEPT; else i goes on
@@ -37,6 +30,7 @@
 #include <cmath>
 
 #include "philox_device.h"
+#include "point_grid_device.h"
 #include "poisson_kernels.h"
 
 namespace cgrt {
@@ -44,9 +38,8 @@ namespace cgrt {
 namespace {
 
 enum : uint32_t { P_UNDECIDED = 0, P_KEPT = 1, P_REJECTED = 2 };
-// header words
-enum : uint32_t { H_LO = 0, H_HI = 3, H_CNT = 6, H_KEPT = 9, H_PAIRS = 10 /* 64 bits */, H_USED = 12, H_ROUNDS = 13 };
-const float kCellMax = 2097151.0f;  // 2^21 - 1: three cell coordinates make one 63-bit word
+// header words (H_LO = 0 and H_HI = 3: point_grid_device.h)
+enum : uint32_t { H_CNT = 6, H_KEPT = 9, H_PAIRS = 10 /* 64 bits */, H_USED = 12, H_ROUNDS = 13 };
 
 struct PoissonDev {
     const float* points;
@@ -67,39 +60,6 @@ struct PoissonDev {
     uint8_t* keep;
 };
 
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-
-// floats as unsigned integers of the same order (finite values give words above 0x00800000 and their complements too: 0 is "none yet")
-__device__ __forceinline__ uint32_t ordered(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float unordered(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-struct Grid {
-    float lo[3], h;
-};
-// the same values in every thread of every pass: the header's bounds are complete before the first pass that calls this
-__device__ __forceinline__ Grid load_grid(const uint32_t* hdr, float R) {
-    Grid g;
-    float e = 0.0f;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        g.lo[a] = unordered(~hdr[H_LO + a]);
-        e = fmaxf(e, unordered(hdr[H_HI + a]) * 0.5f - g.lo[a] * 0.5f);
-    }
-    g.h = fmaxf(R, e * 3.814697265625e-6f);  // 2^-18 of the half extent: quotients below 2^20
-    return g;
-}
-__device__ __forceinline__ uint32_t cell(float x, float lo, float h) { return (uint32_t)fminf(fmaxf((x - lo) / h, 0.0f), kCellMax); }
-__device__ __forceinline__ uint32_t bucket(uint32_t cx, uint32_t cy, uint32_t cz, uint32_t bmask) {
-    unsigned long long k = (unsigned long long)cx | ((unsigned long long)cy << 21) | ((unsigned long long)cz << 42);
-    k *= 0x9E3779B97F4A7C15ull;
-    k ^= k >> 29;
-    k *= 0xBF58476D1CE4E5B9ull;
-    k ^= k >> 32;
-    return (uint32_t)k & bmask;
-}
 // the conflict test of include/cgrt.h: every operation rounded on its own (-ffp-contract=off), symmetric in the two points
 __device__ __forceinline__ bool conflict(float xi, float yi, float zi, float xj, float yj, float zj, float m) {
     const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
@@ -116,12 +76,6 @@ __device__ __forceinline__ void wave_append(bool pred, uint32_t value, uint32_t*
     base = __shfl(base, leader);
     if (pred) list[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = value;
 }
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
-    return v;
-}
-
 // first: the state of a finite point (P_KEPT when nothing can conflict)
 __global__ __launch_bounds__(256) void k_poisson_init(const PoissonDev A, const uint32_t first, const int bounds) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -168,22 +122,6 @@ __global__ __launch_bounds__(256) void k_poisson_count(const PoissonDev A) {
     }
 }
 
-// exclusive scan of one value per thread over the block's 256 threads; *total: the block's sum.  lds: 4 words
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
-    const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= (uint32_t)d) incl += t;
-    }
-    if (lane == 63u) lds[w] = incl;
-    __syncthreads();
-    const uint32_t s0 = lds[0], s1 = lds[1], s2 = lds[2], s3 = lds[3];
-    __syncthreads();
-    *total = s0 + s1 + s2 + s3;
-    return (w > 0u ? s0 : 0u) + (w > 1u ? s1 : 0u) + (w > 2u ? s2 : 0u) + incl - v;
-}
 __global__ __launch_bounds__(256) void k_poisson_scan_tiles(const uint32_t* counts, uint32_t* sums) {
     __shared__ uint32_t lds[4];
     const uint4 c = reinterpret_cast<const uint4*>(counts)[blockIdx.x * 256u + threadIdx.x];
@@ -309,6 +247,14 @@ uint64_t now_ns() { return (uint64_t)std::chrono::duration_cast<std::chrono::nan
 
 }  // namespace
 
+void launch_bucket_scan(const uint32_t* bcount, uint32_t* sums, uint32_t* bstart, uint32_t B, hipStream_t stream) {
+    const uint32_t ntiles = B / 1024u;
+    const dim3 block(256);
+    hipLaunchKernelGGL(k_poisson_scan_tiles, dim3(ntiles), block, 0, stream, bcount, sums);
+    hipLaunchKernelGGL(k_poisson_scan_sums, dim3(1), block, 0, stream, sums, ntiles, bstart + B);
+    hipLaunchKernelGGL(k_poisson_scan_apply, dim3(ntiles), block, 0, stream, bcount, sums, bstart);
+}
+
 hipError_t run_poisson_disk(const PoissonCall& Q, bool brute, uint32_t* pinned, hipStream_t stream, uint64_t* kept, PoissonWork* work) {
     if (Q.n == 0u || Q.n > 0x7fffffffu || !pinned) return hipErrorInvalidValue;
     const uint64_t n = Q.n, B = poisson_buckets(n);
@@ -357,10 +303,7 @@ hipError_t run_poisson_disk(const PoissonCall& Q, bool brute, uint32_t* pinned, 
             hipLaunchKernelGGL(k_poisson_count<true>, grid, block, 0, stream, A);
         else
             hipLaunchKernelGGL(k_poisson_count<false>, grid, block, 0, stream, A);
-        const uint32_t ntiles = (uint32_t)(B / 1024);
-        hipLaunchKernelGGL(k_poisson_scan_tiles, dim3(ntiles), block, 0, stream, A.bcount, A.sums);
-        hipLaunchKernelGGL(k_poisson_scan_sums, dim3(1), block, 0, stream, A.sums, ntiles, A.bstart + B);
-        hipLaunchKernelGGL(k_poisson_scan_apply, dim3(ntiles), block, 0, stream, A.bcount, A.sums, A.bstart);
+        launch_bucket_scan(A.bcount, A.sums, A.bstart, (uint32_t)B, stream);
         hipLaunchKernelGGL(k_poisson_scatter, grid, block, 0, stream, A);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -1325,6 +1325,108 @@ int cgrt_poisson_disk_workspace(CgrtScene* scene, uint64_t n, uint64_t* bytes);
 int cgrt_poisson_disk_brute(CgrtScene* scene, const float* points, uint64_t n, const CgrtPoissonParams* params, uint8_t* keep, uint64_t* kept);
 int cgrt_debug_poisson_work(CgrtScene* scene, const float* points, uint64_t n, const CgrtPoissonParams* params, uint64_t* out6);
 
+/* Point-set neighbours: "which points of this cloud lie within r of p -- all of them, nearest first?" and "which
+ * are the k nearest?" for a list of query points -- normals and densities from the k nearest samples, kNN graphs and ball-query groups for
+ * point-cloud networks, Chamfer distances between two clouds, outlier removal, smoothing over a radius.  Every other query relates a point
+ * to the mesh; these relate points to points, over a hashed uniform grid that outlives the call that built it.  The scene names the
+ * device and lends its call lanes, as for cgrt_poisson_disk; its geometry is not read.  All f32 arithmetic is IEEE, every operation rounded
+ * on its own, nothing contracted.  The definition below IS the specification.
+ * Data and queries.  data: m x 3 f32, 0 <= m <= 0x7fffffff.  points: n x 3 f32, the queries, n <= 0x7fffffff.  A data point with a
+ * non-finite coordinate is nobody's neighbour; a non-finite query has no neighbours.
+ * Distance.  For query q and data point j: dx = fl(q.x - d_j.x), dy and dz likewise; d2 = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)) -- the
+ * conflict arithmetic of "Poisson-disk sets", a pure function of the two points.
+ * Bound.  query (CgrtPointQuery, not NULL): r2 = radius2 ? radius2[i] : max_dist2, exactly as cgrt_count_neighbors defines and checks it:
+ * a scalar max_dist2 that is NaN or negative is CGRT_E_ARG (also where radius2 is given), +inf is unbounded; a per-query radius2[i] for
+ * which `radius2[i] >= 0` is false gives that query no neighbours, decided in the kernel, identically in all forms (radius2: n f32, host
+ * memory in the host forms, device memory in the device forms; the host forms do not scan it).
+ * Neighbour.  j is a neighbour of query i iff both are finite and `d2 <= r2` is true -- non-strictly, like the triangle neighbours and
+ * unlike Poisson's `<` -- and the flag below does not exclude it.  A NaN d2 never qualifies.  A d2 that overflows to +inf qualifies under
+ * r2 = +inf only.
+ * Flag.  With CGRT_POINTS_SKIP_SAME_INDEX in query->flags, j == i is never a neighbour of query i (a cloud queried against itself).  Any
+ * other bit: CGRT_E_ARG.
+ * Order and slots.  A query's neighbours are ordered by d2 compared as floats, equal d2 going to the smaller index: a total order, so
+ * every output byte is determined.  CgrtPointNeighbor = {dist2, index}, 8 bytes, CgrtNeighbor's layout.  The slot rule is word for word
+ * that of "Crossing queries" and "Neighbour queries": the count calls write counts[i] = the number of neighbours of query i; in the list
+ * calls query i owns the records [offsets[i], offsets[i + 1]) of out (offsets: n + 1 u64) or, with offsets == NULL, [i * k, (i + 1) * k):
+ * exactly one of offsets and k > 0 must be given.  A slot of s records receives the first min(s, count) neighbours in order and
+ * {+inf, CGRT_NO_PRIM} in its remaining entries; counts[i] (may be NULL in the list calls) is always the full count.  Every record of
+ * every slot is written, nothing outside the slots.  The host forms check that offsets start at 0, do not decrease and end <= capacity;
+ * the device form never reads the offsets on the host: the kernel treats a decreasing pair as an empty slot and clamps both ends to
+ * capacity (slots that overlap are written by several queries, in no defined order).
+ * Exact nearest.  With k > 0 and counts == NULL the call is "the k nearest within r2"; with r2 = +inf, the k nearest.
+ * Determinism.  The result is a function of (data, points, bound, flags) alone: not of the cell size, the bucket count, the order inside
+ * a bucket, the launch shape, the stream or the run.  cgrt_list_point_neighbors_brute -- every data point in turn, the same function, the
+ * same slot rule, no grid -- returns the same bytes; it is the yardstick.
+ * Accuracy.  While no intermediate is subnormal or overflows, d2 = exact * (1 + e) with |e| <= (1 + u)^5 - 1 < 5.0000006 u, u = 2^-24:
+ * each difference carries one rounding (1 + a), |a| <= u, so its exact square carries (1 + a)^2; the product adds one rounding, the first
+ * sum one (over non-negative terms, whose relative errors do not grow under addition), the second sum one: the x and y terms pass through
+ * 2 + 1 + 1 + 1 = 5 factors, the z term through 4.  Membership can therefore differ from the float64 answer only for pairs whose exact
+ * squared distance lies within that relative band of r2 (tests/test_point_neighbors_cpu.py).
+ * The grid.  cgrt_point_grid_workspace reports the bytes a grid over m points needs (24 per point and 8 per bucket, of which there are
+ * about as many as points, at least 1024).  cgrt_point_grid_build_device enqueues the build on `stream` (NULL = default
+ * stream) into caller-owned device memory (8-byte aligned, contents need no initialisation): it never blocks and reads nothing back.
+ * The grid is self-contained -- its entries hold the coordinates -- so d_data may be freed or overwritten once the build has run.
+ * cell (finite, > 0) is the wanted cell edge; the edge used is h = max(cell, half extent of the finite data * 2^-18), Poisson's rule.
+ * A good cell is about the query radius; no result depends on it.  m == 0 or a cloud with no finite point builds an empty grid, in which
+ * no query has a neighbour.  A grid may be queried any number of times, from several streams and threads at once; the caller orders
+ * the queries behind the build, and a rebuild behind the queries.  The query entries read every grid parameter from the grid's header on
+ * the device; a header that does not describe a grid within grid_bytes (memory that was never built) reads as an empty or a wrong grid,
+ * never as an address outside [d_grid, d_grid + grid_bytes).  grid_bytes is what the memory holds, at least cgrt_point_grid_workspace(m).
+ * Search.  One query per lane.  R_i: the root of the next float above r2, rounded up, plus an ulp.  d2 <= r2 implies |q.x - d_j.x| < R_i
+ * exactly (monotone rounding, point_neighbor_kernels.hip), so per axis the lane visits the cells [cell(fl(x - R_i)), min(cell(fl(x + R_i)),
+ * cell(hi))], hi the data's maximum: cell() is monotone, so the clamp loses nobody and a query far outside the cloud visits few cells.  A
+ * bucket of the hash also holds points of other cells; every entry carries its own cell's 63-bit key and is accepted only in the visit of
+ * that cell, so each data point is met exactly once per query.  A range with more cells than the grid has entries (r2 = +inf, radii far
+ * above the cell edge) is not walked: the lane reads the entry array itself, once.  A slot is kept sorted by insertion: a full list of c
+ * neighbours costs up to c^2 / 2 record moves.  While a slot is full and no count is asked for, entries beyond the largest d2 kept are
+ * passed over (non-strictly: an equal-d2 smaller index still arrives).
+ * Host forms (host pointers, synchronous) run on a call lane like cgrt_closest_points and allocate, build and free a grid of their own
+ * per call: any number of threads may call at once.  cgrt_debug_point_neighbor_work (host form; a counted launch, never part of a timed
+ * region; k = 0: the count search, k > 0: k records per query and no counts): out6 = {cells visited, entries read, entries passed over
+ * because they belong to another cell, d2 evaluations, queries that took the linear walk, buckets in use}, summed over the n queries.
+ * The device forms read no host array but *query and only enqueue on `stream`; they neither read nor write any frame state.
+ * Checks, all CGRT_E_ARG, in this order and before any device work.  Query entries: NULL scene or query; with n > 0, NULL points, result
+ * array (counts of the count calls, out of the list calls, out6), data with m > 0 (host forms) or d_grid (device forms); n > 0x7fffffff;
+ * (host forms) m > 0x7fffffff; (host forms with a grid) cell not finite or <= 0; max_dist2 NaN or negative; an unknown flag; (list calls)
+ * both or neither of offsets and k > 0; capacity above 2^37 records; with k, n * k > capacity; (host list calls, n > 0) offsets not
+ * starting at 0, decreasing, or ending above capacity; (device forms) a pointer not aligned to its element (4 bytes; 8 for d_offsets and
+ * d_grid); (device forms, n > 0) grid_bytes below cgrt_point_grid_workspace(0).  cgrt_point_grid_build_device: NULL scene; NULL d_data
+ * with m > 0 or NULL d_grid; m > 0x7fffffff; cell; d_data not 4-byte or d_grid not 8-byte aligned; grid_bytes below
+ * cgrt_point_grid_workspace(m).  cgrt_point_grid_workspace: NULL scene or bytes; m > 0x7fffffff.  Then a host-only scene:
+ * CGRT_E_NO_DEVICE (not cgrt_point_grid_workspace, which only computes).  n == 0 succeeds and touches nothing.  Device forms: then
+ * d_points (n * 12 bytes), radius2 (n * 4), d_offsets ((n + 1) * 8), d_out (capacity records with offsets, n * k with k), d_counts (n * 4)
+ * and d_grid (grid_bytes; the build: d_data, m * 12, and the workspace of m) checked as device memory of the scene's device.
+ * Not offered: per-record coordinates (they are data[index]); a per-query k (offsets give per-query slot sizes); periodic domains;
+ * incremental insertion; enqueued-ticket forms (the device forms never block); the k nearest without a bound in one entry (r2 = +inf
+ * walks every entry: compose growing radii, as the Python PointGrid.knn does); the C++ host mirror. */
+#define CGRT_POINTS_SKIP_SAME_INDEX 1u
+typedef struct CgrtPointNeighbor {
+    float dist2;    /* d2 as defined above; +inf in an unused entry       */
+    uint32_t index; /* the data point; CGRT_NO_PRIM in an unused entry    */
+} CgrtPointNeighbor;
+typedef struct CgrtPointQuery {
+    const float* radius2; /* NULL, or n squared radii (NaN or negative: that query has no neighbours) */
+    float max_dist2;      /* the bound of every query where radius2 == NULL; NaN or negative -> CGRT_E_ARG; +inf: unbounded */
+    uint32_t flags;       /* 0, or CGRT_POINTS_SKIP_SAME_INDEX */
+} CgrtPointQuery;
+int cgrt_point_grid_workspace(CgrtScene* scene, uint64_t m, uint64_t* bytes);
+int cgrt_point_grid_build_device(CgrtScene* scene, const float* d_data, uint64_t m, float cell, void* d_grid, uint64_t grid_bytes, void* stream);
+int cgrt_count_point_neighbors_device(CgrtScene* scene, const void* d_grid, uint64_t grid_bytes, const float* d_points, uint64_t n,
+                                      const CgrtPointQuery* query, uint32_t* d_counts, void* stream);
+int cgrt_list_point_neighbors_device(CgrtScene* scene, const void* d_grid, uint64_t grid_bytes, const float* d_points, uint64_t n,
+                                     const CgrtPointQuery* query, const uint64_t* d_offsets, uint32_t k, CgrtPointNeighbor* d_out,
+                                     uint64_t capacity, uint32_t* d_counts, void* stream);
+int cgrt_count_point_neighbors(CgrtScene* scene, const float* data, uint64_t m, float cell, const float* points, uint64_t n,
+                               const CgrtPointQuery* query, uint32_t* counts);
+int cgrt_list_point_neighbors(CgrtScene* scene, const float* data, uint64_t m, float cell, const float* points, uint64_t n,
+                              const CgrtPointQuery* query, const uint64_t* offsets, uint32_t k, CgrtPointNeighbor* out, uint64_t capacity,
+                              uint32_t* counts);
+int cgrt_list_point_neighbors_brute(CgrtScene* scene, const float* data, uint64_t m, const float* points, uint64_t n,
+                                    const CgrtPointQuery* query, const uint64_t* offsets, uint32_t k, CgrtPointNeighbor* out, uint64_t capacity,
+                                    uint32_t* counts);
+int cgrt_debug_point_neighbor_work(CgrtScene* scene, const float* data, uint64_t m, float cell, const float* points, uint64_t n,
+                                   const CgrtPointQuery* query, uint32_t k, uint64_t* out6);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
