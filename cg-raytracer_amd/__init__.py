@@ -46,6 +46,7 @@ assert SURFACE_SAMPLE_DTYPE.itemsize == 32
 POINT_NEIGHBOR_DTYPE = np.dtype([("dist2", np.float32), ("index", np.uint32)])
 assert POINT_NEIGHBOR_DTYPE.itemsize == 8
 POINTS_SKIP_SAME_INDEX = 1  # include/cgrt.h CGRT_POINTS_SKIP_SAME_INDEX
+ISO_INSIDE_ABOVE = 1  # include/cgrt.h CGRT_ISO_INSIDE_ABOVE
 _SLOT_RECORDS = {"crossings": CROSSING_DTYPE, "neighbors": NEIGHBOR_DTYPE}  # the slot-list entries (Scene._slots_*) by the name in their symbols
 # Scene.inside_tensor's default directions: three fixed generic ones (no component zero, none along an axis, a face diagonal or a space
 # diagonal, pairwise far from parallel), so that a ray through an edge or a vertex of an axis-aligned or diagonal-symmetric mesh is the
@@ -119,6 +120,18 @@ def _point_query(radius2_ptr: int = 0, max_dist2: float = float("inf"), skip_sam
     q = PointQuery()
     q.radius2, q.max_dist2, q.flags = (int(radius2_ptr) or None), float(max_dist2), (POINTS_SKIP_SAME_INDEX if skip_same_index else 0)
     return q
+
+
+class IsoParams(C.Structure):
+    """include/cgrt.h CgrtIsoParams."""
+    _fields_ = [("iso", C.c_float), ("flags", C.c_uint32)]
+
+
+def _iso_params(iso: float = 0.0, inside_above: bool = False) -> IsoParams:
+    """CgrtIsoParams; the library checks iso (finite)."""
+    p = IsoParams()
+    p.iso, p.flags = float(iso), (ISO_INSIDE_ABOVE if inside_above else 0)
+    return p
 
 
 def _sdf_params(max_dist2: float = float("inf"), directions=None) -> SdfParams:
@@ -400,7 +413,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_point_grid_workspace", "cgrt_point_grid_build_device", "cgrt_count_point_neighbors", "cgrt_count_point_neighbors_device", "cgrt_list_point_neighbors", "cgrt_list_point_neighbors_device", "cgrt_list_point_neighbors_brute", "cgrt_debug_point_neighbor_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_point_grid_workspace", "cgrt_point_grid_build_device", "cgrt_count_point_neighbors", "cgrt_count_point_neighbors_device", "cgrt_list_point_neighbors", "cgrt_list_point_neighbors_device", "cgrt_list_point_neighbors_brute", "cgrt_debug_point_neighbor_work", "cgrt_isosurface_workspace", "cgrt_isosurface_count_device", "cgrt_isosurface_device", "cgrt_isosurface", "cgrt_debug_isosurface_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -571,6 +584,12 @@ def lib() -> C.CDLL:
     L.cgrt_list_point_neighbors.argtypes = [vp, vp, u64, C.c_float, vp, u64, pq, vp, u32, vp, u64, vp]
     L.cgrt_list_point_neighbors_brute.argtypes = [vp, vp, u64, vp, u64, pq, vp, u32, vp, u64, vp]
     L.cgrt_debug_point_neighbor_work.argtypes = [vp, vp, u64, C.c_float, vp, u64, pq, u32, vp]
+    gp, ip = C.POINTER(Grid), C.POINTER(IsoParams)
+    L.cgrt_isosurface_workspace.argtypes = [vp, gp, C.POINTER(u64)]
+    L.cgrt_isosurface_count_device.argtypes = [vp, gp, vp, ip, vp, vp, u64, vp]
+    L.cgrt_isosurface_device.argtypes = [vp, gp, vp, ip, vp, u64, vp, u64, vp, vp, u64, vp]
+    L.cgrt_isosurface.argtypes = [vp, gp, vp, ip, vp, u64, vp, u64, vp]
+    L.cgrt_debug_isosurface_work.argtypes = [vp, gp, vp, ip, vp]
     L.cgrt_triangle_areas.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.cgrt_debug_get_sample_table.argtypes = [vp, vp, C.POINTER(u32)]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
@@ -3006,6 +3025,116 @@ class Scene:
             grid = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
         self.point_grid_build_device(data.data_ptr() if m else 0, m, cell, grid.data_ptr(), nbytes, stream=stream.cuda_stream)
         return PointGrid(self, grid, m, float(cell))
+
+    # ---- iso-surfaces (include/cgrt.h cgrt_isosurface*) ----
+    def isosurface(self, values, origin, spacing, iso: float = 0.0, inside_above: bool = False):
+        """cgrt_isosurface: the triangle mesh of the level `iso` of values ((nz, ny, nx) float32 on the grid origin + i * spacing), by
+        marching tetrahedra, in the order include/cgrt.h defines.  Returns (verts (nv, 3) float32, tris (nt, 3) uint32).  Inside is
+        value < iso (inside_above: value > iso); normals point from inside to outside."""
+        v = np.ascontiguousarray(np.asarray(values, np.float32))
+        if v.ndim != 3:
+            raise ValueError("values must be shaped (nz, ny, nx)")
+        g, prm = _sdf_grid_struct(origin, spacing, v.shape[::-1]), _iso_params(iso, inside_above)
+        counts = np.zeros(2, np.uint64)
+        _check(lib().cgrt_isosurface(self._h, C.byref(g), _ptr(v), C.byref(prm), None, 0, None, 0, _ptr(counts)))
+        verts, tris = np.zeros((int(counts[0]), 3), np.float32), np.zeros((int(counts[1]), 3), np.uint32)
+        if len(verts) or len(tris):
+            _check(lib().cgrt_isosurface(self._h, C.byref(g), _ptr(v), C.byref(prm), _ptr(verts) if len(verts) else None, len(verts),
+                                         _ptr(tris) if len(tris) else None, len(tris), _ptr(counts)))
+        return verts, tris
+
+    def debug_isosurface_work(self, values, origin, spacing, iso: float = 0.0, inside_above: bool = False):
+        """cgrt_debug_isosurface_work: (cells that emit a triangle, tetrahedra that emit one, vertices, triangles) of isosurface (a
+        counted run)."""
+        v = np.ascontiguousarray(np.asarray(values, np.float32))
+        if v.ndim != 3:
+            raise ValueError("values must be shaped (nz, ny, nx)")
+        g, prm = _sdf_grid_struct(origin, spacing, v.shape[::-1]), _iso_params(iso, inside_above)
+        w = np.zeros(4, np.uint64)
+        _check(lib().cgrt_debug_isosurface_work(self._h, C.byref(g), _ptr(v), C.byref(prm), _ptr(w)))
+        return tuple(int(x) for x in w)
+
+    def isosurface_workspace(self, dims) -> int:
+        """cgrt_isosurface_workspace: the bytes of device memory an isosurface call on a grid of dims = (nx, ny, nz) needs."""
+        g = _sdf_grid_struct((0, 0, 0), (1, 1, 1), dims)
+        b = C.c_uint64(0)
+        _check(lib().cgrt_isosurface_workspace(self._h, C.byref(g), C.byref(b)))
+        return int(b.value)
+
+    def isosurface_count_device(self, origin, spacing, dims, d_values_ptr: int, d_counts2_ptr: int, d_workspace_ptr: int, workspace_bytes: int,
+                                iso: float = 0.0, inside_above: bool = False, stream: int = 0) -> None:
+        """cgrt_isosurface_count_device: nx * ny * nz float32 at d_values_ptr -> {vertices, triangles} as two uint64 at d_counts2_ptr
+        (8-byte aligned), with the caller's workspace; enqueued on the hipStream_t `stream`.  Raw integers."""
+        g, prm = _sdf_grid_struct(origin, spacing, dims), _iso_params(iso, inside_above)
+        _check(lib().cgrt_isosurface_count_device(self._h, C.byref(g), _vp(d_values_ptr), C.byref(prm), _vp(d_counts2_ptr), _vp(d_workspace_ptr),
+                                                  int(workspace_bytes), _vp(stream)))
+
+    def isosurface_device(self, origin, spacing, dims, d_values_ptr: int, d_verts_ptr: int, vert_capacity: int, d_tris_ptr: int,
+                          tri_capacity: int, d_counts2_ptr: int, d_workspace_ptr: int, workspace_bytes: int, iso: float = 0.0,
+                          inside_above: bool = False, stream: int = 0) -> None:
+        """cgrt_isosurface_device: the vertices below vert_capacity (3 floats each) to d_verts_ptr, the triangles below tri_capacity (3
+        uint32 each) to d_tris_ptr, the full counts to d_counts2_ptr; nothing beyond the capacities is written.  Enqueued on `stream`.
+        Raw integers."""
+        g, prm = _sdf_grid_struct(origin, spacing, dims), _iso_params(iso, inside_above)
+        _check(lib().cgrt_isosurface_device(self._h, C.byref(g), _vp(d_values_ptr), C.byref(prm), _vp(d_verts_ptr), int(vert_capacity),
+                                            _vp(d_tris_ptr), int(tri_capacity), _vp(d_counts2_ptr), _vp(d_workspace_ptr), int(workspace_bytes),
+                                            _vp(stream)))
+
+    def isosurface_tensor(self, values, origin, spacing, iso: float = 0.0, inside_above: bool = False, capacity=None, workspace=None,
+                          stream=None):
+        """isosurface on torch tensors: values (nz, ny, nx) float32 on cuda:<device> -> {'verts': (nv, 3) float32, 'tris': (nt, 3) int32
+        (the uint32 indices, viewed), 'counts': (2,) int64 {vertices, triangles}, the full counts}.  capacity None: counts, reads the two
+        counts (this blocks), allocates exactly and lists.  capacity = (v, t): lists in one pass into tensors of that size and returns
+        them cut to the counts (the cut reads the counts: it blocks too; records beyond a capacity are dropped, the counts say so).
+        workspace: None (allocated here), or a torch.uint8 tensor of at least isosurface_workspace(dims) bytes, 8-byte aligned.  Ordered
+        on `stream` (default: torch.cuda.current_stream())."""
+        import torch
+
+        self._device_tensor(values, "values", (torch.float32,))
+        if values.dim() != 3:
+            raise ValueError("values must be shaped (nz, ny, nx)")
+        nz, ny, nx = (int(x) for x in values.shape)
+        dims = (nx, ny, nz)
+        nbytes = self.isosurface_workspace(dims)
+        if workspace is not None:
+            self._device_tensor(workspace, "workspace", (torch.uint8,))
+            if workspace.numel() < nbytes or workspace.data_ptr() % 8:
+                raise ValueError(f"workspace must hold {nbytes} bytes and be 8-byte aligned")
+        dev, stream = self._torch_stream(stream)
+        _check_one_hip_runtime()
+        with torch.cuda.stream(stream):
+            if workspace is None:
+                workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            counts = torch.empty((2,), dtype=torch.int64, device=dev)
+            if capacity is None:
+                self.isosurface_count_device(origin, spacing, dims, values.data_ptr(), counts.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                             iso=iso, inside_above=inside_above, stream=stream.cuda_stream)
+                capacity = tuple(int(x) for x in counts.cpu())
+            vcap, tcap = (int(x) for x in capacity)
+            verts = torch.empty((vcap, 3), dtype=torch.float32, device=dev)
+            tris = torch.empty((tcap, 3), dtype=torch.int32, device=dev)
+            self.isosurface_device(origin, spacing, dims, values.data_ptr(), verts.data_ptr() if vcap else 0, vcap, tris.data_ptr() if tcap else 0,
+                                   tcap, counts.data_ptr(), workspace.data_ptr(), workspace.numel(), iso=iso, inside_above=inside_above,
+                                   stream=stream.cuda_stream)
+            nv, nt = (int(x) for x in counts.cpu())
+            return {"verts": verts[: min(nv, vcap)], "tris": tris[: min(nt, tcap)], "counts": counts}
+
+    def sdf_isosurface_tensor(self, origin, spacing, dims, offset: float = 0.0, **sdf_kw):
+        """The offset surface of the scene: sdf_grid_tensor(origin, spacing, dims, **sdf_kw)'s signed distances, extracted at
+        iso = offset (isosurface_tensor's result plus 'values', the (nz, ny, nx) grid)."""
+        values = self.sdf_grid_tensor(origin, spacing, dims, want="sdf", **sdf_kw)
+        res = self.isosurface_tensor(values, origin, spacing, iso=offset, stream=sdf_kw.get("stream"))
+        res["values"] = values
+        return res
+
+    def winding_isosurface_tensor(self, origin, spacing, dims, level: float = 0.5, beta: float = 2.0):
+        """A watertight stand-in for an open mesh: the `level` surface of |w|, w the winding numbers of winding_grid_tensor, inside where
+        |w| > level (isosurface_tensor's result plus 'values', the (nz, ny, nx) grid of |w|).  Closed as long as no cell on the grid's
+        boundary is crossed: choose a margin over which |w| has fallen below the level."""
+        values = self.winding_grid_tensor(origin, spacing, dims, beta=beta, want="w").abs()
+        res = self.isosurface_tensor(values, origin, spacing, iso=level, inside_above=True)
+        res["values"] = values
+        return res
 
     def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream, reproducible=False):
         import torch

@@ -32,6 +32,7 @@
 #include "cgrt_math.h"
 #include "closest_kernels.h"
 #include "crossing_kernels.h"
+#include "isosurface_kernels.h"
 #include "neighbor_kernels.h"
 #include "point_neighbor_kernels.h"
 #include "poisson_kernels.h"

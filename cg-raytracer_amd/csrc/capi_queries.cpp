@@ -1,5 +1,5 @@
 // capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
-// closest points, crossings, neighbours, signed distance, winding numbers, surface samples, Poisson-disk sets, point-set neighbours.  None of them touches the scene's frame state (workspace, prediction, hints).
+// closest points, crossings, neighbours, signed distance, winding numbers, surface samples, Poisson-disk sets, point-set neighbours, iso-surfaces.  None of them touches the scene's frame state (workspace, prediction, hints).
 // Every family is ONE body for its host-pointer and its device-pointer entries, written with a QueryCall (capi_internal.h): the argument
 // checks in the order include/cgrt.h states (`device`: the pointers' alignment too), the host-only scene, the empty call, then begin,
 // in / out per array, the launch on the call's stream, finish.  The exported entries are one-line forwarders.
@@ -1184,6 +1184,139 @@ int cgrt_debug_point_neighbor_work(CgrtScene* s, const float* data, uint64_t m, 
     // (n <= 0x7fffffff is checked before the capacity n k is looked at)
     return point_neighbor_query(s, false, {data, m, cell, nullptr, 0}, points, n, query, {k > 0, nullptr, k, nullptr, n * (uint64_t)k, nullptr}, 2,
                                 out6, nullptr);
+}
+
+// ---- iso-surfaces (include/cgrt.h cgrt_isosurface*): the triangle mesh of one level of a scalar grid, by marching
+// tetrahedra, in a defined order.  The scene only names the device and lends the call lane; no frame state is read or written; the checks
+// come in the order include/cgrt.h states, all before any device work.
+namespace {
+struct IsoWorkspace {
+    void* d;
+    uint64_t bytes;
+};
+// the output of a list entry (count entries: list false, the rest unused)
+struct IsoMesh {
+    bool list;
+    float* verts;
+    uint64_t vert_capacity;
+    uint32_t* tris;
+    uint64_t tri_capacity;
+};
+int iso_grid(const CgrtGrid* grid, uint64_t* points) {
+    uint64_t n = 1;
+    for (int c = 0; c < 3; c++) {
+        if (grid->dims[c] < 1 || grid->dims[c] > (1u << 24)) return fail(CGRT_E_ARG, "grid dims must be in 1..2^24");
+        n *= grid->dims[c];  // (below 2^52 before the test, which follows every factor)
+        if (n > kIsoMaxPoints) return fail(CGRT_E_ARG, "too many grid points: nx * ny * nz exceeds 2^28");
+        if (!std::isfinite(grid->origin[c]) || !std::isfinite(grid->spacing[c])) return fail(CGRT_E_ARG, "grid origin and spacing must be finite");
+    }
+    *points = n;
+    return CGRT_OK;
+}
+// slots: 0 the values, 1 the vertices, 2 the triangles, 3 the two counts, 4 the workspace (host form: the lane's).  work: the counted
+// classify pass (host form only: out4 in the place of counts2)
+int iso_query(CgrtScene* s, bool device, const CgrtGrid* grid, const float* values, const CgrtIsoParams* params, const IsoMesh& M,
+              uint64_t* counts2, const IsoWorkspace* ws, bool counted, uint64_t* work, void* stream) {
+    if (!s || !grid || !params) return fail(CGRT_E_ARG, "scene, grid or params is NULL");
+    uint64_t N = 0;
+    CGRT_TRY(iso_grid(grid, &N));
+    if (!std::isfinite(params->iso)) return fail(CGRT_E_ARG, "iso must be finite");
+    if (params->flags & ~(uint32_t)CGRT_ISO_INSIDE_ABOVE) return fail(CGRT_E_ARG, "unknown flags");
+    if (!values) return fail(CGRT_E_ARG, "NULL argument: values");
+    if (counted ? !work : !counts2) return fail(CGRT_E_ARG, counted ? "NULL argument: out4" : "NULL argument: counts2");
+    if (M.list && ((M.vert_capacity && !M.verts) || (M.tri_capacity && !M.tris))) return fail(CGRT_E_ARG, "NULL output with a non-zero capacity");
+    if (device && ((uintptr_t)values % 4 || (uintptr_t)M.verts % 4 || (uintptr_t)M.tris % 4 || (uintptr_t)counts2 % 8))
+        return fail(CGRT_E_ARG, "device pointers must be aligned to their elements (d_counts2: 8 bytes)");
+    if (ws) {
+        if (!ws->d) return fail(CGRT_E_ARG, "NULL argument: d_workspace");
+        if ((uintptr_t)ws->d % 8) return fail(CGRT_E_ARG, "d_workspace must be 8-byte aligned");
+        if (ws->bytes < iso_workspace_bytes(N)) return fail(CGRT_E_ARG, "workspace_bytes is below cgrt_isosurface_workspace");
+    }
+    NEED_DEVICE(s);
+    QueryCall c(s, device, stream);
+    void *dv = nullptr, *dverts = nullptr, *dtris = nullptr, *dcounts = nullptr, *dws = nullptr;
+    IsoCall Q{};
+    memcpy(Q.origin, grid->origin, 12);
+    memcpy(Q.spacing, grid->spacing, 12);
+    memcpy(Q.dims, grid->dims, 12);
+    Q.iso = params->iso;
+    Q.above = (params->flags & CGRT_ISO_INSIDE_ABOVE) ? 1u : 0u;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, values, N * 4, "d_values", &dv));
+    Q.values = static_cast<const float*>(dv);
+    if (device) {  // in place on the caller's stream: no slot holds more than the grid can give
+        const uint64_t vmax = std::min<uint64_t>(M.vert_capacity, 7 * N), tmax = std::min<uint64_t>(M.tri_capacity, 12 * N);
+        CGRT_TRY(c.out(1, M.verts, M.list ? vmax * 12 : 0, "d_verts", &dverts));
+        CGRT_TRY(c.out(2, M.tris, M.list ? tmax * 12 : 0, "d_tris", &dtris));
+        CGRT_TRY(c.out(3, counts2, 16, "d_counts2", &dcounts));
+        CGRT_TRY(check_device_span(s, ws->d, iso_workspace_bytes(N), "d_workspace"));
+        Q.list = M.list;
+        Q.verts = static_cast<float*>(dverts);
+        Q.vert_capacity = M.vert_capacity;
+        Q.tris = static_cast<uint32_t*>(dtris);
+        Q.tri_capacity = M.tri_capacity;
+        Q.counts2 = static_cast<unsigned long long*>(dcounts);
+        Q.workspace = ws->d;
+        HIP_TRY(launch_isosurface(Q, nullptr, c.stream()));
+        return c.finish();
+    }
+    HIP_TRY(c.c.scratch(4, iso_workspace_bytes(N), &dws));
+    Q.workspace = dws;
+    if (counted) {
+        CGRT_TRY(c.zero_counters(4));
+        Q.counts2 = c.counters() + 2;
+        HIP_TRY(launch_isosurface(Q, c.counters(), c.stream()));
+        return c.read_counters(work, 4);
+    }
+    // the count, read back; then the list into buffers no larger than what will be written (a caller may over-allocate freely), so that
+    // nothing beyond the written records reaches the caller's arrays
+    HIP_TRY(c.c.scratch(3, 16, &dcounts));
+    Q.counts2 = static_cast<unsigned long long*>(dcounts);
+    HIP_TRY(launch_isosurface(Q, nullptr, c.stream()));
+    unsigned long long h[2];
+    HIP_TRY(hipMemcpyAsync(h, dcounts, 16, hipMemcpyDeviceToHost, c.stream()));
+    HIP_TRY(hipStreamSynchronize(c.stream()));
+    const uint64_t nv = M.list ? std::min<uint64_t>(M.vert_capacity, h[0]) : 0, nt = M.list ? std::min<uint64_t>(M.tri_capacity, h[1]) : 0;
+    if (nv || nt) {
+        CGRT_TRY(c.out(1, M.verts, nv * 12, "verts", &dverts));
+        CGRT_TRY(c.out(2, M.tris, nt * 12, "tris", &dtris));
+        Q.list = true;
+        Q.verts = static_cast<float*>(dverts);
+        Q.vert_capacity = nv;
+        Q.tris = static_cast<uint32_t*>(dtris);
+        Q.tri_capacity = nt;
+        HIP_TRY(launch_isosurface(Q, nullptr, c.stream()));
+    }
+    counts2[0] = h[0];
+    counts2[1] = h[1];
+    return c.finish();
+}
+}  // namespace
+
+int cgrt_isosurface_workspace(CgrtScene* s, const CgrtGrid* grid, uint64_t* bytes) {
+    if (!s || !grid || !bytes) return fail(CGRT_E_ARG, "NULL argument");
+    uint64_t N = 0;
+    CGRT_TRY(iso_grid(grid, &N));
+    *bytes = iso_workspace_bytes(N);
+    return CGRT_OK;
+}
+int cgrt_isosurface_count_device(CgrtScene* s, const CgrtGrid* grid, const float* d_values, const CgrtIsoParams* params, uint64_t* d_counts2,
+                                 void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    const IsoWorkspace ws{d_workspace, workspace_bytes};
+    return iso_query(s, true, grid, d_values, params, {false, nullptr, 0, nullptr, 0}, d_counts2, &ws, false, nullptr, stream);
+}
+int cgrt_isosurface_device(CgrtScene* s, const CgrtGrid* grid, const float* d_values, const CgrtIsoParams* params, float* d_verts,
+                           uint64_t vert_capacity, uint32_t* d_tris, uint64_t tri_capacity, uint64_t* d_counts2, void* d_workspace,
+                           uint64_t workspace_bytes, void* stream) {
+    const IsoWorkspace ws{d_workspace, workspace_bytes};
+    return iso_query(s, true, grid, d_values, params, {true, d_verts, vert_capacity, d_tris, tri_capacity}, d_counts2, &ws, false, nullptr, stream);
+}
+int cgrt_isosurface(CgrtScene* s, const CgrtGrid* grid, const float* values, const CgrtIsoParams* params, float* verts, uint64_t vert_capacity,
+                    uint32_t* tris, uint64_t tri_capacity, uint64_t* counts2) {
+    return iso_query(s, false, grid, values, params, {true, verts, vert_capacity, tris, tri_capacity}, counts2, nullptr, false, nullptr, nullptr);
+}
+int cgrt_debug_isosurface_work(CgrtScene* s, const CgrtGrid* grid, const float* values, const CgrtIsoParams* params, uint64_t* out4) {
+    return iso_query(s, false, grid, values, params, {false, nullptr, 0, nullptr, 0}, nullptr, nullptr, true, out4, nullptr);
 }
 
 }  // extern "C"

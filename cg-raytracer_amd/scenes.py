@@ -433,3 +433,31 @@ def make_blob(ntris_target: int = 2000, seed: int = 7) -> SceneData:
     )
     center_and_scale_to_unit(sd)
     return sd
+
+
+def mesh_scene_data(verts, tris, material=None) -> SceneData:
+    """A SceneData from an indexed mesh (verts (nv, 3) float32, tris (nt, 3) vertex indices) -- what Scene.isosurface returns becomes a
+    Scene in one line.  Vertex normals are the area-weighted sums of the face normals (the cross products themselves, accumulated in
+    float64), normalised; a zero sum gives (0, 0, 1).  One mesh, one material (8 floats: kd ks shininess transparency; None: grey)."""
+    v = np.ascontiguousarray(np.asarray(verts, F32).reshape(-1, 3))
+    t = np.ascontiguousarray(np.asarray(tris).reshape(-1, 3).astype(np.int64))
+    if len(t) and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError("a triangle names a vertex that does not exist")
+    p = v.astype(np.float64)
+    fn = np.cross(p[t[:, 1]] - p[t[:, 0]], p[t[:, 2]] - p[t[:, 0]])
+    n = np.zeros_like(p)
+    for k in range(3):
+        np.add.at(n, t[:, k], fn)
+    ln = np.linalg.norm(n, axis=1)
+    ok = np.isfinite(ln) & (ln > 0.0)
+    n[ok] /= ln[ok, None]
+    n[~ok] = (0.0, 0.0, 1.0)
+    mat = np.asarray([0.8, 0.8, 0.8, 0.5, 0.5, 0.5, 225.0, 1.0] if material is None else material, F32).reshape(1, 8)
+    return SceneData(
+        pos_nrm=np.concatenate([v, n.astype(F32)], 1),
+        tri=t.astype(np.uint32),
+        tri_mesh=np.zeros(len(t), np.uint32),
+        materials=mat,
+        point_lights=np.asarray([[-1, 1, -1, 1, 1, 1]], F32),
+        name=f"mesh{len(t)}",
+    )

@@ -1427,6 +1427,79 @@ int cgrt_list_point_neighbors_brute(CgrtScene* scene, const float* data, uint64_
 int cgrt_debug_point_neighbor_work(CgrtScene* scene, const float* data, uint64_t m, float cell, const float* points, uint64_t n,
                                    const CgrtPointQuery* query, uint32_t k, uint64_t* out6);
 
+/* Iso-surfaces: the way back from a volume to a surface -- the indexed triangle mesh of one level of a scalar
+ * grid, by marching tetrahedra (six per cell around the main diagonal: no ambiguous case, closed by construction).  The values are the
+ * caller's: what cgrt_signed_distance_grid or cgrt_winding_numbers_grid made (offset and shell surfaces, the 0.5 level of an open mesh's
+ * winding field as its watertight stand-in), or anything else.  The output is defined to the last bit and to the last index: a pure
+ * function of (grid, values, iso, flags), whatever the launch shape, the stream, the thread or the run.  The scene names the device and
+ * lends its call lanes; its geometry is not read.  All f32 arithmetic is IEEE, every operation rounded on its own, nothing contracted.
+ * Inputs.  grid: a CgrtGrid.  values: nx ny nz f32 in the result order of cgrt_signed_distance_grid, index (iz ny + iy) nx + ix.  params
+ * (CgrtIsoParams, not NULL): iso (finite) and flags (0 or CGRT_ISO_INSIDE_ABOVE).
+ * Limits.  Each dim in 1..2^24; nx ny nz <= 2^28 (7 vertices and 12 triangles per point stay below 2^32); origin and spacing finite.  A grid
+ * with a dim of 1 has no cell and gives the empty mesh: no vertex, no triangle.
+ * Classification.  A grid point is finite iff its value is.  It is inside iff value < iso, strictly; with CGRT_ISO_INSIDE_ABOVE iff
+ * value > iso -- the definition applied to the negated values and the negated level: the positions are the same bits, the triangles face
+ * the other way.  A value equal to iso is outside under either flag.
+ * Edges.  Point q = (ix, iy, iz) owns up to seven edges, to q + (dx, dy, dz) with (dx, dy, dz) in {0,1}^3 without 0; the edge's type is
+ * e = dx + 2 dy + 4 dz - 1, in 0..6.  An owned edge exists where its far end is in the grid.  It carries a vertex iff both ends are finite
+ * and exactly one of them is inside.
+ * Vertex.  A the owner, B the far end: t = fl(fl(iso - vA) / fl(vB - vA)); if !(t >= 0) then t = 0; if t > 1 then t = 1;
+ * p.c = fl(pA.c + fl(t fl(pB.c - pA.c))) per component, with the grid positions origin.c + (float)i spacing.c of cgrt_signed_distance_grid.
+ * Vertices are ordered by the owner's index (iz ny + iy) nx + ix, then by edge type.
+ * Cells.  The cell of q (ix < nx - 1, iy < ny - 1, iz < nz - 1) has corners c = x + 2 y + 4 z.  Its six tetrahedra, in this order and
+ * corner order, all positively oriented: (0,1,3,7) (0,5,1,7) (0,3,2,7) (0,2,6,7) (0,4,5,7) (0,6,4,7).  A tetrahedron with a non-finite
+ * corner emits nothing.  Otherwise mask m has bit k set iff its k-th corner is inside, and it emits the triangles of row m below; a table
+ * vertex names a tetrahedron edge by its two corner positions, and a triangle is listed in the order its indices are written:
+ *    1: (01,02,03)             14: (01,03,02)
+ *    2: (01,13,12)             13: (01,12,13)
+ *    4: (02,12,23)             11: (02,23,12)
+ *    8: (03,23,13)              7: (03,13,23)
+ *    3: (02,03,13) (02,13,12)  12: (02,12,13) (02,13,03)
+ *    5: (01,23,03) (01,12,23)  10: (01,23,12) (01,03,23)
+ *    6: (01,13,23) (01,23,02)   9: (01,02,23) (01,23,13)
+ *    0, 15: nothing
+ * Normals by the right-hand rule point from inside to outside: for an SDF the mesh is outward-oriented and encloses positive signed
+ * volume.  A triangle's index is its vertex's rank in the vertex order (the edge between cell corners lo < hi is owned by corner lo, type
+ * hi - lo - 1).  Triangles are ordered by the cell's index, then tetrahedron, then table position.
+ * Properties.  If every value is finite and no cell on the grid's boundary is crossed, every directed edge occurs exactly once and its
+ * reverse exactly once.  A value equal to iso puts vertices on the grid point and gives zero-area triangles, which are kept.  Next to
+ * non-finite values there may be unreferenced vertices and open borders.  Scaling by a power of two is exact within f32's range:
+ * multiplying origin and spacing by 2^k multiplies the vertices by 2^k and changes nothing else; multiplying values and iso by 2^k
+ * changes nothing.
+ * Outputs.  verts: 3 f32 per vertex.  tris: 3 u32 per triangle.  counts2 = {vertices, triangles}, always the full counts (device forms:
+ * device memory, 8-byte aligned; host form: host memory).  Vertex j is written iff j < vert_capacity, triangle j iff j < tri_capacity, its
+ * indices as they are even where >= vert_capacity; nothing else in or outside the arrays is touched (the slot rule of the crossing lists).
+ * cgrt_isosurface_device is self-contained: it redoes the count inside its workspace, so a caller who over-allocates needs one call.
+ * Both device forms only enqueue on `stream` (NULL = default stream) and read nothing back.  The host form (host pointers) runs on a call
+ * lane like cgrt_closest_points and blocks: any number of threads may call at once.
+ * Workspace (device forms).  cgrt_isosurface_workspace reports the bytes a call on `grid` needs (6 per grid point, 1/16 per point for the
+ * block totals, under 20 KB of padding): caller-owned device memory, 8-byte aligned, contents need no initialisation, not shared between
+ * calls in flight.
+ * cgrt_debug_isosurface_work (host form, a counted run): out4 = {cells that emit a triangle, tetrahedra that emit one, vertices, triangles}.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene, grid or params; the grid's limits; iso not finite, or an
+ * unknown flag; NULL values; NULL counts2 (out4); NULL verts or tris with a non-zero capacity; (device forms) d_values, d_verts or d_tris
+ * not 4-byte aligned, d_counts2 not 8-byte aligned; (device forms) d_workspace NULL, not 8-byte aligned, or workspace_bytes below
+ * cgrt_isosurface_workspace.  Then a host-only scene: CGRT_E_NO_DEVICE (not cgrt_isosurface_workspace, which only computes: NULL argument,
+ * then the grid's limits).  Device forms: then d_values (4 bytes per point), d_verts (12 bytes per vertex of min(vert_capacity, 7 per point)),
+ * d_tris (likewise, 12 per point), d_counts2 (16 bytes) and d_workspace checked as device memory of the scene's device.  No form reads or
+ * writes the prediction record, the frame hints, the layout or any frame state.
+ * Not offered: marching cubes, dual contouring or sharp features; vertex normals or gradients as outputs; removal of zero-area triangles
+ * and unreferenced vertices; a narrow-band mode that skips empty bricks; batched grids; the C++ host mirror. */
+#define CGRT_ISO_INSIDE_ABOVE 1u
+typedef struct CgrtIsoParams {
+    float iso;      /* the level; not finite -> CGRT_E_ARG */
+    uint32_t flags; /* 0, or CGRT_ISO_INSIDE_ABOVE */
+} CgrtIsoParams;
+int cgrt_isosurface_workspace(CgrtScene* scene, const CgrtGrid* grid, uint64_t* bytes);
+int cgrt_isosurface_count_device(CgrtScene* scene, const CgrtGrid* grid, const float* d_values, const CgrtIsoParams* params,
+                                 uint64_t* d_counts2, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int cgrt_isosurface_device(CgrtScene* scene, const CgrtGrid* grid, const float* d_values, const CgrtIsoParams* params, float* d_verts,
+                           uint64_t vert_capacity, uint32_t* d_tris, uint64_t tri_capacity, uint64_t* d_counts2, void* d_workspace,
+                           uint64_t workspace_bytes, void* stream);
+int cgrt_isosurface(CgrtScene* scene, const CgrtGrid* grid, const float* values, const CgrtIsoParams* params, float* verts,
+                    uint64_t vert_capacity, uint32_t* tris, uint64_t tri_capacity, uint64_t* counts2);
+int cgrt_debug_isosurface_work(CgrtScene* scene, const CgrtGrid* grid, const float* values, const CgrtIsoParams* params, uint64_t* out4);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
