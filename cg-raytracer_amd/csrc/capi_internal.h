@@ -1,5 +1,6 @@
-// capi_internal.h -- what the translation units of the C-ABI (capi.cpp, capi_lanes.cpp, capi_queries.cpp, capi_prims.cpp) share:
-// error reporting, the scene, the helpers more than one of them calls, the call lanes.  Host code only: no .hip file includes it.
+// capi_internal.h -- what the translation units of the C-ABI (capi.cpp, capi_combine.cpp, capi_primary.cpp, capi_frames.cpp,
+// capi_frame_entries.cpp, capi_multi.cpp, capi_lanes.cpp, capi_queries.cpp, capi_prims.cpp) share: error reporting, the scene, the helpers
+// more than one of them calls, the call lanes.  The shaded frame's units share capi_frames.h besides.  Host code only: no .hip file includes it.
 // What it declares in namespace cgrt has hidden visibility: libcgrt.so exports include/cgrt.h's entries, not these.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -57,6 +58,7 @@ extern std::atomic<int> g_frame_gate;      // cgrt_set_frame_gate: 1 = tiles out
 extern std::atomic<int> g_primary_mode;  // 0 = one wave per tile, 1 = persistent waves with lane refill
 
 // Every failure returns through these: the message is cgrt_last_error()'s, per thread (capi.cpp)
+extern thread_local std::string g_err;
 int fail(int code, const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
 #define HIP_TRY(expr)                                  \
@@ -86,10 +88,13 @@ struct DevBuf {
 int select_device(int device);
 CameraDev make_camera(const CgrtCamera& c);
 bool make_frame(int W, int H, int x0, int y0, int x1, int y1, int rank, int nranks, int block, FrameDev& F);
+bool make_views_frame(int W, int H, uint32_t nviews, int block, FrameDev& F);
+bool frame_gate_rect(const CameraDev& C, const Box6& box, int W, int H, int out[4]);
+unsigned long long owned_pixels(const FrameDev& F);
 }  // namespace cgrt
 #pragma GCC visibility pop
 
-// The slots of a scene's device workspace (CgrtScene::work), by what the shaded frame keeps in them (Wavefront and render_impl below).  A
+// The slots of a scene's device workspace (CgrtScene::work), by what the shaded frame keeps in them (capi_frames.cpp Wavefront and render_impl).  A
 // level's list (rays / hits / normals / pixels) has four buffer sets and its shadow list two; their numbers are not contiguous because
 // slots were added as features came.
 enum WorkSlotId {
@@ -127,7 +132,7 @@ struct CgrtScene {
     // launch that used it last (an event per block), so any number of frames may be in flight on any streams
     std::mutex queue_mutex;
     unsigned launch_seq = 0;
-    // Frame hints (cgrt_layout.h HintDev; attach_hints below): the hard-tile lists a primary frame leaves for the next frame of
+    // Frame hints (cgrt_layout.h HintDev; capi_primary.cpp attach_hints): the hard-tile lists a primary frame leaves for the next frame of
     // the same shape.  Guarded by hints_mutex while a launch is being issued; the buffers themselves are only touched by kernels.
     struct FrameHints {
         std::mutex mu;
@@ -284,7 +289,7 @@ struct CgrtScene {
         std::vector<uint32_t> counts;
         int last_path = 0;  // how the last frame was drawn: 0 exact, 1 as predicted, 2 predicted, found too small, drawn again exactly
     } rpred;
-    // Enqueued frames (cgrt_enqueue_*; enqueue_impl below): a ring of ENQ_SLOTS ticket slots, each with pinned
+    // Enqueued frames (cgrt_enqueue_*; capi_frames.cpp enqueue_impl): a ring of ENQ_SLOTS ticket slots, each with pinned
     // staging for the frame's tables (copied to enq_dev by hipMemcpyAsync on the caller's stream), a pinned read-back of its counter block
     // and the events behind it.  A slot is refilled only once its last frame has finished.  Every frame of the scene (enqueued or blocking)
     // starts behind the last enqueued one on the device (enq_done), so all of them share the workspace above.
@@ -383,53 +388,29 @@ struct CgrtScene {
     }
 };
 
-struct WsBuf {  // a slot of the scene's workspace, with DevBuf's interface
-    CgrtScene* sc;
-    int slot;
-    void* p = nullptr;
-    hipError_t alloc(size_t bytes) {
-        CgrtScene::WorkSlot& w = sc->work[slot];
-        if (w.cap < bytes || !w.p) {
-            // enqueued frames (and a blocking frame's export) may still use the buffer: they finish before it is released
-            if (w.p && sc->enq_pending) {
-                const hipError_t e = hipEventSynchronize(sc->enq_done);
-                if (e != hipSuccess) return e;
-                sc->enq_pending = false;
-            }
-            if (w.p && sc->export_pending) {
-                const hipError_t e = hipEventSynchronize(sc->export_done);
-                if (e != hipSuccess) return e;
-            }
-            if (w.p) (void)hipFree(w.p);
-            w.p = nullptr;
-            w.cap = 0;
-            const hipError_t e = hipMalloc(&w.p, bytes ? bytes : 1);
-            if (e != hipSuccess) return e;
-            w.cap = bytes ? bytes : 1;
-        }
-        p = w.p;
-        return hipSuccess;
-    }
-    size_t cap() const { return sc->work[slot].cap; }
-    template <class T>
-    T* as() const {
-        return static_cast<T*>(p);
-    }
-};
-
 #define NEED_DEVICE(s) \
     if ((s)->device < 0) return fail(CGRT_E_NO_DEVICE, "scene was created host-only (CGRT_DEVICE_NONE); there is no CPU traversal path")
 
 #pragma GCC visibility push(hidden)
 namespace cgrt {
 // ---- capi.cpp
-int check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, const char* name);
-int soft_rules(const CgrtSoftShadows* soft);
+hipError_t staged_h2d(void* dst, const void* src, size_t bytes);
+
+// ---- capi_primary.cpp
+void apply_frame_gate(const CgrtScene* s, const CameraDev& C, FrameDev& F);
 SoftDev soft_dev(const CgrtSoftShadows& soft, unsigned SL, const float* lights, const float* units);
+int views_extent_args(uint32_t nviews, int W, int H);
+int raycams_check(const CgrtRayCamera* cams, uint32_t nviews, int W, int H);
 int views_args(const void* cams, uint32_t nviews, int W, int H, const CgrtRayCamera* ray = nullptr);
 std::vector<uint8_t> view_table(const CgrtCamera* cams, const CgrtRayCamera* raycams, uint32_t nviews);
 int launch_with_view_table(CgrtScene* s, const std::vector<uint8_t>& tab, hipStream_t st, const std::function<hipError_t(const void*)>& launch);
-hipError_t staged_h2d(void* dst, const void* src, size_t bytes);
+
+// ---- capi_frame_entries.cpp
+int check_device_span(const CgrtScene* s, const void* p, uint64_t bytes, const char* name);
+int soft_rules(const CgrtSoftShadows* soft);
+int aa_args(const CgrtCamera* cam, const void* out, int W, int H, const float* lights, uint32_t nlights, const CgrtSoftShadows* soft,
+            int max_level, int rank, int nranks);
+int export_args(const void* out, int W, int H, int format, uint64_t row_bytes, uint64_t* pitch, uint64_t* extent);
 
 // ---- capi_lanes.cpp
 void parallel_copy(void* dst, const void* src, size_t bytes);  // large host copies on a few threads

@@ -199,7 +199,7 @@ struct HintDev {  // one per rotation phase, resident in device memory
     uint32_t* count_z;       // the third set's counter, zeroed by this frame
     uint32_t* ctl;           // shared by the phases: [0] the threshold in force (s_memrealtime ticks, 100 MHz, for a 64-ray wave)
     uint32_t* mailbox;       // pinned host memory: {generation, length of the list this frame reads, threshold} -- what the host
-                             // learns about the lists without ever waiting for the device (capi.cpp attach_hints)
+                             // learns about the lists without ever waiting for the device (capi_primary.cpp attach_hints)
     uint32_t cap;            // tiles a list holds (<= 0xfffe)
     uint32_t per_tile;       // workgroups per hard tile: 1 or 4
     // The threshold follows the scene: how many tiles are worth treating specially is a matter of their SHARE of the frame (best

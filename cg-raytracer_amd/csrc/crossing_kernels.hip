@@ -11,7 +11,7 @@
 // The per-lane stack is lane-interleaved in LDS, one dword per entry.  A lane owns its slot of the output and keeps it sorted in global
 // memory by insertion, dropping the largest when full: no atomics, no scratch (query_device.h QuerySlot).
 // k_crossings<.., BRUTE>: every record in turn for every ray, same function, same slot rule (validation, and the whole call on scenes
-// where the conservative argument does not hold: capi.cpp crossing_brute_scene).
+// where the conservative argument does not hold: capi_queries.cpp crossing_brute_scene).
 #include <hip/hip_runtime.h>
 
 #include "crossing_device.h"

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_spawn(const float* __restr
         if (tot) atomicAdd(counters + 2, tot);
     }
 }
-// The count-driven forms of this file's list kernels (enqueued frames, capi.cpp enqueue_impl): dcount is required, n is the list's
+// The count-driven forms of this file's list kernels (enqueued frames, capi_frames.cpp enqueue_impl): dcount is required, n is the list's
 // capacity, and a capped grid strides over the *dcount entries present, gridDim.x * blockDim.x at a time (the loops are uniform per
 // workgroup, as block_append needs).  An entry is handled by the expressions of the one-pass kernel: the results are its results.
 __global__ __launch_bounds__(CGRT_SHADE_BLOCK) void k_spawn_strided(const float* __restrict__ rays, const CgrtHitDev* __restrict__ hits,

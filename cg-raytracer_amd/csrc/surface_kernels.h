@@ -10,7 +10,7 @@
 namespace cgrt {
 
 // Per prim_id < ntris: where the triangle's TriRecord lives and which rows of a per-vertex table belong to its three vertices.  Built by
-// capi.cpp on the first surface call of a scene (16 bytes per triangle), never by a scene that makes none.
+// capi_queries.cpp on the first surface call of a scene (16 bytes per triangle), never by a scene that makes none.
 struct SurfaceLookup {
     uint32_t record;  // index into SceneDev::tris (the global record array)
     uint32_t v[3];    // tri[prim_id][0..2] as given to cgrt_scene_create

@@ -30,7 +30,7 @@ struct SoftDev {
     const uint32_t* set_index;
 };
 
-// A batch of light sets on the device (capi.cpp LightSetSrc; cgrt_render_light_sets*): set b holds the point lights point_off[b] ..
+// A batch of light sets on the device (capi_frames.h LightSetSrc; cgrt_render_light_sets*): set b holds the point lights point_off[b] ..
 // point_off[b + 1] - 1 and the spherical lights sph_off[b] .. sph_off[b + 1] - 1, in the caller's order.  Light k is two float4s
 // {position, slot}, {colour, 0}; slot (the bits of .w) is its distinct entry: the light index k_spawn traced its shadow ray with, or
 // the soft-shadow key whose samples k_soft_shadow_sets counted.
@@ -126,7 +126,7 @@ hipError_t launch_trace_list_compact(const SceneDev& S, const float* in_rays, un
                                      int* pixels, uint32_t* count, float* rgb, hipStream_t stream, unsigned long long* counters = nullptr);
 hipError_t launch_clear_owned(const FrameDev& F, float* rgb, hipStream_t stream);
 // shading wavefront (shade_kernels.hip); every level is a compact list of live paths
-// One level of it, as the launchers below take it: typed device pointers into the frame's workspace (capi.cpp Wavefront::level -- the
+// One level of it, as the launchers below take it: typed device pointers into the frame's workspace (capi_frames.cpp Wavefront::level -- the
 // only place that knows which buffer set a level lives in).  A plain value, built on the stack per launch group.
 struct LevelDev {
     float* rays;  // the level's list: a ray, a hit, a normal and a pixel per entry

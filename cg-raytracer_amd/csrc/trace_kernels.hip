@@ -164,7 +164,7 @@ __global__ CGRT_LB void k_trace_primary_compact(SceneDev S, CameraDev C, FrameDe
     // one atomic per workgroup (same-address atomics serialise at the L2); the workgroup's LDS is only released when its
     // last wave ends anyway, so waiting for it here costs no occupancy
     const bool keep = active && writer && h.hit != 0;
-    // Fused level-0 spawn (a predicted frame, capi.cpp render_impl; k_spawn's work from this lane's registers, spawn_rays.h): does
+    // Fused level-0 spawn (a predicted frame, capi_frames.cpp render_impl; k_spawn's work from this lane's registers, spawn_rays.h): does
     // the hit want a mirror ray?  (The parameters are read from device memory HERE: as kernel arguments they were loaded before
     // the walk and their 22 scalar registers pushed the walk into scratch.)
     F3 ks = f3(0.f, 0.f, 0.f);
@@ -316,7 +316,7 @@ __global__ CGRT_LB void k_trace_list_compact(SceneDev S, const float* __restrict
     }
 }
 // Two lists in ONE launch: a level's shadow list (occlusion queries, k_trace_shadow's body) and its mirror list (closest hits,
-// k_trace_batch's body), workgroups dealt alternately so that both are on the chip at once.  A predicted frame (capi.cpp
+// k_trace_batch's body), workgroups dealt alternately so that both are on the chip at once.  A predicted frame (capi_frames.cpp
 // render_impl) used to run them on two streams; the event that started the second stream and the wait that joined it again cost
 // ~17 us of an idle GPU per frame (profiles/r3_config3.txt) -- one launch on one stream needs neither.  Lane shapes only (64 or 16
 // rays per single-wave workgroup, by the host's estimate or on the device: see "kernel shape per launch").
@@ -372,7 +372,7 @@ __device__ __forceinline__ void pair_b_wg(const SceneDev& S, const ListPairDev& 
     walk_tree<false, FAST>(S, active, o, d, t, hit_rec, CGRT_WAVE_STACK(s_lds), CGRT_WAVE_MAP(s_lds), cnt);
     if (active) finish_ray(S, o, d, t, hit_rec, P.hits_b + i, P.normals_b ? P.normals_b + 3 * i : nullptr);
 }
-// STRIDED (enqueued frames, capi.cpp enqueue_impl): the grid is capped (P.blocks_a / P.blocks_b workgroups per list, whatever the lists'
+// STRIDED (enqueued frames, capi_frames.cpp enqueue_impl): the grid is capped (P.blocks_a / P.blocks_b workgroups per list, whatever the lists'
 // capacities) and each workgroup strides over the entries its list's device count holds, blocks_a (blocks_b) workgroups at a time.
 template <bool FAST, bool STRIDED = false>
 __global__ CGRT_LB void k_trace_pair(SceneDev S, ListPairDev P) {
@@ -488,7 +488,7 @@ __device__ __forceinline__ void trace_batch_wg(const SceneDev& S, const float* _
 }
 // dcount (optional): device word holding the number of rays actually present (<= n); the grid covers n.  The shapes: see the
 // comment in the body.
-// STRIDED (lane shapes, enqueued frames): the grid is capped instead (capi.cpp enqueue_impl) and each workgroup strides over the rays
+// STRIDED (lane shapes, enqueued frames): the grid is capped instead (capi_frames.cpp enqueue_impl) and each workgroup strides over the rays
 // present, gridDim.x workgroups at a time; the rays' layout on the lanes is the one a full grid gives them.
 template <bool COUNT, bool FAST, bool QUAD = false, bool STRIDED = false>
 __global__ CGRT_LB void k_trace_batch(SceneDev S, const float* __restrict__ rays, unsigned long long n,
@@ -946,7 +946,7 @@ static unsigned lane_grid(unsigned long long n, unsigned block, unsigned rpw, un
     if (adapt_max) return std::max(grid_for(n, block), grid_for(std::min<unsigned long long>(n, adapt_max), 16));
     return grid_for(n, rpw < 64u ? rpw : block);
 }
-// ---- capped, count-driven grids (GRID_STRIDED; enqueued frames: capi.cpp enqueue_impl) ----
+// ---- capped, count-driven grids (GRID_STRIDED; enqueued frames: capi_frames.cpp enqueue_impl) ----
 // Every list of an enqueued frame is sized for the worst case and only the device knows its length, so a launch covers at most
 // strided_waves() waves, whatever the capacity, and its workgroups stride over the entries present (the STRIDED instantiations).
 // The default is twice the walk waves the chip holds at once (256 CUs x 4 SIMDs x 3 waves); CGRT_STRIDED_WAVES overrides it.
@@ -1208,7 +1208,7 @@ hipError_t launch_in_shadow(const SceneDev& S, const float* points, unsigned lon
     return launch_visibility<true>(S, points, lights, nlights, npoints * nlights, out, stream);
 }
 // One word into host-visible memory, behind whatever the stream holds: lets a host thread wait for a launch by looking at its own
-// memory instead of sleeping in a runtime call (capi.cpp combined_intersect).
+// memory instead of sleeping in a runtime call (capi_combine.cpp combined_intersect).
 __global__ void k_signal(uint32_t* __restrict__ flag, uint32_t value) {
     if (threadIdx.x == 0 && blockIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }

@@ -202,7 +202,7 @@ def test_end_to_end_image(pkg, orc, scene_data, tmp_path, nrep):
 
 
 # ---------------------------------------------------------------------------------------------------
-# call combining: concurrent per-ray calls share launches inside the library (capi.cpp combined_intersect)
+# call combining: concurrent per-ray calls share launches inside the library (capi_combine.cpp combined_intersect)
 # ---------------------------------------------------------------------------------------------------
 def test_64_threads_of_per_ray_calls_equal_one_batch(pkg, orc):
     """VERDICT r2 item 2: 64 threads x 10 000 BoundingVolumeHierarchy::intersect(Ray&, HitInfo&) calls on ONE object (the

@@ -1,4 +1,4 @@
-"""GPU tests of the primary frames' HINTS (cgrt_layout.h HintDev, capi.cpp attach_hints, include/cgrt.h cgrt_set_frame_hints): the
+"""GPU tests of the primary frames' HINTS (cgrt_layout.h HintDev, capi_primary.cpp attach_hints, include/cgrt.h cgrt_set_frame_hints): the
 tiles whose wave took long in one frame are traced first (mode 1) or as four 16-ray waves (mode 2) by the next frame of the same
 shape.  Only order and layout change, so every frame must equal the unhinted frame -- and through it the oracle -- bit for bit:
 hits, t bits, primitive and material ids, normals; whole frames, rectangles, rank tiles, frames not divisible by the tile size,
@@ -103,7 +103,7 @@ def test_hints_on_thin_leaf_scenes_and_every_walk(pkg, scene_data, hints):
 
 def test_hints_go_dormant_and_come_back(pkg, scene_data, hints):
     """A scene without long waves: after eight frames with empty lists the library traces 56 frames without hints, then probes
-    again (capi.cpp attach_hints) -- 150 frames cross that cycle twice; and a threshold that adapts (HintDev::ctl) while the camera
+    again (capi_primary.cpp attach_hints) -- 150 frames cross that cycle twice; and a threshold that adapts (HintDev::ctl) while the camera
     keeps moving."""
     sd = scene_data("monkey")
     W, H = 256, 192

@@ -8,7 +8,7 @@ every round appends one seed):
     with frame hints (hard tiles first / as 16-ray waves, thresholds of 20 .. 400 ticks) against the plain frame byte for byte;
   * render: cgrt_render (random scene, camera, 1-3 point lights, depth 0-4) against the oracle's recursive per-pixel driver:
     RGB <= 1e-5 (BASELINE.json north_star's tolerance), equal ray counts, certified == exact == quad-shape frames byte for byte
-    (the first frame of a scene is exactly sized, the later ones are predicted frames: capi.cpp render_impl);
+    (the first frame of a scene is exactly sized, the later ones are predicted frames: capi_frames.cpp render_impl);
   * shade: tools/fuzz_shade.py, every shading entry (frames, anti-aliased frames, ray lists) with spherical lights, spheres and
     depths up to 16 against the oracle, RGB <= 1e-5 and ray counts equal by kind; and its occlusion leg: the shadow verdicts of
     cgrt_debug_trace_shadow in every kernel shape and on every path against the oracle's.

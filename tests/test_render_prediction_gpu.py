@@ -1,4 +1,4 @@
-"""GPU tests of cgrt_render's predicted frames (capi.cpp render_impl; include/cgrt.h cgrt_set_render_prediction).
+"""GPU tests of cgrt_render's predicted frames (capi_frames.cpp render_impl; include/cgrt.h cgrt_set_render_prediction).
 A frame of the same shape as the scene's previous frame is issued in one go -- every launch sized from what the previous frame found
 per level, the kernels stopping at the counts on the device -- and checked once behind the frame; a frame whose lists outgrew their
 launches, or that reaches a level the previous frame did not, is drawn again the exact way.  Same kernels on the same lists, so the
