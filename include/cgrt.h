@@ -1291,6 +1291,13 @@ int cgrt_debug_get_sample_table(CgrtScene* scene, uint32_t* thresholds, uint32_t
  * Conflict.  dx = fl(x_i - x_j), dy and dz likewise; d2 = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)), nothing contracted; the value is the
  * same for (i, j) and (j, i).  i and j conflict iff both are finite, i != j and d2 < min_dist2, strictly.  A d2 that overflows to +inf
  * is never a conflict.  min_dist2 NaN or <= 0: nothing conflicts, every finite point is kept.  min_dist2 == +inf: CGRT_E_ARG.
+ * Envelope.  d2 is a sum of squares of differences: it grows as the SQUARE of the cloud's size.  Multiplying every point by 2^k and
+ * min_dist2 by 2^2k changes no significand, so while, for every pair, the smallest non-zero |dx|, |dy|, |dz| still has a normal square,
+ * d2 does not overflow, and min_dist2 * 2^2k is a normal float, every operation rounds as at scale 1 and the flags are those of scale 1
+ * (tests/scale_ref.py in_point_envelope states the predicate).  Outside it the flags are still the defined ones on every path -- grid,
+ * brute and restatement agree byte for byte -- they are only no longer the flags of scale 1: subnormal squares lose bits (a
+ * subnormal min_dist2 of a few ulps keeps other points), a min_dist2 that underflows to 0 keeps every finite point, a d2 of +inf never
+ * conflicts, and a cloud whose extent overflows f32 (x - lo = +inf) is binned into the last cell, 2^21 - 1, of that axis.
  * Result.  Going through the points in the order, i is kept iff it is finite and no point kept before it conflicts with it: the
  * lexicographically first maximal independent set of the conflict graph, which is unique.  No two kept points conflict, and every finite
  * point that is not kept conflicts with a kept point that comes before it.
@@ -1362,6 +1369,16 @@ int cgrt_debug_poisson_work(CgrtScene* scene, const float* points, uint64_t n, c
  * sum one (over non-negative terms, whose relative errors do not grow under addition), the second sum one: the x and y terms pass through
  * 2 + 1 + 1 + 1 = 5 factors, the z term through 4.  Membership can therefore differ from the float64 answer only for pairs whose exact
  * squared distance lies within that relative band of r2 (tests/test_point_neighbors_cpu.py).
+ * Envelope.  d2 grows as the SQUARE of the cloud's size.  Multiplying data, queries (and the cell) by 2^k and every bound by 2^2k
+ * changes no significand.  A query is inside the envelope at 2^k while (min |dx|)^2 * 2^2k >= FLT_MIN, min |dx| the smallest non-zero
+ * coordinate difference between it and any finite data point; (max d2) * 2^2k <= FLT_MAX, over the finite data points; r2 * 2^2k is a
+ * normal float; and the query and r2 are finite (tests/scale_ref.py point_measures, in_point_envelope).  Inside it every operation of
+ * d2 rounds as at scale 1: counts and index order are unchanged, every dist2 is multiplied by 2^2k exactly, and the search visits the
+ * images of the same cells (the work counters are equal).  Outside it the bytes are still the defined ones on every path -- grid form,
+ * brute form and the definition agree -- only the relation to scale 1 is lost: subnormal d2 lose bits and tie; where r2 and every d2
+ * underflow to 0 every finite data point is a neighbour of every finite query, in index order; a d2 of +inf qualifies under r2 = +inf
+ * only and ties on index; a cloud whose x - lo overflows is binned into cell 2^21 - 1 of that axis; a subnormal cell or bound is taken
+ * as it is (the reach R of a subnormal r2 is a normal float).
  * The grid.  cgrt_point_grid_workspace reports the bytes a grid over m points needs (24 per point and 8 per bucket, of which there are
  * about as many as points, at least 1024).  cgrt_point_grid_build_device enqueues the build on `stream` (NULL = default
  * stream) into caller-owned device memory (8-byte aligned, contents need no initialisation): it never blocks and reads nothing back.
@@ -1463,9 +1480,17 @@ int cgrt_debug_point_neighbor_work(CgrtScene* scene, const float* data, uint64_t
  * hi - lo - 1).  Triangles are ordered by the cell's index, then tetrahedron, then table position.
  * Properties.  If every value is finite and no cell on the grid's boundary is crossed, every directed edge occurs exactly once and its
  * reverse exactly once.  A value equal to iso puts vertices on the grid point and gives zero-area triangles, which are kept.  Next to
- * non-finite values there may be unreferenced vertices and open borders.  Scaling by a power of two is exact within f32's range:
- * multiplying origin and spacing by 2^k multiplies the vertices by 2^k and changes nothing else; multiplying values and iso by 2^k
- * changes nothing.
+ * non-finite values there may be unreferenced vertices and open borders.
+ * Envelope.  Every intermediate is LINEAR in the values or in the positions, and the two never mix: t is a ratio of two value
+ * differences, a coordinate is a position plus t times a position difference.  Per vertex-carrying edge, multiplying values and iso by
+ * 2^kv changes nothing while every non-zero one of vA, vB, iso, fl(iso - vA), fl(vB - vA) times 2^kv stays a normal float; multiplying
+ * origin and spacing by 2^kp multiplies the vertex by 2^kp exactly while every non-zero one of both ends' grid positions (and their
+ * products (float)i spacing.c), fl(pB.c - pA.c), fl(t fl(pB.c - pA.c)) and the coordinate itself times 2^kp stays normal
+ * (tests/scale_ref.py in_iso_envelope).  The triangles and both counts never depend on origin or spacing, and on the values only through
+ * the classification, which a scale changes only where a value or iso underflows to 0 or overflows.  Outside the envelope the bytes are
+ * still the defined ones on every path -- device, host and count forms agree with the definition -- only the relation to scale 1 is
+ * lost: a subnormal vB - vA or position loses bits; a vB - vA of +-inf gives t = 0; where grid_coord overflows, pA.c - pA.c on an axis
+ * the edge does not move along is inf - inf and the coordinate a NaN (of either sign bit: compare NaNs as NaNs, not by bytes).
  * Outputs.  verts: 3 f32 per vertex.  tris: 3 u32 per triangle.  counts2 = {vertices, triangles}, always the full counts (device forms:
  * device memory, 8-byte aligned; host form: host memory).  Vertex j is written iff j < vert_capacity, triangle j iff j < tri_capacity, its
  * indices as they are even where >= vert_capacity; nothing else in or outside the arrays is touched (the slot rule of the crossing lists).

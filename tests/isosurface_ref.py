@@ -1,5 +1,6 @@
 """A numpy restatement of include/cgrt.h "Iso-surfaces" (marching tetrahedra on a scalar grid), vectorised over the grid, with the mesh
 checks the tests share: directed edges, Euler characteristic, signed volume.  float32 throughout, one rounding per operation.
+`carrying_edges` is the vertex order on its own; `compose_slabs` builds the mesh of a grid too large to restate whole from z-slabs of it.
 
 The triangle table is DERIVED here by rule and never typed in:
   * one or three inside corners: one triangle on the three edges at the odd corner, the edges in ascending order;
@@ -70,6 +71,23 @@ def _table_arrays():
     return n, e
 
 
+def carrying_edges(values, iso=0.0, inside_above=False):
+    """(owner, etype): the vertex-carrying edges of values ((nz, ny, nx) float32, every dim >= 2) in the vertex order -- by the owner's
+    point index, then by edge type."""
+    v = np.ascontiguousarray(np.asarray(values, F32))
+    nz, ny, nx = v.shape
+    iso = F32(iso)
+    fin = np.isfinite(v)
+    ins = fin & ((v > iso) if inside_above else (v < iso))
+    carries = np.zeros((nz, ny, nx, 7), bool)
+    for e in range(7):
+        dx, dy, dz = CORNERS[e + 1]
+        A = (slice(0, nz - dz), slice(0, ny - dy), slice(0, nx - dx))
+        B = (slice(dz, nz), slice(dy, ny), slice(dx, nx))
+        carries[A + (e,)] = fin[A] & fin[B] & (ins[A] != ins[B])
+    return np.nonzero(carries.reshape(-1, 7))  # row-major: by owner, then by edge type
+
+
 def isosurface(values, origin, spacing, iso=0.0, inside_above=False, want_work=False):
     """(verts (nv, 3) float32, tris (nt, 3) uint32) of values ((nz, ny, nx) float32); want_work: also the four counters
     (cells that emit, tetrahedra that emit, vertices, triangles)."""
@@ -83,13 +101,7 @@ def isosurface(values, origin, spacing, iso=0.0, inside_above=False, want_work=F
     N = nx * ny * nz
     fin = np.isfinite(v)
     ins = fin & ((v > iso) if inside_above else (v < iso))
-    carries = np.zeros((nz, ny, nx, 7), bool)
-    for e in range(7):
-        dx, dy, dz = CORNERS[e + 1]
-        A = (slice(0, nz - dz), slice(0, ny - dy), slice(0, nx - dx))
-        B = (slice(dz, nz), slice(dy, ny), slice(dx, nx))
-        carries[A + (e,)] = fin[A] & fin[B] & (ins[A] != ins[B])
-    owner, etype = np.nonzero(carries.reshape(N, 7))  # row-major: by owner, then by edge type
+    owner, etype = carrying_edges(v, iso, inside_above)
     nv = len(owner)
     vid = np.full((N, 7), -1, np.int64)
     vid[owner, etype] = np.arange(nv)
@@ -138,6 +150,41 @@ def isosurface(values, origin, spacing, iso=0.0, inside_above=False, want_work=F
     if want_work:
         res += ((int(live.sum()), int((ntri > 0).sum()), nv, len(tris)),)
     return res
+
+
+def compose_slabs(values_slabs, z0s, origin, spacing, iso=0.0, inside_above=False):
+    """(verts, tris) of a whole grid from z-slabs of it: slab s holds the layers [z0s[s], z0s[s] + len(values_slabs[s])) of the grid on
+    (origin, spacing), the slabs ascend and do not overlap, and no edge outside the slabs carries a vertex: every layer between two
+    slabs lies on the side of the level on which a slab's last layer and, unless it is layer 0, its first layer lie (that these outer
+    layers are finite and of one side is asserted; the layers in between are the caller's).  Vertices are
+    ordered by owner index and triangles by cell index, both z-major, so the whole grid's mesh is the slabs' vertices concatenated, then
+    the slabs' triangles concatenated with every later slab's indices shifted by the vertices before it.
+    Precondition, asserted: every coordinate origin.c + i * spacing.c involved is exact in float32, so that a slab's own origin
+    origin.z + z0 * spacing.z and the positions built on it have the bits the whole grid gives them."""
+    o, sp = np.asarray(origin, F32).reshape(3), np.asarray(spacing, F32).reshape(3)
+    iso = F32(iso)
+    verts, tris, base, last = [], [], 0, 0
+    for val, z0 in zip(values_slabs, z0s):
+        val = np.ascontiguousarray(np.asarray(val, F32))
+        nz, ny, nx = val.shape
+        z0 = int(z0)
+        assert z0 >= last, "the slabs ascend and do not overlap"
+        last = z0 + nz
+        for c, n in ((0, nx), (1, ny), (2, z0 + nz)):
+            i = np.arange(n)
+            exact = float(o[c]) + i.astype(np.float64) * float(sp[c])
+            assert n <= 1 << 24 and np.array_equal((o[c] + i.astype(F32) * sp[c]).astype(np.float64), exact), "a grid coordinate is not exact"
+            assert np.array_equal((i.astype(F32) * sp[c]).astype(np.float64), i.astype(np.float64) * float(sp[c]))
+        for layer in ([val[0]] if z0 > 0 else []) + [val[-1]]:
+            side = (layer > iso) if inside_above else (layer < iso)
+            assert np.isfinite(layer).all() and (side.all() or not side.any()), "a slab's outer layer is crossed"
+        so = o.copy()
+        so[2] = o[2] + F32(z0) * sp[2]
+        v, t = isosurface(val, so, sp, iso=iso, inside_above=inside_above)
+        verts.append(v)
+        tris.append((t.astype(np.int64) + base).astype(np.uint32))
+        base += len(v)
+    return np.concatenate(verts), np.concatenate(tris)
 
 
 # ---- mesh checks

@@ -102,6 +102,30 @@ def exact_d2(points, data):
     return ((q[:, None, :] - d[None, :, :]) ** 2).sum(-1)
 
 
+def scale_cloud():
+    """(data (4096, 3), queries (2048, 3)) of the across-scale tests: the uniform unit-cube cloud of test_point_neighbors_gpu._main()
+    (seed 7), every eighth query set equal to a data point (256 of them)."""
+    rng = np.random.default_rng(7)
+    data, pts = rng.random((4096, 3)).astype(F32), rng.random((2048, 3)).astype(F32)
+    pts[0::8] = data[0::16]
+    return data, pts
+
+
+def overflow_cloud(k=127, m=2048, n=512, seed=19):
+    """(data (m, 3), queries (n, 3)): coordinates +-2^k * u, u uniform in [0.5, 1.99) -- at k = 127 all are finite, `x - lo` overflows to
+    +inf for the part of the cloud more than 2^128 above the minimum, and d2 to +inf between all pairs that differ; every second query is
+    a data point, and the first 64 data points are repeated at 64 .. 127 (exact duplicates)."""
+    rng = np.random.default_rng(seed)
+    with np.errstate(over="ignore"):
+        u = rng.uniform(0.5, 1.99, (m + n, 3)) * rng.choice([-1.0, 1.0], (m + n, 3))
+        p = np.ldexp(u.astype(F32), int(k)).astype(F32)
+    data, pts = p[:m].copy(), p[m:].copy()
+    data[64:128] = data[0:64]
+    pts[0::2] = data[: n // 2]
+    assert np.isfinite(p).all()
+    return data, pts
+
+
 def lattice_case():
     """An 8^3 lattice of spacing 0.25 (every coordinate and every distance exact)."""
     g = np.arange(8, dtype=F32) * F32(0.25)

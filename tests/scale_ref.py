@@ -9,7 +9,10 @@ the float64 generalised winding number and queries just off the surface.
 The neighbour lists share dist2's envelope (`covariant_neighbors`).  The winding numbers (5.25) have one of their own,
 cubic where the others are quartic (`in_winding_envelope`, `covariant_winding_tree`): inside it w is not scaled but unchanged.
 The surface attributes (5.19) have a quadratic one, per item (`surface_items`, `surface_measures`, `in_surface_envelope`,
-`covariant_weights`): inside it the weights are unchanged; `covariant_samples` is the same statement for surface-sample records (5.27)."""
+`covariant_weights`): inside it the weights are unchanged; `covariant_samples` is the same statement for surface-sample records (5.27).
+The point-set neighbours (5.30) and the Poisson-disk sets (5.29) have d2's quadratic envelope per query (`point_measures`,
+`in_point_envelope`, `covariant_point_neighbors`); the iso-surfaces (5.31) a linear one per vertex-carrying edge, in the values and in the
+positions separately (`in_iso_envelope`)."""
 import dataclasses
 
 import numpy as np
@@ -88,17 +91,23 @@ def covariant_sdf(a, b, k):
     return (np.asarray(i0) == np.asarray(ik)) & _bits_eq(_ld(s0, k), sk)
 
 
-def covariant_neighbors(full0, fullk, k):
+def covariant_neighbors(full0, fullk, k, field="prim_id"):
     """(offsets, records) of neighbour lists (neighbors_ref.neighbors, Scene.list_neighbors; slots of any size described by their
     offsets) at scale 1 and at scale 2^k, the radius multiplied by 2^2k: the same count, the same prim_id order, dist2 = ldexp(dist2_0,
-    2k) (+inf of an unused entry stays +inf).  (n,) bool, one verdict per query."""
+    2k) (+inf of an unused entry stays +inf).  (n,) bool, one verdict per query.  `field` names the records' id."""
     (o0, rec0), (ok_, reck) = full0, fullk
     o0, ok_ = np.asarray(o0, np.int64), np.asarray(ok_, np.int64)
     good = np.diff(o0) == np.diff(ok_)
     for i in np.flatnonzero(good):
         a, b = rec0[o0[i] : o0[i + 1]], reck[ok_[i] : ok_[i + 1]]
-        good[i] = bool((a["prim_id"] == b["prim_id"]).all() and _bits_eq(_ld(a["dist2"], 2 * k), b["dist2"]).all())
+        good[i] = bool((a[field] == b[field]).all() and _bits_eq(_ld(a["dist2"], 2 * k), b["dist2"]).all())
     return good
+
+
+def covariant_point_neighbors(full0, fullk, k):
+    """covariant_neighbors for point_neighbors_ref.RECORD lists ((offsets, records) of point_neighbors_ref.neighbors, PointGrid.list):
+    the same count, the same `index` order, dist2 = ldexp(dist2_0, 2k)."""
+    return covariant_neighbors(full0, fullk, k, field="index")
 
 
 def covariant_winding_tree(tree0, treek, k):
@@ -389,3 +398,91 @@ def covariant_samples(r0, rk, k):
     ldexp(point0, k)."""
     ok = (r0["prim_id"] == rk["prim_id"]) & (r0["mesh_id"] == rk["mesh_id"]) & _bits_eq(r0["bary"], rk["bary"]).all(axis=1)
     return ok & _bits_eq(_ld(r0["point"], k), rk["point"]).all(axis=1)
+
+
+# ---- point sets (include/cgrt.h "Point-set neighbours" and "Poisson-disk sets", "Envelope"; DESIGN.md 5.29, 5.30) ----
+def point_measures(points, data, block=256):
+    """(min_dx, max_d2, finite), each (n,): per query, in float64 from the float32 inputs, the smallest non-zero |q.c - d_j.c| over all
+    finite data points j and the three axes (+inf where there is none), the largest exact squared distance to a finite data point (0
+    where there is none), and whether the query is finite."""
+    q = np.asarray(points, F32).reshape(-1, 3).astype(np.float64)
+    d = np.asarray(data, F32).reshape(-1, 3).astype(np.float64)
+    d = d[np.isfinite(d).all(axis=1)]
+    fin = np.isfinite(q).all(axis=1)
+    min_dx, max_d2 = np.full(len(q), np.inf), np.zeros(len(q))
+    if len(d) == 0:
+        return min_dx, max_d2, fin
+    with np.errstate(all="ignore"):
+        for s in range(0, len(q), block):
+            dx = np.abs(np.where(fin[s : s + block, None, None], q[s : s + block, None, :], 0.0) - d[None])
+            max_d2[s : s + block] = (dx * dx).sum(axis=-1).max(axis=1)
+            min_dx[s : s + block] = np.where(dx > 0, dx, np.inf).min(axis=(1, 2))
+    return min_dx, np.where(fin, max_d2, 0.0), fin
+
+
+def in_point_envelope(measures, r2, k):
+    """(n,) bool: the query lies in the envelope of the point-set queries at scale 2^k (data, queries by 2^k; r2, the scale-1 bound, a
+    scalar or (n,), by 2^2k) -- the "Envelope" paragraph of include/cgrt.h "Point-set neighbours" in code:
+
+      lower edge   min|dx|^2 * 2^2k >= FLT_MIN   the smallest non-zero coordinate difference still has a normal square: every dx, every
+                                                 product and both sums are normal or zero
+      upper edge   max d2 * 2^2k <= FLT_MAX      no d2 to any data point overflows, hence no product or partial sum
+      bound        r2 * 2^2k is a normal float   (finite, not zero, not subnormal: the comparison `d2 <= r2` sees the image of r2)
+      the query and r2 are finite
+
+    Inside it every float32 operation of d2 rounds as at scale 1: d2 is multiplied by 2^2k exactly, membership and order are unchanged."""
+    min_dx, max_d2, fin = measures
+    k = int(k)
+    r = np.broadcast_to(np.asarray(r2, np.float64), fin.shape)
+    with np.errstate(all="ignore"):
+        rk = np.ldexp(r, 2 * k)
+        ok = fin & np.isfinite(r) & (rk >= FLT_MIN) & (rk <= FLT_MAX)
+        ok &= np.ldexp(min_dx * min_dx, 2 * k) >= FLT_MIN
+        ok &= np.ldexp(max_d2, 2 * k) <= FLT_MAX
+    return ok
+
+
+# ---- iso-surfaces (include/cgrt.h "Iso-surfaces", "Envelope"; DESIGN.md 5.31) ----
+def _normal_or_zero(x, k):
+    """x (float32 magnitudes at scale 1) times 2^k, taken in float64: zero, or a normal float32."""
+    a = np.abs(np.asarray(x, np.float64))
+    with np.errstate(all="ignore"):
+        s = np.ldexp(a, int(k))
+        return (a == 0) | ((s >= FLT_MIN) & (s <= FLT_MAX))
+
+
+def in_iso_envelope(values, iso, origin, spacing, dims, kv, kp, inside_above=False):
+    """(nv,) bool, one verdict per vertex-carrying edge in the vertex order: the edge lies in the envelope of the iso-surface at values and
+    iso times 2^kv and origin and spacing times 2^kp -- the "Envelope" paragraph of include/cgrt.h "Iso-surfaces" in code.  Every non-zero
+    one of these float32 intermediates of the definition, taken at scale 1, stays a normal float:
+      times 2^kv   vA, vB, iso, fl(iso - vA), fl(vB - vA)
+      times 2^kp   per component: both ends' grid positions with their products (float)i * spacing.c, fl(pB.c - pA.c), fl(t fl(pB.c - pA.c))
+                   and the vertex's coordinate
+    Inside it t has the bits it has at scale 1 (both operands of the ratio carry 2^kv) and every coordinate is multiplied by 2^kp exactly.
+    Non-finite origin, spacing or iso: outside."""
+    import isosurface_ref as iref
+
+    v = np.ascontiguousarray(np.asarray(values, F32))
+    nz, ny, nx = v.shape
+    assert (nx, ny, nz) == tuple(int(x) for x in dims)
+    o, sp = np.asarray(origin, F32).reshape(3), np.asarray(spacing, F32).reshape(3)
+    iso = F32(iso)
+    owner, etype = iref.carrying_edges(v, iso, inside_above)
+    d = iref.CORNERS[etype + 1]
+    idx = [owner % nx, (owner // nx) % ny, owner // (nx * ny)]
+    flat = v.reshape(-1)
+    vA, vB = flat[owner], flat[owner + d[:, 0] + d[:, 1] * nx + d[:, 2] * nx * ny]
+    ok = np.full(len(owner), bool(np.isfinite(iso) and np.isfinite(o).all() and np.isfinite(sp).all()))
+    with np.errstate(all="ignore"):
+        t = (iso - vA) / (vB - vA)
+        t = np.where(t >= F32(0), t, F32(0)).astype(F32)
+        t = np.where(t > F32(1), F32(1), t).astype(F32)
+        for x in (vA, vB, np.full(len(owner), iso, F32), iso - vA, vB - vA):
+            ok &= _normal_or_zero(x, kv)
+        for c in range(3):
+            iA, iB = idx[c].astype(F32), (idx[c] + d[:, c]).astype(F32)
+            pA, pB = o[c] + iA * sp[c], o[c] + iB * sp[c]
+            diff = pB - pA
+            for x in (np.full(len(owner), o[c], F32), iA * sp[c], iB * sp[c], pA, pB, diff, t * diff, pA + t * diff):
+                ok &= _normal_or_zero(x, kp)
+    return ok
