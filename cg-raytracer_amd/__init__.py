@@ -411,7 +411,7 @@ _lib: Optional[C.CDLL] = None
 
 # every symbol include/cgrt.h declares
 EXPORTS = [
-    "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
+    "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_set_frame_order", "cgrt_debug_set_frame_order", "cgrt_debug_get_frame_order", "cgrt_debug_build_frame_order", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
     "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_point_grid_workspace", "cgrt_point_grid_build_device", "cgrt_count_point_neighbors", "cgrt_count_point_neighbors_device", "cgrt_list_point_neighbors", "cgrt_list_point_neighbors_device", "cgrt_list_point_neighbors_brute", "cgrt_debug_point_neighbor_work", "cgrt_isosurface_workspace", "cgrt_isosurface_count_device", "cgrt_isosurface_device", "cgrt_isosurface", "cgrt_debug_isosurface_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
@@ -455,6 +455,10 @@ def lib() -> C.CDLL:
     L.cgrt_set_render_prediction.argtypes = [i32]
     L.cgrt_set_frame_hints.argtypes = [i32]
     L.cgrt_set_frame_gate.argtypes = [i32]
+    L.cgrt_set_frame_order.argtypes = [i32]
+    L.cgrt_debug_set_frame_order.argtypes = [vp] + [i32] * 8 + [C.POINTER(C.c_uint16), C.c_uint32]
+    L.cgrt_debug_get_frame_order.argtypes = [vp, C.POINTER(C.c_uint16), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(i32)]
+    L.cgrt_debug_build_frame_order.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint16)]
     L.cgrt_debug_frame_gate.argtypes = [vp, C.POINTER(Camera), i32, i32, C.POINTER(i32)]
     L.cgrt_debug_set_hint_thresholds.argtypes = [u32, u32]
     L.cgrt_debug_render_path.argtypes = [C.c_void_p]
@@ -697,6 +701,20 @@ def set_frame_hints(mode: int = -1) -> None:
     _check(lib().cgrt_set_frame_hints(int(mode)))
 
 
+def set_frame_order(mode: int = -1) -> None:
+    """Primary frames: -1 the library's policy (order tables for whole frames and large shares: include/cgrt.h), 0 off, 1 on wherever a
+    frame qualifies; same pixels."""
+    _check(lib().cgrt_set_frame_order(int(mode)))
+
+
+def debug_build_frame_order(ticks) -> np.ndarray:
+    """cgrt_debug_build_frame_order: the device builder's table for injected per-position ticks (uint16, padded to 8)."""
+    t = np.ascontiguousarray(ticks, np.uint32)
+    out = np.empty((len(t) + 7) // 8 * 8, np.uint16)
+    _check(lib().cgrt_debug_build_frame_order(t.ctypes.data_as(C.POINTER(C.c_uint32)), len(t), out.ctypes.data_as(C.POINTER(C.c_uint16))))
+    return out
+
+
 def set_frame_gate(enabled: bool = True) -> None:
     """Camera frames: waves whose pixels all lie outside the root box's screen rectangle write their misses without tracing (default),
     or every pixel takes the per-pixel root gate; same bytes either way."""
@@ -880,6 +898,26 @@ class Scene:
         out = (C.c_uint32 * 3)()
         _check(lib().cgrt_debug_hint_counts(self._h, out))
         return [int(v) for v in out]
+
+    def debug_set_frame_order(self, W: int, H: int, table=None, rect=None, rank: int = 0, nranks: int = 1) -> None:
+        """cgrt_debug_set_frame_order: install `table` for the next launches of that shape (None: back to the policy)."""
+        x0, y0, x1, y1 = rect if rect is not None else (0, 0, W, H)
+        if table is None:
+            _check(lib().cgrt_debug_set_frame_order(self._h, int(W), int(H), x0, y0, x1, y1, int(rank), int(nranks), None, 0))
+            return
+        t = np.ascontiguousarray(table, np.uint16)
+        _check(lib().cgrt_debug_set_frame_order(self._h, int(W), int(H), x0, y0, x1, y1, int(rank), int(nranks),
+                                                t.ctypes.data_as(C.POINTER(C.c_uint16)), len(t)))
+
+    def debug_get_frame_order(self):
+        """cgrt_debug_get_frame_order: (table in use or None, state 0 none / 1 profiled / 2 active, launches since the profile frame)."""
+        n, st = C.c_uint32(0), (C.c_int * 2)()
+        _check(lib().cgrt_debug_get_frame_order(self._h, None, 0, C.byref(n), st))
+        if n.value == 0:
+            return None, int(st[0]), int(st[1])
+        out = np.empty(n.value, np.uint16)
+        _check(lib().cgrt_debug_get_frame_order(self._h, out.ctypes.data_as(C.POINTER(C.c_uint16)), n.value, C.byref(n), st))
+        return out, int(st[0]), int(st[1])
 
     def frame_gate(self, cam, W: int, H: int):
         """cgrt_debug_frame_gate: (x0, y0, x1, y1) -- every pixel of the W x H frame outside it misses the mesh root gate ((0, 0, 0, 0):

@@ -24,6 +24,7 @@ std::atomic<int> g_call_combining{1};  // cgrt_set_call_combining
 std::atomic<int> g_render_predict{1};  // cgrt_set_render_prediction
 std::atomic<int> g_frame_hints{-1};    // cgrt_set_frame_hints: -1 auto, 0 off, 1 hard tiles first, 2 hard tiles 16 rays per wave
 std::atomic<unsigned> g_hint_thr_dense{0}, g_hint_thr_sparse{0};  // cgrt_debug_set_hint_thresholds (0: the defaults)
+std::atomic<int> g_frame_order{-1};    // cgrt_set_frame_order: -1 = the library's policy (on), 0 = off, 1 = on wherever a frame qualifies
 std::atomic<int> g_frame_gate{1};      // cgrt_set_frame_gate: 1 = tiles outside the root box's screen rectangle skip their rays, 0 = off
 std::atomic<int> g_primary_mode{0};  // 0 = one wave per tile, 1 = persistent waves with lane refill
 
@@ -95,6 +96,7 @@ bool make_frame(int W, int H, int x0, int y0, int x1, int y1, int rank, int nran
     F.views = nullptr;
     F.view_st = 0;
     F.gate_x0 = F.gate_y0 = F.gate_x1 = F.gate_y1 = 0;  // no gate (apply_frame_gate)
+    F.order = nullptr;
     return true;
 }
 

@@ -54,6 +54,7 @@ extern std::atomic<int> g_call_combining;  // cgrt_set_call_combining
 extern std::atomic<int> g_render_predict;  // cgrt_set_render_prediction
 extern std::atomic<int> g_frame_hints;    // cgrt_set_frame_hints: -1 auto, 0 off, 1 hard tiles first, 2 hard tiles 16 rays per wave
 extern std::atomic<unsigned> g_hint_thr_dense, g_hint_thr_sparse;  // cgrt_debug_set_hint_thresholds (0: the defaults)
+extern std::atomic<int> g_frame_order;     // cgrt_set_frame_order: -1 = the library's policy (on), 0 = off, 1 = on wherever a frame qualifies
 extern std::atomic<int> g_frame_gate;      // cgrt_set_frame_gate: 1 = tiles outside the root box's screen rectangle skip their rays, 0 = off
 extern std::atomic<int> g_primary_mode;  // 0 = one wave per tile, 1 = persistent waves with lane refill
 
@@ -161,6 +162,29 @@ struct CgrtScene {
         bool hint_stream_valid = false;
         int cooldown = 0;             // frames to run without hints after the caller changed streams
     } hints;
+    // Frame order (cgrt_layout.h FrameDev::order; capi_primary.cpp attach_order): the order table the frames of one shape on
+    // one stream are launched with, rebuilt on the device behind a profile frame.  Guarded by hints.mu, like the hints, while a launch is
+    // being issued; ticks and tables are only touched by kernels and copies on `use_stream`.
+    struct FrameOrder {
+        bool ready = false;            // buffers allocated for `key`
+        int key[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // W, H, x0, y0, x1, y1, rank, nranks
+        int wanted[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the shape of the last launches that asked for other buffers
+        int wanted_count = 0;          // ... and how many in a row did
+        void* mem = nullptr;           // ticks[n_pad] u32 | table 0 [n_pad] u16 | table 1 [n_pad] u16
+        size_t mem_bytes = 0;
+        uint32_t n_pad = 0;            // positions of the launch: the shape's super-tiles padded to 8
+        int active = -1;               // the table frames are launched with (-1: none yet)
+        int state = 0;                 // 0 none, 1 profiled (the builder is behind the last launch), 2 active (the last launch read the table)
+        int since_profile = 0;         // launches of the shape since its profile frame
+        bool installed = false;        // the table is a caller's (cgrt_debug_set_frame_order): used as it is, never profiled
+        hipStream_t last_stream = nullptr;  // the stream of the last launch that could have taken a table
+        bool last_stream_valid = false;
+        hipStream_t use_stream = nullptr;   // the stream of the last launch that touched the buffers
+        bool use_stream_valid = false;
+        int cooldown = 0;              // launches to run without a table after the caller changed streams or shapes
+        uint32_t* ticks() const { return static_cast<uint32_t*>(mem); }
+        uint16_t* table(int k) const { return reinterpret_cast<uint16_t*>(ticks() + n_pad) + (size_t)k * n_pad; }
+    } order;
     hipEvent_t queue_done[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // Host-pointer entries (cgrt_intersect_batch, cgrt_trace_primary, cgrt_count_*, ...) run on "call lanes": a private
     // stream + device scratch + pinned staging + a counter block, taken from this pool for the duration of one call and
@@ -354,7 +378,7 @@ struct CgrtScene {
             if (v.dev) (void)hipFree(v.dev);
             if (v.pin) (void)hipHostFree(v.pin);
         }
-        for (void* p : {d_records, d_leaves, d_tri_normals, d_spheres, d_materials, d_tri_leaf, d_paths, (void*)d_queues, hints.mem})
+        for (void* p : {d_records, d_leaves, d_tri_normals, d_spheres, d_materials, d_tri_leaf, d_paths, (void*)d_queues, hints.mem, order.mem})
             if (p) (void)hipFree(p);
         if (hints.mailbox) (void)hipHostFree(hints.mailbox);
         if (pin_frame) (void)hipHostFree(pin_frame);

@@ -189,6 +189,126 @@ static int attach_hints(CgrtScene* s, FrameDev& F, hipStream_t stream) {
     return CGRT_OK;
 }
 
+// Frame order (cgrt_layout.h FrameDev::order): which frames get an order table, and when the table is rebuilt.  A frame
+// qualifies when it is launched as single-wave workgroups on a fast tree, unpacked, and the hint policy above left it alone (whole
+// frames and large shares: the frames whose end is set by WHERE in the launch their medium-long waves sit, not by their longest wave).
+// The third launch in a row of one shape on one stream is a PROFILE frame (k_trace_primary's STAMP: same pixels, and the longest wave
+// time of every super-tile), the builder follows it on the same stream and writes the table that is not in use, and the launches after it
+// carry that table; every CGRT_ORDER_PERIOD launches the shape is profiled again.  All of it is enqueued: the host never waits, so a
+// caller dozens of launches ahead of the device gets its table from the fourth launch on.  Streams and shapes as with the hints: a
+// change means eight launches without a table, and the stream that touched the buffers last is waited for before they are used again.
+#ifndef CGRT_ORDER_PERIOD
+#define CGRT_ORDER_PERIOD 32
+#endif
+static int order_mode() {
+    static const int env = [] {
+        const char* e = getenv("CGRT_FRAME_ORDER");
+        return e ? atoi(e) : -2;
+    }();
+    const int m = env >= -1 ? env : g_frame_order.load();
+    return m > 1 ? 1 : m;
+}
+static uint32_t order_live_ticks() {
+    static const uint32_t env = [] {
+        const char* e = getenv("CGRT_ORDER_LIVE_TICKS");  // (experiments)
+        return e ? (uint32_t)atoi(e) : CGRT_ORDER_LIVE_TICKS;
+    }();
+    return env;
+}
+static bool order_buffers(CgrtScene::FrameOrder& O, uint32_t n_pad) {
+    const size_t bytes = (size_t)n_pad * 4 + 2 * (size_t)n_pad * 2;
+    if (O.mem_bytes < bytes) {
+        if (O.mem) (void)hipFree(O.mem);
+        O.mem = nullptr;
+        O.mem_bytes = 0;
+        if (hipMalloc(&O.mem, bytes) != hipSuccess) {  // (the table is an accelerator: without its buffers the frame is traced plain)
+            (void)hipGetLastError();
+            return false;
+        }
+        O.mem_bytes = bytes;
+    }
+    O.n_pad = n_pad;
+    return true;
+}
+static void order_drop(CgrtScene::FrameOrder& O) {
+    O.state = 0;
+    O.active = -1;
+    O.since_profile = 0;
+    O.installed = false;
+}
+// For ONE launch on `stream`, with s->hints.mu held until the launch has been issued (after attach_hints): 0 = no table, 1 = F.order is
+// set, 2 = this launch is the shape's profile frame (launch_primary issues it and the builder, then order_profiled).
+static int attach_order(CgrtScene* s, FrameDev& F, hipStream_t stream) {
+    CgrtScene::FrameOrder& O = s->order;
+    const uint32_t n_pad = (F.nst_rank + 7u) / 8u * 8u;
+    const bool qualifies = order_mode() != 0 && !F.hint && n_pad <= CGRT_ORDER_MAX_POSITIONS && can_profile_frame(s->dev, F) && hint_mode_for(F) == 0;
+    if (O.last_stream_valid && stream != O.last_stream) {
+        O.cooldown = 8;
+        if (!O.installed) order_drop(O);
+        else O.state = 0;
+    }
+    const hipStream_t prev_stream = O.last_stream;
+    const bool prev_valid = O.last_stream_valid;
+    O.last_stream = stream;
+    O.last_stream_valid = true;
+    if (!qualifies) {
+        O.wanted_count = 0;
+        if (O.state == 2) O.state = 1;
+        return 0;
+    }
+    const int key[8] = {F.W, F.H, F.x0, F.y0, F.x1, F.y1, F.rank, F.nranks};
+    if (O.ready && std::memcmp(key, O.key, sizeof(key)) != 0) {  // another shape
+        O.ready = false;
+        order_drop(O);
+        O.cooldown = 8;
+    }
+    if (!O.ready) {
+        if (std::memcmp(key, O.wanted, sizeof(key)) != 0) {
+            std::memcpy(O.wanted, key, sizeof(key));
+            O.wanted_count = 0;
+        }
+        if (O.wanted_count < 3) O.wanted_count++;
+    }
+    if (O.cooldown > 0) {
+        if (--O.cooldown > 0) return 0;
+        if (prev_valid) (void)hipStreamSynchronize(prev_stream);  // (a destroyed stream answers with an error: nothing of ours is on it then)
+        if (O.use_stream_valid && O.use_stream != stream) (void)hipStreamSynchronize(O.use_stream);
+        (void)hipGetLastError();
+    }
+    if (!O.ready) {
+        if (O.wanted_count < 3) return 0;
+        O.wanted_count = 0;
+        if (O.use_stream_valid && O.use_stream != stream) (void)hipStreamSynchronize(O.use_stream);  // whatever used the old buffers
+        (void)hipGetLastError();
+        if (!order_buffers(O, n_pad)) return 0;
+        std::memcpy(O.key, key, sizeof(key));
+        order_drop(O);
+        O.ready = true;
+    }
+    O.use_stream = stream;
+    O.use_stream_valid = true;
+    if (!O.installed && (O.active < 0 || O.since_profile >= CGRT_ORDER_PERIOD - 1)) return 2;
+    F.order = O.table(O.active);
+    O.state = 2;
+    O.since_profile++;
+    return 1;
+}
+static void order_profiled(CgrtScene::FrameOrder& O, int table) {
+    O.active = table;
+    O.state = 1;
+    O.since_profile = 0;
+}
+// A table is valid iff it is a permutation of the n positions that keeps every position's % 8 residue and maps the padded ones to themselves.
+static bool order_table_valid(const uint16_t* t, uint32_t n, uint32_t nst) {
+    std::vector<uint8_t> seen(n, 0);
+    for (uint32_t p = 0; p < n; p++) {
+        const uint32_t e = t[p];
+        if (e >= n || (e & 7u) != (p & 7u) || seen[e] || ((p >= nst || e >= nst) && e != p)) return false;
+        seen[e] = 1;
+    }
+    return true;
+}
+
 // The frame gate of one camera launch (frame_gate_rect): F's rectangle, or none.  What disables it beyond the geometry: the switch, a
 // scene with spheres (resolve_hit tests every sphere for a ray that failed the mesh root gate) and a scene without a tree (walk_begin
 // returns before the gate).  Nothing else is evaluated for such a ray: finish_ray writes {t as given, no primitive, no material, hit = 0}.
@@ -231,6 +351,78 @@ int cgrt_set_frame_hints(int mode) {
     g_frame_hints.store(mode);
     return CGRT_OK;
 }
+int cgrt_set_frame_order(int mode) {
+    if (mode < -1 || mode > 1) return fail(CGRT_E_ARG, "frame order mode: -1 the library's policy (default), 0 off, 1 on wherever a frame qualifies");
+    g_frame_order.store(mode);
+    return CGRT_OK;
+}
+int cgrt_debug_set_frame_order(CgrtScene* s, int W, int H, int x0, int y0, int x1, int y1, int rank, int nranks, const uint16_t* table, uint32_t n) {
+    if (!s) return fail(CGRT_E_ARG, "NULL argument");
+    NEED_DEVICE(s);
+    std::lock_guard<std::mutex> lk(s->hints.mu);
+    CgrtScene::FrameOrder& O = s->order;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());  // nothing in flight reads or writes the tables
+    if (!table && n == 0) {  // back to the policy
+        O.ready = false;
+        order_drop(O);
+        O.wanted_count = 0;
+        O.cooldown = 0;
+        O.last_stream_valid = O.use_stream_valid = false;
+        return CGRT_OK;
+    }
+    FrameDev F;
+    if (!table || !make_frame(W, H, x0, y0, x1, y1, rank, nranks, 64, F)) return fail(CGRT_E_ARG, "NULL table, bad frame rectangle or rank");
+    const uint32_t n_pad = (F.nst_rank + 7u) / 8u * 8u;
+    if (n != n_pad || n_pad == 0 || n_pad > CGRT_ORDER_MAX_POSITIONS) return fail(CGRT_E_ARG, "order table: its length must be the shape's super-tiles padded to 8");
+    if (!order_table_valid(table, n, F.nst_rank)) return fail(CGRT_E_ARG, "order table: not a permutation that keeps every position's % 8 residue and the padded positions");
+    if (!order_buffers(O, n_pad)) return fail(CGRT_E_HIP, "order table: no device memory");
+    HIP_TRY(hipMemcpy(O.table(0), table, (size_t)n * 2, hipMemcpyHostToDevice));
+    const int key[8] = {W, H, x0, y0, x1, y1, rank, nranks};
+    std::memcpy(O.key, key, sizeof(key));
+    order_drop(O);
+    O.ready = true;
+    O.installed = true;
+    O.active = 0;
+    O.wanted_count = 0;
+    O.cooldown = 0;
+    O.last_stream_valid = O.use_stream_valid = false;
+    return CGRT_OK;
+}
+int cgrt_debug_get_frame_order(CgrtScene* s, uint16_t* table, uint32_t cap, uint32_t* n, int* state2) {
+    if (!s || !n || !state2) return fail(CGRT_E_ARG, "NULL argument");
+    NEED_DEVICE(s);
+    std::lock_guard<std::mutex> lk(s->hints.mu);
+    const CgrtScene::FrameOrder& O = s->order;
+    state2[0] = O.state;
+    state2[1] = O.since_profile;
+    *n = 0;
+    if (!O.ready || O.active < 0) return CGRT_OK;
+    *n = O.n_pad;
+    if (!table) return CGRT_OK;
+    if (cap < O.n_pad) return fail(CGRT_E_ARG, "order table: the buffer is too short");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(table, O.table(O.active), (size_t)O.n_pad * 2, hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+int cgrt_debug_build_frame_order(const uint32_t* ticks, uint32_t n, uint16_t* out) {
+    if (!ticks || !out) return fail(CGRT_E_ARG, "NULL argument");
+    const uint32_t n_pad = (n + 7u) / 8u * 8u;
+    if (n == 0 || n_pad > CGRT_ORDER_MAX_POSITIONS) return fail(CGRT_E_ARG, "order builder: 1 .. 16384 positions");
+    void* mem = nullptr;
+    HIP_TRY(hipMalloc(&mem, (size_t)n_pad * 6));
+    uint32_t* d_ticks = static_cast<uint32_t*>(mem);
+    uint16_t* d_out = reinterpret_cast<uint16_t*>(d_ticks + n_pad);
+    hipError_t e = hipMemset(mem, 0, (size_t)n_pad * 6);
+    if (e == hipSuccess) e = hipMemcpy(d_ticks, ticks, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_build_frame_order(d_ticks, n, CGRT_ORDER_LIVE_TICKS, d_out, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n_pad * 2, hipMemcpyDeviceToHost);
+    (void)hipFree(mem);
+    HIP_TRY(e);
+    return CGRT_OK;
+}
 int cgrt_set_frame_gate(int mode) {
     if (mode != 0 && mode != 1) return fail(CGRT_E_ARG, "frame gate mode: 1 on (default), 0 off");
     g_frame_gate.store(mode);
@@ -252,6 +444,14 @@ static int launch_primary(CgrtScene* s, const CameraDev& C, const FrameDev& F_in
         std::lock_guard<std::mutex> lk(s->hints.mu);
         const int rc = attach_hints(s, F, stream);
         if (rc) return rc;
+        if (attach_order(s, F, stream) == 2) {  // the shape's profile frame, and the builder behind it
+            CgrtScene::FrameOrder& O = s->order;
+            const int next = O.active < 0 ? 0 : 1 - O.active;
+            HIP_TRY(launch_trace_primary_profile(s->dev, C, F, d_hits, d_normals, O.ticks(), stream));
+            HIP_TRY(launch_build_frame_order(O.ticks(), F.nst_rank, order_live_ticks(), O.table(next), stream));
+            order_profiled(O, next);
+            return CGRT_OK;
+        }
         HIP_TRY(launch_trace_primary(s->dev, C, F, d_hits, d_normals, counters, stream));
         return CGRT_OK;
     }
@@ -491,6 +691,15 @@ int cgrt_debug_wave_times(CgrtScene* s, const CgrtCamera* cam, int W, int H, uin
     HIP_TRY(dh.alloc((size_t)W * (size_t)H * sizeof(CgrtHit)));
     HIP_TRY(ds.alloc(nwaves * 128));
     HIP_TRY(hipMemset(ds.p, 0, nwaves * 128));
+    std::lock_guard<std::mutex> lk(s->hints.mu);
+    {  // the whole frame's order table, when the scene has one in use: the stamps are then those of the ordered launch
+        const CgrtScene::FrameOrder& O = s->order;
+        const int key[8] = {W, H, 0, 0, W, H, 0, 1};
+        if (order_mode() != 0 && O.ready && O.active >= 0 && std::memcmp(key, O.key, sizeof(key)) == 0) {
+            HIP_TRY(hipDeviceSynchronize());  // (the builder may be behind a frame on another stream)
+            F.order = O.table(O.active);
+        }
+    }
     for (int rep = 0; rep < 3; rep++)  // warm caches, keep the last
         HIP_TRY(launch_trace_primary_stamped(s->dev, make_camera(*cam), F, dh.as<CgrtHitDev>(), ds.as<unsigned long long>(), nullptr));
     HIP_TRY(hipDeviceSynchronize());

@@ -241,7 +241,16 @@ struct FrameDev {
     // miss the mesh root gate whatever else is true of them, so a wave whose pixels all lie outside writes its miss records without
     // generating a ray.  gate_x1 == 0: no gate (what FrameDev{} and make_frame leave).  Read by the CameraDev frame kernels only, the hinted instantiation excepted.
     int gate_x0, gate_y0, gate_x1, gate_y1;
+    // Frame order (walk_exact.h tile_pixel_of<VIEWS, ORDER>, capi_primary.cpp attach_order): the workgroups of rank-local
+    // super-tile POSITION s trace super-tile order[s] instead of super-tile s.  One entry per position, padded to 8 like nblocks; a
+    // permutation that keeps s % 8 (the XCD lane above) and maps the padded positions to themselves, so every pixel is still traced
+    // exactly once.  nullptr: the mapping above.  Read by the ORDER instantiation of k_trace_primary only.
+    const uint16_t* order;
 };
+// live threshold of the order builder (k_build_frame_order): a super-tile whose longest wave took at least this many 10 ns ticks
+#define CGRT_ORDER_LIVE_TICKS 500u
+// positions an order table can have (u16 entries; the builder keeps one lane's ticks, an eighth of them, in LDS)
+#define CGRT_ORDER_MAX_POSITIONS 16384u
 static const int ST_TILES = 8;  // tiles per super-tile side
 // Workgroups of the traversal kernels hold 64, 128 or 256 threads (chosen per launch: FrameDev::block, blockDim.x): one wave
 // per 8x8 tile, so a 64x64 super-tile takes 64 / (block / 64) consecutive workgroups of one blockIdx % 8 residue.  CGRT_BLOCK

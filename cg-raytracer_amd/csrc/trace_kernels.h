@@ -78,6 +78,13 @@ bool quad_shape_for(const SceneDev& S, unsigned long long rays);
 // counters (optional): 5 x u64 device words {rays, inner_visits, leaf_visits, tri_tests, sub_visits}, accumulated.
 hipError_t launch_trace_primary(const SceneDev& S, const CameraDev& C, const FrameDev& F, CgrtHitDev* hits, float* normals,
                                 unsigned long long* counters, hipStream_t stream);
+// Frame order (FrameDev::order).  A profile frame: the plain frame of a launch for which can_profile_frame holds, whose
+// waves leave their longest wall time per super-tile in ticks[(nst_rank + 7) / 8 * 8] (u32, 10 ns; zeroed on the stream in front of
+// the launch); the builder turns ticks into a table of as many u16 entries (live: the builder's threshold, CGRT_ORDER_LIVE_TICKS).
+bool can_profile_frame(const SceneDev& S, const FrameDev& F);
+hipError_t launch_trace_primary_profile(const SceneDev& S, const CameraDev& C, const FrameDev& F, CgrtHitDev* hits, float* normals,
+                                        uint32_t* ticks, hipStream_t stream);
+hipError_t launch_build_frame_order(const uint32_t* ticks, uint32_t nst, uint32_t live, uint16_t* out, hipStream_t stream);
 // persistent variant: queue = CGRT_QUEUE_BLOCK_WORDS zeroed u32 (8 heads + exit counter, one 128-B line each) owned by this launch; blocks = persistent grid size
 hipError_t launch_trace_primary_persistent(const SceneDev& S, const CameraDev& C, const FrameDev& F, CgrtHitDev* hits, float* normals,
                                            unsigned long long* counters, unsigned int* queue, unsigned blocks, hipStream_t stream);

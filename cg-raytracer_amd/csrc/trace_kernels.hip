@@ -30,7 +30,7 @@ namespace cgrt {
 // residue, i.e. same XCD -- and of its 64 pixels the 16 with index (b / 8 % 4) * 16 + threadIdx / 4; the four lanes of a quad
 // carry the same pixel.  Results land where the lane-per-ray launch puts them (packed or not).
 // VIEWS: a multi-view frame (FrameDev::views); *view = the lane's view (wave-uniform).
-template <bool QUAD, bool VIEWS = false>
+template <bool QUAD, bool VIEWS = false, bool ORDER = false>
 __device__ __forceinline__ bool frame_pixel(const FrameDev& F, int& x, int& y, size_t& packed_index, bool& writer, uint32_t* view = nullptr) {
     if (QUAD) {
         const uint32_t b = blockIdx.x, tb = ((b >> 5) << 3) | (b & 7u);
@@ -41,7 +41,7 @@ __device__ __forceinline__ bool frame_pixel(const FrameDev& F, int& x, int& y, s
     }
     packed_index = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     writer = true;
-    return tile_pixel_of<VIEWS>(F, blockIdx.x, threadIdx.x, x, y, view);
+    return tile_pixel_of<VIEWS, ORDER>(F, blockIdx.x, threadIdx.x, x, y, view);
 }
 // A multi-view frame's pixel index: view * W * H + y * W + x (< 2^31: the entries check nviews * W * H).
 __device__ __forceinline__ size_t view_pixel(const FrameDev& F, uint32_t view, int x, int y) {
@@ -63,11 +63,17 @@ __device__ __forceinline__ bool wave_outside_gate(const FrameDev& F, const bool 
 // reason; each wave reads its view's camera from the device table (C is not used) and writes at view_pixel.  Never with HINT.
 // RAYCAM (with VIEWS only): the table holds ray cameras (FrameDev::raycams, cgrt_*_raycams*) -- again instantiations of their own.  The
 // wave reads its 80-byte entry before the walk; only o and d live through it.
-template <bool COUNT, bool FAST, bool QUAD = false, bool HINT = false, bool VIEWS = false, bool RAYCAM = false>
+// ORDER: the launch carries an order table (FrameDev::order) -- an instantiation of its own for HINT's reason; the plain
+// frame kernel plus one scalar load per wave.
+// STAMP: a profile frame of the order policy -- the plain kernel, and every wave that enters the tree leaves its wall time (s_memrealtime,
+// 10 ns ticks) in ticks[its super-tile] by one atomicMax; `counters` carries the ticks (one u32 per padded super-tile, zeroed in front of
+// the launch).  The start stamp waits in LDS like hint_park's.  Never timed against the plain kernel: one frame in CGRT_ORDER_PERIOD.
+template <bool COUNT, bool FAST, bool QUAD = false, bool HINT = false, bool VIEWS = false, bool RAYCAM = false, bool ORDER = false, bool STAMP = false>
 __global__ CGRT_LB void k_trace_primary(SceneDev S, CameraDev C, FrameDev F, CgrtHitDev* __restrict__ hits, float* __restrict__ normals,
                                         unsigned long long* counters) {
     static_assert(!(HINT && VIEWS), "multi-view frames take no hints");
     static_assert(VIEWS || !RAYCAM, "ray cameras come from the views table");
+    static_assert(!((ORDER || STAMP) && (COUNT || QUAD || HINT || VIEWS)) && !(ORDER && STAMP), "ordered and profile frames: the plain kernel only");
     extern __shared__ uint32_t s_lds[];  // CGRT_LDS_WORDS(blockDim.x): stacks, quad-tail owner maps, workgroup scratch
     int x = 0, y = 0;
     size_t pidx;
@@ -80,7 +86,8 @@ __global__ CGRT_LB void k_trace_primary(SceneDev S, CameraDev C, FrameDev F, Cgr
         active = hinted_tile_pixel(F, x, y, CGRT_HINT_SCRATCH(s_lds));
     } else {
         if (HINT && (threadIdx.x & 63u) == 0u) CGRT_HINT_SCRATCH(s_lds)[1] = 0xffffffffu;  // nothing for hint_finish
-        active = frame_pixel<QUAD, VIEWS>(F, x, y, pidx, writer, &view);
+        if (STAMP && (threadIdx.x & 63u) == 0u) CGRT_HINT_SCRATCH(s_lds)[0] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+        active = frame_pixel<QUAD, VIEWS, ORDER>(F, x, y, pidx, writer, &view);
     }
     // The counting instantiations take every pixel through the per-pixel gate (their counters are the per-pixel path's), the multi-view
     // ones carry no rectangle, and the hinted one is the kernel it was: its frames are as long as their longest wave, not their empty ones
@@ -117,6 +124,47 @@ __global__ CGRT_LB void k_trace_primary(SceneDev S, CameraDev C, FrameDev F, Cgr
     }
     if (COUNT) flush_counters(cnt, active && writer, counters);
     if (HINT) hint_finish(CGRT_HINT_SCRATCH(s_lds));
+    if (STAMP && (threadIdx.x & 63u) == 0u) {  // (single-wave workgroups: the launcher sees to it)
+        const uint32_t dt = (uint32_t)__builtin_amdgcn_s_memrealtime() - CGRT_HINT_SCRATCH(s_lds)[0];
+        atomicMax(reinterpret_cast<uint32_t*>(counters) + ((blockIdx.x >> 9) * 8u + (blockIdx.x & 7u)), dt);
+    }
+}
+
+// The order builder (tests/frame_order_ref.py states it in NumPy): from the ticks a profile frame left, per % 8 lane,
+// the positions with ticks >= live are LIVE; every other position keeps its own super-tile, and the live super-tiles are dealt to the live
+// positions in descending order of ticks, ties by position -- the launch keeps its pattern of heavy and background super-tiles, the
+// super-tile with the longest wave starts first, those whose waves are all short start last.  One workgroup per lane, the lane's ticks
+// in LDS; a rank sort: the thread of live position p counts the live positions of the lane that go before it in the sorted order (r) and
+// in the launch (c), leaves p at by_rank[r], and after a barrier takes by_rank[c] -- the ranks of a lane are distinct, so every slot of
+// by_rank and of the table is written exactly once, by one thread.
+__global__ __launch_bounds__(256) void k_build_frame_order(const uint32_t* __restrict__ ticks, uint32_t n_pad, uint32_t nst, uint32_t live,
+                                                           uint16_t* __restrict__ out) {
+    __shared__ uint32_t s_ticks[CGRT_ORDER_MAX_POSITIONS / 8];
+    __shared__ uint16_t s_by_rank[CGRT_ORDER_MAX_POSITIONS / 8], s_before[CGRT_ORDER_MAX_POSITIONS / 8];
+    const uint32_t lane8 = blockIdx.x, m = n_pad >> 3;  // the lane's positions: lane8 + 8 i, i < m (m <= CGRT_ORDER_MAX_POSITIONS / 8: the launcher)
+    for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
+        const uint32_t p = lane8 + 8u * i;
+        s_ticks[i] = p < nst ? ticks[p] : 0u;
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
+        const uint32_t tp = s_ticks[i];
+        if (tp < live) continue;
+        uint32_t r = 0, c = 0;
+        for (uint32_t k = 0; k < m; k++) {
+            const uint32_t tq = s_ticks[k];
+            const bool lv = tq >= live;
+            r += (lv && (tq > tp || (tq == tp && k < i))) ? 1u : 0u;
+            c += (lv && k < i) ? 1u : 0u;
+        }
+        s_by_rank[r] = (uint16_t)(lane8 + 8u * i);
+        s_before[i] = (uint16_t)c;
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
+        const uint32_t p = lane8 + 8u * i;
+        out[p] = s_ticks[i] >= live ? s_by_rank[s_before[i]] : (uint16_t)p;
+    }
 }
 
 // Primary frame for the shading wavefront (cgrt_render): the fused kernel's walk, but only the rays that HIT are written,
@@ -1014,6 +1062,7 @@ hipError_t launch_trace_primary(const SceneDev& S, const CameraDev& C, const Fra
     if (F.nblocks == 0) return hipSuccess;
     const FramePlan p = plan_frame(S, F);
     const bool hint = !p.quad && F.hint && p.fast && F.block == 64 && !counters;  // frame hints: the hard list's workgroups come first
+    const bool order = !p.quad && !hint && F.order && p.fast && F.block == 64 && !counters;  // order table (else: the table is not read)
     with_bools(counters != nullptr, p.fast, [&](auto count, auto fast) {
         constexpr bool COUNT = decltype(count)::value, FAST = decltype(fast)::value;
         auto go = [&](auto kernel, unsigned grid) { launch(kernel, grid, p.block, stream, S, C, F, hits, normals, counters); };
@@ -1021,10 +1070,34 @@ hipError_t launch_trace_primary(const SceneDev& S, const CameraDev& C, const Fra
             if (p.quad) return go(k_trace_primary<COUNT, true, true>, p.grid);
             if constexpr (!COUNT) {
                 if (hint) return go(k_trace_primary<false, true, false, true>, F.nblocks + F.hint_blocks);
+                if (order) return go(k_trace_primary<false, true, false, false, false, false, true>, p.grid);
             }
         }
         go(k_trace_primary<COUNT, FAST>, p.grid);
     });
+    return hipGetLastError();
+}
+// A profile frame (k_trace_primary's STAMP): the plain frame of single-wave workgroups on a scene with a fast tree, no table; ticks =
+// ((nst_rank + 7) / 8) * 8 device words, zeroed here on the launch's stream.  false: the launch is not of that kind (nothing was issued).
+bool can_profile_frame(const SceneDev& S, const FrameDev& F) {
+    return F.nblocks != 0 && F.block == 64 && !F.hint && !F.packed && S.fast_root != REF_NONE && !plan_frame(S, F).quad;
+}
+hipError_t launch_trace_primary_profile(const SceneDev& S, const CameraDev& C, const FrameDev& F_in, CgrtHitDev* hits, float* normals,
+                                        uint32_t* ticks, hipStream_t stream) {
+    if (!can_profile_frame(S, F_in) || !ticks) return hipErrorInvalidValue;
+    FrameDev F = F_in;
+    F.order = nullptr;
+    const hipError_t e = hipMemsetAsync(ticks, 0, sizeof(uint32_t) * (size_t)(F.nblocks / 64u), stream);
+    if (e != hipSuccess) return e;
+    launch(k_trace_primary<false, true, false, false, false, false, false, true>, F.nblocks, 64u, stream, S, C, F, hits, normals,
+           reinterpret_cast<unsigned long long*>(ticks));
+    return hipGetLastError();
+}
+hipError_t launch_build_frame_order(const uint32_t* ticks, uint32_t nst, uint32_t live, uint16_t* out, hipStream_t stream) {
+    const uint32_t n_pad = (nst + 7u) / 8u * 8u;
+    if (n_pad == 0) return hipSuccess;
+    if (n_pad > CGRT_ORDER_MAX_POSITIONS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_build_frame_order, dim3(8), dim3(256), 0, stream, ticks, n_pad, nst, live, out);
     return hipGetLastError();
 }
 hipError_t launch_trace_batch(const SceneDev& S, const RayList& R, unsigned long long* counters, hipStream_t stream, ListGrid grid) {

@@ -23,7 +23,8 @@ __global__ CGRT_LB void k_trace_primary_stamped(SceneDev S, CameraDev C, FrameDe
     const uint32_t wave_global = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const unsigned long long st0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
     int x = 0, y = 0;
-    const bool active = tile_pixel(F, lane, x, y);
+    // (F.order: the launch order of the scene's ordered frames, so that their wave anatomy can be set beside the plain launch's)
+    const bool active = F.order ? tile_pixel_of<false, true>(F, blockIdx.x, threadIdx.x, x, y) : tile_pixel(F, lane, x, y);
     LaneCounters cnt;
     F3 o = f3(0, 0, 0), d = f3(0, 0, 0);
     if (active) primary_ray(C, F.W, F.H, x, y, o, d);

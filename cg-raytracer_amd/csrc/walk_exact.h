@@ -816,12 +816,19 @@ __device__ __forceinline__ void primary_ray(const RayCameraDev& C, int x, int y,
 // of a workgroup take 4 horizontally adjacent 8x8 tiles.
 // VIEWS (multi-view frames, FrameDev::views): the same rule over the super-tiles of all views as one list; *view = the view of
 // super-tile s, which the workgroup's waves share (wave-uniform).
-template <bool VIEWS = false>
+// ORDER (FrameDev::order): position s of the launch traces super-tile order[s] -- one scalar load of the aligned word that holds the
+// entry (s depends on the workgroup alone).  The table has an entry for every position of the padded launch and maps the padded
+// positions to themselves, so the test against nst_rank is the same test.
+template <bool VIEWS = false, bool ORDER = false>
 __device__ __forceinline__ bool tile_pixel_of(const FrameDev& F, const uint32_t b, const uint32_t tid, int& x, int& y, uint32_t* view = nullptr) {
     const uint32_t lane8 = b & 7u, j = b >> 3;
     const int lane = (int)(tid & 63u);
     const uint32_t wpb = blockDim.x >> 6, bps = 64u / wpb;  // waves per workgroup, workgroups per super-tile
-    const uint32_t s = (j / bps) * 8u + lane8;  // rank-local super-tile
+    uint32_t s = (j / bps) * 8u + lane8;  // rank-local super-tile
+    if (ORDER) {
+        const uint32_t w = reinterpret_cast<const uint32_t*>(F.order)[s >> 1];
+        s = (s & 1u) ? (w >> 16) : (w & 0xffffu);
+    }
     if (s >= F.nst_rank) return false;
     uint32_t st;
     if (VIEWS) {  // (one rank)

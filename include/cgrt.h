@@ -138,6 +138,26 @@ int cgrt_get_kernel_shape(int* mode, uint64_t* max_rays);
  * streams the library falls back to unhinted launches for a few frames (the *_device entries stay safe to call from several
  * threads, they are just not accelerated then).  Process-wide. */
 int cgrt_set_frame_hints(int mode);
+/* Frame order of the primary frame entries (cgrt_trace_primary*): whole frames and large shares -- single-wave
+ * workgroups on a fast tree, not packed, no counters, left alone by the frame hints above -- are launched with an ORDER TABLE once one
+ * shape has been traced three times in a row on one stream: the third launch also records the longest wave time of every 64x64
+ * super-tile, a small kernel behind it deals the super-tiles with long waves to the earliest of the launch positions that heavy
+ * super-tiles hold anyway (per blockIdx % 8 lane: XCD placement and the pattern of heavy and background work stay what they are), and
+ * the launches after it read that table; the shape is profiled again every 32 launches.  Nothing waits for the host.  Only the order of
+ * dispatch changes: every pixel is traced once, by the same arithmetic (tested bit for bit).  Streams and shapes as with the hints: a
+ * change means eight launches without a table.  -1 (default) = the library's policy (on), 0 = off, 1 = on wherever a frame qualifies.
+ * Process-wide; the CGRT_FRAME_ORDER environment variable overrides it (experiments). */
+int cgrt_set_frame_order(int mode);
+/* Tests.  cgrt_debug_set_frame_order installs `table` (n = the shape's super-tiles for this rank, padded to 8) for the next launches of
+ * that shape on this scene, in place of the policy's profile frames, after a device synchronise; CGRT_E_ARG unless the table is a
+ * permutation that keeps every position's % 8 residue and the padded positions and n is that length; table = NULL, n = 0 returns the
+ * scene to the policy.  cgrt_debug_get_frame_order: *n = entries of the table in use (0: none) and, when `table` holds at least that
+ * many (cap), the table, after a device synchronise; state2 = {0 none / 1 profiled: the builder follows the last launch / 2 active: the
+ * last launch read the table, launches since the profile frame}.  cgrt_debug_build_frame_order runs the device builder alone on n
+ * injected tick values (10 ns each; 500 and more: live) and returns the (n + 7) / 8 * 8 entries it makes. */
+int cgrt_debug_set_frame_order(CgrtScene* scene, int W, int H, int x0, int y0, int x1, int y1, int rank, int nranks, const uint16_t* table, uint32_t n);
+int cgrt_debug_get_frame_order(CgrtScene* scene, uint16_t* table, uint32_t cap, uint32_t* n, int* state2);
+int cgrt_debug_build_frame_order(const uint32_t* ticks, uint32_t n, uint16_t* out);
 /* Frame gate of the camera frames (cgrt_trace_primary*, cgrt_render* with one CgrtCamera): 1 (default) = the host projects the mesh
  * root box onto the screen per launch, and a wave whose pixels all lie outside that rectangle (widened by a margin)
  * writes its miss records without generating rays; 0 = every pixel takes the per-pixel root gate.  Same bytes either way (tested).

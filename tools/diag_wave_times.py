@@ -10,6 +10,11 @@ sd = pkg.scenes.make_dragon(int(os.environ.get("TRIS", "800000")))
 W, H = 1920, 1080
 cam = pkg.scenes.default_camera(W, H)
 sc = pkg.Scene(sd)
+if os.environ.get("ORDERED"):  # frames of the shape first, so that the scene has its order table: the stamps are the ordered launch's
+    for _ in range(int(os.environ["ORDERED"])):
+        sc.trace_primary(cam, W, H)
+    tab, state, since = sc.debug_get_frame_order()
+    print("order table:", "none" if tab is None else "%d of %d positions moved" % (int((tab != np.arange(len(tab))).sum()), len(tab)), "state", state)
 t = sc.debug_wave_times(cam, W, H).astype(np.int64)
 dur = t[:, 1] - t[:, 0]           # shader cycles
 rt = (t[:, 2:4] - t[:, 2].min()) / 100.0  # us (s_memrealtime ticks at 100 MHz)
@@ -23,6 +28,7 @@ print("heavy waves (>5us):", heavy.sum(), "sum wall us", wall[heavy].sum(), "=> 
 edges = np.arange(0, rt[:, 1].max() + 10, 10)
 running = [(int(((rt[:, 0] <= x) & (rt[:, 1] > x)).sum())) for x in edges]
 print("running waves every 10us:", running)
+print("last wave starts at us:", round(float(rt[:, 0].max()), 1), "drain after it us:", round(float(rt[:, 1].max() - rt[:, 0].max()), 1))
 print("start time of waves (us) percentiles:", [round(float(np.percentile(rt[:, 0], p)), 1) for p in (1, 25, 50, 75, 99, 100)])
 order = np.argsort(-wall)[:10]
 print("slowest waves: idx, start, wall:", [(int(i), round(float(rt[i, 0]), 1), round(float(wall[i]), 1)) for i in order])
