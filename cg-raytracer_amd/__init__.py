@@ -45,6 +45,10 @@ assert SURFACE_SAMPLE_DTYPE.itemsize == 32
 # include/cgrt.h CgrtPointNeighbor: one data point within a query point's radius (8 bytes); an unused entry of a slot is {+inf, NO_PRIM}
 POINT_NEIGHBOR_DTYPE = np.dtype([("dist2", np.float32), ("index", np.uint32)])
 assert POINT_NEIGHBOR_DTYPE.itemsize == 8
+# include/cgrt.h CgrtPointFrame
+POINT_FRAME_DTYPE = np.dtype([("centroid", np.float32, 3), ("used", np.uint32), ("normal", np.float32, 3), ("lambda0", np.float32),
+                              ("tangent_u", np.float32, 3), ("lambda1", np.float32), ("tangent_v", np.float32, 3), ("lambda2", np.float32)])
+assert POINT_FRAME_DTYPE.itemsize == 64
 POINTS_SKIP_SAME_INDEX = 1  # include/cgrt.h CGRT_POINTS_SKIP_SAME_INDEX
 ISO_INSIDE_ABOVE = 1  # include/cgrt.h CGRT_ISO_INSIDE_ABOVE
 _SLOT_RECORDS = {"crossings": CROSSING_DTYPE, "neighbors": NEIGHBOR_DTYPE}  # the slot-list entries (Scene._slots_*) by the name in their symbols
@@ -113,6 +117,12 @@ class PointNeighbor(C.Structure):
 class PointQuery(C.Structure):
     """include/cgrt.h CgrtPointQuery."""
     _fields_ = [("radius2", C.c_void_p), ("max_dist2", C.c_float), ("flags", C.c_uint32)]
+
+
+class PointFrame(C.Structure):
+    """include/cgrt.h CgrtPointFrame."""
+    _fields_ = [("centroid", C.c_float * 3), ("used", C.c_uint32), ("normal", C.c_float * 3), ("lambda0", C.c_float),
+                ("tangent_u", C.c_float * 3), ("lambda1", C.c_float), ("tangent_v", C.c_float * 3), ("lambda2", C.c_float)]
 
 
 def _point_query(radius2_ptr: int = 0, max_dist2: float = float("inf"), skip_same_index: bool = False) -> PointQuery:
@@ -413,7 +423,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_set_frame_order", "cgrt_debug_set_frame_order", "cgrt_debug_get_frame_order", "cgrt_debug_build_frame_order", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_point_grid_workspace", "cgrt_point_grid_build_device", "cgrt_count_point_neighbors", "cgrt_count_point_neighbors_device", "cgrt_list_point_neighbors", "cgrt_list_point_neighbors_device", "cgrt_list_point_neighbors_brute", "cgrt_debug_point_neighbor_work", "cgrt_isosurface_workspace", "cgrt_isosurface_count_device", "cgrt_isosurface_device", "cgrt_isosurface", "cgrt_debug_isosurface_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_point_grid_workspace", "cgrt_point_grid_build_device", "cgrt_count_point_neighbors", "cgrt_count_point_neighbors_device", "cgrt_list_point_neighbors", "cgrt_list_point_neighbors_device", "cgrt_list_point_neighbors_brute", "cgrt_debug_point_neighbor_work", "cgrt_point_frames", "cgrt_point_frames_device", "cgrt_point_frames_brute", "cgrt_isosurface_workspace", "cgrt_isosurface_count_device", "cgrt_isosurface_device", "cgrt_isosurface", "cgrt_debug_isosurface_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -588,6 +598,9 @@ def lib() -> C.CDLL:
     L.cgrt_list_point_neighbors.argtypes = [vp, vp, u64, C.c_float, vp, u64, pq, vp, u32, vp, u64, vp]
     L.cgrt_list_point_neighbors_brute.argtypes = [vp, vp, u64, vp, u64, pq, vp, u32, vp, u64, vp]
     L.cgrt_debug_point_neighbor_work.argtypes = [vp, vp, u64, C.c_float, vp, u64, pq, u32, vp]
+    L.cgrt_point_frames_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, pq, u32, vp, vp, vp, vp]
+    L.cgrt_point_frames.argtypes = [vp, vp, u64, C.c_float, vp, u64, pq, u32, vp, vp, vp]
+    L.cgrt_point_frames_brute.argtypes = [vp, vp, u64, vp, u64, pq, u32, vp, vp, vp]
     gp, ip = C.POINTER(Grid), C.POINTER(IsoParams)
     L.cgrt_isosurface_workspace.argtypes = [vp, gp, C.POINTER(u64)]
     L.cgrt_isosurface_count_device.argtypes = [vp, gp, vp, ip, vp, vp, u64, vp]
@@ -3064,6 +3077,48 @@ class Scene:
         self.point_grid_build_device(data.data_ptr() if m else 0, m, cell, grid.data_ptr(), nbytes, stream=stream.cuda_stream)
         return PointGrid(self, grid, m, float(cell))
 
+    # ---- point-set frames (include/cgrt.h cgrt_point_frames*) ----
+    def _point_frames_host(self, data, cell, points, k, radius2, max_dist2, skip_same_index, orient, want_neighbors, brute):
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        d, p, r, q = self._point_cloud_args(data, points, radius2, max_dist2, skip_same_index)
+        o = None if orient is None else _f32(orient, (-1, 3))
+        if o is not None and len(o) != len(p):
+            raise ValueError("orient must hold one vector per point")
+        n = len(p)
+        frames = np.zeros(n, POINT_FRAME_DTYPE)
+        nb = np.zeros((n, k), POINT_NEIGHBOR_DTYPE) if want_neighbors else None
+        tail = (_ptr(p), n, C.byref(q), int(k), _ptr(o), _ptr(nb), _ptr(frames))
+        if brute:
+            _check(lib().cgrt_point_frames_brute(self._h, _ptr(d), len(d), *tail))
+        else:
+            _check(lib().cgrt_point_frames(self._h, _ptr(d), len(d), float(cell), *tail))
+        return (frames, nb) if want_neighbors else frames
+
+    def point_frames(self, data, cell: float, points, k: int, radius2=None, max_dist2: float = float("inf"), skip_same_index: bool = False,
+                     orient=None, want_neighbors: bool = False):
+        """cgrt_point_frames: for every query point ((n, 3) float32) the local PCA of its k nearest points of `data` ((m, 3) float32) within
+        its squared radius -- (n,) POINT_FRAME_DTYPE records {centroid, used, normal, lambda0, tangent_u, lambda1, tangent_v, lambda2},
+        defined to the last bit by include/cgrt.h "Point-set frames".  cell: the wanted cell edge of the call's own grid (no result
+        depends on it).  orient ((n, 3) float32, optional): the normal is turned to the side of orient[i].  With want_neighbors=True
+        returns (frames, neighbors (n, k) POINT_NEIGHBOR_DTYPE): the records nearest_points gives."""
+        return self._point_frames_host(data, cell, points, k, radius2, max_dist2, skip_same_index, orient, want_neighbors, False)
+
+    def point_frames_brute(self, data, points, k: int, radius2=None, max_dist2: float = float("inf"), skip_same_index: bool = False,
+                           orient=None, want_neighbors: bool = False):
+        """cgrt_point_frames_brute: point_frames by testing every data point in turn, no grid (validation; the same bytes)."""
+        return self._point_frames_host(data, 0.0, points, k, radius2, max_dist2, skip_same_index, orient, want_neighbors, True)
+
+    def point_frames_device(self, d_grid_ptr: int, grid_bytes: int, d_data_ptr: int, m: int, d_points_ptr: int, n: int, k: int,
+                            d_neighbors_ptr: int, d_frames_ptr: int, d_orient_ptr: int = 0, d_radius2_ptr: int = 0,
+                            max_dist2: float = float("inf"), skip_same_index: bool = False, stream: int = 0) -> None:
+        """cgrt_point_frames_device: n points at d_points_ptr against the built grid at d_grid_ptr and the m points at d_data_ptr it was
+        built on -> n * k neighbour records of 8 bytes at d_neighbors_ptr and n frame records of 64 bytes at d_frames_ptr (16-byte
+        aligned), enqueued on the hipStream_t `stream`.  Raw integers."""
+        q = _point_query(d_radius2_ptr, max_dist2, skip_same_index)
+        _check(lib().cgrt_point_frames_device(self._h, _vp(d_grid_ptr), int(grid_bytes), _vp(d_data_ptr), int(m), _vp(d_points_ptr), int(n),
+                                              C.byref(q), int(k), _vp(d_orient_ptr), _vp(d_neighbors_ptr), _vp(d_frames_ptr), _vp(stream)))
+
     # ---- iso-surfaces (include/cgrt.h cgrt_isosurface*; DESIGN.md section 5.31) ----
     def isosurface(self, values, origin, spacing, iso: float = 0.0, inside_above: bool = False):
         """cgrt_isosurface: the triangle mesh of the level `iso` of values ((nz, ny, nx) float32 on the grid origin + i * spacing), by
@@ -3436,6 +3491,76 @@ class PointGrid:
                     break
                 r2 = torch.where(done, torch.full_like(r2, -1.0), r2 * 4.0)
         return out
+
+    @staticmethod
+    def _frame_views(buf, neighbors) -> dict:
+        """The fields of (n, 16) float32 frame records as views of that one tensor (include/cgrt.h CgrtPointFrame)."""
+        import torch
+
+        return dict(centroid=buf[:, 0:3], used=buf.view(torch.int32)[:, 3], normal=buf[:, 4:7], tangent_u=buf[:, 8:11], tangent_v=buf[:, 12:15],
+                    eigenvalues=buf[:, 7::4], neighbors=neighbors, records=buf)
+
+    def _frames_call(self, points, data, k: int, radius2, max_dist2, skip_same_index, orient, stream):
+        """(frames (n, 16) float32, neighbors (n, k, 2) float32), enqueued on `stream`."""
+        import torch
+
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        n, rad, md, g, gb = self._args(points, radius2, max_dist2)
+        m = self.scene._points_tensor(data)
+        if m != self.m:
+            raise ValueError("data must be the (m, 3) tensor the grid was built on")
+        if orient is not None:
+            self.scene._device_tensor(orient, "orient", (torch.float32,), (n, 3))
+        dev, stream = self.scene._torch_stream(stream)
+        _check_one_hip_runtime()
+        with torch.cuda.stream(stream):
+            buf = torch.empty((n, 16), dtype=torch.float32, device=dev)
+            nb = torch.empty((n, k, 2), dtype=torch.float32, device=dev)
+        if n:
+            self.scene.point_frames_device(g, gb, data.data_ptr() if m else 0, m, points.data_ptr(), n, k, nb.data_ptr(), buf.data_ptr(),
+                                           d_orient_ptr=orient.data_ptr() if orient is not None else 0, d_radius2_ptr=rad, max_dist2=md,
+                                           skip_same_index=skip_same_index, stream=stream.cuda_stream)
+        return buf, nb
+
+    def frames(self, points, data, k: int, radius2=None, max_dist2: float = float("inf"), skip_same_index: bool = False, orient=None,
+               stream=None) -> dict:
+        """The local PCA of every query's k nearest data points within its squared radius (include/cgrt.h "Point-set frames"): search
+        and solve in one kernel, only enqueued.  data: the (m, 3) tensor the grid was built on, alive and unchanged until the call has
+        run (the frames read coordinates by index).  orient ((n, 3) float32, optional): normals are turned to the side of orient[i].
+        A dict of views over ONE (n, 16) float32 tensor ('records'): 'centroid', 'normal', 'tangent_u', 'tangent_v' (n, 3), 'eigenvalues'
+        (n, 3) ascending, 'used' (n,) int32 -- and 'neighbors' (n, k, 2), the records `nearest` gives.  used == 0: a record of zeros."""
+        return self._frame_views(*self._frames_call(points, data, k, radius2, max_dist2, skip_same_index, orient, stream))
+
+    def knn_frames(self, points, data, k: int, skip_same_index: bool = False, orient=None, stream=None) -> dict:
+        """`frames` over the k nearest data points with no radius from the caller: byte for byte what the brute form gives for r2 = +inf.
+        The composition of `knn`: `frames` at r2 = cell^2; a query whose used reaches k is finished; the others are asked again in place
+        with 4 r2 (a negative radius for the finished ones) up to KNN_PASSES times, and what is still short takes one unbounded pass.
+        BLOCKS: the number of unfinished queries is read back after every pass."""
+        import torch
+
+        n = self.scene._points_tensor(points)
+        dev, stream = self.scene._torch_stream(stream)
+        with torch.cuda.stream(stream):
+            if n == 0:
+                return self._frame_views(*self._frames_call(points, data, k, None, float("inf"), skip_same_index, orient, stream))
+            c2 = float(np.float32(self.cell) * np.float32(self.cell))
+            r2 = torch.full((n,), c2, dtype=torch.float32, device=dev)
+            done = torch.zeros((n,), dtype=torch.bool, device=dev)
+            buf = nb = None
+            for p in range(self.KNN_PASSES + 1):
+                if p == self.KNN_PASSES:
+                    r2 = torch.where(done, torch.full_like(r2, -1.0), torch.full_like(r2, float("inf")))
+                b, r = self._frames_call(points, data, k, r2, float("inf"), skip_same_index, orient, stream)
+                if p:  # (as integers: an index's bits may spell a NaN)
+                    b = torch.where(done[:, None], buf.view(torch.int32), b.view(torch.int32)).view(torch.float32)
+                    r = torch.where(done[:, None, None], nb.view(torch.int32), r.view(torch.int32)).view(torch.float32)
+                buf, nb = b, r
+                done = done | (buf.view(torch.int32)[:, 3] >= k)
+                if p == self.KNN_PASSES or bool(done.all().item()):
+                    break
+                r2 = torch.where(done, torch.full_like(r2, -1.0), r2 * 4.0)
+        return self._frame_views(buf, nb)
 
 
 # ---- one caller, N devices, one framebuffer ----

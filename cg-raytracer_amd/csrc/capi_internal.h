@@ -35,6 +35,7 @@
 #include "crossing_kernels.h"
 #include "isosurface_kernels.h"
 #include "neighbor_kernels.h"
+#include "point_frame_kernels.h"
 #include "point_neighbor_kernels.h"
 #include "poisson_kernels.h"
 #include "sdf_kernels.h"

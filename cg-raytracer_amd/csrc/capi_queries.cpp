@@ -1,5 +1,5 @@
 // capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
-// closest points, crossings, neighbours, signed distance, winding numbers, surface samples, Poisson-disk sets, point-set neighbours, iso-surfaces.  None of them touches the scene's frame state (workspace, prediction, hints).
+// closest points, crossings, neighbours, signed distance, winding numbers, surface samples, Poisson-disk sets, point-set neighbours, point-set frames, iso-surfaces.  None of them touches the scene's frame state (workspace, prediction, hints).
 // Every family is ONE body for its host-pointer and its device-pointer entries, written with a QueryCall (capi_internal.h): the argument
 // checks in the order include/cgrt.h states (`device`: the pointers' alignment too), the host-only scene, the empty call, then begin,
 // in / out per array, the launch on the call's stream, finish.  The exported entries are one-line forwarders.
@@ -1184,6 +1184,89 @@ int cgrt_debug_point_neighbor_work(CgrtScene* s, const float* data, uint64_t m, 
     // (n <= 0x7fffffff is checked before the capacity n k is looked at)
     return point_neighbor_query(s, false, {data, m, cell, nullptr, 0}, points, n, query, {k > 0, nullptr, k, nullptr, n * (uint64_t)k, nullptr}, 2,
                                 out6, nullptr);
+}
+
+// ---- point-set frames (include/cgrt.h cgrt_point_frames*): centroid, covariance eigenvalues and a right-handed
+// frame of every query's k nearest data points within its squared radius, search and solve in one kernel.  The checks are the point-set
+// neighbour entries' in their order, with k, n * k and the frames' alignment added; all before any device work.
+namespace {
+static_assert(sizeof(CgrtPointFrame) == sizeof(CgrtPointFrameDev), "CgrtPointFrame is what the kernel writes");
+// slots: 0 the points, 4 the radii, 1 the orientation vectors, 2 the neighbour records (the lane's own where the caller wants none), 3 the
+// frames; how: 0 the grid, 1 brute force (host form only)
+int point_frame_query(CgrtScene* s, bool device, const PointCloud& G, const float* points, uint64_t n, const CgrtPointQuery* q, uint32_t k,
+                      const float* orient, CgrtPointNeighbor* neighbors, CgrtPointFrame* frames, int how, void* stream) {
+    if (!s || !q) return fail(CGRT_E_ARG, "scene or query is NULL");
+    if (n && (!points || !frames || (device && !neighbors) || (G.m && !G.data) || (device && !G.d_grid))) return fail(CGRT_E_ARG, "NULL argument");
+    if (n > kMaxCloud) return fail(CGRT_E_ARG, "too many queries: n exceeds 0x7fffffff");
+    if (G.m > kMaxCloud) return fail(CGRT_E_ARG, "too many data points: m exceeds 0x7fffffff");
+    if (!device && how != 1 && !cell_ok(G.cell)) return fail(CGRT_E_ARG, "cell must be finite and > 0");
+    if (!(q->max_dist2 >= 0.0f)) return fail(CGRT_E_ARG, "max_dist2 must be a number >= 0 (+inf: unbounded)");
+    if (q->flags & ~(uint32_t)CGRT_POINTS_SKIP_SAME_INDEX) return fail(CGRT_E_ARG, "unknown flags");
+    if (k == 0) return fail(CGRT_E_ARG, "k must be at least 1");
+    if (n * (uint64_t)k > kSlotMaxCapacity) return fail(CGRT_E_ARG, "n * k exceeds 2^37 records");
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)q->radius2 % 4 || (uintptr_t)G.data % 4 || (uintptr_t)orient % 4 ||
+                   (uintptr_t)neighbors % 4 || (uintptr_t)G.d_grid % 8))
+        return fail(CGRT_E_ARG, "device pointers must be aligned to their elements (d_grid: 8 bytes)");
+    if (device && (uintptr_t)frames % 16) return fail(CGRT_E_ARG, "d_frames must be 16-byte aligned");
+    if (device && n && G.grid_bytes < point_grid_bytes(0)) return fail(CGRT_E_ARG, "grid_bytes is below cgrt_point_grid_workspace");
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    OwnedDevice own;
+    QueryCall c(s, device, stream);
+    void *dp = nullptr, *drad = nullptr, *dorient = nullptr, *dnb = nullptr, *dfr = nullptr;
+    PointFrameArgs A{};
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, points, n * 12, "d_points", &dp));
+    CGRT_TRY(c.in(4, q->radius2, q->radius2 ? n * 4 : 0, "d_radius2", &drad));
+    CGRT_TRY(c.in(1, orient, orient ? n * 12 : 0, "d_orient", &dorient));
+    if (device || neighbors)
+        CGRT_TRY(c.out(2, neighbors, n * k * sizeof(CgrtPointNeighbor), "d_neighbors", &dnb));
+    else
+        HIP_TRY(c.c.scratch(2, n * k * sizeof(CgrtPointNeighbor), &dnb));  // (the kernel's slots; nothing comes back)
+    CGRT_TRY(c.out(3, frames, n * sizeof(CgrtPointFrame), "d_frames", &dfr));
+    if (device) {
+        CGRT_TRY(check_device_span(s, G.d_grid, G.grid_bytes, "d_grid"));
+        CGRT_TRY(check_device_span(s, G.data, G.m * 12, "d_data"));
+        A.grid = G.d_grid;
+        A.grid_bytes = G.grid_bytes;
+        A.data = G.data;
+    } else {  // the grid (none: brute force), then the cloud
+        const uint64_t gbytes = how == 1 ? 0 : point_grid_bytes(G.m);
+        HIP_TRY(hipMalloc(&own.p, gbytes + 12 * G.m + 16));
+        float* const ddata = reinterpret_cast<float*>(static_cast<char*>(own.p) + gbytes);
+        if (G.m) HIP_TRY(staged_h2d(ddata, G.data, 12 * G.m));  // (complete when it returns)
+        if (how != 1) HIP_TRY(launch_point_grid_build(ddata, G.m, G.cell, own.p, c.stream()));
+        A.grid = own.p;
+        A.grid_bytes = gbytes;
+        A.data = ddata;
+    }
+    A.m = G.m;
+    A.points = static_cast<const float*>(dp);
+    A.radius2 = static_cast<const float*>(drad);
+    A.max_dist2 = q->max_dist2;
+    A.flags = q->flags;
+    A.n = n;
+    A.k = k;
+    A.orient = orient ? static_cast<const float*>(dorient) : nullptr;
+    A.neighbors = static_cast<CgrtPointNeighborDev*>(dnb);
+    A.frames = static_cast<CgrtPointFrameDev*>(dfr);
+    HIP_TRY(launch_point_frames(A, how == 1, c.stream()));
+    return c.finish();
+}
+}  // namespace
+
+int cgrt_point_frames_device(CgrtScene* s, const void* d_grid, uint64_t grid_bytes, const float* d_data, uint64_t m, const float* d_points,
+                             uint64_t n, const CgrtPointQuery* query, uint32_t k, const float* d_orient, CgrtPointNeighbor* d_neighbors,
+                             CgrtPointFrame* d_frames, void* stream) {
+    return point_frame_query(s, true, {d_data, m, 0.0f, d_grid, grid_bytes}, d_points, n, query, k, d_orient, d_neighbors, d_frames, 0, stream);
+}
+int cgrt_point_frames(CgrtScene* s, const float* data, uint64_t m, float cell, const float* points, uint64_t n, const CgrtPointQuery* query,
+                      uint32_t k, const float* orient, CgrtPointNeighbor* neighbors, CgrtPointFrame* frames) {
+    return point_frame_query(s, false, {data, m, cell, nullptr, 0}, points, n, query, k, orient, neighbors, frames, 0, nullptr);
+}
+int cgrt_point_frames_brute(CgrtScene* s, const float* data, uint64_t m, const float* points, uint64_t n, const CgrtPointQuery* query, uint32_t k,
+                            const float* orient, CgrtPointNeighbor* neighbors, CgrtPointFrame* frames) {
+    return point_frame_query(s, false, {data, m, 0.0f, nullptr, 0}, points, n, query, k, orient, neighbors, frames, 1, nullptr);
 }
 
 // ---- iso-surfaces (include/cgrt.h cgrt_isosurface*): the triangle mesh of one level of a scalar grid, by marching

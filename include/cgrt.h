@@ -1464,6 +1464,94 @@ int cgrt_list_point_neighbors_brute(CgrtScene* scene, const float* data, uint64_
 int cgrt_debug_point_neighbor_work(CgrtScene* scene, const float* data, uint64_t m, float cell, const float* points, uint64_t n,
                                    const CgrtPointQuery* query, uint32_t k, uint64_t* out6);
 
+/* Point-set frames: the first use "Point-set neighbours" names -- a normal per point -- and what needs a local
+ * frame: per query point the centroid, the three eigenvalues of the covariance and a right-handed frame of its k nearest data points
+ * within a squared radius (local PCA).  normal is the direction of least variance; lambda0 / (lambda0 + lambda1 + lambda2) is the surface
+ * variation; tangent_u and tangent_v span the tangent plane.  One kernel does the search and the solve; nothing is left to a library
+ * routine.  The scene names the device and lends its call lanes; its geometry is not read.  All arithmetic is f32 and IEEE, every operation
+ * rounded on its own, nothing contracted; the only operations are + - x / sqrt and comparisons.  The definition below IS the specification
+ * (tests/point_frames_ref.py restates it in numpy and gives the same bytes).  For query i:
+ * 1. Neighbourhood.  Exactly the slot cgrt_list_point_neighbors writes for this data, query, bound and flag with k records per query and
+ *    no counts: the first min(k, count) neighbours in (d2, index) order, then {+inf, CGRT_NO_PRIM}.  used = the number of real records.
+ *    used == 0 (also: a non-finite query, a NaN or negative radius2[i]) gives a record of 64 zero bytes.
+ * 2. Centroid.  p_j = data[index_j], j = 0 .. used - 1 in slot order; ref = p_0.  Per axis s = sum_j fl(p_j - ref), added one by one
+ *    from +0 in that order; c = fl(ref + fl(s / (float)used)).
+ * 3. Covariance.  e_j = fl(p_j - c).  The six sums xx, xy, xz, yy, yz, zz of fl(e_a e_b), each added one by one from +0 in slot order,
+ *    each then divided by (float)used: the symmetric matrix a.
+ * 4. Eigen-solve.  Cyclic Jacobi on a, V = identity.  A sweep visits the pairs (p, q) = (0, 1), (0, 2), (1, 2), r the third index.  A
+ *    pair with a_pq == 0 is skipped.  Otherwise theta = fl(fl(a_qq - a_pp) / fl(2 a_pq)); t = (theta < 0 ? -1 : 1) / fl(|theta| +
+ *    sqrt(fl(fl(theta theta) + 1))); c = 1 / sqrt(fl(fl(t t) + 1)); s = fl(t c); h = fl(t a_pq); a_pp = fl(a_pp - h); a_qq = fl(a_qq + h);
+ *    a_pq = 0; a_rp' = fl(fl(c a_rp) - fl(s a_rq)), a_rq' = fl(fl(s a_rp) + fl(c a_rq)); and in every row i of V, V_ip' = fl(fl(c V_ip) -
+ *    fl(s V_iq)), V_iq' = fl(fl(s V_ip) + fl(c V_iq)).  After a sweep the loop ends if all three off-diagonals are == 0; it ends after 8
+ *    sweeps in any case.
+ * 5. Order.  The eigenvalues are the diagonal, sorted ascending together with their columns of V by three exchanges: (0, 1), (1, 2),
+ *    (0, 1), each made iff `d_b < d_a` is true -- a stable sort: ties and NaNs keep column order.  normal, tangent_u, tangent_v are the
+ *    columns of lambda0 <= lambda1 <= lambda2.  Nothing is renormalised.
+ * 6. Signs.  normal and tangent_u are each negated iff their component of largest magnitude is < 0 (found by `|v_1| > |v_0|`, then
+ *    `|v_2| > the larger`: on a tie the first counts, a NaN never does).  If orient is given, o = orient[i] has three finite components and
+ *    fl(fl(fl(n.x o.x) + fl(n.y o.y)) + fl(n.z o.z)) < 0, normal is negated.  Then with w = (fl(fl(n.y u.z) - fl(n.z u.y)), fl(fl(n.z u.x) -
+ *    fl(n.x u.z)), fl(fl(n.x u.y) - fl(n.y u.x))), tangent_v is negated iff fl(fl(fl(w.x v.x) + fl(w.y v.y)) + fl(w.z v.z)) < 0: a
+ *    right-handed frame (normal x tangent_u = tangent_v) wherever that means something.
+ * 7. Record.  CgrtPointFrame below, 64 bytes; every float that is a NaN is stored as 0x7fc00000 (the sign and payload of a NaN are the one
+ *    thing IEEE arithmetic leaves open).  Every byte of every record is written.
+ * 8. Degenerate input is returned as the arithmetic gives it.  used == 1: a zero matrix, the identity's columns, centroid = p_0.  used
+ *    == 2 and collinear or coplanar neighbours: a rank-deficient matrix; the eigenvalues are right (0 up to rounding), the vectors of
+ *    the null space deterministic but arbitrary.  Equal eigenvalues: any frame of the eigenspace.  Differences or squares that overflow
+ *    give inf and then NaN, which propagate as defined above.
+ * Determinism.  The record is a function of (data, points, bound, flag, k, orient) alone: not of the cell size, the bucket count, the
+ * order inside a bucket, the launch shape, the stream or the run.  cgrt_point_frames_brute -- every data point in turn, the same function
+ * -- returns the same bytes; it is the yardstick.  The neighbour array receives exactly the bytes of the list call.
+ * Scale.  Multiplying data, queries (and the cell) by 2^s and every bound by 2^2s multiplies centroid by 2^s and the eigenvalues by 2^2s
+ * exactly and leaves the vectors and used unchanged, while the query is inside the point-neighbour envelope at 2^s AND every product or
+ * quotient of steps 2 to 4 that carries the scale -- s / used, e_a e_b, sum / used, t a_pq, c a_rp, s a_rq, s a_rp, c a_rq -- is zero or a
+ * normal float at both scales (additions and subtractions are exact where they underflow; theta, t, c, s and V carry no scale).  This is
+ * a sufficient condition and a narrow one: the late sweeps multiply off-diagonals that are already far below an ulp of the diagonal, down
+ * to about 2^-140 of the trace T, so it asks T and T 2^2s to lie within about [2^14, 2^120].  Outside it the bytes are still the defined
+ * ones on every path; the relation to scale 1 was observed to hold there too (the values that underflow meet nothing they could change)
+ * but is not claimed.  tests/point_frames_ref.py reports the smallest and largest such value per query (in_frame_envelope).
+ * Accuracy (measured through the restatement against numpy.linalg.eigh in float64 on the float64 covariance of the same neighbours,
+ * tests/test_point_frames_cpu.py; the clouds are a sample of inputs, not a worst case, and the tests hold four times these figures).
+ * With u = 2^-24, T the trace and P the largest coordinate magnitude of the neighbourhood, the largest values measured (k = 3, 8, 32):
+ * |lambda - lambda64| <= 3.36 u T + 1.03 u^2 P^2 (the second term is the centroid's rounding, which enters every e_j; it dominates for a
+ * cloud far from the origin relative to its spread: 8000 u T at offset 100 with spread 0.01 and k = 3); the squared length of every
+ * vector is within 13.2 u of 1; the angle between normal and the float64 eigenvector, times the relative gap (lambda1 - lambda0) / T, is
+ * at most 1.50 (u + u^2 P^2 / T) over the queries whose gap exceeds 1e-2.  Every off-diagonal was exactly zero after at most 5 sweeps.
+ * The entries.  cgrt_point_frames_device enqueues on `stream` (NULL = default stream) and never blocks: d_grid, grid_bytes a built grid;
+ * d_data, m the array it was built on, which the caller keeps alive and unchanged until the call has run -- unlike the list queries, the
+ * frames read coordinates by index (an index that is not below m, which only a grid of other data holds, is never used as an address:
+ * that query's record is 64 zero bytes); d_orient NULL or n x 3 f32; d_neighbors n * k records, a required output (the k nearest and the
+ * frames come from one call); d_frames n records, 16-byte aligned.  cgrt_point_frames (host pointers, synchronous) builds and frees a grid
+ * of its own on a call lane like cgrt_list_point_neighbors; its neighbors may be NULL.  cgrt_point_frames_brute: the host form over every
+ * data point in turn.  One query per lane, 256 lanes per block; after its search the lane reads its own slot back, gathers data[index]
+ * and stores its record as four 16-byte stores: no atomics, no LDS, no scratch.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene or query; with n > 0, NULL points, frames, d_neighbors
+ * (device form), data with m > 0, d_grid (device form); n > 0x7fffffff; m > 0x7fffffff; (host form with a grid) cell not finite or <= 0;
+ * max_dist2 NaN or negative; an unknown flag; k == 0; n * k above 2^37 records; (device form) a pointer not aligned to its element (4
+ * bytes; 8 for d_grid), then d_frames not 16-byte aligned; (device form, n > 0) grid_bytes below cgrt_point_grid_workspace(0).  Then a
+ * host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and touches nothing.  Device form: then d_points, radius2, d_orient, d_neighbors,
+ * d_frames, d_grid and d_data checked as device memory of the scene's device.
+ * Not offered: weighted neighbourhoods; globally consistent orientation (propagation over a graph: orient takes what the caller knows,
+ * a view point or a coarse normal); a per-query k; curvature tensors and higher moments; the k nearest without a bound in one entry
+ * (compose growing radii, as the Python PointGrid.knn_frames does); enqueued-ticket forms (the device form never blocks); the C++ host
+ * mirror. */
+typedef struct CgrtPointFrame {
+    float centroid[3];
+    uint32_t used; /* real neighbour records, 0 .. k; 0: the whole record is zero bytes */
+    float normal[3];
+    float lambda0; /* lambda0 <= lambda1 <= lambda2 */
+    float tangent_u[3];
+    float lambda1;
+    float tangent_v[3];
+    float lambda2;
+} CgrtPointFrame;
+int cgrt_point_frames_device(CgrtScene* scene, const void* d_grid, uint64_t grid_bytes, const float* d_data, uint64_t m, const float* d_points,
+                             uint64_t n, const CgrtPointQuery* query, uint32_t k, const float* d_orient /* NULL or n x 3 */,
+                             CgrtPointNeighbor* d_neighbors /* n * k */, CgrtPointFrame* d_frames /* n */, void* stream);
+int cgrt_point_frames(CgrtScene* scene, const float* data, uint64_t m, float cell, const float* points, uint64_t n, const CgrtPointQuery* query,
+                      uint32_t k, const float* orient, CgrtPointNeighbor* neighbors /* NULL or n * k */, CgrtPointFrame* frames);
+int cgrt_point_frames_brute(CgrtScene* scene, const float* data, uint64_t m, const float* points, uint64_t n, const CgrtPointQuery* query,
+                            uint32_t k, const float* orient, CgrtPointNeighbor* neighbors /* NULL or n * k */, CgrtPointFrame* frames);
+
 /* Iso-surfaces: the way back from a volume to a surface -- the indexed triangle mesh of one level of a scalar
  * grid, by marching tetrahedra (six per cell around the main diagonal: no ambiguous case, closed by construction).  The values are the
  * caller's: what cgrt_signed_distance_grid or cgrt_winding_numbers_grid made (offset and shell surfaces, the 0.5 level of an open mesh's
