@@ -889,7 +889,10 @@ int cgrt_surface_raycams_grad_repro_device(CgrtScene* scene, const CgrtRayCamera
  *               max(S, |p|inf) >= 2^-39    (the square of a residual of one rounding, 2^-24 of the coordinates, stays normal)
  * e.g. a unit-sized mesh with edges of 1/16 and queries within its box: about 2^-24 .. 2^+32. Inside the envelope (a) the accuracy
  * bound holds -- sqrt(dist2) and the distance to the returned triangle are within 5.66 * 2^-24 * max(1, |p|inf, S) of the float64
- * distance (tests/test_closest_cpu.py) -- and (b) multiplying every position and every query by 2^k is an exact symmetry: the same
+ * distance (tests/test_closest_cpu.py: a measurement on well-shaped meshes, not a proof.  It does not hold on slivers: (va+vb)+vc is
+ * |ab x ac|^2 computed from products of dot products, and where that is small against 2^-24 * (E * M)^2 the interior region's quotients
+ * carry no correct digit.  On a triangle with edges of 0.3 and 3e-8, inside this envelope, the defined point was 0.017 from the nearest
+ * one, 5.4e4 times the bound -- tools/fuzz_queries.py, seed 6606, iteration 3; every path returns those bytes) -- and (b) multiplying every position and every query by 2^k is an exact symmetry: the same
  * prim_id and bary bits, point * 2^k, dist2 * 2^2k.  The upper edge is a proof.  The lower one is a margin: a query whose weight towards
  * an edge is non-zero but below 2^-12 can have that va, vb or vc rounded as a subnormal.  Outside the envelope the result is still the
  * defined one, bit for bit, on every path, but can be far from the geometric answer: on a unit cube scaled by 2^33 about 5 % of

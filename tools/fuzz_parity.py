@@ -12,26 +12,7 @@ import __graft_entry__ as e
 pkg = e.load_package(); orc = e.load_oracle()
 import rayfam
 import test_adversarial_gpu as adv
-
-
-def soup(rng):
-    nmesh = rng.randint(1, 30)
-    rows, tris, tm = [], [], []
-    for m in range(nmesh):
-        nt = int(rng.choice([1, 2, 5, 30, 200, 1500, 6000]))
-        c = rng.uniform(-0.8, 0.8, 3); sz = rng.uniform(0.02, 0.5)
-        for _ in range(nt):
-            p0 = c + rng.uniform(-sz, sz, 3)
-            tri = np.stack([p0, p0 + rng.uniform(-0.1, 0.1, 3), p0 + rng.uniform(-0.1, 0.1, 3)])
-            kind = rng.randint(0, 40)
-            if kind == 0: tri[2] = tri[1]
-            elif kind == 1 and tris: tri = np.asarray(rows[-3:])[:, 0:3]
-            elif kind == 2: tri[:, rng.randint(0, 3)] = tri[0, 0]  # axis-aligned
-            base = len(rows); nrm = rng.normal(size=(3, 3))
-            for k in range(3): rows.append(np.concatenate([tri[k], nrm[k] / np.linalg.norm(nrm[k])]))
-            tris.append((base, base + 1, base + 2)); tm.append(m)
-    return pkg.scenes.SceneData(pos_nrm=np.asarray(rows, np.float32), tri=np.asarray(tris, np.uint32), tri_mesh=np.asarray(tm, np.uint32),
-                                materials=rng.uniform(0, 1, (nmesh, 8)).astype(np.float32))
+from fuzz_scenes import soup  # (tools/fuzz_scenes.py: the multi-mesh soup, shared with fuzz_queries.py; the same draws)
 
 
 def same(h, n, ref):
