@@ -51,6 +51,11 @@ POINT_FRAME_DTYPE = np.dtype([("centroid", np.float32, 3), ("used", np.uint32), 
 assert POINT_FRAME_DTYPE.itemsize == 64
 POINTS_SKIP_SAME_INDEX = 1  # include/cgrt.h CGRT_POINTS_SKIP_SAME_INDEX
 ISO_INSIDE_ABOVE = 1  # include/cgrt.h CGRT_ISO_INSIDE_ABOVE
+FIELD_CLAMP = 1  # include/cgrt.h CGRT_FIELD_CLAMP
+MARCH_MISS, MARCH_HIT, MARCH_EXHAUSTED, MARCH_NONFINITE = 0, 1, 2, 3  # include/cgrt.h CGRT_MARCH_*
+# CgrtGridHit as a numpy record
+GRID_HIT_DTYPE = np.dtype([("t", np.float32), ("value", np.float32), ("steps", np.uint32), ("status", np.uint32), ("gradient", np.float32, 3),
+                           ("reserved", np.uint32)])
 _SLOT_RECORDS = {"crossings": CROSSING_DTYPE, "neighbors": NEIGHBOR_DTYPE}  # the slot-list entries (Scene._slots_*) by the name in their symbols
 # Scene.inside_tensor's default directions: three fixed generic ones (no component zero, none along an axis, a face diagonal or a space
 # diagonal, pairwise far from parallel), so that a ray through an edge or a vertex of an axis-aligned or diagonal-symmetric mesh is the
@@ -141,6 +146,43 @@ def _iso_params(iso: float = 0.0, inside_above: bool = False) -> IsoParams:
     """CgrtIsoParams; the library checks iso (finite)."""
     p = IsoParams()
     p.iso, p.flags = float(iso), (ISO_INSIDE_ABOVE if inside_above else 0)
+    return p
+
+
+class FieldParams(C.Structure):
+    """include/cgrt.h CgrtFieldParams."""
+    _fields_ = [("outside", C.c_float), ("flags", C.c_uint32)]
+
+
+class MarchParams(C.Structure):
+    """include/cgrt.h CgrtMarchParams."""
+    _fields_ = [("iso", C.c_float), ("relax", C.c_float), ("min_step", C.c_float), ("hit_eps", C.c_float), ("max_steps", C.c_uint32),
+                ("refine", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class GridHit(C.Structure):
+    """include/cgrt.h CgrtGridHit."""
+    _fields_ = [("t", C.c_float), ("value", C.c_float), ("steps", C.c_uint32), ("status", C.c_uint32), ("gradient", C.c_float * 3),
+                ("reserved", C.c_uint32)]
+
+
+def _field_params(outside=float("nan"), clamp: bool = False) -> FieldParams:
+    """CgrtFieldParams; outside a float or a numpy float32 whose bits are kept as they are."""
+    p = FieldParams()
+    C.memmove(C.byref(p), np.asarray(outside, np.float32).tobytes(), 4)
+    p.flags = FIELD_CLAMP if clamp else 0
+    return p
+
+
+def _march_params(iso: float = 0.0, relax: float = 1.0, min_step: float = 1e-4, hit_eps: float = 1e-4, max_steps: int = 256, refine: int = 0,
+                  inside_above: bool = False) -> MarchParams:
+    """CgrtMarchParams; max_steps and refine 32-bit unsigned values (ValueError otherwise), the library checks the rest."""
+    for name, v in (("max_steps", max_steps), ("refine", refine)):
+        if not 0 <= int(v) < 1 << 32:
+            raise ValueError(f"{name} must be in 0 .. 2^32 - 1")
+    p = MarchParams()
+    p.iso, p.relax, p.min_step, p.hit_eps = float(iso), float(relax), float(min_step), float(hit_eps)
+    p.max_steps, p.refine, p.flags = int(max_steps), int(refine), (ISO_INSIDE_ABOVE if inside_above else 0)
     return p
 
 
@@ -423,7 +465,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_set_frame_order", "cgrt_debug_set_frame_order", "cgrt_debug_get_frame_order", "cgrt_debug_build_frame_order", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_point_grid_workspace", "cgrt_point_grid_build_device", "cgrt_count_point_neighbors", "cgrt_count_point_neighbors_device", "cgrt_list_point_neighbors", "cgrt_list_point_neighbors_device", "cgrt_list_point_neighbors_brute", "cgrt_debug_point_neighbor_work", "cgrt_point_frames", "cgrt_point_frames_device", "cgrt_point_frames_brute", "cgrt_isosurface_workspace", "cgrt_isosurface_count_device", "cgrt_isosurface_device", "cgrt_isosurface", "cgrt_debug_isosurface_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_point_grid_workspace", "cgrt_point_grid_build_device", "cgrt_count_point_neighbors", "cgrt_count_point_neighbors_device", "cgrt_list_point_neighbors", "cgrt_list_point_neighbors_device", "cgrt_list_point_neighbors_brute", "cgrt_debug_point_neighbor_work", "cgrt_point_frames", "cgrt_point_frames_device", "cgrt_point_frames_brute", "cgrt_isosurface_workspace", "cgrt_isosurface_count_device", "cgrt_isosurface_device", "cgrt_isosurface", "cgrt_debug_isosurface_work", "cgrt_sample_grid", "cgrt_sample_grid_device", "cgrt_march_grid", "cgrt_march_grid_device", "cgrt_debug_march_work", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -607,6 +649,12 @@ def lib() -> C.CDLL:
     L.cgrt_isosurface_device.argtypes = [vp, gp, vp, ip, vp, u64, vp, u64, vp, vp, u64, vp]
     L.cgrt_isosurface.argtypes = [vp, gp, vp, ip, vp, u64, vp, u64, vp]
     L.cgrt_debug_isosurface_work.argtypes = [vp, gp, vp, ip, vp]
+    fp, mp = C.POINTER(FieldParams), C.POINTER(MarchParams)
+    L.cgrt_sample_grid.argtypes = [vp, gp, vp, vp, u64, fp, vp, vp, vp]
+    L.cgrt_sample_grid_device.argtypes = [vp, gp, vp, vp, u64, fp, vp, vp, vp, vp]
+    L.cgrt_march_grid.argtypes = [vp, gp, vp, vp, u64, mp, vp]
+    L.cgrt_march_grid_device.argtypes = [vp, gp, vp, vp, u64, mp, vp, vp]
+    L.cgrt_debug_march_work.argtypes = [vp, gp, vp, vp, u64, mp, vp]
     L.cgrt_triangle_areas.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.cgrt_debug_get_sample_table.argtypes = [vp, vp, C.POINTER(u32)]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
@@ -3228,6 +3276,144 @@ class Scene:
         res = self.isosurface_tensor(values, origin, spacing, iso=level, inside_above=True)
         res["values"] = values
         return res
+
+    # ---- grid fields (include/cgrt.h "Grid fields") ----
+    _GRID_WANT = ("value", "gradient", "inside")
+
+    def _grid_want(self, want):
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or len(set(want)) != len(want) or any(w not in self._GRID_WANT for w in want):
+            raise ValueError(f"want must name some of {self._GRID_WANT}, each once")
+        return want
+
+    @staticmethod
+    def _grid_values(values):
+        v = np.ascontiguousarray(np.asarray(values, np.float32))
+        if v.ndim != 3:
+            raise ValueError("values must be shaped (nz, ny, nx)")
+        return v
+
+    def sample_grid(self, values, origin, spacing, points, outside=float("nan"), clamp: bool = False, want=("value", "gradient", "inside")):
+        """cgrt_sample_grid: the trilinear sample of values ((nz, ny, nx) float32 on the grid origin + i * spacing) at every point ((n, 3)
+        float32), as include/cgrt.h defines it to the last bit.  Returns a dict of the arrays named by `want`: 'value' (n,) float32,
+        'gradient' (n, 3) float32 (the derivative of the trilinear polynomial), 'inside' (n,) bool.  A point outside the grid gets
+        (`outside`, 0, False); clamp: the nearest point of the grid's box is sampled instead."""
+        want = self._grid_want(want)
+        v, p = self._grid_values(values), _f32(points, (-1, 3))
+        g, prm = _sdf_grid_struct(origin, spacing, v.shape[::-1]), _field_params(outside, clamp)
+        res = {"value": np.zeros(len(p), np.float32), "gradient": np.zeros((len(p), 3), np.float32), "inside": np.zeros(len(p), np.uint8)}
+        res = {w: res[w] for w in want}
+        _check(lib().cgrt_sample_grid(self._h, C.byref(g), _ptr(v), _ptr(p), len(p), C.byref(prm), _ptr(res.get("value")),
+                                      _ptr(res.get("gradient")), _ptr(res.get("inside"))))
+        if "inside" in res:
+            res["inside"] = res["inside"].view(np.bool_)
+        return res
+
+    def sample_grid_device(self, origin, spacing, dims, d_values_ptr: int, d_points_ptr: int, n: int, d_value_ptr: int, d_gradient_ptr: int,
+                           d_inside_ptr: int, outside=float("nan"), clamp: bool = False, stream: int = 0) -> None:
+        """cgrt_sample_grid_device: nx * ny * nz float32 at d_values_ptr and n points (3 floats each) at d_points_ptr -> n float32 at
+        d_value_ptr, 3 n float32 at d_gradient_ptr, n bytes at d_inside_ptr (0: not wanted), enqueued on the hipStream_t `stream`.  Raw
+        integers."""
+        g, prm = _sdf_grid_struct(origin, spacing, dims), _field_params(outside, clamp)
+        _check(lib().cgrt_sample_grid_device(self._h, C.byref(g), _vp(d_values_ptr), _vp(d_points_ptr), int(n), C.byref(prm), _vp(d_value_ptr),
+                                             _vp(d_gradient_ptr), _vp(d_inside_ptr), _vp(stream)))
+
+    def _grid_values_tensor(self, values):
+        import torch
+
+        self._device_tensor(values, "values", (torch.float32,))
+        if values.dim() != 3:
+            raise ValueError("values must be shaped (nz, ny, nx)")
+        nz, ny, nx = (int(x) for x in values.shape)
+        return (nx, ny, nz)
+
+    def sample_grid_tensor(self, values, origin, spacing, points, outside=float("nan"), clamp: bool = False,
+                           want=("value", "gradient", "inside"), out=None, stream=None):
+        """sample_grid on torch tensors: values (nz, ny, nx) and points (n, 3), contiguous float32 on cuda:<device> -> a dict of the
+        tensors named by `want` ('value' (n,) float32, 'gradient' (n, 3) float32, 'inside' (n,) torch.bool), written into `out` (a dict
+        by name; inside may also be torch.uint8) or new ones, enqueued on `stream` (default: torch.cuda.current_stream())."""
+        import torch
+
+        want = self._grid_want(want)
+        dims = self._grid_values_tensor(values)
+        self._device_tensor(points, "points", (torch.float32,))
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be shaped (n, 3)")
+        n = int(points.shape[0])
+        shapes = {"value": ((n,), (torch.float32,)), "gradient": ((n, 3), (torch.float32,)), "inside": ((n,), (torch.bool, torch.uint8))}
+        if out is not None and (not isinstance(out, dict) or set(out) - set(want)):
+            raise ValueError("out must be a dict of tensors by the names in want")
+        dev, stream = self._torch_stream(stream)
+        _check_one_hip_runtime()
+        res = {}
+        with torch.cuda.stream(stream):
+            for w in want:
+                shape, dtypes = shapes[w]
+                if out is not None and w in out:
+                    t = out[w]
+                    if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype not in dtypes:
+                        raise ValueError(f"out[{w!r}] must be a torch tensor of shape {shape} and one of {dtypes}")
+                    if t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() or (w != "inside" and t.data_ptr() % 4):
+                        raise ValueError(f"out[{w!r}] must be contiguous (4-byte aligned) on cuda:{self.device}")
+                else:
+                    t = torch.empty(shape, dtype=dtypes[0], device=dev)
+                res[w] = t
+        if n:  # (an empty tensor has no address to pass: the call would touch nothing anyway)
+            ptr = {w: (res[w].data_ptr() if w in res else 0) for w in self._GRID_WANT}
+            self.sample_grid_device(origin, spacing, dims, values.data_ptr(), points.data_ptr(), n, ptr["value"], ptr["gradient"], ptr["inside"],
+                                    outside=outside, clamp=clamp, stream=stream.cuda_stream)
+        return res
+
+    def march_grid(self, values, origin, spacing, rays, iso: float = 0.0, relax: float = 1.0, min_step: float = 1e-4, hit_eps: float = 1e-4,
+                   max_steps: int = 256, refine: int = 0, inside_above: bool = False) -> np.ndarray:
+        """cgrt_march_grid: every ray (a RAY_DTYPE array or (n, 7) float32; the direction as given) marched through values ((nz, ny, nx)
+        float32 on the grid origin + i * spacing) to its first sample with value - iso <= hit_eps (inside_above: iso - value), as
+        include/cgrt.h defines it to the last bit.  relax = 1: sphere tracing of a signed distance field; relax = 0: steps of min_step;
+        refine: bisection steps of a hit.  Returns an (n,) GRID_HIT_DTYPE array {t, value, steps, status (MARCH_*), gradient}."""
+        v, r = self._grid_values(values), _as_ray_array(rays)
+        g, prm = _sdf_grid_struct(origin, spacing, v.shape[::-1]), _march_params(iso, relax, min_step, hit_eps, max_steps, refine, inside_above)
+        hits = np.zeros(len(r), GRID_HIT_DTYPE)
+        _check(lib().cgrt_march_grid(self._h, C.byref(g), _ptr(v), _ptr(r), len(r), C.byref(prm), _ptr(hits)))
+        return hits
+
+    def march_grid_device(self, origin, spacing, dims, d_values_ptr: int, d_rays_ptr: int, n: int, d_hits_ptr: int, iso: float = 0.0,
+                          relax: float = 1.0, min_step: float = 1e-4, hit_eps: float = 1e-4, max_steps: int = 256, refine: int = 0,
+                          inside_above: bool = False, stream: int = 0) -> None:
+        """cgrt_march_grid_device: nx * ny * nz float32 at d_values_ptr and n rays (7 floats each) at d_rays_ptr -> n records of 32
+        bytes (CgrtGridHit) at d_hits_ptr, enqueued on the hipStream_t `stream`.  Raw integers."""
+        g, prm = _sdf_grid_struct(origin, spacing, dims), _march_params(iso, relax, min_step, hit_eps, max_steps, refine, inside_above)
+        _check(lib().cgrt_march_grid_device(self._h, C.byref(g), _vp(d_values_ptr), _vp(d_rays_ptr), int(n), C.byref(prm), _vp(d_hits_ptr),
+                                            _vp(stream)))
+
+    def march_grid_tensor(self, values, origin, spacing, rays, out=None, stream=None, **march):
+        """march_grid on torch tensors: values (nz, ny, nx) and rays (n, 7), contiguous float32 on cuda:<device>; `march`: march_grid's
+        parameters.  Returns views over ONE (n, 8) float32 tensor of records (`out`, or a new one; also returned as 'records'): 't' (n,)
+        float32, 'value' (n,) float32, 'steps' (n,) int32, 'status' (n,) int32, 'gradient' (n, 3) float32.  Enqueued on `stream`
+        (default: torch.cuda.current_stream())."""
+        import torch
+
+        dims = self._grid_values_tensor(values)
+        self._device_tensor(rays, "rays", (torch.float32,))
+        if rays.dim() != 2 or rays.shape[1] != 7:
+            raise ValueError("rays must be shaped (n, 7)")
+        n = int(rays.shape[0])
+        if out is not None:
+            self._device_tensor(out, "out", (torch.float32,), (n, 8))
+        rec = self._tensor_call(out, (n, 8), torch.float32, stream,
+                                lambda o, s: self.march_grid_device(origin, spacing, dims, values.data_ptr(), rays.data_ptr(), n, o.data_ptr(),
+                                                                    stream=s, **march))
+        words = rec.view(torch.int32)
+        return {"records": rec, "t": rec[:, 0], "value": rec[:, 1], "steps": words[:, 2], "status": words[:, 3], "gradient": rec[:, 4:7]}
+
+    def debug_march_work(self, values, origin, spacing, rays, iso: float = 0.0, relax: float = 1.0, min_step: float = 1e-4,
+                         hit_eps: float = 1e-4, max_steps: int = 256, refine: int = 0, inside_above: bool = False):
+        """cgrt_debug_march_work: (rays that entered the grid's box, main-loop samples, refinement samples) of march_grid, summed over
+        the rays (a separate counting launch)."""
+        v, r = self._grid_values(values), _as_ray_array(rays)
+        g, prm = _sdf_grid_struct(origin, spacing, v.shape[::-1]), _march_params(iso, relax, min_step, hit_eps, max_steps, refine, inside_above)
+        w = np.zeros(3, np.uint64)
+        _check(lib().cgrt_debug_march_work(self._h, C.byref(g), _ptr(v), _ptr(r), len(r), C.byref(prm), _ptr(w)))
+        return tuple(int(x) for x in w)
 
     def _surface_frames_tensor(self, raycams, cams, W, H, depth, prim_id, attr, want_bary, chw, out, stream, reproducible=False):
         import torch

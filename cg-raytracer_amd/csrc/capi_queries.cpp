@@ -1,5 +1,5 @@
 // capi_queries.cpp -- the C-ABI's queries on a built scene (include/cgrt.h): visibility, surface attributes and their gradients,
-// closest points, crossings, neighbours, signed distance, winding numbers, surface samples, Poisson-disk sets, point-set neighbours, point-set frames, iso-surfaces.  None of them touches the scene's frame state (workspace, prediction, hints).
+// closest points, crossings, neighbours, signed distance, winding numbers, surface samples, Poisson-disk sets, point-set neighbours, point-set frames, iso-surfaces, grid fields.  None of them touches the scene's frame state (workspace, prediction, hints).
 // Every family is ONE body for its host-pointer and its device-pointer entries, written with a QueryCall (capi_internal.h): the argument
 // checks in the order include/cgrt.h states (`device`: the pointers' alignment too), the host-only scene, the empty call, then begin,
 // in / out per array, the launch on the call's stream, finish.  The exported entries are one-line forwarders.
@@ -1400,6 +1400,135 @@ int cgrt_isosurface(CgrtScene* s, const CgrtGrid* grid, const float* values, con
 }
 int cgrt_debug_isosurface_work(CgrtScene* s, const CgrtGrid* grid, const float* values, const CgrtIsoParams* params, uint64_t* out4) {
     return iso_query(s, false, grid, values, params, {false, nullptr, 0, nullptr, 0}, nullptr, nullptr, true, out4, nullptr);
+}
+
+// ---- grid fields (include/cgrt.h "Grid fields"): the trilinear sample of a scalar grid with its gradient, and the
+// march of rays to a level of it.  The scene only names the device and lends the call lane; no frame state is read or written; the checks
+// come in the order include/cgrt.h states, all before any device work.
+namespace {
+static_assert(sizeof(CgrtGridHit) == 32 && sizeof(CgrtMarchParams) == 28 && sizeof(CgrtFieldParams) == 8, "the records of include/cgrt.h");
+static_assert(CGRT_FIELD_CLAMP == kFieldClamp && CGRT_ISO_INSIDE_ABOVE == kMarchInsideAbove && CGRT_MARCH_MISS == kMarchMiss &&
+                  CGRT_MARCH_HIT == kMarchHit && CGRT_MARCH_EXHAUSTED == kMarchExhausted && CGRT_MARCH_NONFINITE == kMarchNonfinite,
+              "the kernels' constants are the header's");
+int field_grid(const CgrtGrid* grid, GridField* G, uint64_t* points) {
+    uint64_t n = 1;
+    for (int c = 0; c < 3; c++) {
+        if (grid->dims[c] < 2 || grid->dims[c] > (1u << 24)) return fail(CGRT_E_ARG, "grid dims must be in 2..2^24");
+        n *= grid->dims[c];  // (below 2^55 before the test, which follows every factor)
+        if (n > kFieldMaxPoints) return fail(CGRT_E_ARG, "too many grid points: nx * ny * nz exceeds 0x7fffffff");
+        if (!std::isfinite(grid->origin[c]) || !std::isfinite(grid->spacing[c])) return fail(CGRT_E_ARG, "grid origin and spacing must be finite");
+        if (grid->spacing[c] == 0.0f) return fail(CGRT_E_ARG, "grid spacing must not be zero");
+        G->origin[c] = grid->origin[c];
+        G->spacing[c] = grid->spacing[c];
+        G->top[c] = (float)(grid->dims[c] - 1u);
+    }
+    G->nx = grid->dims[0], G->ny = grid->dims[1], G->nz = grid->dims[2];
+    *points = n;
+    return CGRT_OK;
+}
+// slots: 0 the values, 1 the points, 2 value, 3 gradient, 4 inside
+int field_sample_query(CgrtScene* s, bool device, const CgrtGrid* grid, const float* values, const float* points, uint64_t n,
+                       const CgrtFieldParams* params, float* value, float* gradient, uint8_t* inside, void* stream) {
+    if (!s || !grid) return fail(CGRT_E_ARG, "scene or grid is NULL");
+    FieldSampleCall Q{};
+    uint64_t N = 0;
+    CGRT_TRY(field_grid(grid, &Q.grid, &N));
+    if (params && (params->flags & ~(uint32_t)CGRT_FIELD_CLAMP)) return fail(CGRT_E_ARG, "unknown flags");
+    if (!values) return fail(CGRT_E_ARG, "NULL argument: values");
+    if (n && !points) return fail(CGRT_E_ARG, "NULL argument: points");
+    if (!value && !gradient && !inside) return fail(CGRT_E_ARG, "NULL argument: none of value, gradient and inside is asked for");
+    if (n > kFieldMaxPoints) return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
+    if (device && ((uintptr_t)values % 4 || (uintptr_t)points % 4 || (uintptr_t)value % 4 || (uintptr_t)gradient % 4))
+        return fail(CGRT_E_ARG, "d_values, d_points, d_value and d_gradient must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    Q.outside_bits = kCanonicalNan;
+    if (params) memcpy(&Q.outside_bits, &params->outside, 4);
+    Q.clamp = params && (params->flags & CGRT_FIELD_CLAMP) ? 1u : 0u;
+    Q.n = (uint32_t)n;
+    QueryCall c(s, device, stream);
+    void *dv = nullptr, *dp = nullptr, *dval = nullptr, *dg = nullptr, *di = nullptr;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, values, N * 4, "d_values", &dv));
+    CGRT_TRY(c.in(1, points, n * 12, "d_points", &dp));
+    CGRT_TRY(c.out(2, value, value ? n * 4 : 0, "d_value", &dval));
+    CGRT_TRY(c.out(3, gradient, gradient ? n * 12 : 0, "d_gradient", &dg));
+    CGRT_TRY(c.out(4, inside, inside ? n : 0, "d_inside", &di));
+    Q.grid.values = static_cast<const float*>(dv);
+    Q.points = static_cast<const float*>(dp);
+    Q.value = static_cast<float*>(dval);
+    Q.gradient = static_cast<float*>(dg);
+    Q.inside = static_cast<uint8_t*>(di);
+    HIP_TRY(launch_sample_grid(Q, c.stream()));
+    return c.finish();
+}
+// slots: 0 the values, 1 the rays, 2 the records; work: the counting launch (host form only: out3 in the place of hits)
+int field_march_query(CgrtScene* s, bool device, const CgrtGrid* grid, const float* values, const CgrtRay* rays, uint64_t n,
+                      const CgrtMarchParams* params, CgrtGridHit* hits, bool counted, uint64_t* work, void* stream) {
+    if (!s || !grid) return fail(CGRT_E_ARG, "scene or grid is NULL");
+    FieldMarchCall Q{};
+    uint64_t N = 0;
+    CGRT_TRY(field_grid(grid, &Q.grid, &N));
+    if (!params) return fail(CGRT_E_ARG, "NULL argument: params");
+    if (!std::isfinite(params->iso)) return fail(CGRT_E_ARG, "iso must be finite");
+    if (!std::isfinite(params->relax) || !(params->relax >= 0.0f)) return fail(CGRT_E_ARG, "relax must be finite and >= 0");
+    if (!std::isfinite(params->min_step) || !(params->min_step > 0.0f)) return fail(CGRT_E_ARG, "min_step must be finite and > 0");
+    if (!std::isfinite(params->hit_eps) || !(params->hit_eps >= 0.0f)) return fail(CGRT_E_ARG, "hit_eps must be finite and >= 0");
+    if (params->max_steps < 1 || params->max_steps > 65536) return fail(CGRT_E_ARG, "max_steps must be in 1..65536");
+    if (params->refine > 32) return fail(CGRT_E_ARG, "refine must be in 0..32");
+    if (params->flags & ~(uint32_t)CGRT_ISO_INSIDE_ABOVE) return fail(CGRT_E_ARG, "unknown flags");
+    if (!values) return fail(CGRT_E_ARG, "NULL argument: values");
+    if (n && !rays) return fail(CGRT_E_ARG, "NULL argument: rays");
+    if (counted ? !work : !hits) return fail(CGRT_E_ARG, counted ? "NULL argument: out3" : "NULL argument: hits");
+    if (n > kFieldMaxPoints) return fail(CGRT_E_ARG, "too many rays: n exceeds 0x7fffffff");
+    if (device && ((uintptr_t)values % 4 || (uintptr_t)rays % 4 || (uintptr_t)hits % 4))
+        return fail(CGRT_E_ARG, "d_values, d_rays and d_hits must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0) {
+        if (counted) work[0] = work[1] = work[2] = 0;
+        return CGRT_OK;
+    }
+    Q.rules = {params->iso, params->relax, params->min_step, params->hit_eps, params->max_steps, params->refine,
+               (params->flags & CGRT_ISO_INSIDE_ABOVE) ? 1u : 0u};
+    Q.n = (uint32_t)n;
+    QueryCall c(s, device, stream);
+    void *dv = nullptr, *dr = nullptr, *dh = nullptr;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, values, N * 4, "d_values", &dv));
+    CGRT_TRY(c.in(1, rays, n * sizeof(CgrtRay), "d_rays", &dr));
+    Q.grid.values = static_cast<const float*>(dv);
+    Q.rays = static_cast<const float*>(dr);
+    if (counted) {
+        CGRT_TRY(c.zero_counters(3));
+        HIP_TRY(launch_march_grid(Q, c.counters(), c.stream()));
+        return c.read_counters(work, 3);
+    }
+    CGRT_TRY(c.out(2, hits, n * sizeof(CgrtGridHit), "d_hits", &dh));
+    Q.hits = static_cast<uint32_t*>(dh);
+    HIP_TRY(launch_march_grid(Q, nullptr, c.stream()));
+    return c.finish();
+}
+}  // namespace
+
+int cgrt_sample_grid(CgrtScene* s, const CgrtGrid* grid, const float* values, const float* points, uint64_t n, const CgrtFieldParams* params,
+                     float* value, float* gradient, uint8_t* inside) {
+    return field_sample_query(s, false, grid, values, points, n, params, value, gradient, inside, nullptr);
+}
+int cgrt_sample_grid_device(CgrtScene* s, const CgrtGrid* grid, const float* d_values, const float* d_points, uint64_t n,
+                            const CgrtFieldParams* params, float* d_value, float* d_gradient, uint8_t* d_inside, void* stream) {
+    return field_sample_query(s, true, grid, d_values, d_points, n, params, d_value, d_gradient, d_inside, stream);
+}
+int cgrt_march_grid(CgrtScene* s, const CgrtGrid* grid, const float* values, const CgrtRay* rays, uint64_t n, const CgrtMarchParams* params,
+                    CgrtGridHit* hits) {
+    return field_march_query(s, false, grid, values, rays, n, params, hits, false, nullptr, nullptr);
+}
+int cgrt_march_grid_device(CgrtScene* s, const CgrtGrid* grid, const float* d_values, const CgrtRay* d_rays, uint64_t n,
+                           const CgrtMarchParams* params, CgrtGridHit* d_hits, void* stream) {
+    return field_march_query(s, true, grid, d_values, d_rays, n, params, d_hits, false, nullptr, stream);
+}
+int cgrt_debug_march_work(CgrtScene* s, const CgrtGrid* grid, const float* values, const CgrtRay* rays, uint64_t n, const CgrtMarchParams* params,
+                          uint64_t* out3) {
+    return field_march_query(s, false, grid, values, rays, n, params, nullptr, true, out3, nullptr);
 }
 
 }  // extern "C"

@@ -1636,6 +1636,117 @@ int cgrt_isosurface(CgrtScene* scene, const CgrtGrid* grid, const float* values,
                     uint64_t vert_capacity, uint32_t* tris, uint64_t tri_capacity, uint64_t* counts2);
 int cgrt_debug_isosurface_work(CgrtScene* scene, const CgrtGrid* grid, const float* values, const CgrtIsoParams* params, uint64_t* out4);
 
+/* Grid fields: the two questions a volume is asked -- "what is the field, and its gradient, at this point?" and
+ * "where does this ray first reach the level?" -- for the grids cgrt_signed_distance_grid and cgrt_winding_numbers_grid make and
+ * cgrt_isosurface reads, or anyone's.  Both answers are defined to the last bit: pure functions of (grid, values, points or rays,
+ * params), whatever the launch shape, the stream, the thread or the run.  The scene names the device and lends its call lanes; its
+ * geometry is not read.  All f32 arithmetic is IEEE, every operation rounded on its own, nothing contracted; division and sqrt are
+ * correctly rounded; every NaN the library computes is stored as 0x7fc00000.  Below, min(a, b) is a < b ? a : b and max(a, b) is
+ * a > b ? a : b (a NaN first operand yields the second).
+ * Grid and values.  grid: a CgrtGrid.  values: nx ny nz f32 in the result order of cgrt_signed_distance_grid, index (iz ny + iy) nx + ix.
+ * Limits.  Each dim in 2..2^24; nx ny nz <= 0x7fffffff; origin and spacing finite; every spacing non-zero (a negative one is allowed: the
+ * axis runs backwards).  Anything else: CGRT_E_ARG.
+ * Sample of a point p.  params: CgrtFieldParams {outside, flags}, flags 0 or CGRT_FIELD_CLAMP; NULL means {NaN, 0}.
+ *   Per axis c: u_c = fl(fl(p.c - origin.c) / spacing.c), top_c = (float)(n_c - 1).  With CGRT_FIELD_CLAMP u_c is first replaced by
+ *   u_c < 0 ? 0 : (u_c > top_c ? top_c : u_c), which leaves a NaN a NaN.  p is inside iff 0 <= u_c && u_c <= top_c on all three axes
+ *   (false for a NaN): under CGRT_FIELD_CLAMP only a point with a NaN u_c is outside.
+ *   Outside: value = params.outside (its bits as given, a NaN's payload included), gradient = 0, inside = 0.
+ *   Inside: i_c = min((int)floor(u_c), n_c - 2), f_c = fl(u_c - (float)i_c), which is exact and lies in [0, 1] (1 only on the last plane).
+ *   The corners are v_xyz = values at (i_x + x, i_y + y, i_z + z).  lerp(a, b, f) = fl(a + fl(f fl(b - a))), the form of the iso-surface's
+ *   vertex.  Along x: d_yz = fl(v_1yz - v_0yz), a_yz = fl(v_0yz + fl(f_x d_yz)).  Along y: e_z = fl(a_1z - a_0z), b_z = fl(a_0z + fl(f_y e_z)).
+ *   Along z: w = fl(b_1 - b_0), value = fl(b_0 + fl(f_z w)).  The gradient is the derivative of that polynomial from the same differences:
+ *   g_z = fl(w / spacing.z); g_y = fl(lerp(e_0, e_1, f_z) / spacing.y); g_x = fl(lerp(lerp(d_00, d_10, f_y), lerp(d_01, d_11, f_y), f_z)
+ *   / spacing.x).  inside = 1.  A cell with a non-finite corner gives whatever IEEE gives (with the NaNs canonical).
+ * Properties.  (a) Where f = 0 on all axes, value is the stored grid value's bits for finite corners: every product is a zero and every
+ *   sum a + (+-0) (the one exception: a stored -0 may come back as +0; differences that overflow are not finite corners' business either).  On the last plane of an axis f = 1 and the
+ *   value along it is fl(a + fl(b - a)), which need NOT be b: the difference rounds.  (b) A field that is affine in the position, with
+ *   exactly representable data (every difference, product and sum above exact), is reproduced exactly, value and gradient alike.
+ *   (c) Against float64 trilinear interpolation T64 at the same (i, f): |value - T64| <= 16 * 2^-24 * M, M the largest |corner|, for finite
+ *   corners whose differences do not overflow.  Derivation, u = 2^-24: one lerp of inputs bounded by m rounds three times -- the
+ *   difference (|b - a| <= 2m, error <= 2mu, times f <= 1), the product (<= 2mu), the sum (its exact value is a convex combination, so
+ *   <= mu): 5mu to first order.  A lerp passes errors of its inputs on without growth (convex weights), its output stays within
+ *   m (1 + 5u), and the three stages add: 15 M u + O(u^2); the second-order terms are below M u.  Hence C = 16.  (d) Both power-of-two
+ *   scale symmetries hold.  Every intermediate is LINEAR in the values, and u, f depend on positions alone: multiplying the values by 2^k
+ *   multiplies value and gradient by 2^k exactly while every non-zero one of the corners, d, f d, a, e, f e, b, w, f w, the value, the
+ *   gradient's lerps and quotients times 2^k stays a normal float; multiplying origin, spacing and the points by 2^k leaves u, i, f and the
+ *   value alone and multiplies the gradient by 2^-k exactly while every non-zero one of p.c, origin.c, p.c - origin.c, spacing.c and the
+ *   gradient's quotients stays normal under the scale.  Outside the envelope the bytes are still the defined ones; only the relation to
+ *   scale 1 is lost.
+ * March of a ray.  A ray is the 7-float record {o, d, t_ray} (CgrtRay); d is taken as given and may be unnormalised.  params:
+ *   CgrtMarchParams, 28 bytes, not NULL: iso finite; relax finite and >= 0; min_step finite and > 0; hit_eps finite and >= 0; max_steps in
+ *   1..65536; refine in 0..32; flags 0 or CGRT_ISO_INSIDE_ABOVE.  A ray takes at most max_steps + refine samples by construction, which is
+ *   what the caps are for: there is no unbounded mode.
+ *   1. len = fl(sqrt(fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)))).  A ray is rejected -- a MISS with steps 0 -- if a component of o or d
+ *      is not finite, if t_ray is a NaN, if !(len > 0), or if len is infinite.
+ *   2. Box.  far_c = fl(origin.c + fl(top_c spacing.c)); lo_c = min(origin.c, far_c), hi_c = max(origin.c, far_c).  t0 = 0, t1 = t_ray.
+ *      Per axis in x, y, z order: if d.c == 0 the ray is a MISS (steps 0) unless lo_c <= o.c && o.c <= hi_c; otherwise
+ *      ta = fl(fl(lo_c - o.c) / d.c), tb = fl(fl(hi_c - o.c) / d.c), t0 = max(t0, min(ta, tb)), t1 = min(t1, max(ta, tb)).  MISS (steps 0)
+ *      if !(t0 <= t1).
+ *   3. t = t0, k = 0, no previous t.
+ *   4. Sample: p.c = fl(o.c + fl(t d.c)); v = the sample at p under CGRT_FIELD_CLAMP with outside = NaN; g = fl(v - iso), with
+ *      CGRT_ISO_INSIDE_ABOVE g = fl(iso - v).
+ *   5. g a NaN: NONFINITE at t, steps = k.   6. g <= hit_eps: HIT (below).   7. Else t >= t1: MISS, steps = k.
+ *   8. Else k + 1 == max_steps: EXHAUSTED at t, steps = max_steps.
+ *   9. Else dt = max(fl(fl(relax g) / len), min_step); t_prev = t; t = min(fl(t + dt), t1); k += 1; back to 4.
+ *   Hit.  ta = t_prev, tb = t.  Without a previous t (the first sample hit) no refinement runs.  Otherwise, `refine` times:
+ *   tm = fl(ta + fl(0.5 fl(tb - ta))); gm as in 4 at tm; gm <= hit_eps sets tb = tm, anything else (a NaN too) ta = tm.  The record is
+ *   t = tb, the field value v at tb, the sampler's gradient at p(tb) -- the field's own, not negated under CGRT_ISO_INSIDE_ABOVE --
+ *   and steps = k.
+ *   relax = 1 is sphere tracing of a signed distance field; relax = 0 a fixed-step march of any field (the 0.5 level of a winding grid
+ *   with CGRT_ISO_INSIDE_ABOVE); refine makes either precise.
+ * Record.  CgrtGridHit, 32 bytes {t, value, steps, status, gradient[3], reserved = 0}.  MISS: t = +inf, value 0, gradient 0.  EXHAUSTED: the
+ *   last t and its v, gradient 0.  NONFINITE: t, value NaN, gradient 0.
+ * Entries.  Sampling: value (n f32), gradient (3n f32), inside (n u8); any of the three may be NULL, not all.  Marching: hits, n records.
+ * cgrt_debug_march_work (host form, a counting launch of its own, no record written): out3 = {rays that entered the box (passed step 2),
+ * main-loop samples (step 4), refinement samples}; the closing evaluation of a HIT's gradient is not counted; n == 0 gives zeros.
+ * The host forms (host pointers) run on a call lane like cgrt_isosurface and block: any number of threads may call at once.  The device
+ * forms only enqueue on `stream` (NULL = default stream) and read nothing back.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene or grid; the grid's limits; bad params (sampling: an
+ * unknown flag; marching: NULL, then its fields in the order above); NULL values; NULL points or rays with n > 0; every output NULL (hits;
+ * out3); n > 0x7fffffff; (device forms) a pointer not 4-byte aligned (d_inside: any).  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0
+ * succeeds and touches nothing.  Device forms: then d_values (4 bytes per grid point), d_points (12 n) or d_rays (28 n) and each output
+ * given (4 n, 12 n, n; 32 n) checked as device memory of the scene's device.  Nothing outside the n records is written.  No form reads or
+ * writes the prediction record, the frame hints, the layout or any frame state.
+ * Not offered: tricubic or tetrahedral interpolation (the iso-surface's piecewise-linear field); gradients with respect to the values
+ * (autograd); vector-valued or batched grids; wrap or reflect padding; a bricked or narrow-band value layout; empty-space skipping; frame,
+ * AOV and enqueued-ticket forms; shading of marched hits through the render wavefront; the C++ host mirror. */
+#define CGRT_FIELD_CLAMP 1u
+#define CGRT_MARCH_MISS 0u
+#define CGRT_MARCH_HIT 1u
+#define CGRT_MARCH_EXHAUSTED 2u
+#define CGRT_MARCH_NONFINITE 3u
+typedef struct CgrtFieldParams {
+    float outside;  /* the value of a point outside the grid, stored as given */
+    uint32_t flags; /* 0, or CGRT_FIELD_CLAMP */
+} CgrtFieldParams;
+typedef struct CgrtMarchParams {
+    float iso;          /* the level; finite */
+    float relax;        /* step = relax * g / |d|; finite, >= 0 */
+    float min_step;     /* the smallest step in t; finite, > 0 */
+    float hit_eps;      /* a sample with g <= hit_eps hits; finite, >= 0 */
+    uint32_t max_steps; /* main-loop samples per ray, 1..65536 */
+    uint32_t refine;    /* bisection samples of a hit, 0..32 */
+    uint32_t flags;     /* 0, or CGRT_ISO_INSIDE_ABOVE */
+} CgrtMarchParams;
+typedef struct CgrtGridHit {
+    float t;
+    float value;
+    uint32_t steps;
+    uint32_t status; /* CGRT_MARCH_* */
+    float gradient[3];
+    uint32_t reserved; /* 0 */
+} CgrtGridHit;
+int cgrt_sample_grid(CgrtScene* scene, const CgrtGrid* grid, const float* values, const float* points, uint64_t n, const CgrtFieldParams* params,
+                     float* value, float* gradient, uint8_t* inside);
+int cgrt_sample_grid_device(CgrtScene* scene, const CgrtGrid* grid, const float* d_values, const float* d_points, uint64_t n,
+                            const CgrtFieldParams* params, float* d_value, float* d_gradient, uint8_t* d_inside, void* stream);
+int cgrt_march_grid(CgrtScene* scene, const CgrtGrid* grid, const float* values, const CgrtRay* rays, uint64_t n, const CgrtMarchParams* params,
+                    CgrtGridHit* hits);
+int cgrt_march_grid_device(CgrtScene* scene, const CgrtGrid* grid, const float* d_values, const CgrtRay* d_rays, uint64_t n,
+                           const CgrtMarchParams* params, CgrtGridHit* d_hits, void* stream);
+int cgrt_debug_march_work(CgrtScene* scene, const CgrtGrid* grid, const float* values, const CgrtRay* rays, uint64_t n,
+                          const CgrtMarchParams* params, uint64_t* out3);
+
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
  * The queries neither read nor write the scene's frame prediction or frame hints.  The host forms (host pointers, synchronous) run on a
