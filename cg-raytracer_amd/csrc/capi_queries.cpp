@@ -1508,6 +1508,39 @@ int field_march_query(CgrtScene* s, bool device, const CgrtGrid* grid, const flo
     HIP_TRY(launch_march_grid(Q, nullptr, c.stream()));
     return c.finish();
 }
+// the sampler's adjoint (include/cgrt.h "Grid fields, the adjoint").  slots: 0 the points, 1 grad_value,
+// 2 grad_gradient, 3 grad_values (host form: uploaded, added into, downloaded)
+int field_grad_query(CgrtScene* s, bool device, const CgrtGrid* grid, const float* points, uint64_t n, const CgrtFieldParams* params,
+                     const float* grad_value, const float* grad_gradient, float* grad_values, void* stream) {
+    if (!s || !grid) return fail(CGRT_E_ARG, "scene or grid is NULL");
+    FieldGradCall Q{};
+    uint64_t N = 0;
+    CGRT_TRY(field_grid(grid, &Q.grid, &N));
+    if (params && (params->flags & ~(uint32_t)CGRT_FIELD_CLAMP)) return fail(CGRT_E_ARG, "unknown flags");
+    if (n && !points) return fail(CGRT_E_ARG, "NULL argument: points");
+    if (!grad_value && !grad_gradient) return fail(CGRT_E_ARG, "NULL argument: neither grad_value nor grad_gradient is given");
+    if (!grad_values) return fail(CGRT_E_ARG, "NULL argument: grad_values");
+    if (n > kFieldMaxPoints) return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
+    if (device && ((uintptr_t)points % 4 || (uintptr_t)grad_value % 4 || (uintptr_t)grad_gradient % 4 || (uintptr_t)grad_values % 4))
+        return fail(CGRT_E_ARG, "d_points, d_grad_value, d_grad_gradient and d_grad_values must be 4-byte aligned");
+    NEED_DEVICE(s);
+    if (n == 0) return CGRT_OK;
+    Q.clamp = params && (params->flags & CGRT_FIELD_CLAMP) ? 1u : 0u;
+    Q.n = (uint32_t)n;
+    QueryCall c(s, device, stream);
+    void *dp = nullptr, *dgv = nullptr, *dgg = nullptr, *dout = nullptr;
+    CGRT_TRY(c.begin());
+    CGRT_TRY(c.in(0, points, n * 12, "d_points", &dp));
+    CGRT_TRY(c.in(1, grad_value, grad_value ? n * 4 : 0, "d_grad_value", &dgv));
+    CGRT_TRY(c.in(2, grad_gradient, grad_gradient ? n * 12 : 0, "d_grad_gradient", &dgg));
+    CGRT_TRY(c.inout(3, grad_values, N * 4, "d_grad_values", &dout));
+    Q.points = static_cast<const float*>(dp);
+    Q.grad_value = grad_value ? static_cast<const float*>(dgv) : nullptr;
+    Q.grad_gradient = grad_gradient ? static_cast<const float*>(dgg) : nullptr;
+    Q.grad_values = static_cast<float*>(dout);
+    HIP_TRY(launch_sample_grid_grad(Q, c.stream()));
+    return c.finish();
+}
 }  // namespace
 
 int cgrt_sample_grid(CgrtScene* s, const CgrtGrid* grid, const float* values, const float* points, uint64_t n, const CgrtFieldParams* params,
@@ -1517,6 +1550,14 @@ int cgrt_sample_grid(CgrtScene* s, const CgrtGrid* grid, const float* values, co
 int cgrt_sample_grid_device(CgrtScene* s, const CgrtGrid* grid, const float* d_values, const float* d_points, uint64_t n,
                             const CgrtFieldParams* params, float* d_value, float* d_gradient, uint8_t* d_inside, void* stream) {
     return field_sample_query(s, true, grid, d_values, d_points, n, params, d_value, d_gradient, d_inside, stream);
+}
+int cgrt_sample_grid_grad(CgrtScene* s, const CgrtGrid* grid, const float* points, uint64_t n, const CgrtFieldParams* params,
+                          const float* grad_value, const float* grad_gradient, float* grad_values) {
+    return field_grad_query(s, false, grid, points, n, params, grad_value, grad_gradient, grad_values, nullptr);
+}
+int cgrt_sample_grid_grad_device(CgrtScene* s, const CgrtGrid* grid, const float* d_points, uint64_t n, const CgrtFieldParams* params,
+                                 const float* d_grad_value, const float* d_grad_gradient, float* d_grad_values, void* stream) {
+    return field_grad_query(s, true, grid, d_points, n, params, d_grad_value, d_grad_gradient, d_grad_values, stream);
 }
 int cgrt_march_grid(CgrtScene* s, const CgrtGrid* grid, const float* values, const CgrtRay* rays, uint64_t n, const CgrtMarchParams* params,
                     CgrtGridHit* hits) {

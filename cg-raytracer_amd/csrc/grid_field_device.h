@@ -2,6 +2,8 @@
 // and the march of one ray to a level of it.  f32 throughout, every operation rounded on its own (-ffp-contract=off), only + - x / sqrt,
 // floor and comparisons: the numpy restatement (tests/grid_field_ref.py) gives the same bits.  Written __host__ __device__: both kernels of
 // grid_field_kernels.hip and the stand-alone checker (tools/grid_field_check.cpp, a C++ compiler that is not hipcc) share these bodies.
+// field_cell and field_adjoint are the sampler's adjoint (tests/grid_field_grad_ref.py), shared by
+// k_sample_grid_grad and tools/grid_field_grad_check.cpp in the same way.
 // min and max are the header's: a < b ? a : b and a > b ? a : b, so a NaN first operand yields the second.
 #pragma once
 #include <math.h>
@@ -86,6 +88,50 @@ CGRT_HD bool field_sample(const GridField& G, const float px, const float py, co
         g[2] = w / G.spacing[2];
     }
     return true;
+}
+
+// The cell of p under the sampler's rule, with the sampler's bits (the dozen lines of field_sample above, which keeps its own copy so
+// that its kernels keep their registers).  false: p is outside and i, f are not written.
+CGRT_HD bool field_cell(const GridField& G, const float px, const float py, const float pz, const bool clamp, int (&i)[3], float (&f)[3]) {
+    float u[3] = {(px - G.origin[0]) / G.spacing[0], (py - G.origin[1]) / G.spacing[1], (pz - G.origin[2]) / G.spacing[2]};
+    if (clamp) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int c = 0; c < 3; c++) u[c] = u[c] < 0.0f ? 0.0f : (u[c] > G.top[c] ? G.top[c] : u[c]);
+    }
+    if (!(0.0f <= u[0] && u[0] <= G.top[0] && 0.0f <= u[1] && u[1] <= G.top[1] && 0.0f <= u[2] && u[2] <= G.top[2])) return false;
+    const int fx = (int)floorf(u[0]), fy = (int)floorf(u[1]), fz = (int)floorf(u[2]);
+    const int mx = (int)G.nx - 2, my = (int)G.ny - 2, mz = (int)G.nz - 2;
+    i[0] = fx < mx ? fx : mx, i[1] = fy < my ? fy : my, i[2] = fz < mz ? fz : mz;
+    f[0] = u[0] - (float)i[0], f[1] = u[1] - (float)i[1], f[2] = u[2] - (float)i[2];
+    return true;
+}
+
+// The eight contributions of an inside point to the values' gradient (include/cgrt.h "Grid fields, the adjoint"),
+// c[x + 2 y + 4 z] for the corner (i_x + x, i_y + y, i_z + z).  gv / gg are read only where has_gv / has_gg say they were given; the terms of
+// an input that was not given are left out of the sum.  Every loop has constant bounds: unrolled, no array is indexed at run time.
+CGRT_HD void field_adjoint(const float (&spacing)[3], const float (&f)[3], const bool has_gv, const float gv, const bool has_gg,
+                           const float (&gg)[3], float (&c)[8]) {
+    const float wx[2] = {1.0f - f[0], f[0]}, wy[2] = {1.0f - f[1], f[1]}, wz[2] = {1.0f - f[2], f[2]};
+    float q[3] = {0.0f, 0.0f, 0.0f};
+    if (has_gg) q[0] = gg[0] / spacing[0], q[1] = gg[1] / spacing[1], q[2] = gg[2] / spacing[2];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 8; k++) {
+        const int x = k & 1, y = (k >> 1) & 1, z = k >> 2;
+        const float wxy = wx[x] * wy[y];
+        float s = 0.0f;
+        if (has_gv) s = gv * (wxy * wz[z]);
+        if (has_gg) {
+            const float tx = (x ? q[0] : -q[0]) * (wy[y] * wz[z]);
+            const float ty = (y ? q[1] : -q[1]) * (wx[x] * wz[z]);
+            const float tz = (z ? q[2] : -q[2]) * wxy;
+            s = has_gv ? ((s + tx) + ty) + tz : (tx + ty) + tz;
+        }
+        c[k] = s;
+    }
 }
 
 // The march of one ray {o, d, t_ray}.  work (COUNT only): {1 if the ray entered the box, main-loop samples, refinement samples} are added.

@@ -1708,7 +1708,7 @@ int cgrt_debug_isosurface_work(CgrtScene* scene, const CgrtGrid* grid, const flo
  * given (4 n, 12 n, n; 32 n) checked as device memory of the scene's device.  Nothing outside the n records is written.  No form reads or
  * writes the prediction record, the frame hints, the layout or any frame state.
  * Not offered: tricubic or tetrahedral interpolation (the iso-surface's piecewise-linear field); gradients with respect to the values
- * (autograd); vector-valued or batched grids; wrap or reflect padding; a bricked or narrow-band value layout; empty-space skipping; frame,
+ * from THESE entries (cgrt_sample_grid_grad below is the sampler's adjoint; the march's hit record has none); vector-valued or batched grids; wrap or reflect padding; a bricked or narrow-band value layout; empty-space skipping; frame,
  * AOV and enqueued-ticket forms; shading of marched hits through the render wavefront; the C++ host mirror. */
 #define CGRT_FIELD_CLAMP 1u
 #define CGRT_MARCH_MISS 0u
@@ -1746,6 +1746,64 @@ int cgrt_march_grid_device(CgrtScene* scene, const CgrtGrid* grid, const float* 
                            const CgrtMarchParams* params, CgrtGridHit* d_hits, void* stream);
 int cgrt_debug_march_work(CgrtScene* scene, const CgrtGrid* grid, const float* values, const CgrtRay* rays, uint64_t n,
                           const CgrtMarchParams* params, uint64_t* out3);
+
+/* Grid fields, the adjoint of the sampler.  Value and gradient of cgrt_sample_grid are linear in `values`; these
+ * entries apply the transpose of that map, so that a volume can be fitted to samples of its value and of its gradient, and so that points
+ * can be deposited into a volume (with grad_value alone the adjoint IS the trilinear splat of the weights grad_value).  Given grad_value
+ * (n f32, may be NULL) and grad_gradient (3n f32, may be NULL; not both), the gradients of some scalar with respect to the forward's
+ * value and gradient outputs, they ADD the gradient with respect to the values into grad_values (nx ny nz f32 in the values' order).
+ * `values` is not an argument.  Grid, limits, params, arithmetic and the meaning of fl() are those of "Grid fields" above.
+ * Validity and cell.  Exactly the forward's, with the same bits: u_c, its clamp under CGRT_FIELD_CLAMP, the inside rule, i_c and f_c.
+ *   params->outside is ignored.  A point the forward calls outside contributes nothing: its grad_value and grad_gradient are not read
+ *   (a NaN there stays out) and it indexes nothing.
+ * Contributions of an inside point, gv = grad_value[i], gg = grad_gradient[i].  Per axis c: w_c[0] = fl(1 - f_c), w_c[1] = f_c;
+ *   s[0] = -1, s[1] = +1; with grad_gradient given, q_c = fl(gg_c / spacing.c).  For each corner (x, y, z) in {0, 1}^3:
+ *     T_v = fl(gv fl(fl(w_x[x] w_y[y]) w_z[z]))
+ *     T_x = fl((s[x] q_x) fl(w_y[y] w_z[z]))     T_y = fl((s[y] q_y) fl(w_x[x] w_z[z]))     T_z = fl((s[z] q_z) fl(w_x[x] w_y[y]))
+ *   (s q is a change of sign and exact).  The contribution c_xyz is the sum, left to right and each sum rounded, of those of
+ *   T_v, T_x, T_y, T_z whose input array was given: fl(fl(fl(T_v + T_x) + T_y) + T_z) with both, T_v alone with grad_value only,
+ *   fl(fl(T_x + T_y) + T_z) with grad_gradient only.  The terms of a NULL input are left out of the sum, not added as zeros.
+ *   c_xyz is added to grad_values at (i_x + x, i_y + y, i_z + z) UNLESS c_xyz == 0: a zero of either sign is not added, a NaN is not
+ *   equal to 0 and is added.  An element that receives only zero contributions keeps its bits, a stored -0 included; a point on a grid
+ *   point (f = 0 on all axes) with grad_value alone touches one element.  Each contribution is thus a defined f32 bit pattern, a pure
+ *   function of (grid, point, gv, gg, flags).
+ * Order and bound.  The order of the additions into one element is unspecified: the value is the sum, in f32, of the element's previous
+ *   content and its contributions in SOME order (contributions of neighbouring points may be summed with each other first), and its last
+ *   bits may differ from run to run.  For an element with m contributions c and previous content a, every such order obeys
+ *     |got - exact| <= gamma(m + 1) * S + (m + 1) * 2^-126,   gamma(k) = k*u / (1 - k*u),  u = 2^-24,  S = |a| + sum |c|
+ *   (exact: the sum of a and the f32 contributions, in real arithmetic); this is the bound the tests use.  The hardware add keeps
+ *   subnormals on gfx950 (see the surface gradients above), so the absolute term is slack there; it stays in the bound.
+ * Against real arithmetic.  With W = w_x w_y w_z and W_x = w_y w_z, W_y = w_x w_z, W_z = w_x w_y the REAL products of the real weights
+ *   (1 - f_c, f_c) of the corner, the real adjoint coefficient is C = gv W + sum_c s_c (gg_c / spacing.c) W_c, and
+ *     |c_xyz - C| <= K u (|gv| W + sum_c |gg_c / spacing.c| W_c),   K = 10,
+ *   while no intermediate is subnormal.  Derivation: T_v carries six roundings (up to three of 1 - f, two weight products, the product
+ *   with gv), a T_c five (the division, up to two of 1 - f, one weight product, the product with q_c); the three sums put at most three
+ *   more on each term.  So every term is its real value times a product of at most nine factors (1 + d), |d| <= u, and
+ *   |c_xyz - C| <= gamma(9) B with B the bracket above; gamma(9) = 9u / (1 - 9u) < 10 u.  (First order: 9; the count "1 - f, division,
+ *   two products, the product with g, three sums" gives 8 when a single 1 - f is counted.)
+ * Scale symmetries, as property (d) above.  Multiplying grad_value and grad_gradient by 2^k multiplies every contribution by 2^k
+ *   exactly while every non-zero one of q_c, T_v, T_x, T_y, T_z and the partial sums, times 2^k, stays a normal float (the weights do not
+ *   move).  Multiplying origin, spacing and the points by 2^k leaves u, i, f, the weights and T_v alone and multiplies q_c, hence T_x,
+ *   T_y, T_z, by 2^-k exactly while every non-zero one of p.c, origin.c, p.c - origin.c, spacing.c, q_c, T_x, T_y, T_z times the scale
+ *   stays normal; the contribution of a call with grad_value only does not move, that of a call with grad_gradient only is multiplied
+ *   by 2^-k exactly (its partial sums inside the same envelope), and with both the sum mixes the two and only the terms obey it.
+ *   Outside the envelope the bytes are still the defined ones; only the relation to scale 1 is lost.
+ * Forms.  cgrt_sample_grid_grad takes host pointers, runs on a call lane like cgrt_sample_grid and blocks; any number of threads may
+ *   call at once; grad_values goes up, is added into and comes back.  cgrt_sample_grid_grad_device only enqueues on `stream` (NULL =
+ *   default stream) and reads nothing back.
+ * Checks, all CGRT_E_ARG, in this order and before any device work: NULL scene or grid; the grid's limits (the forward's); an unknown
+ *   flag in params (NULL params means flags 0); NULL points with n > 0; both grads NULL; NULL grad_values; n > 0x7fffffff; (device form) a
+ *   pointer not 4-byte aligned.  Then a host-only scene: CGRT_E_NO_DEVICE.  n == 0 succeeds and touches nothing.  Device form: then
+ *   d_points (12 n), each grad given (4 n, 12 n) and d_grad_values (4 bytes per grid point) checked as device memory of the scene's device.
+ *   Nothing outside the nx ny nz elements is written.  No form reads or writes the prediction record, the frame hints, the layout or any
+ *   frame state.  Overlap of grad_values with an input is the caller's error and is not checked.
+ * Not offered: a bitwise-reproducible form (as the *_grad_repro* entries are for the surface gradients); gradients of the march's hit
+ *   record (re-sample the hit point: README); second derivatives with respect to the points; vector-valued or batched grids; f16 / bf16;
+ *   the C++ host mirror. */
+int cgrt_sample_grid_grad(CgrtScene* scene, const CgrtGrid* grid, const float* points, uint64_t n, const CgrtFieldParams* params,
+                          const float* grad_value, const float* grad_gradient, float* grad_values);
+int cgrt_sample_grid_grad_device(CgrtScene* scene, const CgrtGrid* grid, const float* d_points, uint64_t n, const CgrtFieldParams* params,
+                                 const float* d_grad_value, const float* d_grad_gradient, float* d_grad_values, void* stream);
 
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.
