@@ -452,7 +452,9 @@ _grid_fn = None
 
 def _grid_function():
     """The torch.autograd.Function behind sample_grid_tensor when values or points requires grad:
-    apply(values, points, forward, backward, want) -> the tensors named by `want`, in its order.  forward(values, points) is the
+    apply(values, points, forward, backward, want, reproducible=False) -> the tensors named by `want`, in its order.  With `reproducible`
+    the backward call is the bitwise-reproducible entry and deterministic mode has nothing to object to.
+    forward(values, points) is the
     ordinary, non-recording call on detached tensors and returns a dict that always holds 'gradient'; backward(points, grad_value,
     grad_gradient) is the sample_grid_grad_tensor call on torch.cuda.current_stream().  'value' and 'gradient' are differentiable with
     respect to values; 'value' with respect to points, as grad_value[:, None] * gradient; the 'gradient' output is held constant in the
@@ -465,8 +467,8 @@ def _grid_function():
 
     class GridSample(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, values, points, forward, backward, want):
-            ctx.backward_call, ctx.want = backward, want
+        def forward(ctx, values, points, forward, backward, want, reproducible=False):
+            ctx.backward_call, ctx.want, ctx.reproducible = backward, want, reproducible
             ctx.set_materialize_grads(False)
             res = forward(values.detach(), points.detach())
             ctx.save_for_backward(points, res["gradient"])
@@ -482,7 +484,7 @@ def _grid_function():
             points, gradient = ctx.saved_tensors
             grad_values = grad_points = None
             if ctx.needs_input_grad[0] and (gv is not None or gg is not None):
-                if torch.are_deterministic_algorithms_enabled():
+                if not ctx.reproducible and torch.are_deterministic_algorithms_enabled():
                     msg = ("the grid-sample backward adds into the volume with float atomics: the order of the additions into one element "
                            "is unspecified and the last bits of the gradient may differ from run to run")
                     if torch.is_deterministic_algorithms_warn_only_enabled():
@@ -492,7 +494,7 @@ def _grid_function():
                 grad_values = ctx.backward_call(points, None if gv is None else gv.contiguous(), None if gg is None else gg.contiguous())
             if ctx.needs_input_grad[1] and gv is not None:
                 grad_points = gv[:, None] * gradient
-            return grad_values, grad_points, None, None, None
+            return grad_values, grad_points, None, None, None, None
 
     _grid_fn = GridSample
     return _grid_fn
@@ -516,7 +518,7 @@ _lib: Optional[C.CDLL] = None
 EXPORTS = [
     "cgrt_scene_create", "cgrt_scene_destroy", "cgrt_set_leaf_accel", "cgrt_num_subnodes", "cgrt_set_primary_mode", "cgrt_set_kernel_shape", "cgrt_get_kernel_shape", "cgrt_set_render_prediction", "cgrt_set_frame_hints", "cgrt_set_frame_gate", "cgrt_debug_frame_gate", "cgrt_set_frame_order", "cgrt_debug_set_frame_order", "cgrt_debug_get_frame_order", "cgrt_debug_build_frame_order", "cgrt_debug_set_hint_thresholds", "cgrt_debug_hint_counts", "cgrt_debug_render_path", "cgrt_set_fast_tree", "cgrt_scene_set_walk", "cgrt_scene_walk", "cgrt_scene_build_info", "cgrt_num_levels", "cgrt_num_nodes", "cgrt_get_nodes", "cgrt_leaf_prims",
     "cgrt_build_seconds", "cgrt_device_bytes", "cgrt_intersect_batch", "cgrt_set_call_combining", "cgrt_debug_combiner_stats", "cgrt_intersect_brute_batch", "cgrt_intersect_batch_device", "cgrt_trace_primary",
-    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_point_grid_workspace", "cgrt_point_grid_build_device", "cgrt_count_point_neighbors", "cgrt_count_point_neighbors_device", "cgrt_list_point_neighbors", "cgrt_list_point_neighbors_device", "cgrt_list_point_neighbors_brute", "cgrt_debug_point_neighbor_work", "cgrt_point_frames", "cgrt_point_frames_device", "cgrt_point_frames_brute", "cgrt_isosurface_workspace", "cgrt_isosurface_count_device", "cgrt_isosurface_device", "cgrt_isosurface", "cgrt_debug_isosurface_work", "cgrt_sample_grid", "cgrt_sample_grid_device", "cgrt_march_grid", "cgrt_march_grid_device", "cgrt_debug_march_work", "cgrt_sample_grid_grad", "cgrt_sample_grid_grad_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
+    "cgrt_trace_primary_device", "cgrt_generate_rays", "cgrt_render", "cgrt_render_soft", "cgrt_render_mapped", "cgrt_render_rank", "cgrt_render_counted", "cgrt_trace_primary_multi", "cgrt_render_multi", "cgrt_render_aa", "cgrt_render_aa_mapped", "cgrt_render_multi_aa", "cgrt_render_device", "cgrt_debug_export_frame", "cgrt_shade_rays", "cgrt_shade_rays_device", "cgrt_trace_primary_views_device", "cgrt_render_views", "cgrt_render_views_device", "cgrt_render_light_sets", "cgrt_render_light_sets_device", "cgrt_render_views_light_sets", "cgrt_render_views_light_sets_device", "cgrt_enqueue_render_views_light_sets_device", "cgrt_enqueue_render_device", "cgrt_enqueue_render_views_device", "cgrt_render_aov_device", "cgrt_render_views_aov_device", "cgrt_enqueue_render_aov_device", "cgrt_enqueue_render_views_aov_device", "cgrt_generate_rays_raycam", "cgrt_trace_primary_raycams_device", "cgrt_render_raycams_device", "cgrt_enqueue_render_raycams_device", "cgrt_render_raycams_light_sets_device", "cgrt_enqueue_shade_rays_device", "cgrt_enqueue_stats", "cgrt_debug_strided_waves", "cgrt_occluded", "cgrt_occluded_device", "cgrt_in_shadow", "cgrt_in_shadow_device", "cgrt_soft_lit", "cgrt_soft_lit_device", "cgrt_hit_barycentrics", "cgrt_hit_barycentrics_device", "cgrt_interpolate_hits", "cgrt_interpolate_hits_device", "cgrt_surface_views_device", "cgrt_surface_raycams_device", "cgrt_interpolate_hits_grad", "cgrt_interpolate_hits_grad_device", "cgrt_surface_views_grad_device", "cgrt_surface_raycams_grad_device", "cgrt_surface_grad_repro_workspace", "cgrt_interpolate_hits_grad_repro", "cgrt_interpolate_hits_grad_repro_device", "cgrt_surface_views_grad_repro_device", "cgrt_surface_raycams_grad_repro_device", "cgrt_closest_points", "cgrt_closest_points_device", "cgrt_closest_points_brute", "cgrt_debug_closest_work", "cgrt_count_crossings", "cgrt_count_crossings_device", "cgrt_list_crossings", "cgrt_list_crossings_device", "cgrt_list_crossings_brute", "cgrt_debug_crossing_work", "cgrt_count_neighbors", "cgrt_count_neighbors_device", "cgrt_list_neighbors", "cgrt_list_neighbors_device", "cgrt_list_neighbors_brute", "cgrt_debug_neighbor_work", "cgrt_signed_distance", "cgrt_signed_distance_device", "cgrt_signed_distance_grid", "cgrt_signed_distance_grid_device", "cgrt_debug_sdf_work", "cgrt_debug_set_sdf_grid_mapping", "cgrt_winding_numbers", "cgrt_winding_numbers_device", "cgrt_winding_numbers_grid", "cgrt_winding_numbers_grid_device", "cgrt_winding_numbers_brute", "cgrt_debug_winding_work", "cgrt_debug_get_winding_tree", "cgrt_sample_surface", "cgrt_sample_surface_device", "cgrt_triangle_areas", "cgrt_debug_get_sample_table", "cgrt_poisson_disk", "cgrt_poisson_disk_device", "cgrt_poisson_disk_workspace", "cgrt_poisson_disk_brute", "cgrt_debug_poisson_work", "cgrt_point_grid_workspace", "cgrt_point_grid_build_device", "cgrt_count_point_neighbors", "cgrt_count_point_neighbors_device", "cgrt_list_point_neighbors", "cgrt_list_point_neighbors_device", "cgrt_list_point_neighbors_brute", "cgrt_debug_point_neighbor_work", "cgrt_point_frames", "cgrt_point_frames_device", "cgrt_point_frames_brute", "cgrt_isosurface_workspace", "cgrt_isosurface_count_device", "cgrt_isosurface_device", "cgrt_isosurface", "cgrt_debug_isosurface_work", "cgrt_sample_grid", "cgrt_sample_grid_device", "cgrt_march_grid", "cgrt_march_grid_device", "cgrt_debug_march_work", "cgrt_sample_grid_grad", "cgrt_sample_grid_grad_device", "cgrt_sample_grid_grad_repro_workspace", "cgrt_sample_grid_grad_repro", "cgrt_sample_grid_grad_repro_device", "cgrt_count_primary", "cgrt_count_batch", "cgrt_debug_wave_times", "cgrt_debug_trace_shadow", "cgrt_debug_soft_lit", "cgrt_debug_fastdiv_check", "cgrt_debug_gather_calibration", "cgrt_debug_check_layout", "cgrt_debug_layout_hash", "cgrt_debug_node_pack", "cgrt_debug_node_unpack", "cgrt_debug_get_subnodes", "cgrt_set_build_threads", "cgrt_record_sizes",
     "cgrt_ray_triangle_batch", "cgrt_ray_plane_batch", "cgrt_ray_box_batch", "cgrt_ray_sphere_batch",
     "cgrt_triangle_plane_batch", "cgrt_point_in_triangle_batch", "cgrt_device_count", "cgrt_last_error", "cgrt_version", "cgrt_source_hash",
 ]  # fmt: skip
@@ -708,6 +710,9 @@ def lib() -> C.CDLL:
     L.cgrt_debug_march_work.argtypes = [vp, gp, vp, vp, u64, mp, vp]
     L.cgrt_sample_grid_grad.argtypes = [vp, gp, vp, u64, fp, vp, vp, vp]
     L.cgrt_sample_grid_grad_device.argtypes = [vp, gp, vp, u64, fp, vp, vp, vp, vp]
+    L.cgrt_sample_grid_grad_repro_workspace.argtypes = [vp, gp, C.POINTER(C.c_uint64)]
+    L.cgrt_sample_grid_grad_repro.argtypes = L.cgrt_sample_grid_grad.argtypes
+    L.cgrt_sample_grid_grad_repro_device.argtypes = [vp, gp, vp, u64, fp, vp, vp, vp, vp, u64, vp]
     L.cgrt_triangle_areas.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.cgrt_debug_get_sample_table.argtypes = [vp, vp, C.POINTER(u32)]
     L.cgrt_count_primary.argtypes = [vp, C.POINTER(Camera)] + [i32] * 8 + [C.POINTER(Counters)]
@@ -3381,7 +3386,7 @@ class Scene:
         return (nx, ny, nz)
 
     def sample_grid_tensor(self, values, origin, spacing, points, outside=float("nan"), clamp: bool = False,
-                           want=("value", "gradient", "inside"), out=None, stream=None):
+                           want=("value", "gradient", "inside"), out=None, stream=None, reproducible: bool = False):
         """sample_grid on torch tensors: values (nz, ny, nx) and points (n, 3), contiguous float32 on cuda:<device> -> a dict of the
         tensors named by `want` ('value' (n,) float32, 'gradient' (n, 3) float32, 'inside' (n,) torch.bool), written into `out` (a dict
         by name; inside may also be torch.uint8) or new ones, enqueued on `stream` (default: torch.cuda.current_stream()).
@@ -3390,8 +3395,10 @@ class Scene:
         backward; 'value' is differentiable with respect to points, as grad_value[:, None] * gradient (the sampler's own gradient
         output, computed internally when it is not in want); the 'gradient' OUTPUT is treated as constant in the points (no second
         derivatives); 'inside' is not differentiable.  The backward runs once (no double backward) and, since the adds into the volume
-        are float atomics, raises under torch.use_deterministic_algorithms(True) (warns in warn-only mode) when values needs a gradient.
-        With nothing requiring grad the call and its bytes are the plain ones."""
+        are float atomics, raises under torch.use_deterministic_algorithms(True) (warns in warn-only mode) when values needs a gradient
+        -- unless reproducible: then the recorded backward is the bitwise-reproducible entry (sample_grid_grad_tensor(...,
+        reproducible=True); include/cgrt.h cgrt_sample_grid_grad_repro*), which runs in deterministic mode and gives the same bytes in
+        every run.  With nothing requiring grad the call and its bytes are the plain ones, whatever the keyword."""
         import torch
 
         want = self._grid_want(want)
@@ -3406,7 +3413,8 @@ class Scene:
             res = _grid_function().apply(
                 values, points,
                 lambda v, p: self.sample_grid_tensor(v, origin, spacing, p, outside=outside, clamp=clamp, want=inner, stream=stream),
-                lambda p, gv, gg: self.sample_grid_grad_tensor(origin, spacing, dims, p, gv, gg, clamp=clamp), want)
+                lambda p, gv, gg: self.sample_grid_grad_tensor(origin, spacing, dims, p, gv, gg, clamp=clamp, reproducible=bool(reproducible)),
+                want, bool(reproducible))
             return dict(zip(want, res))
         n = int(points.shape[0])
         shapes = {"value": ((n,), (torch.float32,)), "gradient": ((n, 3), (torch.float32,)), "inside": ((n,), (torch.bool, torch.uint8))}
@@ -3434,14 +3442,36 @@ class Scene:
         return res
 
     # ---- grid fields, the sampler's adjoint (include/cgrt.h cgrt_sample_grid_grad*) ----
+    def sample_grid_grad_repro_workspace(self, origin, spacing, dims) -> int:
+        """cgrt_sample_grid_grad_repro_workspace: the bytes of device memory a reproducible adjoint call on this grid needs
+        (12 * nx * ny * nz)."""
+        b = C.c_uint64(0)
+        g = _sdf_grid_struct(origin, spacing, dims)
+        _check(lib().cgrt_sample_grid_grad_repro_workspace(self._h, C.byref(g), C.byref(b)))
+        return int(b.value)
+
+    def _grid_repro_workspace_tensor(self, reproducible: bool, origin, spacing, dims, stream):
+        """(workspace, keywords) of a reproducible sample_grid_grad_device call, as _repro_workspace_tensor makes them for the surface
+        gradients: a torch.uint8 tensor allocated on the call's stream and held until the call has enqueued its passes.  (None, {}) for
+        the float form."""
+        if not reproducible:
+            return None, {}
+        import torch
+
+        nbytes = self.sample_grid_grad_repro_workspace(origin, spacing, dims)
+        with torch.cuda.stream(stream):
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=stream.device)
+        return ws, {"reproducible": True, "d_workspace_ptr": ws.data_ptr(), "workspace_bytes": nbytes}
+
     def sample_grid_grad(self, origin, spacing, dims, points, grad_value=None, grad_gradient=None, grad_values=None,
-                         clamp: bool = False) -> np.ndarray:
+                         clamp: bool = False, reproducible: bool = False) -> np.ndarray:
         """cgrt_sample_grid_grad, the adjoint of sample_grid with respect to values: grad_value ((n,) float32) and grad_gradient ((n, 3)
         float32) are the gradients with respect to sample_grid's value and gradient at points ((n, 3) float32); either may be None, not
         both.  Every inside point's eight contributions are ADDED into grad_values -- a writeable C-contiguous (nz, ny, nx) float32 array
         that is accumulated into in place, or None for a new zero array -- which is returned.  dims = (nx, ny, nz).  The order of the
         additions into one element is unspecified (last bits may differ from run to run); each contribution is defined to the last bit
-        (include/cgrt.h).  With grad_value alone this is the trilinear splat of the weights grad_value."""
+        (include/cgrt.h).  With grad_value alone this is the trilinear splat of the weights grad_value.  reproducible: then
+        cgrt_sample_grid_grad_repro, whose result is defined to the last bit (include/cgrt.h)."""
         p = _f32(points, (-1, 3))
         gv = None if grad_value is None else _f32(grad_value, (-1,))
         gg = None if grad_gradient is None else _f32(grad_gradient, (-1, 3))
@@ -3454,24 +3484,33 @@ class Scene:
                   and grad_values.flags.writeable and grad_values.shape == (nz, ny, nx)):
             raise ValueError(f"grad_values must be a writeable C-contiguous float32 array of shape ({nz}, {ny}, {nx})")
         g, prm = _sdf_grid_struct(origin, spacing, (nx, ny, nz)), _field_params(clamp=clamp)
-        _check(lib().cgrt_sample_grid_grad(self._h, C.byref(g), _ptr(p), len(p), C.byref(prm), _ptr(gv), _ptr(gg), _ptr(grad_values)))
+        f = lib().cgrt_sample_grid_grad_repro if reproducible else lib().cgrt_sample_grid_grad
+        _check(f(self._h, C.byref(g), _ptr(p), len(p), C.byref(prm), _ptr(gv), _ptr(gg), _ptr(grad_values)))
         return grad_values
 
     def sample_grid_grad_device(self, origin, spacing, dims, d_points_ptr: int, n: int, d_grad_value_ptr: int, d_grad_gradient_ptr: int,
-                                d_grad_values_ptr: int, clamp: bool = False, stream: int = 0) -> None:
+                                d_grad_values_ptr: int, clamp: bool = False, stream: int = 0, reproducible: bool = False,
+                                d_workspace_ptr: int = 0, workspace_bytes: int = 0) -> None:
         """cgrt_sample_grid_grad_device: n points (3 floats each) at d_points_ptr, n float32 at d_grad_value_ptr and 3 n float32 at
         d_grad_gradient_ptr (0: not given; not both) are added, weighted, into the nx * ny * nz float32 at d_grad_values_ptr; enqueued on
-        the hipStream_t `stream`.  Raw integers."""
+        the hipStream_t `stream`.  Raw integers.  reproducible: cgrt_sample_grid_grad_repro_device with the caller's workspace
+        (sample_grid_grad_repro_workspace(origin, spacing, dims) bytes of device memory, 8-byte aligned, this call's alone)."""
         g, prm = _sdf_grid_struct(origin, spacing, dims), _field_params(clamp=clamp)
+        if reproducible:
+            _check(lib().cgrt_sample_grid_grad_repro_device(self._h, C.byref(g), _vp(d_points_ptr), int(n), C.byref(prm),
+                                                            _vp(d_grad_value_ptr), _vp(d_grad_gradient_ptr), _vp(d_grad_values_ptr),
+                                                            _vp(d_workspace_ptr), int(workspace_bytes), _vp(stream)))
+            return
         _check(lib().cgrt_sample_grid_grad_device(self._h, C.byref(g), _vp(d_points_ptr), int(n), C.byref(prm), _vp(d_grad_value_ptr),
                                                   _vp(d_grad_gradient_ptr), _vp(d_grad_values_ptr), _vp(stream)))
 
     def sample_grid_grad_tensor(self, origin, spacing, dims, points, grad_value=None, grad_gradient=None, out=None, clamp: bool = False,
-                                stream=None):
+                                stream=None, reproducible: bool = False):
         """sample_grid_grad on torch tensors: points (n, 3), grad_value (n,) and grad_gradient (n, 3) (either may be None, not both),
         contiguous float32 on cuda:<device>; added into `out` ((nz, ny, nx) float32 on the device, or None for a new zero tensor), which
         is returned.  dims = (nx, ny, nz).  Enqueued on `stream` (default: torch.cuda.current_stream()).  sample_grid_tensor calls this in
-        its backward when values requires grad."""
+        its backward when values requires grad.  reproducible: the bitwise-reproducible entry, its workspace (12 bytes per grid element)
+        allocated here on the call's stream."""
         import torch
 
         self._device_tensor(points, "points", (torch.float32,))
@@ -3493,21 +3532,25 @@ class Scene:
         else:
             self._device_tensor(out, "out", (torch.float32,), (nz, ny, nx))
         if n:  # (an empty tensor has no address to pass: the call would touch nothing anyway)
+            ws, kw = self._grid_repro_workspace_tensor(reproducible, origin, spacing, (nx, ny, nz), stream)
             self.sample_grid_grad_device(origin, spacing, (nx, ny, nz), points.data_ptr(), n,
                                          0 if grad_value is None else grad_value.data_ptr(),
                                          0 if grad_gradient is None else grad_gradient.data_ptr(), out.data_ptr(), clamp=clamp,
-                                         stream=stream.cuda_stream)
+                                         stream=stream.cuda_stream, **kw)
+            del ws  # (held until the passes were enqueued: the allocator hands the block only to later work of the same stream)
         return out
 
-    def splat_grid_tensor(self, points, weights, origin, spacing, dims, out=None, clamp: bool = False, stream=None):
+    def splat_grid_tensor(self, points, weights, origin, spacing, dims, out=None, clamp: bool = False, stream=None,
+                          reproducible: bool = False):
         """Points -> volume: the trilinear splat of weights ((n,) float32) at points ((n, 3) float32) into the grid origin + i * spacing
         of dims = (nx, ny, nz) -- sample_grid_grad_tensor with grad_value = weights and no grad_gradient.  Added into `out` ((nz, ny, nx)
         float32, or None for a new zero tensor), which is returned: a density estimate or a particle-to-grid deposit that
         isosurface_tensor, sample_grid_tensor and march_grid_tensor read as it is.  Points outside the grid deposit nothing (clamp: they
-        deposit at the nearest point of its box)."""
+        deposit at the nearest point of its box).  reproducible: the bitwise-reproducible entry, a density defined to the last bit."""
         if weights is None:
             raise ValueError("weights must be a torch tensor of shape (n,)")
-        return self.sample_grid_grad_tensor(origin, spacing, dims, points, grad_value=weights, out=out, clamp=clamp, stream=stream)
+        return self.sample_grid_grad_tensor(origin, spacing, dims, points, grad_value=weights, out=out, clamp=clamp, stream=stream,
+                                            reproducible=reproducible)
 
     def march_grid(self, values, origin, spacing, rays, iso: float = 0.0, relax: float = 1.0, min_step: float = 1e-4, hit_eps: float = 1e-4,
                    max_steps: int = 256, refine: int = 0, inside_above: bool = False) -> np.ndarray:

@@ -1509,9 +1509,11 @@ int field_march_query(CgrtScene* s, bool device, const CgrtGrid* grid, const flo
     return c.finish();
 }
 // the sampler's adjoint (include/cgrt.h "Grid fields, the adjoint").  slots: 0 the points, 1 grad_value,
-// 2 grad_gradient, 3 grad_values (host form: uploaded, added into, downloaded)
+// 2 grad_gradient, 3 grad_values (host form: uploaded, added into, downloaded).  repro: the bitwise-reproducible form (DESIGN.md section
+// 5.36), whose workspace is the caller's `ws` (device form) or the lane's slot 4 (host form)
 int field_grad_query(CgrtScene* s, bool device, const CgrtGrid* grid, const float* points, uint64_t n, const CgrtFieldParams* params,
-                     const float* grad_value, const float* grad_gradient, float* grad_values, void* stream) {
+                     const float* grad_value, const float* grad_gradient, float* grad_values, bool repro, const ReproWorkspace* ws,
+                     void* stream) {
     if (!s || !grid) return fail(CGRT_E_ARG, "scene or grid is NULL");
     FieldGradCall Q{};
     uint64_t N = 0;
@@ -1523,6 +1525,11 @@ int field_grad_query(CgrtScene* s, bool device, const CgrtGrid* grid, const floa
     if (n > kFieldMaxPoints) return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
     if (device && ((uintptr_t)points % 4 || (uintptr_t)grad_value % 4 || (uintptr_t)grad_gradient % 4 || (uintptr_t)grad_values % 4))
         return fail(CGRT_E_ARG, "d_points, d_grad_value, d_grad_gradient and d_grad_values must be 4-byte aligned");
+    if (n && ws) {  // d_workspace NULL, misaligned or too small: after the twin's checks, before the host-only scene
+        if (!ws->d) return fail(CGRT_E_ARG, "NULL argument: d_workspace");
+        if ((uintptr_t)ws->d % 8) return fail(CGRT_E_ARG, "d_workspace must be 8-byte aligned");
+        if (ws->bytes < field_grad_repro_bytes(N)) return fail(CGRT_E_ARG, "workspace_bytes is below cgrt_sample_grid_grad_repro_workspace");
+    }
     NEED_DEVICE(s);
     if (n == 0) return CGRT_OK;
     Q.clamp = params && (params->flags & CGRT_FIELD_CLAMP) ? 1u : 0u;
@@ -1538,7 +1545,17 @@ int field_grad_query(CgrtScene* s, bool device, const CgrtGrid* grid, const floa
     Q.grad_value = grad_value ? static_cast<const float*>(dgv) : nullptr;
     Q.grad_gradient = grad_gradient ? static_cast<const float*>(dgg) : nullptr;
     Q.grad_values = static_cast<float*>(dout);
-    HIP_TRY(launch_sample_grid_grad(Q, c.stream()));
+    void* dws = nullptr;
+    if (ws) {
+        dws = ws->d;
+        CGRT_TRY(check_device_span(s, dws, field_grad_repro_bytes(N), "d_workspace"));
+    } else if (repro) {
+        HIP_TRY(c.c.scratch(4, field_grad_repro_bytes(N), &dws));
+    }
+    if (repro)
+        HIP_TRY(launch_sample_grid_grad_repro(Q, N, dws, c.stream()));
+    else
+        HIP_TRY(launch_sample_grid_grad(Q, c.stream()));
     return c.finish();
 }
 }  // namespace
@@ -1553,11 +1570,29 @@ int cgrt_sample_grid_device(CgrtScene* s, const CgrtGrid* grid, const float* d_v
 }
 int cgrt_sample_grid_grad(CgrtScene* s, const CgrtGrid* grid, const float* points, uint64_t n, const CgrtFieldParams* params,
                           const float* grad_value, const float* grad_gradient, float* grad_values) {
-    return field_grad_query(s, false, grid, points, n, params, grad_value, grad_gradient, grad_values, nullptr);
+    return field_grad_query(s, false, grid, points, n, params, grad_value, grad_gradient, grad_values, false, nullptr, nullptr);
 }
 int cgrt_sample_grid_grad_device(CgrtScene* s, const CgrtGrid* grid, const float* d_points, uint64_t n, const CgrtFieldParams* params,
                                  const float* d_grad_value, const float* d_grad_gradient, float* d_grad_values, void* stream) {
-    return field_grad_query(s, true, grid, d_points, n, params, d_grad_value, d_grad_gradient, d_grad_values, stream);
+    return field_grad_query(s, true, grid, d_points, n, params, d_grad_value, d_grad_gradient, d_grad_values, false, nullptr, stream);
+}
+int cgrt_sample_grid_grad_repro_workspace(CgrtScene* s, const CgrtGrid* grid, uint64_t* bytes) {
+    if (!s || !grid || !bytes) return fail(CGRT_E_ARG, "NULL argument");
+    GridField G{};
+    uint64_t N = 0;
+    CGRT_TRY(field_grid(grid, &G, &N));
+    *bytes = field_grad_repro_bytes(N);
+    return CGRT_OK;
+}
+int cgrt_sample_grid_grad_repro(CgrtScene* s, const CgrtGrid* grid, const float* points, uint64_t n, const CgrtFieldParams* params,
+                                const float* grad_value, const float* grad_gradient, float* grad_values) {
+    return field_grad_query(s, false, grid, points, n, params, grad_value, grad_gradient, grad_values, true, nullptr, nullptr);
+}
+int cgrt_sample_grid_grad_repro_device(CgrtScene* s, const CgrtGrid* grid, const float* d_points, uint64_t n, const CgrtFieldParams* params,
+                                       const float* d_grad_value, const float* d_grad_gradient, float* d_grad_values, void* d_workspace,
+                                       uint64_t workspace_bytes, void* stream) {
+    const ReproWorkspace ws{d_workspace, workspace_bytes};
+    return field_grad_query(s, true, grid, d_points, n, params, d_grad_value, d_grad_gradient, d_grad_values, true, &ws, stream);
 }
 int cgrt_march_grid(CgrtScene* s, const CgrtGrid* grid, const float* values, const CgrtRay* rays, uint64_t n, const CgrtMarchParams* params,
                     CgrtGridHit* hits) {

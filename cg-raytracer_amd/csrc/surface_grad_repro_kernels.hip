@@ -16,9 +16,11 @@
 //             or a + s for the kinds, stored plainly.
 // The two mappings are k_surface_grad's: lanes over the wave's contiguous 64 x C run of grad_out (by_item == 0), or each lane the
 // channels of its own item (by_item != 0), there with consecutive lanes of one prim_id combined inside the wave first -- the max pass
-// combines codes, the add pass INTEGER terms, never floats.  256-thread blocks, no LDS, no scratch.
+// combines codes, the add pass INTEGER terms, never floats.  256-thread blocks, no LDS, no scratch.  The element arithmetic (repro_code,
+// repro_join, repro_mark, repro_term, repro_value_*) is grad_repro_device.h's, shared with the grid form (grid_field_grad_repro_kernels.hip).
 #include <hip/hip_runtime.h>
 
+#include "grad_repro_device.h"
 #include "surface_device.h"
 #include "surface_grad_repro_kernels.h"
 
@@ -26,46 +28,12 @@ namespace cgrt {
 
 namespace {
 
-const uint32_t REPRO_EXP = 0xffu;       // the word's exponent field
-const uint32_t REPRO_POS_INF = 0x100u;  // kinds
-const uint32_t REPRO_NEG_INF = 0x200u;
-const uint32_t REPRO_NAN = 0x400u;
-const uint32_t REPRO_KINDS = 0x700u;
-
 struct SurfaceGradReproDev {
     SurfaceGradDev g;         // grad_attr is not touched by the max and add passes
     unsigned long long* acc;  // one per table element
     uint32_t* word;           // one per table element
     uint32_t shift;           // S
 };
-
-// What a contribution x brings to its element's word: e' = max(exponent field, 1) if it is finite, else its kind.
-__device__ __forceinline__ uint32_t repro_code(const float x) {
-    const uint32_t b = __float_as_uint(x), ef = (b >> 23) & 0xffu;
-    if (ef == 0xffu) return (b & 0x7fffffu) ? REPRO_NAN : ((b >> 31) ? REPRO_NEG_INF : REPRO_POS_INF);
-    return ef ? ef : 1u;
-}
-__device__ __forceinline__ uint32_t repro_join(const uint32_t a, const uint32_t b) {
-    const uint32_t ea = a & REPRO_EXP, eb = b & REPRO_EXP;
-    return ((a | b) & REPRO_KINDS) | (ea > eb ? ea : eb);
-}
-__device__ __forceinline__ void repro_mark(uint32_t* const w, const uint32_t code) {
-    if (code & REPRO_KINDS) atomicOr(w, code & REPRO_KINDS);
-    if (code & REPRO_EXP) atomicMax(w, code & REPRO_EXP);
-}
-// The integer term of a finite x under the element's word (E in its low byte) with S guard bits; 0 if the element carries a kind.
-__device__ __forceinline__ long long repro_term(const float x, const uint32_t word, const uint32_t S) {
-    const uint32_t b = __float_as_uint(x), ef = (b >> 23) & 0xffu;
-    if (ef == 0xffu || (word & REPRO_KINDS)) return 0;
-    const uint32_t e = ef ? ef : 1u, M = (b & 0x7fffffu) | (ef ? 0x800000u : 0u);
-    const uint32_t d = (word & REPRO_EXP) - e;  // >= 0: the max pass saw this very x
-    long long T;
-    if (d <= S)
-        T = (long long)((unsigned long long)M << (S - d));
-    else
-        T = d - S >= 24u ? 0 : (long long)(M >> (d - S));
-    return (b >> 31) ? -T : T;
-}
 
 template <int PASS>
 __device__ __forceinline__ void repro_contribute(const SurfaceGradReproDev& R, const unsigned long long at, const float x) {
@@ -188,17 +156,14 @@ __global__ __launch_bounds__(256) void k_surface_grad_repro_finalise(const unsig
         if (!w) continue;
         const float a = grad_attr[e];
         float r;
-        if (w & REPRO_KINDS) {
+        if (w & REPRO_KINDS) {  // (repro_value_kinds, kept as the lines it was moved from: through the call this kernel takes two more VGPRs)
             const uint32_t k = w & REPRO_KINDS;
             const float s = k == REPRO_POS_INF ? __uint_as_float(0x7f800000u) : (k == REPRO_NEG_INF ? __uint_as_float(0xff800000u) : __uint_as_float(0x7fc00000u));
             r = a + s;
         } else {
-            const long long I = (long long)acc[e];
-            // 2^(E - 150 - S): E in 1..254, S in 5..24, |I| < 2^62 -- the product stays a normal double, so the scaling is exact
-            const double scale = __longlong_as_double((long long)(1023u + (w & REPRO_EXP) - 150u - S) << 52);
-            r = (float)((double)a + (double)I * scale);
+            r = repro_value_sum(a, w, (long long)acc[e], S);
         }
-        if (r != r) r = __uint_as_float(0x7fc00000u);  // every NaN result is this one quiet NaN
+        r = repro_canonical(r);
         grad_attr[e] = r;
     }
 }

@@ -1797,13 +1797,74 @@ int cgrt_debug_march_work(CgrtScene* scene, const CgrtGrid* grid, const float* v
  *   d_points (12 n), each grad given (4 n, 12 n) and d_grad_values (4 bytes per grid point) checked as device memory of the scene's device.
  *   Nothing outside the nx ny nz elements is written.  No form reads or writes the prediction record, the frame hints, the layout or any
  *   frame state.  Overlap of grad_values with an input is the caller's error and is not checked.
- * Not offered: a bitwise-reproducible form (as the *_grad_repro* entries are for the surface gradients); gradients of the march's hit
- *   record (re-sample the hit point: README); second derivatives with respect to the points; vector-valued or batched grids; f16 / bf16;
- *   the C++ host mirror. */
+ * Not offered: reproducible bits from THESE entries (the cgrt_sample_grid_grad_repro* entries below are the bitwise-reproducible form);
+ *   gradients of the march's hit record (re-sample the hit point: README); second derivatives with respect to the points;
+ *   vector-valued or batched grids; f16 / bf16; the C++ host mirror. */
 int cgrt_sample_grid_grad(CgrtScene* scene, const CgrtGrid* grid, const float* points, uint64_t n, const CgrtFieldParams* params,
                           const float* grad_value, const float* grad_gradient, float* grad_values);
 int cgrt_sample_grid_grad_device(CgrtScene* scene, const CgrtGrid* grid, const float* d_points, uint64_t n, const CgrtFieldParams* params,
                                  const float* d_grad_value, const float* d_grad_gradient, float* d_grad_values, void* stream);
+
+/* Grid fields, the bitwise-reproducible form of the sampler's adjoint.  An opt-in second form of the entries
+ * above whose result is a pure function of the call's inputs, as the *_grad_repro* entries of the surface attributes are for the table
+ * adjoint: one definition of "reproducible" for the library.  The entries above are unchanged.
+ * Definition.  Validity, cell and contributions are those of cgrt_sample_grid_grad, bit for bit: u, its clamp, the inside rule, i and f
+ * (field_cell), the eight c_xyz with the terms of a NULL input left out (field_adjoint); an outside point is neither read nor indexed.
+ * A contribution that compares equal to zero is NOT a contribution, as in the float form (this is where the grid form departs from
+ * the surface form, where +-0 counts): an element that receives only zeros is untouched.  Every dim is at least 2, so the eight corners
+ * of a point are eight distinct elements: an element receives at most one contribution per point, m <= n.  For an element with previous
+ * content a and contributions x_1..x_m (m >= 1), n the call's point count:
+ *   S = min(24, 38 - bitlength(n))                        (n <= 0x7fffffff, so S >= 7)
+ *   a finite x_j is +-M_j * 2^(e'_j - 150), e'_j = max(exponent field, 1), M_j the 24-bit significand (a subnormal: no implicit bit)
+ *   E = max_j e'_j,  d_j = E - e'_j
+ *   T_j = +-(M_j << (S - d_j)) if d_j <= S, else +-(M_j >> (d_j - S))   (the magnitude is truncated; 0 once the shift reaches 24)
+ *   I = sum_j T_j in int64                                (no overflow: |I| < 2^(24 + S) * n <= 2^62)
+ *   new value = fl32( fl64(a) + fl64(I) * 2^(E - 150 - S) )
+ * fl64(I) is the round-to-nearest-even conversion, the scaling is exact, the sum is rounded to double and then once to float,
+ * subnormals kept.  If any x_j is not finite the element becomes fl32(a + s), s = NaN if a NaN contribution is present or both +inf and
+ * -inf are, else the infinity that is present.  Every NaN result is stored as the quiet NaN 0x7fc00000.  Elements without a contribution
+ * are neither read nor written: a stored -0, a signalling-NaN payload and a sentinel byte pattern survive.  An element whose
+ * contributions all truncate to T = 0 is still touched and becomes fl32(fl64(a) + 0).
+ * Properties.
+ *   (a) Order-freedom.  E is a maximum, the kinds an OR, I an integer sum: all three are associative and commutative, and the last step
+ *       is a function of (a, E, kinds, I, S) alone.  So the result does not depend on the order of the additions, the mapping of lanes
+ *       to points, a permutation of the points, the stream, the thread or the run.
+ *   (b) A legal value of the float form.  Write sigma = 2^(E - 150 - S), X = sum x_j in real arithmetic, S_abs = |a| + sum |x_j|.
+ *       x_j = T_j sigma exactly when d_j <= S; otherwise the truncation loses less than sigma, towards zero.  If E = 1 every d_j is 0
+ *       and nothing is lost; else the largest contribution is normal, |x_max| >= 2^(23 + S) sigma, so sigma <= 2^(1 - S) u |x_max| and
+ *       |I sigma - X| < (m - 1) sigma <= (m - 1) 2^(1 - S) u |x_max| <= (m - 1) u |x_max| / 64 (S >= 7).  fl64(I) is exact below 2^53
+ *       and within 2^-53 relative above, the scaling is exact, the double sum adds 2^-53 relative and the rounding to float u relative,
+ *       or at most 2^-150 absolute among subnormals.  Together
+ *         |new - (a + X)| <= u S_abs (1 + (m - 1) / 64 + 2^-27) + 2^-150 <= gamma(m + 1) S_abs + (m + 1) 2^-126
+ *       since gamma(m + 1) >= (m + 1) u and m >= 1: the bound of cgrt_sample_grid_grad holds for every element (the tests assert it
+ *       with none excluded), so the result is one the float form may return.
+ *   (c) Per call.  S depends on n, and E on the call's contributions: a gradient accumulated over several calls is reproducible because
+ *       each call is, and equals no single larger call.
+ *   (d) Scale.  With a = 0, multiplying grad_value and grad_gradient by 2^k multiplies every contribution by 2^k exactly (the scale
+ *       symmetry of the entries above, inside its envelope), hence every e'_j and E by +k, every d_j, T_j and I not at all, and the
+ *       result by 2^k exactly while it stays a normal float.
+ *   (e) Exact data.  Where every sum is exact in f32 in every order (no d_j exceeds S, I 2^(E - 150 - S) = X exactly and a + X is a
+ *       float), the result is the float form's.
+ * Workspace.  cgrt_sample_grid_grad_repro_workspace reports the bytes a call on `grid` needs: 12 per grid element, 12 nx ny nz (a 64-bit
+ * accumulator and a 32-bit exponent / kind word each); it applies the grid's limit checks (NULL scene, grid or bytes: CGRT_E_ARG).
+ * The device form takes it as d_workspace / workspace_bytes: device memory of the scene's device, 8-byte aligned, contents need no
+ * initialisation (the launch clears it), owned by the caller, and not to be shared by calls in flight at the same time.
+ * Forms.  cgrt_sample_grid_grad_repro_device only enqueues on `stream` (NULL = default stream) and reads nothing back: a clear of the
+ * workspace, two passes over the points (integer atomic max / or into the word; 64-bit integer atomic add into the accumulator) and one
+ * pass over the grid, which reads and writes the touched elements of d_grad_values alone.  cgrt_sample_grid_grad_repro takes host
+ * pointers, runs on a call lane like cgrt_sample_grid_grad, blocks, and allocates the workspace itself.
+ * Checks.  Those of the float twin, in its order (CGRT_E_ARG); then d_workspace NULL, not 8-byte aligned or workspace_bytes too small
+ * (CGRT_E_ARG; a call with n == 0 skips these); then a host-only scene: CGRT_E_NO_DEVICE; n == 0 succeeds and touches nothing; then
+ * the extents of the device buffers, the workspace included.  No form reads or writes the prediction record, the frame hints, the
+ * layout or any frame state.
+ * Not offered: a form reproducible across a split into several calls; merging the lanes of a wave that share a cell (DESIGN.md section
+ * 9); f16 / bf16 grids; the C++ host mirror. */
+int cgrt_sample_grid_grad_repro_workspace(CgrtScene* scene, const CgrtGrid* grid, uint64_t* bytes);
+int cgrt_sample_grid_grad_repro(CgrtScene* scene, const CgrtGrid* grid, const float* points, uint64_t n, const CgrtFieldParams* params,
+                                const float* grad_value, const float* grad_gradient, float* grad_values);
+int cgrt_sample_grid_grad_repro_device(CgrtScene* scene, const CgrtGrid* grid, const float* d_points, uint64_t n,
+                                       const CgrtFieldParams* params, const float* d_grad_value, const float* d_grad_gradient,
+                                       float* d_grad_values, void* d_workspace, uint64_t workspace_bytes, void* stream);
 
 /* Visibility queries: the reference's second question, "is this point visible?" (DESIGN.md section 5.12).  One byte (or one count) per
  * answer instead of a 16-byte hit; every answer equals the reference's own, whatever the walk (certified or exact) and the kernel shape.

@@ -1,0 +1,287 @@
+// grid_field_grad_repro_check.cpp -- the host side of the bitwise-reproducible form of the sampler's adjoint (include/cgrt.h
+// cgrt_sample_grid_grad_repro*) as a stand-alone program: no GPU, no library, nothing but the two headers the
+// kernels are compiled from (field_cell and field_adjoint of grid_field_device.h; repro_shift, repro_code, repro_join, repro_term and
+// repro_value_* of grad_repro_device.h).  The sum is made SEQUENTIALLY: a first walk over the points joins every contribution's code into
+// its element's word, a second adds the integer terms, a third converts the touched elements -- the three passes of the kernels on one
+// thread.  Two uses:
+//   grid_field_grad_repro_check adjoint GRID POINTS GRAD_VALUE GRAD_GRADIENT OUT FLAGS
+//       GRID: 3 u32 {nx, ny, nz}, 3 f32 origin, 3 f32 spacing, then nx ny nz f32 -- the PREVIOUS content of grad_values; POINTS: records
+//       of 3 f32; GRAD_VALUE: n f32, GRAD_GRADIENT: records of 3 f32, either may be "-" (not given), not both; FLAGS: 0 or 1
+//       (CGRT_FIELD_CLAMP).  OUT: nx ny nz f32, the reproducible result -- what tests/test_grid_field_grad_repro_cpu.py compares with the
+//       numpy restatement, byte for byte
+//   grid_field_grad_repro_check --self-test
+//       the shift at its thresholds; codes, joins and terms of chosen floats; a pile-up into one cell in three orders (one result);
+//       untouched elements keep a -0, a signalling NaN and a sentinel; the non-finite rules; a term far below E truncates to 0 and its
+//       element is still touched; scaling the grads by 2^8 scales the result by 2^8; every element index lies inside the grid.  Meant
+//       to be built with -fsanitize=address,undefined
+// Build: c++ -std=c++17 -O2 -ffp-contract=off -I cg-raytracer_amd/csrc tools/grid_field_grad_repro_check.cpp -o grid_field_grad_repro_check
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "grad_repro_device.h"
+#include "grid_field_device.h"
+
+using namespace cgrt;
+
+struct Grid {
+    GridField G;
+    std::vector<float> values;
+};
+
+static void set_grid(Grid& g, const uint32_t dims[3], const float origin[3], const float spacing[3]) {
+    for (int c = 0; c < 3; c++) g.G.origin[c] = origin[c], g.G.spacing[c] = spacing[c], g.G.top[c] = (float)(dims[c] - 1u);
+    g.G.nx = dims[0], g.G.ny = dims[1], g.G.nz = dims[2];
+    g.values.assign((size_t)dims[0] * dims[1] * dims[2], 0.0f);
+    g.G.values = g.values.data();
+}
+
+static bool read_grid(const char* path, Grid& g) {
+    std::FILE* f = std::fopen(path, "rb");
+    if (!f) return false;
+    uint32_t dims[3];
+    float os[6];
+    bool ok = std::fread(dims, 4, 3, f) == 3 && std::fread(os, 4, 6, f) == 6;
+    for (int c = 0; ok && c < 3; c++) ok = dims[c] >= 2 && dims[c] <= (1u << 24) && os[3 + c] != 0.0f;
+    ok = ok && (uint64_t)dims[0] * dims[1] * dims[2] <= 0x7fffffffull;
+    if (ok) {
+        set_grid(g, dims, os, os + 3);
+        ok = std::fread(g.values.data(), 4, g.values.size(), f) == g.values.size();
+    }
+    std::fclose(f);
+    return ok;
+}
+
+static bool read_floats(const char* path, std::vector<float>& out) {
+    std::FILE* f = std::fopen(path, "rb");
+    if (!f) return false;
+    float rec[256];
+    size_t got;
+    while ((got = std::fread(rec, 4, 256, f)) > 0) out.insert(out.end(), rec, rec + got);
+    std::fclose(f);
+    return true;
+}
+
+// The eight contributions of point i and their elements (checked against `elements`, not trusted).  false: an index left the grid.
+// count: 0 for an outside point, else 8.
+static bool point_contributions(const GridField& G, size_t elements, const float* p, const float* gv, const float* gg, bool clamp,
+                                uint64_t (&at)[8], float (&c)[8], int& count) {
+    int ic[3];
+    float f[3];
+    count = 0;
+    if (!field_cell(G, p[0], p[1], p[2], clamp, ic, f)) return true;
+    const float none[3] = {0.0f, 0.0f, 0.0f};
+    const float g3[3] = {gg ? gg[0] : 0.0f, gg ? gg[1] : 0.0f, gg ? gg[2] : 0.0f};
+    field_adjoint(G.spacing, f, gv != nullptr, gv ? *gv : 0.0f, gg != nullptr, gg ? g3 : none, c);
+    for (int a = 0; a < 3; a++)
+        if (ic[a] < 0 || (uint32_t)ic[a] + 1u >= (a == 0 ? G.nx : a == 1 ? G.ny : G.nz)) return false;
+    const uint64_t base = ((uint64_t)ic[2] * G.ny + (uint64_t)ic[1]) * G.nx + (uint64_t)ic[0];
+    for (int k = 0; k < 8; k++) {
+        at[k] = base + (uint64_t)(k & 1) + (uint64_t)((k >> 1) & 1) * G.nx + (uint64_t)(k >> 2) * G.nx * G.ny;
+        if (at[k] >= elements) return false;
+    }
+    count = 8;
+    return true;
+}
+
+// The reproducible call, sequentially, the points taken in the order `order` gives (null: 0..n-1).  into: the previous content, replaced
+// by the result.  false: an element index left the grid.
+static bool repro_adjoint(const GridField& G, std::vector<float>& into, const float* pts, size_t n, const float* gv, const float* gg,
+                          bool clamp, const size_t* order = nullptr) {
+    const uint32_t S = repro_shift((uint64_t)n);
+    std::vector<uint32_t> word(into.size(), 0u);
+    std::vector<long long> acc(into.size(), 0);
+    for (int pass = 0; pass < 2; pass++)
+        for (size_t j = 0; j < n; j++) {
+            const size_t i = order ? order[j] : j;
+            uint64_t at[8];
+            float c[8];
+            int count;
+            if (!point_contributions(G, into.size(), pts + 3 * i, gv ? gv + i : nullptr, gg ? gg + 3 * i : nullptr, clamp, at, c, count)) return false;
+            for (int k = 0; k < count; k++) {
+                if (!(c[k] != 0.0f)) continue;  // a zero of either sign is not a contribution; a NaN is one
+                if (pass == 0)
+                    word[at[k]] = repro_join(word[at[k]], repro_code(c[k]));
+                else  // (unsigned: the sum wraps like the kernel's 64-bit atomic add; it cannot overflow, |I| < 2^62)
+                    acc[at[k]] = (long long)((unsigned long long)acc[at[k]] + (unsigned long long)repro_term(c[k], word[at[k]], S));
+            }
+        }
+    for (size_t e = 0; e < into.size(); e++)
+        if (word[e]) into[e] = repro_canonical((word[e] & REPRO_KINDS) ? repro_value_kinds(into[e], word[e]) : repro_value_sum(into[e], word[e], acc[e], S));
+    return true;
+}
+
+static float repro_value(float a, uint32_t w, long long I, uint32_t S) {
+    return repro_canonical((w & REPRO_KINDS) ? repro_value_kinds(a, w) : repro_value_sum(a, w, I, S));
+}
+
+static uint32_t bits(float x) {
+    uint32_t u;
+    std::memcpy(&u, &x, 4);
+    return u;
+}
+static float from_bits(uint32_t u) {
+    float x;
+    std::memcpy(&x, &u, 4);
+    return x;
+}
+
+static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
+static uint64_t next_u64() {
+    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
+    return rng_state >> 11;
+}
+static float uniform() { return (float)((double)next_u64() / 4503599627370496.0 - 1.0); }  // [-1, 1)
+
+static int self_test() {
+    int bad = 0;
+    // the shift at its thresholds
+    if (repro_shift(1) != 24 || repro_shift(16383) != 24 || repro_shift(16384) != 23 || repro_shift(0x7fffffffull) != 7) bad++;
+    if (repro_shift(3ull * 0x7fffffffull) != 5) bad++;  // (the surface form's smallest)
+    // codes, joins and terms
+    if (repro_code(1.0f) != 127u || repro_code(from_bits(1u)) != 1u || repro_code(from_bits(0x00800000u)) != 1u) bad++;
+    if (repro_code(INFINITY) != REPRO_POS_INF || repro_code(-INFINITY) != REPRO_NEG_INF || repro_code(NAN) != REPRO_NAN) bad++;
+    if (repro_join(127u, 130u) != 130u || repro_join(REPRO_NAN | 3u, REPRO_POS_INF | 9u) != (REPRO_NAN | REPRO_POS_INF | 9u)) bad++;
+    if (repro_term(1.0f, 127u, 24) != (1ll << 47) || repro_term(-1.0f, 128u, 24) != -(1ll << 46)) bad++;
+    if (repro_term(1.5f, 127u + 30u, 7) != (0xc00000 >> 23) || repro_term(1.5f, 127u + 31u, 7) != 0 || repro_term(1.5f, 127u + 200u - 127u, 7) != 0) bad++;
+    if (repro_term(1.0f, REPRO_NAN | 127u, 24) != 0 || repro_term(INFINITY, 254u, 24) != 0) bad++;
+    if (bits(repro_value(-0.0f, 127u, 0, 24)) != 0u) bad++;  // a touched element: fl32(fl64(-0) + 0) = +0
+    if (bits(repro_value(1.0f, REPRO_POS_INF | REPRO_NEG_INF, 0, 24)) != 0x7fc00000u || repro_value(1.0f, REPRO_NEG_INF, 0, 24) != -INFINITY) bad++;
+    if (bits(repro_value(from_bits(0x7fa00001u), REPRO_POS_INF, 0, 24)) != 0x7fc00000u) bad++;
+    // a pile-up into one cell of 2 x 2 x 2, grads over 40 binades and both signs, in three orders
+    {
+        Grid g;
+        const uint32_t dims[3] = {2, 2, 2};
+        const float origin[3] = {-1.0f, 1.0f, 0.5f}, spacing[3] = {2.0f, -2.0f, 0.25f};
+        const size_t n = 20000;
+        std::vector<float> pts, gv, gg;
+        for (size_t i = 0; i < n; i++) {
+            for (int c = 0; c < 3; c++) pts.push_back(origin[c] + (0.5f + 0.5f * uniform()) * spacing[c]);
+            gv.push_back(std::ldexp(uniform(), (int)(next_u64() % 40u) - 20));
+            for (int c = 0; c < 3; c++) gg.push_back(std::ldexp(uniform(), (int)(next_u64() % 40u) - 20));
+        }
+        std::vector<size_t> rev(n), mixed(n);
+        for (size_t i = 0; i < n; i++) rev[i] = n - 1 - i, mixed[i] = (i * 7919u) % n;  // (7919 is prime and does not divide 20 000)
+        std::vector<float> first;
+        for (int combo = 1; combo < 4; combo++)
+            for (int o = 0; o < 3; o++) {
+                set_grid(g, dims, origin, spacing);
+                for (size_t e = 0; e < g.values.size(); e++) g.values[e] = (float)e - 3.5f;
+                if (!repro_adjoint(g.G, g.values, pts.data(), n, combo & 1 ? gv.data() : nullptr, combo & 2 ? gg.data() : nullptr, false,
+                                   o == 0 ? nullptr : (o == 1 ? rev.data() : mixed.data())))
+                    bad++;
+                if (o == 0)
+                    first = g.values;
+                else if (std::memcmp(first.data(), g.values.data(), 4 * first.size()) != 0)
+                    bad++;
+            }
+        // the grads times 2^8, from a zero grid: the result times 2^8
+        std::vector<float> one, big, gv8(gv), gg8(gg);
+        for (float& v : gv8) v *= 256.0f;
+        for (float& v : gg8) v *= 256.0f;
+        set_grid(g, dims, origin, spacing);
+        if (!repro_adjoint(g.G, g.values, pts.data(), n, gv.data(), gg.data(), false)) bad++;
+        one = g.values;
+        set_grid(g, dims, origin, spacing);
+        if (!repro_adjoint(g.G, g.values, pts.data(), n, gv8.data(), gg8.data(), false)) bad++;
+        for (size_t e = 0; e < one.size(); e++)
+            if (bits(one[e] * 256.0f) != bits(g.values[e])) bad++;
+    }
+    // untouched elements, the non-finite rules, a term far below E
+    {
+        Grid g;
+        const uint32_t dims[3] = {5, 4, 3};
+        const float origin[3] = {0.0f, 0.0f, 0.0f}, spacing[3] = {1.0f, 1.0f, 1.0f};
+        set_grid(g, dims, origin, spacing);
+        const uint32_t keep[3] = {0x80000000u, 0x7fa00001u, 0xa5a5a5a5u};
+        for (size_t e = 0; e < g.values.size(); e++) g.values[e] = from_bits(keep[e % 3]);
+        // grid points with grad_value alone: one element each.  (1,1,1) gets 1 and 2^-60 (truncated to 0 under S = 24: 60 >= 48),
+        // (2,1,1) gets only 2^-60, (0,0,0) a zero grad (no contribution); the NaN grad sits on an outside point
+        const float pts[] = {1, 1, 1, 1, 1, 1, 2, 1, 1, 0, 0, 0, 9, 9, 9};
+        const float gv[] = {1.0f, std::ldexp(1.0f, -60), std::ldexp(1.0f, -60), 0.0f, NAN};
+        std::vector<float> before = g.values;
+        if (!repro_adjoint(g.G, g.values, pts, 5, gv, nullptr, false)) bad++;
+        const size_t e111 = (1 * 4 + 1) * 5 + 1, e211 = e111 + 1;
+        for (size_t e = 0; e < g.values.size(); e++) {
+            if (e == e111 || e == e211) continue;
+            if (bits(g.values[e]) != bits(before[e])) bad++;  // the zero grad and the outside NaN touched nothing
+        }
+        std::vector<float> prev2(before);
+        prev2[e111] = 4.0f, prev2[e211] = -0.0f;
+        g.values = prev2;
+        if (!repro_adjoint(g.G, g.values, pts, 5, gv, nullptr, false)) bad++;
+        if (g.values[e111] != 5.0f) bad++;                               // 4 + (1 + a term that truncated to 0)
+        if (bits(g.values[e211]) != bits(std::ldexp(1.0f, -60))) bad++;  // alone, the small term is exact
+        // the non-finite rules at the centre of a cell (all eight weights 1/8): +inf; +inf and -inf; -inf onto a stored +inf
+        const float mid[] = {3.5f, 2.5f, 1.5f, 3.5f, 2.5f, 1.5f};
+        const float pinf[] = {INFINITY, -INFINITY};
+        const size_t e321 = (1 * 4 + 2) * 5 + 3;
+        g.values = prev2, g.values[e321] = 2.0f;
+        if (!repro_adjoint(g.G, g.values, mid, 1, pinf, nullptr, false) || g.values[e321] != INFINITY) bad++;
+        g.values[e321] = 2.0f;
+        if (!repro_adjoint(g.G, g.values, mid, 2, pinf, nullptr, false) || bits(g.values[e321]) != 0x7fc00000u) bad++;
+        g.values[e321] = INFINITY;
+        if (!repro_adjoint(g.G, g.values, mid, 1, pinf + 1, nullptr, false) || bits(g.values[e321]) != 0x7fc00000u) bad++;
+        // the same small term beside a large one in ONE element: T = 0, and a -0 there still becomes +0 + 1
+        const float pts2[] = {2, 1, 1, 2, 1, 1};
+        const float gv2[] = {std::ldexp(1.0f, -60), 1.0f};
+        g.values = prev2;
+        if (!repro_adjoint(g.G, g.values, pts2, 2, gv2, nullptr, false)) bad++;
+        if (g.values[e211] != 1.0f) bad++;
+    }
+    // every kind of point on small grids: indices stay inside, an outside point adds nothing
+    {
+        const float inf = INFINITY, nan = NAN;
+        const float odd[] = {0.0f, -0.0f, 1.0f, -1.5f, 0.25f, 3.0e38f, -3.0e38f, 1.0e-45f, inf, -inf, nan};
+        const uint32_t shapes[3][3] = {{2, 2, 2}, {3, 2, 2}, {17, 9, 5}};
+        for (int s = 0; s < 3; s++) {
+            Grid g;
+            const float origin[3] = {-1.0f, 0.5f, 2.0f}, spacing[3] = {2.0f / (float)(shapes[s][0] - 1), -0.125f, 0.5f};
+            set_grid(g, shapes[s], origin, spacing);
+            std::vector<float> pts, gv, gg;
+            for (int i = 0; i < 2000; i++)
+                for (int c = 0; c < 3; c++) pts.push_back(origin[c] + (uniform() * 0.6f + 0.5f) * g.G.top[c] * spacing[c]);
+            for (float x : odd)
+                for (float y : odd)
+                    for (float z : odd) pts.push_back(x), pts.push_back(y), pts.push_back(z);
+            const size_t n = pts.size() / 3;
+            for (size_t i = 0; i < n; i++) {
+                gv.push_back(i % 13 == 5 ? odd[(i / 13) % 11] : uniform() * 8.0f);
+                gg.push_back(uniform()), gg.push_back(i % 17 == 3 ? odd[(i / 17) % 11] : uniform()), gg.push_back(uniform());
+            }
+            for (int clamp = 0; clamp < 2; clamp++)
+                for (int combo = 1; combo < 4; combo++)
+                    if (!repro_adjoint(g.G, g.values, pts.data(), n, combo & 1 ? gv.data() : nullptr, combo & 2 ? gg.data() : nullptr, clamp != 0))
+                        bad++;
+        }
+    }
+    std::printf("%d failures\n", bad);
+    return bad ? 1 : 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 2 && std::string(argv[1]) == "--self-test") return self_test();
+    if (argc == 8 && std::string(argv[1]) == "adjoint") {
+        Grid g;
+        std::vector<float> pts, gv, gg;
+        const bool has_gv = std::string(argv[4]) != "-", has_gg = std::string(argv[5]) != "-";
+        if (!has_gv && !has_gg) return 2;
+        if (!read_grid(argv[2], g) || !read_floats(argv[3], pts) || pts.size() % 3) return 2;
+        const size_t n = pts.size() / 3;
+        if (n > 0x7fffffffull) return 2;
+        if (has_gv && (!read_floats(argv[4], gv) || gv.size() != n)) return 2;
+        if (has_gg && (!read_floats(argv[5], gg) || gg.size() != 3 * n)) return 2;
+        const bool clamp = std::strtoul(argv[7], nullptr, 10) == kFieldClamp;
+        if (!repro_adjoint(g.G, g.values, pts.data(), n, has_gv ? gv.data() : nullptr, has_gg ? gg.data() : nullptr, clamp)) return 3;
+        std::FILE* f = std::fopen(argv[6], "wb");
+        if (!f) return 2;
+        const bool ok = std::fwrite(g.values.data(), 4, g.values.size(), f) == g.values.size();
+        return std::fclose(f) == 0 && ok ? 0 : 2;
+    }
+    std::fprintf(stderr, "usage: grid_field_grad_repro_check [--self-test | adjoint GRID POINTS GRAD_VALUE GRAD_GRADIENT OUT FLAGS]\n");
+    return 2;
+}
