@@ -2255,15 +2255,16 @@ class Scene:
             self._device_tensor(grad_attr, "grad_attr", (torch.float32,), (nverts, channels))
         return grad_attr, stream
 
-    def _repro_workspace_tensor(self, reproducible: bool, channels: int, stream):
-        """(workspace, keywords) of a reproducible *_grad_device call: the workspace is a torch.uint8 tensor allocated on the call's
-        stream, which the caller holds until the call has enqueued its passes -- from then on the caching allocator hands the block only
-        to work that the same stream runs later.  (None, {}) for the float form."""
-        if not reproducible:
+    @staticmethod
+    def _repro_workspace_tensor(nbytes, stream):
+        """(workspace, keywords) of a reproducible *_grad_device call that needs `nbytes` (its family's *_grad_repro_workspace): the
+        workspace is a torch.uint8 tensor allocated on the call's stream, which the caller holds until the call has enqueued its passes
+        -- from then on the caching allocator hands the block only to work that the same stream runs later.  nbytes None, the float
+        form: (None, {})."""
+        if nbytes is None:
             return None, {}
         import torch
 
-        nbytes = self.surface_grad_repro_workspace(channels)
         with torch.cuda.stream(stream):
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=stream.device)
         return ws, {"reproducible": True, "d_workspace_ptr": ws.data_ptr(), "workspace_bytes": nbytes}
@@ -2283,7 +2284,7 @@ class Scene:
         ch = grad_out.shape[-1]
         grad_attr, stream = self._grad_attr_tensor(grad_attr, ch, stream)
         if n:
-            ws, kw = self._repro_workspace_tensor(reproducible, ch, stream)
+            ws, kw = self._repro_workspace_tensor(self.surface_grad_repro_workspace(ch) if reproducible else None, stream)
             self.interpolate_hits_grad_device(rays.data_ptr(), hits.data_ptr(), n, grad_out.data_ptr(), ch, grad_attr.data_ptr(),
                                               stream=stream.cuda_stream, **kw)
             del ws  # (held until here: the passes are enqueued)
@@ -3450,19 +3451,6 @@ class Scene:
         _check(lib().cgrt_sample_grid_grad_repro_workspace(self._h, C.byref(g), C.byref(b)))
         return int(b.value)
 
-    def _grid_repro_workspace_tensor(self, reproducible: bool, origin, spacing, dims, stream):
-        """(workspace, keywords) of a reproducible sample_grid_grad_device call, as _repro_workspace_tensor makes them for the surface
-        gradients: a torch.uint8 tensor allocated on the call's stream and held until the call has enqueued its passes.  (None, {}) for
-        the float form."""
-        if not reproducible:
-            return None, {}
-        import torch
-
-        nbytes = self.sample_grid_grad_repro_workspace(origin, spacing, dims)
-        with torch.cuda.stream(stream):
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=stream.device)
-        return ws, {"reproducible": True, "d_workspace_ptr": ws.data_ptr(), "workspace_bytes": nbytes}
-
     def sample_grid_grad(self, origin, spacing, dims, points, grad_value=None, grad_gradient=None, grad_values=None,
                          clamp: bool = False, reproducible: bool = False) -> np.ndarray:
         """cgrt_sample_grid_grad, the adjoint of sample_grid with respect to values: grad_value ((n,) float32) and grad_gradient ((n, 3)
@@ -3532,7 +3520,8 @@ class Scene:
         else:
             self._device_tensor(out, "out", (torch.float32,), (nz, ny, nx))
         if n:  # (an empty tensor has no address to pass: the call would touch nothing anyway)
-            ws, kw = self._grid_repro_workspace_tensor(reproducible, origin, spacing, (nx, ny, nz), stream)
+            ws, kw = self._repro_workspace_tensor(
+                self.sample_grid_grad_repro_workspace(origin, spacing, (nx, ny, nz)) if reproducible else None, stream)
             self.sample_grid_grad_device(origin, spacing, (nx, ny, nz), points.data_ptr(), n,
                                          0 if grad_value is None else grad_value.data_ptr(),
                                          0 if grad_gradient is None else grad_gradient.data_ptr(), out.data_ptr(), clamp=clamp,
@@ -3685,7 +3674,7 @@ class Scene:
             raise ValueError("grad_out must have 1..256 channels")
         self._device_tensor(grad_out, "grad_out", (torch.float32,), lead + ((ch, H, W) if chw else (H, W, ch)))
         grad_attr, stream = self._grad_attr_tensor(grad_attr, ch, stream)
-        ws, kw = self._repro_workspace_tensor(reproducible, ch, stream)
+        ws, kw = self._repro_workspace_tensor(self.surface_grad_repro_workspace(ch) if reproducible else None, stream)
         self.surface_views_grad_device(a, W, H, depth.data_ptr(), prim_id.data_ptr(), grad_out.data_ptr(), ch, grad_attr.data_ptr(), chw=chw,
                                        stream=stream.cuda_stream, raycams=raycams, **kw)
         del ws  # (held until here: the passes are enqueued)

@@ -33,6 +33,7 @@
 #include "cgrt_math.h"
 #include "closest_kernels.h"
 #include "crossing_kernels.h"
+#include "grad_repro_kernels.h"
 #include "grid_field_grad_repro_kernels.h"
 #include "grid_field_kernels.h"
 #include "isosurface_kernels.h"

@@ -327,14 +327,27 @@ struct ReproWorkspace {
     void* d;
     uint64_t bytes;
 };
-// d_workspace NULL, misaligned or too small: the checks that follow the twin's, before the host-only scene
-int surface_repro_args(const CgrtScene* s, uint32_t channels, const ReproWorkspace* ws) {
+// d_workspace NULL (with the family's text for it), misaligned or below `need` bytes (what `entry`, the family's *_workspace entry,
+// returns): the checks that follow the twin's, before the host-only scene
+int repro_workspace_args(const ReproWorkspace* ws, uint64_t need, const char* null_text, const char* entry) {
     if (!ws) return CGRT_OK;
-    if (!ws->d) return fail(CGRT_E_ARG, "NULL argument");
+    if (!ws->d) return fail(CGRT_E_ARG, null_text);
     if ((uintptr_t)ws->d % 8) return fail(CGRT_E_ARG, "d_workspace must be 8-byte aligned");
-    if (ws->bytes < surface_grad_repro_bytes((uint64_t)s->nverts * channels))
-        return fail(CGRT_E_ARG, "workspace_bytes is below cgrt_surface_grad_repro_workspace");
+    if (ws->bytes < need) return fail(CGRT_E_ARG, std::string("workspace_bytes is below ") + entry);
     return CGRT_OK;
+}
+// The device workspace of a call: the caller's `ws`, checked; else slot 4 of `lane` (the host form of a reproducible call); else none
+int repro_workspace_device(const CgrtScene* s, const ReproWorkspace* ws, LaneCall* lane, uint64_t need, void** d) {
+    *d = nullptr;
+    if (ws) {
+        *d = ws->d;
+        return check_device_span(s, ws->d, need, "d_workspace");
+    }
+    if (lane) HIP_TRY(lane->scratch(4, need, d));
+    return CGRT_OK;
+}
+int surface_repro_args(const CgrtScene* s, uint32_t channels, const ReproWorkspace* ws) {
+    return repro_workspace_args(ws, repro_workspace_bytes((uint64_t)s->nverts * channels), "NULL argument", "cgrt_surface_grad_repro_workspace");
 }
 int surface_list_grad_launch(CgrtScene* s, const void* d_rays, const void* d_hits, uint64_t n, const float* d_grad_out, uint32_t channels,
                              float* d_grad_attr, void* d_workspace, hipStream_t st) {
@@ -366,12 +379,7 @@ int surface_list_grad(CgrtScene* s, bool device, const CgrtRay* rays, const Cgrt
     CGRT_TRY(c.inout(3, grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr", &dt));
     CGRT_TRY(c.in(2, grad_out, n * channels * 4ull, "d_grad_out", &dgo));
     void* dws = nullptr;
-    if (ws) {
-        dws = ws->d;
-        CGRT_TRY(check_device_span(s, dws, surface_grad_repro_bytes((uint64_t)s->nverts * channels), "d_workspace"));
-    } else if (repro) {
-        HIP_TRY(c.c.scratch(4, surface_grad_repro_bytes((uint64_t)s->nverts * channels), &dws));
-    }
+    CGRT_TRY(repro_workspace_device(s, ws, repro ? &c.c : nullptr, repro_workspace_bytes((uint64_t)s->nverts * channels), &dws));
     CGRT_TRY(surface_list_grad_launch(s, dr, dh, n, static_cast<const float*>(dgo), channels, static_cast<float*>(dt), dws, c.stream()));
     return c.finish();
 }
@@ -394,7 +402,8 @@ int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtR
     if ((rc = check_device_span(s, d_grad_attr, (uint64_t)s->nverts * channels * 4ull, "d_grad_attr")) != CGRT_OK) return rc;
     if ((rc = check_device_span(s, d_grad_out, npix * channels * 4ull, "d_grad_out")) != CGRT_OK) return rc;
     const uint64_t elements = (uint64_t)s->nverts * channels;
-    if (ws && (rc = check_device_span(s, ws->d, surface_grad_repro_bytes(elements), "d_workspace")) != CGRT_OK) return rc;
+    void* dws = nullptr;
+    if ((rc = repro_workspace_device(s, ws, nullptr, repro_workspace_bytes(elements), &dws)) != CGRT_OK) return rc;
     const SurfaceLookup* lookup = nullptr;
     if ((rc = surface_lookup(s, &lookup)) != CGRT_OK) return rc;
     SurfaceGradDev A = surface_grad_dev(s, lookup, npix, d_grad_out, channels, d_grad_attr, chw);
@@ -406,7 +415,7 @@ int surface_frames_grad_device(CgrtScene* s, const CgrtCamera* cams, const CgrtR
     hipStream_t const st = static_cast<hipStream_t>(stream);
     return launch_with_view_table(s, view_table(cams, raycams, nviews), st, [&](const void* d_table) {
         A.cams = d_table;
-        if (ws) return launch_surface_grad_repro(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, elements, ws->d, st);
+        if (dws) return launch_surface_grad_repro(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, elements, dws, st);
         return launch_surface_grad(A, raycams ? SURFACE_RAYCAM : SURFACE_TRACKBALL, st);
     });
 }
@@ -419,7 +428,7 @@ int cgrt_interpolate_hits_grad(CgrtScene* s, const CgrtRay* rays, const CgrtHit*
 int cgrt_surface_grad_repro_workspace(CgrtScene* s, uint32_t channels, uint64_t* bytes) {
     if (!s || !bytes) return fail(CGRT_E_ARG, "NULL argument");
     if (channels < 1 || channels > 256) return fail(CGRT_E_ARG, "channels must be in 1..256");
-    *bytes = surface_grad_repro_bytes((uint64_t)s->nverts * channels);
+    *bytes = repro_workspace_bytes((uint64_t)s->nverts * channels);
     return CGRT_OK;
 }
 int cgrt_interpolate_hits_grad_repro(CgrtScene* s, const CgrtRay* rays, const CgrtHit* hits, uint64_t n, const float* grad_out,
@@ -1525,11 +1534,8 @@ int field_grad_query(CgrtScene* s, bool device, const CgrtGrid* grid, const floa
     if (n > kFieldMaxPoints) return fail(CGRT_E_ARG, "too many points: n exceeds 0x7fffffff");
     if (device && ((uintptr_t)points % 4 || (uintptr_t)grad_value % 4 || (uintptr_t)grad_gradient % 4 || (uintptr_t)grad_values % 4))
         return fail(CGRT_E_ARG, "d_points, d_grad_value, d_grad_gradient and d_grad_values must be 4-byte aligned");
-    if (n && ws) {  // d_workspace NULL, misaligned or too small: after the twin's checks, before the host-only scene
-        if (!ws->d) return fail(CGRT_E_ARG, "NULL argument: d_workspace");
-        if ((uintptr_t)ws->d % 8) return fail(CGRT_E_ARG, "d_workspace must be 8-byte aligned");
-        if (ws->bytes < field_grad_repro_bytes(N)) return fail(CGRT_E_ARG, "workspace_bytes is below cgrt_sample_grid_grad_repro_workspace");
-    }
+    if (n)
+        CGRT_TRY(repro_workspace_args(ws, repro_workspace_bytes(N), "NULL argument: d_workspace", "cgrt_sample_grid_grad_repro_workspace"));
     NEED_DEVICE(s);
     if (n == 0) return CGRT_OK;
     Q.clamp = params && (params->flags & CGRT_FIELD_CLAMP) ? 1u : 0u;
@@ -1546,12 +1552,7 @@ int field_grad_query(CgrtScene* s, bool device, const CgrtGrid* grid, const floa
     Q.grad_gradient = grad_gradient ? static_cast<const float*>(dgg) : nullptr;
     Q.grad_values = static_cast<float*>(dout);
     void* dws = nullptr;
-    if (ws) {
-        dws = ws->d;
-        CGRT_TRY(check_device_span(s, dws, field_grad_repro_bytes(N), "d_workspace"));
-    } else if (repro) {
-        HIP_TRY(c.c.scratch(4, field_grad_repro_bytes(N), &dws));
-    }
+    CGRT_TRY(repro_workspace_device(s, ws, repro ? &c.c : nullptr, repro_workspace_bytes(N), &dws));
     if (repro)
         HIP_TRY(launch_sample_grid_grad_repro(Q, N, dws, c.stream()));
     else
@@ -1581,7 +1582,7 @@ int cgrt_sample_grid_grad_repro_workspace(CgrtScene* s, const CgrtGrid* grid, ui
     GridField G{};
     uint64_t N = 0;
     CGRT_TRY(field_grid(grid, &G, &N));
-    *bytes = field_grad_repro_bytes(N);
+    *bytes = repro_workspace_bytes(N);
     return CGRT_OK;
 }
 int cgrt_sample_grid_grad_repro(CgrtScene* s, const CgrtGrid* grid, const float* points, uint64_t n, const CgrtFieldParams* params,

@@ -1,6 +1,6 @@
 // grad_repro_device.h -- the element arithmetic of the bitwise-reproducible adjoints (include/cgrt.h cgrt_*_grad_repro*; DESIGN.md sections
 // 5.28 and 5.36): what a contribution brings to its element's word, how two words join, the integer term of a contribution under the
-// element's largest exponent, and the element's new value.  Shared by surface_grad_repro_kernels.hip, grid_field_grad_repro_kernels.hip
+// element's largest exponent, and the element's new value.  Shared by the accumulator (grad_repro_kernels.h, which both forms' kernels use)
 // and the stand-alone checker (tools/grid_field_grad_repro_check.cpp, a C++ compiler that is not hipcc): the pure parts are written
 // __host__ __device__, as grid_field_device.h and sym3_eigen.h are; repro_mark, which is two atomics, exists for hipcc alone.
 // The word of an element: bits 0..7 the largest e' seen (1..254; 0: untouched), bits 8..10 the non-finite kinds seen (+inf, -inf, NaN).

@@ -2,8 +2,9 @@
 // and the march of one ray to a level of it.  f32 throughout, every operation rounded on its own (-ffp-contract=off), only + - x / sqrt,
 // floor and comparisons: the numpy restatement (tests/grid_field_ref.py) gives the same bits.  Written __host__ __device__: both kernels of
 // grid_field_kernels.hip and the stand-alone checker (tools/grid_field_check.cpp, a C++ compiler that is not hipcc) share these bodies.
-// field_cell and field_adjoint are the sampler's adjoint (tests/grid_field_grad_ref.py), shared by
-// k_sample_grid_grad and tools/grid_field_grad_check.cpp in the same way.
+// field_cell is the one cell rule of the sample, the march and the adjoints.  field_grad_item, field_adjoint and field_corners are the
+// sampler's adjoint (DESIGN.md sections 5.35 and 5.36; tests/grid_field_grad_ref.py), shared in the same way by k_sample_grid_grad,
+// k_sample_grid_grad_repro and the two adjoint checkers (tools/grid_field_grad_check.cpp, tools/grid_field_grad_repro_check.cpp).
 // min and max are the header's: a < b ? a : b and a > b ? a : b, so a NaN first operand yields the second.
 #pragma once
 #include <math.h>
@@ -52,10 +53,9 @@ CGRT_HD uint32_t field_bits(const float v) {  // the stored word: every NaN is 0
 }
 CGRT_HD bool field_finite(const float v) { return fabsf(v) <= 3.402823466e+38f; }
 
-// The sample at p.  false: p is outside (the caller stores its `outside` value and a zero gradient).  GRAD false: g is not touched.
-// The eight corner loads are issued together, ahead of the first use; the element offset is 64-bit.
-template <bool GRAD>
-CGRT_HD bool field_sample(const GridField& G, const float px, const float py, const float pz, const bool clamp, float& value, float (&g)[3]) {
+// The cell of p under the sampler's rule: the clamp, the containment test, min(floor, n - 2) and the fraction -- the one definition that
+// the sample, the march and both adjoints share.  false: p is outside and i, f are not written.
+CGRT_HD bool field_cell(const GridField& G, const float px, const float py, const float pz, const bool clamp, int (&i)[3], float (&f)[3]) {
     float u[3] = {(px - G.origin[0]) / G.spacing[0], (py - G.origin[1]) / G.spacing[1], (pz - G.origin[2]) / G.spacing[2]};
     if (clamp) {
 #if defined(__HIPCC__)
@@ -66,10 +66,21 @@ CGRT_HD bool field_sample(const GridField& G, const float px, const float py, co
     if (!(0.0f <= u[0] && u[0] <= G.top[0] && 0.0f <= u[1] && u[1] <= G.top[1] && 0.0f <= u[2] && u[2] <= G.top[2])) return false;
     const int fx = (int)floorf(u[0]), fy = (int)floorf(u[1]), fz = (int)floorf(u[2]);
     const int mx = (int)G.nx - 2, my = (int)G.ny - 2, mz = (int)G.nz - 2;
-    const int ix = fx < mx ? fx : mx, iy = fy < my ? fy : my, iz = fz < mz ? fz : mz;
-    const float tx = u[0] - (float)ix, ty = u[1] - (float)iy, tz = u[2] - (float)iz;
+    i[0] = fx < mx ? fx : mx, i[1] = fy < my ? fy : my, i[2] = fz < mz ? fz : mz;
+    f[0] = u[0] - (float)i[0], f[1] = u[1] - (float)i[1], f[2] = u[2] - (float)i[2];
+    return true;
+}
+
+// The sample at p.  false: p is outside (the caller stores its `outside` value and a zero gradient).  GRAD false: g is not touched.
+// The eight corner loads are issued together, ahead of the first use; the element offset is 64-bit.
+template <bool GRAD>
+CGRT_HD bool field_sample(const GridField& G, const float px, const float py, const float pz, const bool clamp, float& value, float (&g)[3]) {
+    int i[3];
+    float t[3];
+    if (!field_cell(G, px, py, pz, clamp, i, t)) return false;
+    const float tx = t[0], ty = t[1], tz = t[2];
     const uint64_t sy = G.nx, sz = (uint64_t)G.nx * G.ny;
-    const float* q = G.values + (((uint64_t)iz * G.ny + (uint64_t)iy) * G.nx + (uint64_t)ix);
+    const float* q = G.values + (((uint64_t)i[2] * G.ny + (uint64_t)i[1]) * G.nx + (uint64_t)i[0]);
     const float v000 = q[0], v100 = q[1], v010 = q[sy], v110 = q[sy + 1], v001 = q[sz], v101 = q[sz + 1], v011 = q[sz + sy],
                 v111 = q[sz + sy + 1];
     // along x: d_yz and a_yz
@@ -87,24 +98,6 @@ CGRT_HD bool field_sample(const GridField& G, const float px, const float py, co
         g[1] = (e0 + tz * (e1 - e0)) / G.spacing[1];
         g[2] = w / G.spacing[2];
     }
-    return true;
-}
-
-// The cell of p under the sampler's rule, with the sampler's bits (the dozen lines of field_sample above, which keeps its own copy so
-// that its kernels keep their registers).  false: p is outside and i, f are not written.
-CGRT_HD bool field_cell(const GridField& G, const float px, const float py, const float pz, const bool clamp, int (&i)[3], float (&f)[3]) {
-    float u[3] = {(px - G.origin[0]) / G.spacing[0], (py - G.origin[1]) / G.spacing[1], (pz - G.origin[2]) / G.spacing[2]};
-    if (clamp) {
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-        for (int c = 0; c < 3; c++) u[c] = u[c] < 0.0f ? 0.0f : (u[c] > G.top[c] ? G.top[c] : u[c]);
-    }
-    if (!(0.0f <= u[0] && u[0] <= G.top[0] && 0.0f <= u[1] && u[1] <= G.top[1] && 0.0f <= u[2] && u[2] <= G.top[2])) return false;
-    const int fx = (int)floorf(u[0]), fy = (int)floorf(u[1]), fz = (int)floorf(u[2]);
-    const int mx = (int)G.nx - 2, my = (int)G.ny - 2, mz = (int)G.nz - 2;
-    i[0] = fx < mx ? fx : mx, i[1] = fy < my ? fy : my, i[2] = fz < mz ? fz : mz;
-    f[0] = u[0] - (float)i[0], f[1] = u[1] - (float)i[1], f[2] = u[2] - (float)i[2];
     return true;
 }
 
@@ -132,6 +125,49 @@ CGRT_HD void field_adjoint(const float (&spacing)[3], const float (&f)[3], const
         }
         c[k] = s;
     }
+}
+
+// One call of the sampler's adjoint.  grid.values is not read (the sampler is linear in it).  One of grad_value /
+// grad_gradient may be null; grad_values (nx ny nz) is added into.
+struct FieldGradCall {
+    GridField grid;
+    const float* points;  // n x 3
+    uint32_t n;
+    uint32_t clamp;             // CGRT_FIELD_CLAMP
+    const float* grad_value;    // n
+    const float* grad_gradient; // n x 3
+    float* grad_values;
+};
+// Point i of an adjoint call (i < Q.n): its cell, its grads where they were given, its eight contributions c and the element offset `at`
+// of corner 0.  false: the point is outside -- it contributes nothing, no grad is read, at and c are not written.
+CGRT_HD bool field_grad_item(const FieldGradCall& Q, const uint32_t i, uint64_t& at, float (&c)[8]) {
+    const float* p = Q.points + 3ull * i;
+    int ic[3];
+    float f[3];
+    if (!field_cell(Q.grid, p[0], p[1], p[2], Q.clamp != 0u, ic, f)) return false;
+    const bool has_gv = Q.grad_value != nullptr, has_gg = Q.grad_gradient != nullptr;
+    float gv = 0.0f, gg[3] = {0.0f, 0.0f, 0.0f};
+    if (has_gv) gv = Q.grad_value[i];
+    if (has_gg) {
+        const float* g = Q.grad_gradient + 3ull * i;
+        gg[0] = g[0], gg[1] = g[1], gg[2] = g[2];
+    }
+    field_adjoint(Q.grid.spacing, f, has_gv, gv, has_gg, gg, c);
+    at = ((uint64_t)ic[2] * Q.grid.ny + (uint64_t)ic[1]) * Q.grid.nx + (uint64_t)ic[0];
+    return true;
+}
+// fn(k, element offset) for the eight corners of the cell at `at`, k = x + 2 y + 4 z a constant in every call.
+template <class F>
+CGRT_HD void field_corners(const GridField& G, const uint64_t at, F fn) {
+    const uint64_t sy = G.nx, sz = (uint64_t)G.nx * G.ny;
+    fn(0, at);
+    fn(1, at + 1);
+    fn(2, at + sy);
+    fn(3, at + sy + 1);
+    fn(4, at + sz);
+    fn(5, at + sz + 1);
+    fn(6, at + sz + sy);
+    fn(7, at + sz + sy + 1);
 }
 
 // The march of one ray {o, d, t_ray}.  work (COUNT only): {1 if the ray entered the box, main-loop samples, refinement samples} are added.

@@ -29,17 +29,7 @@ struct FieldMarchCall {
     uint32_t n;
     uint32_t* hits;
 };
-// One call of the sampler's adjoint.  grid.values is not read (the sampler is linear in it).  One of grad_value /
-// grad_gradient may be null; grad_values (nx ny nz) is added into.
-struct FieldGradCall {
-    GridField grid;
-    const float* points;  // n x 3
-    uint32_t n;
-    uint32_t clamp;             // CGRT_FIELD_CLAMP
-    const float* grad_value;    // n
-    const float* grad_gradient; // n x 3
-    float* grad_values;
-};
+// (FieldGradCall, one call of the sampler's adjoint, is grid_field_device.h's: field_grad_item reads it.)
 // All enqueue on `stream` and read nothing back.  n == 0: nothing is launched.
 hipError_t launch_sample_grid(const FieldSampleCall& Q, hipStream_t stream);
 hipError_t launch_sample_grid_grad(const FieldGradCall& Q, hipStream_t stream);

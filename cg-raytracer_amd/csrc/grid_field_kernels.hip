@@ -3,8 +3,8 @@
 //   k_sample_grid        one point per lane: the sample, stored to whichever of value / gradient / inside the caller gave
 //   k_march_grid<COUNT>  one ray per lane: the bounded march and its bisection; COUNT adds the lane's three work figures to the
 //                        counters and writes no record
-//   k_sample_grid_grad   one point per lane: the sampler's adjoint -- the forward's cell, eight contributions,
-//                        up to eight no-return float atomic adds into the values' gradient; a zero contribution is not added
+//   k_sample_grid_grad   one point per lane: the sampler's adjoint -- field_grad_item (the forward's cell, eight
+//                        contributions), up to eight no-return float atomic adds into the values' gradient; a zero contribution is not added
 // A sample is eight gathers at one 64-bit element offset, issued together ahead of the first use; a lane's next offset depends on the
 // value it just read, so a march is a chain of dependent round trips and its throughput comes from the waves in flight, not from a lane.
 // Neighbouring rays walk neighbouring cells: the x-adjacent corner pairs share lines.  Plain vector loads and stores only (atomics in the
@@ -40,29 +40,12 @@ __global__ __launch_bounds__(kFieldBlock) void k_sample_grid(const FieldSampleCa
 __global__ __launch_bounds__(kFieldBlock) void k_sample_grid_grad(const FieldGradCall Q) {
     const uint32_t i = blockIdx.x * kFieldBlock + threadIdx.x;
     if (i >= Q.n) return;
-    const float* p = Q.points + 3ull * i;
-    int ic[3];
-    float f[3];
-    if (!field_cell(Q.grid, p[0], p[1], p[2], Q.clamp != 0u, ic, f)) return;
-    const bool has_gv = Q.grad_value != nullptr, has_gg = Q.grad_gradient != nullptr;
-    float gv = 0.0f, gg[3] = {0.0f, 0.0f, 0.0f};
-    if (has_gv) gv = Q.grad_value[i];
-    if (has_gg) {
-        const float* g = Q.grad_gradient + 3ull * i;
-        gg[0] = g[0], gg[1] = g[1], gg[2] = g[2];
-    }
+    uint64_t at;
     float c[8];
-    field_adjoint(Q.grid.spacing, f, has_gv, gv, has_gg, gg, c);
-    const uint64_t sy = Q.grid.nx, sz = (uint64_t)Q.grid.nx * Q.grid.ny;
-    float* q = Q.grad_values + (((uint64_t)ic[2] * Q.grid.ny + (uint64_t)ic[1]) * Q.grid.nx + (uint64_t)ic[0]);
-    if (c[0] != 0.0f) atomicAdd(q, c[0]);
-    if (c[1] != 0.0f) atomicAdd(q + 1, c[1]);
-    if (c[2] != 0.0f) atomicAdd(q + sy, c[2]);
-    if (c[3] != 0.0f) atomicAdd(q + sy + 1, c[3]);
-    if (c[4] != 0.0f) atomicAdd(q + sz, c[4]);
-    if (c[5] != 0.0f) atomicAdd(q + sz + 1, c[5]);
-    if (c[6] != 0.0f) atomicAdd(q + sz + sy, c[6]);
-    if (c[7] != 0.0f) atomicAdd(q + sz + sy + 1, c[7]);
+    if (!field_grad_item(Q, i, at, c)) return;
+    field_corners(Q.grid, at, [&](const int k, const uint64_t e) {
+        if (c[k] != 0.0f) atomicAdd(Q.grad_values + e, c[k]);
+    });
 }
 
 template <bool COUNT>

@@ -4,23 +4,24 @@
 // the sum: per table element the contributions are aligned to the element's largest exponent E, turned into integers T with S guard bits
 // and added in int64 -- integer addition is associative, so the order the hardware picks cannot show in the result.
 //
-// The workspace holds, per table element, a 64-bit accumulator and a 32-bit word: bits 0..7 the largest e' seen (1..254; 0: untouched),
-// bits 8..10 the non-finite kinds seen (+inf, -inf, NaN).  Passes, each a launch on the call's stream:
-//   clear     hipMemsetAsync of the workspace
+// The workspace holds, per table element, a 64-bit accumulator and a 32-bit word (grad_repro_kernels.h): bits 0..7 the largest e' seen
+// (1..254; 0: untouched), bits 8..10 the non-finite kinds seen (+inf, -inf, NaN).  Passes, each a launch on the call's stream:
+//   clear     repro_begin
 //   max       k_surface_grad_repro<SRC, 0>: per contribution one atomicMax(e') into the word (global_atomic_umax), or one atomicOr of its
 //             kind for a non-finite one (global_atomic_or).  A word that carries a kind no longer takes part in the max: its element's
 //             value is decided by the kinds alone.
 //   add       k_surface_grad_repro<SRC, 1>: the same products again, the element's word read, T formed, one
 //             atomicAdd(unsigned long long) into the accumulator (global_atomic_add_x2); zero terms and flagged elements add nothing.
-//   finalise  k_surface_grad_repro_finalise: one lane per table element; a touched one gets fl32(fl64(a) + fl64(I) * 2^(E - 150 - S)),
-//             or a + s for the kinds, stored plainly.
+//   finalise  repro_finish (k_grad_repro_finalise of grad_repro_kernels.hip): one lane per table element; a touched one gets
+//             fl32(fl64(a) + fl64(I) * 2^(E - 150 - S)), or a + s for the kinds, stored plainly.
 // The two mappings are k_surface_grad's: lanes over the wave's contiguous 64 x C run of grad_out (by_item == 0), or each lane the
 // channels of its own item (by_item != 0), there with consecutive lanes of one prim_id combined inside the wave first -- the max pass
 // combines codes, the add pass INTEGER terms, never floats.  256-thread blocks, no LDS, no scratch.  The element arithmetic (repro_code,
-// repro_join, repro_mark, repro_term, repro_value_*) is grad_repro_device.h's, shared with the grid form (grid_field_grad_repro_kernels.hip).
+// repro_join, repro_mark, repro_term) is grad_repro_device.h's and the accumulator (ReproAccum, repro_contribute, the clear and finalise
+// passes) grad_repro_kernels.h's, both shared with the grid form (grid_field_grad_repro_kernels.hip).
 #include <hip/hip_runtime.h>
 
-#include "grad_repro_device.h"
+#include "grad_repro_kernels.h"
 #include "surface_device.h"
 #include "surface_grad_repro_kernels.h"
 
@@ -28,26 +29,8 @@ namespace cgrt {
 
 namespace {
 
-struct SurfaceGradReproDev {
-    SurfaceGradDev g;         // grad_attr is not touched by the max and add passes
-    unsigned long long* acc;  // one per table element
-    uint32_t* word;           // one per table element
-    uint32_t shift;           // S
-};
-
-template <int PASS>
-__device__ __forceinline__ void repro_contribute(const SurfaceGradReproDev& R, const unsigned long long at, const float x) {
-    if (PASS == 0) {
-        repro_mark(R.word + at, repro_code(x));
-    } else {
-        const long long T = repro_term(x, R.word[at], R.shift);
-        if (T) atomicAdd(R.acc + at, (unsigned long long)T);
-    }
-}
-
 template <int SRC, int PASS>
-__global__ __launch_bounds__(256) void k_surface_grad_repro(const SurfaceGradReproDev R) {
-    const SurfaceGradDev& A = R.g;
+__global__ __launch_bounds__(256) void k_surface_grad_repro(const SurfaceGradDev A, const ReproAccum R) {  // (A.grad_attr is not touched)
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
     float wa, wb, wg;
@@ -146,64 +129,36 @@ __global__ __launch_bounds__(256) void k_surface_grad_repro(const SurfaceGradRep
     }
 }
 
-// One lane per table element (a grid-stride loop for tables beyond the grid).  An untouched element is neither read nor written.
-__global__ __launch_bounds__(256) void k_surface_grad_repro_finalise(const unsigned long long* const acc, const uint32_t* const word,
-                                                                     float* const grad_attr, const unsigned long long elements,
-                                                                     const uint32_t S) {
-    const unsigned long long stride = (unsigned long long)gridDim.x * 256ull;
-    for (unsigned long long e = (unsigned long long)blockIdx.x * 256ull + threadIdx.x; e < elements; e += stride) {
-        const uint32_t w = word[e];
-        if (!w) continue;
-        const float a = grad_attr[e];
-        float r;
-        if (w & REPRO_KINDS) {  // (repro_value_kinds, kept as the lines it was moved from: through the call this kernel takes two more VGPRs)
-            const uint32_t k = w & REPRO_KINDS;
-            const float s = k == REPRO_POS_INF ? __uint_as_float(0x7f800000u) : (k == REPRO_NEG_INF ? __uint_as_float(0xff800000u) : __uint_as_float(0x7fc00000u));
-            r = a + s;
-        } else {
-            r = repro_value_sum(a, w, (long long)acc[e], S);
-        }
-        r = repro_canonical(r);
-        grad_attr[e] = r;
-    }
-}
-
 template <int SRC>
-void launch_passes(const SurfaceGradReproDev& R, hipStream_t stream) {
-    const dim3 grid((R.g.n + 255u) / 256u), block(256);
-    hipLaunchKernelGGL((k_surface_grad_repro<SRC, 0>), grid, block, 0, stream, R);
-    hipLaunchKernelGGL((k_surface_grad_repro<SRC, 1>), grid, block, 0, stream, R);
+void launch_passes(const SurfaceGradDev& A, const ReproAccum& R, hipStream_t stream) {
+    const dim3 grid((A.n + 255u) / 256u), block(256);
+    hipLaunchKernelGGL((k_surface_grad_repro<SRC, 0>), grid, block, 0, stream, A, R);
+    hipLaunchKernelGGL((k_surface_grad_repro<SRC, 1>), grid, block, 0, stream, A, R);
 }
 
 }  // namespace
 
 hipError_t launch_surface_grad_repro(const SurfaceGradDev& A, int source, uint64_t elements, void* workspace, hipStream_t stream) {
     if (A.n == 0 || elements == 0) return hipSuccess;
-    SurfaceGradReproDev R;
-    R.g = A;
-    R.acc = static_cast<unsigned long long*>(workspace);
-    R.word = reinterpret_cast<uint32_t*>(R.acc + elements);
-    R.shift = surface_grad_repro_shift(A.n);
-    hipError_t e = hipMemsetAsync(workspace, 0, surface_grad_repro_bytes(elements), stream);
+    // S of the definition: min(24, 38 - bitlength(3 n)), so that 3 n terms below 2^(24 + S) sum in int64.
+    const ReproAccum R = repro_accum(workspace, elements, 3ull * A.n);
+    hipError_t e = repro_begin(workspace, elements, stream);
     if (e != hipSuccess) return e;
     switch (source) {
         case SURFACE_LIST:
-            launch_passes<SURFACE_LIST>(R, stream);
+            launch_passes<SURFACE_LIST>(A, R, stream);
             break;
         case SURFACE_TRACKBALL:
-            launch_passes<SURFACE_TRACKBALL>(R, stream);
+            launch_passes<SURFACE_TRACKBALL>(A, R, stream);
             break;
         case SURFACE_RAYCAM:
-            launch_passes<SURFACE_RAYCAM>(R, stream);
+            launch_passes<SURFACE_RAYCAM>(A, R, stream);
             break;
         default:
             return hipErrorInvalidValue;
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    const unsigned long long blocks = (elements + 255ull) / 256ull;
-    const dim3 grid((uint32_t)(blocks < (1ull << 20) ? blocks : (1ull << 20))), block(256);
-    hipLaunchKernelGGL(k_surface_grad_repro_finalise, grid, block, 0, stream, R.acc, R.word, A.grad_attr, (unsigned long long)elements, R.shift);
-    return hipGetLastError();
+    return repro_finish(R, A.grad_attr, elements, stream);
 }
 
 }  // namespace cgrt

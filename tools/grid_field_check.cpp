@@ -1,5 +1,6 @@
 // grid_field_check.cpp -- the host side of cg-raytracer_amd/csrc/grid_field_device.h (include/cgrt.h "Grid fields") as a stand-alone
-// program: no GPU, no library, nothing but the header the kernels are compiled from.  Three uses:
+// program: no GPU, no library, nothing but the header the kernels are compiled from (grid_field_check_common.h holds what the three
+// grid checkers share).  Three uses:
 //   grid_field_check sample GRID POINTS OUT OUTSIDE FLAGS
 //       GRID: 3 u32 {nx, ny, nz}, 3 f32 origin, 3 f32 spacing, then nx ny nz f32 values; POINTS: records of 3 f32; OUTSIDE: the bits of
 //       CgrtFieldParams.outside as a decimal u32; FLAGS: 0 or 1 (CGRT_FIELD_CLAMP).  OUT: per point 5 words {value, gradient x y z, inside}
@@ -20,46 +21,9 @@
 #include <string>
 #include <vector>
 
-#include "grid_field_device.h"
+#include "grid_field_check_common.h"
 
 using namespace cgrt;
-
-struct Grid {
-    GridField G;
-    std::vector<float> values;
-};
-
-static void set_grid(Grid& g, const uint32_t dims[3], const float origin[3], const float spacing[3]) {
-    for (int c = 0; c < 3; c++) g.G.origin[c] = origin[c], g.G.spacing[c] = spacing[c], g.G.top[c] = (float)(dims[c] - 1u);
-    g.G.nx = dims[0], g.G.ny = dims[1], g.G.nz = dims[2];
-    g.values.resize((size_t)dims[0] * dims[1] * dims[2]);
-    g.G.values = g.values.data();
-}
-
-static bool read_grid(const char* path, Grid& g) {
-    std::FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    uint32_t dims[3];
-    float os[6];
-    bool ok = std::fread(dims, 4, 3, f) == 3 && std::fread(os, 4, 6, f) == 6;
-    for (int c = 0; ok && c < 3; c++) ok = dims[c] >= 2 && dims[c] <= (1u << 24) && os[3 + c] != 0.0f;
-    ok = ok && (uint64_t)dims[0] * dims[1] * dims[2] <= 0x7fffffffull;
-    if (ok) {
-        set_grid(g, dims, os, os + 3);
-        ok = std::fread(g.values.data(), 4, g.values.size(), f) == g.values.size();
-    }
-    std::fclose(f);
-    return ok;
-}
-
-static bool read_floats(const char* path, size_t width, std::vector<float>& out) {
-    std::FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    float rec[8];
-    while (std::fread(rec, 4, width, f) == width) out.insert(out.end(), rec, rec + width);
-    std::fclose(f);
-    return true;
-}
 
 static float from_bits(const char* s) {
     const uint32_t u = (uint32_t)std::strtoul(s, nullptr, 10);
@@ -84,12 +48,6 @@ static void march_ray(const GridField& G, const MarchRules& P, const float* ray,
     for (int c = 0; c < 3; c++) out8[4 + c] = field_bits(R.gradient[c]);
     out8[7] = 0u;
     for (int c = 0; c < 3; c++) work3[c] += w[c];
-}
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static float uniform() {  // [-1, 1)
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    return (float)((double)(rng_state >> 11) / 4503599627370496.0 - 1.0);
 }
 
 static int self_test() {
@@ -162,7 +120,7 @@ int main(int argc, char** argv) {
     Grid g;
     if (mode == "sample" && argc == 7) {
         std::vector<float> pts;
-        if (!read_grid(argv[2], g) || !read_floats(argv[3], 3, pts)) return 2;
+        if (!read_grid(argv[2], g) || !read_floats(argv[3], pts)) return 2;
         const uint32_t outside = (uint32_t)std::strtoul(argv[5], nullptr, 10);
         const bool clamp = std::strtoul(argv[6], nullptr, 10) == kFieldClamp;
         const size_t n = pts.size() / 3;
@@ -172,7 +130,7 @@ int main(int argc, char** argv) {
     }
     if (mode == "march" && argc == 12) {
         std::vector<float> rays;
-        if (!read_grid(argv[2], g) || !read_floats(argv[3], 7, rays)) return 2;
+        if (!read_grid(argv[2], g) || !read_floats(argv[3], rays)) return 2;
         const MarchRules P = {from_bits(argv[5]), from_bits(argv[6]), from_bits(argv[7]), from_bits(argv[8]),
                               (uint32_t)std::strtoul(argv[9], nullptr, 10), (uint32_t)std::strtoul(argv[10], nullptr, 10),
                               (uint32_t)std::strtoul(argv[11], nullptr, 10) & kMarchInsideAbove};

@@ -1,6 +1,6 @@
 // grid_field_grad_check.cpp -- the host side of the sampler's adjoint (include/cgrt.h "Grid fields, the adjoint of the sampler";
-// field_cell and field_adjoint of cg-raytracer_amd/csrc/grid_field_device.h) as a stand-alone program: no GPU, no library, nothing but
-// the header the kernel is compiled from.  Two uses:
+// field_grad_item and field_corners of cg-raytracer_amd/csrc/grid_field_device.h) as a stand-alone program: no GPU, no library, nothing
+// but the header the kernel is compiled from (grid_field_check_common.h holds what the three grid checkers share).  Two uses:
 //   grid_field_grad_check adjoint GRID POINTS GRAD_VALUE GRAD_GRADIENT OUT FLAGS
 //       GRID: 3 u32 {nx, ny, nz}, 3 f32 origin, 3 f32 spacing, then nx ny nz f32 -- the PREVIOUS content of grad_values; POINTS: records
 //       of 3 f32; GRAD_VALUE: n f32, GRAD_GRADIENT: records of 3 f32, either may be "-" (not given), not both; FLAGS: 0 or 1
@@ -20,76 +20,21 @@
 #include <string>
 #include <vector>
 
-#include "grid_field_device.h"
+#include "grid_field_check_common.h"
 
 using namespace cgrt;
 
-struct Grid {
-    GridField G;
-    std::vector<float> values;
-};
-
-static void set_grid(Grid& g, const uint32_t dims[3], const float origin[3], const float spacing[3]) {
-    for (int c = 0; c < 3; c++) g.G.origin[c] = origin[c], g.G.spacing[c] = spacing[c], g.G.top[c] = (float)(dims[c] - 1u);
-    g.G.nx = dims[0], g.G.ny = dims[1], g.G.nz = dims[2];
-    g.values.assign((size_t)dims[0] * dims[1] * dims[2], 0.0f);
-    g.G.values = g.values.data();
-}
-
-static bool read_grid(const char* path, Grid& g) {
-    std::FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    uint32_t dims[3];
-    float os[6];
-    bool ok = std::fread(dims, 4, 3, f) == 3 && std::fread(os, 4, 6, f) == 6;
-    for (int c = 0; ok && c < 3; c++) ok = dims[c] >= 2 && dims[c] <= (1u << 24) && os[3 + c] != 0.0f;
-    ok = ok && (uint64_t)dims[0] * dims[1] * dims[2] <= 0x7fffffffull;
-    if (ok) {
-        set_grid(g, dims, os, os + 3);
-        ok = std::fread(g.values.data(), 4, g.values.size(), f) == g.values.size();
-    }
-    std::fclose(f);
-    return ok;
-}
-
-static bool read_floats(const char* path, std::vector<float>& out) {
-    std::FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    float rec[256];
-    size_t got;
-    while ((got = std::fread(rec, 4, 256, f)) > 0) out.insert(out.end(), rec, rec + got);
-    std::fclose(f);
-    return true;
-}
-
-// One point: its non-zero contributions are added to `into` (the grid's element count is checked, not trusted).  Returns the number of
-// additions, or -1 if an element index left the grid.
-static int add_point(const GridField& G, std::vector<float>& into, const float* p, const float* gv, const float* gg, bool clamp,
-                     float (*seen)[8] = nullptr) {
-    int ic[3];
-    float f[3];
-    if (!field_cell(G, p[0], p[1], p[2], clamp, ic, f)) return 0;
-    const float none[3] = {0.0f, 0.0f, 0.0f};
-    const float g3[3] = {gg ? gg[0] : 0.0f, gg ? gg[1] : 0.0f, gg ? gg[2] : 0.0f};
+// Point i of the call Q: its non-zero contributions are added to `into`.  Returns the number of additions, or -1 if an element index
+// left the grid.
+static int add_point(const FieldGradCall& Q, uint32_t i, std::vector<float>& into, float (*seen)[8] = nullptr) {
+    uint64_t at[8];
     float c[8];
-    field_adjoint(G.spacing, f, gv != nullptr, gv ? *gv : 0.0f, gg != nullptr, gg ? g3 : none, c);
-    if (seen) std::memcpy(*seen, c, sizeof c);
-    for (int a = 0; a < 3; a++)
-        if (ic[a] < 0 || (uint32_t)ic[a] + 1u >= (a == 0 ? G.nx : a == 1 ? G.ny : G.nz)) return -1;
-    const uint64_t base = ((uint64_t)ic[2] * G.ny + (uint64_t)ic[1]) * G.nx + (uint64_t)ic[0];
-    int added = 0;
-    for (int k = 0; k < 8; k++) {
-        const uint64_t at = base + (uint64_t)(k & 1) + (uint64_t)((k >> 1) & 1) * G.nx + (uint64_t)(k >> 2) * G.nx * G.ny;
-        if (at >= into.size()) return -1;
-        if (c[k] != 0.0f) into[at] += c[k], added++;
-    }
+    int count, added = 0;
+    if (!grad_point(Q, i, into.size(), at, c, count)) return -1;
+    if (seen && count) std::memcpy(*seen, c, sizeof c);
+    for (int k = 0; k < count; k++)
+        if (c[k] != 0.0f) into[at[k]] += c[k], added++;
     return added;
-}
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static float uniform() {  // [-1, 1)
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    return (float)((double)(rng_state >> 11) / 4503599627370496.0 - 1.0);
 }
 
 static int self_test() {
@@ -122,7 +67,7 @@ static int self_test() {
                     int ic[3];
                     float f[3];
                     const bool in = field_cell(g.G, p[0], p[1], p[2], clamp != 0, ic, f);
-                    const int a = add_point(g.G, g.values, p, combo & 1 ? &gv : nullptr, combo & 2 ? gg : nullptr, clamp != 0, &c1);
+                    const int a = add_point(grad_call(g, p, 1, combo & 1 ? &gv : nullptr, combo & 2 ? gg : nullptr, clamp != 0), 0, g.values, &c1);
                     points++;
                     if (a < 0 || a > 8 || (!in && a != 0)) bad++;
                     if (a > 0) adds += (size_t)a;
@@ -132,7 +77,7 @@ static int self_test() {
                     if (!in || i >= first_odd || i % 13 == 5 || i % 17 == 3) continue;  // ordinary points and grads: inside the envelope
                     gv *= 4.0f, gg[0] *= 4.0f, gg[1] *= 4.0f, gg[2] *= 4.0f;
                     std::vector<float> scratch(g.values.size(), 0.0f);
-                    if (add_point(g.G, scratch, p, combo & 1 ? &gv : nullptr, combo & 2 ? gg : nullptr, clamp != 0, &c4) < 0) bad++;
+                    if (add_point(grad_call(g, p, 1, combo & 1 ? &gv : nullptr, combo & 2 ? gg : nullptr, clamp != 0), 0, scratch, &c4) < 0) bad++;
                     for (int k = 0; k < 8; k++) {
                         const float want = 4.0f * c1[k];
                         const bool normal = std::fabs(c1[k]) > 1.0e-30f && std::fabs(c1[k]) < 1.0e30f;  // (well inside the envelope)
@@ -156,12 +101,10 @@ int main(int argc, char** argv) {
         if (has_gv && (!read_floats(argv[4], gv) || gv.size() != n)) return 2;
         if (has_gg && (!read_floats(argv[5], gg) || gg.size() != 3 * n)) return 2;
         const bool clamp = std::strtoul(argv[7], nullptr, 10) == kFieldClamp;
+        const FieldGradCall Q = grad_call(g, pts.data(), n, has_gv ? gv.data() : nullptr, has_gg ? gg.data() : nullptr, clamp);
         for (size_t i = 0; i < n; i++)
-            if (add_point(g.G, g.values, &pts[3 * i], has_gv ? &gv[i] : nullptr, has_gg ? &gg[3 * i] : nullptr, clamp) < 0) return 3;
-        std::FILE* f = std::fopen(argv[6], "wb");
-        if (!f) return 2;
-        const bool ok = std::fwrite(g.values.data(), 4, g.values.size(), f) == g.values.size();
-        return std::fclose(f) == 0 && ok ? 0 : 2;
+            if (add_point(Q, (uint32_t)i, g.values) < 0) return 3;
+        return write_floats(argv[6], g.values) ? 0 : 2;
     }
     std::fprintf(stderr, "usage: grid_field_grad_check [--self-test | adjoint GRID POINTS GRAD_VALUE GRAD_GRADIENT OUT FLAGS]\n");
     return 2;

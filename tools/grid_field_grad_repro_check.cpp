@@ -1,6 +1,6 @@
 // grid_field_grad_repro_check.cpp -- the host side of the bitwise-reproducible form of the sampler's adjoint (include/cgrt.h
 // cgrt_sample_grid_grad_repro*) as a stand-alone program: no GPU, no library, nothing but the two headers the
-// kernels are compiled from (field_cell and field_adjoint of grid_field_device.h; repro_shift, repro_code, repro_join, repro_term and
+// kernels are compiled from (field_grad_item and field_corners of grid_field_device.h; repro_shift, repro_code, repro_join, repro_term and
 // repro_value_* of grad_repro_device.h).  The sum is made SEQUENTIALLY: a first walk over the points joins every contribution's code into
 // its element's word, a second adds the integer terms, a third converts the touched elements -- the three passes of the kernels on one
 // thread.  Two uses:
@@ -24,74 +24,15 @@
 #include <vector>
 
 #include "grad_repro_device.h"
-#include "grid_field_device.h"
+#include "grid_field_check_common.h"
 
 using namespace cgrt;
 
-struct Grid {
-    GridField G;
-    std::vector<float> values;
-};
-
-static void set_grid(Grid& g, const uint32_t dims[3], const float origin[3], const float spacing[3]) {
-    for (int c = 0; c < 3; c++) g.G.origin[c] = origin[c], g.G.spacing[c] = spacing[c], g.G.top[c] = (float)(dims[c] - 1u);
-    g.G.nx = dims[0], g.G.ny = dims[1], g.G.nz = dims[2];
-    g.values.assign((size_t)dims[0] * dims[1] * dims[2], 0.0f);
-    g.G.values = g.values.data();
-}
-
-static bool read_grid(const char* path, Grid& g) {
-    std::FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    uint32_t dims[3];
-    float os[6];
-    bool ok = std::fread(dims, 4, 3, f) == 3 && std::fread(os, 4, 6, f) == 6;
-    for (int c = 0; ok && c < 3; c++) ok = dims[c] >= 2 && dims[c] <= (1u << 24) && os[3 + c] != 0.0f;
-    ok = ok && (uint64_t)dims[0] * dims[1] * dims[2] <= 0x7fffffffull;
-    if (ok) {
-        set_grid(g, dims, os, os + 3);
-        ok = std::fread(g.values.data(), 4, g.values.size(), f) == g.values.size();
-    }
-    std::fclose(f);
-    return ok;
-}
-
-static bool read_floats(const char* path, std::vector<float>& out) {
-    std::FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    float rec[256];
-    size_t got;
-    while ((got = std::fread(rec, 4, 256, f)) > 0) out.insert(out.end(), rec, rec + got);
-    std::fclose(f);
-    return true;
-}
-
-// The eight contributions of point i and their elements (checked against `elements`, not trusted).  false: an index left the grid.
-// count: 0 for an outside point, else 8.
-static bool point_contributions(const GridField& G, size_t elements, const float* p, const float* gv, const float* gg, bool clamp,
-                                uint64_t (&at)[8], float (&c)[8], int& count) {
-    int ic[3];
-    float f[3];
-    count = 0;
-    if (!field_cell(G, p[0], p[1], p[2], clamp, ic, f)) return true;
-    const float none[3] = {0.0f, 0.0f, 0.0f};
-    const float g3[3] = {gg ? gg[0] : 0.0f, gg ? gg[1] : 0.0f, gg ? gg[2] : 0.0f};
-    field_adjoint(G.spacing, f, gv != nullptr, gv ? *gv : 0.0f, gg != nullptr, gg ? g3 : none, c);
-    for (int a = 0; a < 3; a++)
-        if (ic[a] < 0 || (uint32_t)ic[a] + 1u >= (a == 0 ? G.nx : a == 1 ? G.ny : G.nz)) return false;
-    const uint64_t base = ((uint64_t)ic[2] * G.ny + (uint64_t)ic[1]) * G.nx + (uint64_t)ic[0];
-    for (int k = 0; k < 8; k++) {
-        at[k] = base + (uint64_t)(k & 1) + (uint64_t)((k >> 1) & 1) * G.nx + (uint64_t)(k >> 2) * G.nx * G.ny;
-        if (at[k] >= elements) return false;
-    }
-    count = 8;
-    return true;
-}
-
 // The reproducible call, sequentially, the points taken in the order `order` gives (null: 0..n-1).  into: the previous content, replaced
 // by the result.  false: an element index left the grid.
-static bool repro_adjoint(const GridField& G, std::vector<float>& into, const float* pts, size_t n, const float* gv, const float* gg,
+static bool repro_adjoint(const Grid& g, std::vector<float>& into, const float* pts, size_t n, const float* gv, const float* gg,
                           bool clamp, const size_t* order = nullptr) {
+    const FieldGradCall Q = grad_call(g, pts, n, gv, gg, clamp);
     const uint32_t S = repro_shift((uint64_t)n);
     std::vector<uint32_t> word(into.size(), 0u);
     std::vector<long long> acc(into.size(), 0);
@@ -101,7 +42,7 @@ static bool repro_adjoint(const GridField& G, std::vector<float>& into, const fl
             uint64_t at[8];
             float c[8];
             int count;
-            if (!point_contributions(G, into.size(), pts + 3 * i, gv ? gv + i : nullptr, gg ? gg + 3 * i : nullptr, clamp, at, c, count)) return false;
+            if (!grad_point(Q, (uint32_t)i, into.size(), at, c, count)) return false;
             for (int k = 0; k < count; k++) {
                 if (!(c[k] != 0.0f)) continue;  // a zero of either sign is not a contribution; a NaN is one
                 if (pass == 0)
@@ -129,13 +70,6 @@ static float from_bits(uint32_t u) {
     std::memcpy(&x, &u, 4);
     return x;
 }
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint64_t next_u64() {
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    return rng_state >> 11;
-}
-static float uniform() { return (float)((double)next_u64() / 4503599627370496.0 - 1.0); }  // [-1, 1)
 
 static int self_test() {
     int bad = 0;
@@ -171,7 +105,7 @@ static int self_test() {
             for (int o = 0; o < 3; o++) {
                 set_grid(g, dims, origin, spacing);
                 for (size_t e = 0; e < g.values.size(); e++) g.values[e] = (float)e - 3.5f;
-                if (!repro_adjoint(g.G, g.values, pts.data(), n, combo & 1 ? gv.data() : nullptr, combo & 2 ? gg.data() : nullptr, false,
+                if (!repro_adjoint(g, g.values, pts.data(), n, combo & 1 ? gv.data() : nullptr, combo & 2 ? gg.data() : nullptr, false,
                                    o == 0 ? nullptr : (o == 1 ? rev.data() : mixed.data())))
                     bad++;
                 if (o == 0)
@@ -184,10 +118,10 @@ static int self_test() {
         for (float& v : gv8) v *= 256.0f;
         for (float& v : gg8) v *= 256.0f;
         set_grid(g, dims, origin, spacing);
-        if (!repro_adjoint(g.G, g.values, pts.data(), n, gv.data(), gg.data(), false)) bad++;
+        if (!repro_adjoint(g, g.values, pts.data(), n, gv.data(), gg.data(), false)) bad++;
         one = g.values;
         set_grid(g, dims, origin, spacing);
-        if (!repro_adjoint(g.G, g.values, pts.data(), n, gv8.data(), gg8.data(), false)) bad++;
+        if (!repro_adjoint(g, g.values, pts.data(), n, gv8.data(), gg8.data(), false)) bad++;
         for (size_t e = 0; e < one.size(); e++)
             if (bits(one[e] * 256.0f) != bits(g.values[e])) bad++;
     }
@@ -204,7 +138,7 @@ static int self_test() {
         const float pts[] = {1, 1, 1, 1, 1, 1, 2, 1, 1, 0, 0, 0, 9, 9, 9};
         const float gv[] = {1.0f, std::ldexp(1.0f, -60), std::ldexp(1.0f, -60), 0.0f, NAN};
         std::vector<float> before = g.values;
-        if (!repro_adjoint(g.G, g.values, pts, 5, gv, nullptr, false)) bad++;
+        if (!repro_adjoint(g, g.values, pts, 5, gv, nullptr, false)) bad++;
         const size_t e111 = (1 * 4 + 1) * 5 + 1, e211 = e111 + 1;
         for (size_t e = 0; e < g.values.size(); e++) {
             if (e == e111 || e == e211) continue;
@@ -213,7 +147,7 @@ static int self_test() {
         std::vector<float> prev2(before);
         prev2[e111] = 4.0f, prev2[e211] = -0.0f;
         g.values = prev2;
-        if (!repro_adjoint(g.G, g.values, pts, 5, gv, nullptr, false)) bad++;
+        if (!repro_adjoint(g, g.values, pts, 5, gv, nullptr, false)) bad++;
         if (g.values[e111] != 5.0f) bad++;                               // 4 + (1 + a term that truncated to 0)
         if (bits(g.values[e211]) != bits(std::ldexp(1.0f, -60))) bad++;  // alone, the small term is exact
         // the non-finite rules at the centre of a cell (all eight weights 1/8): +inf; +inf and -inf; -inf onto a stored +inf
@@ -221,16 +155,16 @@ static int self_test() {
         const float pinf[] = {INFINITY, -INFINITY};
         const size_t e321 = (1 * 4 + 2) * 5 + 3;
         g.values = prev2, g.values[e321] = 2.0f;
-        if (!repro_adjoint(g.G, g.values, mid, 1, pinf, nullptr, false) || g.values[e321] != INFINITY) bad++;
+        if (!repro_adjoint(g, g.values, mid, 1, pinf, nullptr, false) || g.values[e321] != INFINITY) bad++;
         g.values[e321] = 2.0f;
-        if (!repro_adjoint(g.G, g.values, mid, 2, pinf, nullptr, false) || bits(g.values[e321]) != 0x7fc00000u) bad++;
+        if (!repro_adjoint(g, g.values, mid, 2, pinf, nullptr, false) || bits(g.values[e321]) != 0x7fc00000u) bad++;
         g.values[e321] = INFINITY;
-        if (!repro_adjoint(g.G, g.values, mid, 1, pinf + 1, nullptr, false) || bits(g.values[e321]) != 0x7fc00000u) bad++;
+        if (!repro_adjoint(g, g.values, mid, 1, pinf + 1, nullptr, false) || bits(g.values[e321]) != 0x7fc00000u) bad++;
         // the same small term beside a large one in ONE element: T = 0, and a -0 there still becomes +0 + 1
         const float pts2[] = {2, 1, 1, 2, 1, 1};
         const float gv2[] = {std::ldexp(1.0f, -60), 1.0f};
         g.values = prev2;
-        if (!repro_adjoint(g.G, g.values, pts2, 2, gv2, nullptr, false)) bad++;
+        if (!repro_adjoint(g, g.values, pts2, 2, gv2, nullptr, false)) bad++;
         if (g.values[e211] != 1.0f) bad++;
     }
     // every kind of point on small grids: indices stay inside, an outside point adds nothing
@@ -255,7 +189,7 @@ static int self_test() {
             }
             for (int clamp = 0; clamp < 2; clamp++)
                 for (int combo = 1; combo < 4; combo++)
-                    if (!repro_adjoint(g.G, g.values, pts.data(), n, combo & 1 ? gv.data() : nullptr, combo & 2 ? gg.data() : nullptr, clamp != 0))
+                    if (!repro_adjoint(g, g.values, pts.data(), n, combo & 1 ? gv.data() : nullptr, combo & 2 ? gg.data() : nullptr, clamp != 0))
                         bad++;
         }
     }
@@ -276,11 +210,8 @@ int main(int argc, char** argv) {
         if (has_gv && (!read_floats(argv[4], gv) || gv.size() != n)) return 2;
         if (has_gg && (!read_floats(argv[5], gg) || gg.size() != 3 * n)) return 2;
         const bool clamp = std::strtoul(argv[7], nullptr, 10) == kFieldClamp;
-        if (!repro_adjoint(g.G, g.values, pts.data(), n, has_gv ? gv.data() : nullptr, has_gg ? gg.data() : nullptr, clamp)) return 3;
-        std::FILE* f = std::fopen(argv[6], "wb");
-        if (!f) return 2;
-        const bool ok = std::fwrite(g.values.data(), 4, g.values.size(), f) == g.values.size();
-        return std::fclose(f) == 0 && ok ? 0 : 2;
+        if (!repro_adjoint(g, g.values, pts.data(), n, has_gv ? gv.data() : nullptr, has_gg ? gg.data() : nullptr, clamp)) return 3;
+        return write_floats(argv[6], g.values) ? 0 : 2;
     }
     std::fprintf(stderr, "usage: grid_field_grad_repro_check [--self-test | adjoint GRID POINTS GRAD_VALUE GRAD_GRADIENT OUT FLAGS]\n");
     return 2;
